@@ -21,7 +21,16 @@ to (device ordinal, PCI bus id).
 Timing protocol: `prewarm_s` seconds of real, untimed training steps first (a freshly leased GPU
 needs that long to reach its sustained clocks; reported in the line), then W untimed warm-up
 steps, then EXACTLY K timed steps between barrier+synchronize pairs.  Nothing is skipped in the
-timed region.  Prints ONE JSON line on rank 0.
+timed region.  Prints ONE JSON line on rank 0.  With one process the clock-driven part of the
+pre-warm runs on a handle of its own and the timed handle gets a fixed 200 steps of it: what the
+timed handle holds after its last step depends on the arguments alone.
+
+A plain run does only what the headline needs.  --full adds everything else, as one line: the
+sustained rate, the in-step roofline and measured peaks, this run's own rocprofv3 passes, the other
+configurations (c5_bf16, c1_end_to_end, c3_nat, c2_window_chunk, dp_world1) and the CPU baseline
+(--no-extras / --no-cpu-baseline leave parts of that out again).  --dump-outputs DIR writes, after
+the timed steps, what the last timed step left for a caller of the step (the trained weights and
+biases, float32 .npy), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -43,6 +52,7 @@ PEAK_MFMA_F32_TF = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense pe
 PEAK_HBM_GBS = 8000.0     # spec
 C5_LAYERS = [257 * 11, 4096, 4096, 4096, 4096, 4096, 257]   # BASELINE.json configs[4], per-GPU shard of 512 frames
 C5_BUNCH = 512
+PREWARM_FIXED_STEPS = 200  # one process: the pre-warm's last steps, on the timed handle (a fixed count: --dump-outputs)
 
 
 def n_params(ls):
@@ -374,9 +384,15 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--prewarm-s", type=float, default=1.5, help="seconds of real untimed training steps before the warm-up")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C5 line, the measured peaks and the live counter passes")
-    ap.add_argument("--sustained-s", type=float, default=4.0, help="seconds of the additional sustained-rate measurement (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: sustained rate, in-step roofline, measured peaks, this run's own "
+                         "rocprofv3 passes, the other configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the weights and biases the last timed step left as DIR/W<l>.npy, DIR/b<l>.npy "
+                         "(float32; one process only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the C5 line, the measured peaks and the live counter passes")
+    ap.add_argument("--sustained-s", type=float, default=4.0, help="with --full: seconds of the additional sustained-rate measurement (0 = skip)")
     ap.add_argument("--chunk", type=int, default=CHUNK)
     ap.add_argument("--exchange", choices=["all", "both", "native", "native_push", "native_push_bf16", "rccl"], default="all",
                     help="transport of the data-parallel exchange (N > 1): the library's peer kernels, RCCL reduce-scatter/all-gather, or "
@@ -593,6 +609,9 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dp or os.environ.get("BENCH_FORCE_DP") == "1"):
+        # a group's handle is attached and timed once per transport: its last step is not one fixed computation
+        sys.exit("bench.py: --dump-outputs needs one process without the exchange path (--gpus 1, no --force-dp)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)                              # no launcher around us: become one
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -675,9 +694,14 @@ def main():
     kw = dict(dropoutflag=1, visible_omit=0.1, hid_omit=0.2, seed=20260927, device=dev, max_chunk_frames=chunk)
     if dp:
         kw.update(global_bunchsize=BUNCH * world, rank_frame_offset=rank * BUNCH)
-    g = dnnse_amd.BP_GPU(world, len(LAYERS), LAYERS, BUNCH, 1.0, 0.5, 0.0, W, b, **kw)
-    g.fill_chunk_synthetic(chunk, 20260927 + rank)            # each rank holds its own shard of every bunch
-    g.sync()
+
+    def new_handle():
+        h = dnnse_amd.BP_GPU(world, len(LAYERS), LAYERS, BUNCH, 1.0, 0.5, 0.0, W, b, **kw)
+        h.fill_chunk_synthetic(chunk, 20260927 + rank)        # each rank holds its own shard of every bunch
+        h.sync()
+        return h
+
+    g = new_handle()
     nb_chunk = chunk // BUNCH
     state = {"pos": 0, "attached": False}
 
@@ -699,8 +723,8 @@ def main():
             pos = (pos + k) % nb_chunk
         state["pos"] = pos
 
-    def timed(tr=None):
-        """untimed pre-warm (real steps, the same count on every rank), W warm-up steps, EXACTLY K timed steps between barriers"""
+    def prewarm():
+        """untimed pre-warm on g: real steps for --prewarm-s seconds, the same count on every rank -> (seconds, steps)"""
         t0, prewarm_steps = time.perf_counter(), 0
         if args.prewarm_s > 0:
             run(200); g.sync(); prewarm_steps = 200
@@ -708,7 +732,34 @@ def main():
             extra = int(max_over_ranks(float(int(max(0.0, args.prewarm_s - (time.perf_counter() - t0)) / per))))
             if extra > 0:
                 run(extra); g.sync(); prewarm_steps += extra
-        prewarm_s = time.perf_counter() - t0
+        return time.perf_counter() - t0, prewarm_steps
+
+    warmed = None
+    if not dp and args.prewarm_s > 0:
+        # The pre-warm's step count follows the clock, so it runs on a handle of its own; the timed handle g, made before it so
+        # that the GPU does not idle in between, gets a fixed PREWARM_FIXED_STEPS instead (after an idle pause the step needs
+        # ~75 steps to come back to speed).  The last timed step is then the same computation in every run with these
+        # arguments (--dump-outputs), whatever the clock did.
+        timed_g, g = g, new_handle()
+        prewarm_s, prewarm_steps = prewarm()
+        g.close()
+        g, state["pos"] = timed_g, 0
+        t0 = time.perf_counter()
+        run(PREWARM_FIXED_STEPS); g.sync()
+        warmed = (prewarm_s + time.perf_counter() - t0, prewarm_steps + PREWARM_FIXED_STEPS)
+
+    def dump_outputs(d):
+        """--dump-outputs: what a caller of the timed step receives after its last step -- the trained weights W<l> [in][out]
+        and biases b<l>, l = 1..L-1 (returnWeights), float32: 14.7 M values, 59 MB for C2"""
+        os.makedirs(d, exist_ok=True)
+        ws, bs = g.get_weights()
+        for l in range(1, len(LAYERS)):
+            np.save(os.path.join(d, "W%d.npy" % l), ws[l])
+            np.save(os.path.join(d, "b%d.npy" % l), bs[l])
+
+    def timed(tr=None):
+        """untimed pre-warm (real steps, the same count on every rank), W warm-up steps, EXACTLY K timed steps between barriers"""
+        prewarm_s, prewarm_steps = warmed if warmed is not None else prewarm()
         run(args.warmup)
         barrier()
         t0 = time.perf_counter()
@@ -717,6 +768,8 @@ def main():
         dt = max_over_ranks(time.perf_counter() - t0)
         r = {"ms_per_step": 1e3 * dt / args.steps, "value": args.steps * BUNCH * world / dt, "unit": "frames/s", "steps": args.steps,
              "prewarm_s": prewarm_s, "prewarm_steps": prewarm_steps, "dt": dt}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs)
         if tr is not None:
             # what each rank attached to, as the library saw it: a reader can check N ranks on N devices
             table = []
@@ -729,7 +782,7 @@ def main():
             assert dp_world == world and dp_rank == rank
         # ---- sustained rate (an extra field, not `value`): the same steps for --sustained-s seconds, so that clocks, power and
         # temperature are at their steady state -- and so that whoever samples the GPU's busy counter during this run sees it
-        if args.sustained_s > 0 and not args.no_extras:
+        if args.full and args.sustained_s > 0 and not args.no_extras:
             n_sus = int(max_over_ranks(float(max(1, int(args.sustained_s / (dt / args.steps))))))      # same count on every rank
             barrier()
             t1 = time.perf_counter()
@@ -797,7 +850,7 @@ def main():
     else:
         res = make_line(None, None, head=timed(None))
     value = res["value"]
-    if rank == 0 and not dp:
+    if rank == 0 and not dp and args.full:
         # ---- roofline of the TIME-DOMINANT kernel: the grouped wgrad + fused momentum update of all layers
         # (bp_wgrad_dma<16,4,4,256>, LDS-DMA staged, one grouped launch per step, ~35 % of the step).  achieved = algorithmic FLOPs per launch (2*B*P: every layer's G = y^T.dEdX) / its average duration
         # INSIDE the step, measured live with HIP events on the launch stream (bp_profile_step: an event after every
@@ -880,7 +933,7 @@ def main():
                                                 "frac_of_measured_mfma": res["roofline"]["achieved"] / mf if mf > 0 else None,
                                                 "note": "bare v_mfma_f32_32x32x2_f32 loop and 1 GiB float4 copy, this device, this process"}
     g.close()
-    if rank == 0 and not dp and not args.no_extras:
+    if rank == 0 and not dp and args.full and not args.no_extras:
         # ---- THIS run's own counter passes (the handle is closed: the child processes have the GPU to themselves)
         try:
             lc = live_counters()
@@ -933,7 +986,7 @@ def main():
         if isinstance(res.get("dp_world1"), dict) and "ms_per_step" in res["dp_world1"]:
             res["dp_world1"]["vs_fused_step"] = res["dp_world1"]["ms_per_step"] / res["ms_per_step"]
     if rank == 0:
-        if world == 1 and not dp and not args.no_cpu_baseline:
+        if world == 1 and not dp and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(W, b)
         try:                                   # anything native code left in C stdio goes out first,
             import ctypes                      # so that the JSON line is the last thing on stdout
