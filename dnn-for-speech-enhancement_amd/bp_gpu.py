@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "bp_fill_chunk_synthetic", "bp_train_resident", "bp_sync", "bp_grads_resident",
     "bp_grad_layout", "bp_grad_floats", "bp_read_grads", "bp_read_layer_output", "bp_last_train_ms", "bp_time_kernel",
     "bp_upload_chunk_windows", "bp_train_chunk_windows", "bp_cv_chunk_windows",
-    "bp_set_hyper", "bp_dp_attach", "bp_dp_attach_ex", "bp_dp_detach", "bp_dp_info", "bp_dp_peer_info", "bp_dp_handoff", "bp_dp_barrier", "bp_dp_allgather",
+    "bp_set_hyper", "bp_set_output", "bp_dp_attach", "bp_dp_attach_ex", "bp_dp_detach", "bp_dp_info", "bp_dp_peer_info", "bp_dp_handoff", "bp_dp_barrier", "bp_dp_allgather",
     "bp_rdv_open", "bp_rdv_barrier", "bp_rdv_allgather", "bp_rdv_close", "bp_device_pci_bus_id", "bp_host_register", "bp_host_unregister",
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
 ]
@@ -107,6 +107,7 @@ def load_library(path=None):
     lib.bp_profile_step.argtypes = [hp, C.c_int, C.c_int, fp, C.POINTER(C.c_int)]
     lib.bp_measure_peaks.argtypes = [hp, fp, fp]
     lib.bp_set_hyper.argtypes = [hp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
+    lib.bp_set_output.argtypes = [hp, C.c_int, C.c_int, C.c_int]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.bp_dp_peer_info.argtypes = [hp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -147,7 +148,8 @@ class BP_GPU(object):
 
     def __init__(self, gpu_used, numlayers, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
                  dropoutflag=0, visible_omit=0.0, hid_omit=0.0, activation=0, momentum_rule=0, seed=0, device=0,
-                 global_bunchsize=0, rank_frame_offset=0, max_chunk_frames=0, strict_exit=False, compute_dtype=0):
+                 global_bunchsize=0, rank_frame_offset=0, max_chunk_frames=0, strict_exit=False, compute_dtype=0,
+                 output_activation=0, output_linear_cols=0, output_loss=0):
         self._h = None
         self._strict = strict_exit
         self._lib = load_library()
@@ -176,9 +178,13 @@ class BP_GPU(object):
             b[l] = np.ascontiguousarray(bias[l], dtype=np.float32).reshape(-1)
             if w[l].size != self.layersizes[l - 1] * self.layersizes[l] or b[l].size != self.layersizes[l]:
                 self._fail("weights[%d]/bias[%d] have the wrong size" % (l, l))
+        out_mode = self._output_args(output_activation, output_linear_cols, output_loss)
+        self.output_activation = self.output_linear_cols = self.output_loss = 0
         h = C.c_void_p()
         self._check(self._lib.bp_create(C.byref(cfg), _ptrs(w), _ptrs(b), C.byref(h)))
         self._h = h
+        if out_mode != (0, 0, 0):
+            self.set_output(*out_mode)
 
     # ------------------------------------------------------------------ errors
     def _fail(self, msg):
@@ -203,6 +209,26 @@ class BP_GPU(object):
         assign obj.lrate / momentum / weightcost / dropoutflag / visible_omit / hid_omit between chunks."""
         self._check(self._lib.bp_set_hyper(self._h, float(self.lrate), float(self.momentum), float(self.weightcost),
                                            int(self.dropoutflag), float(self.visible_omit), float(self.hid_omit)))
+
+    def _output_args(self, activation, linear_cols, loss):
+        """Checks of bp_set_output, made here so that a bad value never reaches the library."""
+        a, c, s = int(activation), int(linear_cols), int(loss)
+        if a not in (0, 1):
+            self._fail("output activation must be 0 (linear) or 1 (logistic)")
+        if s not in (0, 1):
+            self._fail("output loss must be 0 (cross-entropy) or 1 (squared error)")
+        if a == 0 and (c != 0 or s != 0):
+            self._fail("output linear_cols and loss must be 0 with the linear output")
+        if a == 1 and not 0 <= c < self.layersizes[-1]:
+            self._fail("output linear_cols must be in [0, %d) with the logistic output" % self.layersizes[-1])
+        return a, c, s
+
+    def set_output(self, activation, linear_cols=0, loss=0):
+        """Output-layer nonlinearity (bp_set_output): 0 linear; 1 logistic on the output columns [linear_cols, sL), trained
+        with loss 0 (cross-entropy: dEdz = 2/Bg (y - t)) or 1 (squared error through the logistic).  From the next call on."""
+        a, c, s = self._output_args(activation, linear_cols, loss)
+        self._check(self._lib.bp_set_output(self._h, a, c, s))
+        self.output_activation, self.output_linear_cols, self.output_loss = a, c, s
 
     def train(self, n_frames, indata, targ):
         x = self._in(indata, n_frames, self.layersizes[0], "in")

@@ -20,6 +20,7 @@
 // (DMA = true; the 128-row tiles of the 4096-wide layers of configs[4]).  The grouped update launch is bp_wgrad_dma_bf16.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 typedef uint16_t bf16_t;
@@ -34,7 +35,8 @@ __device__ __forceinline__ bf16_t f2bf(float f)          // round to nearest eve
 }
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((uint32_t)h << 16); }
 
-enum { BEPI_FWD_HIDDEN = 0, BEPI_FWD_OUT = 1, BEPI_DGRAD = 2, BEPI_WGRAD_UPDATE = 3, BEPI_WGRAD_STORE = 4 };
+enum { BEPI_FWD_HIDDEN = 0, BEPI_FWD_OUT = 1, BEPI_DGRAD = 2, BEPI_WGRAD_UPDATE = 3, BEPI_WGRAD_STORE = 4,
+       BEPI_FWD_OUT_LOGI = 5 /* logistic output layer (bp_set_output; EPI_FWD_OUT_LOGI of bp_kernels.h) */ };
 
 struct BfGemmArgs {
     const bf16_t *A, *B;       // A [M][lda], B [N][ldb], both k-contiguous; rows padded to 64, k padded to 64 (zeros)
@@ -48,11 +50,14 @@ struct BfEpiArgs {
     // outputs in both orientations (bf16): C [M][ldc] and CT [N][ldct]
     bf16_t *C, *CT; int ldc, ldct;
     const float *bias; float alpha; int act;                       // fwd
-    const float *targ; int ldt; float *out; int ldo; float scale;  // fwd_out: targets, optional fp32 output, 2/n
-    const bf16_t *yprev; int ldy;                                  // dgrad: y_{l-1} (post-dropout)
+    const float *targ; int ldt; int lin_cols;                      // fwd_out: targets | fwd_out_logi: columns [0, lin_cols) stay linear
+    float *out; int ldo; float scale;                              // fwd_out: optional fp32 output, 2/n
+    const bf16_t *yprev; int ldy; int loss;                        // dgrad: y_{l-1} (post-dropout) | fwd_out_logi: 0 cross-entropy, 1 squared error
     float *W, *D; int ldw; float mom, c1, wc, ndiv;                // wgrad: fp32 master W / delta (update) or G (store, in W)
     uint32_t drop_thresh, seed_lo, seed_hi, step, layer; int frame_off;
 };
+// (lin_cols / loss sit in what was alignment padding: the linear kernels see the same argument layout as without them)
+static_assert(sizeof(BfEpiArgs) == 168 && offsetof(BfEpiArgs, out) == 72 && offsetof(BfEpiArgs, W) == 104, "BfEpiArgs layout");
 
 static constexpr int BF_BN = 64, BF_BK = 64, BF_LDS = BF_BK + 8;   // LDS row stride in halfs (144 B: conflict-free b128)
 static constexpr int BF_NPF = 3;                                     // k-tiles in flight in registers
@@ -164,14 +169,14 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
             }
     }
     if (n < e.n_limit) {
-        if constexpr (EPI == BEPI_FWD_HIDDEN || EPI == BEPI_FWD_OUT) bn = e.bias[n];
+        if constexpr (EPI == BEPI_FWD_HIDDEN || EPI == BEPI_FWD_OUT || EPI == BEPI_FWD_OUT_LOGI) bn = e.bias[n];
 #pragma unroll
         for (int b = 0; b < TMB; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = rbase + 32 * b + (r & 3) + 8 * (r >> 2);
                 if (m < e.m_limit) {
-                    if constexpr (EPI == BEPI_FWD_OUT) { if (e.C && live) in0[b][r] = e.targ[(size_t)m * e.ldt + n]; }
+                    if constexpr (EPI == BEPI_FWD_OUT || EPI == BEPI_FWD_OUT_LOGI) { if (e.C && live) in0[b][r] = e.targ[(size_t)m * e.ldt + n]; }
                     if constexpr (EPI == BEPI_WGRAD_UPDATE) { in0[b][r] = e.W[(size_t)m * e.ldw + n]; in1[b][r] = e.D[(size_t)m * e.ldw + n]; }
                 }
             }
@@ -392,11 +397,29 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
                 v[j] = d;
             }
             if (!e.C) continue;
+        } else if constexpr (EPI == BEPI_FWD_OUT_LOGI) {
+            // sigmoid on the logistic columns, output error per loss (bp_kernels.h EPI_FWD_OUT_LOGI); pad columns stay 0
+            const bool logi = live && n >= e.lin_cols, chain = logi && e.loss == 1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int m = mq + j;
+                float d = 0.0f;
+                if (m < e.m_limit) {
+                    const float z = live ? e.alpha * acc[4 * q + j] + bn : 0.0f;
+                    const float o = logi ? 1.0f / (1.0f + expf(-z)) : z;
+                    if (e.out) e.out[(size_t)m * e.ldo + n] = o;
+                    if (e.C && live) d = e.scale * (o - in0[blk][4 * q + j]);
+                    if (chain) d *= o * (1.0f - o);
+                }
+                v[j] = d;
+            }
+            if (!e.C) continue;
         } else if constexpr (EPI == BEPI_DGRAD) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 v[j] = (mq + j < e.m_limit && live) ? act_bwd(e.act, __uint_as_float(__float_as_uint(in0[blk][4 * q + j]) << 16)) * acc[4 * q + j] : 0.0f;
         } else {                                      // wgrad: rows = units of layer l-1, cols = units of layer l
+            static_assert(EPI == BEPI_WGRAD_UPDATE || EPI == BEPI_WGRAD_STORE, "epilogue without a branch");
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int m = mq + j;

@@ -73,6 +73,7 @@ struct bp_handle {
     size_t out_chunk_frames;
     uint32_t step;               // bunches trained so far (dropout stream position)
     uint32_t th_vis, th_hid;
+    int out_act, out_lin, out_loss;   // output layer (bp_set_output): 0 linear | 1 logistic on columns [out_lin, s_L), loss of those columns
     hipEvent_t ev0, ev1; float last_ms; int last_bunches;
     std::vector<void *> allocs;
     // Upload path: host->device copies run on copy_stream so that chunk i+1 is uploaded while chunk i trains.

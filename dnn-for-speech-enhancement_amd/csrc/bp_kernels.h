@@ -16,6 +16,7 @@
 // t+2 are in flight while tile t is multiplied and tile t+1 moves into the other LDS stage; one barrier per k-tile.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -34,7 +35,12 @@ __device__ __forceinline__ void static_for(F &&f)
 
 enum { EPI_FWD_HIDDEN = 0, EPI_FWD_OUT = 1, EPI_DGRAD = 2, EPI_WGRAD_UPDATE = 3, EPI_WGRAD_STORE = 4,
        EPI_PARTIAL = 5 /* raw k-slice partial sums into slab blockIdx.y (split-K) */,
-       EPI_OUT_SPLIT = 6 /* split-K output layer in ONE launch: k-slice partials into the slabs, the tile's last arriver sums them and runs EPI_FWD_OUT */ };
+       EPI_OUT_SPLIT = 6 /* split-K output layer in ONE launch: k-slice partials into the slabs, the tile's last arriver sums them and runs EPI_FWD_OUT */,
+       // logistic output layer (bp_set_output): EPI_FWD_OUT / EPI_OUT_SPLIT with y = 1/(1+expf(-z)) on the columns [lin_cols, n_true)
+       // and the output error of EpiArgs::loss there; separate IDs, so the linear kernels keep their code and names
+       EPI_FWD_OUT_LOGI = 7, EPI_OUT_SPLIT_LOGI = 8 };
+static constexpr bool epi_out(int epi) { return epi == EPI_FWD_OUT || epi == EPI_FWD_OUT_LOGI; }
+static constexpr bool epi_out_split(int epi) { return epi == EPI_OUT_SPLIT || epi == EPI_OUT_SPLIT_LOGI; }
 static constexpr int OUT_SPLITS = 4;                       // k-slices of the narrow output layer (EPI_OUT_SPLIT)
 
 // The k-loop loads carry NO predicates (a predicated load makes hipcc drain vmcnt at the top of
@@ -65,6 +71,8 @@ struct EpiArgs {
     float alpha;                     // fwd: x = alpha*acc + bias (alpha = keep in CV, BP_GPU.cu:726-746)
     int act;                         // 0 ReLU, 1 Sigmoid
     const float *aux; int ldaux;     // fwd_out: targ | dgrad: y_prev
+    int lin_cols;                    // fwd_out_logi: columns [0, lin_cols) stay linear (in what was alignment padding: the layout of
+                                     // the struct, and so the code of every kernel that takes it, is the same as without the field)
     float *aux2; int ldaux2;         // fwd_out: out (may be null) | wgrad_update: delta_W
     float scale;                     // fwd_out: 2/n_frames (DevFunc.cu:263)
     // wgrad update (DevFunc.cu:313-318 + 270-277)
@@ -75,8 +83,10 @@ struct EpiArgs {
     int frame_off;                   // global frame index of row 0 of this bunch
     const uint8_t *mask; int ldmask; // injected dropout mask of the produced activation ([row][unit] bytes, 1 = drop;
                                      // bp_train_resident_masked, parity tests only) -- replaces the Philox draw
+    int loss;                        // fwd_out_logi, logistic columns: 0 dEdz = scale*(y-t) (cross-entropy), 1 ... * y*(1-y) (squared error); padding slot too
     unsigned *done;                  // wgrad store (data parallel): +1 per finished tile, for the exchange stream (bp_dp.h); may be null
 };
+static_assert(sizeof(EpiArgs) == 160 && offsetof(EpiArgs, aux2) == 56 && offsetof(EpiArgs, done) == 152, "lin_cols / loss must sit in padding");
 
 // ------------------------------------------------------------------ Philox4x32-10
 __device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3,
@@ -177,10 +187,10 @@ __device__ __forceinline__ void epilogue_fetch(const EpiArgs &e, int mb, int nb,
     }
     const int n = nb + (lane & 31);
     const int rbase = mb + 4 * (lane >> 5);
-    static_assert(EPI != EPI_OUT_SPLIT, "fetched as EPI_FWD_OUT");
-    if constexpr (EPI == EPI_FWD_HIDDEN || EPI == EPI_FWD_OUT) p.bias = e.bias[n];
-    if constexpr (EPI == EPI_FWD_OUT || EPI == EPI_DGRAD) {
-        if (EPI == EPI_FWD_OUT && !e.C) return;
+    static_assert(!epi_out_split(EPI), "fetched as EPI_FWD_OUT[_LOGI]");
+    if constexpr (EPI == EPI_FWD_HIDDEN || epi_out(EPI)) p.bias = e.bias[n];
+    if constexpr (epi_out(EPI) || EPI == EPI_DGRAD) {
+        if (epi_out(EPI) && !e.C) return;
 #pragma unroll
         for (int r = R0; r < R0 + RN; ++r) {
             const int m = rbase + (r & 3) + 8 * (r >> 2);
@@ -253,6 +263,25 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
                 if (e.C) e.C[(size_t)m * e.ldc + n] = live ? e.scale * (o - p.p0[r]) : 0.0f;   // kernSubClean
             }
         }
+    } else if constexpr (EPI == EPI_FWD_OUT_LOGI) {
+        // BP_GPU.cu.bak:565-630: kernSigmoid on the output, then kernSubClean on the post-sigmoid output (loss 0); loss 1 adds the
+        // logistic's derivative.  Pad columns (n >= n_true) stay 0 in the output and the error: sigmoid(0) = 0.5 must not leak.
+        const float bn = p.bias;
+        const bool live = n < e.n_true, logi = live && n >= e.lin_cols, chain = logi && e.loss == 1;
+#pragma unroll
+        for (int r = R0; r < R0 + RN; ++r) {
+            const int m = rbase + (r & 3) + 8 * (r >> 2);
+            if (m < e.m_limit) {
+                const float z = live ? e.alpha * acc[r] + bn : 0.0f;
+                const float o = logi ? 1.0f / (1.0f + expf(-z)) : z;
+                if (e.aux2) e.aux2[(size_t)m * e.ldaux2 + n] = o;
+                if (e.C) {
+                    float d = live ? e.scale * (o - p.p0[r]) : 0.0f;
+                    if (chain) d *= o * (1.0f - o);
+                    e.C[(size_t)m * e.ldc + n] = d;
+                }
+            }
+        }
     } else if constexpr (EPI == EPI_DGRAD) {
 #pragma unroll
         for (int r = R0; r < R0 + RN; ++r) {
@@ -260,6 +289,7 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = act_bwd(e.act, p.p0[r]) * acc[r];   // kernDsigmoid*kernVecMul
         }
     } else {  // EPI_PARTIAL: plain store
+        static_assert(EPI == EPI_PARTIAL || EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE, "epilogue without a branch");   // (wgrad returned above)
 #pragma unroll
         for (int r = R0; r < R0 + RN; ++r) {
             const int m = rbase + (r & 3) + 8 * (r >> 2);
@@ -534,8 +564,8 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     const int ks = wave / (WM * WN), wq = wave % (WM * WN), wm = wq / WN, wn = wq % WN;
     GemmArgs g = g_in;
     EpiArgs e = e_in;
-    constexpr int EPI_E = EPI == EPI_OUT_SPLIT ? EPI_FWD_OUT : EPI;      // the epilogue proper
-    if constexpr (EPI == EPI_PARTIAL || EPI == EPI_OUT_SPLIT) {      // this workgroup row's k-slice and output slab
+    constexpr int EPI_E = EPI == EPI_OUT_SPLIT ? EPI_FWD_OUT : EPI == EPI_OUT_SPLIT_LOGI ? EPI_FWD_OUT_LOGI : EPI;      // the epilogue proper
+    if constexpr (EPI == EPI_PARTIAL || epi_out_split(EPI)) {      // this workgroup row's k-slice and output slab
         const size_t kz = (size_t)block_y * g.k_split;
         g.A += A_KC ? kz : kz * g.lda;
         g.B += B_KC ? kz : kz * g.ldb;
@@ -720,7 +750,7 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // done.  Nobody waits for anybody.  (The ticket words only grow: OUT_SPLITS per launch; the slices of a tile are workgroups
     // b, b + tiles, ... of the launch -- on one XCD, block index mod 8, whenever the tile count is a multiple of 8.)
     bool finish = true;
-    if constexpr (EPI == EPI_OUT_SPLIT) {
+    if constexpr (epi_out_split(EPI)) {
         static_assert(KS == 4 && OUT_SPLITS == 4, "one 32x32 block per workgroup, four registers of it per wave");
         float *mine = g.ks_slab + (size_t)block_y * g.slab_stride;
         if (ks == 0) out_split_store<0>(e, mine, mb0, nb0, acc[0][0], lane);

@@ -136,6 +136,7 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
     h->last_ms = 0.f; h->last_bunches = 0; h->dp = nullptr; h->params = h->deltas = nullptr;
     h->next_first = -1; h->pre.valid = false; h->wgen = 0; h->stage_cur = 0;
     h->bf_ks_slab = nullptr; h->bf_ks_cnt = nullptr;
+    h->out_act = h->out_lin = h->out_loss = 0;
 
 #define CK(x) do { int _r = (x); if (_r != BP_OK) { std::string m = g_bp_err; bp_destroy(h); g_bp_err = m; return _r; } } while (0)
 #define HK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::string m = std::string(#x) + ": " + hipGetErrorString(_e); bp_destroy(h); return fail(BP_ERR_DEVICE, m); } } while (0)
@@ -248,6 +249,20 @@ extern "C" int bp_set_hyper(bp_handle *h, float lrate, float momentum, float wei
     return BP_OK;
 }
 
+extern "C" int bp_set_output(bp_handle *h, int activation, int linear_cols, int loss)
+{
+    if (!h) return fail(BP_ERR_ARG, "bp_set_output: null handle");
+    if (activation != 0 && activation != 1) return fail(BP_ERR_ARG, "bp_set_output: activation must be 0 (linear) or 1 (logistic)");
+    if (loss != 0 && loss != 1) return fail(BP_ERR_ARG, "bp_set_output: loss must be 0 (cross-entropy) or 1 (squared error)");
+    const int sL = h->s[h->L - 1];
+    if (activation == 0 && (linear_cols != 0 || loss != 0))
+        return fail(BP_ERR_ARG, "bp_set_output: linear_cols and loss must be 0 with the linear output");
+    if (activation == 1 && (linear_cols < 0 || linear_cols >= sL))
+        return fail(BP_ERR_ARG, "bp_set_output: linear_cols must be in [0, " + std::to_string(sL) + ") with the logistic output");
+    h->out_act = activation; h->out_lin = linear_cols; h->out_loss = loss;
+    return BP_OK;
+}
+
 extern "C" int bp_sync(bp_handle *h)
 {
     if (!h) return fail(BP_ERR_ARG, "null handle");
@@ -297,6 +312,8 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
         return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN>(st, g, e, M, cur);
     }
     e.scale = 2.0f / (float)h->Bg;                       // kernSubClean: 2.0f/rows (global rows under DP)
+    const bool logi = h->out_act == 1;                   // bp_set_output: the EPI_*_LOGI siblings
+    e.lin_cols = h->out_lin; e.loss = h->out_loss;
     if (h->out_splits > 1) {
         g.K = prev / h->out_splits; g.k_split = g.K; g.slab_stride = h->slab_stride;
         g.ks_slab = h->slabs; g.ks_ticket = h->out_ticket;
@@ -304,6 +321,7 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
         e.C = train ? h->dx[l] : nullptr; e.ldc = cur;
         e.aux = targ; e.ldaux = cur; e.aux2 = out; e.ldaux2 = cur;
         using KOut = GemmKernel<32, 32, 64, 1, 1, true, false, EPI_OUT_SPLIT>;
+        using KOutLogi = GemmKernel<32, 32, 64, 1, 1, true, false, EPI_OUT_SPLIT_LOGI>;
         const int n_gemm = g.tiles_m * g.tiles_n * OUT_SPLITS;
         StageArgs sa; memset(&sa, 0, sizeof(sa));
         int n_stage = 0;
@@ -315,11 +333,16 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
             n_stage = stage_blocks(h, sa);
             h->pre.valid = true; h->pre.first = h->next_first; h->pre.tile = tile; h->pre.step = h->step + 1; h->pre.gen = h->wgen;
         }
-        hipLaunchKernelGGL(bp_out_split_stage<KOut>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, st, g, e, n_gemm, sa);
+        if (logi) hipLaunchKernelGGL(bp_out_split_stage<KOutLogi>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, st, g, e, n_gemm, sa);
+        else hipLaunchKernelGGL(bp_out_split_stage<KOut>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, st, g, e, n_gemm, sa);
         return hipGetLastError();
     }
     e.C = train ? h->dx[l] : nullptr; e.ldc = cur;
     e.aux = targ; e.ldaux = cur; e.aux2 = out; e.ldaux2 = cur;
+    if (logi) {
+        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT_LOGI>(st, g, e, M, cur);
+        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT_LOGI>(st, g, e, M, cur);
+    }
     if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT>(st, g, e, M, cur);
     return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT>(st, g, e, M, cur);
 }
@@ -513,7 +536,7 @@ static hipError_t bf_launch(bp_handle *h, BfGemmArgs g, const BfEpiArgs &e, int 
         hipLaunchKernelGGL((bp_gemm_bf16<EPI, 64, BKN>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, h->stream, g, e);
     } else {
         g.tiles_m = M / 32;
-        if constexpr (EPI == BEPI_FWD_OUT) {
+        if constexpr (EPI == BEPI_FWD_OUT || EPI == BEPI_FWD_OUT_LOGI) {
             if (h->bf_ks_slab && M == h->Bp && N == h->ld[h->L - 1]) {
                 g.ks_slab = h->bf_ks_slab; g.ks_cnt = h->bf_ks_cnt;
                 hipLaunchKernelGGL((bp_gemm_bf16<EPI, 32, BKN, false, BF_OUT_KS>), dim3(g.tiles_m * g.tiles_n * BF_OUT_KS), dim3(128), 0, h->stream, g, e);
@@ -544,6 +567,7 @@ static hipError_t bf_fwd(bp_handle *h, int l, int M, const float *targ, float *o
     e.scale = 2.0f / (float)h->Bg;
     e.targ = targ; e.ldt = cur; e.out = out; e.ldo = cur;
     if (train) { e.C = h->dxb[l]; e.CT = h->dxbT[l]; }
+    if (h->out_act == 1) { e.lin_cols = h->out_lin; e.loss = h->out_loss; return bf_launch<BEPI_FWD_OUT_LOGI, true>(h, g, e, h->Bp, cur); }
     return bf_launch<BEPI_FWD_OUT, true>(h, g, e, h->Bp, cur);
 }
 static hipError_t bf_input(bp_handle *h, const float *x0, int M)

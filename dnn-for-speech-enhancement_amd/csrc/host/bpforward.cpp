@@ -8,6 +8,7 @@
 //   bpforward fea_file=noisy.pfile norm_file=x.norm initwts_file=mlp.N.wts out_file=enh.pfile layersizes=1548,2048,...,129
 //             fea_dim=129 fea_context=11 targ_offset=5 sent_range=0-99 [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //             [bunchsize=1024] [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
+//             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
 //
 // out_file: an ICSI Pfile with the input's sentence structure; sentence s holds one record per window of that
 // sentence (frame id = window start + targ_offset), layersizes[last] features each: EVERY window of every sentence,
@@ -32,7 +33,7 @@ int main(int argc, char **argv)
 {
     std::string fea_file, norm_file, wts_file, out_file, range = "";
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
-    int activation = 0, device = 0, compute = 0;
+    int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0;
     float vis = 0.f, hid = 0.f;
     for (int i = 1; i < argc; ++i) {
         char *eq = strchr(argv[i], '=');
@@ -46,6 +47,19 @@ int main(int argc, char **argv)
         else if (k == "bunchsize") bunch = atoi(v.c_str()); else if (k == "traincache") cache = atoi(v.c_str());
         else if (k == "activation") activation = v == "sigmoid" ? 1 : 0; else if (k == "device") device = atoi(v.c_str());
         else if (k == "compute") compute = v == "bf16" ? 1 : 0;
+        // output layer (.wts files do not record it): the keys and checks of bptrain
+        else if (k == "output_act") {
+            if (v == "linear") out_act = 0; else if (v == "sigmoid") out_act = 1;
+            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
+        } else if (k == "output_linear_dims") {
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
+            out_lin = (int)n;
+        } else if (k == "output_loss") {
+            if (v == "xent") out_loss = 0; else if (v == "mse") out_loss = 1;
+            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
+        }
         else if (k == "layersizes") {
             size_t pos = 0;
             while (L < MAXLAYER) {
@@ -88,6 +102,7 @@ int main(int argc, char **argv)
     cfg.activation = activation; cfg.device = device; cfg.compute_dtype = compute; cfg.max_chunk_frames = cache;
     bp_handle *h = nullptr;
     if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
 
     // ---- output Pfile: header, records in reader order, sentence table
     FILE *fo = fopen(out_file.c_str(), "wb");

@@ -2,7 +2,7 @@
 // ("next" row N2 of SURVEY.md 8f): same `name=value` arguments (Interface.cc:89-244), same log lines,
 // same weight-file bytes, one epoch = train over the chunks of train_sent_range in shuffled order,
 // save weights, cross-validate over cv_sent_range (BPtrain.cc:16-101).  The trainer behind it is the
-// MI355X library through the drop-in class include/BP_GPU.h; the Perl epoch driver
+// MI355X library through the calls of the drop-in class include/BP_GPU.h (class Trainer below); the Perl epoch driver
 // (finetune_DNN_speech_enhancement_dropout_NAT.pl) can call this binary unchanged.
 //
 // gpu_used=N (N > 1) is data parallel, which the reference only has as commented-out code (BP_GPU.cu:29-36, 775-908):
@@ -18,7 +18,10 @@
 // momentum_rule=live|classic, seed=<u64> (dropout stream), device=<ordinal>, compute=fp32|bf16;
 // stack=device|host (default device: raw frames + index tables go to the GPU, which builds the context
 // windows -- 11x less host work and upload, identical samples; host = the reference's Readchunk layout),
-// prefetch=1|0 (default 1: the next chunk is read while the current one is uploaded / trained).
+// prefetch=1|0 (default 1: the next chunk is read while the current one is uploaded / trained);
+// output_act=linear|sigmoid, output_linear_dims=<n>, output_loss=xent|mse (output layer, bp_set_output: default linear; with
+// sigmoid the first n output columns stay linear -- e.g. LPS + IBM multi-objective targets -- and the logistic columns train
+// with cross-entropy (default) or squared error).  Unlike activation=, an unknown value of these is an error.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,6 +49,7 @@ struct Params {
     float wmin = -0.1f, wmax = 0.1f, bmin = -0.1f, bmax = 0.1f;          // Interface.cc:79-82
     bool stack_on_device = true, prefetch = true;
     int activation = 0, momentum_rule = 0, device = -1, compute_dtype = 0;
+    int output_act = 0, output_linear_dims = 0, output_loss = 0;
     unsigned long long dropout_seed = 0;
 };
 
@@ -58,6 +62,52 @@ static bool g_ring_finished = false;
 static void ring_abort_at_exit() { if (g_ring && !g_ring_finished) g_ring->abort(); }
 
 typedef bp::PfileReader::WindowChunk WindowChunk;
+
+// The trainer object: the calls of the drop-in class include/BP_GPU.h (same messages, same error convention), on a handle
+// this file owns, so that the output layer can be configured (bp_set_output) right after bp_create.
+class Trainer {
+public:
+    Trainer(bp_config cfg, float **weights, float **bias, int dp_world, int dp_rank, const char *dp_key, int out_act, int out_lin,
+            int out_loss)
+        : cfg_(cfg)
+    {
+        if (dp_world > 1) { cfg_.global_bunchsize = cfg_.bunchsize * dp_world; cfg_.rank_frame_offset = cfg_.bunchsize * dp_rank; }
+        check(bp_create(&cfg_, weights, bias, &h_));
+        if (dp_world > 1) check(bp_dp_attach(h_, dp_world, dp_rank, dp_key));
+        check(bp_set_output(h_, out_act, out_lin, out_loss));
+        printf("Created net with %d layers, bunchsize %d.\n", cfg_.numlayers, cfg_.bunchsize);   // BP_GPU.cu:196
+    }
+    ~Trainer() { bp_destroy(h_); }
+    void train(int n_frames, float *in, const float *targ) { push_hyper(); check(bp_train_chunk(h_, n_frames, in, targ)); }
+    void train_windows(const bp_window_chunk &c) { push_hyper(); check(bp_train_chunk_windows(h_, &c)); }
+    float CrossValid(int n_frames, const float *in, const float *targ)
+    {
+        float e = 0.0f;
+        push_hyper();
+        check(bp_cv_chunk(h_, n_frames, in, targ, &e));
+        return e;
+    }
+    float CrossValid_windows(const bp_window_chunk &c)
+    {
+        float e = 0.0f;
+        push_hyper();
+        check(bp_cv_chunk_windows(h_, &c, &e));
+        return e;
+    }
+    void dp_detach() { check(bp_dp_detach(h_)); }
+    void returnWeights(float **weights, float **bias) { check(bp_get_weights(h_, weights, bias)); }
+
+private:
+    Trainer(const Trainer &);
+    Trainer &operator=(const Trainer &);
+    void push_hyper() { check(bp_set_hyper(h_, cfg_.lrate, cfg_.momentum, cfg_.weightcost, cfg_.dropoutflag, cfg_.visible_omit, cfg_.hid_omit)); }
+    static void check(int rc)
+    {
+        if (rc != 0) { printf("%s\n", bp_last_error()); exit(0); }   // reference convention: message + exit(0)
+    }
+    bp_config cfg_;
+    bp_handle *h_ = nullptr;
+};
 static bp_window_chunk describe(const WindowChunk &w, int context)
 {
     bp_window_chunk c;
@@ -171,6 +221,19 @@ int main(int argc, char **argv)
         else if (k == "compute") P.compute_dtype = v == "bf16" ? 1 : 0;         // fp32 (default) | bf16
         else if (k == "stack") P.stack_on_device = (v != "host");
         else if (k == "prefetch") P.prefetch = atoi(v.c_str()) != 0;
+        // output layer (bp_set_output): strict, a typo must not silently train a different model
+        else if (k == "output_act") {
+            if (v == "linear") P.output_act = 0; else if (v == "sigmoid") P.output_act = 1;
+            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
+        } else if (k == "output_linear_dims") {
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
+            P.output_linear_dims = (int)n;
+        } else if (k == "output_loss") {
+            if (v == "xent") P.output_loss = 0; else if (v == "mse") P.output_loss = 1;
+            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
+        }
         // unknown names are silently ignored, as in the reference (e.g. the .pl passes numlayers=)
     }
     // ---- gpu_used > 1: data-parallel ranks, forked further down -- after the parent has opened the files, initialised the
@@ -306,7 +369,7 @@ int main(int argc, char **argv)
         cfg.device = rank % ndev;
     }
     if (lead) printf("Use GPU Device : %d\n", P.gpu_used);
-    BP_GPU *TrainObj = new BP_GPU(cfg, weights, bias, world, rank, dp_key.c_str());
+    Trainer *TrainObj = new Trainer(cfg, weights, bias, world, rank, dp_key.c_str(), P.output_act, P.output_linear_dims, P.output_loss);
     struct timespec ts0, ts1;
     clock_gettime(CLOCK_MONOTONIC, &ts0);
     if (world > 1) {

@@ -96,6 +96,21 @@ int bp_destroy(bp_handle *h);
 int bp_set_hyper(bp_handle *h, float lrate, float momentum, float weightcost, int dropoutflag,
                  float visible_omit, float hid_omit);
 
+/* Output-layer nonlinearity and loss (no counterpart in the live reference; its older revision BP_GPU.cu.bak:565-630
+ * applies kernSigmoid to the output layer and feeds the post-sigmoid output into kernSubClean).
+ * activation 0 = linear (default, = the live reference; linear_cols and loss must be 0).
+ * activation 1 = logistic y = 1/(1+expf(-z)) on output columns [linear_cols, sL); columns [0, linear_cols) stay linear
+ *   (z = alpha*acc + b, alpha = the CV keep-scale as for the linear output).
+ * loss (logistic columns only): 0 = dEdz = (2/Bg)(y - t)            (gradient of 2*BCE/Bg w.r.t. z; targets are NOT
+ *                                                                      range-checked: outside [0, 1] is the caller's business)
+ *                               1 = dEdz = (2/Bg)(y - t) * y * (1 - y)  (squared error through the logistic)
+ * Linear columns keep dEdz = (2/Bg)(o - t); Bg = global bunch.  Applies from the next call on, in fp32 and bf16 mode, on
+ * stacked and window chunks, in bp_train_*, bp_grads_resident, bp_cv_chunk[_windows] (squared error of the post-activation
+ * outputs) and bp_forward[_windows] (post-activation outputs).  On an attached data-parallel handle every rank must pass the
+ * same values (as for bp_set_hyper).  Bad values (activation or loss not 0/1, linear_cols outside [0, sL) with activation 1,
+ * non-zero linear_cols or loss with activation 0, null handle) return BP_ERR_ARG and leave the handle unchanged. */
+int bp_set_output(bp_handle *h, int activation, int linear_cols, int loss);
+
 /* BP_GPU::train (BP_GPU.cu:241-331): upload a chunk of n_frames stacked input frames and
  * targets, then run one SGD-momentum step (train_bunch_single, BP_GPU.cu:484-673) per
  * consecutive full bunch; the partial last bunch is ignored (:315-318).  Synchronous with
