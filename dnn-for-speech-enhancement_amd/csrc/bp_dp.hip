@@ -558,7 +558,7 @@ hipError_t dp_bunch(bp_handle *h, int first)
     for (int l = 1; l < L; ++l) {
         CKE(dp_wait_weights(h, l, prev_epoch));
         if (prev_epoch) CKE(step_shadow(h, l));                 // bf16 mode: bf16 copy of the gathered fp32 weights
-        CKE(step_forward(h, l, x0, tg));
+        CKE(step_forward(h, l, h->B, x0, tg, nullptr, true, 1.0f));
     }
     for (int l = L - 1; l >= 2; --l) CKE(step_dgrad(h, l));
     int all[BP_MAXLAYER], nall = 0;
@@ -588,14 +588,14 @@ hipError_t dp_bunch(bp_handle *h, int first)
             CKE(hipGetLastError());
             CKE(dp_reduce_layer(h, l));
         }
-        CKE(step_wgrads_store(h, all, nall, x0, done));
+        CKE(step_wgrads(h, all, nall, x0, false, done));
     } else {
         // layer 1 (the largest segment, needed first by the next forward) goes out alone; the rest as ONE grouped launch:
         // its exchange queues behind layer 1's on the comm stream anyway, and one launch + one event replace L-2 of each
-        CKE(step_wgrads_store(h, all, 1, x0, nullptr));
+        CKE(step_wgrads(h, all, 1, x0, false, nullptr));
         CKE(dp_exchange_layers(h, all, 1));
         if (nall > 1) {
-            CKE(step_wgrads_store(h, all + 1, nall - 1, x0, nullptr));
+            CKE(step_wgrads(h, all + 1, nall - 1, x0, false, nullptr));
             CKE(dp_exchange_layers(h, all + 1, nall - 1));
         }
     }

@@ -123,22 +123,28 @@ struct StepProf {
 // One bunch starting at chunk frame `first`: forward + backward; fused: momentum update inside the wgrad epilogues
 // (train_bunch_single, BP_GPU.cu:484-673), else gradients to the flat buffer.
 hipError_t bunch(bp_handle *h, int first, bool fused);
-// The pieces of a bunch, for the driver that cuts the step at the gradient exchange (bp_dp.hip):
+// nb fused bunches from chunk frame `first` (dp_bunch on an attached handle): the one place that sets next_first, advances
+// h->step (per enqueued bunch) and leaves neither next_first nor a pre-staged tile behind, on every path
+hipError_t train_bunches(bp_handle *h, int first, int nb);
+// The pieces of a bunch, shared by bunch(), the CV / inference forward and the driver that cuts the step at the gradient
+// exchange (bp_dp.hip):
 hipError_t step_inputs(bp_handle *h, int first, const float **x0, const float **tg);   // stage / mask the bunch's rows; where they lie
-hipError_t step_forward(bp_handle *h, int l, const float *x0, const float *tg);        // training forward of weight layer l (bf16: converts the input rows at l == 1)
+// forward of weight layer l on M frames from the input rows x0 (bf16: converted at l == 1).  train: hidden outputs get the
+// dropout mask and the output layer writes dEdX_L against tg; out (optional): the network outputs; alpha: keep-scale of the inputs
+hipError_t step_forward(bp_handle *h, int l, int M, const float *x0, const float *tg, float *out, bool train, float alpha);
 hipError_t step_dgrad(bp_handle *h, int l);                                             // dEdX_{l-1} from dEdX_l and the pre-update W_l
-// weight + bias gradients of layers ls[0..n) into the flat gradient buffer, ONE grouped launch where the kernel set allows it.
-// done != null: done[l] is a device counter every tile of layer l's segment bumps behind its stores (in-kernel hand-off);
-// only legal when step_wgrads_count(h) says the launch really counts.
-hipError_t step_wgrads_store(bp_handle *h, const int *ls, int n, const float *x0, unsigned *const *done);
+// weight + bias gradients of layers ls[0..n), ONE grouped launch where the kernel set allows it; fused: momentum update in the
+// epilogue, else store into the flat gradient buffer.  done != null (store only): done[l] is a device counter every tile of
+// layer l's segment bumps behind its stores (in-kernel hand-off); only legal when step_wgrads_count(h) says the launch really counts.
+hipError_t step_wgrads(bp_handle *h, const int *ls, int n, const float *x0, bool fused, unsigned *const *done);
 bool step_wgrads_count(const bp_handle *h);
 unsigned step_wgrad_tiles(const bp_handle *h, int l);                                   // tiles of layer l in that launch
 hipError_t step_shadow(bp_handle *h, int l);                                            // fp32 master W_l -> bf16 shadow (bf16 mode)
 bool step_stages(const bp_handle *h);                                                   // the bunch's input rows go through the staged tile (window chunk | visible dropout)
-// single launches (bp_profile.hip: isolated kernel timing)
-hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y_prev, const float *targ, float *out, bool train, float alpha);
-hipError_t launch_dgrad(bp_handle *h, hipStream_t st, int l, int M);
-hipError_t launch_wgrad(bp_handle *h, hipStream_t st, int l, int M, const float *y_prev, bool fused);
+// single launches on h->stream (bp_profile.hip: isolated kernel timing)
+hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const float *targ, float *out, bool train, float alpha);
+hipError_t launch_dgrad(bp_handle *h, int l, int M);
+hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused);
 hipError_t prof_mark(bp_handle *h, int kind);
 
 // ------------------------------------------------------------------ data-parallel driver (bp_dp.hip)

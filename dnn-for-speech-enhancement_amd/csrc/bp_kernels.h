@@ -34,7 +34,6 @@ __device__ __forceinline__ void static_for(F &&f)
 }
 
 enum { EPI_FWD_HIDDEN = 0, EPI_FWD_OUT = 1, EPI_DGRAD = 2, EPI_WGRAD_UPDATE = 3, EPI_WGRAD_STORE = 4,
-       EPI_PARTIAL = 5 /* raw k-slice partial sums into slab blockIdx.y (split-K) */,
        EPI_OUT_SPLIT = 6 /* split-K output layer in ONE launch: k-slice partials into the slabs, the tile's last arriver sums them and runs EPI_FWD_OUT */,
        // logistic output layer (bp_set_output): EPI_FWD_OUT / EPI_OUT_SPLIT with y = 1/(1+expf(-z)) on the columns [lin_cols, n_true)
        // and the output error of EpiArgs::loss there; separate IDs, so the linear kernels keep their code and names
@@ -288,13 +287,8 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             const int m = rbase + (r & 3) + 8 * (r >> 2);
             if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = act_bwd(e.act, p.p0[r]) * acc[r];   // kernDsigmoid*kernVecMul
         }
-    } else {  // EPI_PARTIAL: plain store
-        static_assert(EPI == EPI_PARTIAL || EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE, "epilogue without a branch");   // (wgrad returned above)
-#pragma unroll
-        for (int r = R0; r < R0 + RN; ++r) {
-            const int m = rbase + (r & 3) + 8 * (r >> 2);
-            if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = acc[r];
-        }
+    } else {
+        static_assert(EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE, "epilogue without a branch");   // (wgrad returned above)
     }
 }
 
@@ -541,8 +535,8 @@ struct GemmCfg {
 };
 
 // The workgroup program of one GEMM problem: workgroups first_block, first_block+stride, ... of
-// the launch walk its tiles.  Wrapped by bp_gemm (one problem per launch) and bp_gemm_dual (two
-// independent problems in one launch, see there).
+// the launch walk its tiles.  Wrapped by bp_gemm (one problem per launch), bp_gemm_multi (up to
+// four independent problems in one launch) and bp_out_split_stage.
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int EPI>
 struct GemmKernel {
     using Cfg = GemmCfg<BM, BN, BK, WM, WN, A_KC, B_KC, EPI>;
@@ -565,11 +559,10 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     GemmArgs g = g_in;
     EpiArgs e = e_in;
     constexpr int EPI_E = EPI == EPI_OUT_SPLIT ? EPI_FWD_OUT : EPI == EPI_OUT_SPLIT_LOGI ? EPI_FWD_OUT_LOGI : EPI;      // the epilogue proper
-    if constexpr (EPI == EPI_PARTIAL || epi_out_split(EPI)) {      // this workgroup row's k-slice and output slab
+    if constexpr (epi_out_split(EPI)) {      // this workgroup row's k-slice
         const size_t kz = (size_t)block_y * g.k_split;
         g.A += A_KC ? kz : kz * g.lda;
         g.B += B_KC ? kz : kz * g.ldb;
-        if constexpr (EPI == EPI_PARTIAL) e.C += (size_t)block_y * g.slab_stride;
     }
 
     // ---- XCD-aware tile mapping: block b runs on XCD b%8; give each XCD a contiguous range of
@@ -974,22 +967,4 @@ __global__ __launch_bounds__(256, K::MIN_WG) void bp_out_split_stage(const GemmA
     const int b = blockIdx.x;
     if (b < n_gemm) { const int tiles = g.tiles_m * g.tiles_n; K::run(g, e, b % tiles, tiles, b / tiles, smem); }
     else { const int i = b - n_gemm; stage_block(st, i % st.nbx, i / st.nbx, threadIdx.x); }
-}
-
-// Momentum update on a flat [W|b] gradient segment after the data-parallel sum
-// (kernUpdatedelta + kernAccSum, DevFunc.cu:313-318, 270-277); wc applies to the W part only.
-__global__ void bp_update_flat(float *w, float *d, const float *g, size_t n_w, float *bw, float *bd,
-                               const float *bg, int n_b, float mom, float c1, float wc, float ndiv)
-{
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_w; i += stride) {
-        const float wi = w[i];
-        const float di = mom * d[i] - c1 * (g[i] / ndiv + wc * wi);
-        d[i] = di; w[i] = di + 1.0f * wi;
-    }
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n_b; i += stride) {
-        const float wi = bw[i];
-        const float di = mom * bd[i] - c1 * (bg[i] / ndiv + 0.0f * wi);
-        bd[i] = di; bw[i] = di + 1.0f * wi;
-    }
 }

@@ -24,12 +24,7 @@ extern "C" int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, flo
     int rc = BP_OK;
     h->prof = &prof;
     hipError_t er = prof_mark(h, -1);                        // origin
-    for (int i = 0; er == hipSuccess && i < n_bunches; ++i) {
-        h->next_first = (step_stages(h) && i + 1 < n_bunches) ? first_frame + (i + 1) * h->B : -1;   // (as bp_train_resident)
-        er = bunch(h, first_frame + i * h->B, true);
-        h->step++;
-    }
-    h->next_first = -1; h->pre.valid = false;
+    if (er == hipSuccess) er = train_bunches(h, first_frame, n_bunches);
     h->prof = nullptr;
     if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
     double sum[BP_PROF_KINDS] = {0}; long cnt[BP_PROF_KINDS] = {0};
@@ -137,8 +132,8 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
         if (it == 0) HIPCHK(hipEventRecord(a, h->stream));
         hipError_t er = hipSuccess;
         switch (which) {
-        case 0: er = launch_fwd(h, h->stream, 2, B, h->y[1], nullptr, nullptr, true, 1.0f); break;
-        case 1: er = launch_dgrad(h, h->stream, 3 < L ? 3 : 2, B); break;
+        case 0: er = launch_fwd(h, 2, B, h->y[1], nullptr, nullptr, true, 1.0f); break;
+        case 1: er = launch_dgrad(h, 3 < L ? 3 : 2, B); break;
         case 2: case 5: {
             // wgrad + fused update on scratch copies of W / delta (same traffic, state untouched)
             const int l = which == 2 ? 2 : 1;
@@ -152,12 +147,12 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
             }
             float *W0 = h->W[l], *D0 = h->dW[l], *b0 = h->b[l], *db0 = h->db[l];
             h->W[l] = scratch_w; h->dW[l] = scratch_d; h->b[l] = scratch_b; h->db[l] = scratch_b + h->ld[l];
-            er = launch_wgrad(h, h->stream, l, B, l == 1 ? h->in : h->y[l - 1], true);
+            er = launch_wgrad(h, l, B, l == 1 ? h->in : h->y[l - 1], true);
             h->W[l] = W0; h->dW[l] = D0; h->b[l] = b0; h->db[l] = db0;
             break;
         }
-        case 3: er = launch_fwd(h, h->stream, 1, B, h->in, nullptr, nullptr, true, 1.0f); break;
-        case 4: er = launch_fwd(h, h->stream, L - 1, B, h->y[L - 2], h->targ, nullptr, true, 1.0f); break;
+        case 3: er = launch_fwd(h, 1, B, h->in, nullptr, nullptr, true, 1.0f); break;
+        case 4: er = launch_fwd(h, L - 1, B, h->y[L - 2], h->targ, nullptr, true, 1.0f); break;
         default: HIPCHK(hipEventDestroy(a)); HIPCHK(hipEventDestroy(b));
                  return fail(BP_ERR_ARG, "bp_time_kernel: unknown kernel id");
         }

@@ -273,13 +273,11 @@ extern "C" int bp_sync(bp_handle *h)
 
 // ------------------------------------------------------------------ launches
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int EPI, int TAG = 0>
-static hipError_t launch(hipStream_t st, GemmArgs g, const EpiArgs &e, int M, int N, int max_grid = 0)
+static hipError_t launch(hipStream_t st, GemmArgs g, const EpiArgs &e, int M, int N)
 {
     g.tiles_m = (M + BM - 1) / BM;
     g.tiles_n = (N + BN - 1) / BN;
-    int grid = g.tiles_m * g.tiles_n;
-    if (max_grid > 0 && grid > max_grid) grid = max_grid;     // persistent: workgroups loop over tiles
-    hipLaunchKernelGGL((bp_gemm<BM, BN, BK, WM, WN, A_KC, B_KC, EPI, TAG>), dim3(grid), dim3(256), 0, st, g, e);
+    hipLaunchKernelGGL((bp_gemm<BM, BN, BK, WM, WN, A_KC, B_KC, EPI, TAG>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, st, g, e);
     return hipGetLastError();
 }
 
@@ -293,8 +291,7 @@ static EpiArgs epi_zero()
 
 // forward of weight layer l on M frames.  y_prev [M][ld_{l-1}].  train: hidden outputs get the
 // hid_omit mask; output layer writes dEdX_L (and out when out != null).
-hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y_prev, const float *targ,
-                      float *out, bool train, float alpha)
+hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const float *targ, float *out, bool train, float alpha)
 {
     const int L = h->L, prev = h->ld[l - 1], cur = h->ld[l];
     GemmArgs g; memset(&g, 0, sizeof(g));
@@ -307,9 +304,9 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
         e.seed_lo = (uint32_t)h->cfg.seed; e.seed_hi = (uint32_t)(h->cfg.seed >> 32);
         e.step = h->step; e.layer = (uint32_t)l; e.frame_off = h->cfg.rank_frame_offset;
         if (train && h->inj_mask[l]) { e.mask = h->inj_mask[l]; e.ldmask = h->s[l]; e.drop_thresh = 1u; }   // injected mask (tests)
-        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_HIDDEN>(st, g, e, M, cur);
-        if (l == 1) return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN, 1>(st, g, e, M, cur);   // (TAG 1: own name in profiles)
-        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN>(st, g, e, M, cur);
+        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_HIDDEN>(h->stream, g, e, M, cur);
+        if (l == 1) return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN, 1>(h->stream, g, e, M, cur);   // (TAG 1: own name in profiles)
+        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN>(h->stream, g, e, M, cur);
     }
     e.scale = 2.0f / (float)h->Bg;                       // kernSubClean: 2.0f/rows (global rows under DP)
     const bool logi = h->out_act == 1;                   // bp_set_output: the EPI_*_LOGI siblings
@@ -325,7 +322,7 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
         const int n_gemm = g.tiles_m * g.tiles_n * OUT_SPLITS;
         StageArgs sa; memset(&sa, 0, sizeof(sa));
         int n_stage = 0;
-        if (train && h->next_first >= 0 && st == h->stream) {
+        if (train && h->next_first >= 0) {
             // another staged bunch behind this one (window chunk, or stacked chunk with visible dropout): stack / copy (and mask, with the NEXT step's Philox position) that bunch
             // into the other tile from the spare workgroups of this launch
             const int tile = 1 - h->stage_cur;
@@ -333,18 +330,18 @@ hipError_t launch_fwd(bp_handle *h, hipStream_t st, int l, int M, const float *y
             n_stage = stage_blocks(h, sa);
             h->pre.valid = true; h->pre.first = h->next_first; h->pre.tile = tile; h->pre.step = h->step + 1; h->pre.gen = h->wgen;
         }
-        if (logi) hipLaunchKernelGGL(bp_out_split_stage<KOutLogi>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, st, g, e, n_gemm, sa);
-        else hipLaunchKernelGGL(bp_out_split_stage<KOut>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, st, g, e, n_gemm, sa);
+        if (logi) hipLaunchKernelGGL(bp_out_split_stage<KOutLogi>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, h->stream, g, e, n_gemm, sa);
+        else hipLaunchKernelGGL(bp_out_split_stage<KOut>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, h->stream, g, e, n_gemm, sa);
         return hipGetLastError();
     }
     e.C = train ? h->dx[l] : nullptr; e.ldc = cur;
     e.aux = targ; e.ldaux = cur; e.aux2 = out; e.ldaux2 = cur;
     if (logi) {
-        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT_LOGI>(st, g, e, M, cur);
-        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT_LOGI>(st, g, e, M, cur);
+        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT_LOGI>(h->stream, g, e, M, cur);
+        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT_LOGI>(h->stream, g, e, M, cur);
     }
-    if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT>(st, g, e, M, cur);
-    return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT>(st, g, e, M, cur);
+    if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT>(h->stream, g, e, M, cur);
+    return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT>(h->stream, g, e, M, cur);
 }
 
 // A prepared backward GEMM: arguments + which tile configuration it uses.
@@ -459,16 +456,16 @@ static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n)
     return hipSuccess;
 }
 
-hipError_t launch_dgrad(bp_handle *h, hipStream_t st, int l, int M)
+hipError_t launch_dgrad(bp_handle *h, int l, int M)
 {
     Prepared p = prep_dgrad(h, l, M);
-    if (p.cfg == CFG_DGRAD_WIDE128) return run_multi<KDgradWide128, 32, 64>(st, &p, 1);
-    return p.cfg == CFG_DGRAD_WIDE ? run_multi<KDgradWide, 32, 64>(st, &p, 1) : run_multi<KDgradNarrow, 32, 32>(st, &p, 1);
+    if (p.cfg == CFG_DGRAD_WIDE128) return run_multi<KDgradWide128, 32, 64>(h->stream, &p, 1);
+    return p.cfg == CFG_DGRAD_WIDE ? run_multi<KDgradWide, 32, 64>(h->stream, &p, 1) : run_multi<KDgradNarrow, 32, 32>(h->stream, &p, 1);
 }
-hipError_t launch_wgrad(bp_handle *h, hipStream_t st, int l, int M, const float *y_prev, bool fused)
+hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused)
 {
     Prepared p = prep_wgrad(h, l, M, y_prev, fused);
-    return run_wgrads(st, &p, 1);
+    return run_wgrads(h->stream, &p, 1);
 }
 
 // Bunches whose input rows go through the staged tile (x0s2): every bunch of a window chunk (stacked on the device, SURVEY 8f
@@ -689,24 +686,25 @@ hipError_t step_inputs(bp_handle *h, int first, const float **x0, const float **
     }
     return hipSuccess;
 }
-hipError_t step_forward(bp_handle *h, int l, const float *x0, const float *tg)
+// forward of weight layer l on M frames; x0: the input rows (read at l == 1; bf16: converted there)
+hipError_t step_forward(bp_handle *h, int l, int M, const float *x0, const float *tg, float *out, bool train, float alpha)
 {
     if (h->bf) {
-        if (l == 1) { const hipError_t er = bf_input(h, x0, h->B); if (er != hipSuccess) return er; }
-        return bf_fwd(h, l, h->B, tg, nullptr, true, 1.0f);
+        if (l == 1) { const hipError_t er = bf_input(h, x0, M); if (er != hipSuccess) return er; }
+        return bf_fwd(h, l, M, tg, out, train, alpha);
     }
-    return launch_fwd(h, h->stream, l, h->B, l == 1 ? x0 : h->y[l - 1], tg, nullptr, true, 1.0f);
+    return launch_fwd(h, l, M, l == 1 ? x0 : h->y[l - 1], tg, out, train, alpha);
 }
-hipError_t step_dgrad(bp_handle *h, int l) { return h->bf ? bf_dgrad(h, l) : launch_dgrad(h, h->stream, l, h->B); }
+hipError_t step_dgrad(bp_handle *h, int l) { return h->bf ? bf_dgrad(h, l) : launch_dgrad(h, l, h->B); }
 // (fp32: the LDS-DMA store kernel of the static bunch sizes is the one that counts its tiles, up to 4 layers per launch)
 bool step_wgrads_count(const bp_handle *h) { return !h->bf && (h->B == 128 || h->B == 256 || h->B == 512) && h->L - 1 <= 4; }
 unsigned step_wgrad_tiles(const bp_handle *h, int l) { return (unsigned)(((h->ld[l - 1] + 63) / 64) * ((h->ld[l] + 63) / 64)); }
-hipError_t step_wgrads_store(bp_handle *h, const int *ls, int n, const float *x0, unsigned *const *done)
+hipError_t step_wgrads(bp_handle *h, const int *ls, int n, const float *x0, bool fused, unsigned *const *done)
 {
-    if (h->bf) return bf_wgrads(h, ls, n, false);
+    if (h->bf) return bf_wgrads(h, ls, n, fused);
     Prepared ws[BP_MAXLAYER];
     for (int i = 0; i < n; ++i) {
-        ws[i] = prep_wgrad(h, ls[i], h->B, ls[i] == 1 ? x0 : h->y[ls[i] - 1], false);
+        ws[i] = prep_wgrad(h, ls[i], h->B, ls[i] == 1 ? x0 : h->y[ls[i] - 1], fused);
         if (done) ws[i].e.done = done[ls[i]];
     }
     return run_wgrads(h->stream, ws, n);
@@ -718,32 +716,41 @@ hipError_t step_wgrads_store(bp_handle *h, const int *ls, int n, const float *x0
 // sees pre-update weights because wgrad+update(l) always follows dgrad(l).
 hipError_t bunch(bp_handle *h, int first, bool fused)
 {
-    const int L = h->L, B = h->B;
+    const int L = h->L;
     hipError_t er;
 #define CKE(x) do { er = (x); if (er != hipSuccess) return er; } while (0)
     const float *x0, *tg;
     CKE(step_inputs(h, first, &x0, &tg));
-    int ls[BP_MAXLAYER];
-    for (int l = 1; l < L; ++l) ls[l - 1] = l;          // wgrad problems: layer 1 (the largest) first
-    if (h->bf) {
-        for (int l = 1; l < L; ++l) CKE(step_forward(h, l, x0, tg));
-        for (int l = L - 1; l >= 2; --l) CKE(bf_dgrad(h, l));   // every dgrad sees pre-update (shadow) weights
-        return bf_wgrads(h, ls, L - 1, fused);
-    }
     for (int l = 1; l < L; ++l) {
-        CKE(launch_fwd(h, h->stream, l, B, l == 1 ? x0 : h->y[l - 1], tg, nullptr, true, 1.0f));
+        CKE(step_forward(h, l, h->B, x0, tg, nullptr, true, 1.0f));
         CKE(prof_mark(h, l == 1 ? BP_PROF_FWD_L1 : (l == L - 1 ? BP_PROF_FWD_OUT : BP_PROF_FWD_HIDDEN)));
     }
     // Every dgrad of the step reads pre-update weights (BP_GPU.cu:636 runs before :643-652 of the same
     // layer and the lower layers' updates come later), so the wgrad+update problems can all wait until
     // the last dgrad and share grouped launches (bp_gemm_multi).
-    for (int l = L - 1; l >= 2; --l) { CKE(launch_dgrad(h, h->stream, l, B)); CKE(prof_mark(h, l == L - 1 ? BP_PROF_DGRAD_OUT : BP_PROF_DGRAD_HIDDEN)); }
-    Prepared ws[BP_MAXLAYER];
-    for (int l = 1; l < L; ++l) ws[l - 1] = prep_wgrad(h, l, B, l == 1 ? x0 : h->y[l - 1], fused);
-    CKE(run_wgrads(h->stream, ws, L - 1));
+    for (int l = L - 1; l >= 2; --l) { CKE(step_dgrad(h, l)); CKE(prof_mark(h, l == L - 1 ? BP_PROF_DGRAD_OUT : BP_PROF_DGRAD_HIDDEN)); }
+    int ls[BP_MAXLAYER];
+    for (int l = 1; l < L; ++l) ls[l - 1] = l;          // wgrad problems: layer 1 (the largest) first
+    CKE(step_wgrads(h, ls, L - 1, x0, fused, nullptr));
     CKE(prof_mark(h, BP_PROF_WGRAD));
 #undef CKE
     return hipSuccess;
+}
+
+// nb bunches from chunk frame `first`, each on the data-parallel driver when the handle is attached.  The per-bunch state
+// lives here alone: next_first names the bunch that the output layer's launch may pre-stage, h->step advances once per
+// enqueued bunch, and on the way out -- also on the error path, where a stale index would stage rows of a later, smaller
+// chunk -- neither next_first nor a pre-staged tile survives.
+hipError_t train_bunches(bp_handle *h, int first, int nb)
+{
+    hipError_t er = hipSuccess;
+    for (int i = 0; i < nb && er == hipSuccess; ++i) {
+        h->next_first = (step_stages(h) && !h->bf && i + 1 < nb) ? first + (i + 1) * h->B : -1;
+        er = h->dp ? dp_bunch(h, first + i * h->B) : bunch(h, first + i * h->B, true);
+        if (er == hipSuccess) h->step++;
+    }
+    h->next_first = -1; h->pre.valid = false;
+    return er;
 }
 
 // ------------------------------------------------------------------ chunk interface
@@ -973,17 +980,8 @@ extern "C" int bp_train_resident(bp_handle *h, int first_frame, int n_frames)
     HIPCHK(hipSetDevice(h->cfg.device));
     const int nb = n_frames / h->B;          // partial last bunch ignored (BP_GPU.cu:315-318)
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipError_t er = hipSuccess;
-    for (int i = 0; i < nb && er == hipSuccess; ++i) {
-        h->next_first = (step_stages(h) && !h->bf && i + 1 < nb) ? first_frame + (i + 1) * h->B : -1;
-        er = h->dp ? dp_bunch(h, first_frame + i * h->B) : bunch(h, first_frame + i * h->B, true);
-        if (er == hipSuccess) h->step++;
-    }
-    h->next_first = -1;                      // (also on the error path: a stale index would stage rows of a later, smaller chunk)
-    if (er != hipSuccess) {
-        h->pre.valid = false;
-        return fail(BP_ERR_DEVICE, std::string("bp_train_resident: ") + hipGetErrorString(er));
-    }
+    const hipError_t er = train_bunches(h, first_frame, nb);
+    if (er != hipSuccess) return fail(BP_ERR_DEVICE, std::string("bp_train_resident: ") + hipGetErrorString(er));
     if (h->dp && nb > 0) HIPCHK(dp_flush(h));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->last_bunches = nb;
@@ -1051,20 +1049,20 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
         if (dm[0]) {
             hipLaunchKernelGGL(bp_apply_mask, dim3((h->ld[0] + 255) / 256, B), dim3(256), 0, h->stream, h->in + (size_t)first * h->ld[0], xm,
                                h->ld[0], h->s[0], dm[0] + (size_t)i * B * h->s[0], B);
-            er = hipGetLastError();
-            h->inj_x0 = xm;
+            if ((er = hipGetLastError()) != hipSuccess) break;
         }
-        for (int l = 1; l < L - 1; ++l) h->inj_mask[l] = dm[l] ? dm[l] + (size_t)i * B * h->s[l] : nullptr;
-        // with injected masks the Philox thresholds must stay out of the way: layers without a mask get no dropout
+        // the injected state of this bunch; with injected masks the Philox thresholds must stay out of the way: layers
+        // without a mask get no dropout
         const uint32_t th_hid = h->th_hid, th_vis = h->th_vis;
+        h->inj_x0 = xm;
+        for (int l = 1; l < L - 1; ++l) h->inj_mask[l] = dm[l] ? dm[l] + (size_t)i * B * h->s[l] : nullptr;
         h->th_hid = 0u; h->th_vis = 0u;
-        if (er == hipSuccess) er = bunch(h, first, true);
+        er = train_bunches(h, first, 1);
         h->th_hid = th_hid; h->th_vis = th_vis;
-        h->step++;
+        h->inj_x0 = nullptr;
+        for (int l = 0; l < BP_MAXLAYER; ++l) h->inj_mask[l] = nullptr;
         if (er == hipSuccess) er = hipStreamSynchronize(h->stream);     // (xm is reused by the next bunch)
     }
-    h->inj_x0 = nullptr;
-    for (int l = 0; l < BP_MAXLAYER; ++l) h->inj_mask[l] = nullptr;
     if (er != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_train_resident_masked: ") + hipGetErrorString(er));
     (void)hipStreamSynchronize(h->stream);
     for (auto p : dm) if (p) (void)hipFree(p);
@@ -1178,13 +1176,10 @@ static int forward_bunch(bp_handle *h, int first, int fb)
     float *out = h->out_chunk + (size_t)first * h->ld[L - 1];
     const float *x0 = h->windows ? h->x0s : h->in + (size_t)first * h->ld[0];
     if (h->windows) HIPCHK(stage_bunch(h, first, fb, false));
-    if (h->bf) HIPCHK(bf_input(h, x0, fb));
     for (int l = 1; l < L; ++l) {
         float alpha = 1.0f;
         if (h->cfg.dropoutflag == 1) alpha = (l == 1) ? vis_keep : hid_keep;
-        if (h->bf) { HIPCHK(bf_fwd(h, l, fb, nullptr, out, false, alpha)); continue; }
-        const float *yp = (l == 1) ? x0 : h->y[l - 1];
-        HIPCHK(launch_fwd(h, h->stream, l, fb, yp, nullptr, out, false, alpha));
+        HIPCHK(step_forward(h, l, fb, x0, nullptr, out, false, alpha));
     }
     return BP_OK;
 }

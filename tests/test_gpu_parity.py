@@ -811,3 +811,27 @@ def test_visible_mask_over_a_chunk_larger_than_the_old_grid_limit(pkg):
     w, _ = g.get_weights()
     assert all(np.isfinite(a).all() for a in w[1:]) and not np.array_equal(w[1], W[1])
     g.close()
+
+
+def test_profile_step_drives_the_training_bunch_loop(pkg):
+    """bp_profile_step runs the bunch loop of bp_train_resident with an event after every launch.  At C2's shape (split-K output
+    layer, visible dropout: every bunch after the first is pre-staged by the previous bunch's output-layer launch) it reports the
+    step's eight launches per class, and it leaves the step counter where training the same bunches would: profiling 4 bunches and
+    training 4 more gives, bit for bit, the weights and momentum of training all 8 in one call."""
+    ls, B, nb = [2827, 2048, 2048, 2048, 257], 256, 4
+    W, b = N.glorot_net(ls, seed=1, beta=0.5)
+    kw = dict(lr=0.01, cap=2 * nb * B, dropoutflag=1, visible_omit=0.1, hid_omit=0.2, seed=11)
+    g1, g2 = _mk(pkg, ls, B, W, b, **kw), _mk(pkg, ls, B, W, b, **kw)
+    for g in (g1, g2):
+        g.fill_chunk_synthetic(2 * nb * B, 5)
+    prof = g1.profile_step(0, nb)
+    kinds = ["fwd_l1", "fwd_hidden", "fwd_out", "dgrad_out", "dgrad_hidden", "wgrad_update_grouped"]
+    assert [prof[k][1] for k in kinds] == [1, 2, 1, 1, 2, 1], prof
+    assert all(prof[k][0] > 0 for k in kinds), prof
+    g1.train_resident(nb * B, nb * B)
+    g2.train_resident(0, 2 * nb * B)
+    r1, r2 = g1.get_weights() + g1.get_deltas(), g2.get_weights() + g2.get_deltas()
+    for l in range(1, len(ls)):
+        for a, c in zip(r1, r2):
+            assert np.array_equal(a[l], c[l]), l
+    g1.close(); g2.close()
