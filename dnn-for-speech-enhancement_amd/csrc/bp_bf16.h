@@ -23,6 +23,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "bp_device.h"
+
 typedef uint16_t bf16_t;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
@@ -90,9 +92,8 @@ template <int N> __device__ __forceinline__ void bf_lgkm3(bf_f32x4 &a, bf_f32x4 
 template <int N> __device__ __forceinline__ void bf_lgkm4(bf_f32x4 &a, bf_f32x4 &b, bf_v4s &c, bf_v4s &d) { asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N)); }
 // KS > 1 (the narrow output layer of configs[4]: 80 tiles of 32 x 64 over K = 4096 are 64 DEPENDENT k-tile round trips on a third of the
 // CUs, 17.7 us): the k range of a tile is split over KS workgroups -- launched next to each other on ONE XCD (block index mod 8), so they
-// meet in one L2 -- that write their fp32 partial tiles (write-through), drain, and take a ticket from the tile's word; the LAST arriver
-// sums the KS partials in the fixed order 0..KS-1 (its own included, from memory: the same bits whoever arrives last) and runs the
-// epilogue.  Nobody waits for anybody.  The ticket words only grow (KS per launch; 2^32 is a multiple of KS).
+// meet in one L2 -- that write their fp32 partial tiles and take a ticket from the tile's word (last_arrival); the LAST arriver sums the
+// KS partials in the fixed order 0..KS-1 (its own included, from memory: the same bits whoever arrives last) and runs the epilogue.
 template <int EPI, int BM, bool BKN = false, bool DMA = false, int KS = 1>
 __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf16(const BfGemmArgs g, const BfEpiArgs e)
 {
@@ -338,12 +339,8 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
         for (int b = 0; b < TMB; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) __hip_atomic_store(mine + (b * 16 + r) * NTHR + tid, accs[b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        unsigned *tk = reinterpret_cast<unsigned *>(smem);    // (the stages are free: the loop ended on a barrier)
-        if (tid == 0) *tk = __hip_atomic_fetch_add(g.ks_cnt + tile_lin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if ((*tk & (KS - 1)) != KS - 1) return;               // not the last of this launch's KS arrivals
+        // (the ticket's LDS word: the stages are free, the loop ended on a barrier)
+        if (!last_arrival(g.ks_cnt + tile_lin, reinterpret_cast<unsigned *>(smem), KS)) return;   // not the last of this launch's KS arrivals
         constexpr int ZG = KS < 4 ? KS : 4;                    // partials in flight per pass (4 x 16 x TMB registers)
 #pragma unroll
         for (int z0 = 0; z0 < KS; z0 += ZG) {
@@ -427,7 +424,7 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
                 const size_t i = (size_t)m * e.ldw + n;
                 if constexpr (EPI == BEPI_WGRAD_UPDATE) {
                     const float w = in0[blk][4 * q + j];
-                    const float d = e.mom * in1[blk][4 * q + j] - e.c1 * (acc[4 * q + j] / e.ndiv + e.wc * w);   // kernUpdatedelta
+                    const float d = update_delta(e.mom, e.c1, e.wc, e.ndiv, in1[blk][4 * q + j], acc[4 * q + j], w);
                     e.D[i] = d;
                     v[j] = d + 1.0f * w;                                                                    // kernAccSum
                     e.W[i] = v[j];
@@ -525,7 +522,7 @@ __global__ void bp_bias_bf16(const bf16_t *dx, int ld, int rows, int n_true, flo
 #pragma unroll
     for (int y = 0; y < 16; ++y) s += part[y][threadIdx.x];
     if (gout) { gout[n] = s; return; }
-    const float d = mom * dbias[n] - c1 * (s / ndiv + 0.0f * bias[n]);
+    const float d = update_delta(mom, c1, 0.0f, ndiv, dbias[n], s, bias[n]);
     dbias[n] = d;
     bias[n] = d + 1.0f * bias[n];
 }

@@ -37,6 +37,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bp_device.h"
+
 enum { BP_DP_MAXRANKS = 8 };
 // flag words of one rank: [kind][layer][source rank]
 enum { BP_DP_FLAG_GRAD = 0, BP_DP_FLAG_W = 1, BP_DP_FLAG_PROBE = 2 /* attach-time self-test: layer index = direction */, BP_DP_FLAG_KINDS = 3 };
@@ -219,10 +221,10 @@ __global__ __launch_bounds__(256) void bp_dp_reduce_update(const DpReduceArgs a)
                 if (p < world) s += g[u][p];
             const float wc = a.lo + 4 * q < a.w_end ? a.wc : 0.0f;      // (segments are multiples of 64 floats: a float4 never straddles)
             float4 dn; bp_f32x4 wn;
-            dn.x = a.mom * d[u].x - a.c1 * (s.x / a.ndiv + wc * w[u].x); wn.x = dn.x + 1.0f * w[u].x;   // kernUpdatedelta, kernAccSum
-            dn.y = a.mom * d[u].y - a.c1 * (s.y / a.ndiv + wc * w[u].y); wn.y = dn.y + 1.0f * w[u].y;
-            dn.z = a.mom * d[u].z - a.c1 * (s.z / a.ndiv + wc * w[u].z); wn.z = dn.z + 1.0f * w[u].z;
-            dn.w = a.mom * d[u].w - a.c1 * (s.w / a.ndiv + wc * w[u].w); wn.w = dn.w + 1.0f * w[u].w;
+            dn.x = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].x, s.x, w[u].x); wn.x = dn.x + 1.0f * w[u].x;   // kernAccSum
+            dn.y = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].y, s.y, w[u].y); wn.y = dn.y + 1.0f * w[u].y;
+            dn.z = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].z, s.z, w[u].z); wn.z = dn.z + 1.0f * w[u].z;
+            dn.w = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].w, s.w, w[u].w); wn.w = dn.w + 1.0f * w[u].w;
             *reinterpret_cast<float4 *>(d_own + 4 * q) = dn;      // (nontemporal accesses for the momentum stream: 0.2657 vs 0.2537 ms, profiles/r05_dp_world1.txt)
 #pragma unroll
             for (int p = 0; p < BP_DP_MAXRANKS; ++p)

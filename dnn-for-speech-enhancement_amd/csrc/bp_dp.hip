@@ -433,8 +433,8 @@ static void dp_update_args(bp_handle *h, int l, DpReduceArgs &a)
     a.delta = h->deltas; a.lo = d->lo[l]; a.hi = d->hi[l];
     a.w_end = h->g_off[l] + (size_t)h->ld[l - 1] * h->ld[l];
     a.world = d->world; a.rank = d->rank;
-    const float m = h->cfg.momentum, lr = h->cfg.lrate;
-    a.mom = m; a.c1 = h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr; a.wc = h->cfg.weightcost; a.ndiv = (float)h->Bg;
+    const UpdateCoef u = update_coef(h);
+    a.mom = u.mom; a.c1 = u.c1; a.wc = u.wc; a.ndiv = u.ndiv;
     a.arrive = d->arrive + l; a.peers = dp_peers(d); a.flag_index = bp_dp_flag_index(BP_DP_FLAG_W, l, d->rank); a.epoch = d->epoch;
 }
 static int dp_update_grid(const DpReduceArgs &a, int layer)

@@ -108,6 +108,15 @@ struct bp_handle {
     float *bf_ks_slab; unsigned *bf_ks_cnt;                  // split-k output forward (bp_bf16.h, KS): partial tiles and ticket words, or null
 };
 
+// Coefficients of the momentum update (update_delta, bp_device.h; DevFunc.cu:313-318 for momentum_rule 0, :306-311 for 1):
+// c1 = (1-m)*lr or lr, ndiv = the global bunch.
+struct UpdateCoef { float mom, c1, wc, ndiv; };
+static inline UpdateCoef update_coef(const bp_handle *h)
+{
+    const float m = h->cfg.momentum, lr = h->cfg.lrate;
+    return {m, h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr, h->cfg.weightcost, (float)h->Bg};
+}
+
 // Every device buffer gets SLACK floats of zeroed tail so that whole-tile reads of the GEMM loaders (no predicates,
 // see GemmArgs) stay inside the allocation.
 static const size_t SLACK = 4096;

@@ -19,19 +19,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <type_traits>
-#include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(std::forward<F>(f));
-    }
-}
+#include "bp_device.h"
 
 enum { EPI_FWD_HIDDEN = 0, EPI_FWD_OUT = 1, EPI_DGRAD = 2, EPI_WGRAD_UPDATE = 3, EPI_WGRAD_STORE = 4,
        EPI_OUT_SPLIT = 6 /* split-K output layer in ONE launch: k-slice partials into the slabs, the tile's last arriver sums them and runs EPI_FWD_OUT */,
@@ -86,51 +74,6 @@ struct EpiArgs {
     unsigned *done;                  // wgrad store (data parallel): +1 per finished tile, for the exchange stream (bp_dp.h); may be null
 };
 static_assert(sizeof(EpiArgs) == 160 && offsetof(EpiArgs, aux2) == 56 && offsetof(EpiArgs, done) == 152, "lin_cols / loss must sit in padding");
-
-// ------------------------------------------------------------------ Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3,
-                                              uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-// Dropout words of the 4 consecutive bunch rows r0..r0+3 (r0 % 4 == 0) of unit n: word (gf & 3) of the Philox block
-// keyed by (gf >> 2, unit) with gf = global frame index = row + frame_off.  frame_off % 4 == 0 (the usual case) needs
-// one block; otherwise the four rows straddle two (frame_off is a launch constant, so the branch is uniform).
-__device__ __forceinline__ void drop_words4(uint32_t (&w)[4], int r0, int n, int frame_off, uint32_t n_true, uint32_t layer,
-                                            uint32_t step, uint32_t seed_lo, uint32_t seed_hi)
-{
-    const uint64_t g0 = (uint64_t)(uint32_t)(r0 + frame_off);
-    const uint64_t idx = (g0 >> 2) * (uint64_t)n_true + (uint32_t)n;
-    uint32_t a[4] = {(uint32_t)idx, (uint32_t)(idx >> 32), layer, step};
-    philox4x32_10(a[0], a[1], a[2], a[3], seed_lo, seed_hi);
-    const int sh = frame_off & 3;
-    if (sh == 0) { w[0] = a[0]; w[1] = a[1]; w[2] = a[2]; w[3] = a[3]; return; }
-    const uint64_t idx2 = idx + (uint64_t)n_true;
-    uint32_t b[4] = {(uint32_t)idx2, (uint32_t)(idx2 >> 32), layer, step};
-    philox4x32_10(b[0], b[1], b[2], b[3], seed_lo, seed_hi);
-    if (sh == 1) { w[0] = a[1]; w[1] = a[2]; w[2] = a[3]; w[3] = b[0]; }
-    else if (sh == 2) { w[0] = a[2]; w[1] = a[3]; w[2] = b[0]; w[3] = b[1]; }
-    else { w[0] = a[3]; w[1] = b[0]; w[2] = b[1]; w[3] = b[2]; }
-}
-
-__device__ __forceinline__ float act_fwd(int act, float x)
-{
-    // DevFunc.cu:67-79 (ReLU, strict > 0) | DevFunc.cu:47-54 (.bak: 1/(1+expf(-x)))
-    return act == 0 ? (x > 0.0f ? x : 0.0f) : 1.0f / (1.0f + expf(-x));
-}
-__device__ __forceinline__ float act_bwd(int act, float y)
-{
-    // DevFunc.cu:81-97 (y>0 ? 1 : 0) | :56-64 (.bak: (1-y)*y), from the post-dropout output y
-    return act == 0 ? (y > 0.0f ? 1.0f : 0.0f) : (1.0f - y) * y;
-}
 
 // ------------------------------------------------------------------ epilogue of one 32x32 block
 // C/D layout of v_mfma_f32_32x32x2_f32: lane l, reg r -> row (r&3) + 8*(r>>2) + 4*(l>>5), col l&31.
@@ -216,7 +159,7 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             if constexpr (EPI == EPI_WGRAD_UPDATE) {
                 float *cd = uniform_ptr(e.aux2 + (size_t)mb * e.ldc + nb);
                 const float w = p.p0[r];
-                const float d = e.mom * p.p1[r] - e.c1 * (acc[r] / e.ndiv + e.wc * w);   // kernUpdatedelta
+                const float d = update_delta(e.mom, e.c1, e.wc, e.ndiv, p.p1[r], acc[r], w);
                 *reinterpret_cast<float *>(reinterpret_cast<char *>(sgpr_row_base(cd + ro)) + lob) = d;
                 *reinterpret_cast<float *>(reinterpret_cast<char *>(sgpr_row_base(cw + ro)) + lob) = d + 1.0f * w;   // kernAccSum
             } else {
@@ -293,7 +236,7 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
 }
 
 // EPI_OUT_SPLIT, registers [R0, R0+4) of the wave's 32x32 block.  store: this k-slice's partial sums into its slab, agent-scope
-// write-through (complete in memory once the wave has drained vmcnt).  sum: the OUT_SPLITS partials of the tile, added in slice order
+// write-through (the accesses last_arrival relies on).  sum: the OUT_SPLITS partials of the tile, added in slice order
 // 0..3 whichever slice arrived last (the summation order of the two-launch form this replaces: the same bits), agent-scope loads.
 template <int R0>
 __device__ __forceinline__ void out_split_store(const EpiArgs &e, float *slab, int mb, int nb, const f32x16 &acc, int lane)
@@ -728,7 +671,7 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
                 for (int r = 0; r < RG; ++r) s += red[r * BN + tid];
                 const int n = n0 + tid;
                 if constexpr (EPI == EPI_WGRAD_UPDATE) {
-                    const float d = e.mom * e.bias_d[n] - e.c1 * (s / e.ndiv + 0.0f * e.bias_w[n]);
+                    const float d = update_delta(e.mom, e.c1, 0.0f, e.ndiv, e.bias_d[n], s, e.bias_w[n]);
                     e.bias_d[n] = d;
                     e.bias_w[n] = d + 1.0f * e.bias_w[n];
                 } else {
@@ -738,10 +681,10 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         }
     }
 
-    // ---- split-K across workgroups in one launch (EPI_OUT_SPLIT): every slice writes its partial tile, drains, takes a ticket from the
-    // tile's word; the last of the OUT_SPLITS arrivals of this launch sums the slices and runs the output epilogue, the others are
-    // done.  Nobody waits for anybody.  (The ticket words only grow: OUT_SPLITS per launch; the slices of a tile are workgroups
-    // b, b + tiles, ... of the launch -- on one XCD, block index mod 8, whenever the tile count is a multiple of 8.)
+    // ---- split-K across workgroups in one launch (EPI_OUT_SPLIT): every slice writes its partial tile and takes a ticket from the
+    // tile's word (last_arrival); the last of the OUT_SPLITS arrivals of this launch sums the slices and runs the output epilogue,
+    // the others are done.  (The slices of a tile are workgroups b, b + tiles, ... of the launch -- on one XCD, block index mod 8,
+    // whenever the tile count is a multiple of 8.)
     bool finish = true;
     if constexpr (epi_out_split(EPI)) {
         static_assert(KS == 4 && OUT_SPLITS == 4, "one 32x32 block per workgroup, four registers of it per wave");
@@ -750,12 +693,8 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         if (ks == 1) out_split_store<4>(e, mine, mb0, nb0, acc[0][0], lane);
         if (ks == 2) out_split_store<8>(e, mine, mb0, nb0, acc[0][0], lane);
         if (ks == 3) out_split_store<12>(e, mine, mb0, nb0, acc[0][0], lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                       // (also: every wave is past its reads of the exchange area)
-        unsigned *tk = reinterpret_cast<unsigned *>(smem);
-        if (tid == 0) *tk = __hip_atomic_fetch_add(g.ks_ticket + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        finish = (*tk & (OUT_SPLITS - 1)) == OUT_SPLITS - 1;
+        // (the ticket's LDS word: its first barrier also puts every wave past its reads of the exchange area)
+        finish = last_arrival(g.ks_ticket + b, reinterpret_cast<unsigned *>(smem), OUT_SPLITS);
         if (finish) {
             if (ks == 0) out_split_sum<0>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);
             if (ks == 1) out_split_sum<4>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);

@@ -385,10 +385,9 @@ static Prepared prep_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool
     p.e = epi_zero();
     p.e.ldc = cur; p.e.m_limit = prev; p.e.n_limit = cur; p.e.n_true = h->s[l];
     if (fused) {
-        const float m = h->cfg.momentum, lr = h->cfg.lrate;
+        const UpdateCoef u = update_coef(h);
         p.e.C = h->W[l]; p.e.aux2 = h->dW[l]; p.e.ldaux2 = cur;
-        p.e.mom = m; p.e.c1 = h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr; p.e.wc = h->cfg.weightcost;
-        p.e.ndiv = (float)h->Bg;
+        p.e.mom = u.mom; p.e.c1 = u.c1; p.e.wc = u.wc; p.e.ndiv = u.ndiv;
         p.e.bias_w = h->b[l]; p.e.bias_d = h->db[l];
     } else {
         p.e.C = h->grad + h->g_off[l];
@@ -592,10 +591,9 @@ static hipError_t bf_wgrad(bp_handle *h, int l, bool fused)
     g.A = h->ybT[l - 1]; g.lda = h->Bp; g.B = h->dxbT[l]; g.ldb = h->Bp; g.K = h->Bp;
     BfEpiArgs e; memset(&e, 0, sizeof(e));
     e.m_limit = prev; e.n_limit = cur; e.n_true = h->s[l]; e.ldw = cur;
-    const float m = h->cfg.momentum, lr = h->cfg.lrate;
-    const float c1 = h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr;
+    const UpdateCoef u = update_coef(h);
     if (fused) {
-        e.W = h->W[l]; e.D = h->dW[l]; e.mom = m; e.c1 = c1; e.wc = h->cfg.weightcost; e.ndiv = (float)h->Bg;
+        e.W = h->W[l]; e.D = h->dW[l]; e.mom = u.mom; e.c1 = u.c1; e.wc = u.wc; e.ndiv = u.ndiv;
         e.C = h->Wb[l]; e.ldc = cur; e.CT = nullptr; e.ldct = 0;
         er = bf_launch<BEPI_WGRAD_UPDATE>(h, g, e, prev, cur);
     } else {
@@ -604,8 +602,8 @@ static hipError_t bf_wgrad(bp_handle *h, int l, bool fused)
     }
     if (er != hipSuccess) return er;
     hipLaunchKernelGGL(bp_bias_bf16, dim3((h->s[l] + 63) / 64), dim3(64, 16), 0, h->stream, h->dxb[l], cur, h->B, h->s[l],
-                       h->b[l], h->db[l], fused ? (float *)nullptr : h->grad + h->g_off[l] + (size_t)prev * cur, m, c1,
-                       (float)h->Bg);
+                       h->b[l], h->db[l], fused ? (float *)nullptr : h->grad + h->g_off[l] + (size_t)prev * cur, u.mom, u.c1,
+                       u.ndiv);
     return hipGetLastError();
 }
 // The LDS-DMA wgrad of bp_wgrad_dma_bf16.h: static bunch sizes, layers ls[0..n) in one grouped launch (bias gradient
@@ -613,8 +611,7 @@ static hipError_t bf_wgrad(bp_handle *h, int l, bool fused)
 static bool bf_dma_ok(const bp_handle *h) { return h->Bp == 128 || h->Bp == 256 || h->Bp == 512 || h->Bp == 1024; }
 static hipError_t bf_wgrads_dma(bp_handle *h, const int *ls, int n, bool fused)
 {
-    const float m = h->cfg.momentum, lr = h->cfg.lrate;
-    const float c1 = h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr;
+    const UpdateCoef u = update_coef(h);
     for (int i0 = 0; i0 < n; i0 += BF_WGRAD_MAXP) {
         BfWgradMulti a; memset(&a, 0, sizeof(a));
         const int cnt = n - i0 < BF_WGRAD_MAXP ? n - i0 : BF_WGRAD_MAXP;
@@ -628,7 +625,7 @@ static hipError_t bf_wgrads_dma(bp_handle *h, const int *ls, int n, bool fused)
             p.e.ldc = cur; p.e.m_limit = prev; p.e.n_limit = cur; p.e.n_true = h->s[l];
             if (fused) {
                 p.e.C = h->W[l]; p.e.aux2 = h->dW[l]; p.e.ldaux2 = cur;
-                p.e.mom = m; p.e.c1 = c1; p.e.wc = h->cfg.weightcost; p.e.ndiv = (float)h->Bg;
+                p.e.mom = u.mom; p.e.c1 = u.c1; p.e.wc = u.wc; p.e.ndiv = u.ndiv;
                 p.e.bias_w = h->b[l]; p.e.bias_d = h->db[l];
                 p.Wb = h->Wb[l]; p.ldwb = cur;
             } else {

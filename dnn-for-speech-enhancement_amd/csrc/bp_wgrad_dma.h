@@ -120,7 +120,7 @@ struct WgradDma {
                     if constexpr (STORE) {
                         __hip_atomic_store(e.bias_g + n, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);     // (write-through, like the tile below)
                     } else {
-                        const float d = e.mom * e.bias_d[n] - e.c1 * (s / e.ndiv + 0.0f * e.bias_w[n]);
+                        const float d = update_delta(e.mom, e.c1, 0.0f, e.ndiv, e.bias_d[n], s, e.bias_w[n]);
                         e.bias_d[n] = d;
                         e.bias_w[n] = d + 1.0f * e.bias_w[n];
                     }

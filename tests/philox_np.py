@@ -1,4 +1,4 @@
-"""Philox4x32-10 and the dropout-mask keying of the HIP path (dnn-for-speech-enhancement_amd/csrc/bp_kernels.h, drop_words4 /
+"""Philox4x32-10 and the dropout-mask keying of the HIP path (dnn-for-speech-enhancement_amd/csrc/bp_device.h, drop_words4 /
 bp_mask_input), restated in numpy for the tests: a third implementation next to the device's and the oracle's, so that a
 GPU parity test can build its reference without importing anything under oracle/.
 Keying: counter = (idx_lo, idx_hi, layer, step), key = (seed_lo, seed_hi), idx = (global_frame >> 2) * width + unit;
