@@ -36,7 +36,9 @@ ABI_SYMBOLS = [
     "bp_set_hyper", "bp_set_output", "bp_dp_attach", "bp_dp_attach_ex", "bp_dp_detach", "bp_dp_info", "bp_dp_peer_info", "bp_dp_handoff", "bp_dp_barrier", "bp_dp_allgather",
     "bp_rdv_open", "bp_rdv_barrier", "bp_rdv_allgather", "bp_rdv_close", "bp_device_pci_bus_id", "bp_host_register", "bp_host_unregister",
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
+    "bp_enhance_waves", "bp_wave_lps",
 ]
+WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 PROF_KINDS = ["fwd_l1", "fwd_hidden", "fwd_out", "dgrad_out", "dgrad_hidden", "wgrad_update_grouped"]
 
 
@@ -50,6 +52,16 @@ class BPWindowChunk(C.Structure):
         ("n_samples", C.c_int), ("n_frames", C.c_int), ("fea_dim", C.c_int), ("context", C.c_int), ("n_nat", C.c_int),
         ("fea", C.POINTER(C.c_float)), ("targ_frames", C.POINTER(C.c_float)), ("nat", C.POINTER(C.c_float)),
         ("win_start", C.POINTER(C.c_int)), ("targ_frame", C.POINTER(C.c_int)), ("nat_row", C.POINTER(C.c_int)),
+    ]
+
+
+class BPWaveChunk(C.Structure):
+    """bp_wave_chunk (include/bp_c_api.h): noisy sentences for bp_enhance_waves."""
+    _fields_ = [
+        ("n_sent", C.c_int), ("sent_len", C.POINTER(C.c_int)), ("pcm", C.POINTER(C.c_float)),
+        ("context", C.c_int), ("targ_offset", C.c_int),
+        ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
+        ("target", C.c_int), ("out_col", C.c_int),
     ]
 
 
@@ -94,6 +106,8 @@ def load_library(path=None):
     lib.bp_train_chunk_windows.argtypes = [hp, C.POINTER(BPWindowChunk)]
     lib.bp_cv_chunk_windows.argtypes = [hp, C.POINTER(BPWindowChunk), fp]
     lib.bp_forward_windows.argtypes = [hp, C.POINTER(BPWindowChunk), fp]
+    lib.bp_enhance_waves.argtypes = [hp, C.c_int, C.POINTER(BPWaveChunk), fp, fp]
+    lib.bp_wave_lps.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp]
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -314,6 +328,28 @@ class BP_GPU(object):
         self._check(self._lib.bp_cv_chunk_windows(self._h, C.byref(c), C.byref(e)))
         return float(e.value)
 
+    # ---- waveform enhancement (bp_enhance_waves; signal definition: include/bp_c_api.h)
+    def enhance_waves(self, sentences, mean, inv_std, context, targ_offset, target=WAVE_LPS, out_col=0, return_net=False):
+        """Noisy sentences (1-D float32, int16 units) -> enhanced sentences of the same lengths; with return_net also the
+        net outputs per frame, one [T_s][layersizes[-1]] array per sentence."""
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).reshape(-1)
+        D = mean.size
+        if inv_std.size != D:
+            self._fail("enhance_waves: mean and inv_std differ in length")
+        pcm, lens, frames = _sentences(sentences, D)
+        c = BPWaveChunk()
+        c.n_sent, c.sent_len, c.pcm = len(lens), lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm)
+        c.context, c.targ_offset, c.mean, c.inv_std = int(context), int(targ_offset), _fp(mean), _fp(inv_std)
+        c.target, c.out_col = int(target), int(out_col)
+        out = np.empty(max(pcm.size, 1), np.float32)
+        net = np.empty((max(int(frames.sum()), 1), self.layersizes[-1]), np.float32) if return_net else None
+        self._check(self._lib.bp_enhance_waves(self._h, D, C.byref(c), _fp(out), _fp(net) if return_net else None))
+        waves = np.split(out[:pcm.size], np.cumsum(lens)[:-1])
+        if not return_net:
+            return waves
+        return waves, np.split(net[:int(frames.sum())], np.cumsum(frames)[:-1])
+
     def fill_chunk_synthetic(self, n_frames, seed=20260927):
         self._check(self._lib.bp_fill_chunk_synthetic(self._h, int(n_frames), int(seed)))
 
@@ -437,6 +473,27 @@ class BP_GPU(object):
             self.close()
         except Exception:
             pass
+
+
+def _sentences(sentences, fea_dim):
+    """Concatenated float32 samples, int32 lengths and the frame count of every sentence (T = (n-1)/hop + 2)."""
+    arrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in sentences]
+    lens = np.array([a.size for a in arrs], np.int32)
+    pcm = np.concatenate(arrs) if arrs else np.zeros(0, np.float32)
+    hop = max(fea_dim - 1, 1)
+    frames = np.where(lens > 0, (lens - 1) // hop + 2, 0).astype(np.int64)
+    return np.ascontiguousarray(pcm), lens, frames
+
+
+def wave_lps(device, fea_dim, sentences):
+    """bp_wave_lps: the log-power spectrum of every sentence, one [T_s][fea_dim] float32 array each (no handle)."""
+    lib = load_library()
+    pcm, lens, frames = _sentences(sentences, int(fea_dim))
+    out = np.empty((max(int(frames.sum()), 1), int(fea_dim)), np.float32)
+    rc = lib.bp_wave_lps(int(device), int(fea_dim), len(lens), lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
 
 
 def device_count():

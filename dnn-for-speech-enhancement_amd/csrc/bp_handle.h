@@ -6,6 +6,7 @@
 //   bp_step.hip     handle construction, chunk interface, every kernel launch of the training / CV / forward step
 //   bp_dp.hip       in-library data-parallel exchange (rendezvous, hipIpc peers, RCCL transport, the sharded step driver)
 //   bp_profile.hip  in-step event profile, measured peaks, isolated kernel timing
+//   bp_wave.hip     the signal layer: STFT analysis into a window chunk, overlap-add resynthesis (bp_enhance_waves, bp_wave_lps)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -106,6 +107,9 @@ struct bp_handle {
     bf16_t *yb[BP_MAXLAYER], *ybT[BP_MAXLAYER];              // [Bp][ld_l], [ld_l][Bp]   (l = 0: the input bunch)
     bf16_t *dxb[BP_MAXLAYER], *dxbT[BP_MAXLAYER];
     float *bf_ks_slab; unsigned *bf_ks_cnt;                  // split-k output forward (bp_bf16.h, KS): partial tiles and ticket words, or null
+    // bp_enhance_waves (bp_wave.hip), grow-only: device input block, noisy spectrum, synthesis frames, padded output samples;
+    // pinned host staging of the input block and of the output samples
+    Raw wave[4], wave_pin[2];
 };
 
 // Coefficients of the momentum update (update_delta, bp_device.h; DevFunc.cu:313-318 for momentum_rule 0, :306-311 for 1):
@@ -155,6 +159,14 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
 hipError_t launch_dgrad(bp_handle *h, int l, int M);
 hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused);
 hipError_t prof_mark(bp_handle *h, int kind);
+// A window chunk written by kernels on h->stream (bp_wave.hip): window_reserve sizes the staging set that is not current
+// (rows_b bytes of raw frames, nat_b bytes of NAT rows, n_samples entries of win_start and nat_row) and returns where they lie;
+// window_adopt then makes it the resident window chunk with the bookkeeping of bp_upload_chunk_windows (no targets).
+int window_reserve(bp_handle *h, size_t rows_b, size_t nat_b, size_t n_samples, float **rows, float **nat, int **win_start, int **nat_row);
+int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat);
+// CV-semantics forward of samples [0, n) of the resident chunk into out_chunk (the partial last bunch included), no copy
+int out_chunk_reserve(bp_handle *h, int n_frames);
+int forward_resident(bp_handle *h, int n);
 
 // ------------------------------------------------------------------ data-parallel driver (bp_dp.hip)
 int dp_check(bp_handle *h);                       // BP_OK, or the device-side timeout an exchange kernel raised

@@ -1,6 +1,6 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), part 1 of 3: the device state of one BP_GPU replacement
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), part 1 of 4: the device state of one BP_GPU replacement
 // object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.  The handle and
-// what the other two translation units use of this one: bp_handle.h.
+// what the other three translation units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -71,6 +71,8 @@ extern "C" int bp_destroy(bp_handle *h)
     if (h->dp) (void)bp_dp_detach(h);
     for (void *p : h->allocs) (void)hipFree(p);
     for (auto &ws : h->wset) for (auto &r : ws.r) if (r.p) (void)hipFree(r.p);
+    for (auto &r : h->wave) if (r.p) (void)hipFree(r.p);
+    for (auto &r : h->wave_pin) if (r.p) (void)hipHostFree(r.p);
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
     if (h->ev_retired) (void)hipEventDestroy(h->ev_retired);
@@ -872,6 +874,21 @@ static hipError_t stage_bunch(bp_handle *h, int first, int rows, bool train)
     return hipGetLastError();
 }
 
+// Staging set `set` with n samples (tables laid out win_start | targ_frame | nat_row) becomes the current one; everything queued
+// on h->stream so far read the other set.
+static int adopt_set(bp_handle *h, int set, int n, int D, int ctx, bool with_targ, bool nat)
+{
+    HIPCHK(hipEventRecord(h->ev_wretired, h->stream));
+    h->wretired_valid = true;
+    h->wcur = set;
+    bp_handle::Raw *rw = h->wset[set].r;
+    int *d_ws = (int *)rw[3].p;
+    h->wv.fea = (float *)rw[0].p; h->wv.tg = with_targ ? (float *)rw[1].p : nullptr; h->wv.nat = nat ? (float *)rw[2].p : nullptr;
+    h->wv.ws = d_ws; h->wv.tf = with_targ ? d_ws + n : nullptr; h->wv.nr = nat ? d_ws + 2 * (size_t)n : nullptr;
+    h->wv.D = D; h->wv.win = ctx * D;
+    return BP_OK;
+}
+
 static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ, const char *who)
 {
     if (!h || !c) return fail(BP_ERR_ARG, std::string(who) + ": null argument");
@@ -923,16 +940,37 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
         HIPCHK(hipEventRecord(h->ev_copy, cs));
         HIPCHK(hipStreamSynchronize(cs));                       // the caller may overwrite its buffers as soon as we return
         HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-        HIPCHK(hipEventRecord(h->ev_wretired, h->stream));      // everything queued so far read the other set
-        h->wretired_valid = true;
-        h->wcur = set;
-        h->wv.fea = d_fea; h->wv.tg = with_targ ? d_tg : nullptr; h->wv.nat = nat ? d_nat : nullptr;
-        h->wv.ws = d_ws; h->wv.tf = with_targ ? d_tf : nullptr; h->wv.nr = nat ? d_nr : nullptr;
-        h->wv.D = D; h->wv.win = ctx * D;
+        const int r2 = adopt_set(h, set, n, D, ctx, with_targ, nat);
+        if (r2 != BP_OK) return r2;
     }
     h->windows = true;
     h->wgen++; h->pre.valid = false; h->next_first = -1;
     h->chunk_frames = n;
+    return BP_OK;
+}
+
+// A window chunk that kernels on h->stream write (bp_wave.hip): the same staging set, tables and bookkeeping as an upload
+// without targets.  Everything queued on h->stream before the writers has finished with that set by stream order.
+int window_reserve(bp_handle *h, size_t rows_b, size_t nat_b, size_t n_samples, float **rows, float **nat, int **win_start, int **nat_row)
+{
+    { const int r = ensure_stage_tiles(h); if (r != BP_OK) return r; }
+    const int set = 1 - h->wcur;
+    int r;
+    if ((r = raw_reserve(h, set, 0, rows_b)) != BP_OK || (r = raw_reserve(h, set, 2, nat_b)) != BP_OK ||
+        (r = raw_reserve(h, set, 3, 3 * n_samples * 4)) != BP_OK)
+        return r;
+    bp_handle::Raw *rw = h->wset[set].r;
+    *rows = (float *)rw[0].p; *nat = (float *)rw[2].p;
+    *win_start = (int *)rw[3].p; *nat_row = *win_start + 2 * n_samples;
+    return BP_OK;
+}
+int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat)
+{
+    const int r = adopt_set(h, 1 - h->wcur, n_samples, fea_dim, context, false, nat);
+    if (r != BP_OK) return r;
+    h->windows = true;
+    h->wgen++; h->pre.valid = false; h->next_first = -1;
+    h->chunk_frames = n_samples;
     return BP_OK;
 }
 
@@ -1150,7 +1188,7 @@ extern "C" int bp_device_pci_bus_id(int device, char *buf, int len)
 // ------------------------------------------------------------------ inference / CV
 // Outputs of a whole chunk stay on the device until ONE device-to-host copy at the end (the reference copies and
 // synchronises per bunch and cudaMallocs per call, BP_GPU.cu:699,762-763).
-static int out_chunk_reserve(bp_handle *h, int n_frames)
+int out_chunk_reserve(bp_handle *h, int n_frames)
 {
     if ((size_t)n_frames <= h->out_chunk_frames) return BP_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1181,8 +1219,8 @@ static int forward_bunch(bp_handle *h, int first, int fb)
     return BP_OK;
 }
 
-// every bunch of the resident chunk (partial last bunch included, BP_GPU.cu:450-453), then one copy into host_out
-static int forward_chunk(bp_handle *h, int n)
+// every bunch of the resident chunk (partial last bunch included, BP_GPU.cu:450-453) into out_chunk
+int forward_resident(bp_handle *h, int n)
 {
     int r = out_chunk_reserve(h, n);
     if (r != BP_OK) return r;
@@ -1190,6 +1228,14 @@ static int forward_chunk(bp_handle *h, int n)
         const int fb = h->B > n - i ? n - i : h->B;
         if ((r = forward_bunch(h, i, fb)) != BP_OK) return r;
     }
+    return BP_OK;
+}
+
+// ... then one copy into host_out
+static int forward_chunk(bp_handle *h, int n)
+{
+    const int r = forward_resident(h, n);
+    if (r != BP_OK) return r;
     if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return BP_OK;

@@ -1,0 +1,393 @@
+// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 4: the signal layer around the network.  Noisy PCM
+// in, enhanced PCM out (bp_enhance_waves), and the same analysis alone for feature extraction (bp_wave_lps).  gfx950 only.
+//
+// One signal definition, derived from fea_dim: n_fft = 2 (fea_dim - 1), a power of two in 64 .. 2048;
+// hop = n_fft / 2; periodic Hamming window for analysis and synthesis; a sentence of n samples is padded with n_fft - hop
+// zeros in front and zeros behind, and has T = (n - 1) / hop + 2 frames, frame t covering padded samples [t hop, t hop + n_fft).
+//
+// Device layout of one call (everything in ONE host->device copy, `WaveIn`): sentence s occupies the padded samples
+// [(F_s + s) hop, (F_s + s + T_s + 1) hop) of the PCM buffer, F_s = frames of the sentences before it, so frame t of sentence s
+// -- global frame g = F_s + t -- starts at sample (g + s) hop: aligned, contiguous, no predicates.  The enhanced samples come
+// back in the same padded layout (one device->host copy) and the host trims the padding.
+//
+// Kernels (one workgroup of 256 threads = 4 wave64 per frame; the frame's FFT lives in LDS):
+//   bp_wave_analysis   window, real FFT of n_fft points as a complex FFT of n_fft/2 points + the split step, then per bin:
+//                      the noisy spectrum Y, ln(max(|Y|^2, 1e-10)), the normalised row written where bp_stage_bunch reads it
+//                      (the replicated edge rows included), the window chunk's win_start / nat_row entries
+//   bp_wave_nat        the noise-aware row of every sentence (mean of its first 6 normalised frames, PfileReader::try_nat_rows order)
+//   bp_wave_synthesis  per frame: S from the net output and Y, inverse real FFT, times the window -> frames [T][n_fft]
+//   bp_wave_overlap    per output sample: the sum over the two covering frames / the sum of squared window values (a gather: no
+//                      atomics, the same bits on every run)
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "bp_handle.h"
+
+namespace {
+
+constexpr int WAVE_THREADS = 256;
+constexpr float LN_FLOOR = -23.025850929940457f;   // ln(1e-10)
+
+// LDS index of complex point i: one float2 of padding after every 32, so that the power-of-two strides of the butterfly
+// stages (and the bit-reversed scatter) do not pile up on a few banks of ds_read_b64 / ds_write_b64.
+__device__ __forceinline__ int lp(int i) { return i + (i >> 5); }
+__host__ __device__ inline size_t lds_bytes(int M) { return (size_t)(M + M / 32 + 1) * sizeof(float2); }
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
+
+// Radix-2 decimation-in-time FFT of M points in LDS (input in bit-reversed order).  tw[j] = exp(-2 pi i j / n_fft), n_fft = 2M;
+// inverse: conjugated twiddles, no scaling.
+__device__ void fft_lds(float2 *z, int M, const float2 *__restrict__ tw, bool inverse)
+{
+    for (int h = 1; h < M; h <<= 1) {
+        const int tstep = M / h;                                // exp(-2 pi i (j%h) / (2h)) = tw[(j%h) * (2M / (2h))]
+        for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
+            const int jh = j & (h - 1), i0 = ((j - jh) << 1) + jh, i1 = i0 + h;
+            const float2 w = tw[jh * tstep];
+            const float2 a = z[lp(i0)], bb = z[lp(i1)];
+            const float2 b = inverse ? cmulc(bb, w) : cmul(bb, w);
+            z[lp(i0)] = make_float2(a.x + b.x, a.y + b.y);
+            z[lp(i1)] = make_float2(a.x - b.x, a.y - b.y);
+        }
+        __syncthreads();
+    }
+}
+
+// Sentence of global frame g: the last s with F[s] <= g (F[n_sent] = all frames).  Uniform per workgroup.
+__device__ __forceinline__ int sentence_of(const int *__restrict__ F, int n_sent, int g)
+{
+    int lo = 0, hi = n_sent - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (F[mid] <= g) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+}  // namespace
+
+struct WaveAnaArgs {
+    const float *pcm; const float *win; const float2 *tw; const int *F; const float *mean, *inv_std;
+    int n_sent, log2M, D, hop, ctx, toff;
+    float2 *Y;            // [frames][D] noisy spectrum, or null
+    float *lps;           // [frames][D] un-normalised LPS, or null
+    float *rows;          // staged normalised rows [frames + n_sent (ctx - 1)][D], or null
+    int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
+};
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_analysis(const WaveAnaArgs a)
+{
+    extern __shared__ float2 z[];
+    const int g = blockIdx.x, M = 1 << a.log2M, N = 2 * M, tid = threadIdx.x;
+    const int s = sentence_of(a.F, a.n_sent, g), t = g - a.F[s], T = a.F[s + 1] - a.F[s];
+    const float *x = a.pcm + (size_t)(g + s) * a.hop;
+    // windowed samples as M complex points z[m] = (x[2m], x[2m+1]), scattered to bit-reversed positions; 16-byte loads
+    for (int q = tid; q < N / 4; q += blockDim.x) {
+        const float4 v = *reinterpret_cast<const float4 *>(x + 4 * q), w = *reinterpret_cast<const float4 *>(a.win + 4 * q);
+        const int m0 = 2 * q, m1 = 2 * q + 1;
+        z[lp((int)(__brev((unsigned)m0) >> (32 - a.log2M)))] = make_float2(v.x * w.x, v.y * w.y);
+        z[lp((int)(__brev((unsigned)m1) >> (32 - a.log2M)))] = make_float2(v.z * w.z, v.w * w.w);
+    }
+    __syncthreads();
+    fft_lds(z, M, a.tw, false);
+    // split step: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i, k = 0 .. M
+    const int base = a.F[s] + s * (a.ctx - 1);          // first staged row of the sentence
+    for (int k = tid; k <= M; k += blockDim.x) {
+        const float2 zk = z[lp(k & (M - 1))], zm = z[lp((M - k) & (M - 1))];
+        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+        const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+        const float2 X = k == 0 ? make_float2(zk.x + zk.y, 0.0f) : k == M ? make_float2(zk.x - zk.y, 0.0f)
+                                                                         : make_float2(e.x + (a.tw[k].x * o.x - a.tw[k].y * o.y),
+                                                                                       e.y + (a.tw[k].x * o.y + a.tw[k].y * o.x));
+        const size_t gi = (size_t)g * a.D + k;
+        if (a.Y) a.Y[gi] = X;
+        const float p = X.x * X.x + X.y * X.y;
+        const float l = p > 1e-10f ? logf(p) : LN_FLOOR;
+        if (a.lps) a.lps[gi] = l;
+        if (a.rows) {
+            const float v = (l - a.mean[k]) * a.inv_std[k];
+            // staged row base + u holds frame clamp(u - toff, 0, T-1): frame t at u = t + toff, the first frame also at the
+            // toff rows in front of it, the last one also at the ctx-1-toff rows behind it
+            a.rows[(size_t)(base + t + a.toff) * a.D + k] = v;
+            if (t == 0) for (int u = 0; u < a.toff; ++u) a.rows[(size_t)(base + u) * a.D + k] = v;
+            if (t == T - 1) for (int u = T + a.toff; u < T + a.ctx - 1; ++u) a.rows[(size_t)(base + u) * a.D + k] = v;
+        }
+    }
+    if (a.rows && tid == 0) { a.win_start[g] = base + t; if (a.nat_row) a.nat_row[g] = s; }
+}
+
+// nat[s][k] = ((((v0 + v1) + v2) + v3) + v4 + v5) / 6 over the sentence's first 6 normalised frames, frame f clamped to T-1
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_nat(const float *__restrict__ rows, const int *__restrict__ F, int D, int ctx,
+                                                         int toff, float *__restrict__ nat)
+{
+    const int kb = (D + WAVE_THREADS - 1) / WAVE_THREADS, s = blockIdx.x / kb, k = (blockIdx.x % kb) * WAVE_THREADS + threadIdx.x;
+    if (k >= D) return;
+    const int T = F[s + 1] - F[s], nf = T < 6 ? T : 6;
+    const float *r = rows + (size_t)(F[s] + s * (ctx - 1) + toff) * D + k;
+    float acc = 0.0f;
+    for (int f = 0; f < 6; ++f) { const float v = r[(size_t)(f < nf ? f : nf - 1) * D]; acc = f == 0 ? v : acc + v; }
+    nat[(size_t)s * D + k] = acc / 6.0f;
+}
+
+struct WaveSynArgs {
+    const float *out; int ldo, out_col;     // net outputs [frames][ldo], columns [out_col, out_col + D)
+    const float2 *Y; const float *win; const float2 *tw;
+    int log2M, D, target;
+    float *frames;                          // [frames][n_fft]: window * irfft(S)
+};
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_synthesis(const WaveSynArgs a)
+{
+    extern __shared__ float2 z[];
+    const int g = blockIdx.x, M = 1 << a.log2M, N = 2 * M, tid = threadIdx.x;
+    float2 *S = z + lds_bytes(M) / sizeof(float2);      // S[0 .. M], unpadded (read twice below, written once)
+    const float *o = a.out + (size_t)g * a.ldo + a.out_col;
+    const float2 *Y = a.Y + (size_t)g * a.D;
+    for (int k = tid; k <= M; k += blockDim.x) {
+        const float2 y = Y[k];
+        const float ok = o[k];
+        float2 v;
+        if (a.target == BP_WAVE_MASK) v = make_float2(ok * y.x, ok * y.y);
+        else {
+            const float r = sqrtf(y.x * y.x + y.y * y.y), m = expf(0.5f * ok);
+            v = r > 0.0f ? make_float2(m * (y.x / r), m * (y.y / r)) : make_float2(m, 0.0f);
+        }
+        if (k == 0 || k == M) v.y = 0.0f;               // (irfft ignores the imaginary part of DC and Nyquist)
+        S[k] = v;
+    }
+    __syncthreads();
+    // inverse split step: Z[k] = E[k] + i O[k], E = (S[k] + conj S[M-k]) / 2, O = (S[k] - conj S[M-k]) conj(W^k) / 2
+    for (int k = tid; k < M; k += blockDim.x) {
+        const float2 sk = S[k], sm = S[M - k];
+        const float2 e = make_float2(0.5f * (sk.x + sm.x), 0.5f * (sk.y - sm.y));
+        const float2 d = make_float2(0.5f * (sk.x - sm.x), 0.5f * (sk.y + sm.y));
+        const float2 od = cmulc(d, a.tw[k]);
+        z[lp((int)(__brev((unsigned)k) >> (32 - a.log2M)))] = make_float2(e.x - od.y, e.y + od.x);
+    }
+    __syncthreads();
+    fft_lds(z, M, a.tw, true);
+    const float sc = 1.0f / (float)M;
+    float *fr = a.frames + (size_t)g * N;
+    for (int q = tid; q < N / 4; q += blockDim.x) {
+        const float2 z0 = z[lp(2 * q)], z1 = z[lp(2 * q + 1)];
+        const float4 w = *reinterpret_cast<const float4 *>(a.win + 4 * q);
+        *reinterpret_cast<float4 *>(fr + 4 * q) = make_float4(z0.x * sc * w.x, z0.y * sc * w.y, z1.x * sc * w.z, z1.y * sc * w.w);
+    }
+}
+
+// Segment t >= 1 of a sentence (padded samples [t hop, (t+1) hop)) is covered by frame t (offset k) and frame t-1 (offset
+// hop + k); segment 0 is front padding.  One workgroup per global frame, 16-byte accesses.
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_overlap(const float *__restrict__ frames, const float *__restrict__ win,
+                                                             const int *__restrict__ F, int n_sent, int hop, float *__restrict__ pcm)
+{
+    const int g = blockIdx.x, s = sentence_of(F, n_sent, g);
+    if (g == F[s]) return;
+    const int N = 2 * hop;
+    const float *cur = frames + (size_t)g * N, *prev = frames + (size_t)(g - 1) * N + hop;
+    float *dst = pcm + (size_t)(g + s) * hop;
+    for (int q = threadIdx.x; q < hop / 4; q += blockDim.x) {
+        const float4 a = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(prev + 4 * q);
+        const float4 wa = *reinterpret_cast<const float4 *>(win + 4 * q), wb = *reinterpret_cast<const float4 *>(win + hop + 4 * q);
+        *reinterpret_cast<float4 *>(dst + 4 * q) = make_float4((a.x + b.x) / (wa.x * wa.x + wb.x * wb.x), (a.y + b.y) / (wa.y * wa.y + wb.y * wb.y),
+                                                               (a.z + b.z) / (wa.z * wa.z + wb.z * wb.z), (a.w + b.w) / (wa.w * wa.w + wb.w * wb.w));
+    }
+}
+
+// ------------------------------------------------------------------ host side
+namespace {
+
+int log2_fft(int fea_dim)
+{
+    if (fea_dim < 33 || fea_dim > 1025) return -1;
+    const int n = 2 * (fea_dim - 1);
+    if (n & (n - 1)) return -1;
+    int l = 0;
+    while ((1 << l) < n) ++l;
+    return l - 1;                                        // log2 of M = n_fft / 2
+}
+
+// Frame plan of a call: T_s per sentence, F = prefix sums.  Checked before any device work.
+struct Plan {
+    int M, N, hop, log2M, n_sent;
+    std::vector<int> F;                                  // [n_sent + 1]
+    size_t frames, padded;                               // frames of the call, padded samples of the PCM buffer
+};
+int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, Plan &p)
+{
+    p.log2M = log2_fft(fea_dim);
+    if (p.log2M < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (n_sent < 1 || !sent_len || !pcm) return fail(BP_ERR_ARG, std::string(who) + ": no sentences or null pointer");
+    p.M = 1 << p.log2M; p.N = 2 * p.M; p.hop = p.M; p.n_sent = n_sent;
+    p.F.assign((size_t)n_sent + 1, 0);
+    size_t f = 0;
+    for (int s = 0; s < n_sent; ++s) {
+        if (sent_len[s] < 1) return fail(BP_ERR_ARG, std::string(who) + ": empty sentence " + std::to_string(s));
+        f += (size_t)((sent_len[s] - 1) / p.hop + 2);
+        if (f > (size_t)INT32_MAX / 2) return fail(BP_ERR_ARG, std::string(who) + ": too many frames in one call");
+        p.F[s + 1] = (int)f;
+    }
+    p.frames = f;
+    p.padded = (f + (size_t)n_sent) * p.hop;             // sentence s: T_s + 1 segments of hop samples
+    return BP_OK;
+}
+
+// Grow-only buffers (device or pinned host).
+int grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st)
+{
+    if (bytes <= r.bytes) return BP_OK;
+    if (r.p) {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)(pinned ? hipHostFree(r.p) : hipFree(r.p)); r.p = nullptr; r.bytes = 0;
+    }
+    const size_t want = bytes + bytes / 4 + 4096;
+    const hipError_t e = pinned ? hipHostMalloc(&r.p, want) : hipMalloc(&r.p, want);
+    if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("wave buffers: ") + hipGetErrorString(e));
+    r.bytes = want;
+    return BP_OK;
+}
+
+// The single host->device block: F | mean | inv_std | window | twiddles | padded PCM, each 256-byte aligned.
+struct WaveIn { size_t F, mean, istd, win, tw, pcm, bytes; };
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+WaveIn wave_in_layout(const Plan &p, int D)
+{
+    WaveIn w;
+    w.F = 0; w.mean = al256(((size_t)p.n_sent + 1) * 4); w.istd = w.mean + al256((size_t)D * 4); w.win = w.istd + al256((size_t)D * 4);
+    w.tw = w.win + al256((size_t)p.N * 4); w.pcm = w.tw + al256((size_t)(p.M + 1) * 8); w.bytes = w.pcm + al256(p.padded * 4);
+    return w;
+}
+// Fill it on the host: window and twiddles computed in double and rounded once; the sentences at their padded places.
+void wave_in_fill(char *hb, const WaveIn &w, const Plan &p, int D, const float *mean, const float *inv_std, const int *sent_len,
+                  const float *pcm)
+{
+    memcpy(hb + w.F, p.F.data(), p.F.size() * 4);
+    if (mean) { memcpy(hb + w.mean, mean, (size_t)D * 4); memcpy(hb + w.istd, inv_std, (size_t)D * 4); }
+    float *win = (float *)(hb + w.win);
+    float2 *tw = (float2 *)(hb + w.tw);
+    const double pi2 = 6.283185307179586476925286766559;
+    for (int k = 0; k < p.N; ++k) win[k] = (float)(0.54 - 0.46 * cos(pi2 * k / p.N));
+    for (int k = 0; k <= p.M; ++k) tw[k] = make_float2((float)cos(pi2 * k / p.N), (float)-sin(pi2 * k / p.N));
+    float *x = (float *)(hb + w.pcm);
+    memset(x, 0, p.padded * 4);
+    size_t src = 0;
+    for (int s = 0; s < p.n_sent; ++s) {
+        memcpy(x + (size_t)(p.F[s] + s + 1) * p.hop, pcm + src, (size_t)sent_len[s] * 4);
+        src += (size_t)sent_len[s];
+    }
+}
+
+}  // namespace
+
+extern "C" int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_len, const float *pcm, float *lps)
+{
+    Plan p;
+    { const int r = plan_waves("bp_wave_lps", fea_dim, n_sent, sent_len, pcm, p); if (r != BP_OK) return r; }
+    if (!lps) return fail(BP_ERR_ARG, "bp_wave_lps: null output");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_wave_lps: device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    const WaveIn w = wave_in_layout(p, fea_dim);
+    const size_t out_b = p.frames * fea_dim * 4;
+    std::vector<char> hb(w.bytes);
+    wave_in_fill(hb.data(), w, p, fea_dim, nullptr, nullptr, sent_len, pcm);
+    hipStream_t st = nullptr;
+    char *d = nullptr;
+    int rc = BP_OK;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, w.bytes + out_b);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        WaveAnaArgs a; memset(&a, 0, sizeof(a));
+        a.pcm = (const float *)(d + w.pcm); a.win = (const float *)(d + w.win); a.tw = (const float2 *)(d + w.tw); a.F = (const int *)(d + w.F);
+        a.n_sent = n_sent; a.log2M = p.log2M; a.D = fea_dim; a.hop = p.hop; a.ctx = 1;
+        a.lps = (float *)(d + w.bytes);
+        hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)p.frames), dim3(WAVE_THREADS), lds_bytes(p.M), st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(lps, d + w.bytes, out_b, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_wave_lps: ") + hipGetErrorString(e));
+    if (d) (void)hipFree(d);
+    if (st) (void)hipStreamDestroy(st);
+    return rc;
+}
+
+extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *c, float *out_pcm, float *out_net)
+{
+    if (!h || !c) return fail(BP_ERR_ARG, "bp_enhance_waves: null handle or chunk");
+    Plan p;
+    { const int r = plan_waves("bp_enhance_waves", fea_dim, c->n_sent, c->sent_len, c->pcm, p); if (r != BP_OK) return r; }
+    if (!out_pcm || !c->mean || !c->inv_std) return fail(BP_ERR_ARG, "bp_enhance_waves: null pointer");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_enhance_waves: not on an attached data-parallel handle");
+    const int D = fea_dim, ctx = c->context, toff = c->targ_offset, L = h->L, sL = h->s[L - 1];
+    if (ctx < 1 || toff < 0 || toff >= ctx) return fail(BP_ERR_ARG, "bp_enhance_waves: need context >= 1 and 0 <= targ_offset < context");
+    const bool nat = (long)h->s[0] == (long)(ctx + 1) * D;
+    if (!nat && (long)h->s[0] != (long)ctx * D)
+        return fail(BP_ERR_ARG, "bp_enhance_waves: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
+    if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_enhance_waves: target must be BP_WAVE_LPS or BP_WAVE_MASK");
+    if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_enhance_waves: out_col + fea_dim exceeds layersizes[last]");
+    const size_t rows = p.frames + (size_t)c->n_sent * (ctx - 1);
+    if (rows > (size_t)h->cap)
+        return fail(BP_ERR_ARG, "bp_enhance_waves: " + std::to_string(rows) + " rows (frames + replicated edge rows) exceed the chunk capacity " +
+                                std::to_string(h->cap));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int n = (int)p.frames, N = p.N;
+    const WaveIn w = wave_in_layout(p, D);
+    const size_t y_b = p.frames * D * sizeof(float2), fr_b = p.frames * N * 4, pcm_b = p.padded * 4;
+    int r;
+    if ((r = grow(h->wave[0], w.bytes, false, h->stream)) != BP_OK || (r = grow(h->wave[1], y_b, false, h->stream)) != BP_OK ||
+        (r = grow(h->wave[2], fr_b, false, h->stream)) != BP_OK || (r = grow(h->wave[3], pcm_b, false, h->stream)) != BP_OK ||
+        (r = grow(h->wave_pin[0], w.bytes, true, h->stream)) != BP_OK || (r = grow(h->wave_pin[1], pcm_b, true, h->stream)) != BP_OK)
+        return r;
+    float *rows_d, *nat_d; int *ws_d, *nr_d;
+    if ((r = window_reserve(h, rows * D * 4, nat ? (size_t)c->n_sent * D * 4 : 0, p.frames, &rows_d, &nat_d, &ws_d, &nr_d)) != BP_OK) return r;
+    if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;      // (forward_resident would; growing it here keeps its sync out of the sequence)
+    // The pinned blocks are reused by the next call: the previous call ended in a synchronisation, so nothing still reads them.
+    char *hin = (char *)h->wave_pin[0].p, *din = (char *)h->wave[0].p;
+    wave_in_fill(hin, w, p, D, c->mean, c->inv_std, c->sent_len, c->pcm);
+    HIPCHK(hipMemcpyAsync(din, hin, w.bytes, hipMemcpyHostToDevice, h->stream));
+    const float *win = (const float *)(din + w.win);
+    const float2 *tw = (const float2 *)(din + w.tw);
+    const int *F = (const int *)(din + w.F);
+    float2 *Y = (float2 *)h->wave[1].p;
+    {
+        WaveAnaArgs a; memset(&a, 0, sizeof(a));
+        a.pcm = (const float *)(din + w.pcm); a.win = win; a.tw = tw; a.F = F;
+        a.mean = (const float *)(din + w.mean); a.inv_std = (const float *)(din + w.istd);
+        a.n_sent = c->n_sent; a.log2M = p.log2M; a.D = D; a.hop = p.hop; a.ctx = ctx; a.toff = toff;
+        a.Y = Y; a.rows = rows_d; a.win_start = ws_d; a.nat_row = nat ? nr_d : nullptr;
+        hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(p.M), h->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (nat) {
+        hipLaunchKernelGGL(bp_wave_nat, dim3((unsigned)(((D + WAVE_THREADS - 1) / WAVE_THREADS) * c->n_sent)), dim3(WAVE_THREADS), 0, h->stream,
+                           (const float *)rows_d, F, D, ctx, toff, nat_d);
+        HIPCHK(hipGetLastError());
+    }
+    window_adopt(h, n, D, ctx, nat);
+    if ((r = forward_resident(h, n)) != BP_OK) return r;
+    {
+        WaveSynArgs a; memset(&a, 0, sizeof(a));
+        a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = c->out_col;
+        a.Y = Y; a.win = win; a.tw = tw; a.log2M = p.log2M; a.D = D; a.target = c->target; a.frames = (float *)h->wave[2].p;
+        hipLaunchKernelGGL(bp_wave_synthesis, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(p.M) + (size_t)(p.M + 1) * sizeof(float2), h->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(bp_wave_overlap, dim3((unsigned)n), dim3(WAVE_THREADS), 0, h->stream, (const float *)h->wave[2].p, win, F, c->n_sent, p.hop,
+                       (float *)h->wave[3].p);
+    HIPCHK(hipGetLastError());
+    float *hout = (float *)h->wave_pin[1].p;
+    HIPCHK(hipMemcpyAsync(hout, h->wave[3].p, pcm_b, hipMemcpyDeviceToHost, h->stream));
+    if (out_net) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    size_t dst = 0;
+    for (int s = 0; s < c->n_sent; ++s) {
+        memcpy(out_pcm + dst, hout + (size_t)(p.F[s] + s + 1) * p.hop, (size_t)c->sent_len[s] * 4);
+        dst += (size_t)c->sent_len[s];
+    }
+    if (out_net)
+        for (int j = 0; j < n; ++j) memcpy(out_net + (size_t)j * sL, h->host_out + (size_t)j * h->ld[L - 1], sizeof(float) * sL);
+    return BP_OK;
+}

@@ -1,0 +1,182 @@
+// bpenhance.cpp -- waveform enhancement: noisy WAV in, enhanced WAV out, on the MI355X through bp_enhance_waves (analysis,
+// the forward of bpforward, resynthesis, overlap-add; include/bp_c_api.h).
+//
+//   bpenhance norm_file=x.norm initwts_file=mlp.N.wts layersizes=1548,2048,2048,2048,129 fea_dim=129 fea_context=11
+//             targ_offset=5 (wav_list=<"in.wav out.wav" per line> | in_wav=noisy.wav out_wav=enh.wav)
+//             [wave_target=lps|mask] [out_col=0] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2] [bunchsize=1024]
+//             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
+//             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
+//
+// As many sentences go into one call as fit traincache rows (frames + context-1 replicated edge rows per sentence).  The
+// output is PCM16 at the input's sample rate, rounded to nearest and clipped.  Every input is read and checked before the
+// device is used.  Errors: message + exit(0), success: return 1 (reference convention).
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../../include/BP_GPU.h"
+#include "wav_io.h"
+#include "wts_io.h"
+
+static std::string trim(std::string s)
+{
+    while (!s.empty() && (s.back() == '\n' || s.back() == '\r' || s.back() == ' ' || s.back() == '\t')) s.pop_back();
+    size_t i = 0;
+    while (i < s.size() && (s[i] == ' ' || s[i] == '\t')) ++i;
+    return s.substr(i);
+}
+
+int main(int argc, char **argv)
+{
+    std::string norm_file, wts_file, list, in_wav, out_wav;
+    int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
+    int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
+    float vis = 0.f, hid = 0.f;
+    for (int i = 1; i < argc; ++i) {
+        char *eq = strchr(argv[i], '=');
+        if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
+        const std::string k(argv[i], eq - argv[i]), v(eq + 1);
+        if (k == "norm_file") norm_file = v; else if (k == "initwts_file") wts_file = v;
+        else if (k == "wav_list") list = v; else if (k == "in_wav") in_wav = v; else if (k == "out_wav") out_wav = v;
+        else if (k == "fea_dim") fea_dim = atoi(v.c_str()); else if (k == "fea_context") ctx = atoi(v.c_str());
+        else if (k == "targ_offset") toff = atoi(v.c_str()); else if (k == "dropoutflag") dropoutflag = atoi(v.c_str());
+        else if (k == "visible_omit") vis = (float)atof(v.c_str()); else if (k == "hid_omit") hid = (float)atof(v.c_str());
+        else if (k == "bunchsize") bunch = atoi(v.c_str()); else if (k == "traincache") cache = atoi(v.c_str());
+        else if (k == "activation") activation = v == "sigmoid" ? 1 : 0; else if (k == "device") device = atoi(v.c_str());
+        else if (k == "compute") compute = v == "bf16" ? 1 : 0;
+        else if (k == "out_col") out_col = atoi(v.c_str());
+        else if (k == "wave_target") {
+            if (v == "lps") target = BP_WAVE_LPS; else if (v == "mask") target = BP_WAVE_MASK;
+            else { printf("wave_target: %s is not lps or mask\n", v.c_str()); exit(0); }
+        }
+        // output layer (.wts files do not record it): the keys and checks of bptrain
+        else if (k == "output_act") {
+            if (v == "linear") out_act = 0; else if (v == "sigmoid") out_act = 1;
+            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
+        } else if (k == "output_linear_dims") {
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
+            out_lin = (int)n;
+        } else if (k == "output_loss") {
+            if (v == "xent") out_loss = 0; else if (v == "mse") out_loss = 1;
+            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
+        }
+        else if (k == "layersizes") {
+            size_t pos = 0;
+            while (L < MAXLAYER) {
+                const size_t c = v.find(',', pos);
+                ls[L++] = atoi(v.substr(pos, c == std::string::npos ? c : c - pos).c_str());
+                if (c == std::string::npos) break;
+                pos = c + 1;
+            }
+        }
+        else { printf("bpenhance: unknown key %s\n", k.c_str()); exit(0); }
+    }
+    if (L < 2 || L > MAXLAYER - 1 || fea_dim < 1 || ctx < 1 || toff < 0 || toff >= ctx || cache < 1 || cache > MAXCACHEFRAME || bunch < 1) {
+        printf("bpenhance: need layersizes (2..%d sizes), fea_dim, fea_context, 0 <= targ_offset < fea_context, traincache <= %d\n", MAXLAYER - 1, MAXCACHEFRAME);
+        exit(0);
+    }
+    if (norm_file.empty() || wts_file.empty()) { printf("bpenhance: need norm_file and initwts_file\n"); exit(0); }
+    if (list.empty() == (in_wav.empty() || out_wav.empty())) { printf("bpenhance: need wav_list, or in_wav and out_wav\n"); exit(0); }
+    const int n_fft = 2 * (fea_dim - 1), hop = n_fft / 2;
+    if (fea_dim < 33 || fea_dim > 1025 || (n_fft & (n_fft - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
+    if (ls[0] != ctx * fea_dim && ls[0] != (ctx + 1) * fea_dim) { printf("bpenhance: layersizes[0] must be fea_context*fea_dim (+ fea_dim with a NAT block)\n"); exit(0); }
+    if (out_col < 0 || out_col + fea_dim > ls[L - 1]) { printf("bpenhance: out_col + fea_dim exceeds layersizes[last]\n"); exit(0); }
+
+    // ---- inputs (all read and checked before the device is used)
+    std::vector<std::string> ins, outs;
+    if (!list.empty()) {
+        FILE *fl = fopen(list.c_str(), "rt");
+        if (!fl) { printf("can not open wav list: %s\n", list.c_str()); exit(0); }
+        char line[8192];
+        while (fgets(line, sizeof(line), fl)) {
+            const std::string t = trim(line);
+            if (t.empty()) continue;
+            const size_t sp = t.find_first_of(" \t");
+            if (sp == std::string::npos) { printf("wav list %s: line \"%s\" needs an input and an output file\n", list.c_str(), t.c_str()); exit(0); }
+            ins.push_back(t.substr(0, sp)); outs.push_back(trim(t.substr(sp)));
+        }
+        fclose(fl);
+        if (ins.empty()) { printf("bpenhance: %s lists no wav file\n", list.c_str()); exit(0); }
+    } else { ins.push_back(in_wav); outs.push_back(out_wav); }
+    const int ns = (int)ins.size();
+    std::vector<std::vector<float>> waves(ns);
+    std::vector<int> rates(ns);
+    for (int s = 0; s < ns; ++s) {
+        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
+        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+        const size_t rows = (waves[s].size() - 1) / hop + 2 + ctx - 1;
+        if (rows > (size_t)cache) { printf("%s: %zu rows exceed traincache=%d (one sentence per call at most)\n", ins[s].c_str(), rows, cache); exit(0); }
+    }
+    std::vector<float> mean(fea_dim), istd(fea_dim);
+    {
+        // normalisation file: 1 header line, fea_dim means, 1 header line, fea_dim inverse std (as PfileReader reads it)
+        FILE *fn = fopen(norm_file.c_str(), "rt");
+        if (!fn) { printf("can not open normalization file: %s\n", norm_file.c_str()); exit(0); }
+        char buff[256];
+        bool ok = fgets(buff, sizeof(buff), fn) != nullptr;
+        for (int j = 0; ok && j < fea_dim; ++j) { ok = fgets(buff, sizeof(buff), fn) != nullptr; mean[j] = (float)atof(buff); }
+        ok = ok && fgets(buff, sizeof(buff), fn) != nullptr;
+        for (int j = 0; ok && j < fea_dim; ++j) { ok = fgets(buff, sizeof(buff), fn) != nullptr; istd[j] = (float)atof(buff); }
+        fclose(fn);
+        if (!ok) { printf("normalization file too short\n"); exit(0); }
+    }
+    std::vector<std::vector<float>> Wv(L), Bv(L);
+    float *weights[MAXLAYER] = {0}, *bias[MAXLAYER] = {0};
+    for (int i = 1; i < L; ++i) { Wv[i].assign((size_t)ls[i] * ls[i - 1], 0.f); Bv[i].assign(ls[i], 0.f); weights[i] = Wv[i].data(); bias[i] = Bv[i].data(); }
+    FILE *fi = fopen(wts_file.c_str(), "rb");
+    if (!fi) { printf("can not open initial weights file: %s\n", wts_file.c_str()); exit(0); }
+    const std::string err = bp::read_weights(fi, L, ls, weights, bias);
+    fclose(fi);
+    if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+
+    bp_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.gpu_used = 1; cfg.numlayers = L;
+    for (int i = 0; i < L; ++i) cfg.layersizes[i] = ls[i];
+    cfg.bunchsize = bunch; cfg.lrate = 0.f; cfg.momentum = 0.f; cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid;
+    cfg.activation = activation; cfg.device = device; cfg.compute_dtype = compute; cfg.max_chunk_frames = cache;
+    bp_handle *h = nullptr;
+    if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+
+    // ---- as many sentences per call as fit the chunk
+    std::vector<float> pcm, out;
+    std::vector<int> lens;
+    size_t samples = 0;
+    for (int s0 = 0; s0 < ns;) {
+        int s1 = s0;
+        size_t rows = 0;
+        pcm.clear(); lens.clear();
+        while (s1 < ns) {
+            const size_t r = (waves[s1].size() - 1) / hop + 2 + ctx - 1;
+            if (rows + r > (size_t)cache) break;
+            rows += r;
+            pcm.insert(pcm.end(), waves[s1].begin(), waves[s1].end());
+            lens.push_back((int)waves[s1].size());
+            ++s1;
+        }
+        out.resize(pcm.size());
+        bp_wave_chunk c;
+        memset(&c, 0, sizeof(c));
+        c.n_sent = s1 - s0; c.sent_len = lens.data(); c.pcm = pcm.data(); c.context = ctx; c.targ_offset = toff;
+        c.mean = mean.data(); c.inv_std = istd.data(); c.target = target; c.out_col = out_col;
+        if (bp_enhance_waves(h, fea_dim, &c, out.data(), nullptr) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        size_t off = 0;
+        for (int s = s0; s < s1; ++s) {
+            const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
+            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+            off += waves[s].size();
+        }
+        samples += pcm.size();
+        s0 = s1;
+    }
+    bp_destroy(h);
+    printf("bpenhance: %zu samples of %d sentences enhanced\n", samples, ns);
+    return 1;
+}

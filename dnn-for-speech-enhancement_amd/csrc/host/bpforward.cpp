@@ -25,9 +25,8 @@
 
 #include "../../../include/BP_GPU.h"
 #include "pfile_reader.h"
+#include "pfile_writer.h"
 #include "wts_io.h"
-
-static inline uint32_t be32(uint32_t v) { return __builtin_bswap32(v); }
 
 int main(int argc, char **argv)
 {
@@ -104,18 +103,14 @@ int main(int argc, char **argv)
     if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
     if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
 
-    // ---- output Pfile: header, records in reader order, sentence table
-    FILE *fo = fopen(out_file.c_str(), "wb");
-    if (!fo) { printf("can not open output file: %s\n", out_file.c_str()); exit(0); }
-    std::vector<char> header(32768, 0);
-    fwrite(header.data(), 1, header.size(), fo);                       // rewritten at the end with the counts
+    // ---- output Pfile: records in reader order
     const std::vector<int> &fbs = reader.frames_before_sent();         // end offset (frames) of every sentence
     const int nsent = en - st + 1;
-    std::vector<uint32_t> per_sent(nsent, 0);
+    bp::PfileWriter pw;
+    if (!pw.open(out_file, nsent, sL)) { printf("can not open output file: %s\n", out_file.c_str()); exit(0); }
     const bp::PfileReader::Plan plan = reader.plan_inference(st, en);    // every window exactly once (no training-style cut losses)
     bp::PfileReader::WindowChunk w;
     std::vector<float> out;
-    std::vector<uint32_t> rec(2 + sL);
     unsigned total = 0;
     for (int c = 0; c < (int)plan.chunk_frame_st.size(); ++c) {
         const int n = reader.read_chunk_windows(plan, c, false, w);
@@ -131,21 +126,11 @@ int main(int argc, char **argv)
             const int gframe = plan.chunk_frame_st[c] + w.win_start[i];            // first frame of the window, file-global
             const int s = (int)(std::upper_bound(fbs.begin(), fbs.end(), gframe) - fbs.begin());
             const int s_begin = s == 0 ? 0 : fbs[s - 1];
-            rec[0] = be32((uint32_t)(s - st)); rec[1] = be32((uint32_t)(gframe - s_begin + toff));
-            for (int k = 0; k < sL; ++k) { uint32_t u; memcpy(&u, &out[(size_t)i * sL + k], 4); rec[2 + k] = be32(u); }
-            fwrite(rec.data(), 4, rec.size(), fo);
-            if (s - st >= 0 && s - st < nsent) per_sent[s - st]++;
+            pw.add(s - st, gframe - s_begin + toff, &out[(size_t)i * sL]);
             ++total;
         }
     }
-    uint32_t cum = 0, v = be32(0);
-    fwrite(&v, 4, 1, fo);
-    for (int s = 0; s < nsent; ++s) { cum += per_sent[s]; v = be32(cum); fwrite(&v, 4, 1, fo); }
-    snprintf(header.data(), header.size(), "-pfile_header version 0 size 32768\n-num_sentences %d\n-num_frames %u\n-first_feature_column 2\n-num_features %d\n-end\n",
-             nsent, total, sL);
-    fseek(fo, 0, SEEK_SET);
-    fwrite(header.data(), 1, header.size(), fo);
-    fclose(fo);
+    pw.close();
     bp_destroy(h);
     printf("bpforward: %u frames of %d sentences enhanced -> %s\n", total, nsent, out_file.c_str());
     return 1;

@@ -182,6 +182,34 @@ int bp_cv_chunk_windows(bp_handle *h, const bp_window_chunk *c, float *sq_err_su
 int bp_forward_windows(bp_handle *h, const bp_window_chunk *c, float *out);         /* = bp_forward: out[n_samples][sL] (enhancement) */
 
 /* ------------------------------------------------------------------------------------
+ * Waveform enhancement (no reference counterpart: the reference reads and writes log-power-spectrum Pfiles made by outside
+ * tools).  One signal definition, derived from fea_dim: n_fft = 2*(fea_dim-1), a power of two from 64
+ * to 2048 (else BP_ERR_ARG); hop = n_fft/2; periodic Hamming window w[k] = 0.54 - 0.46 cos(2 pi k / n_fft) for analysis and
+ * synthesis; a sentence of n >= 1 samples is padded with n_fft-hop zeros in front and zeros behind and has
+ * T = (n-1)/hop + 2 frames; samples are floats in int16 units; LPS = ln(max(|Y_k|^2, 1e-10)), k = 0 .. fea_dim-1.
+ *
+ * bp_enhance_waves: analysis -> (lps - mean) * inv_std -> the forward of bp_forward_windows on windows of `context` frames
+ * whose output frame sits at targ_offset, the first and last frame of each sentence REPLICATED so that every frame gets an
+ * output (bpforward drops edge windows instead) [+ the noise-aware block: mean of the sentence's first 6 normalised frames,
+ * iff layersizes[0] == (context+1)*fea_dim] -> output columns o = [out_col, out_col+fea_dim) of the post-activation
+ * output -> S = exp(o/2) Y/|Y| (BP_WAVE_LPS; phasor 1 where |Y| = 0) or S = o Y (BP_WAVE_MASK: amplitude gain) ->
+ * least-squares overlap-add, sum_t w irfft(S_t) / sum_t w^2, trimmed to n samples.  out_pcm holds sum(sent_len) samples,
+ * out_net (NULL or [sum T][layersizes[L-1]]) the net outputs per frame.  The frames of the call plus n_sent*(context-1)
+ * replicated rows must fit the chunk capacity (max_chunk_frames).  The call becomes the handle's resident window chunk (as
+ * after bp_forward_windows); training afterwards is unaffected.  Every argument is checked before the device is touched;
+ * BP_ERR_STATE on a data-parallel-attached handle.  The same bits on every run.
+ * bp_wave_lps: the analysis alone (no handle): lps[sum T][fea_dim], un-normalised. */
+enum { BP_WAVE_LPS = 0, BP_WAVE_MASK = 1 };
+typedef struct bp_wave_chunk {
+    int n_sent; const int *sent_len; const float *pcm;   /* sentences back to back, int16 units */
+    int context, targ_offset;                           /* as trained; NAT iff layersizes[0] == (context+1)*fea_dim */
+    const float *mean, *inv_std;                        /* [fea_dim], the norm file */
+    int target, out_col;                                /* BP_WAVE_LPS | BP_WAVE_MASK; first output column used */
+} bp_wave_chunk;
+int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *c, float *out_pcm, float *out_net);
+int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_len, const float *pcm, float *lps);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias
