@@ -4,5 +4,6 @@
 (The directory name contains '-', import it through `dnnse_amd.py` at the repo root.)"""
 from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMBOLS, MAXLAYER, MAXCACHEFRAME,  # noqa: F401
                      Rendezvous, device_count, device_pci_bus_id, wave_lps, WAVE_LPS, WAVE_MASK,
-                     BPWaveChunk)
+                     BPWaveChunk, BPMixCorpus, MIXTURE_DTYPE, MIX_TARGETS, MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM,
+                     MIX_LPS_IBM, mix_plan, mix_shuffle)
 from .weights_init import glorot_net  # noqa: F401

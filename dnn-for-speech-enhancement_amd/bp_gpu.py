@@ -37,8 +37,14 @@ ABI_SYMBOLS = [
     "bp_rdv_open", "bp_rdv_barrier", "bp_rdv_allgather", "bp_rdv_close", "bp_device_pci_bus_id", "bp_host_register", "bp_host_unregister",
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
     "bp_enhance_waves", "bp_wave_lps",
+    "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
+MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
+MIX_TARGETS = {"lps": MIX_LPS, "irm": MIX_IRM, "ibm": MIX_IBM, "lps+irm": MIX_LPS_IRM, "lps+ibm": MIX_LPS_IBM}
+# bp_mixture: a numpy structured array of this dtype is a mixture plan
+MIXTURE_DTYPE = np.dtype({"names": ["clean", "noise", "offset", "snr_db"], "formats": [np.int32, np.int32, np.int64, np.float32],
+                          "offsets": [0, 4, 8, 16], "itemsize": 24})
 PROF_KINDS = ["fwd_l1", "fwd_hidden", "fwd_out", "dgrad_out", "dgrad_hidden", "wgrad_update_grouped"]
 
 
@@ -62,6 +68,16 @@ class BPWaveChunk(C.Structure):
         ("context", C.c_int), ("targ_offset", C.c_int),
         ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
         ("target", C.c_int), ("out_col", C.c_int),
+    ]
+
+
+class BPMixCorpus(C.Structure):
+    """bp_mix_corpus (include/bp_c_api.h): clean and noise recordings, resident on the handle."""
+    _fields_ = [
+        ("fea_dim", C.c_int), ("context", C.c_int), ("targ_offset", C.c_int), ("target", C.c_int), ("lc_db", C.c_float),
+        ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
+        ("n_clean", C.c_int), ("clean_len", C.POINTER(C.c_int64)), ("clean_pcm", C.POINTER(C.c_float)),
+        ("n_noise", C.c_int), ("noise_len", C.POINTER(C.c_int64)), ("noise_pcm", C.POINTER(C.c_float)),
     ]
 
 
@@ -108,6 +124,12 @@ def load_library(path=None):
     lib.bp_forward_windows.argtypes = [hp, C.POINTER(BPWindowChunk), fp]
     lib.bp_enhance_waves.argtypes = [hp, C.c_int, C.POINTER(BPWaveChunk), fp, fp]
     lib.bp_wave_lps.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp]
+    lib.bp_set_mix_corpus.argtypes = [hp, C.POINTER(BPMixCorpus)]
+    lib.bp_train_mix.argtypes = [hp, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    lib.bp_cv_mix.argtypes = [hp, C.c_int, C.c_void_p, fp]
+    lib.bp_mix_features.argtypes = [hp, C.c_int, C.c_void_p, fp, fp, fp, fp, fp]
+    lib.bp_mix_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, fp, C.c_void_p]
+    lib.bp_mix_shuffle.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -350,6 +372,75 @@ class BP_GPU(object):
             return waves
         return waves, np.split(net[:int(frames.sum())], np.cumsum(frames)[:-1])
 
+    # ---- training mixtures made on the device (bp_set_mix_corpus ...; definition: include/bp_c_api.h)
+    def set_mix_corpus(self, clean, noise, mean, inv_std, context, targ_offset, target=MIX_LPS, lc_db=5.0):
+        """clean, noise: lists of 1-D arrays (int16 units), uploaded once; target: MIX_* or a name of MIX_TARGETS."""
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).reshape(-1)
+        if inv_std.size != mean.size:
+            self._fail("set_mix_corpus: mean and inv_std differ in length")
+        target = MIX_TARGETS[target] if isinstance(target, str) else int(target)
+        cl = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in clean]
+        no = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in noise]
+        cpcm = np.ascontiguousarray(np.concatenate(cl) if cl else np.zeros(0, np.float32))
+        npcm = np.ascontiguousarray(np.concatenate(no) if no else np.zeros(0, np.float32))
+        clen = np.array([x.size for x in cl], np.int64)
+        nlen = np.array([x.size for x in no], np.int64)
+        c = BPMixCorpus()
+        c.fea_dim, c.context, c.targ_offset, c.target, c.lc_db = mean.size, int(context), int(targ_offset), target, float(lc_db)
+        c.mean, c.inv_std = _fp(mean), _fp(inv_std)
+        lp = C.POINTER(C.c_int64)
+        c.n_clean, c.clean_len, c.clean_pcm = len(cl), clen.ctypes.data_as(lp), _fp(cpcm)
+        c.n_noise, c.noise_len, c.noise_pcm = len(no), nlen.ctypes.data_as(lp), _fp(npcm)
+        self._check(self._lib.bp_set_mix_corpus(self._h, C.byref(c)))
+        self.mix_fea_dim, self.mix_clean_len = mean.size, clen
+        self.mix_nat = self.layersizes[0] == (int(context) + 1) * mean.size
+
+    def _plan(self, plan):
+        p = np.ascontiguousarray(plan, dtype=MIXTURE_DTYPE).reshape(-1)
+        return p, p.ctypes.data_as(C.c_void_p)
+
+    def mix_frames(self, plan):
+        """Frames of every mixture of the plan (T = (len_c - 1)/hop + 2), per the corpus set last."""
+        p = np.ascontiguousarray(plan, dtype=MIXTURE_DTYPE).reshape(-1)
+        if getattr(self, "mix_fea_dim", None) is None:
+            self._fail("mix_frames: no corpus (set_mix_corpus)")
+        lens = self.mix_clean_len[p["clean"]]
+        return (lens - 1) // (self.mix_fea_dim - 1) + 2
+
+    def train_mix(self, plan, order=None):
+        p, pp = self._plan(plan)
+        self._push_hyper()
+        o = None if order is None else np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        if o is not None and o.size != int(self.mix_frames(p).sum()):     # (the library reads sum(T) entries)
+            self._fail("train_mix: order must have one entry per frame of the plan (%d), not %d" % (int(self.mix_frames(p).sum()), o.size))
+        self._check(self._lib.bp_train_mix(self._h, p.size, pp, None if o is None else o.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def CrossValid_mix(self, plan):
+        p, pp = self._plan(plan)
+        self._push_hyper()
+        e = C.c_float(0.0)
+        self._check(self._lib.bp_cv_mix(self._h, p.size, pp, C.byref(e)))
+        return float(e.value)
+
+    def mix_features(self, plan):
+        """dict of fea [sum T][D] (normalised), lps [sum T][D] (noisy), targ [sum T][sL], nat [n_mix][D] (None without the
+        noise-aware block) and pcm [sum len_c] (the mixed samples), unshuffled."""
+        p, pp = self._plan(plan)
+        D = getattr(self, "mix_fea_dim", None)
+        if D is None:                                   # no corpus: the library reports the state error
+            self._check(self._lib.bp_mix_features(self._h, p.size, pp, None, None, None, None, None))
+        T = int(self.mix_frames(p).sum())
+        n_pcm = int(self.mix_clean_len[p["clean"]].sum())
+        has_nat = self.mix_nat
+        out = {"fea": np.empty((T, D), np.float32), "lps": np.empty((T, D), np.float32),
+               "targ": np.empty((T, self.layersizes[-1]), np.float32),
+               "nat": np.empty((p.size, D), np.float32) if has_nat else None, "pcm": np.empty(max(n_pcm, 1), np.float32)}
+        self._check(self._lib.bp_mix_features(self._h, p.size, pp, _fp(out["fea"]), _fp(out["lps"]), _fp(out["targ"]),
+                                              _fp(out["nat"]) if has_nat else None, _fp(out["pcm"])))
+        out["pcm"] = out["pcm"][:n_pcm]
+        return out
+
     def fill_chunk_synthetic(self, n_frames, seed=20260927):
         self._check(self._lib.bp_fill_chunk_synthetic(self._h, int(n_frames), int(seed)))
 
@@ -494,6 +585,29 @@ def wave_lps(device, fea_dim, sentences):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
+
+
+def mix_plan(seed, n_clean, per_clean, noise_lens, snr_list):
+    """bp_mix_plan: the shuffled mixture list (MIXTURE_DTYPE [n_clean * per_clean]); host only."""
+    lib = load_library()
+    nl = np.ascontiguousarray(noise_lens, dtype=np.int64)
+    snr = np.ascontiguousarray(snr_list, dtype=np.float32)
+    out = np.zeros(max(int(n_clean) * int(per_clean), 1), MIXTURE_DTYPE)
+    rc = lib.bp_mix_plan(int(seed), int(n_clean), int(per_clean), nl.size, nl.ctypes.data_as(C.POINTER(C.c_int64)), snr.size,
+                         _fp(snr), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out[:int(n_clean) * int(per_clean)]
+
+
+def mix_shuffle(seed, stream, n):
+    """bp_mix_shuffle: a permutation of range(n) (int32), keyed by (seed, stream); host only."""
+    lib = load_library()
+    out = np.zeros(max(int(n), 1), np.int32)
+    rc = lib.bp_mix_shuffle(int(seed), int(stream), int(n), out.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out[:int(n)]
 
 
 def device_count():

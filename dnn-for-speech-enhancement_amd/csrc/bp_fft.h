@@ -1,0 +1,100 @@
+// bp_fft.h -- what the two signal-layer translation units share (bp_wave.hip: enhancement and LPS features; bp_mix.hip: training
+// mixtures made on the device): the real FFT of one analysis frame in LDS, the analysis kernel's arguments and host-side launchers
+// of the bp_wave.hip kernels.  Internal: nothing in here is part of the C ABI.
+//
+// Signal definition: n_fft = 2 (fea_dim - 1) = 2M, hop = M, periodic Hamming window.  A real frame of 2M
+// samples is transformed as a complex FFT of M points z[m] = (x[2m], x[2m+1]) followed by the split step.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include "bp_handle.h"
+
+namespace {
+
+constexpr int WAVE_THREADS = 256;
+constexpr float LN_FLOOR = -23.025850929940457f;   // ln(1e-10)
+
+// LDS index of complex point i: one float2 of padding after every 32, so that the power-of-two strides of the butterfly
+// stages (and the bit-reversed scatter) do not pile up on a few banks of ds_read_b64 / ds_write_b64.
+__device__ __forceinline__ int lp(int i) { return i + (i >> 5); }
+__host__ __device__ inline size_t lds_bytes(int M) { return (size_t)(M + M / 32 + 1) * sizeof(float2); }
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
+
+// Radix-2 decimation-in-time FFT of M points in LDS (input in bit-reversed order).  tw[j] = exp(-2 pi i j / n_fft), n_fft = 2M;
+// inverse: conjugated twiddles, no scaling.
+__device__ void fft_lds(float2 *z, int M, const float2 *__restrict__ tw, bool inverse)
+{
+    for (int h = 1; h < M; h <<= 1) {
+        const int tstep = M / h;                                // exp(-2 pi i (j%h) / (2h)) = tw[(j%h) * (2M / (2h))]
+        for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
+            const int jh = j & (h - 1), i0 = ((j - jh) << 1) + jh, i1 = i0 + h;
+            const float2 w = tw[jh * tstep];
+            const float2 a = z[lp(i0)], bb = z[lp(i1)];
+            const float2 b = inverse ? cmulc(bb, w) : cmul(bb, w);
+            z[lp(i0)] = make_float2(a.x + b.x, a.y + b.y);
+            z[lp(i1)] = make_float2(a.x - b.x, a.y - b.y);
+        }
+        __syncthreads();
+    }
+}
+
+// Sentence of global frame g: the last s with F[s] <= g (F[n_sent] = all frames).  Uniform per workgroup.
+__device__ __forceinline__ int sentence_of(const int *__restrict__ F, int n_sent, int g)
+{
+    int lo = 0, hi = n_sent - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (F[mid] <= g) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// Forward real FFT of the 2M samples at x (16-byte aligned) times the window: leaves Z = FFT_M(z) in LDS (natural order, lp
+// indexing) for rfft_bin.  Ends with a barrier.
+__device__ __forceinline__ void rfft_frame(float2 *z, const float *__restrict__ x, const float *__restrict__ win, const float2 *__restrict__ tw,
+                                           int log2M)
+{
+    const int M = 1 << log2M, N = 2 * M;
+    // windowed samples as M complex points z[m] = (x[2m], x[2m+1]), scattered to bit-reversed positions; 16-byte loads
+    for (int q = threadIdx.x; q < N / 4; q += blockDim.x) {
+        const float4 v = *reinterpret_cast<const float4 *>(x + 4 * q), w = *reinterpret_cast<const float4 *>(win + 4 * q);
+        const int m0 = 2 * q, m1 = 2 * q + 1;
+        z[lp((int)(__brev((unsigned)m0) >> (32 - log2M)))] = make_float2(v.x * w.x, v.y * w.y);
+        z[lp((int)(__brev((unsigned)m1) >> (32 - log2M)))] = make_float2(v.z * w.z, v.w * w.w);
+    }
+    __syncthreads();
+    fft_lds(z, M, tw, false);
+}
+
+// split step: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i, k = 0 .. M
+__device__ __forceinline__ float2 rfft_bin(const float2 *z, const float2 *__restrict__ tw, int M, int k)
+{
+    const float2 zk = z[lp(k & (M - 1))], zm = z[lp((M - k) & (M - 1))];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    return k == 0 ? make_float2(zk.x + zk.y, 0.0f) : k == M ? make_float2(zk.x - zk.y, 0.0f)
+                                                          : make_float2(e.x + (tw[k].x * o.x - tw[k].y * o.y),
+                                                                        e.y + (tw[k].x * o.y + tw[k].y * o.x));
+}
+
+// the LPS of one bin's power, with the 1e-10 floor
+__device__ __forceinline__ float lps_of(float p) { return p > 1e-10f ? logf(p) : LN_FLOOR; }
+
+}  // namespace
+
+// bp_wave_analysis arguments (bp_wave.hip): frame g of sentence s reads the padded samples [(g + s) hop, (g + s) hop + n_fft).
+struct WaveAnaArgs {
+    const float *pcm; const float *win; const float2 *tw; const int *F; const float *mean, *inv_std;
+    int n_sent, log2M, D, hop, ctx, toff;
+    float2 *Y;            // [frames][D] noisy spectrum, or null
+    float *lps;           // [frames][D] un-normalised LPS, or null
+    float *rows;          // staged normalised rows [frames + n_sent (ctx - 1)][D], or null
+    int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
+};
+
+// Host side of bp_wave.hip, for bp_mix.hip
+int wave_log2_fft(int fea_dim);                                   // log2 of M, or -1 outside 1d's range
+void wave_window_twiddles(int log2M, float *win, float2 *tw);     // win[2M], tw[M + 1], computed in double and rounded once
+int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st);   // grow-only device / pinned host buffer
+hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st);
+hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, int ctx, int toff, float *nat, hipStream_t st);

@@ -7,6 +7,7 @@
 //   bp_dp.hip       in-library data-parallel exchange (rendezvous, hipIpc peers, RCCL transport, the sharded step driver)
 //   bp_profile.hip  in-step event profile, measured peaks, isolated kernel timing
 //   bp_wave.hip     the signal layer: STFT analysis into a window chunk, overlap-add resynthesis (bp_enhance_waves, bp_wave_lps)
+//   bp_mix.hip      training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -110,6 +111,8 @@ struct bp_handle {
     // bp_enhance_waves (bp_wave.hip), grow-only: device input block, noisy spectrum, synthesis frames, padded output samples;
     // pinned host staging of the input block and of the output samples
     Raw wave[4], wave_pin[2];
+    // bp_set_mix_corpus (bp_mix.hip): the resident corpus and the grow-only buffers of the mixing calls, or null
+    struct MixState *mix;
 };
 
 // Coefficients of the momentum update (update_delta, bp_device.h; DevFunc.cu:313-318 for momentum_rule 0, :306-311 for 1):
@@ -159,14 +162,19 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
 hipError_t launch_dgrad(bp_handle *h, int l, int M);
 hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused);
 hipError_t prof_mark(bp_handle *h, int kind);
-// A window chunk written by kernels on h->stream (bp_wave.hip): window_reserve sizes the staging set that is not current
-// (rows_b bytes of raw frames, nat_b bytes of NAT rows, n_samples entries of win_start and nat_row) and returns where they lie;
-// window_adopt then makes it the resident window chunk with the bookkeeping of bp_upload_chunk_windows (no targets).
-int window_reserve(bp_handle *h, size_t rows_b, size_t nat_b, size_t n_samples, float **rows, float **nat, int **win_start, int **nat_row);
-int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat);
+// A window chunk written by kernels on h->stream (bp_wave.hip, bp_mix.hip): window_reserve sizes the staging set that is not
+// current (rows_b bytes of raw frames, targ_b bytes of target frames, nat_b bytes of NAT rows, n_samples entries of each of the
+// tables win_start | targ_frame | nat_row) and returns where they lie; window_adopt then makes it the resident window chunk with
+// the bookkeeping of bp_upload_chunk_windows (with or without targets).
+int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, size_t n_samples, float **rows, float **targ, float **nat,
+                   int **tables);
+int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat, bool with_targ);
 // CV-semantics forward of samples [0, n) of the resident chunk into out_chunk (the partial last bunch included), no copy
 int out_chunk_reserve(bp_handle *h, int n_frames);
 int forward_resident(bp_handle *h, int n);
+
+// ------------------------------------------------------------------ mixtures (bp_mix.hip)
+void mix_free(bp_handle *h);                      // the corpus and the mixing buffers (bp_destroy)
 
 // ------------------------------------------------------------------ data-parallel driver (bp_dp.hip)
 int dp_check(bp_handle *h);                       // BP_OK, or the device-side timeout an exchange kernel raised

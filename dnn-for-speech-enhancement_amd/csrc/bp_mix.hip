@@ -1,0 +1,510 @@
+// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 5: training mixtures made on the device.  A clean-speech
+// corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
+// SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
+// reads.  gfx950 only.
+//
+// Device layout of one call: mixture m is a "sentence" of bp_wave.hip's padded layout -- its T_m + 1 segments of hop samples start
+// at segment Fs[m] = F[m] + m (F = prefix sums of T), sample i of the mixture lies at padded sample (Fs[m] + 1) hop + i, and frame
+// t at (Fs[m] + t) hop.  Three such buffers: x (mixed), s (clean), g v (scaled noise).  The per-call input is ONE host->device
+// copy (`MixIn`: F | Fs | clean | noise | offset | snr | order); the order table is the only per-frame data the host sends.
+//
+// Kernels, each a launch on the handle's stream:
+//   bp_mix_gain      one workgroup per mixture: E_s and E_v in double (per-thread strided sums, then a fixed LDS tree), the gain
+//   bp_mix_pcm       one workgroup per segment: x = fmaf(g, v, s), s and g v into the padded buffers (padding written as zeros)
+//   bp_wave_analysis (bp_wave.hip) on x: the staged normalised rows, win_start / nat_row, the noisy LPS (bp_mix_features)
+//   bp_mix_targets   one workgroup per frame: the FFTs of s and g v in LDS, one after the other, and the frame's target row
+//   bp_wave_nat      (bp_wave.hip) the noise-aware rows
+//   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "bp_fft.h"
+#include "bp_handle.h"
+
+namespace {
+
+struct MixArgs {
+    const float *clean, *noise;                                  // the corpus, back to back
+    const int64_t *clean_off, *clean_len, *noise_off, *noise_len;
+    const int *Fs, *mc, *mn; const int64_t *mo; const float *msnr;  // per mixture
+    int n_mix, hop;
+    float *gain;                                                 // [n_mix]
+    float *x, *s, *v;                                            // padded [Fs[n_mix] hop]
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_mix_gain(const MixArgs a)
+{
+    __shared__ double es[WAVE_THREADS], ev[WAVE_THREADS];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int c = a.mc[m], n = a.mn[m];
+    const int64_t lc = a.clean_len[c], ln = a.noise_len[n], step = WAVE_THREADS % ln;
+    const float *cs = a.clean + a.clean_off[c], *ns = a.noise + a.noise_off[n];
+    double s2 = 0.0, v2 = 0.0;
+    int64_t p = (a.mo[m] + tid) % ln;                            // noise sample of clean sample i = tid, tid + 256, ...
+    for (int64_t i = tid; i < lc; i += WAVE_THREADS) {
+        const double sv = cs[i], vv = ns[p];
+        s2 += sv * sv; v2 += vv * vv;
+        p += step; if (p >= ln) p -= ln;
+    }
+    es[tid] = s2; ev[tid] = v2;
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { es[tid] += es[tid + w]; ev[tid] += ev[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double Es = es[0], Ev = ev[0];
+        a.gain[m] = Ev > 0.0 ? (float)sqrt(Es / (Ev * pow(10.0, (double)a.msnr[m] / 10.0))) : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_mix_pcm(const MixArgs a)
+{
+    const int q = blockIdx.x, m = sentence_of(a.Fs, a.n_mix, q);
+    const int c = a.mc[m], n = a.mn[m];
+    const int64_t lc = a.clean_len[c], ln = a.noise_len[n], o = a.mo[m];
+    const float *cs = a.clean + a.clean_off[c], *ns = a.noise + a.noise_off[n];
+    const float g = a.gain[m];
+    const int64_t i0 = (int64_t)(q - a.Fs[m] - 1) * a.hop;     // mixture sample at the segment's first position (front pad: hop)
+    for (int r = threadIdx.x; r < a.hop; r += blockDim.x) {
+        const int64_t i = i0 + r;
+        float xv = 0.0f, sv = 0.0f, vv = 0.0f;
+        if (i >= 0 && i < lc) {
+            const float s = cs[i], v = ns[(o + i) % ln];
+            xv = fmaf(g, v, s); sv = s; vv = g * v;
+        }
+        const size_t d = (size_t)q * a.hop + r;
+        a.x[d] = xv; a.s[d] = sv; a.v[d] = vv;
+    }
+}
+
+namespace {
+struct MixTargArgs {
+    const float *s, *v; const float *win; const float2 *tw; const int *F;
+    int n_mix, log2M, D, hop, target, ldt;
+    float thr;                                                   // 10^(lc_db / 10)
+    float *targ;                                                 // [frames][ldt]
+};
+}  // namespace
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_mix_targets(const MixTargArgs a)
+{
+    extern __shared__ float2 z[];
+    const int g = blockIdx.x, M = 1 << a.log2M, tid = threadIdx.x;
+    float *pS = reinterpret_cast<float *>(z + lds_bytes(M) / sizeof(float2));   // |S|^2 [M + 1]: each thread reads back its own bins
+    const int m = sentence_of(a.F, a.n_mix, g);
+    const size_t at = (size_t)(g + m) * a.hop;
+    rfft_frame(z, a.s + at, a.win, a.tw, a.log2M);
+    for (int k = tid; k <= M; k += blockDim.x) { const float2 X = rfft_bin(z, a.tw, M, k); pS[k] = X.x * X.x + X.y * X.y; }
+    __syncthreads();                                             // (z is reloaded below)
+    rfft_frame(z, a.v + at, a.win, a.tw, a.log2M);
+    float *t = a.targ + (size_t)g * a.ldt;
+    for (int k = tid; k <= M; k += blockDim.x) {
+        const float2 X = rfft_bin(z, a.tw, M, k);
+        const float ps = pS[k], pn = X.x * X.x + X.y * X.y;
+        const float lps = lps_of(ps), irm = sqrtf(ps / fmaxf(ps + pn, 1e-10f)), ibm = ps > a.thr * pn ? 1.0f : 0.0f;
+        switch (a.target) {
+        case BP_MIX_LPS: t[k] = lps; break;
+        case BP_MIX_IRM: t[k] = irm; break;
+        case BP_MIX_IBM: t[k] = ibm; break;
+        case BP_MIX_LPS_IRM: t[k] = lps; t[a.D + k] = irm; break;
+        default: t[k] = lps; t[a.D + k] = ibm; break;
+        }
+    }
+}
+
+// row i of the chunk trains mixture-frame g = order[i] (identity without order): its window starts at staged row g + m (ctx - 1)
+__global__ __launch_bounds__(WAVE_THREADS) void bp_mix_tables(const int *__restrict__ order, const int *__restrict__ F, int n_mix, int n,
+                                                           int ctx, int *__restrict__ ws, int *__restrict__ tf, int *__restrict__ nr)
+{
+    const int i = blockIdx.x * WAVE_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int g = order ? order[i] : i, m = sentence_of(F, n_mix, g);
+    ws[i] = g + m * (ctx - 1);
+    tf[i] = g;
+    if (nr) nr[i] = m;
+}
+
+// ------------------------------------------------------------------ host side
+struct MixState {
+    int D, log2M, M, hop, ctx, toff, target, sL;
+    bool nat;
+    float thr;
+    int n_clean, n_noise;
+    std::vector<int64_t> clean_len, noise_len;
+    char *corpus;                                                // device: clean | noise | offsets and lengths | mean | inv_std | window | twiddles
+    size_t o_clean, o_noise, o_cl_off, o_cl_len, o_no_off, o_no_len, o_mean, o_istd, o_win, o_tw;
+    bp_handle::Raw in_d, x, s, v, gain, lps;                     // grow-only device buffers of the calls
+    bp_handle::Raw in_pin[2]; hipEvent_t ev_in[2]; bool ev_valid[2]; int pin_cur;   // pinned input blocks, alternating
+};
+
+namespace {
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+void free_raw(bp_handle::Raw &r, bool pinned)
+{
+    if (r.p) (void)(pinned ? hipHostFree(r.p) : hipFree(r.p));
+    r.p = nullptr; r.bytes = 0;
+}
+
+void free_state(MixState *ms)
+{
+    if (!ms) return;
+    if (ms->corpus) (void)hipFree(ms->corpus);
+    for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps}) free_raw(*r, false);
+    for (int k = 0; k < 2; ++k) {
+        if (ms->ev_in[k]) { (void)hipEventSynchronize(ms->ev_in[k]); (void)hipEventDestroy(ms->ev_in[k]); }
+        free_raw(ms->in_pin[k], true);
+    }
+    delete ms;
+}
+
+int parts_of(int target) { return target == BP_MIX_LPS_IRM || target == BP_MIX_LPS_IBM ? 2 : 1; }
+
+// The frame plan of a call, checked before any device work.
+struct Call {
+    int n;
+    std::vector<int> F, Fs;                                      // [n + 1]
+    size_t frames, rows, segs;                                   // frames, staged rows, padded segments
+    size_t o_F, o_Fs, o_c, o_n, o_o, o_snr, o_order, bytes;      // MixIn layout
+};
+int plan_call(const bp_handle *h, const char *who, int n_mix, const bp_mixture *m, Call &c)
+{
+    if (!h) return fail(BP_ERR_ARG, std::string(who) + ": null handle");
+    const MixState *ms = h->mix;
+    if (!ms) return fail(BP_ERR_STATE, std::string(who) + ": no corpus (bp_set_mix_corpus)");
+    if (h->dp) return fail(BP_ERR_STATE, std::string(who) + ": not on an attached data-parallel handle");
+    if (n_mix < 1 || !m) return fail(BP_ERR_ARG, std::string(who) + ": no mixtures or null pointer");
+    c.n = n_mix;
+    c.F.assign((size_t)n_mix + 1, 0); c.Fs.assign((size_t)n_mix + 1, 0);
+    size_t f = 0;
+    for (int i = 0; i < n_mix; ++i) {
+        const bp_mixture &x = m[i];
+        if (x.clean < 0 || x.clean >= ms->n_clean) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": clean index out of range");
+        if (x.noise < 0 || x.noise >= ms->n_noise) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": noise index out of range");
+        if (x.offset < 0 || x.offset >= ms->noise_len[x.noise])
+            return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": offset outside the noise recording");
+        if (!std::isfinite(x.snr_db)) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": SNR is not finite");
+        f += (size_t)((ms->clean_len[x.clean] - 1) / ms->hop + 2);
+        if (f > (size_t)h->cap) break;                            // (caught below; keeps the sums small)
+        c.F[i + 1] = (int)f; c.Fs[i + 1] = (int)f + i + 1;
+    }
+    c.frames = f;
+    c.rows = f + (size_t)n_mix * (ms->ctx - 1);
+    if (c.rows > (size_t)h->cap)
+        return fail(BP_ERR_ARG, std::string(who) + ": frames + n_mix*(context-1) exceed the chunk capacity " + std::to_string(h->cap));
+    c.segs = (size_t)c.Fs[n_mix];
+    c.o_F = 0; c.o_Fs = al256(((size_t)n_mix + 1) * 4); c.o_c = c.o_Fs + al256(((size_t)n_mix + 1) * 4);
+    c.o_n = c.o_c + al256((size_t)n_mix * 4); c.o_o = c.o_n + al256((size_t)n_mix * 4); c.o_snr = c.o_o + al256((size_t)n_mix * 8);
+    c.o_order = c.o_snr + al256((size_t)n_mix * 4); c.bytes = c.o_order + al256(c.frames * 4);
+    return BP_OK;
+}
+
+int check_order(const char *who, const Call &c, const int *order)
+{
+    if (!order) return BP_OK;
+    std::vector<char> seen(c.frames, 0);
+    for (size_t i = 0; i < c.frames; ++i) {
+        const int g = order[i];
+        if (g < 0 || (size_t)g >= c.frames || seen[g]) return fail(BP_ERR_ARG, std::string(who) + ": order is not a permutation of [0, frames)");
+        seen[g] = 1;
+    }
+    return BP_OK;
+}
+
+// Mix, analyse and write the window chunk of a call into the staging set that is not current (targets included), on h->stream.
+// Then the caller adopts it.  lps_out: also keep the noisy LPS in ms->lps.
+int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order, bool lps_out, float **rows_out, float **targ_out,
+             float **nat_out)
+{
+    MixState *ms = h->mix;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int D = ms->D, n = (int)c.frames;
+    const size_t pcm_b = c.segs * ms->hop * 4;
+    int r;
+    if ((r = wave_grow(ms->in_d, c.bytes, false, h->stream)) != BP_OK || (r = wave_grow(ms->x, pcm_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->s, pcm_b, false, h->stream)) != BP_OK || (r = wave_grow(ms->v, pcm_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->gain, (size_t)c.n * 4, false, h->stream)) != BP_OK ||
+        (lps_out && (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK))
+        return r;
+    float *rows_d, *targ_d, *nat_d; int *tab;
+    if ((r = window_reserve(h, c.rows * D * 4, c.frames * ms->sL * 4, ms->nat ? (size_t)c.n * D * 4 : 0, c.frames, &rows_d, &targ_d,
+                            &nat_d, &tab)) != BP_OK)
+        return r;
+    // the pinned input block: the copy out of this one was enqueued two calls ago; wait for it (not for the training behind it)
+    const int k = ms->pin_cur;
+    ms->pin_cur ^= 1;
+    if (ms->ev_valid[k]) HIPCHK(hipEventSynchronize(ms->ev_in[k]));
+    if ((r = wave_grow(ms->in_pin[k], c.bytes, true, h->stream)) != BP_OK) return r;
+    char *hb = (char *)ms->in_pin[k].p, *db = (char *)ms->in_d.p;
+    memcpy(hb + c.o_F, c.F.data(), c.F.size() * 4);
+    memcpy(hb + c.o_Fs, c.Fs.data(), c.Fs.size() * 4);
+    for (int i = 0; i < c.n; ++i) {
+        ((int *)(hb + c.o_c))[i] = m[i].clean; ((int *)(hb + c.o_n))[i] = m[i].noise;
+        ((int64_t *)(hb + c.o_o))[i] = m[i].offset; ((float *)(hb + c.o_snr))[i] = m[i].snr_db;
+    }
+    const size_t in_b = order ? c.bytes : c.o_order;
+    if (order) memcpy(hb + c.o_order, order, c.frames * 4);
+    HIPCHK(hipMemcpyAsync(db, hb, in_b, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(ms->ev_in[k], h->stream));
+    ms->ev_valid[k] = true;
+
+    const char *cp = ms->corpus;
+    const float *win = (const float *)(cp + ms->o_win);
+    const float2 *tw = (const float2 *)(cp + ms->o_tw);
+    const int *F = (const int *)(db + c.o_F);
+    MixArgs a; memset(&a, 0, sizeof(a));
+    a.clean = (const float *)(cp + ms->o_clean); a.noise = (const float *)(cp + ms->o_noise);
+    a.clean_off = (const int64_t *)(cp + ms->o_cl_off); a.clean_len = (const int64_t *)(cp + ms->o_cl_len);
+    a.noise_off = (const int64_t *)(cp + ms->o_no_off); a.noise_len = (const int64_t *)(cp + ms->o_no_len);
+    a.Fs = (const int *)(db + c.o_Fs); a.mc = (const int *)(db + c.o_c); a.mn = (const int *)(db + c.o_n);
+    a.mo = (const int64_t *)(db + c.o_o); a.msnr = (const float *)(db + c.o_snr);
+    a.n_mix = c.n; a.hop = ms->hop; a.gain = (float *)ms->gain.p;
+    a.x = (float *)ms->x.p; a.s = (float *)ms->s.p; a.v = (float *)ms->v.p;
+    hipLaunchKernelGGL(bp_mix_gain, dim3((unsigned)c.n), dim3(WAVE_THREADS), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(bp_mix_pcm, dim3((unsigned)c.segs), dim3(WAVE_THREADS), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    {
+        WaveAnaArgs w; memset(&w, 0, sizeof(w));
+        w.pcm = a.x; w.win = win; w.tw = tw; w.F = F;
+        w.mean = (const float *)(cp + ms->o_mean); w.inv_std = (const float *)(cp + ms->o_istd);
+        w.n_sent = c.n; w.log2M = ms->log2M; w.D = D; w.hop = ms->hop; w.ctx = ms->ctx; w.toff = ms->toff;
+        w.lps = lps_out ? (float *)ms->lps.p : nullptr; w.rows = rows_d;
+        w.win_start = tab; w.nat_row = ms->nat ? tab + 2 * (size_t)n : nullptr;
+        HIPCHK(wave_analysis_launch(w, n, h->stream));
+    }
+    {
+        MixTargArgs t; memset(&t, 0, sizeof(t));
+        t.s = a.s; t.v = a.v; t.win = win; t.tw = tw; t.F = F;
+        t.n_mix = c.n; t.log2M = ms->log2M; t.D = D; t.hop = ms->hop; t.target = ms->target; t.ldt = ms->sL; t.thr = ms->thr;
+        t.targ = targ_d;
+        hipLaunchKernelGGL(bp_mix_targets, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(ms->M) + (size_t)(ms->M + 1) * 4, h->stream, t);
+        HIPCHK(hipGetLastError());
+    }
+    if (ms->nat) HIPCHK(wave_nat_launch(rows_d, F, c.n, D, ms->ctx, ms->toff, nat_d, h->stream));
+    hipLaunchKernelGGL(bp_mix_tables, dim3((unsigned)((n + WAVE_THREADS - 1) / WAVE_THREADS)), dim3(WAVE_THREADS), 0, h->stream,
+                       order ? (const int *)(db + c.o_order) : (const int *)nullptr, F, c.n, n, ms->ctx, tab, tab + n,
+                       ms->nat ? tab + 2 * (size_t)n : (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (rows_out) *rows_out = rows_d;
+    if (targ_out) *targ_out = targ_d;
+    if (nat_out) *nat_out = nat_d;
+    return BP_OK;
+}
+
+// Philox4x32-10 (bp_device.h) on the host
+void philox(uint32_t c[4], uint64_t seed)
+{
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+uint32_t word0(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2)
+{
+    uint32_t c[4] = {c0, c1, c2, 0};
+    philox(c, seed);
+    return c[0];
+}
+uint64_t scale(uint32_t u, uint64_t n) { return ((uint64_t)u * n) >> 32; }
+
+}  // namespace
+
+void mix_free(bp_handle *h)
+{
+    free_state(h->mix);
+    h->mix = nullptr;
+}
+
+extern "C" int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c)
+{
+    if (!h || !c) return fail(BP_ERR_ARG, "bp_set_mix_corpus: null handle or corpus");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_set_mix_corpus: not on an attached data-parallel handle");
+    const int log2M = wave_log2_fft(c->fea_dim);
+    if (log2M < 0) return fail(BP_ERR_ARG, "bp_set_mix_corpus: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    const int D = c->fea_dim, ctx = c->context, toff = c->targ_offset, L = h->L, sL = h->s[L - 1];
+    if (ctx < 1 || toff < 0 || toff >= ctx) return fail(BP_ERR_ARG, "bp_set_mix_corpus: need context >= 1 and 0 <= targ_offset < context");
+    const bool nat = (long)h->s[0] == (long)(ctx + 1) * D;
+    if (!nat && (long)h->s[0] != (long)ctx * D)
+        return fail(BP_ERR_ARG, "bp_set_mix_corpus: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
+    if (c->target < BP_MIX_LPS || c->target > BP_MIX_LPS_IBM) return fail(BP_ERR_ARG, "bp_set_mix_corpus: unknown target");
+    if ((long)sL != (long)parts_of(c->target) * D)
+        return fail(BP_ERR_ARG, "bp_set_mix_corpus: layersizes[last] must be fea_dim (LPS, IRM, IBM) or 2*fea_dim (LPS+IRM, LPS+IBM)");
+    if (!std::isfinite(c->lc_db)) return fail(BP_ERR_ARG, "bp_set_mix_corpus: lc_db is not finite");
+    if (!c->mean || !c->inv_std) return fail(BP_ERR_ARG, "bp_set_mix_corpus: null mean / inv_std");
+    if (c->n_clean < 1 || c->n_noise < 1 || !c->clean_len || !c->noise_len || !c->clean_pcm || !c->noise_pcm)
+        return fail(BP_ERR_ARG, "bp_set_mix_corpus: need at least one clean sentence and one noise recording");
+    size_t nc = 0, nn = 0;
+    for (int i = 0; i < c->n_clean; ++i) {
+        if (c->clean_len[i] < 1) return fail(BP_ERR_ARG, "bp_set_mix_corpus: empty clean sentence " + std::to_string(i));
+        if ((c->clean_len[i] - 1) / ((int64_t)1 << log2M) + 2 > (int64_t)h->cap)
+            return fail(BP_ERR_ARG, "bp_set_mix_corpus: clean sentence " + std::to_string(i) + " is longer than one chunk");
+        nc += (size_t)c->clean_len[i];
+    }
+    for (int i = 0; i < c->n_noise; ++i) {
+        if (c->noise_len[i] < 1) return fail(BP_ERR_ARG, "bp_set_mix_corpus: empty noise recording " + std::to_string(i));
+        nn += (size_t)c->noise_len[i];
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));                     // (an earlier corpus may still be read)
+    mix_free(h);
+    MixState *ms = new MixState();
+    ms->D = D; ms->log2M = log2M; ms->M = 1 << log2M; ms->hop = ms->M; ms->ctx = ctx; ms->toff = toff; ms->target = c->target; ms->sL = sL;
+    ms->nat = nat; ms->thr = (float)pow(10.0, (double)c->lc_db / 10.0);
+    ms->n_clean = c->n_clean; ms->n_noise = c->n_noise;
+    ms->clean_len.assign(c->clean_len, c->clean_len + c->n_clean);
+    ms->noise_len.assign(c->noise_len, c->noise_len + c->n_noise);
+    ms->o_clean = 0; ms->o_noise = al256(nc * 4); ms->o_cl_off = ms->o_noise + al256(nn * 4);
+    ms->o_cl_len = ms->o_cl_off + al256((size_t)c->n_clean * 8); ms->o_no_off = ms->o_cl_len + al256((size_t)c->n_clean * 8);
+    ms->o_no_len = ms->o_no_off + al256((size_t)c->n_noise * 8); ms->o_mean = ms->o_no_len + al256((size_t)c->n_noise * 8);
+    ms->o_istd = ms->o_mean + al256((size_t)D * 4); ms->o_win = ms->o_istd + al256((size_t)D * 4);
+    ms->o_tw = ms->o_win + al256((size_t)2 * ms->M * 4);
+    const size_t bytes = ms->o_tw + al256((size_t)(ms->M + 1) * 8);
+    h->mix = ms;
+    if (hipMalloc((void **)&ms->corpus, bytes) != hipSuccess) { mix_free(h); return fail(BP_ERR_NOMEM, "bp_set_mix_corpus: hipMalloc (corpus)"); }
+    for (int k = 0; k < 2; ++k)
+        if (hipEventCreateWithFlags(&ms->ev_in[k], hipEventDisableTiming) != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, "bp_set_mix_corpus: event"); }
+    std::vector<char> small(bytes - ms->o_cl_off);
+    char *sb = small.data() - ms->o_cl_off;                      // (indexed with the block's offsets)
+    std::vector<int64_t> off(c->n_clean, 0);
+    for (int i = 1; i < c->n_clean; ++i) off[i] = off[i - 1] + c->clean_len[i - 1];
+    memcpy(sb + ms->o_cl_off, off.data(), off.size() * 8);
+    memcpy(sb + ms->o_cl_len, c->clean_len, (size_t)c->n_clean * 8);
+    off.assign(c->n_noise, 0);
+    for (int i = 1; i < c->n_noise; ++i) off[i] = off[i - 1] + c->noise_len[i - 1];
+    memcpy(sb + ms->o_no_off, off.data(), off.size() * 8);
+    memcpy(sb + ms->o_no_len, c->noise_len, (size_t)c->n_noise * 8);
+    memcpy(sb + ms->o_mean, c->mean, (size_t)D * 4);
+    memcpy(sb + ms->o_istd, c->inv_std, (size_t)D * 4);
+    wave_window_twiddles(log2M, (float *)(sb + ms->o_win), (float2 *)(sb + ms->o_tw));
+    hipError_t e = hipMemcpy(ms->corpus + ms->o_clean, c->clean_pcm, nc * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ms->corpus + ms->o_noise, c->noise_pcm, nn * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ms->corpus + ms->o_cl_off, small.data(), small.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, std::string("bp_set_mix_corpus: ") + hipGetErrorString(e)); }
+    return BP_OK;
+}
+
+extern "C" int bp_train_mix(bp_handle *h, int n_mix, const bp_mixture *m, const int *order)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_train_mix", n_mix, m, c)) != BP_OK || (r = check_order("bp_train_mix", c, order)) != BP_OK) return r;
+    if (h->Bg != h->B) return fail(BP_ERR_STATE, "bp_train_mix: data-parallel handle (global_bunchsize != bunchsize)");
+    if ((r = generate(h, c, m, order, false, nullptr, nullptr, nullptr)) != BP_OK) return r;
+    if ((r = window_adopt(h, (int)c.frames, h->mix->D, h->mix->ctx, h->mix->nat, true)) != BP_OK) return r;
+    if (c.frames % h->B)
+        printf("this bunch has only %d samples and is ignored.\n", (int)(c.frames % h->B));   // BP_GPU.cu:317
+    return bp_train_resident(h, 0, (int)c.frames);
+}
+
+extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq_err_sum)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_cv_mix", n_mix, m, c)) != BP_OK) return r;
+    if (!sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_mix: null argument");
+    const int n = (int)c.frames, L = h->L, sL = h->s[L - 1], ldL = h->ld[L - 1];
+    if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;
+    float *targ_d;
+    if ((r = generate(h, c, m, nullptr, false, nullptr, &targ_d, nullptr)) != BP_OK) return r;
+    // forward without staging the targets (as bp_cv_chunk_windows); the target frames stay in the set for the sum below
+    if ((r = window_adopt(h, n, h->mix->D, h->mix->ctx, h->mix->nat, false)) != BP_OK) return r;
+    if ((r = forward_resident(h, n)) != BP_OK) return r;
+    std::vector<float> tg((size_t)n * sL);
+    HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * ldL * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(tg.data(), targ_d, tg.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float squared_err = 0.0f;
+    for (int j = 0; j < n; ++j) {                                // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
+        const float *t = tg.data() + (size_t)j * sL;
+        for (int d = 0; d < sL; ++d) {
+            const float e = h->host_out[(size_t)j * ldL + d] - t[d];
+            squared_err = squared_err + e * e;
+        }
+    }
+    *sq_err_sum = squared_err;
+    return BP_OK;
+}
+
+extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, float *fea, float *lps, float *targ, float *nat, float *pcm)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_mix_features", n_mix, m, c)) != BP_OK) return r;
+    MixState *ms = h->mix;
+    if (nat && !ms->nat) return fail(BP_ERR_ARG, "bp_mix_features: nat requested for a net without the noise-aware block");
+    const int D = ms->D, n = (int)c.frames;
+    float *rows_d, *targ_d, *nat_d;
+    if ((r = generate(h, c, m, nullptr, lps != nullptr, &rows_d, &targ_d, &nat_d)) != BP_OK) return r;
+    if ((r = window_adopt(h, n, D, ms->ctx, ms->nat, true)) != BP_OK) return r;
+    std::vector<float> rows(fea ? c.rows * D : 0), x(pcm ? c.segs * ms->hop : 0);
+    if (fea) HIPCHK(hipMemcpyAsync(rows.data(), rows_d, rows.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    if (lps) HIPCHK(hipMemcpyAsync(lps, ms->lps.p, c.frames * D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (targ) HIPCHK(hipMemcpyAsync(targ, targ_d, c.frames * ms->sL * 4, hipMemcpyDeviceToHost, h->stream));
+    if (nat) HIPCHK(hipMemcpyAsync(nat, nat_d, (size_t)c.n * D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (pcm) HIPCHK(hipMemcpyAsync(x.data(), ms->x.p, x.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    size_t dst = 0;
+    for (int i = 0; i < c.n; ++i) {
+        const int T = c.F[i + 1] - c.F[i];
+        if (fea)
+            memcpy(fea + (size_t)c.F[i] * D, rows.data() + ((size_t)c.F[i] + (size_t)i * (ms->ctx - 1) + ms->toff) * D, (size_t)T * D * 4);
+        if (pcm) {
+            const int64_t len = ms->clean_len[m[i].clean];
+            memcpy(pcm + dst, x.data() + ((size_t)c.Fs[i] + 1) * ms->hop, (size_t)len * 4);
+            dst += (size_t)len;
+        }
+    }
+    return BP_OK;
+}
+
+extern "C" int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const int64_t *noise_len, int n_snr,
+                           const float *snr_db, bp_mixture *out)
+{
+    if (n_clean < 1 || per_clean < 1 || n_noise < 1 || n_snr < 1 || !noise_len || !snr_db || !out)
+        return fail(BP_ERR_ARG, "bp_mix_plan: need n_clean, per_clean, n_noise, n_snr >= 1 and non-null arrays");
+    if ((int64_t)n_clean * per_clean > INT32_MAX) return fail(BP_ERR_ARG, "bp_mix_plan: too many mixtures");
+    for (int k = 0; k < n_noise; ++k)
+        if (noise_len[k] < 1 || noise_len[k] >= ((int64_t)1 << 32)) return fail(BP_ERR_ARG, "bp_mix_plan: noise_len must lie in [1, 2^32)");
+    for (int k = 0; k < n_snr; ++k)
+        if (!std::isfinite(snr_db[k])) return fail(BP_ERR_ARG, "bp_mix_plan: SNR is not finite");
+    const int n = n_clean * per_clean;
+    for (int m = 0; m < n; ++m) {
+        uint32_t c[4] = {(uint32_t)m, 0, 0, 0};
+        philox(c, seed);
+        bp_mixture &x = out[m];
+        memset(&x, 0, sizeof(x));
+        x.clean = m / per_clean;
+        x.noise = (int)scale(c[0], (uint64_t)n_noise);
+        x.offset = (int64_t)scale(c[1], (uint64_t)noise_len[x.noise]);
+        x.snr_db = snr_db[scale(c[2], (uint64_t)n_snr)];
+    }
+    for (int i = n - 1; i > 0; --i) {
+        const int j = (int)scale(word0(seed, (uint32_t)i, 0, 1), (uint64_t)i + 1);
+        const bp_mixture t = out[i]; out[i] = out[j]; out[j] = t;
+    }
+    return BP_OK;
+}
+
+extern "C" int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order)
+{
+    if (n < 0 || (n > 0 && !order)) return fail(BP_ERR_ARG, "bp_mix_shuffle: bad n or null order");
+    for (int i = 0; i < n; ++i) order[i] = i;
+    for (int i = n - 1; i > 0; --i) {
+        const int j = (int)scale(word0(seed, (uint32_t)i, stream, 2), (uint64_t)i + 1);
+        const int t = order[i]; order[i] = order[j]; order[j] = t;
+    }
+    return BP_OK;
+}

@@ -1,6 +1,6 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), part 1 of 4: the device state of one BP_GPU replacement
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), part 1 of 5: the device state of one BP_GPU replacement
 // object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.  The handle and
-// what the other three translation units use of this one: bp_handle.h.
+// what the other four translation units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,6 +73,7 @@ extern "C" int bp_destroy(bp_handle *h)
     for (auto &ws : h->wset) for (auto &r : ws.r) if (r.p) (void)hipFree(r.p);
     for (auto &r : h->wave) if (r.p) (void)hipFree(r.p);
     for (auto &r : h->wave_pin) if (r.p) (void)hipHostFree(r.p);
+    mix_free(h);
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
     if (h->ev_retired) (void)hipEventDestroy(h->ev_retired);
@@ -949,24 +950,27 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
     return BP_OK;
 }
 
-// A window chunk that kernels on h->stream write (bp_wave.hip): the same staging set, tables and bookkeeping as an upload
-// without targets.  Everything queued on h->stream before the writers has finished with that set by stream order.
-int window_reserve(bp_handle *h, size_t rows_b, size_t nat_b, size_t n_samples, float **rows, float **nat, int **win_start, int **nat_row)
+// A window chunk that kernels on h->stream write (bp_wave.hip, bp_mix.hip): the same staging set, tables and bookkeeping as an
+// upload.  Everything queued on h->stream before the writers has finished with that set by stream order.  targ_b == 0: no target
+// frames (targ is left alone).  The tables lie win_start | targ_frame | nat_row, n_samples entries each, from *tables on.
+int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, size_t n_samples, float **rows, float **targ, float **nat,
+                   int **tables)
 {
     { const int r = ensure_stage_tiles(h); if (r != BP_OK) return r; }
     const int set = 1 - h->wcur;
     int r;
-    if ((r = raw_reserve(h, set, 0, rows_b)) != BP_OK || (r = raw_reserve(h, set, 2, nat_b)) != BP_OK ||
-        (r = raw_reserve(h, set, 3, 3 * n_samples * 4)) != BP_OK)
+    if ((r = raw_reserve(h, set, 0, rows_b)) != BP_OK || (r = raw_reserve(h, set, 1, targ_b)) != BP_OK ||
+        (r = raw_reserve(h, set, 2, nat_b)) != BP_OK || (r = raw_reserve(h, set, 3, 3 * n_samples * 4)) != BP_OK)
         return r;
     bp_handle::Raw *rw = h->wset[set].r;
     *rows = (float *)rw[0].p; *nat = (float *)rw[2].p;
-    *win_start = (int *)rw[3].p; *nat_row = *win_start + 2 * n_samples;
+    if (targ) *targ = (float *)rw[1].p;
+    *tables = (int *)rw[3].p;
     return BP_OK;
 }
-int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat)
+int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat, bool with_targ)
 {
-    const int r = adopt_set(h, 1 - h->wcur, n_samples, fea_dim, context, false, nat);
+    const int r = adopt_set(h, 1 - h->wcur, n_samples, fea_dim, context, with_targ, nat);
     if (r != BP_OK) return r;
     h->windows = true;
     h->wgen++; h->pre.valid = false; h->next_first = -1;

@@ -1,4 +1,4 @@
-// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 4: the signal layer around the network.  Noisy PCM
+// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 5: the signal layer around the network.  Noisy PCM
 // in, enhanced PCM out (bp_enhance_waves), and the same analysis alone for feature extraction (bp_wave_lps).  gfx950 only.
 //
 // One signal definition, derived from fea_dim: n_fft = 2 (fea_dim - 1), a power of two in 64 .. 2048;
@@ -24,86 +24,22 @@
 #include <string>
 #include <vector>
 
+#include "bp_fft.h"
 #include "bp_handle.h"
-
-namespace {
-
-constexpr int WAVE_THREADS = 256;
-constexpr float LN_FLOOR = -23.025850929940457f;   // ln(1e-10)
-
-// LDS index of complex point i: one float2 of padding after every 32, so that the power-of-two strides of the butterfly
-// stages (and the bit-reversed scatter) do not pile up on a few banks of ds_read_b64 / ds_write_b64.
-__device__ __forceinline__ int lp(int i) { return i + (i >> 5); }
-__host__ __device__ inline size_t lds_bytes(int M) { return (size_t)(M + M / 32 + 1) * sizeof(float2); }
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
-
-// Radix-2 decimation-in-time FFT of M points in LDS (input in bit-reversed order).  tw[j] = exp(-2 pi i j / n_fft), n_fft = 2M;
-// inverse: conjugated twiddles, no scaling.
-__device__ void fft_lds(float2 *z, int M, const float2 *__restrict__ tw, bool inverse)
-{
-    for (int h = 1; h < M; h <<= 1) {
-        const int tstep = M / h;                                // exp(-2 pi i (j%h) / (2h)) = tw[(j%h) * (2M / (2h))]
-        for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
-            const int jh = j & (h - 1), i0 = ((j - jh) << 1) + jh, i1 = i0 + h;
-            const float2 w = tw[jh * tstep];
-            const float2 a = z[lp(i0)], bb = z[lp(i1)];
-            const float2 b = inverse ? cmulc(bb, w) : cmul(bb, w);
-            z[lp(i0)] = make_float2(a.x + b.x, a.y + b.y);
-            z[lp(i1)] = make_float2(a.x - b.x, a.y - b.y);
-        }
-        __syncthreads();
-    }
-}
-
-// Sentence of global frame g: the last s with F[s] <= g (F[n_sent] = all frames).  Uniform per workgroup.
-__device__ __forceinline__ int sentence_of(const int *__restrict__ F, int n_sent, int g)
-{
-    int lo = 0, hi = n_sent - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (F[mid] <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
-}  // namespace
-
-struct WaveAnaArgs {
-    const float *pcm; const float *win; const float2 *tw; const int *F; const float *mean, *inv_std;
-    int n_sent, log2M, D, hop, ctx, toff;
-    float2 *Y;            // [frames][D] noisy spectrum, or null
-    float *lps;           // [frames][D] un-normalised LPS, or null
-    float *rows;          // staged normalised rows [frames + n_sent (ctx - 1)][D], or null
-    int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
-};
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_analysis(const WaveAnaArgs a)
 {
     extern __shared__ float2 z[];
-    const int g = blockIdx.x, M = 1 << a.log2M, N = 2 * M, tid = threadIdx.x;
+    const int g = blockIdx.x, M = 1 << a.log2M, tid = threadIdx.x;
     const int s = sentence_of(a.F, a.n_sent, g), t = g - a.F[s], T = a.F[s + 1] - a.F[s];
-    const float *x = a.pcm + (size_t)(g + s) * a.hop;
-    // windowed samples as M complex points z[m] = (x[2m], x[2m+1]), scattered to bit-reversed positions; 16-byte loads
-    for (int q = tid; q < N / 4; q += blockDim.x) {
-        const float4 v = *reinterpret_cast<const float4 *>(x + 4 * q), w = *reinterpret_cast<const float4 *>(a.win + 4 * q);
-        const int m0 = 2 * q, m1 = 2 * q + 1;
-        z[lp((int)(__brev((unsigned)m0) >> (32 - a.log2M)))] = make_float2(v.x * w.x, v.y * w.y);
-        z[lp((int)(__brev((unsigned)m1) >> (32 - a.log2M)))] = make_float2(v.z * w.z, v.w * w.w);
-    }
-    __syncthreads();
-    fft_lds(z, M, a.tw, false);
-    // split step: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i, k = 0 .. M
+    rfft_frame(z, a.pcm + (size_t)(g + s) * a.hop, a.win, a.tw, a.log2M);
     const int base = a.F[s] + s * (a.ctx - 1);          // first staged row of the sentence
     for (int k = tid; k <= M; k += blockDim.x) {
-        const float2 zk = z[lp(k & (M - 1))], zm = z[lp((M - k) & (M - 1))];
-        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-        const float2 X = k == 0 ? make_float2(zk.x + zk.y, 0.0f) : k == M ? make_float2(zk.x - zk.y, 0.0f)
-                                                                         : make_float2(e.x + (a.tw[k].x * o.x - a.tw[k].y * o.y),
-                                                                                       e.y + (a.tw[k].x * o.y + a.tw[k].y * o.x));
+        const float2 X = rfft_bin(z, a.tw, M, k);
         const size_t gi = (size_t)g * a.D + k;
         if (a.Y) a.Y[gi] = X;
         const float p = X.x * X.x + X.y * X.y;
-        const float l = p > 1e-10f ? logf(p) : LN_FLOOR;
+        const float l = lps_of(p);
         if (a.lps) a.lps[gi] = l;
         if (a.rows) {
             const float v = (l - a.mean[k]) * a.inv_std[k];
@@ -195,9 +131,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_overlap(const float *__r
 }
 
 // ------------------------------------------------------------------ host side
-namespace {
-
-int log2_fft(int fea_dim)
+int wave_log2_fft(int fea_dim)
 {
     if (fea_dim < 33 || fea_dim > 1025) return -1;
     const int n = 2 * (fea_dim - 1);
@@ -207,6 +141,44 @@ int log2_fft(int fea_dim)
     return l - 1;                                        // log2 of M = n_fft / 2
 }
 
+void wave_window_twiddles(int log2M, float *win, float2 *tw)
+{
+    const int M = 1 << log2M, N = 2 * M;
+    const double pi2 = 6.283185307179586476925286766559;
+    for (int k = 0; k < N; ++k) win[k] = (float)(0.54 - 0.46 * cos(pi2 * k / N));
+    for (int k = 0; k <= M; ++k) tw[k] = make_float2((float)cos(pi2 * k / N), (float)-sin(pi2 * k / N));
+}
+
+// Grow-only buffers (device or pinned host).
+int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st)
+{
+    if (bytes <= r.bytes) return BP_OK;
+    if (r.p) {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)(pinned ? hipHostFree(r.p) : hipFree(r.p)); r.p = nullptr; r.bytes = 0;
+    }
+    const size_t want = bytes + bytes / 4 + 4096;
+    const hipError_t e = pinned ? hipHostMalloc(&r.p, want) : hipMalloc(&r.p, want);
+    if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("signal-layer buffers: ") + hipGetErrorString(e));
+    r.bytes = want;
+    return BP_OK;
+}
+
+hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st)
+{
+    hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)frames), dim3(WAVE_THREADS), lds_bytes(1 << a.log2M), st, a);
+    return hipGetLastError();
+}
+
+hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, int ctx, int toff, float *nat, hipStream_t st)
+{
+    hipLaunchKernelGGL(bp_wave_nat, dim3((unsigned)(((D + WAVE_THREADS - 1) / WAVE_THREADS) * n_sent)), dim3(WAVE_THREADS), 0, st,
+                       rows, F, D, ctx, toff, nat);
+    return hipGetLastError();
+}
+
+namespace {
+
 // Frame plan of a call: T_s per sentence, F = prefix sums.  Checked before any device work.
 struct Plan {
     int M, N, hop, log2M, n_sent;
@@ -215,7 +187,7 @@ struct Plan {
 };
 int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, Plan &p)
 {
-    p.log2M = log2_fft(fea_dim);
+    p.log2M = wave_log2_fft(fea_dim);
     if (p.log2M < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
     if (n_sent < 1 || !sent_len || !pcm) return fail(BP_ERR_ARG, std::string(who) + ": no sentences or null pointer");
     p.M = 1 << p.log2M; p.N = 2 * p.M; p.hop = p.M; p.n_sent = n_sent;
@@ -229,21 +201,6 @@ int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, co
     }
     p.frames = f;
     p.padded = (f + (size_t)n_sent) * p.hop;             // sentence s: T_s + 1 segments of hop samples
-    return BP_OK;
-}
-
-// Grow-only buffers (device or pinned host).
-int grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st)
-{
-    if (bytes <= r.bytes) return BP_OK;
-    if (r.p) {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)(pinned ? hipHostFree(r.p) : hipFree(r.p)); r.p = nullptr; r.bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4 + 4096;
-    const hipError_t e = pinned ? hipHostMalloc(&r.p, want) : hipMalloc(&r.p, want);
-    if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("wave buffers: ") + hipGetErrorString(e));
-    r.bytes = want;
     return BP_OK;
 }
 
@@ -263,11 +220,7 @@ void wave_in_fill(char *hb, const WaveIn &w, const Plan &p, int D, const float *
 {
     memcpy(hb + w.F, p.F.data(), p.F.size() * 4);
     if (mean) { memcpy(hb + w.mean, mean, (size_t)D * 4); memcpy(hb + w.istd, inv_std, (size_t)D * 4); }
-    float *win = (float *)(hb + w.win);
-    float2 *tw = (float2 *)(hb + w.tw);
-    const double pi2 = 6.283185307179586476925286766559;
-    for (int k = 0; k < p.N; ++k) win[k] = (float)(0.54 - 0.46 * cos(pi2 * k / p.N));
-    for (int k = 0; k <= p.M; ++k) tw[k] = make_float2((float)cos(pi2 * k / p.N), (float)-sin(pi2 * k / p.N));
+    wave_window_twiddles(p.log2M, (float *)(hb + w.win), (float2 *)(hb + w.tw));
     float *x = (float *)(hb + w.pcm);
     memset(x, 0, p.padded * 4);
     size_t src = 0;
@@ -337,12 +290,13 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     const WaveIn w = wave_in_layout(p, D);
     const size_t y_b = p.frames * D * sizeof(float2), fr_b = p.frames * N * 4, pcm_b = p.padded * 4;
     int r;
-    if ((r = grow(h->wave[0], w.bytes, false, h->stream)) != BP_OK || (r = grow(h->wave[1], y_b, false, h->stream)) != BP_OK ||
-        (r = grow(h->wave[2], fr_b, false, h->stream)) != BP_OK || (r = grow(h->wave[3], pcm_b, false, h->stream)) != BP_OK ||
-        (r = grow(h->wave_pin[0], w.bytes, true, h->stream)) != BP_OK || (r = grow(h->wave_pin[1], pcm_b, true, h->stream)) != BP_OK)
+    if ((r = wave_grow(h->wave[0], w.bytes, false, h->stream)) != BP_OK || (r = wave_grow(h->wave[1], y_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(h->wave[2], fr_b, false, h->stream)) != BP_OK || (r = wave_grow(h->wave[3], pcm_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(h->wave_pin[0], w.bytes, true, h->stream)) != BP_OK || (r = wave_grow(h->wave_pin[1], pcm_b, true, h->stream)) != BP_OK)
         return r;
-    float *rows_d, *nat_d; int *ws_d, *nr_d;
-    if ((r = window_reserve(h, rows * D * 4, nat ? (size_t)c->n_sent * D * 4 : 0, p.frames, &rows_d, &nat_d, &ws_d, &nr_d)) != BP_OK) return r;
+    float *rows_d, *nat_d; int *tab_d;
+    if ((r = window_reserve(h, rows * D * 4, 0, nat ? (size_t)c->n_sent * D * 4 : 0, p.frames, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
+    int *ws_d = tab_d, *nr_d = tab_d + 2 * p.frames;
     if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;      // (forward_resident would; growing it here keeps its sync out of the sequence)
     // The pinned blocks are reused by the next call: the previous call ended in a synchronisation, so nothing still reads them.
     char *hin = (char *)h->wave_pin[0].p, *din = (char *)h->wave[0].p;
@@ -362,11 +316,9 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
         HIPCHK(hipGetLastError());
     }
     if (nat) {
-        hipLaunchKernelGGL(bp_wave_nat, dim3((unsigned)(((D + WAVE_THREADS - 1) / WAVE_THREADS) * c->n_sent)), dim3(WAVE_THREADS), 0, h->stream,
-                           (const float *)rows_d, F, D, ctx, toff, nat_d);
-        HIPCHK(hipGetLastError());
+        HIPCHK(wave_nat_launch(rows_d, F, c->n_sent, D, ctx, toff, nat_d, h->stream));
     }
-    window_adopt(h, n, D, ctx, nat);
+    window_adopt(h, n, D, ctx, nat, false);
     if ((r = forward_resident(h, n)) != BP_OK) return r;
     {
         WaveSynArgs a; memset(&a, 0, sizeof(a));

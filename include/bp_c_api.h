@@ -210,6 +210,56 @@ int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *c, float *o
 int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_len, const float *pcm, float *lps);
 
 /* ------------------------------------------------------------------------------------
+ * Training from clean speech and noise mixed on the device (no reference counterpart: the reference trains on Pfiles of
+ * mixtures made offline by outside tools).  INTEGRATION.md 1e.  The signal definition of bp_enhance_waves applies unchanged.
+ *
+ * bp_set_mix_corpus uploads n_clean clean sentences and n_noise noise recordings (fp32 in int16 units, back to back, each at least
+ * 1 sample long) plus the norm file, once; they stay resident on the handle until it is destroyed or the corpus is replaced.
+ * target: BP_MIX_LPS | _IRM | _IBM | _LPS_IRM | _LPS_IBM (columns concatenated in that order); layersizes[L-1] must be fea_dim
+ * (one part) or 2*fea_dim (two parts); layersizes[0] must be context*fea_dim or (context+1)*fea_dim (noise-aware block).
+ *
+ * A mixture {clean c, noise n, offset o, snr_db} (0 <= o < len(noise n), snr_db finite) of the clean sentence s (len_c samples):
+ *   v[i] = noise_n[(o + i) mod len_n], i < len_c                       (the noise wraps)
+ *   E_s = sum s^2, E_v = sum v^2, in double, fixed order; g = sqrt(E_s / (E_v 10^(snr_db/10))) in double rounded to fp32 once,
+ *   g = 0 when E_v = 0;  x[i] = fmaf(g, v[i], s[i])
+ * Features: the analysis of x, bit-identical to bp_wave_lps(x), normalised with mean / inv_std and stacked with replicated edge
+ * frames [+ the noise-aware block] exactly as bp_enhance_waves stages them; every frame of every mixture is one sample.
+ * Targets per frame, from S = analysis of s and N = analysis of the fp32 products g v[i]:
+ *   LPS = ln(max(|S|^2, 1e-10)) (not normalised), IRM = sqrt(|S|^2 / max(|S|^2 + |N|^2, 1e-10)), IBM = (|S|^2 > 10^(lc_db/10) |N|^2).
+ * Sample order: mixture-frame g runs over the frames of mixture 0, then mixture 1, ...  Row i of a call trains frame order[i]
+ * (order == NULL: the identity; otherwise a permutation of [0, sum T)).  Capacity: sum T + n_mix*(context-1) <= max_chunk_frames.
+ *
+ * bp_train_mix = BP_GPU::train (bp_train_chunk_windows) on that chunk: consecutive full bunches, the partial last one ignored.
+ * bp_cv_mix = BP_GPU::CrossValid (bp_cv_chunk_windows) on it in mixture-frame order: the same fp32 sum in the same order.
+ * bp_mix_features: the chunk's data, unshuffled (any output may be NULL): fea [sum T][fea_dim] the normalised row of every frame
+ * (as staged), lps [sum T][fea_dim] the noisy LPS, targ [sum T][layersizes[L-1]], nat [n_mix][fea_dim] (noise-aware nets only),
+ * pcm [sum len_c] the mixed samples x.  Each of the three calls leaves the chunk as the handle's resident window chunk.
+ * Every argument is checked before the device is touched (BP_ERR_ARG, the handle unchanged); BP_ERR_STATE without a corpus and
+ * on a data-parallel-attached handle.  fp32 and bf16 handles.  No float atomics: the same bits on every run.
+ *
+ * Host only (no device), one definition for the command-line tool and Python.  philox(c0, c1, c2, c3) = the 4 output words of
+ * Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and that counter; draws scale a word u to [0, n) as (u * n) >> 32.
+ * bp_mix_plan: for mixture m = 0 .. n_clean*per_clean-1, u = philox(m, 0, 0, 0): clean = m / per_clean, noise = (u0 * n_noise)
+ *   >> 32, offset = (u1 * noise_len[noise]) >> 32, snr_db = snr_db[(u2 * n_snr) >> 32].  Then the list is shuffled: for i from
+ *   n-1 down to 1, j = (philox(i, 0, 1, 0)[0] * (i+1)) >> 32, swap entries i and j.  noise_len[k] in [1, 2^32).
+ * bp_mix_shuffle: order = 0 .. n-1, then for i from n-1 down to 1, j = (philox(i, stream, 2, 0)[0] * (i+1)) >> 32, swap i and j. */
+enum { BP_MIX_LPS = 0, BP_MIX_IRM = 1, BP_MIX_IBM = 2, BP_MIX_LPS_IRM = 3, BP_MIX_LPS_IBM = 4 };
+typedef struct bp_mix_corpus {
+    int fea_dim, context, targ_offset, target; float lc_db;
+    const float *mean, *inv_std;                                   /* [fea_dim], the norm file */
+    int n_clean; const int64_t *clean_len; const float *clean_pcm; /* back to back */
+    int n_noise; const int64_t *noise_len; const float *noise_pcm;
+} bp_mix_corpus;
+typedef struct bp_mixture { int clean, noise; int64_t offset; float snr_db; } bp_mixture;
+int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c);
+int bp_train_mix(bp_handle *h, int n_mix, const bp_mixture *m, const int *order);
+int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq_err_sum);
+int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, float *fea, float *lps, float *targ, float *nat, float *pcm);
+int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const int64_t *noise_len, int n_snr, const float *snr_db,
+                bp_mixture *out);
+int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias

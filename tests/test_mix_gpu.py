@@ -1,0 +1,456 @@
+"""GPU tests of the training mixtures made on the device (bp_set_mix_corpus, bp_train_mix, bp_cv_mix, bp_mix_features; -m gpu)
+against the float64 restatement in tests/mix_np.py and against the window-chunk path fed with the same data from the host.
+Bars: mixed samples 1e-6 of max|x|; noisy LPS bit-identical to bp_wave_lps; clean LPS 1e-5 of the frame's largest magnitude
+(the analysis bar of test_wave_gpu.py); IRM 1e-4 absolute where the bin carries 1e-3 of the frame's largest magnitude; IBM exact
+away from the threshold; training and CV bit-identical to bp_train_chunk_windows / bp_cv_chunk_windows."""
+import os
+
+import numpy as np
+import pytest
+
+import mix_np as MX
+import wave_np as WN
+
+pytestmark = pytest.mark.gpu
+
+
+def _corpus(rng, D):
+    n_fft, hop = WN.geometry(D)
+    clean = [x + np.float32(0.0) for x in WN.make_sentences(rng, [1, 3 * n_fft + 5, 2 * hop, 5000])]   # (no -0.0 samples)
+    clean[2][:] = 0.0                                            # silent clean sentence
+    noise = WN.make_sentences(rng, [37, 6000, 500], scale=2000.0)
+    noise[2][:] = 0.0                                            # silent noise
+    mixes = [(0, 1, 5999, 0.0),                                  # 1-sample sentence, offset at len - 1
+             (1, 0, 5, -10.0),                                   # noise shorter than the sentence: wraps
+             (1, 2, 0, 5.0),                                     # silent noise: g = 0, x == s
+             (2, 1, 100, 0.0),                                   # silent clean
+             (3, 1, 5999, 30.0),                                 # offset at len - 1, wraps
+             (3, 0, 36, -10.0)]
+    return clean, noise, mixes
+
+
+def _plan(pkg, mixes):
+    p = np.zeros(len(mixes), pkg.MIXTURE_DTYPE)
+    for i, (c, n, o, s) in enumerate(mixes):
+        p[i] = (c, n, o, s)
+    return p
+
+
+def _norm(D, rng):
+    return rng.normal(10.0, 2.0, D).astype(np.float32), rng.uniform(0.2, 0.5, D).astype(np.float32)
+
+
+# ---- 1. mixed samples, features and targets
+@pytest.mark.parametrize("D", [33, 129, 257])
+def test_features_match_restatement(pkg, D, parity_record):
+    rng = np.random.default_rng(D)
+    clean, noise, mixes = _corpus(rng, D)
+    mean, istd = _norm(D, rng)
+    ctx, toff, lc = 5, 2, 5.0
+    ls = [(ctx + 1) * D, 32, 2 * D]
+    W, b = pkg.glorot_net(ls, seed=1, beta=0.5)
+    g = pkg.BP_GPU(1, 3, ls, 16, 0.0, 0.0, 0.0, W, b, max_chunk_frames=20000)
+    plan = _plan(pkg, mixes)
+    rec = {}
+    try:
+        for target in (MX.LPS_IRM, MX.LPS_IBM):                  # (the second call replaces the corpus)
+            g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, target, lc)
+            got = g.mix_features(plan)
+            ref = MX.features(clean, noise, mixes, D, mean.astype(np.float64), istd.astype(np.float64), target, lc)
+            frames = [r["z"].shape[0] for r in ref]
+            assert got["fea"].shape[0] == sum(frames)
+            # mixed samples
+            pcm = np.split(got["pcm"], np.cumsum([clean[c].size for c, _, _, _ in mixes])[:-1])
+            for (c, n, o, s), x, r in zip(mixes, pcm, ref):
+                assert np.abs(x - r["x"]).max() <= 1e-6 * np.abs(r["x"]).max()
+            assert np.array_equal(pcm[2].view(np.uint32), clean[1].view(np.uint32)), "silent noise: x must equal s bit for bit"
+            assert not pcm[3].any()
+            # noisy LPS: bit-identical to the analysis of the mixed samples; normalised rows
+            lps = pkg.wave_lps(0, D, pcm)
+            assert np.array_equal(got["lps"].view(np.uint32), np.concatenate(lps).view(np.uint32))
+            zref = (got["lps"] - mean) * istd
+            assert np.abs(got["fea"] - zref).max() <= 1e-6 * max(1.0, float(np.abs(zref).max()))
+            # NAT rows from the normalised rows
+            f0 = 0
+            for m, T in enumerate(frames):
+                z = got["fea"][f0:f0 + T].astype(np.float64)
+                assert np.abs(got["nat"][m] - WN.nat_row(z)).max() <= 1e-5 * max(1.0, float(np.abs(z).max()))
+                f0 += T
+            # targets
+            tg = np.split(got["targ"], np.cumsum(frames)[:-1])
+            worst_lps = worst_irm = 0.0
+            near = faint = 0
+            for r, t in zip(ref, tg):
+                S, N = r["S"], r["N"]
+                magS = np.abs(S)
+                for f in range(S.shape[0]):
+                    if magS[f].max() > 0:
+                        worst_lps = max(worst_lps, float(np.abs(np.exp(t[f, :D].astype(np.float64) / 2) - magS[f]).max() / magS[f].max()))
+                    else:
+                        assert np.all(t[f, :D] == np.float32(WN.LN_FLOOR))
+                big = np.maximum(magS, np.abs(N))
+                sel = big >= 1e-3 * big.max(1, keepdims=True)
+                if target == MX.LPS_IRM:
+                    irm = r["targ"][:, D:]
+                    if sel.any():
+                        worst_irm = max(worst_irm, float(np.abs(t[:, D:] - irm)[sel].max()))
+                else:
+                    # exact except near the threshold (1e-3 relative in float64) and on bins that carry less than 1e-3 of the
+                    # frame's largest magnitude (where fp32 rounding of the FFT alone exceeds that margin)
+                    ibm = r["targ"][:, D:]
+                    near_thr = MX.ibm_margin(S, N, lc) < 1e-3
+                    close = near_thr | ~sel
+                    near += int(near_thr.sum())
+                    faint += int((~sel & ~near_thr).sum())
+                    assert np.array_equal(t[:, D:][~close], ibm[~close])
+                    assert set(np.unique(t[:, D:])) <= {0.0, 1.0}
+            assert worst_lps <= 1e-5, worst_lps
+            assert worst_irm <= 1e-4, worst_irm
+            rec["lps_%d" % target], rec["irm_%d" % target] = worst_lps, worst_irm
+            rec["ibm_near_threshold_%d" % target], rec["ibm_faint_bins_%d" % target] = near, faint
+    finally:
+        g.close()
+    parity_record(**rec)
+
+
+@pytest.mark.parametrize("target", [MX.LPS, MX.IRM, MX.IBM])
+def test_single_part_targets_match_restatement(pkg, target, parity_record):
+    """layersizes[-1] == fea_dim: the target row is that one part (no NAT block)."""
+    D, ctx, toff, lc = 129, 3, 1, 3.0
+    rng = np.random.default_rng(70 + target)
+    clean, noise, mixes = _corpus(rng, D)
+    mean, istd = _norm(D, rng)
+    ls = [ctx * D, 32, D]
+    W, b = pkg.glorot_net(ls, seed=1, beta=0.5)
+    g = pkg.BP_GPU(1, 3, ls, 16, 0.0, 0.0, 0.0, W, b, max_chunk_frames=20000)
+    try:
+        g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, target, lc)
+        got = g.mix_features(_plan(pkg, mixes))
+    finally:
+        g.close()
+    assert got["nat"] is None and got["targ"].shape[1] == D
+    ref = MX.features(clean, noise, mixes, D, mean.astype(np.float64), istd.astype(np.float64), target, lc)
+    t = got["targ"].astype(np.float64)
+    S = np.concatenate([r["S"] for r in ref]); N = np.concatenate([r["N"] for r in ref])
+    want = np.concatenate([r["targ"] for r in ref])
+    big = np.maximum(np.abs(S), np.abs(N))
+    sel = big >= 1e-3 * np.maximum(big.max(1, keepdims=True), 1e-30)
+    if target == MX.LPS:
+        mag = np.abs(S)
+        fr = mag.max(1) > 0
+        err = float((np.abs(np.exp(t[fr] / 2) - mag[fr]).max(1) / mag[fr].max(1)).max())
+        assert np.all(t[~fr] == np.float32(WN.LN_FLOOR))
+        assert err <= 1e-5, err
+    elif target == MX.IRM:
+        err = float(np.abs(t - want)[sel].max())
+        assert np.all((t >= 0) & (t <= 1))
+        assert err <= 1e-4, err
+    else:
+        near_thr = MX.ibm_margin(S, N, lc) < 1e-3
+        keep = sel & ~near_thr
+        err = int((t != want)[keep].sum())
+        assert err == 0
+        assert set(np.unique(t)) <= {0.0, 1.0}
+        assert 0 < t.mean() < 1
+        parity_record(ibm_near_threshold=int(near_thr.sum()), ibm_faint_bins=int((~sel & ~near_thr).sum()))
+    parity_record(err=err)
+
+
+# ---- 2. training equivalence with the window-chunk path
+def _train_corpus(rng, D):
+    clean = WN.make_sentences(rng, [1, 300, 1000, 2500, 777, 64])
+    noise = WN.make_sentences(rng, [50, 5000, 3], scale=1500.0)
+    return clean, noise
+
+
+def _pair(pkg, D, target, compute_dtype=0, dropout=1, nat=True):
+    ctx, toff, B = 3, 1, 32
+    sL = D * (2 if target in (MX.LPS_IRM, MX.LPS_IBM) else 1)
+    ls = [(ctx + (1 if nat else 0)) * D, 64, 48, sL]
+    W, b = pkg.glorot_net(ls, seed=5, beta=0.5)
+    kw = dict(dropoutflag=dropout, visible_omit=0.1, hid_omit=0.2, seed=99, max_chunk_frames=4000, compute_dtype=compute_dtype)
+    return [pkg.BP_GPU(1, len(ls), ls, B, 0.01, 0.5, 1e-4, W, b, **kw) for _ in range(2)], ctx, toff
+
+
+def _host_chunk(g, plan, ctx, toff, order=None):
+    f = g.mix_features(plan)
+    frames = g.mix_frames(plan)
+    rows = MX.staged_rows(f["fea"], frames, ctx, toff)
+    tg = np.zeros((rows.shape[0], f["targ"].shape[1]), np.float32)
+    tg[:f["targ"].shape[0]] = f["targ"]
+    ws, tf, nr = MX.window_tables(frames, ctx, order)
+    return rows, tg, ws, tf, f["nat"], nr
+
+
+def _bits_equal(a, b):
+    (wa, ba), (da, dba) = a.get_weights(), a.get_deltas()
+    (wb, bb), (db, dbb) = b.get_weights(), b.get_deltas()
+    for l in range(1, a.numlayers):
+        for u, v in ((wa[l], wb[l]), (ba[l], bb[l]), (da[l], db[l]), (dba[l], dbb[l])):
+            if not np.array_equal(u.view(np.uint32), v.view(np.uint32)):
+                return False
+    return True
+
+
+@pytest.mark.parametrize("target,compute_dtype", [(MX.LPS, 0), (MX.IRM, 0), (MX.IBM, 0), (MX.LPS_IRM, 0), (MX.LPS_IBM, 0),
+                                                  (MX.LPS, 1), (MX.LPS_IBM, 1)])
+def test_training_equals_window_path(pkg, target, compute_dtype):
+    D = 33
+    rng = np.random.default_rng(40 + target)
+    clean, noise = _train_corpus(rng, D)
+    mean, istd = _norm(D, rng)
+    (a, b), ctx, toff = _pair(pkg, D, target, compute_dtype)
+    plan = pkg.mix_plan(7 + target, len(clean), 2, [x.size for x in noise], [-5, 0, 5, 10])
+    try:
+        for g in (a, b):
+            g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, target, 3.0)
+        calls = [(plan[:7], True), (plan[7:], False), (plan[2:9], True)]
+        for ci, (p, shuffled) in enumerate(calls):
+            T = int(a.mix_frames(p).sum())
+            order = pkg.mix_shuffle(345, ci, T) if shuffled else None
+            a.train_mix(p, order)
+            rows, tg, ws, tf, nat, nr = _host_chunk(b, p, ctx, toff, order)
+            b.train_windows(rows, tg, ctx, ws, tf, nat=nat, nat_row=nr)
+        assert _bits_equal(a, b)
+        ea = a.CrossValid_mix(plan)
+        rows, tg, ws, tf, nat, nr = _host_chunk(b, plan, ctx, toff)
+        eb = b.CrossValid_windows(rows, tg, ctx, ws, tf, nat=nat, nat_row=nr)
+        assert np.float32(ea).view(np.uint32) == np.float32(eb).view(np.uint32), (ea, eb)
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 3. determinism
+def test_two_handles_same_bits(pkg):
+    D = 129
+    rng = np.random.default_rng(3)
+    clean, noise = _train_corpus(rng, D)
+    mean, istd = _norm(D, rng)
+    (a, b), ctx, toff = _pair(pkg, D, MX.LPS_IBM)
+    plan = pkg.mix_plan(11, len(clean), 3, [x.size for x in noise], [0, 10])
+    try:
+        for g in (a, b):
+            g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, MX.LPS_IBM)
+            g.train_mix(plan, pkg.mix_shuffle(1, 0, int(g.mix_frames(plan).sum())))
+            g.train_mix(plan[:5])
+        assert _bits_equal(a, b)
+        fa, fb = a.mix_features(plan), b.mix_features(plan)
+        for k in ("fea", "lps", "targ", "nat", "pcm"):
+            assert np.array_equal(fa[k].view(np.uint32), fb[k].view(np.uint32)), k
+        assert np.float32(a.CrossValid_mix(plan)).view(np.uint32) == np.float32(b.CrossValid_mix(plan)).view(np.uint32)
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 4. argument checks; a training call afterwards gives the bits of a handle that never saw them
+def test_errors_leave_handle_unchanged(pkg):
+    D = 33
+    rng = np.random.default_rng(4)
+    clean, noise = _train_corpus(rng, D)
+    mean, istd = _norm(D, rng)
+    (a, b), ctx, toff = _pair(pkg, D, MX.LPS)
+    plan = pkg.mix_plan(2, len(clean), 1, [x.size for x in noise], [0.0])
+    try:
+        with pytest.raises(pkg.BPError, match="status -3"):          # no corpus yet
+            a.train_mix(plan)
+        with pytest.raises(pkg.BPError, match="status -3"):
+            a.CrossValid_mix(plan)
+        with pytest.raises(pkg.BPError, match="status -3"):
+            a.mix_features(plan)
+        bad_corpus = [dict(target=MX.LPS_IRM),                        # layersizes[last] is fea_dim, not 2 fea_dim
+                      dict(context=5), dict(targ_offset=3), dict(targ_offset=-1), dict(target=7), dict(lc_db=float("nan"))]
+        for kw in bad_corpus:
+            args = dict(context=ctx, targ_offset=toff, target=MX.LPS, lc_db=5.0)
+            args.update(kw)
+            with pytest.raises(pkg.BPError, match="status -1"):
+                a.set_mix_corpus(clean, noise, mean, istd, args["context"], args["targ_offset"], args["target"], args["lc_db"])
+        with pytest.raises(pkg.BPError, match="status -1"):          # fea_dim outside 1d
+            a.set_mix_corpus(clean, noise, mean[:32], istd[:32], ctx, toff, MX.LPS)
+        with pytest.raises(pkg.BPError, match="status -1"):          # an empty recording
+            a.set_mix_corpus(clean + [np.zeros(0, np.float32)], noise, mean, istd, ctx, toff, MX.LPS)
+        for g in (a, b):
+            g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, MX.LPS)
+        T = int(a.mix_frames(plan).sum())
+        lens = [x.size for x in noise]
+        for field, val in (("clean", len(clean)), ("clean", -1), ("noise", len(noise)), ("noise", -1), ("offset", -1),
+                           ("snr_db", np.nan), ("snr_db", np.inf)):
+            p = plan.copy()
+            p[field][1] = val
+            with pytest.raises(pkg.BPError, match="status -1"):
+                a.train_mix(p)
+            with pytest.raises(pkg.BPError, match="status -1"):
+                a.CrossValid_mix(p)
+        p = plan.copy()
+        p["offset"][0] = lens[p["noise"][0]]                          # offset == len(noise)
+        with pytest.raises(pkg.BPError, match="status -1"):
+            a.train_mix(p)
+        for order in (np.zeros(T, np.int32), np.arange(1, T + 1, dtype=np.int32), -np.arange(T, dtype=np.int32)):
+            with pytest.raises(pkg.BPError, match="status -1"):       # not a permutation of [0, T)
+                a.train_mix(plan, order)
+        with pytest.raises(pkg.BPError, match="one entry per frame"):   # too short: refused by the wrapper
+            a.train_mix(plan, np.arange(T - 1, dtype=np.int32))
+        big = np.repeat(plan, 30)                                     # over the 4000-frame capacity
+        with pytest.raises(pkg.BPError, match="status -1"):
+            a.train_mix(big)
+        order = pkg.mix_shuffle(3, 0, T)
+        a.train_mix(plan, order)
+        b.train_mix(plan, order)
+        assert _bits_equal(a, b)
+        a.dp_attach(1, 0, "mix-%d" % os.getpid())
+        with pytest.raises(pkg.BPError, match="status -3"):
+            a.train_mix(plan)
+        with pytest.raises(pkg.BPError, match="status -3"):
+            a.CrossValid_mix(plan)
+        with pytest.raises(pkg.BPError, match="status -3"):
+            a.set_mix_corpus(clean, noise, mean, istd, ctx, toff, MX.LPS)
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 5. sanity: training on tone-plus-noise mixtures lowers the CV error
+def _tones(rng, n, length):
+    t = np.arange(length)
+    out = []
+    for _ in range(n):
+        x = sum(rng.uniform(1000, 6000) * np.sin(2 * np.pi * rng.uniform(0.02, 0.45) * t + rng.uniform(0, 6.3)) for _ in range(3))
+        out.append(np.round(x).astype(np.float32))
+    return out
+
+
+@pytest.mark.parametrize("target", [MX.LPS, MX.IBM])
+def test_training_lowers_cv_error(pkg, target, parity_record):
+    D, ctx, toff, B = 33, 3, 1, 64
+    rng = np.random.default_rng(50 + target)
+    clean = _tones(rng, 24, 2000)
+    noise = [rng.normal(0, 2000, 30000).astype(np.float32).round(), rng.normal(0, 500, 7000).astype(np.float32).round()]
+    ls = [ctx * D, 128, D]
+    W, b = pkg.glorot_net(ls, seed=8, beta=0.5)
+    lr = 0.005 if target == MX.LPS else 0.05
+    g = pkg.BP_GPU(1, 3, ls, B, lr, 0.5, 0.0, W, b, seed=3, max_chunk_frames=10000)
+    try:
+        if target == MX.IBM:
+            g.set_output(1, 0, 0)
+        lens = [x.size for x in noise]
+        g.set_mix_corpus(clean[:20], noise, np.zeros(D, np.float32), np.ones(D, np.float32), ctx, toff, target)
+        p0 = pkg.mix_plan(1, 20, 3, lens, [-5, 0, 5, 10])
+        L = g.mix_features(p0)["lps"].astype(np.float64)
+        mean, istd = L.mean(0).astype(np.float32), (1.0 / L.std(0)).astype(np.float32)
+        g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, target)
+        cv = pkg.mix_plan(1000, 24, 1, lens, [0, 5])
+        cv = cv[cv["clean"] >= 20]
+        e0 = g.CrossValid_mix(cv)
+        bunches = 0
+        for epoch in range(6):
+            plan = pkg.mix_plan(345 * epoch, 20, 3, lens, [-5, 0, 5, 10])
+            T = int(g.mix_frames(plan).sum())
+            g.train_mix(plan, pkg.mix_shuffle(345 * epoch, 0, T))
+            bunches += T // B
+        e1 = g.CrossValid_mix(cv)
+    finally:
+        g.close()
+    parity_record(cv_start=e0, cv_end=e1, bunches=bunches)
+    assert bunches >= 300
+    assert e1 < 0.8 * e0, (e0, e1)
+
+
+# ---- 6. the bpmix command-line tool
+def _write_pcm16(path, x, rate=8000):
+    import wave
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(rate)
+        w.writeframes(np.asarray(x, np.int16).tobytes())
+
+
+def _write_list(d, tag, xs):
+    for i, x in enumerate(xs):
+        _write_pcm16(d / ("%s%d.wav" % (tag, i)), x)
+    (d / (tag + ".list")).write_text("".join("%s\n" % (d / ("%s%d.wav" % (tag, i))) for i in range(len(xs))))
+    return str(d / (tag + ".list"))
+
+
+def _cut(frames, ctx, cap):
+    """the calls of bpmix: consecutive mixtures while frames + n_mix (ctx-1) <= traincache"""
+    calls, first, rows = [], 0, 0
+    for m, T in enumerate(frames):
+        if rows + T + ctx - 1 > cap:
+            calls.append((first, m)); first, rows = m, 0
+        rows += T + ctx - 1
+    return calls + [(first, len(frames))]
+
+
+def test_bpmix_epoch_matches_python_api(pkg, tmp_path, parity_record):
+    import subprocess
+    import pfile_util as PU
+    exe = str(pkg.LIB_PATH).replace("libbp_hip.so", "bpmix")
+    D, ctx, toff, B, cap, seed, per, lc = 65, 3, 1, 32, 200, 345, 2, 5.0
+    snrs = [-5.0, 0.0, 5.0, 10.0]
+    rng = np.random.default_rng(61)
+    ints = lambda n, s: np.clip(np.round(rng.normal(0, s, n)), -32768, 32767).astype(np.float32)
+    clean = [ints(n, 3000) for n in (1500, 400, 3000, 90, 2200, 1200)]
+    noise = [ints(n, 1500) for n in (5000, 700)]
+    cv_clean = [ints(n, 3000) for n in (1800, 600, 1000)]
+    lists = dict(clean_list=_write_list(tmp_path, "clean", clean), noise_list=_write_list(tmp_path, "noise", noise),
+                 cv_clean_list=_write_list(tmp_path, "cv", cv_clean))
+    common = ["clean_list=" + lists["clean_list"], "noise_list=" + lists["noise_list"], "fea_dim=%d" % D,
+              "snr_list=-5,0,5,10", "mix_per_clean=%d" % per, "init_randem_seed=%d" % seed, "traincache=%d" % cap]
+    # norm_out: the statistics of the epoch's noisy LPS
+    r = subprocess.run([exe] + common + ["norm_out=%s" % (tmp_path / "mix.norm")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1, r.stdout + r.stderr
+    v = (tmp_path / "mix.norm").read_text().split("\n")
+    m_cli, i_cli = np.array(v[1:1 + D], np.float64), np.array(v[2 + D:2 + 2 * D], np.float64)
+    ls = [(ctx + 1) * D, 64, 2 * D]
+    W, b = pkg.glorot_net(ls, seed=9, beta=0.5)
+    plan = pkg.mix_plan(seed, len(clean), per, [x.size for x in noise], snrs)
+    kw = dict(dropoutflag=1, visible_omit=0.1, hid_omit=0.2, max_chunk_frames=cap, output_activation=1, output_linear_cols=D)
+    g = pkg.BP_GPU(1, 3, ls, B, 0.01, 0.5, 1e-4, W, b, **kw)
+    try:
+        g.set_mix_corpus(clean, noise, np.zeros(D, np.float32), np.ones(D, np.float32), ctx, toff, "lps+ibm", lc)
+        L = np.concatenate([g.mix_features(plan[a:e])["lps"] for a, e in _cut(g.mix_frames(plan), ctx, cap)]).astype(np.float64)
+    finally:
+        g.close()
+    e_norm = max(float(np.abs(m_cli - L.mean(0)).max() / np.abs(L.mean(0)).max()),
+                 float(np.abs(i_cli - 1.0 / L.std(0)).max() / np.abs(1.0 / L.std(0)).max()))
+    assert e_norm <= 1e-6, e_norm
+    # one epoch, twice
+    PU.write_wts(str(tmp_path / "init.wts"), ls, W, b)
+    train = common + ["norm_file=%s" % (tmp_path / "mix.norm"), "cv_clean_list=" + lists["cv_clean_list"], "fea_context=%d" % ctx,
+                      "targ_offset=%d" % toff, "numlayers=3", "layersizes=%s" % ",".join(map(str, ls)), "bunchsize=%d" % B,
+                      "lrate=0.01", "momentum=0.5", "weightcost=0.0001", "dropoutflag=1", "visible_omit=0.1", "hid_omit=0.2",
+                      "target=lps+ibm", "lc_db=5", "output_act=sigmoid", "output_linear_dims=%d" % D,
+                      "initwts_file=%s" % (tmp_path / "init.wts")]
+    for run in (1, 2):
+        r = subprocess.run([exe] + train + ["outwts_file=%s" % (tmp_path / ("out%d.wts" % run)), "log_file=%s" % (tmp_path / ("out%d.log" % run)),
+                                            "mix_plan_out=%s" % (tmp_path / ("plan%d.txt" % run))], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 1 and "all finish!" in r.stdout, r.stdout + r.stderr
+    out1, out2 = (tmp_path / "out1.wts").read_bytes(), (tmp_path / "out2.wts").read_bytes()
+    assert out1 == out2, "same seed, same bytes"
+    rows = [ln.split() for ln in (tmp_path / "plan1.txt").read_text().splitlines()]
+    assert [(int(c), int(n), int(o), np.float32(s)) for c, n, o, s in rows] == [(int(c), int(n), int(o), s) for c, n, o, s in plan.tolist()]
+    log = (tmp_path / "out1.log").read_text()
+    cv_line = [ln for ln in log.splitlines() if ln.startswith("CV over. squared error: ")]
+    assert len(cv_line) == 1, log
+    # the same epoch through the Python API: the plan of mix_plan_out, the same calls and shuffles
+    mean, istd = m_cli.astype(np.float32), i_cli.astype(np.float32)
+    g = pkg.BP_GPU(1, 3, ls, B, 0.01, 0.5, 1e-4, W, b, **kw)
+    try:
+        g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, "lps+ibm", lc)
+        calls = _cut(g.mix_frames(plan), ctx, cap)
+        assert len(calls) > 1
+        for k, (a, e) in enumerate(calls):
+            g.train_mix(plan[a:e], pkg.mix_shuffle(seed, k, int(g.mix_frames(plan[a:e]).sum())))
+        Wp, bp = g.get_weights()
+        PU.write_wts(str(tmp_path / "py.wts"), ls, Wp, bp)
+        g.set_mix_corpus(cv_clean, noise, mean, istd, ctx, toff, "lps+ibm", lc)
+        cv = pkg.mix_plan(20261016, len(cv_clean), 1, [x.size for x in noise], snrs)
+        err, frames = np.float32(0.0), 0
+        for a, e in _cut(g.mix_frames(cv), ctx, cap):
+            err = np.float32(err + np.float32(g.CrossValid_mix(cv[a:e])))
+            frames += int(g.mix_frames(cv[a:e]).sum())
+    finally:
+        g.close()
+    assert (tmp_path / "py.wts").read_bytes() == out1
+    assert cv_line[0] == "CV over. squared error: %f" % (np.float32(err) / np.float32(frames))
+    parity_record(norm_relerr=e_norm, calls=len(calls))
