@@ -38,9 +38,11 @@ ABI_SYMBOLS = [
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
     "bp_enhance_waves", "bp_wave_lps",
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
+    "bp_score_waves", "bp_eval_mix",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
+SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
 MIX_TARGETS = {"lps": MIX_LPS, "irm": MIX_IRM, "ibm": MIX_IBM, "lps+irm": MIX_LPS_IRM, "lps+ibm": MIX_LPS_IBM}
 # bp_mixture: a numpy structured array of this dtype is a mixture plan
 MIXTURE_DTYPE = np.dtype({"names": ["clean", "noise", "offset", "snr_db"], "formats": [np.int32, np.int32, np.int64, np.float32],
@@ -130,6 +132,8 @@ def load_library(path=None):
     lib.bp_mix_features.argtypes = [hp, C.c_int, C.c_void_p, fp, fp, fp, fp, fp]
     lib.bp_mix_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, fp, C.c_void_p]
     lib.bp_mix_shuffle.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
+    lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
+    lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -441,6 +445,23 @@ class BP_GPU(object):
         out["pcm"] = out["pcm"][:n_pcm]
         return out
 
+    def eval_mix(self, plan, sample_rate, target=WAVE_LPS, out_col=0, return_pcm=False):
+        """bp_eval_mix: the plan's mixtures made on the device, enhanced with this net and scored against their clean sentences.
+        dict of noisy [n_mix][3] and enhanced [n_mix][3] float32 scores (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where
+        undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None."""
+        p, pp = self._plan(plan)
+        noisy = np.empty((max(p.size, 1), 3), np.float32)
+        enh = np.empty((max(p.size, 1), 3), np.float32)
+        pcm = None
+        if return_pcm and getattr(self, "mix_fea_dim", None) is not None:
+            lens = self.mix_clean_len[p["clean"]] if p.size else np.zeros(0, np.int64)
+            pcm = np.empty(max(int(lens.sum()), 1), np.float32)
+        self._check(self._lib.bp_eval_mix(self._h, p.size, pp, int(sample_rate), int(target), int(out_col), _fp(noisy), _fp(enh),
+                                          _fp(pcm) if pcm is not None else None))
+        if pcm is not None:
+            pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
+        return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
+
     def fill_chunk_synthetic(self, n_frames, seed=20260927):
         self._check(self._lib.bp_fill_chunk_synthetic(self._h, int(n_frames), int(seed)))
 
@@ -585,6 +606,28 @@ def wave_lps(device, fea_dim, sentences):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
+
+
+def score_waves(device, fea_dim, sample_rate, refs, ests):
+    """bp_score_waves: SSNR, LSD and STOI of every estimate against its reference (lists of 1-D arrays, int16 units, pairwise
+    equal lengths), float32 [n][3] (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where undefined).  No handle."""
+    lib = load_library()
+    if len(refs) != len(ests):
+        raise BPError("score_waves: %d references but %d estimates" % (len(refs), len(ests)))
+    r = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in refs]
+    e = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in ests]
+    for k, (a, b) in enumerate(zip(r, e)):
+        if a.size != b.size:
+            raise BPError("score_waves: pair %d: reference has %d samples, estimate %d" % (k, a.size, b.size))
+    lens = np.array([a.size for a in r], np.int32)
+    rp = np.ascontiguousarray(np.concatenate(r) if r else np.zeros(0, np.float32))
+    ep = np.ascontiguousarray(np.concatenate(e) if e else np.zeros(0, np.float32))
+    out = np.empty((max(len(r), 1), 3), np.float32)
+    rc = lib.bp_score_waves(int(device), int(fea_dim), int(sample_rate), len(r), lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(rp),
+                            _fp(ep), _fp(out))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out[:len(r)]
 
 
 def mix_plan(seed, n_clean, per_clean, noise_lens, snr_list):

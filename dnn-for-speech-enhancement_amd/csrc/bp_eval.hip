@@ -1,0 +1,492 @@
+// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 6: objective scores of enhanced speech.  Segmental SNR,
+// log-spectral distortion on the 1d analysis and STOI of estimates against a reference (bp_score_waves here; bp_eval_mix in
+// bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.
+//
+// Kernels (signal 0 is the reference, 1 .. nsig-1 the estimates; blockIdx.y picks the signal; a flat grid of workgroups finds its
+// sentence by a binary search over a prefix table, as bp_wave_analysis does over F):
+//   bp_eval_resample  per 10 kHz output sample: the polyphase sum of scipy's resample_poly (taps in double on the host), in double
+//   bp_eval_energy    reference only, one wave64 per STOI frame: E_j = sum (v r)^2 in double (a fixed shuffle tree)
+//   bp_eval_mask      reference only, one workgroup per sentence: max E, the 40 dB rule, the ranks of the kept frames (LDS scan)
+//   bp_eval_compact   per compacted sample: the (at most two) kept frames that overlap it, the earlier one added first
+//   bp_eval_bands     one workgroup per STFT frame: rfft_frame / rfft_bin of bp_fft.h at 512 points, 15 band envelopes
+//   bp_eval_corr      per (segment, band) pair of an estimate: the clipped, normalised correlation over 30 frames, in double
+//   bp_eval_ssnr      one wave64 per SSNR frame of an estimate: E_s, E_d in double, the clamped frame SNR
+//   bp_eval_lsd       one wave64 per analysis frame of an estimate: the RMS of the dB difference of the two LPS rows, in double
+//   bp_eval_reduce    one workgroup per (sentence, estimate): the three means in double (strided sums, a fixed LDS tree)
+//   bp_eval_trim      per padded sample: zero outside the sentence (the overlap-add output, before it is analysed)
+// No float atomics and no cross-workgroup hand-off inside a kernel: the same bits on every run.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "bp_eval.h"
+#include "bp_fft.h"
+#include "bp_handle.h"
+
+namespace {
+
+constexpr int EV_N = 256, EV_K = 128, EV_NFFT = 512, EV_NB = 15, EV_BS = 16, EV_SEG = 30;   // STOI frame, hop, FFT, bands, band stride, segment
+constexpr int EV_LOG2M = 8;                                                                 // rfft_frame: 512 points as 256 complex
+constexpr double EV_EPS = 2.220446049250313e-16;
+__constant__ int ev_band_lo[EV_NB] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174};
+__constant__ int ev_band_hi[EV_NB] = {9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
+constexpr int EV_BIN_LO = 7, EV_BIN_HI = 219;
+
+struct EvalArgs {
+    const int64_t *off; const int *len;
+    const int *o10, *rb, *P, *eb, *Q, *qb, *CP, *cb, *SJ, *sb, *F, *FS;
+    const float *h, *v; const float2 *tw; const double *w;
+    int n, p, q, Lh, taps, win, skip, D;
+    double clip;                                             // 1 + 10^(15/20)
+    const float *sig[EVAL_MAXSIG], *lps[EVAL_MAXSIG];
+    float *r10; size_t s10;                                  // [sig][o10[n]]
+    double *E; int *frm, *C;                                 // [P[n]], [P[n]], [n]
+    float *comp; size_t scomp;                               // [sig][Q[n]]
+    float *band; size_t sband;                               // [sig][P[n]][EV_BS]
+    double *rho, *ssnr, *lsd; size_t srho, sssnr, slsd;      // [est][CP[n]], [est][SJ[n]], [est][F[n]]
+    float *scores;                                           // [est][n][BP_SCORE_N]
+};
+
+__device__ __forceinline__ double wave_sum(double x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_resample(const EvalArgs a)
+{
+    const int sg = blockIdx.y, s = sentence_of(a.rb, a.n, blockIdx.x);
+    const int k = (blockIdx.x - a.rb[s]) * WAVE_THREADS + threadIdx.x;
+    if (k >= a.o10[s + 1] - a.o10[s]) return;
+    const float *x = a.sig[sg] + a.off[s];
+    const int64_t n = a.len[s], t0 = (int64_t)k * a.q + a.Lh;      // u index at tap 0: u[t] = x[t / p] when p | t, 0 <= t / p < n
+    int64_t j = t0 % a.p, i = (t0 - j) / a.p;                       // taps j, j + p, ... meet samples i, i - 1, ...
+    if (i >= n) { j += (i - n + 1) * a.p; i = n - 1; }
+    double acc = 0.0;
+    for (; j < a.taps && i >= 0; j += a.p, --i) acc += (double)a.h[j] * (double)x[i];
+    a.r10[sg * a.s10 + a.o10[s] + k] = (float)acc;
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_energy(const EvalArgs a)
+{
+    const int s = sentence_of(a.eb, a.n, blockIdx.x), ln = threadIdx.x & 63;
+    const int j = (blockIdx.x - a.eb[s]) * (WAVE_THREADS / 64) + (threadIdx.x >> 6);
+    if (j >= a.P[s + 1] - a.P[s]) return;                           // (a whole wave64: no barrier below)
+    const float *x = a.r10 + a.o10[s] + (size_t)j * EV_K;
+    double e = 0.0;
+    for (int i = ln; i < EV_N; i += 64) { const double u = (double)a.v[i] * (double)x[i]; e += u * u; }
+    e = wave_sum(e);
+    if (ln == 0) a.E[a.P[s] + j] = e;
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_mask(const EvalArgs a)
+{
+    __shared__ double mx[WAVE_THREADS];
+    __shared__ int cnt[WAVE_THREADS];
+    const int s = blockIdx.x, tid = threadIdx.x, base = a.P[s], J = a.P[s + 1] - base;
+    double m = 0.0;
+    for (int j = tid; j < J; j += WAVE_THREADS) m = fmax(m, a.E[base + j]);
+    mx[tid] = m;
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) mx[tid] = fmax(mx[tid], mx[tid + w]);
+        __syncthreads();
+    }
+    const double thr = 1e-4 * mx[0];
+    int total = 0;
+    for (int j0 = 0; j0 < J; j0 += WAVE_THREADS) {
+        const int j = j0 + tid, keep = j < J && a.E[base + j] > thr;
+        cnt[tid] = keep;
+        __syncthreads();
+        for (int o = 1; o < WAVE_THREADS; o <<= 1) {                // inclusive scan
+            const int add = tid >= o ? cnt[tid - o] : 0;
+            __syncthreads();
+            cnt[tid] += add;
+            __syncthreads();
+        }
+        if (keep) a.frm[base + total + cnt[tid] - 1] = j;
+        total += cnt[WAVE_THREADS - 1];
+        __syncthreads();
+    }
+    if (tid == 0) a.C[s] = total;
+}
+
+// compacted sample t of a sentence: kept frames c0 = t/K - 1 and c1 = t/K overlap it (c < C)
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_compact(const EvalArgs a)
+{
+    const int sg = blockIdx.y, s = sentence_of(a.qb, a.n, blockIdx.x);
+    const int t = (blockIdx.x - a.qb[s]) * WAVE_THREADS + threadIdx.x, C = a.C[s], c1 = t / EV_K, c0 = c1 - 1;
+    const float *x = a.r10 + sg * a.s10 + a.o10[s];
+    const int *frm = a.frm + a.P[s];
+    float y = 0.0f;
+    if (c0 >= 0 && c0 < C) y = a.v[t - c0 * EV_K] * x[(size_t)frm[c0] * EV_K + t - c0 * EV_K];
+    if (c1 < C) y += a.v[t - c1 * EV_K] * x[(size_t)frm[c1] * EV_K + t - c1 * EV_K];
+    a.comp[sg * a.scomp + a.Q[s] + t] = y;
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_bands(const EvalArgs a)
+{
+    extern __shared__ float2 z[];
+    const int sg = blockIdx.y, g = blockIdx.x, s = sentence_of(a.P, a.n, g), f = g - a.P[s], tid = threadIdx.x;
+    if (f >= a.C[s] - 1) return;                                    // S = C - 1 frames (the grid is sized by the bound)
+    float *pw = reinterpret_cast<float *>(z + lds_bytes(1 << EV_LOG2M) / sizeof(float2));   // |X_k|^2 of the band bins
+    rfft_frame(z, a.comp + sg * a.scomp + a.Q[s] + (size_t)f * EV_K, a.v, a.tw, EV_LOG2M);
+    for (int k = EV_BIN_LO + tid; k < EV_BIN_HI; k += blockDim.x) {
+        const float2 X = rfft_bin(z, a.tw, 1 << EV_LOG2M, k);
+        pw[k - EV_BIN_LO] = X.x * X.x + X.y * X.y;
+    }
+    __syncthreads();
+    if (tid < EV_NB) {
+        double acc = 0.0;
+        for (int k = ev_band_lo[tid]; k < ev_band_hi[tid]; ++k) acc += (double)pw[k - EV_BIN_LO];
+        a.band[sg * a.sband + (size_t)g * EV_BS + tid] = (float)sqrt(acc);
+    }
+}
+
+// pair i of a sentence: segment m = 29 + i / 15 (its last frame), band i % 15
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_corr(const EvalArgs a)
+{
+    const int e = blockIdx.y + 1, s = sentence_of(a.cb, a.n, blockIdx.x);
+    const int i = (blockIdx.x - a.cb[s]) * WAVE_THREADS + threadIdx.x, m = EV_SEG - 1 + i / EV_NB, b = i % EV_NB;
+    if (m >= a.C[s] - 1) return;
+    const float *X = a.band + (size_t)(a.P[s] + m - (EV_SEG - 1)) * EV_BS + b, *Y = X + e * a.sband;
+    double sx = 0.0, sy = 0.0;
+    for (int u = 0; u < EV_SEG; ++u) { const double x = X[u * EV_BS], y = Y[u * EV_BS]; sx += x * x; sy += y * y; }
+    const double al = sqrt(sx / (sy + EV_EPS));
+    double mx = 0.0, my = 0.0;
+    for (int u = 0; u < EV_SEG; ++u) { const double x = X[u * EV_BS]; mx += x; my += fmin(al * (double)Y[u * EV_BS], a.clip * x); }
+    mx /= EV_SEG; my /= EV_SEG;
+    double sxy = 0.0, sxx = 0.0, syy = 0.0;
+    for (int u = 0; u < EV_SEG; ++u) {
+        const double x = X[u * EV_BS], dx = x - mx, dy = fmin(al * (double)Y[u * EV_BS], a.clip * x) - my;
+        sxy += dx * dy; sxx += dx * dx; syy += dy * dy;
+    }
+    a.rho[(e - 1) * a.srho + a.CP[s] + i] = sxy / ((sqrt(sxx) + EV_EPS) * (sqrt(syy) + EV_EPS));
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_ssnr(const EvalArgs a)
+{
+    const int e = blockIdx.y + 1, s = sentence_of(a.sb, a.n, blockIdx.x), ln = threadIdx.x & 63;
+    const int j = (blockIdx.x - a.sb[s]) * (WAVE_THREADS / 64) + (threadIdx.x >> 6);
+    if (j >= a.SJ[s + 1] - a.SJ[s]) return;
+    const size_t at = (size_t)a.off[s] + (size_t)j * a.skip;
+    const float *r = a.sig[0] + at, *x = a.sig[e] + at;
+    double es = 0.0, ed = 0.0;
+    for (int i = ln; i < a.win; i += 64) {
+        const double rv = r[i], wr = a.w[i] * rv, wd = a.w[i] * (rv - (double)x[i]);
+        es += wr * wr; ed += wd * wd;
+    }
+    es = wave_sum(es); ed = wave_sum(ed);
+    if (ln == 0) a.ssnr[(e - 1) * a.sssnr + a.SJ[s] + j] = fmin(fmax(10.0 * log10(es / (ed + EV_EPS) + EV_EPS), -10.0), 35.0);
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lsd(const EvalArgs a)
+{
+    const int e = blockIdx.y + 1, ln = threadIdx.x & 63, g = blockIdx.x * (WAVE_THREADS / 64) + (threadIdx.x >> 6);
+    if (g >= a.F[a.n]) return;
+    const float *lr = a.lps[0] + (size_t)g * a.D, *le = a.lps[e] + (size_t)g * a.D;
+    const double db = 4.3429448190325182765;                        // 10 / ln 10
+    double acc = 0.0;
+    for (int k = ln; k < a.D; k += 64) { const double d = db * ((double)lr[k] - (double)le[k]); acc += d * d; }
+    acc = wave_sum(acc);
+    if (ln == 0) a.lsd[(e - 1) * a.slsd + g] = sqrt(acc / a.D);
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_reduce(const EvalArgs a)
+{
+    __shared__ double red[3][WAVE_THREADS];
+    const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x;
+    const int J = a.SJ[s + 1] - a.SJ[s], T = a.F[s + 1] - a.F[s], S = a.C[s] - 1, np = S >= EV_SEG ? EV_NB * (S - (EV_SEG - 1)) : 0;
+    const double *ss = a.ssnr + (e - 1) * a.sssnr + a.SJ[s], *ls = a.lsd + (e - 1) * a.slsd + a.F[s], *rh = a.rho + (e - 1) * a.srho + a.CP[s];
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    for (int i = tid; i < J; i += WAVE_THREADS) q0 += ss[i];
+    for (int i = tid; i < T; i += WAVE_THREADS) q1 += ls[i];
+    for (int i = tid; i < np; i += WAVE_THREADS) q2 += rh[i];
+    red[0][tid] = q0; red[1][tid] = q1; red[2][tid] = q2;
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; red[2][tid] += red[2][tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float nan = __int_as_float(0x7fc00000);
+        float *o = a.scores + ((size_t)(e - 1) * a.n + s) * BP_SCORE_N;
+        o[BP_SCORE_SSNR] = J >= 1 ? (float)(red[0][0] / J) : nan;
+        o[BP_SCORE_LSD] = T >= 1 ? (float)(red[1][0] / T) : nan;
+        o[BP_SCORE_STOI] = np > 0 ? (float)(red[2][0] / np) : nan;
+    }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_trim(const int64_t *__restrict__ off, const int *__restrict__ len,
+                                                          const int *__restrict__ FS, int n, int hop, float *__restrict__ pcm)
+{
+    const int q = blockIdx.x, s = sentence_of(FS, n, q);
+    for (int r = threadIdx.x; r < hop; r += blockDim.x) {
+        const int64_t at = (int64_t)q * hop + r, i = at - off[s];
+        if (i < 0 || i >= len[s]) pcm[at] = 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------ host side
+namespace {
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Where the tables lie in the table block (all offsets 256-byte aligned).
+struct TabLayout {
+    size_t off, len, pre[12], h, v, tw, w, bytes;   // pre: the prefix tables in EvalPlan order
+};
+TabLayout tab_layout(const EvalPlan &ep)
+{
+    TabLayout t;
+    const size_t n = (size_t)ep.n, pb = al256((n + 1) * 4);
+    t.off = 0; t.len = al256(n * 8);
+    size_t o = t.len + al256(n * 4);
+    for (int k = 0; k < 12; ++k) { t.pre[k] = o; o += pb; }
+    t.h = o; o += al256((size_t)ep.taps * 4);
+    t.v = o; o += al256((size_t)EV_NFFT * 4);
+    t.tw = o; o += al256((size_t)(EV_NFFT / 2 + 1) * 8);
+    t.w = o; o += al256((size_t)ep.win * 8);
+    t.bytes = o;
+    return t;
+}
+const std::vector<int> &pre_k(const EvalPlan &ep, int k)
+{
+    const std::vector<int> *v[12] = {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS};
+    return *v[k];
+}
+
+double bessel_i0(double x)
+{
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 200 && t > 1e-20 * s; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; }
+    return s;
+}
+
+// Work block layout for nsig signals.
+struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, bytes; size_t s10, scomp, sband, srho, sssnr, slsd; };
+WorkLayout work_layout(const EvalPlan &ep, int nsig)
+{
+    WorkLayout w;
+    const int n = ep.n, ne = nsig - 1;
+    w.s10 = ((size_t)ep.o10[n] + 3) & ~(size_t)3; w.scomp = (size_t)ep.Q[n];
+    w.sband = (size_t)ep.P[n] * EV_BS; w.srho = (size_t)ep.CP[n]; w.sssnr = (size_t)ep.SJ[n]; w.slsd = (size_t)ep.F[n];
+    size_t o = 0;
+    w.r10 = o; o += al256(nsig * w.s10 * 4);
+    w.E = o; o += al256((size_t)ep.P[n] * 8);
+    w.frm = o; o += al256((size_t)ep.P[n] * 4);
+    w.C = o; o += al256((size_t)n * 4);
+    w.comp = o; o += al256(nsig * w.scomp * 4);
+    w.band = o; o += al256(nsig * w.sband * 4);
+    w.rho = o; o += al256(ne * w.srho * 8);
+    w.ssnr = o; o += al256(ne * w.sssnr * 8);
+    w.lsd = o; o += al256(ne * w.slsd * 8);
+    w.bytes = o;
+    return w;
+}
+
+}  // namespace
+
+bool eval_rate(int fs, int *p, int *q)
+{
+    if (fs <= 0) return false;
+    int a = 10000, b = fs;
+    while (b) { const int t = a % b; a = b; b = t; }
+    *p = 10000 / a; *q = fs / a;
+    return *p <= 32 && *q <= 32;
+}
+
+int eval_plan(const char *who, int fs, int fea_dim, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep)
+{
+    if (!eval_rate(fs, &ep.p, &ep.q))
+        return fail(BP_ERR_ARG, std::string(who) + ": sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32 "
+                                                   "(8, 10, 12, 16, 20, 24, 32, 48 kHz)");
+    ep.n = n; ep.fs = fs; ep.D = fea_dim;
+    const int m = ep.p > ep.q ? ep.p : ep.q;
+    ep.Lh = ep.p == 1 && ep.q == 1 ? 0 : 10 * m;                 // 10 kHz in: a copy (one tap of 1)
+    ep.taps = 2 * ep.Lh + 1;
+    ep.win = (int)floor(0.03 * fs + 0.5);
+    ep.skip = ep.win / 4;
+    ep.off.assign(off, off + n); ep.len.assign(len, len + n);
+    for (std::vector<int> *v : {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS})
+        v->assign((size_t)n + 1, 0);
+    const int64_t LIM = INT32_MAX / 8;
+    for (int s = 0; s < n; ++s) {
+        const int64_t L = len[s], n10 = (L * ep.p + ep.q - 1) / ep.q;
+        const int64_t J10 = n10 > EV_N ? (n10 - EV_N - 1) / EV_K + 1 : 0;   // frames j with j K < n10 - N
+        const int64_t qc = (J10 * EV_K + 2 * EV_NFFT + 255) / 256 * 256;
+        const int64_t pairs = J10 > EV_SEG ? (int64_t)EV_NB * (J10 - EV_SEG) : 0;
+        const double jd = floor((double)L / ep.skip - (double)ep.win / ep.skip);
+        const int64_t J = jd >= 1.0 ? (int64_t)jd : 0;
+        const int64_t nx[12] = {ep.o10[s] + n10, ep.rb[s] + (n10 + WAVE_THREADS - 1) / WAVE_THREADS, ep.P[s] + J10, ep.eb[s] + (J10 + 3) / 4,
+                                ep.Q[s] + qc, ep.qb[s] + qc / WAVE_THREADS, ep.CP[s] + pairs, ep.cb[s] + (pairs + WAVE_THREADS - 1) / WAVE_THREADS,
+                                ep.SJ[s] + J, ep.sb[s] + (J + 3) / 4, F[s + 1], F[s + 1] + s + 1};
+        std::vector<int> *v[12] = {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS};
+        for (int k = 0; k < 12; ++k) {
+            if (nx[k] > LIM) return fail(BP_ERR_ARG, std::string(who) + ": too many samples in one call");
+            (*v[k])[s + 1] = (int)nx[k];
+        }
+    }
+    // resampler: h[j] = kaiser_{2Lh+1, 5}[j] sinc((j - Lh) / m), normalised to sum 1, times p (double, rounded once)
+    ep.h.assign((size_t)ep.taps, 1.0f);
+    if (ep.Lh > 0) {
+        std::vector<double> hd((size_t)ep.taps);
+        const double pi = 3.141592653589793238462643383279502884, i0b = bessel_i0(5.0);
+        double sum = 0.0;
+        for (int j = 0; j < ep.taps; ++j) {
+            const double r = 2.0 * j / (ep.taps - 1) - 1.0, kw = bessel_i0(5.0 * sqrt(fmax(0.0, 1.0 - r * r))) / i0b;
+            const double xs = (double)(j - ep.Lh) / m, sc = xs == 0.0 ? 1.0 : sin(pi * xs) / (pi * xs);
+            hd[j] = kw * sc; sum += hd[j];
+        }
+        for (int j = 0; j < ep.taps; ++j) ep.h[j] = (float)(hd[j] / sum * ep.p);
+    }
+    const double pi2 = 6.283185307179586476925286766559;
+    ep.v.assign(EV_NFFT, 0.0f);
+    for (int i = 0; i < EV_N; ++i) ep.v[i] = (float)(0.5 * (1.0 - cos(pi2 * (i + 1) / (EV_N + 1))));
+    ep.w.assign((size_t)ep.win, 0.0);
+    for (int i = 0; i < ep.win; ++i) ep.w[i] = 0.5 * (1.0 - cos(pi2 * (i + 1) / (ep.win + 1)));
+    ep.t_bytes = tab_layout(ep).bytes;
+    return BP_OK;
+}
+
+void eval_fill(const EvalPlan &ep, char *tab)
+{
+    const TabLayout t = tab_layout(ep);
+    memset(tab, 0, t.bytes);
+    memcpy(tab + t.off, ep.off.data(), (size_t)ep.n * 8);
+    memcpy(tab + t.len, ep.len.data(), (size_t)ep.n * 4);
+    for (int k = 0; k < 12; ++k) memcpy(tab + t.pre[k], pre_k(ep, k).data(), ((size_t)ep.n + 1) * 4);
+    memcpy(tab + t.h, ep.h.data(), ep.h.size() * 4);
+    memcpy(tab + t.v, ep.v.data(), ep.v.size() * 4);
+    const double pi2 = 6.283185307179586476925286766559;
+    float2 *tw = (float2 *)(tab + t.tw);
+    for (int k = 0; k <= EV_NFFT / 2; ++k) tw[k] = make_float2((float)cos(pi2 * k / EV_NFFT), (float)-sin(pi2 * k / EV_NFFT));
+    memcpy(tab + t.w, ep.w.data(), ep.w.size() * 8);
+}
+
+size_t eval_work_bytes(const EvalPlan &ep, int nsig) { return work_layout(ep, nsig).bytes; }
+
+hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream_t st)
+{
+    const TabLayout t = tab_layout(ep);
+    const WorkLayout w = work_layout(ep, nsig);
+    EvalArgs a; memset(&a, 0, sizeof(a));
+    const int *pre[12];
+    for (int k = 0; k < 12; ++k) pre[k] = (const int *)(d.tab + t.pre[k]);
+    a.off = (const int64_t *)(d.tab + t.off); a.len = (const int *)(d.tab + t.len);
+    a.o10 = pre[0]; a.rb = pre[1]; a.P = pre[2]; a.eb = pre[3]; a.Q = pre[4]; a.qb = pre[5]; a.CP = pre[6]; a.cb = pre[7];
+    a.SJ = pre[8]; a.sb = pre[9]; a.F = pre[10]; a.FS = pre[11];
+    a.h = (const float *)(d.tab + t.h); a.v = (const float *)(d.tab + t.v); a.tw = (const float2 *)(d.tab + t.tw); a.w = (const double *)(d.tab + t.w);
+    a.n = ep.n; a.p = ep.p; a.q = ep.q; a.Lh = ep.Lh; a.taps = ep.taps; a.win = ep.win; a.skip = ep.skip; a.D = ep.D;
+    a.clip = 1.0 + pow(10.0, 15.0 / 20.0);
+    for (int k = 0; k < nsig; ++k) { a.sig[k] = d.sig[k]; a.lps[k] = d.lps[k]; }
+    a.r10 = (float *)(d.work + w.r10); a.s10 = w.s10;
+    a.E = (double *)(d.work + w.E); a.frm = (int *)(d.work + w.frm); a.C = (int *)(d.work + w.C);
+    a.comp = (float *)(d.work + w.comp); a.scomp = w.scomp;
+    a.band = (float *)(d.work + w.band); a.sband = w.sband;
+    a.rho = (double *)(d.work + w.rho); a.srho = w.srho;
+    a.ssnr = (double *)(d.work + w.ssnr); a.sssnr = w.sssnr;
+    a.lsd = (double *)(d.work + w.lsd); a.slsd = w.slsd;
+    a.scores = d.scores;
+    const int n = ep.n, ne = nsig - 1;
+    const dim3 blk(WAVE_THREADS);
+    // (grids that can be empty -- no STOI or SSNR frame in the whole call -- are skipped)
+    hipLaunchKernelGGL(bp_eval_resample, dim3((unsigned)ep.rb[n], (unsigned)nsig), blk, 0, st, a);
+    if (ep.eb[n]) hipLaunchKernelGGL(bp_eval_energy, dim3((unsigned)ep.eb[n]), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_mask, dim3((unsigned)n), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_compact, dim3((unsigned)ep.qb[n], (unsigned)nsig), blk, 0, st, a);
+    if (ep.P[n])
+        hipLaunchKernelGGL(bp_eval_bands, dim3((unsigned)ep.P[n], (unsigned)nsig), blk,
+                           lds_bytes(1 << EV_LOG2M) + (size_t)(EV_BIN_HI - EV_BIN_LO) * 4, st, a);
+    if (ep.cb[n]) hipLaunchKernelGGL(bp_eval_corr, dim3((unsigned)ep.cb[n], (unsigned)ne), blk, 0, st, a);
+    if (ep.sb[n]) hipLaunchKernelGGL(bp_eval_ssnr, dim3((unsigned)ep.sb[n], (unsigned)ne), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_lsd, dim3((unsigned)((ep.F[n] + 3) / 4), (unsigned)ne), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_reduce, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t eval_trim_launch(const EvalPlan &ep, const char *tab, int hop, float *pcm, hipStream_t st)
+{
+    const TabLayout t = tab_layout(ep);
+    hipLaunchKernelGGL(bp_eval_trim, dim3((unsigned)ep.FS[ep.n]), dim3(WAVE_THREADS), 0, st, (const int64_t *)(tab + t.off),
+                       (const int *)(tab + t.len), (const int *)(tab + t.pre[11]), ep.n, hop, pcm);
+    return hipGetLastError();
+}
+
+extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
+                              float *scores)
+{
+    const char *who = "bp_score_waves";
+    const int log2M = wave_log2_fft(fea_dim);
+    if (log2M < 0) return fail(BP_ERR_ARG, "bp_score_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    { int p, q; if (!eval_rate(sample_rate, &p, &q)) return fail(BP_ERR_ARG, "bp_score_waves: sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32"); }
+    if (n_sent < 1 || !sent_len || !ref || !est || !scores) return fail(BP_ERR_ARG, "bp_score_waves: no sentences or null pointer");
+    const int M = 1 << log2M, hop = M, N = 2 * M, D = fea_dim;
+    std::vector<int> F((size_t)n_sent + 1, 0);
+    std::vector<int64_t> off(n_sent);
+    size_t f = 0;
+    for (int s = 0; s < n_sent; ++s) {
+        if (sent_len[s] < 1) return fail(BP_ERR_ARG, "bp_score_waves: empty sentence " + std::to_string(s));
+        off[s] = ((int64_t)f + s + 1) * hop;                     // the padded layout of bp_wave_lps
+        f += (size_t)((sent_len[s] - 1) / hop + 2);
+        if (f > (size_t)INT32_MAX / 8) return fail(BP_ERR_ARG, "bp_score_waves: too many frames in one call");
+        F[s + 1] = (int)f;
+    }
+    EvalPlan ep;
+    { const int r = eval_plan(who, sample_rate, D, n_sent, sent_len, off.data(), F.data(), ep); if (r != BP_OK) return r; }
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_score_waves: device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    // one host->device block: tables | analysis window | twiddles | padded reference | padded estimate
+    const size_t padded = (f + (size_t)n_sent) * hop;
+    const size_t o_win = al256(ep.t_bytes), o_tw = o_win + al256((size_t)N * 4), o_ref = o_tw + al256((size_t)(M + 1) * 8);
+    const size_t o_est = o_ref + al256(padded * 4), in_b = o_est + al256(padded * 4);
+    const size_t o_lps = in_b, lps_b = f * D * 4, o_sc = o_lps + 2 * al256(lps_b), o_work = o_sc + al256((size_t)n_sent * BP_SCORE_N * 4);
+    const size_t total = o_work + eval_work_bytes(ep, 2);
+    std::vector<char> hb(in_b, 0);
+    eval_fill(ep, hb.data());
+    wave_window_twiddles(log2M, (float *)(hb.data() + o_win), (float2 *)(hb.data() + o_tw));
+    {
+        float *xr = (float *)(hb.data() + o_ref), *xe = (float *)(hb.data() + o_est);
+        size_t src = 0;
+        for (int s = 0; s < n_sent; ++s) {
+            memcpy(xr + off[s], ref + src, (size_t)sent_len[s] * 4);
+            memcpy(xe + off[s], est + src, (size_t)sent_len[s] * 4);
+            src += (size_t)sent_len[s];
+        }
+    }
+    hipStream_t st = nullptr;
+    char *d = nullptr;
+    int rc = BP_OK;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, st);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        WaveAnaArgs a; memset(&a, 0, sizeof(a));
+        a.pcm = (const float *)(d + (k ? o_est : o_ref)); a.win = (const float *)(d + o_win); a.tw = (const float2 *)(d + o_tw);
+        a.F = (const int *)(d + tab_layout(ep).pre[10]);
+        a.n_sent = n_sent; a.log2M = log2M; a.D = D; a.hop = hop; a.ctx = 1;
+        a.lps = (float *)(d + o_lps + k * al256(lps_b));
+        e = wave_analysis_launch(a, (int)f, st);
+    }
+    if (e == hipSuccess) {
+        EvalDev v; memset(&v, 0, sizeof(v));
+        v.tab = d; v.work = d + o_work;
+        v.sig[0] = (const float *)(d + o_ref); v.sig[1] = (const float *)(d + o_est);
+        v.lps[0] = (const float *)(d + o_lps); v.lps[1] = (const float *)(d + o_lps + al256(lps_b));
+        v.scores = (float *)(d + o_sc);
+        e = eval_launch(ep, v, 2, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(scores, d + o_sc, (size_t)n_sent * BP_SCORE_N * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_score_waves: ") + hipGetErrorString(e));
+    if (d) (void)hipFree(d);
+    if (st) (void)hipStreamDestroy(st);
+    return rc;
+}

@@ -1,5 +1,5 @@
-// bp_fft.h -- what the two signal-layer translation units share (bp_wave.hip: enhancement and LPS features; bp_mix.hip: training
-// mixtures made on the device): the real FFT of one analysis frame in LDS, the analysis kernel's arguments and host-side launchers
+// bp_fft.h -- what the signal-layer translation units share (bp_wave.hip: enhancement and LPS features; bp_mix.hip: training
+// mixtures made on the device; bp_eval.hip: objective scores): the real FFT of one analysis frame in LDS, the analysis kernel's arguments and host-side launchers
 // of the bp_wave.hip kernels.  Internal: nothing in here is part of the C ABI.
 //
 // Signal definition: n_fft = 2 (fea_dim - 1) = 2M, hop = M, periodic Hamming window.  A real frame of 2M
@@ -92,9 +92,14 @@ struct WaveAnaArgs {
     int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
 };
 
-// Host side of bp_wave.hip, for bp_mix.hip
+// Host side of bp_wave.hip, for bp_mix.hip and bp_eval.hip
 int wave_log2_fft(int fea_dim);                                   // log2 of M, or -1 outside 1d's range
 void wave_window_twiddles(int log2M, float *win, float2 *tw);     // win[2M], tw[M + 1], computed in double and rounded once
 int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st);   // grow-only device / pinned host buffer
 hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st);
 hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, int ctx, int toff, float *nat, hipStream_t st);
+// synthesis of `frames` frames from the net outputs out[frames][ldo] (columns [out_col, out_col + D)) and Y -> syn[frames][n_fft]
+hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
+                                 int D, int target, float *syn, int frames, hipStream_t st);
+// overlap-add of those frames into the padded layout (segment 0 and segment T of every sentence are not written)
+hipError_t wave_overlap_launch(const float *syn, const float *win, const int *F, int n_sent, int hop, float *pcm, int frames, hipStream_t st);

@@ -1,4 +1,4 @@
-// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 5: training mixtures made on the device.  A clean-speech
+// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 6: training mixtures made on the device.  A clean-speech
 // corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
 // SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
 // reads.  gfx950 only.
@@ -15,6 +15,8 @@
 //   bp_mix_targets   one workgroup per frame: the FFTs of s and g v in LDS, one after the other, and the frame's target row
 //   bp_wave_nat      (bp_wave.hip) the noise-aware rows
 //   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
+// bp_eval_mix runs the same sequence without the targets, keeps the noisy spectrum Y, then bp_enhance_waves'
+// forward / synthesis / overlap-add on it and the scoring kernels of bp_eval.hip (bp_eval.h) on s, x and the enhanced samples.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -23,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "bp_eval.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
 
@@ -143,6 +146,7 @@ struct MixState {
     size_t o_clean, o_noise, o_cl_off, o_cl_len, o_no_off, o_no_len, o_mean, o_istd, o_win, o_tw;
     bp_handle::Raw in_d, x, s, v, gain, lps;                     // grow-only device buffers of the calls
     bp_handle::Raw in_pin[2]; hipEvent_t ev_in[2]; bool ev_valid[2]; int pin_cur;   // pinned input blocks, alternating
+    bp_handle::Raw ev_Y, ev_syn, ev_ola, ev_lps, ev_tab, ev_work, ev_pin;             // bp_eval_mix (ev_pin: pinned table block)
 };
 
 namespace {
@@ -159,7 +163,10 @@ void free_state(MixState *ms)
 {
     if (!ms) return;
     if (ms->corpus) (void)hipFree(ms->corpus);
-    for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps}) free_raw(*r, false);
+    for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps, &ms->ev_Y, &ms->ev_syn, &ms->ev_ola, &ms->ev_lps,
+                              &ms->ev_tab, &ms->ev_work})
+        free_raw(*r, false);
+    free_raw(ms->ev_pin, true);
     for (int k = 0; k < 2; ++k) {
         if (ms->ev_in[k]) { (void)hipEventSynchronize(ms->ev_in[k]); (void)hipEventDestroy(ms->ev_in[k]); }
         free_raw(ms->in_pin[k], true);
@@ -220,10 +227,10 @@ int check_order(const char *who, const Call &c, const int *order)
     return BP_OK;
 }
 
-// Mix, analyse and write the window chunk of a call into the staging set that is not current (targets included), on h->stream.
-// Then the caller adopts it.  lps_out: also keep the noisy LPS in ms->lps.
+// Mix, analyse and write the window chunk of a call into the staging set that is not current (targets included unless !targets),
+// on h->stream.  Then the caller adopts it.  lps_out: also keep the noisy LPS in ms->lps; Y: also keep the noisy spectrum there.
 int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order, bool lps_out, float **rows_out, float **targ_out,
-             float **nat_out)
+             float **nat_out, float2 *Y = nullptr, bool targets = true)
 {
     MixState *ms = h->mix;
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -236,8 +243,9 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
         (lps_out && (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK))
         return r;
     float *rows_d, *targ_d, *nat_d; int *tab;
-    if ((r = window_reserve(h, c.rows * D * 4, c.frames * ms->sL * 4, ms->nat ? (size_t)c.n * D * 4 : 0, c.frames, &rows_d, &targ_d,
-                            &nat_d, &tab)) != BP_OK)
+    targ_d = nullptr;
+    if ((r = window_reserve(h, c.rows * D * 4, targets ? c.frames * ms->sL * 4 : 0, ms->nat ? (size_t)c.n * D * 4 : 0, c.frames, &rows_d,
+                            targets ? &targ_d : nullptr, &nat_d, &tab)) != BP_OK)
         return r;
     // the pinned input block: the copy out of this one was enqueued two calls ago; wait for it (not for the training behind it)
     const int k = ms->pin_cur;
@@ -278,11 +286,11 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
         w.pcm = a.x; w.win = win; w.tw = tw; w.F = F;
         w.mean = (const float *)(cp + ms->o_mean); w.inv_std = (const float *)(cp + ms->o_istd);
         w.n_sent = c.n; w.log2M = ms->log2M; w.D = D; w.hop = ms->hop; w.ctx = ms->ctx; w.toff = ms->toff;
-        w.lps = lps_out ? (float *)ms->lps.p : nullptr; w.rows = rows_d;
+        w.lps = lps_out ? (float *)ms->lps.p : nullptr; w.rows = rows_d; w.Y = Y;
         w.win_start = tab; w.nat_row = ms->nat ? tab + 2 * (size_t)n : nullptr;
         HIPCHK(wave_analysis_launch(w, n, h->stream));
     }
-    {
+    if (targets) {
         MixTargArgs t; memset(&t, 0, sizeof(t));
         t.s = a.s; t.v = a.v; t.win = win; t.tw = tw; t.F = F;
         t.n_mix = c.n; t.log2M = ms->log2M; t.D = D; t.hop = ms->hop; t.target = ms->target; t.ldt = ms->sL; t.thr = ms->thr;
@@ -466,6 +474,76 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
             memcpy(pcm + dst, x.data() + ((size_t)c.Fs[i] + 1) * ms->hop, (size_t)len * 4);
             dst += (size_t)len;
         }
+    }
+    return BP_OK;
+}
+
+extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
+                           float *enh_scores, float *enh_pcm)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_eval_mix", n_mix, m, c)) != BP_OK) return r;
+    MixState *ms = h->mix;
+    const int D = ms->D, L = h->L, sL = h->s[L - 1], n = (int)c.frames, hop = ms->hop;
+    if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_eval_mix: target must be BP_WAVE_LPS or BP_WAVE_MASK");
+    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, "bp_eval_mix: out_col + fea_dim exceeds layersizes[last]");
+    if (!noisy_scores || !enh_scores) return fail(BP_ERR_ARG, "bp_eval_mix: null scores");
+    std::vector<int> len(n_mix);
+    std::vector<int64_t> off(n_mix);
+    for (int i = 0; i < n_mix; ++i) { len[i] = (int)ms->clean_len[m[i].clean]; off[i] = ((int64_t)c.Fs[i] + 1) * hop; }
+    EvalPlan ep;
+    if ((r = eval_plan("bp_eval_mix", sample_rate, D, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // every buffer first (a growth waits for the stream), then the sequence without a host wait
+    const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * BP_SCORE_N * 4;
+    if ((r = wave_grow(ms->ev_Y, c.frames * D * sizeof(float2), false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->ev_syn, c.frames * 2 * hop * 4, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_ola, pcm_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->ev_lps, 2 * lps_b, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_tab, ep.t_bytes + sc_b, false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->ev_work, eval_work_bytes(ep, 3), false, h->stream)) != BP_OK ||
+        (r = wave_grow(ms->ev_pin, ep.t_bytes, true, h->stream)) != BP_OK || (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK)
+        return r;
+    if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;
+    // the table block: the pinned buffer is free (the previous call ended in a synchronisation)
+    char *tab = (char *)ms->ev_tab.p;
+    eval_fill(ep, (char *)ms->ev_pin.p);
+    HIPCHK(hipMemcpyAsync(tab, ms->ev_pin.p, ep.t_bytes, hipMemcpyHostToDevice, h->stream));
+    float2 *Y = (float2 *)ms->ev_Y.p;
+    if ((r = generate(h, c, m, nullptr, true, nullptr, nullptr, nullptr, Y, false)) != BP_OK) return r;
+    if ((r = window_adopt(h, n, D, ms->ctx, ms->nat, false)) != BP_OK) return r;
+    if ((r = forward_resident(h, n)) != BP_OK) return r;
+    const char *cp = ms->corpus;
+    const float *win = (const float *)(cp + ms->o_win);
+    const float2 *tw = (const float2 *)(cp + ms->o_tw);
+    const int *F = (const int *)((const char *)ms->in_d.p + c.o_F);
+    float *ola = (float *)ms->ev_ola.p, *lps_s = (float *)ms->ev_lps.p, *lps_e = (float *)((char *)ms->ev_lps.p + lps_b);
+    HIPCHK(wave_synthesis_launch(h->out_chunk, h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
+    HIPCHK(wave_overlap_launch((const float *)ms->ev_syn.p, win, F, n_mix, hop, ola, n, h->stream));
+    HIPCHK(eval_trim_launch(ep, tab, hop, ola, h->stream));        // = the enhanced sentences in bp_score_waves' padded layout
+    for (int k = 0; k < 2; ++k) {                                  // the LPS of s and of the enhanced samples (x's: generate)
+        WaveAnaArgs w; memset(&w, 0, sizeof(w));
+        w.pcm = k ? ola : (const float *)ms->s.p; w.win = win; w.tw = tw; w.F = F;
+        w.n_sent = n_mix; w.log2M = ms->log2M; w.D = D; w.hop = hop; w.ctx = 1;
+        w.lps = k ? lps_e : lps_s;
+        HIPCHK(wave_analysis_launch(w, n, h->stream));
+    }
+    {
+        EvalDev d; memset(&d, 0, sizeof(d));
+        d.tab = tab; d.work = (char *)ms->ev_work.p;
+        d.sig[0] = (const float *)ms->s.p; d.sig[1] = (const float *)ms->x.p; d.sig[2] = ola;
+        d.lps[0] = lps_s; d.lps[1] = (const float *)ms->lps.p; d.lps[2] = lps_e;
+        d.scores = (float *)(tab + al256(ep.t_bytes));
+        HIPCHK(eval_launch(ep, d, 3, h->stream));
+    }
+    std::vector<float> sc((size_t)2 * n_mix * BP_SCORE_N), pcm(enh_pcm ? c.segs * hop : 0);
+    HIPCHK(hipMemcpyAsync(sc.data(), tab + al256(ep.t_bytes), sc_b, hipMemcpyDeviceToHost, h->stream));
+    if (enh_pcm) HIPCHK(hipMemcpyAsync(pcm.data(), ola, pcm_b, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    memcpy(noisy_scores, sc.data(), (size_t)n_mix * BP_SCORE_N * 4);
+    memcpy(enh_scores, sc.data() + (size_t)n_mix * BP_SCORE_N, (size_t)n_mix * BP_SCORE_N * 4);
+    if (enh_pcm) {
+        size_t dst = 0;
+        for (int i = 0; i < n_mix; ++i) { memcpy(enh_pcm + dst, pcm.data() + off[i], (size_t)len[i] * 4); dst += (size_t)len[i]; }
     }
     return BP_OK;
 }

@@ -1,4 +1,4 @@
-// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 5: the signal layer around the network.  Noisy PCM
+// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 6: the signal layer around the network.  Noisy PCM
 // in, enhanced PCM out (bp_enhance_waves), and the same analysis alone for feature extraction (bp_wave_lps).  gfx950 only.
 //
 // One signal definition, derived from fea_dim: n_fft = 2 (fea_dim - 1), a power of two in 64 .. 2048;
@@ -174,6 +174,23 @@ hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, i
 {
     hipLaunchKernelGGL(bp_wave_nat, dim3((unsigned)(((D + WAVE_THREADS - 1) / WAVE_THREADS) * n_sent)), dim3(WAVE_THREADS), 0, st,
                        rows, F, D, ctx, toff, nat);
+    return hipGetLastError();
+}
+
+hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
+                                 int D, int target, float *syn, int frames, hipStream_t st)
+{
+    WaveSynArgs a; memset(&a, 0, sizeof(a));
+    a.out = out; a.ldo = ldo; a.out_col = out_col;
+    a.Y = Y; a.win = win; a.tw = tw; a.log2M = log2M; a.D = D; a.target = target; a.frames = syn;
+    const int M = 1 << log2M;
+    hipLaunchKernelGGL(bp_wave_synthesis, dim3((unsigned)frames), dim3(WAVE_THREADS), lds_bytes(M) + (size_t)(M + 1) * sizeof(float2), st, a);
+    return hipGetLastError();
+}
+
+hipError_t wave_overlap_launch(const float *syn, const float *win, const int *F, int n_sent, int hop, float *pcm, int frames, hipStream_t st)
+{
+    hipLaunchKernelGGL(bp_wave_overlap, dim3((unsigned)frames), dim3(WAVE_THREADS), 0, st, syn, win, F, n_sent, hop, pcm);
     return hipGetLastError();
 }
 

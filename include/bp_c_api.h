@@ -260,6 +260,43 @@ int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const in
 int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order);
 
 /* ------------------------------------------------------------------------------------
+ * Objective scores of enhanced speech (no reference counterpart: the papers it asks its users to cite score with outside tools).
+ * INTEGRATION.md 1f.  Samples are fp32 in int16 units; a score compares an estimate e with a reference r of the same length n
+ * at sample rate fs; eps = 2.220446049250313e-16; an undefined score is NaN, never an error.  Accepted rates: fs > 0 and
+ * 10000/fs = p/q in lowest terms with max(p, q) <= 32 (8, 10, 12, 16, 20, 24, 32, 48 kHz), else BP_ERR_ARG.
+ *
+ * SSNR (dB; Hu & Loizou): win = floor(0.03 fs + 0.5), skip = floor(win/4), J = floor(n/skip - win/skip) frames (double; J < 1:
+ *   NaN), w[i] = 0.5 (1 - cos(2 pi (i+1)/(win+1))), frame j at j skip, E_s = sum (w r)^2, E_d = sum (w (r - e))^2 in double,
+ *   snr_j = clamp(10 log10(E_s/(E_d + eps) + eps), -10, 35), SSNR = mean_j snr_j.
+ * LSD (dB): on the analysis of bp_wave_lps (fea_dim gives n_fft, hop, window, padding and the T frames), L = the fp32 LPS,
+ *   LSD_t = sqrt((1/D) sum_k ((10/ln 10)(L_r - L_e))^2), LSD = mean_t LSD_t over all T frames (double).
+ * STOI (Taal et al. 2011, with pystoi's guards): r and e resampled to 10 kHz unless fs = 10000 (scipy.signal.resample_poly(x, p,
+ *   q): m = max(p, q), Lh = 10 m, h[j] = kaiser_{2Lh+1, 5}[j] sinc((j - Lh)/m) normalised to sum 1 times p, in double rounded
+ *   once; y[k] = sum_j h[j] u[k q + Lh - j], u[t] = x[t/p] when p | t and 0 <= t/p < n; k < ceil(n p/q)); frames of N = 256 at
+ *   K = 128 (every jK < n10 - N), symmetric Hann v[i] = 0.5 (1 - cos(2 pi (i+1)/(N+1))); frame j kept iff sum (v r)^2 >
+ *   1e-4 max_j sum (v r)^2 (double); the kept frames of r and e (r's mask) overlap-added at cK, c = their rank (C kept);
+ *   S = C - 1 STFT frames of v times the segment, zero-padded to 512; 15 one-third-octave band envelopes from 150 Hz (bins
+ *   [7,9) [9,11) [11,14) [14,17) [17,22) [22,27) [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138) [138,174) [174,219));
+ *   S < 30: NaN; for m = 29 .. S-1 and each band, over x = X_b(m-29 .. m) and y likewise: alpha = sqrt(sum x^2/(sum y^2 + eps)),
+ *   y' = min(alpha y, (1 + 10^0.75) x), rho = sum (x - mean x)(y' - mean y')/((|x - mean x| + eps)(|y' - mean y'| + eps));
+ *   STOI = mean rho over the 15 (S - 29) pairs.
+ *
+ * bp_score_waves (no handle): n_sent pairs back to back in ref and est (equal lengths sent_len[s] >= 1) -> scores[n_sent][BP_SCORE_N].
+ *   One host->device copy, one device->host copy, one synchronisation; every argument is checked before the device is touched.
+ * bp_eval_mix: each mixture of the corpus set by bp_set_mix_corpus made exactly as bp_mix_features makes it, enhanced exactly as
+ *   bp_enhance_waves would with target (BP_WAVE_LPS | BP_WAVE_MASK) and out_col, and both the mixed x and the enhanced samples
+ *   scored against the clean s: noisy_scores[n_mix][BP_SCORE_N], enh_scores[n_mix][BP_SCORE_N], enh_pcm NULL or [sum len_c].  The
+ *   audio stays on the device.  The argument checks and the capacity rule of bp_train_mix and bp_enhance_waves (BP_ERR_ARG, the
+ *   handle unchanged); BP_ERR_STATE without a corpus and on a data-parallel-attached handle; fp32 and bf16 handles.  The call
+ *   leaves the chunk as the resident window chunk; weights and momentum state are untouched.
+ * Both: no float atomics, reductions in a fixed order -- the same bits on every run. */
+enum { BP_SCORE_SSNR = 0, BP_SCORE_LSD = 1, BP_SCORE_STOI = 2, BP_SCORE_N = 3 };
+int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
+                   float *scores);
+int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
+                float *enh_scores, float *enh_pcm);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias

@@ -1,0 +1,61 @@
+"""Time of bp_eval_mix (mixtures made on the device, enhanced with the net, and the noisy and enhanced sentences scored: SSNR,
+LSD, STOI) against bp_enhance_waves on the same mixtures (enhancement alone), in the setting of tools/bench_mix.py: 100 clean
+sentences of 6 s at 8 kHz, 4 noise recordings of 60 s, the shipped enhancement net (1548-2048x3-129: 11 frames of 129 bins +
+the noise-aware block), bunch 256.  The two calls alternate, each timed to its synchronisation; median of --reps.  One JSON
+line.  Kernel times come from running it under `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py` (bp_eval_*
+against the forward's kernels).
+
+    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import dnnse_amd  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--compute", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--sentences", type=int, default=100)
+    a = ap.parse_args()
+    D, ctx, toff, rate, B = 129, 11, 5, 8000, 256
+    ls = [(ctx + 1) * D, 2048, 2048, 2048, D]
+    W, b = dnnse_amd.glorot_net(ls, seed=1, beta=0.5)
+    rng = np.random.default_rng(0)
+    n = 6 * rate
+    clean = [np.round(rng.normal(0, 3000, n)).astype(np.float32) for _ in range(a.sentences)]
+    noise = [np.round(rng.normal(0, 2000, 60 * rate)).astype(np.float32) for _ in range(4)]
+    frames = a.sentences * ((n - 1) // (D - 1) + 2)
+    mean, istd = np.full(D, 10.0, np.float32), np.full(D, 0.25, np.float32)
+    g = dnnse_amd.BP_GPU(1, len(ls), ls, B, 0.0, 0.0, 0.0, W, b, max_chunk_frames=frames + a.sentences * (ctx - 1),
+                         compute_dtype=1 if a.compute == "bf16" else 0)
+    g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, "lps")
+    plan = dnnse_amd.mix_plan(0, a.sentences, 1, [x.size for x in noise], [-5, 0, 5, 10, 15, 20])
+    mix = np.split(g.mix_features(plan)["pcm"], np.cumsum([x.size for x in clean])[:-1])
+    t_eval, t_enh = [], []
+    for r in range(a.reps + 1):                                    # (rep 0: warm-up -- buffers, code objects)
+        t0 = time.perf_counter()
+        ev = g.eval_mix(plan, rate)
+        t1 = time.perf_counter()
+        g.enhance_waves(mix, mean, istd, ctx, toff)                # the same mixtures, enhancement alone
+        t2 = time.perf_counter()
+        if r:
+            t_eval.append(t1 - t0)
+            t_enh.append(t2 - t1)
+    g.close()
+    m, s = float(np.median(t_eval)), float(np.median(t_enh))
+    print(json.dumps({"what": "bp_eval_mix vs bp_enhance_waves", "compute": a.compute, "mixtures": a.sentences, "frames": frames,
+                      "eval_ms_median": 1e3 * m, "enhance_ms_median": 1e3 * s, "eval_over_enhance": m / s,
+                      "noisy_mean": np.nanmean(ev["noisy"], axis=0).tolist(), "enhanced_mean": np.nanmean(ev["enhanced"], axis=0).tolist()}))
+
+
+if __name__ == "__main__":
+    main()
