@@ -494,8 +494,9 @@ class BP_GPU(object):
         self._check(self._lib.bp_grad_layout(self._h, int(layer), C.byref(o), C.byref(c)))
         return o.value, c.value
 
-    def read_grads(self):
-        """Per-layer weight / bias gradients of the last bp_grads_resident, unpadded: ([None, G_1 [prev][cur], ...], [None, gb_1, ...])."""
+    def read_grads(self, padded=False):
+        """Per-layer weight / bias gradients of the last bp_grads_resident, unpadded: ([None, G_1 [prev][cur], ...], [None, gb_1, ...]).
+        padded: the layers as they lie in the flat buffer (bp_grad_layout), widths rounded up to 64, pad rows and columns included."""
         g = np.empty(self.grad_floats(), np.float32)
         self._check(self._lib.bp_read_grads(self._h, _fp(g), g.size))
         pad = lambda v: (v + 63) & ~63
@@ -504,8 +505,9 @@ class BP_GPU(object):
             off, cnt = self.grad_layout(l)
             lp, lc = pad(self.layersizes[l - 1]), pad(self.layersizes[l])
             assert cnt == lp * lc + lc
-            gw.append(g[off:off + lp * lc].reshape(lp, lc)[:self.layersizes[l - 1], :self.layersizes[l]].copy())
-            gb.append(g[off + lp * lc:off + cnt][:self.layersizes[l]].copy())
+            rows, cols = (lp, lc) if padded else (self.layersizes[l - 1], self.layersizes[l])
+            gw.append(g[off:off + lp * lc].reshape(lp, lc)[:rows, :cols].copy())
+            gb.append(g[off + lp * lc:off + cnt][:cols].copy())
         return gw, gb
 
     def read_layer_output(self, layer):

@@ -373,11 +373,18 @@ struct GemmCfg {
         for (int i = 0; i < NVB; ++i) load_b(r, i, pb, o);
     }
 
-    // one float4 of the A / B register image -> LDS (k-major, transposing k-contiguous operands)
-    static __device__ __forceinline__ void store_a(const Regs &r, int i, float *As, int tid)
+    // one float4 of the A / B register image -> LDS (k-major, transposing k-contiguous operands).  krows: rows of this k-tile
+    // below K.  Only the weight gradients look at it: their k runs over the frames of the bunch, and the rows of y_0 behind
+    // the bunch are whatever follows it in the chunk buffer -- other frames, possibly NaN or Inf, which a zero row of dEdX does
+    // not cancel.  They are selected away here, where the value is on its way to LDS anyway (the load itself stays
+    // unconditional).  Every other configuration has K a multiple of BK.
+    static __device__ __forceinline__ void store_a(const Regs &r, int i, float *As, int tid, int krows)
     {
         const int f = tid + i * 256;
-        const float4 v = r.a[i];          // (a local copy keeps the register set out of scratch)
+        float4 v = r.a[i];                // (a local copy keeps the register set out of scratch)
+        if constexpr (BIASG && !A_KC) {
+            if (f / (BM / 4) >= krows) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         if constexpr (A_KC) {
             const int l8 = f % LPS, seg = f / LPS, row = seg % BM, k4 = (seg / BM) * LPS + l8;
             As[(k4 * 4 + 0) * LDA_S + row] = v.x; As[(k4 * 4 + 1) * LDA_S + row] = v.y;
@@ -403,10 +410,10 @@ struct GemmCfg {
             }
         }
     }
-    static __device__ __forceinline__ void store(const Regs &r, float *As, float *Bs, int tid, float4 &bsum)
+    static __device__ __forceinline__ void store(const Regs &r, float *As, float *Bs, int tid, float4 &bsum, int krows)
     {
 #pragma unroll
-        for (int i = 0; i < NVA; ++i) store_a(r, i, As, tid);
+        for (int i = 0; i < NVA; ++i) store_a(r, i, As, tid, krows);
 #pragma unroll
         for (int i = 0; i < NVB; ++i) store_b(r, i, Bs, tid, bsum);
     }
@@ -422,7 +429,7 @@ struct GemmCfg {
     static __device__ __forceinline__ void step(const float *As, const float *Bs, f32x16 (&acc)[NCH][TM][TN], int ks,
                                                 int a_off, int b_off, int kh, const Regs &rs, float *AsN, float *BsN,
                                                 Regs &rl, const float *pa, const float *pb, const Offs &o, int tid,
-                                                float4 &bsum)
+                                                float4 &bsum, int krows)
     {
         constexpr int NK = BK / KS / 2, NP = NVA + NVB, RD = NK < 4 ? NK : 4;
         const float *ap = As + (ks * (BK / KS) + kh) * LDA_S + a_off;
@@ -467,7 +474,7 @@ struct GemmCfg {
 #pragma unroll
                 for (int q = 0; q < NP; ++q) {               // store piece q: same slots
                     if (q == ps && (q * NK) / NP == s) {
-                        if (q < NVA) store_a(rs, q, AsN, tid); else store_b(rs, q - NVA, BsN, tid, bsum);
+                        if (q < NVA) store_a(rs, q, AsN, tid, krows); else store_b(rs, q - NVA, BsN, tid, bsum);
                         ++ps;
                     }
                 }
@@ -592,13 +599,13 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
 #define PB(t) Cfg::base_b(g, n0, K0_OF(t))
 #define AS(buf) (smem + (buf) * STAGE)
 #define BS(buf) (smem + (buf) * STAGE + A_STAGE)
-// multiply stage `buf`; ST: store image RS into the other stage; LD: load tile TL into image RL
-#define STEP(ST, LD, buf, RS, RL, TL)                                                                      \
+// multiply stage `buf`; ST: store image RS (k-tile TS) into the other stage; LD: load tile TL into image RL
+#define STEP(ST, LD, buf, RS, TS, RL, TL)                                                                  \
     Cfg::template step<ST, LD>(AS(buf), BS(buf), accs, ks, a_off, b_off, kh, RS, AS((buf) ^ 1), BS((buf) ^ 1),    \
-                               RL, PA(TL), PB(TL), offs, tid, bsum)
+                               RL, PA(TL), PB(TL), offs, tid, bsum, g.K - (TS) * BK)
     Regs r0, r1;
     Cfg::load(r0, PA(0), PB(0), offs);
-    Cfg::store(r0, AS(0), BS(0), tid, bsum);
+    Cfg::store(r0, AS(0), BS(0), tid, bsum, g.K);
     Cfg::load(r1, PA(1), PB(1), offs);
     __syncthreads();
     TRACE(1);
@@ -608,17 +615,17 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // hipcc copy the accumulators between register ranges every iteration); the last one or two tiles run after.
     int t = 0, buf = 0;
     for (; t + 3 <= nt; t += 2) {
-        STEP(true, true, 0, r1, r0, t + 2);
+        STEP(true, true, 0, r1, t + 1, r0, t + 2);
         __syncthreads();
-        STEP(true, true, 1, r0, r1, t + 3);
+        STEP(true, true, 1, r0, t + 2, r1, t + 3);
         __syncthreads();
     }
     if (nt - t == 2) {
-        STEP(true, false, 0, r1, r0, 0);
+        STEP(true, false, 0, r1, t + 1, r0, 0);
         __syncthreads();
         buf = 1;
     }
-    STEP(false, false, buf, r0, r0, 0);    // last tile: nothing left to stage or fetch
+    STEP(false, false, buf, r0, 0, r0, 0);    // last tile: nothing left to stage or fetch
     __syncthreads();
     TRACE(2);
 #undef K0_OF

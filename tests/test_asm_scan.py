@@ -15,23 +15,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dnn-for-speech-enhancement_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
-# mangled-name fragment -> most full drains (s_waitcnt vmcnt(0)) the kernel may contain
+# demangled kernel name up to its argument list (the names tests/dispatch_np.py and tests/test_dispatch_coverage.py use) -> most full
+# drains (s_waitcnt vmcnt(0)) the kernel may contain
 BOUNDS = {
     "bp_step": {
-        "_Z12bp_wgrad_dmaILi16ELi4ELi4ELi256ELb0EE": 6,          # fused wgrad + update (3: epilogue + the explicit drains)
-        "_Z12bp_wgrad_dmaILi16ELi4ELi4ELi256ELb1EE": 6,          # data-parallel store form
-        "_Z12bp_gemm_bf16ILi2ELi128ELb0ELb1ELi1EE": 6,           # bf16 dgrad, LDS-DMA form (was 34: 32 serial prologue loads)
-        "_Z12bp_gemm_bf16ILi2ELi128ELb0ELb0ELi1EE": 6,
-        "_Z12bp_gemm_bf16ILi2ELi64ELb0ELb0ELi1EE": 5,
-        "_Z12bp_gemm_bf16ILi2ELi32ELb0ELb0ELi1EE": 5,
-        "_Z12bp_gemm_bf16ILi0ELi128ELb1ELb1ELi1EE": 5,           # bf16 forward, LDS-DMA form
-        "_Z21bp_wgrad_dma_bf16_sixILi512ELi64ELi3EE": 7,
-        "_Z13bp_gemm_multiI10GemmKernelILi32ELi64ELi128ELi1ELi2ELb1ELb1ELi2EEE": 5,   # hidden dgrad
+        "void bp_wgrad_dma<16, 4, 4, 256, false>(": 6,           # fused wgrad + update (3: epilogue + the explicit drains)
+        "void bp_wgrad_dma<16, 4, 4, 256, true>(": 6,            # data-parallel store form
+        "void bp_gemm_bf16<2, 128, false, true, 1>(": 6,         # bf16 dgrad, LDS-DMA form (was 34: 32 serial prologue loads)
+        "void bp_gemm_bf16<2, 128, false, false, 1>(": 6,
+        "void bp_gemm_bf16<2, 64, false, false, 1>(": 5,
+        "void bp_gemm_bf16<2, 32, false, false, 1>(": 5,
+        "void bp_gemm_bf16<0, 128, true, true, 1>(": 5,          # bf16 forward, LDS-DMA form
+        "void bp_wgrad_dma_bf16_six<512, 64, 3>(": 7,
+        "void bp_gemm_multi<GemmKernel<32, 64, 128, 1, 2, true, true, 2> >(": 5,   # hidden dgrad
     },
     "bp_dp": {
-        "_Z19bp_dp_reduce_updateILi0ELb1EE": 8,                  # bf16 gradient segments (was 36 for 41 loads)
-        "_Z19bp_dp_reduce_updateILi0ELb0EE": 8,
-        "_Z19bp_dp_reduce_updateILi8ELb0EE": 8,
+        "void bp_dp_reduce_update<0, true>(": 8,                 # bf16 gradient segments (was 36 for 41 loads)
+        "void bp_dp_reduce_update<0, false>(": 8,
+        "void bp_dp_reduce_update<8, false>(": 8,
     },
 }
 
@@ -47,7 +48,8 @@ def _drains(unit, tmp):
             cur = m.group(1); counts[cur] = 0
         elif cur and "s_waitcnt vmcnt(0)" in line:
             counts[cur] += 1
-    return counts
+    names = subprocess.check_output(["c++filt"], input="\n".join(counts) + "\n", universal_newlines=True).split("\n")
+    return {n.strip(): v for n, v in zip(names, counts.values())}
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
@@ -56,7 +58,8 @@ def test_hot_kernels_have_no_load_by_load_drains(unit, tmp_path):
     counts = _drains(unit, str(tmp_path))
     for frag, bound in BOUNDS[unit].items():
         hits = {k: v for k, v in counts.items() if k.startswith(frag)}
-        assert hits, "kernel %s not found in %s (renamed? update the table)" % (frag, unit)
+        assert hits, "kernel %s not found in %s (renamed? update the table); kernels of that family: %s" % (
+            frag, unit, sorted(k for k in counts if k.startswith(frag.split("<")[0] + "<")))
         for k, v in hits.items():
             assert v <= bound, "%s: %d full vmcnt drains (bound %d): loads serialised by the compiler?" % (k, v, bound)
     shutil.rmtree(str(tmp_path), ignore_errors=True)

@@ -1,5 +1,5 @@
 """GPU tests of the logistic output layer (bp_set_output, -m gpu).  The C oracle only knows the linear output, so the reference
-here is float64 torch autograd of the loss written out below:
+here is float64 torch autograd of the loss (the helpers live in tests/output_ref.py, shared with tests/test_dispatch_gpu.py):
     linear columns [0, lin):     L = (1/Bg) sum (o - t)^2
     logistic columns, loss 0:    L = (2/Bg) sum BCE(y, t)        (dL/dz = (2/Bg)(y - t), BP_GPU.cu.bak:565-630)
     logistic columns, loss 1:    L = (1/Bg) sum (y - t)^2
@@ -13,6 +13,7 @@ import pytest
 
 import pfile_util as PU
 from flip_accounting import relu_flips
+from output_ref import _dedz, _trajectory, ref_forward, ref_grads
 from philox_np import drop_mask
 from util import TOL, relerr
 
@@ -37,57 +38,6 @@ def _targets(rng, n, sL, lin):
     t[:, :lin] = rng.standard_normal((n, lin), dtype=np.float32)
     t[:, lin:] = (rng.random((n, sL - lin)) < 0.4).astype(np.float32)
     return t
-
-
-def ref_forward(ls, W, b, x, masks=None, act=0, lin=0, keep=None):
-    """float64 torch forward; returns (parameter tensors, hidden outputs as numpy, z and y of the output layer as tensors).
-    keep: CV keep-scales per weight layer (non-inverted dropout: the pre-activation is scaled)."""
-    import torch
-    L = len(ls)
-    Wt = [None] + [torch.tensor(np.asarray(W[l], np.float64), requires_grad=True) for l in range(1, L)]
-    bt = [None] + [torch.tensor(np.asarray(b[l], np.float64), requires_grad=True) for l in range(1, L)]
-    h = torch.from_numpy(np.asarray(x, np.float64))
-    if masks is not None:
-        h = h * torch.from_numpy(1.0 - masks[0].astype(np.float64))
-    ys = [h.detach().numpy()]
-    for l in range(1, L):
-        z = (keep[l] if keep else 1.0) * (h @ Wt[l]) + bt[l]
-        if l < L - 1:
-            h = torch.clamp(z, min=0.0) if act == 0 else torch.sigmoid(z)
-            if masks is not None:
-                h = h * torch.from_numpy(1.0 - masks[l].astype(np.float64))
-            ys.append(h.detach().numpy())
-    y = torch.cat([z[:, :lin], torch.sigmoid(z[:, lin:])], 1)
-    return Wt, bt, ys, z, y
-
-
-def ref_loss(z, y, t, lin, loss, Bg, keep_rows=None):
-    import torch
-    import torch.nn.functional as F
-    t = torch.from_numpy(np.asarray(t, np.float64))
-    r = torch.ones(z.shape[0], 1, dtype=torch.float64) if keep_rows is None else torch.from_numpy(np.asarray(keep_rows, np.float64))[:, None]
-    L = (((y[:, :lin] - t[:, :lin]) ** 2) * r).sum() / Bg
-    if loss == 0:                                    # BCE through the logits: softplus(z) - t z = -(t log y + (1-t) log(1-y))
-        L = L + 2.0 * ((F.softplus(z[:, lin:]) - t[:, lin:] * z[:, lin:]) * r).sum() / Bg
-    else:
-        L = L + (((y[:, lin:] - t[:, lin:]) ** 2) * r).sum() / Bg
-    return L
-
-
-def ref_grads(ls, W, b, x, t, masks=None, act=0, lin=0, loss=0, Bg=None, keep_rows=None):
-    Wt, bt, ys, z, y = ref_forward(ls, W, b, x, masks, act, lin)
-    ref_loss(z, y, t, lin, loss, Bg or x.shape[0], keep_rows).backward()
-    L = len(ls)
-    return [None] + [Wt[l].grad.numpy() for l in range(1, L)], [None] + [bt[l].grad.numpy() for l in range(1, L)], ys
-
-
-def _dedz(z, t, lin, loss, Bg):
-    y = z.copy()
-    y[:, lin:] = 1.0 / (1.0 + np.exp(-z[:, lin:]))
-    d = (2.0 / Bg) * (y - t)
-    if loss == 1:
-        d[:, lin:] *= y[:, lin:] * (1.0 - y[:, lin:])
-    return d
 
 
 def _mk(pkg, ls, B, W, b, lr=1.0, m=0.5, **kw):
@@ -161,24 +111,6 @@ def test_shipped_geometry_multi_objective_gradient_on_the_split_path(pkg, parity
 
 
 # ------------------------------------------------------------------ 2. ten-step trajectory
-def _trajectory(ls, W, b, x, t, B, NS, lr, m, act, lin, loss, drop_seed=None):
-    L = len(ls)
-    W64 = [None] + [np.asarray(W[l], np.float64).copy() for l in range(1, L)]
-    b64 = [None] + [np.asarray(b[l], np.float64).copy() for l in range(1, L)]
-    dW = [None] + [np.zeros_like(W64[l]) for l in range(1, L)]
-    db = [None] + [np.zeros_like(b64[l]) for l in range(1, L)]
-    c1 = (1.0 - m) * lr
-    for i in range(NS):
-        masks = None
-        if drop_seed is not None:
-            masks = [drop_mask(drop_seed, i, l, B, ls[l], 0.1 if l == 0 else 0.2) for l in range(L - 1)]
-        gw, gb, _ = ref_grads(ls, W64, b64, x[i * B:(i + 1) * B], t[i * B:(i + 1) * B], masks, act, lin, loss)
-        for l in range(1, L):
-            dW[l] = m * dW[l] - c1 * (gw[l] / B); W64[l] = W64[l] + dW[l]
-            db[l] = m * db[l] - c1 * (gb[l] / B); b64[l] = b64[l] + db[l]
-    return W64, b64, dW, db
-
-
 @pytest.mark.parametrize("lin,loss", [(16, 0), (0, 1)], ids=["lin16-xent", "all-logistic-mse"])
 def test_small_net_ten_step_trajectory(pkg, parity_record, lin, loss):
     pytest.importorskip("torch")
