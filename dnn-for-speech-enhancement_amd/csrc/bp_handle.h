@@ -41,7 +41,7 @@ static inline int pad64(int x) { return (x + 63) & ~63; }
 
 // Development switches (A/B aids of the measurements quoted in DESIGN.md): environment variables that only a library
 // built with -DBP_DEV (`make dev` -> libbp_hip_dev.so, loaded through BP_HIP_LIB) reads.  The shipped library has ONE
-// code path per shape and reads no environment except BP_DP_TIMEOUT_S.
+// code path per shape and reads no environment except BP_DP_TIMEOUT_S and BP_WGRAD_SLOTS (bp_create).
 #ifdef BP_DEV
 static inline bool dev_flag(const char *name) { return getenv(name) != nullptr; }
 static inline int dev_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
@@ -57,6 +57,7 @@ struct bp_handle {
     int B, Bg;                   // local / global bunch
     int cap, chunk_frames;
     hipStream_t own_stream, stream;
+    int wgrad_slots;             // workgroups of the persistent weight-gradient launch (4 per CU; BP_WGRAD_SLOTS at creation)
     // parameters and momentum state live in two flat arenas with the layout of the flat gradient buffer
     // ([W_1|b_1|W_2|b_2|...], padded; g_off/g_cnt) so that data-parallel ranks can export them as ONE hipIpc
     // allocation each and the sharded update is a flat elementwise pass (bp_dp.h); W/b/dW/db point into them

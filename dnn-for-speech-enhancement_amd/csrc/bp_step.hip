@@ -143,6 +143,16 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
 
 #define CK(x) do { int _r = (x); if (_r != BP_OK) { std::string m = g_bp_err; bp_destroy(h); g_bp_err = m; return _r; } } while (0)
 #define HK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::string m = std::string(#x) + ": " + hipGetErrorString(_e); bp_destroy(h); return fail(BP_ERR_DEVICE, m); } } while (0)
+    {
+        // the persistent weight-gradient launch (bp_wgrad_dma.h): 4 workgroups per CU (its launch bound), a multiple of 8 so that
+        // a workgroup's XCD stays the low bits of every entry it walks.  BP_WGRAD_SLOTS, read here once: tests and probes (a
+        // small net has fewer tiles than slots and would never walk a second one).
+        int cus = 0;
+        HK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
+        const char *ev = getenv("BP_WGRAD_SLOTS");
+        const int slots = ev ? atoi(ev) : 4 * cus;
+        h->wgrad_slots = slots < 8 ? 8 : slots & ~7;
+    }
     HK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
     HK(hipEventCreate(&h->ev0));
@@ -419,9 +429,10 @@ static hipError_t run_multi(hipStream_t st, Prepared *ps, int n)
     return hipGetLastError();
 }
 
-// The same for a plain __global__ kernel taking MultiArgs with 64x64 tiles (bp_wgrad_dma.h).
+// The same for a plain __global__ kernel taking MultiArgs with 64x64 tiles (bp_wgrad_dma.h): at most `slots` (a multiple of 8)
+// workgroups, workgroup w walks the entries w, w + grid, ... of the tile list.
 template <void (*KERNEL)(const MultiArgs)>
-static hipError_t run_multi_k(hipStream_t st, Prepared *ps, int n)
+static hipError_t run_multi_k(hipStream_t st, Prepared *ps, int n, int slots)
 {
     MultiArgs a; memset(&a, 0, sizeof(a));
     int t = 0;
@@ -431,12 +442,12 @@ static hipError_t run_multi_k(hipStream_t st, Prepared *ps, int n)
         t += (ps[i].g.tiles_m * ps[i].g.tiles_n + 7) & ~7;      // (problem-relative block index keeps the XCD bits, see run_multi)
     }
     a.first_tile[n] = t; a.n = n;
-    hipLaunchKernelGGL(KERNEL, dim3(t), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(KERNEL, dim3(t < slots ? t : slots), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 // The wgrad problems ps[0..n) (all fused or all store): grouped launches of up to 4 problems.
-static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n)
+static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n, int slots)
 {
     for (int i = 0; i < n;) {
         const int m = n - i < 4 ? n - i : 4;
@@ -444,12 +455,12 @@ static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n)
         int kk = ps[i].g.K;
         for (int j = 0; j < m; ++j) if (ps[i + j].g.K != kk) kk = 0;
         hipError_t er;
-        if (kk == 256 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256>>(st, ps + i, m);
-        else if (kk == 128 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128>>(st, ps + i, m);
-        else if (kk == 512 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512>>(st, ps + i, m);
-        else if (kk == 256) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256, true>>(st, ps + i, m);       // data-parallel gradient store
-        else if (kk == 128) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128, true>>(st, ps + i, m);
-        else if (kk == 512) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512, true>>(st, ps + i, m);
+        if (kk == 256 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256>>(st, ps + i, m, slots);
+        else if (kk == 128 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128>>(st, ps + i, m, slots);
+        else if (kk == 512 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512>>(st, ps + i, m, slots);
+        else if (kk == 256) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256, true>>(st, ps + i, m, slots);       // data-parallel gradient store
+        else if (kk == 128) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128, true>>(st, ps + i, m, slots);
+        else if (kk == 512) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512, true>>(st, ps + i, m, slots);
         else if (ps[i].fused) er = run_multi<KWgrad<EPI_WGRAD_UPDATE>, 64, 64>(st, ps + i, m);
         else er = run_multi<KWgradStore, 128, 64>(st, ps + i, m);
         if (er != hipSuccess) return er;
@@ -467,7 +478,7 @@ hipError_t launch_dgrad(bp_handle *h, int l, int M)
 hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused)
 {
     Prepared p = prep_wgrad(h, l, M, y_prev, fused);
-    return run_wgrads(h->stream, &p, 1);
+    return run_wgrads(h->stream, &p, 1, h->wgrad_slots);
 }
 
 // Bunches whose input rows go through the staged tile (x0s2): every bunch of a window chunk (stacked on the device, SURVEY 8f
@@ -707,7 +718,7 @@ hipError_t step_wgrads(bp_handle *h, const int *ls, int n, const float *x0, bool
         ws[i] = prep_wgrad(h, ls[i], h->B, ls[i] == 1 ? x0 : h->y[ls[i] - 1], fused);
         if (done) ws[i].e.done = done[ls[i]];
     }
-    return run_wgrads(h->stream, ws, n);
+    return run_wgrads(h->stream, ws, n, h->wgrad_slots);
 }
 
 // One bunch starting at chunk frame `first`: forward + backward.  fused: momentum update inside

@@ -7,19 +7,41 @@
 // Both operands of this GEMM are k-major in memory ([frame][unit]: the reduction runs over the frames of the bunch),
 // which is exactly the LDS image the MFMA fragment fetch wants ([k][m] / [k][n], conflict-free ds_read_b32).  So the
 // tiles go global -> LDS by `global_load_lds_dwordx4` (1 KiB per wave instruction = 4 k-rows of a 64-wide tile): no
-// register staging, no ds_write, 116 VGPRs => 4 workgroups per CU instead of 3.  64x64 tiles, 16-row k-tiles in a
-// 4-stage LDS ring (32 KB), three k-tiles in flight ahead of the one being multiplied, ONE raw s_barrier per k-tile with
-// an exact, counted s_waitcnt vmcnt (a __syncthreads() would fence with vmcnt(0) and drain the DMA queue); the k-loop is
-// fully unrolled for the bunch size, so every count is an immediate.  The W / delta tile of the fused update is
-// fetched by plain loads issued right behind the LAST operand tile: no operand wait ever includes it (vmcnt retires in
-// order) and it has three k-tiles of MFMA work to land.  Measured on C2 (grouped launch of all four layers, in-step):
-// 80.4 us vs 84.7 us for the register-staged GemmKernel<64,64,32,...> it replaces; results are bit-identical to it
-// for W and delta (same k-order, same two accumulator chains).  Other shapes of this design that were measured and
-// not adopted (128x64 tiles, dynamic k-loop, 3/6-stage rings) live in tools/wgrad_glds_probe.h.
+// register staging, no ds_write, 90 VGPRs => 4 workgroups per CU instead of 3.  64x64 tiles, 16-row k-tiles in a
+// 4-stage LDS ring (32 KB), ONE raw s_barrier per k-tile with an exact, counted s_waitcnt vmcnt (a __syncthreads()
+// would fence with vmcnt(0) and drain the DMA queue); the k-loop is fully unrolled for the bunch size, so every count is
+// an immediate.  Results are bit-identical to the register-staged GemmKernel<64,64,32,...> it replaced (same k-order,
+// same two accumulator chains).  Other shapes of this design that were measured and not adopted (128x64 tiles, dynamic
+// k-loop, 3/6-stage rings) live in tools/wgrad_glds_probe.h.
+//
+// PERSISTENT GRID, RING CARRIED ACROSS TILES.  The launch has G = min(entries, 4 x CUs) workgroups (bp_handle::wgrad_slots);
+// workgroup w walks the entries w, w + G, ... of the concatenated tile list of the grouped problems (every problem padded
+// to a multiple of 8 entries and G a multiple of 8: w & 7, the XCD, stays the low bits of the problem-relative index the
+// tile map wants; padding entries are skipped; consecutive tiles of a walk may belong to different problems).  Invariant
+// at every barrier of the walk: the D = ST - 1 = 3 k-tiles that follow the one about to be multiplied are in flight, k-tile j
+// of EVERY tile in ring stage j % ST (NT % ST == 0).  From iteration NT - D on, the k-tiles issued are those of the
+// workgroup's NEXT tile, so only a workgroup's first tile waits a memory latency before its first MFMA; the tile boundary
+// costs no wait and no barrier.  Behind the last tile of a walk the same loads are issued once more from that tile's
+// panels and never read (unconditional loads: bp_kernels.h says what a conditional one costs), and drained before exit.
+//
+// THE vmcnt COUNTS (vmcnt retires in order; LDS-DMA loads, plain loads and stores all count).  A wave's queue, per tile:
+//     k0 k1 k2 | S x the previous tile's epilogue stores | k3 ... k(NT-1) | 32 W/delta loads | n0 n1 n2 (next tile) | S stores
+// Each k-tile is NDMA = 2 instructions per wave.  The wait in front of k-tile T leaves outstanding what was issued behind it:
+// the two following k-tiles (4), plus the 32 W/delta loads for T > NT - D, plus -- for T < D of every tile but the
+// workgroup's first -- the S = 32 (fused) / 16 (store form) stores of the previous epilogue, which must not be waited
+// for: a store's acknowledgement is a memory latency of its own.  S is a LOWER bound of what lies there (bias lanes and
+// the tile count add to it): more behind a k-tile than counted only makes its wait stricter.  It holds because no tile of
+// a padded layer is partial; after an epilogue that stored nothing the wave drains instead.  The W / delta tile is fetched
+// right behind the tile's LAST operand k-tile and has three k-tiles of MFMA work to land; the epilogue waits for it with
+// vmcnt(D * NDMA), which leaves the next tile's head in flight.  Those loads are written out (wd_fetch): with LDS-DMA in
+// flight the compiler turns every wait it places for a load of its own into vmcnt(0).
+// The bias reduction's scratch is ring stage ST - 1: it held the tile's last k-tile and is next written behind the barrier
+// of the next tile's iter<0>.  Measured on C2 (grouped launch of all four layers, rocprofv3 average in the step): 74.5 us
+// against 77.5 us for one tile per workgroup (profiles/r08_wgrad_cross_tile_prefetch.txt).
 #pragma once
 #include "bp_kernels.h"
 
-// template <BK, ST, MINWG, K>: K = frames of the bunch (static).  Prefetch distance D = ST-1 tiles.
+// template <BK, ST, MINWG, K>: K = frames of the bunch (static).  Prefetch distance D = ST-1 k-tiles.
 template <int N> struct VmWait { static __device__ __forceinline__ void go() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N < 63 ? N : 63) : "memory"); } };
 
 template <int BKX, int STX, int MINWG, int KTOT, bool STORE = false>
@@ -37,18 +59,88 @@ struct WgradDma {
     typedef __attribute__((address_space(3))) void *lds_ptr;
     typedef const __attribute__((address_space(1))) void *glb_ptr;
 
-    static __device__ __forceinline__ void issue_tile(const GemmArgs &g, int m0, int n0, int k0, float *smem, int st, int wave, int lane)
+    // Stores of one wave's epilogue (no tile of a padded layer is partial, run() drains after one that were): what lies between
+    // the carried k-tiles 0..D-1 of a tile and its k-tile D in the wave's queue.  A LOWER bound is what the waits need: more
+    // operations behind a k-tile than counted only make its wait stricter (bias lanes, the tile count of the store form).
+    static constexpr int NST = STORE ? 16 : 32;
+    static_assert(NT % ST == 0, "k-tile j of EVERY tile lies in ring stage j % ST: the ring runs on across tiles");
+    static_assert(NT >= 2 * D, "the carried head and the W/delta tail of a tile do not overlap");
+    static_assert((D - 1) * NDMA + (NWD > NST ? NWD : NST) < 64, "vmcnt is 6 bits");
+
+    struct Pos { int p, m0, n0; };                                // problem of the launch, origin of the tile
+    struct Src { const float *a, *b; int lda, ldb; };             // operand panels of one tile (k-row 0)
+
+    // entry i of the concatenated tile list (every problem padded to a multiple of 8 entries): false for a padding entry.
+    // t.p only grows along a workgroup's walk.
+    static __device__ __forceinline__ bool decode(const MultiArgs &a, int i, Pos &t)
     {
+        int p = t.p;
+        while (p + 1 < a.n && i >= a.first_tile[p + 1]) ++p;
+        const GemmArgs &g = a.g[p];
+        const int b = i - a.first_tile[p];                        // (low 3 bits = the workgroup's XCD: G and first_tile are multiples of 8)
+        if (b >= g.tiles_m * g.tiles_n) return false;
+        int tile_m, tile_n;
+        if ((g.tiles_n & 7) == 0) { const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3; tile_n = xcd * per + j % per; tile_m = j / per; }
+        else { tile_m = b % g.tiles_m; tile_n = b / g.tiles_m; }
+        t.p = p; t.m0 = tile_m * BM; t.n0 = tile_n * BN;
+        return true;
+    }
+    static __device__ __forceinline__ int seek(const MultiArgs &a, int i, int stride, int total, Pos &t)
+    {
+        while (i < total && !decode(a, i, t)) i += stride;
+        return i;
+    }
+    static __device__ __forceinline__ Src src_of(const MultiArgs &a, const Pos &t)
+    {
+        const GemmArgs &g = a.g[t.p];
+        return Src{g.A + t.m0, g.B + t.n0, g.lda, g.ldb};
+    }
+
+    // The W / delta tile of one wave's 32x32 block (the lane -> element map of epilogue_fetch, bp_kernels.h).  The loads are
+    // written out: with LDS-DMA in flight hipcc turns every wait IT places for a load into vmcnt(0), which here would drain the
+    // next tile's head in every epilogue (and, through the registers of a skipped epilogue, in every iter<0>).  So the compiler
+    // never sees these registers pending; wd_landed() is the one wait, and hands the values on only behind it.
+    struct WD { float w[16], d[16]; };
+    static __device__ __forceinline__ void wd_fetch(const EpiArgs &e, int mb, int nb, int lane, WD &x)
+    {
+        const int mbc = mb < e.m_limit ? mb : 0;                  // (a block outside the matrix reads row 0 and is never stored)
+        const float *cw = uniform_ptr(e.C + (size_t)mbc * e.ldc + nb);
+        const float *cd = uniform_ptr(e.aux2 + (size_t)mbc * e.ldc + nb);
+        const unsigned ldc = __builtin_amdgcn_readfirstlane(e.ldc);
+        const unsigned lob = 4u * ((unsigned)(4 * (lane >> 5)) * (unsigned)e.ldc + (unsigned)(lane & 31));   // bytes
 #pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int q = wave * NA + i, r = q * 4 + (lane >> 4), c = (lane & 15) * 4;
-            __builtin_amdgcn_global_load_lds((glb_ptr)(g.A + (size_t)(k0 + r) * g.lda + m0 + c), (lds_ptr)(smem + st * STAGE + q * 256), 16, 0, 0);
+        for (int r = 0; r < 16; ++r) {
+            const unsigned ro = (unsigned)((r & 3) + 8 * (r >> 2)) * ldc;
+            // (r == 0: the hazard recogniser does not look into these, and a base that came straight from a v_readfirstlane must be 5
+            // wait states old when a load reads it)
+            if (r == 0) asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2" : "=v"(x.w[r]) : "v"(lob), "s"(cw + ro) : "memory");
+            else asm volatile("global_load_dword %0, %1, %2" : "=v"(x.w[r]) : "v"(lob), "s"(cw + ro) : "memory");
+            asm volatile("global_load_dword %0, %1, %2" : "=v"(x.d[r]) : "v"(lob), "s"(cd + ro) : "memory");
+        }
+    }
+    // behind the W/delta loads at the epilogue: the D k-tiles of the next tile's head, which stay in flight
+    static __device__ __forceinline__ void wd_landed(WD &x, EpiPre &pre)
+    {
+        VmWait<D * NDMA>::go();
+#pragma unroll
+        for (int r = 0; r < 16; r += 8) {
+            asm volatile("" : "+v"(x.w[r]), "+v"(x.w[r + 1]), "+v"(x.w[r + 2]), "+v"(x.w[r + 3]), "+v"(x.w[r + 4]), "+v"(x.w[r + 5]), "+v"(x.w[r + 6]), "+v"(x.w[r + 7]) :: "memory");
+            asm volatile("" : "+v"(x.d[r]), "+v"(x.d[r + 1]), "+v"(x.d[r + 2]), "+v"(x.d[r + 3]), "+v"(x.d[r + 4]), "+v"(x.d[r + 5]), "+v"(x.d[r + 6]), "+v"(x.d[r + 7]) :: "memory");
         }
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int q = wave * NB + i, r = q * 4 + (lane >> 4), c = (lane & 15) * 4;
-            __builtin_amdgcn_global_load_lds((glb_ptr)(g.B + (size_t)(k0 + r) * g.ldb + n0 + c), (lds_ptr)(smem + st * STAGE + A_STAGE + q * 256), 16, 0, 0);
-        }
+        for (int r = 0; r < 16; ++r) { pre.p0[r] = x.w[r]; pre.p1[r] = x.d[r]; }
+    }
+
+    // One k-tile: uniform row base (SGPRs) + the lane's byte offset inside a k-tile of its panel (lane_off; NA = NB = 1: wave w
+    // moves k-rows 4w .. 4w+3 of either operand) -- one address register per operand instead of a 64-bit address per load.
+    static_assert(NA == 1 && NB == 1, "one LDS-DMA per wave, operand and k-tile");
+    static __device__ __forceinline__ unsigned lane_off(int ld, int wave, int lane) { return 4u * ((unsigned)(wave * 4 + (lane >> 4)) * (unsigned)ld + (unsigned)(lane & 15) * 4u); }
+    static __device__ __forceinline__ void issue_tile(const Src &s, int k0, float *smem, int st, int wave, int lane)
+    {
+        const char *pa = reinterpret_cast<const char *>(sgpr_row_base(s.a + (size_t)k0 * s.lda));
+        const char *pb = reinterpret_cast<const char *>(sgpr_row_base(s.b + (size_t)k0 * s.ldb));
+        __builtin_amdgcn_global_load_lds((glb_ptr)(pa + lane_off(s.lda, wave, lane)), (lds_ptr)(smem + st * STAGE + wave * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_ptr)(pb + lane_off(s.ldb, wave, lane)), (lds_ptr)(smem + st * STAGE + A_STAGE + wave * 256), 16, 0, 0);
     }
     static __device__ __forceinline__ void multiply(const float *smem, int st, int a_off, int b_off, int kh, f32x16 (&acc)[2])
     {
@@ -66,18 +158,22 @@ struct WgradDma {
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    // k-tile T of the tile `cur`.  carried: this is not the workgroup's first tile, so the epilogue stores of the tile before lie in
+    // the queue between k-tiles D-1 and D.
     template <int T>
-    static __device__ __forceinline__ void iter(const GemmArgs &g, const EpiArgs &e, int m0, int n0, float *smem, int wave, int lane, int tid,
-                                                int a_off, int b_off, int kh, int mb, int nb, bool do_bias, float &bsum, f32x16 (&acc)[2], EpiPre &pre)
+    static __device__ __forceinline__ void iter(const Src &cur, const Src &nxt, const EpiArgs &e, bool carried, float *smem, int wave, int lane, int tid,
+                                                int a_off, int b_off, int kh, int mb, int nb, bool do_bias, float &bsum, f32x16 (&acc)[2], WD &wd)
     {
         if constexpr (T < NT) {
-            // in flight at this point: tiles T .. min(T+D, NT)-1, plus the 32 W/delta loads once the last tile has been issued
-            constexpr int tiles_after = (T + D < NT ? D : NT - T) - 1;
-            constexpr bool wd_out = T + D > NT;                       // W/delta were issued in an earlier iteration (right after tile NT-1)
-            VmWait<tiles_after * NDMA + (wd_out ? NWD : 0)>::go();
+            // behind k-tile T at this point: k-tiles T+1 .. T+D-1 (of the next tile from NT on), the W/delta loads once issued, and
+            // the previous tile's stores while k-tile D has not been issued
+            constexpr int behind = (D - 1) * NDMA + (T + D > NT ? NWD : 0);
+            if constexpr (T < D) { if (carried) VmWait<behind + NST>::go(); else VmWait<behind>::go(); }
+            else VmWait<behind>::go();
             __builtin_amdgcn_s_barrier();
-            if constexpr (T + D < NT) issue_tile(g, m0, n0, (T + D) * BK, smem, (T + D) % ST, wave, lane);
-            if constexpr (T + D == NT && !STORE) epilogue_fetch<EPI_WGRAD_UPDATE, 0, 16>(e, mb, nb, lane, pre);   // behind the last tile (issued at T-1)
+            if constexpr (T + D < NT) issue_tile(cur, (T + D) * BK, smem, (T + D) % ST, wave, lane);
+            if constexpr (T + D == NT && !STORE) wd_fetch(e, mb, nb, lane, wd);   // behind the last k-tile (issued at T-1)
+            if constexpr (T + D >= NT) issue_tile(nxt, (T + D - NT) * BK, smem, (T + D) % ST, wave, lane);       // the next tile's head
             if (do_bias) {
                 constexpr int RPT = BK / 4;
                 const float *bs = smem + (T % ST) * STAGE + A_STAGE + (tid >> 6) * RPT * BN + (tid & 63);
@@ -85,38 +181,52 @@ struct WgradDma {
                 for (int k = 0; k < RPT; ++k) bsum += bs[k * BN];
             }
             multiply(smem, T % ST, a_off, b_off, kh, acc);
-            iter<T + 1>(g, e, m0, n0, smem, wave, lane, tid, a_off, b_off, kh, mb, nb, do_bias, bsum, acc, pre);
+            iter<T + 1>(cur, nxt, e, carried, smem, wave, lane, tid, a_off, b_off, kh, mb, nb, do_bias, bsum, acc, wd);
         }
     }
-    static __device__ __forceinline__ void run(const GemmArgs &g, const EpiArgs &e, int first_block, int stride, float *smem)
+    // Workgroup w of G walks the entries w, w + G, ... of the launch's tile list.
+    static __device__ __forceinline__ void run(const MultiArgs &a, float *smem)
     {
         const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int wm = wave >> 1, wn = wave & 1;
-        for (int b = first_block; b < g.tiles_m * g.tiles_n; b += stride) {
-            int tile_m, tile_n;
-            if ((g.tiles_n & 7) == 0) { const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3; tile_n = xcd * per + j % per; tile_m = j / per; }
-            else { tile_m = b % g.tiles_m; tile_n = b / g.tiles_m; }
-            const int m0 = tile_m * BM, n0 = tile_n * BN, mb = m0 + wm * 32, nb = n0 + wn * 32;
+        const int stride = gridDim.x, total = a.first_tile[a.n];
+        Pos t; t.p = 0;
+        int i = seek(a, blockIdx.x, stride, total, t);
+        if (i >= total) return;
+        Src cur = src_of(a, t);
+#pragma unroll
+        for (int k = 0; k < D; ++k) issue_tile(cur, k * BK, smem, k, wave, lane);
+        bool carried = false;
+        for (;;) {
+            // the tile after this one; none: the same loads again from this tile's panels, never read (a conditional load would
+            // cost every wait its immediate)
+            Pos tn = t;
+            const int in = seek(a, i + stride, stride, total, tn);
+            const bool more = in < total;
+            const Src nxt = more ? src_of(a, tn) : cur;
+            const EpiArgs &e = a.e[t.p];
+            const int mb = t.m0 + wm * 32, nb = t.n0 + wn * 32;
             const int a_off = wm * 32 + (lane & 31), b_off = wn * 32 + (lane & 31), kh = lane >> 5;
             f32x16 acc[2];
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-            const bool do_bias = tile_m == 0;
+            const bool do_bias = t.m0 == 0;
             float bsum = 0.f;
-            EpiPre pre;
-#pragma unroll
-            for (int t = 0; t < D; ++t) issue_tile(g, m0, n0, t * BK, smem, t, wave, lane);
-            iter<0>(g, e, m0, n0, smem, wave, lane, tid, a_off, b_off, kh, mb, nb, do_bias, bsum, acc, pre);
+            WD wd;
+            iter<0>(cur, nxt, e, carried, smem, wave, lane, tid, a_off, b_off, kh, mb, nb, do_bias, bsum, acc, wd);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[0][r] += acc[1][r];
-            __syncthreads();
             if (do_bias) {
-                float *red = smem;
+                // scratch in stage ST-1: it held this tile's last k-tile and is next written by k-tile D of the next tile, behind the
+                // barrier of its iter<0>; stages 0..D-1 are receiving the next tile.  Raw barriers: nothing is drained.
+                float *red = smem + (ST - 1) * STAGE;
+                __builtin_amdgcn_s_barrier();                     // every wave has multiplied the last k-tile
                 red[(tid >> 6) * BN + (tid & 63)] = bsum;
-                __syncthreads();
-                if (tid < BN && n0 + tid < e.n_limit) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                if (tid < BN && t.n0 + tid < e.n_limit) {
                     const float s = (red[tid] + red[BN + tid]) + (red[2 * BN + tid] + red[3 * BN + tid]);
-                    const int n = n0 + tid;
+                    const int n = t.n0 + tid;
                     if constexpr (STORE) {
                         __hip_atomic_store(e.bias_g + n, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);     // (write-through, like the tile below)
                     } else {
@@ -125,9 +235,11 @@ struct WgradDma {
                         e.bias_w[n] = d + 1.0f * e.bias_w[n];
                     }
                 }
-                __syncthreads();
             }
+            EpiPre pre;
+            if constexpr (!STORE) wd_landed(wd, pre);
             epilogue_block<EPI, 0, 16>(e, mb, nb, acc[0], lane, pre);
+            if (mb >= e.m_limit || nb >= e.n_limit) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no stores: NST does not hold
             if constexpr (STORE) {
                 // data-parallel step: tell the exchange stream that this tile of the layer's gradient segment is complete, WITHOUT a
                 // kernel boundary (one grouped launch for all layers; the exchange of layer 1 starts while the other layers' tiles
@@ -138,13 +250,17 @@ struct WgradDma {
                 // Measured alternatives (C2 through the exchange path at world 1, profiles/r05_dp_world1.txt): a system-scope RELEASE on
                 // the count (ADVICE r4's first proposal: one buffer_wbl2 per tile, 3648 per step) 0.3445 ms against 0.2533; one release
                 // per layer on every XCD inside bp_dp_sync 0.2750 (16 waves) / 0.2640 (8) against 0.2551.
+                // (The drain takes the next tile's head with it: it was issued before the stores.)
                 if (e.done) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __syncthreads();
                     if (tid == 0) __hip_atomic_fetch_add(e.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
             }
+            if (!more) break;
+            t = tn; i = in; cur = nxt; carried = true;
         }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the unread head behind the last tile lands before the LDS is given back
     }
 };
 
@@ -153,8 +269,5 @@ __global__ __launch_bounds__(256, MINWG) void bp_wgrad_dma(const MultiArgs a)
 {
     using K = WgradDma<BKX, STX, MINWG, KTOT, STORE>;
     __shared__ __attribute__((aligned(16))) float smem[K::SMEM];
-    const int b = blockIdx.x;
-    int p = 0;
-    while (p + 1 < a.n && b >= a.first_tile[p + 1]) ++p;
-    K::run(a.g[p], a.e[p], b - a.first_tile[p], a.first_tile[p + 1] - a.first_tile[p], smem);
+    K::run(a, smem);
 }
