@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "bp_enhance_waves", "bp_wave_lps",
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
     "bp_score_waves", "bp_eval_mix",
+    "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
@@ -80,6 +81,15 @@ class BPMixCorpus(C.Structure):
         ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
         ("n_clean", C.c_int), ("clean_len", C.POINTER(C.c_int64)), ("clean_pcm", C.POINTER(C.c_float)),
         ("n_noise", C.c_int), ("noise_len", C.POINTER(C.c_int64)), ("noise_pcm", C.POINTER(C.c_float)),
+    ]
+
+
+class BPStreamConfig(C.Structure):
+    """bp_stream_config (include/bp_c_api.h): a streaming session of n_chan channels."""
+    _fields_ = [
+        ("fea_dim", C.c_int), ("context", C.c_int), ("targ_offset", C.c_int),
+        ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
+        ("target", C.c_int), ("out_col", C.c_int), ("n_chan", C.c_int), ("max_push_samples", C.c_int),
     ]
 
 
@@ -134,6 +144,10 @@ def load_library(path=None):
     lib.bp_mix_shuffle.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
     lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
     lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
+    lib.bp_stream_open.argtypes = [hp, C.POINTER(BPStreamConfig), C.POINTER(C.c_void_p)]
+    lib.bp_stream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
+    lib.bp_stream_close.argtypes = [C.c_void_p]
+    lib.bp_stream_counts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -376,6 +390,21 @@ class BP_GPU(object):
             return waves
         return waves, np.split(net[:int(frames.sum())], np.cumsum(frames)[:-1])
 
+    # ---- streaming sessions (bp_stream_open ...; contract: include/bp_c_api.h)
+    def stream_open(self, mean, inv_std, context, targ_offset, target=WAVE_LPS, out_col=0, n_chan=1, max_push_samples=16000):
+        """A Stream of n_chan channels on this handle: push(blocks, end) returns the samples that became final, the same bits as
+        enhance_waves on the finished sentences.  Close it (or the handle) when done."""
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+        inv_std = np.ascontiguousarray(inv_std, dtype=np.float32).reshape(-1)
+        if inv_std.size != mean.size:
+            self._fail("stream_open: mean and inv_std differ in length")
+        c = BPStreamConfig()
+        c.fea_dim, c.context, c.targ_offset, c.mean, c.inv_std = mean.size, int(context), int(targ_offset), _fp(mean), _fp(inv_std)
+        c.target, c.out_col, c.n_chan, c.max_push_samples = int(target), int(out_col), int(n_chan), int(max_push_samples)
+        s = C.c_void_p()
+        self._check(self._lib.bp_stream_open(self._h, C.byref(c), C.byref(s)))
+        return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan))
+
     # ---- training mixtures made on the device (bp_set_mix_corpus ...; definition: include/bp_c_api.h, INTEGRATION.md 1e)
     def set_mix_corpus(self, clean, noise, mean, inv_std, context, targ_offset, target=MIX_LPS, lc_db=5.0):
         """clean, noise: lists of 1-D arrays (int16 units), uploaded once; target: MIX_* or a name of MIX_TARGETS."""
@@ -579,7 +608,7 @@ class BP_GPU(object):
 
     def close(self):
         if self._h is not None:
-            self._lib.bp_destroy(self._h)
+            self._lib.bp_destroy(self._h)       # (releases the handle's open streams too)
             self._h = None
 
     def __del__(self):
@@ -587,6 +616,55 @@ class BP_GPU(object):
             self.close()
         except Exception:
             pass
+
+
+class Stream(object):
+    """A streaming session (bp_stream_*): n_chan live feeds enhanced in blocks of any sizes."""
+
+    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan):
+        self._g, self._s = owner, s
+        self.fea_dim, self.context, self.targ_offset, self.n_chan = fea_dim, context, targ_offset, n_chan
+        self.look_ahead = context - 1 - targ_offset
+
+    def push(self, blocks, end=None, out_cap=None):
+        """blocks: one 1-D array of new samples per channel (None or empty: none); end: per channel, true closes the channel's
+        sentence after these samples.  Returns one float32 array per channel: the samples that became final.  out_cap: size of
+        the output buffer in samples (default: everything a push of this size can return)."""
+        g = self._g
+        if self._s is None or g._h is None:
+            g._fail("Stream.push: the stream or its handle is closed")
+        if len(blocks) != self.n_chan or (end is not None and len(end) != self.n_chan):
+            g._fail("Stream.push: need one block (and one end flag) per channel (%d)" % self.n_chan)
+        arrs = [np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
+        n_in = np.array([a.size for a in arrs], np.int32)
+        pcm = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(0, np.float32)
+        e = None if end is None else np.ascontiguousarray([1 if v else 0 for v in end], dtype=np.uint8)
+        hop = self.fea_dim - 1
+        if out_cap is None:     # what waited (at most max(look-ahead, 5) + 1 frames) and what arrived, rounded up to frames
+            out_cap = int(pcm.size) + self.n_chan * (max(self.look_ahead, 5) + 3) * hop
+        out = np.empty(max(int(out_cap), 1), np.float32)
+        n_out = np.zeros(self.n_chan, np.int32)
+        ip = C.POINTER(C.c_int)
+        g._check(g._lib.bp_stream_push(self._s, n_in.ctypes.data_as(ip), _fp(pcm) if pcm.size else None,
+                                       None if e is None else e.ctypes.data_as(C.POINTER(C.c_ubyte)), n_out.ctypes.data_as(ip),
+                                       _fp(out), int(out_cap)))
+        return [a.copy() for a in np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])]
+
+    def close(self):
+        if self._s is not None and self._g._h is not None:
+            self._g._lib.bp_stream_close(self._s)
+        self._s = None
+
+
+def stream_counts(fea_dim, context, targ_offset, nat, received, ended):
+    """bp_stream_counts: (frames_in, frames_out, samples_out) of a channel after `received` samples of its sentence; host only."""
+    lib = load_library()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.bp_stream_counts(int(fea_dim), int(context), int(targ_offset), 1 if nat else 0, int(received), 1 if ended else 0,
+                              C.byref(a), C.byref(b), C.byref(c))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def _sentences(sentences, fea_dim):

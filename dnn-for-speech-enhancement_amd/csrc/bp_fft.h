@@ -80,6 +80,55 @@ __device__ __forceinline__ float2 rfft_bin(const float2 *z, const float2 *__rest
 // the LPS of one bin's power, with the 1e-10 floor
 __device__ __forceinline__ float lps_of(float p) { return p > 1e-10f ? logf(p) : LN_FLOOR; }
 
+// Synthesis of one frame (bp_wave_synthesis, bp_stream_synthesis): S from the net outputs o[0 .. M] and the noisy spectrum
+// Y[0 .. M], inverse real FFT, times the window -> fr[0 .. 2M) (16-byte aligned; global or LDS).  z: lds_bytes(M) of FFT space
+// followed by M + 1 float2 for S.  Every thread of the workgroup calls it; no barrier behind the stores to fr.
+__device__ __forceinline__ void synth_frame(float2 *z, const float *__restrict__ o, const float2 *__restrict__ Y, const float *__restrict__ win,
+                                            const float2 *__restrict__ tw, int log2M, int target, float *fr)
+{
+    const int M = 1 << log2M, N = 2 * M, tid = threadIdx.x;
+    float2 *S = z + lds_bytes(M) / sizeof(float2);      // S[0 .. M], unpadded (read twice below, written once)
+    for (int k = tid; k <= M; k += blockDim.x) {
+        const float2 y = Y[k];
+        const float ok = o[k];
+        float2 v;
+        if (target == BP_WAVE_MASK) v = make_float2(ok * y.x, ok * y.y);
+        else {
+            const float r = sqrtf(y.x * y.x + y.y * y.y), m = expf(0.5f * ok);
+            v = r > 0.0f ? make_float2(m * (y.x / r), m * (y.y / r)) : make_float2(m, 0.0f);
+        }
+        if (k == 0 || k == M) v.y = 0.0f;               // (irfft ignores the imaginary part of DC and Nyquist)
+        S[k] = v;
+    }
+    __syncthreads();
+    // inverse split step: Z[k] = E[k] + i O[k], E = (S[k] + conj S[M-k]) / 2, O = (S[k] - conj S[M-k]) conj(W^k) / 2
+    for (int k = tid; k < M; k += blockDim.x) {
+        const float2 sk = S[k], sm = S[M - k];
+        const float2 e = make_float2(0.5f * (sk.x + sm.x), 0.5f * (sk.y - sm.y));
+        const float2 d = make_float2(0.5f * (sk.x - sm.x), 0.5f * (sk.y + sm.y));
+        const float2 od = cmulc(d, tw[k]);
+        z[lp((int)(__brev((unsigned)k) >> (32 - log2M)))] = make_float2(e.x - od.y, e.y + od.x);
+    }
+    __syncthreads();
+    fft_lds(z, M, tw, true);
+    const float sc = 1.0f / (float)M;
+    for (int q = tid; q < N / 4; q += blockDim.x) {
+        const float2 z0 = z[lp(2 * q)], z1 = z[lp(2 * q + 1)];
+        const float4 w = *reinterpret_cast<const float4 *>(win + 4 * q);
+        *reinterpret_cast<float4 *>(fr + 4 * q) = make_float4(z0.x * sc * w.x, z0.y * sc * w.y, z1.x * sc * w.z, z1.y * sc * w.w);
+    }
+}
+
+// Least-squares overlap-add of four samples: a from the frame that starts at the segment, b from the second half of the frame
+// before it, wa / wb the window values at those offsets
+__device__ __forceinline__ float4 overlap4(float4 a, float4 b, float4 wa, float4 wb)
+{
+    // (the fused multiply-add is spelled out: which of the two squares the compiler would fuse depends on the code around the
+    // call, and both callers must return the same bits)
+    return make_float4((a.x + b.x) / fmaf(wa.x, wa.x, wb.x * wb.x), (a.y + b.y) / fmaf(wa.y, wa.y, wb.y * wb.y),
+                       (a.z + b.z) / fmaf(wa.z, wa.z, wb.z * wb.z), (a.w + b.w) / fmaf(wa.w, wa.w, wb.w * wb.w));
+}
+
 }  // namespace
 
 // bp_wave_analysis arguments (bp_wave.hip): frame g of sentence s reads the padded samples [(g + s) hop, (g + s) hop + n_fft).

@@ -9,6 +9,7 @@
 //   bp_wave.hip     the signal layer: STFT analysis into a window chunk, overlap-add resynthesis (bp_enhance_waves, bp_wave_lps)
 //   bp_mix.hip      training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...)
 //   bp_eval.hip     objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval_mix lives in bp_mix.hip)
+//   bp_stream.hip   streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -115,6 +116,8 @@ struct bp_handle {
     Raw wave[4], wave_pin[2];
     // bp_set_mix_corpus (bp_mix.hip): the resident corpus and the grow-only buffers of the mixing calls, or null
     struct MixState *mix;
+    // bp_stream_open (bp_stream.hip): the open streaming sessions of this handle
+    std::vector<struct bp_stream *> streams;
 };
 
 // Coefficients of the momentum update (update_delta, bp_device.h; DevFunc.cu:313-318 for momentum_rule 0, :306-311 for 1):
@@ -177,6 +180,9 @@ int forward_resident(bp_handle *h, int n);
 
 // ------------------------------------------------------------------ mixtures (bp_mix.hip)
 void mix_free(bp_handle *h);                      // the corpus and the mixing buffers (bp_destroy)
+
+// ------------------------------------------------------------------ streaming sessions (bp_stream.hip)
+void stream_free_all(bp_handle *h);               // every open stream of the handle (bp_destroy)
 
 // ------------------------------------------------------------------ data-parallel driver (bp_dp.hip)
 int dp_check(bp_handle *h);                       // BP_OK, or the device-side timeout an exchange kernel raised

@@ -1,4 +1,4 @@
-// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 6: training mixtures made on the device.  A clean-speech
+// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 7: training mixtures made on the device.  A clean-speech
 // corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
 // SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
 // reads.  gfx950 only.

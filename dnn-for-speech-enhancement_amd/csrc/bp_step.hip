@@ -74,6 +74,7 @@ extern "C" int bp_destroy(bp_handle *h)
     for (auto &r : h->wave) if (r.p) (void)hipFree(r.p);
     for (auto &r : h->wave_pin) if (r.p) (void)hipHostFree(r.p);
     mix_free(h);
+    stream_free_all(h);
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
     if (h->ev_retired) (void)hipEventDestroy(h->ev_retired);

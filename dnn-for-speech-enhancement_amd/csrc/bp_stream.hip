@@ -1,0 +1,483 @@
+// bp_stream.hip -- C-ABI implementation (include/bp_c_api.h), part 7 of 7: streaming sessions.  Audio that is still arriving is
+// enhanced in blocks of any sizes, on n_chan independent channels per push, and returns the SAME BITS as one bp_enhance_waves
+// call on the finished sentence: the analysis and the synthesis are the device functions of bp_wave.hip (bp_fft.h), the forward
+// is forward_resident on a window chunk, and the overlap-add is the same gather of two frames.  gfx950 only.
+//
+// What a channel has after `received` samples of its sentence is a pure function of that number (stream_counts, exported as
+// bp_stream_counts): frames analysed fi, frames enhanced fo, samples returned.  The host plans a push from those numbers alone
+// and never reads device state.  It keeps each channel's carry -- the last hop + received % hop samples -- and builds ONE
+// pinned input block per push: three job tables and every active channel's [carry | new] samples at hop-aligned places, so
+// that the frame loads of the analysis are the aligned 16-byte loads of rfft_frame.
+//
+// Device state of a channel (allocated at open, R = context + 6 slots, all of it double-buffered by a parity that the host flips
+// whenever a push touches it, so that no launch reads what another workgroup of the same launch writes):
+//   rows  the normalised rows of frames [max(0, fo - targ_offset), fi): the history the next windows need
+//   Y     the noisy spectra of frames [fo, fi): analysed, waiting for their look-ahead (same slots as the rows)
+//   nat   the noise-aware row of the sentence (single: written once per sentence, by a launch of its own)
+//   half  the second half of the last synthesised frame
+//
+// Kernels (one workgroup of 256 threads per job; tables in the input block):
+//   bp_stream_analysis   a new frame: window, FFT, Y, LPS, normalised row -- or an old frame: its row (and Y) from the state.  Either
+//                        goes where it is needed: the staged rows of the push's window chunk (replicated at the sentence's edges),
+//                        the Y of the push, the other parity of the state; plus the frame's win_start / nat_row entries
+//   bp_stream_nat        the noise-aware row, once per sentence, in bp_wave_nat's summation order; later pushes copy it into the chunk
+//   bp_stream_synthesis  per enhanced frame: its synthesis, the synthesis of the frame before it when that is of the same push
+//                        (else the carried half), overlap-add into the compact output, the new carried half
+//
+// Where a frame sits in its bunch matters: the forward kernels give a row the same bits whoever its neighbours are, but NOT at
+// every row of the bunch (the in-workgroup k-split of the narrow-layer GEMM hands rows 16..23 and 24..31 of a tile to waves that add
+// the four partial sums in another order; measured: one sentence alone and the same sentence behind others differ in the last bit).
+// bp_enhance_waves on one sentence runs frame t as row t mod bunchsize, so a push places frame t of a channel at a sample g with
+// g = t (mod bunchsize): the channels of a push start in bunches of their own unless their rows happen to follow each other, and
+// the samples in between are fillers (window 0, computed and ignored).
+// No float atomics.  Per push: one host->device copy, one device->host copy, one synchronisation.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "bp_fft.h"
+#include "bp_handle.h"
+
+namespace {
+
+// src >= 0: analyse the frame at hop unit src of the block's samples; src < 0: copy state slot -1 - src.
+// Staged rows [stage_lo, stage_hi) of the window chunk get the row; state_dst (or -1) is its slot in the new parity;
+// g >= 0: the frame is enhanced by this push as sample g of the window chunk (win_start[g] = ws, nat_row[g] = chan) and its Y
+// goes to row y of the push's Y; y_state >= 0: the frame waits, Y to that slot.  has_y: a copied frame whose Y is still needed.
+struct AnaJob { int src, stage_lo, stage_hi, state_dst, g, ws, chan, y_state, has_y, y, pad[2]; };
+// mode 0: from the staged rows (src = row of frame 0), 1: from the state rows (src = slot of frame 0), 2: copy the state's row.
+// nf = min(T, 6) frames exist; stage: also into the chunk's NAT rows.
+struct NatJob { int chan, mode, src, nf, stage, pad[3]; };
+// The frame is sample g of the chunk (its net output) and row y of the push's Y.  prev: -1 none (frame 0 of a sentence: front
+// padding, no output), 0 the frame before it is of this push too (sample g - 1, row y - 1), 1 the carried half in slot half_src.
+// out_n samples to out_off of the compact output; half_dst (or -1): where the second half goes.
+struct SynJob { int g, prev, half_src, out_off, out_n, half_dst, y, pad; };
+
+struct StreamAnaArgs {
+    const AnaJob *jobs; const float *pcm, *win; const float2 *tw; const float *mean, *inv_std;
+    int log2M, D, hop;
+    float *st_rows; float2 *st_Y;       // [2][n_chan][R][D]
+    float *rows; float2 *Y;             // the push: staged rows of the window chunk, Y[y][D]
+    int *win_start, *nat_row;
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_stream_analysis(const StreamAnaArgs a)
+{
+    extern __shared__ float2 z[];
+    const AnaJob j = a.jobs[blockIdx.x];
+    const int M = 1 << a.log2M, tid = threadIdx.x;
+    if (j.src >= 0) rfft_frame(z, a.pcm + (size_t)j.src * a.hop, a.win, a.tw, a.log2M);
+    for (int k = tid; k <= M; k += blockDim.x) {
+        float v;
+        float2 X = make_float2(0.0f, 0.0f);
+        if (j.src >= 0) {
+            X = rfft_bin(z, a.tw, M, k);
+            const float p = X.x * X.x + X.y * X.y;
+            const float l = lps_of(p);
+            v = (l - a.mean[k]) * a.inv_std[k];
+        } else {
+            const size_t si = (size_t)(-1 - j.src) * a.D + k;
+            v = a.st_rows[si];
+            if (j.has_y) X = a.st_Y[si];
+        }
+        for (int u = j.stage_lo; u < j.stage_hi; ++u) a.rows[(size_t)u * a.D + k] = v;
+        if (j.state_dst >= 0) a.st_rows[(size_t)j.state_dst * a.D + k] = v;
+        if (j.g >= 0) a.Y[(size_t)j.y * a.D + k] = X;
+        if (j.y_state >= 0) a.st_Y[(size_t)j.y_state * a.D + k] = X;
+    }
+    if (j.g >= 0 && tid == 0) { a.win_start[j.g] = j.ws; if (a.nat_row) a.nat_row[j.g] = j.chan; }
+}
+
+// nat[k] = ((((v0 + v1) + v2) + v3) + v4 + v5) / 6 over the sentence's first 6 normalised frames, frame f clamped to nf - 1
+__global__ __launch_bounds__(WAVE_THREADS) void bp_stream_nat(const NatJob *__restrict__ jobs, const float *__restrict__ rows,
+                                                           const float *__restrict__ st_rows, int D, float *__restrict__ st_nat,
+                                                           float *__restrict__ nat)
+{
+    const int kb = (D + WAVE_THREADS - 1) / WAVE_THREADS, k = (blockIdx.x % kb) * WAVE_THREADS + threadIdx.x;
+    const NatJob j = jobs[blockIdx.x / kb];
+    if (k >= D) return;
+    float out;
+    if (j.mode == 2) out = st_nat[(size_t)j.chan * D + k];
+    else {
+        const float *r = (j.mode == 0 ? rows : st_rows) + (size_t)j.src * D + k;
+        float acc = 0.0f;
+        for (int f = 0; f < 6; ++f) { const float v = r[(size_t)(f < j.nf ? f : j.nf - 1) * D]; acc = f == 0 ? v : acc + v; }
+        out = acc / 6.0f;
+        st_nat[(size_t)j.chan * D + k] = out;
+    }
+    if (j.stage) nat[(size_t)j.chan * D + k] = out;
+}
+
+namespace {
+// floats of LDS in front of the two frames of bp_stream_synthesis: synth_frame's FFT space and S, rounded up to 16 bytes
+__host__ __device__ inline size_t syn_frames_at(int M) { return ((lds_bytes(M) + (size_t)(M + 1) * sizeof(float2) + 15) & ~(size_t)15) / sizeof(float); }
+struct StreamSynArgs {
+    const SynJob *jobs;
+    const float *out; int ldo, out_col;     // net outputs [n][ldo], columns [out_col, out_col + D)
+    const float2 *Y; const float *win; const float2 *tw;
+    int log2M, D, target;
+    float *half;                            // [2][n_chan][hop]
+    float *pcm;                             // compact output of the push
+};
+}  // namespace
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_stream_synthesis(const StreamSynArgs a)
+{
+    extern __shared__ __align__(16) float2 zs[];
+    float2 *z = zs;
+    const SynJob j = a.jobs[blockIdx.x];
+    const int M = 1 << a.log2M, N = 2 * M, hop = M, tid = threadIdx.x;
+    float *cur = reinterpret_cast<float *>(zs) + syn_frames_at(M), *prev = cur + N;   // two frames behind synth_frame's space
+    synth_frame(z, a.out + (size_t)j.g * a.ldo + a.out_col, a.Y + (size_t)j.y * a.D, a.win, a.tw, a.log2M, a.target, cur);
+    __syncthreads();
+    if (j.prev == 0) {
+        synth_frame(z, a.out + (size_t)(j.g - 1) * a.ldo + a.out_col, a.Y + (size_t)(j.y - 1) * a.D, a.win, a.tw, a.log2M, a.target, prev);
+        __syncthreads();
+    }
+    if (j.prev >= 0) {
+        const float *pv = j.prev == 0 ? prev + hop : a.half + (size_t)j.half_src * hop;
+        float *dst = a.pcm + j.out_off;                 // compact: only 4-byte aligned
+        for (int q = tid; q < hop / 4; q += blockDim.x) {
+            const float4 x = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(pv + 4 * q);
+            const float4 wa = *reinterpret_cast<const float4 *>(a.win + 4 * q), wb = *reinterpret_cast<const float4 *>(a.win + hop + 4 * q);
+            const float4 r = overlap4(x, b, wa, wb);
+            const int i = 4 * q;
+            if (i < j.out_n) dst[i] = r.x;
+            if (i + 1 < j.out_n) dst[i + 1] = r.y;
+            if (i + 2 < j.out_n) dst[i + 2] = r.z;
+            if (i + 3 < j.out_n) dst[i + 3] = r.w;
+        }
+    }
+    if (j.half_dst >= 0) {
+        float *hd = a.half + (size_t)j.half_dst * hop;
+        for (int q = tid; q < hop / 4; q += blockDim.x)
+            *reinterpret_cast<float4 *>(hd + 4 * q) = *reinterpret_cast<const float4 *>(cur + hop + 4 * q);
+    }
+}
+
+// ------------------------------------------------------------------ host side
+namespace {
+
+// What a channel has produced after `received` samples of its sentence (include/bp_c_api.h)
+struct Counts { int64_t fi, fo, so; };
+Counts stream_counts(int hop, int la, bool nat, int64_t received, bool ended)
+{
+    Counts c = {0, 0, 0};
+    if (received <= 0) return c;
+    const int64_t T = (received - 1) / hop + 2;
+    c.fi = ended ? T : received / hop;
+    const bool known = !nat || ended || c.fi >= 6;
+    c.fo = !known ? 0 : ended ? T : std::max<int64_t>(0, c.fi - la);
+    c.so = ended ? received : std::max<int64_t>(0, c.fo - 1) * hop;
+    return c;
+}
+
+size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct Chan {
+    int64_t received;            // samples of the current sentence
+    int par, hpar;               // parity of the rows / Y state and of the carried half frame
+    int carry_n;                 // hop + received % hop
+    std::vector<float> carry;    // [2 hop]: the samples the next frame starts with (hop zeros in front of a sentence)
+};
+
+// plan of one channel for one push
+struct ChanPlan { int64_t r1, g0; bool ended; Counts c0, c1; };   // g0: the chunk sample of the channel's first frame
+
+}  // namespace
+
+struct bp_stream {
+    bp_handle *h;
+    int D, ctx, toff, la, target, out_col, n_chan, max_push, hop, log2M, R;
+    bool nat;
+    std::vector<Chan> ch;
+    std::vector<ChanPlan> plan;
+    std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<SynJob> syn;
+    size_t max_enh;              // samples (frames to enhance) of one push at most
+    char *dev;                   // consts | state | input block | Y of the push | output samples
+    size_t o_mean, o_istd, o_win, o_tw, o_rows, o_Y, o_nat, o_half, o_in, o_pY, o_out, in_cap;
+    char *pin_in; float *pin_out;
+};
+
+static void stream_release(bp_stream *s)
+{
+    if (s->dev) (void)hipFree(s->dev);
+    if (s->pin_in) (void)hipHostFree(s->pin_in);
+    if (s->pin_out) (void)hipHostFree(s->pin_out);
+    delete s;
+}
+
+void stream_free_all(bp_handle *h)
+{
+    for (bp_stream *s : h->streams) stream_release(s);
+    h->streams.clear();
+}
+
+static int stream_cfg_check(const char *who, int fea_dim, int ctx, int toff)
+{
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (ctx < 1 || toff < 0 || toff >= ctx) return fail(BP_ERR_ARG, std::string(who) + ": need context >= 1 and 0 <= targ_offset < context");
+    return BP_OK;
+}
+
+extern "C" int bp_stream_counts(int fea_dim, int context, int targ_offset, int nat, int64_t received, int ended, int64_t *frames_in,
+                                int64_t *frames_out, int64_t *samples_out)
+{
+    { const int r = stream_cfg_check("bp_stream_counts", fea_dim, context, targ_offset); if (r != BP_OK) return r; }
+    if (received < 0) return fail(BP_ERR_ARG, "bp_stream_counts: received < 0");
+    if (!frames_in || !frames_out || !samples_out) return fail(BP_ERR_ARG, "bp_stream_counts: null output");
+    const Counts c = stream_counts(fea_dim - 1, context - 1 - targ_offset, nat != 0, received, ended != 0);
+    *frames_in = c.fi; *frames_out = c.fo; *samples_out = c.so;
+    return BP_OK;
+}
+
+extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream **out)
+{
+    if (!h || !c || !out) return fail(BP_ERR_ARG, "bp_stream_open: null argument");
+    { const int r = stream_cfg_check("bp_stream_open", c->fea_dim, c->context, c->targ_offset); if (r != BP_OK) return r; }
+    const int D = c->fea_dim, ctx = c->context, L = h->L, sL = h->s[L - 1];
+    if (!c->mean || !c->inv_std) return fail(BP_ERR_ARG, "bp_stream_open: null pointer");
+    const bool nat = (long)h->s[0] == (long)(ctx + 1) * D;
+    if (!nat && (long)h->s[0] != (long)ctx * D)
+        return fail(BP_ERR_ARG, "bp_stream_open: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
+    if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_stream_open: target must be BP_WAVE_LPS or BP_WAVE_MASK");
+    if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_stream_open: out_col + fea_dim exceeds layersizes[last]");
+    if (c->n_chan < 1 || c->n_chan > (1 << 16)) return fail(BP_ERR_ARG, "bp_stream_open: n_chan must be in 1 .. 65536");
+    if (c->max_push_samples < 1) return fail(BP_ERR_ARG, "bp_stream_open: max_push_samples must be >= 1");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_stream_open: not on an attached data-parallel handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+
+    bp_stream *s = new bp_stream();
+    s->h = h; s->D = D; s->ctx = ctx; s->toff = c->targ_offset; s->la = ctx - 1 - c->targ_offset; s->target = c->target;
+    s->out_col = c->out_col; s->n_chan = c->n_chan; s->max_push = c->max_push_samples; s->hop = D - 1; s->log2M = wave_log2_fft(D);
+    s->R = ctx + 6; s->nat = nat;
+    const int hop = s->hop, N = 2 * hop, nc = s->n_chan;
+    // A push analyses at most n_in/hop + 3 frames per channel (the end of a sentence adds up to 3) and enhances those plus the
+    // frames that waited; it can never enhance more than the chunk capacity lets it stage.
+    const size_t new_frames = (size_t)s->max_push / hop + 3 * (size_t)nc;
+    const size_t max_ana = new_frames + (size_t)nc * s->R;
+    s->max_enh = std::min(max_ana, (size_t)h->cap);
+    s->in_cap = al256(max_ana * sizeof(AnaJob)) + al256((size_t)nc * sizeof(NatJob)) + al256(s->max_enh * sizeof(SynJob)) +
+                al256((new_frames + nc) * hop * 4);
+    const size_t slots = 2 * (size_t)nc * s->R;
+    size_t o = 0;
+    s->o_mean = o; o += al256((size_t)D * 4);
+    s->o_istd = o; o += al256((size_t)D * 4);
+    s->o_win = o; o += al256((size_t)N * 4);
+    s->o_tw = o; o += al256((size_t)(hop + 1) * 8);
+    s->o_rows = o; o += al256(slots * D * 4);
+    s->o_Y = o; o += al256(slots * D * 8);
+    s->o_nat = o; o += al256((size_t)nc * D * 4);
+    s->o_half = o; o += al256(2 * (size_t)nc * hop * 4);
+    const size_t consts = s->o_rows;
+    s->o_in = o; o += s->in_cap;
+    s->o_pY = o; o += al256(s->max_enh * D * 8);
+    s->o_out = o; o += al256(s->max_enh * hop * 4);
+    hipError_t e = hipMalloc((void **)&s->dev, o);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_in, std::max(s->in_cap, consts));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_out, al256(s->max_enh * hop * 4));
+    if (e != hipSuccess) { stream_release(s); return fail(BP_ERR_NOMEM, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
+    int r = out_chunk_reserve(h, (int)(s->max_enh + (size_t)nc * h->B));   // (fillers included: so that no push has to grow it)
+    if (r != BP_OK) { stream_release(s); return r; }
+    // constants, once: the norm file, window and twiddles (computed in double and rounded once, as bp_enhance_waves does)
+    memset(s->pin_in, 0, consts);
+    memcpy(s->pin_in + s->o_mean, c->mean, (size_t)D * 4);
+    memcpy(s->pin_in + s->o_istd, c->inv_std, (size_t)D * 4);
+    wave_window_twiddles(s->log2M, (float *)(s->pin_in + s->o_win), (float2 *)(s->pin_in + s->o_tw));
+    e = hipMemcpyAsync(s->dev, s->pin_in, consts, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dev + s->o_rows, 0, s->o_in - s->o_rows, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { stream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
+    s->ch.resize(nc);
+    for (Chan &ch : s->ch) { ch.received = 0; ch.par = ch.hpar = 0; ch.carry_n = hop; ch.carry.assign((size_t)2 * hop, 0.0f); }
+    s->plan.resize(nc);
+    s->ana.reserve(max_ana); s->natj.reserve(nc); s->syn.reserve(s->max_enh);
+    h->streams.push_back(s);
+    *out = s;
+    return BP_OK;
+}
+
+extern "C" int bp_stream_close(bp_stream *s)
+{
+    if (!s) return BP_OK;
+    bp_handle *h = s->h;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipStreamSynchronize(h->stream);
+    h->streams.erase(std::remove(h->streams.begin(), h->streams.end(), s), h->streams.end());
+    stream_release(s);
+    return BP_OK;
+}
+
+extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, const unsigned char *end, int *n_out, float *out_pcm,
+                              size_t out_cap)
+{
+    if (!s || !n_in || !n_out) return fail(BP_ERR_ARG, "bp_stream_push: null argument");
+    bp_handle *h = s->h;
+    if (h->dp) return fail(BP_ERR_STATE, "bp_stream_push: not on an attached data-parallel handle");
+    const int D = s->D, ctx = s->ctx, toff = s->toff, hop = s->hop, nc = s->n_chan, R = s->R, L = h->L, B = h->B;
+    // ---- the plan: counts before and after, per channel (nothing of the stream changes until every check has passed)
+    int64_t total_in = 0, due = 0, n = 0, n_enh = 0, rows = 0, ana_max = 0, active = 0;
+    for (int c = 0; c < nc; ++c) {
+        if (n_in[c] < 0) return fail(BP_ERR_ARG, "bp_stream_push: n_in[" + std::to_string(c) + "] < 0");
+        total_in += n_in[c];
+        if (total_in > s->max_push)
+            return fail(BP_ERR_ARG, "bp_stream_push: more than max_push_samples = " + std::to_string(s->max_push) + " samples in one push");
+    }
+    if (total_in > 0 && !pcm) return fail(BP_ERR_ARG, "bp_stream_push: null pcm");
+    for (int c = 0; c < nc; ++c) {
+        ChanPlan &p = s->plan[c];
+        const Chan &ch = s->ch[c];
+        p.r1 = ch.received + n_in[c];
+        p.ended = end && end[c] && p.r1 > 0;
+        p.c0 = stream_counts(hop, s->la, s->nat, ch.received, false);
+        p.c1 = stream_counts(hop, s->la, s->nat, p.r1, p.ended);
+        const int64_t ne = p.c1.fo - p.c0.fo;
+        due += p.c1.so - p.c0.so; n_enh += ne;
+        if (ne > 0) { p.g0 = n + ((p.c0.fo - n) % B + B) % B; n = p.g0 + ne; }      // frame t as row t mod B of its bunch
+        if (ne > 0) rows += ne + ctx - 1;
+        if (p.c1.fi > p.c0.fi) { ana_max += p.c1.fi - std::max<int64_t>(0, p.c0.fo - toff); ++active; }
+        if (!p.ended && p.c1.fi - std::max<int64_t>(0, p.c1.fo - toff) > R)
+            return fail(BP_ERR_STATE, "bp_stream_push: internal: channel state exceeds context + 6 frames");
+    }
+    if ((size_t)due > out_cap) return fail(BP_ERR_ARG, "bp_stream_push: " + std::to_string(due) + " samples are due, out_cap is " + std::to_string(out_cap));
+    if (due > 0 && !out_pcm) return fail(BP_ERR_ARG, "bp_stream_push: null out_pcm");
+    if (rows > h->cap)
+        return fail(BP_ERR_ARG, "bp_stream_push: " + std::to_string(rows) + " rows (frames + context-1 per active channel) exceed the chunk capacity " +
+                                std::to_string(h->cap));
+    if ((size_t)n_enh > s->max_enh) return fail(BP_ERR_STATE, "bp_stream_push: internal: more frames than the stream was sized for");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    float *rows_d = nullptr, *nat_d = nullptr; int *tab_d = nullptr;
+    if (n > 0) {
+        int r;
+        if ((r = window_reserve(h, (size_t)rows * D * 4, 0, s->nat ? (size_t)nc * D * 4 : 0, (size_t)n, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
+        if ((r = out_chunk_reserve(h, (int)n)) != BP_OK) return r;
+    }
+    // ---- the input block: analysis jobs | NAT jobs | synthesis jobs | samples, each 256-byte aligned (the pinned block is reused
+    // by every push: the previous one ended in a synchronisation); with it the channels' new state
+    s->ana.clear(); s->natj.clear(); s->syn.clear();
+    const size_t o_ana = 0, o_nat = o_ana + al256((size_t)ana_max * sizeof(AnaJob)), o_syn = o_nat + al256((size_t)active * sizeof(NatJob));
+    const size_t o_pcm = o_syn + al256((size_t)n_enh * sizeof(SynJob));
+    float *hp = (float *)(s->pin_in + o_pcm);
+    size_t unit = 0, src = 0;
+    int64_t y0 = 0, srow = 0, out_base = 0;
+    for (int c = 0; c < nc; ++c) {
+        const ChanPlan &p = s->plan[c];
+        Chan &ch = s->ch[c];
+        const float *in = pcm ? pcm + src : nullptr;
+        src += (size_t)n_in[c];
+        const int64_t fi0 = p.c0.fi, fi1 = p.c1.fi, fo0 = p.c0.fo, fo1 = p.c1.fo, nf = fi1 - fi0, ne = fo1 - fo0;
+        if (nf > 0) {
+            // [carry | new] at hop unit `unit`, zeros behind a sentence's end: frame t starts at unit + t - fi0
+            float *x = hp + unit * hop;
+            const size_t seg = (size_t)(nf + 1) * hop, nca = std::min(seg, (size_t)ch.carry_n), nin = std::min(seg - nca, (size_t)n_in[c]);
+            memcpy(x, ch.carry.data(), nca * 4);
+            if (nin) memcpy(x + nca, in, nin * 4);
+            memset(x + nca + nin, 0, (seg - nca - nin) * 4);
+            const int64_t base0 = std::max<int64_t>(0, fo0 - toff), base1 = std::max<int64_t>(0, fo1 - toff), T = fi1;
+            const int64_t srows = ne > 0 ? ne + ctx - 1 : 0;
+            const int slot0 = (ch.par * nc + c) * R, slot1 = ((ch.par ^ 1) * nc + c) * R;
+            for (int64_t t = base0; t < fi1; ++t) {
+                AnaJob j; memset(&j, 0, sizeof(j));
+                // staged row u of the channel holds frame clamp(fo0 - toff + u, 0, T - 1) (the upper clamp only at the end)
+                int64_t lo = t == 0 ? 0 : t - fo0 + toff, hi = (p.ended && t == T - 1) ? srows : t - fo0 + toff + 1;
+                lo = std::max<int64_t>(lo, 0); hi = std::min(hi, srows);
+                if (lo < hi) { j.stage_lo = (int)(srow + lo); j.stage_hi = (int)(srow + hi); }
+                j.state_dst = (!p.ended && t >= base1) ? slot1 + (int)(t - base1) : -1;
+                const bool now = t >= fo0 && t < fo1;
+                j.g = now ? (int)(p.g0 + t - fo0) : -1; j.y = (int)(y0 + t - fo0); j.ws = (int)(srow + t - fo0); j.chan = c;
+                j.y_state = (!p.ended && t >= fo1) ? j.state_dst : -1;
+                if (t >= fi0) j.src = (int)(unit + (size_t)(t - fi0));
+                else {
+                    if (lo >= hi && j.state_dst < 0) continue;      // an old frame nobody needs any more
+                    j.src = -1 - (slot0 + (int)(t - base0)); j.has_y = t >= fo0;
+                }
+                s->ana.push_back(j);
+            }
+            if (s->nat) {
+                const bool known0 = fi0 >= 6, known1 = p.ended || fi1 >= 6;
+                NatJob j; memset(&j, 0, sizeof(j));
+                j.chan = c; j.stage = ne > 0;
+                if (!known0 && known1) {
+                    j.nf = (int)std::min<int64_t>(fi1, 6);
+                    if (ne > 0) { j.mode = 0; j.src = (int)(srow + toff); } else { j.mode = 1; j.src = slot1; }
+                    s->natj.push_back(j);
+                } else if (known0 && ne > 0) { j.mode = 2; s->natj.push_back(j); }
+            }
+            for (int64_t t = fo0; t < fo1; ++t) {
+                SynJob j; memset(&j, 0, sizeof(j));
+                j.g = (int)(p.g0 + t - fo0); j.y = (int)(y0 + t - fo0);
+                j.prev = t == 0 ? -1 : t == fo0 ? 1 : 0;
+                j.half_src = ch.hpar * nc + c;
+                j.out_off = (int)(out_base + (t - 1) * hop - p.c0.so);
+                j.out_n = t == 0 ? 0 : (int)std::min<int64_t>(hop, p.c1.so - (t - 1) * hop);
+                j.half_dst = (!p.ended && t == fo1 - 1) ? (ch.hpar ^ 1) * nc + c : -1;
+                s->syn.push_back(j);
+            }
+            unit += (size_t)(nf + 1);
+            y0 += ne; srow += srows; out_base += p.c1.so - p.c0.so;
+            ch.par ^= 1;
+            if (ne > 0) ch.hpar ^= 1;
+        }
+        n_out[c] = (int)(p.c1.so - p.c0.so);
+        // the carry: the last hop + r1 % hop samples of [carry | new]; a new sentence starts from hop zeros
+        if (p.ended) { ch.received = 0; ch.carry_n = hop; memset(ch.carry.data(), 0, (size_t)hop * 4); }
+        else if (n_in[c] > 0) {
+            const int keep = hop + (int)(p.r1 % hop);
+            if (n_in[c] >= keep) memcpy(ch.carry.data(), in + (n_in[c] - keep), (size_t)keep * 4);
+            else {
+                const int old = keep - n_in[c];                     // (old <= carry_n: carry_n + n_in >= keep)
+                memmove(ch.carry.data(), ch.carry.data() + (ch.carry_n - old), (size_t)old * 4);
+                memcpy(ch.carry.data() + old, in, (size_t)n_in[c] * 4);
+            }
+            ch.carry_n = keep; ch.received = p.r1;
+        }
+    }
+    if (s->ana.empty()) return BP_OK;                               // nothing became a frame: no device work
+    const size_t in_bytes = o_pcm + unit * hop * 4;
+    memcpy(s->pin_in + o_ana, s->ana.data(), s->ana.size() * sizeof(AnaJob));
+    if (!s->natj.empty()) memcpy(s->pin_in + o_nat, s->natj.data(), s->natj.size() * sizeof(NatJob));
+    if (!s->syn.empty()) memcpy(s->pin_in + o_syn, s->syn.data(), s->syn.size() * sizeof(SynJob));
+    char *din = s->dev + s->o_in;
+    HIPCHK(hipMemcpyAsync(din, s->pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const float *win = (const float *)(s->dev + s->o_win);
+    const float2 *tw = (const float2 *)(s->dev + s->o_tw);
+    float2 *Y = (float2 *)(s->dev + s->o_pY);
+    {
+        StreamAnaArgs a; memset(&a, 0, sizeof(a));
+        a.jobs = (const AnaJob *)(din + o_ana); a.pcm = (const float *)(din + o_pcm); a.win = win; a.tw = tw;
+        a.mean = (const float *)(s->dev + s->o_mean); a.inv_std = (const float *)(s->dev + s->o_istd);
+        a.log2M = s->log2M; a.D = D; a.hop = hop;
+        a.st_rows = (float *)(s->dev + s->o_rows); a.st_Y = (float2 *)(s->dev + s->o_Y);
+        a.rows = rows_d; a.Y = Y; a.win_start = tab_d; a.nat_row = (s->nat && n > 0) ? tab_d + 2 * n : nullptr;
+        // fillers between the channels: window 0, NAT row 0 (the first channel with frames staged at least `context` rows)
+        if (n > n_enh) HIPCHK(hipMemsetAsync(tab_d, 0, (size_t)3 * n * sizeof(int), h->stream));
+        hipLaunchKernelGGL(bp_stream_analysis, dim3((unsigned)s->ana.size()), dim3(WAVE_THREADS), lds_bytes(hop), h->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (!s->natj.empty()) {
+        const int kb = (D + WAVE_THREADS - 1) / WAVE_THREADS;
+        hipLaunchKernelGGL(bp_stream_nat, dim3((unsigned)(kb * s->natj.size())), dim3(WAVE_THREADS), 0, h->stream, (const NatJob *)(din + o_nat),
+                           (const float *)rows_d, (const float *)(s->dev + s->o_rows), D, (float *)(s->dev + s->o_nat), nat_d);
+        HIPCHK(hipGetLastError());
+    }
+    if (n > 0) {
+        int r;
+        if ((r = window_adopt(h, (int)n, D, ctx, s->nat, false)) != BP_OK) return r;
+        if ((r = forward_resident(h, (int)n)) != BP_OK) return r;
+        StreamSynArgs a; memset(&a, 0, sizeof(a));
+        a.jobs = (const SynJob *)(din + o_syn); a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = s->out_col;
+        a.Y = Y; a.win = win; a.tw = tw; a.log2M = s->log2M; a.D = D; a.target = s->target;
+        a.half = (float *)(s->dev + s->o_half); a.pcm = (float *)(s->dev + s->o_out);
+        const size_t lds = (syn_frames_at(hop) + (size_t)4 * hop) * sizeof(float);
+        hipLaunchKernelGGL(bp_stream_synthesis, dim3((unsigned)n_enh), dim3(WAVE_THREADS), lds, h->stream, a);
+        HIPCHK(hipGetLastError());
+        if (due > 0) HIPCHK(hipMemcpyAsync(s->pin_out, s->dev + s->o_out, (size_t)due * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (due > 0) memcpy(out_pcm, s->pin_out, (size_t)due * 4);
+    return BP_OK;
+}

@@ -1,4 +1,4 @@
-// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 6: the signal layer around the network.  Noisy PCM
+// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 7: the signal layer around the network.  Noisy PCM
 // in, enhanced PCM out (bp_enhance_waves), and the same analysis alone for feature extraction (bp_wave_lps).  gfx950 only.
 //
 // One signal definition, derived from fea_dim: n_fft = 2 (fea_dim - 1), a power of two in 64 .. 2048;
@@ -76,40 +76,9 @@ struct WaveSynArgs {
 __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_synthesis(const WaveSynArgs a)
 {
     extern __shared__ float2 z[];
-    const int g = blockIdx.x, M = 1 << a.log2M, N = 2 * M, tid = threadIdx.x;
-    float2 *S = z + lds_bytes(M) / sizeof(float2);      // S[0 .. M], unpadded (read twice below, written once)
-    const float *o = a.out + (size_t)g * a.ldo + a.out_col;
-    const float2 *Y = a.Y + (size_t)g * a.D;
-    for (int k = tid; k <= M; k += blockDim.x) {
-        const float2 y = Y[k];
-        const float ok = o[k];
-        float2 v;
-        if (a.target == BP_WAVE_MASK) v = make_float2(ok * y.x, ok * y.y);
-        else {
-            const float r = sqrtf(y.x * y.x + y.y * y.y), m = expf(0.5f * ok);
-            v = r > 0.0f ? make_float2(m * (y.x / r), m * (y.y / r)) : make_float2(m, 0.0f);
-        }
-        if (k == 0 || k == M) v.y = 0.0f;               // (irfft ignores the imaginary part of DC and Nyquist)
-        S[k] = v;
-    }
-    __syncthreads();
-    // inverse split step: Z[k] = E[k] + i O[k], E = (S[k] + conj S[M-k]) / 2, O = (S[k] - conj S[M-k]) conj(W^k) / 2
-    for (int k = tid; k < M; k += blockDim.x) {
-        const float2 sk = S[k], sm = S[M - k];
-        const float2 e = make_float2(0.5f * (sk.x + sm.x), 0.5f * (sk.y - sm.y));
-        const float2 d = make_float2(0.5f * (sk.x - sm.x), 0.5f * (sk.y + sm.y));
-        const float2 od = cmulc(d, a.tw[k]);
-        z[lp((int)(__brev((unsigned)k) >> (32 - a.log2M)))] = make_float2(e.x - od.y, e.y + od.x);
-    }
-    __syncthreads();
-    fft_lds(z, M, a.tw, true);
-    const float sc = 1.0f / (float)M;
-    float *fr = a.frames + (size_t)g * N;
-    for (int q = tid; q < N / 4; q += blockDim.x) {
-        const float2 z0 = z[lp(2 * q)], z1 = z[lp(2 * q + 1)];
-        const float4 w = *reinterpret_cast<const float4 *>(a.win + 4 * q);
-        *reinterpret_cast<float4 *>(fr + 4 * q) = make_float4(z0.x * sc * w.x, z0.y * sc * w.y, z1.x * sc * w.z, z1.y * sc * w.w);
-    }
+    const int g = blockIdx.x;
+    synth_frame(z, a.out + (size_t)g * a.ldo + a.out_col, a.Y + (size_t)g * a.D, a.win, a.tw, a.log2M, a.target,
+                a.frames + ((size_t)g << (a.log2M + 1)));
 }
 
 // Segment t >= 1 of a sentence (padded samples [t hop, (t+1) hop)) is covered by frame t (offset k) and frame t-1 (offset
@@ -125,8 +94,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_overlap(const float *__r
     for (int q = threadIdx.x; q < hop / 4; q += blockDim.x) {
         const float4 a = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(prev + 4 * q);
         const float4 wa = *reinterpret_cast<const float4 *>(win + 4 * q), wb = *reinterpret_cast<const float4 *>(win + hop + 4 * q);
-        *reinterpret_cast<float4 *>(dst + 4 * q) = make_float4((a.x + b.x) / (wa.x * wa.x + wb.x * wb.x), (a.y + b.y) / (wa.y * wa.y + wb.y * wb.y),
-                                                               (a.z + b.z) / (wa.z * wa.z + wb.z * wb.z), (a.w + b.w) / (wa.w * wa.w + wb.w * wb.w));
+        *reinterpret_cast<float4 *>(dst + 4 * q) = overlap4(a, b, wa, wb);
     }
 }
 

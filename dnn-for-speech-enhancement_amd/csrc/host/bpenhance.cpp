@@ -6,14 +6,19 @@
 //             [wave_target=lps|mask] [out_col=0] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2] [bunchsize=1024]
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
+//             [stream_block=<samples> [stream_chan=<n>]]
 //
 // As many sentences go into one call as fit traincache rows (frames + context-1 replicated edge rows per sentence).  The
 // output is PCM16 at the input's sample rate, rounded to nearest and clipped.  Every input is read and checked before the
-// device is used.  Errors: message + exit(0), success: return 1 (reference convention).
+// device is used.  With stream_block the files go through a streaming session instead (bp_stream_push): they
+// are dealt to stream_chan channels (file s to channel s mod stream_chan) and pushed stream_block samples at a time, the last
+// block of a file with its end flag -- the way a live feed would arrive; the output files hold the bytes of a run without
+// stream_block that enhances one sentence per call.  Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -34,6 +39,7 @@ int main(int argc, char **argv)
     std::string norm_file, wts_file, list, in_wav, out_wav;
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
+    int stream_block = 0, stream_chan = 1;
     float vis = 0.f, hid = 0.f;
     for (int i = 1; i < argc; ++i) {
         char *eq = strchr(argv[i], '=');
@@ -48,6 +54,12 @@ int main(int argc, char **argv)
         else if (k == "activation") activation = v == "sigmoid" ? 1 : 0; else if (k == "device") device = atoi(v.c_str());
         else if (k == "compute") compute = v == "bf16" ? 1 : 0;
         else if (k == "out_col") out_col = atoi(v.c_str());
+        else if (k == "stream_block" || k == "stream_chan") {
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 1 || n > (1 << 24)) { printf("%s: %s is not a count >= 1\n", k.c_str(), v.c_str()); exit(0); }
+            (k == "stream_block" ? stream_block : stream_chan) = (int)n;
+        }
         else if (k == "wave_target") {
             if (v == "lps") target = BP_WAVE_LPS; else if (v == "mask") target = BP_WAVE_MASK;
             else { printf("wave_target: %s is not lps or mask\n", v.c_str()); exit(0); }
@@ -85,6 +97,8 @@ int main(int argc, char **argv)
     const int n_fft = 2 * (fea_dim - 1), hop = n_fft / 2;
     if (fea_dim < 33 || fea_dim > 1025 || (n_fft & (n_fft - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
     if (ls[0] != ctx * fea_dim && ls[0] != (ctx + 1) * fea_dim) { printf("bpenhance: layersizes[0] must be fea_context*fea_dim (+ fea_dim with a NAT block)\n"); exit(0); }
+    if (stream_chan > 1 && stream_block < 1) { printf("bpenhance: stream_chan needs stream_block\n"); exit(0); }
+    if (stream_block > 0 && (long)stream_block * stream_chan > (1L << 28)) { printf("bpenhance: stream_block * stream_chan is too large\n"); exit(0); }
     if (out_col < 0 || out_col + fea_dim > ls[L - 1]) { printf("bpenhance: out_col + fea_dim exceeds layersizes[last]\n"); exit(0); }
 
     // ---- inputs (all read and checked before the device is used)
@@ -111,7 +125,7 @@ int main(int argc, char **argv)
         if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
         if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
         const size_t rows = (waves[s].size() - 1) / hop + 2 + ctx - 1;
-        if (rows > (size_t)cache) { printf("%s: %zu rows exceed traincache=%d (one sentence per call at most)\n", ins[s].c_str(), rows, cache); exit(0); }
+        if (stream_block < 1 && rows > (size_t)cache) { printf("%s: %zu rows exceed traincache=%d (one sentence per call at most)\n", ins[s].c_str(), rows, cache); exit(0); }
     }
     std::vector<float> mean(fea_dim), istd(fea_dim);
     {
@@ -145,11 +159,57 @@ int main(int argc, char **argv)
     if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
     if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
 
-    // ---- as many sentences per call as fit the chunk
     std::vector<float> pcm, out;
     std::vector<int> lens;
     size_t samples = 0;
-    for (int s0 = 0; s0 < ns;) {
+    if (stream_block > 0) {
+        // ---- a streaming session: channel c plays files c, c + stream_chan, ... one after the other
+        bp_stream_config sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.fea_dim = fea_dim; sc.context = ctx; sc.targ_offset = toff; sc.mean = mean.data(); sc.inv_std = istd.data();
+        sc.target = target; sc.out_col = out_col; sc.n_chan = stream_chan; sc.max_push_samples = stream_block * stream_chan;
+        bp_stream *st = nullptr;
+        if (bp_stream_open(h, &sc, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        std::vector<int> file(stream_chan), n_in(stream_chan), n_out(stream_chan);
+        std::vector<size_t> pos(stream_chan, 0);
+        std::vector<unsigned char> end(stream_chan);
+        std::vector<std::vector<float>> enh(ns);
+        // a push returns what arrived plus, at the end of a sentence, the frames that waited for their look-ahead or the NAT row
+        out.resize((size_t)stream_chan * ((size_t)stream_block + (size_t)(ctx + 8) * hop));
+        for (int c = 0; c < stream_chan; ++c) file[c] = c;
+        for (;;) {
+            pcm.clear();
+            bool any = false;
+            for (int c = 0; c < stream_chan; ++c) {
+                n_in[c] = 0; end[c] = 0;
+                if (file[c] >= ns) continue;
+                const std::vector<float> &w = waves[file[c]];
+                n_in[c] = (int)std::min((size_t)stream_block, w.size() - pos[c]);
+                end[c] = pos[c] + n_in[c] == w.size();
+                pcm.insert(pcm.end(), w.begin() + pos[c], w.begin() + pos[c] + n_in[c]);
+                any = true;
+            }
+            if (!any) break;
+            if (bp_stream_push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+            size_t off = 0;
+            for (int c = 0; c < stream_chan; ++c) {
+                if (file[c] >= ns) continue;
+                enh[file[c]].insert(enh[file[c]].end(), out.begin() + off, out.begin() + off + n_out[c]);
+                off += n_out[c];
+                pos[c] += n_in[c];
+                if (end[c]) { file[c] += stream_chan; pos[c] = 0; }
+            }
+            samples += pcm.size();
+        }
+        bp_stream_close(st);
+        for (int s = 0; s < ns; ++s) {
+            if (enh[s].size() != waves[s].size()) { printf("%s: the stream returned %zu of %zu samples\n", ins[s].c_str(), enh[s].size(), waves[s].size()); exit(0); }
+            const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
+            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+        }
+    }
+    // ---- as many sentences per call as fit the chunk
+    for (int s0 = stream_block > 0 ? ns : 0; s0 < ns;) {
         int s1 = s0;
         size_t rows = 0;
         pcm.clear(); lens.clear();

@@ -297,6 +297,49 @@ int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, i
                 float *enh_scores, float *enh_pcm);
 
 /* ------------------------------------------------------------------------------------
+ * Streaming sessions: audio that is still arriving, enhanced in blocks (no reference counterpart).  INTEGRATION.md 1g.  The signal
+ * definition of bp_enhance_waves applies unchanged, and a sentence pushed in blocks of ANY sizes returns the same bits as one
+ * bp_enhance_waves call on the finished sentence on the same handle.
+ *
+ * A stream has n_chan independent channels (feeds); one bp_stream_push advances all of them.  n_in[ch] >= 0 new samples per channel,
+ * back to back in channel order in pcm; end[ch] != 0 (end may be NULL) closes the channel's current sentence after these samples;
+ * n_out[ch] and out_pcm return the samples that became final, back to back in channel order.  After end the channel has returned
+ * exactly as many samples as it received and starts a new sentence with the next push; end on a channel that has received nothing
+ * is a no-op.
+ *
+ * bp_stream_counts (host only): what a channel has produced after `received` samples of its sentence.  hop = fea_dim - 1,
+ * la = context - 1 - targ_offset (the look-ahead), T = (received - 1)/hop + 2 (0 when nothing was received):
+ *   frames_in  = ended ? T : received / hop           (frame t needs the real samples [(t-1) hop, (t+1) hop))
+ *   the noise-aware row is known once frames_in >= 6, or at the end (nets without the block: always)
+ *   frames_out = 0 until then, after that ended ? T : max(0, frames_in - la)
+ *   samples_out = ended ? received : max(0, frames_out - 1) hop
+ * A push returns samples_out(after) - samples_out(before) per channel; the latency of a live feed is (la + 1) hop samples plus
+ * the block, and 6 hop at the start of a sentence of a noise-aware net.
+ *
+ * Every argument is checked before the device or the stream's state is touched; after an error the stream continues as if the
+ * call had not happened.  BP_ERR_ARG: the checks of bp_enhance_waves, n_chan < 1, max_push_samples < 1, sum(n_in) >
+ * max_push_samples, out_cap smaller than the samples due, or the rows of the push (frames to enhance + context-1 per active
+ * channel) exceeding max_chunk_frames.  BP_ERR_STATE on a data-parallel-attached handle.  A handle may hold several streams;
+ * bp_destroy releases those still open.  fp32 and bf16 handles, every output option of bp_set_output.  A push leaves its rows as the
+ * handle's resident window chunk; training, bp_enhance_waves, bp_forward_windows and bp_eval_mix calls between pushes disturb
+ * neither the stream nor themselves.  Per push: one host->device copy, one device->host copy, one synchronisation; everything is
+ * allocated at bp_stream_open.  No float atomics: the same bits on every run. */
+typedef struct bp_stream bp_stream;
+typedef struct bp_stream_config {
+    int fea_dim, context, targ_offset;      /* as bp_wave_chunk; NAT iff layersizes[0] == (context+1)*fea_dim */
+    const float *mean, *inv_std;            /* [fea_dim], copied at open */
+    int target, out_col;                    /* BP_WAVE_LPS | BP_WAVE_MASK; first output column used */
+    int n_chan;                             /* independent channels (feeds) advanced by one push, >= 1 */
+    int max_push_samples;                   /* upper bound of sum(n_in) of one push, >= 1 */
+} bp_stream_config;
+int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream **out);
+int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, const unsigned char *end, int *n_out, float *out_pcm,
+                   size_t out_cap);
+int bp_stream_close(bp_stream *s);
+int bp_stream_counts(int fea_dim, int context, int targ_offset, int nat, int64_t received, int ended, int64_t *frames_in,
+                     int64_t *frames_out, int64_t *samples_out);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias
