@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "bp_device.h"
+#include "bp_kernels.h"      // xcd_tile
 
 typedef uint16_t bf16_t;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -106,20 +107,13 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
     constexpr int DMA_STAGE = 192 * 128, DMA_ST = 4;                                            // bytes per stage, ring length
     __shared__ __attribute__((aligned(1024))) bf16_t smem[DMA ? DMA_ST * DMA_STAGE / 2 : 2 * STAGE_H];
     const int tid = threadIdx.x, lane = tid & 63, wave = DMA ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, wm = (BM >= 64) ? wave >> 1 : 0, wn = wave & 1;
-    // XCD-aware tile map (block b runs on XCD b % 8): the workgroups that share a B panel (same tile_n, all tile_m)
-    // sit on one XCD, so the panel is fetched into that XCD's L2 once instead of eight times
     int tile_m, tile_n;
     int tile_lin = blockIdx.x, kz = 0;
     if constexpr (KS > 1) {                                   // groups of 8 tiles x KS slices: slice z of tile 8g+j is block (8*KS)g + 8z + j (the launch has tiles % 8 == 0)
         const int grp = blockIdx.x / (8 * KS), r = blockIdx.x % (8 * KS);
         kz = r >> 3; tile_lin = grp * 8 + (r & 7);
     }
-    if ((g.tiles_n & 7) == 0) {
-        const int b = tile_lin, xcd = b & 7, jj = b >> 3, per = g.tiles_n >> 3;
-        tile_n = xcd * per + jj / g.tiles_m; tile_m = jj % g.tiles_m;
-    } else {
-        tile_m = tile_lin % g.tiles_m; tile_n = tile_lin / g.tiles_m;
-    }
+    xcd_tile<false>(tile_lin, g.tiles_m, g.tiles_n, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BF_BN;
     // chunk c of a tile: row c>>3 (rows [0, BM) from A, then BF_BN rows from B), 8 halfs at column (c&7)*8
     const bf16_t *src[NCHK]; int dst[NCHK];

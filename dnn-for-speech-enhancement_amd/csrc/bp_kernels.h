@@ -484,6 +484,31 @@ struct GemmCfg {
     }
 };
 
+// ------------------------------------------------------------------ launch geometry shared by every GEMM family
+// XCD-aware tile map: workgroup b of a problem runs on XCD b % 8 (a grouped launch keeps that true for the problem-relative index,
+// pack_tiles in bp_step.hip).  With a multiple of 8 n-tiles each XCD gets a contiguous range of `per` n-panels, so the W / dEdX
+// column panels it streams stay in its private L2 and are fetched into it once instead of eight times; forward and dgrad walk m
+// fastest inside it (the workgroups that share an n-panel run back to back).  M_SLOW is the weight gradient's order: its few
+// n-panels (dEdX columns) stay hot anyway, so it walks the m-panels (activation columns) slowly and the `per` workgroups that share
+// one run back to back -- the panel is fetched into this L2 once instead of being evicted by the W / delta stream before its next use.
+template <bool M_SLOW>
+__device__ __forceinline__ void xcd_tile(int b, int tiles_m, int tiles_n, int &tile_m, int &tile_n)
+{
+    if ((tiles_n & 7) == 0) {
+        const int xcd = b & 7, j = b >> 3, per = tiles_n >> 3;
+        if constexpr (M_SLOW) { tile_n = xcd * per + j % per; tile_m = j / per; }
+        else { tile_n = xcd * per + j / tiles_m; tile_m = j % tiles_m; }
+    } else { tile_m = b % tiles_m; tile_n = b / tiles_m; }       // any other n-tile count: plain column-major order
+}
+// The problem of a grouped launch (MultiArgs, BfWgradMulti) that owns entry b of the concatenated tile list: problem p has the
+// entries first_tile[p] .. first_tile[p + 1] - 1.  A walk over growing entries continues from the p it found last.
+template <class Multi>
+__device__ __forceinline__ int problem_of(const Multi &a, int b, int p)
+{
+    while (p + 1 < a.n && b >= a.first_tile[p + 1]) ++p;
+    return p;
+}
+
 // The workgroup program of one GEMM problem: workgroups first_block, first_block+stride, ... of
 // the launch walk its tiles.  Wrapped by bp_gemm (one problem per launch), bp_gemm_multi (up to
 // four independent problems in one launch) and bp_out_split_stage.
@@ -515,8 +540,6 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         g.B += B_KC ? kz : kz * g.ldb;
     }
 
-    // ---- XCD-aware tile mapping: block b runs on XCD b%8; give each XCD a contiguous range of
-    // n-tiles so the W / dEdX column panels it streams stay in its private L2.
     // Persistent over tiles (grid may be smaller than the tile count): the epilogue's stores of
     // one tile are still draining while the next tile's k-loop runs.
 #ifdef BP_TRACE
@@ -530,24 +553,7 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     TRACE(0);
     for (int b = first_block; b < g.tiles_m * g.tiles_n; b += stride) {
     int tile_m, tile_n;
-    {
-        if ((g.tiles_n & 7) == 0) {
-            const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3;
-            if constexpr (BIASG) {
-                // wgrad: the XCD's few n-panels (dEdX columns) stay hot anyway; walk the m-panels (activation
-                // columns) slowly so the `per` workgroups that share one run back to back and the panel is fetched
-                // into this L2 once, instead of being evicted by the W/delta stream before its next use
-                tile_n = xcd * per + j % per;
-                tile_m = j / per;
-            } else {
-                tile_n = xcd * per + j / g.tiles_m;
-                tile_m = j % g.tiles_m;
-            }
-        } else {
-            tile_m = b % g.tiles_m;
-            tile_n = b / g.tiles_m;
-        }
-    }
+    xcd_tile<BIASG>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);   // bias-gradient partial sums (wgrad; used by m-tile 0)
@@ -752,13 +758,14 @@ struct MultiArgs {
     int first_tile[5];       // first_tile[p] .. first_tile[p+1]-1 = workgroups of problem p
     int n;
 };
+#ifndef BP_TRACE            // (the development build's GemmArgs carries one more pointer)
+static_assert(sizeof(MultiArgs) == 920 && offsetof(MultiArgs, first_tile) == 896 && offsetof(MultiArgs, n) == 916, "MultiArgs layout");
+#endif
 template <class K>
 __global__ __launch_bounds__(256, K::MIN_WG) void bp_gemm_multi(const MultiArgs a)
 {
     __shared__ __attribute__((aligned(16))) float smem[K::SMEM];
-    const int b = blockIdx.x;
-    int p = 0;
-    while (p + 1 < a.n && b >= a.first_tile[p + 1]) ++p;
+    const int b = blockIdx.x, p = problem_of(a, b, 0);
     K::run(a.g[p], a.e[p], b - a.first_tile[p], a.first_tile[p + 1] - a.first_tile[p], 0, smem);
 }
 

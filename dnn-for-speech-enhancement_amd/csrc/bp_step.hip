@@ -1,6 +1,6 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), part 1 of 5: the device state of one BP_GPU replacement
-// object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.  The handle and
-// what the other four translation units use of this one: bp_handle.h.
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of seven translation units: the device state of one
+// BP_GPU replacement object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.
+// The handle and what the other six units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -295,6 +295,15 @@ static hipError_t launch(hipStream_t st, GemmArgs g, const EpiArgs &e, int M, in
     return hipGetLastError();
 }
 
+// The forward's tile pick: 32x32 tiles up to 512 columns, else 32x64 (the input layer's, l1, as TAG 1: own name in profiles).
+template <int EPI>
+static hipError_t launch_fwd_tiles(hipStream_t st, const GemmArgs &g, const EpiArgs &e, int M, int cur, bool l1 = false)
+{
+    if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI>(st, g, e, M, cur);
+    if constexpr (EPI == EPI_FWD_HIDDEN) { if (l1) return launch<32, 64, 64, 1, 2, true, false, EPI, 1>(st, g, e, M, cur); }
+    return launch<32, 64, 64, 1, 2, true, false, EPI>(st, g, e, M, cur);
+}
+
 static EpiArgs epi_zero()
 {
     EpiArgs e;
@@ -318,9 +327,7 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
         e.seed_lo = (uint32_t)h->cfg.seed; e.seed_hi = (uint32_t)(h->cfg.seed >> 32);
         e.step = h->step; e.layer = (uint32_t)l; e.frame_off = h->cfg.rank_frame_offset;
         if (train && h->inj_mask[l]) { e.mask = h->inj_mask[l]; e.ldmask = h->s[l]; e.drop_thresh = 1u; }   // injected mask (tests)
-        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_HIDDEN>(h->stream, g, e, M, cur);
-        if (l == 1) return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN, 1>(h->stream, g, e, M, cur);   // (TAG 1: own name in profiles)
-        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN>(h->stream, g, e, M, cur);
+        return launch_fwd_tiles<EPI_FWD_HIDDEN>(h->stream, g, e, M, cur, l == 1);
     }
     e.scale = 2.0f / (float)h->Bg;                       // kernSubClean: 2.0f/rows (global rows under DP)
     const bool logi = h->out_act == 1;                   // bp_set_output: the EPI_*_LOGI siblings
@@ -350,12 +357,7 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
     }
     e.C = train ? h->dx[l] : nullptr; e.ldc = cur;
     e.aux = targ; e.ldaux = cur; e.aux2 = out; e.ldaux2 = cur;
-    if (logi) {
-        if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT_LOGI>(h->stream, g, e, M, cur);
-        return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT_LOGI>(h->stream, g, e, M, cur);
-    }
-    if (cur <= 512) return launch<32, 32, 64, 1, 1, true, false, EPI_FWD_OUT>(h->stream, g, e, M, cur);
-    return launch<32, 64, 64, 1, 2, true, false, EPI_FWD_OUT>(h->stream, g, e, M, cur);
+    return logi ? launch_fwd_tiles<EPI_FWD_OUT_LOGI>(h->stream, g, e, M, cur) : launch_fwd_tiles<EPI_FWD_OUT>(h->stream, g, e, M, cur);
 }
 
 // A prepared backward GEMM: arguments + which tile configuration it uses.
@@ -389,81 +391,97 @@ static Prepared prep_dgrad(bp_handle *h, int l, int M)
     return p;
 }
 
-// G_l = y_{l-1}^T . dEdX_l, gb_l = colsum(dEdX_l); fused momentum update (single device) or
-// store into the flat gradient buffer (data parallel).   (BP_GPU.cu:642-652)
+// The epilogue of layer l's weight gradient (fp32, and the fp32 side of the bf16 LDS-DMA launch): fused momentum update
+// (single device) or store into layer l's segment of the flat gradient buffer (data parallel).   (BP_GPU.cu:643-652)
+static EpiArgs wgrad_epi(const bp_handle *h, int l, bool fused)
+{
+    const int prev = h->ld[l - 1], cur = h->ld[l];
+    EpiArgs e = epi_zero();
+    e.ldc = cur; e.m_limit = prev; e.n_limit = cur; e.n_true = h->s[l];
+    if (fused) {
+        const UpdateCoef u = update_coef(h);
+        e.C = h->W[l]; e.aux2 = h->dW[l]; e.ldaux2 = cur;
+        e.mom = u.mom; e.c1 = u.c1; e.wc = u.wc; e.ndiv = u.ndiv;
+        e.bias_w = h->b[l]; e.bias_d = h->db[l];
+    } else {
+        e.C = h->grad + h->g_off[l];
+        e.bias_g = h->grad + h->g_off[l] + (size_t)prev * cur;
+    }
+    return e;
+}
+// G_l = y_{l-1}^T . dEdX_l, gb_l = colsum(dEdX_l)   (BP_GPU.cu:642)
 static Prepared prep_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused)
 {
     const int prev = h->ld[l - 1], cur = h->ld[l];
     Prepared p; memset(&p, 0, sizeof(p));
     p.g.A = y_prev; p.g.lda = prev; p.g.B = h->dx[l]; p.g.ldb = cur; p.g.K = M;
-    p.e = epi_zero();
-    p.e.ldc = cur; p.e.m_limit = prev; p.e.n_limit = cur; p.e.n_true = h->s[l];
-    if (fused) {
-        const UpdateCoef u = update_coef(h);
-        p.e.C = h->W[l]; p.e.aux2 = h->dW[l]; p.e.ldaux2 = cur;
-        p.e.mom = u.mom; p.e.c1 = u.c1; p.e.wc = u.wc; p.e.ndiv = u.ndiv;
-        p.e.bias_w = h->b[l]; p.e.bias_d = h->db[l];
-    } else {
-        p.e.C = h->grad + h->g_off[l];
-        p.e.bias_g = h->grad + h->g_off[l] + (size_t)prev * cur;
-    }
+    p.e = wgrad_epi(h, l, fused);
     p.M = prev; p.N = cur; p.cfg = CFG_WGRAD; p.fused = fused;
     return p;
 }
 
-// n (1..4) independent problems of one tile configuration in one launch (bp_gemm_multi).
-template <class K, int BMT, int BNT>
-static hipError_t run_multi(hipStream_t st, Prepared *ps, int n)
+// The tile list of a grouped launch (MultiArgs, BfWgradMulti) from the tile counts of its n problems: fills first_tile[0..n] and
+// n, returns the number of entries.  Every problem starts on a multiple of 8 entries: its problem-relative index then has the
+// same low 3 bits as the hardware's block index (= the XCD), which xcd_tile (bp_kernels.h) relies on; the up-to-7 padding
+// entries behind a problem find no tile and are skipped.  (A persistent grid keeps that true by being a multiple of 8 itself.)
+template <class Multi>
+static int pack_tiles(Multi &a, const int *tiles, int n)
+{
+    int t = 0;
+    for (int i = 0; i < n; ++i) { a.first_tile[i] = t; t += (tiles[i] + 7) & ~7; }
+    a.first_tile[n] = t; a.n = n;
+    return t;
+}
+// n (1..4) independent problems of BMT x BNT tiles in one launch of KERNEL: bp_gemm_multi<K>, one workgroup per entry, or
+// bp_wgrad_dma, at most `slots` (a multiple of 8) workgroups of which workgroup w walks the entries w, w + grid, ...
+template <void (*KERNEL)(const MultiArgs), int BMT, int BNT>
+static hipError_t run_multi(hipStream_t st, Prepared *ps, int n, int slots = 1 << 30)
 {
     MultiArgs a; memset(&a, 0, sizeof(a));
-    int t = 0;
+    int tiles[4];
     for (int i = 0; i < n; ++i) {
         ps[i].g.tiles_m = (ps[i].M + BMT - 1) / BMT; ps[i].g.tiles_n = (ps[i].N + BNT - 1) / BNT;
-        a.g[i] = ps[i].g; a.e[i] = ps[i].e; a.first_tile[i] = t;
-        // every problem starts on a multiple of 8 workgroups: its problem-relative block index then has the same
-        // low 3 bits as the hardware's blockIdx (= the XCD), which the XCD-aware tile map inside run() relies on
-        // (the up-to-7 padding workgroups find no tile and exit)
-        t += (ps[i].g.tiles_m * ps[i].g.tiles_n + 7) & ~7;
+        a.g[i] = ps[i].g; a.e[i] = ps[i].e; tiles[i] = ps[i].g.tiles_m * ps[i].g.tiles_n;
     }
-    a.first_tile[n] = t; a.n = n;
-    hipLaunchKernelGGL((bp_gemm_multi<K>), dim3(t), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// The same for a plain __global__ kernel taking MultiArgs with 64x64 tiles (bp_wgrad_dma.h): at most `slots` (a multiple of 8)
-// workgroups, workgroup w walks the entries w, w + grid, ... of the tile list.
-template <void (*KERNEL)(const MultiArgs)>
-static hipError_t run_multi_k(hipStream_t st, Prepared *ps, int n, int slots)
-{
-    MultiArgs a; memset(&a, 0, sizeof(a));
-    int t = 0;
-    for (int i = 0; i < n; ++i) {
-        ps[i].g.tiles_m = (ps[i].M + 63) / 64; ps[i].g.tiles_n = (ps[i].N + 63) / 64;
-        a.g[i] = ps[i].g; a.e[i] = ps[i].e; a.first_tile[i] = t;
-        t += (ps[i].g.tiles_m * ps[i].g.tiles_n + 7) & ~7;      // (problem-relative block index keeps the XCD bits, see run_multi)
-    }
-    a.first_tile[n] = t; a.n = n;
+    const int t = pack_tiles(a, tiles, n);
     hipLaunchKernelGGL(KERNEL, dim3(t < slots ? t : slots), dim3(256), 0, st, a);
     return hipGetLastError();
 }
+
+// THE STATIC BUNCH SIZES for which an unrolled LDS-DMA weight-gradient kernel is built: fp32 (BF = false, bp_wgrad_dma.h, k = the
+// bunch) 128 / 256 / 512 -- the shipped .pl uses 128, BASELINE.json 256 and 512 --, bf16 (BF = true, bp_wgrad_dma_bf16.h, k = the
+// padded bunch) those and 1024.  f gets k as a std::integral_constant; false: no such kernel, f was not called (no_kernel: a query).
+// The fp32 STORE kernel of this table, bp_wgrad_dma<16, 4, 4, K, true>, is the one kernel that counts its tiles into EpiArgs::done:
+// step_wgrads_count below is a query of this table.  Its other clause, L - 1 <= 4: the in-kernel hand-off is ONE grouped launch
+// (MultiArgs holds 4 problems) that the exchange kernels of all layers wait beside; a deeper net keeps the event per launch.
+template <bool BF, class F>
+static bool static_bunch(int k, F &&f)
+{
+    switch (k) {
+    case 128: f(std::integral_constant<int, 128>()); return true;
+    case 256: f(std::integral_constant<int, 256>()); return true;
+    case 512: f(std::integral_constant<int, 512>()); return true;
+    case 1024: if constexpr (BF) { f(std::integral_constant<int, 1024>()); return true; }
+    }
+    return false;
+}
+static const auto no_kernel = [](auto) {};
 
 // The wgrad problems ps[0..n) (all fused or all store): grouped launches of up to 4 problems.
 static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n, int slots)
 {
     for (int i = 0; i < n;) {
         const int m = n - i < 4 ? n - i : 4;
-        // bunches of 128 / 256 / 512 frames (the shipped .pl uses 128, BASELINE.json 256 and 512): LDS-DMA kernel, unrolled
+        const bool fused = ps[i].fused;
         int kk = ps[i].g.K;
         for (int j = 0; j < m; ++j) if (ps[i + j].g.K != kk) kk = 0;
-        hipError_t er;
-        if (kk == 256 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256>>(st, ps + i, m, slots);
-        else if (kk == 128 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128>>(st, ps + i, m, slots);
-        else if (kk == 512 && ps[i].fused) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512>>(st, ps + i, m, slots);
-        else if (kk == 256) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 256, true>>(st, ps + i, m, slots);       // data-parallel gradient store
-        else if (kk == 128) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 128, true>>(st, ps + i, m, slots);
-        else if (kk == 512) er = run_multi_k<bp_wgrad_dma<16, 4, 4, 512, true>>(st, ps + i, m, slots);
-        else if (ps[i].fused) er = run_multi<KWgrad<EPI_WGRAD_UPDATE>, 64, 64>(st, ps + i, m);
-        else er = run_multi<KWgradStore, 128, 64>(st, ps + i, m);
+        hipError_t er = hipSuccess;
+        const bool dma = static_bunch<false>(kk, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            er = fused ? run_multi<bp_wgrad_dma<16, 4, 4, K>, 64, 64>(st, ps + i, m, slots)
+                       : run_multi<bp_wgrad_dma<16, 4, 4, K, true>, 64, 64>(st, ps + i, m, slots);       // data-parallel gradient store
+        });
+        if (!dma) er = fused ? run_multi<bp_gemm_multi<KWgrad<EPI_WGRAD_UPDATE>>, 64, 64>(st, ps + i, m) : run_multi<bp_gemm_multi<KWgradStore>, 128, 64>(st, ps + i, m);
         if (er != hipSuccess) return er;
         i += m;
     }
@@ -473,8 +491,11 @@ static hipError_t run_wgrads(hipStream_t st, Prepared *ps, int n, int slots)
 hipError_t launch_dgrad(bp_handle *h, int l, int M)
 {
     Prepared p = prep_dgrad(h, l, M);
-    if (p.cfg == CFG_DGRAD_WIDE128) return run_multi<KDgradWide128, 32, 64>(h->stream, &p, 1);
-    return p.cfg == CFG_DGRAD_WIDE ? run_multi<KDgradWide, 32, 64>(h->stream, &p, 1) : run_multi<KDgradNarrow, 32, 32>(h->stream, &p, 1);
+    switch (p.cfg) {
+    case CFG_DGRAD_WIDE128: return run_multi<bp_gemm_multi<KDgradWide128>, 32, 64>(h->stream, &p, 1);
+    case CFG_DGRAD_WIDE: return run_multi<bp_gemm_multi<KDgradWide>, 32, 64>(h->stream, &p, 1);
+    default: return run_multi<bp_gemm_multi<KDgradNarrow>, 32, 32>(h->stream, &p, 1);
+    }
 }
 hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fused)
 {
@@ -623,47 +644,30 @@ static hipError_t bf_wgrad(bp_handle *h, int l, bool fused)
 }
 // The LDS-DMA wgrad of bp_wgrad_dma_bf16.h: static bunch sizes, layers ls[0..n) in one grouped launch (bias gradient
 // fused); other bunch sizes keep bf_wgrad (GEMM kernel + bias kernel per layer).
-static bool bf_dma_ok(const bp_handle *h) { return h->Bp == 128 || h->Bp == 256 || h->Bp == 512 || h->Bp == 1024; }
+static bool bf_dma_ok(const bp_handle *h) { return static_bunch<true>(h->Bp, no_kernel); }
 static hipError_t bf_wgrads_dma(bp_handle *h, const int *ls, int n, bool fused)
 {
-    const UpdateCoef u = update_coef(h);
     for (int i0 = 0; i0 < n; i0 += BF_WGRAD_MAXP) {
         BfWgradMulti a; memset(&a, 0, sizeof(a));
         const int cnt = n - i0 < BF_WGRAD_MAXP ? n - i0 : BF_WGRAD_MAXP;
-        int t = 0;
+        int tiles[BF_WGRAD_MAXP];
         for (int i = 0; i < cnt; ++i) {
             const int l = ls[i0 + i], prev = h->ld[l - 1], cur = h->ld[l];
             BfWgradProblem &p = a.p[i];
             p.A = h->ybT[l - 1]; p.B = h->dxbT[l]; p.ldk = h->Bp;
-            p.tiles_m = prev / 64; p.tiles_n = cur / 64;
-            p.e = epi_zero();
-            p.e.ldc = cur; p.e.m_limit = prev; p.e.n_limit = cur; p.e.n_true = h->s[l];
-            if (fused) {
-                p.e.C = h->W[l]; p.e.aux2 = h->dW[l]; p.e.ldaux2 = cur;
-                p.e.mom = u.mom; p.e.c1 = u.c1; p.e.wc = u.wc; p.e.ndiv = u.ndiv;
-                p.e.bias_w = h->b[l]; p.e.bias_d = h->db[l];
-                p.Wb = h->Wb[l]; p.ldwb = cur;
-            } else {
-                p.e.C = h->grad + h->g_off[l];
-                p.e.bias_g = h->grad + h->g_off[l] + (size_t)prev * cur;
-            }
-            a.first_tile[i] = t;
-            t += (p.tiles_m * p.tiles_n + 7) & ~7;             // (problem-relative block index keeps the XCD bits, see run_multi)
+            p.tiles_m = prev / 64; p.tiles_n = cur / 64; tiles[i] = p.tiles_m * p.tiles_n;
+            p.e = wgrad_epi(h, l, fused);
+            if (fused) { p.Wb = h->Wb[l]; p.ldwb = cur; }
         }
-        a.first_tile[cnt] = t; a.n = cnt;
+        const int t = pack_tiles(a, tiles, cnt);
         // fused update: six waves (two of them own W / delta), 64-frame k-tiles in a ring of 3 when the bunch has at least 4;
         // data-parallel gradient store: the four-wave loop alone
-#define BF_DMA_LAUNCH(K)                                                                                             \
-        do { if (fused) hipLaunchKernelGGL((bp_wgrad_dma_bf16_six<K, (K >= 256 ? 64 : 32), (K >= 256 ? 3 : 4)>), dim3(t), dim3(384), 0, h->stream, a); \
-             else hipLaunchKernelGGL((bp_wgrad_dma_bf16_store<K>), dim3(t), dim3(256), 0, h->stream, a); } while (0)
-        switch (h->Bp) {
-        case 128: BF_DMA_LAUNCH(128); break;
-        case 256: BF_DMA_LAUNCH(256); break;
-        case 512: BF_DMA_LAUNCH(512); break;
-        default: BF_DMA_LAUNCH(1024); break;
-        }
-#undef BF_DMA_LAUNCH
-        hipError_t er = hipGetLastError();
+        const bool built = static_bunch<true>(h->Bp, [&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            if (fused) hipLaunchKernelGGL((bp_wgrad_dma_bf16_six<K, (K >= 256 ? 64 : 32), (K >= 256 ? 3 : 4)>), dim3(t), dim3(384), 0, h->stream, a);
+            else hipLaunchKernelGGL((bp_wgrad_dma_bf16_store<K>), dim3(t), dim3(256), 0, h->stream, a);
+        });
+        const hipError_t er = built ? hipGetLastError() : hipErrorInvalidValue;     // (bf_wgrads asks bf_dma_ok first)
         if (er != hipSuccess) return er;
     }
     return hipSuccess;
@@ -708,8 +712,8 @@ hipError_t step_forward(bp_handle *h, int l, int M, const float *x0, const float
     return launch_fwd(h, l, M, l == 1 ? x0 : h->y[l - 1], tg, out, train, alpha);
 }
 hipError_t step_dgrad(bp_handle *h, int l) { return h->bf ? bf_dgrad(h, l) : launch_dgrad(h, l, h->B); }
-// (fp32: the LDS-DMA store kernel of the static bunch sizes is the one that counts its tiles, up to 4 layers per launch)
-bool step_wgrads_count(const bp_handle *h) { return !h->bf && (h->B == 128 || h->B == 256 || h->B == 512) && h->L - 1 <= 4; }
+// (the store launch counts its tiles: run_wgrads takes the fp32 store kernel of the static_bunch table, all layers in one launch)
+bool step_wgrads_count(const bp_handle *h) { return !h->bf && static_bunch<false>(h->B, no_kernel) && h->L - 1 <= 4; }
 unsigned step_wgrad_tiles(const bp_handle *h, int l) { return (unsigned)(((h->ld[l - 1] + 63) / 64) * ((h->ld[l] + 63) / 64)); }
 hipError_t step_wgrads(bp_handle *h, const int *ls, int n, const float *x0, bool fused, unsigned *const *done)
 {

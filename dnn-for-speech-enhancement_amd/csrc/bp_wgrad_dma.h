@@ -74,14 +74,12 @@ struct WgradDma {
     // t.p only grows along a workgroup's walk.
     static __device__ __forceinline__ bool decode(const MultiArgs &a, int i, Pos &t)
     {
-        int p = t.p;
-        while (p + 1 < a.n && i >= a.first_tile[p + 1]) ++p;
+        const int p = problem_of(a, i, t.p);
         const GemmArgs &g = a.g[p];
         const int b = i - a.first_tile[p];                        // (low 3 bits = the workgroup's XCD: G and first_tile are multiples of 8)
         if (b >= g.tiles_m * g.tiles_n) return false;
         int tile_m, tile_n;
-        if ((g.tiles_n & 7) == 0) { const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3; tile_n = xcd * per + j % per; tile_m = j / per; }
-        else { tile_m = b % g.tiles_m; tile_n = b / g.tiles_m; }
+        xcd_tile<true>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
         t.p = p; t.m0 = tile_m * BM; t.n0 = tile_n * BN;
         return true;
     }

@@ -33,6 +33,7 @@ struct BfWgradProblem {
 };
 enum { BF_WGRAD_MAXP = 8 };
 struct BfWgradMulti { BfWgradProblem p[BF_WGRAD_MAXP]; int first_tile[BF_WGRAD_MAXP + 1]; int n; };
+static_assert(sizeof(BfWgradMulti) == 1704 && offsetof(BfWgradMulti, first_tile) == 1664 && offsetof(BfWgradMulti, n) == 1700, "BfWgradMulti layout");
 
 // BKX = 64 (rows of 128 bytes = whole lines per DMA request instead of halves; slot s of row r holds chunk s ^ ((r>>1)&7)), STX = ring length
 template <int KTOT, int BKX = 32, int STX = 4>
@@ -109,8 +110,7 @@ struct WgradDmaBf {
         const EpiArgs &e = g.e;
         for (int b = first_block; b < g.tiles_m * g.tiles_n; b += stride) {
             int tile_m, tile_n;
-            if ((g.tiles_n & 7) == 0) { const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3; tile_n = xcd * per + j % per; tile_m = j / per; }
-            else { tile_m = b % g.tiles_m; tile_n = b / g.tiles_m; }
+            xcd_tile<true>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
             const int m0 = tile_m * BM, n0 = tile_n * BN, mb = m0 + wm * 32, nb = n0 + wn * 32;
             const int ra = wm * 32 + (lane & 31), rb = wn * 32 + (lane & 31), kh = lane >> 5;
             f32x16 acc;
@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256, 4) void bp_wgrad_dma_bf16_store(const BfWgradM
 {
     using K = WgradDmaBf<KTOT>;
     __shared__ __attribute__((aligned(16))) bf16_t smem[K::SMEM];
-    const int b = blockIdx.x;
-    int p = 0;
-    while (p + 1 < a.n && b >= a.first_tile[p + 1]) ++p;
+    const int b = blockIdx.x, p = problem_of(a, b, 0);
     K::run(a.p[p], b - a.first_tile[p], a.first_tile[p + 1] - a.first_tile[p], smem);
 }
 
@@ -173,8 +171,7 @@ struct WgradDmaBf6 {
         const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         if (b >= g.tiles_m * g.tiles_n) return;            // (padding workgroups of the grouped launch: all six waves leave)
         int tile_m, tile_n;
-        if ((g.tiles_n & 7) == 0) { const int xcd = b & 7, j = b >> 3, per = g.tiles_n >> 3; tile_n = xcd * per + j % per; tile_m = j / per; }
-        else { tile_m = b % g.tiles_m; tile_n = b / g.tiles_m; }
+        xcd_tile<true>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
         const int m0 = tile_m * 64, n0 = tile_n * 64;
         const EpiArgs &e = g.e;
         float *sg = reinterpret_cast<float *>(smem);
@@ -251,9 +248,7 @@ template <int KTOT, int BKX = 32, int STX = 4>
 __global__ __launch_bounds__(384, 3) void bp_wgrad_dma_bf16_six(const BfWgradMulti a)
 {
     __shared__ __attribute__((aligned(16))) bf16_t smem[WgradDmaBf<KTOT, BKX, STX>::SMEM];
-    const int b = blockIdx.x;
-    int p = 0;
-    while (p + 1 < a.n && b >= a.first_tile[p + 1]) ++p;
+    const int b = blockIdx.x, p = problem_of(a, b, 0);
     WgradDmaBf6<KTOT, BKX, STX>::run(a.p[p], b - a.first_tile[p], smem);
 }
 

@@ -13,7 +13,8 @@ Seams and the smallest shapes that reach them:
   second grouped launch (more than 4 weight layers)                  six layers, widths 130-192 B 128
   gradient-store form (grads_resident) and its tile counters         both nets                  B 128, B 256
 The tile counters are only read by the exchange kernels of an attached group: a one-rank group trains through them, and a layer
-whose counter stopped short of its tile count would leave the exchange waiting until BP_DP_TIMEOUT_S and fail the call."""
+whose counter stopped short of its tile count would leave the exchange waiting until BP_DP_TIMEOUT_S and fail the call.
+The last test holds the other direction too: which handles report the in-kernel hand-off, and that each trains right."""
 import os
 
 import numpy as np
@@ -109,3 +110,42 @@ def test_store_walk_counts_every_tile(pkg, ls, B, kw):
     few = _trained(pkg, FEW, ls, B, W, b, x, t, kw, attach="walk")
     many = _trained(pkg, MANY, ls, B, W, b, x, t, kw, attach="walk")
     _same_bits(ls, few, many)
+
+
+@pytest.mark.parametrize("ls,B,dtype,handoff", [
+    (NET_PLAIN, 512, 0, True),
+    (NET_PLAIN, 1024, 0, False),
+    (NET_DEEP, 128, 0, False),
+    (NET_PLAIN, 128, 1, False),
+], ids=["fp32_b512", "fp32_b1024_bf16_only_size", "fp32_six_weight_layers", "bf16_b128"])
+def test_handoff_follows_the_kernel_that_counts(pkg, oracle_mod, ls, B, dtype, handoff):
+    """The exchange waits on tile counters exactly when the launch it runs beside bumps them (fp32 store kernel of a static bunch
+    size, at most four weight layers).  A one-rank group, three bunches, against the oracle: a handle that claims the hand-off
+    without the counting kernel times out in the exchange, one that counts unasked or takes the wrong kernel misses the oracle.
+    Bars: fp32 util.TOL (the oracle's own fp32 / fp64-accumulation spread on these nets, bunches and seeds is at most 7.5e-7);
+    bf16 those of test_dispatch_gpu (W, b at TOL_BF16 / 4, momentum state 2e-2 rms; rate 0.5)."""
+    from test_dispatch_gpu import LR, TOL_BF16, relerr_rms
+    W, b, x, t = _data(ls, 3 * B, seed=B + 3)
+    g = pkg.BP_GPU(1, len(ls), ls, B, LR[dtype], 0.5, 0.0, W, b, max_chunk_frames=3 * B, compute_dtype=dtype)
+    g.dp_attach(1, 0, "handoff-%d-%d-%d-%d" % (os.getpid(), len(ls), B, dtype))
+    assert g.dp_handoff() is handoff
+    g.train(3 * B, x, t)
+    got = g.get_weights() + g.get_deltas()
+    g.dp_detach()
+    g.close()
+    o = oracle_mod.Oracle(ls, B, LR[dtype], 0.5, 0.0, W, b, compute_dtype=dtype)
+    o.train(x, t)
+    errs, fails = {}, []
+    for k, (name, ref) in enumerate((("W", o.W), ("b", o.b), ("dW", o.dW), ("db", o.db))):
+        for l in range(1, len(ls)):
+            if dtype == 0:
+                e, bar = relerr(got[k][l], ref[l]), TOL
+            elif k < 2:
+                e, bar = relerr(got[k][l], ref[l]), TOL_BF16 / 4
+            else:
+                e, bar = relerr_rms(got[k][l], ref[l]), TOL_BF16
+            errs["%s%d" % (name, l)] = e
+            if not e < bar:
+                fails.append(("%s%d" % (name, l), e, bar))
+    print(ls, B, dtype, errs)
+    assert not fails, fails
