@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
     "bp_score_waves", "bp_eval_mix",
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts",
+    "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
@@ -90,6 +91,14 @@ class BPStreamConfig(C.Structure):
         ("fea_dim", C.c_int), ("context", C.c_int), ("targ_offset", C.c_int),
         ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
         ("target", C.c_int), ("out_col", C.c_int), ("n_chan", C.c_int), ("max_push_samples", C.c_int),
+    ]
+
+
+class BPLogmmseParams(C.Structure):
+    """bp_logmmse_params (include/bp_c_api.h): the log-MMSE baseline's parameters."""
+    _fields_ = [
+        ("alpha", C.c_double), ("mu", C.c_double), ("eta", C.c_double), ("xi_min_db", C.c_double), ("gamma_max", C.c_double),
+        ("init_frames", C.c_int),
     ]
 
 
@@ -144,6 +153,9 @@ def load_library(path=None):
     lib.bp_mix_shuffle.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
     lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
     lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
+    lib.bp_logmmse_defaults.argtypes = [C.POINTER(BPLogmmseParams)]
+    lib.bp_logmmse_waves.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.c_int, C.POINTER(C.c_int), fp, fp, fp, fp]
+    lib.bp_eval_mix_logmmse.argtypes = [hp, C.POINTER(BPLogmmseParams), C.c_int, C.c_void_p, C.c_int, fp, fp, fp]
     lib.bp_stream_open.argtypes = [hp, C.POINTER(BPStreamConfig), C.POINTER(C.c_void_p)]
     lib.bp_stream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
     lib.bp_stream_close.argtypes = [C.c_void_p]
@@ -491,6 +503,23 @@ class BP_GPU(object):
             pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
         return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
 
+    def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False):
+        """bp_eval_mix_logmmse: eval_mix with the log-MMSE baseline in place of the net (params: None for the defaults, a dict of
+        bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix."""
+        p, pp = self._plan(plan)
+        noisy = np.empty((max(p.size, 1), 3), np.float32)
+        enh = np.empty((max(p.size, 1), 3), np.float32)
+        pcm = None
+        if return_pcm and getattr(self, "mix_fea_dim", None) is not None:
+            lens = self.mix_clean_len[p["clean"]] if p.size else np.zeros(0, np.int64)
+            pcm = np.empty(max(int(lens.sum()), 1), np.float32)
+        lm = logmmse_params(params)
+        self._check(self._lib.bp_eval_mix_logmmse(self._h, None if lm is None else C.byref(lm), p.size, pp, int(sample_rate), _fp(noisy),
+                                                  _fp(enh), _fp(pcm) if pcm is not None else None))
+        if pcm is not None:
+            pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
+        return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
+
     def fill_chunk_synthetic(self, n_frames, seed=20260927):
         self._check(self._lib.bp_fill_chunk_synthetic(self._h, int(n_frames), int(seed)))
 
@@ -686,6 +715,44 @@ def wave_lps(device, fea_dim, sentences):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
+
+
+def logmmse_params(params=None):
+    """None (the library's defaults), or a BPLogmmseParams: bp_logmmse_defaults overridden by the fields of a dict."""
+    if params is None or isinstance(params, BPLogmmseParams):
+        return params
+    lib = load_library()
+    lm = BPLogmmseParams()
+    lib.bp_logmmse_defaults(C.byref(lm))
+    names = [f[0] for f in BPLogmmseParams._fields_]
+    for k, v in dict(params).items():
+        if k not in names:
+            raise BPError("logmmse_params: unknown field %s" % k)
+        setattr(lm, k, int(v) if k == "init_frames" else float(v))
+    return lm
+
+
+def logmmse_waves(device, fea_dim, sentences, params=None, return_gain=False, return_vad=False):
+    """bp_logmmse_waves: every sentence enhanced by the log-MMSE baseline (no handle, no net): a list of float32 arrays, or with
+    return_gain / return_vad a tuple (pcm, gain [T_s][fea_dim] per sentence, vad [T_s] per sentence; the ones not asked for omitted)."""
+    lib = load_library()
+    pcm, lens, frames = _sentences(sentences, int(fea_dim))
+    T = int(frames.sum())
+    out = np.empty(max(pcm.size, 1), np.float32)
+    gain = np.empty((max(T, 1), int(fea_dim)), np.float32) if return_gain else None
+    vad = np.empty(max(T, 1), np.float32) if return_vad else None
+    lm = logmmse_params(params)
+    rc = lib.bp_logmmse_waves(int(device), int(fea_dim), None if lm is None else C.byref(lm), len(lens),
+                              lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out), None if gain is None else _fp(gain),
+                              None if vad is None else _fp(vad))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    res = [np.split(out[:pcm.size], np.cumsum(lens)[:-1])]
+    if return_gain:
+        res.append(np.split(gain[:T], np.cumsum(frames)[:-1]))
+    if return_vad:
+        res.append(np.split(vad[:T], np.cumsum(frames)[:-1]))
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def score_waves(device, fea_dim, sample_rate, refs, ests):

@@ -10,6 +10,7 @@
 //   bp_mix.hip      training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...)
 //   bp_eval.hip     objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval_mix lives in bp_mix.hip)
 //   bp_stream.hip   streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
+//   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in bp_mix.hip)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need

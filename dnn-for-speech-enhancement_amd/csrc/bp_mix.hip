@@ -1,4 +1,4 @@
-// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 7: training mixtures made on the device.  A clean-speech
+// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 8: training mixtures made on the device.  A clean-speech
 // corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
 // SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
 // reads.  gfx950 only.
@@ -17,6 +17,8 @@
 //   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
 // bp_eval_mix runs the same sequence without the targets, keeps the noisy spectrum Y, then bp_enhance_waves'
 // forward / synthesis / overlap-add on it and the scoring kernels of bp_eval.hip (bp_eval.h) on s, x and the enhanced samples.
+// bp_eval_mix_logmmse is the same call with the log-MMSE recursion of bp_classic.hip (bp_classic.h) in place of
+// the forward: its gain rows go where the net's output columns went.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "bp_classic.h"
 #include "bp_eval.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
@@ -147,6 +150,7 @@ struct MixState {
     bp_handle::Raw in_d, x, s, v, gain, lps;                     // grow-only device buffers of the calls
     bp_handle::Raw in_pin[2]; hipEvent_t ev_in[2]; bool ev_valid[2]; int pin_cur;   // pinned input blocks, alternating
     bp_handle::Raw ev_Y, ev_syn, ev_ola, ev_lps, ev_tab, ev_work, ev_pin;             // bp_eval_mix (ev_pin: pinned table block)
+    bp_handle::Raw ev_gain;                                      // bp_eval_mix_logmmse: gain rows [frames][D] | vad [frames]
 };
 
 namespace {
@@ -164,7 +168,7 @@ void free_state(MixState *ms)
     if (!ms) return;
     if (ms->corpus) (void)hipFree(ms->corpus);
     for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps, &ms->ev_Y, &ms->ev_syn, &ms->ev_ola, &ms->ev_lps,
-                              &ms->ev_tab, &ms->ev_work})
+                              &ms->ev_tab, &ms->ev_work, &ms->ev_gain})
         free_raw(*r, false);
     free_raw(ms->ev_pin, true);
     for (int k = 0; k < 2; ++k) {
@@ -478,22 +482,21 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
     return BP_OK;
 }
 
-extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
-                           float *enh_scores, float *enh_pcm)
+// bp_eval_mix (lm == null: the net's output columns [out_col, out_col + D) as `target`) and bp_eval_mix_logmmse (lm: the checked
+// parameters; the gain rows of the recursion as BP_WAVE_MASK): one sequence, one enhancer swapped for the other
+static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const Call &c, const bp_mixture *m, int sample_rate, int target,
+                        int out_col, float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
-    Call c;
     int r;
-    if ((r = plan_call(h, "bp_eval_mix", n_mix, m, c)) != BP_OK) return r;
+    const int n_mix = c.n;
     MixState *ms = h->mix;
-    const int D = ms->D, L = h->L, sL = h->s[L - 1], n = (int)c.frames, hop = ms->hop;
-    if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_eval_mix: target must be BP_WAVE_LPS or BP_WAVE_MASK");
-    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, "bp_eval_mix: out_col + fea_dim exceeds layersizes[last]");
-    if (!noisy_scores || !enh_scores) return fail(BP_ERR_ARG, "bp_eval_mix: null scores");
+    const int D = ms->D, L = h->L, n = (int)c.frames, hop = ms->hop;
+    if (!noisy_scores || !enh_scores) return fail(BP_ERR_ARG, std::string(who) + ": null scores");
     std::vector<int> len(n_mix);
     std::vector<int64_t> off(n_mix);
     for (int i = 0; i < n_mix; ++i) { len[i] = (int)ms->clean_len[m[i].clean]; off[i] = ((int64_t)c.Fs[i] + 1) * hop; }
     EvalPlan ep;
-    if ((r = eval_plan("bp_eval_mix", sample_rate, D, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
+    if ((r = eval_plan(who, sample_rate, D, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
     HIPCHK(hipSetDevice(h->cfg.device));
     // every buffer first (a growth waits for the stream), then the sequence without a host wait
     const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * BP_SCORE_N * 4;
@@ -501,9 +504,10 @@ extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sam
         (r = wave_grow(ms->ev_syn, c.frames * 2 * hop * 4, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_ola, pcm_b, false, h->stream)) != BP_OK ||
         (r = wave_grow(ms->ev_lps, 2 * lps_b, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_tab, ep.t_bytes + sc_b, false, h->stream)) != BP_OK ||
         (r = wave_grow(ms->ev_work, eval_work_bytes(ep, 3), false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->ev_pin, ep.t_bytes, true, h->stream)) != BP_OK || (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK)
+        (r = wave_grow(ms->ev_pin, ep.t_bytes, true, h->stream)) != BP_OK || (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK ||
+        (lm && (r = wave_grow(ms->ev_gain, c.frames * ((size_t)D + 1) * 4, false, h->stream)) != BP_OK))
         return r;
-    if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;
+    if (!lm && (r = out_chunk_reserve(h, n)) != BP_OK) return r;
     // the table block: the pinned buffer is free (the previous call ended in a synchronisation)
     char *tab = (char *)ms->ev_tab.p;
     eval_fill(ep, (char *)ms->ev_pin.p);
@@ -511,13 +515,18 @@ extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sam
     float2 *Y = (float2 *)ms->ev_Y.p;
     if ((r = generate(h, c, m, nullptr, true, nullptr, nullptr, nullptr, Y, false)) != BP_OK) return r;
     if ((r = window_adopt(h, n, D, ms->ctx, ms->nat, false)) != BP_OK) return r;
-    if ((r = forward_resident(h, n)) != BP_OK) return r;
+    if (!lm && (r = forward_resident(h, n)) != BP_OK) return r;
     const char *cp = ms->corpus;
     const float *win = (const float *)(cp + ms->o_win);
     const float2 *tw = (const float2 *)(cp + ms->o_tw);
     const int *F = (const int *)((const char *)ms->in_d.p + c.o_F);
     float *ola = (float *)ms->ev_ola.p, *lps_s = (float *)ms->ev_lps.p, *lps_e = (float *)((char *)ms->ev_lps.p + lps_b);
-    HIPCHK(wave_synthesis_launch(h->out_chunk, h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
+    if (lm) {
+        float *gain = (float *)ms->ev_gain.p;
+        HIPCHK(logmmse_gain_launch(*lm, Y, F, n_mix, D, gain, gain + c.frames * D, h->stream));
+        HIPCHK(wave_synthesis_launch(gain, D, 0, Y, win, tw, ms->log2M, D, BP_WAVE_MASK, (float *)ms->ev_syn.p, n, h->stream));
+    } else
+        HIPCHK(wave_synthesis_launch(h->out_chunk, h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
     HIPCHK(wave_overlap_launch((const float *)ms->ev_syn.p, win, F, n_mix, hop, ola, n, h->stream));
     HIPCHK(eval_trim_launch(ep, tab, hop, ola, h->stream));        // = the enhanced sentences in bp_score_waves' padded layout
     for (int k = 0; k < 2; ++k) {                                  // the LPS of s and of the enhanced samples (x's: generate)
@@ -546,6 +555,28 @@ extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sam
         for (int i = 0; i < n_mix; ++i) { memcpy(enh_pcm + dst, pcm.data() + off[i], (size_t)len[i] * 4); dst += (size_t)len[i]; }
     }
     return BP_OK;
+}
+
+extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
+                           float *enh_scores, float *enh_pcm)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_eval_mix", n_mix, m, c)) != BP_OK) return r;
+    const int D = h->mix->D, sL = h->s[h->L - 1];
+    if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_eval_mix: target must be BP_WAVE_LPS or BP_WAVE_MASK");
+    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, "bp_eval_mix: out_col + fea_dim exceeds layersizes[last]");
+    return eval_mix_run("bp_eval_mix", h, nullptr, c, m, sample_rate, target, out_col, noisy_scores, enh_scores, enh_pcm);
+}
+
+extern "C" int bp_eval_mix_logmmse(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
+                                   float *noisy_scores, float *enh_scores, float *enh_pcm)
+{
+    Call c;
+    LogmmseP lp;
+    int r;
+    if ((r = logmmse_check("bp_eval_mix_logmmse", p, lp)) != BP_OK || (r = plan_call(h, "bp_eval_mix_logmmse", n_mix, m, c)) != BP_OK) return r;
+    return eval_mix_run("bp_eval_mix_logmmse", h, &lp, c, m, sample_rate, BP_WAVE_MASK, 0, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const int64_t *noise_len, int n_snr,

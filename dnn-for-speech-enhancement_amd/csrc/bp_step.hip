@@ -1,6 +1,6 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of seven translation units: the device state of one
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of eight translation units: the device state of one
 // BP_GPU replacement object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.
-// The handle and what the other six units use of this one: bp_handle.h.
+// The handle and what the other seven units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -7,13 +7,17 @@
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
 //             [stream_block=<samples> [stream_chan=<n>]]
+//   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
+//             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6]
 //
 // As many sentences go into one call as fit traincache rows (frames + context-1 replicated edge rows per sentence).  The
 // output is PCM16 at the input's sample rate, rounded to nearest and clipped.  Every input is read and checked before the
 // device is used.  With stream_block the files go through a streaming session instead (bp_stream_push): they
 // are dealt to stream_chan channels (file s to channel s mod stream_chan) and pushed stream_block samples at a time, the last
 // block of a file with its end flag -- the way a live feed would arrive; the output files hold the bytes of a run without
-// stream_block that enhances one sentence per call.  Errors: message + exit(0), success: return 1 (reference convention).
+// stream_block that enhances one sentence per call.  method=logmmse is the classic baseline instead of a net (bp_logmmse_waves,
+// INTEGRATION.md 1h): no weights, no norm file; it takes only the keys of its line above, and the lm_ keys only go with it.
+// Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,9 +38,74 @@ static std::string trim(std::string s)
     return s.substr(i);
 }
 
+// the input and output files of wav_list, or the one pair
+static void read_wav_list(const std::string &list, const std::string &in_wav, const std::string &out_wav, std::vector<std::string> &ins,
+                          std::vector<std::string> &outs)
+{
+    if (list.empty()) { ins.push_back(in_wav); outs.push_back(out_wav); return; }
+    FILE *fl = fopen(list.c_str(), "rt");
+    if (!fl) { printf("can not open wav list: %s\n", list.c_str()); exit(0); }
+    char line[8192];
+    while (fgets(line, sizeof(line), fl)) {
+        const std::string t = trim(line);
+        if (t.empty()) continue;
+        const size_t sp = t.find_first_of(" \t");
+        if (sp == std::string::npos) { printf("wav list %s: line \"%s\" needs an input and an output file\n", list.c_str(), t.c_str()); exit(0); }
+        ins.push_back(t.substr(0, sp)); outs.push_back(trim(t.substr(sp)));
+    }
+    fclose(fl);
+    if (ins.empty()) { printf("bpenhance: %s lists no wav file\n", list.c_str()); exit(0); }
+}
+
+// method=logmmse: every file through bp_logmmse_waves, as many sentences per call as stay below MAXCACHEFRAME frames
+static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, const std::vector<std::string> &ins, const std::vector<std::string> &outs)
+{
+    const int ns = (int)ins.size(), hop = fea_dim - 1;
+    std::vector<std::vector<float>> waves(ns);
+    std::vector<int> rates(ns);
+    for (int s = 0; s < ns; ++s) {
+        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
+        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+        if (waves[s].size() > (size_t)1 << 30) { printf("%s: too long\n", ins[s].c_str()); exit(0); }
+    }
+    std::vector<float> pcm, out;
+    std::vector<int> lens;
+    size_t samples = 0;
+    for (int s0 = 0; s0 < ns;) {
+        int s1 = s0;
+        size_t frames = 0;
+        pcm.clear(); lens.clear();
+        while (s1 < ns) {
+            const size_t T = (waves[s1].size() - 1) / hop + 2;
+            if (s1 > s0 && frames + T > (size_t)MAXCACHEFRAME) break;
+            frames += T;
+            pcm.insert(pcm.end(), waves[s1].begin(), waves[s1].end());
+            lens.push_back((int)waves[s1].size());
+            ++s1;
+        }
+        out.resize(pcm.size());
+        if (bp_logmmse_waves(device, fea_dim, &lm, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        size_t off = 0;
+        for (int s = s0; s < s1; ++s) {
+            const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
+            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+            off += waves[s].size();
+        }
+        samples += pcm.size();
+        s0 = s1;
+    }
+    printf("bpenhance: %zu samples of %d sentences enhanced (logmmse)\n", samples, ns);
+    return 1;
+}
+
 int main(int argc, char **argv)
 {
     std::string norm_file, wts_file, list, in_wav, out_wav;
+    bool logmmse = false;
+    std::vector<std::string> given;
+    bp_logmmse_params lm;
+    bp_logmmse_defaults(&lm);
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
     int stream_block = 0, stream_chan = 1;
@@ -45,7 +114,23 @@ int main(int argc, char **argv)
         char *eq = strchr(argv[i], '=');
         if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
         const std::string k(argv[i], eq - argv[i]), v(eq + 1);
-        if (k == "norm_file") norm_file = v; else if (k == "initwts_file") wts_file = v;
+        given.push_back(k);
+        if (k == "method") {
+            if (v == "net") logmmse = false; else if (v == "logmmse") logmmse = true;
+            else { printf("method: %s is not net or logmmse\n", v.c_str()); exit(0); }
+        } else if (k.compare(0, 3, "lm_") == 0) {
+            char *end = nullptr;
+            const double d = strtod(v.c_str(), &end);
+            if (v.empty() || *end) { printf("%s: %s is not a number\n", k.c_str(), v.c_str()); exit(0); }
+            if (k == "lm_alpha") lm.alpha = d; else if (k == "lm_mu") lm.mu = d; else if (k == "lm_eta") lm.eta = d;
+            else if (k == "lm_xi_min_db") lm.xi_min_db = d; else if (k == "lm_gamma_max") lm.gamma_max = d;
+            else if (k == "lm_init_frames") {
+                if (!(d >= -1e9 && d <= 1e9) || d != (double)(int)d) { printf("%s: %s is not a count\n", k.c_str(), v.c_str()); exit(0); }
+                lm.init_frames = (int)d;
+            }
+            else { printf("bpenhance: unknown key %s\n", k.c_str()); exit(0); }
+        }
+        else if (k == "norm_file") norm_file = v; else if (k == "initwts_file") wts_file = v;
         else if (k == "wav_list") list = v; else if (k == "in_wav") in_wav = v; else if (k == "out_wav") out_wav = v;
         else if (k == "fea_dim") fea_dim = atoi(v.c_str()); else if (k == "fea_context") ctx = atoi(v.c_str());
         else if (k == "targ_offset") toff = atoi(v.c_str()); else if (k == "dropoutflag") dropoutflag = atoi(v.c_str());
@@ -88,6 +173,22 @@ int main(int argc, char **argv)
         }
         else { printf("bpenhance: unknown key %s\n", k.c_str()); exit(0); }
     }
+    for (const std::string &k : given) {
+        const bool lm_key = k.compare(0, 3, "lm_") == 0;
+        if (!logmmse && lm_key) { printf("bpenhance: %s needs method=logmmse\n", k.c_str()); exit(0); }
+        if (logmmse && !lm_key && k != "method" && k != "fea_dim" && k != "device" && k != "wav_list" && k != "in_wav" && k != "out_wav") {
+            printf("bpenhance: method=logmmse takes no %s (only fea_dim, device, wav_list or in_wav and out_wav, and the lm_ keys)\n", k.c_str());
+            exit(0);
+        }
+    }
+    if (logmmse) {
+        if (list.empty() == (in_wav.empty() || out_wav.empty())) { printf("bpenhance: need wav_list, or in_wav and out_wav\n"); exit(0); }
+        const int nf = 2 * (fea_dim - 1);
+        if (fea_dim < 33 || fea_dim > 1025 || (nf & (nf - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
+        std::vector<std::string> li, lo;
+        read_wav_list(list, in_wav, out_wav, li, lo);
+        return logmmse_mode(fea_dim, device, lm, li, lo);
+    }
     if (L < 2 || L > MAXLAYER - 1 || fea_dim < 1 || ctx < 1 || toff < 0 || toff >= ctx || cache < 1 || cache > MAXCACHEFRAME || bunch < 1) {
         printf("bpenhance: need layersizes (2..%d sizes), fea_dim, fea_context, 0 <= targ_offset < fea_context, traincache <= %d\n", MAXLAYER - 1, MAXCACHEFRAME);
         exit(0);
@@ -103,20 +204,7 @@ int main(int argc, char **argv)
 
     // ---- inputs (all read and checked before the device is used)
     std::vector<std::string> ins, outs;
-    if (!list.empty()) {
-        FILE *fl = fopen(list.c_str(), "rt");
-        if (!fl) { printf("can not open wav list: %s\n", list.c_str()); exit(0); }
-        char line[8192];
-        while (fgets(line, sizeof(line), fl)) {
-            const std::string t = trim(line);
-            if (t.empty()) continue;
-            const size_t sp = t.find_first_of(" \t");
-            if (sp == std::string::npos) { printf("wav list %s: line \"%s\" needs an input and an output file\n", list.c_str(), t.c_str()); exit(0); }
-            ins.push_back(t.substr(0, sp)); outs.push_back(trim(t.substr(sp)));
-        }
-        fclose(fl);
-        if (ins.empty()) { printf("bpenhance: %s lists no wav file\n", list.c_str()); exit(0); }
-    } else { ins.push_back(in_wav); outs.push_back(out_wav); }
+    read_wav_list(list, in_wav, out_wav, ins, outs);
     const int ns = (int)ins.size();
     std::vector<std::vector<float>> waves(ns);
     std::vector<int> rates(ns);

@@ -5,7 +5,7 @@
 //          targ_offset=5 layersizes=1548,2048,2048,2048,129 [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [init_randem_seed=0]
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
-//          [scores_out=scores.txt]
+//          [scores_out=scores.txt] [baseline=logmmse]
 //   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt]
 //
 // Test-set mode: the plan is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list), cut into calls
@@ -13,7 +13,10 @@
 // stdout: one line per SNR (ascending) and one "all:" line, noisy -> enhanced; means skip NaN, and the count of NaN scores of the
 // line is printed.  scores_out: one line per mixture in plan order, `clean noise offset snr ssnr_noisy ssnr_enh lsd_noisy lsd_enh
 // stoi_noisy stoi_enh` (%.9g: the floats round-trip); pairs mode: `ref est ssnr lsd stoi` per pair.  Every key, list and WAV is
-// checked before the device is used.  Errors: message + exit(0); success: return 1 (reference convention).
+// checked before the device is used.  baseline=logmmse (test-set mode only) scores the classic log-MMSE enhancer on the same
+// mixtures beside the net (bp_eval_mix_logmmse): after every stdout line a second one with `logmmse:` in place of
+// the net's figures (noisy -> logmmse), and three more columns `ssnr_lm lsd_lm stoi_lm` at the end of every scores_out line.
+// Errors: message + exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -49,6 +52,7 @@ struct Params {
     unsigned long long seed = 0;
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
     bool net_keys = false;                                   // a key of test-set mode was given
+    bool baseline = false;                                   // baseline=logmmse
 };
 
 bool parse_int(const std::string &v, long lo, long hi, int *out)
@@ -117,6 +121,7 @@ Params parse(int argc, char **argv)
                 pos = c + 1;
             }
         }
+        else if (k == "baseline") { if (v == "logmmse") P.baseline = true; else ok = false; }
         else if (k == "wave_target") { if (v == "lps") P.wave_target = BP_WAVE_LPS; else if (v == "mask") P.wave_target = BP_WAVE_MASK; else ok = false; }
         else if (k == "activation") { if (v == "relu") P.activation = 0; else if (v == "sigmoid") P.activation = 1; else ok = false; }
         else if (k == "compute") { if (v == "fp32") P.compute_dtype = 0; else if (v == "bf16") P.compute_dtype = 1; else ok = false; }
@@ -218,7 +223,7 @@ void read_norm(const std::string &path, int D, std::vector<float> &mean, std::ve
 
 int pairs_mode(const Params &P)
 {
-    if (P.net_keys) die("bpeval: pairs_list takes only fea_dim, device and scores_out");
+    if (P.net_keys) die("bpeval: pairs_list takes only fea_dim, device and scores_out");   // (baseline= counts as a key of test-set mode)
     std::vector<std::string> refs, ests;
     for (const std::string &t : read_lines("pairs_list", P.pairs_list)) {
         const size_t sp = t.find_first_of(" \t");
@@ -330,20 +335,30 @@ int main(int argc, char **argv)
     mc.n_clean = (int)clean.len.size(); mc.clean_len = clean.len.data(); mc.clean_pcm = clean.pcm.data();
     mc.n_noise = (int)noise.len.size(); mc.noise_len = noise.len.data(); mc.noise_pcm = noise.pcm.data();
     check(bp_set_mix_corpus(h, &mc));
-    std::map<float, Acc> by_snr;
-    Acc all;
-    std::vector<float> ns, es;
+    std::map<float, Acc> by_snr, by_snr_lm;
+    Acc all, all_lm;
+    std::vector<float> ns, es, ls;
     for (const auto &c : calls) {
         const int n = c.second - c.first;
         ns.resize((size_t)n * BP_SCORE_N); es.resize((size_t)n * BP_SCORE_N);
         check(bp_eval_mix(h, n, plan.data() + c.first, rate, P.wave_target, P.out_col, ns.data(), es.data(), nullptr));
+        if (P.baseline) {                                    // (its noisy scores are those of bp_eval_mix: ns is written twice)
+            ls.resize((size_t)n * BP_SCORE_N);
+            check(bp_eval_mix_logmmse(h, nullptr, n, plan.data() + c.first, rate, ns.data(), ls.data(), nullptr));
+        }
         for (int i = 0; i < n; ++i) {
             const bp_mixture &m = plan[c.first + i];
             const float *a = &ns[(size_t)i * BP_SCORE_N], *b = &es[(size_t)i * BP_SCORE_N];
             add(by_snr[m.snr_db], a, b); add(all, a, b);
             if (fo)
-                fprintf(fo, "%d %d %lld %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", m.clean, m.noise, (long long)m.offset, m.snr_db,
+                fprintf(fo, "%d %d %lld %.9g %.9g %.9g %.9g %.9g %.9g %.9g", m.clean, m.noise, (long long)m.offset, m.snr_db,
                         a[BP_SCORE_SSNR], b[BP_SCORE_SSNR], a[BP_SCORE_LSD], b[BP_SCORE_LSD], a[BP_SCORE_STOI], b[BP_SCORE_STOI]);
+            if (P.baseline) {
+                const float *l = &ls[(size_t)i * BP_SCORE_N];
+                add(by_snr_lm[m.snr_db], a, l); add(all_lm, a, l);
+                if (fo) fprintf(fo, " %.9g %.9g %.9g", l[BP_SCORE_SSNR], l[BP_SCORE_LSD], l[BP_SCORE_STOI]);
+            }
+            if (fo) fprintf(fo, "\n");
         }
     }
     bp_destroy(h);
@@ -353,11 +368,18 @@ int main(int argc, char **argv)
                avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_N + BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_N + BP_SCORE_LSD),
                avg(a, BP_SCORE_STOI), avg(a, BP_SCORE_N + BP_SCORE_STOI), a.nan);
     };
+    const auto line_lm = [](const char *head, const Acc &a) {
+        printf("%s: %d mixtures, logmmse: SSNR %.3f -> %.3f dB, LSD %.3f -> %.3f dB, STOI %.4f -> %.4f (%d undefined)\n", head, a.n,
+               avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_N + BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_N + BP_SCORE_LSD),
+               avg(a, BP_SCORE_STOI), avg(a, BP_SCORE_N + BP_SCORE_STOI), a.nan);
+    };
     for (const auto &kv : by_snr) {
         char head[64];
         snprintf(head, sizeof(head), "SNR %g dB", kv.first);
         line(head, kv.second);
+        if (P.baseline) line_lm(head, by_snr_lm[kv.first]);
     }
     line("all", all);
+    if (P.baseline) line_lm("all", all_lm);
     return 1;
 }

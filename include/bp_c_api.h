@@ -297,6 +297,58 @@ int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, i
                 float *enh_scores, float *enh_pcm);
 
 /* ------------------------------------------------------------------------------------
+ * The classic baseline: the log-MMSE (Ephraim-Malah log-spectral-amplitude) enhancer, the column every results table of the papers
+ * the reference asks its users to cite sets beside the DNN (the reference ships enh_wav_example/test3_ForestGump_logMMSE_enh.wav
+ * for that comparison; it has no code for it).  INTEGRATION.md 1h.  The signal definition of bp_enhance_waves applies unchanged
+ * (n_fft, hop, window, padding, the T frames, fp32 samples in int16 units); Y_t[k] is the fp32 spectrum of that analysis, D =
+ * fea_dim bins.  Everything below runs in double on those fp32 values.
+ *
+ * bp_logmmse_params {alpha, mu, eta, xi_min_db, gamma_max, init_frames}; bp_logmmse_defaults writes 0.98, 0.98, 0.15, -25, 40, 6
+ * (Loizou's logmmse); a NULL params pointer means the defaults.  Valid: 0 <= alpha < 1, 0 <= mu <= 1, eta finite,
+ * -100 <= xi_min_db <= 0, gamma_max >= 1 and finite, init_frames >= 1; anything else is BP_ERR_ARG before the device is touched.
+ *
+ * Per sentence and per bin k, P_t = re^2 + im^2, xi_min = 10^(xi_min_db/10), lambda_floor = 1e-10 (the LPS floor):
+ *   lambda = max(mean_{t < min(init_frames, T)} P_t, lambda_floor)     (the noise start: the sentence's first frames, as the
+ *                                                                      noise-aware block takes them)
+ *   for t = 0 .. T-1:
+ *     gamma = min(P_t / lambda, gamma_max)
+ *     xi    = (t == 0 ? alpha : alpha A_prev / lambda) + (1 - alpha) max(gamma - 1, 0);  xi = max(xi, xi_min)
+ *     Lambda = gamma xi/(1+xi) - ln(1+xi)
+ *     vad_t = (1/D) sum_k Lambda_k                                     (one fixed summation order)
+ *     if vad_t < eta: lambda <- max(mu lambda + (1 - mu) P_t, lambda_floor)   (from frame t+1 on; frame t's gain uses the xi, gamma above)
+ *     A = xi/(1+xi);  v = A gamma
+ *     G = P_t > 0 ? A exp(E1(v)/2) : 0                                 (no clamp at 1: the usual form; G|Y| stays below about
+ *                                                                      0.75 sqrt(A lambda))
+ *     A_prev = G^2 P_t                                                 (G unrounded)
+ *     S_t[k] = fl32(G) Y_t[k]
+ * E1 is the exponential integral: for x <= 1, -gamma_E - ln x - sum_{n>=1} (-x)^n/(n n!) summed to convergence; for x > 1 the
+ * continued fraction e^-x/(x+1 - 1/(x+3 - 4/(x+5 - ...))) by the modified Lentz method to 1e-16.
+ * Synthesis and overlap-add are those of bp_enhance_waves with BP_WAVE_MASK and the gain row in place of the net's output, trimmed
+ * to n samples.  No float atomics: the same bits on every run.
+ *
+ * bp_logmmse_waves (no handle): out_pcm holds sum(sent_len) samples; out_gain NULL or [sum T][fea_dim], fl32(G); out_vad NULL or
+ *   [sum T], fl32(vad_t).  One host->device copy, one device->host copy, one synchronisation; every argument is checked before the
+ *   device is touched.
+ * bp_eval_mix_logmmse: bp_eval_mix with this enhancer in place of the net -- each mixture made exactly as bp_mix_features makes
+ *   it, enhanced exactly as bp_logmmse_waves would enhance the mixed samples, x and the result scored against the clean s exactly
+ *   as bp_eval_mix scores them; the audio stays on the device.  The argument and capacity rules of bp_eval_mix; BP_ERR_STATE
+ *   without a corpus and on a data-parallel-attached handle.  The call leaves the chunk as the resident window chunk; weights and
+ *   momentum state are untouched. */
+typedef struct bp_logmmse_params {
+    double alpha;        /* decision-directed weight of the a-priori SNR */
+    double mu;           /* smoothing of the noise update in frames the VAD calls noise */
+    double eta;          /* VAD threshold on the mean log likelihood ratio */
+    double xi_min_db;    /* floor of the a-priori SNR, dB */
+    double gamma_max;    /* cap of the a-posteriori SNR */
+    int    init_frames;  /* frames of the noise start */
+} bp_logmmse_params;
+int bp_logmmse_defaults(bp_logmmse_params *p);
+int bp_logmmse_waves(int device, int fea_dim, const bp_logmmse_params *p, int n_sent, const int *sent_len, const float *pcm,
+                     float *out_pcm, float *out_gain, float *out_vad);
+int bp_eval_mix_logmmse(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
+                        float *noisy_scores, float *enh_scores, float *enh_pcm);
+
+/* ------------------------------------------------------------------------------------
  * Streaming sessions: audio that is still arriving, enhanced in blocks (no reference counterpart).  INTEGRATION.md 1g.  The signal
  * definition of bp_enhance_waves applies unchanged, and a sentence pushed in blocks of ANY sizes returns the same bits as one
  * bp_enhance_waves call on the finished sentence on the same handle.
