@@ -3,7 +3,7 @@
 `libbp_hip.so` behind the C ABI in include/bp_c_api.h; this package is its Python host mirror.
 (The directory name contains '-', import it through `dnnse_amd.py` at the repo root.)"""
 from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMBOLS, MAXLAYER, MAXCACHEFRAME,  # noqa: F401
-                     Rendezvous, device_count, device_pci_bus_id, wave_lps, WAVE_LPS, WAVE_MASK,
+                     Rendezvous, device_count, device_pci_bus_id, wave_lps, WAVE_LPS, WAVE_MASK, FORWARD_DEFAULT, FORWARD_ROWINV,
                      BPWaveChunk, BPMixCorpus, MIXTURE_DTYPE, MIX_TARGETS, MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM,
                      MIX_LPS_IBM, mix_plan, mix_shuffle, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves)

@@ -33,16 +33,17 @@ ABI_SYMBOLS = [
     "bp_fill_chunk_synthetic", "bp_train_resident", "bp_sync", "bp_grads_resident",
     "bp_grad_layout", "bp_grad_floats", "bp_read_grads", "bp_read_layer_output", "bp_last_train_ms", "bp_time_kernel",
     "bp_upload_chunk_windows", "bp_train_chunk_windows", "bp_cv_chunk_windows",
-    "bp_set_hyper", "bp_set_output", "bp_dp_attach", "bp_dp_attach_ex", "bp_dp_detach", "bp_dp_info", "bp_dp_peer_info", "bp_dp_handoff", "bp_dp_barrier", "bp_dp_allgather",
+    "bp_set_hyper", "bp_set_output", "bp_set_forward", "bp_dp_attach", "bp_dp_attach_ex", "bp_dp_detach", "bp_dp_info", "bp_dp_peer_info", "bp_dp_handoff", "bp_dp_barrier", "bp_dp_allgather",
     "bp_rdv_open", "bp_rdv_barrier", "bp_rdv_allgather", "bp_rdv_close", "bp_device_pci_bus_id", "bp_host_register", "bp_host_unregister",
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
     "bp_enhance_waves", "bp_wave_lps",
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
     "bp_score_waves", "bp_eval_mix",
-    "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts",
+    "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
+FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
 MIX_TARGETS = {"lps": MIX_LPS, "irm": MIX_IRM, "ibm": MIX_IBM, "lps+irm": MIX_LPS_IRM, "lps+ibm": MIX_LPS_IBM}
@@ -174,6 +175,8 @@ def load_library(path=None):
     lib.bp_measure_peaks.argtypes = [hp, fp, fp]
     lib.bp_set_hyper.argtypes = [hp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
     lib.bp_set_output.argtypes = [hp, C.c_int, C.c_int, C.c_int]
+    lib.bp_set_forward.argtypes = [hp, C.c_int]
+    lib.bp_stream_packed.argtypes = [C.c_void_p]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.bp_dp_peer_info.argtypes = [hp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -215,7 +218,7 @@ class BP_GPU(object):
     def __init__(self, gpu_used, numlayers, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
                  dropoutflag=0, visible_omit=0.0, hid_omit=0.0, activation=0, momentum_rule=0, seed=0, device=0,
                  global_bunchsize=0, rank_frame_offset=0, max_chunk_frames=0, strict_exit=False, compute_dtype=0,
-                 output_activation=0, output_linear_cols=0, output_loss=0):
+                 output_activation=0, output_linear_cols=0, output_loss=0, forward_mode=FORWARD_DEFAULT):
         self._h = None
         self._strict = strict_exit
         self._lib = load_library()
@@ -249,8 +252,11 @@ class BP_GPU(object):
         h = C.c_void_p()
         self._check(self._lib.bp_create(C.byref(cfg), _ptrs(w), _ptrs(b), C.byref(h)))
         self._h = h
+        self.forward_mode = FORWARD_DEFAULT
         if out_mode != (0, 0, 0):
             self.set_output(*out_mode)
+        if int(forward_mode) != FORWARD_DEFAULT:
+            self.set_forward(forward_mode)
 
     # ------------------------------------------------------------------ errors
     def _fail(self, msg):
@@ -295,6 +301,12 @@ class BP_GPU(object):
         a, c, s = self._output_args(activation, linear_cols, loss)
         self._check(self._lib.bp_set_output(self._h, a, c, s))
         self.output_activation, self.output_linear_cols, self.output_loss = a, c, s
+
+    def set_forward(self, mode):
+        """The kernels of the inference forward (bp_set_forward): FORWARD_DEFAULT, or FORWARD_ROWINV -- a frame's output bits then
+        depend on its input row and the net alone, and streams opened from now on pack their channels.  fp32 handles."""
+        self._check(self._lib.bp_set_forward(self._h, int(mode)))
+        self.forward_mode = int(mode)
 
     def train(self, n_frames, indata, targ):
         x = self._in(indata, n_frames, self.layersizes[0], "in")
@@ -415,7 +427,7 @@ class BP_GPU(object):
         c.target, c.out_col, c.n_chan, c.max_push_samples = int(target), int(out_col), int(n_chan), int(max_push_samples)
         s = C.c_void_p()
         self._check(self._lib.bp_stream_open(self._h, C.byref(c), C.byref(s)))
-        return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan))
+        return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan), bool(self._lib.bp_stream_packed(s)))
 
     # ---- training mixtures made on the device (bp_set_mix_corpus ...; definition: include/bp_c_api.h)
     def set_mix_corpus(self, clean, noise, mean, inv_std, context, targ_offset, target=MIX_LPS, lc_db=5.0):
@@ -650,10 +662,16 @@ class BP_GPU(object):
 class Stream(object):
     """A streaming session (bp_stream_*): n_chan live feeds enhanced in blocks of any sizes."""
 
-    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan):
-        self._g, self._s = owner, s
+    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan, packed=False):
+        self._g, self._s, self._packed = owner, s, bool(packed)
         self.fea_dim, self.context, self.targ_offset, self.n_chan = fea_dim, context, targ_offset, n_chan
         self.look_ahead = context - 1 - targ_offset
+
+    @property
+    def packed(self):
+        """True for a stream opened in FORWARD_ROWINV: a push places its frames densely and runs the row-invariant forward, whatever
+        the handle's mode is by then."""
+        return self._packed
 
     def push(self, blocks, end=None, out_cap=None):
         """blocks: one 1-D array of new samples per channel (None or empty: none); end: per channel, true closes the channel's

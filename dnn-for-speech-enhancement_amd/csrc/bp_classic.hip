@@ -1,4 +1,4 @@
-// bp_classic.hip -- C-ABI implementation (include/bp_c_api.h), part 8 of 8: the classic baseline.  The log-MMSE (Ephraim-Malah
+// bp_classic.hip -- C-ABI implementation (include/bp_c_api.h), part 8 of 9: the classic baseline.  The log-MMSE (Ephraim-Malah
 // log-spectral-amplitude) enhancer on the signal definition of bp_wave.hip: noisy PCM in, enhanced PCM out, no net
 // (bp_logmmse_waves here; bp_eval_mix_logmmse in bp_mix.hip through bp_classic.h).  Definition: include/bp_c_api.h,
 // INTEGRATION.md 1h.  gfx950 only.

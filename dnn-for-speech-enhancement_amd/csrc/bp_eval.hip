@@ -1,4 +1,4 @@
-// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 8: objective scores of enhanced speech.  Segmental SNR,
+// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 9: objective scores of enhanced speech.  Segmental SNR,
 // log-spectral distortion on the 1d analysis and STOI of estimates against a reference (bp_score_waves here; bp_eval_mix in
 // bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.
 //

@@ -11,6 +11,7 @@
 //   bp_eval.hip     objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval_mix lives in bp_mix.hip)
 //   bp_stream.hip   streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
 //   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in bp_mix.hip)
+//   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -79,6 +80,8 @@ struct bp_handle {
     size_t out_chunk_frames;
     uint32_t step;               // bunches trained so far (dropout stream position)
     uint32_t th_vis, th_hid;
+    int fwd_mode;                     // bp_set_forward: the kernels of the inference forward (BP_FORWARD_DEFAULT | BP_FORWARD_ROWINV)
+    float *inf_slab; unsigned *inf_ticket[BP_MAXLAYER];   // ROWINV: k-slice slabs (shared by the layers) and each layer's ticket words, or null
     int out_act, out_lin, out_loss;   // output layer (bp_set_output): 0 linear | 1 logistic on columns [out_lin, s_L), loss of those columns
     hipEvent_t ev0, ev1; float last_ms; int last_bunches;
     std::vector<void *> allocs;
@@ -177,7 +180,8 @@ int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, siz
 int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat, bool with_targ);
 // CV-semantics forward of samples [0, n) of the resident chunk into out_chunk (the partial last bunch included), no copy
 int out_chunk_reserve(bp_handle *h, int n_frames);
-int forward_resident(bp_handle *h, int n);
+int forward_resident(bp_handle *h, int n);                 // ... with the kernels of the handle's mode (bp_set_forward)
+int forward_resident_as(bp_handle *h, int n, int mode);    // ... with those of `mode` (CV: always BP_FORWARD_DEFAULT; a stream: its own)
 
 // ------------------------------------------------------------------ mixtures (bp_mix.hip)
 void mix_free(bp_handle *h);                      // the corpus and the mixing buffers (bp_destroy)

@@ -1,4 +1,4 @@
-// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 8: training mixtures made on the device.  A clean-speech
+// bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 9: training mixtures made on the device.  A clean-speech
 // corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
 // SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
 // reads.  gfx950 only.
@@ -433,7 +433,7 @@ extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq
     if ((r = generate(h, c, m, nullptr, false, nullptr, &targ_d, nullptr)) != BP_OK) return r;
     // forward without staging the targets (as bp_cv_chunk_windows); the target frames stay in the set for the sum below
     if ((r = window_adopt(h, n, h->mix->D, h->mix->ctx, h->mix->nat, false)) != BP_OK) return r;
-    if ((r = forward_resident(h, n)) != BP_OK) return r;
+    if ((r = forward_resident_as(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV: the step's kernels in either mode)
     std::vector<float> tg((size_t)n * sL);
     HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * ldL * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(tg.data(), targ_d, tg.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));

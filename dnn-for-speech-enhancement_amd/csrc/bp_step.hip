@@ -1,10 +1,11 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of eight translation units: the device state of one
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of nine translation units: the device state of one
 // BP_GPU replacement object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.
-// The handle and what the other seven units use of this one: bp_handle.h.
+// The handle and what the other units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <utility>
@@ -12,6 +13,7 @@
 
 #include "bp_handle.h"
 #include "bp_kernels.h"
+#include "bp_infer.h"
 #include "bp_bf16.h"
 #include "bp_wgrad_dma.h"
 #include "bp_wgrad_dma_bf16.h"
@@ -141,6 +143,8 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
     h->next_first = -1; h->pre.valid = false; h->wgen = 0; h->stage_cur = 0;
     h->bf_ks_slab = nullptr; h->bf_ks_cnt = nullptr;
     h->out_act = h->out_lin = h->out_loss = 0;
+    h->fwd_mode = BP_FORWARD_DEFAULT; h->inf_slab = nullptr;
+    for (int l = 0; l < BP_MAXLAYER; ++l) h->inf_ticket[l] = nullptr;
 
 #define CK(x) do { int _r = (x); if (_r != BP_OK) { std::string m = g_bp_err; bp_destroy(h); g_bp_err = m; return _r; } } while (0)
 #define HK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::string m = std::string(#x) + ": " + hipGetErrorString(_e); bp_destroy(h); return fail(BP_ERR_DEVICE, m); } } while (0)
@@ -274,6 +278,37 @@ extern "C" int bp_set_output(bp_handle *h, int activation, int linear_cols, int 
     if (activation == 1 && (linear_cols < 0 || linear_cols >= sL))
         return fail(BP_ERR_ARG, "bp_set_output: linear_cols must be in [0, " + std::to_string(sL) + ") with the logistic output");
     h->out_act = activation; h->out_lin = linear_cols; h->out_loss = loss;
+    return BP_OK;
+}
+
+// The inference forward's kernels (include/bp_c_api.h).  ROWINV allocates its workspace on first use: the slabs of the widest
+// k-split layer and one zeroed ticket word per output tile and layer (the words of a layer only ever grow by its own splitk).
+extern "C" int bp_set_forward(bp_handle *h, int mode)
+{
+    if (!h) return fail(BP_ERR_ARG, "bp_set_forward: null handle");
+    if (mode != BP_FORWARD_DEFAULT && mode != BP_FORWARD_ROWINV)
+        return fail(BP_ERR_ARG, "bp_set_forward: mode must be BP_FORWARD_DEFAULT (0) or BP_FORWARD_ROWINV (1)");
+    if (mode == BP_FORWARD_ROWINV && h->bf)
+        return fail(BP_ERR_ARG, "bp_set_forward: BP_FORWARD_ROWINV needs an fp32 handle (compute_dtype = 0); the bf16 forward has no row-invariant kernel");
+    if (mode == BP_FORWARD_ROWINV && !h->inf_ticket[1]) {
+        HIPCHK(hipSetDevice(h->cfg.device));
+        const size_t rows = (size_t)((h->B + INFER_BM - 1) / INFER_BM) * INFER_BM;
+        // every layer lays its slices out at its own stride rows * ld_l (forward_bunch), so the largest layer's need is enough
+        size_t slab = 0;
+        for (int l = 1; l < h->L; ++l) {
+            const InferPlan p = infer_plan(h->ld[l - 1], h->ld[l]);
+            if (p.splitk > 1) slab = std::max(slab, rows * h->ld[l] * p.splitk);
+        }
+        if (slab && !h->inf_slab) { const int r = dev_alloc(h, &h->inf_slab, slab); if (r != BP_OK) return r; }
+        for (int l = h->L - 1; l >= 1; --l) {                // (layer 1 last: its pointer marks the workspace complete)
+            if (h->inf_ticket[l]) continue;                  // (kept from a call that failed further on)
+            float *tk = nullptr;
+            const int r = dev_alloc(h, &tk, (rows / INFER_BM) * (size_t)infer_plan(h->ld[l - 1], h->ld[l]).tiles_n);
+            if (r != BP_OK) return r;
+            h->inf_ticket[l] = reinterpret_cast<unsigned *>(tk);
+        }
+    }
+    h->fwd_mode = mode;
     return BP_OK;
 }
 
@@ -1224,7 +1259,7 @@ int out_chunk_reserve(bp_handle *h, int n_frames)
 }
 
 // forward of frames [first, first+fb) of the resident chunk with CV semantics; output rows go to out_chunk[first ..]
-static int forward_bunch(bp_handle *h, int first, int fb)
+static int forward_bunch(bp_handle *h, int first, int fb, int mode)
 {
     const int L = h->L;
     const float vis_keep = 1.0f - h->cfg.visible_omit, hid_keep = 1.0f - h->cfg.hid_omit;   // BP_GPU.cu:703-704
@@ -1234,27 +1269,43 @@ static int forward_bunch(bp_handle *h, int first, int fb)
     for (int l = 1; l < L; ++l) {
         float alpha = 1.0f;
         if (h->cfg.dropoutflag == 1) alpha = (l == 1) ? vis_keep : hid_keep;
+        if (mode == BP_FORWARD_ROWINV) {
+            // the row-invariant kernel of bp_infer.hip: same inputs, same outputs, a summation order that K and N alone fix
+            const InferPlan p = infer_plan(h->ld[l - 1], h->ld[l]);
+            InferArgs a; memset(&a, 0, sizeof(a));
+            a.X = l == 1 ? x0 : h->y[l - 1]; a.ldx = h->ld[l - 1]; a.W = h->W[l]; a.ldw = h->ld[l]; a.bias = h->b[l];
+            a.out = l == L - 1; a.Y = a.out ? out : h->y[l]; a.ldy = h->ld[l];
+            a.M = fb; a.K = h->ld[l - 1]; a.N = h->ld[l]; a.n_true = h->s[l];
+            a.splitk = p.splitk; a.per = p.per; a.tiles_n = p.tiles_n; a.alpha = alpha;
+            a.act = h->cfg.activation; a.logi = h->out_act == 1; a.lin_cols = h->out_lin;
+            a.slab = h->inf_slab; a.ticket = h->inf_ticket[l];
+            a.slab_stride = (size_t)((h->B + INFER_BM - 1) / INFER_BM) * INFER_BM * h->ld[l];   // (what bp_set_forward sized the slab for)
+            HIPCHK(infer_layer_launch(a, h->stream));
+            continue;
+        }
         HIPCHK(step_forward(h, l, fb, x0, nullptr, out, false, alpha));
     }
     return BP_OK;
 }
 
 // every bunch of the resident chunk (partial last bunch included, BP_GPU.cu:450-453) into out_chunk
-int forward_resident(bp_handle *h, int n)
+int forward_resident(bp_handle *h, int n) { return forward_resident_as(h, n, h->fwd_mode); }
+int forward_resident_as(bp_handle *h, int n, int mode)
 {
+    if (mode == BP_FORWARD_ROWINV && (h->bf || !h->inf_ticket[1])) return fail(BP_ERR_STATE, "forward: BP_FORWARD_ROWINV without its workspace");
     int r = out_chunk_reserve(h, n);
     if (r != BP_OK) return r;
     for (int i = 0; i < n; i += h->B) {
         const int fb = h->B > n - i ? n - i : h->B;
-        if ((r = forward_bunch(h, i, fb)) != BP_OK) return r;
+        if ((r = forward_bunch(h, i, fb, mode)) != BP_OK) return r;
     }
     return BP_OK;
 }
 
 // ... then one copy into host_out
-static int forward_chunk(bp_handle *h, int n)
+static int forward_chunk(bp_handle *h, int n, int mode)
 {
-    const int r = forward_resident(h, n);
+    const int r = forward_resident_as(h, n, mode);
     if (r != BP_OK) return r;
     if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1266,7 +1317,7 @@ extern "C" int bp_forward(bp_handle *h, int n_frames, const float *in, float *ou
     if (!h || !in || !out) return fail(BP_ERR_ARG, "bp_forward: null argument");
     int r = bp_upload_chunk(h, n_frames, in, nullptr);
     if (r != BP_OK) return r;
-    if ((r = forward_chunk(h, n_frames)) != BP_OK) return r;
+    if ((r = forward_chunk(h, n_frames, h->fwd_mode)) != BP_OK) return r;
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
     for (int j = 0; j < n_frames; ++j) memcpy(out + (size_t)j * sL, h->host_out + (size_t)j * ldL, sizeof(float) * sL);
     return BP_OK;
@@ -1277,7 +1328,7 @@ extern "C" int bp_forward_windows(bp_handle *h, const bp_window_chunk *c, float 
     if (!out) return fail(BP_ERR_ARG, "bp_forward_windows: null argument");
     int r = upload_windows(h, c, false, "bp_forward_windows");
     if (r != BP_OK) return r;
-    if ((r = forward_chunk(h, c->n_samples)) != BP_OK) return r;
+    if ((r = forward_chunk(h, c->n_samples, h->fwd_mode)) != BP_OK) return r;
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
     for (int j = 0; j < c->n_samples; ++j) memcpy(out + (size_t)j * sL, h->host_out + (size_t)j * ldL, sizeof(float) * sL);
     return BP_OK;
@@ -1288,7 +1339,7 @@ extern "C" int bp_cv_chunk(bp_handle *h, int n_frames, const float *in, const fl
     if (!h || !in || !targ || !sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_chunk: null argument");
     int r = bp_upload_chunk(h, n_frames, in, nullptr);
     if (r != BP_OK) return r;
-    if ((r = forward_chunk(h, n_frames)) != BP_OK) return r;
+    if ((r = forward_chunk(h, n_frames, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV keeps the step's kernels in either mode)
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
     float squared_err = 0.0f;
     for (int j = 0; j < n_frames; ++j)                   // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
@@ -1309,7 +1360,7 @@ extern "C" int bp_cv_chunk_windows(bp_handle *h, const bp_window_chunk *c, float
     if (n > 0 && (!c->targ_frames || !c->targ_frame)) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: null targets");
     for (int i = 0; i < n; ++i)
         if (c->targ_frame[i] < 0 || c->targ_frame[i] >= c->n_frames) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: targ_frame out of range");
-    if ((r = forward_chunk(h, n)) != BP_OK) return r;
+    if ((r = forward_chunk(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;
     float squared_err = 0.0f;
     for (int j = 0; j < n; ++j) {                        // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
         const float *t = c->targ_frames + (size_t)c->targ_frame[j] * sL;

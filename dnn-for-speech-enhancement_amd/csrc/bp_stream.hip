@@ -1,4 +1,4 @@
-// bp_stream.hip -- C-ABI implementation (include/bp_c_api.h), part 7 of 8: streaming sessions.  Audio that is still arriving is
+// bp_stream.hip -- C-ABI implementation (include/bp_c_api.h), part 7 of 9: streaming sessions.  Audio that is still arriving is
 // enhanced in blocks of any sizes, on n_chan independent channels per push, and returns the SAME BITS as one bp_enhance_waves
 // call on the finished sentence: the analysis and the synthesis are the device functions of bp_wave.hip (bp_fft.h), the forward
 // is forward_resident on a window chunk, and the overlap-add is the same gather of two frames.  gfx950 only.
@@ -30,6 +30,9 @@
 // bp_enhance_waves on one sentence runs frame t as row t mod bunchsize, so a push places frame t of a channel at a sample g with
 // g = t (mod bunchsize): the channels of a push start in bunches of their own unless their rows happen to follow each other, and
 // the samples in between are fillers (window 0, computed and ignored).
+// A stream opened while the handle is in BP_FORWARD_ROWINV (bp_set_forward) runs the row-invariant forward of bp_infer.hip, whose
+// bits do not depend on the row: it is `packed` -- the frames of a push follow each other in channel order, without fillers, and a
+// push of n frames costs ceil(n / bunchsize) bunches whatever the number of channels.  The mode is the stream's from then on.
 // No float atomics.  Per push: one host->device copy, one device->host copy, one synchronisation.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -194,6 +197,7 @@ struct bp_stream {
     bp_handle *h;
     int D, ctx, toff, la, target, out_col, n_chan, max_push, hop, log2M, R;
     bool nat;
+    bool packed;                 // opened in BP_FORWARD_ROWINV: dense placement, the row-invariant forward on every push
     std::vector<Chan> ch;
     std::vector<ChanPlan> plan;
     std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<SynJob> syn;
@@ -254,7 +258,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     bp_stream *s = new bp_stream();
     s->h = h; s->D = D; s->ctx = ctx; s->toff = c->targ_offset; s->la = ctx - 1 - c->targ_offset; s->target = c->target;
     s->out_col = c->out_col; s->n_chan = c->n_chan; s->max_push = c->max_push_samples; s->hop = D - 1; s->log2M = wave_log2_fft(D);
-    s->R = ctx + 6; s->nat = nat;
+    s->R = ctx + 6; s->nat = nat; s->packed = h->fwd_mode == BP_FORWARD_ROWINV;
     const int hop = s->hop, N = 2 * hop, nc = s->n_chan;
     // A push analyses at most n_in/hop + 3 frames per channel (the end of a sentence adds up to 3) and enhances those plus the
     // frames that waited; it can never enhance more than the chunk capacity lets it stage.
@@ -301,6 +305,8 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     return BP_OK;
 }
 
+extern "C" int bp_stream_packed(const bp_stream *s) { return s && s->packed ? 1 : 0; }
+
 extern "C" int bp_stream_close(bp_stream *s)
 {
     if (!s) return BP_OK;
@@ -337,7 +343,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         p.c1 = stream_counts(hop, s->la, s->nat, p.r1, p.ended);
         const int64_t ne = p.c1.fo - p.c0.fo;
         due += p.c1.so - p.c0.so; n_enh += ne;
-        if (ne > 0) { p.g0 = n + ((p.c0.fo - n) % B + B) % B; n = p.g0 + ne; }      // frame t as row t mod B of its bunch
+        if (ne > 0) { p.g0 = s->packed ? n : n + ((p.c0.fo - n) % B + B) % B; n = p.g0 + ne; }      // frame t as row t mod B of its bunch; packed: any row
         if (ne > 0) rows += ne + ctx - 1;
         if (p.c1.fi > p.c0.fi) { ana_max += p.c1.fi - std::max<int64_t>(0, p.c0.fo - toff); ++active; }
         if (!p.ended && p.c1.fi - std::max<int64_t>(0, p.c1.fo - toff) > R)
@@ -467,7 +473,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     if (n > 0) {
         int r;
         if ((r = window_adopt(h, (int)n, D, ctx, s->nat, false)) != BP_OK) return r;
-        if ((r = forward_resident(h, (int)n)) != BP_OK) return r;
+        if ((r = forward_resident_as(h, (int)n, s->packed ? BP_FORWARD_ROWINV : BP_FORWARD_DEFAULT)) != BP_OK) return r;
         StreamSynArgs a; memset(&a, 0, sizeof(a));
         a.jobs = (const SynJob *)(din + o_syn); a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = s->out_col;
         a.Y = Y; a.win = win; a.tw = tw; a.log2M = s->log2M; a.D = D; a.target = s->target;

@@ -1,4 +1,4 @@
-// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 8: the signal layer around the network.  Noisy PCM
+// bp_wave.hip -- C-ABI implementation (include/bp_c_api.h), part 4 of 9: the signal layer around the network.  Noisy PCM
 // in, enhanced PCM out (bp_enhance_waves), and the same analysis alone for feature extraction (bp_wave_lps).  gfx950 only.
 //
 // One signal definition, derived from fea_dim: n_fft = 2 (fea_dim - 1), a power of two in 64 .. 2048;

@@ -6,7 +6,7 @@
 //             [wave_target=lps|mask] [out_col=0] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2] [bunchsize=1024]
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
-//             [stream_block=<samples> [stream_chan=<n>]]
+//             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
 //             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6]
 //
@@ -15,7 +15,9 @@
 // device is used.  With stream_block the files go through a streaming session instead (bp_stream_push): they
 // are dealt to stream_chan channels (file s to channel s mod stream_chan) and pushed stream_block samples at a time, the last
 // block of a file with its end flag -- the way a live feed would arrive; the output files hold the bytes of a run without
-// stream_block that enhances one sentence per call.  method=logmmse is the classic baseline instead of a net (bp_logmmse_waves,
+// stream_block that enhances one sentence per call.  forward=rowinv selects the row-invariant forward (bp_set_forward,
+// INTEGRATION.md 1i; fp32): a sentence's bytes then do not depend on what else went into its call, and a streaming session packs
+// its channels.  method=logmmse is the classic baseline instead of a net (bp_logmmse_waves,
 // INTEGRATION.md 1h): no weights, no norm file; it takes only the keys of its line above, and the lm_ keys only go with it.
 // Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
@@ -108,7 +110,7 @@ int main(int argc, char **argv)
     bp_logmmse_defaults(&lm);
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
-    int stream_block = 0, stream_chan = 1;
+    int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT;
     float vis = 0.f, hid = 0.f;
     for (int i = 1; i < argc; ++i) {
         char *eq = strchr(argv[i], '=');
@@ -144,6 +146,10 @@ int main(int argc, char **argv)
             const long n = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end || n < 1 || n > (1 << 24)) { printf("%s: %s is not a count >= 1\n", k.c_str(), v.c_str()); exit(0); }
             (k == "stream_block" ? stream_block : stream_chan) = (int)n;
+        }
+        else if (k == "forward") {
+            if (v == "default") forward = BP_FORWARD_DEFAULT; else if (v == "rowinv") forward = BP_FORWARD_ROWINV;
+            else { printf("forward: %s is not default or rowinv\n", v.c_str()); exit(0); }
         }
         else if (k == "wave_target") {
             if (v == "lps") target = BP_WAVE_LPS; else if (v == "mask") target = BP_WAVE_MASK;
@@ -200,6 +206,7 @@ int main(int argc, char **argv)
     if (ls[0] != ctx * fea_dim && ls[0] != (ctx + 1) * fea_dim) { printf("bpenhance: layersizes[0] must be fea_context*fea_dim (+ fea_dim with a NAT block)\n"); exit(0); }
     if (stream_chan > 1 && stream_block < 1) { printf("bpenhance: stream_chan needs stream_block\n"); exit(0); }
     if (stream_block > 0 && (long)stream_block * stream_chan > (1L << 28)) { printf("bpenhance: stream_block * stream_chan is too large\n"); exit(0); }
+    if (forward == BP_FORWARD_ROWINV && compute == 1) { printf("bpenhance: forward=rowinv needs compute=fp32\n"); exit(0); }
     if (out_col < 0 || out_col + fea_dim > ls[L - 1]) { printf("bpenhance: out_col + fea_dim exceeds layersizes[last]\n"); exit(0); }
 
     // ---- inputs (all read and checked before the device is used)
@@ -246,6 +253,7 @@ int main(int argc, char **argv)
     bp_handle *h = nullptr;
     if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
     if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    if (bp_set_forward(h, forward) != 0) { printf("%s\n", bp_last_error()); exit(0); }
 
     std::vector<float> pcm, out;
     std::vector<int> lens;

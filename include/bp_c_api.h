@@ -111,6 +111,25 @@ int bp_set_hyper(bp_handle *h, float lrate, float momentum, float weightcost, in
  * non-zero linear_cols or loss with activation 0, null handle) return BP_ERR_ARG and leave the handle unchanged. */
 int bp_set_output(bp_handle *h, int activation, int linear_cols, int loss);
 
+/* The kernels of the INFERENCE forward: bp_forward[_windows], bp_enhance_waves, bp_eval_mix (and the forward of the mixing calls
+ * that score the net) and the pushes of streams opened afterwards.  bp_train_*, bp_cv_*, bp_grads_resident, bp_profile_step and
+ * bp_eval_mix_logmmse are the same in either mode.
+ * BP_FORWARD_DEFAULT (0, the default): the step's forward GEMMs, today's bits.  There a frame's output can differ in the last
+ *   bit with the row of the bunch it sits in.
+ * BP_FORWARD_ROWINV (1): one thin-M kernel per layer (bp_infer.hip) whose summation order is fixed by the layer's shape alone.  A
+ *   frame's output row is a function of the bits of its stacked input row, the weights and biases, dropoutflag and the omit
+ *   rates, the hidden activation and the bp_set_output setting -- and of nothing else: not of the row's index in the chunk, the
+ *   number of rows of the call, the handle's bunchsize or max_chunk_frames, what other rows hold, or the entry point.  The same
+ *   bits on every run (no float atomics).  Against the default mode only the summation order differs (the same activation and
+ *   output arithmetic).  On thousands of frames it runs bunch by bunch and is slower than the default.
+ * A stream keeps the mode its handle had at bp_stream_open: one opened in ROWINV packs the frames of a push densely, in channel
+ * order, so that a push of n frames costs ceil(n / bunchsize) bunches however many channels there are, and returns the bits of
+ * bp_enhance_waves in ROWINV mode.  A later bp_set_forward does not change open streams.
+ * fp32 handles (compute_dtype = 0): ROWINV on a bf16 handle returns BP_ERR_ARG.  A bad mode or a null handle returns BP_ERR_ARG;
+ * the handle is unchanged after an error. */
+enum { BP_FORWARD_DEFAULT = 0, BP_FORWARD_ROWINV = 1 };
+int bp_set_forward(bp_handle *h, int mode);
+
 /* BP_GPU::train (BP_GPU.cu:241-331): upload a chunk of n_frames stacked input frames and
  * targets, then run one SGD-momentum step (train_bunch_single, BP_GPU.cu:484-673) per
  * consecutive full bunch; the partial last bunch is ignored (:315-318).  Synchronous with
@@ -388,6 +407,8 @@ int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream **out);
 int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, const unsigned char *end, int *n_out, float *out_pcm,
                    size_t out_cap);
 int bp_stream_close(bp_stream *s);
+/* 1 for a stream opened while its handle was in BP_FORWARD_ROWINV (it packs its channels, bp_set_forward), else 0 (null: 0) */
+int bp_stream_packed(const bp_stream *s);
 int bp_stream_counts(int fea_dim, int context, int targ_offset, int nat, int64_t received, int ended, int64_t *frames_in,
                      int64_t *frames_out, int64_t *samples_out);
 
