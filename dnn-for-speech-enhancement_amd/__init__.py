@@ -6,5 +6,6 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      Rendezvous, device_count, device_pci_bus_id, wave_lps, WAVE_LPS, WAVE_MASK, FORWARD_DEFAULT, FORWARD_ROWINV,
                      BPWaveChunk, BPMixCorpus, MIXTURE_DTYPE, MIX_TARGETS, MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM,
                      MIX_LPS_IBM, mix_plan, mix_shuffle, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
-                     BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves)
+                     BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
+                     LogmmseStream, logmmse_stream_open, logmmse_stream_counts)
 from .weights_init import glorot_net  # noqa: F401

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "bp_score_waves", "bp_eval_mix",
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
+    "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
@@ -161,6 +162,10 @@ def load_library(path=None):
     lib.bp_stream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
     lib.bp_stream_close.argtypes = [C.c_void_p]
     lib.bp_stream_counts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
+    lib.bp_lmstream_open.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.bp_lmstream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
+    lib.bp_lmstream_close.argtypes = [C.c_void_p]
+    lib.bp_lmstream_counts.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -771,6 +776,80 @@ def logmmse_waves(device, fea_dim, sentences, params=None, return_gain=False, re
     if return_vad:
         res.append(np.split(vad[:T], np.cumsum(frames)[:-1]))
     return res[0] if len(res) == 1 else tuple(res)
+
+
+class LogmmseStream(object):
+    """A log-MMSE stream (bp_lmstream_*): n_chan live feeds enhanced by the classic baseline in blocks of any sizes; no handle."""
+
+    def __init__(self, lib, s, fea_dim, init_frames, n_chan):
+        self._lib, self._s = lib, s
+        self.fea_dim, self.init_frames, self.n_chan = fea_dim, init_frames, n_chan
+
+    def push(self, blocks, end=None, out_cap=None):
+        """blocks: one 1-D array of new samples per channel (None or empty: none); end: per channel, true closes the channel's
+        sentence after these samples.  Returns one float32 array per channel: the samples that became final.  out_cap: size of
+        the output buffer in samples (default: everything a push of this size can return)."""
+        if self._s is None:
+            raise BPError("LogmmseStream.push: the stream is closed")
+        if len(blocks) != self.n_chan or (end is not None and len(end) != self.n_chan):
+            raise BPError("LogmmseStream.push: need one block (and one end flag) per channel (%d)" % self.n_chan)
+        arrs = [np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
+        n_in = np.array([a.size for a in arrs], np.int32)
+        pcm = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(0, np.float32)
+        e = None if end is None else np.ascontiguousarray([1 if v else 0 for v in end], dtype=np.uint8)
+        if out_cap is None:     # what waited for the noise start (fewer than init_frames + 1 hops) and what arrived
+            out_cap = int(pcm.size) + self.n_chan * (self.init_frames + 1) * (self.fea_dim - 1)
+        out = np.empty(max(int(out_cap), 1), np.float32)
+        n_out = np.zeros(self.n_chan, np.int32)
+        ip = C.POINTER(C.c_int)
+        rc = self._lib.bp_lmstream_push(self._s, n_in.ctypes.data_as(ip), _fp(pcm) if pcm.size else None,
+                                        None if e is None else e.ctypes.data_as(C.POINTER(C.c_ubyte)), n_out.ctypes.data_as(ip),
+                                        _fp(out), int(out_cap))
+        if rc != 0:
+            raise BPError("%s (status %d)" % (self._lib.bp_last_error().decode(), rc))
+        return [a.copy() for a in np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])]
+
+    def close(self):
+        if self._s is not None:
+            self._lib.bp_lmstream_close(self._s)
+        self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def logmmse_stream_open(device, fea_dim, params=None, n_chan=1, max_push_samples=16000):
+    """bp_lmstream_open: a LogmmseStream of n_chan channels on a device ordinal (params as for logmmse_waves)."""
+    lib = load_library()
+    lm = logmmse_params(params)
+    s = C.c_void_p()
+    rc = lib.bp_lmstream_open(int(device), int(fea_dim), None if lm is None else C.byref(lm), int(n_chan), int(max_push_samples), C.byref(s))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    if lm is None:
+        lm = BPLogmmseParams()
+        lib.bp_logmmse_defaults(C.byref(lm))
+    return LogmmseStream(lib, s, int(fea_dim), int(lm.init_frames), int(n_chan))
+
+
+def logmmse_stream_counts(fea_dim, init_frames, received, ended):
+    """bp_lmstream_counts: (frames_in, frames_out, samples_out) of a channel after `received` samples of its sentence; host only."""
+    lib = load_library()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.bp_lmstream_counts(int(fea_dim), int(init_frames), int(received), 1 if ended else 0, C.byref(a), C.byref(b), C.byref(c))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def score_waves(device, fea_dim, sample_rate, refs, ests):

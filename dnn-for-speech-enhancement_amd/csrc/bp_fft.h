@@ -67,14 +67,16 @@ __device__ __forceinline__ void rfft_frame(float2 *z, const float *__restrict__ 
 }
 
 // split step: X[k] = E[k] + W^k O[k], E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i, k = 0 .. M
+// (the contraction is spelled out, as in overlap4: left to itself the compiler folds the halving of E and one product of W^k O
+// into the sums in the analysis kernels, and folds neither where the call sits in other code; every caller must return these bits)
 __device__ __forceinline__ float2 rfft_bin(const float2 *z, const float2 *__restrict__ tw, int M, int k)
 {
+#pragma clang fp contract(off)
     const float2 zk = z[lp(k & (M - 1))], zm = z[lp((M - k) & (M - 1))];
-    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
     const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
     return k == 0 ? make_float2(zk.x + zk.y, 0.0f) : k == M ? make_float2(zk.x - zk.y, 0.0f)
-                                                          : make_float2(e.x + (tw[k].x * o.x - tw[k].y * o.y),
-                                                                        e.y + (tw[k].x * o.y + tw[k].y * o.x));
+                                                          : make_float2(fmaf(zk.x + zm.x, 0.5f, fmaf(o.x, tw[k].x, -(o.y * tw[k].y))),
+                                                                        fmaf(zk.y - zm.y, 0.5f, fmaf(o.x, tw[k].y, o.y * tw[k].x)));
 }
 
 // the LPS of one bin's power, with the 1e-10 floor

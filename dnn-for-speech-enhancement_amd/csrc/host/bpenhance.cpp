@@ -8,7 +8,7 @@
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
 //             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
-//             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6]
+//             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6] [lm_stream_block=<samples> [lm_stream_chan=<n>]]
 //
 // As many sentences go into one call as fit traincache rows (frames + context-1 replicated edge rows per sentence).  The
 // output is PCM16 at the input's sample rate, rounded to nearest and clipped.  Every input is read and checked before the
@@ -19,6 +19,9 @@
 // INTEGRATION.md 1i; fp32): a sentence's bytes then do not depend on what else went into its call, and a streaming session packs
 // its channels.  method=logmmse is the classic baseline instead of a net (bp_logmmse_waves,
 // INTEGRATION.md 1h): no weights, no norm file; it takes only the keys of its line above, and the lm_ keys only go with it.
+// With lm_stream_block the files go through a log-MMSE stream (bp_lmstream_push) by the rules of stream_block:
+// file s to channel s mod lm_stream_chan, lm_stream_block samples per push, the end flag on a file's last block; the output
+// files hold the bytes of a run without the key.
 // Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
 #include <stdlib.h>
@@ -101,6 +104,61 @@ static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, co
     return 1;
 }
 
+// method=logmmse lm_stream_block=...: channel c plays files c, c + chan, ... one after the other through a log-MMSE stream
+static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params &lm, int block, int chan, const std::vector<std::string> &ins,
+                               const std::vector<std::string> &outs)
+{
+    const int ns = (int)ins.size(), hop = fea_dim - 1;
+    std::vector<std::vector<float>> waves(ns), enh(ns);
+    std::vector<int> rates(ns);
+    for (int s = 0; s < ns; ++s) {
+        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
+        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+    }
+    bp_lmstream *st = nullptr;
+    if (bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    std::vector<int> file(chan), n_in(chan), n_out(chan);
+    std::vector<size_t> pos(chan, 0);
+    std::vector<unsigned char> end(chan);
+    // a push returns what arrived plus what waited for the noise start or for the end of the sentence
+    std::vector<float> pcm, out((size_t)chan * ((size_t)block + ((size_t)lm.init_frames + 1) * hop));
+    size_t samples = 0;
+    for (int c = 0; c < chan; ++c) file[c] = c;
+    for (;;) {
+        pcm.clear();
+        bool any = false;
+        for (int c = 0; c < chan; ++c) {
+            n_in[c] = 0; end[c] = 0;
+            if (file[c] >= ns) continue;
+            const std::vector<float> &w = waves[file[c]];
+            n_in[c] = (int)std::min((size_t)block, w.size() - pos[c]);
+            end[c] = pos[c] + n_in[c] == w.size();
+            pcm.insert(pcm.end(), w.begin() + pos[c], w.begin() + pos[c] + n_in[c]);
+            any = true;
+        }
+        if (!any) break;
+        if (bp_lmstream_push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        size_t off = 0;
+        for (int c = 0; c < chan; ++c) {
+            if (file[c] >= ns) continue;
+            enh[file[c]].insert(enh[file[c]].end(), out.begin() + off, out.begin() + off + n_out[c]);
+            off += n_out[c];
+            pos[c] += n_in[c];
+            if (end[c]) { file[c] += chan; pos[c] = 0; }
+        }
+        samples += pcm.size();
+    }
+    bp_lmstream_close(st);
+    for (int s = 0; s < ns; ++s) {
+        if (enh[s].size() != waves[s].size()) { printf("%s: the stream returned %zu of %zu samples\n", ins[s].c_str(), enh[s].size(), waves[s].size()); exit(0); }
+        const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
+        if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+    }
+    printf("bpenhance: %zu samples of %d sentences enhanced (logmmse, streamed)\n", samples, ns);
+    return 1;
+}
+
 int main(int argc, char **argv)
 {
     std::string norm_file, wts_file, list, in_wav, out_wav;
@@ -110,7 +168,8 @@ int main(int argc, char **argv)
     bp_logmmse_defaults(&lm);
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
-    int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT;
+    int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1;
+    bool lm_chan_given = false;
     float vis = 0.f, hid = 0.f;
     for (int i = 1; i < argc; ++i) {
         char *eq = strchr(argv[i], '=');
@@ -120,6 +179,11 @@ int main(int argc, char **argv)
         if (k == "method") {
             if (v == "net") logmmse = false; else if (v == "logmmse") logmmse = true;
             else { printf("method: %s is not net or logmmse\n", v.c_str()); exit(0); }
+        } else if (k == "lm_stream_block" || k == "lm_stream_chan") {
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 1 || n > (1 << 24)) { printf("%s: %s is not a count >= 1\n", k.c_str(), v.c_str()); exit(0); }
+            if (k == "lm_stream_block") lm_block = (int)n; else { lm_chan = (int)n; lm_chan_given = true; }
         } else if (k.compare(0, 3, "lm_") == 0) {
             char *end = nullptr;
             const double d = strtod(v.c_str(), &end);
@@ -183,7 +247,7 @@ int main(int argc, char **argv)
         const bool lm_key = k.compare(0, 3, "lm_") == 0;
         if (!logmmse && lm_key) { printf("bpenhance: %s needs method=logmmse\n", k.c_str()); exit(0); }
         if (logmmse && !lm_key && k != "method" && k != "fea_dim" && k != "device" && k != "wav_list" && k != "in_wav" && k != "out_wav") {
-            printf("bpenhance: method=logmmse takes no %s (only fea_dim, device, wav_list or in_wav and out_wav, and the lm_ keys)\n", k.c_str());
+            printf("bpenhance: method=logmmse takes no %s (only fea_dim, device, wav_list or in_wav and out_wav, and the lm_ keys, lm_stream_block and lm_stream_chan among them)\n", k.c_str());
             exit(0);
         }
     }
@@ -191,8 +255,11 @@ int main(int argc, char **argv)
         if (list.empty() == (in_wav.empty() || out_wav.empty())) { printf("bpenhance: need wav_list, or in_wav and out_wav\n"); exit(0); }
         const int nf = 2 * (fea_dim - 1);
         if (fea_dim < 33 || fea_dim > 1025 || (nf & (nf - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
+        if (lm_chan_given && lm_block < 1) { printf("bpenhance: lm_stream_chan needs lm_stream_block\n"); exit(0); }
+        if (lm_block > 0 && ((long)lm_block * lm_chan > (1L << 28) || lm_chan > (1 << 16))) { printf("bpenhance: lm_stream_block * lm_stream_chan is too large\n"); exit(0); }
         std::vector<std::string> li, lo;
         read_wav_list(list, in_wav, out_wav, li, lo);
+        if (lm_block > 0) return logmmse_stream_mode(fea_dim, device, lm, lm_block, lm_chan, li, lo);
         return logmmse_mode(fea_dim, device, lm, li, lo);
     }
     if (L < 2 || L > MAXLAYER - 1 || fea_dim < 1 || ctx < 1 || toff < 0 || toff >= ctx || cache < 1 || cache > MAXCACHEFRAME || bunch < 1) {

@@ -413,6 +413,47 @@ int bp_stream_counts(int fea_dim, int context, int targ_offset, int nat, int64_t
                      int64_t *frames_out, int64_t *samples_out);
 
 /* ------------------------------------------------------------------------------------
+ * Log-MMSE streams: the classic baseline on audio that is still arriving (no reference counterpart).  INTEGRATION.md 1j.  A
+ * log-MMSE stream has no handle and no net: it is opened on a device ordinal, as bp_logmmse_waves is called on one, and a
+ * sentence pushed in blocks of ANY sizes, on any channel, in any company, returns the same bits as
+ * bp_logmmse_waves(device, fea_dim, p, 1, ...) on the finished sentence.
+ *
+ * Channels, pushes and ends are those of bp_stream_push: n_in[ch] >= 0 new samples per channel, back to back in channel order in
+ * pcm; end[ch] != 0 (end may be NULL) closes the channel's sentence after these samples; n_out[ch] and out_pcm return the samples
+ * that became final.  After end the channel has returned exactly as many samples as it received, and its next push starts a new
+ * sentence from a fresh noise start; end on a channel that has received nothing is a no-op.
+ *
+ * bp_lmstream_counts (host only) is bp_stream_counts with look-ahead 0 and the noise start in place of the noise-aware row.
+ * hop = fea_dim - 1, T = (received - 1)/hop + 2 (0 when nothing was received):
+ *   frames_in  = ended ? T : received / hop
+ *   the noise start (the mean power of the sentence's first min(init_frames, T) frames) is known once frames_in >= init_frames,
+ *   or at the end
+ *   frames_out = 0 until then, after that ended ? T : frames_in
+ *   samples_out = ended ? received : max(0, frames_out - 1) hop
+ * A push returns samples_out(after) - samples_out(before) per channel; the latency of a live feed is one hop plus the block, and
+ * init_frames hops at the start of a sentence (until the noise start is known the samples wait on the host).
+ *
+ * Every argument is checked before the device or the stream's state is touched; after an error the stream continues as if the
+ * call had not happened.  BP_ERR_ARG: the checks of bp_logmmse_waves (fea_dim, the parameter ranges, the device ordinal), n_chan
+ * outside 1 .. 65536, max_push_samples < 1, a negative n_in, sum(n_in) > max_push_samples, a null pcm or out_pcm that is needed,
+ * out_cap smaller than the samples due (bp_lmstream_counts: received < 0, a null output, init_frames < 1).  BP_ERR_NOMEM when the
+ * allocations of bp_lmstream_open fail, or when one push could hold 2^31 samples.  Everything is allocated at open; per channel
+ * that is 2 fea_dim doubles and hop floats of device state, (init_frames + 4) hop floats in each of the push's input block (device
+ * and pinned host) and its output block (the same), and (init_frames + 2) hop floats of host carry; besides max_push_samples
+ * floats in each of the four blocks.  A push that gives some channel a new output frame makes one host->device copy, ONE kernel
+ * launch (one workgroup per such channel takes its new frames from PCM to PCM), one device->host copy and one synchronisation; a
+ * push that gives none does not touch the device.  No float atomics: the same bits on every run.  The stream owns a non-blocking
+ * HIP stream of its own; bp_lmstream_close is its only release (NULL: BP_OK).  Other calls on the device between pushes --
+ * bp_logmmse_waves, a handle's training or enhancement, other streams -- disturb neither the stream nor themselves. */
+typedef struct bp_lmstream bp_lmstream;
+int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params *p, int n_chan, int max_push_samples, bp_lmstream **out);
+int bp_lmstream_push(bp_lmstream *s, const int *n_in, const float *pcm, const unsigned char *end, int *n_out, float *out_pcm,
+                     size_t out_cap);
+int bp_lmstream_close(bp_lmstream *s);
+int bp_lmstream_counts(int fea_dim, int init_frames, int64_t received, int ended, int64_t *frames_in, int64_t *frames_out,
+                       int64_t *samples_out);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias
