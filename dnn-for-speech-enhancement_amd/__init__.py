@@ -5,7 +5,8 @@
 from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMBOLS, MAXLAYER, MAXCACHEFRAME,  # noqa: F401
                      Rendezvous, device_count, device_pci_bus_id, wave_lps, WAVE_LPS, WAVE_MASK, FORWARD_DEFAULT, FORWARD_ROWINV,
                      BPWaveChunk, BPMixCorpus, MIXTURE_DTYPE, MIX_TARGETS, MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM,
-                     MIX_LPS_IBM, mix_plan, mix_shuffle, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
+                     MIX_LPS_IBM, mix_plan, mix_shuffle, BPMixReverb, REVERB_TARGETS, REVERB_TARGET_REVERBERANT,
+                     REVERB_TARGET_EARLY, MIX_RIR_MAX_TAPS, reverb_waves, rir_delay, mix_reverb_pairs, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
                      LogmmseStream, logmmse_stream_open, logmmse_stream_counts)
 from .weights_init import glorot_net  # noqa: F401

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "bp_profile_step", "bp_measure_peaks", "bp_device_count", "bp_train_resident_masked", "bp_forward_windows",
     "bp_enhance_waves", "bp_wave_lps",
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
+    "bp_set_mix_reverb", "bp_reverb_waves", "bp_mix_rir_delay", "bp_mix_reverb_pairs",
     "bp_score_waves", "bp_eval_mix",
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
@@ -47,6 +48,9 @@ WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
+REVERB_TARGET_REVERBERANT, REVERB_TARGET_EARLY = 0, 1   # bp_mix_reverb.target
+REVERB_TARGETS = {"reverberant": REVERB_TARGET_REVERBERANT, "early": REVERB_TARGET_EARLY}
+MIX_RIR_MAX_TAPS = 65536
 MIX_TARGETS = {"lps": MIX_LPS, "irm": MIX_IRM, "ibm": MIX_IBM, "lps+irm": MIX_LPS_IRM, "lps+ibm": MIX_LPS_IBM}
 # bp_mixture: a numpy structured array of this dtype is a mixture plan
 MIXTURE_DTYPE = np.dtype({"names": ["clean", "noise", "offset", "snr_db"], "formats": [np.int32, np.int32, np.int64, np.float32],
@@ -84,6 +88,15 @@ class BPMixCorpus(C.Structure):
         ("mean", C.POINTER(C.c_float)), ("inv_std", C.POINTER(C.c_float)),
         ("n_clean", C.c_int), ("clean_len", C.POINTER(C.c_int64)), ("clean_pcm", C.POINTER(C.c_float)),
         ("n_noise", C.c_int), ("noise_len", C.POINTER(C.c_int64)), ("noise_pcm", C.POINTER(C.c_float)),
+    ]
+
+
+class BPMixReverb(C.Structure):
+    """bp_mix_reverb (include/bp_c_api.h): impulse responses and the {clean, response} pairs that become derived entries."""
+    _fields_ = [
+        ("n_rir", C.c_int), ("rir_len", C.POINTER(C.c_int)), ("rir_pcm", C.POINTER(C.c_float)),
+        ("n_pair", C.c_int), ("pair_clean", C.POINTER(C.c_int)), ("pair_rir", C.POINTER(C.c_int)),
+        ("target", C.c_int), ("early_taps", C.c_int),
     ]
 
 
@@ -153,6 +166,11 @@ def load_library(path=None):
     lib.bp_mix_features.argtypes = [hp, C.c_int, C.c_void_p, fp, fp, fp, fp, fp]
     lib.bp_mix_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, fp, C.c_void_p]
     lib.bp_mix_shuffle.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
+    ip = C.POINTER(C.c_int)
+    lib.bp_set_mix_reverb.argtypes = [hp, C.POINTER(BPMixReverb)]
+    lib.bp_reverb_waves.argtypes = [C.c_int, C.c_int, ip, fp, ip, C.c_int, ip, fp, C.c_int, fp, fp]
+    lib.bp_mix_rir_delay.argtypes = [fp, C.c_int, ip]
+    lib.bp_mix_reverb_pairs.argtypes = [C.c_uint64, C.c_int, C.c_int, ip]
     lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
     lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
     lib.bp_logmmse_defaults.argtypes = [C.POINTER(BPLogmmseParams)]
@@ -457,6 +475,28 @@ class BP_GPU(object):
         self._check(self._lib.bp_set_mix_corpus(self._h, C.byref(c)))
         self.mix_fea_dim, self.mix_clean_len = mean.size, clen
         self.mix_nat = self.layersizes[0] == (int(context) + 1) * mean.size
+        self.mix_n_clean, self.mix_reverb_entries = len(cl), 0
+
+    def set_mix_reverb(self, rirs, pair_clean, pair_rir, target="reverberant", early_taps=0):
+        """bp_set_mix_reverb: pair k = (clean sentence pair_clean[k], response rirs[pair_rir[k]]) becomes clean entry n_clean + k
+        of the corpus; target: "reverberant" | "early" (REVERB_TARGETS) or the number; replaces the entries of an earlier call."""
+        target = REVERB_TARGETS[target] if isinstance(target, str) else int(target)
+        hs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in rirs]
+        hlen = np.array([x.size for x in hs], np.int32)
+        hpcm = np.ascontiguousarray(np.concatenate(hs) if hs else np.zeros(0, np.float32))
+        pc = np.ascontiguousarray(pair_clean, dtype=np.int32).reshape(-1)
+        pr = np.ascontiguousarray(pair_rir, dtype=np.int32).reshape(-1)
+        if pc.size != pr.size:
+            self._fail("set_mix_reverb: pair_clean and pair_rir differ in length")
+        ip = C.POINTER(C.c_int)
+        r = BPMixReverb()
+        r.n_rir, r.rir_len, r.rir_pcm = len(hs), hlen.ctypes.data_as(ip), _fp(hpcm)
+        r.n_pair, r.pair_clean, r.pair_rir = pc.size, pc.ctypes.data_as(ip), pr.ctypes.data_as(ip)
+        r.target, r.early_taps = target, int(early_taps)
+        self._check(self._lib.bp_set_mix_reverb(self._h, C.byref(r)))
+        n = self.mix_n_clean
+        self.mix_clean_len = np.concatenate([self.mix_clean_len[:n], self.mix_clean_len[:n][pc]])
+        self.mix_reverb_entries = int(pc.size)
 
     def _plan(self, plan):
         p = np.ascontiguousarray(plan, dtype=MIXTURE_DTYPE).reshape(-1)
@@ -872,6 +912,52 @@ def score_waves(device, fea_dim, sample_rate, refs, ests):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return out[:len(r)]
+
+
+def reverb_waves(device, sents, sent_rir, rirs, early_taps=0, early=True):
+    """bp_reverb_waves: (rev, early) lists of the reverberant sentences and their direct-plus-early parts (None for early=False):
+    sentence k convolved with rirs[sent_rir[k]], aligned to the direct path (include/bp_c_api.h).  No handle."""
+    lib = load_library()
+    ss = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in sents]
+    hs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in rirs]
+    slen = np.array([x.size for x in ss], np.int32)
+    hlen = np.array([x.size for x in hs], np.int32)
+    sr = np.ascontiguousarray(sent_rir, dtype=np.int32).reshape(-1)
+    if sr.size != len(ss):
+        raise BPError("reverb_waves: %d sentences but %d response indices" % (len(ss), sr.size))
+    spcm = np.ascontiguousarray(np.concatenate(ss) if ss else np.zeros(0, np.float32))
+    hpcm = np.ascontiguousarray(np.concatenate(hs) if hs else np.zeros(0, np.float32))
+    n = int(slen.sum())
+    rev = np.empty(max(n, 1), np.float32)
+    ear = np.empty(max(n, 1), np.float32) if early else None
+    ip = C.POINTER(C.c_int)
+    rc = lib.bp_reverb_waves(int(device), len(ss), slen.ctypes.data_as(ip), _fp(spcm), sr.ctypes.data_as(ip), len(hs),
+                             hlen.ctypes.data_as(ip), _fp(hpcm), int(early_taps), _fp(rev), _fp(ear) if early else None)
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    cut = np.cumsum(slen)[:-1]
+    return np.split(rev[:n], cut), (np.split(ear[:n], cut) if early else None)
+
+
+def rir_delay(h):
+    """bp_mix_rir_delay: the first index at which |h[j]| is largest; host only."""
+    lib = load_library()
+    h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+    d = C.c_int()
+    rc = lib.bp_mix_rir_delay(_fp(h) if h.size else None, h.size, C.byref(d))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return int(d.value)
+
+
+def mix_reverb_pairs(seed, n_clean, n_rir):
+    """bp_mix_reverb_pairs: the response of every clean sentence (int32 [n_clean]), keyed by the seed; host only."""
+    lib = load_library()
+    out = np.zeros(max(int(n_clean), 1), np.int32)
+    rc = lib.bp_mix_reverb_pairs(int(seed), int(n_clean), int(n_rir), out.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out[:int(n_clean)]
 
 
 def mix_plan(seed, n_clean, per_clean, noise_lens, snr_list):

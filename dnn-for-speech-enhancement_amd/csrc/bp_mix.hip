@@ -15,6 +15,9 @@
 //   bp_mix_targets   one workgroup per frame: the FFTs of s and g v in LDS, one after the other, and the frame's target row
 //   bp_wave_nat      (bp_wave.hip) the noise-aware rows
 //   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
+//   bp_mix_reverb_fir  (bp_set_mix_reverb, once per call, not per mixture) clean sentences convolved with room impulse responses:
+//                    the derived entries n_clean + k of the corpus; bp_mix_gain and bp_mix_pcm read an
+//                    entry's mixing signal, bp_mix_pcm writes its target signal into s
 // bp_eval_mix runs the same sequence without the targets, keeps the noisy spectrum Y, then bp_enhance_waves'
 // forward / synthesis / overlap-add on it and the scoring kernels of bp_eval.hip (bp_eval.h) on s, x and the enhanced samples.
 // bp_eval_mix_logmmse is the same call with the log-MMSE recursion of bp_classic.hip (bp_classic.h) in place of
@@ -34,14 +37,26 @@
 
 namespace {
 
+// one derived (reverberant) entry, or one sentence of bp_reverb_waves: n outputs at dst from the n source samples at src and the
+// Lh taps at rir (delay d, early sum up to tap je); blk0: its first workgroup of bp_mix_reverb_fir
+struct ReverbJob { int64_t src, dst, rir; int n, Lh, d, je, blk0, pad; };
+
 struct MixArgs {
     const float *clean, *noise;                                  // the corpus, back to back
     const int64_t *clean_off, *clean_len, *noise_off, *noise_len;
+    const float *rev, *rev_t; const ReverbJob *rjob; int n_clean;   // derived entries n_clean + k: mixing and target signals at rjob[k].dst
     const int *Fs, *mc, *mn; const int64_t *mo; const float *msnr;  // per mixture
     int n_mix, hop;
     float *gain;                                                 // [n_mix]
     float *x, *s, *v;                                            // padded [Fs[n_mix] hop]
 };
+
+// clean entry c: its mixing signal, its target signal (the same samples for a dry entry) and its length
+__device__ __forceinline__ void mix_entry(const MixArgs &a, int c, const float *&sm, const float *&st, int64_t &len)
+{
+    if (c < a.n_clean) { sm = st = a.clean + a.clean_off[c]; len = a.clean_len[c]; }
+    else { const ReverbJob &j = a.rjob[c - a.n_clean]; sm = a.rev + j.dst; st = a.rev_t + j.dst; len = j.n; }
+}
 
 }  // namespace
 
@@ -50,8 +65,11 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_gain(const MixArgs a)
     __shared__ double es[WAVE_THREADS], ev[WAVE_THREADS];
     const int m = blockIdx.x, tid = threadIdx.x;
     const int c = a.mc[m], n = a.mn[m];
-    const int64_t lc = a.clean_len[c], ln = a.noise_len[n], step = WAVE_THREADS % ln;
-    const float *cs = a.clean + a.clean_off[c], *ns = a.noise + a.noise_off[n];
+    const float *cs, *ts; int64_t lc;
+    mix_entry(a, c, cs, ts, lc);
+    (void)ts;                                                    // (E_s is the mixing signal's)
+    const int64_t ln = a.noise_len[n], step = WAVE_THREADS % ln;
+    const float *ns = a.noise + a.noise_off[n];
     double s2 = 0.0, v2 = 0.0;
     int64_t p = (a.mo[m] + tid) % ln;                            // noise sample of clean sample i = tid, tid + 256, ...
     for (int64_t i = tid; i < lc; i += WAVE_THREADS) {
@@ -75,8 +93,10 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_pcm(const MixArgs a)
 {
     const int q = blockIdx.x, m = sentence_of(a.Fs, a.n_mix, q);
     const int c = a.mc[m], n = a.mn[m];
-    const int64_t lc = a.clean_len[c], ln = a.noise_len[n], o = a.mo[m];
-    const float *cs = a.clean + a.clean_off[c], *ns = a.noise + a.noise_off[n];
+    const float *cs, *ts; int64_t lc;                            // mixing and target signal (one pointer for a dry entry)
+    mix_entry(a, c, cs, ts, lc);
+    const int64_t ln = a.noise_len[n], o = a.mo[m];
+    const float *ns = a.noise + a.noise_off[n];
     const float g = a.gain[m];
     const int64_t i0 = (int64_t)(q - a.Fs[m] - 1) * a.hop;     // mixture sample at the segment's first position (front pad: hop)
     for (int r = threadIdx.x; r < a.hop; r += blockDim.x) {
@@ -84,7 +104,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_pcm(const MixArgs a)
         float xv = 0.0f, sv = 0.0f, vv = 0.0f;
         if (i >= 0 && i < lc) {
             const float s = cs[i], v = ns[(o + i) % ln];
-            xv = fmaf(g, v, s); sv = s; vv = g * v;
+            xv = fmaf(g, v, s); sv = ts[i]; vv = g * v;
         }
         const size_t d = (size_t)q * a.hop + r;
         a.x[d] = xv; a.s[d] = sv; a.v[d] = vv;
@@ -138,13 +158,110 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_tables(const int *__restr
     if (nr) nr[i] = m;
 }
 
+// ------------------------------------------------------------------ reverberant entries
+// bp_mix_reverb_fir: r[i] = fl32(sum_j (double)h[j] (double)s[i + d - j]), j ascending, one double accumulator per output sample (the
+// order over j is the definition: no tap of a sample is ever added by another thread).  A workgroup owns RV_BLOCK consecutive
+// outputs of one job, a thread RV_R consecutive ones.  Per tile of RV_TILE taps the workgroup stages, already converted to double,
+// the taps and the RV_BLOCK + RV_TILE source samples the tile touches; a thread then walks the tile 8 taps at a time with the 15
+// source samples those 8 taps x 8 outputs need held in registers (8 new ones per step, one aligned chunk of the segment).  The
+// segment is stored with 2 doubles of padding after every 8, which makes the lanes' 64-byte chunks 80 bytes apart: every 16-lane
+// group of a ds_read_b128 then covers all 64 banks once.  Taps are read as broadcasts.  Tiles whose samples all lie outside
+// [0, n) add exact zeros and are skipped.  EARLY: the accumulators are also copied when tap je has been added.
+namespace {
+constexpr int RV_R = 8, RV_BLOCK = WAVE_THREADS * RV_R, RV_TILE = WAVE_THREADS;
+static_assert(RV_R == 8 && RV_TILE % 8 == 0, "the inner step is 8 taps x 8 outputs");
+struct ReverbArgs { const ReverbJob *job; int n_job; const float *src, *rir; float *out_r, *out_e; };
+
+__device__ __forceinline__ int rv_pad(int k) { return k + ((k >> 3) << 1); }
+
+// taps hh[0..7] on outputs 0..7: tap u of output r reads sample 7 - u + r of cur (0..7) | prev (8..14); jl: the tap after which the
+// accumulators are copied (SNAP), else unused
+template <bool SNAP>
+__device__ __forceinline__ void rv_step(double (&acc)[RV_R], double (&snap)[RV_R], const double (&hh)[8], const double (&cur)[8],
+                                        const double (&prev)[8], int jl)
+{
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+#pragma unroll
+        for (int r = 0; r < RV_R; ++r) {
+            const int k = 7 - u + r;
+            acc[r] = fma(hh[u], k < 8 ? cur[k] : prev[k - 8], acc[r]);
+        }
+        if (SNAP && u == jl) {
+#pragma unroll
+            for (int r = 0; r < RV_R; ++r) snap[r] = acc[r];
+        }
+    }
+}
+}  // namespace
+
+template <bool EARLY>
+__global__ __launch_bounds__(WAVE_THREADS) void bp_mix_reverb_fir(const ReverbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double seg[(RV_BLOCK + RV_TILE) / 8 * 10];
+    __shared__ __attribute__((aligned(16))) double tap[RV_TILE];
+    const int q = blockIdx.x, tid = threadIdx.x, o0 = tid * RV_R;
+    int lo = 0, hi = a.n_job - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.job[mid].blk0 <= q) lo = mid; else hi = mid - 1; }
+    const ReverbJob J = a.job[lo];
+    const float *s = a.src + J.src, *h = a.rir + J.rir;
+    const int i0 = (q - J.blk0) * RV_BLOCK, i_last = min(i0 + RV_BLOCK, J.n) - 1;
+    // tile t (taps [t RV_TILE, (t+1) RV_TILE)) reads samples [i0 + d - (t+1) RV_TILE + 1, i_last + d - t RV_TILE]: inside [0, n) for
+    // a contiguous range of t only
+    const int nt = (J.Lh + RV_TILE - 1) / RV_TILE, qlo = i0 + J.d - J.n - RV_TILE + 2;
+    const int ta = qlo <= 0 ? 0 : (qlo + RV_TILE - 1) / RV_TILE, tb = min(nt, (i_last + J.d) / RV_TILE + 1);
+    double acc[RV_R], snap[RV_R];
+#pragma unroll
+    for (int r = 0; r < RV_R; ++r) acc[r] = snap[r] = 0.0;
+    for (int t = ta; t < tb; ++t) {
+        const int j0 = t * RV_TILE, base = i0 + J.d - j0 - RV_TILE + 1;
+        __syncthreads();                                         // (the previous tile is read)
+        for (int k = tid; k < RV_BLOCK + RV_TILE; k += WAVE_THREADS) {
+            const int p = base + k;
+            seg[rv_pad(k)] = p >= 0 && p < J.n ? (double)s[p] : 0.0;
+        }
+        tap[tid] = j0 + tid < J.Lh ? (double)h[j0 + tid] : 0.0;
+        __syncthreads();
+        const int ng = (min(RV_TILE, J.Lh - j0) + 7) >> 3, jl = J.je - j0;
+        double prev[8], cur[8], hh[8];
+        {
+            const double *c = seg + rv_pad(o0 + RV_TILE);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) prev[k] = c[k];
+        }
+        for (int g = 0; g < ng; ++g) {
+            const double *c = seg + rv_pad(o0 + RV_TILE - 8 - 8 * g);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { cur[k] = c[k]; hh[k] = tap[8 * g + k]; }
+            if (EARLY && (jl >> 3) == g) rv_step<true>(acc, snap, hh, cur, prev, jl & 7);
+            else rv_step<false>(acc, snap, hh, cur, prev, 0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) prev[k] = cur[k];
+        }
+    }
+    if (EARLY && J.je >= tb * RV_TILE) {                         // (the rest of the early sum was skipped zeros)
+#pragma unroll
+        for (int r = 0; r < RV_R; ++r) snap[r] = acc[r];
+    }
+#pragma unroll
+    for (int r = 0; r < RV_R; ++r) {
+        const int i = i0 + o0 + r;
+        if (i < J.n) {
+            if (a.out_r) a.out_r[J.dst + i] = (float)acc[r];
+            if (EARLY) a.out_e[J.dst + i] = (float)snap[r];
+        }
+    }
+}
+
 // ------------------------------------------------------------------ host side
 struct MixState {
     int D, log2M, M, hop, ctx, toff, target, sL;
     bool nat;
     float thr;
-    int n_clean, n_noise;
-    std::vector<int64_t> clean_len, noise_len;
+    int n_clean, n_noise, n_pair;                                // n_pair: derived entries n_clean .. n_clean + n_pair - 1
+    std::vector<int64_t> clean_len, noise_len;                   // clean_len: [n_clean + n_pair]
+    char *reverb;                                                // device: r | e (early target only) | ReverbJob [n_pair]
+    size_t o_rv_t, o_rv_job;
     char *corpus;                                                // device: clean | noise | offsets and lengths | mean | inv_std | window | twiddles
     size_t o_clean, o_noise, o_cl_off, o_cl_len, o_no_off, o_no_len, o_mean, o_istd, o_win, o_tw;
     bp_handle::Raw in_d, x, s, v, gain, lps;                     // grow-only device buffers of the calls
@@ -167,6 +284,7 @@ void free_state(MixState *ms)
 {
     if (!ms) return;
     if (ms->corpus) (void)hipFree(ms->corpus);
+    if (ms->reverb) (void)hipFree(ms->reverb);
     for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps, &ms->ev_Y, &ms->ev_syn, &ms->ev_ola, &ms->ev_lps,
                               &ms->ev_tab, &ms->ev_work, &ms->ev_gain})
         free_raw(*r, false);
@@ -199,7 +317,7 @@ int plan_call(const bp_handle *h, const char *who, int n_mix, const bp_mixture *
     size_t f = 0;
     for (int i = 0; i < n_mix; ++i) {
         const bp_mixture &x = m[i];
-        if (x.clean < 0 || x.clean >= ms->n_clean) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": clean index out of range");
+        if (x.clean < 0 || x.clean >= ms->n_clean + ms->n_pair) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": clean index out of range");
         if (x.noise < 0 || x.noise >= ms->n_noise) return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": noise index out of range");
         if (x.offset < 0 || x.offset >= ms->noise_len[x.noise])
             return fail(BP_ERR_ARG, std::string(who) + ": mixture " + std::to_string(i) + ": offset outside the noise recording");
@@ -277,6 +395,11 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     a.clean = (const float *)(cp + ms->o_clean); a.noise = (const float *)(cp + ms->o_noise);
     a.clean_off = (const int64_t *)(cp + ms->o_cl_off); a.clean_len = (const int64_t *)(cp + ms->o_cl_len);
     a.noise_off = (const int64_t *)(cp + ms->o_no_off); a.noise_len = (const int64_t *)(cp + ms->o_no_len);
+    a.n_clean = ms->n_clean;
+    if (ms->n_pair) {
+        a.rev = (const float *)ms->reverb; a.rev_t = (const float *)(ms->reverb + ms->o_rv_t);
+        a.rjob = (const ReverbJob *)(ms->reverb + ms->o_rv_job);
+    }
     a.Fs = (const int *)(db + c.o_Fs); a.mc = (const int *)(db + c.o_c); a.mn = (const int *)(db + c.o_n);
     a.mo = (const int64_t *)(db + c.o_o); a.msnr = (const float *)(db + c.o_snr);
     a.n_mix = c.n; a.hop = ms->hop; a.gain = (float *)ms->gain.p;
@@ -616,4 +739,194 @@ extern "C" int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order)
         const int t = order[i]; order[i] = order[j]; order[j] = t;
     }
     return BP_OK;
+}
+
+// ------------------------------------------------------------------ reverberant entries: host side
+namespace {
+
+int rir_delay(const float *h, int n)
+{
+    int d = 0;
+    for (int j = 1; j < n; ++j)
+        if (fabsf(h[j]) > fabsf(h[d])) d = j;
+    return d;
+}
+
+// the responses of a call, checked; off[k]: first tap of response k in rir_pcm, delay[k]
+int check_rirs(const char *who, int n_rir, const int *rir_len, const float *rir_pcm, int early_taps, std::vector<int64_t> &off,
+               std::vector<int> &delay)
+{
+    if (!rir_len || !rir_pcm) return fail(BP_ERR_ARG, std::string(who) + ": null pointer");
+    if (n_rir < 1) return fail(BP_ERR_ARG, std::string(who) + ": need at least one impulse response");
+    if (early_taps < 0) return fail(BP_ERR_ARG, std::string(who) + ": early_taps is negative");
+    off.assign((size_t)n_rir + 1, 0); delay.assign(n_rir, 0);
+    for (int k = 0; k < n_rir; ++k) {
+        if (rir_len[k] < 1 || rir_len[k] > BP_MIX_RIR_MAX_TAPS)
+            return fail(BP_ERR_ARG, std::string(who) + ": impulse response " + std::to_string(k) + ": length outside [1, " +
+                                    std::to_string(BP_MIX_RIR_MAX_TAPS) + "]");
+        off[k + 1] = off[k] + rir_len[k];
+    }
+    for (int k = 0; k < n_rir; ++k) {
+        const float *hh = rir_pcm + off[k];
+        for (int j = 0; j < rir_len[k]; ++j)
+            if (!std::isfinite(hh[j])) return fail(BP_ERR_ARG, std::string(who) + ": impulse response " + std::to_string(k) + ": tap " +
+                                                                   std::to_string(j) + " is not finite");
+        delay[k] = rir_delay(hh, rir_len[k]);
+    }
+    return BP_OK;
+}
+
+constexpr int RV_MAX_LEN = 1 << 30;                              // (sample indices of a sentence are ints on the device)
+
+// job k: n outputs at dst[k] from the sentence at src[k] and response rir[k]; returns the workgroups of the launch
+int64_t fill_jobs(std::vector<ReverbJob> &job, const std::vector<int64_t> &off, const std::vector<int> &delay, const int *rir_len,
+                  int early_taps)
+{
+    int64_t blk = 0, dst = 0;
+    for (ReverbJob &j : job) {
+        const int k = (int)j.rir;                                // (the caller left the response's index here)
+        j.rir = off[k]; j.Lh = rir_len[k]; j.d = delay[k];
+        j.je = (int)std::min<int64_t>((int64_t)j.Lh - 1, (int64_t)j.d + early_taps);
+        j.dst = dst; j.blk0 = (int)blk; j.pad = 0;
+        dst += j.n; blk += (j.n + RV_BLOCK - 1) / RV_BLOCK;
+    }
+    return blk;
+}
+
+hipError_t reverb_launch(const ReverbArgs &a, int64_t blocks, bool early, hipStream_t st)
+{
+    if (early) bp_mix_reverb_fir<true><<<dim3((unsigned)blocks), dim3(WAVE_THREADS), 0, st>>>(a);
+    else bp_mix_reverb_fir<false><<<dim3((unsigned)blocks), dim3(WAVE_THREADS), 0, st>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int bp_mix_rir_delay(const float *h, int n_taps, int *delay)
+{
+    if (!h || !delay) return fail(BP_ERR_ARG, "bp_mix_rir_delay: null pointer");
+    if (n_taps < 1 || n_taps > BP_MIX_RIR_MAX_TAPS) return fail(BP_ERR_ARG, "bp_mix_rir_delay: length outside [1, " + std::to_string(BP_MIX_RIR_MAX_TAPS) + "]");
+    for (int j = 0; j < n_taps; ++j)
+        if (!std::isfinite(h[j])) return fail(BP_ERR_ARG, "bp_mix_rir_delay: tap " + std::to_string(j) + " is not finite");
+    *delay = rir_delay(h, n_taps);
+    return BP_OK;
+}
+
+extern "C" int bp_mix_reverb_pairs(uint64_t seed, int n_clean, int n_rir, int *pair_rir)
+{
+    if (n_clean < 1 || n_rir < 1 || !pair_rir) return fail(BP_ERR_ARG, "bp_mix_reverb_pairs: need n_clean, n_rir >= 1 and a non-null array");
+    for (int c = 0; c < n_clean; ++c) pair_rir[c] = (int)scale(word0(seed, (uint32_t)c, 0, 3), (uint64_t)n_rir);
+    return BP_OK;
+}
+
+extern "C" int bp_set_mix_reverb(bp_handle *h, const bp_mix_reverb *r)
+{
+    if (!h || !r) return fail(BP_ERR_ARG, "bp_set_mix_reverb: null handle or argument");
+    std::vector<int64_t> off;
+    std::vector<int> delay;
+    int rc;
+    if ((rc = check_rirs("bp_set_mix_reverb", r->n_rir, r->rir_len, r->rir_pcm, r->early_taps, off, delay)) != BP_OK) return rc;
+    if (r->n_pair < 1 || !r->pair_clean || !r->pair_rir) return fail(BP_ERR_ARG, "bp_set_mix_reverb: need at least one pair and non-null pair arrays");
+    if (r->target != BP_REVERB_TARGET_REVERBERANT && r->target != BP_REVERB_TARGET_EARLY)
+        return fail(BP_ERR_ARG, "bp_set_mix_reverb: unknown target");
+    for (int k = 0; k < r->n_pair; ++k)
+        if (r->pair_rir[k] < 0 || r->pair_rir[k] >= r->n_rir)
+            return fail(BP_ERR_ARG, "bp_set_mix_reverb: pair " + std::to_string(k) + ": response index out of range");
+    MixState *ms = h->mix;
+    if (!ms) return fail(BP_ERR_STATE, "bp_set_mix_reverb: no corpus (bp_set_mix_corpus)");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_set_mix_reverb: not on an attached data-parallel handle");
+    std::vector<int64_t> coff((size_t)ms->n_clean + 1, 0);
+    for (int i = 0; i < ms->n_clean; ++i) coff[i + 1] = coff[i] + ms->clean_len[i];
+    std::vector<ReverbJob> job(r->n_pair);
+    int64_t tot = 0;
+    for (int k = 0; k < r->n_pair; ++k) {
+        const int c = r->pair_clean[k];
+        if (c < 0 || c >= ms->n_clean) return fail(BP_ERR_ARG, "bp_set_mix_reverb: pair " + std::to_string(k) + ": clean index out of range");
+        if (ms->clean_len[c] > RV_MAX_LEN) return fail(BP_ERR_ARG, "bp_set_mix_reverb: pair " + std::to_string(k) + ": clean sentence too long");
+        job[k].src = coff[c]; job[k].n = (int)ms->clean_len[c]; job[k].rir = r->pair_rir[k];
+        tot += job[k].n;
+    }
+    const bool early = r->target == BP_REVERB_TARGET_EARLY;
+    const int64_t blocks = fill_jobs(job, off, delay, r->rir_len, r->early_taps);
+    if (blocks > INT32_MAX) return fail(BP_ERR_ARG, "bp_set_mix_reverb: too many samples for one call");
+    const size_t sig_b = al256((size_t)tot * 4), o_t = early ? sig_b : 0, o_job = sig_b * (early ? 2 : 1);
+    const size_t bytes = o_job + al256(job.size() * sizeof(ReverbJob)), rir_b = (size_t)off[r->n_rir] * 4;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    char *nd = nullptr, *hd = nullptr;
+    if (hipMalloc((void **)&nd, bytes) != hipSuccess || hipMalloc((void **)&hd, rir_b) != hipSuccess) {
+        (void)hipGetLastError();
+        if (nd) (void)hipFree(nd);
+        return fail(BP_ERR_NOMEM, "bp_set_mix_reverb: hipMalloc (the previous entries stay)");
+    }
+    hipError_t e = hipMemcpyAsync(nd + o_job, job.data(), job.size() * sizeof(ReverbJob), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hd, r->rir_pcm, rir_b, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        ReverbArgs a; memset(&a, 0, sizeof(a));
+        a.job = (const ReverbJob *)(nd + o_job); a.n_job = r->n_pair;
+        a.src = (const float *)(ms->corpus + ms->o_clean); a.rir = (const float *)hd;
+        a.out_r = (float *)nd; a.out_e = early ? (float *)(nd + o_t) : nullptr;
+        e = reverb_launch(a, blocks, early, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);       // (the host arrays are the caller's; earlier calls may read the old entries)
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(hd);
+    if (e != hipSuccess) { (void)hipFree(nd); return fail(BP_ERR_DEVICE, std::string("bp_set_mix_reverb: ") + hipGetErrorString(e)); }
+    if (ms->reverb) (void)hipFree(ms->reverb);
+    ms->reverb = nd; ms->o_rv_t = o_t; ms->o_rv_job = o_job; ms->n_pair = r->n_pair;
+    ms->clean_len.resize(ms->n_clean);
+    for (const ReverbJob &j : job) ms->clean_len.push_back(j.n);
+    return BP_OK;
+}
+
+extern "C" int bp_reverb_waves(int device, int n_sent, const int *sent_len, const float *pcm, const int *sent_rir, int n_rir, const int *rir_len,
+                               const float *rir_pcm, int early_taps, float *out_rev, float *out_early)
+{
+    std::vector<int64_t> off;
+    std::vector<int> delay;
+    int rc;
+    if ((rc = check_rirs("bp_reverb_waves", n_rir, rir_len, rir_pcm, early_taps, off, delay)) != BP_OK) return rc;
+    if (n_sent < 1 || !sent_len || !pcm || !sent_rir) return fail(BP_ERR_ARG, "bp_reverb_waves: need at least one sentence and non-null arrays");
+    if (!out_rev && !out_early) return fail(BP_ERR_ARG, "bp_reverb_waves: both outputs are null");
+    std::vector<ReverbJob> job(n_sent);
+    int64_t tot = 0;
+    for (int k = 0; k < n_sent; ++k) {
+        if (sent_len[k] < 1 || sent_len[k] > RV_MAX_LEN) return fail(BP_ERR_ARG, "bp_reverb_waves: sentence " + std::to_string(k) + ": length outside [1, 2^30]");
+        if (sent_rir[k] < 0 || sent_rir[k] >= n_rir) return fail(BP_ERR_ARG, "bp_reverb_waves: sentence " + std::to_string(k) + ": response index out of range");
+        job[k].src = tot; job[k].n = sent_len[k]; job[k].rir = sent_rir[k];
+        tot += sent_len[k];
+    }
+    const int64_t blocks = fill_jobs(job, off, delay, rir_len, early_taps);
+    if (blocks > INT32_MAX) return fail(BP_ERR_ARG, "bp_reverb_waves: too many samples for one call");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_reverb_waves: device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    // one input block: jobs | sentences | responses; one output block: r | e (whichever are asked for)
+    const bool early = out_early != nullptr;
+    const size_t o_pcm = al256(job.size() * sizeof(ReverbJob)), o_rir = o_pcm + al256((size_t)tot * 4);
+    const size_t in_b = o_rir + al256((size_t)off[n_rir] * 4), sig_b = (size_t)tot * 4, out_b = sig_b * ((out_rev ? 1 : 0) + (early ? 1 : 0));
+    std::vector<char> hb(in_b), ho(out_rev && early ? out_b : 0);
+    memcpy(hb.data(), job.data(), job.size() * sizeof(ReverbJob));
+    memcpy(hb.data() + o_pcm, pcm, sig_b);
+    memcpy(hb.data() + o_rir, rir_pcm, (size_t)off[n_rir] * 4);
+    hipStream_t st = nullptr;
+    char *d = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, in_b + out_b);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        ReverbArgs a; memset(&a, 0, sizeof(a));
+        a.job = (const ReverbJob *)d; a.n_job = n_sent; a.src = (const float *)(d + o_pcm); a.rir = (const float *)(d + o_rir);
+        a.out_r = out_rev ? (float *)(d + in_b) : nullptr;
+        a.out_e = early ? (float *)(d + in_b + (out_rev ? sig_b : 0)) : nullptr;
+        e = reverb_launch(a, blocks, early, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ho.empty() ? (char *)(out_rev ? out_rev : out_early) : ho.data(), d + in_b, out_b, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    rc = BP_OK;
+    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_reverb_waves: ") + hipGetErrorString(e));
+    else if (!ho.empty()) { memcpy(out_rev, ho.data(), sig_b); memcpy(out_early, ho.data() + sig_b, sig_b); }
+    if (d) (void)hipFree(d);
+    if (st) (void)hipStreamDestroy(st);
+    return rc;
 }

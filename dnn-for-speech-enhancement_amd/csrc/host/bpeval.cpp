@@ -5,7 +5,7 @@
 //          targ_offset=5 layersizes=1548,2048,2048,2048,129 [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [init_randem_seed=0]
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
-//          [scores_out=scores.txt] [baseline=logmmse]
+//          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
 //   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt]
 //
 // Test-set mode: the plan is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list), cut into calls
@@ -16,6 +16,10 @@
 // checked before the device is used.  baseline=logmmse (test-set mode only) scores the classic log-MMSE enhancer on the same
 // mixtures beside the net (bp_eval_mix_logmmse): after every stdout line a second one with `logmmse:` in place of
 // the net's figures (noisy -> logmmse), and three more columns `ssnr_lm lsd_lm stoi_lm` at the end of every scores_out line.
+// rir_list: one room impulse response per WAV, at the rate of the others; clean sentence c is paired with response
+// bp_mix_reverb_pairs(init_randem_seed, ...)[c], the plan addresses the derived entry n_clean + c in place of c (so scores_out
+// lists it), the mixtures are reverberant and the scores are taken against reverb_target: the reverberant sentence or its direct
+// sound + early_ms of reflections.
 // Errors: message + exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -44,7 +48,9 @@ void check(int rc)
 }
 
 struct Params {
-    std::string clean_list, noise_list, pairs_list, norm_file, initwts_file, scores_out;
+    std::string clean_list, noise_list, pairs_list, norm_file, initwts_file, scores_out, rir_list;
+    int reverb_target = BP_REVERB_TARGET_REVERBERANT;
+    float early_ms = 50.0f;
     int fea_dim = 0, fea_context = 1, targ_offset = 0, dropoutflag = 0, traincache = 102400, bunchsize = 1024, numlayers = 0;
     int layersizes[BP_MAXLAYER] = {0}, mix_per_clean = 1, activation = 0, compute_dtype = 0, device = 0;
     int output_act = 0, output_linear_dims = 0, output_loss = 0, wave_target = BP_WAVE_LPS, out_col = 0;
@@ -86,6 +92,12 @@ Params parse(int argc, char **argv)
         else if (k == "device") { ok = parse_int(v, 0, 1023, &P.device); net = false; }
         else if (k == "clean_list") P.clean_list = v; else if (k == "noise_list") P.noise_list = v;
         else if (k == "norm_file") P.norm_file = v; else if (k == "initwts_file") P.initwts_file = v;
+        else if (k == "rir_list") P.rir_list = v;
+        else if (k == "reverb_target") {
+            if (v == "reverberant") P.reverb_target = BP_REVERB_TARGET_REVERBERANT; else if (v == "early") P.reverb_target = BP_REVERB_TARGET_EARLY;
+            else die("reverb_target: " + v + " is not reverberant or early");
+        }
+        else if (k == "early_ms") ok = parse_float(v, &P.early_ms) && P.early_ms >= 0.0f && P.early_ms <= 1e6f;
         else if (k == "fea_context") ok = parse_int(v, 1, 1000, &P.fea_context);
         else if (k == "targ_offset") ok = parse_int(v, 0, 999, &P.targ_offset);
         else if (k == "dropoutflag") ok = parse_int(v, 0, 1, &P.dropoutflag);
@@ -282,6 +294,17 @@ int main(int argc, char **argv)
     int rate = 0;
     const Corpus clean = read_corpus("clean_list", P.clean_list, &rate);
     const Corpus noise = read_corpus("noise_list", P.noise_list, &rate);
+    std::vector<float> rir_pcm;                                  // rir_list: the responses, at the rate of the others
+    std::vector<int> rir_len;
+    if (!P.rir_list.empty()) {
+        const std::vector<std::string> paths = read_lines("rir_list", P.rir_list);
+        for (size_t k = 0; k < paths.size(); ++k) {
+            const std::vector<float> w = read_one(paths[k], &rate);
+            if (w.size() > (size_t)BP_MIX_RIR_MAX_TAPS) die("bpeval: rir_list: " + paths[k] + " has more than " + std::to_string(BP_MIX_RIR_MAX_TAPS) + " taps");
+            rir_pcm.insert(rir_pcm.end(), w.begin(), w.end());
+            rir_len.push_back((int)w.size());
+        }
+    }
     check_rate(rate);
     for (int64_t n : noise.len)
         if (n >= ((int64_t)1 << 32)) die("bpeval: a noise recording has 2^32 samples or more");
@@ -301,6 +324,8 @@ int main(int argc, char **argv)
         }
         calls.push_back({first, (int)plan.size()});
     }
+    const int n_clean = (int)clean.len.size();
+    if (!rir_len.empty()) for (bp_mixture &m : plan) m.clean += n_clean;            // (the derived entry of sentence c: n_clean + c)
     std::vector<float> mean, istd;
     read_norm(P.norm_file, D, mean, istd);
     std::vector<std::vector<float>> Wv(L), Bv(L);
@@ -335,6 +360,17 @@ int main(int argc, char **argv)
     mc.n_clean = (int)clean.len.size(); mc.clean_len = clean.len.data(); mc.clean_pcm = clean.pcm.data();
     mc.n_noise = (int)noise.len.size(); mc.noise_len = noise.len.data(); mc.noise_pcm = noise.pcm.data();
     check(bp_set_mix_corpus(h, &mc));
+    if (!rir_len.empty()) {
+        std::vector<int> pc(n_clean), pr(n_clean);
+        for (int c = 0; c < n_clean; ++c) pc[c] = c;
+        check(bp_mix_reverb_pairs(P.seed, n_clean, (int)rir_len.size(), pr.data()));
+        bp_mix_reverb mr;
+        memset(&mr, 0, sizeof(mr));
+        mr.n_rir = (int)rir_len.size(); mr.rir_len = rir_len.data(); mr.rir_pcm = rir_pcm.data();
+        mr.n_pair = n_clean; mr.pair_clean = pc.data(); mr.pair_rir = pr.data();
+        mr.target = P.reverb_target; mr.early_taps = (int)((double)P.early_ms * rate / 1000.0 + 0.5);
+        check(bp_set_mix_reverb(h, &mr));
+    }
     std::map<float, Acc> by_snr, by_snr_lm;
     Acc all, all_lm;
     std::vector<float> ns, es, ls;

@@ -6,6 +6,7 @@
 //         dropoutflag=1 visible_omit=0.1 hid_omit=0.2 traincache=100000 init_randem_seed=345 initwts_file=... outwts_file=...
 //         log_file=... [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [target=lps|irm|ibm|lps+irm|lps+ibm] [lc_db=5]
 //         [cv_noise_list=noise.list] [cv_seed=20261016] [mix_plan_out=plan.txt] [output_act=...] [compute=fp32|bf16] ...
+//         [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50] [cv_rir_list=rir.list]
 //   bpmix clean_list=... noise_list=... fea_dim=129 norm_out=mix.norm [snr_list=...] [mix_per_clean=...] [init_randem_seed=...]
 //
 // The plan of the epoch is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list); it is cut into
@@ -14,7 +15,11 @@
 // epoch.  CV mixes cv_clean_list with cv_noise_list (default noise_list), one mixture per clean sentence, from cv_seed (fixed by
 // default, so the CV error is comparable across epochs).  norm_out: per-bin mean and inverse std of the noisy LPS of one epoch's
 // training mixtures, accumulated in double, in bpfeat's format; nothing is trained.  mix_plan_out: the drawn training plan, one
-// `clean noise offset snr` line per mixture.  Every key, list and WAV is checked before the device is used.  Errors: message +
+// `clean noise offset snr` line per mixture.  rir_list: one room impulse response per WAV, at the rate of the
+// clean sentences; clean sentence c is paired with response bp_mix_reverb_pairs(init_randem_seed, ...)[c], the pairs become the
+// derived entries n_clean + c of the corpus and the plan addresses entry n_clean + c in place of c.  reverb_target: what the net
+// learns to produce, the reverberant sentence or its direct sound + early_ms of reflections.  CV: cv_rir_list (default rir_list),
+// paired from cv_seed.  Every key, list and WAV is checked before the device is used.  Errors: message +
 // exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -44,7 +49,9 @@ void check(int rc)
 
 struct Params {
     std::string clean_list, noise_list, cv_clean_list, cv_noise_list, norm_file, norm_out, mix_plan_out;
-    std::string initwts_file, outwts_file, log_file;
+    std::string initwts_file, outwts_file, log_file, rir_list, cv_rir_list;
+    int reverb_target = BP_REVERB_TARGET_REVERBERANT;
+    float early_ms = 50.0f;
     int fea_dim = 0, fea_context = 1, targ_offset = 0, dropoutflag = 0, traincache = 0, bunchsize = 0, numlayers = 0;
     int layersizes[BP_MAXLAYER] = {0}, mix_per_clean = 1, target = BP_MIX_LPS, activation = 0, momentum_rule = 0, compute_dtype = 0;
     int output_act = 0, output_linear_dims = 0, output_loss = 0, device = 0;
@@ -91,6 +98,12 @@ Params parse(int argc, char **argv)
         else if (k == "cv_clean_list") P.cv_clean_list = v; else if (k == "cv_noise_list") P.cv_noise_list = v;
         else if (k == "norm_file") P.norm_file = v; else if (k == "norm_out") P.norm_out = v; else if (k == "mix_plan_out") P.mix_plan_out = v;
         else if (k == "initwts_file") P.initwts_file = v; else if (k == "outwts_file") P.outwts_file = v; else if (k == "log_file") P.log_file = v;
+        else if (k == "rir_list") P.rir_list = v; else if (k == "cv_rir_list") P.cv_rir_list = v;
+        else if (k == "reverb_target") {
+            if (v == "reverberant") P.reverb_target = BP_REVERB_TARGET_REVERBERANT; else if (v == "early") P.reverb_target = BP_REVERB_TARGET_EARLY;
+            else die("reverb_target: " + v + " is not reverberant or early");
+        }
+        else if (k == "early_ms") ok = parse_float(v, &P.early_ms) && P.early_ms >= 0.0f && P.early_ms <= 1e6f;
         else if (k == "fea_dim") ok = parse_int(v, 1, 1 << 20, &P.fea_dim);
         else if (k == "fea_context") ok = parse_int(v, 1, 1000, &P.fea_context);
         else if (k == "targ_offset") ok = parse_int(v, 0, 999, &P.targ_offset);
@@ -147,7 +160,7 @@ Params parse(int argc, char **argv)
     return P;
 }
 
-std::vector<std::vector<float>> read_list(const std::string &what, const std::string &list)
+std::vector<std::vector<float>> read_list(const std::string &what, const std::string &list, std::vector<int> *rates = nullptr)
 {
     if (list.empty()) die("bpmix: " + what + " is not given");
     FILE *fl = fopen(list.c_str(), "rt");
@@ -163,6 +176,7 @@ std::vector<std::vector<float>> read_list(const std::string &what, const std::st
         const std::string err = bp::read_wav(p, waves.back(), sr);
         if (!err.empty()) { fclose(fl); die(err); }
         if (waves.back().empty()) { fclose(fl); die(p + ": no samples"); }
+        if (rates) rates->push_back(sr);
     }
     fclose(fl);
     if (waves.empty()) die("bpmix: " + list + " lists no wav file");
@@ -178,6 +192,53 @@ Corpus flatten(const std::vector<std::vector<float>> &w)
     Corpus c;
     for (const auto &x : w) { c.pcm.insert(c.pcm.end(), x.begin(), x.end()); c.len.push_back((int64_t)x.size()); }
     return c;
+}
+
+// The impulse responses of rir_list, checked against the rate of the clean sentences (on: the list was given)
+struct Reverb {
+    bool on = false;
+    std::vector<float> pcm;
+    std::vector<int> len;
+    int target = 0, early_taps = 0;
+};
+Reverb read_reverb(const Params &P, const std::string &what, const std::string &list, const std::vector<int> &clean_rates)
+{
+    Reverb r;
+    if (list.empty()) return r;
+    std::vector<int> rates;
+    const auto w = read_list(what, list, &rates);
+    for (size_t k = 0; k < clean_rates.size(); ++k)
+        if (clean_rates[k] != clean_rates[0])
+            die("bpmix: " + what + " needs clean sentences of one sample rate (sentence " + std::to_string(k) + " has " +
+                std::to_string(clean_rates[k]) + " Hz, sentence 0 " + std::to_string(clean_rates[0]) + " Hz)");
+    for (size_t k = 0; k < w.size(); ++k) {
+        if (rates[k] != clean_rates[0])
+            die("bpmix: " + what + ": response " + std::to_string(k) + " has " + std::to_string(rates[k]) + " Hz, the clean sentences " +
+                std::to_string(clean_rates[0]) + " Hz");
+        if (w[k].size() > (size_t)BP_MIX_RIR_MAX_TAPS)
+            die("bpmix: " + what + ": response " + std::to_string(k) + " has more than " + std::to_string(BP_MIX_RIR_MAX_TAPS) + " taps");
+        for (float v : w[k])
+            if (!std::isfinite(v)) die("bpmix: " + what + ": response " + std::to_string(k) + " has a tap that is not finite");
+        r.pcm.insert(r.pcm.end(), w[k].begin(), w[k].end());
+        r.len.push_back((int)w[k].size());
+    }
+    r.on = true; r.target = P.reverb_target;
+    r.early_taps = (int)((double)P.early_ms * clean_rates[0] / 1000.0 + 0.5);
+    return r;
+}
+
+// the derived entries of a corpus of n_clean sentences: sentence c with response bp_mix_reverb_pairs(seed)[c]
+void set_reverb(bp_handle *h, const Reverb &r, unsigned long long seed, int n_clean)
+{
+    std::vector<int> pc(n_clean), pr(n_clean);
+    for (int c = 0; c < n_clean; ++c) pc[c] = c;
+    check(bp_mix_reverb_pairs(seed, n_clean, (int)r.len.size(), pr.data()));
+    bp_mix_reverb mr;
+    memset(&mr, 0, sizeof(mr));
+    mr.n_rir = (int)r.len.size(); mr.rir_len = r.len.data(); mr.rir_pcm = r.pcm.data();
+    mr.n_pair = n_clean; mr.pair_clean = pc.data(); mr.pair_rir = pr.data();
+    mr.target = r.target; mr.early_taps = r.early_taps;
+    check(bp_set_mix_reverb(h, &mr));
 }
 
 // Calls of at most `cap` rows (frames + n_mix (context-1)), consecutive mixtures of the plan: [first, last) per call.
@@ -217,7 +278,7 @@ bp_mix_corpus describe(const Params &P, int target, int ctx, int toff, const flo
 }
 
 // norm_out: mean and inverse std of the noisy LPS of the epoch's training mixtures (bpfeat's format), on a one-layer handle
-int norm_pass(const Params &P, const Corpus &clean, const Corpus &noise, const std::vector<bp_mixture> &plan)
+int norm_pass(const Params &P, const Corpus &clean, const Corpus &noise, std::vector<bp_mixture> plan, const Reverb &rv)
 {
     const int D = P.fea_dim, hop = D - 1, cap = P.traincache ? P.traincache : BP_MAXCACHEFRAME;
     std::vector<int> frames;
@@ -235,6 +296,10 @@ int norm_pass(const Params &P, const Corpus &clean, const Corpus &noise, const s
     check(bp_create(&cfg, w, b, &h));
     const bp_mix_corpus mc = describe(P, BP_MIX_LPS, 1, 0, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
+    if (rv.on) {
+        set_reverb(h, rv, P.seed, (int)clean.len.size());
+        for (bp_mixture &m : plan) m.clean += (int)clean.len.size();
+    }
     std::vector<double> sum(D, 0.0), sq(D, 0.0);
     size_t total = 0;
     std::vector<float> lps;
@@ -284,12 +349,14 @@ int main(int argc, char **argv)
     if (P.snr.empty()) die("bpmix: snr_list is empty");
     const int hop = D - 1;
     // every list and WAV is read and checked before the device is used
-    const Corpus clean = flatten(read_list("clean_list", P.clean_list));
+    std::vector<int> clean_rates, cv_rates;
+    const Corpus clean = flatten(read_list("clean_list", P.clean_list, &clean_rates));
     const Corpus noise = flatten(read_list("noise_list", P.noise_list));
     for (int64_t n : noise.len)
         if (n >= ((int64_t)1 << 32)) die("bpmix: a noise recording has 2^32 samples or more");
-    const std::vector<bp_mixture> plan = make_plan(P.seed, (int)clean.len.size(), P.mix_per_clean, noise, P.snr);
-    if (!P.norm_out.empty()) return norm_pass(P, clean, noise, plan);
+    std::vector<bp_mixture> plan = make_plan(P.seed, (int)clean.len.size(), P.mix_per_clean, noise, P.snr);
+    const Reverb rv = read_reverb(P, "rir_list", P.rir_list, clean_rates);
+    if (!P.norm_out.empty()) return norm_pass(P, clean, noise, plan, rv);
 
     const int L = P.numlayers, ctx = P.fea_context, toff = P.targ_offset;
     if (L < 2 || P.layersizes[L - 1] < 1) die("bpmix: numlayers / layersizes: need 2.." + std::to_string(BP_MAXLAYER - 1) + " layer sizes");
@@ -299,12 +366,15 @@ int main(int argc, char **argv)
     const int parts = P.target == BP_MIX_LPS_IRM || P.target == BP_MIX_LPS_IBM ? 2 : 1;
     if (P.layersizes[L - 1] != parts * D) die("bpmix: layersizes[last] must be " + std::to_string(parts * D) + " for this target");
     if (P.layersizes[0] != ctx * D && P.layersizes[0] != (ctx + 1) * D) die("bpmix: layersizes[0] must be fea_context*fea_dim (+ fea_dim with NAT)");
-    const Corpus cv_clean = flatten(read_list("cv_clean_list", P.cv_clean_list));
+    const Corpus cv_clean = flatten(read_list("cv_clean_list", P.cv_clean_list, &cv_rates));
     const Corpus cv_noise = P.cv_noise_list.empty() ? noise : flatten(read_list("cv_noise_list", P.cv_noise_list));
-    const std::vector<bp_mixture> cv_plan = make_plan(P.cv_seed, (int)cv_clean.len.size(), 1, cv_noise, P.snr);
+    std::vector<bp_mixture> cv_plan = make_plan(P.cv_seed, (int)cv_clean.len.size(), 1, cv_noise, P.snr);
+    const Reverb cv_rv = read_reverb(P, P.cv_rir_list.empty() ? "rir_list" : "cv_rir_list", P.cv_rir_list.empty() ? P.rir_list : P.cv_rir_list, cv_rates);
     std::vector<int> frames, cv_frames;
     const auto calls = cut(plan, clean, hop, ctx, P.traincache, &frames);
     const auto cv_calls = cut(cv_plan, cv_clean, hop, ctx, P.traincache, &cv_frames);
+    if (rv.on) for (bp_mixture &m : plan) m.clean += (int)clean.len.size();          // (the derived entry of sentence c: n_clean + c)
+    if (cv_rv.on) for (bp_mixture &m : cv_plan) m.clean += (int)cv_clean.len.size();
     std::vector<float> mean, istd;
     read_norm(P.norm_file, D, mean, istd);
 
@@ -380,6 +450,11 @@ int main(int argc, char **argv)
     printf("Created net with %d layers, bunchsize %d.\n", L, P.bunchsize);
     const bp_mix_corpus mc = describe(P, P.target, ctx, toff, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
+    if (rv.on) {
+        set_reverb(h, rv, P.seed, (int)clean.len.size());
+        fprintf(log, "Reverberation: %zu impulse responses, target %s, %d early taps.\n", rv.len.size(),
+                rv.target == BP_REVERB_TARGET_EARLY ? "early" : "reverberant", rv.early_taps);
+    }
     fprintf(log, "Corpus loaded: %zu clean sentences, %zu noise recordings, %zu mixtures in %zu chunks.\n", clean.len.size(),
             noise.len.size(), plan.size(), calls.size());
     struct timespec ts0, ts1;
@@ -412,6 +487,7 @@ int main(int argc, char **argv)
     fprintf(log, "Starting CV.\n");
     const bp_mix_corpus cvc = describe(P, P.target, ctx, toff, mean.data(), istd.data(), cv_clean, cv_noise);
     check(bp_set_mix_corpus(h, &cvc));
+    if (cv_rv.on) set_reverb(h, cv_rv, P.cv_seed, (int)cv_clean.len.size());
     fprintf(log, "Get cv chunk info over: CV mixtures have %d chunks.\n", (int)cv_calls.size());
     float squared_err = 0.0f;
     long cv_total = 0;

@@ -279,6 +279,47 @@ int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const in
 int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order);
 
 /* ------------------------------------------------------------------------------------
+ * Reverberant entries of the mixing corpus (no reference counterpart).  INTEGRATION.md 1k.
+ *
+ * A room impulse response h has Lh taps, fp32 and finite, 1 <= Lh <= BP_MIX_RIR_MAX_TAPS.  Its delay d is the first index at
+ * which |h[j]| is largest (bp_mix_rir_delay, host only).  For a clean sentence s of n samples, s[k] = 0 outside [0, n):
+ *   acc_i(J) = sum_{j=0..J} (double)h[j] * (double)s[i + d - j]    added for j ascending, in double, starting from +0.0
+ *   r[i] = fl32(acc_i(Lh - 1))                                      the reverberant sentence, n samples, aligned to the direct path
+ *   e[i] = fl32(acc_i(min(Lh - 1, d + early_taps)))                 direct sound + early reflections (early_taps >= 0)
+ * The product of two fp32 numbers is exact in double, so each step is one rounded double addition (fma or multiply-then-add:
+ * the same bits); out-of-range terms are exact zeros and may be skipped.  The order over j is the definition.  h is not
+ * normalised.
+ *
+ * bp_set_mix_reverb: pair k = {clean sentence pair_clean[k], response pair_rir[k]} becomes clean entry n_clean + k of the corpus
+ * set by bp_set_mix_corpus, with the length of its clean sentence.  Its mixing signal is r; its target signal is r
+ * (BP_REVERB_TARGET_REVERBERANT) or e (BP_REVERB_TARGET_EARLY).  The entries are made once per call on the device and stay
+ * resident; a later bp_set_mix_reverb replaces them, bp_set_mix_corpus drops them.  Every mixing call (bp_train_mix, bp_cv_mix,
+ * bp_mix_features, bp_eval_mix, bp_eval_mix_logmmse) then accepts bp_mixture.clean in [0, n_clean + n_pair).  The mixing
+ * definition above holds with "clean sentence" read two ways: E_s, x = fmaf(g, v, s) and the noisy features use the mixing
+ * signal; S, the LPS / IRM / IBM targets and the reference bp_eval_mix* scores against use the target signal.  Dry entries
+ * [0, n_clean) are both signals at once and keep their bits.
+ * BP_ERR_ARG before the device is touched, the handle unchanged: null pointers, n_rir < 1, n_pair < 1, a length outside
+ * [1, BP_MIX_RIR_MAX_TAPS], a non-finite tap, a pair index out of range, a bad target, early_taps < 0.  BP_ERR_STATE without a
+ * corpus or on a data-parallel-attached handle.  BP_ERR_NOMEM leaves the previous entries in place.
+ *
+ * bp_reverb_waves: the same kernel on caller-supplied sentences (sentence k of sent_len[k] >= 1 samples, back to back in pcm, with
+ * response sent_rir[k]); out_rev / out_early [sum sent_len], either may be NULL (not both).  No handle: one host->device copy,
+ * one launch, one device->host copy, one synchronisation.
+ * bp_mix_reverb_pairs (host only): pair_rir[c] = (philox(c, 0, 3, 0)[0] * n_rir) >> 32 for c < n_clean. */
+#define BP_MIX_RIR_MAX_TAPS 65536
+enum { BP_REVERB_TARGET_REVERBERANT = 0, BP_REVERB_TARGET_EARLY = 1 };
+typedef struct bp_mix_reverb {
+    int n_rir; const int *rir_len; const float *rir_pcm;           /* back to back */
+    int n_pair; const int *pair_clean, *pair_rir;
+    int target, early_taps;
+} bp_mix_reverb;
+int bp_set_mix_reverb(bp_handle *h, const bp_mix_reverb *r);
+int bp_reverb_waves(int device, int n_sent, const int *sent_len, const float *pcm, const int *sent_rir, int n_rir, const int *rir_len,
+                    const float *rir_pcm, int early_taps, float *out_rev, float *out_early);
+int bp_mix_rir_delay(const float *h, int n_taps, int *delay);
+int bp_mix_reverb_pairs(uint64_t seed, int n_clean, int n_rir, int *pair_rir);
+
+/* ------------------------------------------------------------------------------------
  * Objective scores of enhanced speech (no reference counterpart: the papers it asks its users to cite score with outside tools).
  * INTEGRATION.md 1f.  Samples are fp32 in int16 units; a score compares an estimate e with a reference r of the same length n
  * at sample rate fs; eps = 2.220446049250313e-16; an undefined score is NaN, never an error.  Accepted rates: fs > 0 and
