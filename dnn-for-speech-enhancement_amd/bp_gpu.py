@@ -704,6 +704,33 @@ class BP_GPU(object):
             pass
 
 
+def _stream_push(lib_call, handle, n_chan, blocks, end, out_cap):
+    """One push of either kind of stream (bp_stream_push, bp_lmstream_push): (status, one float32 array per channel or None).
+    out_cap: samples of the output buffer, or a function of the samples pushed that gives them."""
+    arrs = [np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
+    n_in = np.array([a.size for a in arrs], np.int32)
+    pcm = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(0, np.float32)
+    e = None if end is None else np.ascontiguousarray([1 if v else 0 for v in end], dtype=np.uint8)
+    if callable(out_cap):
+        out_cap = out_cap(int(pcm.size))
+    out = np.empty(max(int(out_cap), 1), np.float32)
+    n_out = np.zeros(n_chan, np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib_call(handle, n_in.ctypes.data_as(ip), _fp(pcm) if pcm.size else None,
+                  None if e is None else e.ctypes.data_as(C.POINTER(C.c_ubyte)), n_out.ctypes.data_as(ip), _fp(out), int(out_cap))
+    return rc, None if rc != 0 else [a.copy() for a in np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])]
+
+
+def _counts3(fn, *args):
+    """(frames_in, frames_out, samples_out) from the count call named fn (bp_stream_counts, bp_lmstream_counts); host only."""
+    lib = load_library()
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = getattr(lib, fn)(*(args + (C.byref(a), C.byref(b), C.byref(c))))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return int(a.value), int(b.value), int(c.value)
+
+
 class Stream(object):
     """A streaming session (bp_stream_*): n_chan live feeds enhanced in blocks of any sizes."""
 
@@ -727,20 +754,11 @@ class Stream(object):
             g._fail("Stream.push: the stream or its handle is closed")
         if len(blocks) != self.n_chan or (end is not None and len(end) != self.n_chan):
             g._fail("Stream.push: need one block (and one end flag) per channel (%d)" % self.n_chan)
-        arrs = [np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
-        n_in = np.array([a.size for a in arrs], np.int32)
-        pcm = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(0, np.float32)
-        e = None if end is None else np.ascontiguousarray([1 if v else 0 for v in end], dtype=np.uint8)
-        hop = self.fea_dim - 1
         if out_cap is None:     # what waited (at most max(look-ahead, 5) + 1 frames) and what arrived, rounded up to frames
-            out_cap = int(pcm.size) + self.n_chan * (max(self.look_ahead, 5) + 3) * hop
-        out = np.empty(max(int(out_cap), 1), np.float32)
-        n_out = np.zeros(self.n_chan, np.int32)
-        ip = C.POINTER(C.c_int)
-        g._check(g._lib.bp_stream_push(self._s, n_in.ctypes.data_as(ip), _fp(pcm) if pcm.size else None,
-                                       None if e is None else e.ctypes.data_as(C.POINTER(C.c_ubyte)), n_out.ctypes.data_as(ip),
-                                       _fp(out), int(out_cap)))
-        return [a.copy() for a in np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])]
+            out_cap = lambda n: n + self.n_chan * (max(self.look_ahead, 5) + 3) * (self.fea_dim - 1)
+        rc, outs = _stream_push(g._lib.bp_stream_push, self._s, self.n_chan, blocks, end, out_cap)
+        g._check(rc)
+        return outs
 
     def close(self):
         if self._s is not None and self._g._h is not None:
@@ -750,13 +768,8 @@ class Stream(object):
 
 def stream_counts(fea_dim, context, targ_offset, nat, received, ended):
     """bp_stream_counts: (frames_in, frames_out, samples_out) of a channel after `received` samples of its sentence; host only."""
-    lib = load_library()
-    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-    rc = lib.bp_stream_counts(int(fea_dim), int(context), int(targ_offset), 1 if nat else 0, int(received), 1 if ended else 0,
-                              C.byref(a), C.byref(b), C.byref(c))
-    if rc != 0:
-        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
-    return int(a.value), int(b.value), int(c.value)
+    return _counts3("bp_stream_counts", int(fea_dim), int(context), int(targ_offset), 1 if nat else 0, int(received),
+                    1 if ended else 0)
 
 
 def _sentences(sentences, fea_dim):
@@ -833,21 +846,12 @@ class LogmmseStream(object):
             raise BPError("LogmmseStream.push: the stream is closed")
         if len(blocks) != self.n_chan or (end is not None and len(end) != self.n_chan):
             raise BPError("LogmmseStream.push: need one block (and one end flag) per channel (%d)" % self.n_chan)
-        arrs = [np.zeros(0, np.float32) if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in blocks]
-        n_in = np.array([a.size for a in arrs], np.int32)
-        pcm = np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros(0, np.float32)
-        e = None if end is None else np.ascontiguousarray([1 if v else 0 for v in end], dtype=np.uint8)
         if out_cap is None:     # what waited for the noise start (fewer than init_frames + 1 hops) and what arrived
-            out_cap = int(pcm.size) + self.n_chan * (self.init_frames + 1) * (self.fea_dim - 1)
-        out = np.empty(max(int(out_cap), 1), np.float32)
-        n_out = np.zeros(self.n_chan, np.int32)
-        ip = C.POINTER(C.c_int)
-        rc = self._lib.bp_lmstream_push(self._s, n_in.ctypes.data_as(ip), _fp(pcm) if pcm.size else None,
-                                        None if e is None else e.ctypes.data_as(C.POINTER(C.c_ubyte)), n_out.ctypes.data_as(ip),
-                                        _fp(out), int(out_cap))
+            out_cap = lambda n: n + self.n_chan * (self.init_frames + 1) * (self.fea_dim - 1)
+        rc, outs = _stream_push(self._lib.bp_lmstream_push, self._s, self.n_chan, blocks, end, out_cap)
         if rc != 0:
             raise BPError("%s (status %d)" % (self._lib.bp_last_error().decode(), rc))
-        return [a.copy() for a in np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])]
+        return outs
 
     def close(self):
         if self._s is not None:
@@ -884,12 +888,7 @@ def logmmse_stream_open(device, fea_dim, params=None, n_chan=1, max_push_samples
 
 def logmmse_stream_counts(fea_dim, init_frames, received, ended):
     """bp_lmstream_counts: (frames_in, frames_out, samples_out) of a channel after `received` samples of its sentence; host only."""
-    lib = load_library()
-    a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-    rc = lib.bp_lmstream_counts(int(fea_dim), int(init_frames), int(received), 1 if ended else 0, C.byref(a), C.byref(b), C.byref(c))
-    if rc != 0:
-        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
-    return int(a.value), int(b.value), int(c.value)
+    return _counts3("bp_lmstream_counts", int(fea_dim), int(init_frames), int(received), 1 if ended else 0)
 
 
 def score_waves(device, fea_dim, sample_rate, refs, ests):

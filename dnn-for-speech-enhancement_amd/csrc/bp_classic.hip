@@ -1,10 +1,11 @@
 // bp_classic.hip -- C-ABI implementation (include/bp_c_api.h), part 8 of 9: the classic baseline.  The log-MMSE (Ephraim-Malah
 // log-spectral-amplitude) enhancer on the signal definition of bp_wave.hip: noisy PCM in, enhanced PCM out, no net
 // (bp_logmmse_waves here; bp_eval_mix_logmmse in bp_mix.hip through bp_classic.h).  Definition: include/bp_c_api.h,
-// INTEGRATION.md 1h.  gfx950 only.
+// INTEGRATION.md 1h.  gfx950 only.  The second half of the unit is the baseline on live audio (bp_lmstream_*):
+// its own job table and kernel; counts, carry, push checks and the owner of its blocks are bp_stream_core.h's, shared with bp_stream.hip.
 //
 // A call is bp_wave_analysis (bp_wave.hip) -> bp_logmmse_gain -> bp_wave_synthesis with BP_WAVE_MASK and the gain rows in place of
-// the net's output -> bp_wave_overlap.  The one kernel of this unit:
+// the net's output -> bp_wave_overlap, on the frame plan and input block of bp_wave_lps (bp_fft.h).  Its kernel:
 //   bp_logmmse_gain  one workgroup of 256 threads per sentence; the frames of a sentence are a dependent chain (the noise estimate
 //                    and the decision-directed a-priori SNR carry over), the bins are independent but for the VAD, the mean of the
 //                    log likelihood ratio over all bins of a frame.  Thread i owns bins i, i + 256, ... (NB of them, 5 at fea_dim
@@ -20,13 +21,26 @@
 #include <algorithm>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "bp_classic.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
+#include "bp_stream_core.h"
 
 namespace {
+
+// f(std::integral_constant<int, NB>) for the NB = bins per thread of fea_dim D: 33 .. 129, 257, 513, 1025
+template <class F> void with_nb(int D, F f)
+{
+    switch ((D + WAVE_THREADS - 1) / WAVE_THREADS) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 5>()); break;
+    }
+}
 
 struct LogmmseArgs {
     const float2 *Y; const int *F;
@@ -140,9 +154,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_lmstream_push(const LmStreamA
     } else {
 #pragma unroll
         for (int j = 0; j < NB; ++j) { lam[j] = a.lam[(size_t)job.chan * D + kc[j]]; Ap[j] = a.Ap[(size_t)job.chan * D + kc[j]]; }
-        const float *hs = a.half + (size_t)job.chan * hop;      // the frame before the job's first: as the second half of fr[1]
-        for (int q = tid; q < hop / 4; q += WAVE_THREADS)
-            *reinterpret_cast<float4 *>(fr + N + hop + 4 * q) = *reinterpret_cast<const float4 *>(hs + 4 * q);
+        copy_half(fr + N + hop, a.half + (size_t)job.chan * hop, hop, WAVE_THREADS);   // the frame before the job's first: as the second half of fr[1]
     }
     for (int i = 0; i < job.nf; ++i) {
         const int t = job.t0 + i;
@@ -160,28 +172,15 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_lmstream_push(const LmStreamA
         synth_frame(z, grow, Yrow, a.win, a.tw, a.log2M, BP_WAVE_MASK, cur);
         __syncthreads();
         if (t > 0) {                                             // frame 0 of a sentence covers the front padding: no output
-            const int off = (t - 1 - (job.t0 > 0 ? job.t0 - 1 : 0)) * hop, n = job.out_n - off;   // clipped at a sentence's end
-            float *dst = a.out + job.out_off + off;              // compact: only 4-byte aligned
-            for (int q = tid; q < hop / 4; q += WAVE_THREADS) {
-                const float4 c = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(pv + 4 * q);
-                const float4 wa = *reinterpret_cast<const float4 *>(a.win + 4 * q), wb = *reinterpret_cast<const float4 *>(a.win + hop + 4 * q);
-                const float4 r = overlap4(c, b, wa, wb);
-                const int e = 4 * q;
-                if (e < n) dst[e] = r.x;
-                if (e + 1 < n) dst[e + 1] = r.y;
-                if (e + 2 < n) dst[e + 2] = r.z;
-                if (e + 3 < n) dst[e + 3] = r.w;
-            }
+            const int off = (t - 1 - (job.t0 > 0 ? job.t0 - 1 : 0)) * hop;
+            overlap_store(cur, pv, a.win, hop, a.out + job.out_off + off, job.out_n - off, WAVE_THREADS);   // clipped at a sentence's end
         }
     }
     if (!job.ended) {
 #pragma unroll
         for (int j = 0; j < NB; ++j)
             if (on[j]) { a.lam[(size_t)job.chan * D + kc[j]] = lam[j]; a.Ap[(size_t)job.chan * D + kc[j]] = Ap[j]; }
-        const float *last = fr + (size_t)((job.nf - 1) & 1) * N + hop;
-        float *hd = a.half + (size_t)job.chan * hop;
-        for (int q = tid; q < hop / 4; q += WAVE_THREADS)
-            *reinterpret_cast<float4 *>(hd + 4 * q) = *reinterpret_cast<const float4 *>(last + 4 * q);
+        copy_half(a.half + (size_t)job.chan * hop, fr + (size_t)((job.nf - 1) & 1) * N + hop, hop, WAVE_THREADS);
     }
 }
 
@@ -209,12 +208,7 @@ hipError_t logmmse_gain_launch(const LogmmseP &p, const float2 *Y, const int *F,
     a.Y = Y; a.F = F; a.gain = gain; a.vad = vad; a.D = D; a.init_frames = p.init_frames;
     a.alpha = p.alpha; a.mu = p.mu; a.eta = p.eta; a.xi_min = p.xi_min; a.gamma_max = p.gamma_max;
     const dim3 grid((unsigned)n_sent), blk(WAVE_THREADS);
-    switch ((D + WAVE_THREADS - 1) / WAVE_THREADS) {             // fea_dim 33 .. 129, 257, 513, 1025
-    case 1: hipLaunchKernelGGL(bp_logmmse_gain<1>, grid, blk, 0, st, a); break;
-    case 2: hipLaunchKernelGGL(bp_logmmse_gain<2>, grid, blk, 0, st, a); break;
-    case 3: hipLaunchKernelGGL(bp_logmmse_gain<3>, grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL(bp_logmmse_gain<5>, grid, blk, 0, st, a); break;
-    }
+    with_nb(D, [&](auto nb) { hipLaunchKernelGGL(bp_logmmse_gain<decltype(nb)::value>, grid, blk, 0, st, a); });
     return hipGetLastError();
 }
 
@@ -228,127 +222,68 @@ extern "C" int bp_logmmse_defaults(bp_logmmse_params *p)
 extern "C" int bp_logmmse_waves(int device, int fea_dim, const bp_logmmse_params *p, int n_sent, const int *sent_len, const float *pcm,
                                 float *out_pcm, float *out_gain, float *out_vad)
 {
-    const int log2M = wave_log2_fft(fea_dim);
-    if (log2M < 0) return fail(BP_ERR_ARG, "bp_logmmse_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    const char *who = "bp_logmmse_waves";
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, "bp_logmmse_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
     LogmmseP lp;
-    { const int r = logmmse_check("bp_logmmse_waves", p, lp); if (r != BP_OK) return r; }
-    if (n_sent < 1 || !sent_len || !pcm || !out_pcm) return fail(BP_ERR_ARG, "bp_logmmse_waves: no sentences or null pointer");
-    const int M = 1 << log2M, hop = M, N = 2 * M, D = fea_dim;
-    std::vector<int> F((size_t)n_sent + 1, 0);
-    size_t f = 0;
-    for (int s = 0; s < n_sent; ++s) {
-        if (sent_len[s] < 1) return fail(BP_ERR_ARG, "bp_logmmse_waves: empty sentence " + std::to_string(s));
-        f += (size_t)((sent_len[s] - 1) / hop + 2);
-        if (f > (size_t)INT32_MAX / 8) return fail(BP_ERR_ARG, "bp_logmmse_waves: too many frames in one call");
-        F[s + 1] = (int)f;
-    }
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_logmmse_waves: device ordinal out of range");
-    HIPCHK(hipSetDevice(device));
-    const auto al256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // one host->device block: F | window | twiddles | padded PCM (the layout of bp_wave_lps: sentence s at sample (F_s + s + 1) hop);
-    // one device->host block: padded enhanced PCM | vad | gain; between them the spectrum and the synthesis frames
-    const size_t padded = (f + (size_t)n_sent) * hop;
-    const size_t o_win = al256(((size_t)n_sent + 1) * 4), o_tw = o_win + al256((size_t)N * 4), o_pcm = o_tw + al256((size_t)(M + 1) * 8);
-    const size_t in_b = o_pcm + al256(padded * 4);
-    const size_t o_out = in_b, o_vad = o_out + al256(padded * 4), o_gain = o_vad + al256(f * 4), out_end = o_gain + al256(f * D * 4);
-    const size_t o_Y = out_end, o_syn = o_Y + al256(f * D * sizeof(float2)), total = o_syn + al256(f * N * 4);
+    { const int r = logmmse_check(who, p, lp); if (r != BP_OK) return r; }
+    if (!out_pcm) return fail(BP_ERR_ARG, "bp_logmmse_waves: no sentences or null pointer");
+    WavePlan wp;
+    { const int r = plan_waves(who, fea_dim, n_sent, sent_len, pcm, (size_t)INT32_MAX / 8, wp); if (r != BP_OK) return r; }
+    const int D = fea_dim;
+    const size_t f = wp.frames;
+    // one host->device block, that of bp_wave_lps (no norm file); one device->host block: padded enhanced PCM | vad | gain; between
+    // them the spectrum and the synthesis frames
+    const WaveIn w = wave_in_layout(wp, D);
+    const size_t o_out = w.bytes, o_vad = o_out + al256(wp.padded * 4), o_gain = o_vad + al256(f * 4), out_end = o_gain + al256(f * D * 4);
+    const size_t o_Y = out_end, o_syn = o_Y + al256(f * D * sizeof(float2)), total = o_syn + al256(f * wp.N * 4);
     const size_t out_b = (out_gain ? out_end : out_vad ? o_gain : o_vad) - o_out;
-    std::vector<char> hb(in_b, 0), ho(out_b);
-    memcpy(hb.data(), F.data(), F.size() * 4);
-    wave_window_twiddles(log2M, (float *)(hb.data() + o_win), (float2 *)(hb.data() + o_tw));
-    {
-        float *x = (float *)(hb.data() + o_pcm);
-        size_t src = 0;
-        for (int s = 0; s < n_sent; ++s) {
-            memcpy(x + (size_t)(F[s] + s + 1) * hop, pcm + src, (size_t)sent_len[s] * 4);
-            src += (size_t)sent_len[s];
-        }
-    }
-    hipStream_t st = nullptr;
-    char *d = nullptr;
-    int rc = BP_OK;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, st);
-    const float *win = (const float *)(d + o_win);
-    const float2 *tw = (const float2 *)(d + o_tw);
-    const int *Fd = (const int *)d;
+    OneShot os;
+    { const int r = os.open(who, device, total); if (r != BP_OK) return r; }
+    std::vector<char> hb(w.bytes), ho(out_b);
+    wave_in_fill(hb.data(), w, wp, D, nullptr, nullptr, sent_len, pcm);
+    hipError_t &e = os.e;
+    char *d = os.d;
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, os.st);
+    const float *win = (const float *)(d + w.win);
+    const float2 *tw = (const float2 *)(d + w.tw);
+    const int *Fd = (const int *)(d + w.F);
     float2 *Y = (float2 *)(d + o_Y);
     float *gain = (float *)(d + o_gain), *syn = (float *)(d + o_syn);
     if (e == hipSuccess) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
-        a.pcm = (const float *)(d + o_pcm); a.win = win; a.tw = tw; a.F = Fd;
-        a.n_sent = n_sent; a.log2M = log2M; a.D = D; a.hop = hop; a.ctx = 1;
+        a.pcm = (const float *)(d + w.pcm); a.win = win; a.tw = tw; a.F = Fd;
+        a.n_sent = n_sent; a.log2M = wp.log2M; a.D = D; a.hop = wp.hop; a.ctx = 1;
         a.Y = Y;
-        e = wave_analysis_launch(a, (int)f, st);
+        e = wave_analysis_launch(a, (int)f, os.st);
     }
-    if (e == hipSuccess) e = logmmse_gain_launch(lp, Y, Fd, n_sent, D, gain, (float *)(d + o_vad), st);
-    if (e == hipSuccess) e = wave_synthesis_launch(gain, D, 0, Y, win, tw, log2M, D, BP_WAVE_MASK, syn, (int)f, st);
-    if (e == hipSuccess) e = wave_overlap_launch(syn, win, Fd, n_sent, hop, (float *)(d + o_out), (int)f, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ho.data(), d + o_out, out_b, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_logmmse_waves: ") + hipGetErrorString(e));
-    if (d) (void)hipFree(d);
-    if (st) (void)hipStreamDestroy(st);
-    if (rc != BP_OK) return rc;
-    const float *xo = (const float *)ho.data();
-    size_t dst = 0;
-    for (int s = 0; s < n_sent; ++s) {
-        memcpy(out_pcm + dst, xo + (size_t)(F[s] + s + 1) * hop, (size_t)sent_len[s] * 4);
-        dst += (size_t)sent_len[s];
-    }
+    if (e == hipSuccess) e = logmmse_gain_launch(lp, Y, Fd, n_sent, D, gain, (float *)(d + o_vad), os.st);
+    if (e == hipSuccess) e = wave_synthesis_launch(gain, D, 0, Y, win, tw, wp.log2M, D, BP_WAVE_MASK, syn, (int)f, os.st);
+    if (e == hipSuccess) e = wave_overlap_launch(syn, win, Fd, n_sent, wp.hop, (float *)(d + o_out), (int)f, os.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ho.data(), d + o_out, out_b, hipMemcpyDeviceToHost, os.st);
+    { const int r = os.finish(who); if (r != BP_OK) return r; }
+    wave_gather(out_pcm, wp, sent_len, (const float *)ho.data());
     if (out_vad) memcpy(out_vad, ho.data() + (o_vad - o_out), f * 4);
     if (out_gain) memcpy(out_gain, ho.data() + (o_gain - o_out), f * D * 4);
     return BP_OK;
 }
 
 // ------------------------------------------------------------------ log-MMSE streams: host side
-namespace {
-
-// What a channel has produced after `received` samples of its sentence (include/bp_c_api.h): bp_stream_counts with look-ahead 0
-// and the noise start in place of the noise-aware row
-struct LmCounts { int64_t fi, fo, so; };
-LmCounts lm_counts(int hop, int init_frames, int64_t received, bool ended)
-{
-    LmCounts c = {0, 0, 0};
-    if (received <= 0) return c;
-    const int64_t T = (received - 1) / hop + 2;
-    c.fi = ended ? T : received / hop;
-    const bool known = ended || c.fi >= init_frames;
-    c.fo = !known ? 0 : c.fi;
-    c.so = ended ? received : std::max<int64_t>(0, c.fo - 1) * hop;
-    return c;
-}
-
-// The carry holds the padded samples from the channel's first frame without output on: hop zeros in front of a sentence, all of
-// the sentence while it waits for its noise start, the last hop + received % hop samples after that.
-struct LmChan { int64_t received; size_t carry_n; std::vector<float> carry; };
-struct LmPlan { int64_t r1; bool ended; LmCounts c0, c1; };
-
-size_t lm_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace
-
 struct bp_lmstream {
     int device, D, hop, log2M, n_chan, max_push;
     LogmmseP lp;
     hipStream_t st;
-    std::vector<LmChan> ch;
-    std::vector<LmPlan> plan;
+    // a channel's carry holds the padded samples from its first frame without output on: hop zeros in front of a sentence, all
+    // of the sentence while it waits for its noise start, the last hop + received % hop samples after that
+    std::vector<Carry> ch;
+    std::vector<ChanStep> plan;
     std::vector<LmJob> jobs;
     size_t max_units;            // hop units of samples in one push's input block at most (and of its output)
-    char *dev;                   // window | twiddles | lambda | A_prev | half frames | input block | output samples
+    StreamBlocks blk;            // device: window | twiddles | lambda | A_prev | half frames | input block | output samples
     size_t o_win, o_tw, o_lam, o_Ap, o_half, o_in, o_out, o_pcm;   // o_pcm: the samples' place in the input block, behind n_chan jobs
-    char *pin_in; float *pin_out;
 };
 
 static void lmstream_release(bp_lmstream *s)
 {
-    if (s->dev) (void)hipFree(s->dev);
-    if (s->pin_in) (void)hipHostFree(s->pin_in);
-    if (s->pin_out) (void)hipHostFree(s->pin_out);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
 }
@@ -360,7 +295,7 @@ extern "C" int bp_lmstream_counts(int fea_dim, int init_frames, int64_t received
     if (init_frames < 1) return fail(BP_ERR_ARG, "bp_lmstream_counts: need init_frames >= 1");
     if (received < 0) return fail(BP_ERR_ARG, "bp_lmstream_counts: received < 0");
     if (!frames_in || !frames_out || !samples_out) return fail(BP_ERR_ARG, "bp_lmstream_counts: null output");
-    const LmCounts c = lm_counts(fea_dim - 1, init_frames, received, ended != 0);
+    const Counts c = stream_counts(fea_dim - 1, 0, init_frames, received, ended != 0);
     *frames_in = c.fi; *frames_out = c.fo; *samples_out = c.so;
     return BP_OK;
 }
@@ -374,10 +309,7 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
     if (n_chan < 1 || n_chan > (1 << 16)) return fail(BP_ERR_ARG, "bp_lmstream_open: n_chan must be in 1 .. 65536");
     if (max_push_samples < 1) return fail(BP_ERR_ARG, "bp_lmstream_open: max_push_samples must be >= 1");
     if (!out) return fail(BP_ERR_ARG, "bp_lmstream_open: null pointer");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_lmstream_open: device ordinal out of range");
-    HIPCHK(hipSetDevice(device));
+    { const int r = use_device("bp_lmstream_open", device); if (r != BP_OK) return r; }
     const int D = fea_dim, hop = D - 1, N = 2 * hop, nc = n_chan;
     int lds_max = 0;
     HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
@@ -388,7 +320,6 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
     bp_lmstream *s = new (std::nothrow) bp_lmstream();
     if (!s) return fail(BP_ERR_NOMEM, "bp_lmstream_open: out of memory");
     s->device = device; s->D = D; s->hop = hop; s->log2M = log2M; s->n_chan = nc; s->max_push = max_push_samples; s->lp = lp;
-    s->st = nullptr; s->dev = nullptr; s->pin_in = nullptr; s->pin_out = nullptr;
     // A channel's job holds what waited -- fewer than init_frames hops of samples behind the hop of front padding -- and what
     // arrived, rounded up to frames, plus the two frames an end adds and the hop behind the last frame's start:
     // at most init_frames + n_in / hop + 4 hop units.
@@ -396,27 +327,24 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
     const size_t carry_cap = ((size_t)lp.init_frames + 2) * hop;
     if (s->max_units * hop > (size_t)INT32_MAX) { lmstream_release(s); return fail(BP_ERR_NOMEM, "bp_lmstream_open: the blocks of a push would exceed 2^31 samples"); }
     size_t o = 0;
-    s->o_win = o; o += lm_al256((size_t)N * 4);
-    s->o_tw = o; o += lm_al256((size_t)(hop + 1) * 8);
+    s->o_win = o; o += al256((size_t)N * 4);
+    s->o_tw = o; o += al256((size_t)(hop + 1) * 8);
     const size_t consts = o;
-    s->o_lam = o; o += lm_al256((size_t)nc * D * 8);
-    s->o_Ap = o; o += lm_al256((size_t)nc * D * 8);
-    s->o_half = o; o += lm_al256((size_t)nc * hop * 4);
+    s->o_lam = o; o += al256((size_t)nc * D * 8);
+    s->o_Ap = o; o += al256((size_t)nc * D * 8);
+    s->o_half = o; o += al256((size_t)nc * hop * 4);
     const size_t state_end = o;
-    s->o_pcm = lm_al256((size_t)nc * sizeof(LmJob));
-    const size_t in_cap = s->o_pcm + lm_al256(s->max_units * hop * 4), out_cap = lm_al256(s->max_units * hop * 4);
+    s->o_pcm = al256((size_t)nc * sizeof(LmJob));
+    const size_t in_cap = s->o_pcm + al256(s->max_units * hop * 4), out_cap = al256(s->max_units * hop * 4);
     s->o_in = o; o += in_cap;
     s->o_out = o; o += out_cap;
     hipError_t e = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
     if (e != hipSuccess) { lmstream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_lmstream_open: ") + hipGetErrorString(e)); }
-    e = hipMalloc((void **)&s->dev, o);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_in, std::max(in_cap, consts));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_out, out_cap);
+    e = s->blk.alloc(o, std::max(in_cap, consts), out_cap);
     bool host_ok = e == hipSuccess;
     if (host_ok) {
         try {
-            s->ch.resize(nc);
-            for (LmChan &ch : s->ch) { ch.received = 0; ch.carry_n = hop; ch.carry.assign(carry_cap, 0.0f); }
+            s->ch.assign(nc, Carry(carry_cap, hop));
             s->plan.resize(nc);
             s->jobs.reserve(nc);
         } catch (const std::bad_alloc &) { host_ok = false; }
@@ -427,11 +355,9 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
         return fail(BP_ERR_NOMEM, std::string("bp_lmstream_open: ") + (e != hipSuccess ? hipGetErrorString(e) : "out of host memory"));
     }
     // constants, once: window and twiddles (computed in double and rounded once, as bp_logmmse_waves does)
-    memset(s->pin_in, 0, consts);
-    wave_window_twiddles(log2M, (float *)(s->pin_in + s->o_win), (float2 *)(s->pin_in + s->o_tw));
-    e = hipMemcpyAsync(s->dev, s->pin_in, consts, hipMemcpyHostToDevice, s->st);
-    if (e == hipSuccess) e = hipMemsetAsync(s->dev + consts, 0, state_end - consts, s->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->st);
+    memset(s->blk.pin_in, 0, consts);
+    wave_window_twiddles(log2M, (float *)(s->blk.pin_in + s->o_win), (float2 *)(s->blk.pin_in + s->o_tw));
+    e = s->blk.upload_consts(consts, state_end, s->st);
     if (e != hipSuccess) { lmstream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_lmstream_open: ") + hipGetErrorString(e)); }
     *out = s;
     return BP_OK;
@@ -453,36 +379,26 @@ extern "C" int bp_lmstream_push(bp_lmstream *s, const int *n_in, const float *pc
     const int D = s->D, hop = s->hop, nc = s->n_chan, init = s->lp.init_frames;
     // ---- the plan: counts before and after, per channel (nothing of the stream changes until every check has passed)
     int64_t total_in = 0, due = 0, units = 0;
+    { const std::string m = stream_push_checks("bp_lmstream_push", nc, s->max_push, n_in, pcm, &total_in); if (!m.empty()) return fail(BP_ERR_ARG, m); }
     for (int c = 0; c < nc; ++c) {
-        if (n_in[c] < 0) return fail(BP_ERR_ARG, "bp_lmstream_push: n_in[" + std::to_string(c) + "] < 0");
-        total_in += n_in[c];
-        if (total_in > s->max_push)
-            return fail(BP_ERR_ARG, "bp_lmstream_push: more than max_push_samples = " + std::to_string(s->max_push) + " samples in one push");
-    }
-    if (total_in > 0 && !pcm) return fail(BP_ERR_ARG, "bp_lmstream_push: null pcm");
-    for (int c = 0; c < nc; ++c) {
-        LmPlan &p = s->plan[c];
-        const LmChan &ch = s->ch[c];
-        p.r1 = ch.received + n_in[c];
-        p.ended = end && end[c] && p.r1 > 0;
-        p.c0 = lm_counts(hop, init, ch.received, false);
-        p.c1 = lm_counts(hop, init, p.r1, p.ended);
+        ChanStep &p = s->plan[c];
+        p = stream_step(hop, 0, init, s->ch[c].received, n_in[c], end && end[c]);
         due += p.c1.so - p.c0.so;
         if (p.c1.fo > p.c0.fo) units += p.c1.fo - p.c0.fo + 1;
     }
-    if ((size_t)due > out_cap) return fail(BP_ERR_ARG, "bp_lmstream_push: " + std::to_string(due) + " samples are due, out_cap is " + std::to_string(out_cap));
-    if (due > 0 && !out_pcm) return fail(BP_ERR_ARG, "bp_lmstream_push: null out_pcm");
+    { const std::string m = stream_out_checks("bp_lmstream_push", due, out_cap, out_pcm); if (!m.empty()) return fail(BP_ERR_ARG, m); }
     if ((size_t)units > s->max_units || (size_t)due > s->max_units * hop)
         return fail(BP_ERR_STATE, "bp_lmstream_push: internal: more frames than the stream was sized for");
     // ---- the input block: one job per channel with output frames | their [carry | new] samples at hop-aligned places (the pinned
     // block is reused by every push: the previous one ended in a synchronisation); with it the channels' new carry
     s->jobs.clear();
-    float *hp = (float *)(s->pin_in + s->o_pcm);
+    char *pin = s->blk.pin_in, *dev = s->blk.dev;
+    float *hp = (float *)(pin + s->o_pcm);
     size_t unit = 0, src = 0;
     int64_t out_base = 0;
     for (int c = 0; c < nc; ++c) {
-        const LmPlan &p = s->plan[c];
-        LmChan &ch = s->ch[c];
+        const ChanStep &p = s->plan[c];
+        Carry &ch = s->ch[c];
         const float *in = pcm ? pcm + src : nullptr;
         const size_t n = (size_t)n_in[c];
         src += n;
@@ -490,11 +406,7 @@ extern "C" int bp_lmstream_push(bp_lmstream *s, const int *n_in, const float *pc
         n_out[c] = (int)(p.c1.so - p.c0.so);
         if (nf > 0) {
             // frame fo0 + i starts at unit + i; zeros behind a sentence's end
-            float *x = hp + unit * hop;
-            const size_t seg = (size_t)(nf + 1) * hop, nca = std::min(seg, ch.carry_n), nin = std::min(seg - nca, n);
-            memcpy(x, ch.carry.data(), nca * 4);
-            if (nin) memcpy(x + nca, in, nin * 4);
-            memset(x + nca + nin, 0, (seg - nca - nin) * 4);
+            ch.fill_segment(hp + unit * hop, (size_t)(nf + 1) * hop, in, n);
             LmJob j; memset(&j, 0, sizeof(j));
             j.chan = c; j.unit = (int)unit; j.t0 = (int)fo0; j.nf = (int)nf; j.ended = p.ended ? 1 : 0;
             j.out_off = (int)out_base; j.out_n = n_out[c];
@@ -503,41 +415,26 @@ extern "C" int bp_lmstream_push(bp_lmstream *s, const int *n_in, const float *pc
             out_base += n_out[c];
         }
         // the carry: a new sentence starts from hop zeros; else the last hop + r1 - fo1 hop samples of [carry | new]
-        if (p.ended) { ch.received = 0; ch.carry_n = hop; memset(ch.carry.data(), 0, (size_t)hop * 4); }
-        else if (n > 0) {
-            const size_t keep = (size_t)hop + (size_t)(p.r1 - fo1 * hop);
-            if (n >= keep) memcpy(ch.carry.data(), in + (n - keep), keep * 4);
-            else {
-                const size_t old = keep - n;                        // (old <= carry_n: carry_n + n >= keep)
-                memmove(ch.carry.data(), ch.carry.data() + (ch.carry_n - old), old * 4);
-                memcpy(ch.carry.data() + old, in, n * 4);
-            }
-            ch.carry_n = keep; ch.received = p.r1;
-        }
+        if (p.ended) ch.reset(hop);
+        else if (n > 0 && !ch.keep_last(in, n, (size_t)hop + (size_t)(p.r1 - fo1 * hop)))
+            return fail(BP_ERR_STATE, "bp_lmstream_push: internal: the carry exceeds its capacity");
     }
     if (s->jobs.empty()) return BP_OK;                              // no channel got a new output frame: no device work
     HIPCHK(hipSetDevice(s->device));
-    memcpy(s->pin_in, s->jobs.data(), s->jobs.size() * sizeof(LmJob));
-    char *din = s->dev + s->o_in;
-    HIPCHK(hipMemcpyAsync(din, s->pin_in, s->o_pcm + unit * hop * 4, hipMemcpyHostToDevice, s->st));
+    memcpy(pin, s->jobs.data(), s->jobs.size() * sizeof(LmJob));
+    char *din = dev + s->o_in;
+    HIPCHK(hipMemcpyAsync(din, pin, s->o_pcm + unit * hop * 4, hipMemcpyHostToDevice, s->st));
     LmStreamArgs a; memset(&a, 0, sizeof(a));
     a.jobs = (const LmJob *)din; a.pcm = (const float *)(din + s->o_pcm);
-    a.win = (const float *)(s->dev + s->o_win); a.tw = (const float2 *)(s->dev + s->o_tw);
-    a.lam = (double *)(s->dev + s->o_lam); a.Ap = (double *)(s->dev + s->o_Ap); a.half = (float *)(s->dev + s->o_half);
-    a.out = (float *)(s->dev + s->o_out);
+    a.win = (const float *)(dev + s->o_win); a.tw = (const float2 *)(dev + s->o_tw);
+    a.lam = (double *)(dev + s->o_lam); a.Ap = (double *)(dev + s->o_Ap); a.half = (float *)(dev + s->o_half);
+    a.out = (float *)(dev + s->o_out);
     a.log2M = s->log2M; a.D = D; a.init_frames = init;
     a.alpha = s->lp.alpha; a.mu = s->lp.mu; a.eta = s->lp.eta; a.xi_min = s->lp.xi_min; a.gamma_max = s->lp.gamma_max;
     const dim3 grid((unsigned)s->jobs.size()), blk(WAVE_THREADS);
     const size_t lds = lm_lds_bytes(hop);
-    switch ((D + WAVE_THREADS - 1) / WAVE_THREADS) {                // fea_dim 33 .. 129, 257, 513, 1025
-    case 1: hipLaunchKernelGGL(bp_lmstream_push<1>, grid, blk, lds, s->st, a); break;
-    case 2: hipLaunchKernelGGL(bp_lmstream_push<2>, grid, blk, lds, s->st, a); break;
-    case 3: hipLaunchKernelGGL(bp_lmstream_push<3>, grid, blk, lds, s->st, a); break;
-    default: hipLaunchKernelGGL(bp_lmstream_push<5>, grid, blk, lds, s->st, a); break;
-    }
+    with_nb(D, [&](auto nb) { hipLaunchKernelGGL(bp_lmstream_push<decltype(nb)::value>, grid, blk, lds, s->st, a); });
     HIPCHK(hipGetLastError());
-    if (due > 0) HIPCHK(hipMemcpyAsync(s->pin_out, s->dev + s->o_out, (size_t)due * 4, hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    if (due > 0) memcpy(out_pcm, s->pin_out, (size_t)due * 4);
+    HIPCHK(s->blk.copy_back(s->o_out, due, out_pcm, s->st));
     return BP_OK;
 }

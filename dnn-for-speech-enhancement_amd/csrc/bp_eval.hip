@@ -1,6 +1,7 @@
 // bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 9: objective scores of enhanced speech.  Segmental SNR,
 // log-spectral distortion on the 1d analysis and STOI of estimates against a reference (bp_score_waves here; bp_eval_mix in
-// bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.
+// bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame
+// plan and padded layout from bp_wave.hip (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
 //
 // Kernels (signal 0 is the reference, 1 .. nsig-1 the estimates; blockIdx.y picks the signal; a flat grid of workgroups finds its
 // sentence by a binary search over a prefix table, as bp_wave_analysis does over F):
@@ -235,8 +236,6 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_trim(const int64_t *__re
 // ------------------------------------------------------------------ host side
 namespace {
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // Where the tables lie in the table block (all offsets 256-byte aligned).
 struct TabLayout {
     size_t off, len, pre[12], h, v, tw, w, bytes;   // pre: the prefix tables in EvalPlan order
@@ -422,58 +421,38 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
                               float *scores)
 {
     const char *who = "bp_score_waves";
-    const int log2M = wave_log2_fft(fea_dim);
-    if (log2M < 0) return fail(BP_ERR_ARG, "bp_score_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, "bp_score_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
     { int p, q; if (!eval_rate(sample_rate, &p, &q)) return fail(BP_ERR_ARG, "bp_score_waves: sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32"); }
-    if (n_sent < 1 || !sent_len || !ref || !est || !scores) return fail(BP_ERR_ARG, "bp_score_waves: no sentences or null pointer");
-    const int M = 1 << log2M, hop = M, N = 2 * M, D = fea_dim;
-    std::vector<int> F((size_t)n_sent + 1, 0);
+    if (!est || !scores) return fail(BP_ERR_ARG, "bp_score_waves: no sentences or null pointer");
+    WavePlan wp;
+    { const int r = plan_waves(who, fea_dim, n_sent, sent_len, ref, (size_t)INT32_MAX / 8, wp); if (r != BP_OK) return r; }
+    const int D = fea_dim;
+    const size_t f = wp.frames, padded = wp.padded;
     std::vector<int64_t> off(n_sent);
-    size_t f = 0;
-    for (int s = 0; s < n_sent; ++s) {
-        if (sent_len[s] < 1) return fail(BP_ERR_ARG, "bp_score_waves: empty sentence " + std::to_string(s));
-        off[s] = ((int64_t)f + s + 1) * hop;                     // the padded layout of bp_wave_lps
-        f += (size_t)((sent_len[s] - 1) / hop + 2);
-        if (f > (size_t)INT32_MAX / 8) return fail(BP_ERR_ARG, "bp_score_waves: too many frames in one call");
-        F[s + 1] = (int)f;
-    }
+    for (int s = 0; s < n_sent; ++s) off[s] = ((int64_t)wp.F[s] + s + 1) * wp.hop;   // the padded layout of bp_wave_lps
     EvalPlan ep;
-    { const int r = eval_plan(who, sample_rate, D, n_sent, sent_len, off.data(), F.data(), ep); if (r != BP_OK) return r; }
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_score_waves: device ordinal out of range");
-    HIPCHK(hipSetDevice(device));
+    { const int r = eval_plan(who, sample_rate, D, n_sent, sent_len, off.data(), wp.F.data(), ep); if (r != BP_OK) return r; }
     // one host->device block: tables | analysis window | twiddles | padded reference | padded estimate
-    const size_t padded = (f + (size_t)n_sent) * hop;
-    const size_t o_win = al256(ep.t_bytes), o_tw = o_win + al256((size_t)N * 4), o_ref = o_tw + al256((size_t)(M + 1) * 8);
+    const size_t o_win = al256(ep.t_bytes), o_tw = o_win + al256((size_t)wp.N * 4), o_ref = o_tw + al256((size_t)(wp.M + 1) * 8);
     const size_t o_est = o_ref + al256(padded * 4), in_b = o_est + al256(padded * 4);
     const size_t o_lps = in_b, lps_b = f * D * 4, o_sc = o_lps + 2 * al256(lps_b), o_work = o_sc + al256((size_t)n_sent * BP_SCORE_N * 4);
-    const size_t total = o_work + eval_work_bytes(ep, 2);
+    OneShot os;
+    { const int r = os.open(who, device, o_work + eval_work_bytes(ep, 2)); if (r != BP_OK) return r; }
     std::vector<char> hb(in_b, 0);
     eval_fill(ep, hb.data());
-    wave_window_twiddles(log2M, (float *)(hb.data() + o_win), (float2 *)(hb.data() + o_tw));
-    {
-        float *xr = (float *)(hb.data() + o_ref), *xe = (float *)(hb.data() + o_est);
-        size_t src = 0;
-        for (int s = 0; s < n_sent; ++s) {
-            memcpy(xr + off[s], ref + src, (size_t)sent_len[s] * 4);
-            memcpy(xe + off[s], est + src, (size_t)sent_len[s] * 4);
-            src += (size_t)sent_len[s];
-        }
-    }
-    hipStream_t st = nullptr;
-    char *d = nullptr;
-    int rc = BP_OK;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, st);
+    wave_window_twiddles(wp.log2M, (float *)(hb.data() + o_win), (float2 *)(hb.data() + o_tw));
+    wave_scatter((float *)(hb.data() + o_ref), wp, sent_len, ref);
+    wave_scatter((float *)(hb.data() + o_est), wp, sent_len, est);
+    hipError_t &e = os.e;
+    char *d = os.d;
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
         a.pcm = (const float *)(d + (k ? o_est : o_ref)); a.win = (const float *)(d + o_win); a.tw = (const float2 *)(d + o_tw);
         a.F = (const int *)(d + tab_layout(ep).pre[10]);
-        a.n_sent = n_sent; a.log2M = log2M; a.D = D; a.hop = hop; a.ctx = 1;
+        a.n_sent = n_sent; a.log2M = wp.log2M; a.D = D; a.hop = wp.hop; a.ctx = 1;
         a.lps = (float *)(d + o_lps + k * al256(lps_b));
-        e = wave_analysis_launch(a, (int)f, st);
+        e = wave_analysis_launch(a, (int)f, os.st);
     }
     if (e == hipSuccess) {
         EvalDev v; memset(&v, 0, sizeof(v));
@@ -481,12 +460,8 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
         v.sig[0] = (const float *)(d + o_ref); v.sig[1] = (const float *)(d + o_est);
         v.lps[0] = (const float *)(d + o_lps); v.lps[1] = (const float *)(d + o_lps + al256(lps_b));
         v.scores = (float *)(d + o_sc);
-        e = eval_launch(ep, v, 2, st);
+        e = eval_launch(ep, v, 2, os.st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(scores, d + o_sc, (size_t)n_sent * BP_SCORE_N * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_score_waves: ") + hipGetErrorString(e));
-    if (d) (void)hipFree(d);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(scores, d + o_sc, (size_t)n_sent * BP_SCORE_N * 4, hipMemcpyDeviceToHost, os.st);
+    return os.finish(who);
 }

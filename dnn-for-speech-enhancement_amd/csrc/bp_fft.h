@@ -1,6 +1,8 @@
 // bp_fft.h -- what the signal-layer translation units share (bp_wave.hip: enhancement and LPS features; bp_mix.hip: training
-// mixtures made on the device; bp_eval.hip: objective scores): the real FFT of one analysis frame in LDS, the analysis kernel's arguments and host-side launchers
-// of the bp_wave.hip kernels.  Internal: nothing in here is part of the C ABI.
+// mixtures made on the device; bp_eval.hip: objective scores; bp_stream.hip and bp_classic.hip: streams and the log-MMSE baseline):
+// on the device the real FFT of one analysis frame in LDS, the synthesis of a frame, the overlap-add and its clipped store; on the
+// host the frame plan of a call with its padded layout, the analysis kernel's arguments and the launchers of the bp_wave.hip
+// kernels.  Internal: nothing in here is part of the C ABI.
 //
 // Signal definition: n_fft = 2 (fea_dim - 1) = 2M, hop = M, periodic Hamming window.  A real frame of 2M
 // samples is transformed as a complex FFT of M points z[m] = (x[2m], x[2m+1]) followed by the split step.
@@ -131,6 +133,32 @@ __device__ __forceinline__ float4 overlap4(float4 a, float4 b, float4 wa, float4
                        (a.z + b.z) / fmaf(wa.z, wa.z, wb.z * wb.z), (a.w + b.w) / fmaf(wa.w, wa.w, wb.w * wb.w));
 }
 
+// The overlap-add of one segment of hop samples into a compact output that is only 4-byte aligned (bp_stream_synthesis,
+// bp_lmstream_push): cur the frame that starts at the segment, prev_half the second half of the frame before it; the first n
+// samples are stored (n >= hop: all of them; n <= 0: none), one scalar store each.  Every thread of the workgroup calls it;
+// threads: their number, spelled as the caller's own loops spell it (blockDim.x or WAVE_THREADS), so that each kernel keeps its code.
+__device__ __forceinline__ void overlap_store(const float *cur, const float *prev_half, const float *__restrict__ win, int hop, float *dst, int n,
+                                              int threads)
+{
+    for (int q = threadIdx.x; q < hop / 4; q += threads) {
+        const float4 x = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(prev_half + 4 * q);
+        const float4 wa = *reinterpret_cast<const float4 *>(win + 4 * q), wb = *reinterpret_cast<const float4 *>(win + hop + 4 * q);
+        const float4 r = overlap4(x, b, wa, wb);
+        const int i = 4 * q;
+        if (i < n) dst[i] = r.x;
+        if (i + 1 < n) dst[i + 1] = r.y;
+        if (i + 2 < n) dst[i + 2] = r.z;
+        if (i + 3 < n) dst[i + 3] = r.w;
+    }
+}
+
+// Half a frame (hop samples, 16-byte aligned at both ends) between the LDS frames and a channel's carried half
+__device__ __forceinline__ void copy_half(float *dst, const float *src, int hop, int threads)
+{
+    for (int q = threadIdx.x; q < hop / 4; q += threads)
+        *reinterpret_cast<float4 *>(dst + 4 * q) = *reinterpret_cast<const float4 *>(src + 4 * q);
+}
+
 }  // namespace
 
 // bp_wave_analysis arguments (bp_wave.hip): frame g of sentence s reads the padded samples [(g + s) hop, (g + s) hop + n_fft).
@@ -143,8 +171,25 @@ struct WaveAnaArgs {
     int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
 };
 
-// Host side of bp_wave.hip, for bp_mix.hip and bp_eval.hip
+// Host side of bp_wave.hip, for the other signal-layer units
 int wave_log2_fft(int fea_dim);                                   // log2 of M, or -1 outside 1d's range
+// Frame plan of a call: T_s = (sent_len[s] - 1) / hop + 2 frames per sentence, F = prefix sums; in the padded layout sentence s
+// has T_s + 1 segments of hop samples and its first sample lies at (F[s] + s + 1) hop.  plan_waves checks (fea_dim, the
+// pointers, no empty sentence, at most max_frames frames) before any device work, with the caller's name in the messages.
+struct WavePlan {
+    int M, N, hop, log2M, n_sent;
+    std::vector<int> F;                                  // [n_sent + 1]
+    size_t frames, padded;                               // frames of the call, padded samples of a PCM buffer
+};
+int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, size_t max_frames, WavePlan &p);
+void wave_scatter(float *dst, const WavePlan &p, const int *sent_len, const float *pcm);   // the sentences to their padded places (dst: zeros)
+void wave_gather(float *out, const WavePlan &p, const int *sent_len, const float *src);    // ... and back, the padding trimmed
+// The single host->device block of a call: F | mean | inv_std | window | twiddles | padded PCM, each 256-byte aligned; filled on the
+// host (mean null: no norm file; window and twiddles as wave_window_twiddles makes them)
+struct WaveIn { size_t F, mean, istd, win, tw, pcm, bytes; };
+WaveIn wave_in_layout(const WavePlan &p, int D);
+void wave_in_fill(char *hb, const WaveIn &w, const WavePlan &p, int D, const float *mean, const float *inv_std, const int *sent_len,
+                  const float *pcm);
 void wave_window_twiddles(int log2M, float *win, float2 *tw);     // win[2M], tw[M + 1], computed in double and rounded once
 int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st);   // grow-only device / pinned host buffer
 hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st);

@@ -10,7 +10,10 @@
 //   bp_mix.hip      training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...)
 //   bp_eval.hip     objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval_mix lives in bp_mix.hip)
 //   bp_stream.hip   streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
-//   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in bp_mix.hip)
+//   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in
+//                   bp_mix.hip) and its streams (bp_lmstream_open, _push, ...)
+//   (bp_fft.h: the device functions and the frame plan of the signal-layer units; bp_stream_core.h: counts, carry, push checks and
+//   the block owner of the two streaming engines)
 //   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
@@ -41,6 +44,7 @@ static inline int fail(int code, const std::string &msg) { g_bp_err = msg; retur
     } while (0)
 
 static inline int pad64(int x) { return (x + 63) & ~63; }
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }   // the parts of a device block start 256-byte aligned
 
 // Development switches (A/B aids of the measurements quoted in DESIGN.md): environment variables that only a library
 // built with -DBP_DEV (`make dev` -> libbp_hip_dev.so, loaded through BP_HIP_LIB) reads.  The shipped library has ONE
@@ -142,6 +146,38 @@ int dev_alloc(bp_handle *h, float **p, size_t n_floats);
 // launch is the time between the previous event and its own (= kernel + the dependent-launch boundary in front of it).
 struct StepProf {
     std::vector<hipEvent_t> ev; std::vector<int> kind; size_t used;
+};
+
+// ------------------------------------------------------------------ calls without a handle
+// BP_OK once `device` is a valid ordinal and current
+static inline int use_device(const char *who, int device)
+{
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, std::string(who) + ": device ordinal out of range");
+    HIPCHK(hipSetDevice(device));
+    return BP_OK;
+}
+// The device side of a one-shot call (bp_wave_lps, bp_logmmse_waves, bp_score_waves, bp_reverb_waves): a stream and one device
+// block, both freed when the holder goes.  e is sticky: the call chains its copies and launches with `if (e == hipSuccess) e = ...`,
+// finish() synchronises and turns the first error into BP_ERR_DEVICE "<who>: <hip error string>".
+struct OneShot {
+    hipStream_t st = nullptr;
+    char *d = nullptr;
+    hipError_t e = hipSuccess;
+    ~OneShot() { if (d) (void)hipFree(d); if (st) (void)hipStreamDestroy(st); }
+    int open(const char *who, int device, size_t bytes)
+    {
+        { const int r = use_device(who, device); if (r != BP_OK) return r; }
+        e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipMalloc((void **)&d, bytes);
+        return BP_OK;
+    }
+    int finish(const char *who)
+    {
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        return e == hipSuccess ? BP_OK : fail(BP_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
 };
 
 // ------------------------------------------------------------------ step operations (bp_step.hip)

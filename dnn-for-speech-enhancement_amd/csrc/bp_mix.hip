@@ -1,7 +1,7 @@
 // bp_mix.hip -- C-ABI implementation (include/bp_c_api.h), part 5 of 9: training mixtures made on the device.  A clean-speech
 // corpus and a noise corpus stay resident on the handle (bp_set_mix_corpus); every call mixes its list of {clean, noise, offset,
 // SNR} on the device, runs the analysis of bp_wave.hip on the mixtures and writes the window chunk that the training / CV step
-// reads.  gfx950 only.
+// reads.  gfx950 only.  (bp_reverb_waves, the one call here without a handle, runs in a OneShot of bp_handle.h.)
 //
 // Device layout of one call: mixture m is a "sentence" of bp_wave.hip's padded layout -- its T_m + 1 segments of hop samples start
 // at segment Fs[m] = F[m] + m (F = prefix sums of T), sample i of the mixture lies at padded sample (Fs[m] + 1) hop + i, and frame
@@ -272,7 +272,6 @@ struct MixState {
 
 namespace {
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void free_raw(bp_handle::Raw &r, bool pinned)
 {
@@ -897,36 +896,28 @@ extern "C" int bp_reverb_waves(int device, int n_sent, const int *sent_len, cons
     }
     const int64_t blocks = fill_jobs(job, off, delay, rir_len, early_taps);
     if (blocks > INT32_MAX) return fail(BP_ERR_ARG, "bp_reverb_waves: too many samples for one call");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_reverb_waves: device ordinal out of range");
-    HIPCHK(hipSetDevice(device));
     // one input block: jobs | sentences | responses; one output block: r | e (whichever are asked for)
     const bool early = out_early != nullptr;
     const size_t o_pcm = al256(job.size() * sizeof(ReverbJob)), o_rir = o_pcm + al256((size_t)tot * 4);
     const size_t in_b = o_rir + al256((size_t)off[n_rir] * 4), sig_b = (size_t)tot * 4, out_b = sig_b * ((out_rev ? 1 : 0) + (early ? 1 : 0));
+    OneShot os;
+    if ((rc = os.open("bp_reverb_waves", device, in_b + out_b)) != BP_OK) return rc;
     std::vector<char> hb(in_b), ho(out_rev && early ? out_b : 0);
     memcpy(hb.data(), job.data(), job.size() * sizeof(ReverbJob));
     memcpy(hb.data() + o_pcm, pcm, sig_b);
     memcpy(hb.data() + o_rir, rir_pcm, (size_t)off[n_rir] * 4);
-    hipStream_t st = nullptr;
-    char *d = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, in_b + out_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, st);
+    hipError_t &e = os.e;
+    char *d = os.d;
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
     if (e == hipSuccess) {
         ReverbArgs a; memset(&a, 0, sizeof(a));
         a.job = (const ReverbJob *)d; a.n_job = n_sent; a.src = (const float *)(d + o_pcm); a.rir = (const float *)(d + o_rir);
         a.out_r = out_rev ? (float *)(d + in_b) : nullptr;
         a.out_e = early ? (float *)(d + in_b + (out_rev ? sig_b : 0)) : nullptr;
-        e = reverb_launch(a, blocks, early, st);
+        e = reverb_launch(a, blocks, early, os.st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(ho.empty() ? (char *)(out_rev ? out_rev : out_early) : ho.data(), d + in_b, out_b, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    rc = BP_OK;
-    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_reverb_waves: ") + hipGetErrorString(e));
-    else if (!ho.empty()) { memcpy(out_rev, ho.data(), sig_b); memcpy(out_early, ho.data() + sig_b, sig_b); }
-    if (d) (void)hipFree(d);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(ho.empty() ? (char *)(out_rev ? out_rev : out_early) : ho.data(), d + in_b, out_b, hipMemcpyDeviceToHost, os.st);
+    if ((rc = os.finish("bp_reverb_waves")) != BP_OK) return rc;
+    if (!ho.empty()) { memcpy(out_rev, ho.data(), sig_b); memcpy(out_early, ho.data() + sig_b, sig_b); }
+    return BP_OK;
 }

@@ -3,10 +3,10 @@
 // call on the finished sentence: the analysis and the synthesis are the device functions of bp_wave.hip (bp_fft.h), the forward
 // is forward_resident on a window chunk, and the overlap-add is the same gather of two frames.  gfx950 only.
 //
-// What a channel has after `received` samples of its sentence is a pure function of that number (stream_counts, exported as
-// bp_stream_counts): frames analysed fi, frames enhanced fo, samples returned.  The host plans a push from those numbers alone
-// and never reads device state.  It keeps each channel's carry -- the last hop + received % hop samples -- and builds ONE
-// pinned input block per push: three job tables and every active channel's [carry | new] samples at hop-aligned places, so
+// What a channel has after `received` samples of its sentence is a pure function of that number (stream_counts in
+// bp_stream_core.h, exported as bp_stream_counts): frames analysed fi, frames enhanced fo, samples returned.  The host plans a
+// push from those numbers alone and never reads device state.  It keeps each channel's carry (bp_stream_core.h: here the last
+// hop + received % hop samples) and builds ONE pinned input block per push: three job tables and every active channel's [carry | new] samples at hop-aligned places, so
 // that the frame loads of the analysis are the aligned 16-byte loads of rfft_frame.
 //
 // Device state of a channel (allocated at open, R = context + 6 slots, all of it double-buffered by a parity that the host flips
@@ -42,6 +42,7 @@
 
 #include "bp_fft.h"
 #include "bp_handle.h"
+#include "bp_stream_core.h"
 
 namespace {
 
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_stream_synthesis(const Stream
     extern __shared__ __align__(16) float2 zs[];
     float2 *z = zs;
     const SynJob j = a.jobs[blockIdx.x];
-    const int M = 1 << a.log2M, N = 2 * M, hop = M, tid = threadIdx.x;
+    const int M = 1 << a.log2M, N = 2 * M, hop = M;
     float *cur = reinterpret_cast<float *>(zs) + syn_frames_at(M), *prev = cur + N;   // two frames behind synth_frame's space
     synth_frame(z, a.out + (size_t)j.g * a.ldo + a.out_col, a.Y + (size_t)j.y * a.D, a.win, a.tw, a.log2M, a.target, cur);
     __syncthreads();
@@ -143,81 +144,41 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_stream_synthesis(const Stream
     }
     if (j.prev >= 0) {
         const float *pv = j.prev == 0 ? prev + hop : a.half + (size_t)j.half_src * hop;
-        float *dst = a.pcm + j.out_off;                 // compact: only 4-byte aligned
-        for (int q = tid; q < hop / 4; q += blockDim.x) {
-            const float4 x = *reinterpret_cast<const float4 *>(cur + 4 * q), b = *reinterpret_cast<const float4 *>(pv + 4 * q);
-            const float4 wa = *reinterpret_cast<const float4 *>(a.win + 4 * q), wb = *reinterpret_cast<const float4 *>(a.win + hop + 4 * q);
-            const float4 r = overlap4(x, b, wa, wb);
-            const int i = 4 * q;
-            if (i < j.out_n) dst[i] = r.x;
-            if (i + 1 < j.out_n) dst[i + 1] = r.y;
-            if (i + 2 < j.out_n) dst[i + 2] = r.z;
-            if (i + 3 < j.out_n) dst[i + 3] = r.w;
-        }
+        overlap_store(cur, pv, a.win, hop, a.pcm + j.out_off, j.out_n, blockDim.x);
     }
-    if (j.half_dst >= 0) {
-        float *hd = a.half + (size_t)j.half_dst * hop;
-        for (int q = tid; q < hop / 4; q += blockDim.x)
-            *reinterpret_cast<float4 *>(hd + 4 * q) = *reinterpret_cast<const float4 *>(cur + hop + 4 * q);
-    }
+    if (j.half_dst >= 0) copy_half(a.half + (size_t)j.half_dst * hop, cur + hop, hop, blockDim.x);
 }
 
 // ------------------------------------------------------------------ host side
 namespace {
 
-// What a channel has produced after `received` samples of its sentence (include/bp_c_api.h)
-struct Counts { int64_t fi, fo, so; };
-Counts stream_counts(int hop, int la, bool nat, int64_t received, bool ended)
-{
-    Counts c = {0, 0, 0};
-    if (received <= 0) return c;
-    const int64_t T = (received - 1) / hop + 2;
-    c.fi = ended ? T : received / hop;
-    const bool known = !nat || ended || c.fi >= 6;
-    c.fo = !known ? 0 : ended ? T : std::max<int64_t>(0, c.fi - la);
-    c.so = ended ? received : std::max<int64_t>(0, c.fo - 1) * hop;
-    return c;
-}
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct Chan {
-    int64_t received;            // samples of the current sentence
     int par, hpar;               // parity of the rows / Y state and of the carried half frame
-    int carry_n;                 // hop + received % hop
-    std::vector<float> carry;    // [2 hop]: the samples the next frame starts with (hop zeros in front of a sentence)
+    Carry carry;                 // [2 hop]: the samples the next frame starts with, hop + received % hop of them
 };
 
 // plan of one channel for one push
-struct ChanPlan { int64_t r1, g0; bool ended; Counts c0, c1; };   // g0: the chunk sample of the channel's first frame
+struct ChanPlan : ChanStep { int64_t g0; };   // g0: the chunk sample of the channel's first frame
 
 }  // namespace
 
 struct bp_stream {
     bp_handle *h;
     int D, ctx, toff, la, target, out_col, n_chan, max_push, hop, log2M, R;
+    int warm;                    // frames before the first is enhanced: 6 with a noise-aware row (nat), else 0
     bool nat;
     bool packed;                 // opened in BP_FORWARD_ROWINV: dense placement, the row-invariant forward on every push
     std::vector<Chan> ch;
     std::vector<ChanPlan> plan;
     std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<SynJob> syn;
     size_t max_enh;              // samples (frames to enhance) of one push at most
-    char *dev;                   // consts | state | input block | Y of the push | output samples
+    StreamBlocks blk;            // device: consts | state | input block | Y of the push | output samples
     size_t o_mean, o_istd, o_win, o_tw, o_rows, o_Y, o_nat, o_half, o_in, o_pY, o_out, in_cap;
-    char *pin_in; float *pin_out;
 };
-
-static void stream_release(bp_stream *s)
-{
-    if (s->dev) (void)hipFree(s->dev);
-    if (s->pin_in) (void)hipHostFree(s->pin_in);
-    if (s->pin_out) (void)hipHostFree(s->pin_out);
-    delete s;
-}
 
 void stream_free_all(bp_handle *h)
 {
-    for (bp_stream *s : h->streams) stream_release(s);
+    for (bp_stream *s : h->streams) delete s;
     h->streams.clear();
 }
 
@@ -234,7 +195,7 @@ extern "C" int bp_stream_counts(int fea_dim, int context, int targ_offset, int n
     { const int r = stream_cfg_check("bp_stream_counts", fea_dim, context, targ_offset); if (r != BP_OK) return r; }
     if (received < 0) return fail(BP_ERR_ARG, "bp_stream_counts: received < 0");
     if (!frames_in || !frames_out || !samples_out) return fail(BP_ERR_ARG, "bp_stream_counts: null output");
-    const Counts c = stream_counts(fea_dim - 1, context - 1 - targ_offset, nat != 0, received, ended != 0);
+    const Counts c = stream_counts(fea_dim - 1, context - 1 - targ_offset, nat ? 6 : 0, received, ended != 0);
     *frames_in = c.fi; *frames_out = c.fo; *samples_out = c.so;
     return BP_OK;
 }
@@ -258,7 +219,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     bp_stream *s = new bp_stream();
     s->h = h; s->D = D; s->ctx = ctx; s->toff = c->targ_offset; s->la = ctx - 1 - c->targ_offset; s->target = c->target;
     s->out_col = c->out_col; s->n_chan = c->n_chan; s->max_push = c->max_push_samples; s->hop = D - 1; s->log2M = wave_log2_fft(D);
-    s->R = ctx + 6; s->nat = nat; s->packed = h->fwd_mode == BP_FORWARD_ROWINV;
+    s->R = ctx + 6; s->nat = nat; s->warm = nat ? 6 : 0; s->packed = h->fwd_mode == BP_FORWARD_ROWINV;
     const int hop = s->hop, N = 2 * hop, nc = s->n_chan;
     // A push analyses at most n_in/hop + 3 frames per channel (the end of a sentence adds up to 3) and enhances those plus the
     // frames that waited; it can never enhance more than the chunk capacity lets it stage.
@@ -281,23 +242,19 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     s->o_in = o; o += s->in_cap;
     s->o_pY = o; o += al256(s->max_enh * D * 8);
     s->o_out = o; o += al256(s->max_enh * hop * 4);
-    hipError_t e = hipMalloc((void **)&s->dev, o);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_in, std::max(s->in_cap, consts));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->pin_out, al256(s->max_enh * hop * 4));
-    if (e != hipSuccess) { stream_release(s); return fail(BP_ERR_NOMEM, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
+    hipError_t e = s->blk.alloc(o, std::max(s->in_cap, consts), al256(s->max_enh * hop * 4));
+    if (e != hipSuccess) { delete s; return fail(BP_ERR_NOMEM, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
     int r = out_chunk_reserve(h, (int)(s->max_enh + (size_t)nc * h->B));   // (fillers included: so that no push has to grow it)
-    if (r != BP_OK) { stream_release(s); return r; }
+    if (r != BP_OK) { delete s; return r; }
     // constants, once: the norm file, window and twiddles (computed in double and rounded once, as bp_enhance_waves does)
-    memset(s->pin_in, 0, consts);
-    memcpy(s->pin_in + s->o_mean, c->mean, (size_t)D * 4);
-    memcpy(s->pin_in + s->o_istd, c->inv_std, (size_t)D * 4);
-    wave_window_twiddles(s->log2M, (float *)(s->pin_in + s->o_win), (float2 *)(s->pin_in + s->o_tw));
-    e = hipMemcpyAsync(s->dev, s->pin_in, consts, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->dev + s->o_rows, 0, s->o_in - s->o_rows, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { stream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
-    s->ch.resize(nc);
-    for (Chan &ch : s->ch) { ch.received = 0; ch.par = ch.hpar = 0; ch.carry_n = hop; ch.carry.assign((size_t)2 * hop, 0.0f); }
+    char *pin = s->blk.pin_in;
+    memset(pin, 0, consts);
+    memcpy(pin + s->o_mean, c->mean, (size_t)D * 4);
+    memcpy(pin + s->o_istd, c->inv_std, (size_t)D * 4);
+    wave_window_twiddles(s->log2M, (float *)(pin + s->o_win), (float2 *)(pin + s->o_tw));
+    e = s->blk.upload_consts(consts, s->o_in, h->stream);
+    if (e != hipSuccess) { delete s; return fail(BP_ERR_DEVICE, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
+    s->ch.assign(nc, Chan{0, 0, Carry((size_t)2 * hop, hop)});
     s->plan.resize(nc);
     s->ana.reserve(max_ana); s->natj.reserve(nc); s->syn.reserve(s->max_enh);
     h->streams.push_back(s);
@@ -314,7 +271,7 @@ extern "C" int bp_stream_close(bp_stream *s)
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
     h->streams.erase(std::remove(h->streams.begin(), h->streams.end(), s), h->streams.end());
-    stream_release(s);
+    delete s;
     return BP_OK;
 }
 
@@ -327,20 +284,10 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     const int D = s->D, ctx = s->ctx, toff = s->toff, hop = s->hop, nc = s->n_chan, R = s->R, L = h->L, B = h->B;
     // ---- the plan: counts before and after, per channel (nothing of the stream changes until every check has passed)
     int64_t total_in = 0, due = 0, n = 0, n_enh = 0, rows = 0, ana_max = 0, active = 0;
-    for (int c = 0; c < nc; ++c) {
-        if (n_in[c] < 0) return fail(BP_ERR_ARG, "bp_stream_push: n_in[" + std::to_string(c) + "] < 0");
-        total_in += n_in[c];
-        if (total_in > s->max_push)
-            return fail(BP_ERR_ARG, "bp_stream_push: more than max_push_samples = " + std::to_string(s->max_push) + " samples in one push");
-    }
-    if (total_in > 0 && !pcm) return fail(BP_ERR_ARG, "bp_stream_push: null pcm");
+    { const std::string m = stream_push_checks("bp_stream_push", nc, s->max_push, n_in, pcm, &total_in); if (!m.empty()) return fail(BP_ERR_ARG, m); }
     for (int c = 0; c < nc; ++c) {
         ChanPlan &p = s->plan[c];
-        const Chan &ch = s->ch[c];
-        p.r1 = ch.received + n_in[c];
-        p.ended = end && end[c] && p.r1 > 0;
-        p.c0 = stream_counts(hop, s->la, s->nat, ch.received, false);
-        p.c1 = stream_counts(hop, s->la, s->nat, p.r1, p.ended);
+        static_cast<ChanStep &>(p) = stream_step(hop, s->la, s->warm, s->ch[c].carry.received, n_in[c], end && end[c]);
         const int64_t ne = p.c1.fo - p.c0.fo;
         due += p.c1.so - p.c0.so; n_enh += ne;
         if (ne > 0) { p.g0 = s->packed ? n : n + ((p.c0.fo - n) % B + B) % B; n = p.g0 + ne; }      // frame t as row t mod B of its bunch; packed: any row
@@ -349,8 +296,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         if (!p.ended && p.c1.fi - std::max<int64_t>(0, p.c1.fo - toff) > R)
             return fail(BP_ERR_STATE, "bp_stream_push: internal: channel state exceeds context + 6 frames");
     }
-    if ((size_t)due > out_cap) return fail(BP_ERR_ARG, "bp_stream_push: " + std::to_string(due) + " samples are due, out_cap is " + std::to_string(out_cap));
-    if (due > 0 && !out_pcm) return fail(BP_ERR_ARG, "bp_stream_push: null out_pcm");
+    { const std::string m = stream_out_checks("bp_stream_push", due, out_cap, out_pcm); if (!m.empty()) return fail(BP_ERR_ARG, m); }
     if (rows > h->cap)
         return fail(BP_ERR_ARG, "bp_stream_push: " + std::to_string(rows) + " rows (frames + context-1 per active channel) exceed the chunk capacity " +
                                 std::to_string(h->cap));
@@ -367,7 +313,8 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     s->ana.clear(); s->natj.clear(); s->syn.clear();
     const size_t o_ana = 0, o_nat = o_ana + al256((size_t)ana_max * sizeof(AnaJob)), o_syn = o_nat + al256((size_t)active * sizeof(NatJob));
     const size_t o_pcm = o_syn + al256((size_t)n_enh * sizeof(SynJob));
-    float *hp = (float *)(s->pin_in + o_pcm);
+    char *pin = s->blk.pin_in, *dev = s->blk.dev;
+    float *hp = (float *)(pin + o_pcm);
     size_t unit = 0, src = 0;
     int64_t y0 = 0, srow = 0, out_base = 0;
     for (int c = 0; c < nc; ++c) {
@@ -378,11 +325,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         const int64_t fi0 = p.c0.fi, fi1 = p.c1.fi, fo0 = p.c0.fo, fo1 = p.c1.fo, nf = fi1 - fi0, ne = fo1 - fo0;
         if (nf > 0) {
             // [carry | new] at hop unit `unit`, zeros behind a sentence's end: frame t starts at unit + t - fi0
-            float *x = hp + unit * hop;
-            const size_t seg = (size_t)(nf + 1) * hop, nca = std::min(seg, (size_t)ch.carry_n), nin = std::min(seg - nca, (size_t)n_in[c]);
-            memcpy(x, ch.carry.data(), nca * 4);
-            if (nin) memcpy(x + nca, in, nin * 4);
-            memset(x + nca + nin, 0, (seg - nca - nin) * 4);
+            ch.carry.fill_segment(hp + unit * hop, (size_t)(nf + 1) * hop, in, (size_t)n_in[c]);
             const int64_t base0 = std::max<int64_t>(0, fo0 - toff), base1 = std::max<int64_t>(0, fo1 - toff), T = fi1;
             const int64_t srows = ne > 0 ? ne + ctx - 1 : 0;
             const int slot0 = (ch.par * nc + c) * R, slot1 = ((ch.par ^ 1) * nc + c) * R;
@@ -430,34 +373,26 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         }
         n_out[c] = (int)(p.c1.so - p.c0.so);
         // the carry: the last hop + r1 % hop samples of [carry | new]; a new sentence starts from hop zeros
-        if (p.ended) { ch.received = 0; ch.carry_n = hop; memset(ch.carry.data(), 0, (size_t)hop * 4); }
-        else if (n_in[c] > 0) {
-            const int keep = hop + (int)(p.r1 % hop);
-            if (n_in[c] >= keep) memcpy(ch.carry.data(), in + (n_in[c] - keep), (size_t)keep * 4);
-            else {
-                const int old = keep - n_in[c];                     // (old <= carry_n: carry_n + n_in >= keep)
-                memmove(ch.carry.data(), ch.carry.data() + (ch.carry_n - old), (size_t)old * 4);
-                memcpy(ch.carry.data() + old, in, (size_t)n_in[c] * 4);
-            }
-            ch.carry_n = keep; ch.received = p.r1;
-        }
+        if (p.ended) ch.carry.reset(hop);
+        else if (n_in[c] > 0 && !ch.carry.keep_last(in, (size_t)n_in[c], (size_t)hop + (size_t)(p.r1 % hop)))
+            return fail(BP_ERR_STATE, "bp_stream_push: internal: the carry exceeds its capacity");
     }
     if (s->ana.empty()) return BP_OK;                               // nothing became a frame: no device work
     const size_t in_bytes = o_pcm + unit * hop * 4;
-    memcpy(s->pin_in + o_ana, s->ana.data(), s->ana.size() * sizeof(AnaJob));
-    if (!s->natj.empty()) memcpy(s->pin_in + o_nat, s->natj.data(), s->natj.size() * sizeof(NatJob));
-    if (!s->syn.empty()) memcpy(s->pin_in + o_syn, s->syn.data(), s->syn.size() * sizeof(SynJob));
-    char *din = s->dev + s->o_in;
-    HIPCHK(hipMemcpyAsync(din, s->pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
-    const float *win = (const float *)(s->dev + s->o_win);
-    const float2 *tw = (const float2 *)(s->dev + s->o_tw);
-    float2 *Y = (float2 *)(s->dev + s->o_pY);
+    memcpy(pin + o_ana, s->ana.data(), s->ana.size() * sizeof(AnaJob));
+    if (!s->natj.empty()) memcpy(pin + o_nat, s->natj.data(), s->natj.size() * sizeof(NatJob));
+    if (!s->syn.empty()) memcpy(pin + o_syn, s->syn.data(), s->syn.size() * sizeof(SynJob));
+    char *din = dev + s->o_in;
+    HIPCHK(hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const float *win = (const float *)(dev + s->o_win);
+    const float2 *tw = (const float2 *)(dev + s->o_tw);
+    float2 *Y = (float2 *)(dev + s->o_pY);
     {
         StreamAnaArgs a; memset(&a, 0, sizeof(a));
         a.jobs = (const AnaJob *)(din + o_ana); a.pcm = (const float *)(din + o_pcm); a.win = win; a.tw = tw;
-        a.mean = (const float *)(s->dev + s->o_mean); a.inv_std = (const float *)(s->dev + s->o_istd);
+        a.mean = (const float *)(dev + s->o_mean); a.inv_std = (const float *)(dev + s->o_istd);
         a.log2M = s->log2M; a.D = D; a.hop = hop;
-        a.st_rows = (float *)(s->dev + s->o_rows); a.st_Y = (float2 *)(s->dev + s->o_Y);
+        a.st_rows = (float *)(dev + s->o_rows); a.st_Y = (float2 *)(dev + s->o_Y);
         a.rows = rows_d; a.Y = Y; a.win_start = tab_d; a.nat_row = (s->nat && n > 0) ? tab_d + 2 * n : nullptr;
         // fillers between the channels: window 0, NAT row 0 (the first channel with frames staged at least `context` rows)
         if (n > n_enh) HIPCHK(hipMemsetAsync(tab_d, 0, (size_t)3 * n * sizeof(int), h->stream));
@@ -467,7 +402,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     if (!s->natj.empty()) {
         const int kb = (D + WAVE_THREADS - 1) / WAVE_THREADS;
         hipLaunchKernelGGL(bp_stream_nat, dim3((unsigned)(kb * s->natj.size())), dim3(WAVE_THREADS), 0, h->stream, (const NatJob *)(din + o_nat),
-                           (const float *)rows_d, (const float *)(s->dev + s->o_rows), D, (float *)(s->dev + s->o_nat), nat_d);
+                           (const float *)rows_d, (const float *)(dev + s->o_rows), D, (float *)(dev + s->o_nat), nat_d);
         HIPCHK(hipGetLastError());
     }
     if (n > 0) {
@@ -477,13 +412,11 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         StreamSynArgs a; memset(&a, 0, sizeof(a));
         a.jobs = (const SynJob *)(din + o_syn); a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = s->out_col;
         a.Y = Y; a.win = win; a.tw = tw; a.log2M = s->log2M; a.D = D; a.target = s->target;
-        a.half = (float *)(s->dev + s->o_half); a.pcm = (float *)(s->dev + s->o_out);
+        a.half = (float *)(dev + s->o_half); a.pcm = (float *)(dev + s->o_out);
         const size_t lds = (syn_frames_at(hop) + (size_t)4 * hop) * sizeof(float);
         hipLaunchKernelGGL(bp_stream_synthesis, dim3((unsigned)n_enh), dim3(WAVE_THREADS), lds, h->stream, a);
         HIPCHK(hipGetLastError());
-        if (due > 0) HIPCHK(hipMemcpyAsync(s->pin_out, s->dev + s->o_out, (size_t)due * 4, hipMemcpyDeviceToHost, h->stream));
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (due > 0) memcpy(out_pcm, s->pin_out, (size_t)due * 4);
+    HIPCHK(s->blk.copy_back(s->o_out, due, out_pcm, h->stream));
     return BP_OK;
 }

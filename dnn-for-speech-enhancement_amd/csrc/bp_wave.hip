@@ -8,7 +8,8 @@
 // Device layout of one call (everything in ONE host->device copy, `WaveIn`): sentence s occupies the padded samples
 // [(F_s + s) hop, (F_s + s + T_s + 1) hop) of the PCM buffer, F_s = frames of the sentences before it, so frame t of sentence s
 // -- global frame g = F_s + t -- starts at sample (g + s) hop: aligned, contiguous, no predicates.  The enhanced samples come
-// back in the same padded layout (one device->host copy) and the host trims the padding.
+// back in the same padded layout (one device->host copy) and the host trims the padding.  The plan and the layout (plan_waves,
+// wave_scatter / wave_gather, wave_in_layout / wave_in_fill) are declared in bp_fft.h: bp_classic.hip and bp_eval.hip use them too.
 //
 // Kernels (one workgroup of 256 threads = 4 wave64 per frame; the frame's FFT lives in LDS):
 //   bp_wave_analysis   window, real FFT of n_fft points as a complex FFT of n_fft/2 points + the split step, then per bin:
@@ -162,15 +163,8 @@ hipError_t wave_overlap_launch(const float *syn, const float *win, const int *F,
     return hipGetLastError();
 }
 
-namespace {
-
-// Frame plan of a call: T_s per sentence, F = prefix sums.  Checked before any device work.
-struct Plan {
-    int M, N, hop, log2M, n_sent;
-    std::vector<int> F;                                  // [n_sent + 1]
-    size_t frames, padded;                               // frames of the call, padded samples of the PCM buffer
-};
-int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, Plan &p)
+// Frame plan of a call (bp_fft.h).  Checked before any device work.
+int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, size_t max_frames, WavePlan &p)
 {
     p.log2M = wave_log2_fft(fea_dim);
     if (p.log2M < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
@@ -181,7 +175,7 @@ int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, co
     for (int s = 0; s < n_sent; ++s) {
         if (sent_len[s] < 1) return fail(BP_ERR_ARG, std::string(who) + ": empty sentence " + std::to_string(s));
         f += (size_t)((sent_len[s] - 1) / p.hop + 2);
-        if (f > (size_t)INT32_MAX / 2) return fail(BP_ERR_ARG, std::string(who) + ": too many frames in one call");
+        if (f > max_frames) return fail(BP_ERR_ARG, std::string(who) + ": too many frames in one call");
         p.F[s + 1] = (int)f;
     }
     p.frames = f;
@@ -189,18 +183,25 @@ int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, co
     return BP_OK;
 }
 
-// The single host->device block: F | mean | inv_std | window | twiddles | padded PCM, each 256-byte aligned.
-struct WaveIn { size_t F, mean, istd, win, tw, pcm, bytes; };
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-WaveIn wave_in_layout(const Plan &p, int D)
+void wave_scatter(float *dst, const WavePlan &p, const int *sent_len, const float *pcm)
+{
+    for (int s = 0; s < p.n_sent; pcm += sent_len[s++]) memcpy(dst + (size_t)(p.F[s] + s + 1) * p.hop, pcm, (size_t)sent_len[s] * 4);
+}
+
+void wave_gather(float *out, const WavePlan &p, const int *sent_len, const float *src)
+{
+    for (int s = 0; s < p.n_sent; out += sent_len[s++]) memcpy(out, src + (size_t)(p.F[s] + s + 1) * p.hop, (size_t)sent_len[s] * 4);
+}
+
+WaveIn wave_in_layout(const WavePlan &p, int D)
 {
     WaveIn w;
     w.F = 0; w.mean = al256(((size_t)p.n_sent + 1) * 4); w.istd = w.mean + al256((size_t)D * 4); w.win = w.istd + al256((size_t)D * 4);
     w.tw = w.win + al256((size_t)p.N * 4); w.pcm = w.tw + al256((size_t)(p.M + 1) * 8); w.bytes = w.pcm + al256(p.padded * 4);
     return w;
 }
-// Fill it on the host: window and twiddles computed in double and rounded once; the sentences at their padded places.
-void wave_in_fill(char *hb, const WaveIn &w, const Plan &p, int D, const float *mean, const float *inv_std, const int *sent_len,
+
+void wave_in_fill(char *hb, const WaveIn &w, const WavePlan &p, int D, const float *mean, const float *inv_std, const int *sent_len,
                   const float *pcm)
 {
     memcpy(hb + w.F, p.F.data(), p.F.size() * 4);
@@ -208,55 +209,42 @@ void wave_in_fill(char *hb, const WaveIn &w, const Plan &p, int D, const float *
     wave_window_twiddles(p.log2M, (float *)(hb + w.win), (float2 *)(hb + w.tw));
     float *x = (float *)(hb + w.pcm);
     memset(x, 0, p.padded * 4);
-    size_t src = 0;
-    for (int s = 0; s < p.n_sent; ++s) {
-        memcpy(x + (size_t)(p.F[s] + s + 1) * p.hop, pcm + src, (size_t)sent_len[s] * 4);
-        src += (size_t)sent_len[s];
-    }
+    wave_scatter(x, p, sent_len, pcm);
 }
 
-}  // namespace
+// the most frames of a call that goes through a window chunk or returns LPS rows
+static const size_t WAVE_MAX_FRAMES = (size_t)INT32_MAX / 2;
 
 extern "C" int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_len, const float *pcm, float *lps)
 {
-    Plan p;
-    { const int r = plan_waves("bp_wave_lps", fea_dim, n_sent, sent_len, pcm, p); if (r != BP_OK) return r; }
+    WavePlan p;
+    { const int r = plan_waves("bp_wave_lps", fea_dim, n_sent, sent_len, pcm, WAVE_MAX_FRAMES, p); if (r != BP_OK) return r; }
     if (!lps) return fail(BP_ERR_ARG, "bp_wave_lps: null output");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BP_ERR_ARG, "bp_wave_lps: device ordinal out of range");
-    HIPCHK(hipSetDevice(device));
     const WaveIn w = wave_in_layout(p, fea_dim);
     const size_t out_b = p.frames * fea_dim * 4;
+    OneShot os;
+    { const int r = os.open("bp_wave_lps", device, w.bytes + out_b); if (r != BP_OK) return r; }
     std::vector<char> hb(w.bytes);
     wave_in_fill(hb.data(), w, p, fea_dim, nullptr, nullptr, sent_len, pcm);
-    hipStream_t st = nullptr;
-    char *d = nullptr;
-    int rc = BP_OK;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, w.bytes + out_b);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, st);
+    hipError_t &e = os.e;
+    char *d = os.d;
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, os.st);
     if (e == hipSuccess) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
         a.pcm = (const float *)(d + w.pcm); a.win = (const float *)(d + w.win); a.tw = (const float2 *)(d + w.tw); a.F = (const int *)(d + w.F);
         a.n_sent = n_sent; a.log2M = p.log2M; a.D = fea_dim; a.hop = p.hop; a.ctx = 1;
         a.lps = (float *)(d + w.bytes);
-        hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)p.frames), dim3(WAVE_THREADS), lds_bytes(p.M), st, a);
-        e = hipGetLastError();
+        e = wave_analysis_launch(a, (int)p.frames, os.st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(lps, d + w.bytes, out_b, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_wave_lps: ") + hipGetErrorString(e));
-    if (d) (void)hipFree(d);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(lps, d + w.bytes, out_b, hipMemcpyDeviceToHost, os.st);
+    return os.finish("bp_wave_lps");
 }
 
 extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *c, float *out_pcm, float *out_net)
 {
     if (!h || !c) return fail(BP_ERR_ARG, "bp_enhance_waves: null handle or chunk");
-    Plan p;
-    { const int r = plan_waves("bp_enhance_waves", fea_dim, c->n_sent, c->sent_len, c->pcm, p); if (r != BP_OK) return r; }
+    WavePlan p;
+    { const int r = plan_waves("bp_enhance_waves", fea_dim, c->n_sent, c->sent_len, c->pcm, WAVE_MAX_FRAMES, p); if (r != BP_OK) return r; }
     if (!out_pcm || !c->mean || !c->inv_std) return fail(BP_ERR_ARG, "bp_enhance_waves: null pointer");
     if (h->dp) return fail(BP_ERR_STATE, "bp_enhance_waves: not on an attached data-parallel handle");
     const int D = fea_dim, ctx = c->context, toff = c->targ_offset, L = h->L, sL = h->s[L - 1];
@@ -319,11 +307,7 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     HIPCHK(hipMemcpyAsync(hout, h->wave[3].p, pcm_b, hipMemcpyDeviceToHost, h->stream));
     if (out_net) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    size_t dst = 0;
-    for (int s = 0; s < c->n_sent; ++s) {
-        memcpy(out_pcm + dst, hout + (size_t)(p.F[s] + s + 1) * p.hop, (size_t)c->sent_len[s] * 4);
-        dst += (size_t)c->sent_len[s];
-    }
+    wave_gather(out_pcm, p, c->sent_len, hout);
     if (out_net)
         for (int j = 0; j < n; ++j) memcpy(out_net + (size_t)j * sL, h->host_out + (size_t)j * h->ld[L - 1], sizeof(float) * sL);
     return BP_OK;

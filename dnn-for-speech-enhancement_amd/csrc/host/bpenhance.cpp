@@ -104,26 +104,21 @@ static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, co
     return 1;
 }
 
-// method=logmmse lm_stream_block=...: channel c plays files c, c + chan, ... one after the other through a log-MMSE stream
-static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params &lm, int block, int chan, const std::vector<std::string> &ins,
-                               const std::vector<std::string> &outs)
+// A streaming run of either kind (stream_block, lm_stream_block): channel c plays files c, c + chan, ... one after the other,
+// `block` samples per push, the last block of a file with its end flag.  push is bp_stream_push or bp_lmstream_push, st its open
+// stream; out_cap: the samples one push can return.  Returns the samples pushed; enh[s]: what came back for file s.
+template <class S>
+static size_t play_files(S *st, int (*push)(S *, const int *, const float *, const unsigned char *, int *, float *, size_t), int chan, int block,
+                         const std::vector<std::string> &ins, const std::vector<std::vector<float>> &waves, size_t out_cap,
+                         std::vector<std::vector<float>> &enh)
 {
-    const int ns = (int)ins.size(), hop = fea_dim - 1;
-    std::vector<std::vector<float>> waves(ns), enh(ns);
-    std::vector<int> rates(ns);
-    for (int s = 0; s < ns; ++s) {
-        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
-        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
-        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
-    }
-    bp_lmstream *st = nullptr;
-    if (bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    const int ns = (int)waves.size();
     std::vector<int> file(chan), n_in(chan), n_out(chan);
     std::vector<size_t> pos(chan, 0);
     std::vector<unsigned char> end(chan);
-    // a push returns what arrived plus what waited for the noise start or for the end of the sentence
-    std::vector<float> pcm, out((size_t)chan * ((size_t)block + ((size_t)lm.init_frames + 1) * hop));
+    std::vector<float> pcm, out(out_cap);
     size_t samples = 0;
+    enh.assign(ns, std::vector<float>());
     for (int c = 0; c < chan; ++c) file[c] = c;
     for (;;) {
         pcm.clear();
@@ -138,7 +133,7 @@ static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params 
             any = true;
         }
         if (!any) break;
-        if (bp_lmstream_push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        if (push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
         size_t off = 0;
         for (int c = 0; c < chan; ++c) {
             if (file[c] >= ns) continue;
@@ -149,9 +144,29 @@ static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params 
         }
         samples += pcm.size();
     }
+    for (int s = 0; s < ns; ++s)
+        if (enh[s].size() != waves[s].size()) { printf("%s: the stream returned %zu of %zu samples\n", ins[s].c_str(), enh[s].size(), waves[s].size()); exit(0); }
+    return samples;
+}
+
+// method=logmmse lm_stream_block=...: the files through a log-MMSE stream
+static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params &lm, int block, int chan, const std::vector<std::string> &ins,
+                               const std::vector<std::string> &outs)
+{
+    const int ns = (int)ins.size(), hop = fea_dim - 1;
+    std::vector<std::vector<float>> waves(ns), enh;
+    std::vector<int> rates(ns);
+    for (int s = 0; s < ns; ++s) {
+        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
+        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+    }
+    bp_lmstream *st = nullptr;
+    if (bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    // a push returns what arrived plus what waited for the noise start or for the end of the sentence
+    const size_t samples = play_files(st, bp_lmstream_push, chan, block, ins, waves, (size_t)chan * ((size_t)block + ((size_t)lm.init_frames + 1) * hop), enh);
     bp_lmstream_close(st);
     for (int s = 0; s < ns; ++s) {
-        if (enh[s].size() != waves[s].size()) { printf("%s: the stream returned %zu of %zu samples\n", ins[s].c_str(), enh[s].size(), waves[s].size()); exit(0); }
         const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
         if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
     }
@@ -333,40 +348,11 @@ int main(int argc, char **argv)
         sc.target = target; sc.out_col = out_col; sc.n_chan = stream_chan; sc.max_push_samples = stream_block * stream_chan;
         bp_stream *st = nullptr;
         if (bp_stream_open(h, &sc, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
-        std::vector<int> file(stream_chan), n_in(stream_chan), n_out(stream_chan);
-        std::vector<size_t> pos(stream_chan, 0);
-        std::vector<unsigned char> end(stream_chan);
-        std::vector<std::vector<float>> enh(ns);
+        std::vector<std::vector<float>> enh;
         // a push returns what arrived plus, at the end of a sentence, the frames that waited for their look-ahead or the NAT row
-        out.resize((size_t)stream_chan * ((size_t)stream_block + (size_t)(ctx + 8) * hop));
-        for (int c = 0; c < stream_chan; ++c) file[c] = c;
-        for (;;) {
-            pcm.clear();
-            bool any = false;
-            for (int c = 0; c < stream_chan; ++c) {
-                n_in[c] = 0; end[c] = 0;
-                if (file[c] >= ns) continue;
-                const std::vector<float> &w = waves[file[c]];
-                n_in[c] = (int)std::min((size_t)stream_block, w.size() - pos[c]);
-                end[c] = pos[c] + n_in[c] == w.size();
-                pcm.insert(pcm.end(), w.begin() + pos[c], w.begin() + pos[c] + n_in[c]);
-                any = true;
-            }
-            if (!any) break;
-            if (bp_stream_push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
-            size_t off = 0;
-            for (int c = 0; c < stream_chan; ++c) {
-                if (file[c] >= ns) continue;
-                enh[file[c]].insert(enh[file[c]].end(), out.begin() + off, out.begin() + off + n_out[c]);
-                off += n_out[c];
-                pos[c] += n_in[c];
-                if (end[c]) { file[c] += stream_chan; pos[c] = 0; }
-            }
-            samples += pcm.size();
-        }
+        samples = play_files(st, bp_stream_push, stream_chan, stream_block, ins, waves, (size_t)stream_chan * ((size_t)stream_block + (size_t)(ctx + 8) * hop), enh);
         bp_stream_close(st);
         for (int s = 0; s < ns; ++s) {
-            if (enh[s].size() != waves[s].size()) { printf("%s: the stream returned %zu of %zu samples\n", ins[s].c_str(), enh[s].size(), waves[s].size()); exit(0); }
             const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
             if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
         }
