@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "bp_enhance_waves", "bp_wave_lps",
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
     "bp_set_mix_reverb", "bp_reverb_waves", "bp_mix_rir_delay", "bp_mix_reverb_pairs",
+    "bp_rir_image", "bp_rir_orders", "bp_rir_beta", "bp_rir_rooms",
     "bp_score_waves", "bp_eval_mix",
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
@@ -51,6 +52,11 @@ SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_e
 REVERB_TARGET_REVERBERANT, REVERB_TARGET_EARLY = 0, 1   # bp_mix_reverb.target
 REVERB_TARGETS = {"reverberant": REVERB_TARGET_REVERBERANT, "early": REVERB_TARGET_EARLY}
 MIX_RIR_MAX_TAPS = 65536
+RIR_MAX_IMAGES = 1 << 26
+# bp_rir_room: a numpy structured array of this dtype is a list of rooms
+RIR_ROOM_DTYPE = np.dtype([("L", np.float64, 3), ("src", np.float64, 3), ("mic", np.float64, 3), ("beta", np.float64, 6)])
+# bp_rir_range: the defaults of rir_rooms (and of bpmix / bpeval)
+RIR_RANGE_DEFAULTS = dict(L_lo=(3.0, 3.0, 2.5), L_hi=(10.0, 8.0, 4.0), t60=(0.2, 0.8), margin=0.5, dist=(0.5, 3.0))
 MIX_TARGETS = {"lps": MIX_LPS, "irm": MIX_IRM, "ibm": MIX_IBM, "lps+irm": MIX_LPS_IRM, "lps+ibm": MIX_LPS_IBM}
 # bp_mixture: a numpy structured array of this dtype is a mixture plan
 MIXTURE_DTYPE = np.dtype({"names": ["clean", "noise", "offset", "snr_db"], "formats": [np.int32, np.int32, np.int64, np.float32],
@@ -97,6 +103,14 @@ class BPMixReverb(C.Structure):
         ("n_rir", C.c_int), ("rir_len", C.POINTER(C.c_int)), ("rir_pcm", C.POINTER(C.c_float)),
         ("n_pair", C.c_int), ("pair_clean", C.POINTER(C.c_int)), ("pair_rir", C.POINTER(C.c_int)),
         ("target", C.c_int), ("early_taps", C.c_int),
+    ]
+
+
+class BPRirRange(C.Structure):
+    """bp_rir_range (include/bp_c_api.h): the ranges bp_rir_rooms draws rooms from."""
+    _fields_ = [
+        ("L_lo", C.c_double * 3), ("L_hi", C.c_double * 3), ("t60_lo", C.c_double), ("t60_hi", C.c_double),
+        ("margin", C.c_double), ("dist_lo", C.c_double), ("dist_hi", C.c_double),
     ]
 
 
@@ -171,6 +185,11 @@ def load_library(path=None):
     lib.bp_reverb_waves.argtypes = [C.c_int, C.c_int, ip, fp, ip, C.c_int, ip, fp, C.c_int, fp, fp]
     lib.bp_mix_rir_delay.argtypes = [fp, C.c_int, ip]
     lib.bp_mix_reverb_pairs.argtypes = [C.c_uint64, C.c_int, C.c_int, ip]
+    dp = C.POINTER(C.c_double)
+    lib.bp_rir_image.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, ip, fp]
+    lib.bp_rir_orders.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_int64)]
+    lib.bp_rir_beta.argtypes = [dp, C.c_double, dp]
+    lib.bp_rir_rooms.argtypes = [C.c_uint64, C.c_int, C.POINTER(BPRirRange), C.c_void_p]
     lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
     lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
     lib.bp_logmmse_defaults.argtypes = [C.POINTER(BPLogmmseParams)]
@@ -957,6 +976,82 @@ def mix_reverb_pairs(seed, n_clean, n_rir):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return out[:int(n_clean)]
+
+
+def _rooms(rooms):
+    r = np.ascontiguousarray(rooms, dtype=RIR_ROOM_DTYPE).reshape(-1)
+    return r
+
+
+def rir_window_default(sample_rate):
+    """the delay window rir_image uses when none is given: 2 round(0.004 fs) taps (8 ms; halves round up)"""
+    return 2 * int(np.floor(0.004 * int(sample_rate) + 0.5))
+
+
+def rir_image(device, sample_rate, rooms, rir_len, window_taps=None):
+    """bp_rir_image: a list of float32 arrays, response k of rir_len[k] taps for rooms[k] (RIR_ROOM_DTYPE) by the image method
+    (include/bp_c_api.h); the list is what BP_GPU.set_mix_reverb takes.  No handle."""
+    lib = load_library()
+    r = _rooms(rooms)
+    n = np.ascontiguousarray(rir_len, dtype=np.int32).reshape(-1)
+    if n.size != r.size:
+        raise BPError("rir_image: %d rooms but %d lengths" % (r.size, n.size))
+    tw = rir_window_default(sample_rate) if window_taps is None else int(window_taps)
+    out = np.zeros(max(int(np.clip(n, 0, MIX_RIR_MAX_TAPS).sum()), 1), np.float32)
+    rc = lib.bp_rir_image(int(device), int(sample_rate), tw, int(r.size), r.ctypes.data_as(C.c_void_p) if r.size else None,
+                          n.ctypes.data_as(C.POINTER(C.c_int)) if n.size else None, _fp(out))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return np.split(out[:int(n.sum())], np.cumsum(n)[:-1])
+
+
+def rir_orders(room, sample_rate, n_taps, window_taps=None):
+    """bp_rir_orders: ((N_0, N_1, N_2), images of the box) of one room; host only."""
+    lib = load_library()
+    r = _rooms(room)
+    tw = rir_window_default(sample_rate) if window_taps is None else int(window_taps)
+    order = np.zeros(3, np.int32)
+    n = C.c_int64()
+    rc = lib.bp_rir_orders(r.ctypes.data_as(C.c_void_p), int(sample_rate), int(n_taps), tw, order.ctypes.data_as(C.POINTER(C.c_int)),
+                           C.byref(n))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return tuple(int(x) for x in order), int(n.value)
+
+
+def rir_beta(L, t60):
+    """bp_rir_beta: the six reflection coefficients (float64 [6]) Eyring's formula gives a box L for a NOMINAL t60; host only."""
+    lib = load_library()
+    Ld = np.ascontiguousarray(L, dtype=np.float64).reshape(-1)
+    if Ld.size != 3:
+        raise BPError("rir_beta: L needs 3 numbers")
+    beta = np.zeros(6, np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = lib.bp_rir_beta(Ld.ctypes.data_as(dp), float(t60), beta.ctypes.data_as(dp))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return beta
+
+
+def rir_rooms(seed, n, **ranges):
+    """bp_rir_rooms: n rooms (RIR_ROOM_DTYPE) drawn from the seed; ranges: L_lo, L_hi (3 numbers each), t60 and dist (lo, hi),
+    margin -- RIR_RANGE_DEFAULTS where not given; host only."""
+    lib = load_library()
+    unknown = set(ranges) - set(RIR_RANGE_DEFAULTS)
+    if unknown:
+        raise BPError("rir_rooms: unknown range %s" % ", ".join(sorted(unknown)))
+    g = dict(RIR_RANGE_DEFAULTS, **ranges)
+    rg = BPRirRange()
+    rg.L_lo[:] = [float(x) for x in g["L_lo"]]
+    rg.L_hi[:] = [float(x) for x in g["L_hi"]]
+    rg.t60_lo, rg.t60_hi = (float(x) for x in g["t60"])
+    rg.dist_lo, rg.dist_hi = (float(x) for x in g["dist"])
+    rg.margin = float(g["margin"])
+    out = np.zeros(max(int(n), 1), RIR_ROOM_DTYPE)
+    rc = lib.bp_rir_rooms(int(seed), int(n), C.byref(rg), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out[:int(n)]
 
 
 def mix_plan(seed, n_clean, per_clean, noise_lens, snr_list):

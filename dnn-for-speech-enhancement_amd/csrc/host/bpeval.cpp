@@ -19,7 +19,9 @@
 // rir_list: one room impulse response per WAV, at the rate of the others; clean sentence c is paired with response
 // bp_mix_reverb_pairs(init_randem_seed, ...)[c], the plan addresses the derived entry n_clean + c in place of c (so scores_out
 // lists it), the mixtures are reverberant and the scores are taken against reverb_target: the reverberant sentence or its direct
-// sound + early_ms of reflections.
+// sound + early_ms of reflections.  rir_rooms=N with rir_room_lo / rir_room_hi / rir_t60 / rir_margin / rir_dist / rir_ms / rir_window /
+// rir_rooms_out (bpmix's keys, its defaults) takes the place of rir_list: N simulated responses, their rooms drawn
+// by bp_rir_rooms(init_randem_seed, N, ...) and made by bp_rir_image at the rate of the others.
 // Errors: message + exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -31,6 +33,7 @@
 #include <vector>
 
 #include "../../../include/bp_c_api.h"
+#include "rir_keys.h"
 #include "wav_io.h"
 #include "wts_io.h"
 
@@ -59,6 +62,7 @@ struct Params {
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
     bool net_keys = false;                                   // a key of test-set mode was given
     bool baseline = false;                                   // baseline=logmmse
+    bp::RirKeys rir;                                         // rir_rooms=N ...: simulated responses in place of rir_list
 };
 
 bool parse_int(const std::string &v, long lo, long hi, int *out)
@@ -139,6 +143,7 @@ Params parse(int argc, char **argv)
         else if (k == "compute") { if (v == "fp32") P.compute_dtype = 0; else if (v == "bf16") P.compute_dtype = 1; else ok = false; }
         else if (k == "output_act") { if (v == "linear") P.output_act = 0; else if (v == "sigmoid") P.output_act = 1; else ok = false; }
         else if (k == "output_loss") { if (v == "xent") P.output_loss = 0; else if (v == "mse") P.output_loss = 1; else ok = false; }
+        else if (const int r = bp::rir_key(P.rir, k, v)) ok = r > 0;
         else die("bpeval: unknown key " + k);
         if (!ok) die("bpeval: bad value for " + k + ": " + v);
         P.net_keys = P.net_keys || net;
@@ -306,6 +311,14 @@ int main(int argc, char **argv)
         }
     }
     check_rate(rate);
+    std::vector<bp_rir_room> rooms;                              // rir_rooms: drawn and checked here, made on the device below
+    if (P.rir.rooms && !P.rir_list.empty()) die("bpeval: rir_rooms and rir_list exclude each other");
+    if ((P.rir.any || P.rir.cv_rooms) && !P.rir.rooms) die("bpeval: the rir_* keys need rir_rooms (cv_rir_rooms is bpmix's)");
+    if (P.rir.rooms) {
+        std::string err = bp::rir_draw(P.rir, P.seed, P.rir.rooms, rate, rooms, rir_len);
+        if (err.empty() && !P.rir.rooms_out.empty()) err = bp::rir_write_rooms(P.rir.rooms_out, rooms);
+        if (!err.empty()) die("bpeval: " + err);
+    }
     for (int64_t n : noise.len)
         if (n >= ((int64_t)1 << 32)) die("bpeval: a noise recording has 2^32 samples or more");
     std::vector<bp_mixture> plan((size_t)clean.len.size() * P.mix_per_clean);
@@ -360,6 +373,10 @@ int main(int argc, char **argv)
     mc.n_clean = (int)clean.len.size(); mc.clean_len = clean.len.data(); mc.clean_pcm = clean.pcm.data();
     mc.n_noise = (int)noise.len.size(); mc.noise_len = noise.len.data(); mc.noise_pcm = noise.pcm.data();
     check(bp_set_mix_corpus(h, &mc));
+    if (!rooms.empty()) {
+        const std::string err = bp::rir_generate(P.rir, P.device, rate, rooms, rir_len, rir_pcm);
+        if (!err.empty()) die(err);
+    }
     if (!rir_len.empty()) {
         std::vector<int> pc(n_clean), pr(n_clean);
         for (int c = 0; c < n_clean; ++c) pc[c] = c;

@@ -7,6 +7,8 @@
 //         log_file=... [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [target=lps|irm|ibm|lps+irm|lps+ibm] [lc_db=5]
 //         [cv_noise_list=noise.list] [cv_seed=20261016] [mix_plan_out=plan.txt] [output_act=...] [compute=fp32|bf16] ...
 //         [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50] [cv_rir_list=rir.list]
+//         [rir_rooms=N] [rir_room_lo=3,3,2.5] [rir_room_hi=10,8,4] [rir_t60=0.2,0.8] [rir_margin=0.5] [rir_dist=0.5,3] [rir_ms=400]
+//         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N]
 //   bpmix clean_list=... noise_list=... fea_dim=129 norm_out=mix.norm [snr_list=...] [mix_per_clean=...] [init_randem_seed=...]
 //
 // The plan of the epoch is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list); it is cut into
@@ -19,7 +21,10 @@
 // clean sentences; clean sentence c is paired with response bp_mix_reverb_pairs(init_randem_seed, ...)[c], the pairs become the
 // derived entries n_clean + c of the corpus and the plan addresses entry n_clean + c in place of c.  reverb_target: what the net
 // learns to produce, the reverberant sentence or its direct sound + early_ms of reflections.  CV: cv_rir_list (default rir_list),
-// paired from cv_seed.  Every key, list and WAV is checked before the device is used.  Errors: message +
+// paired from cv_seed.  rir_rooms=N takes the place of rir_list: N simulated responses of rir_ms milliseconds
+// at the rate of the clean sentences, their rooms drawn by bp_rir_rooms(init_randem_seed, N, the rir_* ranges) and made by
+// bp_rir_image; rir_rooms_out lists the rooms, one `L src mic beta` line each; CV draws cv_rir_rooms (default N) from cv_seed.
+// Every key, list, WAV and drawn room is checked before the device is used.  Errors: message +
 // exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -31,6 +36,7 @@
 #include <vector>
 
 #include "../../../include/bp_c_api.h"
+#include "rir_keys.h"
 #include "wav_io.h"
 #include "wts_io.h"
 
@@ -59,6 +65,7 @@ struct Params {
     float wmin = -0.1f, wmax = 0.1f, bmin = -0.1f, bmax = 0.1f;
     unsigned long long seed = 0, cv_seed = 20261016ull, dropout_seed = 0;
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
+    bp::RirKeys rir;
 };
 
 bool parse_int(const std::string &v, long lo, long hi, int *out)
@@ -154,6 +161,7 @@ Params parse(int argc, char **argv)
         else if (k == "output_act") { if (v == "linear") P.output_act = 0; else if (v == "sigmoid") P.output_act = 1; else ok = false; }
         else if (k == "output_linear_dims") ok = parse_int(v, 0, 1000000, &P.output_linear_dims);
         else if (k == "output_loss") { if (v == "xent") P.output_loss = 0; else if (v == "mse") P.output_loss = 1; else ok = false; }
+        else if (const int r = bp::rir_key(P.rir, k, v)) ok = r > 0;
         else die("bpmix: unknown key " + k);
         if (!ok) die("bpmix: bad value for " + k + ": " + v);
     }
@@ -200,17 +208,33 @@ struct Reverb {
     std::vector<float> pcm;
     std::vector<int> len;
     int target = 0, early_taps = 0;
+    std::vector<bp_rir_room> rooms;                              // rir_rooms: pcm is made from these by set_reverb
+    int rate = 0;
 };
-Reverb read_reverb(const Params &P, const std::string &what, const std::string &list, const std::vector<int> &clean_rates)
+void one_rate(const std::string &what, const std::vector<int> &clean_rates)
 {
-    Reverb r;
-    if (list.empty()) return r;
-    std::vector<int> rates;
-    const auto w = read_list(what, list, &rates);
     for (size_t k = 0; k < clean_rates.size(); ++k)
         if (clean_rates[k] != clean_rates[0])
             die("bpmix: " + what + " needs clean sentences of one sample rate (sentence " + std::to_string(k) + " has " +
                 std::to_string(clean_rates[k]) + " Hz, sentence 0 " + std::to_string(clean_rates[0]) + " Hz)");
+}
+// list: the responses of a rir_list; else n_rooms > 0: rooms drawn from the seed (checked here, made on the device by set_reverb)
+Reverb read_reverb(const Params &P, const std::string &what, const std::string &list, int n_rooms, unsigned long long seed,
+                   const std::vector<int> &clean_rates)
+{
+    Reverb r;
+    if (list.empty() && n_rooms > 0) {
+        one_rate("rir_rooms", clean_rates);
+        const std::string err = bp::rir_draw(P.rir, seed, n_rooms, clean_rates[0], r.rooms, r.len);
+        if (!err.empty()) die("bpmix: " + err);
+        r.on = true; r.target = P.reverb_target; r.rate = clean_rates[0];
+        r.early_taps = (int)((double)P.early_ms * clean_rates[0] / 1000.0 + 0.5);
+        return r;
+    }
+    if (list.empty()) return r;
+    std::vector<int> rates;
+    const auto w = read_list(what, list, &rates);
+    one_rate(what, clean_rates);
     for (size_t k = 0; k < w.size(); ++k) {
         if (rates[k] != clean_rates[0])
             die("bpmix: " + what + ": response " + std::to_string(k) + " has " + std::to_string(rates[k]) + " Hz, the clean sentences " +
@@ -228,14 +252,19 @@ Reverb read_reverb(const Params &P, const std::string &what, const std::string &
 }
 
 // the derived entries of a corpus of n_clean sentences: sentence c with response bp_mix_reverb_pairs(seed)[c]
-void set_reverb(bp_handle *h, const Reverb &r, unsigned long long seed, int n_clean)
+void set_reverb(bp_handle *h, const Params &P, const Reverb &r, unsigned long long seed, int n_clean)
 {
+    std::vector<float> made;
+    if (!r.rooms.empty()) {
+        const std::string err = bp::rir_generate(P.rir, P.device, r.rate, r.rooms, r.len, made);
+        if (!err.empty()) die(err);
+    }
     std::vector<int> pc(n_clean), pr(n_clean);
     for (int c = 0; c < n_clean; ++c) pc[c] = c;
     check(bp_mix_reverb_pairs(seed, n_clean, (int)r.len.size(), pr.data()));
     bp_mix_reverb mr;
     memset(&mr, 0, sizeof(mr));
-    mr.n_rir = (int)r.len.size(); mr.rir_len = r.len.data(); mr.rir_pcm = r.pcm.data();
+    mr.n_rir = (int)r.len.size(); mr.rir_len = r.len.data(); mr.rir_pcm = r.rooms.empty() ? r.pcm.data() : made.data();
     mr.n_pair = n_clean; mr.pair_clean = pc.data(); mr.pair_rir = pr.data();
     mr.target = r.target; mr.early_taps = r.early_taps;
     check(bp_set_mix_reverb(h, &mr));
@@ -297,7 +326,7 @@ int norm_pass(const Params &P, const Corpus &clean, const Corpus &noise, std::ve
     const bp_mix_corpus mc = describe(P, BP_MIX_LPS, 1, 0, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) {
-        set_reverb(h, rv, P.seed, (int)clean.len.size());
+        set_reverb(h, P, rv, P.seed, (int)clean.len.size());
         for (bp_mixture &m : plan) m.clean += (int)clean.len.size();
     }
     std::vector<double> sum(D, 0.0), sq(D, 0.0);
@@ -355,7 +384,14 @@ int main(int argc, char **argv)
     for (int64_t n : noise.len)
         if (n >= ((int64_t)1 << 32)) die("bpmix: a noise recording has 2^32 samples or more");
     std::vector<bp_mixture> plan = make_plan(P.seed, (int)clean.len.size(), P.mix_per_clean, noise, P.snr);
-    const Reverb rv = read_reverb(P, "rir_list", P.rir_list, clean_rates);
+    if (P.rir.rooms && !P.rir_list.empty()) die("bpmix: rir_rooms and rir_list exclude each other");
+    if ((P.rir.cv_rooms || P.rir.rooms) && !P.cv_rir_list.empty()) die("bpmix: rir_rooms / cv_rir_rooms and cv_rir_list exclude each other");
+    if ((P.rir.any || P.rir.cv_rooms) && !P.rir.rooms) die("bpmix: the rir_* keys need rir_rooms");
+    const Reverb rv = read_reverb(P, "rir_list", P.rir_list, P.rir.rooms, P.seed, clean_rates);
+    if (!P.rir.rooms_out.empty()) {
+        const std::string err = bp::rir_write_rooms(P.rir.rooms_out, rv.rooms);
+        if (!err.empty()) die(err);
+    }
     if (!P.norm_out.empty()) return norm_pass(P, clean, noise, plan, rv);
 
     const int L = P.numlayers, ctx = P.fea_context, toff = P.targ_offset;
@@ -369,7 +405,8 @@ int main(int argc, char **argv)
     const Corpus cv_clean = flatten(read_list("cv_clean_list", P.cv_clean_list, &cv_rates));
     const Corpus cv_noise = P.cv_noise_list.empty() ? noise : flatten(read_list("cv_noise_list", P.cv_noise_list));
     std::vector<bp_mixture> cv_plan = make_plan(P.cv_seed, (int)cv_clean.len.size(), 1, cv_noise, P.snr);
-    const Reverb cv_rv = read_reverb(P, P.cv_rir_list.empty() ? "rir_list" : "cv_rir_list", P.cv_rir_list.empty() ? P.rir_list : P.cv_rir_list, cv_rates);
+    const Reverb cv_rv = read_reverb(P, P.cv_rir_list.empty() ? "rir_list" : "cv_rir_list", P.cv_rir_list.empty() ? P.rir_list : P.cv_rir_list,
+                                     P.rir.rooms ? (P.rir.cv_rooms ? P.rir.cv_rooms : P.rir.rooms) : 0, P.cv_seed, cv_rates);
     std::vector<int> frames, cv_frames;
     const auto calls = cut(plan, clean, hop, ctx, P.traincache, &frames);
     const auto cv_calls = cut(cv_plan, cv_clean, hop, ctx, P.traincache, &cv_frames);
@@ -451,8 +488,8 @@ int main(int argc, char **argv)
     const bp_mix_corpus mc = describe(P, P.target, ctx, toff, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) {
-        set_reverb(h, rv, P.seed, (int)clean.len.size());
-        fprintf(log, "Reverberation: %zu impulse responses, target %s, %d early taps.\n", rv.len.size(),
+        set_reverb(h, P, rv, P.seed, (int)clean.len.size());
+        fprintf(log, "Reverberation: %zu %simpulse responses, target %s, %d early taps.\n", rv.len.size(), rv.rooms.empty() ? "" : "simulated ",
                 rv.target == BP_REVERB_TARGET_EARLY ? "early" : "reverberant", rv.early_taps);
     }
     fprintf(log, "Corpus loaded: %zu clean sentences, %zu noise recordings, %zu mixtures in %zu chunks.\n", clean.len.size(),
@@ -487,7 +524,7 @@ int main(int argc, char **argv)
     fprintf(log, "Starting CV.\n");
     const bp_mix_corpus cvc = describe(P, P.target, ctx, toff, mean.data(), istd.data(), cv_clean, cv_noise);
     check(bp_set_mix_corpus(h, &cvc));
-    if (cv_rv.on) set_reverb(h, cv_rv, P.cv_seed, (int)cv_clean.len.size());
+    if (cv_rv.on) set_reverb(h, P, cv_rv, P.cv_seed, (int)cv_clean.len.size());
     fprintf(log, "Get cv chunk info over: CV mixtures have %d chunks.\n", (int)cv_calls.size());
     float squared_err = 0.0f;
     long cv_total = 0;

@@ -320,6 +320,57 @@ int bp_mix_rir_delay(const float *h, int n_taps, int *delay);
 int bp_mix_reverb_pairs(uint64_t seed, int n_clean, int n_rir, int *pair_rir);
 
 /* ------------------------------------------------------------------------------------
+ * Simulated room impulse responses: the image-source model of a shoebox room (Allen & Berkley 1979) with windowed-sinc
+ * fractional delays (Peterson 1986).  No reference counterpart.  INTEGRATION.md 1l, DESIGN.md 20.
+ *
+ * All arithmetic is in double; c = 343.0 m/s.  A room is a box L[0] x L[1] x L[2] metres with a source at src and a microphone
+ * at mic; beta[2d] and beta[2d+1] are the reflection coefficients of the walls at coordinate 0 and at L[d] of axis d.  A response
+ * has n_taps taps at sample_rate = fs and a delay window of window_taps = Tw samples.
+ *   d0 = |src - mic| = sqrt((dx^2 + dy^2) + dz^2),  reach = (n_taps + Tw/2) c / fs,  N_d = ceil(reach / (2 L_d))
+ *   images (n, p), n_d in [-N_d, N_d], p_d in {0, 1}:
+ *     x_d = (1 - 2 p_d) src_d + 2 n_d L_d - mic_d,  dist = sqrt((x_0^2 + x_1^2) + x_2^2),  tau = dist fs / c
+ *     a = ((B_0[n_0][p_0] B_1[n_1][p_1]) B_2[n_2][p_2]) (d0 / dist),  B_d[n][p] = beta[2d]^|n-p| beta[2d+1]^|n|
+ *   h[j] = fl32( sum over the images of a w(j - tau) ),  j = 0 .. n_taps-1
+ *     w(u) = 0.5 (1 + cos(2 pi u / Tw)) sinc(u) for |u| < Tw/2, else 0;  sinc(u) = sin(pi u) / (pi u), sinc(0) = 1
+ * Each power of B_d is a repeated multiplication from 1.0 on the host (0^0 = 1); the device reads B_d as a table and calls no
+ * pow.  The direct path has amplitude 1, so h peaks near tap round(d0 fs / c); h is not normalised otherwise (1k does not want
+ * it).  Images whose window does not reach a tap add exact zeros to it and are skipped.
+ * Order of one tap's sum: the images ascending in ((((n_2 + N_2) 2 + p_2) (2 N_1 + 1) + n_1 + N_1) 2 + p_1) (2 (2 N_0 + 1)) +
+ * (n_0 + N_0) 2 + p_0, one double accumulator per tap starting from +0.0, no atomics and no sum across threads: the bits of a
+ * response depend on its own room, length, fs and Tw only -- not on the other responses of the call, their order or the run.
+ * The device evaluates w in a factored form: with m = rint(tau), f = tau - m and u = j - tau,
+ * sin(pi u) = -(-1)^(j-m) sin(pi f) and cos(2 pi u / Tw) = cos(2 pi j / Tw) cos(2 pi tau / Tw) + sin(2 pi j / Tw) sin(2 pi tau / Tw),
+ * so sin and cos are called per image and per tap, never per term; its distance from the formula above is a few double ulps of
+ * the largest term.
+ * The t60 of bp_rir_beta and bp_rir_rooms is NOMINAL: the image model of a shoebox decays more slowly than Eyring's formula
+ * predicts (a float64 evaluation of a 5 x 4 x 3 m room gave a T20-fit decay of 0.30 s for nominal 0.20 s, 0.60 s for 0.40 s).
+ * Limitation: 1k aligns a response at its LARGEST tap.  In long narrow rooms (8 x 2 x 2.4 m is one) a cluster of early
+ * reflections can exceed the direct path; the reverberant sentence is then aligned to that cluster.
+ *
+ * bp_rir_image: response k for rooms[k] with rir_len[k] taps; out holds them back to back, the layout bp_mix_reverb.rir_pcm
+ * takes.  One host->device copy, one launch, one device->host copy, one synchronisation; nothing global grows.
+ * BP_ERR_ARG before the device is touched: n_rir < 1, null pointers, sample_rate outside [1000, 192000], window_taps outside
+ * [2, 1024], a length outside [1, BP_MIX_RIR_MAX_TAPS], a non-finite field, L_d outside [0.5, 100], a position not strictly
+ * inside the box, a beta outside [0, 1], d0 < 0.05, or (2 N_0 + 1)(2 N_1 + 1)(2 N_2 + 1) 8 > BP_RIR_MAX_IMAGES for a response
+ * (the bound on how long one launch can run).
+ * bp_rir_orders (host only): N_d and the number of images of the box, under the same checks except the last.
+ * bp_rir_beta (host only): Eyring, alpha = 1 - exp(-((24 ln 10) / c) V / (S t60)), all six beta = sqrt(1 - alpha); V = (L_0 L_1) L_2,
+ * S = 2 ((L_0 L_1 + L_0 L_2) + L_1 L_2); L_d in [0.5, 100], t60 > 0 and finite.
+ * bp_rir_rooms (host only): n rooms from the seed, in the Philox convention of bp_mix_plan with third counter word 4:
+ * U(r, a)[i] = philox(r, a, 4, 0)[i] / 2^32.  Room r: L_d = L_lo_d + U(r,0)[d] (L_hi_d - L_lo_d), t60 = t60_lo + U(r,0)[3]
+ * (t60_hi - t60_lo), mic_d = margin + U(r,1)[d] (L_d - 2 margin), src the same from U(r, 2+k) for attempt k = 0 .. 31, the first
+ * with dist_lo <= |src - mic| <= dist_hi (none: BP_ERR_ARG, the room named in the error string); beta = bp_rir_beta(L, t60).
+ * BP_ERR_ARG: n < 1, null pointers, a non-finite field, lo > hi, L_lo_d < 0.5, L_hi_d > 100, t60_lo <= 0, margin <= 0,
+ * 2 margin >= L_lo_d, dist_lo < 0.05.  Every room it returns passes the checks of bp_rir_image. */
+#define BP_RIR_MAX_IMAGES (1 << 26)
+typedef struct bp_rir_room { double L[3], src[3], mic[3], beta[6]; } bp_rir_room;
+typedef struct bp_rir_range { double L_lo[3], L_hi[3], t60_lo, t60_hi, margin, dist_lo, dist_hi; } bp_rir_range;
+int bp_rir_image(int device, int sample_rate, int window_taps, int n_rir, const bp_rir_room *rooms, const int *rir_len, float *out);
+int bp_rir_orders(const bp_rir_room *r, int sample_rate, int n_taps, int window_taps, int order[3], int64_t *n_images);
+int bp_rir_beta(const double L[3], double t60, double beta[6]);
+int bp_rir_rooms(uint64_t seed, int n, const bp_rir_range *g, bp_rir_room *out);
+
+/* ------------------------------------------------------------------------------------
  * Objective scores of enhanced speech (no reference counterpart: the papers it asks its users to cite score with outside tools).
  * INTEGRATION.md 1f.  Samples are fp32 in int16 units; a score compares an estimate e with a reference r of the same length n
  * at sample rate fs; eps = 2.220446049250313e-16; an undefined score is NaN, never an error.  Accepted rates: fs > 0 and
