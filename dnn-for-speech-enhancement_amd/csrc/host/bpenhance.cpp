@@ -32,34 +32,20 @@
 #include <vector>
 
 #include "../../../include/BP_GPU.h"
+#include "corpus.h"
+#include "keys.h"
+#include "net_setup.h"
 #include "wav_io.h"
-#include "wts_io.h"
 
-static std::string trim(std::string s)
-{
-    while (!s.empty() && (s.back() == '\n' || s.back() == '\r' || s.back() == ' ' || s.back() == '\t')) s.pop_back();
-    size_t i = 0;
-    while (i < s.size() && (s[i] == ' ' || s[i] == '\t')) ++i;
-    return s.substr(i);
-}
+using namespace bp;
+static const char *const WHO = "bpenhance";
 
 // the input and output files of wav_list, or the one pair
-static void read_wav_list(const std::string &list, const std::string &in_wav, const std::string &out_wav, std::vector<std::string> &ins,
+static void wav_pairs(const std::string &list, const std::string &in_wav, const std::string &out_wav, std::vector<std::string> &ins,
                           std::vector<std::string> &outs)
 {
     if (list.empty()) { ins.push_back(in_wav); outs.push_back(out_wav); return; }
-    FILE *fl = fopen(list.c_str(), "rt");
-    if (!fl) { printf("can not open wav list: %s\n", list.c_str()); exit(0); }
-    char line[8192];
-    while (fgets(line, sizeof(line), fl)) {
-        const std::string t = trim(line);
-        if (t.empty()) continue;
-        const size_t sp = t.find_first_of(" \t");
-        if (sp == std::string::npos) { printf("wav list %s: line \"%s\" needs an input and an output file\n", list.c_str(), t.c_str()); exit(0); }
-        ins.push_back(t.substr(0, sp)); outs.push_back(trim(t.substr(sp)));
-    }
-    fclose(fl);
-    if (ins.empty()) { printf("bpenhance: %s lists no wav file\n", list.c_str()); exit(0); }
+    read_pairs(WHO, "wav list", "wav list", "an input and an output file", list, ins, outs);
 }
 
 // method=logmmse: every file through bp_logmmse_waves, as many sentences per call as stay below MAXCACHEFRAME frames
@@ -69,10 +55,8 @@ static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, co
     std::vector<std::vector<float>> waves(ns);
     std::vector<int> rates(ns);
     for (int s = 0; s < ns; ++s) {
-        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
-        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
-        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
-        if (waves[s].size() > (size_t)1 << 30) { printf("%s: too long\n", ins[s].c_str()); exit(0); }
+        waves[s] = read_one(WHO, ins[s], &rates[s]);
+        if (waves[s].size() > (size_t)1 << 30) fail(ins[s] + ": too long");
     }
     std::vector<float> pcm, out;
     std::vector<int> lens;
@@ -90,11 +74,11 @@ static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, co
             ++s1;
         }
         out.resize(pcm.size());
-        if (bp_logmmse_waves(device, fea_dim, &lm, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(bp_logmmse_waves(device, fea_dim, &lm, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr));
         size_t off = 0;
         for (int s = s0; s < s1; ++s) {
             const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
-            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+            if (!e.empty()) fail(e);
             off += waves[s].size();
         }
         samples += pcm.size();
@@ -133,7 +117,7 @@ static size_t play_files(S *st, int (*push)(S *, const int *, const float *, con
             any = true;
         }
         if (!any) break;
-        if (push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(push(st, n_in.data(), pcm.data(), end.data(), n_out.data(), out.data(), out.size()));
         size_t off = 0;
         for (int c = 0; c < chan; ++c) {
             if (file[c] >= ns) continue;
@@ -157,18 +141,16 @@ static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params 
     std::vector<std::vector<float>> waves(ns), enh;
     std::vector<int> rates(ns);
     for (int s = 0; s < ns; ++s) {
-        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
-        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
-        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+        waves[s] = read_one(WHO, ins[s], &rates[s]);
     }
     bp_lmstream *st = nullptr;
-    if (bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    check(bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st));
     // a push returns what arrived plus what waited for the noise start or for the end of the sentence
     const size_t samples = play_files(st, bp_lmstream_push, chan, block, ins, waves, (size_t)chan * ((size_t)block + ((size_t)lm.init_frames + 1) * hop), enh);
     bp_lmstream_close(st);
     for (int s = 0; s < ns; ++s) {
         const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
-        if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+        if (!e.empty()) fail(e);
     }
     printf("bpenhance: %zu samples of %d sentences enhanced (logmmse, streamed)\n", samples, ns);
     return 1;
@@ -177,7 +159,7 @@ static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params 
 int main(int argc, char **argv)
 {
     std::string norm_file, wts_file, list, in_wav, out_wav;
-    bool logmmse = false;
+    int logmmse = 0;
     std::vector<std::string> given;
     bp_logmmse_params lm;
     bp_logmmse_defaults(&lm);
@@ -186,94 +168,57 @@ int main(int argc, char **argv)
     int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1;
     bool lm_chan_given = false;
     float vis = 0.f, hid = 0.f;
+    const char *const count = "is not a count >= 1";
+    const Key keys[] = {
+        {"method", K_CHOICE, &logmmse, 0, 0, "net|logmmse", "is not net or logmmse"},
+        {"lm_stream_block", K_INT, &lm_block, 1, 1 << 24, nullptr, count}, {"lm_stream_chan", K_INT, &lm_chan, 1, 1 << 24, nullptr, count},
+        {"norm_file", K_STR, &norm_file}, {"initwts_file", K_STR, &wts_file},
+        {"wav_list", K_STR, &list}, {"in_wav", K_STR, &in_wav}, {"out_wav", K_STR, &out_wav},
+        {"fea_dim", K_ATOI, &fea_dim}, {"fea_context", K_ATOI, &ctx}, {"targ_offset", K_ATOI, &toff}, {"dropoutflag", K_ATOI, &dropoutflag},
+        {"visible_omit", K_ATOF, &vis}, {"hid_omit", K_ATOF, &hid},
+        {"bunchsize", K_ATOI, &bunch}, {"traincache", K_ATOI, &cache},
+        {"activation", K_IS, &activation, 0, 0, "sigmoid"}, {"device", K_ATOI, &device},
+        {"compute", K_IS, &compute, 0, 0, "bf16"},
+        {"out_col", K_ATOI, &out_col},
+        {"stream_block", K_INT, &stream_block, 1, 1 << 24, nullptr, count}, {"stream_chan", K_INT, &stream_chan, 1, 1 << 24, nullptr, count},
+        {"forward", K_CHOICE, &forward, BP_FORWARD_DEFAULT, 0, "default|rowinv", "is not default or rowinv"},
+        {"wave_target", K_CHOICE, &target, BP_WAVE_LPS, 0, "lps|mask", "is not lps or mask"},
+        {"layersizes", K_ATOI_SIZES, ls, 0, MAXLAYER, nullptr, nullptr, &L},
+    };
     for (int i = 1; i < argc; ++i) {
-        char *eq = strchr(argv[i], '=');
-        if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
-        const std::string k(argv[i], eq - argv[i]), v(eq + 1);
+        const Arg a = split_arg(argv[i]);
+        const std::string &k = a.k, &v = a.v;
         given.push_back(k);
-        if (k == "method") {
-            if (v == "net") logmmse = false; else if (v == "logmmse") logmmse = true;
-            else { printf("method: %s is not net or logmmse\n", v.c_str()); exit(0); }
-        } else if (k == "lm_stream_block" || k == "lm_stream_chan") {
-            char *end = nullptr;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 1 || n > (1 << 24)) { printf("%s: %s is not a count >= 1\n", k.c_str(), v.c_str()); exit(0); }
-            if (k == "lm_stream_block") lm_block = (int)n; else { lm_chan = (int)n; lm_chan_given = true; }
-        } else if (k.compare(0, 3, "lm_") == 0) {
-            char *end = nullptr;
-            const double d = strtod(v.c_str(), &end);
-            if (v.empty() || *end) { printf("%s: %s is not a number\n", k.c_str(), v.c_str()); exit(0); }
-            if (k == "lm_alpha") lm.alpha = d; else if (k == "lm_mu") lm.mu = d; else if (k == "lm_eta") lm.eta = d;
-            else if (k == "lm_xi_min_db") lm.xi_min_db = d; else if (k == "lm_gamma_max") lm.gamma_max = d;
-            else if (k == "lm_init_frames") {
-                if (!(d >= -1e9 && d <= 1e9) || d != (double)(int)d) { printf("%s: %s is not a count\n", k.c_str(), v.c_str()); exit(0); }
-                lm.init_frames = (int)d;
-            }
-            else { printf("bpenhance: unknown key %s\n", k.c_str()); exit(0); }
-        }
-        else if (k == "norm_file") norm_file = v; else if (k == "initwts_file") wts_file = v;
-        else if (k == "wav_list") list = v; else if (k == "in_wav") in_wav = v; else if (k == "out_wav") out_wav = v;
-        else if (k == "fea_dim") fea_dim = atoi(v.c_str()); else if (k == "fea_context") ctx = atoi(v.c_str());
-        else if (k == "targ_offset") toff = atoi(v.c_str()); else if (k == "dropoutflag") dropoutflag = atoi(v.c_str());
-        else if (k == "visible_omit") vis = (float)atof(v.c_str()); else if (k == "hid_omit") hid = (float)atof(v.c_str());
-        else if (k == "bunchsize") bunch = atoi(v.c_str()); else if (k == "traincache") cache = atoi(v.c_str());
-        else if (k == "activation") activation = v == "sigmoid" ? 1 : 0; else if (k == "device") device = atoi(v.c_str());
-        else if (k == "compute") compute = v == "bf16" ? 1 : 0;
-        else if (k == "out_col") out_col = atoi(v.c_str());
-        else if (k == "stream_block" || k == "stream_chan") {
-            char *end = nullptr;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 1 || n > (1 << 24)) { printf("%s: %s is not a count >= 1\n", k.c_str(), v.c_str()); exit(0); }
-            (k == "stream_block" ? stream_block : stream_chan) = (int)n;
-        }
-        else if (k == "forward") {
-            if (v == "default") forward = BP_FORWARD_DEFAULT; else if (v == "rowinv") forward = BP_FORWARD_ROWINV;
-            else { printf("forward: %s is not default or rowinv\n", v.c_str()); exit(0); }
-        }
-        else if (k == "wave_target") {
-            if (v == "lps") target = BP_WAVE_LPS; else if (v == "mask") target = BP_WAVE_MASK;
-            else { printf("wave_target: %s is not lps or mask\n", v.c_str()); exit(0); }
-        }
+        if (k == "lm_stream_chan") lm_chan_given = true;
         // output layer (.wts files do not record it): the keys and checks of bptrain
-        else if (k == "output_act") {
-            if (v == "linear") out_act = 0; else if (v == "sigmoid") out_act = 1;
-            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
-        } else if (k == "output_linear_dims") {
-            char *end = nullptr;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
-            out_lin = (int)n;
-        } else if (k == "output_loss") {
-            if (v == "xent") out_loss = 0; else if (v == "mse") out_loss = 1;
-            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
+        if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss)) continue;
+        // the log-MMSE parameters stay by hand: any lm_ name is a number first (nan and inf included), and only then a known key
+        if (k.compare(0, 3, "lm_") != 0) fail("bpenhance: unknown key " + k);
+        char *end = nullptr;
+        const double d = strtod(v.c_str(), &end);
+        if (v.empty() || *end) fail(k + ": " + v + " is not a number");
+        if (k == "lm_alpha") lm.alpha = d; else if (k == "lm_mu") lm.mu = d; else if (k == "lm_eta") lm.eta = d;
+        else if (k == "lm_xi_min_db") lm.xi_min_db = d; else if (k == "lm_gamma_max") lm.gamma_max = d;
+        else if (k == "lm_init_frames") {
+            if (!(d >= -1e9 && d <= 1e9) || d != (double)(int)d) fail(k + ": " + v + " is not a count");
+            lm.init_frames = (int)d;
         }
-        else if (k == "layersizes") {
-            size_t pos = 0;
-            while (L < MAXLAYER) {
-                const size_t c = v.find(',', pos);
-                ls[L++] = atoi(v.substr(pos, c == std::string::npos ? c : c - pos).c_str());
-                if (c == std::string::npos) break;
-                pos = c + 1;
-            }
-        }
-        else { printf("bpenhance: unknown key %s\n", k.c_str()); exit(0); }
+        else fail("bpenhance: unknown key " + k);
     }
     for (const std::string &k : given) {
         const bool lm_key = k.compare(0, 3, "lm_") == 0;
-        if (!logmmse && lm_key) { printf("bpenhance: %s needs method=logmmse\n", k.c_str()); exit(0); }
+        if (!logmmse && lm_key) fail("bpenhance: " + k + " needs method=logmmse");
         if (logmmse && !lm_key && k != "method" && k != "fea_dim" && k != "device" && k != "wav_list" && k != "in_wav" && k != "out_wav") {
-            printf("bpenhance: method=logmmse takes no %s (only fea_dim, device, wav_list or in_wav and out_wav, and the lm_ keys, lm_stream_block and lm_stream_chan among them)\n", k.c_str());
-            exit(0);
+            fail("bpenhance: method=logmmse takes no " + k + " (only fea_dim, device, wav_list or in_wav and out_wav, and the lm_ keys, lm_stream_block and lm_stream_chan among them)");
         }
     }
     if (logmmse) {
-        if (list.empty() == (in_wav.empty() || out_wav.empty())) { printf("bpenhance: need wav_list, or in_wav and out_wav\n"); exit(0); }
-        const int nf = 2 * (fea_dim - 1);
-        if (fea_dim < 33 || fea_dim > 1025 || (nf & (nf - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
-        if (lm_chan_given && lm_block < 1) { printf("bpenhance: lm_stream_chan needs lm_stream_block\n"); exit(0); }
-        if (lm_block > 0 && ((long)lm_block * lm_chan > (1L << 28) || lm_chan > (1 << 16))) { printf("bpenhance: lm_stream_block * lm_stream_chan is too large\n"); exit(0); }
+        if (list.empty() == (in_wav.empty() || out_wav.empty())) fail("bpenhance: need wav_list, or in_wav and out_wav");
+        if (!fea_dim_ok(fea_dim)) fail("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+        if (lm_chan_given && lm_block < 1) fail("bpenhance: lm_stream_chan needs lm_stream_block");
+        if (lm_block > 0 && ((long)lm_block * lm_chan > (1L << 28) || lm_chan > (1 << 16))) fail("bpenhance: lm_stream_block * lm_stream_chan is too large");
         std::vector<std::string> li, lo;
-        read_wav_list(list, in_wav, out_wav, li, lo);
+        wav_pairs(list, in_wav, out_wav, li, lo);
         if (lm_block > 0) return logmmse_stream_mode(fea_dim, device, lm, lm_block, lm_chan, li, lo);
         return logmmse_mode(fea_dim, device, lm, li, lo);
     }
@@ -281,61 +226,37 @@ int main(int argc, char **argv)
         printf("bpenhance: need layersizes (2..%d sizes), fea_dim, fea_context, 0 <= targ_offset < fea_context, traincache <= %d\n", MAXLAYER - 1, MAXCACHEFRAME);
         exit(0);
     }
-    if (norm_file.empty() || wts_file.empty()) { printf("bpenhance: need norm_file and initwts_file\n"); exit(0); }
-    if (list.empty() == (in_wav.empty() || out_wav.empty())) { printf("bpenhance: need wav_list, or in_wav and out_wav\n"); exit(0); }
+    if (norm_file.empty() || wts_file.empty()) fail("bpenhance: need norm_file and initwts_file");
+    if (list.empty() == (in_wav.empty() || out_wav.empty())) fail("bpenhance: need wav_list, or in_wav and out_wav");
     const int n_fft = 2 * (fea_dim - 1), hop = n_fft / 2;
-    if (fea_dim < 33 || fea_dim > 1025 || (n_fft & (n_fft - 1))) { printf("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048\n"); exit(0); }
-    if (ls[0] != ctx * fea_dim && ls[0] != (ctx + 1) * fea_dim) { printf("bpenhance: layersizes[0] must be fea_context*fea_dim (+ fea_dim with a NAT block)\n"); exit(0); }
-    if (stream_chan > 1 && stream_block < 1) { printf("bpenhance: stream_chan needs stream_block\n"); exit(0); }
-    if (stream_block > 0 && (long)stream_block * stream_chan > (1L << 28)) { printf("bpenhance: stream_block * stream_chan is too large\n"); exit(0); }
-    if (forward == BP_FORWARD_ROWINV && compute == 1) { printf("bpenhance: forward=rowinv needs compute=fp32\n"); exit(0); }
-    if (out_col < 0 || out_col + fea_dim > ls[L - 1]) { printf("bpenhance: out_col + fea_dim exceeds layersizes[last]\n"); exit(0); }
+    if (!fea_dim_ok(fea_dim)) fail("bpenhance: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (ls[0] != ctx * fea_dim && ls[0] != (ctx + 1) * fea_dim) fail("bpenhance: layersizes[0] must be fea_context*fea_dim (+ fea_dim with a NAT block)");
+    if (stream_chan > 1 && stream_block < 1) fail("bpenhance: stream_chan needs stream_block");
+    if (stream_block > 0 && (long)stream_block * stream_chan > (1L << 28)) fail("bpenhance: stream_block * stream_chan is too large");
+    if (forward == BP_FORWARD_ROWINV && compute == 1) fail("bpenhance: forward=rowinv needs compute=fp32");
+    if (out_col < 0 || out_col + fea_dim > ls[L - 1]) fail("bpenhance: out_col + fea_dim exceeds layersizes[last]");
 
     // ---- inputs (all read and checked before the device is used)
     std::vector<std::string> ins, outs;
-    read_wav_list(list, in_wav, out_wav, ins, outs);
+    wav_pairs(list, in_wav, out_wav, ins, outs);
     const int ns = (int)ins.size();
     std::vector<std::vector<float>> waves(ns);
     std::vector<int> rates(ns);
     for (int s = 0; s < ns; ++s) {
-        const std::string err = bp::read_wav(ins[s], waves[s], rates[s]);
-        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
-        if (waves[s].empty()) { printf("%s: no samples\n", ins[s].c_str()); exit(0); }
+        waves[s] = read_one(WHO, ins[s], &rates[s]);
         const size_t rows = (waves[s].size() - 1) / hop + 2 + ctx - 1;
         if (stream_block < 1 && rows > (size_t)cache) { printf("%s: %zu rows exceed traincache=%d (one sentence per call at most)\n", ins[s].c_str(), rows, cache); exit(0); }
     }
-    std::vector<float> mean(fea_dim), istd(fea_dim);
-    {
-        // normalisation file: 1 header line, fea_dim means, 1 header line, fea_dim inverse std (as PfileReader reads it)
-        FILE *fn = fopen(norm_file.c_str(), "rt");
-        if (!fn) { printf("can not open normalization file: %s\n", norm_file.c_str()); exit(0); }
-        char buff[256];
-        bool ok = fgets(buff, sizeof(buff), fn) != nullptr;
-        for (int j = 0; ok && j < fea_dim; ++j) { ok = fgets(buff, sizeof(buff), fn) != nullptr; mean[j] = (float)atof(buff); }
-        ok = ok && fgets(buff, sizeof(buff), fn) != nullptr;
-        for (int j = 0; ok && j < fea_dim; ++j) { ok = fgets(buff, sizeof(buff), fn) != nullptr; istd[j] = (float)atof(buff); }
-        fclose(fn);
-        if (!ok) { printf("normalization file too short\n"); exit(0); }
-    }
-    std::vector<std::vector<float>> Wv(L), Bv(L);
-    float *weights[MAXLAYER] = {0}, *bias[MAXLAYER] = {0};
-    for (int i = 1; i < L; ++i) { Wv[i].assign((size_t)ls[i] * ls[i - 1], 0.f); Bv[i].assign(ls[i], 0.f); weights[i] = Wv[i].data(); bias[i] = Bv[i].data(); }
-    FILE *fi = fopen(wts_file.c_str(), "rb");
-    if (!fi) { printf("can not open initial weights file: %s\n", wts_file.c_str()); exit(0); }
-    const std::string err = bp::read_weights(fi, L, ls, weights, bias);
-    fclose(fi);
-    if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+    std::vector<float> mean, istd;
+    read_norm(norm_file, fea_dim, mean, istd);
+    Weights wts(L, ls);
+    const std::string err = load_weights(wts_file, L, ls, wts);
+    if (!err.empty()) fail(err);
 
-    bp_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.gpu_used = 1; cfg.numlayers = L;
-    for (int i = 0; i < L; ++i) cfg.layersizes[i] = ls[i];
-    cfg.bunchsize = bunch; cfg.lrate = 0.f; cfg.momentum = 0.f; cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid;
-    cfg.activation = activation; cfg.device = device; cfg.compute_dtype = compute; cfg.max_chunk_frames = cache;
-    bp_handle *h = nullptr;
-    if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
-    if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
-    if (bp_set_forward(h, forward) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    bp_config cfg = net_config(L, ls, bunch, cache, device);
+    cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid; cfg.activation = activation; cfg.compute_dtype = compute;
+    bp_handle *h = create_net(cfg, wts, out_act, out_lin, out_loss);
+    check(bp_set_forward(h, forward));
 
     std::vector<float> pcm, out;
     std::vector<int> lens;
@@ -347,14 +268,14 @@ int main(int argc, char **argv)
         sc.fea_dim = fea_dim; sc.context = ctx; sc.targ_offset = toff; sc.mean = mean.data(); sc.inv_std = istd.data();
         sc.target = target; sc.out_col = out_col; sc.n_chan = stream_chan; sc.max_push_samples = stream_block * stream_chan;
         bp_stream *st = nullptr;
-        if (bp_stream_open(h, &sc, &st) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(bp_stream_open(h, &sc, &st));
         std::vector<std::vector<float>> enh;
         // a push returns what arrived plus, at the end of a sentence, the frames that waited for their look-ahead or the NAT row
         samples = play_files(st, bp_stream_push, stream_chan, stream_block, ins, waves, (size_t)stream_chan * ((size_t)stream_block + (size_t)(ctx + 8) * hop), enh);
         bp_stream_close(st);
         for (int s = 0; s < ns; ++s) {
             const std::string e = bp::write_wav(outs[s], enh[s].data(), waves[s].size(), rates[s]);
-            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+            if (!e.empty()) fail(e);
         }
     }
     // ---- as many sentences per call as fit the chunk
@@ -375,11 +296,11 @@ int main(int argc, char **argv)
         memset(&c, 0, sizeof(c));
         c.n_sent = s1 - s0; c.sent_len = lens.data(); c.pcm = pcm.data(); c.context = ctx; c.targ_offset = toff;
         c.mean = mean.data(); c.inv_std = istd.data(); c.target = target; c.out_col = out_col;
-        if (bp_enhance_waves(h, fea_dim, &c, out.data(), nullptr) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(bp_enhance_waves(h, fea_dim, &c, out.data(), nullptr));
         size_t off = 0;
         for (int s = s0; s < s1; ++s) {
             const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
-            if (!e.empty()) { printf("%s\n", e.c_str()); exit(0); }
+            if (!e.empty()) fail(e);
             off += waves[s].size();
         }
         samples += pcm.size();

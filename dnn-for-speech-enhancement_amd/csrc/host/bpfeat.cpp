@@ -15,47 +15,32 @@
 #include <vector>
 
 #include "../../../include/bp_c_api.h"
+#include "corpus.h"
+#include "keys.h"
+#include "net_setup.h"
 #include "pfile_writer.h"
-#include "wav_io.h"
 
 int main(int argc, char **argv)
 {
     std::string list, out_file, norm_out;
     int fea_dim = 0, device = 0;
+    using namespace bp;
+    const Key keys[] = {
+        {"wav_list", K_STR, &list}, {"out_file", K_STR, &out_file}, {"norm_out", K_STR, &norm_out},
+        {"fea_dim", K_ATOI, &fea_dim}, {"device", K_ATOI, &device},
+    };
     for (int i = 1; i < argc; ++i) {
-        const char *eq = strchr(argv[i], '=');
-        if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
-        const std::string k(argv[i], eq - argv[i]), v(eq + 1);
-        if (k == "wav_list") list = v; else if (k == "out_file") out_file = v; else if (k == "norm_out") norm_out = v;
-        else if (k == "fea_dim") fea_dim = atoi(v.c_str()); else if (k == "device") device = atoi(v.c_str());
-        else { printf("bpfeat: unknown key %s\n", k.c_str()); exit(0); }
+        const Arg a = split_arg(argv[i]);
+        if (!key_apply(keys, "bpfeat", a)) fail("bpfeat: unknown key " + a.k);
     }
-    const int n_fft = 2 * (fea_dim - 1);
-    if (list.empty() || out_file.empty() || fea_dim < 33 || fea_dim > 1025 || (n_fft & (n_fft - 1))) {
-        printf("bpfeat: need wav_list, out_file and fea_dim (2*(fea_dim-1) a power of two from 64 to 2048)\n");
-        exit(0);
-    }
+    if (list.empty() || out_file.empty() || !fea_dim_ok(fea_dim))
+        fail("bpfeat: need wav_list, out_file and fea_dim (2*(fea_dim-1) a power of two from 64 to 2048)");
     // every WAV is read and checked before the device is used
-    FILE *fl = fopen(list.c_str(), "rt");
-    if (!fl) { printf("can not open wav list: %s\n", list.c_str()); exit(0); }
-    std::vector<std::vector<float>> waves;
-    char line[4096];
-    while (fgets(line, sizeof(line), fl)) {
-        std::string p(line);
-        while (!p.empty() && (p.back() == '\n' || p.back() == '\r' || p.back() == ' ' || p.back() == '\t')) p.pop_back();
-        if (p.empty()) continue;
-        waves.emplace_back();
-        int sr = 0;
-        const std::string err = bp::read_wav(p, waves.back(), sr);
-        if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
-        if (waves.back().empty()) { printf("%s: no samples\n", p.c_str()); exit(0); }
-    }
-    fclose(fl);
-    if (waves.empty()) { printf("bpfeat: %s lists no wav file\n", list.c_str()); exit(0); }
+    const std::vector<std::vector<float>> waves = read_wav_list("bpfeat", "wav list", list);
 
-    const int hop = n_fft / 2, D = fea_dim, ns = (int)waves.size();
+    const int hop = fea_dim - 1, D = fea_dim, ns = (int)waves.size();
     bp::PfileWriter pw;
-    if (!pw.open(out_file, ns, D)) { printf("can not open output file: %s\n", out_file.c_str()); exit(0); }
+    if (!pw.open(out_file, ns, D)) fail("can not open output file: " + out_file);
     std::vector<double> sum(D, 0.0), sq(D, 0.0);
     size_t frames = 0;
     // sentences in batches of about 2^24 samples per call
@@ -72,7 +57,7 @@ int main(int argc, char **argv)
             ++s1;
         }
         lps.resize(T * D);
-        if (bp_wave_lps(device, D, s1 - s0, lens.data(), pcm.data(), lps.data()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(bp_wave_lps(device, D, s1 - s0, lens.data(), pcm.data(), lps.data()));
         size_t f = 0;
         for (int s = s0; s < s1; ++s) {
             const int Ts = (int)((waves[s].size() - 1) / hop + 2);
@@ -88,15 +73,8 @@ int main(int argc, char **argv)
     pw.close();
     if (!norm_out.empty()) {
         FILE *fn = fopen(norm_out.c_str(), "wt");
-        if (!fn) { printf("can not open norm file: %s\n", norm_out.c_str()); exit(0); }
-        fprintf(fn, "<mean>\n");
-        for (int k = 0; k < D; ++k) fprintf(fn, "%.9g\n", sum[k] / frames);
-        fprintf(fn, "<inverse std>\n");
-        for (int k = 0; k < D; ++k) {
-            const double m = sum[k] / frames, var = sq[k] / frames - m * m;
-            fprintf(fn, "%.9g\n", var > 0.0 ? 1.0 / sqrt(var) : 1.0);
-        }
-        fclose(fn);
+        if (!fn) fail("can not open norm file: " + norm_out);
+        write_norm(fn, sum, sq, frames);
     }
     printf("bpfeat: %zu frames of %d sentences -> %s\n", frames, ns, out_file.c_str());
     return 1;

@@ -24,6 +24,8 @@
 #include <vector>
 
 #include "../../../include/BP_GPU.h"
+#include "keys.h"
+#include "net_setup.h"
 #include "pfile_reader.h"
 #include "pfile_writer.h"
 #include "wts_io.h"
@@ -34,40 +36,21 @@ int main(int argc, char **argv)
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0;
     float vis = 0.f, hid = 0.f;
+    using namespace bp;
+    const Key keys[] = {
+        {"fea_file", K_STR, &fea_file}, {"norm_file", K_STR, &norm_file}, {"initwts_file", K_STR, &wts_file},
+        {"out_file", K_STR, &out_file}, {"sent_range", K_STR, &range},
+        {"fea_dim", K_ATOI, &fea_dim}, {"fea_context", K_ATOI, &ctx}, {"targ_offset", K_ATOI, &toff}, {"dropoutflag", K_ATOI, &dropoutflag},
+        {"visible_omit", K_ATOF, &vis}, {"hid_omit", K_ATOF, &hid},
+        {"bunchsize", K_ATOI, &bunch}, {"traincache", K_ATOI, &cache},
+        {"activation", K_IS, &activation, 0, 0, "sigmoid"}, {"device", K_ATOI, &device},
+        {"compute", K_IS, &compute, 0, 0, "bf16"},
+        {"layersizes", K_ATOI_SIZES, ls, 0, MAXLAYER, nullptr, nullptr, &L},
+    };
     for (int i = 1; i < argc; ++i) {
-        char *eq = strchr(argv[i], '=');
-        if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
-        const std::string k(argv[i], eq - argv[i]), v(eq + 1);
-        if (k == "fea_file") fea_file = v; else if (k == "norm_file") norm_file = v; else if (k == "initwts_file") wts_file = v;
-        else if (k == "out_file") out_file = v; else if (k == "sent_range") range = v;
-        else if (k == "fea_dim") fea_dim = atoi(v.c_str()); else if (k == "fea_context") ctx = atoi(v.c_str());
-        else if (k == "targ_offset") toff = atoi(v.c_str()); else if (k == "dropoutflag") dropoutflag = atoi(v.c_str());
-        else if (k == "visible_omit") vis = (float)atof(v.c_str()); else if (k == "hid_omit") hid = (float)atof(v.c_str());
-        else if (k == "bunchsize") bunch = atoi(v.c_str()); else if (k == "traincache") cache = atoi(v.c_str());
-        else if (k == "activation") activation = v == "sigmoid" ? 1 : 0; else if (k == "device") device = atoi(v.c_str());
-        else if (k == "compute") compute = v == "bf16" ? 1 : 0;
-        // output layer (.wts files do not record it): the keys and checks of bptrain
-        else if (k == "output_act") {
-            if (v == "linear") out_act = 0; else if (v == "sigmoid") out_act = 1;
-            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
-        } else if (k == "output_linear_dims") {
-            char *end = nullptr;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
-            out_lin = (int)n;
-        } else if (k == "output_loss") {
-            if (v == "xent") out_loss = 0; else if (v == "mse") out_loss = 1;
-            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
-        }
-        else if (k == "layersizes") {
-            size_t pos = 0;
-            while (L < MAXLAYER) {
-                const size_t c = v.find(',', pos);
-                ls[L++] = atoi(v.substr(pos, c == std::string::npos ? c : c - pos).c_str());
-                if (c == std::string::npos) break;
-                pos = c + 1;
-            }
-        }
+        const Arg a = split_arg(argv[i]);
+        // output layer (.wts files do not record it): the keys and checks of bptrain; other unknown names are ignored
+        if (!key_apply(keys, "bpforward", a)) output_key(a, &out_act, &out_lin, &out_loss);
     }
     if (L < 2 || L > MAXLAYER - 1 || fea_dim < 1 || ctx < 1 || toff < 0 || toff >= ctx || cache < 1 || cache > MAXCACHEFRAME || bunch < 1) {
         printf("bpforward: need layersizes (2..%d sizes), fea_dim, fea_context, 0 <= targ_offset < fea_context, traincache <= %d\n", MAXLAYER - 1, MAXCACHEFRAME);
@@ -80,34 +63,23 @@ int main(int argc, char **argv)
     rc.traincache = cache; rc.input_dim = ls[0];
     bp::PfileReader reader(rc);
     reader.open();
-    std::vector<std::vector<float>> Wv(L), Bv(L);
-    float *weights[MAXLAYER] = {0}, *bias[MAXLAYER] = {0};
-    for (int i = 1; i < L; ++i) { Wv[i].assign((size_t)ls[i] * ls[i - 1], 0.f); Bv[i].assign(ls[i], 0.f); weights[i] = Wv[i].data(); bias[i] = Bv[i].data(); }
-    FILE *fi = fopen(wts_file.c_str(), "rb");
-    if (!fi) { printf("can not open initial weights file: %s\n", wts_file.c_str()); exit(0); }
-    const std::string err = bp::read_weights(fi, L, ls, weights, bias);
-    fclose(fi);
-    if (!err.empty()) { printf("%s\n", err.c_str()); exit(0); }
+    Weights wts(L, ls);
+    const std::string err = load_weights(wts_file, L, ls, wts);
+    if (!err.empty()) fail(err);
     int st = 0, en = (int)reader.total_sents() - 1;
     if (!range.empty()) { const size_t d = range.find('-'); if (d == std::string::npos) { printf("sent range: %s format error.\n", range.c_str()); exit(0); }
                           st = atoi(range.substr(0, d).c_str()); en = atoi(range.substr(d + 1).c_str()); }
     if (st < 0 || en >= (int)reader.total_sents() || st > en) { printf("sent range: %d to %d number error.\n", st, en); exit(0); }
 
-    bp_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.gpu_used = 1; cfg.numlayers = L;
-    for (int i = 0; i < L; ++i) cfg.layersizes[i] = ls[i];
-    cfg.bunchsize = bunch; cfg.lrate = 0.f; cfg.momentum = 0.f; cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid;
-    cfg.activation = activation; cfg.device = device; cfg.compute_dtype = compute; cfg.max_chunk_frames = cache;
-    bp_handle *h = nullptr;
-    if (bp_create(&cfg, weights, bias, &h) != 0) { printf("%s\n", bp_last_error()); exit(0); }
-    if (bp_set_output(h, out_act, out_lin, out_loss) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+    bp_config cfg = net_config(L, ls, bunch, cache, device);
+    cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid; cfg.activation = activation; cfg.compute_dtype = compute;
+    bp_handle *h = create_net(cfg, wts, out_act, out_lin, out_loss);
 
     // ---- output Pfile: records in reader order
     const std::vector<int> &fbs = reader.frames_before_sent();         // end offset (frames) of every sentence
     const int nsent = en - st + 1;
     bp::PfileWriter pw;
-    if (!pw.open(out_file, nsent, sL)) { printf("can not open output file: %s\n", out_file.c_str()); exit(0); }
+    if (!pw.open(out_file, nsent, sL)) fail("can not open output file: " + out_file);
     const bp::PfileReader::Plan plan = reader.plan_inference(st, en);    // every window exactly once (no training-style cut losses)
     bp::PfileReader::WindowChunk w;
     std::vector<float> out;
@@ -121,7 +93,7 @@ int main(int argc, char **argv)
         d.fea = w.fea.data(); d.nat = w.nat.empty() ? nullptr : w.nat.data(); d.win_start = w.win_start.data();
         d.nat_row = w.nat_row.empty() ? nullptr : w.nat_row.data();
         out.resize((size_t)n * sL);
-        if (bp_forward_windows(h, &d, out.data()) != 0) { printf("%s\n", bp_last_error()); exit(0); }
+        check(bp_forward_windows(h, &d, out.data()));
         for (int i = 0; i < n; ++i) {
             const int gframe = plan.chunk_frame_st[c] + w.win_start[i];            // first frame of the window, file-global
             const int s = (int)(std::upper_bound(fbs.begin(), fbs.end(), gframe) - fbs.begin());

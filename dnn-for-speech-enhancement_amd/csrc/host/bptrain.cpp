@@ -36,6 +36,8 @@
 
 #include "../../../include/BP_GPU.h"
 #include "chunk_ring.h"
+#include "keys.h"
+#include "net_setup.h"
 #include "pfile_reader.h"
 #include "wts_io.h"
 
@@ -47,7 +49,7 @@ struct Params {
     int seed = 0, numlayers = 0, layersizes[MAXLAYER] = {0};
     float momentum = 0, weightcost = 0, lrate = 0, visible_omit = 0, hid_omit = 0;
     float wmin = -0.1f, wmax = 0.1f, bmin = -0.1f, bmax = 0.1f;          // Interface.cc:79-82
-    bool stack_on_device = true, prefetch = true;
+    int stack_on_device = 1, prefetch = 1;
     int activation = 0, momentum_rule = 0, device = -1, compute_dtype = 0;
     int output_act = 0, output_linear_dims = 0, output_loss = 0;
     unsigned long long dropout_seed = 0;
@@ -65,6 +67,8 @@ typedef bp::PfileReader::WindowChunk WindowChunk;
 
 // The trainer object: the calls of the drop-in class include/BP_GPU.h (same messages, same error convention), on a handle
 // this file owns, so that the output layer can be configured (bp_set_output) right after bp_create.
+using bp::check;                                            // (reference convention: message + exit(0))
+
 class Trainer {
 public:
     Trainer(bp_config cfg, float **weights, float **bias, int dp_world, int dp_rank, const char *dp_key, int out_act, int out_lin,
@@ -101,10 +105,6 @@ private:
     Trainer(const Trainer &);
     Trainer &operator=(const Trainer &);
     void push_hyper() { check(bp_set_hyper(h_, cfg_.lrate, cfg_.momentum, cfg_.weightcost, cfg_.dropoutflag, cfg_.visible_omit, cfg_.hid_omit)); }
-    static void check(int rc)
-    {
-        if (rc != 0) { printf("%s\n", bp_last_error()); exit(0); }   // reference convention: message + exit(0)
-    }
     bp_config cfg_;
     bp_handle *h_ = nullptr;
 };
@@ -186,55 +186,34 @@ int main(int argc, char **argv)
 {
     const double t_start = (double)time(NULL);
     Params P;
-    for (int i = 1; i < argc; ++i) {
-        char *eq = strchr(argv[i], '=');
-        if (!eq) { printf("Arg: %s  Format Error\n", argv[i]); exit(0); }
-        const std::string k(argv[i], eq - argv[i]), v(eq + 1);
-        if (k == "fea_file") P.fea_file = v; else if (k == "norm_file") P.norm_file = v;
-        else if (k == "targ_file") P.targ_file = v; else if (k == "outwts_file") P.outwts_file = v;
-        else if (k == "log_file") P.log_file = v; else if (k == "initwts_file") P.initwts_file = v;
-        else if (k == "train_sent_range") P.train_range = v; else if (k == "cv_sent_range") P.cv_range = v;
-        else if (k == "fea_dim") P.fea_dim = atoi(v.c_str()); else if (k == "fea_context") P.fea_context = atoi(v.c_str());
-        else if (k == "targ_offset") P.targ_offset = atoi(v.c_str()); else if (k == "dropoutflag") P.dropoutflag = atoi(v.c_str());
-        else if (k == "traincache") P.traincache = atoi(v.c_str()); else if (k == "bunchsize") P.bunchsize = atoi(v.c_str());
-        else if (k == "gpu_used") P.gpu_used = atoi(v.c_str()); else if (k == "init_randem_seed") P.seed = atoi(v.c_str());
-        else if (k == "momentum") P.momentum = (float)atof(v.c_str()); else if (k == "weightcost") P.weightcost = (float)atof(v.c_str());
-        else if (k == "lrate") P.lrate = (float)atof(v.c_str()); else if (k == "visible_omit") P.visible_omit = (float)atof(v.c_str());
-        else if (k == "hid_omit") P.hid_omit = (float)atof(v.c_str());
-        else if (k == "init_randem_weight_min") P.wmin = (float)atof(v.c_str()); else if (k == "init_randem_weight_max") P.wmax = (float)atof(v.c_str());
-        else if (k == "init_randem_bias_min") P.bmin = (float)atof(v.c_str()); else if (k == "init_randem_bias_max") P.bmax = (float)atof(v.c_str());
-        else if (k == "layersizes") {
-            P.numlayers = 0;
-            size_t pos = 0;
-            while (P.numlayers < MAXLAYER) {
-                const size_t c = v.find(',', pos);
-                P.layersizes[P.numlayers++] = atoi(v.substr(pos, c == std::string::npos ? c : c - pos).c_str());
-                if (c == std::string::npos) break;
-                pos = c + 1;
-            }
-        }
+    using namespace bp;
+    const Key keys[] = {
+        {"fea_file", K_STR, &P.fea_file}, {"norm_file", K_STR, &P.norm_file}, {"targ_file", K_STR, &P.targ_file},
+        {"outwts_file", K_STR, &P.outwts_file}, {"log_file", K_STR, &P.log_file}, {"initwts_file", K_STR, &P.initwts_file},
+        {"train_sent_range", K_STR, &P.train_range}, {"cv_sent_range", K_STR, &P.cv_range},
+        {"fea_dim", K_ATOI, &P.fea_dim}, {"fea_context", K_ATOI, &P.fea_context}, {"targ_offset", K_ATOI, &P.targ_offset},
+        {"dropoutflag", K_ATOI, &P.dropoutflag}, {"traincache", K_ATOI, &P.traincache}, {"bunchsize", K_ATOI, &P.bunchsize},
+        {"gpu_used", K_ATOI, &P.gpu_used}, {"init_randem_seed", K_ATOI, &P.seed},
+        {"momentum", K_ATOF, &P.momentum}, {"weightcost", K_ATOF, &P.weightcost}, {"lrate", K_ATOF, &P.lrate},
+        {"visible_omit", K_ATOF, &P.visible_omit}, {"hid_omit", K_ATOF, &P.hid_omit},
+        {"init_randem_weight_min", K_ATOF, &P.wmin}, {"init_randem_weight_max", K_ATOF, &P.wmax},
+        {"init_randem_bias_min", K_ATOF, &P.bmin}, {"init_randem_bias_max", K_ATOF, &P.bmax},
+        {"layersizes", K_ATOI_SIZES, P.layersizes, 0, MAXLAYER, nullptr, nullptr, &P.numlayers},
         // switches the reference only has as source edits (handed to the shim in its bp_config constructor)
-        else if (k == "activation") P.activation = v == "sigmoid" ? 1 : 0;
-        else if (k == "momentum_rule") P.momentum_rule = v == "classic" ? 1 : 0;
-        else if (k == "seed") P.dropout_seed = strtoull(v.c_str(), 0, 10);
-        else if (k == "device") P.device = atoi(v.c_str());
-        else if (k == "compute") P.compute_dtype = v == "bf16" ? 1 : 0;         // fp32 (default) | bf16
-        else if (k == "stack") P.stack_on_device = (v != "host");
-        else if (k == "prefetch") P.prefetch = atoi(v.c_str()) != 0;
-        // output layer (bp_set_output): strict, a typo must not silently train a different model
-        else if (k == "output_act") {
-            if (v == "linear") P.output_act = 0; else if (v == "sigmoid") P.output_act = 1;
-            else { printf("output_act: %s is not linear or sigmoid\n", v.c_str()); exit(0); }
-        } else if (k == "output_linear_dims") {
-            char *end = nullptr;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || n < 0 || n > 1000000) { printf("output_linear_dims: %s is not a column count\n", v.c_str()); exit(0); }
-            P.output_linear_dims = (int)n;
-        } else if (k == "output_loss") {
-            if (v == "xent") P.output_loss = 0; else if (v == "mse") P.output_loss = 1;
-            else { printf("output_loss: %s is not xent or mse\n", v.c_str()); exit(0); }
-        }
-        // unknown names are silently ignored, as in the reference (e.g. the .pl passes numlayers=)
+        {"activation", K_IS, &P.activation, 0, 0, "sigmoid"},
+        {"momentum_rule", K_IS, &P.momentum_rule, 0, 0, "classic"},
+        {"seed", K_STRTOULL, &P.dropout_seed},
+        {"device", K_ATOI, &P.device},
+        {"compute", K_IS, &P.compute_dtype, 0, 0, "bf16"},                 // fp32 (default) | bf16
+        {"stack", K_ISNT, &P.stack_on_device, 0, 0, "host"},
+        {"prefetch", K_NONZERO, &P.prefetch},
+    };
+    for (int i = 1; i < argc; ++i) {
+        const Arg a = split_arg(argv[i]);
+        if (a.k == "layersizes") P.numlayers = 0;           // (the last layersizes= counts here; bpforward and bpenhance append)
+        // output layer (bp_set_output): strict, a typo must not silently train a different model.  Other unknown names are
+        // silently ignored, as in the reference (e.g. the .pl passes numlayers=)
+        if (!key_apply(keys, "bptrain", a)) output_key(a, &P.output_act, &P.output_linear_dims, &P.output_loss);
     }
     // ---- gpu_used > 1: data-parallel ranks, forked further down -- after the parent has opened the files, initialised the
     // weights, planned and shuffled the chunks and mapped the shared chunk ring (all inherited), but before anything
@@ -295,23 +274,15 @@ int main(int argc, char **argv)
     reader.open();
     fprintf(log, "Norm file loaded.\n");
 
-    std::vector<std::vector<float>> Wv(L), Bv(L);
-    float *weights[MAXLAYER] = {0}, *bias[MAXLAYER] = {0};
-    for (int i = 1; i < L; ++i) {
-        Wv[i].assign((size_t)P.layersizes[i] * P.layersizes[i - 1], 0.f); Bv[i].assign(P.layersizes[i], 0.f);
-        weights[i] = Wv[i].data(); bias[i] = Bv[i].data();
-    }
+    Weights wts(L, P.layersizes);
+    float **weights = wts.weights, **bias = wts.bias;
     srand48(P.seed);                                    // once, for weights and every shuffle (Interface.cc:338)
     if (P.initwts_file.empty()) {
         fprintf(log, "Getting Randemed initial weights...\n");
         bp::random_weights(L, P.layersizes, weights, bias, P.wmin, P.wmax, P.bmin, P.bmax);
         fprintf(log, "Randemed initial weights getted.\n");
     } else {
-        FILE *fi = fopen(P.initwts_file.c_str(), "rb");
-        if (!fi) { fprintf(log, "can not open initial weights file: %s\n", P.initwts_file.c_str()); exit(0); }
-        fprintf(log, "Loading Init weight file...\n");
-        const std::string err = bp::read_weights(fi, L, P.layersizes, weights, bias);
-        fclose(fi);
+        const std::string err = load_weights(P.initwts_file, L, P.layersizes, wts, log);
         if (!err.empty()) { fprintf(log, "%s\n", err.c_str()); exit(0); }
         fprintf(log, "Init weight file loaded.\n");
     }
@@ -353,15 +324,11 @@ int main(int argc, char **argv)
     }
 
     // ---- BPtrain.cc:31-96
-    bp_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.gpu_used = P.gpu_used > 0 ? P.gpu_used : 1; cfg.numlayers = L;
-    for (int i = 0; i < L; ++i) cfg.layersizes[i] = P.layersizes[i];
-    cfg.bunchsize = P.bunchsize / world;                    // BP_GPU.cu:29-36: the bunch is split over the GPUs
+    bp_config cfg = net_config(L, P.layersizes, P.bunchsize / world, P.traincache, 0);      // BP_GPU.cu:29-36: the bunch is split over the GPUs
+    cfg.gpu_used = P.gpu_used > 0 ? P.gpu_used : 1;
     cfg.lrate = P.lrate; cfg.momentum = P.momentum; cfg.weightcost = P.weightcost;
     cfg.dropoutflag = P.dropoutflag; cfg.visible_omit = P.visible_omit; cfg.hid_omit = P.hid_omit;
     cfg.activation = P.activation; cfg.momentum_rule = P.momentum_rule; cfg.seed = P.dropout_seed; cfg.compute_dtype = P.compute_dtype;
-    cfg.max_chunk_frames = P.traincache;
     if (P.device >= 0) cfg.device = P.device + (world > 1 ? rank : 0);
     else if (world > 1) {
         int ndev = 1;

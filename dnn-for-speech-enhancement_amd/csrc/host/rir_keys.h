@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/bp_c_api.h"
+#include "keys.h"
 
 namespace bp {
 
@@ -20,41 +21,19 @@ struct RirKeys {
     bool any = false;                                            // a key that only means something beside rir_rooms was given
 };
 
-inline bool rir_doubles(const std::string &v, int n, double *out)
-{
-    size_t pos = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t c = v.find(',', pos);
-        if ((c == std::string::npos) != (i == n - 1)) return false;
-        const std::string s = v.substr(pos, c == std::string::npos ? c : c - pos);
-        char *end = nullptr;
-        const double d = strtod(s.c_str(), &end);
-        if (s.empty() || *end || !std::isfinite(d)) return false;
-        out[i] = d;
-        pos = c + 1;
-    }
-    return true;
-}
-
 // 0: k is not one of the keys; 1: taken; -1: bad value
 inline int rir_key(RirKeys &K, const std::string &k, const std::string &v)
 {
-    auto count = [&v](int *out) {
-        char *end = nullptr;
-        const long n = strtol(v.c_str(), &end, 10);
-        if (v.empty() || *end || n < 1 || n > (1 << 20)) return -1;
-        *out = (int)n;
-        return 1;
-    };
+    auto count = [&v](int *out) { return parse_int(v, 1, 1 << 20, out) ? 1 : -1; };
     if (k == "rir_rooms") return count(&K.rooms);
     if (k == "cv_rir_rooms") return count(&K.cv_rooms);
     int r = 0;
-    if (k == "rir_room_lo") r = rir_doubles(v, 3, K.lo) ? 1 : -1;
-    else if (k == "rir_room_hi") r = rir_doubles(v, 3, K.hi) ? 1 : -1;
-    else if (k == "rir_t60") r = rir_doubles(v, 2, K.t60) ? 1 : -1;
-    else if (k == "rir_dist") r = rir_doubles(v, 2, K.dist) ? 1 : -1;
-    else if (k == "rir_margin") r = rir_doubles(v, 1, &K.margin) ? 1 : -1;
-    else if (k == "rir_ms") r = rir_doubles(v, 1, &K.ms) && K.ms > 0.0 && K.ms <= 1e6 ? 1 : -1;
+    if (k == "rir_room_lo") r = parse_doubles(v, 3, K.lo) ? 1 : -1;
+    else if (k == "rir_room_hi") r = parse_doubles(v, 3, K.hi) ? 1 : -1;
+    else if (k == "rir_t60") r = parse_doubles(v, 2, K.t60) ? 1 : -1;
+    else if (k == "rir_dist") r = parse_doubles(v, 2, K.dist) ? 1 : -1;
+    else if (k == "rir_margin") r = parse_doubles(v, 1, &K.margin) ? 1 : -1;
+    else if (k == "rir_ms") r = parse_doubles(v, 1, &K.ms) && K.ms > 0.0 && K.ms <= 1e6 ? 1 : -1;
     else if (k == "rir_window") r = count(&K.window);
     else if (k == "rir_rooms_out") { K.rooms_out = v; r = 1; }
     if (r) K.any = true;
