@@ -234,15 +234,16 @@ extern "C" int bp_logmmse_waves(int device, int fea_dim, const bp_logmmse_params
     // one host->device block, that of bp_wave_lps (no norm file); one device->host block: padded enhanced PCM | vad | gain; between
     // them the spectrum and the synthesis frames
     const WaveIn w = wave_in_layout(wp, D);
-    const size_t o_out = w.bytes, o_vad = o_out + al256(wp.padded * 4), o_gain = o_vad + al256(f * 4), out_end = o_gain + al256(f * D * 4);
-    const size_t o_Y = out_end, o_syn = o_Y + al256(f * D * sizeof(float2)), total = o_syn + al256(f * wp.N * 4);
+    Layout lay(w.bytes);
+    const size_t o_out = lay.take(wp.padded * 4), o_vad = lay.take(f * 4), o_gain = lay.take(f * D * 4), out_end = lay.size();
+    const size_t o_Y = lay.take(f * D * sizeof(float2)), o_syn = lay.take(f * wp.N * 4), total = lay.size();
     const size_t out_b = (out_gain ? out_end : out_vad ? o_gain : o_vad) - o_out;
     OneShot os;
     { const int r = os.open(who, device, total); if (r != BP_OK) return r; }
     std::vector<char> hb(w.bytes), ho(out_b);
     wave_in_fill(hb.data(), w, wp, D, nullptr, nullptr, sent_len, pcm);
     hipError_t &e = os.e;
-    char *d = os.d;
+    char *d = os.d.as<char>();
     if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, os.st);
     const float *win = (const float *)(d + w.win);
     const float2 *tw = (const float2 *)(d + w.tw);
@@ -326,18 +327,21 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
     s->max_units = (size_t)nc * ((size_t)lp.init_frames + 4) + (size_t)max_push_samples / hop;
     const size_t carry_cap = ((size_t)lp.init_frames + 2) * hop;
     if (s->max_units * hop > (size_t)INT32_MAX) { lmstream_release(s); return fail(BP_ERR_NOMEM, "bp_lmstream_open: the blocks of a push would exceed 2^31 samples"); }
-    size_t o = 0;
-    s->o_win = o; o += al256((size_t)N * 4);
-    s->o_tw = o; o += al256((size_t)(hop + 1) * 8);
-    const size_t consts = o;
-    s->o_lam = o; o += al256((size_t)nc * D * 8);
-    s->o_Ap = o; o += al256((size_t)nc * D * 8);
-    s->o_half = o; o += al256((size_t)nc * hop * 4);
-    const size_t state_end = o;
-    s->o_pcm = al256((size_t)nc * sizeof(LmJob));
-    const size_t in_cap = s->o_pcm + al256(s->max_units * hop * 4), out_cap = al256(s->max_units * hop * 4);
-    s->o_in = o; o += in_cap;
-    s->o_out = o; o += out_cap;
+    Layout lay;
+    s->o_win = lay.take((size_t)N * 4);
+    s->o_tw = lay.take((size_t)(hop + 1) * 8);
+    const size_t consts = lay.size();
+    s->o_lam = lay.take((size_t)nc * D * 8);
+    s->o_Ap = lay.take((size_t)nc * D * 8);
+    s->o_half = lay.take((size_t)nc * hop * 4);
+    const size_t state_end = lay.size();
+    Layout in;                                                   // a push's input block: n_chan jobs | samples
+    in.take((size_t)nc * sizeof(LmJob));
+    s->o_pcm = in.take(s->max_units * hop * 4);
+    const size_t in_cap = in.size(), out_cap = al256(s->max_units * hop * 4);
+    s->o_in = lay.take(in_cap);
+    s->o_out = lay.take(out_cap);
+    const size_t o = lay.size();
     hipError_t e = hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking);
     if (e != hipSuccess) { lmstream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_lmstream_open: ") + hipGetErrorString(e)); }
     e = s->blk.alloc(o, std::max(in_cap, consts), out_cap);
@@ -355,8 +359,9 @@ extern "C" int bp_lmstream_open(int device, int fea_dim, const bp_logmmse_params
         return fail(BP_ERR_NOMEM, std::string("bp_lmstream_open: ") + (e != hipSuccess ? hipGetErrorString(e) : "out of host memory"));
     }
     // constants, once: window and twiddles (computed in double and rounded once, as bp_logmmse_waves does)
-    memset(s->blk.pin_in, 0, consts);
-    wave_window_twiddles(log2M, (float *)(s->blk.pin_in + s->o_win), (float2 *)(s->blk.pin_in + s->o_tw));
+    char *pin = s->blk.pin_in.as<char>();
+    memset(pin, 0, consts);
+    wave_window_twiddles(log2M, (float *)(pin + s->o_win), (float2 *)(pin + s->o_tw));
     e = s->blk.upload_consts(consts, state_end, s->st);
     if (e != hipSuccess) { lmstream_release(s); return fail(BP_ERR_DEVICE, std::string("bp_lmstream_open: ") + hipGetErrorString(e)); }
     *out = s;
@@ -392,7 +397,7 @@ extern "C" int bp_lmstream_push(bp_lmstream *s, const int *n_in, const float *pc
     // ---- the input block: one job per channel with output frames | their [carry | new] samples at hop-aligned places (the pinned
     // block is reused by every push: the previous one ended in a synchronisation); with it the channels' new carry
     s->jobs.clear();
-    char *pin = s->blk.pin_in, *dev = s->blk.dev;
+    char *pin = s->blk.pin_in.as<char>(), *dev = s->blk.dev.as<char>();
     float *hp = (float *)(pin + s->o_pcm);
     size_t unit = 0, src = 0;
     int64_t out_base = 0;

@@ -243,15 +243,15 @@ struct TabLayout {
 TabLayout tab_layout(const EvalPlan &ep)
 {
     TabLayout t;
-    const size_t n = (size_t)ep.n, pb = al256((n + 1) * 4);
-    t.off = 0; t.len = al256(n * 8);
-    size_t o = t.len + al256(n * 4);
-    for (int k = 0; k < 12; ++k) { t.pre[k] = o; o += pb; }
-    t.h = o; o += al256((size_t)ep.taps * 4);
-    t.v = o; o += al256((size_t)EV_NFFT * 4);
-    t.tw = o; o += al256((size_t)(EV_NFFT / 2 + 1) * 8);
-    t.w = o; o += al256((size_t)ep.win * 8);
-    t.bytes = o;
+    const size_t n = (size_t)ep.n;
+    Layout lay;
+    t.off = lay.take(n * 8); t.len = lay.take(n * 4);
+    for (int k = 0; k < 12; ++k) t.pre[k] = lay.take((n + 1) * 4);
+    t.h = lay.take((size_t)ep.taps * 4);
+    t.v = lay.take((size_t)EV_NFFT * 4);
+    t.tw = lay.take((size_t)(EV_NFFT / 2 + 1) * 8);
+    t.w = lay.take((size_t)ep.win * 8);
+    t.bytes = lay.size();
     return t;
 }
 const std::vector<int> &pre_k(const EvalPlan &ep, int k)
@@ -275,17 +275,17 @@ WorkLayout work_layout(const EvalPlan &ep, int nsig)
     const int n = ep.n, ne = nsig - 1;
     w.s10 = ((size_t)ep.o10[n] + 3) & ~(size_t)3; w.scomp = (size_t)ep.Q[n];
     w.sband = (size_t)ep.P[n] * EV_BS; w.srho = (size_t)ep.CP[n]; w.sssnr = (size_t)ep.SJ[n]; w.slsd = (size_t)ep.F[n];
-    size_t o = 0;
-    w.r10 = o; o += al256(nsig * w.s10 * 4);
-    w.E = o; o += al256((size_t)ep.P[n] * 8);
-    w.frm = o; o += al256((size_t)ep.P[n] * 4);
-    w.C = o; o += al256((size_t)n * 4);
-    w.comp = o; o += al256(nsig * w.scomp * 4);
-    w.band = o; o += al256(nsig * w.sband * 4);
-    w.rho = o; o += al256(ne * w.srho * 8);
-    w.ssnr = o; o += al256(ne * w.sssnr * 8);
-    w.lsd = o; o += al256(ne * w.slsd * 8);
-    w.bytes = o;
+    Layout lay;
+    w.r10 = lay.take(nsig * w.s10 * 4);
+    w.E = lay.take((size_t)ep.P[n] * 8);
+    w.frm = lay.take((size_t)ep.P[n] * 4);
+    w.C = lay.take((size_t)n * 4);
+    w.comp = lay.take(nsig * w.scomp * 4);
+    w.band = lay.take(nsig * w.sband * 4);
+    w.rho = lay.take(ne * w.srho * 8);
+    w.ssnr = lay.take(ne * w.sssnr * 8);
+    w.lsd = lay.take(ne * w.slsd * 8);
+    w.bytes = lay.size();
     return w;
 }
 
@@ -433,9 +433,12 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
     EvalPlan ep;
     { const int r = eval_plan(who, sample_rate, D, n_sent, sent_len, off.data(), wp.F.data(), ep); if (r != BP_OK) return r; }
     // one host->device block: tables | analysis window | twiddles | padded reference | padded estimate
-    const size_t o_win = al256(ep.t_bytes), o_tw = o_win + al256((size_t)wp.N * 4), o_ref = o_tw + al256((size_t)(wp.M + 1) * 8);
-    const size_t o_est = o_ref + al256(padded * 4), in_b = o_est + al256(padded * 4);
-    const size_t o_lps = in_b, lps_b = f * D * 4, o_sc = o_lps + 2 * al256(lps_b), o_work = o_sc + al256((size_t)n_sent * BP_SCORE_N * 4);
+    Layout lay(al256(ep.t_bytes));
+    const size_t o_win = lay.take((size_t)wp.N * 4), o_tw = lay.take((size_t)(wp.M + 1) * 8), o_ref = lay.take(padded * 4);
+    const size_t o_est = lay.take(padded * 4), in_b = lay.size();
+    // behind it: the two LPS blocks | scores | work block
+    const size_t lps_b = f * D * 4, o_lps = lay.take(lps_b), o_lps1 = lay.take(lps_b), o_sc = lay.take((size_t)n_sent * BP_SCORE_N * 4);
+    const size_t o_work = lay.size();
     OneShot os;
     { const int r = os.open(who, device, o_work + eval_work_bytes(ep, 2)); if (r != BP_OK) return r; }
     std::vector<char> hb(in_b, 0);
@@ -444,21 +447,21 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
     wave_scatter((float *)(hb.data() + o_ref), wp, sent_len, ref);
     wave_scatter((float *)(hb.data() + o_est), wp, sent_len, est);
     hipError_t &e = os.e;
-    char *d = os.d;
+    char *d = os.d.as<char>();
     if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
         a.pcm = (const float *)(d + (k ? o_est : o_ref)); a.win = (const float *)(d + o_win); a.tw = (const float2 *)(d + o_tw);
         a.F = (const int *)(d + tab_layout(ep).pre[10]);
         a.n_sent = n_sent; a.log2M = wp.log2M; a.D = D; a.hop = wp.hop; a.ctx = 1;
-        a.lps = (float *)(d + o_lps + k * al256(lps_b));
+        a.lps = (float *)(d + (k ? o_lps1 : o_lps));
         e = wave_analysis_launch(a, (int)f, os.st);
     }
     if (e == hipSuccess) {
         EvalDev v; memset(&v, 0, sizeof(v));
         v.tab = d; v.work = d + o_work;
         v.sig[0] = (const float *)(d + o_ref); v.sig[1] = (const float *)(d + o_est);
-        v.lps[0] = (const float *)(d + o_lps); v.lps[1] = (const float *)(d + o_lps + al256(lps_b));
+        v.lps[0] = (const float *)(d + o_lps); v.lps[1] = (const float *)(d + o_lps1);
         v.scores = (float *)(d + o_sc);
         e = eval_launch(ep, v, 2, os.st);
     }

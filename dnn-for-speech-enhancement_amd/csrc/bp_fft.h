@@ -191,7 +191,8 @@ WaveIn wave_in_layout(const WavePlan &p, int D);
 void wave_in_fill(char *hb, const WaveIn &w, const WavePlan &p, int D, const float *mean, const float *inv_std, const int *sent_len,
                   const float *pcm);
 void wave_window_twiddles(int log2M, float *win, float2 *tw);     // win[2M], tw[M + 1], computed in double and rounded once
-int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st);   // grow-only device / pinned host buffer
+// the grow-only buffers of a signal-layer call, device or pinned host, used by what is queued on h->stream
+static inline int wave_grow(bp_handle *h, std::initializer_list<Grow> list) { return grow_all("signal-layer buffers: ", {h->stream}, list); }
 hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st);
 hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, int ctx, int toff, float *nat, hipStream_t st);
 // synthesis of `frames` frames from the net outputs out[frames][ldo] (columns [out_col, out_col + D)) and Y -> syn[frames][n_fft]

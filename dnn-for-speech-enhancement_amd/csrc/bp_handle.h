@@ -15,6 +15,8 @@
 //   (bp_fft.h: the device functions and the frame plan of the signal-layer units; bp_stream_core.h: counts, carry, push checks and
 //   the block owner of the two streaming engines)
 //   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
+//   (bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
+//   and fail / HIPCHK)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -31,20 +33,11 @@
 #include <vector>
 
 #include "../../include/bp_c_api.h"
+#include "bp_mem.h"
 
 typedef uint16_t bf16_t;
 
-extern thread_local std::string g_bp_err;
-static inline int fail(int code, const std::string &msg) { g_bp_err = msg; return code; }
-#define HIPCHK(x)                                                                                     \
-    do {                                                                                              \
-        hipError_t _e = (x);                                                                          \
-        if (_e != hipSuccess)                                                                         \
-            return fail(BP_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e));               \
-    } while (0)
-
 static inline int pad64(int x) { return (x + 63) & ~63; }
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }   // the parts of a device block start 256-byte aligned
 
 // Development switches (A/B aids of the measurements quoted in DESIGN.md): environment variables that only a library
 // built with -DBP_DEV (`make dev` -> libbp_hip_dev.so, loaded through BP_HIP_LIB) reads.  The shipped library has ONE
@@ -63,7 +56,10 @@ struct bp_handle {
     int s[BP_MAXLAYER], ld[BP_MAXLAYER];
     int B, Bg;                   // local / global bunch
     int cap, chunk_frames;
-    hipStream_t own_stream, stream;
+    // (the holders of a handle go with `delete h`, in reverse order of declaration: the two streams it owns are declared first
+    // and so go last, after everything that was used on them)
+    Stream own_stream, copy_stream;   // copy_stream: see "Upload path" below
+    hipStream_t stream;               // the launch stream (= own_stream)
     int wgrad_slots;             // workgroups of the persistent weight-gradient launch (4 per CU; BP_WGRAD_SLOTS at creation)
     // parameters and momentum state live in two flat arenas with the layout of the flat gradient buffer
     // ([W_1|b_1|W_2|b_2|...], padded; g_off/g_cnt) so that data-parallel ranks can export them as ONE hipIpc
@@ -79,24 +75,23 @@ struct bp_handle {
     float *slabs; size_t slab_stride; int out_splits;   // split-K workspace of the output layer
     unsigned *out_ticket;                               // ... and its ticket words (one per 32 x 32 output tile)
     float *grad; size_t grad_floats; size_t g_off[BP_MAXLAYER], g_cnt[BP_MAXLAYER];
-    float *host_out;             // pinned staging for CV outputs (grow-only, whole chunk)
-    float *out_chunk;            // device: network outputs of a whole chunk [frames][ld_L] (CV / forward), grow-only
-    size_t out_chunk_frames;
+    Buf host_out;                // pinned staging for CV outputs (grow-only, whole chunk)
+    Buf out_chunk;               // device: network outputs of a whole chunk [frames][ld_L] (CV / forward), grow-only
+    size_t out_chunk_frames;     // (both through out_chunk_reserve)
     uint32_t step;               // bunches trained so far (dropout stream position)
     uint32_t th_vis, th_hid;
     int fwd_mode;                     // bp_set_forward: the kernels of the inference forward (BP_FORWARD_DEFAULT | BP_FORWARD_ROWINV)
     float *inf_slab; unsigned *inf_ticket[BP_MAXLAYER];   // ROWINV: k-slice slabs (shared by the layers) and each layer's ticket words, or null
     int out_act, out_lin, out_loss;   // output layer (bp_set_output): 0 linear | 1 logistic on columns [out_lin, s_L), loss of those columns
-    hipEvent_t ev0, ev1; float last_ms; int last_bunches;
-    std::vector<void *> allocs;
+    Event ev0, ev1; float last_ms; int last_bunches;
+    std::vector<Buf> allocs;     // everything dev_alloc handed out: lives as long as the handle
     // Upload path: host->device copies run on copy_stream so that chunk i+1 is uploaded while chunk i trains.
     // STACKED chunks (bp_upload_chunk: the caller hands [frames][layersizes[0]] rows, the reference's interface) alternate
     // between two device buffer pairs (in/targ and in_alt/targ_alt; allocated on first use).
     // WINDOW chunks (bp_upload_chunk_windows: raw frames + index tables) stay as they are uploaded -- two
     // grow-only staging sets alternate the same way -- and every bunch stacks ITS rows into the tile x0s/tgs right
     // before its forward (bp_stage_bunch): no stacked chunk, no masked copy of it.
-    struct Raw { void *p; size_t bytes; };
-    struct WinSet { Raw r[4]; } wset[2];      // raw frames, raw target frames, NAT rows, tables (win_start | targ_frame | nat_row)
+    struct WinSet { Buf r[4]; } wset[2];      // raw frames, raw target frames, NAT rows, tables (win_start | targ_frame | nat_row)
     int wcur;                                 // staging set of the resident window chunk
     bool windows;                             // the resident chunk is a window chunk
     struct { const float *fea, *tg, *nat; const int *ws, *tf, *nr; int D, win; } wv;   // views of set wcur
@@ -106,10 +101,9 @@ struct bp_handle {
     int next_first;                           // chunk frame of the bunch that follows the one being enqueued (-1: none / not a window chunk)
     struct { bool valid; int first, tile; uint32_t step; unsigned gen; } pre;   // what the other tile holds
     unsigned wgen;                            // bumped by every window upload (a pre-staged tile of the old chunk is void)
-    hipStream_t copy_stream;
-    hipEvent_t ev_copy;            // copy_stream: this chunk's H2D copies are done
-    hipEvent_t ev_retired;         // main stream: the stacked buffer pair that is NOT current is no longer read
-    hipEvent_t ev_wretired;        // main stream: the window staging set that is NOT current is no longer read
+    Event ev_copy;                 // copy_stream: this chunk's H2D copies are done
+    Event ev_retired;              // main stream: the stacked buffer pair that is NOT current is no longer read
+    Event ev_wretired;             // main stream: the window staging set that is NOT current is no longer read
     bool retired_valid, wretired_valid;
     float *in_alt, *targ_alt;
     // compute_dtype == 1 (bp_bf16.h): bf16 copies, each in both orientations
@@ -121,7 +115,7 @@ struct bp_handle {
     float *bf_ks_slab; unsigned *bf_ks_cnt;                  // split-k output forward (bp_bf16.h, KS): partial tiles and ticket words, or null
     // bp_enhance_waves (bp_wave.hip), grow-only: device input block, noisy spectrum, synthesis frames, padded output samples;
     // pinned host staging of the input block and of the output samples
-    Raw wave[4], wave_pin[2];
+    Buf wave[4], wave_pin[2];
     // bp_set_mix_corpus (bp_mix.hip): the resident corpus and the grow-only buffers of the mixing calls, or null
     struct MixState *mix;
     // bp_stream_open (bp_stream.hip): the open streaming sessions of this handle
@@ -145,7 +139,7 @@ int dev_alloc(bp_handle *h, float **p, size_t n_floats);
 // bp_profile_step: one HIP event after every launch of the step on the launch stream; the duration attributed to a
 // launch is the time between the previous event and its own (= kernel + the dependent-launch boundary in front of it).
 struct StepProf {
-    std::vector<hipEvent_t> ev; std::vector<int> kind; size_t used;
+    std::vector<Event> ev; std::vector<int> kind; size_t used;
 };
 
 // ------------------------------------------------------------------ calls without a handle
@@ -162,15 +156,14 @@ static inline int use_device(const char *who, int device)
 // block, both freed when the holder goes.  e is sticky: the call chains its copies and launches with `if (e == hipSuccess) e = ...`,
 // finish() synchronises and turns the first error into BP_ERR_DEVICE "<who>: <hip error string>".
 struct OneShot {
-    hipStream_t st = nullptr;
-    char *d = nullptr;
+    Stream st;
+    Buf d;
     hipError_t e = hipSuccess;
-    ~OneShot() { if (d) (void)hipFree(d); if (st) (void)hipStreamDestroy(st); }
     int open(const char *who, int device, size_t bytes)
     {
         { const int r = use_device(who, device); if (r != BP_OK) return r; }
-        e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc((void **)&d, bytes);
+        e = st.create(hipStreamNonBlocking);
+        if (e == hipSuccess) e = d.alloc(bytes);
         return BP_OK;
     }
     int finish(const char *who)

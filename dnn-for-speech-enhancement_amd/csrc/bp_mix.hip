@@ -370,40 +370,18 @@ struct MixState {
     float thr;
     int n_clean, n_noise, n_pair;                                // n_pair: derived entries n_clean .. n_clean + n_pair - 1
     std::vector<int64_t> clean_len, noise_len;                   // clean_len: [n_clean + n_pair]
-    char *reverb;                                                // device: r | e (early target only) | ReverbJob [n_pair]
+    Buf reverb;                                                  // device: r | e (early target only) | ReverbJob [n_pair]
     size_t o_rv_t, o_rv_job;
-    char *corpus;                                                // device: clean | noise | offsets and lengths | mean | inv_std | window | twiddles
+    Buf corpus;                                                  // device: clean | noise | offsets and lengths | mean | inv_std | window | twiddles
     size_t o_clean, o_noise, o_cl_off, o_cl_len, o_no_off, o_no_len, o_mean, o_istd, o_win, o_tw;
-    bp_handle::Raw in_d, x, s, v, gain, lps;                     // grow-only device buffers of the calls
-    bp_handle::Raw in_pin[2]; hipEvent_t ev_in[2]; bool ev_valid[2]; int pin_cur;   // pinned input blocks, alternating
-    bp_handle::Raw ev_Y, ev_syn, ev_ola, ev_lps, ev_tab, ev_work, ev_pin;             // bp_eval_mix (ev_pin: pinned table block)
-    bp_handle::Raw ev_gain;                                      // bp_eval_mix_logmmse: gain rows [frames][D] | vad [frames]
+    Buf in_d, x, s, v, gain, lps;                                // grow-only device buffers of the calls
+    Buf in_pin[2]; Event ev_in[2]; bool ev_valid[2]; int pin_cur;   // pinned input blocks, alternating
+    Buf ev_Y, ev_syn, ev_ola, ev_lps, ev_tab, ev_work, ev_pin;   // bp_eval_mix (ev_pin: pinned table block)
+    Buf ev_gain;                                                 // bp_eval_mix_logmmse: gain rows [frames][D] | vad [frames]
 };
 
 namespace {
 
-
-void free_raw(bp_handle::Raw &r, bool pinned)
-{
-    if (r.p) (void)(pinned ? hipHostFree(r.p) : hipFree(r.p));
-    r.p = nullptr; r.bytes = 0;
-}
-
-void free_state(MixState *ms)
-{
-    if (!ms) return;
-    if (ms->corpus) (void)hipFree(ms->corpus);
-    if (ms->reverb) (void)hipFree(ms->reverb);
-    for (bp_handle::Raw *r : {&ms->in_d, &ms->x, &ms->s, &ms->v, &ms->gain, &ms->lps, &ms->ev_Y, &ms->ev_syn, &ms->ev_ola, &ms->ev_lps,
-                              &ms->ev_tab, &ms->ev_work, &ms->ev_gain})
-        free_raw(*r, false);
-    free_raw(ms->ev_pin, true);
-    for (int k = 0; k < 2; ++k) {
-        if (ms->ev_in[k]) { (void)hipEventSynchronize(ms->ev_in[k]); (void)hipEventDestroy(ms->ev_in[k]); }
-        free_raw(ms->in_pin[k], true);
-    }
-    delete ms;
-}
 
 int parts_of(int target) { return target == BP_MIX_LPS_IRM || target == BP_MIX_LPS_IBM ? 2 : 1; }
 
@@ -440,9 +418,10 @@ int plan_call(const bp_handle *h, const char *who, int n_mix, const bp_mixture *
     if (c.rows > (size_t)h->cap)
         return fail(BP_ERR_ARG, std::string(who) + ": frames + n_mix*(context-1) exceed the chunk capacity " + std::to_string(h->cap));
     c.segs = (size_t)c.Fs[n_mix];
-    c.o_F = 0; c.o_Fs = al256(((size_t)n_mix + 1) * 4); c.o_c = c.o_Fs + al256(((size_t)n_mix + 1) * 4);
-    c.o_n = c.o_c + al256((size_t)n_mix * 4); c.o_o = c.o_n + al256((size_t)n_mix * 4); c.o_snr = c.o_o + al256((size_t)n_mix * 8);
-    c.o_order = c.o_snr + al256((size_t)n_mix * 4); c.bytes = c.o_order + al256(c.frames * 4);
+    Layout lay;
+    c.o_F = lay.take(((size_t)n_mix + 1) * 4); c.o_Fs = lay.take(((size_t)n_mix + 1) * 4);
+    c.o_c = lay.take((size_t)n_mix * 4); c.o_n = lay.take((size_t)n_mix * 4); c.o_o = lay.take((size_t)n_mix * 8);
+    c.o_snr = lay.take((size_t)n_mix * 4); c.o_order = lay.take(c.frames * 4); c.bytes = lay.size();
     return BP_OK;
 }
 
@@ -467,12 +446,9 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     HIPCHK(hipSetDevice(h->cfg.device));
     const int D = ms->D, n = (int)c.frames;
     const size_t pcm_b = c.segs * ms->hop * 4;
-    int r;
-    if ((r = wave_grow(ms->in_d, c.bytes, false, h->stream)) != BP_OK || (r = wave_grow(ms->x, pcm_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->s, pcm_b, false, h->stream)) != BP_OK || (r = wave_grow(ms->v, pcm_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->gain, (size_t)c.n * 4, false, h->stream)) != BP_OK ||
-        (lps_out && (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK))
-        return r;
+    int r = wave_grow(h, {{ms->in_d, c.bytes, false}, {ms->x, pcm_b, false}, {ms->s, pcm_b, false}, {ms->v, pcm_b, false},
+                          {ms->gain, (size_t)c.n * 4, false}, {ms->lps, lps_out ? c.frames * D * 4 : 0, false}});
+    if (r != BP_OK) return r;
     float *rows_d, *targ_d, *nat_d; int *tab;
     targ_d = nullptr;
     if ((r = window_reserve(h, c.rows * D * 4, targets ? c.frames * ms->sL * 4 : 0, ms->nat ? (size_t)c.n * D * 4 : 0, c.frames, &rows_d,
@@ -482,7 +458,7 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     const int k = ms->pin_cur;
     ms->pin_cur ^= 1;
     if (ms->ev_valid[k]) HIPCHK(hipEventSynchronize(ms->ev_in[k]));
-    if ((r = wave_grow(ms->in_pin[k], c.bytes, true, h->stream)) != BP_OK) return r;
+    if ((r = wave_grow(h, {{ms->in_pin[k], c.bytes, true}})) != BP_OK) return r;
     char *hb = (char *)ms->in_pin[k].p, *db = (char *)ms->in_d.p;
     memcpy(hb + c.o_F, c.F.data(), c.F.size() * 4);
     memcpy(hb + c.o_Fs, c.Fs.data(), c.Fs.size() * 4);
@@ -496,7 +472,7 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     HIPCHK(hipEventRecord(ms->ev_in[k], h->stream));
     ms->ev_valid[k] = true;
 
-    const char *cp = ms->corpus;
+    const char *cp = ms->corpus.as<char>();
     const float *win = (const float *)(cp + ms->o_win);
     const float2 *tw = (const float2 *)(cp + ms->o_tw);
     const int *F = (const int *)(db + c.o_F);
@@ -506,8 +482,9 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     a.noise_off = (const int64_t *)(cp + ms->o_no_off); a.noise_len = (const int64_t *)(cp + ms->o_no_len);
     a.n_clean = ms->n_clean;
     if (ms->n_pair) {
-        a.rev = (const float *)ms->reverb; a.rev_t = (const float *)(ms->reverb + ms->o_rv_t);
-        a.rjob = (const ReverbJob *)(ms->reverb + ms->o_rv_job);
+        const char *rv = ms->reverb.as<char>();
+        a.rev = (const float *)rv; a.rev_t = (const float *)(rv + ms->o_rv_t);
+        a.rjob = (const ReverbJob *)(rv + ms->o_rv_job);
     }
     a.Fs = (const int *)(db + c.o_Fs); a.mc = (const int *)(db + c.o_c); a.mn = (const int *)(db + c.o_n);
     a.mo = (const int64_t *)(db + c.o_o); a.msnr = (const float *)(db + c.o_snr);
@@ -568,7 +545,9 @@ uint64_t scale(uint32_t u, uint64_t n) { return ((uint64_t)u * n) >> 32; }
 
 void mix_free(bp_handle *h)
 {
-    free_state(h->mix);
+    if (h->mix)
+        for (Event &e : h->mix->ev_in) if (e) (void)hipEventSynchronize(e);   // (the copy out of a pinned input block may still run)
+    delete h->mix;
     h->mix = nullptr;
 }
 
@@ -610,16 +589,17 @@ extern "C" int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c)
     ms->n_clean = c->n_clean; ms->n_noise = c->n_noise;
     ms->clean_len.assign(c->clean_len, c->clean_len + c->n_clean);
     ms->noise_len.assign(c->noise_len, c->noise_len + c->n_noise);
-    ms->o_clean = 0; ms->o_noise = al256(nc * 4); ms->o_cl_off = ms->o_noise + al256(nn * 4);
-    ms->o_cl_len = ms->o_cl_off + al256((size_t)c->n_clean * 8); ms->o_no_off = ms->o_cl_len + al256((size_t)c->n_clean * 8);
-    ms->o_no_len = ms->o_no_off + al256((size_t)c->n_noise * 8); ms->o_mean = ms->o_no_len + al256((size_t)c->n_noise * 8);
-    ms->o_istd = ms->o_mean + al256((size_t)D * 4); ms->o_win = ms->o_istd + al256((size_t)D * 4);
-    ms->o_tw = ms->o_win + al256((size_t)2 * ms->M * 4);
-    const size_t bytes = ms->o_tw + al256((size_t)(ms->M + 1) * 8);
+    Layout lay;
+    ms->o_clean = lay.take(nc * 4); ms->o_noise = lay.take(nn * 4);
+    ms->o_cl_off = lay.take((size_t)c->n_clean * 8); ms->o_cl_len = lay.take((size_t)c->n_clean * 8);
+    ms->o_no_off = lay.take((size_t)c->n_noise * 8); ms->o_no_len = lay.take((size_t)c->n_noise * 8);
+    ms->o_mean = lay.take((size_t)D * 4); ms->o_istd = lay.take((size_t)D * 4);
+    ms->o_win = lay.take((size_t)2 * ms->M * 4); ms->o_tw = lay.take((size_t)(ms->M + 1) * 8);
+    const size_t bytes = lay.size();
     h->mix = ms;
-    if (hipMalloc((void **)&ms->corpus, bytes) != hipSuccess) { mix_free(h); return fail(BP_ERR_NOMEM, "bp_set_mix_corpus: hipMalloc (corpus)"); }
+    if (ms->corpus.alloc(bytes) != hipSuccess) { mix_free(h); return fail(BP_ERR_NOMEM, "bp_set_mix_corpus: hipMalloc (corpus)"); }
     for (int k = 0; k < 2; ++k)
-        if (hipEventCreateWithFlags(&ms->ev_in[k], hipEventDisableTiming) != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, "bp_set_mix_corpus: event"); }
+        if (ms->ev_in[k].create(hipEventDisableTiming) != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, "bp_set_mix_corpus: event"); }
     std::vector<char> small(bytes - ms->o_cl_off);
     char *sb = small.data() - ms->o_cl_off;                      // (indexed with the block's offsets)
     std::vector<int64_t> off(c->n_clean, 0);
@@ -633,9 +613,10 @@ extern "C" int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c)
     memcpy(sb + ms->o_mean, c->mean, (size_t)D * 4);
     memcpy(sb + ms->o_istd, c->inv_std, (size_t)D * 4);
     wave_window_twiddles(log2M, (float *)(sb + ms->o_win), (float2 *)(sb + ms->o_tw));
-    hipError_t e = hipMemcpy(ms->corpus + ms->o_clean, c->clean_pcm, nc * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ms->corpus + ms->o_noise, c->noise_pcm, nn * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ms->corpus + ms->o_cl_off, small.data(), small.size(), hipMemcpyHostToDevice);
+    char *cp = ms->corpus.as<char>();
+    hipError_t e = hipMemcpy(cp + ms->o_clean, c->clean_pcm, nc * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(cp + ms->o_noise, c->noise_pcm, nn * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(cp + ms->o_cl_off, small.data(), small.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, std::string("bp_set_mix_corpus: ") + hipGetErrorString(e)); }
     return BP_OK;
 }
@@ -667,14 +648,15 @@ extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq
     if ((r = window_adopt(h, n, h->mix->D, h->mix->ctx, h->mix->nat, false)) != BP_OK) return r;
     if ((r = forward_resident_as(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV: the step's kernels in either mode)
     std::vector<float> tg((size_t)n * sL);
-    HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * ldL * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * ldL * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(tg.data(), targ_d, tg.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    const float *host_out = h->host_out.as<float>();
     float squared_err = 0.0f;
     for (int j = 0; j < n; ++j) {                                // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
         const float *t = tg.data() + (size_t)j * sL;
         for (int d = 0; d < sL; ++d) {
-            const float e = h->host_out[(size_t)j * ldL + d] - t[d];
+            const float e = host_out[(size_t)j * ldL + d] - t[d];
             squared_err = squared_err + e * e;
         }
     }
@@ -732,13 +714,11 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     HIPCHK(hipSetDevice(h->cfg.device));
     // every buffer first (a growth waits for the stream), then the sequence without a host wait
     const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * BP_SCORE_N * 4;
-    if ((r = wave_grow(ms->ev_Y, c.frames * D * sizeof(float2), false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->ev_syn, c.frames * 2 * hop * 4, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_ola, pcm_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->ev_lps, 2 * lps_b, false, h->stream)) != BP_OK || (r = wave_grow(ms->ev_tab, ep.t_bytes + sc_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->ev_work, eval_work_bytes(ep, 3), false, h->stream)) != BP_OK ||
-        (r = wave_grow(ms->ev_pin, ep.t_bytes, true, h->stream)) != BP_OK || (r = wave_grow(ms->lps, c.frames * D * 4, false, h->stream)) != BP_OK ||
-        (lm && (r = wave_grow(ms->ev_gain, c.frames * ((size_t)D + 1) * 4, false, h->stream)) != BP_OK))
-        return r;
+    r = wave_grow(h, {{ms->ev_Y, c.frames * D * sizeof(float2), false}, {ms->ev_syn, c.frames * 2 * hop * 4, false}, {ms->ev_ola, pcm_b, false},
+                      {ms->ev_lps, 2 * lps_b, false}, {ms->ev_tab, ep.t_bytes + sc_b, false}, {ms->ev_work, eval_work_bytes(ep, 3), false},
+                      {ms->ev_pin, ep.t_bytes, true}, {ms->lps, c.frames * D * 4, false},
+                      {ms->ev_gain, lm ? c.frames * ((size_t)D + 1) * 4 : 0, false}});
+    if (r != BP_OK) return r;
     if (!lm && (r = out_chunk_reserve(h, n)) != BP_OK) return r;
     // the table block: the pinned buffer is free (the previous call ended in a synchronisation)
     char *tab = (char *)ms->ev_tab.p;
@@ -748,7 +728,7 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     if ((r = generate(h, c, m, nullptr, true, nullptr, nullptr, nullptr, Y, false)) != BP_OK) return r;
     if ((r = window_adopt(h, n, D, ms->ctx, ms->nat, false)) != BP_OK) return r;
     if (!lm && (r = forward_resident(h, n)) != BP_OK) return r;
-    const char *cp = ms->corpus;
+    const char *cp = ms->corpus.as<char>();
     const float *win = (const float *)(cp + ms->o_win);
     const float2 *tw = (const float2 *)(cp + ms->o_tw);
     const int *F = (const int *)((const char *)ms->in_d.p + c.o_F);
@@ -758,7 +738,7 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
         HIPCHK(logmmse_gain_launch(*lm, Y, F, n_mix, D, gain, gain + c.frames * D, h->stream));
         HIPCHK(wave_synthesis_launch(gain, D, 0, Y, win, tw, ms->log2M, D, BP_WAVE_MASK, (float *)ms->ev_syn.p, n, h->stream));
     } else
-        HIPCHK(wave_synthesis_launch(h->out_chunk, h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
+        HIPCHK(wave_synthesis_launch(h->out_chunk.as<float>(), h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
     HIPCHK(wave_overlap_launch((const float *)ms->ev_syn.p, win, F, n_mix, hop, ola, n, h->stream));
     HIPCHK(eval_trim_launch(ep, tab, hop, ola, h->stream));        // = the enhanced sentences in bp_score_waves' padded layout
     for (int k = 0; k < 2; ++k) {                                  // the LPS of s and of the enhanced samples (x's: generate)
@@ -958,30 +938,31 @@ extern "C" int bp_set_mix_reverb(bp_handle *h, const bp_mix_reverb *r)
     const bool early = r->target == BP_REVERB_TARGET_EARLY;
     const int64_t blocks = fill_jobs(job, off, delay, r->rir_len, r->early_taps);
     if (blocks > INT32_MAX) return fail(BP_ERR_ARG, "bp_set_mix_reverb: too many samples for one call");
-    const size_t sig_b = al256((size_t)tot * 4), o_t = early ? sig_b : 0, o_job = sig_b * (early ? 2 : 1);
-    const size_t bytes = o_job + al256(job.size() * sizeof(ReverbJob)), rir_b = (size_t)off[r->n_rir] * 4;
+    Layout lay;                                                  // r | e (early target only) | jobs
+    lay.take((size_t)tot * 4);
+    const size_t o_t = early ? lay.take((size_t)tot * 4) : 0, o_job = lay.take(job.size() * sizeof(ReverbJob));
+    const size_t bytes = lay.size(), rir_b = (size_t)off[r->n_rir] * 4;
     HIPCHK(hipSetDevice(h->cfg.device));
-    char *nd = nullptr, *hd = nullptr;
-    if (hipMalloc((void **)&nd, bytes) != hipSuccess || hipMalloc((void **)&hd, rir_b) != hipSuccess) {
+    Buf nb, hb;                                                  // the new entries; the responses (for this call only)
+    if (nb.alloc(bytes) != hipSuccess || hb.alloc(rir_b) != hipSuccess) {
         (void)hipGetLastError();
-        if (nd) (void)hipFree(nd);
         return fail(BP_ERR_NOMEM, "bp_set_mix_reverb: hipMalloc (the previous entries stay)");
     }
+    char *nd = nb.as<char>(), *hd = hb.as<char>();
     hipError_t e = hipMemcpyAsync(nd + o_job, job.data(), job.size() * sizeof(ReverbJob), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hd, r->rir_pcm, rir_b, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
         ReverbArgs a; memset(&a, 0, sizeof(a));
         a.job = (const ReverbJob *)(nd + o_job); a.n_job = r->n_pair;
-        a.src = (const float *)(ms->corpus + ms->o_clean); a.rir = (const float *)hd;
+        a.src = (const float *)(ms->corpus.as<char>() + ms->o_clean); a.rir = (const float *)hd;
         a.out_r = (float *)nd; a.out_e = early ? (float *)(nd + o_t) : nullptr;
         e = reverb_launch(a, blocks, early, h->stream);
     }
     const hipError_t e2 = hipStreamSynchronize(h->stream);       // (the host arrays are the caller's; earlier calls may read the old entries)
     if (e == hipSuccess) e = e2;
-    (void)hipFree(hd);
-    if (e != hipSuccess) { (void)hipFree(nd); return fail(BP_ERR_DEVICE, std::string("bp_set_mix_reverb: ") + hipGetErrorString(e)); }
-    if (ms->reverb) (void)hipFree(ms->reverb);
-    ms->reverb = nd; ms->o_rv_t = o_t; ms->o_rv_job = o_job; ms->n_pair = r->n_pair;
+    if (e != hipSuccess) return fail(BP_ERR_DEVICE, std::string("bp_set_mix_reverb: ") + hipGetErrorString(e));
+    ms->reverb = std::move(nb);                                  // (the previous entries go)
+    ms->o_rv_t = o_t; ms->o_rv_job = o_job; ms->n_pair = r->n_pair;
     ms->clean_len.resize(ms->n_clean);
     for (const ReverbJob &j : job) ms->clean_len.push_back(j.n);
     return BP_OK;
@@ -1008,8 +989,10 @@ extern "C" int bp_reverb_waves(int device, int n_sent, const int *sent_len, cons
     if (blocks > INT32_MAX) return fail(BP_ERR_ARG, "bp_reverb_waves: too many samples for one call");
     // one input block: jobs | sentences | responses; one output block: r | e (whichever are asked for)
     const bool early = out_early != nullptr;
-    const size_t o_pcm = al256(job.size() * sizeof(ReverbJob)), o_rir = o_pcm + al256((size_t)tot * 4);
-    const size_t in_b = o_rir + al256((size_t)off[n_rir] * 4), sig_b = (size_t)tot * 4, out_b = sig_b * ((out_rev ? 1 : 0) + (early ? 1 : 0));
+    Layout lay;
+    lay.take(job.size() * sizeof(ReverbJob));
+    const size_t o_pcm = lay.take((size_t)tot * 4), o_rir = lay.take((size_t)off[n_rir] * 4);
+    const size_t in_b = lay.size(), sig_b = (size_t)tot * 4, out_b = sig_b * ((out_rev ? 1 : 0) + (early ? 1 : 0));
     OneShot os;
     if ((rc = os.open("bp_reverb_waves", device, in_b + out_b)) != BP_OK) return rc;
     std::vector<char> hb(in_b), ho(out_rev && early ? out_b : 0);
@@ -1017,7 +1000,7 @@ extern "C" int bp_reverb_waves(int device, int n_sent, const int *sent_len, cons
     memcpy(hb.data() + o_pcm, pcm, sig_b);
     memcpy(hb.data() + o_rir, rir_pcm, (size_t)off[n_rir] * 4);
     hipError_t &e = os.e;
-    char *d = os.d;
+    char *d = os.d.as<char>();
     if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
     if (e == hipSuccess) {
         ReverbArgs a; memset(&a, 0, sizeof(a));
@@ -1172,7 +1155,9 @@ extern "C" int bp_rir_image(int device, int sample_rate, int window_taps, int n_
     }
     if (blk > INT32_MAX) return fail(BP_ERR_ARG, "bp_rir_image: too many taps for one call");
     // one input block: jobs | tables; one output block: the taps
-    const size_t o_tab = al256(job.size() * sizeof(RirJob)), in_b = o_tab + al256((size_t)tab * 8), out_b = (size_t)taps * 4;
+    Layout lay;
+    lay.take(job.size() * sizeof(RirJob));
+    const size_t o_tab = lay.take((size_t)tab * 8), in_b = lay.size(), out_b = (size_t)taps * 4;
     std::vector<char> hb(in_b);
     memcpy(hb.data(), job.data(), job.size() * sizeof(RirJob));
     for (int k = 0; k < n_rir; ++k) {
@@ -1182,7 +1167,7 @@ extern "C" int bp_rir_image(int device, int sample_rate, int window_taps, int n_
     OneShot os;
     if ((rc = os.open("bp_rir_image", device, in_b + out_b)) != BP_OK) return rc;
     hipError_t &e = os.e;
-    char *d = os.d;
+    char *d = os.d.as<char>();
     if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
     if (e == hipSuccess) {
         RirArgs a; memset(&a, 0, sizeof(a));

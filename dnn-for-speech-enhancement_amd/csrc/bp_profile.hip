@@ -33,7 +33,6 @@ extern "C" int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, flo
         er = hipEventElapsedTime(&ms, prof.ev[k - 1], prof.ev[k]);
         if (prof.kind[k] >= 0 && prof.kind[k] < BP_PROF_KINDS) { sum[prof.kind[k]] += ms; cnt[prof.kind[k]]++; }
     }
-    for (hipEvent_t e : prof.ev) (void)hipEventDestroy(e);
     if (er != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_profile_step: ") + hipGetErrorString(er));
     for (int k = 0; k < BP_PROF_KINDS; ++k) {
         avg_ms[k] = cnt[k] ? (float)(sum[k] / (double)cnt[k]) : 0.f;
@@ -77,10 +76,11 @@ extern "C" int bp_measure_peaks(bp_handle *h, float *mfma_f32_tflops, float *hbm
 {
     if (!h || !mfma_f32_tflops || !hbm_copy_gbs) return fail(BP_ERR_ARG, "bp_measure_peaks: null argument");
     HIPCHK(hipSetDevice(h->cfg.device));
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-    float *sink = nullptr;
-    HIPCHK(hipMalloc((void **)&sink, 4096));
+    Event a, b;                                                  // (holders: every HIPCHK exit below releases what it holds)
+    HIPCHK(a.create()); HIPCHK(b.create());
+    Buf sink_b, src_b, dst_b;
+    HIPCHK(sink_b.alloc(4096));
+    float *sink = sink_b.as<float>();
     const int iters = 4096, wgs = 256 * 8;
     float ms = 0.f, best = 0.f;
     for (int rep = 0; rep < 4; ++rep) {
@@ -93,10 +93,10 @@ extern "C" int bp_measure_peaks(bp_handle *h, float *mfma_f32_tflops, float *hbm
         if (rep > 0 && tf > best) best = tf;
     }
     *mfma_f32_tflops = best;
-    (void)hipFree(sink);
+    sink_b.release();
     const size_t bytes = (size_t)1 << 30;
-    float4 *src = nullptr, *dst = nullptr;
-    HIPCHK(hipMalloc((void **)&src, bytes)); HIPCHK(hipMalloc((void **)&dst, bytes));
+    HIPCHK(src_b.alloc(bytes)); HIPCHK(dst_b.alloc(bytes));
+    float4 *src = src_b.as<float4>(), *dst = dst_b.as<float4>();
     HIPCHK(hipMemsetAsync(src, 1, bytes, h->stream));
     best = 0.f;
     for (int rep = 0; rep < 6; ++rep) {
@@ -110,8 +110,6 @@ extern "C" int bp_measure_peaks(bp_handle *h, float *mfma_f32_tflops, float *hbm
         if (rep > 0 && gbs > best) best = gbs;
     }
     *hbm_copy_gbs = best;
-    (void)hipFree(src); (void)hipFree(dst);
-    HIPCHK(hipEventDestroy(a)); HIPCHK(hipEventDestroy(b));
     return BP_OK;
 }
 
@@ -125,9 +123,10 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
     if (h->chunk_frames < h->B || h->windows) return fail(BP_ERR_STATE, "bp_time_kernel: no resident stacked chunk");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L, B = h->B;
-    hipEvent_t a, b;
+    Event a, b;
+    Buf sw, sd, sb;                                              // scratch copies of W, delta and bias | bias delta (which 2, 5)
     float *scratch_w = nullptr, *scratch_d = nullptr, *scratch_b = nullptr;
-    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+    HIPCHK(a.create()); HIPCHK(b.create());
     for (int it = -2; it < iters; ++it) {
         if (it == 0) HIPCHK(hipEventRecord(a, h->stream));
         hipError_t er = hipSuccess;
@@ -139,8 +138,9 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
             const int l = which == 2 ? 2 : 1;
             const size_t nw = (size_t)h->ld[l - 1] * h->ld[l];
             if (!scratch_w) {
-                HIPCHK(hipMalloc((void **)&scratch_w, nw * 4)); HIPCHK(hipMalloc((void **)&scratch_d, nw * 4));
-                HIPCHK(hipMalloc((void **)&scratch_b, (size_t)h->ld[l] * 8));
+                HIPCHK(sw.alloc(nw * 4)); HIPCHK(sd.alloc(nw * 4));
+                HIPCHK(sb.alloc((size_t)h->ld[l] * 8));
+                scratch_w = sw.as<float>(); scratch_d = sd.as<float>(); scratch_b = sb.as<float>();
                 HIPCHK(hipMemcpyAsync(scratch_w, h->W[l], nw * 4, hipMemcpyDeviceToDevice, h->stream));
                 HIPCHK(hipMemsetAsync(scratch_d, 0, nw * 4, h->stream));
                 HIPCHK(hipMemsetAsync(scratch_b, 0, (size_t)h->ld[l] * 8, h->stream));
@@ -153,8 +153,7 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
         }
         case 3: er = launch_fwd(h, 1, B, h->in, nullptr, nullptr, true, 1.0f); break;
         case 4: er = launch_fwd(h, L - 1, B, h->y[L - 2], h->targ, nullptr, true, 1.0f); break;
-        default: HIPCHK(hipEventDestroy(a)); HIPCHK(hipEventDestroy(b));
-                 return fail(BP_ERR_ARG, "bp_time_kernel: unknown kernel id");
+        default: return fail(BP_ERR_ARG, "bp_time_kernel: unknown kernel id");
         }
         HIPCHK(er);
     }
@@ -163,7 +162,5 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     *avg_ms = ms / iters;
-    if (scratch_w) { (void)hipFree(scratch_w); (void)hipFree(scratch_d); (void)hipFree(scratch_b); }
-    HIPCHK(hipEventDestroy(a)); HIPCHK(hipEventDestroy(b));
     return BP_OK;
 }

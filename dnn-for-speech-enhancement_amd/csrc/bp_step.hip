@@ -25,9 +25,9 @@ hipError_t prof_mark(bp_handle *h, int kind)
     StepProf *p = h->prof;
     if (!p) return hipSuccess;
     if (p->used == p->ev.size()) {
-        hipEvent_t e; hipError_t er = hipEventCreate(&e);
+        Event e; hipError_t er = e.create();
         if (er != hipSuccess) return er;
-        p->ev.push_back(e); p->kind.push_back(kind);
+        p->ev.push_back(std::move(e)); p->kind.push_back(kind);
     }
     p->kind[p->used] = kind;
     return hipEventRecord(p->ev[p->used++], h->stream);
@@ -54,13 +54,13 @@ extern "C" int bp_device_count(int *n)
 int dev_alloc(bp_handle *h, float **p, size_t n_floats)
 {
     n_floats += SLACK;
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n_floats * sizeof(float));
+    Buf q;
+    hipError_t e = q.alloc(n_floats * sizeof(float));
     if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    e = hipMemsetAsync(q, 0, n_floats * sizeof(float), h->stream);
+    e = hipMemsetAsync(q.p, 0, n_floats * sizeof(float), h->stream);
     if (e != hipSuccess) return fail(BP_ERR_DEVICE, std::string("hipMemset: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (float *)q;
+    *p = q.as<float>();
+    h->allocs.push_back(std::move(q));
     return BP_OK;
 }
 
@@ -71,22 +71,10 @@ extern "C" int bp_destroy(bp_handle *h)
     (void)hipSetDevice(h->cfg.device);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     if (h->dp) (void)bp_dp_detach(h);
-    for (void *p : h->allocs) (void)hipFree(p);
-    for (auto &ws : h->wset) for (auto &r : ws.r) if (r.p) (void)hipFree(r.p);
-    for (auto &r : h->wave) if (r.p) (void)hipFree(r.p);
-    for (auto &r : h->wave_pin) if (r.p) (void)hipHostFree(r.p);
     mix_free(h);
     stream_free_all(h);
-    if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-    if (h->ev_copy) (void)hipEventDestroy(h->ev_copy);
-    if (h->ev_retired) (void)hipEventDestroy(h->ev_retired);
-    if (h->ev_wretired) (void)hipEventDestroy(h->ev_wretired);
-    if (h->host_out) (void)hipHostFree(h->host_out);
-    if (h->out_chunk) (void)hipFree(h->out_chunk);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+    delete h;                    // the holders: buffers and events first, the two streams last (bp_handle.h); the device is current
     return BP_OK;
 }
 
@@ -132,19 +120,10 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
     h->Bg = cfg->global_bunchsize > 0 ? cfg->global_bunchsize : cfg->bunchsize;
     h->cap = cfg->max_chunk_frames > 0 ? cfg->max_chunk_frames : BP_MAXCACHEFRAME;
     if (h->cap < h->B) h->cap = h->B;
-    h->chunk_frames = 0;
-    h->step = 0;
     h->th_vis = cfg->dropoutflag == 1 ? drop_threshold(cfg->visible_omit) : 0u;
     h->th_hid = cfg->dropoutflag == 1 ? drop_threshold(cfg->hid_omit) : 0u;
     for (int l = 0; l < h->L; ++l) { h->s[l] = cfg->layersizes[l]; h->ld[l] = pad64(h->s[l]); }
-    h->own_stream = nullptr; h->host_out = nullptr; h->ev0 = h->ev1 = nullptr;
-    h->in = h->targ = h->out_dev = h->grad = nullptr; h->slabs = nullptr; h->out_splits = 1;
-    h->last_ms = 0.f; h->last_bunches = 0; h->dp = nullptr; h->params = h->deltas = nullptr;
-    h->next_first = -1; h->pre.valid = false; h->wgen = 0; h->stage_cur = 0;
-    h->bf_ks_slab = nullptr; h->bf_ks_cnt = nullptr;
-    h->out_act = h->out_lin = h->out_loss = 0;
-    h->fwd_mode = BP_FORWARD_DEFAULT; h->inf_slab = nullptr;
-    for (int l = 0; l < BP_MAXLAYER; ++l) h->inf_ticket[l] = nullptr;
+    h->out_splits = 1; h->next_first = -1; h->fwd_mode = BP_FORWARD_DEFAULT;   // (everything else: zero, from new bp_handle())
 
 #define CK(x) do { int _r = (x); if (_r != BP_OK) { std::string m = g_bp_err; bp_destroy(h); g_bp_err = m; return _r; } } while (0)
 #define HK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::string m = std::string(#x) + ": " + hipGetErrorString(_e); bp_destroy(h); return fail(BP_ERR_DEVICE, m); } } while (0)
@@ -158,14 +137,14 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
         const int slots = ev ? atoi(ev) : 4 * cus;
         h->wgrad_slots = slots < 8 ? 8 : slots & ~7;
     }
-    HK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    HK(h->own_stream.create(hipStreamNonBlocking));
     h->stream = h->own_stream;
-    HK(hipEventCreate(&h->ev0));
-    HK(hipEventCreate(&h->ev1));
-    HK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HK(hipEventCreateWithFlags(&h->ev_copy, hipEventDisableTiming));
-    HK(hipEventCreateWithFlags(&h->ev_retired, hipEventDisableTiming));
-    HK(hipEventCreateWithFlags(&h->ev_wretired, hipEventDisableTiming));
+    HK(h->ev0.create());
+    HK(h->ev1.create());
+    HK(h->copy_stream.create(hipStreamNonBlocking));
+    HK(h->ev_copy.create(hipEventDisableTiming));
+    HK(h->ev_retired.create(hipEventDisableTiming));
+    HK(h->ev_wretired.create(hipEventDisableTiming));
     const int L = h->L;
     const size_t Bp = (size_t)((h->B + 63) & ~63);             // bunch rows rounded up to a whole tile
     // (the stacked chunk buffers in / targ are allocated by the first stacked upload, ensure_stacked():
@@ -844,19 +823,13 @@ extern "C" int bp_upload_chunk(bp_handle *h, int n_frames, const float *in, cons
 }
 
 // ---- on-device frame stacking (host counterpart: Interface.cc:757-797)
-static int raw_reserve(bp_handle *h, int set, int which, size_t bytes)
+// Staging set `set` (grow-only): raw frames, target frames, NAT rows, the three tables.  A set that grows may still be read by
+// copies on the copy stream and by bunches on the main stream.
+static int wset_reserve(bp_handle *h, int set, size_t rows_b, size_t targ_b, size_t nat_b, size_t tab_b)
 {
-    bp_handle::Raw &r = h->wset[set].r[which];
-    if (bytes <= r.bytes) return BP_OK;
-    if (r.p) {
-        HIPCHK(hipStreamSynchronize(h->copy_stream)); HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(r.p); r.p = nullptr; r.bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4 + 4096;
-    hipError_t e = hipMalloc(&r.p, want);
-    if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("hipMalloc (window staging): ") + hipGetErrorString(e));
-    r.bytes = want;
-    return BP_OK;
+    Buf *rw = h->wset[set].r;
+    return grow_all("hipMalloc (window staging): ", {h->copy_stream, h->stream},
+                    {{rw[0], rows_b, false}, {rw[1], targ_b, false}, {rw[2], nat_b, false}, {rw[3], tab_b, false}});
 }
 
 // The stacked chunk buffers, on the first stacked upload (window chunks never need them).
@@ -933,7 +906,7 @@ static int adopt_set(bp_handle *h, int set, int n, int D, int ctx, bool with_tar
     HIPCHK(hipEventRecord(h->ev_wretired, h->stream));
     h->wretired_valid = true;
     h->wcur = set;
-    bp_handle::Raw *rw = h->wset[set].r;
+    const Buf *rw = h->wset[set].r;
     int *d_ws = (int *)rw[3].p;
     h->wv.fea = (float *)rw[0].p; h->wv.tg = with_targ ? (float *)rw[1].p : nullptr; h->wv.nat = nat ? (float *)rw[2].p : nullptr;
     h->wv.ws = d_ws; h->wv.tf = with_targ ? d_ws + n : nullptr; h->wv.nr = nat ? d_ws + 2 * (size_t)n : nullptr;
@@ -970,11 +943,8 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
         // into the staging set that is not current, on the copy stream: the bunches of the previous chunk (still reading
         // the current set on the main stream) overlap this upload
         const int set = 1 - h->wcur;                            // (always alternate: ev_wretired covers exactly the other set)
-        int r;
-        if ((r = raw_reserve(h, set, 0, fea_b)) != BP_OK || (r = raw_reserve(h, set, 1, tg_b)) != BP_OK ||
-            (r = raw_reserve(h, set, 2, nat_b)) != BP_OK || (r = raw_reserve(h, set, 3, 3 * idx_b)) != BP_OK)
-            return r;
-        bp_handle::Raw *rw = h->wset[set].r;
+        { const int r = wset_reserve(h, set, fea_b, tg_b, nat_b, 3 * idx_b); if (r != BP_OK) return r; }
+        const Buf *rw = h->wset[set].r;
         float *d_fea = (float *)rw[0].p, *d_tg = (float *)rw[1].p, *d_nat = (float *)rw[2].p;
         int *d_ws = (int *)rw[3].p, *d_tf = d_ws + n, *d_nr = d_tf + n;
         hipStream_t cs = h->copy_stream;
@@ -1009,11 +979,8 @@ int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, siz
 {
     { const int r = ensure_stage_tiles(h); if (r != BP_OK) return r; }
     const int set = 1 - h->wcur;
-    int r;
-    if ((r = raw_reserve(h, set, 0, rows_b)) != BP_OK || (r = raw_reserve(h, set, 1, targ_b)) != BP_OK ||
-        (r = raw_reserve(h, set, 2, nat_b)) != BP_OK || (r = raw_reserve(h, set, 3, 3 * n_samples * 4)) != BP_OK)
-        return r;
-    bp_handle::Raw *rw = h->wset[set].r;
+    { const int r = wset_reserve(h, set, rows_b, targ_b, nat_b, 3 * n_samples * 4); if (r != BP_OK) return r; }
+    const Buf *rw = h->wset[set].r;
     *rows = (float *)rw[0].p; *nat = (float *)rw[2].p;
     if (targ) *targ = (float *)rw[1].p;
     *tables = (int *)rw[3].p;
@@ -1122,17 +1089,19 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
         return fail(BP_ERR_ARG, "bp_train_resident_masked: frame range outside the resident chunk");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L, B = h->B, nb = n_frames / B;
-    uint8_t *dm[BP_MAXLAYER] = {nullptr};
-    float *xm = nullptr;
+    Buf dm_b[BP_MAXLAYER], xm_b;                                 // (released on return, behind the final synchronisation)
     int rc = BP_OK;
     hipError_t er = hipSuccess;
     for (int l = 0; l < L - 1 && er == hipSuccess; ++l) {
         if (!masks[l]) continue;
         const size_t bytes = (size_t)nb * B * h->s[l];
-        er = hipMalloc((void **)&dm[l], bytes ? bytes : 1);
-        if (er == hipSuccess) er = hipMemcpyAsync(dm[l], masks[l], bytes, hipMemcpyHostToDevice, h->stream);
+        er = dm_b[l].alloc(bytes ? bytes : 1);
+        if (er == hipSuccess) er = hipMemcpyAsync(dm_b[l].p, masks[l], bytes, hipMemcpyHostToDevice, h->stream);
     }
-    if (er == hipSuccess && dm[0]) er = hipMalloc((void **)&xm, ((size_t)B + 64) * h->ld[0] * sizeof(float) + SLACK * sizeof(float));
+    if (er == hipSuccess && dm_b[0].p) er = xm_b.alloc(((size_t)B + 64) * h->ld[0] * sizeof(float) + SLACK * sizeof(float));
+    uint8_t *dm[BP_MAXLAYER];
+    for (int l = 0; l < BP_MAXLAYER; ++l) dm[l] = dm_b[l].as<uint8_t>();
+    float *xm = xm_b.as<float>();
     if (er == hipSuccess && xm) er = hipMemsetAsync(xm, 0, ((size_t)B + 64) * h->ld[0] * sizeof(float) + SLACK * sizeof(float), h->stream);
     for (int i = 0; i < nb && er == hipSuccess; ++i) {
         const int first = first_frame + i * B;
@@ -1155,8 +1124,6 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
     }
     if (er != hipSuccess) rc = fail(BP_ERR_DEVICE, std::string("bp_train_resident_masked: ") + hipGetErrorString(er));
     (void)hipStreamSynchronize(h->stream);
-    for (auto p : dm) if (p) (void)hipFree(p);
-    if (xm) (void)hipFree(xm);
     return rc;
 }
 
@@ -1247,13 +1214,12 @@ int out_chunk_reserve(bp_handle *h, int n_frames)
 {
     if ((size_t)n_frames <= h->out_chunk_frames) return BP_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->out_chunk) { (void)hipFree(h->out_chunk); h->out_chunk = nullptr; }
-    if (h->host_out) { (void)hipHostFree(h->host_out); h->host_out = nullptr; }
+    h->out_chunk.release(); h->host_out.release();              // (both go before either comes back)
     h->out_chunk_frames = 0;
     const size_t want = (size_t)n_frames + (size_t)n_frames / 4 + 64;
     const size_t bytes = want * h->ld[h->L - 1] * sizeof(float);
-    if (hipMalloc((void **)&h->out_chunk, bytes + SLACK * sizeof(float)) != hipSuccess) return fail(BP_ERR_NOMEM, "hipMalloc (chunk outputs)");
-    if (hipHostMalloc((void **)&h->host_out, bytes) != hipSuccess) return fail(BP_ERR_NOMEM, "hipHostMalloc (chunk outputs)");
+    if (h->out_chunk.alloc(bytes + SLACK * sizeof(float)) != hipSuccess) return fail(BP_ERR_NOMEM, "hipMalloc (chunk outputs)");
+    if (h->host_out.alloc(bytes, true) != hipSuccess) return fail(BP_ERR_NOMEM, "hipHostMalloc (chunk outputs)");
     h->out_chunk_frames = want;
     return BP_OK;
 }
@@ -1263,7 +1229,7 @@ static int forward_bunch(bp_handle *h, int first, int fb, int mode)
 {
     const int L = h->L;
     const float vis_keep = 1.0f - h->cfg.visible_omit, hid_keep = 1.0f - h->cfg.hid_omit;   // BP_GPU.cu:703-704
-    float *out = h->out_chunk + (size_t)first * h->ld[L - 1];
+    float *out = h->out_chunk.as<float>() + (size_t)first * h->ld[L - 1];
     const float *x0 = h->windows ? h->x0s : h->in + (size_t)first * h->ld[0];
     if (h->windows) HIPCHK(stage_bunch(h, first, fb, false));
     for (int l = 1; l < L; ++l) {
@@ -1307,7 +1273,7 @@ static int forward_chunk(bp_handle *h, int n, int mode)
 {
     const int r = forward_resident_as(h, n, mode);
     if (r != BP_OK) return r;
-    if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return BP_OK;
 }
@@ -1319,7 +1285,7 @@ extern "C" int bp_forward(bp_handle *h, int n_frames, const float *in, float *ou
     if (r != BP_OK) return r;
     if ((r = forward_chunk(h, n_frames, h->fwd_mode)) != BP_OK) return r;
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
-    for (int j = 0; j < n_frames; ++j) memcpy(out + (size_t)j * sL, h->host_out + (size_t)j * ldL, sizeof(float) * sL);
+    for (int j = 0; j < n_frames; ++j) memcpy(out + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * ldL, sizeof(float) * sL);
     return BP_OK;
 }
 
@@ -1330,7 +1296,7 @@ extern "C" int bp_forward_windows(bp_handle *h, const bp_window_chunk *c, float 
     if (r != BP_OK) return r;
     if ((r = forward_chunk(h, c->n_samples, h->fwd_mode)) != BP_OK) return r;
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
-    for (int j = 0; j < c->n_samples; ++j) memcpy(out + (size_t)j * sL, h->host_out + (size_t)j * ldL, sizeof(float) * sL);
+    for (int j = 0; j < c->n_samples; ++j) memcpy(out + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * ldL, sizeof(float) * sL);
     return BP_OK;
 }
 
@@ -1341,10 +1307,11 @@ extern "C" int bp_cv_chunk(bp_handle *h, int n_frames, const float *in, const fl
     if (r != BP_OK) return r;
     if ((r = forward_chunk(h, n_frames, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV keeps the step's kernels in either mode)
     const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
+    const float *host_out = h->host_out.as<float>();
     float squared_err = 0.0f;
     for (int j = 0; j < n_frames; ++j)                   // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
         for (int d = 0; d < sL; ++d) {
-            const float e = h->host_out[(size_t)j * ldL + d] - targ[(size_t)j * sL + d];
+            const float e = host_out[(size_t)j * ldL + d] - targ[(size_t)j * sL + d];
             squared_err = squared_err + e * e;
         }
     *sq_err_sum = squared_err;
@@ -1361,11 +1328,12 @@ extern "C" int bp_cv_chunk_windows(bp_handle *h, const bp_window_chunk *c, float
     for (int i = 0; i < n; ++i)
         if (c->targ_frame[i] < 0 || c->targ_frame[i] >= c->n_frames) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: targ_frame out of range");
     if ((r = forward_chunk(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;
+    const float *host_out = h->host_out.as<float>();
     float squared_err = 0.0f;
     for (int j = 0; j < n; ++j) {                        // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
         const float *t = c->targ_frames + (size_t)c->targ_frame[j] * sL;
         for (int d = 0; d < sL; ++d) {
-            const float e = h->host_out[(size_t)j * ldL + d] - t[d];
+            const float e = host_out[(size_t)j * ldL + d] - t[d];
             squared_err = squared_err + e * e;
         }
     }

@@ -226,28 +226,30 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     const size_t new_frames = (size_t)s->max_push / hop + 3 * (size_t)nc;
     const size_t max_ana = new_frames + (size_t)nc * s->R;
     s->max_enh = std::min(max_ana, (size_t)h->cap);
-    s->in_cap = al256(max_ana * sizeof(AnaJob)) + al256((size_t)nc * sizeof(NatJob)) + al256(s->max_enh * sizeof(SynJob)) +
-                al256((new_frames + nc) * hop * 4);
+    Layout in;                                                   // the largest input block of a push (laid out by the push)
+    in.take(max_ana * sizeof(AnaJob)); in.take((size_t)nc * sizeof(NatJob)); in.take(s->max_enh * sizeof(SynJob));
+    in.take((new_frames + nc) * hop * 4);
+    s->in_cap = in.size();
     const size_t slots = 2 * (size_t)nc * s->R;
-    size_t o = 0;
-    s->o_mean = o; o += al256((size_t)D * 4);
-    s->o_istd = o; o += al256((size_t)D * 4);
-    s->o_win = o; o += al256((size_t)N * 4);
-    s->o_tw = o; o += al256((size_t)(hop + 1) * 8);
-    s->o_rows = o; o += al256(slots * D * 4);
-    s->o_Y = o; o += al256(slots * D * 8);
-    s->o_nat = o; o += al256((size_t)nc * D * 4);
-    s->o_half = o; o += al256(2 * (size_t)nc * hop * 4);
+    Layout lay;
+    s->o_mean = lay.take((size_t)D * 4);
+    s->o_istd = lay.take((size_t)D * 4);
+    s->o_win = lay.take((size_t)N * 4);
+    s->o_tw = lay.take((size_t)(hop + 1) * 8);
+    s->o_rows = lay.take(slots * D * 4);
+    s->o_Y = lay.take(slots * D * 8);
+    s->o_nat = lay.take((size_t)nc * D * 4);
+    s->o_half = lay.take(2 * (size_t)nc * hop * 4);
     const size_t consts = s->o_rows;
-    s->o_in = o; o += s->in_cap;
-    s->o_pY = o; o += al256(s->max_enh * D * 8);
-    s->o_out = o; o += al256(s->max_enh * hop * 4);
-    hipError_t e = s->blk.alloc(o, std::max(s->in_cap, consts), al256(s->max_enh * hop * 4));
+    s->o_in = lay.take(s->in_cap);
+    s->o_pY = lay.take(s->max_enh * D * 8);
+    s->o_out = lay.take(s->max_enh * hop * 4);
+    hipError_t e = s->blk.alloc(lay.size(), std::max(s->in_cap, consts), al256(s->max_enh * hop * 4));
     if (e != hipSuccess) { delete s; return fail(BP_ERR_NOMEM, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
     int r = out_chunk_reserve(h, (int)(s->max_enh + (size_t)nc * h->B));   // (fillers included: so that no push has to grow it)
     if (r != BP_OK) { delete s; return r; }
     // constants, once: the norm file, window and twiddles (computed in double and rounded once, as bp_enhance_waves does)
-    char *pin = s->blk.pin_in;
+    char *pin = s->blk.pin_in.as<char>();
     memset(pin, 0, consts);
     memcpy(pin + s->o_mean, c->mean, (size_t)D * 4);
     memcpy(pin + s->o_istd, c->inv_std, (size_t)D * 4);
@@ -311,9 +313,10 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     // ---- the input block: analysis jobs | NAT jobs | synthesis jobs | samples, each 256-byte aligned (the pinned block is reused
     // by every push: the previous one ended in a synchronisation); with it the channels' new state
     s->ana.clear(); s->natj.clear(); s->syn.clear();
-    const size_t o_ana = 0, o_nat = o_ana + al256((size_t)ana_max * sizeof(AnaJob)), o_syn = o_nat + al256((size_t)active * sizeof(NatJob));
-    const size_t o_pcm = o_syn + al256((size_t)n_enh * sizeof(SynJob));
-    char *pin = s->blk.pin_in, *dev = s->blk.dev;
+    Layout ib;
+    const size_t o_ana = ib.take((size_t)ana_max * sizeof(AnaJob)), o_nat = ib.take((size_t)active * sizeof(NatJob));
+    const size_t o_syn = ib.take((size_t)n_enh * sizeof(SynJob)), o_pcm = ib.size();
+    char *pin = s->blk.pin_in.as<char>(), *dev = s->blk.dev.as<char>();
     float *hp = (float *)(pin + o_pcm);
     size_t unit = 0, src = 0;
     int64_t y0 = 0, srow = 0, out_base = 0;
@@ -410,7 +413,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         if ((r = window_adopt(h, (int)n, D, ctx, s->nat, false)) != BP_OK) return r;
         if ((r = forward_resident_as(h, (int)n, s->packed ? BP_FORWARD_ROWINV : BP_FORWARD_DEFAULT)) != BP_OK) return r;
         StreamSynArgs a; memset(&a, 0, sizeof(a));
-        a.jobs = (const SynJob *)(din + o_syn); a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = s->out_col;
+        a.jobs = (const SynJob *)(din + o_syn); a.out = h->out_chunk.as<float>(); a.ldo = h->ld[L - 1]; a.out_col = s->out_col;
         a.Y = Y; a.win = win; a.tw = tw; a.log2M = s->log2M; a.D = D; a.target = s->target;
         a.half = (float *)(dev + s->o_half); a.pcm = (float *)(dev + s->o_out);
         const size_t lds = (syn_frames_at(hop) + (size_t)4 * hop) * sizeof(float);

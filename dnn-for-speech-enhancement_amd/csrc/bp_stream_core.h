@@ -103,39 +103,34 @@ inline std::string stream_out_checks(const char *who, int64_t due, size_t out_ca
 #ifdef __HIP__
 #include <hip/hip_runtime.h>
 
+#include "bp_mem.h"
+
 // The blocks of a stream: one device block (constants | state | a push's input block | its output samples, laid out by the
-// engine) and the pinned host ends of the two copies of a push.  One release path.
+// engine) and the pinned host ends of the two copies of a push, freed with the stream.
 struct StreamBlocks {
-    char *dev = nullptr, *pin_in = nullptr;
-    float *pin_out = nullptr;
-    ~StreamBlocks()
-    {
-        if (dev) (void)hipFree(dev);
-        if (pin_in) (void)hipHostFree(pin_in);
-        if (pin_out) (void)hipHostFree(pin_out);
-    }
+    Buf dev, pin_in, pin_out;
     hipError_t alloc(size_t dev_bytes, size_t pin_in_bytes, size_t pin_out_bytes)
     {
-        hipError_t e = hipMalloc((void **)&dev, dev_bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&pin_in, pin_in_bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&pin_out, pin_out_bytes);
+        hipError_t e = dev.alloc(dev_bytes);
+        if (e == hipSuccess) e = pin_in.alloc(pin_in_bytes, true);
+        if (e == hipSuccess) e = pin_out.alloc(pin_out_bytes, true);
         return e;
     }
     // at open: the constants the engine wrote to pin_in[0 .. consts) go to the front of the device block, the state behind
     // them, [consts, state_end), starts as zeros
     hipError_t upload_consts(size_t consts, size_t state_end, hipStream_t st)
     {
-        hipError_t e = hipMemcpyAsync(dev, pin_in, consts, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(dev + consts, 0, state_end - consts, st);
+        hipError_t e = hipMemcpyAsync(dev.p, pin_in.p, consts, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(dev.as<char>() + consts, 0, state_end - consts, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         return e;
     }
     // the end of a push: the `due` samples at dev + o_out come back, the one synchronisation, and they go to the caller
     hipError_t copy_back(size_t o_out, int64_t due, float *out_pcm, hipStream_t st)
     {
-        hipError_t e = due > 0 ? hipMemcpyAsync(pin_out, dev + o_out, (size_t)due * 4, hipMemcpyDeviceToHost, st) : hipSuccess;
+        hipError_t e = due > 0 ? hipMemcpyAsync(pin_out.p, dev.as<char>() + o_out, (size_t)due * 4, hipMemcpyDeviceToHost, st) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess && due > 0) memcpy(out_pcm, pin_out, (size_t)due * 4);
+        if (e == hipSuccess && due > 0) memcpy(out_pcm, pin_out.p, (size_t)due * 4);
         return e;
     }
 };

@@ -118,21 +118,6 @@ void wave_window_twiddles(int log2M, float *win, float2 *tw)
     for (int k = 0; k <= M; ++k) tw[k] = make_float2((float)cos(pi2 * k / N), (float)-sin(pi2 * k / N));
 }
 
-// Grow-only buffers (device or pinned host).
-int wave_grow(bp_handle::Raw &r, size_t bytes, bool pinned, hipStream_t st)
-{
-    if (bytes <= r.bytes) return BP_OK;
-    if (r.p) {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)(pinned ? hipHostFree(r.p) : hipFree(r.p)); r.p = nullptr; r.bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4 + 4096;
-    const hipError_t e = pinned ? hipHostMalloc(&r.p, want) : hipMalloc(&r.p, want);
-    if (e != hipSuccess) return fail(BP_ERR_NOMEM, std::string("signal-layer buffers: ") + hipGetErrorString(e));
-    r.bytes = want;
-    return BP_OK;
-}
-
 hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st)
 {
     hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)frames), dim3(WAVE_THREADS), lds_bytes(1 << a.log2M), st, a);
@@ -196,8 +181,10 @@ void wave_gather(float *out, const WavePlan &p, const int *sent_len, const float
 WaveIn wave_in_layout(const WavePlan &p, int D)
 {
     WaveIn w;
-    w.F = 0; w.mean = al256(((size_t)p.n_sent + 1) * 4); w.istd = w.mean + al256((size_t)D * 4); w.win = w.istd + al256((size_t)D * 4);
-    w.tw = w.win + al256((size_t)p.N * 4); w.pcm = w.tw + al256((size_t)(p.M + 1) * 8); w.bytes = w.pcm + al256(p.padded * 4);
+    Layout lay;
+    w.F = lay.take(((size_t)p.n_sent + 1) * 4); w.mean = lay.take((size_t)D * 4); w.istd = lay.take((size_t)D * 4);
+    w.win = lay.take((size_t)p.N * 4); w.tw = lay.take((size_t)(p.M + 1) * 8); w.pcm = lay.take(p.padded * 4);
+    w.bytes = lay.size();
     return w;
 }
 
@@ -227,7 +214,7 @@ extern "C" int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_
     std::vector<char> hb(w.bytes);
     wave_in_fill(hb.data(), w, p, fea_dim, nullptr, nullptr, sent_len, pcm);
     hipError_t &e = os.e;
-    char *d = os.d;
+    char *d = os.d.as<char>();
     if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), w.bytes, hipMemcpyHostToDevice, os.st);
     if (e == hipSuccess) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
@@ -262,11 +249,9 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     const int n = (int)p.frames, N = p.N;
     const WaveIn w = wave_in_layout(p, D);
     const size_t y_b = p.frames * D * sizeof(float2), fr_b = p.frames * N * 4, pcm_b = p.padded * 4;
-    int r;
-    if ((r = wave_grow(h->wave[0], w.bytes, false, h->stream)) != BP_OK || (r = wave_grow(h->wave[1], y_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(h->wave[2], fr_b, false, h->stream)) != BP_OK || (r = wave_grow(h->wave[3], pcm_b, false, h->stream)) != BP_OK ||
-        (r = wave_grow(h->wave_pin[0], w.bytes, true, h->stream)) != BP_OK || (r = wave_grow(h->wave_pin[1], pcm_b, true, h->stream)) != BP_OK)
-        return r;
+    int r = wave_grow(h, {{h->wave[0], w.bytes, false}, {h->wave[1], y_b, false}, {h->wave[2], fr_b, false}, {h->wave[3], pcm_b, false},
+                          {h->wave_pin[0], w.bytes, true}, {h->wave_pin[1], pcm_b, true}});
+    if (r != BP_OK) return r;
     float *rows_d, *nat_d; int *tab_d;
     if ((r = window_reserve(h, rows * D * 4, 0, nat ? (size_t)c->n_sent * D * 4 : 0, p.frames, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
     int *ws_d = tab_d, *nr_d = tab_d + 2 * p.frames;
@@ -295,7 +280,7 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     if ((r = forward_resident(h, n)) != BP_OK) return r;
     {
         WaveSynArgs a; memset(&a, 0, sizeof(a));
-        a.out = h->out_chunk; a.ldo = h->ld[L - 1]; a.out_col = c->out_col;
+        a.out = h->out_chunk.as<float>(); a.ldo = h->ld[L - 1]; a.out_col = c->out_col;
         a.Y = Y; a.win = win; a.tw = tw; a.log2M = p.log2M; a.D = D; a.target = c->target; a.frames = (float *)h->wave[2].p;
         hipLaunchKernelGGL(bp_wave_synthesis, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(p.M) + (size_t)(p.M + 1) * sizeof(float2), h->stream, a);
         HIPCHK(hipGetLastError());
@@ -305,10 +290,10 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     HIPCHK(hipGetLastError());
     float *hout = (float *)h->wave_pin[1].p;
     HIPCHK(hipMemcpyAsync(hout, h->wave[3].p, pcm_b, hipMemcpyDeviceToHost, h->stream));
-    if (out_net) HIPCHK(hipMemcpyAsync(h->host_out, h->out_chunk, (size_t)n * h->ld[L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (out_net) HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * h->ld[L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     wave_gather(out_pcm, p, c->sent_len, hout);
     if (out_net)
-        for (int j = 0; j < n; ++j) memcpy(out_net + (size_t)j * sL, h->host_out + (size_t)j * h->ld[L - 1], sizeof(float) * sL);
+        for (int j = 0; j < n; ++j) memcpy(out_net + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * h->ld[L - 1], sizeof(float) * sL);
     return BP_OK;
 }
