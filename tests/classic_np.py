@@ -178,6 +178,9 @@ FIXTURE_SPEC = [
            ("gap", 6000, 8, 5.0)]),
     (257, [("tones", 9000, 9, 5.0), ("tones", 6000, 10, 0.0), ("one", 1, 0, 0.0), ("short", 200, 11, 0.0), ("zero", 1500, 0, 0.0),
            ("gap", 9000, 12, 10.0)]),
+    # (appended: tests index the entries above by position)
+    (65, [("tones", 3000, 61, 5.0), ("tones", 6000, 62, 10.0), ("one", 1, 0, 0.0), ("short", 200, 63, 0.0), ("zero", 1500, 0, 0.0),
+          ("gap", 3000, 64, 5.0)]),
 ]
 
 
@@ -186,7 +189,7 @@ def make_sentence(kind, n, seed, snr_db, fea_dim):
         return np.array([1234.0], np.float32)
     if kind == "zero":
         return np.zeros(n, np.float32)
-    if kind == "short":                                          # T < init_frames at fea_dim 129 and 257
+    if kind == "short":                                          # T < init_frames at fea_dim 65, 129 and 257
         return np.round(np.random.default_rng(seed).normal(0.0, 300.0, n)).astype(np.float32)
     x = gated_tones(seed, n, fea_dim, snr_db)
     if kind == "gap":                                            # an exact-zero stretch of 3.5 hops: whole frames with P = 0

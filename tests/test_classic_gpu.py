@@ -44,11 +44,11 @@ def _against_restatement(D, kinds, xs, got, params):
 
 
 # ---- 1. bp_logmmse_waves against the restatement; the same bits on every run and in any company
-@pytest.mark.parametrize("D", [33, 129, 257])
+@pytest.mark.parametrize("D", [33, 65, 129, 257])
 def test_waves_match_restatement(pkg, D, parity_record):
     _, kinds, xs = [f for f in CN.fixtures() if f[0] == D][0]
     got = pkg.logmmse_waves(0, D, xs, return_gain=True, return_vad=True)
-    parity_record(**_against_restatement(D, kinds, xs, got, {}))
+    parity_record(fea_dim=D, **_against_restatement(D, kinds, xs, got, {}))
     i = kinds.index("tones")
     parity_record(updates=int((got[2][i] < CN.DEFAULTS["eta"]).sum()), frames=int(got[2][i].size))
     again = pkg.logmmse_waves(0, D, xs, return_gain=True, return_vad=True)
@@ -74,13 +74,14 @@ def test_non_default_parameters(pkg, parity_record):
     assert _same(pkg.logmmse_waves(0, D, xs, dict(CN.DEFAULTS)), dflt)
 
 
-def test_wide_spectrum_paths(pkg):
+def test_wide_spectrum_paths(pkg, parity_record):
     """fea_dim 513 and 1025 (3 and 5 bins per thread): the restatement's decisions and the bars, the same bits alone and in a batch."""
     for D, xs in CN.wide_fixtures():                              # (tests/test_classic_host.py vets sentence 0's VAD margin)
         p, g, v = pkg.logmmse_waves(0, D, xs, return_gain=True, return_vad=True)
         r = CN.enhance(xs[0], D)
         assert np.array_equal(v[0] < CN.DEFAULTS["eta"], r["noise"])
         e = dict(vad=relerr(v[0], r["vad"]), pcm=relerr(p[0], r["pcm"]), gain_absY=relerr(g[0].astype(np.float64) * r["absY"], r["G"] * r["absY"]))
+        parity_record(**{"fea_dim_%d" % D: e})
         assert max(e.values()) < TOL, (D, e)
         p1, g1, v1 = pkg.logmmse_waves(0, D, [xs[2]], return_gain=True, return_vad=True)
         assert _same(p1, [p[2]]) and _same(g1, [g[2]]) and _same(v1, [v[2]])

@@ -39,7 +39,7 @@ def test_e1_branches_agree_across_one():
     assert np.all(d < 0) and abs(d[0] / d[1] - 1.0) < 1e-5       # no step at the seam
 
 
-@pytest.mark.parametrize("fea_dim", [33, 129, 257])
+@pytest.mark.parametrize("fea_dim", [33, 65, 129, 257])
 def test_fixtures_are_fair(fea_dim):
     D, kinds, xs = [f for f in CN.fixtures() if f[0] == fea_dim][0]
     assert sorted(x.size for x in xs)[0] == 1 and len(xs) <= 6

@@ -28,6 +28,11 @@ def _set(rng, fs, D):
 @pytest.mark.parametrize("fs", [8000, 10000, 16000, 48000])
 @pytest.mark.parametrize("D", [129, 257])
 def test_score_waves_match_restatement(pkg, fs, D, parity_record):
+    score_case(pkg, fs, D, parity_record)
+
+
+def score_case(pkg, fs, D, parity_record):
+    """The body of test_score_waves_match_restatement (tests/test_geometry_gpu.py runs it at the other frame sizes)."""
     rng = np.random.default_rng(fs + D)
     refs, ests = _set(rng, fs, D)
     got = pkg.score_waves(0, D, fs, refs, ests)
@@ -40,7 +45,7 @@ def test_score_waves_match_restatement(pkg, fs, D, parity_record):
         l64 = EN.lsd_of_lps(lps[i], lps[len(refs) + i])
         err["lsd_rel_gpu_lps"] = max(err["lsd_rel_gpu_lps"], abs(float(got[i, 1]) - l64) / l64)
         err["stoi_abs"] = max(err["stoi_abs"], abs(float(got[i, 2]) - want[2]))
-    parity_record(**err)
+    parity_record(fea_dim=D, **err)
     assert err["ssnr_db"] <= 1e-4 and err["lsd_rel"] <= 1e-3 and err["lsd_rel_gpu_lps"] <= 1e-5 and err["stoi_abs"] <= 1e-4, err
     assert np.all(np.diff(got[:, 2]) > 0)                     # STOI rises with the SNR
 

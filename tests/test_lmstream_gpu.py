@@ -167,7 +167,7 @@ def test_many_channels(pkg, case33, parity_record):
     parity_record(pushes=feed.pushes)
 
 
-# ---- 3. the fixture calls of the offline tests (fea_dim 129 and 257: 1 and 2 bins per thread)
+# ---- 3. the fixture calls of the offline tests (fea_dim 65, 129 and 257: at most 1, 1 and 2 bins per thread)
 def _fixture_call(fea_dim):
     return [f for f in CN.fixtures() if f[0] == fea_dim][0]
 
@@ -178,8 +178,8 @@ def _two_channel_ragged(pkg, fea_dim, xs, ref, params, seed):
     return _run(pkg, fea_dim, chans, ref_chans, plans, params)
 
 
-@pytest.mark.parametrize("fea_dim", [129, 257])
-def test_fixture_sentences(pkg, fea_dim):
+@pytest.mark.parametrize("fea_dim", [65, 129, 257])
+def test_fixture_sentences(pkg, fea_dim, parity_record):
     D, kinds, xs = _fixture_call(fea_dim)
     assert {"one", "short", "zero", "gap"} <= set(kinds)
     ref = _offline(pkg, D, xs)
@@ -187,6 +187,7 @@ def test_fixture_sentences(pkg, fea_dim):
     z = kinds.index("zero")
     got = feed.sentences(z % 2)[z // 2]
     assert got.size == xs[z].size and not got.any()              # the all-zero sentence returns zeros
+    parity_record(fea_dim=D, pushes=feed.pushes, sentences=len(xs), samples_differing=0)
 
 
 def test_non_default_parameters(pkg):
@@ -198,11 +199,12 @@ def test_non_default_parameters(pkg):
 
 # ---- 4. wide spectra (fea_dim 513 and 1025: 3 and 5 bins per thread, the largest LDS layout)
 @pytest.mark.parametrize("fea_dim", [513, 1025])
-def test_wide_spectra(pkg, fea_dim):
+def test_wide_spectra(pkg, fea_dim, parity_record):
     x = [xs for D, xs in CN.wide_fixtures() if D == fea_dim][0][2]
     ref = _offline(pkg, fea_dim, [x])
     for schedule in ("hop", "one"):
-        _run(pkg, fea_dim, [[x]], [ref], [_plan([x], schedule, fea_dim - 1, None)])
+        feed = _run(pkg, fea_dim, [[x]], [ref], [_plan([x], schedule, fea_dim - 1, None)])
+    parity_record(fea_dim=fea_dim, pushes=feed.pushes, samples_differing=0)
 
 
 # ---- 5. determinism and isolation

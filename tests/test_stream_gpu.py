@@ -164,6 +164,15 @@ CONFIGS = {
     "fea129":   dict(ctx=7, toff=3, nat=True, fea_dim=129, hidden=128),
     "bf16":     dict(ctx=7, toff=3, nat=True, hkw=dict(compute_dtype=1)),
 }
+# The other frame sizes (tests/geometry_cases.py): two workgroups per noise-aware row at 257, three at 513, five at 1025, and the
+# large LDS layout of bp_stream_synthesis.  `mask`: the mask block of a [LPS | mask] output layer, read at the odd column offset D
+# of a padded row.  `packed`: the stream is opened after set_forward(FORWARD_ROWINV).
+for _D in (65, 257, 513, 1025):
+    CONFIGS["fea%d" % _D] = dict(ctx=7, toff=3, nat=True, fea_dim=_D, hidden=128)
+for _D in (257, 1025):
+    CONFIGS["fea%d_mask" % _D] = dict(ctx=7, toff=3, nat=True, fea_dim=_D, hidden=128, out_mult=2, target="mask", mask=True)
+for _D in (65, 129, 257, 513, 1025):
+    CONFIGS["fea%d_packed" % _D] = dict(ctx=7, toff=3, nat=True, fea_dim=_D, hidden=128, packed=True)
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
@@ -172,23 +181,28 @@ def test_other_configurations(pkg, name, parity_record):
     D, ctx, toff, nat = cf.get("fea_dim", FD), cf["ctx"], cf["toff"], cf["nat"]
     hop = D - 1
     ls, W, b = _net(pkg, D, ctx, nat, hidden=cf.get("hidden", 96), out_mult=cf.get("out_mult", 1))
-    g = _handle(pkg, ls, W, b, **cf.get("hkw", {}))
+    hkw = dict(output_activation=1, output_linear_cols=D) if cf.get("mask") else cf.get("hkw", {})
+    g = _handle(pkg, ls, W, b, **hkw)
     m, i = _stats(D)
     target = pkg.WAVE_MASK if cf.get("target") == "mask" else pkg.WAVE_LPS
     out_col = D if cf.get("out_mult", 1) == 2 else 0
     rng = np.random.default_rng(len(name))
     xs = WN.make_sentences(rng, [1, 5 * hop, 6 * hop - 1, hop + 1, 12 * hop + 7, 3 * hop])
     try:
+        if cf.get("packed"):
+            g.set_forward(pkg.FORWARD_ROWINV)
         ref = _offline(g, xs, m, i, ctx, toff, target=target, out_col=out_col)
+        assert all(r.size == x.size and np.isfinite(r).all() for r, x in zip(ref, xs)) and any(r.any() for r in ref)
         chans, ref_chans = _deal(xs, 2), _deal(ref, 2)
         s = g.stream_open(m, i, ctx, toff, target=target, out_col=out_col, n_chan=2, max_push_samples=32 * hop)
+        assert bool(s.packed) == bool(cf.get("packed"))
         feed = _Feed(pkg, s, D, ctx, toff, nat)
         feed.play(_plans(chans, "ragged", hop, rng))
         _check(feed, chans, ref_chans)
         s.close()
     finally:
         g.close()
-    parity_record(pushes=feed.pushes)
+    parity_record(pushes=feed.pushes, fea_dim=D, sentences=len(xs), samples_differing=0)
 
 
 # ---- 3. channel reuse and independence

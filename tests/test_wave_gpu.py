@@ -26,7 +26,7 @@ def _wave_err(got, xs):
 
 
 # ---- 1. analysis
-@pytest.mark.parametrize("fea_dim", [33, 129, 257, 1025])
+@pytest.mark.parametrize("fea_dim", [33, 65, 129, 257, 513, 1025])
 def test_analysis_matches_numpy(pkg, fea_dim, parity_record):
     n_fft, hop = WN.geometry(fea_dim)
     rng = np.random.default_rng(fea_dim)
