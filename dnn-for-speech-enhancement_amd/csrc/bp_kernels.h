@@ -74,6 +74,23 @@ struct EpiArgs {
     unsigned *done;                  // wgrad store (data parallel): +1 per finished tile, for the exchange stream (bp_dp.h); may be null
 };
 static_assert(sizeof(EpiArgs) == 160 && offsetof(EpiArgs, aux2) == 56 && offsetof(EpiArgs, done) == 152, "lin_cols / loss must sit in padding");
+// The operand fields of g (and whatever scalars the caller adds as further "+s"(x) operands) are wanted in scalar registers at this
+// one point: their loads from the argument block then go out as ONE batch with one wait.  Left to itself hipcc reads each field
+// where its first use happens to be scheduled -- A and B behind the tile map, a grouped launch's fields behind the branch that
+// picks the problem -- and every such place is another scalar round trip in front of the first operand load.
+typedef __attribute__((address_space(1))) const float *GlobalOperand;      // (an operand pointer that stays GLOBAL, not flat, through the asm)
+#define BP_PIN_OPERANDS(g, ...) do { GlobalOperand pa_ = (GlobalOperand)(g).A, pb_ = (GlobalOperand)(g).B;                                \
+        asm volatile("" : "+s"(pa_), "+s"(pb_), "+s"((g).lda), "+s"((g).ldb), "+s"((g).K), "+s"((g).tiles_m), "+s"((g).tiles_n), ##__VA_ARGS__); \
+        (g).A = (const float *)pa_; (g).B = (const float *)pb_; } while (0)
+// The operand side of a GEMM's arguments: all that the addresses of a workgroup's first k-tiles are formed from (GemmKernel::run reads
+// these in front of everything else).  The other fields are zero in the copy: it is for run's own use, next to the g_in it was
+// made from and from which run reads whatever else it needs -- never hand it to run AS g_in.
+__device__ __forceinline__ GemmArgs operand_args(const GemmArgs &s)
+{
+    GemmArgs g{};
+    g.A = s.A; g.B = s.B; g.lda = s.lda; g.ldb = s.ldb; g.K = s.K; g.tiles_m = s.tiles_m; g.tiles_n = s.tiles_n;
+    return g;
+}
 
 // ------------------------------------------------------------------ epilogue of one 32x32 block
 // C/D layout of v_mfma_f32_32x32x2_f32: lane l, reg r -> row (r&3) + 8*(r>>2) + 4*(l>>5), col l&31.
@@ -530,32 +547,66 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
 {
     using Regs = typename Cfg::Regs;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform => SGPR row bases
-    const int ks = wave / (WM * WN), wq = wave % (WM * WN), wm = wq / WN, wn = wq % WN;
-    GemmArgs g = g_in;
-    EpiArgs e = e_in;
     constexpr int EPI_E = EPI == EPI_OUT_SPLIT ? EPI_FWD_OUT : EPI == EPI_OUT_SPLIT_LOGI ? EPI_FWD_OUT_LOGI : EPI;      // the epilogue proper
-    if constexpr (epi_out_split(EPI)) {      // this workgroup row's k-slice
-        const size_t kz = (size_t)block_y * g.k_split;
-        g.A += A_KC ? kz : kz * g.lda;
-        g.B += B_KC ? kz : kz * g.ldb;
-    }
-
-    // Persistent over tiles (grid may be smaller than the tile count): the epilogue's stores of
-    // one tile are still draining while the next tile's k-loop runs.
 #ifdef BP_TRACE
-#define TRACE(i) do { if (tid == 0 && g.trace) { g.trace[(size_t)first_block * 8 + (i)] = wall_clock64();                 \
-        if ((i) == 0) g.trace[(size_t)first_block * 8 + 6] = clock64();   /* shader-clock counter: */              \
-        if ((i) == 3) g.trace[(size_t)first_block * 8 + 7] = clock64();   /* effective MHz of the run */           \
+#define TRACE(i) do { if (tid == 0 && g_in.trace) { g_in.trace[(size_t)first_block * 8 + (i)] = wall_clock64();           \
+        if ((i) == 0) g_in.trace[(size_t)first_block * 8 + 6] = clock64();   /* shader-clock counter: */           \
+        if ((i) == 3) g_in.trace[(size_t)first_block * 8 + 7] = clock64();   /* effective MHz of the run */        \
     } } while (0)
 #else
 #define TRACE(i) ((void)0)
 #endif
-    TRACE(0);
-    for (int b = first_block; b < g.tiles_m * g.tiles_n; b += stride) {
+#define K0_OF(t) (((t) * BK) < last_k0 ? ((t) * BK) : last_k0)
+#define PA(t) Cfg::base_a(g, m0, K0_OF(t))
+#define PB(t) Cfg::base_b(g, n0, K0_OF(t))
+#define AS(buf) (smem + (buf) * STAGE)
+#define BS(buf) (smem + (buf) * STAGE + A_STAGE)
+
+    TRACE(0);                                     // (development build: at the entry, so that the trace's prologue contains the head)
+    // ---- head: the loads of k-tiles 0 and 1 of the workgroup's first tile go out before anything else.  A workgroup is alone on
+    // its SIMDs when it starts, so whatever runs in front of its first load is paid as latency with nothing in flight.
+    // Only the operand side of the arguments is read here (one batch of scalar loads, one wait); the epilogue's arguments, the
+    // accumulators and the epilogue's own fetches follow behind the loads.
+    GemmArgs g = operand_args(g_in);              // (what else a kernel needs of g_in it reads where it uses it)
+    if constexpr (epi_out_split(EPI)) {      // this workgroup row's k-slice
+        const size_t kz = (size_t)block_y * g_in.k_split;
+        g.A += A_KC ? kz : kz * g.lda;
+        g.B += B_KC ? kz : kz * g.ldb;
+    }
+    BP_PIN_OPERANDS(g);
+    const int tiles = g.tiles_m * g.tiles_n;
+    int b = first_block;
+    if (b >= tiles) return;                       // (padding entry of a grouped launch)
+    const int nt = (g.K + BK - 1) / BK, last_k0 = (nt - 1) * BK;
+    typename Cfg::Offs offs;
+    Cfg::make_offs(offs, g, tid);
     int tile_m, tile_n;
     xcd_tile<BIASG>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0 = tile_m * BM, n0 = tile_n * BN;
+    // Two register images hold k-tiles t+1 (landed, being staged) and t+2 (in flight) of the software pipeline below.  Every load
+    // is unconditional (past the end the tile index is clamped and the data ignored): a conditional load turns into a phi + copy
+    // and hipcc then waits for it right away.
+    Regs r0, r1;
+    Cfg::load(r0, PA(0), PB(0), offs);
+    Cfg::load(r1, PA(1), PB(1), offs);
+    __builtin_amdgcn_sched_barrier(0);
 
+    // The epilogue's arguments are read HERE, behind the loads, at an offset the optimiser does not know to be 0.  Read plainly
+    // (e = e_in), their scalar loads are hoisted into the blocks in front of the tile map (a sched_barrier orders one basic block),
+    // and the first use of any of them there -- hipcc spills one into a VGPR lane -- is a second full scalar wait in front of the
+    // first operand load.  WHEN THE COMPILER CHANGES, rerun the listing check of profiles/r15_gemm_head.txt section 1: this asm,
+    // BP_PIN_OPERANDS and the asm in bp_gemm_multi steer hipcc by side effects it does not promise, and no test on a machine
+    // without a GPU holds the instruction and wait counts in front of the first global_load_dwordx4.
+    int behind = 0;
+    asm volatile("" : "+s"(behind));
+    const EpiArgs e = *reinterpret_cast<const EpiArgs *>(reinterpret_cast<const char *>(&e_in) + behind);
+    const int ks = wave / (WM * WN), wq = wave % (WM * WN), wm = wq / WN, wn = wq % WN;
+    const int a_off = wm * TM * 32 + (lane & 31), b_off = wn * TN * 32 + (lane & 31);
+    const int kh = lane >> 5;
+
+    // Persistent over tiles (grid may be smaller than the tile count): the epilogue's stores of
+    // one tile are still draining while the next tile's k-loop runs.
+    for (;;) {
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);   // bias-gradient partial sums (wgrad; used by m-tile 0)
     const bool do_bias = BIASG && tile_m == 0;
 
@@ -569,10 +620,6 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accs[c][i][j][r] = 0.0f;
-
-    const int nt = (g.K + BK - 1) / BK;
-    const int a_off = wm * TM * 32 + (lane & 31), b_off = wn * TN * 32 + (lane & 31);
-    const int kh = lane >> 5;
 
     // Epilogue inputs (bias / targ / y_prev / W, delta) are fetched up front so their HBM/L2 latency
     // hides under the k-loop (same lane->element map as the accumulator).
@@ -593,26 +640,12 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         }
     }
 
-    // ---- software pipeline: LDS holds tile t (double buffered), two register images hold tiles
-    // t+1 (landed, being staged) and t+2 (in flight).  One barrier per k-tile.  Every load in the steady-state loop is
-    // unconditional (past the end the tile index is clamped and the data ignored): a
-    // conditional load turns into a phi + copy and hipcc then waits for it right away.
-    const int last_k0 = (nt - 1) * BK;
-    typename Cfg::Offs offs;
-    Cfg::make_offs(offs, g, tid);
-#define K0_OF(t) (((t) * BK) < last_k0 ? ((t) * BK) : last_k0)
-#define PA(t) Cfg::base_a(g, m0, K0_OF(t))
-#define PB(t) Cfg::base_b(g, n0, K0_OF(t))
-#define AS(buf) (smem + (buf) * STAGE)
-#define BS(buf) (smem + (buf) * STAGE + A_STAGE)
+    // ---- software pipeline: LDS holds tile t (double buffered), the register images r0 / r1 tiles t+1 and t+2.  One barrier per k-tile.
 // multiply stage `buf`; ST: store image RS (k-tile TS) into the other stage; LD: load tile TL into image RL
 #define STEP(ST, LD, buf, RS, TS, RL, TL)                                                                  \
     Cfg::template step<ST, LD>(AS(buf), BS(buf), accs, ks, a_off, b_off, kh, RS, AS((buf) ^ 1), BS((buf) ^ 1),    \
                                RL, PA(TL), PB(TL), offs, tid, bsum, g.K - (TS) * BK)
-    Regs r0, r1;
-    Cfg::load(r0, PA(0), PB(0), offs);
     Cfg::store(r0, AS(0), BS(0), tid, bsum, g.K);
-    Cfg::load(r1, PA(1), PB(1), offs);
     __syncthreads();
     TRACE(1);
     // Invariant at the top of iteration t: LDS stage t&1 holds tile t; tile t+1 is in flight / landed in registers
@@ -634,12 +667,11 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     STEP(false, false, buf, r0, 0, r0, 0);    // last tile: nothing left to stage or fetch
     __syncthreads();
     TRACE(2);
-#undef K0_OF
-#undef PA
-#undef PB
-#undef AS
-#undef BS
 #undef STEP
+    // Every load issued so far has landed or is dead (the clamped image behind the last k-tile).  Said once, here: the epilogue's
+    // inputs are now fetched BEHIND the first operand loads, and on the one-k-tile path no later wait covers them, so hipcc would
+    // drain in front of every use of one -- also between the epilogue's own stores, waiting for each to be acknowledged.
+    __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0), expcnt and lgkmcnt left alone
     // fold the independent accumulator chains
     f32x16 (&acc)[TM][TN] = accs[0];
     if constexpr (NCH == 2) {
@@ -701,18 +733,18 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     bool finish = true;
     if constexpr (epi_out_split(EPI)) {
         static_assert(KS == 4 && OUT_SPLITS == 4, "one 32x32 block per workgroup, four registers of it per wave");
-        float *mine = g.ks_slab + (size_t)block_y * g.slab_stride;
+        float *mine = g_in.ks_slab + (size_t)block_y * g_in.slab_stride;
         if (ks == 0) out_split_store<0>(e, mine, mb0, nb0, acc[0][0], lane);
         if (ks == 1) out_split_store<4>(e, mine, mb0, nb0, acc[0][0], lane);
         if (ks == 2) out_split_store<8>(e, mine, mb0, nb0, acc[0][0], lane);
         if (ks == 3) out_split_store<12>(e, mine, mb0, nb0, acc[0][0], lane);
         // (the ticket's LDS word: its first barrier also puts every wave past its reads of the exchange area)
-        finish = last_arrival(g.ks_ticket + b, reinterpret_cast<unsigned *>(smem), OUT_SPLITS);
+        finish = last_arrival(g_in.ks_ticket + b, reinterpret_cast<unsigned *>(smem), OUT_SPLITS);
         if (finish) {
-            if (ks == 0) out_split_sum<0>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);
-            if (ks == 1) out_split_sum<4>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);
-            if (ks == 2) out_split_sum<8>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);
-            if (ks == 3) out_split_sum<12>(e, g.ks_slab, g.slab_stride, mb0, nb0, acc[0][0], lane);
+            if (ks == 0) out_split_sum<0>(e, g_in.ks_slab, g_in.slab_stride, mb0, nb0, acc[0][0], lane);
+            if (ks == 1) out_split_sum<4>(e, g_in.ks_slab, g_in.slab_stride, mb0, nb0, acc[0][0], lane);
+            if (ks == 2) out_split_sum<8>(e, g_in.ks_slab, g_in.slab_stride, mb0, nb0, acc[0][0], lane);
+            if (ks == 3) out_split_sum<12>(e, g_in.ks_slab, g_in.slab_stride, mb0, nb0, acc[0][0], lane);
         }
     }
 
@@ -730,9 +762,20 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
             if (ks == 3) epilogue_block<EPI_E, 12, 4>(e, mb0, nb0, acc[0][0], lane, pre[0][0]);
         }
     }
-    if (b + stride < g.tiles_m * g.tiles_n) __syncthreads();   // smem is reused by the next tile
+    b += stride;
+    if (b >= tiles) break;
+    __syncthreads();                              // smem is reused by the next tile
+    xcd_tile<BIASG>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
+    m0 = tile_m * BM; n0 = tile_n * BN;
+    Cfg::load(r0, PA(0), PB(0), offs);            // (the next tile's loads in front of its setup as well)
+    Cfg::load(r1, PA(1), PB(1), offs);
     }   // tile loop
     TRACE(3);
+#undef K0_OF
+#undef PA
+#undef PB
+#undef AS
+#undef BS
 #undef TRACE
 }
 };   // GemmKernel
@@ -765,8 +808,23 @@ template <class K>
 __global__ __launch_bounds__(256, K::MIN_WG) void bp_gemm_multi(const MultiArgs a)
 {
     __shared__ __attribute__((aligned(16))) float smem[K::SMEM];
-    const int b = blockIdx.x, p = problem_of(a, b, 0);
-    K::run(a.g[p], a.e[p], b - a.first_tile[p], a.first_tile[p + 1] - a.first_tile[p], 0, smem);
+    // From the block index to the first operand address in ONE scalar round trip for problem 0 (the dgrad launches of the step hold
+    // one problem each): the tile list and problem 0's operand fields lie at constant offsets of the argument block and are read as
+    // one batch.  (Indexed with a p that is itself loaded -- problem_of, then first_tile[p], then g[p] -- every step was a dependent
+    // scalar load with a full wait in front of the workgroup's first operand load.)  A later problem pays one more round trip for
+    // its own fields; the epilogue's arguments are read through p behind the operand loads (K::run).
+    const int b = blockIdx.x;
+    int n = a.n, first = a.first_tile[0], next = a.first_tile[1];
+    GemmArgs g = a.g[0];                          // (the whole struct: K::run may read any field; only those it reads are loaded)
+    BP_PIN_OPERANDS(g, "+s"(n), "+s"(first), "+s"(next));
+    int p = 0;
+    if (n > 1 && b >= next) {                     // a later problem: walk the list
+        asm volatile("");                         // (not to be speculated: it would put the indexed loads in front of every workgroup)
+        p = problem_of(a, b, 1);
+        g = a.g[p];
+        first = a.first_tile[p]; next = a.first_tile[p + 1];
+    }
+    K::run(g, a.e[p], b - first, next - first, 0, smem);
 }
 
 // ------------------------------------------------------------------ small kernels
@@ -918,6 +976,11 @@ __global__ __launch_bounds__(256, K::MIN_WG) void bp_out_split_stage(const GemmA
 {
     __shared__ __attribute__((aligned(16))) float smem[K::SMEM];
     const int b = blockIdx.x;
-    if (b < n_gemm) { const int tiles = g.tiles_m * g.tiles_n; K::run(g, e, b % tiles, tiles, b / tiles, smem); }
-    else { const int i = b - n_gemm; stage_block(st, i % st.nbx, i / st.nbx, threadIdx.x); }
+    // (the GEMM's operand fields ride in the batch that fetches n_gemm: one scalar round trip in front of a GEMM workgroup's first
+    // operand load instead of two.  The staging workgroups branch away before any GEMM setup.)
+    GemmArgs gg = g;
+    int ng = n_gemm;
+    BP_PIN_OPERANDS(gg, "+s"(ng), "+s"(gg.k_split));
+    if (b < ng) { const int tiles = gg.tiles_m * gg.tiles_n; K::run(gg, e, b % tiles, tiles, b / tiles, smem); }
+    else { const int i = b - ng; stage_block(st, i % st.nbx, i / st.nbx, threadIdx.x); }
 }

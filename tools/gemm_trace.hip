@@ -1,6 +1,6 @@
 // tools/gemm_trace.hip -- development probe: per-workgroup phase timestamps (100 MHz wall clock) of
 // back-to-back bp_gemm launches: entry, end of prologue, end of k-loop, end of epilogue.
-// usage: gemm_trace fwd|wgrad [K]
+// usage: gemm_trace fwd|dgrad|wgrad|wg64 [K]     (dgrad: the 128-deep hidden dgrad through the grouped wrapper, one problem)
 #define BP_TRACE 1
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -15,6 +15,7 @@ int main(int argc, char **argv)
 {
     const bool wg64 = argc > 1 && !strcmp(argv[1], "wg64");     // grouped-launch-sized wgrad: 7168x2048, 64x64x32 tiles
     const bool wgrad = wg64 || (argc > 1 && !strcmp(argv[1], "wgrad"));
+    const bool dgrad = argc > 1 && !strcmp(argv[1], "dgrad");
     const int MW = wg64 ? 7168 : 2048;
     const int B = 256, H = 2048, K = argc > 2 ? atoi(argv[2]) : (wgrad ? 256 : 2048);
     float *Y = dalloc((size_t)2048 * (wg64 ? MW : H)), *W = dalloc((size_t)MW * H), *D = dalloc((size_t)MW * H), *Yo = dalloc((size_t)2048 * H), *bias = dalloc(H), *bd = dalloc(H);
@@ -33,8 +34,13 @@ int main(int argc, char **argv)
     for (int rep = 0; rep < 3; ++rep) {
         for (int l = 0; l < 4; ++l) {
             g.trace = tr + (size_t)l * NWG * 8;
-            if (wg64) hipLaunchKernelGGL((bp_gemm<64, 64, 32, 2, 2, false, false, EPI_WGRAD_UPDATE, 1, 8>), dim3(NWG), dim3(256), 0, st, g, e);
-            else if (wgrad && K == 256 && argc > 3) hipLaunchKernelGGL((bp_gemm<128, 64, 16, 2, 2, false, false, EPI_WGRAD_UPDATE, 1, 16>), dim3(NWG), dim3(256), 0, st, g, e);
+            if (wg64) hipLaunchKernelGGL((bp_gemm<64, 64, 32, 2, 2, false, false, EPI_WGRAD_UPDATE, 1>), dim3(NWG), dim3(256), 0, st, g, e);
+            else if (dgrad) {       // dEdX_prev = act'(y_prev) * (dEdX . W^T): A = dEdX [m][k], B = W [n][k], aux = y_prev
+                MultiArgs a; memset(&a, 0, sizeof(a));
+                a.g[0] = g; a.e[0] = e; a.e[0].bias = nullptr; a.e[0].drop_thresh = 0; a.e[0].aux = D; a.e[0].ldaux = H;
+                a.first_tile[0] = 0; a.first_tile[1] = NWG; a.n = 1;
+                hipLaunchKernelGGL((bp_gemm_multi<GemmKernel<32, 64, 128, 1, 2, true, true, EPI_DGRAD> >), dim3(NWG), dim3(256), 0, st, a);
+            }
             else if (wgrad) hipLaunchKernelGGL((bp_gemm<128, 64, 16, 2, 2, false, false, EPI_WGRAD_UPDATE, 1>), dim3(NWG), dim3(256), 0, st, g, e);
             else hipLaunchKernelGGL((bp_gemm<32, 64, 64, 1, 2, true, false, EPI_FWD_HIDDEN, 1>), dim3(NWG), dim3(256), 0, st, g, e);
         }
@@ -94,7 +100,7 @@ int main(int argc, char **argv)
                     sp_entry += (hi0 - lo0) / 32; sp_loop += (hi2 - lo2) / 32; sp_max = std::max(sp_max, hi2 - lo2);
                 }
             printf("  8 workgroups of one weight panel: spread of entry %.2f us, of k-loop end %.2f us on average (max %.2f); one k-tile = %.2f us\n",
-                   sp_entry, sp_loop, sp_max, dur[1] / ((K + 63) / 64));
+                   sp_entry, sp_loop, sp_max, dur[1] / ((K + (dgrad ? 127 : 63)) / (dgrad ? 128 : 64)));
         }
         if (!wg64) {
             double mhz = 0; int cnt = 0;
@@ -105,7 +111,7 @@ int main(int argc, char **argv)
             printf("  shader clock during the kernel (clock64 / wall_clock64): %.0f MHz\n", cnt ? mhz / cnt : 0.0);
         }
         printf("launch %d (%s K=%d): entry [%.2f..%.2f] prologue_done [%.2f..%.2f] loop_done [%.2f..%.2f] end [%.2f..%.2f] us | per-WG avg: prologue %.2f loop %.2f epilogue %.2f\n",
-               l, wgrad ? "wgrad 128x64x16" : "fwd 32x64x64", K, mn[0], mx[0], mn[1], mx[1], mn[2], mx[2], mn[3], mx[3], dur[0], dur[1], dur[2]);
+               l, wgrad ? "wgrad 128x64x16" : dgrad ? "dgrad 32x64x128" : "fwd 32x64x64", K, mn[0], mx[0], mn[1], mx[1], mn[2], mx[2], mn[3], mx[3], dur[0], dur[1], dur[2]);
     }
     return 0;
 }
