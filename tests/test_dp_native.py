@@ -27,6 +27,9 @@ CASES = [
     # name, layersizes, local B, world, global bunches, extras
     ("tiny2", [12, 7, 5, 3], 4, 2, 4, {}),
     ("odd3_dropout_unaligned", [70, 65, 130, 33], 25, 3, 3, {"drop": True, "wc": 0.01, "act": 1, "tail": 31}),   # bunch 75: offsets 25, 50
+    # the same net under a weight cost and a momentum that matter (tests/update_cases.py says why wc 0.01 at m 0.5 does not bind): the
+    # weights | biases boundary inside a segment of the sharded update, rule 1
+    ("odd3_wc_rule1", [70, 65, 130, 33], 25, 3, 3, {"act": 1, "rule": 1, "m": 0.9, "wc": 0.0625}),
     ("nat4_classic", [1548, 256, 192, 129], 16, 4, 4, {"drop": True, "rule": 1}),
     ("c4_4x512", [2827, 2048, 2048, 2048, 257], 512, 4, 2, {"beta": 0.5}),           # configs[3]'s net and global bunch, 4 ranks
     # configs[3]'s net and global bunch on 4 ranks, SIX global minibatches at lrate 0.02: outputs, weights and biases at PLAIN 1e-4 against the oracle with no
@@ -36,6 +39,7 @@ CASES = [
     # BP_DP_TRANSPORT_NATIVE_PUSH (transport 2): the reduce-scatter by peer WRITES into the owners' receive buffers
     ("push_tiny2", [12, 7, 5, 3], 4, 2, 4, {"transport": 2}),
     ("push_odd3_dropout_unaligned", [70, 65, 130, 33], 25, 3, 3, {"drop": True, "wc": 0.01, "act": 1, "tail": 31, "transport": 2}),
+    ("push_odd3_wc_rule1", [70, 65, 130, 33], 25, 3, 3, {"act": 1, "rule": 1, "m": 0.9, "wc": 0.0625, "transport": 2}),
     ("push_c4_4x512", [2827, 2048, 2048, 2048, 257], 512, 4, 2, {"beta": 0.5, "transport": 2}),   # configs[3]'s net and global bunch, in-kernel hand-off
     ("push_c2_world1", [2827, 2048, 257], 256, 1, 2, {"drop": True, "transport": 2}),
     ("push_bf16_2", [300, 256, 128, 64], 64, 2, 2, {"compute_dtype": 1, "lr": 0.5, "transport": 2}),        # event hand-off
@@ -72,8 +76,24 @@ def run_case(name, ls, B, world, nb, extra, timeout=600):
     return c, case_data(c), res
 
 
+def forward_of_returned_weights_unequal(pkg, c, r0, x):
+    """A handle made as dp_worker.py makes its own (layer sizes, bunch, activation, compute_dtype, dropout scales), but on one rank
+    and unattached, from rank 0's returned W, b: the number of words in which its forward differs from rank 0's `out`."""
+    ls, B = c["ls"], c["B"]
+    kw = dict(activation=c.get("act", 0), momentum_rule=c.get("rule", 0), compute_dtype=c.get("compute_dtype", 0))
+    if c.get("drop"):
+        kw.update(dropoutflag=1, visible_omit=0.1, hid_omit=0.2, seed=99)
+    W = [None] + [r0["W%d" % l] for l in range(1, len(ls))]
+    b = [None] + [r0["b%d" % l] for l in range(1, len(ls))]
+    n_cv = r0["out"].shape[0]
+    g = pkg.BP_GPU(1, len(ls), ls, B, c.get("lr", 1.0), c.get("m", 0.5), c.get("wc", 0.0), W, b, max_chunk_frames=max(4 * B, 64), **kw)
+    out = g.forward(x[:n_cv])
+    g.close()
+    return int(np.count_nonzero(out != r0["out"]))
+
+
 @pytest.mark.parametrize("name,ls,B,world,nb,extra", CASES, ids=[c[0] for c in CASES])
-def test_native_dp_matches_global_bunch_oracle(oracle_mod, parity_record, name, ls, B, world, nb, extra):
+def test_native_dp_matches_global_bunch_oracle(pkg, oracle_mod, parity_record, name, ls, B, world, nb, extra):
     c, (W, b, x, t), res = run_case(name, ls, B, world, nb, extra)
     L = len(ls)
     # 1. replicated state is bit-identical on every rank
@@ -81,6 +101,11 @@ def test_native_dp_matches_global_bunch_oracle(oracle_mod, parity_record, name, 
         for k in res[0]:
             assert np.array_equal(res[0][k], res[r][k]), (name, "rank", r, k)
     assert int(res[0]["epochs"]) == nb
+    # 1b. the forward rank 0 ran on its trained, attached handle is, bit for bit, the forward of a plain handle made from the
+    # weights it returned (bf16 rows: the shadow bf_shadow wrote after the sharded update against the one made at creation)
+    shadow_unequal = forward_of_returned_weights_unequal(pkg, c, res[0], x)
+    parity_record(forward_of_returned_weights_unequal_words=shadow_unequal)
+    assert shadow_unequal == 0, (name, "rank 0's forward differs from a handle made from its returned weights in", shadow_unequal, "words")
     # 2. == the oracle on the global bunch
     kw = dict(activation=c.get("act", 0), momentum_rule=c.get("rule", 0))
     bf = c.get("compute_dtype", 0) == 1
