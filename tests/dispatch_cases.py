@@ -53,6 +53,20 @@ CASES = [
 ]
 BY_ID = {c.id: c for c in CASES}
 
+# The seven logistic cases once more with the squared error through the logistic (output_loss 1: d *= o (1 - o) on the logistic
+# columns).  A list of its own: the kernels are those of the cases above (the loss is a run-time switch), so these claim nothing in
+# tests/test_dispatch_coverage.py; tests/switch_cases.py counts them.
+LOSS1_CASES = [c._replace(id=c.id + "_mse", out=(c.out[0], 1)) for c in CASES if c.out is not None]
+
+# The handle of the keep-scaled forward and CV pass (tests/test_dispatch_gpu.py::test_forward_and_cv_keep_scaled): it never trains,
+# so the dropout keywords only set alpha = 1 - omit in every forward epilogue.
+KEEP_DROP = dict(dropoutflag=1, visible_omit=0.1, hid_omit=0.2)
+
+
+def keep_scales(c, drop=KEEP_DROP):
+    """[None, 1 - visible_omit, 1 - hid_omit, ...]: the factor on the product of weight layer l = 1 .. L-1."""
+    return [None, 1.0 - drop["visible_omit"]] + [1.0 - drop["hid_omit"]] * (len(c.ls) - 2)
+
 
 def strict_bar(spread):
     """fp32: the one-bunch gradient holds 1e-5 where the reference alone supports it.  The spread is one sample of what another

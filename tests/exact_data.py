@@ -25,6 +25,9 @@ checked from the reference alone:
      64 x 64 block of that GEMM's output (slab_holes; the bias sums: to every 64-column tile); 25 .. 75 % of the ReLUs of every
      hidden layer are live; every G_l has more than 256 distinct values and no all-zero 64 x 64 block.
 
+A shard problem (SHARD_CASES) is the same at a global bunch Bg = 2B and a rank_frame_offset: t = o_ref - d Bg/2, and the masks are
+those of the global frames from the offset on.
+
 What it cannot cover: a second step (the updated weights are no longer few-bit numbers), Sigmoid nets, logistic forward columns."""
 import numpy as np
 
@@ -39,7 +42,17 @@ CV_ERRORS = np.array([0.0, 1.0, -1.0, 2.0, -2.0])        # o - t of the CV targe
 
 BF16_CASES = [c for c in DC.CASES if c.dtype == 1]
 FP32_STEP_CASES = ["f32_wide128", "f32_nine_layers_b128", "f32_b512"]     # power-of-two bunches: 2/B is an fp32 number
-DROPOUT_CASES = ["bf_rows128", "bf_nine_layers"]
+DROPOUT_CASES = ["bf_rows128", "bf_nine_layers", "bf_rows64"]
+# Shard handles (one rank's share of a data-parallel bunch; gradient store only, a shard handle trains through its group): the
+# case's bunch B at global bunch 2B and rank_frame_offset 3, with dropout.  dEdX_L = fl32(2/Bg)(o - t), so the targets are
+# o_ref - d Bg/2, and the masks are those of the global frames 3 .. B + 2: the last of the two-block branches of drop_words4.
+SHARD_CASES = ["bf_rows64", "bf_rows128"]
+SHARD_OFFSET = 3
+
+
+def shard_of(cid):
+    """(rank_frame_offset, global bunch) of a shard problem."""
+    return SHARD_OFFSET, 2 * DC.BY_ID[cid].B
 
 
 def exact_case(c):
@@ -103,31 +116,33 @@ def oracle(c, W, b, acc_double=False, drop=False):
     return O.Oracle(c.ls, c.B, LR, MOM, WC, W, b, activation=0, compute_dtype=c.dtype, acc_double=acc_double, **(DROP if drop else {}))
 
 
-def masks(c, W, b):
-    """The Philox masks of the first step of a handle (step 0, frames counted from the start of the bunch), as the oracle draws them."""
+def masks(c, W, b, gframe0=0):
+    """The Philox masks of the first step of a handle (step 0, frames counted from the start of the bunch, which is global frame
+    gframe0), as the oracle draws them."""
     o = oracle(c, W, b, drop=True)
-    return [o.fill_mask(0, l, c.B) for l in range(len(c.ls) - 1)]
+    return [o.fill_mask(0, l, c.B, gframe0=gframe0) for l in range(len(c.ls) - 1)]
 
 
-def reference_outputs(c, W, b, x, drop=False):
+def reference_outputs(c, W, b, x, drop=False, gframe0=0):
     """The pre-activation output of every frame: training mode (with the masks of `masks`) for the whole bunches when drop, else the
     plain forward."""
     o = oracle(c, W, b)
     if not drop:
         return o.forward(x)
-    mk, B = masks(c, W, b), c.B
+    mk, B = masks(c, W, b, gframe0), c.B
     out = o.forward(x)                                             # (the trailing partial bunch is never trained on)
     for i in range(x.shape[0] // B):
         out[i * B:(i + 1) * B] = o.grads(x[i * B:(i + 1) * B], np.zeros((B, c.ls[-1]), np.float32), masks=mk)[3]
     return out
 
 
-def train_targets(c, W, b, x, drop=False):
+def train_targets(c, W, b, x, drop=False, shard=None):
     """(t, t_oracle, d): the targets of the handle, those of the oracle (they differ on logistic columns only) and the dEdX_L both
-    must arrive at, [n][sL] each.  The rows of a longer chunk start with those of a shorter one."""
-    n, sL, B = x.shape[0], c.ls[-1], c.B
-    rng = np.random.default_rng(_seed(c) + 200 + (50 if drop else 0))
-    o = reference_outputs(c, W, b, x, drop).astype(np.float64)
+    must arrive at, [n][sL] each.  The rows of a longer chunk start with those of a shorter one.  shard = (offset, Bg): the scale
+    is 2/Bg, the masks those of the global frames from offset on."""
+    n, sL, B = x.shape[0], c.ls[-1], (c.B if shard is None else shard[1])
+    rng = np.random.default_rng(_seed(c) + 200 + (50 if drop else 0) + (7 if shard else 0))
+    o = reference_outputs(c, W, b, x, drop, shard[0] if shard else 0).astype(np.float64)
     idx = rng.integers(0, len(D_VALUES), size=(n, sL))
     if c.out is not None:
         lin = c.out[0]
@@ -178,7 +193,7 @@ class Bunch(object):
     """One bunch in float64 with the storage rounding of oracle/bp_oracle.c (compute_dtype 1: weights, the masked input, every hidden
     output and every dEdX_l are bf16 numbers).  gemms: (name, A [M][K], B [K][N], addend [N] or None) of every GEMM of the step."""
 
-    def __init__(self, c, W, b, x, t, mk=None):
+    def __init__(self, c, W, b, x, t, mk=None, Bg=None):
         L, B = len(c.ls), x.shape[0]
         r = bf16_round if c.dtype == 1 else (lambda v: np.asarray(v, np.float64))
         Wb = [None] + [r(W[l]) for l in range(1, L)]
@@ -193,7 +208,7 @@ class Bunch(object):
                 y = np.maximum(z, 0.0)
                 ys.append(r(y * (1.0 - mk[l]) if mk else y))
         self.out = z
-        s = np.float32(2.0) / np.float32(B)                                                # kernSubClean, in fp32 as both sides do it
+        s = np.float32(2.0) / np.float32(Bg or B)                                          # kernSubClean, in fp32 as both sides do it
         dx = {L - 1: r((s * (z.astype(np.float32) - np.asarray(t, np.float32))).astype(np.float32))}
         assert np.array_equal(z.astype(np.float32).astype(np.float64), z), (c.id, "the output is no fp32 number")
         for l in range(L - 1, 1, -1):
@@ -296,32 +311,36 @@ def steps_exactly(c):
     return c.dtype == 1 or c.id in FP32_STEP_CASES
 
 
-def problem(cid, drop=False):
+def problem(cid, drop=False, shard=None):
     """The data of a case, made once and read-only: c (exact_case), W, b, x (2B + B/2 frames: two whole bunches and a partial one),
-    t (the handle's training targets), t_oracle, d, masks (drop: the step-0 Philox masks, else None), t_cv, cv_sum, cv_skip."""
-    if (cid, drop) not in _PROBLEMS:
+    t (the handle's training targets), t_oracle, d, masks (drop: the step-0 Philox masks, else None), t_cv, cv_sum, cv_skip.
+    shard: shard_of(cid) for the shard problem of the case (always with dropout)."""
+    if (cid, drop, shard) not in _PROBLEMS:
         p = _Bag()
         p.c = c = exact_case(DC.BY_ID[cid])
         p.W, p.b = net(c)
         p.x = inputs(c, 2 * c.B + c.B // 2)
-        p.t, p.t_oracle, p.d = train_targets(c, p.W, p.b, p.x, drop)
-        p.masks = masks(c, p.W, p.b) if drop else None
+        p.shard = shard
+        p.t, p.t_oracle, p.d = train_targets(c, p.W, p.b, p.x, drop, shard)
+        p.masks = masks(c, p.W, p.b, shard[0] if shard else 0) if drop else None
         p.t_cv, p.cv_sum, p.cv_skip = cv_targets(c, p.W, p.b, p.x)
         _frozen([p.W[1:], p.b[1:], p.x, p.t, p.t_oracle, p.d, p.masks, p.t_cv])
-        _PROBLEMS[(cid, drop)] = p
-    return _PROBLEMS[(cid, drop)]
+        _PROBLEMS[(cid, drop, shard)] = p
+    return _PROBLEMS[(cid, drop, shard)]
 
 
-def reference(cid, drop=False, acc_double=False):
+def reference(cid, drop=False, acc_double=False, shard=None):
     """The oracle's results on problem(cid, drop), computed once and read-only: grads[k] = (gw, gb) of bunch k = 0, 1; state =
     (W, b, dW, db) after one step on bunch 0 from zero momentum; forward = the output of the first B + 3 frames; cv = CrossValid
-    on the whole chunk against t_cv.  acc_double (the oracle's slow loops, condition (b) only): bunch 0, state and forward."""
-    key = (cid, drop, acc_double)
+    on the whole chunk against t_cv.  acc_double (the oracle's slow loops, condition (b) only): bunch 0, state and forward.
+    shard: the gradients at scale 2/Bg; the state is that of the update on bunch 0's gradient, which no shard handle performs."""
+    key = (cid, drop, acc_double, shard)
     if key not in _REFERENCES:
-        p, r = problem(cid, drop), _Bag()
+        p, r = problem(cid, drop, shard), _Bag()
         c, B = p.c, p.c.B
         o = oracle(c, p.W, p.b, acc_double, drop)
-        r.grads = [o.grads(p.x[k * B:(k + 1) * B], p.t_oracle[k * B:(k + 1) * B], masks=p.masks)[:2] for k in ((0,) if acc_double else (0, 1))]
+        r.grads = [o.grads(p.x[k * B:(k + 1) * B], p.t_oracle[k * B:(k + 1) * B], masks=p.masks, scale_frames=shard[1] if shard else None)[:2]
+                   for k in ((0,) if acc_double else (0, 1))]
         r.forward = oracle(c, p.W, p.b, acc_double).forward(p.x[:B + 3])
         r.cv = oracle(c, p.W, p.b).crossvalid(p.x, p.t_cv) if p.cv_sum is not None and not acc_double else None
         o.update(r.grads[0][0], r.grads[0][1], B)                  # one step from zero momentum = the update on bunch 0's gradient
@@ -331,17 +350,17 @@ def reference(cid, drop=False, acc_double=False):
     return _REFERENCES[key]
 
 
-def conditions(cid, drop=False):
+def conditions(cid, drop=False, shard=None):
     """(failures, figures) of the conditions (a) - (c) on problem(cid, drop): a list of texts, empty when all hold, and what was
     measured.  A case that is held on the forward and CV only (an fp32 bunch that is no power of two) is asked about its forward
     GEMMs only."""
-    p = problem(cid, drop)
+    p = problem(cid, drop, shard)
     c, B, L = p.c, p.c.B, len(p.c.ls)
     step = steps_exactly(c)
     fails, fig = [], {"max_over_q_log2": 0.0, "q_min_log2": 0, "live": {}, "distinct": {}}
     for k in (0, 1):
         sl = slice(k * B, (k + 1) * B)
-        bu = Bunch(c, p.W, p.b, p.x[sl], p.t_oracle[sl], p.masks)
+        bu = Bunch(c, p.W, p.b, p.x[sl], p.t_oracle[sl], p.masks, shard[1] if shard else None)
         if step and not np.array_equal(bu.dx[L - 1], p.d[sl]):
             fails.append("bunch %d: dEdX_L is not d in %d places" % (k, int((bu.dx[L - 1] != p.d[sl]).sum())))
         for name, A, Bm, add in bu.gemms:
@@ -369,7 +388,7 @@ def conditions(cid, drop=False):
             if zero_blocks(bu.gw[l]):
                 fails.append("(c) bunch %d: G%d has all-zero blocks %s" % (k, l, zero_blocks(bu.gw[l])[:3]))
         # (b), and the restatement above is the oracle's arithmetic
-        r32, r64 = reference(cid, drop), reference(cid, drop, acc_double=True)
+        r32, r64 = reference(cid, drop, shard=shard), reference(cid, drop, acc_double=True, shard=shard)
         for l in range(1, L):
             for name, i, mine in (("G%d" % l, 0, bu.gw[l]), ("gb%d" % l, 1, bu.gb[l])):
                 a = r32.grads[k][i][l]
@@ -378,7 +397,7 @@ def conditions(cid, drop=False):
                     fails.append("(b) bunch %d %s: the oracle's fp32 and fp64 accumulation differ; %s" % (k, name, unequal(name, a, r)))
                 if not np.array_equal(a, mine.astype(np.float32)) or not np.array_equal(mine.astype(np.float32).astype(np.float64), mine):
                     fails.append("bunch %d %s: the float64 restatement is not the oracle's gradient" % (k, name))
-    r32, r64 = reference(cid, drop), reference(cid, drop, acc_double=True)
+    r32, r64 = reference(cid, drop, shard=shard), reference(cid, drop, acc_double=True, shard=shard)
     if not np.array_equal(r32.forward, r64.forward):
         fails.append("(b) forward: " + unequal("forward", r32.forward, r64.forward))
     if p.cv_sum is not None and r32.cv != p.cv_sum:

@@ -78,22 +78,25 @@ def _trajectory(ls, W, b, x, t, B, NS, lr, m, act, lin, loss, drop_seed=None):
     return W64, b64, dW, db
 
 
-def bf16_logistic_grads(ls, W, b, x, t, act=0, lin=0, loss=0, Bg=None):
+def bf16_logistic_grads(ls, W, b, x, t, act=0, lin=0, loss=0, Bg=None, keep=None):
     """One bunch with bf16 STORAGE of everything a GEMM reads (input, hidden outputs, every dEdX_l, the weights) and float64
     arithmetic in between, written out by hand as torch_ref.bf16_grads is: autograd cannot express the rounding of the
-    back-propagated errors.  No dropout.  Returns (gw, gb, ys, y): gradients, hidden outputs and the post-activation output."""
+    back-propagated errors.  No dropout.  Returns (gw, gb, ys, y): gradients, hidden outputs and the post-activation output.
+    keep: the keep-scales of ref_forward (forward and CV of a dropout handle: the fp32 product is scaled in front of the bias; only
+    with t None)."""
     from torch_ref import bf16_round
     L, Bg = len(ls), Bg or x.shape[0]
     Wb = [None] + [bf16_round(W[l]) for l in range(1, L)]
     ys = [bf16_round(np.asarray(x, np.float64))]
     for l in range(1, L):
-        z = ys[l - 1] @ Wb[l] + np.asarray(b[l], np.float64)
+        z = (keep[l] if keep else 1.0) * (ys[l - 1] @ Wb[l]) + np.asarray(b[l], np.float64)
         if l < L - 1:
             ys.append(bf16_round(np.maximum(z, 0.0) if act == 0 else 1.0 / (1.0 + np.exp(-z))))
     y = z.copy()
     y[:, lin:] = 1.0 / (1.0 + np.exp(-z[:, lin:]))
     if t is None:
         return None, None, ys, y
+    assert keep is None, "keep-scaling belongs to forward and CV"
     dx = {L - 1: bf16_round(_dedz(z, np.asarray(t, np.float64), lin, loss, Bg))}
     for l in range(L - 1, 1, -1):
         d = (ys[l - 1] > 0) if act == 0 else ys[l - 1] * (1.0 - ys[l - 1])
@@ -105,8 +108,9 @@ def bf16_logistic_grads(ls, W, b, x, t, act=0, lin=0, loss=0, Bg=None):
 # torch for ROCm maps its own HIP / HSA runtime and RCCL into the process that imports it; a test process that later initialises
 # the product's RCCL transport (tests/test_dp_native.py) then finds no device.  A test file that sorts in front of that one
 # therefore asks a child for the autograd numbers: `python tests/output_ref.py request.npz reply.npz`.
-def in_child(op, ls, W, b, x, t=None, act=0, lin=0, loss=0, B=0, steps=0, lr=1.0, m=0.5):
-    """op "grads": (gw, gb, ys); "forward": y; "train": (W, b, dW, db) after `steps` bunches of B frames (rule 0, no weight cost)."""
+def in_child(op, ls, W, b, x, t=None, act=0, lin=0, loss=0, B=0, steps=0, lr=1.0, m=0.5, keep=None):
+    """op "grads": (gw, gb, ys); "forward": y (keep: the keep-scales of ref_forward); "train": (W, b, dW, db) after `steps` bunches
+    of B frames (rule 0, no weight cost)."""
     import os
     import subprocess
     import sys
@@ -118,6 +122,9 @@ def in_child(op, ls, W, b, x, t=None, act=0, lin=0, loss=0, B=0, steps=0, lr=1.0
         arrs.update({"b%d" % l: np.asarray(b[l], np.float64) for l in range(1, L)})
         if t is not None:
             arrs["t"] = np.asarray(t)
+        if keep is not None:
+            assert op == "forward", op
+            arrs["keep"] = np.asarray([0.0] + list(keep[1:]), np.float64)
         np.savez(req, op=op, ls=np.asarray(ls), x=np.asarray(x), scalars=np.asarray([act, lin, loss, B, steps, lr, m], np.float64), **arrs)
         subprocess.check_call([sys.executable, os.path.abspath(__file__), req, rep])
         r = np.load(rep)
@@ -142,7 +149,7 @@ def _serve(req, rep):
     out = {}
     if op == "forward":
         with torch.no_grad():
-            out["y"] = ref_forward(ls, W, b, x, act=act, lin=lin)[4].numpy()
+            out["y"] = ref_forward(ls, W, b, x, act=act, lin=lin, keep=list(q["keep"]) if "keep" in q.files else None)[4].numpy()
     elif op == "grads":
         gw, gb, ys = ref_grads(ls, W, b, x, q["t"], act=act, lin=lin, loss=loss)
         for l in range(1, L):

@@ -12,7 +12,11 @@ Bars -- none of them new:
   bf16   the formulas of test_bf16_step_matches_bf16_oracle: forward 2e-3 against the bf16 reference, W and b at TOL_BF16 / 4,
          gradients and momentum state 2e-2 rms; cases deeper or wider than that test's add 1.5 x the oracle's spread, the rule of
          test_bf16_config5_shape_one_step.
-  The ignored-frames and padding checks are exact."""
+  The ignored-frames and padding checks are exact.
+
+Two passes turn on switches of the forward epilogues that the 24 cases leave at rest (tests/switch_cases.py has the table): the
+gradient, the fused step and the trajectory once more over dispatch_cases.LOSS1_CASES (output_loss 1 on every logistic output
+kernel), forward and CV once more on a dropout handle (alpha = 1 - omit in every forward kernel).  Same bars."""
 import numpy as np
 import pytest
 
@@ -42,8 +46,8 @@ def worst_block(a, ref):
         r0, c0, d.shape, d.max(), r, c, int((blk > 1e-3 * max(np.abs(ref).max(), 1e-30)).sum()), blk.size)
 
 
-def _mk(pkg, c, W, b, cap):
-    kw = dict(activation=c.act, compute_dtype=c.dtype, max_chunk_frames=cap)
+def _mk(pkg, c, W, b, cap, **extra):
+    kw = dict(activation=c.act, compute_dtype=c.dtype, max_chunk_frames=cap, **extra)
     if c.out is not None:
         kw.update(output_activation=1, output_linear_cols=c.out[0], output_loss=c.out[1])
     return pkg.BP_GPU(1, len(c.ls), c.ls, c.B, LR[c.dtype], MOM, 0.0, W, b, **kw)
@@ -51,8 +55,9 @@ def _mk(pkg, c, W, b, cap):
 
 # ------------------------------------------------------------------ references with one interface
 class OracleRef(object):
-    def __init__(self, oracle_mod, c, W, b, acc_double=False):
-        self.o = oracle_mod.Oracle(c.ls, c.B, LR[c.dtype], MOM, 0.0, W, b, activation=c.act, compute_dtype=c.dtype, acc_double=acc_double)
+    def __init__(self, oracle_mod, c, W, b, acc_double=False, drop=None):
+        self.o = oracle_mod.Oracle(c.ls, c.B, LR[c.dtype], MOM, 0.0, W, b, activation=c.act, compute_dtype=c.dtype, acc_double=acc_double,
+                                   **(drop or {}))
 
     def grads(self, x, t):
         gw, gb, ys, _ = self.o.grads(x, t)
@@ -73,9 +78,10 @@ class LogisticRef(object):
     """float64 state; fp32 cases: torch autograd (output_ref.ref_grads, asked of a child process: output_ref.in_child says why),
     bf16 cases: bf16 storage written out by hand."""
 
-    def __init__(self, c, W, b):
+    def __init__(self, c, W, b, drop=None):
         L = len(c.ls)
         self.c, self.L = c, L
+        self.keep = DC.keep_scales(c, drop) if drop else None          # forward and CV of a dropout handle
         self.W = [None] + [np.asarray(W[l], np.float64).copy() for l in range(1, L)]
         self.b = [None] + [np.asarray(b[l], np.float64).copy() for l in range(1, L)]
         self.dW = [None] + [np.zeros_like(self.W[l]) for l in range(1, L)]
@@ -93,8 +99,8 @@ class LogisticRef(object):
         import output_ref as R
         c = self.c
         if c.dtype == 1:
-            return R.bf16_logistic_grads(c.ls, self.W, self.b, x, None, c.act, c.out[0], c.out[1])[3]
-        return R.in_child("forward", c.ls, self.W, self.b, x, act=c.act, lin=c.out[0])
+            return R.bf16_logistic_grads(c.ls, self.W, self.b, x, None, c.act, c.out[0], c.out[1], keep=self.keep)[3]
+        return R.in_child("forward", c.ls, self.W, self.b, x, act=c.act, lin=c.out[0], keep=self.keep)
 
     def cv(self, x, t):
         return float(((self.forward(x) - t.astype(np.float64)) ** 2).sum())
@@ -114,8 +120,8 @@ class LogisticRef(object):
         return self.W, self.b, self.dW, self.db
 
 
-def _ref(oracle_mod, c, W, b):
-    return OracleRef(oracle_mod, c, W, b) if c.out is None else LogisticRef(c, W, b)
+def _ref(oracle_mod, c, W, b, drop=None):
+    return OracleRef(oracle_mod, c, W, b, drop=drop) if c.out is None else LogisticRef(c, W, b, drop=drop)
 
 
 def _spread_after_training(oracle_mod, c, W, b, x, t):
@@ -152,8 +158,23 @@ def case(request):
     return request.param
 
 
+@pytest.fixture(params=DC.LOSS1_CASES, ids=[c.id for c in DC.LOSS1_CASES])
+def loss1_case(request):
+    """The logistic cases at output_loss 1 (tests/switch_cases.py: the switch `loss`)."""
+    return request.param
+
+
 # ------------------------------------------------------------------ 1. one bunch's gradient through the store kernels
 def test_gradient_store(pkg, oracle_mod, parity_record, case):
+    _gradient_store(pkg, oracle_mod, parity_record, case)
+
+
+def test_gradient_store_loss1(pkg, oracle_mod, parity_record, loss1_case):
+    """The same at output_loss 1: d *= o (1 - o) on the logistic columns of every logistic output kernel; same bars."""
+    _gradient_store(pkg, oracle_mod, parity_record, loss1_case)
+
+
+def _gradient_store(pkg, oracle_mod, parity_record, case):
     """grads_resident + read_grads against the reference's gradient (fp32 handles: every hidden layer's output too), and every pad
     row and pad column of the flat gradient buffer exactly 0.0."""
     c, L = case, len(case.ls)
@@ -196,6 +217,14 @@ def test_gradient_store(pkg, oracle_mod, parity_record, case):
 
 # ------------------------------------------------------------------ 2. one fused step from zero momentum
 def test_fused_step(pkg, oracle_mod, parity_record, case):
+    _fused_step(pkg, oracle_mod, parity_record, case)
+
+
+def test_fused_step_loss1(pkg, oracle_mod, parity_record, loss1_case):
+    _fused_step(pkg, oracle_mod, parity_record, loss1_case)
+
+
+def _fused_step(pkg, oracle_mod, parity_record, case):
     c = case
     W, b, x, t = DC.case_data(c, c.B)
     g = _mk(pkg, c, W, b, cap=c.B)
@@ -210,19 +239,30 @@ def test_fused_step(pkg, oracle_mod, parity_record, case):
 def test_forward_and_cv(pkg, oracle_mod, parity_record, case):
     """Forward on B + 3 frames and CV on a chunk with a partial last bunch (the fp32 forward then launches with fewer rows than
     the padded bunch)."""
+    _forward_and_cv(pkg, oracle_mod, parity_record, case, None)
+
+
+def test_forward_and_cv_keep_scaled(pkg, oracle_mod, parity_record, case):
+    """The same on a handle with dropout configured that never trains: every forward epilogue runs with alpha = 1 - omit (0.9 on
+    the first weight layer, 0.8 on the others).  Reference: the oracle with the same keywords, which scales as
+    test_train_matches_oracle relies on; logistic cases: the keep argument of tests/output_ref.py.  Same bars."""
+    _forward_and_cv(pkg, oracle_mod, parity_record, case, DC.KEEP_DROP)
+
+
+def _forward_and_cv(pkg, oracle_mod, parity_record, case, drop):
     c = case
     n = 2 * c.B + c.B // 2
     W, b, x, t = DC.case_data(c, n)
-    g = _mk(pkg, c, W, b, cap=n)
+    g = _mk(pkg, c, W, b, cap=n, **(dict(drop, seed=41) if drop else {}))
     out = g.forward(x[:c.B + 3])
     cv = g.CrossValid(n, x, t)
     g.close()
-    r = _ref(oracle_mod, c, W, b)
+    r = _ref(oracle_mod, c, W, b, drop)
     ro, rcv = r.forward(x[:c.B + 3]), r.cv(x, t)
     errs = {"forward": relerr(out, ro), "cv_sum": abs(cv - rcv) / abs(rcv)}
     bars = {"forward": TOL, "cv_sum": TOL} if c.dtype == 0 else {"forward": 2e-3, "cv_sum": TOL_BF16}
-    print(c.id, "forward / CV", errs)
-    parity_record(forward_and_cv={"errors": errs, "bars": bars})
+    print(c.id, "forward / CV", "keep-scaled" if drop else "", errs)
+    parity_record(forward_and_cv={"errors": errs, "bars": bars, "keep_scaled": bool(drop)})
     assert errs["forward"] < bars["forward"], (c.id, errs, worst_block(out, ro))
     assert errs["cv_sum"] < bars["cv_sum"], (c.id, errs)
 
@@ -230,6 +270,14 @@ def test_forward_and_cv(pkg, oracle_mod, parity_record, case):
 # ------------------------------------------------------------------ 4. a short trajectory
 def test_short_trajectory(pkg, oracle_mod, parity_record, case):
     """Three bunches plus an ignored partial one."""
+    _short_trajectory(pkg, oracle_mod, parity_record, case)
+
+
+def test_short_trajectory_loss1(pkg, oracle_mod, parity_record, loss1_case):
+    _short_trajectory(pkg, oracle_mod, parity_record, loss1_case)
+
+
+def _short_trajectory(pkg, oracle_mod, parity_record, case):
     c = case
     n = 3 * c.B + c.B // 2
     W, b, x, t = DC.case_data(c, n)

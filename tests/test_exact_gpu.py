@@ -5,7 +5,8 @@ checks them on the CPU.  The cases, nets and bunches are those of tests/dispatch
 Where tests/test_dispatch_gpu.py can only ask 2e-2 rms of a bf16 gradient (two correct bf16 implementations differ by that much),
 these tests ask np.array_equal: an indexing, k-tail, tile-map, k-split, ring or padding defect is an exact mismatch in a nameable
 64 x 64 block.  Held exactly: the gradient through the store kernels (first and second bunch of a chunk), one fused step from zero
-momentum, the forward on the linear columns and the CV sum -- every bf16 case, with dropout on two of them; of the fp32 cases the
+momentum, the forward on the linear columns and the CV sum -- every bf16 case, with dropout on three of them, and the gradient of a shard handle
+at an unaligned rank offset on two; of the fp32 cases the
 forward and CV sum of all, the gradient and step of those whose bunch is a power of two (2/B must be an fp32 number).  A failure
 names the tensor, the worst block, the number of unequal elements, their size in ulps and the first unequal pair as hex words; the
 counts go to the parity record (all zeros when green)."""
@@ -21,9 +22,9 @@ STEP_RUNS = [(cid, drop) for cid, drop in X.exact_runs() if X.steps_exactly(DC.B
 _ids = lambda runs: ["%s%s" % (cid, "-dropout" if drop else "") for cid, drop in runs]
 
 
-def _mk(pkg, p, cap, drop):
+def _mk(pkg, p, cap, drop, **extra):
     c = p.c
-    kw = dict(activation=0, compute_dtype=c.dtype, max_chunk_frames=cap)
+    kw = dict(activation=0, compute_dtype=c.dtype, max_chunk_frames=cap, **extra)
     if c.out is not None:
         kw.update(output_activation=1, output_linear_cols=c.out[0], output_loss=c.out[1])
     if drop:
@@ -67,6 +68,27 @@ def test_gradient_store_is_exact(pkg, oracle_mod, parity_record, cid, drop):
     fails += _gradient_against(g, p, r.grads[1], "second bunch", counts)
     g.close()
     print(cid, "gradient, unequal elements:", counts)
+    parity_record(exact_gradient={"unequal": counts})
+    assert not fails, (cid, fails)
+
+
+@pytest.mark.parametrize("cid", X.SHARD_CASES)
+def test_shard_gradient_store_is_exact(pkg, oracle_mod, parity_record, cid):
+    """The same on a shard handle with dropout: bunch B of a global bunch 2B at rank_frame_offset 3, so the gradient is scaled by
+    2/(2B) and the masks are those of the global frames 3 .. B + 2, drawn through the last two-block branch of drop_words4 in the
+    64-row and both 128-row hidden forwards.  A shard handle trains only through its group: gradient store alone."""
+    shard = X.shard_of(cid)
+    p, r = X.problem(cid, True, shard), X.reference(cid, True, shard=shard)
+    B = p.c.B
+    g = _mk(pkg, p, 2 * B + B // 2, True, global_bunchsize=shard[1], rank_frame_offset=shard[0])
+    counts = {}
+    g.upload_chunk(p.x, p.t)
+    g.grads_resident(0)
+    fails = _gradient_against(g, p, r.grads[0], "first bunch", counts)
+    g.grads_resident(B)
+    fails += _gradient_against(g, p, r.grads[1], "second bunch", counts)
+    g.close()
+    print(cid, "shard gradient at offset %d of a global bunch %d, unequal elements:" % shard, counts)
     parity_record(exact_gradient={"unequal": counts})
     assert not fails, (cid, fails)
 

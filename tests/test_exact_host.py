@@ -26,6 +26,24 @@ def test_conditions_hold(cid, drop):
     assert fig["max_over_q_log2"] < 24 and fig["q_min_log2"] >= -40
 
 
+@pytest.mark.parametrize("cid", X.SHARD_CASES)
+def test_shard_conditions_hold(cid):
+    """The same for the shard problems (scale 2/Bg, masks from rank_frame_offset 3 on), and the data sees the offset: with the
+    masks of offset 0 or 4 the reference gradient is another one in most places of every tensor."""
+    shard = X.shard_of(cid)
+    assert shard[0] & 3 == 3 and shard[1] == 2 * DC.BY_ID[cid].B
+    fails, fig = X.conditions(cid, True, shard)
+    print(cid, "shard", shard, fig)
+    assert not fails, (cid, fails)
+    p, r = X.problem(cid, True, shard), X.reference(cid, True, shard=shard)
+    B = p.c.B
+    for off in (0, 4):
+        gw, gb = X.oracle(p.c, p.W, p.b, drop=True).grads(p.x[:B], p.t_oracle[:B], masks=X.masks(p.c, p.W, p.b, off), scale_frames=shard[1])[:2]
+        for l in range(1, len(p.c.ls)):
+            share = X.count_unequal(gw[l], r.grads[0][0][l]) / float(gw[l].size)
+            assert share > 0.5, (cid, off, l, share)
+
+
 def test_every_case_is_run_and_reaches_its_kernels():
     """Every bf16 case of the table runs gradient, step, forward and CV; ReLU in place of Sigmoid changes no kernel."""
     ran = set(cid for cid, _ in RUNS)
@@ -39,7 +57,7 @@ def test_every_case_is_run_and_reaches_its_kernels():
         else:                                                       # fp32: 2/B has to be an fp32 number with nothing to snap it back
             assert X.steps_exactly(c) == (c.id in X.FP32_STEP_CASES)
             assert c.id not in X.FP32_STEP_CASES or c.B & (c.B - 1) == 0
-    assert all(DC.BY_ID[cid].dtype == 1 for cid in X.DROPOUT_CASES)
+    assert all(DC.BY_ID[cid].dtype == 1 for cid in X.DROPOUT_CASES + X.SHARD_CASES)
 
 
 def test_cv_comparison_is_skipped_by_logistic_cases_only():
