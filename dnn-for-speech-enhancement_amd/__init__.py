@@ -7,6 +7,7 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      BPWaveChunk, BPMixCorpus, MIXTURE_DTYPE, MIX_TARGETS, MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM,
                      MIX_LPS_IBM, mix_plan, mix_shuffle, BPMixReverb, REVERB_TARGETS, REVERB_TARGET_REVERBERANT,
                      REVERB_TARGET_EARLY, MIX_RIR_MAX_TAPS, reverb_waves, rir_delay, mix_reverb_pairs, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
+                     SCORE_ESTOI, SCORE_SISDR,
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
                      LogmmseStream, logmmse_stream_open, logmmse_stream_counts,
                      rir_image, rir_rooms, rir_beta, rir_orders, rir_window_default, BPRirRange, RIR_ROOM_DTYPE, RIR_RANGE_DEFAULTS,

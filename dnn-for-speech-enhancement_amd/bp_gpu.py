@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "bp_set_mix_corpus", "bp_train_mix", "bp_cv_mix", "bp_mix_features", "bp_mix_plan", "bp_mix_shuffle",
     "bp_set_mix_reverb", "bp_reverb_waves", "bp_mix_rir_delay", "bp_mix_reverb_pairs",
     "bp_rir_image", "bp_rir_orders", "bp_rir_beta", "bp_rir_rooms",
-    "bp_score_waves", "bp_eval_mix",
+    "bp_score_waves", "bp_eval_mix", "bp_score_waves_ext", "bp_eval_mix_ext", "bp_eval_mix_logmmse_ext",
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
     "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
@@ -49,6 +49,7 @@ WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
+SCORE_ESTOI, SCORE_SISDR = 3, 4               # the two further columns of the _ext calls (extended=True)
 REVERB_TARGET_REVERBERANT, REVERB_TARGET_EARLY = 0, 1   # bp_mix_reverb.target
 REVERB_TARGETS = {"reverberant": REVERB_TARGET_REVERBERANT, "early": REVERB_TARGET_EARLY}
 MIX_RIR_MAX_TAPS = 65536
@@ -192,6 +193,9 @@ def load_library(path=None):
     lib.bp_rir_rooms.argtypes = [C.c_uint64, C.c_int, C.POINTER(BPRirRange), C.c_void_p]
     lib.bp_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, fp]
     lib.bp_eval_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, fp, fp, fp]
+    lib.bp_score_waves_ext.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), fp, fp, C.c_int, fp]
+    lib.bp_eval_mix_ext.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp]
+    lib.bp_eval_mix_logmmse_ext.argtypes = [hp, C.POINTER(BPLogmmseParams), C.c_int, C.c_void_p, C.c_int, C.c_int, fp, fp, fp]
     lib.bp_logmmse_defaults.argtypes = [C.POINTER(BPLogmmseParams)]
     lib.bp_logmmse_waves.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.c_int, C.POINTER(C.c_int), fp, fp, fp, fp]
     lib.bp_eval_mix_logmmse.argtypes = [hp, C.POINTER(BPLogmmseParams), C.c_int, C.c_void_p, C.c_int, fp, fp, fp]
@@ -562,36 +566,49 @@ class BP_GPU(object):
         out["pcm"] = out["pcm"][:n_pcm]
         return out
 
-    def eval_mix(self, plan, sample_rate, target=WAVE_LPS, out_col=0, return_pcm=False):
+    def eval_mix(self, plan, sample_rate, target=WAVE_LPS, out_col=0, return_pcm=False, extended=False):
         """bp_eval_mix: the plan's mixtures made on the device, enhanced with this net and scored against their clean sentences.
         dict of noisy [n_mix][3] and enhanced [n_mix][3] float32 scores (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where
-        undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None."""
+        undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None.  extended: bp_eval_mix_ext with five
+        columns, SCORE_ESTOI and SCORE_SISDR behind the same three."""
         p, pp = self._plan(plan)
-        noisy = np.empty((max(p.size, 1), 3), np.float32)
-        enh = np.empty((max(p.size, 1), 3), np.float32)
+        ns = 5 if extended else 3
+        noisy = np.empty((max(p.size, 1), ns), np.float32)
+        enh = np.empty((max(p.size, 1), ns), np.float32)
         pcm = None
         if return_pcm and getattr(self, "mix_fea_dim", None) is not None:
             lens = self.mix_clean_len[p["clean"]] if p.size else np.zeros(0, np.int64)
             pcm = np.empty(max(int(lens.sum()), 1), np.float32)
-        self._check(self._lib.bp_eval_mix(self._h, p.size, pp, int(sample_rate), int(target), int(out_col), _fp(noisy), _fp(enh),
-                                          _fp(pcm) if pcm is not None else None))
+        if extended:
+            self._check(self._lib.bp_eval_mix_ext(self._h, p.size, pp, int(sample_rate), int(target), int(out_col), ns, _fp(noisy),
+                                                  _fp(enh), _fp(pcm) if pcm is not None else None))
+        else:
+            self._check(self._lib.bp_eval_mix(self._h, p.size, pp, int(sample_rate), int(target), int(out_col), _fp(noisy), _fp(enh),
+                                              _fp(pcm) if pcm is not None else None))
         if pcm is not None:
             pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
         return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
 
-    def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False):
+    def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False, extended=False):
         """bp_eval_mix_logmmse: eval_mix with the log-MMSE baseline in place of the net (params: None for the defaults, a dict of
-        bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix."""
+        bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix (extended: five columns,
+        bp_eval_mix_logmmse_ext)."""
         p, pp = self._plan(plan)
-        noisy = np.empty((max(p.size, 1), 3), np.float32)
-        enh = np.empty((max(p.size, 1), 3), np.float32)
+        ns = 5 if extended else 3
+        noisy = np.empty((max(p.size, 1), ns), np.float32)
+        enh = np.empty((max(p.size, 1), ns), np.float32)
         pcm = None
         if return_pcm and getattr(self, "mix_fea_dim", None) is not None:
             lens = self.mix_clean_len[p["clean"]] if p.size else np.zeros(0, np.int64)
             pcm = np.empty(max(int(lens.sum()), 1), np.float32)
         lm = logmmse_params(params)
-        self._check(self._lib.bp_eval_mix_logmmse(self._h, None if lm is None else C.byref(lm), p.size, pp, int(sample_rate), _fp(noisy),
-                                                  _fp(enh), _fp(pcm) if pcm is not None else None))
+        lmp = None if lm is None else C.byref(lm)
+        if extended:
+            self._check(self._lib.bp_eval_mix_logmmse_ext(self._h, lmp, p.size, pp, int(sample_rate), ns, _fp(noisy), _fp(enh),
+                                                          _fp(pcm) if pcm is not None else None))
+        else:
+            self._check(self._lib.bp_eval_mix_logmmse(self._h, lmp, p.size, pp, int(sample_rate), _fp(noisy), _fp(enh),
+                                                      _fp(pcm) if pcm is not None else None))
         if pcm is not None:
             pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
         return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
@@ -910,9 +927,10 @@ def logmmse_stream_counts(fea_dim, init_frames, received, ended):
     return _counts3("bp_lmstream_counts", int(fea_dim), int(init_frames), int(received), 1 if ended else 0)
 
 
-def score_waves(device, fea_dim, sample_rate, refs, ests):
+def score_waves(device, fea_dim, sample_rate, refs, ests, extended=False):
     """bp_score_waves: SSNR, LSD and STOI of every estimate against its reference (lists of 1-D arrays, int16 units, pairwise
-    equal lengths), float32 [n][3] (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where undefined).  No handle."""
+    equal lengths), float32 [n][3] (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where undefined).  No handle.  extended:
+    bp_score_waves_ext, float32 [n][5] with SCORE_ESTOI and SCORE_SISDR behind the same three."""
     lib = load_library()
     if len(refs) != len(ests):
         raise BPError("score_waves: %d references but %d estimates" % (len(refs), len(ests)))
@@ -924,9 +942,12 @@ def score_waves(device, fea_dim, sample_rate, refs, ests):
     lens = np.array([a.size for a in r], np.int32)
     rp = np.ascontiguousarray(np.concatenate(r) if r else np.zeros(0, np.float32))
     ep = np.ascontiguousarray(np.concatenate(e) if e else np.zeros(0, np.float32))
-    out = np.empty((max(len(r), 1), 3), np.float32)
-    rc = lib.bp_score_waves(int(device), int(fea_dim), int(sample_rate), len(r), lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(rp),
-                            _fp(ep), _fp(out))
+    out = np.empty((max(len(r), 1), 5 if extended else 3), np.float32)
+    lp = lens.ctypes.data_as(C.POINTER(C.c_int))
+    if extended:
+        rc = lib.bp_score_waves_ext(int(device), int(fea_dim), int(sample_rate), len(r), lp, _fp(rp), _fp(ep), 5, _fp(out))
+    else:
+        rc = lib.bp_score_waves(int(device), int(fea_dim), int(sample_rate), len(r), lp, _fp(rp), _fp(ep), _fp(out))
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return out[:len(r)]

@@ -1,7 +1,8 @@
 // bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 9: objective scores of enhanced speech.  Segmental SNR,
-// log-spectral distortion on the 1d analysis and STOI of estimates against a reference (bp_score_waves here; bp_eval_mix in
-// bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame
-// plan and padded layout from bp_wave.hip (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
+// log-spectral distortion on the 1d analysis and STOI of estimates against a reference, and with five score columns ESTOI and
+// SI-SDR beside them (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions:
+// include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame plan and padded layout from bp_wave.hip
+// (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
 //
 // Kernels (signal 0 is the reference, 1 .. nsig-1 the estimates; blockIdx.y picks the signal; a flat grid of workgroups finds its
 // sentence by a binary search over a prefix table, as bp_wave_analysis does over F):
@@ -13,7 +14,11 @@
 //   bp_eval_corr      per (segment, band) pair of an estimate: the clipped, normalised correlation over 30 frames, in double
 //   bp_eval_ssnr      one wave64 per SSNR frame of an estimate: E_s, E_d in double, the clamped frame SNR
 //   bp_eval_lsd       one wave64 per analysis frame of an estimate: the RMS of the dB difference of the two LPS rows, in double
-//   bp_eval_reduce    one workgroup per (sentence, estimate): the three means in double (strided sums, a fixed LDS tree)
+//   bp_eval_estoi     five columns only, one wave64 per segment: the 15 x 30 envelope matrices of every signal in LDS, rows then
+//                     columns normalised in double (the reference's once), d_m of every estimate (a fixed shuffle tree)
+//   bp_eval_sisdr     five columns only, one workgroup per (sentence, estimate): rr, er, then with alpha num, den -- two passes
+//                     over the samples in double (strided sums, a fixed LDS tree)
+//   bp_eval_reduce    one workgroup per (sentence, estimate): the means in double (strided sums, a fixed LDS tree), one score row
 //   bp_eval_trim      per padded sample: zero outside the sentence (the overlap-add output, before it is analysed)
 // No float atomics and no cross-workgroup hand-off inside a kernel: the same bits on every run.
 #include <hip/hip_runtime.h>
@@ -48,7 +53,8 @@ struct EvalArgs {
     float *comp; size_t scomp;                               // [sig][Q[n]]
     float *band; size_t sband;                               // [sig][P[n]][EV_BS]
     double *rho, *ssnr, *lsd; size_t srho, sssnr, slsd;      // [est][CP[n]], [est][SJ[n]], [est][F[n]]
-    float *scores;                                           // [est][n][BP_SCORE_N]
+    double *dm, *sdr; size_t sdm; int nsig;                  // five columns: [est][CP[n] / 15], [est][n]
+    float *scores; int ns;                                   // [est][n][ns]
 };
 
 __device__ __forceinline__ double wave_sum(double x)
@@ -198,28 +204,114 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lsd(const EvalArgs a)
     if (ln == 0) a.lsd[(e - 1) * a.slsd + g] = sqrt(acc / a.D);
 }
 
+// segment g of the call (CP / 15 is the segment prefix): m = 29 + g - CP[s] / 15 is its last frame; signal k's matrix lies in
+// LDS as mat[k][u][b] with a row of EV_MS doubles per frame u (17: the column step's stride of 34 banks meets every bank pair once)
+constexpr int EV_MS = 17, EV_MAT = EV_SEG * EV_MS;
+__global__ __launch_bounds__(64) void bp_eval_estoi(const EvalArgs a)
+{
+    __shared__ double mat[EVAL_MAXSIG * EV_MAT];
+    const int g = blockIdx.x, s = sentence_of(a.CP, a.n, EV_NB * g), i = g - a.CP[s] / EV_NB, ln = threadIdx.x;
+    if (i + EV_SEG - 1 >= a.C[s] - 1) return;                       // (the whole wave64: the barriers below are met by all or none)
+    const float *X = a.band + (size_t)(a.P[s] + i) * EV_BS;
+    for (int t = ln; t < a.nsig * EV_SEG * EV_BS; t += 64) {
+        const int k = t / (EV_SEG * EV_BS), r = t % (EV_SEG * EV_BS), u = r / EV_BS, b = r % EV_BS;
+        if (b < EV_NB) mat[k * EV_MAT + u * EV_MS + b] = (double)X[k * a.sband + r];
+    }
+    __syncthreads();
+    for (int t = ln; t < a.nsig * EV_NB; t += 64) {                 // rows: band b of signal k over the 30 frames
+        double *x = mat + (t / EV_NB) * EV_MAT + t % EV_NB;
+        double m = 0.0, q = 0.0;
+        for (int u = 0; u < EV_SEG; ++u) m += x[u * EV_MS];
+        m /= EV_SEG;
+        for (int u = 0; u < EV_SEG; ++u) { const double d = x[u * EV_MS] - m; x[u * EV_MS] = d; q += d * d; }
+        q = sqrt(q) + EV_EPS;
+        for (int u = 0; u < EV_SEG; ++u) x[u * EV_MS] /= q;
+    }
+    __syncthreads();
+    for (int t = ln; t < a.nsig * EV_SEG; t += 64) {                // columns: frame u of signal k over the 15 bands
+        double *x = mat + (t / EV_SEG) * EV_MAT + (t % EV_SEG) * EV_MS;
+        double m = 0.0, q = 0.0;
+        for (int b = 0; b < EV_NB; ++b) m += x[b];
+        m /= EV_NB;
+        for (int b = 0; b < EV_NB; ++b) { const double d = x[b] - m; x[b] = d; q += d * d; }
+        q = sqrt(q) + EV_EPS;
+        for (int b = 0; b < EV_NB; ++b) x[b] /= q;
+    }
+    __syncthreads();
+    for (int e = 1; e < a.nsig; ++e) {
+        double d = 0.0;
+        for (int t = ln; t < EV_SEG * EV_NB; t += 64) {
+            const int at = (t / EV_NB) * EV_MS + t % EV_NB;
+            d += mat[at] * mat[e * EV_MAT + at];
+        }
+        d = wave_sum(d);
+        if (ln == 0) a.dm[(e - 1) * a.sdm + a.CP[s] / EV_NB + i] = d / EV_SEG;
+    }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_sisdr(const EvalArgs a)
+{
+    __shared__ double red[2][WAVE_THREADS];
+    const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, n = a.len[s];
+    const float *r = a.sig[0] + a.off[s], *x = a.sig[e] + a.off[s];
+    double al = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {                          // 0: rr, er; 1: num, den (the residual itself, no cancellation)
+        double q0 = 0.0, q1 = 0.0;
+        for (int i = tid; i < n; i += WAVE_THREADS) {
+            const double rv = r[i], xv = x[i];
+            if (pass == 0) { q0 += rv * rv; q1 += xv * rv; }
+            else { const double t = al * rv, d = t - xv; q0 += t * t; q1 += d * d; }
+        }
+        red[0][tid] = q0; red[1][tid] = q1;
+        __syncthreads();
+        for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+            if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; }
+            __syncthreads();
+        }
+        q0 = red[0][0]; q1 = red[1][0];
+        __syncthreads();                                            // (read before pass 1 writes red again)
+        if (pass == 0) {
+            if (q0 == 0.0) {                                        // a silent reference (uniform over the workgroup)
+                if (tid == 0) a.sdr[(size_t)(e - 1) * a.n + s] = __longlong_as_double(0x7ff8000000000000LL);
+                return;
+            }
+            al = q1 / q0;
+        } else if (tid == 0)
+            a.sdr[(size_t)(e - 1) * a.n + s] = 10.0 * log10(q0 / (q1 + EV_EPS) + EV_EPS);
+    }
+}
+
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_reduce(const EvalArgs a)
 {
-    __shared__ double red[3][WAVE_THREADS];
+    __shared__ double red[4][WAVE_THREADS];
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x;
     const int J = a.SJ[s + 1] - a.SJ[s], T = a.F[s + 1] - a.F[s], S = a.C[s] - 1, np = S >= EV_SEG ? EV_NB * (S - (EV_SEG - 1)) : 0;
     const double *ss = a.ssnr + (e - 1) * a.sssnr + a.SJ[s], *ls = a.lsd + (e - 1) * a.slsd + a.F[s], *rh = a.rho + (e - 1) * a.srho + a.CP[s];
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0;
+    const bool ext = a.ns == BP_SCORE_EXT_N;
+    const int nd = ext ? np / EV_NB : 0;                            // the S - 29 segments
+    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
     for (int i = tid; i < J; i += WAVE_THREADS) q0 += ss[i];
     for (int i = tid; i < T; i += WAVE_THREADS) q1 += ls[i];
     for (int i = tid; i < np; i += WAVE_THREADS) q2 += rh[i];
-    red[0][tid] = q0; red[1][tid] = q1; red[2][tid] = q2;
+    for (int i = tid; i < nd; i += WAVE_THREADS) q3 += a.dm[(e - 1) * a.sdm + a.CP[s] / EV_NB + i];
+    red[0][tid] = q0; red[1][tid] = q1; red[2][tid] = q2; red[3][tid] = q3;
     __syncthreads();
     for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; red[2][tid] += red[2][tid + w]; }
+        if (tid < w) {
+            red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; red[2][tid] += red[2][tid + w]; red[3][tid] += red[3][tid + w];
+        }
         __syncthreads();
     }
     if (tid == 0) {
         const float nan = __int_as_float(0x7fc00000);
-        float *o = a.scores + ((size_t)(e - 1) * a.n + s) * BP_SCORE_N;
+        float *o = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
         o[BP_SCORE_SSNR] = J >= 1 ? (float)(red[0][0] / J) : nan;
         o[BP_SCORE_LSD] = T >= 1 ? (float)(red[1][0] / T) : nan;
         o[BP_SCORE_STOI] = np > 0 ? (float)(red[2][0] / np) : nan;
+        if (ext) {
+            o[BP_SCORE_ESTOI] = nd > 0 ? (float)(red[3][0] / nd) : nan;
+            o[BP_SCORE_SISDR] = (float)a.sdr[(size_t)(e - 1) * a.n + s];
+        }
     }
 }
 
@@ -268,7 +360,7 @@ double bessel_i0(double x)
 }
 
 // Work block layout for nsig signals.
-struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, bytes; size_t s10, scomp, sband, srho, sssnr, slsd; };
+struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
 WorkLayout work_layout(const EvalPlan &ep, int nsig)
 {
     WorkLayout w;
@@ -285,6 +377,10 @@ WorkLayout work_layout(const EvalPlan &ep, int nsig)
     w.rho = lay.take(ne * w.srho * 8);
     w.ssnr = lay.take(ne * w.sssnr * 8);
     w.lsd = lay.take(ne * w.slsd * 8);
+    w.sdm = (size_t)ep.CP[n] / EV_NB;                               // five columns only (a part of 0 bytes takes no room)
+    const bool ext = ep.ns == BP_SCORE_EXT_N;
+    w.dm = lay.take(ext ? ne * w.sdm * 8 : 0);
+    w.sdr = lay.take(ext ? (size_t)ne * n * 8 : 0);
     w.bytes = lay.size();
     return w;
 }
@@ -300,12 +396,18 @@ bool eval_rate(int fs, int *p, int *q)
     return *p <= 32 && *q <= 32;
 }
 
-int eval_plan(const char *who, int fs, int fea_dim, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep)
+int eval_n_scores(const char *who, int n_scores)
+{
+    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N) return BP_OK;
+    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N or BP_SCORE_EXT_N");
+}
+
+int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep)
 {
     if (!eval_rate(fs, &ep.p, &ep.q))
         return fail(BP_ERR_ARG, std::string(who) + ": sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32 "
                                                    "(8, 10, 12, 16, 20, 24, 32, 48 kHz)");
-    ep.n = n; ep.fs = fs; ep.D = fea_dim;
+    ep.n = n; ep.fs = fs; ep.D = fea_dim; ep.ns = n_scores;
     const int m = ep.p > ep.q ? ep.p : ep.q;
     ep.Lh = ep.p == 1 && ep.q == 1 ? 0 : 10 * m;                 // 10 kHz in: a copy (one tap of 1)
     ep.taps = 2 * ep.Lh + 1;
@@ -391,7 +493,8 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
     a.rho = (double *)(d.work + w.rho); a.srho = w.srho;
     a.ssnr = (double *)(d.work + w.ssnr); a.sssnr = w.sssnr;
     a.lsd = (double *)(d.work + w.lsd); a.slsd = w.slsd;
-    a.scores = d.scores;
+    a.dm = (double *)(d.work + w.dm); a.sdm = w.sdm; a.sdr = (double *)(d.work + w.sdr); a.nsig = nsig;
+    a.scores = d.scores; a.ns = ep.ns;
     const int n = ep.n, ne = nsig - 1;
     const dim3 blk(WAVE_THREADS);
     // (grids that can be empty -- no STOI or SSNR frame in the whole call -- are skipped)
@@ -405,6 +508,10 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
     if (ep.cb[n]) hipLaunchKernelGGL(bp_eval_corr, dim3((unsigned)ep.cb[n], (unsigned)ne), blk, 0, st, a);
     if (ep.sb[n]) hipLaunchKernelGGL(bp_eval_ssnr, dim3((unsigned)ep.sb[n], (unsigned)ne), blk, 0, st, a);
     hipLaunchKernelGGL(bp_eval_lsd, dim3((unsigned)((ep.F[n] + 3) / 4), (unsigned)ne), blk, 0, st, a);
+    if (ep.ns == BP_SCORE_EXT_N) {
+        if (ep.CP[n]) hipLaunchKernelGGL(bp_eval_estoi, dim3((unsigned)(ep.CP[n] / EV_NB)), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(bp_eval_sisdr, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    }
     hipLaunchKernelGGL(bp_eval_reduce, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
     return hipGetLastError();
 }
@@ -417,13 +524,14 @@ hipError_t eval_trim_launch(const EvalPlan &ep, const char *tab, int hop, float 
     return hipGetLastError();
 }
 
-extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
-                              float *scores)
+// bp_score_waves (n_scores = BP_SCORE_N) and bp_score_waves_ext: one sequence, the score stride apart
+static int score_waves_run(const char *who, int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref,
+                           const float *est, int n_scores, float *scores)
 {
-    const char *who = "bp_score_waves";
-    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, "bp_score_waves: 2*(fea_dim-1) must be a power of two from 64 to 2048");
-    { int p, q; if (!eval_rate(sample_rate, &p, &q)) return fail(BP_ERR_ARG, "bp_score_waves: sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32"); }
-    if (!est || !scores) return fail(BP_ERR_ARG, "bp_score_waves: no sentences or null pointer");
+    { const int r = eval_n_scores(who, n_scores); if (r != BP_OK) return r; }
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    { int p, q; if (!eval_rate(sample_rate, &p, &q)) return fail(BP_ERR_ARG, std::string(who) + ": sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32"); }
+    if (!est || !scores) return fail(BP_ERR_ARG, std::string(who) + ": no sentences or null pointer");
     WavePlan wp;
     { const int r = plan_waves(who, fea_dim, n_sent, sent_len, ref, (size_t)INT32_MAX / 8, wp); if (r != BP_OK) return r; }
     const int D = fea_dim;
@@ -431,13 +539,13 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
     std::vector<int64_t> off(n_sent);
     for (int s = 0; s < n_sent; ++s) off[s] = ((int64_t)wp.F[s] + s + 1) * wp.hop;   // the padded layout of bp_wave_lps
     EvalPlan ep;
-    { const int r = eval_plan(who, sample_rate, D, n_sent, sent_len, off.data(), wp.F.data(), ep); if (r != BP_OK) return r; }
+    { const int r = eval_plan(who, sample_rate, D, n_scores, n_sent, sent_len, off.data(), wp.F.data(), ep); if (r != BP_OK) return r; }
     // one host->device block: tables | analysis window | twiddles | padded reference | padded estimate
     Layout lay(al256(ep.t_bytes));
     const size_t o_win = lay.take((size_t)wp.N * 4), o_tw = lay.take((size_t)(wp.M + 1) * 8), o_ref = lay.take(padded * 4);
     const size_t o_est = lay.take(padded * 4), in_b = lay.size();
     // behind it: the two LPS blocks | scores | work block
-    const size_t lps_b = f * D * 4, o_lps = lay.take(lps_b), o_lps1 = lay.take(lps_b), o_sc = lay.take((size_t)n_sent * BP_SCORE_N * 4);
+    const size_t lps_b = f * D * 4, o_lps = lay.take(lps_b), o_lps1 = lay.take(lps_b), o_sc = lay.take((size_t)n_sent * n_scores * 4);
     const size_t o_work = lay.size();
     OneShot os;
     { const int r = os.open(who, device, o_work + eval_work_bytes(ep, 2)); if (r != BP_OK) return r; }
@@ -465,6 +573,18 @@ extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_se
         v.scores = (float *)(d + o_sc);
         e = eval_launch(ep, v, 2, os.st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(scores, d + o_sc, (size_t)n_sent * BP_SCORE_N * 4, hipMemcpyDeviceToHost, os.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(scores, d + o_sc, (size_t)n_sent * n_scores * 4, hipMemcpyDeviceToHost, os.st);
     return os.finish(who);
+}
+
+extern "C" int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
+                              float *scores)
+{
+    return score_waves_run("bp_score_waves", device, fea_dim, sample_rate, n_sent, sent_len, ref, est, BP_SCORE_N, scores);
+}
+
+extern "C" int bp_score_waves_ext(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref,
+                                  const float *est, int n_scores, float *scores)
+{
+    return score_waves_run("bp_score_waves_ext", device, fea_dim, sample_rate, n_sent, sent_len, ref, est, n_scores, scores);
 }

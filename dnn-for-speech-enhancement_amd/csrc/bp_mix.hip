@@ -699,7 +699,7 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
 // bp_eval_mix (lm == null: the net's output columns [out_col, out_col + D) as `target`) and bp_eval_mix_logmmse (lm: the checked
 // parameters; the gain rows of the recursion as BP_WAVE_MASK): one sequence, one enhancer swapped for the other
 static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const Call &c, const bp_mixture *m, int sample_rate, int target,
-                        int out_col, float *noisy_scores, float *enh_scores, float *enh_pcm)
+                        int out_col, int NS, float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
     int r;
     const int n_mix = c.n;
@@ -710,10 +710,10 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     std::vector<int64_t> off(n_mix);
     for (int i = 0; i < n_mix; ++i) { len[i] = (int)ms->clean_len[m[i].clean]; off[i] = ((int64_t)c.Fs[i] + 1) * hop; }
     EvalPlan ep;
-    if ((r = eval_plan(who, sample_rate, D, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
+    if ((r = eval_plan(who, sample_rate, D, NS, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
     HIPCHK(hipSetDevice(h->cfg.device));
     // every buffer first (a growth waits for the stream), then the sequence without a host wait
-    const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * BP_SCORE_N * 4;
+    const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * NS * 4;
     r = wave_grow(h, {{ms->ev_Y, c.frames * D * sizeof(float2), false}, {ms->ev_syn, c.frames * 2 * hop * 4, false}, {ms->ev_ola, pcm_b, false},
                       {ms->ev_lps, 2 * lps_b, false}, {ms->ev_tab, ep.t_bytes + sc_b, false}, {ms->ev_work, eval_work_bytes(ep, 3), false},
                       {ms->ev_pin, ep.t_bytes, true}, {ms->lps, c.frames * D * 4, false},
@@ -756,12 +756,12 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
         d.scores = (float *)(tab + al256(ep.t_bytes));
         HIPCHK(eval_launch(ep, d, 3, h->stream));
     }
-    std::vector<float> sc((size_t)2 * n_mix * BP_SCORE_N), pcm(enh_pcm ? c.segs * hop : 0);
+    std::vector<float> sc((size_t)2 * n_mix * NS), pcm(enh_pcm ? c.segs * hop : 0);
     HIPCHK(hipMemcpyAsync(sc.data(), tab + al256(ep.t_bytes), sc_b, hipMemcpyDeviceToHost, h->stream));
     if (enh_pcm) HIPCHK(hipMemcpyAsync(pcm.data(), ola, pcm_b, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(noisy_scores, sc.data(), (size_t)n_mix * BP_SCORE_N * 4);
-    memcpy(enh_scores, sc.data() + (size_t)n_mix * BP_SCORE_N, (size_t)n_mix * BP_SCORE_N * 4);
+    memcpy(noisy_scores, sc.data(), (size_t)n_mix * NS * 4);
+    memcpy(enh_scores, sc.data() + (size_t)n_mix * NS, (size_t)n_mix * NS * 4);
     if (enh_pcm) {
         size_t dst = 0;
         for (int i = 0; i < n_mix; ++i) { memcpy(enh_pcm + dst, pcm.data() + off[i], (size_t)len[i] * 4); dst += (size_t)len[i]; }
@@ -769,26 +769,52 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     return BP_OK;
 }
 
-extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
-                           float *enh_scores, float *enh_pcm)
+// bp_eval_mix (n_scores = BP_SCORE_N) and bp_eval_mix_ext
+static int eval_mix_net(const char *who, bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, int n_scores,
+                        float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
     Call c;
     int r;
-    if ((r = plan_call(h, "bp_eval_mix", n_mix, m, c)) != BP_OK) return r;
+    if ((r = eval_n_scores(who, n_scores)) != BP_OK || (r = plan_call(h, who, n_mix, m, c)) != BP_OK) return r;
     const int D = h->mix->D, sL = h->s[h->L - 1];
-    if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_eval_mix: target must be BP_WAVE_LPS or BP_WAVE_MASK");
-    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, "bp_eval_mix: out_col + fea_dim exceeds layersizes[last]");
-    return eval_mix_run("bp_eval_mix", h, nullptr, c, m, sample_rate, target, out_col, noisy_scores, enh_scores, enh_pcm);
+    if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, std::string(who) + ": target must be BP_WAVE_LPS or BP_WAVE_MASK");
+    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, std::string(who) + ": out_col + fea_dim exceeds layersizes[last]");
+    return eval_mix_run(who, h, nullptr, c, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
+}
+
+// bp_eval_mix_logmmse (n_scores = BP_SCORE_N) and bp_eval_mix_logmmse_ext
+static int eval_mix_lm(const char *who, bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate, int n_scores,
+                       float *noisy_scores, float *enh_scores, float *enh_pcm)
+{
+    Call c;
+    LogmmseP lp;
+    int r;
+    if ((r = eval_n_scores(who, n_scores)) != BP_OK || (r = logmmse_check(who, p, lp)) != BP_OK || (r = plan_call(h, who, n_mix, m, c)) != BP_OK) return r;
+    return eval_mix_run(who, h, &lp, c, m, sample_rate, BP_WAVE_MASK, 0, n_scores, noisy_scores, enh_scores, enh_pcm);
+}
+
+extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
+                           float *enh_scores, float *enh_pcm)
+{
+    return eval_mix_net("bp_eval_mix", h, n_mix, m, sample_rate, target, out_col, BP_SCORE_N, noisy_scores, enh_scores, enh_pcm);
+}
+
+extern "C" int bp_eval_mix_ext(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, int n_scores,
+                               float *noisy_scores, float *enh_scores, float *enh_pcm)
+{
+    return eval_mix_net("bp_eval_mix_ext", h, n_mix, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_eval_mix_logmmse(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
                                    float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
-    Call c;
-    LogmmseP lp;
-    int r;
-    if ((r = logmmse_check("bp_eval_mix_logmmse", p, lp)) != BP_OK || (r = plan_call(h, "bp_eval_mix_logmmse", n_mix, m, c)) != BP_OK) return r;
-    return eval_mix_run("bp_eval_mix_logmmse", h, &lp, c, m, sample_rate, BP_WAVE_MASK, 0, noisy_scores, enh_scores, enh_pcm);
+    return eval_mix_lm("bp_eval_mix_logmmse", h, p, n_mix, m, sample_rate, BP_SCORE_N, noisy_scores, enh_scores, enh_pcm);
+}
+
+extern "C" int bp_eval_mix_logmmse_ext(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate, int n_scores,
+                                       float *noisy_scores, float *enh_scores, float *enh_pcm)
+{
+    return eval_mix_lm("bp_eval_mix_logmmse_ext", h, p, n_mix, m, sample_rate, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const int64_t *noise_len, int n_snr,

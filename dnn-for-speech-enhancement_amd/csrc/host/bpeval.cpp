@@ -1,12 +1,14 @@
 // bpeval.cpp -- objective scores of enhanced speech on the MI355X: segmental SNR, log-spectral distortion and
-// STOI, through bp_eval_mix (a test set mixed on the GPU and enhanced with a trained net) or bp_score_waves (pairs of WAVs).
+// STOI, through bp_eval_mix (a test set mixed on the GPU and enhanced with a trained net) or bp_score_waves (pairs of WAVs); with
+// scores=extended ESTOI and SI-SDR beside them, through the _ext calls.
 //
 //   bpeval clean_list=test_clean.list noise_list=test_noise.list norm_file=x.norm initwts_file=mlp.N.wts fea_dim=129 fea_context=11
 //          targ_offset=5 layersizes=1548,2048,2048,2048,129 [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [init_randem_seed=0]
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
-//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt]
+//          [scores=basic|extended]
+//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended]
 //
 // Test-set mode: the plan is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list), cut into calls
 // of at most traincache rows (frames + n_mix (context-1)) in plan order, as bpmix cuts it; every WAV must have the same rate.
@@ -16,6 +18,9 @@
 // checked before the device is used.  baseline=logmmse (test-set mode only) scores the classic log-MMSE enhancer on the same
 // mixtures beside the net (bp_eval_mix_logmmse): after every stdout line a second one with `logmmse:` in place of
 // the net's figures (noisy -> logmmse), and three more columns `ssnr_lm lsd_lm stoi_lm` at the end of every scores_out line.
+// scores=extended (default basic: the output above, byte for byte): every stdout line gains `, ESTOI a -> b, SI-SDR a -> b dB` before
+// the undefined count, which then counts the NaN of all five columns; scores_out lines gain `estoi_noisy estoi_enh sisdr_noisy
+// sisdr_enh` behind stoi_enh, the baseline's `estoi_lm sisdr_lm` behind its three, and pairs mode `estoi sisdr` behind stoi.
 // rir_list: one room impulse response per WAV, at the rate of the others; clean sentence c is paired with response
 // bp_mix_reverb_pairs(init_randem_seed, ...)[c], the plan addresses the derived entry n_clean + c in place of c (so scores_out
 // lists it), the mixtures are reverberant and the scores are taken against reverb_target: the reverberant sentence or its direct
@@ -55,6 +60,7 @@ struct Params {
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
     bool net_keys = false;                                   // a key of test-set mode was given
     int baseline = 0;                                        // baseline=logmmse
+    int ext = 0;                                             // scores=extended: five score columns
     RirKeys rir;                                             // rir_rooms=N ...: simulated responses in place of rir_list
 };
 
@@ -65,6 +71,7 @@ Params parse(int argc, char **argv)
         {"pairs_list", K_STR, &P.pairs_list}, {"scores_out", K_STR, &P.scores_out},
         {"fea_dim", K_INT, &P.fea_dim, 1, 1 << 20},
         {"device", K_INT, &P.device, 0, 1023},
+        {"scores", K_CHOICE, &P.ext, 0, 0, "basic|extended"},
     };
     const Key keys[] = {
         {"clean_list", K_STR, &P.clean_list}, {"noise_list", K_STR, &P.noise_list}, {"norm_file", K_STR, &P.norm_file},
@@ -111,18 +118,21 @@ void check_rate(int fs)
         fail("bpeval: " + std::to_string(fs) + " Hz is not a scoring rate (8, 10, 12, 16, 20, 24, 32, 48 kHz)");
 }
 
-// mean over the finite values; NaN count
-struct Acc { double sum[BP_SCORE_N * 2] = {0}; int cnt[BP_SCORE_N * 2] = {0}, n = 0, nan = 0; };
-void add(Acc &a, const float *noisy, const float *enh)
+// mean over the finite values; NaN count.  Slot k < BP_SCORE_EXT_N: column k of the noisy side, BP_SCORE_EXT_N + k: of the enhanced
+// side; ns: the columns the rows have
+struct Acc { double sum[BP_SCORE_EXT_N * 2] = {0}; int cnt[BP_SCORE_EXT_N * 2] = {0}, n = 0, nan = 0; };
+void add(Acc &a, int ns, const float *noisy, const float *enh)
 {
     ++a.n;
-    for (int k = 0; k < 2 * BP_SCORE_N; ++k) {
-        const float v = k < BP_SCORE_N ? noisy[k] : enh[k - BP_SCORE_N];
-        if (std::isnan(v)) { ++a.nan; continue; }
-        a.sum[k] += v; ++a.cnt[k];
-    }
+    for (int side = 0; side < 2; ++side)
+        for (int k = 0; k < ns; ++k) {
+            const float v = side ? enh[k] : noisy[k];
+            if (std::isnan(v)) { ++a.nan; continue; }
+            a.sum[side * BP_SCORE_EXT_N + k] += v; ++a.cnt[side * BP_SCORE_EXT_N + k];
+        }
 }
 double avg(const Acc &a, int k) { return a.cnt[k] ? a.sum[k] / a.cnt[k] : NAN; }
+double avg_enh(const Acc &a, int k) { return avg(a, BP_SCORE_EXT_N + k); }
 
 int pairs_mode(const Params &P)
 {
@@ -146,17 +156,22 @@ int pairs_mode(const Params &P)
     check_rate(rate);
     FILE *fo = nullptr;
     if (!P.scores_out.empty() && !(fo = fopen(P.scores_out.c_str(), "wt"))) fail("can not open scores file: " + P.scores_out);
-    std::vector<float> sc(lens.size() * BP_SCORE_N);
-    check(bp_score_waves(P.device, P.fea_dim, rate, (int)lens.size(), lens.data(), r.data(), e.data(), sc.data()));
+    const int ns = P.ext ? (int)BP_SCORE_EXT_N : (int)BP_SCORE_N;
+    std::vector<float> sc(lens.size() * ns);
+    if (P.ext) check(bp_score_waves_ext(P.device, P.fea_dim, rate, (int)lens.size(), lens.data(), r.data(), e.data(), ns, sc.data()));
+    else check(bp_score_waves(P.device, P.fea_dim, rate, (int)lens.size(), lens.data(), r.data(), e.data(), sc.data()));
     Acc a;
     for (size_t i = 0; i < lens.size(); ++i) {
-        const float *s = &sc[i * BP_SCORE_N];
-        add(a, s, s);
-        if (fo) fprintf(fo, "%s %s %.9g %.9g %.9g\n", refs[i].c_str(), ests[i].c_str(), s[0], s[1], s[2]);
+        const float *s = &sc[i * ns];
+        add(a, ns, s, s);
+        if (fo) fprintf(fo, "%s %s %.9g %.9g %.9g", refs[i].c_str(), ests[i].c_str(), s[0], s[1], s[2]);
+        if (fo && P.ext) fprintf(fo, " %.9g %.9g", s[BP_SCORE_ESTOI], s[BP_SCORE_SISDR]);
+        if (fo) fprintf(fo, "\n");
     }
     if (fo) fclose(fo);
-    printf("pairs: %d pairs, SSNR %.3f dB, LSD %.3f dB, STOI %.4f (%d undefined)\n", a.n, avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD),
-           avg(a, BP_SCORE_STOI), a.nan / 2);
+    printf("pairs: %d pairs, SSNR %.3f dB, LSD %.3f dB, STOI %.4f", a.n, avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_STOI));
+    if (P.ext) printf(", ESTOI %.4f, SI-SDR %.3f dB", avg(a, BP_SCORE_ESTOI), avg(a, BP_SCORE_SISDR));
+    printf(" (%d undefined)\n", a.nan / 2);
     return 1;
 }
 
@@ -224,48 +239,53 @@ int main(int argc, char **argv)
     std::map<float, Acc> by_snr, by_snr_lm;
     Acc all, all_lm;
     std::vector<float> ns, es, ls;
+    const int NS = P.ext ? (int)BP_SCORE_EXT_N : (int)BP_SCORE_N;
     for (const auto &c : calls) {
         const int n = c.second - c.first;
-        ns.resize((size_t)n * BP_SCORE_N); es.resize((size_t)n * BP_SCORE_N);
-        check(bp_eval_mix(h, n, plan.data() + c.first, rate, P.wave_target, P.out_col, ns.data(), es.data(), nullptr));
+        const bp_mixture *pm = plan.data() + c.first;
+        ns.resize((size_t)n * NS); es.resize((size_t)n * NS);
+        if (P.ext) check(bp_eval_mix_ext(h, n, pm, rate, P.wave_target, P.out_col, NS, ns.data(), es.data(), nullptr));
+        else check(bp_eval_mix(h, n, pm, rate, P.wave_target, P.out_col, ns.data(), es.data(), nullptr));
         if (P.baseline) {                                    // (its noisy scores are those of bp_eval_mix: ns is written twice)
-            ls.resize((size_t)n * BP_SCORE_N);
-            check(bp_eval_mix_logmmse(h, nullptr, n, plan.data() + c.first, rate, ns.data(), ls.data(), nullptr));
+            ls.resize((size_t)n * NS);
+            if (P.ext) check(bp_eval_mix_logmmse_ext(h, nullptr, n, pm, rate, NS, ns.data(), ls.data(), nullptr));
+            else check(bp_eval_mix_logmmse(h, nullptr, n, pm, rate, ns.data(), ls.data(), nullptr));
         }
         for (int i = 0; i < n; ++i) {
             const bp_mixture &m = plan[c.first + i];
-            const float *a = &ns[(size_t)i * BP_SCORE_N], *b = &es[(size_t)i * BP_SCORE_N];
-            add(by_snr[m.snr_db], a, b); add(all, a, b);
+            const float *a = &ns[(size_t)i * NS], *b = &es[(size_t)i * NS];
+            add(by_snr[m.snr_db], NS, a, b); add(all, NS, a, b);
             if (fo)
                 fprintf(fo, "%d %d %lld %.9g %.9g %.9g %.9g %.9g %.9g %.9g", m.clean, m.noise, (long long)m.offset, m.snr_db,
                         a[BP_SCORE_SSNR], b[BP_SCORE_SSNR], a[BP_SCORE_LSD], b[BP_SCORE_LSD], a[BP_SCORE_STOI], b[BP_SCORE_STOI]);
+            if (fo && P.ext) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_ESTOI], b[BP_SCORE_ESTOI], a[BP_SCORE_SISDR], b[BP_SCORE_SISDR]);
             if (P.baseline) {
-                const float *l = &ls[(size_t)i * BP_SCORE_N];
-                add(by_snr_lm[m.snr_db], a, l); add(all_lm, a, l);
+                const float *l = &ls[(size_t)i * NS];
+                add(by_snr_lm[m.snr_db], NS, a, l); add(all_lm, NS, a, l);
                 if (fo) fprintf(fo, " %.9g %.9g %.9g", l[BP_SCORE_SSNR], l[BP_SCORE_LSD], l[BP_SCORE_STOI]);
+                if (fo && P.ext) fprintf(fo, " %.9g %.9g", l[BP_SCORE_ESTOI], l[BP_SCORE_SISDR]);
             }
             if (fo) fprintf(fo, "\n");
         }
     }
     bp_destroy(h);
     if (fo) fclose(fo);
-    const auto line = [](const char *head, const Acc &a) {
-        printf("%s: %d mixtures, SSNR %.3f -> %.3f dB, LSD %.3f -> %.3f dB, STOI %.4f -> %.4f (%d undefined)\n", head, a.n,
-               avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_N + BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_N + BP_SCORE_LSD),
-               avg(a, BP_SCORE_STOI), avg(a, BP_SCORE_N + BP_SCORE_STOI), a.nan);
-    };
-    const auto line_lm = [](const char *head, const Acc &a) {
-        printf("%s: %d mixtures, logmmse: SSNR %.3f -> %.3f dB, LSD %.3f -> %.3f dB, STOI %.4f -> %.4f (%d undefined)\n", head, a.n,
-               avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_N + BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_N + BP_SCORE_LSD),
-               avg(a, BP_SCORE_STOI), avg(a, BP_SCORE_N + BP_SCORE_STOI), a.nan);
+    const auto line = [&P](const char *head, const char *who, const Acc &a) {       // who: "" or "logmmse: "
+        printf("%s: %d mixtures, %sSSNR %.3f -> %.3f dB, LSD %.3f -> %.3f dB, STOI %.4f -> %.4f", head, a.n, who,
+               avg(a, BP_SCORE_SSNR), avg_enh(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg_enh(a, BP_SCORE_LSD),
+               avg(a, BP_SCORE_STOI), avg_enh(a, BP_SCORE_STOI));
+        if (P.ext)
+            printf(", ESTOI %.4f -> %.4f, SI-SDR %.3f -> %.3f dB", avg(a, BP_SCORE_ESTOI), avg_enh(a, BP_SCORE_ESTOI),
+                   avg(a, BP_SCORE_SISDR), avg_enh(a, BP_SCORE_SISDR));
+        printf(" (%d undefined)\n", a.nan);
     };
     for (const auto &kv : by_snr) {
         char head[64];
         snprintf(head, sizeof(head), "SNR %g dB", kv.first);
-        line(head, kv.second);
-        if (P.baseline) line_lm(head, by_snr_lm[kv.first]);
+        line(head, "", kv.second);
+        if (P.baseline) line(head, "logmmse: ", by_snr_lm[kv.first]);
     }
-    line("all", all);
-    if (P.baseline) line_lm("all", all_lm);
+    line("all", "", all);
+    if (P.baseline) line("all", "logmmse: ", all_lm);
     return 1;
 }

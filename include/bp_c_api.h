@@ -400,12 +400,33 @@ int bp_rir_rooms(uint64_t seed, int n, const bp_rir_range *g, bp_rir_room *out);
  *   audio stays on the device.  The argument checks and the capacity rule of bp_train_mix and bp_enhance_waves (BP_ERR_ARG, the
  *   handle unchanged); BP_ERR_STATE without a corpus and on a data-parallel-attached handle; fp32 and bf16 handles.  The call
  *   leaves the chunk as the resident window chunk; weights and momentum state are untouched.
- * Both: no float atomics, reductions in a fixed order -- the same bits on every run. */
+ * Both: no float atomics, reductions in a fixed order -- the same bits on every run.
+ *
+ * The extended scores (the _ext calls with n_scores = BP_SCORE_EXT_N; two more columns behind the three above):
+ * ESTOI (Jensen & Taal 2016): the STOI front end above unchanged up to the fp32 envelopes X_b(s) of r and Y_b(s) of e, b < 15,
+ *   s < S; S < 30: NaN; for m = 29 .. S-1 the 15 x 30 matrices x[b][u] = X_b(m-29+u) and y likewise; on each matrix alone, in
+ *   double: rows x[b][.] -= mean_u, x[b][.] /= (|x[b][.]| + eps), then columns x[.][u] -= mean_b, x[.][u] /= (|x[.][u]| + eps);
+ *   d_m = (1/30) sum_{b,u} x[b][u] y[b][u]; ESTOI = mean d_m over the S - 29 segments.  No alpha scaling, no clipping, and no
+ *   random dither (estoi.m and pystoi add eps randn; the + eps on the norms does that job here, as in the STOI above).
+ * SI-SDR (dB; Le Roux et al. 2019), over the n samples in double: rr = sum r^2, er = sum e r; rr == 0: NaN; alpha = er/rr; in a
+ *   second pass num = sum (alpha r_i)^2, den = sum (alpha r_i - e_i)^2 (the residual itself: sum e^2 - er^2/rr cancels at high
+ *   SDR); SI-SDR = 10 log10(num/(den + eps) + eps).  The mean is not removed and nothing is clamped.
+ * Not computed: fwSNRseg and the composite measures (they need a 25-band table and PESQ).
+ *
+ * bp_score_waves_ext, bp_eval_mix_ext (and bp_eval_mix_logmmse_ext below): the calls above with rows of n_scores columns, n_scores =
+ *   BP_SCORE_N or BP_SCORE_EXT_N, anything else BP_ERR_ARG before the device is touched; every other check, state and capacity rule
+ *   is that of the call without _ext.  With BP_SCORE_N an _ext call is that call; with BP_SCORE_EXT_N columns 0..2 hold its bits,
+ *   and only then do the ESTOI and SI-SDR kernels run. */
 enum { BP_SCORE_SSNR = 0, BP_SCORE_LSD = 1, BP_SCORE_STOI = 2, BP_SCORE_N = 3 };
+enum { BP_SCORE_ESTOI = 3, BP_SCORE_SISDR = 4, BP_SCORE_EXT_N = 5 };
 int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
                    float *scores);
 int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
                 float *enh_scores, float *enh_pcm);
+int bp_score_waves_ext(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
+                       int n_scores, float *scores);   /* [n_sent][n_scores] */
+int bp_eval_mix_ext(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, int n_scores,
+                    float *noisy_scores, float *enh_scores, float *enh_pcm);
 
 /* ------------------------------------------------------------------------------------
  * The classic baseline: the log-MMSE (Ephraim-Malah log-spectral-amplitude) enhancer, the column every results table of the papers
@@ -444,7 +465,7 @@ int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, i
  *   it, enhanced exactly as bp_logmmse_waves would enhance the mixed samples, x and the result scored against the clean s exactly
  *   as bp_eval_mix scores them; the audio stays on the device.  The argument and capacity rules of bp_eval_mix; BP_ERR_STATE
  *   without a corpus and on a data-parallel-attached handle.  The call leaves the chunk as the resident window chunk; weights and
- *   momentum state are untouched. */
+ *   momentum state are untouched.  bp_eval_mix_logmmse_ext: the same with rows of n_scores columns, as bp_eval_mix_ext has them. */
 typedef struct bp_logmmse_params {
     double alpha;        /* decision-directed weight of the a-priori SNR */
     double mu;           /* smoothing of the noise update in frames the VAD calls noise */
@@ -458,6 +479,8 @@ int bp_logmmse_waves(int device, int fea_dim, const bp_logmmse_params *p, int n_
                      float *out_pcm, float *out_gain, float *out_vad);
 int bp_eval_mix_logmmse(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
                         float *noisy_scores, float *enh_scores, float *enh_pcm);
+int bp_eval_mix_logmmse_ext(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
+                            int n_scores, float *noisy_scores, float *enh_scores, float *enh_pcm);
 
 /* ------------------------------------------------------------------------------------
  * Streaming sessions: audio that is still arriving, enhanced in blocks (no reference counterpart).  INTEGRATION.md 1g.  The signal

@@ -5,7 +5,10 @@ the noise-aware block), bunch 256.  The two calls alternate, each timed to its s
 line.  Kernel times come from running it under `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py` (bp_eval_*
 against the forward's kernels).
 
-    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16]
+--extended: the five-column bp_eval_mix_ext (ESTOI and SI-SDR beside the three) against the three-column bp_eval_mix on the same
+mixtures instead: the two alternate in one process, each timed to its synchronisation; both medians and their ratio.
+
+    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16] [--extended]
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--compute", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--sentences", type=int, default=100)
+    ap.add_argument("--extended", action="store_true", help="time bp_eval_mix_ext with five columns beside bp_eval_mix")
     a = ap.parse_args()
     D, ctx, toff, rate, B = 129, 11, 5, 8000, 256
     ls = [(ctx + 1) * D, 2048, 2048, 2048, D]
@@ -40,6 +44,25 @@ def main():
     g.set_mix_corpus(clean, noise, mean, istd, ctx, toff, "lps")
     plan = dnnse_amd.mix_plan(0, a.sentences, 1, [x.size for x in noise], [-5, 0, 5, 10, 15, 20])
     mix = np.split(g.mix_features(plan)["pcm"], np.cumsum([x.size for x in clean])[:-1])
+    if a.extended:
+        t3, t5 = [], []
+        for r in range(a.reps + 1):                                # (rep 0: warm-up -- buffers, code objects)
+            t0 = time.perf_counter()
+            ev3 = g.eval_mix(plan, rate)
+            t1 = time.perf_counter()
+            ev5 = g.eval_mix(plan, rate, extended=True)
+            t2 = time.perf_counter()
+            if r:
+                t3.append(t1 - t0)
+                t5.append(t2 - t1)
+        g.close()
+        same = all(np.array_equal(ev5[k][:, :3].view(np.uint32), ev3[k].view(np.uint32)) for k in ("noisy", "enhanced"))
+        m3, m5 = float(np.median(t3)), float(np.median(t5))
+        print(json.dumps({"what": "bp_eval_mix_ext (5 columns) vs bp_eval_mix (3 columns)", "compute": a.compute, "mixtures": a.sentences,
+                          "frames": frames, "basic_ms_median": 1e3 * m3, "extended_ms_median": 1e3 * m5, "extended_over_basic": m5 / m3,
+                          "columns_0_to_2_same_bits": same, "noisy_mean": np.nanmean(ev5["noisy"], axis=0).tolist(),
+                          "enhanced_mean": np.nanmean(ev5["enhanced"], axis=0).tolist()}))
+        return
     t_eval, t_enh = [], []
     for r in range(a.reps + 1):                                    # (rep 0: warm-up -- buffers, code objects)
         t0 = time.perf_counter()
