@@ -324,7 +324,10 @@ class BP_GPU(object):
     # ------------------------------------------------------------------ reference API
     def _push_hyper(self):
         """The reference reads its public members afresh on every bunch (BP_GPU.cu:488-500): a caller may
-        assign obj.lrate / momentum / weightcost / dropoutflag / visible_omit / hid_omit between chunks."""
+        assign obj.lrate / momentum / weightcost / dropoutflag / visible_omit / hid_omit between chunks.  Every method that runs
+        the net pushes them first -- training, CV and gradients, and also the forwards (forward, enhance_waves, eval_mix, a
+        stream's push: the keep-scale follows dropoutflag and the omit rates) -- so that what a call computes does not depend
+        on which method was called before it."""
         self._check(self._lib.bp_set_hyper(self._h, float(self.lrate), float(self.momentum), float(self.weightcost),
                                            int(self.dropoutflag), float(self.visible_omit), float(self.hid_omit)))
 
@@ -395,6 +398,7 @@ class BP_GPU(object):
     def forward(self, indata):
         x = np.ascontiguousarray(indata, dtype=np.float32).reshape(-1, self.layersizes[0])
         out = np.empty((x.shape[0], self.layersizes[-1]), np.float32)
+        self._push_hyper()
         self._check(self._lib.bp_forward(self._h, x.shape[0], _fp(x), _fp(out)))
         return out
 
@@ -430,11 +434,13 @@ class BP_GPU(object):
 
     def train_windows(self, fea, targ_frames, context, win_start, targ_frame, nat=None, nat_row=None):
         c, keep = self._windows(fea, targ_frames, context, win_start, targ_frame, nat, nat_row)
+        self._push_hyper()
         self._check(self._lib.bp_train_chunk_windows(self._h, C.byref(c)))
 
     def CrossValid_windows(self, fea, targ_frames, context, win_start, targ_frame, nat=None, nat_row=None):
         c, keep = self._windows(fea, targ_frames, context, win_start, targ_frame, nat, nat_row)
         e = C.c_float(0.0)
+        self._push_hyper()
         self._check(self._lib.bp_cv_chunk_windows(self._h, C.byref(c), C.byref(e)))
         return float(e.value)
 
@@ -454,6 +460,7 @@ class BP_GPU(object):
         c.target, c.out_col = int(target), int(out_col)
         out = np.empty(max(pcm.size, 1), np.float32)
         net = np.empty((max(int(frames.sum()), 1), self.layersizes[-1]), np.float32) if return_net else None
+        self._push_hyper()
         self._check(self._lib.bp_enhance_waves(self._h, D, C.byref(c), _fp(out), _fp(net) if return_net else None))
         waves = np.split(out[:pcm.size], np.cumsum(lens)[:-1])
         if not return_net:
@@ -572,6 +579,7 @@ class BP_GPU(object):
         undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None.  extended: bp_eval_mix_ext with five
         columns, SCORE_ESTOI and SCORE_SISDR behind the same three."""
         p, pp = self._plan(plan)
+        self._push_hyper()
         ns = 5 if extended else 3
         noisy = np.empty((max(p.size, 1), ns), np.float32)
         enh = np.empty((max(p.size, 1), ns), np.float32)
@@ -617,6 +625,7 @@ class BP_GPU(object):
         self._check(self._lib.bp_fill_chunk_synthetic(self._h, int(n_frames), int(seed)))
 
     def train_resident(self, first_frame, n_frames):
+        self._push_hyper()
         self._check(self._lib.bp_train_resident(self._h, int(first_frame), int(n_frames)))
 
     def train_resident_masked(self, first_frame, n_frames, masks):
@@ -629,10 +638,12 @@ class BP_GPU(object):
                 m = np.ascontiguousarray(m, dtype=np.uint8).reshape(int(n_frames), self.layersizes[l])
                 keep.append(m)
                 arr[l] = m.ctypes.data_as(P)
+        self._push_hyper()
         self._check(self._lib.bp_train_resident_masked(self._h, int(first_frame), int(n_frames), arr))
 
     # ---- gradients without the update (parity tests): bp_grads_resident / bp_read_grads / bp_read_layer_output
     def grads_resident(self, first_frame):
+        self._push_hyper()
         self._check(self._lib.bp_grads_resident(self._h, int(first_frame)))
 
     def grad_floats(self):
@@ -720,6 +731,7 @@ class BP_GPU(object):
         """{class: (avg ms per launch inside the step, launches per step)} -- bp_profile_step."""
         ms = (C.c_float * len(PROF_KINDS))()
         cnt = (C.c_int * len(PROF_KINDS))()
+        self._push_hyper()
         self._check(self._lib.bp_profile_step(self._h, int(first_frame), int(n_bunches), ms, cnt))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(PROF_KINDS)}
 
@@ -792,6 +804,7 @@ class Stream(object):
             g._fail("Stream.push: need one block (and one end flag) per channel (%d)" % self.n_chan)
         if out_cap is None:     # what waited (at most max(look-ahead, 5) + 1 frames) and what arrived, rounded up to frames
             out_cap = lambda n: n + self.n_chan * (max(self.look_ahead, 5) + 3) * (self.fea_dim - 1)
+        g._push_hyper()
         rc, outs = _stream_push(g._lib.bp_stream_push, self._s, self.n_chan, blocks, end, out_cap)
         g._check(rc)
         return outs

@@ -124,9 +124,12 @@ static void dp_release(bp_handle *h, bool failed)
     h->dp = nullptr;
 }
 
-extern "C" int bp_dp_detach(bp_handle *h)
+// gather: an explicit bp_dp_detach.  Under more than one rank the momentum state is sharded, and once the peers are unmapped
+// nothing can fetch their slices any more: a group whose barrier succeeded (every rank is here and quiescent) pulls them into the
+// local arena first, so that bp_get_deltas, a checkpoint or a later bp_dp_attach sees the whole state.  The implicit detach of
+// bp_destroy and every failed path do not gather (a peer may be gone; the handle's state is about to be dropped anyway).
+int dp_detach(bp_handle *h, bool gather)
 {
-    if (!h) return fail(BP_ERR_ARG, "null handle");
     if (!h->dp) return BP_OK;
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
@@ -134,8 +137,17 @@ extern "C" int bp_dp_detach(bp_handle *h)
     // nobody may unmap a buffer a peer kernel could still touch: everyone arrives here quiescent first
     int r = BP_OK;
     if (d->peers_open && rdv_barrier(d->rdv) != 0) r = fail(BP_ERR_STATE, g_rdv_err);
+    if (r == BP_OK && gather && d->peers_open && dp_gathers_deltas(h))
+        r = dp_gather_deltas(h);                 // (ends with a barrier: nobody unmaps while a peer still reads)
+    const std::string why = g_bp_err;            // (the release may fail on its own way out: the caller gets the first reason)
     dp_release(h, r != BP_OK);
+    if (r != BP_OK) g_bp_err = why;
     return r;
+}
+extern "C" int bp_dp_detach(bp_handle *h)
+{
+    if (!h) return fail(BP_ERR_ARG, "null handle");
+    return dp_detach(h, true);
 }
 
 static DpPeers dp_peers(const bp_dp *d)

@@ -94,6 +94,8 @@ struct bp_handle {
     struct WinSet { Buf r[4]; } wset[2];      // raw frames, raw target frames, NAT rows, tables (win_start | targ_frame | nat_row)
     int wcur;                                 // staging set of the resident window chunk
     bool windows;                             // the resident chunk is a window chunk
+    bool chunk_has_targ;                      // the call that made the chunk resident supplied targets (stacked: targ / targ_alt were
+                                              // written; window: wv.tg != null); training and gradient calls need them
     struct { const float *fea, *tg, *nat; const int *ws, *tf, *nr; int D, win; } wv;   // views of set wcur
     float *x0s, *tgs;                         // [Bp][ld_0], [Bp][ld_L]: the staged bunch (= tile stage_cur of the pair below)
     float *x0s2[2], *tgs2[2]; int stage_cur;  // two staged tiles: while bunch i trains out of one, the output layer's reduce launch
@@ -223,4 +225,5 @@ int dp_check(bp_handle *h);                       // BP_OK, or the device-side t
 hipError_t dp_bunch(bp_handle *h, int first);
 hipError_t dp_flush(bp_handle *h);
 int dp_gather_deltas(bp_handle *h);
+int dp_detach(bp_handle *h, bool gather);       // bp_dp_detach (gather: the sharded momentum state first) | bp_destroy (no gather)
 bool dp_gathers_deltas(const bp_handle *h);       // attached with more than one rank: the momentum state is sharded

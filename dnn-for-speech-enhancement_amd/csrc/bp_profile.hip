@@ -19,6 +19,8 @@ extern "C" int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, flo
     if (h->bf || h->dp || h->Bg != h->B) return fail(BP_ERR_STATE, "bp_profile_step: fp32 single-device handles only");
     if (n_bunches < 1 || first_frame < 0 || (long)first_frame + (long)n_bunches * h->B > h->chunk_frames)
         return fail(BP_ERR_ARG, "bp_profile_step: frame range outside the resident chunk");
+    if (!h->chunk_has_targ)
+        return fail(BP_ERR_STATE, "bp_profile_step: the resident chunk was uploaded without targets (forward / CV upload)");
     HIPCHK(hipSetDevice(h->cfg.device));
     StepProf prof; prof.used = 0;
     int rc = BP_OK;

@@ -64,13 +64,12 @@ int dev_alloc(bp_handle *h, float **p, size_t n_floats)
     return BP_OK;
 }
 
-extern "C" int bp_dp_detach(bp_handle *h);
 extern "C" int bp_destroy(bp_handle *h)
 {
     if (!h) return BP_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-    if (h->dp) (void)bp_dp_detach(h);
+    if (h->dp) (void)dp_detach(h, false);
     mix_free(h);
     stream_free_all(h);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
@@ -818,6 +817,7 @@ extern "C" int bp_upload_chunk(bp_handle *h, int n_frames, const float *in, cons
         std::swap(h->targ, h->targ_alt);
     }
     h->chunk_frames = n_frames;
+    h->chunk_has_targ = targ != nullptr;                    // (bp_forward / bp_cv_chunk: the pair swapped, its targets are an older chunk's)
     h->wgen++; h->pre.valid = false; h->next_first = -1;    // (a tile pre-staged from the old chunk is void)
     return BP_OK;
 }
@@ -968,6 +968,7 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
     h->windows = true;
     h->wgen++; h->pre.valid = false; h->next_first = -1;
     h->chunk_frames = n;
+    h->chunk_has_targ = with_targ;
     return BP_OK;
 }
 
@@ -993,6 +994,7 @@ int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat
     h->windows = true;
     h->wgen++; h->pre.valid = false; h->next_first = -1;
     h->chunk_frames = n_samples;
+    h->chunk_has_targ = with_targ;
     return BP_OK;
 }
 
@@ -1020,6 +1022,7 @@ extern "C" int bp_fill_chunk_synthetic(bp_handle *h, int n_frames, uint64_t seed
         HIPCHK(hipGetLastError());
     }
     h->chunk_frames = n_frames;
+    h->chunk_has_targ = true;
     h->wgen++; h->pre.valid = false; h->next_first = -1;
     return BP_OK;
 }
@@ -1034,6 +1037,8 @@ extern "C" int bp_train_resident(bp_handle *h, int first_frame, int n_frames)
                                   "(bp_dp_attach: the exchange and the sharded update run inside the library)");
     if (h->windows && n_frames >= h->B && !h->wv.tg)
         return fail(BP_ERR_STATE, "bp_train_resident: the resident window chunk was uploaded without targets (forward / CV upload)");
+    if (!h->windows && n_frames >= h->B && !h->chunk_has_targ)
+        return fail(BP_ERR_STATE, "bp_train_resident: the resident stacked chunk was uploaded without targets (forward / CV upload)");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int nb = n_frames / h->B;          // partial last bunch ignored (BP_GPU.cu:315-318)
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -1087,6 +1092,8 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
     if (h->windows) return fail(BP_ERR_STATE, "bp_train_resident_masked: stacked chunks only (bp_upload_chunk)");
     if (first_frame < 0 || n_frames < 0 || first_frame + n_frames > h->chunk_frames)
         return fail(BP_ERR_ARG, "bp_train_resident_masked: frame range outside the resident chunk");
+    if (n_frames >= h->B && !h->chunk_has_targ)
+        return fail(BP_ERR_STATE, "bp_train_resident_masked: the resident stacked chunk was uploaded without targets (forward / CV upload)");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L, B = h->B, nb = n_frames / B;
     Buf dm_b[BP_MAXLAYER], xm_b;                                 // (released on return, behind the final synchronisation)
@@ -1141,6 +1148,8 @@ extern "C" int bp_grads_resident(bp_handle *h, int first_frame)
     // back-propagate against whatever an earlier bunch left in the staged target tile
     if (h->windows && !h->wv.tg)
         return fail(BP_ERR_STATE, "bp_grads_resident: the resident window chunk was uploaded without targets (forward / CV upload)");
+    if (!h->windows && !h->chunk_has_targ)
+        return fail(BP_ERR_STATE, "bp_grads_resident: the resident stacked chunk was uploaded without targets (forward / CV upload)");
     HIPCHK(hipSetDevice(h->cfg.device));
     if (!h->grad) { int r = dev_alloc(h, &h->grad, h->grad_floats); if (r != BP_OK) return r; }
     h->next_first = -1;

@@ -168,6 +168,16 @@ int bp_sync(bp_handle *h);
  * parity statement).  masks[l], l = 0 .. numlayers-2: host [n_frames][layersizes[l]] bytes, 1 = drop the output of
  * layer l for that frame (l = 0: the input frame); NULL = no dropout on that layer.  fp32 single-device handles. */
 int bp_train_resident_masked(bp_handle *h, int first_frame, int n_frames, const uint8_t *const *masks);
+/* What is resident, and what may train on it.  Every call that takes data makes its chunk the handle's resident chunk, the
+ * queries too: bp_forward and bp_cv_chunk (stacked), bp_forward_windows, bp_cv_chunk_windows, bp_enhance_waves, the mixing calls
+ * and a stream's push (window).  bp_train_resident[_masked], bp_grads_resident and bp_profile_step work on whatever is resident:
+ * A frame range outside the resident chunk returns BP_ERR_ARG (checked first).
+ * A chunk whose targets were not supplied by the call that made it resident returns BP_ERR_STATE from a training or gradient call
+ * that would train a bunch of it: after bp_forward[_windows], bp_cv_chunk[_windows], bp_enhance_waves, bp_cv_mix, bp_eval_mix[_logmmse]
+ * and a stream's push there are no targets on the device (bp_cv_* compare on the host; a stacked upload without targets leaves
+ * an OLDER chunk's targets in the buffer).  bp_upload_chunk[_windows], bp_fill_chunk_synthetic, bp_train_*, bp_train_mix and
+ * bp_mix_features (it makes the targets on the device) leave a chunk that can be trained on.  The handle is unchanged after
+ * either error. */
 
 /* ------------------------------------------------------------------------------------
  * On-device frame stacking.  The reference's reader materialises every
@@ -620,7 +630,15 @@ int bp_read_layer_output(bp_handle *h, int layer, float *host_dst, size_t n_floa
 enum { BP_DP_TRANSPORT_NATIVE = 0, BP_DP_TRANSPORT_RCCL = 1, BP_DP_TRANSPORT_NATIVE_PUSH = 2, BP_DP_TRANSPORT_NATIVE_PUSH_BF16 = 3 };
 int bp_dp_attach(bp_handle *h, int world, int rank, const char *key);
 int bp_dp_attach_ex(bp_handle *h, int world, int rank, const char *key, int transport);
-int bp_dp_detach(bp_handle *h);     /* collective; also done by bp_destroy */
+/* bp_dp_detach is collective.  Under more than one rank the momentum state is sharded (each rank updates its slices only), so a
+ * bp_dp_detach whose barrier succeeded gathers it, as bp_get_deltas does, before it unmaps the peers: the detached handle holds
+ * the whole momentum state, and bp_get_deltas, a checkpoint or a later bp_dp_attach of any transport continue from it.  bp_destroy
+ * detaches too, without the gather (the state goes with the handle), and so does every failed path (a peer may be gone): after a
+ * bp_dp_detach that returned an error the slices of the other ranks are stale.  EVERY rank of a group of more than one must call
+ * bp_dp_detach itself: the gather meets the peers at two more barriers than the detach inside bp_destroy does, so a rank that
+ * only destroys its handle no longer pairs up with a peer's bp_dp_detach -- that peer waits BP_DP_TIMEOUT_S and returns
+ * BP_ERR_STATE, detached, with stale slices (ranks that ALL just call bp_destroy still pair up with each other). */
+int bp_dp_detach(bp_handle *h);
 int bp_dp_info(bp_handle *h, int *world, int *rank, unsigned *minibatches);
 /* What rank `peer` of the group attached to: HIP device ordinal in ITS process and PCI bus id ("0000:c1:00.0";
  * buffer of >= 16 bytes), plus this group's transport and acquire mode (0 kernel boundary, 1 explicit acquire). */
