@@ -11,5 +11,6 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
                      LogmmseStream, logmmse_stream_open, logmmse_stream_counts,
                      rir_image, rir_rooms, rir_beta, rir_orders, rir_window_default, BPRirRange, RIR_ROOM_DTYPE, RIR_RANGE_DEFAULTS,
-                     RIR_MAX_IMAGES)
+                     RIR_MAX_IMAGES,
+                     BPResampleParams, resample_waves, resample_ratio, resample_len, resample_taps, resample_params)
 from .weights_init import glorot_net  # noqa: F401

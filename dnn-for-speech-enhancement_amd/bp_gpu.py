@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
     "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
+    "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
@@ -132,6 +133,11 @@ class BPLogmmseParams(C.Structure):
     ]
 
 
+class BPResampleParams(C.Structure):
+    """bp_resample_params (include/bp_c_api.h): the windowed-sinc filter of the sample-rate converter."""
+    _fields_ = [("zeros", C.c_int), ("beta", C.c_double), ("rolloff", C.c_double)]
+
+
 class BPConfig(C.Structure):
     _fields_ = [
         ("gpu_used", C.c_int), ("numlayers", C.c_int), ("layersizes", C.c_int * MAXLAYER),
@@ -207,6 +213,11 @@ def load_library(path=None):
     lib.bp_lmstream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
     lib.bp_lmstream_close.argtypes = [C.c_void_p]
     lib.bp_lmstream_counts.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
+    lib.bp_resample_defaults.argtypes = [C.POINTER(BPResampleParams)]
+    lib.bp_resample_ratio.argtypes = [C.c_int, C.c_int, ip, ip]
+    lib.bp_resample_len.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    lib.bp_resample_taps.argtypes = [C.c_int, C.c_int, C.POINTER(BPResampleParams), fp, C.c_int]
+    lib.bp_resample_waves.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(BPResampleParams), C.c_int, ip, fp, fp]
     lib.bp_fill_chunk_synthetic.argtypes = [hp, C.c_int, C.c_uint64]
     lib.bp_train_resident.argtypes = [hp, C.c_int, C.c_int]
     lib.bp_sync.argtypes = [hp]
@@ -964,6 +975,77 @@ def score_waves(device, fea_dim, sample_rate, refs, ests, extended=False):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return out[:len(r)]
+
+
+def _raise(lib, rc):
+    raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+
+
+def resample_params(params=None):
+    """None (the library's defaults: zeros 16, beta 8.6, rolloff 0.9), or a BPResampleParams: bp_resample_defaults overridden by
+    the fields of a dict, or by a (zeros, beta, rolloff) tuple."""
+    if params is None or isinstance(params, BPResampleParams):
+        return params
+    lib = load_library()
+    rs = BPResampleParams()
+    lib.bp_resample_defaults(C.byref(rs))
+    if not isinstance(params, dict):
+        params = dict(zip(("zeros", "beta", "rolloff"), params))
+    for k, v in params.items():
+        if k not in ("zeros", "beta", "rolloff"):
+            raise BPError("resample_params: unknown field %s" % k)
+        setattr(rs, k, int(v) if k == "zeros" else float(v))
+    return rs
+
+
+def resample_ratio(rate_in, rate_out):
+    """bp_resample_ratio: (p, q) with rate_out / rate_in = p / q in lowest terms, max(p, q) <= 1024; host only."""
+    lib = load_library()
+    p, q = C.c_int(), C.c_int()
+    rc = lib.bp_resample_ratio(int(rate_in), int(rate_out), C.byref(p), C.byref(q))
+    if rc != 0:
+        _raise(lib, rc)
+    return int(p.value), int(q.value)
+
+
+def resample_len(n, p, q):
+    """bp_resample_len: ceil(n p / q), the samples a sentence of n samples becomes; host only."""
+    lib = load_library()
+    out = C.c_int64()
+    rc = lib.bp_resample_len(int(n), int(p), int(q), C.byref(out))
+    if rc != 0:
+        _raise(lib, rc)
+    return int(out.value)
+
+
+def resample_taps(p, q, params=None):
+    """bp_resample_taps: the 2 zeros max(p, q) + 1 float32 taps of the conversion by p / q; host only."""
+    lib = load_library()
+    rs = resample_params(params)
+    zeros = 16 if rs is None else int(rs.zeros)
+    h = np.empty(max(2 * max(zeros, 0) * max(int(p), int(q), 0) + 1, 1), np.float32)
+    rc = lib.bp_resample_taps(int(p), int(q), None if rs is None else C.byref(rs), _fp(h), h.size)
+    if rc != 0:
+        _raise(lib, rc)
+    return h
+
+
+def resample_waves(device, rate_in, rate_out, sentences, params=None):
+    """bp_resample_waves: every sentence (1-D arrays) converted from rate_in to rate_out, a list of float32 arrays of
+    resample_len samples each (no handle).  Defined to the bit in include/bp_c_api.h."""
+    lib = load_library()
+    rs = resample_params(params)
+    p, q = resample_ratio(rate_in, rate_out)
+    arrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in sentences]
+    lens = np.array([a.size for a in arrs], np.int32)
+    pcm = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.float32))
+    n_out = (lens.astype(np.int64) * p + q - 1) // q
+    out = np.empty(max(int(n_out.sum()), 1), np.float32)
+    rc = lib.bp_resample_waves(int(device), int(rate_in), int(rate_out), None if rs is None else C.byref(rs), len(arrs),
+                               lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out))
+    if rc != 0:
+        _raise(lib, rc)
+    return np.split(out[:int(n_out.sum())], np.cumsum(n_out)[:-1])
 
 
 def reverb_waves(device, sents, sent_rir, rirs, early_taps=0, early=True):

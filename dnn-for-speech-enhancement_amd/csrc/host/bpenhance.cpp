@@ -6,7 +6,7 @@
 //             [wave_target=lps|mask] [out_col=0] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2] [bunchsize=1024]
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
-//             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv]
+//             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv] [rate=8000]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
 //             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6] [lm_stream_block=<samples> [lm_stream_chan=<n>]]
 //
@@ -22,6 +22,10 @@
 // With lm_stream_block the files go through a log-MMSE stream (bp_lmstream_push) by the rules of stream_block:
 // file s to channel s mod lm_stream_chan, lm_stream_block samples per push, the end flag on a file's last block; the output
 // files hold the bytes of a run without the key.
+// rate=R: the rate the net works at.  A file at another rate f is converted to R on the device
+// (bp_resample_waves), enhanced, converted back to f, trimmed to its original length and written at f as without the key; what it
+// held above R/2 is gone.  One call and one line on stdout per distinct rate and direction.  Not with stream_block or
+// lm_stream_block (a stream needs a filter that keeps state), and not with method=logmmse.
 // Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
 #include <stdlib.h>
@@ -165,7 +169,7 @@ int main(int argc, char **argv)
     bp_logmmse_defaults(&lm);
     int fea_dim = 0, ctx = 1, toff = 0, dropoutflag = 0, bunch = 1024, cache = 102400, L = 0, ls[MAXLAYER] = {0};
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
-    int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1;
+    int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1, rate = 0;
     bool lm_chan_given = false;
     float vis = 0.f, hid = 0.f;
     const char *const count = "is not a count >= 1";
@@ -184,6 +188,7 @@ int main(int argc, char **argv)
         {"forward", K_CHOICE, &forward, BP_FORWARD_DEFAULT, 0, "default|rowinv", "is not default or rowinv"},
         {"wave_target", K_CHOICE, &target, BP_WAVE_LPS, 0, "lps|mask", "is not lps or mask"},
         {"layersizes", K_ATOI_SIZES, ls, 0, MAXLAYER, nullptr, nullptr, &L},
+        {"rate", K_INT, &rate, 1, (double)RATE_MAX, nullptr, RATE_TAIL},
     };
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
@@ -205,6 +210,8 @@ int main(int argc, char **argv)
         }
         else fail("bpenhance: unknown key " + k);
     }
+    if (rate && (stream_block > 0 || lm_block > 0))
+        fail("bpenhance: rate does not go with stream_block or lm_stream_block (a stream needs a sample-rate converter that keeps state)");
     for (const std::string &k : given) {
         const bool lm_key = k.compare(0, 3, "lm_") == 0;
         if (!logmmse && lm_key) fail("bpenhance: " + k + " needs method=logmmse");
@@ -244,7 +251,17 @@ int main(int argc, char **argv)
     std::vector<int> rates(ns);
     for (int s = 0; s < ns; ++s) {
         waves[s] = read_one(WHO, ins[s], &rates[s]);
-        const size_t rows = (waves[s].size() - 1) / hop + 2 + ctx - 1;
+        size_t n_net = waves[s].size();                          // samples at the net's rate
+        if (rate && rates[s] != rate) {
+            check_convertible(WHO, ins[s], rates[s], rate);
+            if (waves[s].size() > (size_t)INT32_MAX) fail(ins[s] + ": too long to convert");
+            int p = 0, q = 0;
+            int64_t no = 0;
+            check(bp_resample_ratio(rates[s], rate, &p, &q));
+            check(bp_resample_len((int64_t)waves[s].size(), p, q, &no));
+            n_net = (size_t)no;
+        }
+        const size_t rows = (n_net - 1) / hop + 2 + ctx - 1;
         if (stream_block < 1 && rows > (size_t)cache) { printf("%s: %zu rows exceed traincache=%d (one sentence per call at most)\n", ins[s].c_str(), rows, cache); exit(0); }
     }
     std::vector<float> mean, istd;
@@ -261,6 +278,10 @@ int main(int argc, char **argv)
     std::vector<float> pcm, out;
     std::vector<int> lens;
     size_t samples = 0;
+    std::vector<size_t> orig_len(ns);                            // rate=: the files as they came, and what the net made of them
+    std::vector<std::vector<float>> enh(rate ? ns : 0);
+    for (int s = 0; s < ns; ++s) orig_len[s] = waves[s].size();
+    if (rate) convert_rates(WHO, "input", device, rate, waves, rates);
     if (stream_block > 0) {
         // ---- a streaming session: channel c plays files c, c + stream_chan, ... one after the other
         bp_stream_config sc;
@@ -299,12 +320,22 @@ int main(int argc, char **argv)
         check(bp_enhance_waves(h, fea_dim, &c, out.data(), nullptr));
         size_t off = 0;
         for (int s = s0; s < s1; ++s) {
-            const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
-            if (!e.empty()) fail(e);
+            if (rate) enh[s].assign(out.begin() + off, out.begin() + off + waves[s].size());
+            else {
+                const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
+                if (!e.empty()) fail(e);
+            }
             off += waves[s].size();
         }
         samples += pcm.size();
         s0 = s1;
+    }
+    if (rate) {                                                  // back to every file's own rate, trimmed to its own length
+        convert_rates(WHO, "output", device, rate, enh, rates, rate);
+        for (int s = 0; s < ns; ++s) {
+            const std::string e = bp::write_wav(outs[s], enh[s].data(), orig_len[s], rates[s]);
+            if (!e.empty()) fail(e);
+        }
     }
     bp_destroy(h);
     printf("bpenhance: %zu samples of %d sentences enhanced\n", samples, ns);

@@ -7,11 +7,14 @@
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
-//          [scores=basic|extended]
-//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended]
+//          [scores=basic|extended] [rate=16000]
+//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended] [rate=16000]
 //
+// rate=R (either mode): every clean, noise or pair WAV whose rate is not R is converted to R on the device as it is
+// loaded (bp_resample_waves: one call and one line on stdout per list and distinct rate), and R is the rate handed to the scores;
+// a response of rir_list must have it: an impulse response is not converted.
 // Test-set mode: the plan is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list), cut into calls
-// of at most traincache rows (frames + n_mix (context-1)) in plan order, as bpmix cuts it; every WAV must have the same rate.
+// of at most traincache rows (frames + n_mix (context-1)) in plan order, as bpmix cuts it; every WAV must have the same rate (or rate=).
 // stdout: one line per SNR (ascending) and one "all:" line, noisy -> enhanced; means skip NaN, and the count of NaN scores of the
 // line is printed.  scores_out: one line per mixture in plan order, `clean noise offset snr ssnr_noisy ssnr_enh lsd_noisy lsd_enh
 // stoi_noisy stoi_enh` (%.9g: the floats round-trip); pairs mode: `ref est ssnr lsd stoi` per pair.  Every key, list and WAV is
@@ -54,7 +57,7 @@ struct Params {
     float early_ms = 50.0f;
     int fea_dim = 0, fea_context = 1, targ_offset = 0, dropoutflag = 0, traincache = 102400, bunchsize = 1024, numlayers = 0;
     int layersizes[BP_MAXLAYER] = {0}, mix_per_clean = 1, activation = 0, compute_dtype = 0, device = 0;
-    int output_act = 0, output_linear_dims = 0, output_loss = 0, wave_target = BP_WAVE_LPS, out_col = 0;
+    int output_act = 0, output_linear_dims = 0, output_loss = 0, wave_target = BP_WAVE_LPS, out_col = 0, rate = 0;
     float visible_omit = 0, hid_omit = 0;
     unsigned long long seed = 0;
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
@@ -72,6 +75,7 @@ Params parse(int argc, char **argv)
         {"fea_dim", K_INT, &P.fea_dim, 1, 1 << 20},
         {"device", K_INT, &P.device, 0, 1023},
         {"scores", K_CHOICE, &P.ext, 0, 0, "basic|extended"},
+        {"rate", K_INT, &P.rate, 1, (double)RATE_MAX},
     };
     const Key keys[] = {
         {"clean_list", K_STR, &P.clean_list}, {"noise_list", K_STR, &P.noise_list}, {"norm_file", K_STR, &P.norm_file},
@@ -142,16 +146,27 @@ int pairs_mode(const Params &P)
     std::vector<float> r, e;
     std::vector<int> lens;
     int rate = 0;
+    std::vector<std::vector<float>> both;                    // rate=: reference and estimate of every pair, to be converted together
+    std::vector<int> both_rates;
     for (size_t i = 0; i < refs.size(); ++i) {
         int rr = 0, re = 0;
         const std::vector<float> a = read_one(WHO, refs[i], &rr), b = read_one(WHO, ests[i], &re);
         if (rr != re) fail("bpeval: " + refs[i] + " and " + ests[i] + " differ in sample rate");
         if (a.size() != b.size()) fail("bpeval: " + refs[i] + " and " + ests[i] + " differ in length");
-        if (rate && rr != rate) fail("bpeval: " + refs[i] + " has " + std::to_string(rr) + " Hz, the others " + std::to_string(rate) + " Hz");
-        rate = rr;
+        if (P.rate) check_convertible(WHO, refs[i], rr, P.rate);
+        else if (rate && rr != rate) fail("bpeval: " + refs[i] + " has " + std::to_string(rr) + " Hz, the others " + std::to_string(rate) + " Hz");
+        rate = P.rate ? P.rate : rr;
         if (a.size() > (size_t)INT32_MAX / 2) fail("bpeval: " + refs[i] + " is too long");
+        if (P.rate) { both.push_back(a); both.push_back(b); both_rates.push_back(rr); both_rates.push_back(rr); continue; }
         r.insert(r.end(), a.begin(), a.end()); e.insert(e.end(), b.begin(), b.end());
         lens.push_back((int)a.size());
+    }
+    if (P.rate) {
+        convert_rates(WHO, "pairs_list", P.device, P.rate, both, both_rates);
+        for (size_t i = 0; i < both.size(); i += 2) {
+            r.insert(r.end(), both[i].begin(), both[i].end()); e.insert(e.end(), both[i + 1].begin(), both[i + 1].end());
+            lens.push_back((int)both[i].size());
+        }
     }
     check_rate(rate);
     FILE *fo = nullptr;
@@ -194,12 +209,16 @@ int main(int argc, char **argv)
     if (P.snr.empty()) fail("bpeval: snr_list is empty");
     // every list and WAV is read and checked before the device is used
     int rate = 0;
-    const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, nullptr, &rate));
-    const Corpus noise = flatten(read_wav_list(WHO, "noise_list", P.noise_list, nullptr, &rate));
+    const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, nullptr, &rate, P.rate, P.device));
+    const Corpus noise = flatten(read_wav_list(WHO, "noise_list", P.noise_list, nullptr, &rate, P.rate, P.device));
     Reverb rv;                                                   // rir_list: the responses, at the rate of the others
     if (!P.rir_list.empty()) {
         const std::vector<std::string> paths = read_lines(WHO, "rir_list", P.rir_list);
         for (size_t k = 0; k < paths.size(); ++k) {
+            int rr = 0;
+            if (P.rate && (read_one(WHO, paths[k], &rr), rr != P.rate))
+                fail("bpeval: rir_list: " + paths[k] + " has " + std::to_string(rr) + " Hz and rate=" + std::to_string(P.rate) +
+                     " does not convert impulse responses (resampling one also rescales it)");
             const std::vector<float> w = read_one(WHO, paths[k], &rate);
             if (w.size() > (size_t)BP_MIX_RIR_MAX_TAPS) fail("bpeval: rir_list: " + paths[k] + " has more than " + std::to_string(BP_MIX_RIR_MAX_TAPS) + " taps");
             rv.pcm.insert(rv.pcm.end(), w.begin(), w.end());

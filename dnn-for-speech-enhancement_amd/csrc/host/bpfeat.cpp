@@ -2,8 +2,11 @@
 // WAV, in list order, in the Pfile format bptrain reads.  The analysis is bp_wave_lps, the same that bp_enhance_waves runs at
 // enhancement time (include/bp_c_api.h), so training and enhancement see the same features.
 //
-//   bpfeat wav_list=noisy.list out_file=noisy.pfile fea_dim=129 [norm_out=noisy.norm] [device=0]
+//   bpfeat wav_list=noisy.list out_file=noisy.pfile fea_dim=129 [norm_out=noisy.norm] [device=0] [rate=8000]
 //
+// rate=R: every WAV whose sample rate is not R is converted to R on the device as the list is loaded
+// (bp_resample_waves, one call and one line on stdout per distinct rate), and the features are those of the converted samples.
+// Without the key a file's rate is not looked at.
 // norm_out: per-bin mean and inverse standard deviation over all frames of the list (accumulated in double), in the
 // normalisation-file format the reader takes as norm_file.  Errors: message + exit(0), success: return 1 (reference convention).
 #include <math.h>
@@ -23,11 +26,12 @@
 int main(int argc, char **argv)
 {
     std::string list, out_file, norm_out;
-    int fea_dim = 0, device = 0;
+    int fea_dim = 0, device = 0, rate = 0;
     using namespace bp;
     const Key keys[] = {
         {"wav_list", K_STR, &list}, {"out_file", K_STR, &out_file}, {"norm_out", K_STR, &norm_out},
         {"fea_dim", K_ATOI, &fea_dim}, {"device", K_ATOI, &device},
+        {"rate", K_INT, &rate, 1, (double)RATE_MAX, nullptr, RATE_TAIL},
     };
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
@@ -36,7 +40,7 @@ int main(int argc, char **argv)
     if (list.empty() || out_file.empty() || !fea_dim_ok(fea_dim))
         fail("bpfeat: need wav_list, out_file and fea_dim (2*(fea_dim-1) a power of two from 64 to 2048)");
     // every WAV is read and checked before the device is used
-    const std::vector<std::vector<float>> waves = read_wav_list("bpfeat", "wav list", list);
+    const std::vector<std::vector<float>> waves = read_wav_list("bpfeat", "wav list", list, nullptr, nullptr, rate, device);
 
     const int hop = fea_dim - 1, D = fea_dim, ns = (int)waves.size();
     bp::PfileWriter pw;

@@ -8,7 +8,7 @@
 //         [cv_noise_list=noise.list] [cv_seed=20261016] [mix_plan_out=plan.txt] [output_act=...] [compute=fp32|bf16] ...
 //         [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50] [cv_rir_list=rir.list]
 //         [rir_rooms=N] [rir_room_lo=3,3,2.5] [rir_room_hi=10,8,4] [rir_t60=0.2,0.8] [rir_margin=0.5] [rir_dist=0.5,3] [rir_ms=400]
-//         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N]
+//         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N] [rate=8000]
 //   bpmix clean_list=... noise_list=... fea_dim=129 norm_out=mix.norm [snr_list=...] [mix_per_clean=...] [init_randem_seed=...]
 //
 // The plan of the epoch is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list); it is cut into
@@ -24,7 +24,10 @@
 // paired from cv_seed.  rir_rooms=N takes the place of rir_list: N simulated responses of rir_ms milliseconds
 // at the rate of the clean sentences, their rooms drawn by bp_rir_rooms(init_randem_seed, N, the rir_* ranges) and made by
 // bp_rir_image; rir_rooms_out lists the rooms, one `L src mic beta` line each; CV draws cv_rir_rooms (default N) from cv_seed.
-// Every key, list, WAV and drawn room is checked before the device is used.  Errors: message +
+// rate=R: every clean or noise WAV (training and CV) whose rate is not R is converted to R on the device as its
+// list is loaded (bp_resample_waves: one call and one line on stdout per list and distinct rate; the float samples go on as they
+// come), R is the rate of the corpus, and a response of rir_list must have it: an impulse response is not converted.
+// Every key, list, WAV and drawn room is checked before the device is used (with rate=, before anything but the conversions).  Errors: message +
 // exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -54,7 +57,7 @@ struct Params {
     float early_ms = 50.0f;
     int fea_dim = 0, fea_context = 1, targ_offset = 0, dropoutflag = 0, traincache = 0, bunchsize = 0, numlayers = 0, gpu_used = 1;
     int layersizes[BP_MAXLAYER] = {0}, mix_per_clean = 1, target = BP_MIX_LPS, activation = 0, momentum_rule = 0, compute_dtype = 0;
-    int output_act = 0, output_linear_dims = 0, output_loss = 0, device = 0;
+    int output_act = 0, output_linear_dims = 0, output_loss = 0, device = 0, rate = 0;
     float momentum = 0, weightcost = 0, lrate = 0, visible_omit = 0, hid_omit = 0, lc_db = 5.0f;
     float wmin = -0.1f, wmax = 0.1f, bmin = -0.1f, bmax = 0.1f;
     unsigned long long seed = 0, cv_seed = 20261016ull, dropout_seed = 0;
@@ -81,6 +84,7 @@ Params parse(int argc, char **argv)
         {"numlayers", K_INT, &P.numlayers, 2, BP_MAXLAYER - 1},
         {"gpu_used", K_INT, &P.gpu_used, 1, 1},                                      // (one GPU: mixing is single-device)
         {"device", K_INT, &P.device, 0, 1023},
+        {"rate", K_INT, &P.rate, 1, (double)RATE_MAX},
         {"mix_per_clean", K_INT, &P.mix_per_clean, 1, 1 << 20},
         {"init_randem_seed", K_U64, &P.seed}, {"cv_seed", K_U64, &P.cv_seed}, {"seed", K_U64, &P.dropout_seed},
         {"lrate", K_FLOAT, &P.lrate}, {"momentum", K_FLOAT, &P.momentum}, {"weightcost", K_FLOAT, &P.weightcost},
@@ -133,6 +137,9 @@ Reverb read_reverb(const Params &P, const std::string &what, const std::string &
     const auto w = read_wav_list(WHO, what, list, &rates);
     one_rate(what, clean_rates);
     for (size_t k = 0; k < w.size(); ++k) {
+        if (P.rate && rates[k] != P.rate)
+            fail("bpmix: " + what + ": response " + std::to_string(k) + " has " + std::to_string(rates[k]) + " Hz and rate=" + std::to_string(P.rate) +
+                 " does not convert impulse responses (resampling one also rescales it)");
         if (rates[k] != clean_rates[0])
             fail("bpmix: " + what + ": response " + std::to_string(k) + " has " + std::to_string(rates[k]) + " Hz, the clean sentences " +
                  std::to_string(clean_rates[0]) + " Hz");
@@ -195,8 +202,8 @@ int main(int argc, char **argv)
     const int hop = D - 1;
     // every list and WAV is read and checked before the device is used
     std::vector<int> clean_rates, cv_rates;
-    const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, &clean_rates));
-    const Corpus noise = flatten(read_wav_list(WHO, "noise_list", P.noise_list));
+    const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, &clean_rates, nullptr, P.rate, P.device));
+    const Corpus noise = flatten(read_wav_list(WHO, "noise_list", P.noise_list, nullptr, nullptr, P.rate, P.device));
     check_noise(WHO, noise);
     std::vector<bp_mixture> plan = make_plan(P.seed, (int)clean.len.size(), P.mix_per_clean, noise, P.snr);
     check_rir_keys(WHO, P.rir, P.rir_list, P.cv_rir_list, "");
@@ -215,8 +222,8 @@ int main(int argc, char **argv)
     const int parts = P.target == BP_MIX_LPS_IRM || P.target == BP_MIX_LPS_IBM ? 2 : 1;
     if (P.layersizes[L - 1] != parts * D) fail("bpmix: layersizes[last] must be " + std::to_string(parts * D) + " for this target");
     if (P.layersizes[0] != ctx * D && P.layersizes[0] != (ctx + 1) * D) fail("bpmix: layersizes[0] must be fea_context*fea_dim (+ fea_dim with NAT)");
-    const Corpus cv_clean = flatten(read_wav_list(WHO, "cv_clean_list", P.cv_clean_list, &cv_rates));
-    const Corpus cv_noise = P.cv_noise_list.empty() ? noise : flatten(read_wav_list(WHO, "cv_noise_list", P.cv_noise_list));
+    const Corpus cv_clean = flatten(read_wav_list(WHO, "cv_clean_list", P.cv_clean_list, &cv_rates, nullptr, P.rate, P.device));
+    const Corpus cv_noise = P.cv_noise_list.empty() ? noise : flatten(read_wav_list(WHO, "cv_noise_list", P.cv_noise_list, nullptr, nullptr, P.rate, P.device));
     std::vector<bp_mixture> cv_plan = make_plan(P.cv_seed, (int)cv_clean.len.size(), 1, cv_noise, P.snr);
     const Reverb cv_rv = read_reverb(P, P.cv_rir_list.empty() ? "rir_list" : "cv_rir_list", P.cv_rir_list.empty() ? P.rir_list : P.cv_rir_list,
                                      P.rir.rooms ? (P.rir.cv_rooms ? P.rir.cv_rooms : P.rir.rooms) : 0, P.cv_seed, cv_rates);

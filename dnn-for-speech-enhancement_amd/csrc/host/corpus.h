@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -72,18 +73,69 @@ inline std::vector<float> read_one(const std::string &who, const std::string &pa
     return w;
 }
 
+// ---- rate=R: files of other rates converted on the device as they are loaded
+// a file of f Hz can be brought to R Hz (and back): checked where the file is read, before the device is used
+inline void check_convertible(const std::string &who, const std::string &path, int f, int R)
+{
+    int p = 0, q = 0;
+    if (f != R && bp_resample_ratio(f, R, &p, &q) != 0)
+        fail(who + ": " + path + " has " + std::to_string(f) + " Hz and rate=" + std::to_string(R) + " cannot convert it (" + bp_last_error() + ")");
+}
+// The recordings whose rate is not `to` become recordings at `to`: one bp_resample_waves call and one line on stdout per
+// distinct rate, in the order the rates first appear; the float samples go on as they come, nothing is re-quantised.
+// from != 0: the other direction -- every recording is at `from` and goes to its rates[k] (bpenhance, on the way out).
+inline void convert_rates(const std::string &who, const std::string &what, int device, int to, std::vector<std::vector<float>> &waves,
+                          const std::vector<int> &rates, int from = 0)
+{
+    std::vector<int> todo;
+    for (int f : rates)
+        if (f != (from ? from : to) && std::find(todo.begin(), todo.end(), f) == todo.end()) todo.push_back(f);
+    for (int f : todo) {
+        const int r_in = from ? from : f, r_out = from ? f : to;
+        int p = 0, q = 0;
+        check(bp_resample_ratio(r_in, r_out, &p, &q));
+        std::vector<float> pcm, out;
+        std::vector<int> lens;
+        std::vector<size_t> idx;
+        size_t n_out = 0;
+        for (size_t k = 0; k < waves.size(); ++k) {
+            if (rates[k] != f) continue;
+            if (waves[k].size() > (size_t)INT32_MAX) fail(who + ": " + what + ": recording " + std::to_string(k) + " is too long to convert");
+            int64_t no = 0;
+            check(bp_resample_len((int64_t)waves[k].size(), p, q, &no));
+            idx.push_back(k); lens.push_back((int)waves[k].size()); n_out += (size_t)no;
+            pcm.insert(pcm.end(), waves[k].begin(), waves[k].end());
+        }
+        out.resize(n_out);
+        check(bp_resample_waves(device, r_in, r_out, nullptr, (int)idx.size(), lens.data(), pcm.data(), out.data()));
+        size_t at = 0;
+        for (size_t k : idx) {
+            int64_t no = 0;
+            check(bp_resample_len((int64_t)waves[k].size(), p, q, &no));
+            waves[k].assign(out.begin() + at, out.begin() + at + no);
+            at += (size_t)no;
+        }
+        printf("%s: %s: %zu recording%s converted from %d Hz to %d Hz (%zu samples)\n", who.c_str(), what.c_str(), idx.size(),
+               idx.size() == 1 ? "" : "s", r_in, r_out, n_out);
+    }
+}
+
 // one WAV per line.  rates: the rate of every file, for the caller to judge (bpmix); one_rate: the rate every file must have,
-// 0 until the first one sets it, carried from list to list (bpeval)
+// 0 until the first one sets it, carried from list to list (bpeval).  to_rate != 0 (rate=R): a file may have any rate that can be
+// converted; the list comes back at to_rate, and so do *rates and *one_rate
 inline std::vector<std::vector<float>> read_wav_list(const std::string &who, const std::string &what, const std::string &list,
-                                                     std::vector<int> *rates = nullptr, int *one_rate = nullptr)
+                                                     std::vector<int> *rates = nullptr, int *one_rate = nullptr, int to_rate = 0, int device = 0)
 {
     std::vector<std::vector<float>> waves;
+    std::vector<int> file_rates;
     for (const std::string &p : read_lines(who, what, list)) {
-        int sr = one_rate ? *one_rate : 0;
+        int sr = one_rate && !to_rate ? *one_rate : 0;
         waves.push_back(read_one(who, p, &sr));
+        if (to_rate) { check_convertible(who, p, sr, to_rate); file_rates.push_back(sr); sr = to_rate; }
         if (one_rate) *one_rate = sr;
         if (rates) rates->push_back(sr);
     }
+    if (to_rate) convert_rates(who, what, device, to_rate, waves, file_rates);
     return waves;
 }
 

@@ -189,6 +189,10 @@ inline bool key_apply(const Key (&keys)[N], const char *tool, const Arg &a)
     return false;
 }
 
+// rate=R as the four WAV tools take it: one range, and in the lenient tools one text
+const long RATE_MAX = 1L << 30;
+const char *const RATE_TAIL = "is not a sample rate >= 1";
+
 // output_act / output_linear_dims / output_loss as bptrain, bpforward and bpenhance take them: strict, with their own texts (a
 // typo must not silently run a different model)
 inline bool output_key(const Arg &a, int *act, int *dims, int *loss)

@@ -579,6 +579,49 @@ int bp_lmstream_counts(int fea_dim, int init_frames, int64_t received, int ended
                        int64_t *samples_out);
 
 /* ------------------------------------------------------------------------------------
+ * Sample-rate conversion by a rational factor (no reference counterpart: its README sends its users to TIMIT at 16 kHz, NOISEX-92
+ * at 19.98 kHz and 100 noise types at 20 kHz for nets that work at 8 kHz, and leaves the conversion to outside tools).
+ * INTEGRATION.md 1m, DESIGN.md 24.  Defined to the bit, as the reverberation FIR above is.
+ *
+ * Ratio (bp_resample_ratio, host only): rate_out / rate_in = p / q in lowest terms.  Valid: both rates >= 1 and max(p, q) <= 1024
+ * (44100 <-> 48000 is 160/147, 44100 -> 16000 is 160/441, 19980 -> 16000 is 800/999, 44100 -> 8000 is 80/441); anything else is
+ * BP_ERR_ARG with the reduced ratio in the message.
+ *
+ * bp_resample_params {zeros, beta, rolloff}; bp_resample_defaults writes 16, 8.6, 0.9; a NULL params pointer means the defaults.
+ * Valid: 1 <= zeros <= 32, 0 <= beta <= 20, 0 < rolloff <= 1; anything else is BP_ERR_ARG.
+ *
+ * Taps (bp_resample_taps, host only), made in double: with m = max(p, q) and Lh = zeros m, for j = 0 .. 2 Lh
+ *   g[j] = I0(beta sqrt(1 - ((j - Lh) / Lh)^2)) / I0(beta) * sinc(rolloff (j - Lh) / m)
+ *   h[j] = fl32(p g[j] / sum g)                                     the sum taken for j ascending
+ * I0 is the modified Bessel function's power series sum_k ((x/2)^k / k!)^2 summed until a term no longer changes the sum;
+ * sinc(u) = sin(pi u) / (pi u), sinc(0) = 1.  n_taps must be 2 zeros max(p, q) + 1.  The taps are fp32 on purpose: the product of
+ * an fp32 tap and an fp32 sample is exact in double, so a fused multiply-add cannot change a bit of what follows.
+ *
+ * Output: a sentence x of n >= 1 samples gives n_out = ceil(n p / q) samples (bp_resample_len, host only, in int64):
+ *   y[k] = fl32( sum_j (double)h[j] * (double)x[(k q + Lh - j) / p] )
+ * over the j with p | (k q + Lh - j) and 0 <= (k q + Lh - j) / p < n, accumulated in double from +0.0 for j ascending, one term
+ * after the other.  This is the placement of scipy.signal.resample_poly(x, p, q) with the filter's delay compensated; with
+ * (zeros, beta, rolloff) = (10, 5, 1) it is the formula of the STOI resampler above.  rate_in == rate_out returns the bits of
+ * the input and filters nothing.  Sentences never see each other's samples.  One lane owns one output sample: no float atomics and
+ * no sum across lanes -- the same bits on every run, and for a sentence alone or in any company.
+ *
+ * bp_resample_waves (no handle): sentence s of sent_len[s] >= 1 samples, back to back in pcm; out holds sum n_out samples, back to
+ * back.  One host->device copy, one launch, one device->host copy, one synchronisation (rate_in == rate_out: no device work).
+ * Every argument is checked before the device is touched: BP_ERR_ARG for a bad ratio or parameter, n_sent < 1, null pointers, an
+ * empty sentence, or 2^31 output samples or more in one call. */
+typedef struct bp_resample_params {
+    int    zeros;        /* zero crossings of the sinc on each side of its centre, counted at the lower of the two rates */
+    double beta;         /* Kaiser window parameter */
+    double rolloff;      /* cutoff as a fraction of the lower rate's Nyquist frequency */
+} bp_resample_params;
+int bp_resample_defaults(bp_resample_params *p);
+int bp_resample_ratio(int rate_in, int rate_out, int *p, int *q);
+int bp_resample_len(int64_t n, int p, int q, int64_t *n_out);
+int bp_resample_taps(int p, int q, const bp_resample_params *params, float *h, int n_taps);
+int bp_resample_waves(int device, int rate_in, int rate_out, const bp_resample_params *p, int n_sent, const int *sent_len,
+                      const float *pcm, float *out);
+
+/* ------------------------------------------------------------------------------------
  * Gradients without the update (parity tests; no reference counterpart -- the reference never
  * exposes layer_ydedx).  bp_grads_resident runs forward + backward of ONE local bunch starting at
  * chunk frame first_frame with the kernels of the data-parallel step and leaves the weight and bias
