@@ -3,6 +3,10 @@ tests/test_dp_native.py, one process per rank; ranks may share one device.  No t
 the exchange is the library's own (hipIpc peer kernels), the rendezvous a shared-memory block.
 
     python tests/dp_worker.py <case.json> <rank> <outdir>
+
+"exchange": true in the case (tests/test_dp_exchange_gpu.py) makes the rank run two training calls of exactly one global minibatch each
+-- the second under the hyper-parameters "hyper2", assigned as a caller of the reference assigns them -- and save, after each call,
+its OWN stored gradient (read_grads of the attached handle), the weights and the gathered momentum state.
 """
 import json
 import os
@@ -54,6 +58,8 @@ def main():
     g.dp_attach(world, rank, c["key"], transport=c.get("transport", 0))
     peers = [g.dp_peer_info(p) for p in range(world)]
     idx = shard_rows(x.shape[0], B * world, world, rank)
+    if c.get("exchange"):
+        return exchange_calls(c, rank, outdir, g, x, t, idx, peers)
     # two calls: the exchange state (epochs, flags) must carry across training calls
     half = (c["nb"] // 2) * B
     if half:
@@ -67,6 +73,29 @@ def main():
     json.dump({"device": rank % ndev, "ndev": ndev, "peers": peers}, open(os.path.join(outdir, "rank%d.json" % rank), "w"))
     for l in range(1, len(ls)):
         out["W%d" % l], out["b%d" % l], out["dW%d" % l], out["db%d" % l] = w[l], bb[l], dw[l], dbb[l]
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), **out)
+    g.dp_detach()
+    g.close()
+
+
+def exchange_calls(c, rank, outdir, g, x, t, idx, peers):
+    """The opt-in mode of tests/test_dp_exchange_gpu.py: see the module docstring.  Arrays: <name><layer>_<call>."""
+    ls, B = c["ls"], c["B"]
+    assert c["nb"] == 2 and idx.size == 2 * B, (c["nb"], idx.size)
+    out = {}
+    for call in (1, 2):
+        if call == 2:
+            g.momentum, g.weightcost, g.lrate = c["hyper2"]["m"], c["hyper2"]["wc"], c["hyper2"]["lr"]
+        rows = idx[(call - 1) * B:call * B]
+        g.train(B, x[rows], t[rows])
+        gw, gb = g.read_grads()
+        w, bb = g.get_weights()
+        dw, dbb = g.get_deltas()                  # collective
+        for l in range(1, len(ls)):
+            for nm, a in (("G", gw), ("g", gb), ("W", w), ("b", bb), ("dW", dw), ("db", dbb)):
+                out["%s%d_%d" % (nm, l, call)] = a[l]
+    out["epochs"] = np.int64(g.dp_info()[2])
+    json.dump({"peers": peers, "handoff": "in_kernel" if g.dp_handoff() else "events"}, open(os.path.join(outdir, "rank%d.json" % rank), "w"))
     np.savez(os.path.join(outdir, "rank%d.npz" % rank), **out)
     g.dp_detach()
     g.close()
