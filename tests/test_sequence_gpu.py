@@ -13,183 +13,15 @@ Per walk three long-lived handles take part, all made from the same weights and 
       of whatever is resident, F is also given the chunk of the call that made it resident on S (_load).
 Every expected error is a host-side check: its status and a non-empty message are checked on S and S2, and the checkpoints behind it
 still equal R, which never made the call."""
-import re
-
-import numpy as np
 import pytest
 
-import mix_np as MX
 import sequence_model as SM
+import walk_harness as H
 
 pytestmark = pytest.mark.gpu
 
 PARAMS = [(c.id, w) for c in SM.CONFIGS for w in SM.walk_ids(c)]
-SEED = 77
-
-
-def _plan(pkg, rows):
-    p = np.zeros(len(rows), pkg.MIXTURE_DTYPE)
-    for i, r in enumerate(rows):
-        p[i] = r
-    return p
-
-
-def _make(pkg, cfg, W, b, st, cor):
-    """A handle in model state st (preset, output setting, forward mode) with the corpus."""
-    lr, m, wc, flag = SM.PRESETS[st["preset"]]
-    oa, ol, lo = cfg.outs[st["out"]]
-    g = pkg.BP_GPU(1, len(cfg.ls), cfg.ls, cfg.B, lr, m, wc, W, b, dropoutflag=flag, visible_omit=SM.VISIBLE_OMIT, hid_omit=SM.HID_OMIT,
-                   activation=cfg.act, seed=SEED, max_chunk_frames=SM.CAP, compute_dtype=cfg.dtype, output_activation=oa,
-                   output_linear_cols=ol, output_loss=lo, forward_mode=st["fwd"])
-    g.set_mix_corpus(cor["clean"], cor["noise"], cor["mean"], cor["inv_std"], SM.CONTEXT, SM.TARG_OFFSET, cfg.corpus_target)
-    return g
-
-
-def _win(d):
-    return (d["fea"], d["targ_frames"], SM.CONTEXT, d["win_start"], d["targ_frame"]), dict(nat=d["nat"], nat_row=d["nat_row"])
-
-
-def _state(g):
-    (w, b), (dw, db) = g.get_weights(), g.get_deltas()
-    return [a for l in range(1, g.numlayers) for a in (w[l], b[l], dw[l], db[l])]
-
-
-def _wave_target(pkg, cfg, masked):
-    """(target, out_col): the LPS columns, or on the two-part nets the mask columns."""
-    return (pkg.WAVE_MASK, SM.FEA_DIM) if masked and cfg.ls[-1] == 2 * SM.FEA_DIM else (pkg.WAVE_LPS, 0)
-
-
-def _exec(pkg, g, cfg, cor, step, d):
-    """Make the call of one model step on g; the arrays it returns."""
-    k, B = step.kind, cfg.B
-    if k == "train":
-        g.train(d["x"].shape[0], d["x"], d["t"])
-    elif k == "train_windows":
-        a, kw = _win(d)
-        g.train_windows(*a, **kw)
-    elif k == "upload_train":
-        g.upload_chunk(d["x"], d["t"])
-        g.train_resident(B, B)
-        g.train_resident(0, 2 * B)
-    elif k == "train_resident":
-        g.train_resident(0, B)
-    elif k == "train_mix":
-        g.train_mix(_plan(pkg, d["plan"]), d["order"])
-    elif k == "preset":                                        # assigned like `TrainObj->lrate = ...`; the next call that runs the net pushes them
-        g.lrate, g.momentum, g.weightcost, g.dropoutflag = SM.PRESETS[step.after["preset"]]
-    elif k == "set_output":
-        g.set_output(*cfg.outs[step.after["out"]])
-    elif k == "set_forward":
-        g.set_forward(step.before["fwd"] ^ 1)
-    elif k == "forward":
-        return [g.forward(d["x"])]
-    elif k == "cv":
-        return [np.float32(g.CrossValid(d["x"].shape[0], d["x"], d["t"]))]
-    elif k == "cv_windows":
-        a, kw = _win(d)
-        return [np.float32(g.CrossValid_windows(*a, **kw))]
-    elif k == "cv_mix":
-        return [np.float32(g.CrossValid_mix(_plan(pkg, d["plan"])))]
-    elif k == "mix_features":
-        f = g.mix_features(_plan(pkg, d["plan"]))
-        return [f[n] for n in ("fea", "lps", "targ", "nat", "pcm")]
-    elif k == "enhance":
-        t, c = _wave_target(pkg, cfg, False)
-        waves, nets = g.enhance_waves(d["sentences"], cor["mean"], cor["inv_std"], SM.CONTEXT, SM.TARG_OFFSET, target=t, out_col=c,
-                                      return_net=True)
-        return list(waves) + list(nets)
-    elif k == "eval_mix":
-        t, c = _wave_target(pkg, cfg, True)
-        r = g.eval_mix(_plan(pkg, d["plan"]), SM.SAMPLE_RATE, target=t, out_col=c, return_pcm=True)
-        return [r["noisy"], r["enhanced"]] + list(r["pcm"])
-    elif k == "grads":
-        g.upload_chunk(d["x"], d["t"])
-        g.grads_resident(3)                                    # an unaligned first frame; the bunch ends with the chunk
-        gw, gb = g.read_grads()
-        return gw[1:] + gb[1:]
-    elif k == "grads_resident":
-        g.grads_resident(0)
-        gw, gb = g.read_grads()
-        return gw[1:] + gb[1:]
-    elif k == "stream":
-        t, c = _wave_target(pkg, cfg, False)
-        s = g.stream_open(cor["mean"], cor["inv_std"], SM.CONTEXT, SM.TARG_OFFSET, target=t, out_col=c, n_chan=1, max_push_samples=256)
-        try:
-            n = len(d["blocks"])
-            return [s.push([blk], end=[i == n - 1])[0] for i, blk in enumerate(d["blocks"])]
-        finally:
-            s.close()
-    elif k == "checkpoint":
-        return _state(g)
-    else:
-        raise AssertionError(k)
-    return []
-
-
-def _load(pkg, g, kind, d):
-    """Make the chunk that a call of `kind` with data d leaves resident WITH targets, without its training or its reads."""
-    if kind == "mix_features":
-        g.mix_features(_plan(pkg, d["plan"]))
-    elif kind in ("train", "upload_train", "grads"):
-        g.upload_chunk(d["x"], d["t"])
-    elif kind == "train_windows":
-        a, kw = _win(d)
-        g.upload_chunk_windows(*a, **kw)
-    elif kind == "train_mix":
-        # the shuffled chunk that bp_train_mix makes on the device, fed from the host as tests/test_mix_gpu.py feeds it (the same bits:
-        # test_training_equals_window_path)
-        plan = _plan(pkg, d["plan"])
-        f, frames = g.mix_features(plan), g.mix_frames(plan)
-        rows = MX.staged_rows(f["fea"], frames, SM.CONTEXT, SM.TARG_OFFSET)
-        tg = np.zeros((rows.shape[0], f["targ"].shape[1]), np.float32)
-        tg[:f["targ"].shape[0]] = f["targ"]
-        ws, tf, nr = MX.window_tables(frames, SM.CONTEXT, d["order"])
-        g.upload_chunk_windows(rows, tg, SM.CONTEXT, ws, tf, nat=f["nat"], nat_row=nr)
-    else:
-        raise AssertionError(kind)
-
-
-def _words(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.int64)
-
-
-def _differing(got, want, what):
-    assert len(got) == len(want), (what, len(got), len(want))
-    n = 0
-    for u, v in zip(got, want):
-        if u is None or v is None:
-            assert u is None and v is None, what
-            continue
-        u, v = _words(u).reshape(-1), _words(v).reshape(-1)
-        assert u.shape == v.shape, (what, u.shape, v.shape)
-        n += int(np.count_nonzero(u != v))
-    return n
-
-
-def _expect_error(pkg, g, cfg, cor, step, d):
-    with pytest.raises(pkg.BPError) as e:
-        _exec(pkg, g, cfg, cor, step, d)
-    m = re.match(r"^(.*) \(status (-?\d+)\)$", str(e.value), re.S)
-    assert m, str(e.value)
-    assert int(m.group(2)) == step.status, (step.pos, step.kind, SM.STATUS_NAMES[step.status], str(e.value))
-    assert m.group(1).strip(), "empty bp_last_error"
-
-
-def _advance(g, cfg, n_bunches, W, b):
-    """Bring g's dropout stream to position n_bunches without moving its weights."""
-    saved = (g.lrate, g.momentum, g.weightcost)
-    g.lrate, g.momentum, g.weightcost = 0.0, 0.0, 0.0
-    per = SM.CAP // cfg.B
-    g.fill_chunk_synthetic(per * cfg.B)
-    left = n_bunches
-    while left > 0:
-        k = min(per, left)
-        g.train_resident(0, k * cfg.B)
-        left -= k
-    g.lrate, g.momentum, g.weightcost = saved
-    w, bb = g.get_weights()
-    assert _differing(w[1:] + bb[1:], W[1:] + b[1:], "advance") == 0
+_make, _state, _differing = H.make, H.state, H.differing
 
 
 @pytest.mark.parametrize("cid,wid", PARAMS, ids=["%s-%s" % p for p in PARAMS])
@@ -198,81 +30,8 @@ def test_walk(pkg, parity_record, cid, wid):
     walk, calls = SM.walk_calls(cfg, wid)
     steps = SM.run_model(cfg, calls)
     data = [SM.call_data(cfg, walk, s.pos, s.kind) for s in steps]
-    cor = SM.corpus(cfg)
-    W0, b0 = pkg.glorot_net(cfg.ls, seed=5 + cfg.index, beta=0.5)
-    fresh = SM.fresh_state()
-    S, R, S2 = (_make(pkg, cfg, W0, b0, fresh, cor) for _ in range(3))
-    diff = {"state_vs_replay": 0, "query_vs_fresh": 0, "second_pass": 0}
-    bad = []                                                   # (comparison, what, words) of everything that differs
-
-    def compare(key, got, want, what):
-        n = _differing(got, want, what)
-        diff[key] += n
-        if n:
-            bad.append((key, what, n))
-    count = {"calls": len(steps), "queries_compared": 0, "expected_errors": 0, "checkpoints": 0, "replay_loads": 0}
-    try:
-        # ---- pass 1: the subject
-        outs = {}
-        for i, (s, d) in enumerate(zip(steps, data)):
-            if s.status != SM.BP_OK:
-                _expect_error(pkg, S, cfg, cor, s, d)
-                count["expected_errors"] += 1
-            else:
-                outs[i] = _exec(pkg, S, cfg, cor, s, d)
-        # ---- the replay: training kinds and checkpoints
-        r_maker = None
-        for i, (s, d) in enumerate(zip(steps, data)):
-            if s.status != SM.BP_OK:
-                continue
-            if s.kind == "checkpoint":
-                compare("state_vs_replay", outs[i], _exec(pkg, R, cfg, cor, s, d), ("checkpoint", s.pos))
-                count["checkpoints"] += 1
-                continue
-            if not SM.KINDS[s.kind].training:
-                continue
-            if s.kind == "train_resident" and s.before["maker"] != r_maker:
-                mk, mp = s.before["maker_kind"], s.before["maker"]
-                assert mk in SM.LOADABLE, mk
-                _load(pkg, R, mk, SM.call_data(cfg, walk, mp, mk))
-                r_maker = mp
-                count["replay_loads"] += 1
-            _exec(pkg, R, cfg, cor, s, d)
-            if s.after["maker"] == s.pos and s.after["maker_kind"] == s.kind:
-                r_maker = s.pos
-        end_S = _state(S)
-        compare("state_vs_replay", end_S, _state(R), "end of the walk")
-        assert all(np.isfinite(a).all() for a in end_S), "the walk left the net non-finite"
-        # ---- pass 2: a fresh handle per query
-        cache = None
-        for i, (s, d) in enumerate(zip(steps, data)):
-            if s.status != SM.BP_OK:
-                _expect_error(pkg, S2, cfg, cor, s, d)
-                continue
-            k = SM.KINDS[s.kind]
-            if not k.training and s.kind not in ("checkpoint", "set_forward"):
-                if cache is None:
-                    cache = S2.get_weights()
-                F = _make(pkg, cfg, cache[0], cache[1], s.before, cor)
-                try:
-                    if s.kind in ("grads", "grads_resident"):
-                        _advance(F, cfg, s.before["bunches"], cache[0], cache[1])
-                    if s.kind == "grads_resident":
-                        mk, mp = s.before["maker_kind"], s.before["maker"]
-                        _load(pkg, F, mk, SM.call_data(cfg, walk, mp, mk))
-                    compare("query_vs_fresh", _exec(pkg, F, cfg, cor, s, d), outs[i], (s.pos, s.kind, "after", steps[i - 1].kind if i else None))
-                finally:
-                    F.close()
-                count["queries_compared"] += 1
-            o2 = _exec(pkg, S2, cfg, cor, s, d)
-            if not k.training:
-                compare("second_pass", o2, outs[i], (s.pos, s.kind))
-            else:
-                cache = None
-        compare("second_pass", _state(S2), end_S, "end of the second pass")
-    finally:
-        for g in (S, R, S2):
-            g.close()
+    count, diff, bad = H.run_walk(pkg, cfg, steps, data, SM.corpus(cfg))
+    assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0     # (a size of the walks of tests/size_model.py)
     parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), **dict(count, **diff))
     print(cid, wid, count, diff)
     assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
