@@ -9,7 +9,7 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      REVERB_TARGET_EARLY, MIX_RIR_MAX_TAPS, reverb_waves, rir_delay, mix_reverb_pairs, score_waves, SCORE_SSNR, SCORE_LSD, SCORE_STOI,
                      SCORE_ESTOI, SCORE_SISDR,
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
-                     LogmmseStream, logmmse_stream_open, logmmse_stream_counts,
+                     LogmmseStream, logmmse_stream_open, logmmse_stream_counts, BPNoiseParams, noise_params, NOISE_VAD, NOISE_SPP,
                      rir_image, rir_rooms, rir_beta, rir_orders, rir_window_default, BPRirRange, RIR_ROOM_DTYPE, RIR_RANGE_DEFAULTS,
                      RIR_MAX_IMAGES,
                      BPResampleParams, resample_waves, resample_ratio, resample_len, resample_taps, resample_params)

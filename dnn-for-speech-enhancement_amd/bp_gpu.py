@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
     "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
+    "bp_noise_defaults", "bp_logmmse_waves_nt", "bp_eval_mix_logmmse_nt", "bp_lmstream_open_nt",
     "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
@@ -133,6 +134,17 @@ class BPLogmmseParams(C.Structure):
     ]
 
 
+class BPNoiseParams(C.Structure):
+    """bp_noise_params (include/bp_c_api.h): the noise update of the log-MMSE baseline."""
+    _fields_ = [
+        ("mode", C.c_int), ("xi_h1_db", C.c_double), ("q", C.c_double), ("a_pow", C.c_double), ("a_spp", C.c_double),
+        ("p_lo", C.c_double), ("p_cap", C.c_double),
+    ]
+
+
+NOISE_VAD, NOISE_SPP = 0, 1
+
+
 class BPResampleParams(C.Structure):
     """bp_resample_params (include/bp_c_api.h): the windowed-sinc filter of the sample-rate converter."""
     _fields_ = [("zeros", C.c_int), ("beta", C.c_double), ("rolloff", C.c_double)]
@@ -212,6 +224,13 @@ def load_library(path=None):
     lib.bp_lmstream_open.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.bp_lmstream_push.argtypes = [C.c_void_p, C.POINTER(C.c_int), fp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int), fp, C.c_size_t]
     lib.bp_lmstream_close.argtypes = [C.c_void_p]
+    lib.bp_noise_defaults.argtypes = [C.POINTER(BPNoiseParams)]
+    lib.bp_logmmse_waves_nt.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.POINTER(BPNoiseParams), C.c_int, C.POINTER(C.c_int),
+                                        fp, fp, fp, fp, fp]
+    lib.bp_eval_mix_logmmse_nt.argtypes = [hp, C.POINTER(BPLogmmseParams), C.POINTER(BPNoiseParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                           fp, fp, fp]
+    lib.bp_lmstream_open_nt.argtypes = [C.c_int, C.c_int, C.POINTER(BPLogmmseParams), C.POINTER(BPNoiseParams), C.c_int, C.c_int,
+                                        C.POINTER(C.c_void_p)]
     lib.bp_lmstream_counts.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
     lib.bp_resample_defaults.argtypes = [C.POINTER(BPResampleParams)]
     lib.bp_resample_ratio.argtypes = [C.c_int, C.c_int, ip, ip]
@@ -608,10 +627,10 @@ class BP_GPU(object):
             pcm = np.split(pcm[:int(lens.sum())], np.cumsum(lens)[:-1])
         return {"noisy": noisy[:p.size], "enhanced": enh[:p.size], "pcm": pcm}
 
-    def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False, extended=False):
+    def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False, extended=False, noise=None):
         """bp_eval_mix_logmmse: eval_mix with the log-MMSE baseline in place of the net (params: None for the defaults, a dict of
         bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix (extended: five columns,
-        bp_eval_mix_logmmse_ext)."""
+        bp_eval_mix_logmmse_ext).  noise: as for logmmse_waves (anything but None: bp_eval_mix_logmmse_nt)."""
         p, pp = self._plan(plan)
         ns = 5 if extended else 3
         noisy = np.empty((max(p.size, 1), ns), np.float32)
@@ -622,7 +641,11 @@ class BP_GPU(object):
             pcm = np.empty(max(int(lens.sum()), 1), np.float32)
         lm = logmmse_params(params)
         lmp = None if lm is None else C.byref(lm)
-        if extended:
+        if noise is not None:
+            nz = noise_params(noise)
+            self._check(self._lib.bp_eval_mix_logmmse_nt(self._h, lmp, C.byref(nz), p.size, pp, int(sample_rate), ns, _fp(noisy), _fp(enh),
+                                                         _fp(pcm) if pcm is not None else None))
+        elif extended:
             self._check(self._lib.bp_eval_mix_logmmse_ext(self._h, lmp, p.size, pp, int(sample_rate), ns, _fp(noisy), _fp(enh),
                                                           _fp(pcm) if pcm is not None else None))
         else:
@@ -868,19 +891,55 @@ def logmmse_params(params=None):
     return lm
 
 
-def logmmse_waves(device, fea_dim, sentences, params=None, return_gain=False, return_vad=False):
+def noise_params(noise=None):
+    """A BPNoiseParams: bp_noise_defaults (the MMSE-SPP tracker) for None or "spp", the VAD-gated update for "vad", the defaults
+    overridden by the fields of a dict (mode: 0 / 1 or "vad" / "spp"), or the BPNoiseParams given."""
+    if isinstance(noise, BPNoiseParams):
+        return noise
+    lib = load_library()
+    nz = BPNoiseParams()
+    lib.bp_noise_defaults(C.byref(nz))
+    modes = {"vad": NOISE_VAD, "spp": NOISE_SPP}
+    if noise is None:
+        return nz
+    if isinstance(noise, str):
+        noise = {"mode": noise}
+    names = [f[0] for f in BPNoiseParams._fields_]
+    for k, v in dict(noise).items():
+        if k not in names:
+            raise BPError("noise_params: unknown field %s" % k)
+        if k == "mode":
+            if isinstance(v, str) and v not in modes:
+                raise BPError("noise_params: unknown mode %s" % v)
+            nz.mode = modes[v] if isinstance(v, str) else int(v)
+        else:
+            setattr(nz, k, float(v))
+    return nz
+
+
+def logmmse_waves(device, fea_dim, sentences, params=None, return_gain=False, return_vad=False, noise=None, return_noise=False):
     """bp_logmmse_waves: every sentence enhanced by the log-MMSE baseline (no handle, no net): a list of float32 arrays, or with
-    return_gain / return_vad a tuple (pcm, gain [T_s][fea_dim] per sentence, vad [T_s] per sentence; the ones not asked for omitted)."""
+    return_gain / return_vad / return_noise a tuple (pcm, gain [T_s][fea_dim] per sentence, vad [T_s] per sentence, noise
+    [T_s][fea_dim] per sentence; the ones not asked for omitted).  noise: None for the call as it always was, else "spp", "vad",
+    a dict of bp_noise_params fields or a BPNoiseParams (noise_params): bp_logmmse_waves_nt.  return_noise needs the latter call
+    and, with noise None, makes it in VAD mode: the same bits, and the lambda every frame's gamma used."""
     lib = load_library()
     pcm, lens, frames = _sentences(sentences, int(fea_dim))
     T = int(frames.sum())
     out = np.empty(max(pcm.size, 1), np.float32)
     gain = np.empty((max(T, 1), int(fea_dim)), np.float32) if return_gain else None
     vad = np.empty(max(T, 1), np.float32) if return_vad else None
+    nse = np.empty((max(T, 1), int(fea_dim)), np.float32) if return_noise else None
     lm = logmmse_params(params)
-    rc = lib.bp_logmmse_waves(int(device), int(fea_dim), None if lm is None else C.byref(lm), len(lens),
-                              lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out), None if gain is None else _fp(gain),
-                              None if vad is None else _fp(vad))
+    if noise is None and not return_noise:
+        rc = lib.bp_logmmse_waves(int(device), int(fea_dim), None if lm is None else C.byref(lm), len(lens),
+                                  lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out), None if gain is None else _fp(gain),
+                                  None if vad is None else _fp(vad))
+    else:
+        nz = noise_params("vad" if noise is None else noise)
+        rc = lib.bp_logmmse_waves_nt(int(device), int(fea_dim), None if lm is None else C.byref(lm), C.byref(nz), len(lens),
+                                     lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm), _fp(out), None if gain is None else _fp(gain),
+                                     None if vad is None else _fp(vad), None if nse is None else _fp(nse))
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     res = [np.split(out[:pcm.size], np.cumsum(lens)[:-1])]
@@ -888,6 +947,8 @@ def logmmse_waves(device, fea_dim, sentences, params=None, return_gain=False, re
         res.append(np.split(gain[:T], np.cumsum(frames)[:-1]))
     if return_vad:
         res.append(np.split(vad[:T], np.cumsum(frames)[:-1]))
+    if return_noise:
+        res.append(np.split(nse[:T], np.cumsum(frames)[:-1]))
     return res[0] if len(res) == 1 else tuple(res)
 
 
@@ -932,12 +993,18 @@ class LogmmseStream(object):
             pass
 
 
-def logmmse_stream_open(device, fea_dim, params=None, n_chan=1, max_push_samples=16000):
-    """bp_lmstream_open: a LogmmseStream of n_chan channels on a device ordinal (params as for logmmse_waves)."""
+def logmmse_stream_open(device, fea_dim, params=None, n_chan=1, max_push_samples=16000, noise=None):
+    """bp_lmstream_open: a LogmmseStream of n_chan channels on a device ordinal (params and noise as for logmmse_waves; noise
+    other than None: bp_lmstream_open_nt)."""
     lib = load_library()
     lm = logmmse_params(params)
     s = C.c_void_p()
-    rc = lib.bp_lmstream_open(int(device), int(fea_dim), None if lm is None else C.byref(lm), int(n_chan), int(max_push_samples), C.byref(s))
+    lmp = None if lm is None else C.byref(lm)
+    if noise is None:
+        rc = lib.bp_lmstream_open(int(device), int(fea_dim), lmp, int(n_chan), int(max_push_samples), C.byref(s))
+    else:
+        nz = noise_params(noise)
+        rc = lib.bp_lmstream_open_nt(int(device), int(fea_dim), lmp, C.byref(nz), int(n_chan), int(max_push_samples), C.byref(s))
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     if lm is None:

@@ -698,7 +698,7 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
 
 // bp_eval_mix (lm == null: the net's output columns [out_col, out_col + D) as `target`) and bp_eval_mix_logmmse (lm: the checked
 // parameters; the gain rows of the recursion as BP_WAVE_MASK): one sequence, one enhancer swapped for the other
-static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const Call &c, const bp_mixture *m, int sample_rate, int target,
+static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const NoiseP &nz, const Call &c, const bp_mixture *m, int sample_rate, int target,
                         int out_col, int NS, float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
     int r;
@@ -735,7 +735,7 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     float *ola = (float *)ms->ev_ola.p, *lps_s = (float *)ms->ev_lps.p, *lps_e = (float *)((char *)ms->ev_lps.p + lps_b);
     if (lm) {
         float *gain = (float *)ms->ev_gain.p;
-        HIPCHK(logmmse_gain_launch(*lm, Y, F, n_mix, D, gain, gain + c.frames * D, h->stream));
+        HIPCHK(logmmse_gain_launch(*lm, nz, Y, F, n_mix, D, gain, gain + c.frames * D, nullptr, h->stream));
         HIPCHK(wave_synthesis_launch(gain, D, 0, Y, win, tw, ms->log2M, D, BP_WAVE_MASK, (float *)ms->ev_syn.p, n, h->stream));
     } else
         HIPCHK(wave_synthesis_launch(h->out_chunk.as<float>(), h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
@@ -779,18 +779,21 @@ static int eval_mix_net(const char *who, bp_handle *h, int n_mix, const bp_mixtu
     const int D = h->mix->D, sL = h->s[h->L - 1];
     if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, std::string(who) + ": target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, std::string(who) + ": out_col + fea_dim exceeds layersizes[last]");
-    return eval_mix_run(who, h, nullptr, c, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
+    return eval_mix_run(who, h, nullptr, noise_vad(), c, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 
-// bp_eval_mix_logmmse (n_scores = BP_SCORE_N) and bp_eval_mix_logmmse_ext
-static int eval_mix_lm(const char *who, bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate, int n_scores,
+// bp_eval_mix_logmmse (n_scores = BP_SCORE_N), bp_eval_mix_logmmse_ext and (nt: the noise update of np; else the VAD-gated one
+// whatever np) bp_eval_mix_logmmse_nt
+static int eval_mix_lm(const char *who, bp_handle *h, const bp_logmmse_params *p, bool nt, const bp_noise_params *np, int n_mix, const bp_mixture *m, int sample_rate, int n_scores,
                        float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
     Call c;
     LogmmseP lp;
+    NoiseP nz = noise_vad();
     int r;
-    if ((r = eval_n_scores(who, n_scores)) != BP_OK || (r = logmmse_check(who, p, lp)) != BP_OK || (r = plan_call(h, who, n_mix, m, c)) != BP_OK) return r;
-    return eval_mix_run(who, h, &lp, c, m, sample_rate, BP_WAVE_MASK, 0, n_scores, noisy_scores, enh_scores, enh_pcm);
+    if ((r = eval_n_scores(who, n_scores)) != BP_OK || (r = logmmse_check(who, p, lp)) != BP_OK || (nt && (r = noise_check(who, np, nz)) != BP_OK) ||
+        (r = plan_call(h, who, n_mix, m, c)) != BP_OK) return r;
+    return eval_mix_run(who, h, &lp, nz, c, m, sample_rate, BP_WAVE_MASK, 0, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,
@@ -808,13 +811,19 @@ extern "C" int bp_eval_mix_ext(bp_handle *h, int n_mix, const bp_mixture *m, int
 extern "C" int bp_eval_mix_logmmse(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate,
                                    float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
-    return eval_mix_lm("bp_eval_mix_logmmse", h, p, n_mix, m, sample_rate, BP_SCORE_N, noisy_scores, enh_scores, enh_pcm);
+    return eval_mix_lm("bp_eval_mix_logmmse", h, p, false, nullptr, n_mix, m, sample_rate, BP_SCORE_N, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_eval_mix_logmmse_ext(bp_handle *h, const bp_logmmse_params *p, int n_mix, const bp_mixture *m, int sample_rate, int n_scores,
                                        float *noisy_scores, float *enh_scores, float *enh_pcm)
 {
-    return eval_mix_lm("bp_eval_mix_logmmse_ext", h, p, n_mix, m, sample_rate, n_scores, noisy_scores, enh_scores, enh_pcm);
+    return eval_mix_lm("bp_eval_mix_logmmse_ext", h, p, false, nullptr, n_mix, m, sample_rate, n_scores, noisy_scores, enh_scores, enh_pcm);
+}
+
+extern "C" int bp_eval_mix_logmmse_nt(bp_handle *h, const bp_logmmse_params *p, const bp_noise_params *np, int n_mix, const bp_mixture *m,
+                                      int sample_rate, int n_scores, float *noisy_scores, float *enh_scores, float *enh_pcm)
+{
+    return eval_mix_lm("bp_eval_mix_logmmse_nt", h, p, true, np, n_mix, m, sample_rate, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 
 extern "C" int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const int64_t *noise_len, int n_snr,

@@ -9,6 +9,7 @@
 //             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv] [rate=8000]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
 //             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6] [lm_stream_block=<samples> [lm_stream_chan=<n>]]
+//             [lm_noise=vad|spp]
 //
 // As many sentences go into one call as fit traincache rows (frames + context-1 replicated edge rows per sentence).  The
 // output is PCM16 at the input's sample rate, rounded to nearest and clipped.  Every input is read and checked before the
@@ -21,7 +22,8 @@
 // INTEGRATION.md 1h): no weights, no norm file; it takes only the keys of its line above, and the lm_ keys only go with it.
 // With lm_stream_block the files go through a log-MMSE stream (bp_lmstream_push) by the rules of stream_block:
 // file s to channel s mod lm_stream_chan, lm_stream_block samples per push, the end flag on a file's last block; the output
-// files hold the bytes of a run without the key.
+// files hold the bytes of a run without the key.  lm_noise=spp gives the baseline, streamed or not, the MMSE-SPP noise tracker
+// (bp_logmmse_waves_nt, bp_lmstream_open_nt); vad, the default, is a run without the key.
 // rate=R: the rate the net works at.  A file at another rate f is converted to R on the device
 // (bp_resample_waves), enhanced, converted back to f, trimmed to its original length and written at f as without the key; what it
 // held above R/2 is gone.  One call and one line on stdout per distinct rate and direction.  Not with stream_block or
@@ -53,7 +55,7 @@ static void wav_pairs(const std::string &list, const std::string &in_wav, const 
 }
 
 // method=logmmse: every file through bp_logmmse_waves, as many sentences per call as stay below MAXCACHEFRAME frames
-static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, const std::vector<std::string> &ins, const std::vector<std::string> &outs)
+static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, const bp_noise_params *nz, const std::vector<std::string> &ins, const std::vector<std::string> &outs)
 {
     const int ns = (int)ins.size(), hop = fea_dim - 1;
     std::vector<std::vector<float>> waves(ns);
@@ -78,7 +80,8 @@ static int logmmse_mode(int fea_dim, int device, const bp_logmmse_params &lm, co
             ++s1;
         }
         out.resize(pcm.size());
-        check(bp_logmmse_waves(device, fea_dim, &lm, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr));
+        if (nz) check(bp_logmmse_waves_nt(device, fea_dim, &lm, nz, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr, nullptr));
+        else check(bp_logmmse_waves(device, fea_dim, &lm, s1 - s0, lens.data(), pcm.data(), out.data(), nullptr, nullptr));
         size_t off = 0;
         for (int s = s0; s < s1; ++s) {
             const std::string e = bp::write_wav(outs[s], &out[off], waves[s].size(), rates[s]);
@@ -138,7 +141,7 @@ static size_t play_files(S *st, int (*push)(S *, const int *, const float *, con
 }
 
 // method=logmmse lm_stream_block=...: the files through a log-MMSE stream
-static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params &lm, int block, int chan, const std::vector<std::string> &ins,
+static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params &lm, const bp_noise_params *nz, int block, int chan, const std::vector<std::string> &ins,
                                const std::vector<std::string> &outs)
 {
     const int ns = (int)ins.size(), hop = fea_dim - 1;
@@ -148,7 +151,8 @@ static int logmmse_stream_mode(int fea_dim, int device, const bp_logmmse_params 
         waves[s] = read_one(WHO, ins[s], &rates[s]);
     }
     bp_lmstream *st = nullptr;
-    check(bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st));
+    if (nz) check(bp_lmstream_open_nt(device, fea_dim, &lm, nz, chan, block * chan, &st));
+    else check(bp_lmstream_open(device, fea_dim, &lm, chan, block * chan, &st));
     // a push returns what arrived plus what waited for the noise start or for the end of the sentence
     const size_t samples = play_files(st, bp_lmstream_push, chan, block, ins, waves, (size_t)chan * ((size_t)block + ((size_t)lm.init_frames + 1) * hop), enh);
     bp_lmstream_close(st);
@@ -171,6 +175,7 @@ int main(int argc, char **argv)
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
     int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1, rate = 0;
     bool lm_chan_given = false;
+    int lm_noise = BP_NOISE_VAD;
     float vis = 0.f, hid = 0.f;
     const char *const count = "is not a count >= 1";
     const Key keys[] = {
@@ -196,7 +201,7 @@ int main(int argc, char **argv)
         given.push_back(k);
         if (k == "lm_stream_chan") lm_chan_given = true;
         // output layer (.wts files do not record it): the keys and checks of bptrain
-        if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss)) continue;
+        if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss) || lm_noise_key(a, WHO, "is not vad or spp", &lm_noise)) continue;
         // the log-MMSE parameters stay by hand: any lm_ name is a number first (nan and inf included), and only then a known key
         if (k.compare(0, 3, "lm_") != 0) fail("bpenhance: unknown key " + k);
         char *end = nullptr;
@@ -226,8 +231,12 @@ int main(int argc, char **argv)
         if (lm_block > 0 && ((long)lm_block * lm_chan > (1L << 28) || lm_chan > (1 << 16))) fail("bpenhance: lm_stream_block * lm_stream_chan is too large");
         std::vector<std::string> li, lo;
         wav_pairs(list, in_wav, out_wav, li, lo);
-        if (lm_block > 0) return logmmse_stream_mode(fea_dim, device, lm, lm_block, lm_chan, li, lo);
-        return logmmse_mode(fea_dim, device, lm, li, lo);
+        bp_noise_params nz;                                      // lm_noise=vad: the calls without noise parameters
+        bp_noise_defaults(&nz);
+        nz.mode = lm_noise;
+        const bp_noise_params *np = lm_noise != BP_NOISE_VAD ? &nz : nullptr;
+        if (lm_block > 0) return logmmse_stream_mode(fea_dim, device, lm, np, lm_block, lm_chan, li, lo);
+        return logmmse_mode(fea_dim, device, lm, np, li, lo);
     }
     if (L < 2 || L > MAXLAYER - 1 || fea_dim < 1 || ctx < 1 || toff < 0 || toff >= ctx || cache < 1 || cache > MAXCACHEFRAME || bunch < 1) {
         printf("bpenhance: need layersizes (2..%d sizes), fea_dim, fea_context, 0 <= targ_offset < fea_context, traincache <= %d\n", MAXLAYER - 1, MAXCACHEFRAME);

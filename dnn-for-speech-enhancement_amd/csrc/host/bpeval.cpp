@@ -7,7 +7,7 @@
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
-//          [scores=basic|extended] [rate=16000]
+//          [scores=basic|extended] [rate=16000] [lm_noise=vad|spp]
 //   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended] [rate=16000]
 //
 // rate=R (either mode): every clean, noise or pair WAV whose rate is not R is converted to R on the device as it is
@@ -21,6 +21,8 @@
 // checked before the device is used.  baseline=logmmse (test-set mode only) scores the classic log-MMSE enhancer on the same
 // mixtures beside the net (bp_eval_mix_logmmse): after every stdout line a second one with `logmmse:` in place of
 // the net's figures (noisy -> logmmse), and three more columns `ssnr_lm lsd_lm stoi_lm` at the end of every scores_out line.
+// lm_noise=spp (only with baseline=logmmse; default vad: the output above, byte for byte) gives the baseline the MMSE-SPP noise tracker
+// (bp_eval_mix_logmmse_nt).
 // scores=extended (default basic: the output above, byte for byte): every stdout line gains `, ESTOI a -> b, SI-SDR a -> b dB` before
 // the undefined count, which then counts the NaN of all five columns; scores_out lines gain `estoi_noisy estoi_enh sisdr_noisy
 // sisdr_enh` behind stoi_enh, the baseline's `estoi_lm sisdr_lm` behind its three, and pairs mode `estoi sisdr` behind stoi.
@@ -63,6 +65,8 @@ struct Params {
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
     bool net_keys = false;                                   // a key of test-set mode was given
     int baseline = 0;                                        // baseline=logmmse
+    int lm_noise = BP_NOISE_VAD;                             // lm_noise=vad|spp
+    bool lm_noise_given = false;
     int ext = 0;                                             // scores=extended: five score columns
     RirKeys rir;                                             // rir_rooms=N ...: simulated responses in place of rir_list
 };
@@ -104,13 +108,15 @@ Params parse(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
         if (key_apply(both, WHO, a)) continue;
-        if (!key_apply(keys, WHO, a)) {
+        if (lm_noise_key(a, WHO, nullptr, &P.lm_noise)) P.lm_noise_given = true;
+        else if (!key_apply(keys, WHO, a)) {
             const int r = rir_key(P.rir, a.k, a.v);
             if (!r) fail("bpeval: unknown key " + a.k);
             if (r < 0) bad_value(WHO, a.k, a.v);
         }
         P.net_keys = true;
     }
+    if (P.lm_noise_given && !P.baseline && P.pairs_list.empty()) fail("bpeval: lm_noise needs baseline=logmmse");
     return P;
 }
 
@@ -267,7 +273,13 @@ int main(int argc, char **argv)
         else check(bp_eval_mix(h, n, pm, rate, P.wave_target, P.out_col, ns.data(), es.data(), nullptr));
         if (P.baseline) {                                    // (its noisy scores are those of bp_eval_mix: ns is written twice)
             ls.resize((size_t)n * NS);
-            if (P.ext) check(bp_eval_mix_logmmse_ext(h, nullptr, n, pm, rate, NS, ns.data(), ls.data(), nullptr));
+            if (P.lm_noise != BP_NOISE_VAD) {
+                bp_noise_params nz;
+                bp_noise_defaults(&nz);
+                nz.mode = P.lm_noise;
+                check(bp_eval_mix_logmmse_nt(h, nullptr, &nz, n, pm, rate, NS, ns.data(), ls.data(), nullptr));
+            }
+            else if (P.ext) check(bp_eval_mix_logmmse_ext(h, nullptr, n, pm, rate, NS, ns.data(), ls.data(), nullptr));
             else check(bp_eval_mix_logmmse(h, nullptr, n, pm, rate, ns.data(), ls.data(), nullptr));
         }
         for (int i = 0; i < n; ++i) {

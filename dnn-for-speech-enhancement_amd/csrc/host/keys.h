@@ -193,6 +193,14 @@ inline bool key_apply(const Key (&keys)[N], const char *tool, const Arg &a)
 const long RATE_MAX = 1L << 30;
 const char *const RATE_TAIL = "is not a sample rate >= 1";
 
+// lm_noise=vad|spp as bpenhance (tail: its own text) and bpeval (tail null: `bad value`) take it: the noise
+// update of the log-MMSE baseline, BP_NOISE_VAD or BP_NOISE_SPP
+inline bool lm_noise_key(const Arg &a, const char *tool, const char *tail, int *mode)
+{
+    const Key keys[] = {{"lm_noise", K_CHOICE, mode, BP_NOISE_VAD, 0, "vad|spp", tail}};
+    return key_apply(keys, tool, a);
+}
+
 // output_act / output_linear_dims / output_loss as bptrain, bpforward and bpenhance take them: strict, with their own texts (a
 // typo must not silently run a different model)
 inline bool output_key(const Arg &a, int *act, int *dims, int *loss)

@@ -579,6 +579,57 @@ int bp_lmstream_counts(int fea_dim, int init_frames, int64_t received, int ended
                        int64_t *samples_out);
 
 /* ------------------------------------------------------------------------------------
+ * Noise tracking in the log-MMSE baseline: an MMSE-SPP estimator (Gerkmann and Hendriks, "Unbiased MMSE-based noise power estimation
+ * with low complexity and low tracking delay", 2012) in place of the VAD-gated update, which freezes once the noise level rises
+ * (no reference counterpart).  INTEGRATION.md 1n, DESIGN.md 26.  Everything of the log-MMSE definition above stays -- the signal
+ * layer, P_t, lambda_floor = 1e-10, the noise start from the first min(init_frames, T) frames, gamma, xi, Lambda, vad_t, G, A_prev,
+ * the synthesis -- but the noise update, which in tracker mode also moves IN FRONT OF the frame's gain.
+ *
+ * bp_noise_params {mode, xi_h1_db, q, a_pow, a_spp, p_lo, p_cap}; bp_noise_defaults writes BP_NOISE_SPP, 15, 0.5, 0.8, 0.9, 0.98,
+ * 0.99 (the paper's constants); a NULL pointer means these defaults.  Valid: mode BP_NOISE_VAD or BP_NOISE_SPP, 0 <= xi_h1_db <= 40,
+ * 0 < q < 1, 0 <= a_pow < 1, 0 <= a_spp < 1, 0 < p_lo < p_cap < 1; anything else is BP_ERR_ARG with a message that names the field,
+ * before the device is touched.
+ *
+ * mode BP_NOISE_SPP, per sentence and per bin, in double; the host computes xi = 10^(xi_h1_db/10), c0 = (1-q)/q (1+xi),
+ * c1 = xi/(1+xi); pbar = 0 at the start of every sentence:
+ *   for t = 0 .. T-1:
+ *     ph   = 1 / (1 + c0 exp(-c1 P_t / lambda))                        (speech presence probability under a fixed a-priori SNR)
+ *     pbar = a_spp pbar + (1 - a_spp) ph
+ *     r    = clamp((pbar - p_lo) / (p_cap - p_lo), 0, 1)
+ *     ph   = min(ph, 1 - (1 - p_cap) r)                                (the anti-stagnation ceiling)
+ *     lambda = max(a_pow lambda + (1 - a_pow) ((1 - ph) P_t + ph lambda), lambda_floor)
+ *     noise_t = lambda
+ *     gamma, xi (with alpha A_prev / lambda), Lambda, vad_t, G, A_prev, S_t as above, from this lambda
+ *     (no VAD-gated update: mu and eta take no part; vad_t is still computed and returned)
+ * One deliberate difference from the paper: it caps ph at 0.99 by a hard switch, pbar > 0.99.  On sustained tones pbar comes within
+ * 3e-7 .. 3e-4 of 0.99, a flipped switch moves that bin's lambda by at least 1.7 % (ph > 0.99 needs P/lambda > 8.3), and so an fp32
+ * analysis could not be held to a float64 restatement.  The ceiling here ramps from 1 at pbar = p_lo to p_cap at pbar >= p_cap:
+ * the same cure, continuous.  Tracker mode contains no decision at all: min, max and clamp only.
+ * mode BP_NOISE_VAD is the definition above unchanged: the _nt calls then return the bits of the calls without _nt.
+ *
+ * bp_logmmse_waves_nt, bp_eval_mix_logmmse_nt, bp_lmstream_open_nt: bp_logmmse_waves, bp_eval_mix_logmmse_ext and bp_lmstream_open
+ * with the noise parameters np, and every rule of theirs.  out_noise is NULL or [sum T][fea_dim]: in tracker mode fl32(noise_t), in
+ * VAD mode fl32 of the lambda that frame t's gamma used (row 0: the noise start).  bp_lmstream_push, _close and _counts serve both
+ * kinds of stream unchanged; the noise start still gates a sentence's first output.  A stream in tracker mode carries pbar beside
+ * lambda and A_prev: 3 fea_dim doubles and hop floats of device state per channel; a sentence's end resets it. */
+enum { BP_NOISE_VAD = 0, BP_NOISE_SPP = 1 };
+typedef struct bp_noise_params {
+    int    mode;         /* BP_NOISE_VAD | BP_NOISE_SPP */
+    double xi_h1_db;     /* the fixed a-priori SNR under speech presence, dB */
+    double q;            /* the a-priori probability of speech absence */
+    double a_pow;        /* smoothing of the noise power */
+    double a_spp;        /* smoothing of the presence probability */
+    double p_lo, p_cap;  /* the ceiling of ph ramps from 1 at pbar = p_lo to p_cap at pbar >= p_cap */
+} bp_noise_params;
+int bp_noise_defaults(bp_noise_params *p);
+int bp_logmmse_waves_nt(int device, int fea_dim, const bp_logmmse_params *p, const bp_noise_params *np, int n_sent,
+                        const int *sent_len, const float *pcm, float *out_pcm, float *out_gain, float *out_vad, float *out_noise);
+int bp_eval_mix_logmmse_nt(bp_handle *h, const bp_logmmse_params *p, const bp_noise_params *np, int n_mix, const bp_mixture *m,
+                           int sample_rate, int n_scores, float *noisy_scores, float *enh_scores, float *enh_pcm);
+int bp_lmstream_open_nt(int device, int fea_dim, const bp_logmmse_params *p, const bp_noise_params *np, int n_chan,
+                        int max_push_samples, bp_lmstream **out);
+
+/* ------------------------------------------------------------------------------------
  * Sample-rate conversion by a rational factor (no reference counterpart: its README sends its users to TIMIT at 16 kHz, NOISEX-92
  * at 19.98 kHz and 100 noise types at 20 kHz for nets that work at 8 kHz, and leaves the conversion to outside tools).
  * INTEGRATION.md 1m, DESIGN.md 24.  Defined to the bit, as the reverberation FIR above is.

@@ -5,7 +5,10 @@
 comes from running it under `rocprofv3 --kernel-trace --stats -- python tools/bench_logmmse.py` (against bp_wave_analysis,
 bp_wave_synthesis and bp_wave_overlap around it).
 
-    python tools/bench_logmmse.py [--reps 10] [--compute fp32|bf16]
+--noise spp times the two log-MMSE calls with the MMSE-SPP noise tracker (bp_logmmse_waves_nt, bp_eval_mix_logmmse_nt,
+INTEGRATION.md 1n) beside the VAD-gated ones, on the same audio and in the same alternation.
+
+    python tools/bench_logmmse.py [--reps 10] [--compute fp32|bf16] [--noise spp]
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--compute", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--sentences", type=int, default=100)
+    ap.add_argument("--noise", default=None, choices=["spp"], help="also time the calls with the noise tracker")
     a = ap.parse_args()
     D, ctx, toff, rate, B = 129, 11, 5, 8000, 256
     ls = [(ctx + 1) * D, 2048, 2048, 2048, D]
@@ -41,6 +45,8 @@ def main():
     plan = dnnse_amd.mix_plan(0, a.sentences, 1, [x.size for x in noise], [-5, 0, 5, 10, 15, 20])
     mix = np.split(g.mix_features(plan)["pcm"], np.cumsum([x.size for x in clean])[:-1])
     t = {"logmmse_waves": [], "enhance_waves": [], "eval_mix_logmmse": [], "eval_mix": []}
+    if a.noise:
+        t.update({"logmmse_waves_" + a.noise: [], "eval_mix_logmmse_" + a.noise: []})
     for r in range(a.reps + 1):                                    # (rep 0: warm-up -- buffers, code objects)
         t0 = time.perf_counter()
         dnnse_amd.logmmse_waves(0, D, mix)
@@ -51,8 +57,14 @@ def main():
         t3 = time.perf_counter()
         ev = g.eval_mix(plan, rate)
         t4 = time.perf_counter()
+        dts = [t1 - t0, t2 - t1, t3 - t2, t4 - t3]
+        if a.noise:
+            dnnse_amd.logmmse_waves(0, D, mix, noise=a.noise)
+            t5 = time.perf_counter()
+            lmn = g.eval_mix_logmmse(plan, rate, noise=a.noise)
+            dts += [t5 - t4, time.perf_counter() - t5]
         if r:
-            for k, dt in zip(t, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            for k, dt in zip(t, dts):
                 t[k].append(dt)
     g.close()
     ms = {k + "_ms_median": 1e3 * float(np.median(v)) for k, v in t.items()}
@@ -61,6 +73,8 @@ def main():
     out.update(ms)
     out.update({"noisy_mean": np.nanmean(ev["noisy"], axis=0).tolist(), "logmmse_mean": np.nanmean(lm["enhanced"], axis=0).tolist(),
                 "net_mean": np.nanmean(ev["enhanced"], axis=0).tolist()})
+    if a.noise:
+        out["logmmse_%s_mean" % a.noise] = np.nanmean(lmn["enhanced"], axis=0).tolist()
     print(json.dumps(out))
 
 

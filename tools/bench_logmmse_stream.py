@@ -10,7 +10,10 @@ second -- and the lines together as a JSON file (--out, default profiles/bench_l
 copies of a push show under `rocprofv3 --kernel-trace --stats -- python tools/bench_logmmse_stream.py --only-stream`.
 A tool, not a yardstick.
 
-    python tools/bench_logmmse_stream.py [--rounds 5] [--pushes 200] [--only-stream] [--out FILE]
+--noise spp adds a stream opened with the MMSE-SPP noise tracker (bp_lmstream_open_nt) to the alternation: the
+same pushes, one more column per cell.
+
+    python tools/bench_logmmse_stream.py [--rounds 5] [--pushes 200] [--only-stream] [--noise spp] [--out FILE]
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--only-stream", action="store_true", help="only the log-MMSE stream's pushes (for a kernel trace)")
+    ap.add_argument("--noise", default=None, choices=["spp"], help="also time a stream with the noise tracker")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_logmmse_stream.json"))
     a = ap.parse_args()
     D, ctx, toff, rate, block, B = 129, 11, 5, 8000, 160, 32
@@ -46,18 +50,21 @@ def main():
         n_push = a.rounds * a.pushes + 16
         feed = np.round(rng.normal(0, 3000, (n_push, nc, block))).astype(np.float32)
         lm = dnnse_amd.logmmse_stream_open(0, D, n_chan=nc, max_push_samples=nc * block)
+        lmn = dnnse_amd.logmmse_stream_open(0, D, n_chan=nc, max_push_samples=nc * block, noise=a.noise) if a.noise else None
         net = None if g is None else g.stream_open(mean, istd, ctx, toff, n_chan=nc, max_push_samples=nc * block)
         for p in range(16):                                          # warm-up: past the noise start and the net's look-ahead
             lm.push(list(feed[p]))
+            if lmn is not None:
+                lmn.push(list(feed[p]))
             if net is not None:
                 net.push(list(feed[p]))
                 dnnse_amd.logmmse_waves(0, D, list(feed[p]))
-        t = {"lmstream_push": [], "logmmse_waves": [], "net_packed_push": []}
+        t = {"lmstream_push": [], "lmstream_push_spp": [], "logmmse_waves": [], "net_packed_push": []}
         p = 16
         for r in range(a.rounds):
-            for what, call in (("lmstream_push", lm.push), ("logmmse_waves", lambda bl: dnnse_amd.logmmse_waves(0, D, bl)),
+            for what, call in (("lmstream_push", lm.push), ("lmstream_push_spp", None if lmn is None else lmn.push), ("logmmse_waves", lambda bl: dnnse_amd.logmmse_waves(0, D, bl)),
                                ("net_packed_push", None if net is None else net.push)):
-                if call is None or (a.only_stream and what != "lmstream_push"):
+                if call is None or (a.only_stream and not what.startswith("lmstream_push")):
                     continue
                 for q in range(a.pushes):
                     blocks = list(feed[p + q])
@@ -66,6 +73,8 @@ def main():
                     t[what].append(time.perf_counter() - t0)
             p += a.pushes
         lm.close()
+        if lmn is not None:
+            lmn.close()
         if net is not None:
             net.close()
         audio = nc * block / rate
