@@ -10,6 +10,7 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      SCORE_ESTOI, SCORE_SISDR,
                      BPStreamConfig, Stream, stream_counts, BPLogmmseParams, logmmse_params, logmmse_waves,
                      LogmmseStream, logmmse_stream_open, logmmse_stream_counts, BPNoiseParams, noise_params, NOISE_VAD, NOISE_SPP,
+                     NAT_STATIC, NAT_DYNAMIC, NAT_MODES,
                      rir_image, rir_rooms, rir_beta, rir_orders, rir_window_default, BPRirRange, RIR_ROOM_DTYPE, RIR_RANGE_DEFAULTS,
                      RIR_MAX_IMAGES,
                      BPResampleParams, resample_waves, resample_ratio, resample_len, resample_taps, resample_params)

@@ -44,11 +44,13 @@ ABI_SYMBOLS = [
     "bp_stream_open", "bp_stream_push", "bp_stream_close", "bp_stream_counts", "bp_stream_packed",
     "bp_logmmse_defaults", "bp_logmmse_waves", "bp_eval_mix_logmmse",
     "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
-    "bp_noise_defaults", "bp_logmmse_waves_nt", "bp_eval_mix_logmmse_nt", "bp_lmstream_open_nt",
+    "bp_noise_defaults", "bp_logmmse_waves_nt", "bp_eval_mix_logmmse_nt", "bp_lmstream_open_nt", "bp_set_nat",
     "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
+NAT_STATIC, NAT_DYNAMIC = 0, 1           # bp_set_nat
+NAT_MODES = {"static": NAT_STATIC, "dynamic": NAT_DYNAMIC}
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
 SCORE_ESTOI, SCORE_SISDR = 3, 4               # the two further columns of the _ext calls (extended=True)
@@ -252,6 +254,7 @@ def load_library(path=None):
     lib.bp_set_hyper.argtypes = [hp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
     lib.bp_set_output.argtypes = [hp, C.c_int, C.c_int, C.c_int]
     lib.bp_set_forward.argtypes = [hp, C.c_int]
+    lib.bp_set_nat.argtypes = [hp, C.c_int, C.POINTER(BPNoiseParams)]
     lib.bp_stream_packed.argtypes = [C.c_void_p]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
@@ -294,7 +297,8 @@ class BP_GPU(object):
     def __init__(self, gpu_used, numlayers, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
                  dropoutflag=0, visible_omit=0.0, hid_omit=0.0, activation=0, momentum_rule=0, seed=0, device=0,
                  global_bunchsize=0, rank_frame_offset=0, max_chunk_frames=0, strict_exit=False, compute_dtype=0,
-                 output_activation=0, output_linear_cols=0, output_loss=0, forward_mode=FORWARD_DEFAULT):
+                 output_activation=0, output_linear_cols=0, output_loss=0, forward_mode=FORWARD_DEFAULT, nat_mode="static",
+                 nat_noise=None):
         self._h = None
         self._strict = strict_exit
         self._lib = load_library()
@@ -333,6 +337,9 @@ class BP_GPU(object):
             self.set_output(*out_mode)
         if int(forward_mode) != FORWARD_DEFAULT:
             self.set_forward(forward_mode)
+        self._nat_mode = "static"
+        if nat_mode != "static" or nat_noise is not None:
+            self.set_nat(nat_mode, nat_noise)
 
     # ------------------------------------------------------------------ errors
     def _fail(self, msg):
@@ -386,6 +393,24 @@ class BP_GPU(object):
         depend on its input row and the net alone, and streams opened from now on pack their channels.  fp32 handles."""
         self._check(self._lib.bp_set_forward(self._h, int(mode)))
         self.forward_mode = int(mode)
+
+    def set_nat(self, mode, noise=None):
+        """The noise-aware block of the calls that stage it (bp_set_nat): "static", one row per sentence (the default), or
+        "dynamic", one row per frame from the MMSE-SPP noise tracker -- enhance_waves, train_mix, CrossValid_mix, mix_features
+        and eval_mix from the next call on, and the streams opened from now on (an open stream keeps its mode).  noise: what noise_params takes (None: the tracker's defaults)."""
+        if mode not in NAT_MODES:
+            self._fail("set_nat: mode must be \"static\" or \"dynamic\", not %r" % (mode,))
+        try:
+            nz = noise_params(noise)
+        except BPError as e:
+            self._fail(str(e))
+        self._check(self._lib.bp_set_nat(self._h, NAT_MODES[mode], C.byref(nz)))
+        self._nat_mode = mode
+
+    @property
+    def nat_mode(self):
+        """"static" or "dynamic": what set_nat (or nat_mode= at construction) set last."""
+        return self._nat_mode
 
     def train(self, n_frames, indata, targ):
         x = self._in(indata, n_frames, self.layersizes[0], "in")
@@ -510,7 +535,8 @@ class BP_GPU(object):
         c.target, c.out_col, c.n_chan, c.max_push_samples = int(target), int(out_col), int(n_chan), int(max_push_samples)
         s = C.c_void_p()
         self._check(self._lib.bp_stream_open(self._h, C.byref(c), C.byref(s)))
-        return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan), bool(self._lib.bp_stream_packed(s)))
+        return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan), bool(self._lib.bp_stream_packed(s)),
+                      self._nat_mode)
 
     # ---- training mixtures made on the device (bp_set_mix_corpus ...; definition: include/bp_c_api.h)
     def set_mix_corpus(self, clean, noise, mean, inv_std, context, targ_offset, target=MIX_LPS, lc_db=5.0):
@@ -587,7 +613,8 @@ class BP_GPU(object):
 
     def mix_features(self, plan):
         """dict of fea [sum T][D] (normalised), lps [sum T][D] (noisy), targ [sum T][sL], nat [n_mix][D] (None without the
-        noise-aware block) and pcm [sum len_c] (the mixed samples), unshuffled."""
+        noise-aware block; in nat_mode "dynamic" [sum T][D], the row of every frame) and pcm [sum len_c] (the mixed samples),
+        unshuffled."""
         p, pp = self._plan(plan)
         D = getattr(self, "mix_fea_dim", None)
         if D is None:                                   # no corpus: the library reports the state error
@@ -597,7 +624,7 @@ class BP_GPU(object):
         has_nat = self.mix_nat
         out = {"fea": np.empty((T, D), np.float32), "lps": np.empty((T, D), np.float32),
                "targ": np.empty((T, self.layersizes[-1]), np.float32),
-               "nat": np.empty((p.size, D), np.float32) if has_nat else None, "pcm": np.empty(max(n_pcm, 1), np.float32)}
+               "nat": np.empty((T if self._nat_mode == "dynamic" else p.size, D), np.float32) if has_nat else None, "pcm": np.empty(max(n_pcm, 1), np.float32)}
         self._check(self._lib.bp_mix_features(self._h, p.size, pp, _fp(out["fea"]), _fp(out["lps"]), _fp(out["targ"]),
                                               _fp(out["nat"]) if has_nat else None, _fp(out["pcm"])))
         out["pcm"] = out["pcm"][:n_pcm]
@@ -816,8 +843,8 @@ def _counts3(fn, *args):
 class Stream(object):
     """A streaming session (bp_stream_*): n_chan live feeds enhanced in blocks of any sizes."""
 
-    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan, packed=False):
-        self._g, self._s, self._packed = owner, s, bool(packed)
+    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan, packed=False, nat_mode="static"):
+        self._g, self._s, self._packed, self._nat_mode = owner, s, bool(packed), nat_mode
         self.fea_dim, self.context, self.targ_offset, self.n_chan = fea_dim, context, targ_offset, n_chan
         self.look_ahead = context - 1 - targ_offset
 
@@ -826,6 +853,12 @@ class Stream(object):
         """True for a stream opened in FORWARD_ROWINV: a push places its frames densely and runs the row-invariant forward, whatever
         the handle's mode is by then."""
         return self._packed
+
+    @property
+    def nat_mode(self):
+        """"static" or "dynamic": the noise-aware block the stream stages -- its handle's mode (set_nat) when it was opened,
+        whatever the handle's mode is by then."""
+        return self._nat_mode
 
     def push(self, blocks, end=None, out_cap=None):
         """blocks: one 1-D array of new samples per channel (None or empty: none); end: per channel, true closes the channel's

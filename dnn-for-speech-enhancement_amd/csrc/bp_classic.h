@@ -12,9 +12,8 @@
 struct LogmmseP { double alpha, mu, eta, xi_min, gamma_max; int init_frames; };
 // The range rules of bp_logmmse_params (BP_ERR_ARG, nothing touched); p == null: the defaults.
 int logmmse_check(const char *who, const bp_logmmse_params *p, LogmmseP &out);
-// Checked noise parameters in the units the kernel uses: c0 = (1-q)/q (1+xi), c1 = xi/(1+xi), xi = 10^(xi_h1_db / 10).
-// spp == false: the VAD-gated update of LogmmseP's mu and eta, and nothing else of this is read.
-struct NoiseP { bool spp; double c0, c1, a_pow, a_spp, p_lo, p_cap; };
+// Checked noise parameters: NoiseP (bp_handle.h: a handle keeps one for bp_set_nat).  spp == false: the VAD-gated update of
+// LogmmseP's mu and eta.
 // The range rules of bp_noise_params (BP_ERR_ARG, nothing touched); np == null: the defaults of bp_noise_defaults.
 int noise_check(const char *who, const bp_noise_params *np, NoiseP &out);
 // The NoiseP of the calls without a noise parameter: the VAD-gated update.
@@ -86,6 +85,18 @@ __device__ __forceinline__ void lm_track(const NoiseP &n, const float2 (&y)[NB],
         ph = fmin(ph, 1.0 - (1.0 - n.p_cap) * r);
         lam[j] = fmax(n.a_pow * lam[j] + (1.0 - n.a_pow) * ((1.0 - ph) * P + ph * lam[j]), LM_FLOOR);
     }
+}
+
+// One frame of the dynamic noise-aware input of one bin: the tracker's step on y, then the normalised LPS of
+// fl32(lambda) in the expression of the noisy row.  bp_wave_dnat (bp_wave.hip) and bp_stream_dnat (bp_stream.hip) run exactly this per frame.
+__device__ __forceinline__ float lm_dnat(const NoiseP &n, float2 y, double &lam, double &pb, float mean, float inv_std)
+{
+#pragma clang fp contract(off)
+    const float2 yy[1] = {y};
+    double l[1] = {lam}, p[1] = {pb};
+    lm_track<1>(n, yy, l, p);
+    lam = l[0]; pb = p[0];
+    return (lps_of((float)lam) - mean) * inv_std;
 }
 
 // One frame of the recursion for a workgroup of WAVE_THREADS threads, thread i owning bins i, i + WAVE_THREADS, ... (on[j]: the

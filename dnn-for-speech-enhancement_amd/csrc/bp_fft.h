@@ -169,6 +169,7 @@ struct WaveAnaArgs {
     float *lps;           // [frames][D] un-normalised LPS, or null
     float *rows;          // staged normalised rows [frames + n_sent (ctx - 1)][D], or null
     int *win_start, *nat_row;   // [frames] window tables of the chunk (with rows)
+    int nat_frame;        // nat_row[g] = the sentence (0: one noise-aware row per sentence) or g itself (1: one per frame, bp_wave_dnat)
 };
 
 // Host side of bp_wave.hip, for the other signal-layer units
@@ -195,6 +196,12 @@ void wave_window_twiddles(int log2M, float *win, float2 *tw);     // win[2M], tw
 static inline int wave_grow(bp_handle *h, std::initializer_list<Grow> list) { return grow_all("signal-layer buffers: ", {h->stream}, list); }
 hipError_t wave_analysis_launch(const WaveAnaArgs &a, int frames, hipStream_t st);
 hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, int ctx, int toff, float *nat, hipStream_t st);
+// the dynamic noise-aware rows: nat [frames][D] from the noisy spectrum Y [frames][D], one row per frame
+hipError_t wave_dnat_launch(const NoiseP &np, const float2 *Y, const int *F, int n_sent, int D, const float *mean, const float *inv_std,
+                            float *nat, hipStream_t st);
+// The noise-aware block of a staging call on h (bp_set_nat): *dyn = one tracked row per frame.  BP_ERR_ARG in the caller's name when
+// the handle is in BP_NAT_DYNAMIC and the net has no block (nat == false).
+int wave_nat_mode(const char *who, const bp_handle *h, bool nat, bool *dyn);
 // synthesis of `frames` frames from the net outputs out[frames][ldo] (columns [out_col, out_col + D)) and Y -> syn[frames][n_fft]
 hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
                                  int D, int target, float *syn, int frames, hipStream_t st);

@@ -50,6 +50,10 @@ static inline int dev_int(const char *name, int dflt) { const char *e = getenv(n
 struct StepProf;
 struct bp_dp;
 
+// Checked noise parameters in the units the kernels use: c0 = (1-q)/q (1+xi), c1 = xi/(1+xi), xi = 10^(xi_h1_db / 10) (noise_check,
+// bp_classic.h).  spp == false: the VAD-gated update of the log-MMSE recursion, and nothing else of this is read.
+struct NoiseP { bool spp; double c0, c1, a_pow, a_spp, p_lo, p_cap; };
+
 struct bp_handle {
     bp_config cfg;
     int L;                       // number of layer sizes
@@ -82,6 +86,7 @@ struct bp_handle {
     uint32_t th_vis, th_hid;
     int fwd_mode;                     // bp_set_forward: the kernels of the inference forward (BP_FORWARD_DEFAULT | BP_FORWARD_ROWINV)
     float *inf_slab; unsigned *inf_ticket[BP_MAXLAYER];   // ROWINV: k-slice slabs (shared by the layers) and each layer's ticket words, or null
+    int nat_mode; NoiseP nat_np;      // bp_set_nat: the noise-aware block of the calls that stage it (BP_NAT_STATIC | BP_NAT_DYNAMIC) and the tracker of the latter
     int out_act, out_lin, out_loss;   // output layer (bp_set_output): 0 linear | 1 logistic on columns [out_lin, s_L), loss of those columns
     Event ev0, ev1; float last_ms; int last_bunches;
     std::vector<Buf> allocs;     // everything dev_alloc handed out: lives as long as the handle

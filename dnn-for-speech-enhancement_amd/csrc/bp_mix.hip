@@ -13,7 +13,8 @@
 //   bp_mix_pcm       one workgroup per segment: x = fmaf(g, v, s), s and g v into the padded buffers (padding written as zeros)
 //   bp_wave_analysis (bp_wave.hip) on x: the staged normalised rows, win_start / nat_row, the noisy LPS (bp_mix_features)
 //   bp_mix_targets   one workgroup per frame: the FFTs of s and g v in LDS, one after the other, and the frame's target row
-//   bp_wave_nat      (bp_wave.hip) the noise-aware rows
+//   bp_wave_nat      (bp_wave.hip) the noise-aware rows; in BP_NAT_DYNAMIC (bp_set_nat) bp_wave_dnat: one row per frame from the noisy
+//                    spectrum, which the calls that keep none hold behind those rows for the tracker alone
 //   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
 //   bp_mix_reverb_fir  (bp_set_mix_reverb, once per call, not per mixture) clean sentences convolved with room impulse responses:
 //                    the derived entries n_clean + k of the corpus; bp_mix_gain and bp_mix_pcm read an
@@ -150,14 +151,14 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_targets(const MixTargArgs
 
 // row i of the chunk trains mixture-frame g = order[i] (identity without order): its window starts at staged row g + m (ctx - 1)
 __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_tables(const int *__restrict__ order, const int *__restrict__ F, int n_mix, int n,
-                                                           int ctx, int *__restrict__ ws, int *__restrict__ tf, int *__restrict__ nr)
+                                                           int ctx, int *__restrict__ ws, int *__restrict__ tf, int *__restrict__ nr, int nat_frame)
 {
     const int i = blockIdx.x * WAVE_THREADS + threadIdx.x;
     if (i >= n) return;
     const int g = order ? order[i] : i, m = sentence_of(F, n_mix, g);
     ws[i] = g + m * (ctx - 1);
     tf[i] = g;
-    if (nr) nr[i] = m;
+    if (nr) nr[i] = nat_frame ? g : m;                           // the noise-aware row of the mixture, or (BP_NAT_DYNAMIC) of the frame itself
 }
 
 // ------------------------------------------------------------------ reverberant entries
@@ -451,9 +452,15 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
     if (r != BP_OK) return r;
     float *rows_d, *targ_d, *nat_d; int *tab;
     targ_d = nullptr;
-    if ((r = window_reserve(h, c.rows * D * 4, targets ? c.frames * ms->sL * 4 : 0, ms->nat ? (size_t)c.n * D * 4 : 0, c.frames, &rows_d,
+    // BP_NAT_DYNAMIC (bp_set_nat; the callers have checked that the net has the block): one noise-aware row per frame from the
+    // noisy spectrum, which a call that keeps none (Y == null) holds behind the rows, in the same buffer, for the tracker alone
+    const bool dyn = ms->nat && h->nat_mode == BP_NAT_DYNAMIC;
+    const size_t dnat_b = al256(c.frames * D * 4);
+    const size_t nat_b = !ms->nat ? 0 : !dyn ? (size_t)c.n * D * 4 : Y ? c.frames * D * 4 : dnat_b + c.frames * D * sizeof(float2);
+    if ((r = window_reserve(h, c.rows * D * 4, targets ? c.frames * ms->sL * 4 : 0, nat_b, c.frames, &rows_d,
                             targets ? &targ_d : nullptr, &nat_d, &tab)) != BP_OK)
         return r;
+    if (dyn && !Y) Y = (float2 *)((char *)nat_d + dnat_b);
     // the pinned input block: the copy out of this one was enqueued two calls ago; wait for it (not for the training behind it)
     const int k = ms->pin_cur;
     ms->pin_cur ^= 1;
@@ -500,7 +507,7 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
         w.mean = (const float *)(cp + ms->o_mean); w.inv_std = (const float *)(cp + ms->o_istd);
         w.n_sent = c.n; w.log2M = ms->log2M; w.D = D; w.hop = ms->hop; w.ctx = ms->ctx; w.toff = ms->toff;
         w.lps = lps_out ? (float *)ms->lps.p : nullptr; w.rows = rows_d; w.Y = Y;
-        w.win_start = tab; w.nat_row = ms->nat ? tab + 2 * (size_t)n : nullptr;
+        w.win_start = tab; w.nat_row = ms->nat ? tab + 2 * (size_t)n : nullptr; w.nat_frame = dyn;
         HIPCHK(wave_analysis_launch(w, n, h->stream));
     }
     if (targets) {
@@ -511,10 +518,12 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
         hipLaunchKernelGGL(bp_mix_targets, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(ms->M) + (size_t)(ms->M + 1) * 4, h->stream, t);
         HIPCHK(hipGetLastError());
     }
-    if (ms->nat) HIPCHK(wave_nat_launch(rows_d, F, c.n, D, ms->ctx, ms->toff, nat_d, h->stream));
+    if (dyn)
+        HIPCHK(wave_dnat_launch(h->nat_np, Y, F, c.n, D, (const float *)(cp + ms->o_mean), (const float *)(cp + ms->o_istd), nat_d, h->stream));
+    else if (ms->nat) HIPCHK(wave_nat_launch(rows_d, F, c.n, D, ms->ctx, ms->toff, nat_d, h->stream));
     hipLaunchKernelGGL(bp_mix_tables, dim3((unsigned)((n + WAVE_THREADS - 1) / WAVE_THREADS)), dim3(WAVE_THREADS), 0, h->stream,
                        order ? (const int *)(db + c.o_order) : (const int *)nullptr, F, c.n, n, ms->ctx, tab, tab + n,
-                       ms->nat ? tab + 2 * (size_t)n : (int *)nullptr);
+                       ms->nat ? tab + 2 * (size_t)n : (int *)nullptr, (int)dyn);
     HIPCHK(hipGetLastError());
     if (rows_out) *rows_out = rows_d;
     if (targ_out) *targ_out = targ_d;
@@ -627,6 +636,8 @@ extern "C" int bp_train_mix(bp_handle *h, int n_mix, const bp_mixture *m, const 
     int r;
     if ((r = plan_call(h, "bp_train_mix", n_mix, m, c)) != BP_OK || (r = check_order("bp_train_mix", c, order)) != BP_OK) return r;
     if (h->Bg != h->B) return fail(BP_ERR_STATE, "bp_train_mix: data-parallel handle (global_bunchsize != bunchsize)");
+    bool dyn;
+    if ((r = wave_nat_mode("bp_train_mix", h, h->mix->nat, &dyn)) != BP_OK) return r;
     if ((r = generate(h, c, m, order, false, nullptr, nullptr, nullptr)) != BP_OK) return r;
     if ((r = window_adopt(h, (int)c.frames, h->mix->D, h->mix->ctx, h->mix->nat, true)) != BP_OK) return r;
     if (c.frames % h->B)
@@ -640,6 +651,8 @@ extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq
     int r;
     if ((r = plan_call(h, "bp_cv_mix", n_mix, m, c)) != BP_OK) return r;
     if (!sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_mix: null argument");
+    bool dyn;
+    if ((r = wave_nat_mode("bp_cv_mix", h, h->mix->nat, &dyn)) != BP_OK) return r;
     const int n = (int)c.frames, L = h->L, sL = h->s[L - 1], ldL = h->ld[L - 1];
     if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;
     float *targ_d;
@@ -671,6 +684,8 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
     if ((r = plan_call(h, "bp_mix_features", n_mix, m, c)) != BP_OK) return r;
     MixState *ms = h->mix;
     if (nat && !ms->nat) return fail(BP_ERR_ARG, "bp_mix_features: nat requested for a net without the noise-aware block");
+    bool dyn;
+    if ((r = wave_nat_mode("bp_mix_features", h, ms->nat, &dyn)) != BP_OK) return r;
     const int D = ms->D, n = (int)c.frames;
     float *rows_d, *targ_d, *nat_d;
     if ((r = generate(h, c, m, nullptr, lps != nullptr, &rows_d, &targ_d, &nat_d)) != BP_OK) return r;
@@ -679,7 +694,7 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
     if (fea) HIPCHK(hipMemcpyAsync(rows.data(), rows_d, rows.size() * 4, hipMemcpyDeviceToHost, h->stream));
     if (lps) HIPCHK(hipMemcpyAsync(lps, ms->lps.p, c.frames * D * 4, hipMemcpyDeviceToHost, h->stream));
     if (targ) HIPCHK(hipMemcpyAsync(targ, targ_d, c.frames * ms->sL * 4, hipMemcpyDeviceToHost, h->stream));
-    if (nat) HIPCHK(hipMemcpyAsync(nat, nat_d, (size_t)c.n * D * 4, hipMemcpyDeviceToHost, h->stream));
+    if (nat) HIPCHK(hipMemcpyAsync(nat, nat_d, (dyn ? c.frames : (size_t)c.n) * D * 4, hipMemcpyDeviceToHost, h->stream));
     if (pcm) HIPCHK(hipMemcpyAsync(x.data(), ms->x.p, x.size() * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     size_t dst = 0;
@@ -779,6 +794,8 @@ static int eval_mix_net(const char *who, bp_handle *h, int n_mix, const bp_mixtu
     const int D = h->mix->D, sL = h->s[h->L - 1];
     if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, std::string(who) + ": target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, std::string(who) + ": out_col + fea_dim exceeds layersizes[last]");
+    bool dyn;
+    if ((r = wave_nat_mode(who, h, h->mix->nat, &dyn)) != BP_OK) return r;
     return eval_mix_run(who, h, nullptr, noise_vad(), c, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
 }
 

@@ -21,6 +21,8 @@
 //                        goes where it is needed: the staged rows of the push's window chunk (replicated at the sentence's edges),
 //                        the Y of the push, the other parity of the state; plus the frame's win_start / nat_row entries
 //   bp_stream_nat        the noise-aware row, once per sentence, in bp_wave_nat's summation order; later pushes copy it into the chunk
+//   bp_stream_dnat       a stream opened in BP_NAT_DYNAMIC (bp_set_nat) instead: one noise-aware row per enhanced frame, from the push's Y
+//                        (and for a sentence's noise start the Y that still waits in the state); lambda and pbar [n_chan][D] carried
 //   bp_stream_synthesis  per enhanced frame: its synthesis, the synthesis of the frame before it when that is of the same push
 //                        (else the carried half), overlap-add into the compact output, the new carried half
 //
@@ -40,6 +42,7 @@
 #include <string>
 #include <vector>
 
+#include "bp_classic.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
 #include "bp_stream_core.h"
@@ -54,6 +57,13 @@ struct AnaJob { int src, stage_lo, stage_hi, state_dst, g, ws, chan, y_state, ha
 // mode 0: from the staged rows (src = row of frame 0), 1: from the state rows (src = slot of frame 0), 2: copy the state's row.
 // nf = min(T, 6) frames exist; stage: also into the chunk's NAT rows.
 struct NatJob { int chan, mode, src, nf, stage, pad[3]; };
+// A stream in BP_NAT_DYNAMIC (bp_set_nat) has these in place of NatJobs, one per channel that gets frames enhanced in a push: frames
+// t0 .. t0 + ne - 1 of the channel's sentence, frame t0 + i being row y + i of the push's Y and noise-aware row g + i of the chunk.
+// t0 == 0: the job starts the sentence -- the noise start is over its first ni = min(6, T) frames, frame t of them in row y + t of
+// the push's Y while t < ne and, still waiting for its look-ahead, in slot st + t - ne of the state's NEW parity beyond.
+// ended: the sentence is over and nothing is carried.
+struct DnatJob { int chan, t0, ne, y, g, ni, st, ended; };
+static_assert(sizeof(DnatJob) == sizeof(NatJob), "the two job tables share their place in the input block");
 // The frame is sample g of the chunk (its net output) and row y of the push's Y.  prev: -1 none (frame 0 of a sentence: front
 // padding, no output), 0 the frame before it is of this push too (sample g - 1, row y - 1), 1 the carried half in slot half_src.
 // out_n samples to out_off of the compact output; half_dst (or -1): where the second half goes.
@@ -65,6 +75,7 @@ struct StreamAnaArgs {
     float *st_rows; float2 *st_Y;       // [2][n_chan][R][D]
     float *rows; float2 *Y;             // the push: staged rows of the window chunk, Y[y][D]
     int *win_start, *nat_row;
+    int nat_frame;                      // nat_row[g] = the channel (0) or g itself (1: bp_stream_dnat writes one row per sample)
 };
 
 }  // namespace
@@ -93,7 +104,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_stream_analysis(const StreamA
         if (j.g >= 0) a.Y[(size_t)j.y * a.D + k] = X;
         if (j.y_state >= 0) a.st_Y[(size_t)j.y_state * a.D + k] = X;
     }
-    if (j.g >= 0 && tid == 0) { a.win_start[j.g] = j.ws; if (a.nat_row) a.nat_row[j.g] = j.chan; }
+    if (j.g >= 0 && tid == 0) { a.win_start[j.g] = j.ws; if (a.nat_row) a.nat_row[j.g] = a.nat_frame ? j.g : j.chan; }
 }
 
 // nat[k] = ((((v0 + v1) + v2) + v3) + v4 + v5) / 6 over the sentence's first 6 normalised frames, frame f clamped to nf - 1
@@ -114,6 +125,43 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_stream_nat(const NatJob *__re
         st_nat[(size_t)j.chan * D + k] = out;
     }
     if (j.stage) nat[(size_t)j.chan * D + k] = out;
+}
+
+namespace {
+constexpr int DNAT_THREADS = 64;
+struct StreamDnatArgs {
+    const DnatJob *jobs; const float2 *Y, *st_Y; const float *mean, *inv_std;
+    double *lam, *pb;                   // [n_chan][D]: the tracker's state between pushes
+    float *nat;                         // the chunk's noise-aware rows, one per sample
+    int D; NoiseP np;
+};
+}  // namespace
+
+// The dynamic noise-aware rows of a push: one thread per (job, bin), serial over the job's frames, the step
+// lm_dnat of bp_wave_dnat (bp_classic.h) and its noise start (lm_power in ascending t from 0.0, lm_noise_start): the rows of
+// bp_enhance_waves in the same mode whatever the block sizes.  lambda and pbar wait in the channel's state between pushes; a
+// thread reads and writes its own two doubles only.  No LDS, no barrier.
+__global__ __launch_bounds__(DNAT_THREADS) void bp_stream_dnat(const StreamDnatArgs a)
+{
+#pragma clang fp contract(off)
+    const int D = a.D, kb = (D + DNAT_THREADS - 1) / DNAT_THREADS, k = (blockIdx.x % kb) * DNAT_THREADS + threadIdx.x;
+    const DnatJob j = a.jobs[blockIdx.x / kb];
+    if (k >= D) return;
+    const float2 *Y = a.Y + (size_t)j.y * D + k;
+    double lam = 0.0, pb = 0.0;
+    if (j.t0 == 0) {
+        for (int t = 0; t < j.ni; ++t) lam += lm_power(t < j.ne ? Y[(size_t)t * D] : a.st_Y[(size_t)(j.st + t - j.ne) * D + k]);
+        lam = lm_noise_start(lam, j.ni);
+    } else { lam = a.lam[(size_t)j.chan * D + k]; pb = a.pb[(size_t)j.chan * D + k]; }
+    const float mean = a.mean[k], istd = a.inv_std[k];
+    float *nat = a.nat + (size_t)j.g * D + k;
+    float2 cur = Y[0];
+    for (int i = 0; i < j.ne; ++i) {
+        const float2 nxt = Y[(size_t)(i + 1 < j.ne ? i + 1 : i) * D];   // (in flight under the chain of frame i)
+        nat[(size_t)i * D] = lm_dnat(a.np, cur, lam, pb, mean, istd);
+        cur = nxt;
+    }
+    if (!j.ended) { a.lam[(size_t)j.chan * D + k] = lam; a.pb[(size_t)j.chan * D + k] = pb; }
 }
 
 namespace {
@@ -167,13 +215,14 @@ struct bp_stream {
     int D, ctx, toff, la, target, out_col, n_chan, max_push, hop, log2M, R;
     int warm;                    // frames before the first is enhanced: 6 with a noise-aware row (nat), else 0
     bool nat;
+    bool dyn; NoiseP nat_np;     // opened in BP_NAT_DYNAMIC (bp_set_nat): one tracked noise-aware row per frame, with these parameters
     bool packed;                 // opened in BP_FORWARD_ROWINV: dense placement, the row-invariant forward on every push
     std::vector<Chan> ch;
     std::vector<ChanPlan> plan;
-    std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<SynJob> syn;
+    std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<DnatJob> dnatj; std::vector<SynJob> syn;
     size_t max_enh;              // samples (frames to enhance) of one push at most
     StreamBlocks blk;            // device: consts | state | input block | Y of the push | output samples
-    size_t o_mean, o_istd, o_win, o_tw, o_rows, o_Y, o_nat, o_half, o_in, o_pY, o_out, in_cap;
+    size_t o_mean, o_istd, o_win, o_tw, o_rows, o_Y, o_nat, o_half, o_lam, o_pb, o_in, o_pY, o_out, in_cap;
 };
 
 void stream_free_all(bp_handle *h)
@@ -209,6 +258,8 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     const bool nat = (long)h->s[0] == (long)(ctx + 1) * D;
     if (!nat && (long)h->s[0] != (long)ctx * D)
         return fail(BP_ERR_ARG, "bp_stream_open: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
+    bool dyn;
+    { const int r = wave_nat_mode("bp_stream_open", h, nat, &dyn); if (r != BP_OK) return r; }
     if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_stream_open: target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_stream_open: out_col + fea_dim exceeds layersizes[last]");
     if (c->n_chan < 1 || c->n_chan > (1 << 16)) return fail(BP_ERR_ARG, "bp_stream_open: n_chan must be in 1 .. 65536");
@@ -220,6 +271,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     s->h = h; s->D = D; s->ctx = ctx; s->toff = c->targ_offset; s->la = ctx - 1 - c->targ_offset; s->target = c->target;
     s->out_col = c->out_col; s->n_chan = c->n_chan; s->max_push = c->max_push_samples; s->hop = D - 1; s->log2M = wave_log2_fft(D);
     s->R = ctx + 6; s->nat = nat; s->warm = nat ? 6 : 0; s->packed = h->fwd_mode == BP_FORWARD_ROWINV;
+    s->dyn = dyn; s->nat_np = h->nat_np;                         // the stream's from now on, as the forward's mode is
     const int hop = s->hop, N = 2 * hop, nc = s->n_chan;
     // A push analyses at most n_in/hop + 3 frames per channel (the end of a sentence adds up to 3) and enhances those plus the
     // frames that waited; it can never enhance more than the chunk capacity lets it stage.
@@ -240,6 +292,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     s->o_Y = lay.take(slots * D * 8);
     s->o_nat = lay.take((size_t)nc * D * 4);
     s->o_half = lay.take(2 * (size_t)nc * hop * 4);
+    s->o_lam = lay.take(dyn ? (size_t)nc * D * 8 : 0); s->o_pb = lay.take(dyn ? (size_t)nc * D * 8 : 0);
     const size_t consts = s->o_rows;
     s->o_in = lay.take(s->in_cap);
     s->o_pY = lay.take(s->max_enh * D * 8);
@@ -258,7 +311,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     if (e != hipSuccess) { delete s; return fail(BP_ERR_DEVICE, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
     s->ch.assign(nc, Chan{0, 0, Carry((size_t)2 * hop, hop)});
     s->plan.resize(nc);
-    s->ana.reserve(max_ana); s->natj.reserve(nc); s->syn.reserve(s->max_enh);
+    s->ana.reserve(max_ana); s->natj.reserve(nc); s->dnatj.reserve(nc); s->syn.reserve(s->max_enh);
     h->streams.push_back(s);
     *out = s;
     return BP_OK;
@@ -307,12 +360,14 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     float *rows_d = nullptr, *nat_d = nullptr; int *tab_d = nullptr;
     if (n > 0) {
         int r;
-        if ((r = window_reserve(h, (size_t)rows * D * 4, 0, s->nat ? (size_t)nc * D * 4 : 0, (size_t)n, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
+        // the noise-aware rows: one per channel, or (dyn) one per sample of the chunk
+        const size_t nat_b = !s->nat ? 0 : s->dyn ? (size_t)n * D * 4 : (size_t)nc * D * 4;
+        if ((r = window_reserve(h, (size_t)rows * D * 4, 0, nat_b, (size_t)n, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
         if ((r = out_chunk_reserve(h, (int)n)) != BP_OK) return r;
     }
     // ---- the input block: analysis jobs | NAT jobs | synthesis jobs | samples, each 256-byte aligned (the pinned block is reused
     // by every push: the previous one ended in a synchronisation); with it the channels' new state
-    s->ana.clear(); s->natj.clear(); s->syn.clear();
+    s->ana.clear(); s->natj.clear(); s->dnatj.clear(); s->syn.clear();
     Layout ib;
     const size_t o_ana = ib.take((size_t)ana_max * sizeof(AnaJob)), o_nat = ib.take((size_t)active * sizeof(NatJob));
     const size_t o_syn = ib.take((size_t)n_enh * sizeof(SynJob)), o_pcm = ib.size();
@@ -349,7 +404,14 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
                 }
                 s->ana.push_back(j);
             }
-            if (s->nat) {
+            if (s->dyn) {
+                if (ne > 0) {
+                    DnatJob j; memset(&j, 0, sizeof(j));
+                    j.chan = c; j.t0 = (int)fo0; j.ne = (int)ne; j.y = (int)y0; j.g = (int)p.g0; j.ni = (int)std::min<int64_t>(fi1, 6);
+                    j.st = slot1 + (int)(fo1 - base1); j.ended = p.ended;
+                    s->dnatj.push_back(j);
+                }
+            } else if (s->nat) {
                 const bool known0 = fi0 >= 6, known1 = p.ended || fi1 >= 6;
                 NatJob j; memset(&j, 0, sizeof(j));
                 j.chan = c; j.stage = ne > 0;
@@ -384,6 +446,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
     const size_t in_bytes = o_pcm + unit * hop * 4;
     memcpy(pin + o_ana, s->ana.data(), s->ana.size() * sizeof(AnaJob));
     if (!s->natj.empty()) memcpy(pin + o_nat, s->natj.data(), s->natj.size() * sizeof(NatJob));
+    if (!s->dnatj.empty()) memcpy(pin + o_nat, s->dnatj.data(), s->dnatj.size() * sizeof(DnatJob));
     if (!s->syn.empty()) memcpy(pin + o_syn, s->syn.data(), s->syn.size() * sizeof(SynJob));
     char *din = dev + s->o_in;
     HIPCHK(hipMemcpyAsync(din, pin, in_bytes, hipMemcpyHostToDevice, h->stream));
@@ -396,7 +459,7 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         a.mean = (const float *)(dev + s->o_mean); a.inv_std = (const float *)(dev + s->o_istd);
         a.log2M = s->log2M; a.D = D; a.hop = hop;
         a.st_rows = (float *)(dev + s->o_rows); a.st_Y = (float2 *)(dev + s->o_Y);
-        a.rows = rows_d; a.Y = Y; a.win_start = tab_d; a.nat_row = (s->nat && n > 0) ? tab_d + 2 * n : nullptr;
+        a.rows = rows_d; a.Y = Y; a.win_start = tab_d; a.nat_row = (s->nat && n > 0) ? tab_d + 2 * n : nullptr; a.nat_frame = s->dyn;
         // fillers between the channels: window 0, NAT row 0 (the first channel with frames staged at least `context` rows)
         if (n > n_enh) HIPCHK(hipMemsetAsync(tab_d, 0, (size_t)3 * n * sizeof(int), h->stream));
         hipLaunchKernelGGL(bp_stream_analysis, dim3((unsigned)s->ana.size()), dim3(WAVE_THREADS), lds_bytes(hop), h->stream, a);
@@ -406,6 +469,15 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         const int kb = (D + WAVE_THREADS - 1) / WAVE_THREADS;
         hipLaunchKernelGGL(bp_stream_nat, dim3((unsigned)(kb * s->natj.size())), dim3(WAVE_THREADS), 0, h->stream, (const NatJob *)(din + o_nat),
                            (const float *)rows_d, (const float *)(dev + s->o_rows), D, (float *)(dev + s->o_nat), nat_d);
+        HIPCHK(hipGetLastError());
+    }
+    if (!s->dnatj.empty()) {
+        StreamDnatArgs a; memset(&a, 0, sizeof(a));
+        a.jobs = (const DnatJob *)(din + o_nat); a.Y = Y; a.st_Y = (const float2 *)(dev + s->o_Y);
+        a.mean = (const float *)(dev + s->o_mean); a.inv_std = (const float *)(dev + s->o_istd);
+        a.lam = (double *)(dev + s->o_lam); a.pb = (double *)(dev + s->o_pb); a.nat = nat_d; a.D = D; a.np = s->nat_np;
+        const int kb = (D + DNAT_THREADS - 1) / DNAT_THREADS;
+        hipLaunchKernelGGL(bp_stream_dnat, dim3((unsigned)(kb * s->dnatj.size())), dim3(DNAT_THREADS), 0, h->stream, a);
         HIPCHK(hipGetLastError());
     }
     if (n > 0) {

@@ -16,6 +16,7 @@
 //                      the noisy spectrum Y, ln(max(|Y|^2, 1e-10)), the normalised row written where bp_stage_bunch reads it
 //                      (the replicated edge rows included), the window chunk's win_start / nat_row entries
 //   bp_wave_nat        the noise-aware row of every sentence (mean of its first 6 normalised frames, PfileReader::try_nat_rows order)
+//   bp_wave_dnat       BP_NAT_DYNAMIC (bp_set_nat) instead: one noise-aware row per frame, the MMSE-SPP tracker's noise PSD
 //   bp_wave_synthesis  per frame: S from the net output and Y, inverse real FFT, times the window -> frames [T][n_fft]
 //   bp_wave_overlap    per output sample: the sum over the two covering frames / the sum of squared window values (a gather: no
 //                      atomics, the same bits on every run)
@@ -27,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "bp_classic.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
 #include "bp_resample.h"
@@ -54,7 +56,44 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_analysis(const WaveAnaAr
             if (t == T - 1) for (int u = T + a.toff; u < T + a.ctx - 1; ++u) a.rows[(size_t)(base + u) * a.D + k] = v;
         }
     }
-    if (a.rows && tid == 0) { a.win_start[g] = base + t; if (a.nat_row) a.nat_row[g] = s; }
+    if (a.rows && tid == 0) { a.win_start[g] = base + t; if (a.nat_row) a.nat_row[g] = a.nat_frame ? g : s; }
+}
+
+namespace {
+constexpr int DNAT_THREADS = 64, DNAT_AHEAD = 4;
+struct DnatArgs { const float2 *Y; const int *F; const float *mean, *inv_std; float *nat; int D; NoiseP np; };
+}  // namespace
+
+// The dynamic noise-aware rows: nat[F_s + t][k] = the normalised LPS of the noise PSD that the MMSE-SPP tracker
+// holds at frame t of sentence s.  One thread per (sentence, bin), serial over t: the bins are independent (no sum across them,
+// no LDS, no barrier), the frames a dependent chain of one double exp, two divisions and one logf.  64-thread workgroups, so that
+// n_sent * ceil(D / 64) of them spread over the CUs; the Y of the next DNAT_AHEAD frames is loaded -- from a clamped row, without
+// a predicate -- before the chain of the current ones, which does not depend on it.  The noise start is bp_logmmse_gain's with
+// init_frames = 6 (ascending t from 0.0), the step lm_dnat (bp_classic.h).
+__global__ __launch_bounds__(DNAT_THREADS) void bp_wave_dnat(const DnatArgs a)
+{
+#pragma clang fp contract(off)
+    const int D = a.D, kb = (D + DNAT_THREADS - 1) / DNAT_THREADS, s = blockIdx.x / kb, k = (blockIdx.x % kb) * DNAT_THREADS + threadIdx.x;
+    if (k >= D) return;
+    const int f0 = a.F[s], T = a.F[s + 1] - f0, ni = T < 6 ? T : 6;
+    const float2 *Y = a.Y + (size_t)f0 * D + k;
+    float *nat = a.nat + (size_t)f0 * D + k;
+    const float mean = a.mean[k], istd = a.inv_std[k];
+    float2 cur[DNAT_AHEAD], nxt[DNAT_AHEAD];
+#pragma unroll
+    for (int j = 0; j < DNAT_AHEAD; ++j) cur[j] = Y[(size_t)(j < T ? j : T - 1) * D];
+    double lam = 0.0, pb = 0.0;
+    for (int t = 0; t < ni; ++t) lam += lm_power(Y[(size_t)t * D]);
+    lam = lm_noise_start(lam, ni);
+    for (int t0 = 0; t0 < T; t0 += DNAT_AHEAD) {
+#pragma unroll
+        for (int j = 0; j < DNAT_AHEAD; ++j) { const int t = t0 + DNAT_AHEAD + j; nxt[j] = Y[(size_t)(t < T ? t : T - 1) * D]; }
+#pragma unroll
+        for (int j = 0; j < DNAT_AHEAD; ++j)
+            if (t0 + j < T) nat[(size_t)(t0 + j) * D] = lm_dnat(a.np, cur[j], lam, pb, mean, istd);
+#pragma unroll
+        for (int j = 0; j < DNAT_AHEAD; ++j) cur[j] = nxt[j];
+    }
 }
 
 // nat[s][k] = ((((v0 + v1) + v2) + v3) + v4 + v5) / 6 over the sentence's first 6 normalised frames, frame f clamped to T-1
@@ -179,6 +218,37 @@ hipError_t wave_nat_launch(const float *rows, const int *F, int n_sent, int D, i
     return hipGetLastError();
 }
 
+hipError_t wave_dnat_launch(const NoiseP &np, const float2 *Y, const int *F, int n_sent, int D, const float *mean, const float *inv_std,
+                            float *nat, hipStream_t st)
+{
+    DnatArgs a; memset(&a, 0, sizeof(a));
+    a.Y = Y; a.F = F; a.mean = mean; a.inv_std = inv_std; a.nat = nat; a.D = D; a.np = np;
+    hipLaunchKernelGGL(bp_wave_dnat, dim3((unsigned)(((D + DNAT_THREADS - 1) / DNAT_THREADS) * n_sent)), dim3(DNAT_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+int wave_nat_mode(const char *who, const bp_handle *h, bool nat, bool *dyn)
+{
+    *dyn = h->nat_mode == BP_NAT_DYNAMIC;
+    if (*dyn && !nat)
+        return fail(BP_ERR_ARG, std::string(who) + ": the handle is in BP_NAT_DYNAMIC (bp_set_nat) and this net has no noise-aware block: "
+                                                   "layersizes[0] is context*fea_dim, not (context+1)*fea_dim");
+    return BP_OK;
+}
+
+// The noise-aware block of the calls that stage it (include/bp_c_api.h).  Every check before anything is touched.
+extern "C" int bp_set_nat(bp_handle *h, int mode, const bp_noise_params *np)
+{
+    if (!h) return fail(BP_ERR_ARG, "bp_set_nat: null handle");
+    if (mode != BP_NAT_STATIC && mode != BP_NAT_DYNAMIC) return fail(BP_ERR_ARG, "bp_set_nat: mode must be BP_NAT_STATIC or BP_NAT_DYNAMIC");
+    NoiseP n;
+    { const int r = noise_check("bp_set_nat", np, n); if (r != BP_OK) return r; }
+    if (mode == BP_NAT_DYNAMIC && !n.spp)
+        return fail(BP_ERR_ARG, "bp_set_nat: np->mode must be BP_NOISE_SPP with BP_NAT_DYNAMIC (the VAD-gated update needs the gains of the log-MMSE recursion)");
+    h->nat_mode = mode; h->nat_np = n;
+    return BP_OK;
+}
+
 hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
                                  int D, int target, float *syn, int frames, hipStream_t st)
 {
@@ -287,6 +357,8 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     const bool nat = (long)h->s[0] == (long)(ctx + 1) * D;
     if (!nat && (long)h->s[0] != (long)ctx * D)
         return fail(BP_ERR_ARG, "bp_enhance_waves: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
+    bool dyn;
+    { const int r = wave_nat_mode("bp_enhance_waves", h, nat, &dyn); if (r != BP_OK) return r; }
     if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_enhance_waves: target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_enhance_waves: out_col + fea_dim exceeds layersizes[last]");
     const size_t rows = p.frames + (size_t)c->n_sent * (ctx - 1);
@@ -301,7 +373,8 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
                           {h->wave_pin[0], w.bytes, true}, {h->wave_pin[1], pcm_b, true}});
     if (r != BP_OK) return r;
     float *rows_d, *nat_d; int *tab_d;
-    if ((r = window_reserve(h, rows * D * 4, 0, nat ? (size_t)c->n_sent * D * 4 : 0, p.frames, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
+    const size_t nat_b = !nat ? 0 : dyn ? p.frames * D * 4 : (size_t)c->n_sent * D * 4;     // one row per frame | per sentence
+    if ((r = window_reserve(h, rows * D * 4, 0, nat_b, p.frames, &rows_d, nullptr, &nat_d, &tab_d)) != BP_OK) return r;
     int *ws_d = tab_d, *nr_d = tab_d + 2 * p.frames;
     if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;      // (forward_resident would; growing it here keeps its sync out of the sequence)
     // The pinned blocks are reused by the next call: the previous call ended in a synchronisation, so nothing still reads them.
@@ -317,11 +390,13 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
         a.pcm = (const float *)(din + w.pcm); a.win = win; a.tw = tw; a.F = F;
         a.mean = (const float *)(din + w.mean); a.inv_std = (const float *)(din + w.istd);
         a.n_sent = c->n_sent; a.log2M = p.log2M; a.D = D; a.hop = p.hop; a.ctx = ctx; a.toff = toff;
-        a.Y = Y; a.rows = rows_d; a.win_start = ws_d; a.nat_row = nat ? nr_d : nullptr;
+        a.Y = Y; a.rows = rows_d; a.win_start = ws_d; a.nat_row = nat ? nr_d : nullptr; a.nat_frame = dyn;
         hipLaunchKernelGGL(bp_wave_analysis, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(p.M), h->stream, a);
         HIPCHK(hipGetLastError());
     }
-    if (nat) {
+    if (dyn) {
+        HIPCHK(wave_dnat_launch(h->nat_np, Y, F, c->n_sent, D, (const float *)(din + w.mean), (const float *)(din + w.istd), nat_d, h->stream));
+    } else if (nat) {
         HIPCHK(wave_nat_launch(rows_d, F, c->n_sent, D, ctx, toff, nat_d, h->stream));
     }
     window_adopt(h, n, D, ctx, nat, false);

@@ -6,7 +6,7 @@
 //             [wave_target=lps|mask] [out_col=0] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2] [bunchsize=1024]
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
-//             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv] [rate=8000]
+//             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv] [rate=8000] [nat=static|dynamic]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
 //             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6] [lm_stream_block=<samples> [lm_stream_chan=<n>]]
 //             [lm_noise=vad|spp]
@@ -175,7 +175,7 @@ int main(int argc, char **argv)
     int activation = 0, device = 0, compute = 0, out_act = 0, out_lin = 0, out_loss = 0, target = BP_WAVE_LPS, out_col = 0;
     int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1, rate = 0;
     bool lm_chan_given = false;
-    int lm_noise = BP_NOISE_VAD;
+    int lm_noise = BP_NOISE_VAD, nat = BP_NAT_STATIC;
     float vis = 0.f, hid = 0.f;
     const char *const count = "is not a count >= 1";
     const Key keys[] = {
@@ -201,7 +201,8 @@ int main(int argc, char **argv)
         given.push_back(k);
         if (k == "lm_stream_chan") lm_chan_given = true;
         // output layer (.wts files do not record it): the keys and checks of bptrain
-        if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss) || lm_noise_key(a, WHO, "is not vad or spp", &lm_noise)) continue;
+        if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss) || lm_noise_key(a, WHO, "is not vad or spp", &lm_noise) ||
+            nat_key(a, WHO, "is not static or dynamic", &nat)) continue;
         // the log-MMSE parameters stay by hand: any lm_ name is a number first (nan and inf included), and only then a known key
         if (k.compare(0, 3, "lm_") != 0) fail("bpenhance: unknown key " + k);
         char *end = nullptr;
@@ -283,6 +284,7 @@ int main(int argc, char **argv)
     cfg.dropoutflag = dropoutflag; cfg.visible_omit = vis; cfg.hid_omit = hid; cfg.activation = activation; cfg.compute_dtype = compute;
     bp_handle *h = create_net(cfg, wts, out_act, out_lin, out_loss);
     check(bp_set_forward(h, forward));
+    set_nat(WHO, h, nat, ctx, fea_dim, ls);                      // (a stream opened below keeps the mode, as it keeps the forward's)
 
     std::vector<float> pcm, out;
     std::vector<int> lens;

@@ -7,7 +7,7 @@
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
-//          [scores=basic|extended] [rate=16000] [lm_noise=vad|spp]
+//          [scores=basic|extended] [rate=16000] [lm_noise=vad|spp] [nat=static|dynamic]
 //   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended] [rate=16000]
 //
 // rate=R (either mode): every clean, noise or pair WAV whose rate is not R is converted to R on the device as it is
@@ -67,6 +67,7 @@ struct Params {
     int baseline = 0;                                        // baseline=logmmse
     int lm_noise = BP_NOISE_VAD;                             // lm_noise=vad|spp
     bool lm_noise_given = false;
+    int nat = BP_NAT_STATIC;                                 // nat=static|dynamic: the noise-aware block of the net's input
     int ext = 0;                                             // scores=extended: five score columns
     RirKeys rir;                                             // rir_rooms=N ...: simulated responses in place of rir_list
 };
@@ -109,6 +110,7 @@ Params parse(int argc, char **argv)
         const Arg a = split_arg(argv[i]);
         if (key_apply(both, WHO, a)) continue;
         if (lm_noise_key(a, WHO, nullptr, &P.lm_noise)) P.lm_noise_given = true;
+        else if (nat_key(a, WHO, nullptr, &P.nat)) {}
         else if (!key_apply(keys, WHO, a)) {
             const int r = rir_key(P.rir, a.k, a.v);
             if (!r) fail("bpeval: unknown key " + a.k);
@@ -258,6 +260,7 @@ int main(int argc, char **argv)
     cfg.dropoutflag = P.dropoutflag; cfg.visible_omit = P.visible_omit; cfg.hid_omit = P.hid_omit;
     cfg.activation = P.activation; cfg.compute_dtype = P.compute_dtype;
     bp_handle *h = create_net(cfg, wts, P.output_act, P.output_linear_dims, P.output_loss);
+    set_nat(WHO, h, P.nat, ctx, D, P.layersizes);
     const bp_mix_corpus mc = describe(D, ctx, toff, P.layersizes[L - 1] == D ? BP_MIX_LPS : BP_MIX_LPS_IRM, 5.0f, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) set_reverb(h, P.rir, P.device, rv, P.seed, n_clean);

@@ -8,7 +8,7 @@
 //         [cv_noise_list=noise.list] [cv_seed=20261016] [mix_plan_out=plan.txt] [output_act=...] [compute=fp32|bf16] ...
 //         [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50] [cv_rir_list=rir.list]
 //         [rir_rooms=N] [rir_room_lo=3,3,2.5] [rir_room_hi=10,8,4] [rir_t60=0.2,0.8] [rir_margin=0.5] [rir_dist=0.5,3] [rir_ms=400]
-//         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N] [rate=8000]
+//         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N] [rate=8000] [nat=static|dynamic]
 //   bpmix clean_list=... noise_list=... fea_dim=129 norm_out=mix.norm [snr_list=...] [mix_per_clean=...] [init_randem_seed=...]
 //
 // The plan of the epoch is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list); it is cut into
@@ -54,6 +54,7 @@ struct Params {
     std::string clean_list, noise_list, cv_clean_list, cv_noise_list, norm_file, norm_out, mix_plan_out;
     std::string initwts_file, outwts_file, log_file, rir_list, cv_rir_list;
     int reverb_target = BP_REVERB_TARGET_REVERBERANT;
+    int nat = BP_NAT_STATIC;                                 // nat=static|dynamic: the noise-aware block of the net's input (not read by norm_out)
     float early_ms = 50.0f;
     int fea_dim = 0, fea_context = 1, targ_offset = 0, dropoutflag = 0, traincache = 0, bunchsize = 0, numlayers = 0, gpu_used = 1;
     int layersizes[BP_MAXLAYER] = {0}, mix_per_clean = 1, target = BP_MIX_LPS, activation = 0, momentum_rule = 0, compute_dtype = 0;
@@ -103,7 +104,7 @@ Params parse(int argc, char **argv)
     };
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
-        if (key_apply(keys, WHO, a)) continue;
+        if (key_apply(keys, WHO, a) || nat_key(a, WHO, nullptr, &P.nat)) continue;
         const int r = rir_key(P.rir, a.k, a.v);
         if (!r) fail("bpmix: unknown key " + a.k);
         if (r < 0) bad_value(WHO, a.k, a.v);
@@ -290,6 +291,7 @@ int main(int argc, char **argv)
     cfg.activation = P.activation; cfg.momentum_rule = P.momentum_rule; cfg.seed = P.dropout_seed; cfg.compute_dtype = P.compute_dtype;
     bp_handle *h = create_net(cfg, wts, P.output_act, P.output_linear_dims, P.output_loss);
     printf("Created net with %d layers, bunchsize %d.\n", L, P.bunchsize);
+    set_nat(WHO, h, P.nat, ctx, D, P.layersizes);
     const bp_mix_corpus mc = describe(D, ctx, toff, P.target, P.lc_db, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) {

@@ -201,6 +201,14 @@ inline bool lm_noise_key(const Arg &a, const char *tool, const char *tail, int *
     return key_apply(keys, tool, a);
 }
 
+// nat=static|dynamic as bpenhance (tail: its own text), bpmix and bpeval (tail null: `bad value`) take it: the
+// noise-aware block of the net's input, BP_NAT_STATIC or BP_NAT_DYNAMIC; net_setup.h's set_nat hands it to the handle
+inline bool nat_key(const Arg &a, const char *tool, const char *tail, int *mode)
+{
+    const Key keys[] = {{"nat", K_CHOICE, mode, BP_NAT_STATIC, 0, "static|dynamic", tail}};
+    return key_apply(keys, tool, a);
+}
+
 // output_act / output_linear_dims / output_loss as bptrain, bpforward and bpenhance take them: strict, with their own texts (a
 // typo must not silently run a different model)
 inline bool output_key(const Arg &a, int *act, int *dims, int *loss)

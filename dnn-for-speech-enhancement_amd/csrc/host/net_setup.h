@@ -92,4 +92,14 @@ inline bp_handle *create_net(const bp_config &cfg, Weights &w, int output_act, i
     return h;
 }
 
+// nat=dynamic (keys.h: nat_key) on the handle, with the tracker's defaults.  A net without the noise-aware block ends the run here,
+// in the tool's name, and not at the first call that stages the block.  nat=static is the run without the key: nothing is called.
+inline void set_nat(const char *tool, bp_handle *h, int nat, int context, int fea_dim, const int *ls)
+{
+    if (nat != BP_NAT_DYNAMIC) return;
+    if ((long)ls[0] != (long)(context + 1) * fea_dim)
+        fail(std::string(tool) + ": nat=dynamic needs a net with the noise-aware block: layersizes[0] = (fea_context+1)*fea_dim");
+    check(bp_set_nat(h, BP_NAT_DYNAMIC, nullptr));
+}
+
 }  // namespace bp

@@ -630,6 +630,41 @@ int bp_lmstream_open_nt(int device, int fea_dim, const bp_logmmse_params *p, con
                         int max_push_samples, bp_lmstream **out);
 
 /* ------------------------------------------------------------------------------------
+ * The dynamic noise-aware input: a tracked noise estimate per frame in place of one row per sentence (dynamic noise-aware
+ * training, Xu, Du, Dai, Lee, Interspeech 2014; no counterpart in the reference's code).  INTEGRATION.md 1o, DESIGN.md 27.
+ *
+ * A net with the noise-aware block (layersizes[0] == (context+1)*fea_dim) gets in = window(t) ++ nat.  BP_NAT_STATIC (the default,
+ * today's code path and bits): nat is one row per sentence, the mean of its first 6 normalised frames.  BP_NAT_DYNAMIC: one row per
+ * frame, the noise PSD that the MMSE-SPP tracker above holds at that frame, as a normalised LPS row.  Per sentence of T frames and
+ * per bin k, Y the noisy spectrum of the analysis (1d), np the parameters of bp_set_nat in the units of the tracker above:
+ *   P_t    = |Y_t[k]|^2                                          in double, from the fp32 parts of Y: exact products, one rounding
+ *   lambda = max((sum_{t < min(6,T)} P_t, ascending t) / min(6,T), 1e-10);   pbar = 0        (the noise start, init_frames = 6)
+ *   for t = 0 .. T-1:
+ *     the tracker's step of frame t (ph, pbar, r, the ceiling, lambda: the five lines of mode BP_NOISE_SPP above)
+ *     nat[t][k] = (l - mean[k]) * inv_std[k],   l = fl32(lambda) > 1e-10f ? logf(fl32(lambda)) : ln(1e-10)     in fp32
+ * Sample g of the window chunk -- frame t of sentence s -- gets in = window(t) ++ nat[t]; its table entry nat_row[g] is the global
+ * frame index F_s + t, not s.  No decision anywhere (min, max and the clamp only).  De-normalised, the rows are the log of the
+ * out_noise of bp_logmmse_waves_nt on the same PCM with default bp_logmmse_params: the same Y bits, the same tracker, the same fl32.
+ *
+ * bp_set_nat(h, mode, np): np NULL means bp_noise_defaults.  BP_ERR_ARG, with the handle unchanged and a message that names the
+ * field, for a null handle, a mode that is neither constant, np->mode != BP_NOISE_SPP together with BP_NAT_DYNAMIC (the VAD-gated
+ * update needs the gains of the log-MMSE recursion), and the range rules of bp_noise_params (checked in either mode).  The setter
+ * does not know `context`: BP_NAT_DYNAMIC on a net WITHOUT the block (layersizes[0] == context*fea_dim) is the BP_ERR_ARG of the
+ * first call that stages the block.  Those calls follow the mode from the next call on: bp_enhance_waves, bp_train_mix, bp_cv_mix,
+ * bp_mix_features, bp_eval_mix and bp_eval_mix_ext.  In BP_NAT_DYNAMIC the `nat` output of bp_mix_features is [sum T][fea_dim], one
+ * row per frame in the order of `fea`.  Calls that hand over their own rows do not read the mode (bp_upload_chunk*,
+ * bp_train_chunk_windows, bp_cv_chunk_windows, bp_forward_windows: a caller passes one row per frame through bp_window_chunk.nat
+ * and nat_row as it always could); neither do bp_eval_mix_logmmse* and the other calls without a net.
+ * A stream keeps the mode and the parameters its handle had at bp_stream_open, as it keeps the forward's mode (default and packed
+ * streams alike); a later bp_set_nat does not change open streams.  bp_stream_counts is unchanged: a dynamic stream is nat = 1, and
+ * the noise start is what makes a sentence's first output wait for 6 frames.  A dynamic stream carries lambda and pbar,
+ * 2 fea_dim doubles of device state per channel, across pushes; a sentence's end resets them.  Whatever the block sizes, a
+ * finished sentence returns the bits of bp_enhance_waves in the same mode.
+ * On an attached data-parallel handle every rank passes the same values, as for bp_set_output.  Additive: bp_abi_version stays 5. */
+enum { BP_NAT_STATIC = 0, BP_NAT_DYNAMIC = 1 };
+int bp_set_nat(bp_handle *h, int mode, const bp_noise_params *np);   /* np NULL: bp_noise_defaults */
+
+/* ------------------------------------------------------------------------------------
  * Sample-rate conversion by a rational factor (no reference counterpart: its README sends its users to TIMIT at 16 kHz, NOISEX-92
  * at 19.98 kHz and 100 noise types at 20 kHz for nets that work at 8 kHz, and leaves the conversion to outside tools).
  * INTEGRATION.md 1m, DESIGN.md 24.  Defined to the bit, as the reverberation FIR above is.
