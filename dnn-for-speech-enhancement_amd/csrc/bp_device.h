@@ -26,6 +26,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32
 {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
+        // (two multiplies per product, v_mul_hi_u32 + v_mul_lo_u32, on purpose: written as (uint64_t)c * x it is ONE v_mad_u64_u32,
+        // which is faster with many waves per SIMD but 10 % slower as the chain of dependent products that a GEMM epilogue's single
+        // wave per SIMD runs -- tools/philox_mul_probe.hip, profiles/r16_gemm_tail.txt section 3)
         const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
         const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
         const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;

@@ -159,6 +159,32 @@ __device__ __forceinline__ void epilogue_fetch(const EpiArgs &e, int mb, int nb,
     }
 }
 
+// Stores of registers [R0, R0+RN) of a block: v[r - R0] to row (r&3) + 8*(r>>2) + 4*(lane>>5), column lane&31 of the block at
+// (mb, nb) of C.  A block wholly below m_limit stores through the weight gradient's form, a uniform row base in SGPRs plus one
+// 32-bit lane offset, behind ONE test; a partial block tests every row and forms its 64-bit address.  Rows at or past m_limit are
+// never written (the dEdX rows past the bunch stay zero for the weight gradient).  The caller has sent lanes n >= n_limit away.
+template <int R0, int RN>
+__device__ __forceinline__ void block_store(const EpiArgs &e, int mb, int nb, int lane, const float (&v)[RN])
+{
+    if (mb + 32 <= e.m_limit) {
+        float *c = uniform_ptr(e.C + (size_t)mb * e.ldc + nb);
+        const unsigned ldc = __builtin_amdgcn_readfirstlane(e.ldc);
+        const unsigned lob = 4u * ((unsigned)(4 * (lane >> 5)) * (unsigned)e.ldc + (unsigned)(lane & 31));   // bytes
+#pragma unroll
+        for (int r = R0; r < R0 + RN; ++r) {
+            const unsigned ro = (unsigned)((r & 3) + 8 * (r >> 2)) * ldc;
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(sgpr_row_base(c + ro)) + lob) = v[r - R0];
+        }
+        return;
+    }
+    const int n = nb + (lane & 31), rbase = mb + 4 * (lane >> 5);
+#pragma unroll
+    for (int r = R0; r < R0 + RN; ++r) {
+        const int m = rbase + (r & 3) + 8 * (r >> 2);
+        if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = v[r - R0];
+    }
+}
+
 template <int EPI, int R0, int RN>
 __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb, const f32x16 &acc, int lane,
                                                const EpiPre &p)
@@ -194,6 +220,7 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
     if constexpr (EPI == EPI_FWD_HIDDEN) {
         const float bn = p.bias;
         const bool live = n < e.n_true;
+        float y[RN];
 #pragma unroll
         for (int q = R0 / 4; q < (R0 + RN) / 4; ++q) {
             uint32_t w[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
@@ -204,12 +231,11 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             } else if (e.drop_thresh) drop_words4(w, r0, n, e.frame_off, (uint32_t)e.n_true, e.layer, e.step, e.seed_lo, e.seed_hi);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int m = r0 + j;
-                float y = act_fwd(e.act, e.alpha * acc[q * 4 + j] + bn);
-                if (!live || w[j] < e.drop_thresh) y = 0.0f;
-                if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = y;
+                y[q * 4 + j - R0] = act_fwd(e.act, e.alpha * acc[q * 4 + j] + bn);
+                if (!live || w[j] < e.drop_thresh) y[q * 4 + j - R0] = 0.0f;
             }
         }
+        block_store<R0, RN>(e, mb, nb, lane, y);
     } else if constexpr (EPI == EPI_FWD_OUT) {
         const float bn = p.bias;
         const bool live = n < e.n_true;
@@ -242,11 +268,10 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             }
         }
     } else if constexpr (EPI == EPI_DGRAD) {
+        float d[RN];
 #pragma unroll
-        for (int r = R0; r < R0 + RN; ++r) {
-            const int m = rbase + (r & 3) + 8 * (r >> 2);
-            if (m < e.m_limit) e.C[(size_t)m * e.ldc + n] = act_bwd(e.act, p.p0[r]) * acc[r];   // kernDsigmoid*kernVecMul
-        }
+        for (int r = R0; r < R0 + RN; ++r) d[r - R0] = act_bwd(e.act, p.p0[r]) * acc[r];   // kernDsigmoid*kernVecMul
+        block_store<R0, RN>(e, mb, nb, lane, d);
     } else {
         static_assert(EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE, "epilogue without a branch");   // (wgrad returned above)
     }
@@ -526,9 +551,28 @@ __device__ __forceinline__ int problem_of(const Multi &a, int b, int p)
     return p;
 }
 
-// The workgroup program of one GEMM problem: workgroups first_block, first_block+stride, ... of
-// the launch walk its tiles.  Wrapped by bp_gemm (one problem per launch), bp_gemm_multi (up to
-// four independent problems in one launch) and bp_out_split_stage.
+// Host side of GemmKernel::run's one-tile-per-workgroup contract, checked in front of every launch that wraps it (bp_step.hip;
+// tests/cpp/one_tile_driver.cc): a problem's workgroups -- its share of the launch, the stride a walk over tiles would have --
+// cover its tile list (times the k-slices of a split launch), so no tile is left to a second trip that does not exist.
+static inline bool covers_tiles(long long workgroups, const GemmArgs &g, int slices = 1)
+{
+    return g.tiles_m >= 0 && g.tiles_n >= 0 && workgroups >= (long long)g.tiles_m * g.tiles_n * slices;
+}
+template <class Multi>
+static inline bool multi_covers_tiles(const Multi &a)
+{
+    if (a.n < 1 || a.n > 4) return false;
+    for (int p = 0; p < a.n; ++p)
+        if (!covers_tiles((long long)a.first_tile[p + 1] - a.first_tile[p], a.g[p])) return false;
+    return true;
+}
+
+// The workgroup program of one GEMM problem: workgroup `b` of the problem computes tile b of it, ONE tile per workgroup (a b at or
+// past the tile count is a padding entry and returns).  Wrapped by bp_gemm (one problem per launch), bp_gemm_multi (up to four
+// independent problems in one launch) and bp_out_split_stage; the host gives every problem at least as many workgroups as it has
+// tiles and refuses a launch that would not (covers_tiles above).  There is no walk over further tiles: no launch of the
+// library ever took a second trip, and the loop cost every body a second copy of the tile loads, a barrier and a second tile map
+// (profiles/r16_gemm_tail.txt section 2).  bp_wgrad_dma, the one persistent launch, has its own walk.
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, int EPI>
 struct GemmKernel {
     using Cfg = GemmCfg<BM, BN, BK, WM, WN, A_KC, B_KC, EPI>;
@@ -542,16 +586,15 @@ struct GemmKernel {
     // workgroups per CU the register allocator must leave room for (launch bounds)
     static constexpr int MIN_WG = (SMEM * 4 > 80 * 1024) ? 1 : 2;
 
-static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &e_in, int first_block, int stride,
-                                           int block_y, float *smem)
+static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &e_in, int b, int block_y, float *smem)
 {
     using Regs = typename Cfg::Regs;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform => SGPR row bases
     constexpr int EPI_E = EPI == EPI_OUT_SPLIT ? EPI_FWD_OUT : EPI == EPI_OUT_SPLIT_LOGI ? EPI_FWD_OUT_LOGI : EPI;      // the epilogue proper
 #ifdef BP_TRACE
-#define TRACE(i) do { if (tid == 0 && g_in.trace) { g_in.trace[(size_t)first_block * 8 + (i)] = wall_clock64();           \
-        if ((i) == 0) g_in.trace[(size_t)first_block * 8 + 6] = clock64();   /* shader-clock counter: */           \
-        if ((i) == 3) g_in.trace[(size_t)first_block * 8 + 7] = clock64();   /* effective MHz of the run */        \
+#define TRACE(i) do { if (tid == 0 && g_in.trace) { g_in.trace[(size_t)b * 8 + (i)] = wall_clock64();           \
+        if ((i) == 0) g_in.trace[(size_t)b * 8 + 6] = clock64();   /* shader-clock counter: */           \
+        if ((i) == 3) g_in.trace[(size_t)b * 8 + 7] = clock64();   /* effective MHz of the run */        \
     } } while (0)
 #else
 #define TRACE(i) ((void)0)
@@ -563,7 +606,7 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
 #define BS(buf) (smem + (buf) * STAGE + A_STAGE)
 
     TRACE(0);                                     // (development build: at the entry, so that the trace's prologue contains the head)
-    // ---- head: the loads of k-tiles 0 and 1 of the workgroup's first tile go out before anything else.  A workgroup is alone on
+    // ---- head: the loads of k-tiles 0 and 1 of the workgroup's tile go out before anything else.  A workgroup is alone on
     // its SIMDs when it starts, so whatever runs in front of its first load is paid as latency with nothing in flight.
     // Only the operand side of the arguments is read here (one batch of scalar loads, one wait); the epilogue's arguments, the
     // accumulators and the epilogue's own fetches follow behind the loads.
@@ -575,14 +618,13 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     }
     BP_PIN_OPERANDS(g);
     const int tiles = g.tiles_m * g.tiles_n;
-    int b = first_block;
-    if (b >= tiles) return;                       // (padding entry of a grouped launch)
+    if (b >= tiles) return;                      // (padding entry of a grouped launch)
     const int nt = (g.K + BK - 1) / BK, last_k0 = (nt - 1) * BK;
     typename Cfg::Offs offs;
     Cfg::make_offs(offs, g, tid);
     int tile_m, tile_n;
     xcd_tile<BIASG>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
-    int m0 = tile_m * BM, n0 = tile_n * BN;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
     // Two register images hold k-tiles t+1 (landed, being staged) and t+2 (in flight) of the software pipeline below.  Every load
     // is unconditional (past the end the tile index is clamped and the data ignored): a conditional load turns into a phi + copy
     // and hipcc then waits for it right away.
@@ -594,9 +636,10 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // The epilogue's arguments are read HERE, behind the loads, at an offset the optimiser does not know to be 0.  Read plainly
     // (e = e_in), their scalar loads are hoisted into the blocks in front of the tile map (a sched_barrier orders one basic block),
     // and the first use of any of them there -- hipcc spills one into a VGPR lane -- is a second full scalar wait in front of the
-    // first operand load.  WHEN THE COMPILER CHANGES, rerun the listing check of profiles/r15_gemm_head.txt section 1: this asm,
-    // BP_PIN_OPERANDS and the asm in bp_gemm_multi steer hipcc by side effects it does not promise, and no test on a machine
-    // without a GPU holds the instruction and wait counts in front of the first global_load_dwordx4.
+    // first operand load.  WHEN THE COMPILER CHANGES, rerun the listing check of profiles/r15_gemm_head.txt section 1 and look for
+    // copies of r1 in front of the k-loop (profiles/r16_gemm_tail.txt section 2): this asm, BP_PIN_OPERANDS, the asm in bp_gemm_multi
+    // and the branch weight on the k-loop steer hipcc by side effects it does not promise, and no test on a machine without a GPU
+    // holds the instruction and wait counts in front of the first global_load_dwordx4 or the first MFMA.
     int behind = 0;
     asm volatile("" : "+s"(behind));
     const EpiArgs e = *reinterpret_cast<const EpiArgs *>(reinterpret_cast<const char *>(&e_in) + behind);
@@ -604,9 +647,6 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     const int a_off = wm * TM * 32 + (lane & 31), b_off = wn * TN * 32 + (lane & 31);
     const int kh = lane >> 5;
 
-    // Persistent over tiles (grid may be smaller than the tile count): the epilogue's stores of
-    // one tile are still draining while the next tile's k-loop runs.
-    for (;;) {
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);   // bias-gradient partial sums (wgrad; used by m-tile 0)
     const bool do_bias = BIASG && tile_m == 0;
 
@@ -652,7 +692,11 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // (r1 for even t, r0 for odd t).  The iteration multiplies tile t and, between the MFMAs, issues the global loads of tile
     // t+2 and moves tile t+1 into the other stage.  The steady-state loop contains no conditionals (a conditional step makes
     // hipcc copy the accumulators between register ranges every iteration); the last one or two tiles run after.
+    // The loop is marked as the expected path (every layer of a real net has three or more k-tiles).  Without the mark hipcc
+    // keeps the image r1 that the head loaded in other registers than the loop's r1 and copies it over in front of the loop,
+    // behind a full vmcnt(0): the first MFMA then waits for all of k-tile 1 (profiles/r16_gemm_tail.txt section 2).
     int t = 0, buf = 0;
+    if (__builtin_expect(nt >= 3, 1))
     for (; t + 3 <= nt; t += 2) {
         STEP(true, true, 0, r1, t + 1, r0, t + 2);
         __syncthreads();
@@ -762,14 +806,6 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
             if (ks == 3) epilogue_block<EPI_E, 12, 4>(e, mb0, nb0, acc[0][0], lane, pre[0][0]);
         }
     }
-    b += stride;
-    if (b >= tiles) break;
-    __syncthreads();                              // smem is reused by the next tile
-    xcd_tile<BIASG>(b, g.tiles_m, g.tiles_n, tile_m, tile_n);
-    m0 = tile_m * BM; n0 = tile_n * BN;
-    Cfg::load(r0, PA(0), PB(0), offs);            // (the next tile's loads in front of its setup as well)
-    Cfg::load(r1, PA(1), PB(1), offs);
-    }   // tile loop
     TRACE(3);
 #undef K0_OF
 #undef PA
@@ -786,7 +822,7 @@ __global__ __launch_bounds__(256, (GemmKernel<BM, BN, BK, WM, WN, A_KC, B_KC, EP
 {
     using K = GemmKernel<BM, BN, BK, WM, WN, A_KC, B_KC, EPI>;
     __shared__ __attribute__((aligned(16))) float smem[K::SMEM];
-    K::run(g, e, blockIdx.x, gridDim.x, blockIdx.y, smem);
+    K::run(g, e, blockIdx.x, blockIdx.y, smem);
 }
 
 // Up to 4 INDEPENDENT problems of the same tile configuration in one launch (grouped GEMM): the
@@ -824,7 +860,7 @@ __global__ __launch_bounds__(256, K::MIN_WG) void bp_gemm_multi(const MultiArgs 
         g = a.g[p];
         first = a.first_tile[p]; next = a.first_tile[p + 1];
     }
-    K::run(g, a.e[p], b - first, next - first, 0, smem);
+    K::run(g, a.e[p], b - first, 0, smem);
 }
 
 // ------------------------------------------------------------------ small kernels
@@ -981,6 +1017,6 @@ __global__ __launch_bounds__(256, K::MIN_WG) void bp_out_split_stage(const GemmA
     GemmArgs gg = g;
     int ng = n_gemm;
     BP_PIN_OPERANDS(gg, "+s"(ng), "+s"(gg.k_split));
-    if (b < ng) { const int tiles = gg.tiles_m * gg.tiles_n; K::run(gg, e, b % tiles, tiles, b / tiles, smem); }
+    if (b < ng) { const int tiles = gg.tiles_m * gg.tiles_n; K::run(gg, e, b % tiles, b / tiles, smem); }
     else { const int i = b - ng; stage_block(st, i % st.nbx, i / st.nbx, threadIdx.x); }
 }

@@ -304,7 +304,9 @@ static hipError_t launch(hipStream_t st, GemmArgs g, const EpiArgs &e, int M, in
 {
     g.tiles_m = (M + BM - 1) / BM;
     g.tiles_n = (N + BN - 1) / BN;
-    hipLaunchKernelGGL((bp_gemm<BM, BN, BK, WM, WN, A_KC, B_KC, EPI, TAG>), dim3(g.tiles_m * g.tiles_n), dim3(256), 0, st, g, e);
+    const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n);
+    if (!covers_tiles(grid, g)) return hipErrorInvalidConfiguration;      // (one tile per workgroup: GemmKernel::run walks no further)
+    hipLaunchKernelGGL((bp_gemm<BM, BN, BK, WM, WN, A_KC, B_KC, EPI, TAG>), dim3(grid), dim3(256), 0, st, g, e);
     return hipGetLastError();
 }
 
@@ -356,6 +358,7 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
         const int n_gemm = g.tiles_m * g.tiles_n * OUT_SPLITS;
         StageArgs sa; memset(&sa, 0, sizeof(sa));
         int n_stage = 0;
+        if (!covers_tiles(n_gemm, g, OUT_SPLITS)) return hipErrorInvalidConfiguration;   // (workgroup b: slice b / tiles of tile b % tiles)
         if (train && h->next_first >= 0) {
             // another staged bunch behind this one (window chunk, or stacked chunk with visible dropout): stack / copy (and mask, with the NEXT step's Philox position) that bunch
             // into the other tile from the spare workgroups of this launch
@@ -457,6 +460,7 @@ static hipError_t run_multi(hipStream_t st, Prepared *ps, int n, int slots = 1 <
         a.g[i] = ps[i].g; a.e[i] = ps[i].e; tiles[i] = ps[i].g.tiles_m * ps[i].g.tiles_n;
     }
     const int t = pack_tiles(a, tiles, n);
+    if (!multi_covers_tiles(a)) return hipErrorInvalidConfiguration;     // (bp_gemm_multi: one tile per entry; bp_wgrad_dma walks the entries itself)
     hipLaunchKernelGGL(KERNEL, dim3(t < slots ? t : slots), dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256, MINWG) void bp_dgrad_wgrad(const GemmArgs dg, 
     constexpr int SM = DG::SMEM > WG::SMEM ? DG::SMEM : WG::SMEM;
     __shared__ __attribute__((aligned(16))) float smem[SM];
     const int b = blockIdx.x;
-    if (b < n_dg) { DG::run(dg, de, b, n_dg, 0, smem); return; }
+    if (b < n_dg) { DG::run(dg, de, b, 0, smem); return; }
     const int bw = b - n_dg;
     int p = 0;
     while (p + 1 < w.n && bw >= w.first_tile[p + 1]) ++p;

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256, KF::MIN_WG) void fwd_chain2(const GemmArgs g1,
                                                                unsigned long long budget, unsigned *err)
 {
     __shared__ __attribute__((aligned(16))) float smem[KF::SMEM];
-    KF::run(g1, e1, blockIdx.x, gridDim.x, 0, smem);
+    KF::run(g1, e1, blockIdx.x, 0, smem);
     // which m-tile this workgroup holds (the XCD-aware map of GemmKernel::run, forward form)
     const int b = blockIdx.x, j = b >> 3;
     const int tile_m = (g1.tiles_n & 7) == 0 ? j % g1.tiles_m : b % g1.tiles_m;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256, KF::MIN_WG) void fwd_chain2(const GemmArgs g1,
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
     __syncthreads();
-    KF::run(g2, e2, blockIdx.x, gridDim.x, 0, smem);
+    KF::run(g2, e2, blockIdx.x, 0, smem);
 }
 
 static unsigned long long rng_s = 0x9E3779B97F4A7C15ull;

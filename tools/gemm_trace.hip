@@ -1,6 +1,7 @@
 // tools/gemm_trace.hip -- development probe: per-workgroup phase timestamps (100 MHz wall clock) of
 // back-to-back bp_gemm launches: entry, end of prologue, end of k-loop, end of epilogue.
-// usage: gemm_trace fwd|dgrad|wgrad|wg64 [K]     (dgrad: the 128-deep hidden dgrad through the grouped wrapper, one problem)
+// usage: gemm_trace fwd|fwd0|dgrad|wgrad|wg64 [K]     (dgrad: the 128-deep hidden dgrad through the grouped wrapper, one problem;
+//                                                   fwd0: the forward without dropout, drop_thresh = 0 -- fwd minus fwd0 sizes the draw)
 #define BP_TRACE 1
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -28,7 +29,8 @@ int main(int argc, char **argv)
         e.C = W; e.ldc = H; e.m_limit = MW; e.n_limit = H; e.n_true = H; e.aux2 = D; e.ldaux2 = H; e.mom = 0.5f; e.ndiv = 256.f; e.bias_w = bias; e.bias_d = bd;
     } else {
         g.A = Y; g.lda = H; g.B = W; g.ldb = H; g.K = K; g.tiles_m = 8; g.tiles_n = 32;
-        e.C = Yo; e.ldc = H; e.m_limit = B; e.n_limit = H; e.n_true = H; e.bias = bias; e.drop_thresh = 858993459u;
+        e.C = Yo; e.ldc = H; e.m_limit = B; e.n_limit = H; e.n_true = H; e.bias = bias;
+        e.drop_thresh = (argc > 1 && !strcmp(argv[1], "fwd0")) ? 0u : 858993459u;
     }
     hipStream_t st; CK(hipStreamCreate(&st));
     for (int rep = 0; rep < 3; ++rep) {
