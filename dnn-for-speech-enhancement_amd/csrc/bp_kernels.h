@@ -362,9 +362,26 @@ struct GemmCfg {
     static_assert(NVA >= 1 && NVB >= 1, "tile too small for 256 threads");
     using Regs = TileRegs<NVA, NVB>;
 
-    // Addressing: uniform tile base (SGPR) + per-thread 32-bit offset that never changes, so a
-    // load is one instruction and the k-advance is scalar arithmetic.
-    struct Offs { int a[NVA]; int b[NVB]; };
+    // The k-loop's index functions (tests/cpp/kloop_order_driver.cc enumerates them on the host): of every k-tile wave group ks
+    // multiplies rows [ks*BK/KS, (ks+1)*BK/KS) in NK steps of two rows (lane half kh takes the odd one), step s into chain s % NCH.
+    static constexpr int NCH = (TM * TN == 1) ? 2 : 1;
+    static constexpr int NK = BK / KS / 2;
+    static constexpr int step_row(int ks, int s) { return ks * (BK / KS) + 2 * s; }
+    static constexpr int step_chain(int s) { return s % NCH; }
+
+    // Addressing: uniform tile base (SGPR pair) + per-thread unsigned 32-bit BYTE offset that never changes: a load is one
+    // instruction (global_load_dwordx4 v, v_off, s[base:base+1]) and the k-advance is scalar arithmetic.  Two things are needed
+    // for hipcc to select that form.  The offset is unsigned bytes: a signed element offset is sign-extended and scaled, a 64-bit
+    // VALU add per load with every offset held as a VGPR pair.  And it is made opaque, in place, where it is used (lane_off): the
+    // zero extension then stays in the block of the load, where instruction selection can fold it into the address; hoisted out
+    // of the k-loop it comes back as a VGPR pair and the same add.  Those adds were the only VALU instructions of the
+    // steady-state loops, 12 per 32 MFMAs, and cost the wide forward 1.9 us of an 18.3 us k-loop (profiles/r17_kloop_pairs.txt).
+    struct Offs { unsigned a[NVA]; unsigned b[NVB]; };
+    static __device__ __forceinline__ unsigned lane_off(unsigned &off)
+    {
+        asm volatile("" : "+v"(off));
+        return off;
+    }
     static __device__ __forceinline__ void make_offs(Offs &o, const GemmArgs &g, int tid)
     {
 #pragma unroll
@@ -372,10 +389,10 @@ struct GemmCfg {
             const int f = tid + i * 256;
             if constexpr (A_KC) {
                 const int l8 = f % LPS, seg = f / LPS, row = seg % BM, k4 = (seg / BM) * LPS + l8;
-                o.a[i] = row * g.lda + k4 * 4;
+                o.a[i] = 4u * (unsigned)(row * g.lda + k4 * 4);
             } else {
                 const int c4 = f % (BM / 4), k = f / (BM / 4);
-                o.a[i] = k * g.lda + c4 * 4;
+                o.a[i] = 4u * (unsigned)(k * g.lda + c4 * 4);
             }
         }
 #pragma unroll
@@ -383,10 +400,10 @@ struct GemmCfg {
             const int f = tid + i * 256;
             if constexpr (B_KC) {
                 const int l8 = f % LPS, seg = f / LPS, row = seg % BN, k4 = (seg / BN) * LPS + l8;
-                o.b[i] = row * g.ldb + k4 * 4;
+                o.b[i] = 4u * (unsigned)(row * g.ldb + k4 * 4);
             } else {
                 const int c4 = f % (BN / 4), k = f / (BN / 4);
-                o.b[i] = k * g.ldb + c4 * 4;
+                o.b[i] = 4u * (unsigned)(k * g.ldb + c4 * 4);
             }
         }
     }
@@ -399,15 +416,15 @@ struct GemmCfg {
     {
         return B_KC ? g.B + (size_t)n0 * g.ldb + k0 : g.B + (size_t)k0 * g.ldb + n0;
     }
-    static __device__ __forceinline__ void load_a(Regs &r, int i, const float *pa, const Offs &o)
+    static __device__ __forceinline__ void load_a(Regs &r, int i, const float *pa, Offs &o)
     {
-        r.a[i] = *reinterpret_cast<const float4 *>(pa + o.a[i]);
+        r.a[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(pa) + lane_off(o.a[i]));
     }
-    static __device__ __forceinline__ void load_b(Regs &r, int i, const float *pb, const Offs &o)
+    static __device__ __forceinline__ void load_b(Regs &r, int i, const float *pb, Offs &o)
     {
-        r.b[i] = *reinterpret_cast<const float4 *>(pb + o.b[i]);
+        r.b[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(pb) + lane_off(o.b[i]));
     }
-    static __device__ __forceinline__ void load(Regs &r, const float *pa, const float *pb, const Offs &o)
+    static __device__ __forceinline__ void load(Regs &r, const float *pa, const float *pb, Offs &o)
     {
 #pragma unroll
         for (int i = 0; i < NVA; ++i) load_a(r, i, pa, o);
@@ -466,16 +483,15 @@ struct GemmCfg {
     // (register image rs) into the other LDS stage.  Everything except the first RD fragment
     // reads issues while the matrix pipe is busy.  NCH independent accumulator chains
     // (a single dependent v_mfma_f32_32x32x2_f32 chain only reaches 90 % of the issue rate).
-    static constexpr int NCH = (TM * TN == 1) ? 2 : 1;
     template <bool DO_STORE, bool DO_LOAD>
     static __device__ __forceinline__ void step(const float *As, const float *Bs, f32x16 (&acc)[NCH][TM][TN], int ks,
                                                 int a_off, int b_off, int kh, const Regs &rs, float *AsN, float *BsN,
-                                                Regs &rl, const float *pa, const float *pb, const Offs &o, int tid,
+                                                Regs &rl, const float *pa, const float *pb, Offs &o, int tid,
                                                 float4 &bsum, int krows)
     {
-        constexpr int NK = BK / KS / 2, NP = NVA + NVB, RD = NK < 4 ? NK : 4;
-        const float *ap = As + (ks * (BK / KS) + kh) * LDA_S + a_off;
-        const float *bp = Bs + (ks * (BK / KS) + kh) * LDB_S + b_off;
+        constexpr int NP = NVA + NVB, RD = NK < 4 ? NK : 4;
+        const float *ap = As + (step_row(ks, 0) + kh) * LDA_S + a_off;        // step s reads rows step_row(ks, s) + kh
+        const float *bp = Bs + (step_row(ks, 0) + kh) * LDB_S + b_off;
         float av[NK][TM], bv[NK][TN];
         // hipcc's scheduler otherwise sinks every ds_read next to its MFMA (one exposed LDS latency
         // per pair), gathers the ds_writes in front of the barrier and the global loads + their
@@ -484,9 +500,9 @@ struct GemmCfg {
 #pragma unroll
         for (int s = 0; s < RD; ++s) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) av[s][i] = ap[2 * s * LDA_S + i * 32];
+            for (int i = 0; i < TM; ++i) av[s][i] = ap[step_row(0, s) * LDA_S + i * 32];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) bv[s][j] = bp[2 * s * LDB_S + j * 32];
+            for (int j = 0; j < TN; ++j) bv[s][j] = bp[step_row(0, s) * LDB_S + j * 32];
         }
         __builtin_amdgcn_sched_barrier(0);
         int pl = 0, ps = 0;
@@ -496,12 +512,12 @@ struct GemmCfg {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[s % NCH][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][i], bv[s][j], acc[s % NCH][i][j], 0, 0, 0);
+                    acc[step_chain(s)][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][i], bv[s][j], acc[step_chain(s)][i][j], 0, 0, 0);
             if (s + RD < NK) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) av[s + RD][i] = ap[2 * (s + RD) * LDA_S + i * 32];
+                for (int i = 0; i < TM; ++i) av[s + RD][i] = ap[step_row(0, s + RD) * LDA_S + i * 32];
 #pragma unroll
-                for (int j = 0; j < TN; ++j) bv[s + RD][j] = bp[2 * (s + RD) * LDB_S + j * 32];
+                for (int j = 0; j < TN; ++j) bv[s + RD][j] = bp[step_row(0, s + RD) * LDB_S + j * 32];
             }
             if constexpr (DO_LOAD) {
 #pragma unroll
@@ -637,9 +653,11 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // (e = e_in), their scalar loads are hoisted into the blocks in front of the tile map (a sched_barrier orders one basic block),
     // and the first use of any of them there -- hipcc spills one into a VGPR lane -- is a second full scalar wait in front of the
     // first operand load.  WHEN THE COMPILER CHANGES, rerun the listing check of profiles/r15_gemm_head.txt section 1 and look for
-    // copies of r1 in front of the k-loop (profiles/r16_gemm_tail.txt section 2): this asm, BP_PIN_OPERANDS, the asm in bp_gemm_multi
-    // and the branch weight on the k-loop steer hipcc by side effects it does not promise, and no test on a machine without a GPU
-    // holds the instruction and wait counts in front of the first global_load_dwordx4 or the first MFMA.
+    // copies of r1 in front of the k-loop (profiles/r16_gemm_tail.txt section 2), and for VALU instructions in the steady-state
+    // loop (profiles/r17_kloop_pairs.txt section 1: there are none, every operand load is global_load_dwordx4 v, v_off, s[base]):
+    // this asm, BP_PIN_OPERANDS, the asm in bp_gemm_multi, the one in GemmCfg::lane_off and the branch weight on the k-loop steer
+    // hipcc by side effects it does not promise, and no test on a machine without a GPU holds the instruction and wait counts in
+    // front of the first global_load_dwordx4 or the first MFMA, or the instruction mix of the loop.
     int behind = 0;
     asm volatile("" : "+s"(behind));
     const EpiArgs e = *reinterpret_cast<const EpiArgs *>(reinterpret_cast<const char *>(&e_in) + behind);
@@ -695,6 +713,10 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // The loop is marked as the expected path (every layer of a real net has three or more k-tiles).  Without the mark hipcc
     // keeps the image r1 that the head loaded in other registers than the loop's r1 and copies it over in front of the loop,
     // behind a full vmcnt(0): the first MFMA then waits for all of k-tile 1 (profiles/r16_gemm_tail.txt section 2).
+    // One barrier per k-tile stays, also in the wide forward's 64-deep loop: two of its tiles per LDS stage (one barrier per 32
+    // MFMAs, behind a first step of one tile) were built twice and measured 4.7 and 10.1 us per step SLOWER than this loop
+    // (profiles/r17_kloop_pairs.txt section 3).  What the loop must not contain is VALU work: 12 64-bit adds per two k-tiles cost the
+    // forward a tenth of its k-loop (GemmCfg::lane_off).
     int t = 0, buf = 0;
     if (__builtin_expect(nt >= 3, 1))
     for (; t + 3 <= nt; t += 2) {

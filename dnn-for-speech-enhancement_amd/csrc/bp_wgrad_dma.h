@@ -68,7 +68,7 @@ struct WgradDma {
     static_assert((D - 1) * NDMA + (NWD > NST ? NWD : NST) < 64, "vmcnt is 6 bits");
 
     struct Pos { int p, m0, n0; };                                // problem of the launch, origin of the tile
-    struct Src { const float *a, *b; int lda, ldb; };             // operand panels of one tile (k-row 0)
+    struct Src { const float *a, *b; int lda, ldb; unsigned oa, ob; };       // operand panels of one tile (k-row 0); the lane's byte offsets (lane_off)
 
     // entry i of the concatenated tile list (every problem padded to a multiple of 8 entries): false for a padding entry.
     // t.p only grows along a workgroup's walk.
@@ -88,10 +88,10 @@ struct WgradDma {
         while (i < total && !decode(a, i, t)) i += stride;
         return i;
     }
-    static __device__ __forceinline__ Src src_of(const MultiArgs &a, const Pos &t)
+    static __device__ __forceinline__ Src src_of(const MultiArgs &a, const Pos &t, int wave, int lane)
     {
         const GemmArgs &g = a.g[t.p];
-        return Src{g.A + t.m0, g.B + t.n0, g.lda, g.ldb};
+        return Src{g.A + t.m0, g.B + t.n0, g.lda, g.ldb, lane_off(g.lda, wave, lane), lane_off(g.ldb, wave, lane)};
     }
 
     // The W / delta tile of one wave's 32x32 block (the lane -> element map of epilogue_fetch, bp_kernels.h).  The loads are
@@ -129,16 +129,21 @@ struct WgradDma {
         for (int r = 0; r < 16; ++r) { pre.p0[r] = x.w[r]; pre.p1[r] = x.d[r]; }
     }
 
-    // One k-tile: uniform row base (SGPRs) + the lane's byte offset inside a k-tile of its panel (lane_off; NA = NB = 1: wave w
-    // moves k-rows 4w .. 4w+3 of either operand) -- one address register per operand instead of a 64-bit address per load.
+    // One k-tile: uniform row base (SGPRs) + the lane's byte offset inside a k-tile of its panel (lane_off, formed once per tile in
+    // src_of; NA = NB = 1: wave w moves k-rows 4w .. 4w+3 of either operand) -- one 32-bit address register per operand, and the
+    // DMA is global_load_lds_dwordx4 v_off, s[base:base+1].  The offsets are made opaque in place in front of every DMA: their zero
+    // extension then stays in the block of the DMA, where instruction selection folds it into the address.  (Left alone it is
+    // hoisted in front of the tile, comes back as a 64-bit VGPR pair, and every DMA but the first of a tile pays a 64-bit VALU
+    // add between the MFMAs.)  The empty asm issues nothing: the queue accounting below is what it was.
     static_assert(NA == 1 && NB == 1, "one LDS-DMA per wave, operand and k-tile");
     static __device__ __forceinline__ unsigned lane_off(int ld, int wave, int lane) { return 4u * ((unsigned)(wave * 4 + (lane >> 4)) * (unsigned)ld + (unsigned)(lane & 15) * 4u); }
-    static __device__ __forceinline__ void issue_tile(const Src &s, int k0, float *smem, int st, int wave, int lane)
+    static __device__ __forceinline__ void issue_tile(Src &s, int k0, float *smem, int st, int wave, int lane)
     {
         const char *pa = reinterpret_cast<const char *>(sgpr_row_base(s.a + (size_t)k0 * s.lda));
         const char *pb = reinterpret_cast<const char *>(sgpr_row_base(s.b + (size_t)k0 * s.ldb));
-        __builtin_amdgcn_global_load_lds((glb_ptr)(pa + lane_off(s.lda, wave, lane)), (lds_ptr)(smem + st * STAGE + wave * 256), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((glb_ptr)(pb + lane_off(s.ldb, wave, lane)), (lds_ptr)(smem + st * STAGE + A_STAGE + wave * 256), 16, 0, 0);
+        asm volatile("" : "+v"(s.oa), "+v"(s.ob));
+        __builtin_amdgcn_global_load_lds((glb_ptr)(pa + s.oa), (lds_ptr)(smem + st * STAGE + wave * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_ptr)(pb + s.ob), (lds_ptr)(smem + st * STAGE + A_STAGE + wave * 256), 16, 0, 0);
     }
     static __device__ __forceinline__ void multiply(const float *smem, int st, int a_off, int b_off, int kh, f32x16 (&acc)[2])
     {
@@ -159,7 +164,7 @@ struct WgradDma {
     // k-tile T of the tile `cur`.  carried: this is not the workgroup's first tile, so the epilogue stores of the tile before lie in
     // the queue between k-tiles D-1 and D.
     template <int T>
-    static __device__ __forceinline__ void iter(const Src &cur, const Src &nxt, const EpiArgs &e, bool carried, float *smem, int wave, int lane, int tid,
+    static __device__ __forceinline__ void iter(Src &cur, Src &nxt, const EpiArgs &e, bool carried, float *smem, int wave, int lane, int tid,
                                                 int a_off, int b_off, int kh, int mb, int nb, bool do_bias, float &bsum, f32x16 (&acc)[2], WD &wd)
     {
         if constexpr (T < NT) {
@@ -191,7 +196,7 @@ struct WgradDma {
         Pos t; t.p = 0;
         int i = seek(a, blockIdx.x, stride, total, t);
         if (i >= total) return;
-        Src cur = src_of(a, t);
+        Src cur = src_of(a, t, wave, lane);
 #pragma unroll
         for (int k = 0; k < D; ++k) issue_tile(cur, k * BK, smem, k, wave, lane);
         bool carried = false;
@@ -201,7 +206,7 @@ struct WgradDma {
             Pos tn = t;
             const int in = seek(a, i + stride, stride, total, tn);
             const bool more = in < total;
-            const Src nxt = more ? src_of(a, tn) : cur;
+            Src nxt = more ? src_of(a, tn, wave, lane) : cur;
             const EpiArgs &e = a.e[t.p];
             const int mb = t.m0 + wm * 32, nb = t.n0 + wn * 32;
             const int a_off = wm * 32 + (lane & 31), b_off = wn * 32 + (lane & 31), kh = lane >> 5;
