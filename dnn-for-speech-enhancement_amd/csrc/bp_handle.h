@@ -16,7 +16,7 @@
 //   the block owner of the two streaming engines)
 //   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
 //   (bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
-//   and fail / HIPCHK)
+//   and fail / HIPCHK; bp_chunk.h: the resident chunk -- bp_handle::res --, how one becomes resident and what its readers check)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad
 // columns/rows are zero and stay zero under the step (DESIGN.md "padding invariants"), so the GEMM tiles never need
@@ -24,7 +24,7 @@
 //   W_l   [ld_{l-1}][ld_l]   (reference layout weights[l][p*cur+c], BP_GPU.cu:139)
 //   y_l   [B][ld_l]          post-activation, post-dropout output of layer l (layer_y)
 //   dx_l  [B][ld_l]          dE/dx of layer l (layer_dedx); layer_x/dydx/dedy are never stored
-//   in    [cap][ld_0], targ [cap][ld_{L-1}]   resident chunk (dev.in/dev.targ, BP_GPU.cu:127-130)
+//   in    [cap][ld_0], targ [cap][ld_{L-1}]   resident stacked chunk (res.in() / res.targ(), bp_chunk.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +34,7 @@
 
 #include "../../include/bp_c_api.h"
 #include "bp_mem.h"
+#include "bp_chunk.h"
 
 typedef uint16_t bf16_t;
 
@@ -59,7 +60,7 @@ struct bp_handle {
     int L;                       // number of layer sizes
     int s[BP_MAXLAYER], ld[BP_MAXLAYER];
     int B, Bg;                   // local / global bunch
-    int cap, chunk_frames;
+    int cap;                     // rows a chunk may have (max_chunk_frames)
     // (the holders of a handle go with `delete h`, in reverse order of declaration: the two streams it owns are declared first
     // and so go last, after everything that was used on them)
     Stream own_stream, copy_stream;   // copy_stream: see "Upload path" below
@@ -75,7 +76,7 @@ struct bp_handle {
     const uint8_t *inj_mask[BP_MAXLAYER];   // bp_train_resident_masked in progress: device masks of this bunch per layer output
     const float *inj_x0;                    // ... and the masked copy of its input rows
     float *y[BP_MAXLAYER], *dx[BP_MAXLAYER];
-    float *in, *targ, *out_dev;
+    float *out_dev;
     float *slabs; size_t slab_stride; int out_splits;   // split-K workspace of the output layer
     unsigned *out_ticket;                               // ... and its ticket words (one per 32 x 32 output tile)
     float *grad; size_t grad_floats; size_t g_off[BP_MAXLAYER], g_cnt[BP_MAXLAYER];
@@ -90,29 +91,9 @@ struct bp_handle {
     int out_act, out_lin, out_loss;   // output layer (bp_set_output): 0 linear | 1 logistic on columns [out_lin, s_L), loss of those columns
     Event ev0, ev1; float last_ms; int last_bunches;
     std::vector<Buf> allocs;     // everything dev_alloc handed out: lives as long as the handle
-    // Upload path: host->device copies run on copy_stream so that chunk i+1 is uploaded while chunk i trains.
-    // STACKED chunks (bp_upload_chunk: the caller hands [frames][layersizes[0]] rows, the reference's interface) alternate
-    // between two device buffer pairs (in/targ and in_alt/targ_alt; allocated on first use).
-    // WINDOW chunks (bp_upload_chunk_windows: raw frames + index tables) stay as they are uploaded -- two
-    // grow-only staging sets alternate the same way -- and every bunch stacks ITS rows into the tile x0s/tgs right
-    // before its forward (bp_stage_bunch): no stacked chunk, no masked copy of it.
-    struct WinSet { Buf r[4]; } wset[2];      // raw frames, raw target frames, NAT rows, tables (win_start | targ_frame | nat_row)
-    int wcur;                                 // staging set of the resident window chunk
-    bool windows;                             // the resident chunk is a window chunk
-    bool chunk_has_targ;                      // the call that made the chunk resident supplied targets (stacked: targ / targ_alt were
-                                              // written; window: wv.tg != null); training and gradient calls need them
-    struct { const float *fea, *tg, *nat; const int *ws, *tf, *nr; int D, win; } wv;   // views of set wcur
-    float *x0s, *tgs;                         // [Bp][ld_0], [Bp][ld_L]: the staged bunch (= tile stage_cur of the pair below)
-    float *x0s2[2], *tgs2[2]; int stage_cur;  // two staged tiles: while bunch i trains out of one, the output layer's reduce launch
-                                              // of bunch i stacks bunch i+1 into the other (bp_out_split_stage)
-    int next_first;                           // chunk frame of the bunch that follows the one being enqueued (-1: none / not a window chunk)
-    struct { bool valid; int first, tile; uint32_t step; unsigned gen; } pre;   // what the other tile holds
-    unsigned wgen;                            // bumped by every window upload (a pre-staged tile of the old chunk is void)
-    Event ev_copy;                 // copy_stream: this chunk's H2D copies are done
-    Event ev_retired;              // main stream: the stacked buffer pair that is NOT current is no longer read
-    Event ev_wretired;             // main stream: the window staging set that is NOT current is no longer read
-    bool retired_valid, wretired_valid;
-    float *in_alt, *targ_alt;
+    // Upload path: host->device copies run on copy_stream so that chunk i+1 is uploaded while chunk i trains.  What is resident,
+    // the two copies of each kind of chunk, the staged tiles and the events of the upload: bp_chunk.h
+    Resident res;
     // compute_dtype == 1 (bp_bf16.h): bf16 copies, each in both orientations
     bool bf;
     int Bp;                                                  // bunch rows rounded up to 64
@@ -218,6 +199,8 @@ int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat
 int out_chunk_reserve(bp_handle *h, int n_frames);
 int forward_resident(bp_handle *h, int n);                 // ... with the kernels of the handle's mode (bp_set_forward)
 int forward_resident_as(bp_handle *h, int n, int mode);    // ... with those of `mode` (CV: always BP_FORWARD_DEFAULT; a stream: its own)
+int outputs_to_host(bp_handle *h, int n);                  // rows [0, n) of out_chunk into host_out on h->stream, no synchronisation
+int train_whole_chunk(bp_handle *h, int n);                // every whole bunch of the n resident rows; the remainder gets the reference's line
 
 // ------------------------------------------------------------------ mixtures (bp_mix.hip)
 void mix_free(bp_handle *h);                      // the corpus and the mixing buffers (bp_destroy)

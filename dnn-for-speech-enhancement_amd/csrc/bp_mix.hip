@@ -640,20 +640,18 @@ extern "C" int bp_train_mix(bp_handle *h, int n_mix, const bp_mixture *m, const 
     if ((r = wave_nat_mode("bp_train_mix", h, h->mix->nat, &dyn)) != BP_OK) return r;
     if ((r = generate(h, c, m, order, false, nullptr, nullptr, nullptr)) != BP_OK) return r;
     if ((r = window_adopt(h, (int)c.frames, h->mix->D, h->mix->ctx, h->mix->nat, true)) != BP_OK) return r;
-    if (c.frames % h->B)
-        printf("this bunch has only %d samples and is ignored.\n", (int)(c.frames % h->B));   // BP_GPU.cu:317
-    return bp_train_resident(h, 0, (int)c.frames);
+    return train_whole_chunk(h, (int)c.frames);
 }
 
-extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq_err_sum)
+extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sum)
 {
     Call c;
     int r;
     if ((r = plan_call(h, "bp_cv_mix", n_mix, m, c)) != BP_OK) return r;
-    if (!sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_mix: null argument");
+    if (!sum) return fail(BP_ERR_ARG, "bp_cv_mix: null argument");
     bool dyn;
     if ((r = wave_nat_mode("bp_cv_mix", h, h->mix->nat, &dyn)) != BP_OK) return r;
-    const int n = (int)c.frames, L = h->L, sL = h->s[L - 1], ldL = h->ld[L - 1];
+    const int n = (int)c.frames, L = h->L, sL = h->s[L - 1];
     if ((r = out_chunk_reserve(h, n)) != BP_OK) return r;
     float *targ_d;
     if ((r = generate(h, c, m, nullptr, false, nullptr, &targ_d, nullptr)) != BP_OK) return r;
@@ -661,19 +659,10 @@ extern "C" int bp_cv_mix(bp_handle *h, int n_mix, const bp_mixture *m, float *sq
     if ((r = window_adopt(h, n, h->mix->D, h->mix->ctx, h->mix->nat, false)) != BP_OK) return r;
     if ((r = forward_resident_as(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV: the step's kernels in either mode)
     std::vector<float> tg((size_t)n * sL);
-    HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * ldL * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if ((r = outputs_to_host(h, n)) != BP_OK) return r;
     HIPCHK(hipMemcpyAsync(tg.data(), targ_d, tg.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const float *host_out = h->host_out.as<float>();
-    float squared_err = 0.0f;
-    for (int j = 0; j < n; ++j) {                                // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
-        const float *t = tg.data() + (size_t)j * sL;
-        for (int d = 0; d < sL; ++d) {
-            const float e = host_out[(size_t)j * ldL + d] - t[d];
-            squared_err = squared_err + e * e;
-        }
-    }
-    *sq_err_sum = squared_err;
+    *sum = sq_err_sum(h->host_out.as<float>(), h->ld[L - 1], sL, n, [&](int j) { return tg.data() + (size_t)j * sL; });
     return BP_OK;
 }
 

@@ -17,13 +17,11 @@ extern "C" int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, flo
 {
     if (!h || !avg_ms) return fail(BP_ERR_ARG, "bp_profile_step: null argument");
     if (h->bf || h->dp || h->Bg != h->B) return fail(BP_ERR_STATE, "bp_profile_step: fp32 single-device handles only");
-    if (n_bunches < 1 || first_frame < 0 || (long)first_frame + (long)n_bunches * h->B > h->chunk_frames)
-        return fail(BP_ERR_ARG, "bp_profile_step: frame range outside the resident chunk");
-    if (!h->chunk_has_targ)
-        return fail(BP_ERR_STATE, "bp_profile_step: the resident chunk was uploaded without targets (forward / CV upload)");
+    int rc = resident_range(h->res, "bp_profile_step", first_frame, n_bunches < 1 ? -1L : (long)n_bunches * h->B);
+    if (rc == BP_OK) rc = resident_targets(h->res, "bp_profile_step");
+    if (rc != BP_OK) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     StepProf prof; prof.used = 0;
-    int rc = BP_OK;
     h->prof = &prof;
     hipError_t er = prof_mark(h, -1);                        // origin
     if (er == hipSuccess) er = train_bunches(h, first_frame, n_bunches);
@@ -122,7 +120,7 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
     if (h->L < 4 && (which == 0 || which == 1 || which == 2))
         return fail(BP_ERR_ARG, "bp_time_kernel: needs a hidden->hidden layer (numlayers >= 4)");
     if (h->bf) return fail(BP_ERR_STATE, "bp_time_kernel: fp32 kernels only");
-    if (h->chunk_frames < h->B || h->windows) return fail(BP_ERR_STATE, "bp_time_kernel: no resident stacked chunk");
+    if (h->res.frames < h->B || h->res.windows) return fail(BP_ERR_STATE, "bp_time_kernel: no resident stacked chunk");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L, B = h->B;
     Event a, b;
@@ -149,12 +147,12 @@ extern "C" int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms)
             }
             float *W0 = h->W[l], *D0 = h->dW[l], *b0 = h->b[l], *db0 = h->db[l];
             h->W[l] = scratch_w; h->dW[l] = scratch_d; h->b[l] = scratch_b; h->db[l] = scratch_b + h->ld[l];
-            er = launch_wgrad(h, l, B, l == 1 ? h->in : h->y[l - 1], true);
+            er = launch_wgrad(h, l, B, l == 1 ? h->res.in() : h->y[l - 1], true);
             h->W[l] = W0; h->dW[l] = D0; h->b[l] = b0; h->db[l] = db0;
             break;
         }
-        case 3: er = launch_fwd(h, 1, B, h->in, nullptr, nullptr, true, 1.0f); break;
-        case 4: er = launch_fwd(h, L - 1, B, h->y[L - 2], h->targ, nullptr, true, 1.0f); break;
+        case 3: er = launch_fwd(h, 1, B, h->res.in(), nullptr, nullptr, true, 1.0f); break;
+        case 4: er = launch_fwd(h, L - 1, B, h->y[L - 2], h->res.targ(), nullptr, true, 1.0f); break;
         default: return fail(BP_ERR_ARG, "bp_time_kernel: unknown kernel id");
         }
         HIPCHK(er);

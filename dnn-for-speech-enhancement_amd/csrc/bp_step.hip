@@ -78,7 +78,7 @@ extern "C" int bp_destroy(bp_handle *h)
 }
 
 static int check_hyper(float, float, float, int, float, float, const char *);
-static int ensure_stacked(bp_handle *h);
+static int ensure_pair(bp_handle *h, int k);
 static int ensure_stage_tiles(bp_handle *h);
 static hipError_t stage_bunch(bp_handle *h, int first, int rows, bool train);
 static StageArgs stage_args(bp_handle *h, int first, int rows, bool train, int tile, uint32_t step);
@@ -122,7 +122,7 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
     h->th_vis = cfg->dropoutflag == 1 ? drop_threshold(cfg->visible_omit) : 0u;
     h->th_hid = cfg->dropoutflag == 1 ? drop_threshold(cfg->hid_omit) : 0u;
     for (int l = 0; l < h->L; ++l) { h->s[l] = cfg->layersizes[l]; h->ld[l] = pad64(h->s[l]); }
-    h->out_splits = 1; h->next_first = -1; h->fwd_mode = BP_FORWARD_DEFAULT;   // (everything else: zero, from new bp_handle())
+    h->out_splits = 1; h->res.next_first = -1; h->fwd_mode = BP_FORWARD_DEFAULT;   // (everything else: zero, from new bp_handle())
 
 #define CK(x) do { int _r = (x); if (_r != BP_OK) { std::string m = g_bp_err; bp_destroy(h); g_bp_err = m; return _r; } } while (0)
 #define HK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { std::string m = std::string(#x) + ": " + hipGetErrorString(_e); bp_destroy(h); return fail(BP_ERR_DEVICE, m); } } while (0)
@@ -141,12 +141,12 @@ extern "C" int bp_create(const bp_config *cfg, const float *const *weights, cons
     HK(h->ev0.create());
     HK(h->ev1.create());
     HK(h->copy_stream.create(hipStreamNonBlocking));
-    HK(h->ev_copy.create(hipEventDisableTiming));
-    HK(h->ev_retired.create(hipEventDisableTiming));
-    HK(h->ev_wretired.create(hipEventDisableTiming));
+    HK(h->res.ev_copy.create(hipEventDisableTiming));
+    HK(h->res.retired.ev.create(hipEventDisableTiming));
+    HK(h->res.wretired.ev.create(hipEventDisableTiming));
     const int L = h->L;
     const size_t Bp = (size_t)((h->B + 63) & ~63);             // bunch rows rounded up to a whole tile
-    // (the stacked chunk buffers in / targ are allocated by the first stacked upload, ensure_stacked():
+    // (the stacked chunk buffers are allocated by the first stacked uploads, ensure_pair():
     // a caller that only ever hands window chunks never pays for them)
     CK(dev_alloc(h, &h->out_dev, Bp * h->ld[L - 1]));
     // narrow output layer (e.g. 2048 -> 257): too few 32x32 tiles to fill 256 CUs, so its k range is
@@ -233,13 +233,13 @@ extern "C" int bp_set_hyper(bp_handle *h, float lrate, float momentum, float wei
     if (dropoutflag != h->cfg.dropoutflag || visible_omit != h->cfg.visible_omit || hid_omit != h->cfg.hid_omit) {
         HIPCHK(hipSetDevice(h->cfg.device));
         const uint32_t th_vis = dropoutflag == 1 ? drop_threshold(visible_omit) : 0u;
-        if (th_vis && h->in) {                                  // stacked chunk resident: its bunches are masked into the staged tile from now on
+        if (th_vis && h->res.in()) {                                  // stacked chunk resident: its bunches are masked into the staged tile from now on
             r = ensure_stage_tiles(h);
             if (r != BP_OK) return r;
         }
         h->cfg.dropoutflag = dropoutflag; h->cfg.visible_omit = visible_omit; h->cfg.hid_omit = hid_omit;
         h->th_vis = th_vis;
-        h->pre.valid = false;                                   // (a pre-staged bunch was masked with the old rate)
+        h->res.pre.valid = false;                                   // (a pre-staged bunch was masked with the old rate)
         h->th_hid = dropoutflag == 1 ? drop_threshold(hid_omit) : 0u;
     }
     return BP_OK;
@@ -359,13 +359,13 @@ hipError_t launch_fwd(bp_handle *h, int l, int M, const float *y_prev, const flo
         StageArgs sa; memset(&sa, 0, sizeof(sa));
         int n_stage = 0;
         if (!covers_tiles(n_gemm, g, OUT_SPLITS)) return hipErrorInvalidConfiguration;   // (workgroup b: slice b / tiles of tile b % tiles)
-        if (train && h->next_first >= 0) {
+        if (train && h->res.next_first >= 0) {
             // another staged bunch behind this one (window chunk, or stacked chunk with visible dropout): stack / copy (and mask, with the NEXT step's Philox position) that bunch
             // into the other tile from the spare workgroups of this launch
-            const int tile = 1 - h->stage_cur;
-            sa = stage_args(h, h->next_first, h->B, true, tile, h->step + 1);
+            const int tile = 1 - h->res.stage_cur;
+            sa = stage_args(h, h->res.next_first, h->B, true, tile, h->step + 1);
             n_stage = stage_blocks(h, sa);
-            h->pre.valid = true; h->pre.first = h->next_first; h->pre.tile = tile; h->pre.step = h->step + 1; h->pre.gen = h->wgen;
+            h->res.pre.valid = true; h->res.pre.first = h->res.next_first; h->res.pre.tile = tile; h->res.pre.step = h->step + 1; h->res.pre.gen = h->res.gen;
         }
         if (logi) hipLaunchKernelGGL(bp_out_split_stage<KOutLogi>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, h->stream, g, e, n_gemm, sa);
         else hipLaunchKernelGGL(bp_out_split_stage<KOut>, dim3((unsigned)(n_gemm + n_stage)), dim3(256), 0, h->stream, g, e, n_gemm, sa);
@@ -524,7 +524,7 @@ hipError_t launch_wgrad(bp_handle *h, int l, int M, const float *y_prev, bool fu
 // N3) and, with visible-layer dropout on, every bunch of a STACKED chunk -- the mask of BP_GPU.cu:536-539 is applied while the
 // bunch's rows are copied into the L2-sized tile that the layer-1 forward and the layer-1 weight gradient both read.  The chunk
 // itself is never modified and no masked copy of it exists.
-bool step_stages(const bp_handle *h) { return h->windows || (h->th_vis != 0u && !h->inj_x0); }
+bool step_stages(const bp_handle *h) { return h->res.windows || (h->th_vis != 0u && !h->inj_x0); }
 
 // ------------------------------------------------------------------ compute_dtype == 1 (bp_bf16.h)
 static int bf_alloc(bp_handle *h, bf16_t **p, size_t n_halfs)
@@ -703,21 +703,13 @@ static hipError_t bf_wgrads(bp_handle *h, const int *ls, int n, bool fused)
 // tile now, stacked chunks are read in place or from their masked copy.
 hipError_t step_inputs(bp_handle *h, int first, const float **x0, const float **tg)
 {
-    const int L = h->L, B = h->B;
-    if (h->windows) {
-        const hipError_t er = stage_bunch(h, first, B, true);
-        *x0 = h->x0s; *tg = h->tgs;
-        return er;
-    }
-    *x0 = h->in + (size_t)first * h->ld[0];
-    *tg = h->targ + (size_t)first * h->ld[L - 1];
-    if (h->inj_x0) *x0 = h->inj_x0;                     // bp_train_resident_masked: input rows with the injected visible mask
-    else if (step_stages(h)) {                          // visible-layer dropout: the bunch's rows, masked, in the staged tile
-        const hipError_t er = stage_bunch(h, first, B, true);
-        *x0 = h->x0s;
-        return er;
-    }
-    return hipSuccess;
+    const Resident &c = h->res;
+    const bool staged = step_stages(h);                 // a window chunk's rows, or a stacked chunk's under the visible-layer dropout mask
+    const hipError_t er = staged ? stage_bunch(h, first, h->B, true) : hipSuccess;
+    // (inj_x0: bp_train_resident_masked, input rows with the injected visible mask)
+    *x0 = staged ? c.x0s() : h->inj_x0 ? h->inj_x0 : c.in() + (size_t)first * h->ld[0];
+    *tg = c.windows ? c.tgs() : c.targ() + (size_t)first * h->ld[h->L - 1];
+    return er;
 }
 // forward of weight layer l on M frames; x0: the input rows (read at l == 1; bf16: converted there)
 hipError_t step_forward(bp_handle *h, int l, int M, const float *x0, const float *tg, float *out, bool train, float alpha)
@@ -778,11 +770,11 @@ hipError_t train_bunches(bp_handle *h, int first, int nb)
 {
     hipError_t er = hipSuccess;
     for (int i = 0; i < nb && er == hipSuccess; ++i) {
-        h->next_first = (step_stages(h) && !h->bf && i + 1 < nb) ? first + (i + 1) * h->B : -1;
+        h->res.next_first = (step_stages(h) && !h->bf && i + 1 < nb) ? first + (i + 1) * h->B : -1;
         er = h->dp ? dp_bunch(h, first + i * h->B) : bunch(h, first + i * h->B, true);
         if (er == hipSuccess) h->step++;
     }
-    h->next_first = -1; h->pre.valid = false;
+    h->res.next_first = -1; h->res.pre.valid = false;
     return er;
 }
 
@@ -793,36 +785,18 @@ extern "C" int bp_upload_chunk(bp_handle *h, int n_frames, const float *in, cons
     if (n_frames < 0 || n_frames > h->cap) return fail(BP_ERR_ARG, "bp_upload_chunk: n_frames exceeds chunk capacity");
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L;
-    { const int r = ensure_stacked(h); if (r != BP_OK) return r; }
-    h->windows = false;
-    if (n_frames > 0) {
-        // into the buffer pair that is not current, on the copy stream: the bunches of the previous chunk (still
-        // running on the main stream out of the current pair) overlap this upload
-        if (!h->in_alt) {
-            const size_t capp = (size_t)h->cap + 64;
-            int r;
-            if ((r = dev_alloc(h, &h->in_alt, capp * h->ld[0])) != BP_OK || (r = dev_alloc(h, &h->targ_alt, capp * h->ld[L - 1])) != BP_OK)
-                return r;
-            HIPCHK(hipStreamSynchronize(h->stream));            // (dev_alloc zero-fills on the main stream)
-        }
-        if (h->retired_valid) HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_retired, 0));
-        HIPCHK(hipMemcpy2DAsync(h->in_alt, (size_t)h->ld[0] * 4, in, (size_t)h->s[0] * 4, (size_t)h->s[0] * 4, n_frames,
-                                hipMemcpyHostToDevice, h->copy_stream));
+    Resident &c = h->res;
+    int r = ensure_pair(h, c.cur);
+    if (r != BP_OK) return r;
+    if (n_frames > 0) {                                     // into the pair that is not current
+        if ((r = ensure_pair(h, 1 - c.cur)) != BP_OK || (r = refill_begin(c.retired, h->copy_stream)) != BP_OK) return r;
+        const Resident::Pair &p = c.pair[1 - c.cur];
+        HIPCHK(hipMemcpy2DAsync(p.in, (size_t)h->ld[0] * 4, in, (size_t)h->s[0] * 4, (size_t)h->s[0] * 4, n_frames, hipMemcpyHostToDevice, h->copy_stream));
         if (targ)
-            HIPCHK(hipMemcpy2DAsync(h->targ_alt, (size_t)h->ld[L - 1] * 4, targ, (size_t)h->s[L - 1] * 4,
-                                    (size_t)h->s[L - 1] * 4, n_frames, hipMemcpyHostToDevice, h->copy_stream));
-        HIPCHK(hipEventRecord(h->ev_copy, h->copy_stream));
-        // the caller may overwrite in/targ as soon as we return (BPtrain.cc:50-53)
-        HIPCHK(hipStreamSynchronize(h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-        HIPCHK(hipEventRecord(h->ev_retired, h->stream));       // everything queued so far read the old pair
-        h->retired_valid = true;
-        std::swap(h->in, h->in_alt);
-        std::swap(h->targ, h->targ_alt);
+            HIPCHK(hipMemcpy2DAsync(p.targ, (size_t)h->ld[L - 1] * 4, targ, (size_t)h->s[L - 1] * 4, (size_t)h->s[L - 1] * 4, n_frames, hipMemcpyHostToDevice, h->copy_stream));
+        if ((r = refill_end(c, c.retired, c.cur, h->copy_stream, h->stream)) != BP_OK) return r;
     }
-    h->chunk_frames = n_frames;
-    h->chunk_has_targ = targ != nullptr;                    // (bp_forward / bp_cv_chunk: the pair swapped, its targets are an older chunk's)
-    h->wgen++; h->pre.valid = false; h->next_first = -1;    // (a tile pre-staged from the old chunk is void)
+    make_resident(c, false, n_frames, targ != nullptr);     // (bp_forward / bp_cv_chunk: the pair flipped, its targets are an older chunk's)
     return BP_OK;
 }
 
@@ -831,19 +805,21 @@ extern "C" int bp_upload_chunk(bp_handle *h, int n_frames, const float *in, cons
 // copies on the copy stream and by bunches on the main stream.
 static int wset_reserve(bp_handle *h, int set, size_t rows_b, size_t targ_b, size_t nat_b, size_t tab_b)
 {
-    Buf *rw = h->wset[set].r;
+    Buf *rw = h->res.wset[set].r;
     return grow_all("hipMalloc (window staging): ", {h->copy_stream, h->stream},
                     {{rw[0], rows_b, false}, {rw[1], targ_b, false}, {rw[2], nat_b, false}, {rw[3], tab_b, false}});
 }
 
-// The stacked chunk buffers, on the first stacked upload (window chunks never need them).
-static int ensure_stacked(bp_handle *h)
+// Stacked buffer pair k on its first use (window chunks never need one), and what a stacked chunk needs beside it: the staged
+// tiles, when the visible dropout masks its bunches.
+static int ensure_pair(bp_handle *h, int k)
 {
+    Resident::Pair &p = h->res.pair[k];
     const size_t capp = (size_t)h->cap + 64;
     bool fresh = false;
     int r;
-    if (!h->in) { if ((r = dev_alloc(h, &h->in, capp * h->ld[0])) != BP_OK) return r; fresh = true; }
-    if (!h->targ) { if ((r = dev_alloc(h, &h->targ, capp * h->ld[h->L - 1])) != BP_OK) return r; fresh = true; }
+    if (!p.in) { if ((r = dev_alloc(h, &p.in, capp * h->ld[0])) != BP_OK) return r; fresh = true; }
+    if (!p.targ) { if ((r = dev_alloc(h, &p.targ, capp * h->ld[h->L - 1])) != BP_OK) return r; fresh = true; }
     if (fresh) HIPCHK(hipStreamSynchronize(h->stream));         // (dev_alloc zero-fills on the main stream)
     return h->th_vis ? ensure_stage_tiles(h) : BP_OK;
 }
@@ -851,12 +827,11 @@ static int ensure_stacked(bp_handle *h)
 // The two staged bunch tiles [Bp][ld_0] (+ target tiles for window chunks), on first need.
 static int ensure_stage_tiles(bp_handle *h)
 {
-    if (h->x0s) return BP_OK;
+    if (h->res.tgs2[1]) return BP_OK;                           // (the last of the four)
     int r;
     for (int k = 0; k < 2; ++k)
-        if ((r = dev_alloc(h, &h->x0s2[k], (size_t)h->Bp * h->ld[0])) != BP_OK || (r = dev_alloc(h, &h->tgs2[k], (size_t)h->Bp * h->ld[h->L - 1])) != BP_OK)
+        if ((r = dev_alloc(h, &h->res.x0s2[k], (size_t)h->Bp * h->ld[0])) != BP_OK || (r = dev_alloc(h, &h->res.tgs2[k], (size_t)h->Bp * h->ld[h->L - 1])) != BP_OK)
             return r;
-    h->stage_cur = 0; h->x0s = h->x0s2[0]; h->tgs = h->tgs2[0];
     HIPCHK(hipStreamSynchronize(h->stream));                    // (dev_alloc zero-fills on the main stream)
     return BP_OK;
 }
@@ -867,21 +842,21 @@ static StageArgs stage_args(bp_handle *h, int first, int rows, bool train, int t
 {
     const int L = h->L, ld0 = h->ld[0], ldL = h->ld[L - 1];
     StageArgs a; memset(&a, 0, sizeof(a));
-    a.x = h->x0s2[tile]; a.ld = ld0; a.width = h->s[0];
+    a.x = h->res.x0s2[tile]; a.ld = ld0; a.width = h->s[0];
     a.rows = rows; a.thresh = train ? h->th_vis : 0u; a.frame_off = h->cfg.rank_frame_offset;
     a.seed_lo = (uint32_t)h->cfg.seed; a.seed_hi = (uint32_t)(h->cfg.seed >> 32); a.step = step;
     a.nbx = (rows + 3) / 4;
-    if (!h->windows) {
+    if (!h->res.windows) {
         // stacked chunk: rows [first, first+rows) as they lie (no tables: win_start == null selects the row-copy form, one thread =
         // 4 rows x 4 columns), targets are read in place
-        a.fea = h->in + (size_t)first * ld0; a.fea_dim = ld0; a.win = h->s[0];
+        a.fea = h->res.in() + (size_t)first * ld0; a.fea_dim = ld0; a.win = h->s[0];
         a.yb_in = (ld0 / 4 + 255) / 256;
         return a;
     }
-    a.fea = h->wv.fea; a.fea_dim = h->wv.D; a.win = h->wv.win; a.nat = h->wv.nat;
-    a.win_start = h->wv.ws + first; a.nat_row = h->wv.nr ? h->wv.nr + first : (const int *)nullptr;
-    a.t = h->wv.tg ? h->tgs2[tile] : (float *)nullptr; a.ldt = ldL; a.twidth = h->s[L - 1];
-    a.targ_frames = h->wv.tg; a.targ_frame = h->wv.tf ? h->wv.tf + first : (const int *)nullptr;
+    a.fea = h->res.wv.fea; a.fea_dim = h->res.wv.D; a.win = h->res.wv.win; a.nat = h->res.wv.nat;
+    a.win_start = h->res.wv.ws + first; a.nat_row = h->res.wv.nr ? h->res.wv.nr + first : (const int *)nullptr;
+    a.t = h->res.wv.tg ? h->res.tgs2[tile] : (float *)nullptr; a.ldt = ldL; a.twidth = h->s[L - 1];
+    a.targ_frames = h->res.wv.tg; a.targ_frame = h->res.wv.tf ? h->res.wv.tf + first : (const int *)nullptr;
     a.yb_in = (ld0 + 255) / 256;
     return a;
 }
@@ -891,31 +866,23 @@ static hipError_t stage_bunch(bp_handle *h, int first, int rows, bool train)
 {
     // the bunch may already sit in the other tile: stacked by the previous bunch's output-layer reduce launch (same chunk, same
     // dropout stream position)
-    if (train && h->pre.valid && h->pre.first == first && h->pre.step == h->step && h->pre.gen == h->wgen && rows == h->B) {
-        h->stage_cur = h->pre.tile; h->pre.valid = false;
-        h->x0s = h->x0s2[h->stage_cur]; h->tgs = h->tgs2[h->stage_cur];
-        return hipSuccess;
-    }
-    h->pre.valid = false;
-    h->x0s = h->x0s2[h->stage_cur]; h->tgs = h->tgs2[h->stage_cur];
-    const StageArgs a = stage_args(h, first, rows, train, h->stage_cur, h->step);
+    Resident &c = h->res;
+    const bool there = train && c.pre.valid && c.pre.first == first && c.pre.step == h->step && c.pre.gen == c.gen && rows == h->B;
+    c.pre.valid = false;
+    if (there) { c.stage_cur = c.pre.tile; return hipSuccess; }
+    const StageArgs a = stage_args(h, first, rows, train, h->res.stage_cur, h->step);
     hipLaunchKernelGGL(bp_stage_bunch, dim3((unsigned)stage_blocks(h, a)), dim3(256), 0, h->stream, a);
     return hipGetLastError();
 }
 
-// Staging set `set` with n samples (tables laid out win_start | targ_frame | nat_row) becomes the current one; everything queued
-// on h->stream so far read the other set.
-static int adopt_set(bp_handle *h, int set, int n, int D, int ctx, bool with_targ, bool nat)
+// The views of the current staging set, which holds n samples (tables laid out win_start | targ_frame | nat_row).
+static void view_set(Resident &c, int n, int D, int ctx, bool with_targ, bool nat)
 {
-    HIPCHK(hipEventRecord(h->ev_wretired, h->stream));
-    h->wretired_valid = true;
-    h->wcur = set;
-    const Buf *rw = h->wset[set].r;
+    const Buf *rw = c.wset[c.wcur].r;
     int *d_ws = (int *)rw[3].p;
-    h->wv.fea = (float *)rw[0].p; h->wv.tg = with_targ ? (float *)rw[1].p : nullptr; h->wv.nat = nat ? (float *)rw[2].p : nullptr;
-    h->wv.ws = d_ws; h->wv.tf = with_targ ? d_ws + n : nullptr; h->wv.nr = nat ? d_ws + 2 * (size_t)n : nullptr;
-    h->wv.D = D; h->wv.win = ctx * D;
-    return BP_OK;
+    c.wv.fea = (float *)rw[0].p; c.wv.tg = with_targ ? (float *)rw[1].p : nullptr; c.wv.nat = nat ? (float *)rw[2].p : nullptr;
+    c.wv.ws = d_ws; c.wv.tf = with_targ ? d_ws + n : nullptr; c.wv.nr = nat ? d_ws + 2 * (size_t)n : nullptr;
+    c.wv.D = D; c.wv.win = ctx * D;
 }
 
 static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ, const char *who)
@@ -944,15 +911,14 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
     if (n > 0) {
         const size_t fea_b = (size_t)c->n_frames * D * 4, tg_b = with_targ ? (size_t)c->n_frames * sL * 4 : 0;
         const size_t nat_b = nat ? (size_t)c->n_nat * D * 4 : 0, idx_b = (size_t)n * 4;
-        // into the staging set that is not current, on the copy stream: the bunches of the previous chunk (still reading
-        // the current set on the main stream) overlap this upload
-        const int set = 1 - h->wcur;                            // (always alternate: ev_wretired covers exactly the other set)
-        { const int r = wset_reserve(h, set, fea_b, tg_b, nat_b, 3 * idx_b); if (r != BP_OK) return r; }
-        const Buf *rw = h->wset[set].r;
+        const int set = 1 - h->res.wcur;                        // (always alternate: wretired covers exactly the other set)
+        int r = wset_reserve(h, set, fea_b, tg_b, nat_b, 3 * idx_b);
+        if (r != BP_OK) return r;
+        const Buf *rw = h->res.wset[set].r;
         float *d_fea = (float *)rw[0].p, *d_tg = (float *)rw[1].p, *d_nat = (float *)rw[2].p;
         int *d_ws = (int *)rw[3].p, *d_tf = d_ws + n, *d_nr = d_tf + n;
         hipStream_t cs = h->copy_stream;
-        if (h->wretired_valid) HIPCHK(hipStreamWaitEvent(cs, h->ev_wretired, 0));
+        if ((r = refill_begin(h->res.wretired, cs)) != BP_OK) return r;
         HIPCHK(hipMemcpyAsync(d_fea, c->fea, fea_b, hipMemcpyHostToDevice, cs));
         HIPCHK(hipMemcpyAsync(d_ws, c->win_start, idx_b, hipMemcpyHostToDevice, cs));
         if (nat) {
@@ -963,16 +929,10 @@ static int upload_windows(bp_handle *h, const bp_window_chunk *c, bool with_targ
             HIPCHK(hipMemcpyAsync(d_tg, c->targ_frames, tg_b, hipMemcpyHostToDevice, cs));
             HIPCHK(hipMemcpyAsync(d_tf, c->targ_frame, idx_b, hipMemcpyHostToDevice, cs));
         }
-        HIPCHK(hipEventRecord(h->ev_copy, cs));
-        HIPCHK(hipStreamSynchronize(cs));                       // the caller may overwrite its buffers as soon as we return
-        HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy, 0));
-        const int r2 = adopt_set(h, set, n, D, ctx, with_targ, nat);
-        if (r2 != BP_OK) return r2;
+        if ((r = refill_end(h->res, h->res.wretired, h->res.wcur, cs, h->stream)) != BP_OK) return r;
+        view_set(h->res, n, D, ctx, with_targ, nat);
     }
-    h->windows = true;
-    h->wgen++; h->pre.valid = false; h->next_first = -1;
-    h->chunk_frames = n;
-    h->chunk_has_targ = with_targ;
+    make_resident(h->res, true, n, with_targ);
     return BP_OK;
 }
 
@@ -983,9 +943,9 @@ int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, siz
                    int **tables)
 {
     { const int r = ensure_stage_tiles(h); if (r != BP_OK) return r; }
-    const int set = 1 - h->wcur;
+    const int set = 1 - h->res.wcur;
     { const int r = wset_reserve(h, set, rows_b, targ_b, nat_b, 3 * n_samples * 4); if (r != BP_OK) return r; }
-    const Buf *rw = h->wset[set].r;
+    const Buf *rw = h->res.wset[set].r;
     *rows = (float *)rw[0].p; *nat = (float *)rw[2].p;
     if (targ) *targ = (float *)rw[1].p;
     *tables = (int *)rw[3].p;
@@ -993,56 +953,39 @@ int window_reserve(bp_handle *h, size_t rows_b, size_t targ_b, size_t nat_b, siz
 }
 int window_adopt(bp_handle *h, int n_samples, int fea_dim, int context, bool nat, bool with_targ)
 {
-    const int r = adopt_set(h, 1 - h->wcur, n_samples, fea_dim, context, with_targ, nat);
-    if (r != BP_OK) return r;
-    h->windows = true;
-    h->wgen++; h->pre.valid = false; h->next_first = -1;
-    h->chunk_frames = n_samples;
-    h->chunk_has_targ = with_targ;
-    return BP_OK;
+    const int r = retire_and_flip(h->res.wretired, h->res.wcur, h->stream);     // (no copy stream: everything queued so far read the other set)
+    if (r == BP_OK) { view_set(h->res, n_samples, fea_dim, context, with_targ, nat); make_resident(h->res, true, n_samples, with_targ); }
+    return r;
 }
 
-extern "C" int bp_upload_chunk_windows(bp_handle *h, const bp_window_chunk *c)
-{
-    return upload_windows(h, c, true, "bp_upload_chunk_windows");
-}
+extern "C" int bp_upload_chunk_windows(bp_handle *h, const bp_window_chunk *c) { return upload_windows(h, c, true, "bp_upload_chunk_windows"); }
 
 extern "C" int bp_fill_chunk_synthetic(bp_handle *h, int n_frames, uint64_t seed)
 {
     if (!h) return fail(BP_ERR_ARG, "null handle");
     if (n_frames < 0 || n_frames > h->cap) return fail(BP_ERR_ARG, "bp_fill_chunk_synthetic: n_frames exceeds capacity");
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int L = h->L;
-    { const int r = ensure_stacked(h); if (r != BP_OK) return r; }
-    h->windows = false;
-    if (n_frames > 0) {
-        size_t n4 = (size_t)n_frames * (h->ld[0] / 4);
-        hipLaunchKernelGGL(bp_fill_normal, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream, h->in, h->ld[0],
-                           h->s[0], n_frames, (uint32_t)seed, (uint32_t)(seed >> 32), 0u);
-        HIPCHK(hipGetLastError());
-        n4 = (size_t)n_frames * (h->ld[L - 1] / 4);
-        hipLaunchKernelGGL(bp_fill_normal, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream, h->targ,
-                           h->ld[L - 1], h->s[L - 1], n_frames, (uint32_t)seed, (uint32_t)(seed >> 32), 1u);
+    { const int r = ensure_pair(h, h->res.cur); if (r != BP_OK) return r; }
+    for (unsigned k = 0; k < 2 && n_frames > 0; ++k) {          // inputs, then targets: the current pair, on the main stream, no flip
+        const int l = k ? h->L - 1 : 0;
+        const size_t n4 = (size_t)n_frames * (h->ld[l] / 4);
+        hipLaunchKernelGGL(bp_fill_normal, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream, k ? h->res.targ() : h->res.in(), h->ld[l],
+                           h->s[l], n_frames, (uint32_t)seed, (uint32_t)(seed >> 32), k);
         HIPCHK(hipGetLastError());
     }
-    h->chunk_frames = n_frames;
-    h->chunk_has_targ = true;
-    h->wgen++; h->pre.valid = false; h->next_first = -1;
+    make_resident(h->res, false, n_frames, true);
     return BP_OK;
 }
 
 extern "C" int bp_train_resident(bp_handle *h, int first_frame, int n_frames)
 {
     if (!h) return fail(BP_ERR_ARG, "null handle");
-    if (first_frame < 0 || n_frames < 0 || first_frame + n_frames > h->chunk_frames)
-        return fail(BP_ERR_ARG, "bp_train_resident: frame range outside the resident chunk");
+    int r = resident_range(h->res, "bp_train_resident", first_frame, n_frames);
+    if (r != BP_OK) return r;
     if (h->Bg != h->B && !h->dp)
         return fail(BP_ERR_STATE, "bp_train_resident: data-parallel handle (global_bunchsize != bunchsize): attach it to its group first "
                                   "(bp_dp_attach: the exchange and the sharded update run inside the library)");
-    if (h->windows && n_frames >= h->B && !h->wv.tg)
-        return fail(BP_ERR_STATE, "bp_train_resident: the resident window chunk was uploaded without targets (forward / CV upload)");
-    if (!h->windows && n_frames >= h->B && !h->chunk_has_targ)
-        return fail(BP_ERR_STATE, "bp_train_resident: the resident stacked chunk was uploaded without targets (forward / CV upload)");
+    if (n_frames >= h->B && (r = resident_targets(h->res, "bp_train_resident")) != BP_OK) return r;
     HIPCHK(hipSetDevice(h->cfg.device));
     const int nb = n_frames / h->B;          // partial last bunch ignored (BP_GPU.cu:315-318)
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -1064,25 +1007,25 @@ extern "C" int bp_last_train_ms(bp_handle *h, float *ms, int *bunches)
     return BP_OK;
 }
 
+// Train every whole bunch of the n resident rows, with the reference's line about the rest (BP_GPU.cu:317).
+int train_whole_chunk(bp_handle *h, int n)
+{
+    if (n % h->B) printf("this bunch has only %d samples and is ignored.\n", n % h->B);
+    return bp_train_resident(h, 0, n);
+}
+
 extern "C" int bp_train_chunk(bp_handle *h, int n_frames, const float *in, const float *targ)
 {
     if (!h || !in || !targ) return fail(BP_ERR_ARG, "bp_train_chunk: null argument");
-    int r = bp_upload_chunk(h, n_frames, in, targ);
-    if (r != BP_OK) return r;
-    if (n_frames % h->B)
-        printf("this bunch has only %d samples and is ignored.\n", n_frames % h->B);   // BP_GPU.cu:317
-    return bp_train_resident(h, 0, n_frames);
+    const int r = bp_upload_chunk(h, n_frames, in, targ);
+    return r != BP_OK ? r : train_whole_chunk(h, n_frames);
 }
 
 extern "C" int bp_train_chunk_windows(bp_handle *h, const bp_window_chunk *c)
 {
-    int r = upload_windows(h, c, true, "bp_train_chunk_windows");
-    if (r != BP_OK) return r;
-    if (c->n_samples % h->B)
-        printf("this bunch has only %d samples and is ignored.\n", c->n_samples % h->B);   // BP_GPU.cu:317
-    return bp_train_resident(h, 0, c->n_samples);
+    const int r = upload_windows(h, c, true, "bp_train_chunk_windows");
+    return r != BP_OK ? r : train_whole_chunk(h, c->n_samples);
 }
-
 
 // Parity-test entry (no reference counterpart; the reference's masks come from cuRAND seeded by time(NULL),
 // BP_GPU.cu:77-78,534-551): the bunch loop of bp_train_resident with CALLER-SUPPLIED dropout masks instead of the
@@ -1093,15 +1036,13 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
 {
     if (!h || !masks) return fail(BP_ERR_ARG, "bp_train_resident_masked: null argument");
     if (h->bf || h->dp || h->Bg != h->B) return fail(BP_ERR_STATE, "bp_train_resident_masked: fp32 single-device handles only");
-    if (h->windows) return fail(BP_ERR_STATE, "bp_train_resident_masked: stacked chunks only (bp_upload_chunk)");
-    if (first_frame < 0 || n_frames < 0 || first_frame + n_frames > h->chunk_frames)
-        return fail(BP_ERR_ARG, "bp_train_resident_masked: frame range outside the resident chunk");
-    if (n_frames >= h->B && !h->chunk_has_targ)
-        return fail(BP_ERR_STATE, "bp_train_resident_masked: the resident stacked chunk was uploaded without targets (forward / CV upload)");
+    if (h->res.windows) return fail(BP_ERR_STATE, "bp_train_resident_masked: stacked chunks only (bp_upload_chunk)");
+    int rc = resident_range(h->res, "bp_train_resident_masked", first_frame, n_frames);
+    if (rc == BP_OK && n_frames >= h->B) rc = resident_targets(h->res, "bp_train_resident_masked");
+    if (rc != BP_OK) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const int L = h->L, B = h->B, nb = n_frames / B;
     Buf dm_b[BP_MAXLAYER], xm_b;                                 // (released on return, behind the final synchronisation)
-    int rc = BP_OK;
     hipError_t er = hipSuccess;
     for (int l = 0; l < L - 1 && er == hipSuccess; ++l) {
         if (!masks[l]) continue;
@@ -1117,7 +1058,7 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
     for (int i = 0; i < nb && er == hipSuccess; ++i) {
         const int first = first_frame + i * B;
         if (dm[0]) {
-            hipLaunchKernelGGL(bp_apply_mask, dim3((h->ld[0] + 255) / 256, B), dim3(256), 0, h->stream, h->in + (size_t)first * h->ld[0], xm,
+            hipLaunchKernelGGL(bp_apply_mask, dim3((h->ld[0] + 255) / 256, B), dim3(256), 0, h->stream, h->res.in() + (size_t)first * h->ld[0], xm,
                                h->ld[0], h->s[0], dm[0] + (size_t)i * B * h->s[0], B);
             if ((er = hipGetLastError()) != hipSuccess) break;
         }
@@ -1145,18 +1086,15 @@ extern "C" int bp_train_resident_masked(bp_handle *h, int first_frame, int n_fra
 extern "C" int bp_grads_resident(bp_handle *h, int first_frame)
 {
     if (!h) return fail(BP_ERR_ARG, "null handle");
-    if (first_frame < 0 || first_frame + h->B > h->chunk_frames)
-        return fail(BP_ERR_ARG, "bp_grads_resident: bunch outside the resident chunk");
+    int r = resident_range(h->res, "bp_grads_resident", first_frame, h->B, "bunch");
+    if (r != BP_OK) return r;
     if (h->dp) return fail(BP_ERR_STATE, "bp_grads_resident: not on an attached handle (the exchange owns the gradient buffer)");
     //  a window chunk uploaded for forward / CV carries no targets: bunch() would stage only the input rows and
     // back-propagate against whatever an earlier bunch left in the staged target tile
-    if (h->windows && !h->wv.tg)
-        return fail(BP_ERR_STATE, "bp_grads_resident: the resident window chunk was uploaded without targets (forward / CV upload)");
-    if (!h->windows && !h->chunk_has_targ)
-        return fail(BP_ERR_STATE, "bp_grads_resident: the resident stacked chunk was uploaded without targets (forward / CV upload)");
+    if ((r = resident_targets(h->res, "bp_grads_resident")) != BP_OK) return r;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (!h->grad) { int r = dev_alloc(h, &h->grad, h->grad_floats); if (r != BP_OK) return r; }
-    h->next_first = -1;
+    if (!h->grad && (r = dev_alloc(h, &h->grad, h->grad_floats)) != BP_OK) return r;
+    h->res.next_first = -1;
     HIPCHK(bunch(h, first_frame, false));
     return BP_OK;
 }
@@ -1243,8 +1181,8 @@ static int forward_bunch(bp_handle *h, int first, int fb, int mode)
     const int L = h->L;
     const float vis_keep = 1.0f - h->cfg.visible_omit, hid_keep = 1.0f - h->cfg.hid_omit;   // BP_GPU.cu:703-704
     float *out = h->out_chunk.as<float>() + (size_t)first * h->ld[L - 1];
-    const float *x0 = h->windows ? h->x0s : h->in + (size_t)first * h->ld[0];
-    if (h->windows) HIPCHK(stage_bunch(h, first, fb, false));
+    const float *x0 = h->res.windows ? h->res.x0s() : h->res.in() + (size_t)first * h->ld[0];
+    if (h->res.windows) HIPCHK(stage_bunch(h, first, fb, false));
     for (int l = 1; l < L; ++l) {
         float alpha = 1.0f;
         if (h->cfg.dropoutflag == 1) alpha = (l == 1) ? vis_keep : hid_keep;
@@ -1281,12 +1219,16 @@ int forward_resident_as(bp_handle *h, int n, int mode)
     return BP_OK;
 }
 
-// ... then one copy into host_out
+int outputs_to_host(bp_handle *h, int n)
+{
+    if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return BP_OK;
+}
+// ... then one copy into host_out, and the stream has finished
 static int forward_chunk(bp_handle *h, int n, int mode)
 {
-    const int r = forward_resident_as(h, n, mode);
-    if (r != BP_OK) return r;
-    if (n > 0) HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * h->ld[h->L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    int r = forward_resident_as(h, n, mode);
+    if (r != BP_OK || (r = outputs_to_host(h, n)) != BP_OK) return r;
     HIPCHK(hipStreamSynchronize(h->stream));
     return BP_OK;
 }
@@ -1295,10 +1237,8 @@ extern "C" int bp_forward(bp_handle *h, int n_frames, const float *in, float *ou
 {
     if (!h || !in || !out) return fail(BP_ERR_ARG, "bp_forward: null argument");
     int r = bp_upload_chunk(h, n_frames, in, nullptr);
-    if (r != BP_OK) return r;
-    if ((r = forward_chunk(h, n_frames, h->fwd_mode)) != BP_OK) return r;
-    const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
-    for (int j = 0; j < n_frames; ++j) memcpy(out + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * ldL, sizeof(float) * sL);
+    if (r != BP_OK || (r = forward_chunk(h, n_frames, h->fwd_mode)) != BP_OK) return r;
+    unpad_rows(out, h->s[h->L - 1], h->host_out.as<float>(), h->ld[h->L - 1], n_frames);
     return BP_OK;
 }
 
@@ -1306,51 +1246,33 @@ extern "C" int bp_forward_windows(bp_handle *h, const bp_window_chunk *c, float 
 {
     if (!out) return fail(BP_ERR_ARG, "bp_forward_windows: null argument");
     int r = upload_windows(h, c, false, "bp_forward_windows");
-    if (r != BP_OK) return r;
-    if ((r = forward_chunk(h, c->n_samples, h->fwd_mode)) != BP_OK) return r;
-    const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
-    for (int j = 0; j < c->n_samples; ++j) memcpy(out + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * ldL, sizeof(float) * sL);
+    if (r != BP_OK || (r = forward_chunk(h, c->n_samples, h->fwd_mode)) != BP_OK) return r;
+    unpad_rows(out, h->s[h->L - 1], h->host_out.as<float>(), h->ld[h->L - 1], c->n_samples);
     return BP_OK;
 }
 
-extern "C" int bp_cv_chunk(bp_handle *h, int n_frames, const float *in, const float *targ, float *sq_err_sum)
+extern "C" int bp_cv_chunk(bp_handle *h, int n_frames, const float *in, const float *targ, float *sum)
 {
-    if (!h || !in || !targ || !sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_chunk: null argument");
+    if (!h || !in || !targ || !sum) return fail(BP_ERR_ARG, "bp_cv_chunk: null argument");
     int r = bp_upload_chunk(h, n_frames, in, nullptr);
     if (r != BP_OK) return r;
     if ((r = forward_chunk(h, n_frames, BP_FORWARD_DEFAULT)) != BP_OK) return r;      // (CV keeps the step's kernels in either mode)
-    const int sL = h->s[h->L - 1], ldL = h->ld[h->L - 1];
-    const float *host_out = h->host_out.as<float>();
-    float squared_err = 0.0f;
-    for (int j = 0; j < n_frames; ++j)                   // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
-        for (int d = 0; d < sL; ++d) {
-            const float e = host_out[(size_t)j * ldL + d] - targ[(size_t)j * sL + d];
-            squared_err = squared_err + e * e;
-        }
-    *sq_err_sum = squared_err;
+    const int sL = h->s[h->L - 1];
+    *sum = sq_err_sum(h->host_out.as<float>(), h->ld[h->L - 1], sL, n_frames, [&](int j) { return targ + (size_t)j * sL; });
     return BP_OK;
 }
 
-extern "C" int bp_cv_chunk_windows(bp_handle *h, const bp_window_chunk *c, float *sq_err_sum)
+extern "C" int bp_cv_chunk_windows(bp_handle *h, const bp_window_chunk *c, float *sum)
 {
-    if (!sq_err_sum) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: null argument");
+    if (!sum) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: null argument");
     int r = upload_windows(h, c, false, "bp_cv_chunk_windows");
     if (r != BP_OK) return r;
-    const int L = h->L, sL = h->s[L - 1], ldL = h->ld[L - 1], n = c->n_samples;
+    const int L = h->L, sL = h->s[L - 1], n = c->n_samples;
     if (n > 0 && (!c->targ_frames || !c->targ_frame)) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: null targets");
     for (int i = 0; i < n; ++i)
         if (c->targ_frame[i] < 0 || c->targ_frame[i] >= c->n_frames) return fail(BP_ERR_ARG, "bp_cv_chunk_windows: targ_frame out of range");
     if ((r = forward_chunk(h, n, BP_FORWARD_DEFAULT)) != BP_OK) return r;
-    const float *host_out = h->host_out.as<float>();
-    float squared_err = 0.0f;
-    for (int j = 0; j < n; ++j) {                        // fp32, frame-major / bin-minor (BP_GPU.cu:458-467)
-        const float *t = c->targ_frames + (size_t)c->targ_frame[j] * sL;
-        for (int d = 0; d < sL; ++d) {
-            const float e = host_out[(size_t)j * ldL + d] - t[d];
-            squared_err = squared_err + e * e;
-        }
-    }
-    *sq_err_sum = squared_err;
+    *sum = sq_err_sum(h->host_out.as<float>(), h->ld[L - 1], sL, n, [&](int j) { return c->targ_frames + (size_t)c->targ_frame[j] * sL; });
     return BP_OK;
 }
 

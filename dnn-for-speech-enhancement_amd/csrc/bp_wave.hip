@@ -413,11 +413,10 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     HIPCHK(hipGetLastError());
     float *hout = (float *)h->wave_pin[1].p;
     HIPCHK(hipMemcpyAsync(hout, h->wave[3].p, pcm_b, hipMemcpyDeviceToHost, h->stream));
-    if (out_net) HIPCHK(hipMemcpyAsync(h->host_out.p, h->out_chunk.p, (size_t)n * h->ld[L - 1] * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (out_net && (r = outputs_to_host(h, n)) != BP_OK) return r;
     HIPCHK(hipStreamSynchronize(h->stream));
     wave_gather(out_pcm, p, c->sent_len, hout);
-    if (out_net)
-        for (int j = 0; j < n; ++j) memcpy(out_net + (size_t)j * sL, h->host_out.as<float>() + (size_t)j * h->ld[L - 1], sizeof(float) * sL);
+    if (out_net) unpad_rows(out_net, sL, h->host_out.as<float>(), h->ld[L - 1], n);
     return BP_OK;
 }
 

@@ -224,7 +224,7 @@ def test_training_calls_train_0_1_2_and_an_odd_count_of_bunches_behind_both_tile
     cfg = SM.BY_ID[cid]
     assert ZM.STAGING == "window chunks always, stacked chunks when visible dropout is on"
     step = open(os.path.join(CSRC, "bp_step.hip")).read()
-    assert "return h->th_vis ? ensure_stage_tiles(h) : BP_OK;" in step and "if (h->windows) HIPCHK(stage_bunch(h, first, fb, false));" in step
+    assert "return h->th_vis ? ensure_stage_tiles(h) : BP_OK;" in step and "if (h->res.windows) HIPCHK(stage_bunch(h, first, fb, false));" in step
     counts, parity = collections.defaultdict(set), collections.defaultdict(set)
     for wid, _, calls in ZM.all_walks(cfg):
         staged = 0
