@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "bp_lmstream_open", "bp_lmstream_push", "bp_lmstream_close", "bp_lmstream_counts",
     "bp_noise_defaults", "bp_logmmse_waves_nt", "bp_eval_mix_logmmse_nt", "bp_lmstream_open_nt", "bp_set_nat",
     "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
+    "bp_mel_defaults", "bp_mel_filters", "bp_mel_dct", "bp_wave_mfcc", "bp_set_mix_aux",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
@@ -152,6 +153,16 @@ class BPResampleParams(C.Structure):
     _fields_ = [("zeros", C.c_int), ("beta", C.c_double), ("rolloff", C.c_double)]
 
 
+class BPMelParams(C.Structure):
+    """bp_mel_params (include/bp_c_api.h): the MFCC auxiliary target.  mean / scale point into arrays the owner keeps alive
+    (mel_params stores them on the object)."""
+    _fields_ = [
+        ("sample_rate", C.c_int), ("n_mel", C.c_int), ("n_ceps", C.c_int), ("first_coef", C.c_int),
+        ("f_lo", C.c_float), ("f_hi", C.c_float), ("lifter", C.c_float),
+        ("mean", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
+    ]
+
+
 class BPConfig(C.Structure):
     _fields_ = [
         ("gpu_used", C.c_int), ("numlayers", C.c_int), ("layersizes", C.c_int * MAXLAYER),
@@ -255,6 +266,12 @@ def load_library(path=None):
     lib.bp_set_output.argtypes = [hp, C.c_int, C.c_int, C.c_int]
     lib.bp_set_forward.argtypes = [hp, C.c_int]
     lib.bp_set_nat.argtypes = [hp, C.c_int, C.POINTER(BPNoiseParams)]
+    ip = C.POINTER(C.c_int)
+    lib.bp_mel_defaults.argtypes = [C.c_int, C.POINTER(BPMelParams)]
+    lib.bp_mel_filters.argtypes = [C.c_int, C.POINTER(BPMelParams), fp, ip, ip]
+    lib.bp_mel_dct.argtypes = [C.POINTER(BPMelParams), fp]
+    lib.bp_wave_mfcc.argtypes = [C.c_int, C.c_int, C.POINTER(BPMelParams), C.c_int, ip, fp, fp, fp, fp]
+    lib.bp_set_mix_aux.argtypes = [hp, C.POINTER(BPMelParams)]
     lib.bp_stream_packed.argtypes = [C.c_void_p]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
@@ -338,6 +355,7 @@ class BP_GPU(object):
         if int(forward_mode) != FORWARD_DEFAULT:
             self.set_forward(forward_mode)
         self._nat_mode = "static"
+        self._mix_aux = self._mix_aux_set = None
         if nat_mode != "static" or nat_noise is not None:
             self.set_nat(nat_mode, nat_noise)
 
@@ -411,6 +429,20 @@ class BP_GPU(object):
     def nat_mode(self):
         """"static" or "dynamic": what set_nat (or nat_mode= at construction) set last."""
         return self._nat_mode
+
+    def set_mix_aux(self, mel):
+        """The MFCC auxiliary target of the mixing corpus (bp_set_mix_aux): what mel_params makes, or None for none.  From the next
+        set_mix_corpus on -- its target must then begin with LPS and layersizes[-1] be parts * fea_dim + n_ceps; the target row is
+        [LPS | MFCC | mask].  A corpus that is already set keeps what it was set with."""
+        if mel is not None and not isinstance(mel, BPMelParams):
+            self._fail("set_mix_aux: mel must be None or what mel_params returns")
+        self._check(self._lib.bp_set_mix_aux(self._h, None if mel is None else C.byref(mel)))
+        self._mix_aux = None if mel is None else (int(mel.n_mel), int(mel.n_ceps))
+
+    @property
+    def mix_aux_dims(self):
+        """(n_mel, n_ceps) of the MFCC columns of the corpus set last, or None when it has none."""
+        return self._mix_aux_set
 
     def train(self, n_frames, indata, targ):
         x = self._in(indata, n_frames, self.layersizes[0], "in")
@@ -562,6 +594,7 @@ class BP_GPU(object):
         self.mix_fea_dim, self.mix_clean_len = mean.size, clen
         self.mix_nat = self.layersizes[0] == (int(context) + 1) * mean.size
         self.mix_n_clean, self.mix_reverb_entries = len(cl), 0
+        self._mix_aux_set = self._mix_aux
 
     def set_mix_reverb(self, rirs, pair_clean, pair_rir, target="reverberant", early_taps=0):
         """bp_set_mix_reverb: pair k = (clean sentence pair_clean[k], response rirs[pair_rir[k]]) becomes clean entry n_clean + k
@@ -907,6 +940,81 @@ def wave_lps(device, fea_dim, sentences):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
+
+
+def mel_params(sample_rate, **fields):
+    """A BPMelParams: bp_mel_defaults(sample_rate) -- 26 filters, 13 coefficients from c0, 0 .. sample_rate / 2, lifter 22, no mean
+    or scale -- overridden by the fields given (n_mel, n_ceps, first_coef, f_lo, f_hi, lifter; mean, scale: n_ceps values each).  A
+    weight alpha_r on coefficient r's squared error is scale_r * sqrt(alpha_r)."""
+    lib = load_library()
+    mp = BPMelParams()
+    rc = lib.bp_mel_defaults(int(sample_rate), C.byref(mp))
+    if rc != 0:
+        _raise(lib, rc)
+    names = [f[0] for f in BPMelParams._fields_]
+    for k, v in fields.items():
+        if k not in names or k == "sample_rate":
+            raise BPError("mel_params: unknown field %s" % k)
+        if k in ("mean", "scale"):
+            continue
+        setattr(mp, k, float(v) if k in ("f_lo", "f_hi", "lifter") else int(v))
+    for k in ("mean", "scale"):
+        if fields.get(k) is not None:
+            a = np.ascontiguousarray(fields[k], dtype=np.float32).reshape(-1)
+            if a.size != mp.n_ceps:
+                raise BPError("mel_params: %s must hold n_ceps = %d values, not %d" % (k, mp.n_ceps, a.size))
+            setattr(mp, "_keep_" + k, a)                    # (the struct holds a pointer into it)
+            setattr(mp, k, _fp(a))
+    return mp
+
+
+def mel_filters(fea_dim, mel):
+    """bp_mel_filters: (w [n_mel][fea_dim] float32, first_bin [n_mel], n_bins [n_mel]) -- the triangles and the bins with w > 0; host only."""
+    lib = load_library()
+    n = max(int(mel.n_mel), 0)
+    w = np.zeros((n, max(int(fea_dim), 1)), np.float32)
+    first, nb = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib.bp_mel_filters(int(fea_dim), C.byref(mel), _fp(w) if w.size else None, first.ctypes.data_as(ip), nb.ctypes.data_as(ip))
+    if rc != 0:
+        _raise(lib, rc)
+    return w, first[:n], nb[:n]
+
+
+def mel_dct(mel):
+    """bp_mel_dct: t [n_ceps][n_mel] float32, the liftered DCT-II rows first_coef .. first_coef + n_ceps - 1; host only."""
+    lib = load_library()
+    n, c = max(int(mel.n_mel), 0), max(int(mel.n_ceps), 0)
+    t = np.zeros((c, n), np.float32)
+    rc = lib.bp_mel_dct(C.byref(mel), _fp(t) if t.size else None)
+    if rc != 0:
+        _raise(lib, rc)
+    return t
+
+
+def wave_mfcc(device, fea_dim, sentences, mel, return_logmel=False, return_power=False):
+    """bp_wave_mfcc: the MFCC target rows of every sentence, one [T_s][n_ceps] float32 array each (mean and scale applied; no
+    handle).  With return_logmel / return_power a dict of mfcc and logmel [T_s][n_mel] / power [T_s][fea_dim] lists."""
+    lib = load_library()
+    pcm, lens, frames = _sentences(sentences, int(fea_dim))
+    T = int(frames.sum())
+    n_mel, n_ceps = max(int(mel.n_mel), 1), max(int(mel.n_ceps), 1)
+    cc = np.empty((max(T, 1), n_ceps), np.float32)
+    lm = np.empty((max(T, 1), n_mel), np.float32) if return_logmel else None
+    pw = np.empty((max(T, 1), int(fea_dim)), np.float32) if return_power else None
+    rc = lib.bp_wave_mfcc(int(device), int(fea_dim), C.byref(mel), len(lens), lens.ctypes.data_as(C.POINTER(C.c_int)), _fp(pcm),
+                          None if pw is None else _fp(pw), None if lm is None else _fp(lm), _fp(cc))
+    if rc != 0:
+        _raise(lib, rc)
+    cut = np.cumsum(frames)[:-1]
+    out = {"mfcc": np.split(cc[:T], cut)}
+    if not return_logmel and not return_power:
+        return out["mfcc"]
+    if return_logmel:
+        out["logmel"] = np.split(lm[:T], cut)
+    if return_power:
+        out["power"] = np.split(pw[:T], cut)
+    return out
 
 
 def logmmse_params(params=None):

@@ -13,7 +13,8 @@
 //   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in
 //                   bp_mix.hip) and its streams (bp_lmstream_open, _push, ...)
 //   (bp_fft.h: the device functions and the frame plan of the signal-layer units; bp_stream_core.h: counts, carry, push checks and
-//   the block owner of the two streaming engines)
+//   the block owner of the two streaming engines; bp_mel.h: the tables and the launcher of the MFCC auxiliary target, whose kernel
+//   lives in bp_wave.hip and whose setter in bp_mix.hip)
 //   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
 //   (bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
 //   and fail / HIPCHK; bp_chunk.h: the resident chunk -- bp_handle::res --, how one becomes resident and what its readers check)
@@ -54,6 +55,15 @@ struct bp_dp;
 // Checked noise parameters in the units the kernels use: c0 = (1-q)/q (1+xi), c1 = xi/(1+xi), xi = 10^(xi_h1_db / 10) (noise_check,
 // bp_classic.h).  spp == false: the VAD-gated update of the log-MMSE recursion, and nothing else of this is read.
 struct NoiseP { bool spp; double c0, c1, a_pow, a_spp, p_lo, p_cap; };
+
+// Checked parameters of the MFCC auxiliary target (mel_check, bp_mel.h): bp_mel_params within its ranges, mean / scale copied
+// (NULL: 0 and 1)
+constexpr int MEL_MAX = 128;                                     // the most filters, and so the most coefficients
+struct MelP {
+    int sample_rate, n_mel, n_ceps, first_coef;
+    double f_lo, f_hi, lifter;
+    float mean[MEL_MAX], scale[MEL_MAX];
+};
 
 struct bp_handle {
     bp_config cfg;
@@ -106,6 +116,9 @@ struct bp_handle {
     Buf wave[4], wave_pin[2];
     // bp_set_mix_corpus (bp_mix.hip): the resident corpus and the grow-only buffers of the mixing calls, or null
     struct MixState *mix;
+    // bp_set_mix_aux (bp_mix.hip, bp_mel.h): the MFCC auxiliary target the next bp_set_mix_corpus is set with (checked parameters, or
+    // aux_on) and the device block its tables go to, allocated once at the parameter limits
+    bool aux_on; MelP aux; float *aux_tab;
     // bp_stream_open (bp_stream.hip): the open streaming sessions of this handle
     std::vector<struct bp_stream *> streams;
 };

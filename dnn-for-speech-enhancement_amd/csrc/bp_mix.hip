@@ -13,6 +13,7 @@
 //   bp_mix_pcm       one workgroup per segment: x = fmaf(g, v, s), s and g v into the padded buffers (padding written as zeros)
 //   bp_wave_analysis (bp_wave.hip) on x: the staged normalised rows, win_start / nat_row, the noisy LPS (bp_mix_features)
 //   bp_mix_targets   one workgroup per frame: the FFTs of s and g v in LDS, one after the other, and the frame's target row
+//   bp_wave_mel      (bp_wave.hip, with bp_set_mix_aux) on s: the MFCC columns of the target row, between the LPS and the mask
 //   bp_wave_nat      (bp_wave.hip) the noise-aware rows; in BP_NAT_DYNAMIC (bp_set_nat) bp_wave_dnat: one row per frame from the noisy
 //                    spectrum, which the calls that keep none hold behind those rows for the tracker alone
 //   bp_mix_tables    per row i: win_start / targ_frame / nat_row of mixture-frame order[i]
@@ -37,6 +38,7 @@
 #include "bp_eval.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
+#include "bp_mel.h"
 
 namespace {
 
@@ -120,6 +122,7 @@ struct MixTargArgs {
     int n_mix, log2M, D, hop, target, ldt;
     float thr;                                                   // 10^(lc_db / 10)
     float *targ;                                                 // [frames][ldt]
+    int col2;                                                    // first column of a two-part target's second part: D, or D + n_ceps behind the MFCC columns (bp_set_mix_aux)
 };
 }  // namespace
 
@@ -143,8 +146,8 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_mix_targets(const MixTargArgs
         case BP_MIX_LPS: t[k] = lps; break;
         case BP_MIX_IRM: t[k] = irm; break;
         case BP_MIX_IBM: t[k] = ibm; break;
-        case BP_MIX_LPS_IRM: t[k] = lps; t[a.D + k] = irm; break;
-        default: t[k] = lps; t[a.D + k] = ibm; break;
+        case BP_MIX_LPS_IRM: t[k] = lps; t[a.col2 + k] = irm; break;
+        default: t[k] = lps; t[a.col2 + k] = ibm; break;
         }
     }
 }
@@ -369,6 +372,7 @@ struct MixState {
     int D, log2M, M, hop, ctx, toff, target, sL;
     bool nat;
     float thr;
+    bool aux; MelDev mel;                                        // bp_set_mix_aux when the corpus was set: the MFCC columns [D, D + mel.n_ceps) and their tables (h->aux_tab)
     int n_clean, n_noise, n_pair;                                // n_pair: derived entries n_clean .. n_clean + n_pair - 1
     std::vector<int64_t> clean_len, noise_len;                   // clean_len: [n_clean + n_pair]
     Buf reverb;                                                  // device: r | e (early target only) | ReverbJob [n_pair]
@@ -514,9 +518,17 @@ int generate(bp_handle *h, const Call &c, const bp_mixture *m, const int *order,
         MixTargArgs t; memset(&t, 0, sizeof(t));
         t.s = a.s; t.v = a.v; t.win = win; t.tw = tw; t.F = F;
         t.n_mix = c.n; t.log2M = ms->log2M; t.D = D; t.hop = ms->hop; t.target = ms->target; t.ldt = ms->sL; t.thr = ms->thr;
+        t.col2 = ms->aux ? D + ms->mel.n_ceps : D;
         t.targ = targ_d;
         hipLaunchKernelGGL(bp_mix_targets, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(ms->M) + (size_t)(ms->M + 1) * 4, h->stream, t);
         HIPCHK(hipGetLastError());
+        if (ms->aux) {
+            MelArgs q; memset(&q, 0, sizeof(q));
+            q.pcm = a.s; q.win = win; q.tw = tw; q.F = F;
+            q.n_sent = c.n; q.log2M = ms->log2M; q.D = D; q.hop = ms->hop; q.m = ms->mel;
+            q.mfcc = targ_d; q.ldm = ms->sL; q.col = D;
+            HIPCHK(wave_mel_launch(q, n, h->stream));
+        }
     }
     if (dyn)
         HIPCHK(wave_dnat_launch(h->nat_np, Y, F, c.n, D, (const float *)(cp + ms->o_mean), (const float *)(cp + ms->o_istd), nat_d, h->stream));
@@ -572,8 +584,19 @@ extern "C" int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c)
     if (!nat && (long)h->s[0] != (long)ctx * D)
         return fail(BP_ERR_ARG, "bp_set_mix_corpus: layersizes[0] must be context*fea_dim or (context+1)*fea_dim");
     if (c->target < BP_MIX_LPS || c->target > BP_MIX_LPS_IBM) return fail(BP_ERR_ARG, "bp_set_mix_corpus: unknown target");
-    if ((long)sL != (long)parts_of(c->target) * D)
+    MelTab mel;
+    if (h->aux_on) {                                             // bp_set_mix_aux: [LPS | MFCC | mask]
+        if (c->target != BP_MIX_LPS && c->target != BP_MIX_LPS_IRM && c->target != BP_MIX_LPS_IBM)
+            return fail(BP_ERR_ARG, "bp_set_mix_corpus: with the MFCC auxiliary target (bp_set_mix_aux) the target must begin with LPS (LPS, LPS+IRM, LPS+IBM)");
+        const long want = (long)parts_of(c->target) * D + h->aux.n_ceps;
+        if ((long)sL != want)
+            return fail(BP_ERR_ARG, "bp_set_mix_corpus: layersizes[last] must be parts*fea_dim + n_ceps = " + std::to_string(want) +
+                                        " with the MFCC auxiliary target (bp_set_mix_aux)");
+        const int r = mel_tables("bp_set_mix_corpus", D, h->aux, mel);
+        if (r != BP_OK) return r;
+    } else if ((long)sL != (long)parts_of(c->target) * D) {
         return fail(BP_ERR_ARG, "bp_set_mix_corpus: layersizes[last] must be fea_dim (LPS, IRM, IBM) or 2*fea_dim (LPS+IRM, LPS+IBM)");
+    }
     if (!std::isfinite(c->lc_db)) return fail(BP_ERR_ARG, "bp_set_mix_corpus: lc_db is not finite");
     if (!c->mean || !c->inv_std) return fail(BP_ERR_ARG, "bp_set_mix_corpus: null mean / inv_std");
     if (c->n_clean < 1 || c->n_noise < 1 || !c->clean_len || !c->noise_len || !c->clean_pcm || !c->noise_pcm)
@@ -626,7 +649,32 @@ extern "C" int bp_set_mix_corpus(bp_handle *h, const bp_mix_corpus *c)
     hipError_t e = hipMemcpy(cp + ms->o_clean, c->clean_pcm, nc * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(cp + ms->o_noise, c->noise_pcm, nn * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(cp + ms->o_cl_off, small.data(), small.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h->aux_on) {                          // the tables of this fea_dim into the handle's block (nothing reads it: the stream is idle)
+        const MelBlock mb = mel_block(mel.n_mel, mel.n_ceps, mel_packed_weights(mel));
+        std::vector<char> tb(mb.bytes, 0);
+        mel_block_fill(tb.data(), mb, h->aux, mel);
+        e = hipMemcpy(h->aux_tab, tb.data(), mb.bytes, hipMemcpyHostToDevice);
+        ms->aux = true; ms->mel = mel_dev((const char *)h->aux_tab, mb, mel);
+    }
     if (e != hipSuccess) { mix_free(h); return fail(BP_ERR_DEVICE, std::string("bp_set_mix_corpus: ") + hipGetErrorString(e)); }
+    return BP_OK;
+}
+
+// The MFCC auxiliary target of the next bp_set_mix_corpus (include/bp_c_api.h).  Every check before anything is
+// touched; the table block is allocated by the first call that turns the target on, at the parameter limits, and never again.
+extern "C" int bp_set_mix_aux(bp_handle *h, const bp_mel_params *p)
+{
+    if (!h) return fail(BP_ERR_ARG, "bp_set_mix_aux: null handle");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_set_mix_aux: not on an attached data-parallel handle");
+    if (!p) { h->aux_on = false; return BP_OK; }
+    MelP m;
+    { const int r = mel_check("bp_set_mix_aux", p, m); if (r != BP_OK) return r; }
+    if (!h->aux_tab) {
+        HIPCHK(hipSetDevice(h->cfg.device));
+        const int r = dev_alloc(h, &h->aux_tab, mel_block_limit() / 4);
+        if (r != BP_OK) return r;
+    }
+    h->aux = m; h->aux_on = true;
     return BP_OK;
 }
 

@@ -22,6 +22,8 @@
 //                      atomics, the same bits on every run)
 //   bp_wave_resample   rational sample-rate conversion (bp_resample_waves, bp_resample.h): per output sample one lane's serial sum
 //                      in double over its polyphase taps, the workgroup's input span staged in LDS where it fits
+//   bp_wave_mel        the MFCC auxiliary target (bp_wave_mfcc, bp_set_mix_aux; bp_mel.h): per frame |S|^2 in LDS, one
+//                      lane's serial sum in double per mel filter, one lane's serial sum in double per cepstral coefficient
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cmath>
@@ -31,6 +33,7 @@
 #include "bp_classic.h"
 #include "bp_fft.h"
 #include "bp_handle.h"
+#include "bp_mel.h"
 #include "bp_resample.h"
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_wave_analysis(const WaveAnaArgs a)
@@ -186,6 +189,42 @@ __global__ __launch_bounds__(RS_BLOCK) void bp_wave_resample(const ResampleArgs 
     a.out[(size_t)a.oo[s] + k] = (float)acc;
 }
 
+// One frame's power spectrum, log mel energies and cepstral coefficients.  The order of every sum is the
+// definition, so no sum is spread over lanes: thread j < n_mel adds the bins of filter j in ascending order to one double, thread
+// r < n_ceps the filters in ascending order to another.  A product of two fp32 values is exact in double, so each step is one
+// rounded addition, fused or not.  LDS: the FFT, then P[M + 1] and the n_mel log energies.
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_mel(const MelArgs a)
+{
+    extern __shared__ float2 z[];
+    const int g = blockIdx.x, M = 1 << a.log2M, tid = threadIdx.x;
+    float *P = reinterpret_cast<float *>(z + lds_bytes(M) / sizeof(float2)), *lm = P + (M + 1);
+    const int s = sentence_of(a.F, a.n_sent, g);
+    rfft_frame(z, a.pcm + (size_t)(g + s) * a.hop, a.win, a.tw, a.log2M);
+    for (int k = tid; k <= M; k += blockDim.x) {
+        const float2 X = rfft_bin(z, a.tw, M, k);
+        const float p = X.x * X.x + X.y * X.y;
+        P[k] = p;
+        if (a.power) a.power[(size_t)g * a.D + k] = p;
+    }
+    __syncthreads();
+    if (tid < a.m.n_mel) {
+        const float *w = a.m.wp + a.m.off[tid], *pk = P + a.m.first[tid];
+        const int nb = a.m.nb[tid];
+        double E = 0.0;
+        for (int i = 0; i < nb; ++i) E = fma((double)w[i], (double)pk[i], E);
+        const float l = lps_of((float)E);
+        lm[tid] = l;
+        if (a.logmel) a.logmel[(size_t)g * a.m.n_mel + tid] = l;
+    }
+    __syncthreads();
+    if (a.mfcc && tid < a.m.n_ceps) {
+        const float *t = a.m.tT + tid;
+        double c = 0.0;
+        for (int j = 0; j < a.m.n_mel; ++j) c = fma((double)t[(size_t)j * a.m.n_ceps], (double)lm[j], c);
+        a.mfcc[(size_t)g * a.ldm + a.col + tid] = ((float)c - a.m.mean[tid]) * a.m.scale[tid];
+    }
+}
+
 // ------------------------------------------------------------------ host side
 int wave_log2_fft(int fea_dim)
 {
@@ -266,6 +305,13 @@ hipError_t wave_overlap_launch(const float *syn, const float *win, const int *F,
     return hipGetLastError();
 }
 
+hipError_t wave_mel_launch(const MelArgs &a, int frames, hipStream_t st)
+{
+    const int M = 1 << a.log2M;
+    hipLaunchKernelGGL(bp_wave_mel, dim3((unsigned)frames), dim3(WAVE_THREADS), lds_bytes(M) + (size_t)(M + 1 + MEL_MAX) * 4, st, a);
+    return hipGetLastError();
+}
+
 // Frame plan of a call (bp_fft.h).  Checked before any device work.
 int plan_waves(const char *who, int fea_dim, int n_sent, const int *sent_len, const float *pcm, size_t max_frames, WavePlan &p)
 {
@@ -343,6 +389,75 @@ extern "C" int bp_wave_lps(int device, int fea_dim, int n_sent, const int *sent_
     }
     if (e == hipSuccess) e = hipMemcpyAsync(lps, d + w.bytes, out_b, hipMemcpyDeviceToHost, os.st);
     return os.finish("bp_wave_lps");
+}
+
+// ------------------------------------------------------------------ the MFCC auxiliary target (include/bp_c_api.h)
+extern "C" int bp_mel_defaults(int sample_rate, bp_mel_params *p)
+{
+    if (!p) return fail(BP_ERR_ARG, "bp_mel_defaults: null pointer");
+    if (sample_rate < 1) return fail(BP_ERR_ARG, "bp_mel_defaults: sample_rate must be > 0");
+    p->sample_rate = sample_rate; p->n_mel = 26; p->n_ceps = 13; p->first_coef = 0;
+    p->f_lo = 0.0f; p->f_hi = 0.5f * (float)sample_rate; p->lifter = 22.0f;
+    p->mean = p->scale = nullptr;
+    return BP_OK;
+}
+
+extern "C" int bp_mel_filters(int fea_dim, const bp_mel_params *p, float *w, int *first_bin, int *n_bins)
+{
+    MelP m; MelTab tab;
+    { const int r = mel_check("bp_mel_filters", p, m); if (r != BP_OK) return r; }
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, "bp_mel_filters: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    { const int r = mel_tables("bp_mel_filters", fea_dim, m, tab); if (r != BP_OK) return r; }
+    if (w) memcpy(w, tab.w.data(), tab.w.size() * 4);
+    if (first_bin) memcpy(first_bin, tab.first.data(), tab.first.size() * 4);
+    if (n_bins) memcpy(n_bins, tab.nb.data(), tab.nb.size() * 4);
+    return BP_OK;
+}
+
+extern "C" int bp_mel_dct(const bp_mel_params *p, float *t)
+{
+    MelP m;
+    { const int r = mel_check("bp_mel_dct", p, m); if (r != BP_OK) return r; }
+    if (!t) return fail(BP_ERR_ARG, "bp_mel_dct: null output");
+    mel_dct(m, t);
+    return BP_OK;
+}
+
+extern "C" int bp_wave_mfcc(int device, int fea_dim, const bp_mel_params *mp, int n_sent, const int *sent_len, const float *pcm, float *power,
+                            float *logmel, float *mfcc)
+{
+    MelP m; MelTab tab; WavePlan p;
+    { const int r = mel_check("bp_wave_mfcc", mp, m); if (r != BP_OK) return r; }
+    { const int r = plan_waves("bp_wave_mfcc", fea_dim, n_sent, sent_len, pcm, WAVE_MAX_FRAMES, p); if (r != BP_OK) return r; }
+    { const int r = mel_tables("bp_wave_mfcc", fea_dim, m, tab); if (r != BP_OK) return r; }
+    if (!power && !logmel && !mfcc) return fail(BP_ERR_ARG, "bp_wave_mfcc: no output");
+    const WaveIn w = wave_in_layout(p, fea_dim);
+    const MelBlock mb = mel_block(m.n_mel, m.n_ceps, mel_packed_weights(tab));
+    Layout lay(w.bytes);                                         // the input block | the tables | power | logmel | mfcc
+    const size_t o_mb = lay.take(mb.bytes), in_b = lay.size();
+    const size_t pw_b = power ? p.frames * fea_dim * 4 : 0, lm_b = logmel ? p.frames * m.n_mel * 4 : 0, cc_b = mfcc ? p.frames * m.n_ceps * 4 : 0;
+    const size_t o_pw = lay.take(pw_b), o_lm = lay.take(lm_b), o_cc = lay.take(cc_b);
+    OneShot os;
+    { const int r = os.open("bp_wave_mfcc", device, lay.size()); if (r != BP_OK) return r; }
+    std::vector<char> hb(in_b, 0);
+    wave_in_fill(hb.data(), w, p, fea_dim, nullptr, nullptr, sent_len, pcm);
+    mel_block_fill(hb.data() + o_mb, mb, m, tab);
+    hipError_t &e = os.e;
+    char *d = os.d.as<char>();
+    if (e == hipSuccess) e = hipMemcpyAsync(d, hb.data(), in_b, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess) {
+        MelArgs a; memset(&a, 0, sizeof(a));
+        a.pcm = (const float *)(d + w.pcm); a.win = (const float *)(d + w.win); a.tw = (const float2 *)(d + w.tw); a.F = (const int *)(d + w.F);
+        a.n_sent = n_sent; a.log2M = p.log2M; a.D = fea_dim; a.hop = p.hop;
+        a.m = mel_dev(d + o_mb, mb, tab);
+        a.power = power ? (float *)(d + o_pw) : nullptr; a.logmel = logmel ? (float *)(d + o_lm) : nullptr;
+        a.mfcc = mfcc ? (float *)(d + o_cc) : nullptr; a.ldm = m.n_ceps; a.col = 0;
+        e = wave_mel_launch(a, (int)p.frames, os.st);
+    }
+    if (e == hipSuccess && power) e = hipMemcpyAsync(power, d + o_pw, pw_b, hipMemcpyDeviceToHost, os.st);
+    if (e == hipSuccess && logmel) e = hipMemcpyAsync(logmel, d + o_lm, lm_b, hipMemcpyDeviceToHost, os.st);
+    if (e == hipSuccess && mfcc) e = hipMemcpyAsync(mfcc, d + o_cc, cc_b, hipMemcpyDeviceToHost, os.st);
+    return os.finish("bp_wave_mfcc");
 }
 
 extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *c, float *out_pcm, float *out_net)

@@ -9,7 +9,9 @@
 //         [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50] [cv_rir_list=rir.list]
 //         [rir_rooms=N] [rir_room_lo=3,3,2.5] [rir_room_hi=10,8,4] [rir_t60=0.2,0.8] [rir_margin=0.5] [rir_dist=0.5,3] [rir_ms=400]
 //         [rir_window=taps] [rir_rooms_out=rooms.txt] [cv_rir_rooms=N] [rate=8000] [nat=static|dynamic]
+//         [aux_target=mfcc] [aux_rate=8000] [aux_mel=26] [aux_ceps=13] [aux_first=0] [aux_lifter=22] [aux_weight=1] [aux_norm_file=mfcc.norm]
 //   bpmix clean_list=... noise_list=... fea_dim=129 norm_out=mix.norm [snr_list=...] [mix_per_clean=...] [init_randem_seed=...]
+//   bpmix clean_list=... fea_dim=129 aux_target=mfcc aux_norm_out=mfcc.norm [aux_rate=...] [aux_mel=...] [aux_ceps=...] [aux_first=...] [aux_lifter=...]
 //
 // The plan of the epoch is bp_mix_plan(init_randem_seed, clean sentences, mix_per_clean, noise lengths, snr_list); it is cut into
 // calls of at most traincache rows (frames + n_mix (context-1)) in plan order, and call k trains its frames in the order
@@ -27,6 +29,13 @@
 // rate=R: every clean or noise WAV (training and CV) whose rate is not R is converted to R on the device as its
 // list is loaded (bp_resample_waves: one call and one line on stdout per list and distinct rate; the float samples go on as they
 // come), R is the rate of the corpus, and a response of rir_list must have it: an impulse response is not converted.
+// aux_target=mfcc: the MFCC auxiliary target of multi-objective training.  The target row becomes
+// [LPS | MFCC | mask]: target= must begin with lps, layersizes[last] is parts*fea_dim + aux_ceps, and the net wants
+// output_linear_dims = fea_dim + aux_ceps (both logged).  aux_rate (default: rate=, else the rate of the clean sentences) places the
+// aux_mel triangles between 0 and aux_rate / 2; aux_ceps coefficients from c0 (aux_first=1: from c1), HTK lifter aux_lifter (0:
+// none).  aux_norm_file: mean and inverse std of the coefficients in the norm-file format, aux_ceps values each; aux_weight: the
+// weight of the MFCC columns' squared error, folded as its square root into the scale.  aux_norm_out: those statistics of the clean
+// sentences, one pass of bp_wave_mfcc, accumulated in double; nothing is trained and noise_list is not needed.
 // Every key, list, WAV and drawn room is checked before the device is used (with rate=, before anything but the conversions).  Errors: message +
 // exit(0); success: return 1 (reference convention).
 #include <math.h>
@@ -64,6 +73,10 @@ struct Params {
     unsigned long long seed = 0, cv_seed = 20261016ull, dropout_seed = 0;
     std::vector<float> snr = {-5, 0, 5, 10, 15, 20};
     RirKeys rir;
+    int aux_target = 0, aux_rate = 0, aux_mel = 26, aux_ceps = 13, aux_first = 0;   // aux_target=mfcc (1): the MFCC auxiliary target
+    float aux_lifter = 22.0f, aux_weight = 1.0f;
+    std::string aux_norm_file, aux_norm_out;
+    bool aux_keys = false;                                   // an aux_* key other than aux_target was given
 };
 
 Params parse(int argc, char **argv)
@@ -101,9 +114,16 @@ Params parse(int argc, char **argv)
         {"output_act", K_CHOICE, &P.output_act, 0, 0, "linear|sigmoid"},
         {"output_linear_dims", K_INT, &P.output_linear_dims, 0, 1000000},
         {"output_loss", K_CHOICE, &P.output_loss, 0, 0, "xent|mse"},
+        {"aux_target", K_CHOICE, &P.aux_target, 1, 0, "mfcc", "is not mfcc"},
+    };
+    const Key aux_keys[] = {
+        {"aux_rate", K_INT, &P.aux_rate, 1, (double)RATE_MAX}, {"aux_mel", K_INT, &P.aux_mel, 2, 128}, {"aux_ceps", K_INT, &P.aux_ceps, 1, 128},
+        {"aux_first", K_INT, &P.aux_first, 0, 1}, {"aux_lifter", K_FLOAT, &P.aux_lifter, 0, 1e6}, {"aux_weight", K_FLOAT, &P.aux_weight, 0, 1e12},
+        {"aux_norm_file", K_STR, &P.aux_norm_file}, {"aux_norm_out", K_STR, &P.aux_norm_out},
     };
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
+        if (key_apply(aux_keys, WHO, a)) { P.aux_keys = true; continue; }
         if (key_apply(keys, WHO, a) || nat_key(a, WHO, nullptr, &P.nat)) continue;
         const int r = rir_key(P.rir, a.k, a.v);
         if (!r) fail("bpmix: unknown key " + a.k);
@@ -156,6 +176,49 @@ Reverb read_reverb(const Params &P, const std::string &what, const std::string &
     return r;
 }
 
+// aux_target=mfcc: the parameters of the keys at the corpus' rate, checked against fea_dim on the host (no mean / scale yet)
+bp_mel_params aux_params(const Params &P, const std::vector<int> &clean_rates)
+{
+    int rate = P.aux_rate ? P.aux_rate : P.rate;
+    if (!rate) { one_rate("aux_target", clean_rates); rate = clean_rates[0]; }
+    bp_mel_params mp;
+    check(bp_mel_defaults(rate, &mp));
+    mp.n_mel = P.aux_mel; mp.n_ceps = P.aux_ceps; mp.first_coef = P.aux_first; mp.lifter = P.aux_lifter;
+    if (bp_mel_filters(P.fea_dim, &mp, nullptr, nullptr, nullptr) != 0) fail(std::string("bpmix: aux_target: ") + bp_last_error());
+    return mp;
+}
+
+// aux_norm_out: mean and inverse std of the MFCC of the clean sentences (the norm-file format, aux_ceps values), bp_wave_mfcc in
+// calls of at most 2^24 samples
+int aux_norm_pass(const Params &P, const Corpus &clean, bp_mel_params mp)
+{
+    const int D = P.fea_dim, hop = D - 1, nc = mp.n_ceps, ns = (int)clean.len.size();
+    FILE *fn = fopen(P.aux_norm_out.c_str(), "wt");
+    if (!fn) fail("can not open norm file: " + P.aux_norm_out);
+    std::vector<double> sum(nc, 0.0), sq(nc, 0.0);
+    std::vector<float> cc;
+    std::vector<int> lens;
+    size_t total = 0, at = 0;
+    for (int s0 = 0; s0 < ns;) {
+        int s1 = s0;
+        size_t n = 0, T = 0;
+        lens.clear();
+        while (s1 < ns && (s1 == s0 || n + (size_t)clean.len[s1] <= ((size_t)1 << 24))) {
+            lens.push_back((int)clean.len[s1]);
+            n += (size_t)clean.len[s1]; T += ((size_t)clean.len[s1] - 1) / hop + 2;
+            ++s1;
+        }
+        cc.resize(T * nc);
+        check(bp_wave_mfcc(P.device, D, &mp, s1 - s0, lens.data(), clean.pcm.data() + at, nullptr, nullptr, cc.data()));
+        for (size_t f = 0; f < T; ++f)
+            for (int r = 0; r < nc; ++r) { const double v = cc[f * nc + r]; sum[r] += v; sq[r] += v * v; }
+        total += T; at += n; s0 = s1;
+    }
+    write_norm(fn, sum, sq, total);
+    printf("bpmix: MFCC norm file of %zu clean frames of %d sentences -> %s\n", total, ns, P.aux_norm_out.c_str());
+    return 1;
+}
+
 // norm_out: mean and inverse std of the noisy LPS of the epoch's training mixtures (bpfeat's format), on a one-layer handle
 int norm_pass(const Params &P, const Corpus &clean, const Corpus &noise, std::vector<bp_mixture> plan, const Reverb &rv)
 {
@@ -204,6 +267,13 @@ int main(int argc, char **argv)
     // every list and WAV is read and checked before the device is used
     std::vector<int> clean_rates, cv_rates;
     const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, &clean_rates, nullptr, P.rate, P.device));
+    if (P.aux_keys && !P.aux_target) fail("bpmix: the aux_* keys need aux_target=mfcc");
+    bp_mel_params mp;
+    memset(&mp, 0, sizeof(mp));
+    if (P.aux_target) {
+        mp = aux_params(P, clean_rates);
+        if (!P.aux_norm_out.empty()) return aux_norm_pass(P, clean, mp);
+    }
     const Corpus noise = flatten(read_wav_list(WHO, "noise_list", P.noise_list, nullptr, nullptr, P.rate, P.device));
     check_noise(WHO, noise);
     std::vector<bp_mixture> plan = make_plan(P.seed, (int)clean.len.size(), P.mix_per_clean, noise, P.snr);
@@ -221,7 +291,11 @@ int main(int argc, char **argv)
     if (P.traincache < 1 || P.bunchsize < 1) fail("bpmix: need traincache and bunchsize");
     if (toff >= ctx) fail("bpmix: targ_offset must be below fea_context");
     const int parts = P.target == BP_MIX_LPS_IRM || P.target == BP_MIX_LPS_IBM ? 2 : 1;
-    if (P.layersizes[L - 1] != parts * D) fail("bpmix: layersizes[last] must be " + std::to_string(parts * D) + " for this target");
+    if (P.aux_target) {
+        if (P.target != BP_MIX_LPS && parts != 2) fail("bpmix: aux_target=mfcc needs a target that begins with lps (lps, lps+irm or lps+ibm)");
+        if (P.layersizes[L - 1] != parts * D + mp.n_ceps)
+            fail("bpmix: layersizes[last] must be " + std::to_string(parts * D + mp.n_ceps) + " for this target with aux_target=mfcc (aux_ceps columns behind the LPS)");
+    } else if (P.layersizes[L - 1] != parts * D) fail("bpmix: layersizes[last] must be " + std::to_string(parts * D) + " for this target");
     if (P.layersizes[0] != ctx * D && P.layersizes[0] != (ctx + 1) * D) fail("bpmix: layersizes[0] must be fea_context*fea_dim (+ fea_dim with NAT)");
     const Corpus cv_clean = flatten(read_wav_list(WHO, "cv_clean_list", P.cv_clean_list, &cv_rates, nullptr, P.rate, P.device));
     const Corpus cv_noise = P.cv_noise_list.empty() ? noise : flatten(read_wav_list(WHO, "cv_noise_list", P.cv_noise_list, nullptr, nullptr, P.rate, P.device));
@@ -235,6 +309,12 @@ int main(int argc, char **argv)
     address_reverberant(cv_plan, cv_rv, (int)cv_clean.len.size());
     std::vector<float> mean, istd;
     read_norm(P.norm_file, D, mean, istd);
+    std::vector<float> aux_mean(mp.n_ceps, 0.f), aux_scale(mp.n_ceps, 1.f);
+    if (P.aux_target) {
+        if (!P.aux_norm_file.empty()) read_norm(P.aux_norm_file, mp.n_ceps, aux_mean, aux_scale);
+        for (float &v : aux_scale) v = (float)((double)v * sqrt((double)P.aux_weight));   // a weight on the squared error is its root on the target
+        mp.mean = aux_mean.data(); mp.scale = aux_scale.data();
+    }
 
     FILE *log = fopen(P.log_file.c_str(), "wt");
     if (!log) fail("can not open output log file: " + P.log_file);
@@ -292,6 +372,13 @@ int main(int argc, char **argv)
     bp_handle *h = create_net(cfg, wts, P.output_act, P.output_linear_dims, P.output_loss);
     printf("Created net with %d layers, bunchsize %d.\n", L, P.bunchsize);
     set_nat(WHO, h, P.nat, ctx, D, P.layersizes);
+    if (P.aux_target) {
+        check(bp_set_mix_aux(h, &mp));
+        fprintf(log, "Auxiliary target: mfcc, %d filters up to %d Hz, %d coefficients from c%d, lifter %g, weight %g: target columns [%d, %d).\n",
+                mp.n_mel, mp.sample_rate / 2, mp.n_ceps, mp.first_coef, mp.lifter, P.aux_weight, D, D + mp.n_ceps);
+        fprintf(log, "Auxiliary target: the net's linear prefix is output_linear_dims=%d (LPS and MFCC columns), given %d.\n", D + mp.n_ceps,
+                P.output_linear_dims);
+    }
     const bp_mix_corpus mc = describe(D, ctx, toff, P.target, P.lc_db, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) {

@@ -289,6 +289,54 @@ int bp_mix_plan(uint64_t seed, int n_clean, int per_clean, int n_noise, const in
 int bp_mix_shuffle(uint64_t seed, uint32_t stream, int n, int *order);
 
 /* ------------------------------------------------------------------------------------
+ * MFCC auxiliary target of the mixing corpus (multi-objective training: LPS, MFCC and a mask in one target row; no reference
+ * counterpart).  INTEGRATION.md 1p.  The signal definition of bp_enhance_waves applies unchanged; M = fea_dim - 1.
+ *
+ * Two tables, computed on the host in double and rounded to fp32 once.
+ * Filters: mel(f) = 2595 log10(1 + f/700).  Edges e_p, p = 0 .. n_mel+1: e_0 = f_lo and e_{n_mel+1} = f_hi as given, those between
+ *   them equally spaced in mel between mel(f_lo) and mel(f_hi) and mapped back to Hz.  Bin k lies at f_k = k sample_rate / (2M).
+ *   w[j][k] = max(0, min((f_k - e_j)/(e_{j+1} - e_j), (e_{j+2} - f_k)/(e_{j+2} - e_{j+1}))): triangles linear in Hz, not
+ *   area-normalised.  first_bin[j], n_bins[j]: the bins with w[j][k] > 0 (after the rounding), a contiguous run.  A filter without
+ *   such a bin is BP_ERR_ARG with a message that names it, from every call that takes the parameters together with a fea_dim.
+ * DCT: t[r][j] = lift_i sqrt(2/n_mel) cos(pi i (j + 0.5)/n_mel), i = first_coef + r, lift_i = 1 + (L/2) sin(pi i/L) for the
+ *   lifter L > 0, else 1 (HTK's).
+ * Per frame, from P[k] = |S_k|^2 in fp32, S the analysis of the signal (as the LPS target's):
+ *   E_j = sum_k (double)w[j][k] (double)P[k], k ascending from first_bin[j] over n_bins[j] bins, one double accumulator from +0.0;
+ *   e_j = fl32(E_j);  logmel_j = e_j > 1e-10f ? logf(e_j) : ln(1e-10)                 (the floor of the LPS)
+ *   c_r = fl32(sum_j (double)t[r][j] (double)logmel_j), j ascending, one double accumulator from +0.0
+ *   target_r = (c_r - mean_r) * scale_r                                               in fp32
+ * The product of two fp32 numbers is exact in double, so each step is one rounded double addition and the order is the
+ * definition: e is a function of the bits of P and w, the target one of the bits of logmel, t, mean and scale.  A weight alpha_r on
+ * the squared error of coefficient r needs nothing else: fold sqrt(alpha_r) into scale_r.
+ *
+ * bp_mel_defaults: 26 filters, 13 coefficients from c0, 0 .. sample_rate/2, L = 22, no mean / scale.
+ * bp_mel_filters / bp_mel_dct (host only): the tables; any output of bp_mel_filters may be NULL.
+ * bp_wave_mfcc (no handle, bp_wave_lps's frame plan): power [sum T][fea_dim], logmel [sum T][n_mel], mfcc [sum T][n_ceps] (mean
+ *   and scale applied); any output may be NULL, not all three.
+ * bp_set_mix_aux(h, p): p is checked and copied (NULL: off); it takes effect at the next bp_set_mix_corpus, where the tables are
+ *   made for the corpus' fea_dim and uploaded -- a corpus that is already set keeps what it was set with.  With it the corpus
+ *   target must begin with LPS (BP_MIX_LPS, _LPS_IRM, _LPS_IBM) and layersizes[L-1] must be parts*fea_dim + n_ceps: the target row
+ *   is [LPS | MFCC | mask], the MFCC columns [fea_dim, fea_dim + n_ceps) bit-identical to bp_wave_mfcc of the entry's target
+ *   signal (the early or reverberant signal of a derived entry).  Train with bp_set_output(h, 1, fea_dim +
+ *   n_ceps, loss), enhance with out_col = fea_dim + n_ceps (mask) or 0 (LPS).  Without it nothing changes.  BP_ERR_ARG with the
+ *   handle unchanged for a parameter outside the ranges below; BP_ERR_STATE on a data-parallel-attached handle. */
+typedef struct bp_mel_params {
+    int sample_rate;          /* Hz, > 0 */
+    int n_mel;                /* 2 .. 128 */
+    int n_ceps;               /* 1 .. n_mel - first_coef */
+    int first_coef;           /* 0: c0 is the first column, 1: c1 is */
+    float f_lo, f_hi;         /* 0 <= f_lo < f_hi <= sample_rate / 2 */
+    float lifter;             /* HTK's L; 0: none */
+    const float *mean, *scale;/* [n_ceps] or NULL (0 and 1): target = (c - mean) * scale */
+} bp_mel_params;
+int bp_mel_defaults(int sample_rate, bp_mel_params *p);
+int bp_mel_filters(int fea_dim, const bp_mel_params *p, float *w /* [n_mel][fea_dim] */, int *first_bin, int *n_bins /* [n_mel] */);
+int bp_mel_dct(const bp_mel_params *p, float *t /* [n_ceps][n_mel] */);
+int bp_wave_mfcc(int device, int fea_dim, const bp_mel_params *p, int n_sent, const int *sent_len, const float *pcm,
+                 float *power, float *logmel, float *mfcc);
+int bp_set_mix_aux(bp_handle *h, const bp_mel_params *p);     /* NULL: off */
+
+/* ------------------------------------------------------------------------------------
  * Reverberant entries of the mixing corpus (no reference counterpart).  INTEGRATION.md 1k.
  *
  * A room impulse response h has Lh taps, fp32 and finite, 1 <= Lh <= BP_MIX_RIR_MAX_TAPS.  Its delay d is the first index at
