@@ -47,11 +47,16 @@ ABI_SYMBOLS = [
     "bp_noise_defaults", "bp_logmmse_waves_nt", "bp_eval_mix_logmmse_nt", "bp_lmstream_open_nt", "bp_set_nat",
     "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
     "bp_mel_defaults", "bp_mel_filters", "bp_mel_dct", "bp_wave_mfcc", "bp_set_mix_aux",
+    "bp_post_defaults", "bp_set_post", "bp_post_rows", "bp_gv_mix", "bp_gv_factors",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
 NAT_STATIC, NAT_DYNAMIC = 0, 1           # bp_set_nat
 NAT_MODES = {"static": NAT_STATIC, "dynamic": NAT_DYNAMIC}
+GV_RAW, GV_POST = 0, 1                   # bp_gv_mix: stage
+GV_STAGES = {"raw": GV_RAW, "post": GV_POST}
+GV_INDEP, GV_DEP = 0, 1                  # bp_gv_factors: mode
+GV_MODES = {"indep": GV_INDEP, "dep": GV_DEP}
 MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_corpus.target
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
 SCORE_ESTOI, SCORE_SISDR = 3, 4               # the two further columns of the _ext calls (extended=True)
@@ -160,6 +165,15 @@ class BPMelParams(C.Structure):
         ("sample_rate", C.c_int), ("n_mel", C.c_int), ("n_ceps", C.c_int), ("first_coef", C.c_int),
         ("f_lo", C.c_float), ("f_hi", C.c_float), ("lifter", C.c_float),
         ("mean", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
+    ]
+
+
+class BPPostParams(C.Structure):
+    """bp_post_params (include/bp_c_api.h): post-processing of the LPS estimate.  gv_center / gv_scale point into arrays the owner
+    keeps alive (post_params stores them on the object)."""
+    _fields_ = [
+        ("gv", C.c_int), ("gv_center", C.POINTER(C.c_float)), ("gv_scale", C.POINTER(C.c_float)),
+        ("mask_col", C.c_int), ("mask_lo", C.c_float), ("mask_hi", C.c_float), ("mask_weight", C.c_float),
     ]
 
 
@@ -273,6 +287,11 @@ def load_library(path=None):
     lib.bp_wave_mfcc.argtypes = [C.c_int, C.c_int, C.POINTER(BPMelParams), C.c_int, ip, fp, fp, fp, fp]
     lib.bp_set_mix_aux.argtypes = [hp, C.POINTER(BPMelParams)]
     lib.bp_stream_packed.argtypes = [C.c_void_p]
+    lib.bp_post_defaults.argtypes = [C.POINTER(BPPostParams)]
+    lib.bp_set_post.argtypes = [hp, C.c_int, C.POINTER(BPPostParams)]
+    lib.bp_post_rows.argtypes = [C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(BPPostParams), fp]
+    lib.bp_gv_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    lib.bp_gv_factors.argtypes = [C.c_int, C.c_int64, dp, dp, dp, dp, C.c_int, fp, fp]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.bp_dp_peer_info.argtypes = [hp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -430,6 +449,48 @@ class BP_GPU(object):
         """"static" or "dynamic": what set_nat (or nat_mode= at construction) set last."""
         return self._nat_mode
 
+    def set_post(self, gv_center=None, gv_scale=None, mask_col=-1, mask_lo=0.5, mask_hi=0.5, mask_weight=1.0, fea_dim=None):
+        """Post-processing of the LPS estimate before resynthesis (bp_set_post): GV equalisation x = c + s (x - c) with gv_center and
+        gv_scale (what gv_factors returns), then the mask gate -- the noisy LPS blended in where the mask columns from mask_col on say
+        that speech dominates.  enhance_waves and eval_mix from the next call on, and the streams opened from now on.  set_post(None),
+        or no argument at all, switches it off.  fea_dim: needed only for gating without GV (default: the corpus's)."""
+        if gv_center is None and gv_scale is None and int(mask_col) < 0:
+            self._check(self._lib.bp_set_post(self._h, 0, None))
+            self._post = False
+            return
+        try:
+            p = post_params(gv_center, gv_scale, mask_col, mask_lo, mask_hi, mask_weight)
+        except BPError as e:
+            self._fail(str(e))
+        D = p._center.size if p.gv else fea_dim if fea_dim is not None else getattr(self, "mix_fea_dim", None)
+        if D is None:
+            self._fail("set_post: fea_dim is needed for gating without GV on a handle without a corpus")
+        self._check(self._lib.bp_set_post(self._h, int(D), C.byref(p)))
+        self._post = True
+
+    @property
+    def post(self):
+        """True while post-processing is on (set_post)."""
+        return getattr(self, "_post", False)
+
+    def gv_mix(self, plan, out_col=0, stage="raw"):
+        """bp_gv_mix: the second moments the GV factors are made from, over the plan's mixtures: dict of est_sum, est_sq, ref_sum,
+        ref_sq (float64 [fea_dim]) and frames.  stage "raw": the net's columns from out_col on; "post": the rows that are
+        resynthesised (set_post).  Across plans the caller adds the sums; gv_factors takes the dict."""
+        if stage not in GV_STAGES:
+            self._fail("gv_mix: stage must be \"raw\" or \"post\", not %r" % (stage,))
+        p, pp = self._plan(plan)
+        self._push_hyper()
+        D = getattr(self, "mix_fea_dim", None) or 1
+        out = {k: np.zeros(D, np.float64) for k in ("est_sum", "est_sq", "ref_sum", "ref_sq")}
+        n = C.c_int64(0)
+        dpt = C.POINTER(C.c_double)
+        self._check(self._lib.bp_gv_mix(self._h, p.size, pp, int(out_col), GV_STAGES[stage], out["est_sum"].ctypes.data_as(dpt),
+                                        out["est_sq"].ctypes.data_as(dpt), out["ref_sum"].ctypes.data_as(dpt),
+                                        out["ref_sq"].ctypes.data_as(dpt), C.byref(n)))
+        out["frames"] = int(n.value)
+        return out
+
     def set_mix_aux(self, mel):
         """The MFCC auxiliary target of the mixing corpus (bp_set_mix_aux): what mel_params makes, or None for none.  From the next
         set_mix_corpus on -- its target must then begin with LPS and layersizes[-1] be parts * fea_dim + n_ceps; the target row is
@@ -568,7 +629,7 @@ class BP_GPU(object):
         s = C.c_void_p()
         self._check(self._lib.bp_stream_open(self._h, C.byref(c), C.byref(s)))
         return Stream(self, s, mean.size, int(context), int(targ_offset), int(n_chan), bool(self._lib.bp_stream_packed(s)),
-                      self._nat_mode)
+                      self._nat_mode, self.post)
 
     # ---- training mixtures made on the device (bp_set_mix_corpus ...; definition: include/bp_c_api.h)
     def set_mix_corpus(self, clean, noise, mean, inv_std, context, targ_offset, target=MIX_LPS, lc_db=5.0):
@@ -876,8 +937,8 @@ def _counts3(fn, *args):
 class Stream(object):
     """A streaming session (bp_stream_*): n_chan live feeds enhanced in blocks of any sizes."""
 
-    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan, packed=False, nat_mode="static"):
-        self._g, self._s, self._packed, self._nat_mode = owner, s, bool(packed), nat_mode
+    def __init__(self, owner, s, fea_dim, context, targ_offset, n_chan, packed=False, nat_mode="static", post=False):
+        self._g, self._s, self._packed, self._nat_mode, self._post = owner, s, bool(packed), nat_mode, bool(post)
         self.fea_dim, self.context, self.targ_offset, self.n_chan = fea_dim, context, targ_offset, n_chan
         self.look_ahead = context - 1 - targ_offset
 
@@ -892,6 +953,11 @@ class Stream(object):
         """"static" or "dynamic": the noise-aware block the stream stages -- its handle's mode (set_nat) when it was opened,
         whatever the handle's mode is by then."""
         return self._nat_mode
+
+    @property
+    def post(self):
+        """True for a stream opened with post-processing on (set_post): it keeps the parameters its handle had then."""
+        return self._post
 
     def push(self, blocks, end=None, out_cap=None):
         """blocks: one 1-D array of new samples per channel (None or empty: none); end: per channel, true closes the channel's
@@ -940,6 +1006,60 @@ def wave_lps(device, fea_dim, sentences):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return np.split(out[:int(frames.sum())], np.cumsum(frames)[:-1])
+
+
+def post_params(gv_center=None, gv_scale=None, mask_col=-1, mask_lo=0.5, mask_hi=0.5, mask_weight=1.0):
+    """A BPPostParams over bp_post_defaults: GV on when gv_center and gv_scale are given (both or neither)."""
+    lib = load_library()
+    p = BPPostParams()
+    lib.bp_post_defaults(C.byref(p))
+    if (gv_center is None) != (gv_scale is None):
+        raise BPError("post_params: gv_center and gv_scale come together")
+    if gv_center is not None:
+        p._center = np.ascontiguousarray(gv_center, dtype=np.float32).reshape(-1)
+        p._scale = np.ascontiguousarray(gv_scale, dtype=np.float32).reshape(-1)
+        if p._center.size != p._scale.size:
+            raise BPError("post_params: gv_center and gv_scale differ in length")
+        p.gv, p.gv_center, p.gv_scale = 1, _fp(p._center), _fp(p._scale)
+    p.mask_col, p.mask_lo, p.mask_hi, p.mask_weight = int(mask_col), float(mask_lo), float(mask_hi), float(mask_weight)
+    return p
+
+
+def post_rows(device, est, noisy_lps, mask=None, gv_center=None, gv_scale=None, mask_lo=0.5, mask_hi=0.5, mask_weight=1.0):
+    """bp_post_rows: the post-processed value over rows [n_frames][fea_dim] (no handle): GV with gv_center / gv_scale when given,
+    the gate when a mask block is given."""
+    lib = load_library()
+    est = np.ascontiguousarray(est, dtype=np.float32)
+    y = np.ascontiguousarray(noisy_lps, dtype=np.float32)
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+    if est.ndim != 2 or y.shape != est.shape or (m is not None and m.shape != est.shape):
+        raise BPError("post_rows: est, noisy_lps and mask must be [n_frames][fea_dim] arrays of one shape")
+    p = post_params(gv_center, gv_scale, 0 if m is not None else -1, mask_lo, mask_hi, mask_weight)
+    if p.gv and p._center.size != est.shape[1]:
+        raise BPError("post_rows: gv_center and gv_scale must have fea_dim entries")
+    out = np.empty(est.shape if est.size else (1, 1), np.float32)
+    rc = lib.bp_post_rows(int(device), est.shape[1], est.shape[0], _fp(est), None if m is None else _fp(m), _fp(y), C.byref(p), _fp(out))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return out
+
+
+def gv_factors(stats, mode="indep"):
+    """bp_gv_factors (host only): (center, scale), float32 [fea_dim], from the sums of gv_mix (a dict; sums of several calls added
+    by the caller).  mode "indep": one factor for all bins, "dep": one per bin."""
+    lib = load_library()
+    if mode not in GV_MODES:
+        raise BPError("gv_factors: mode must be \"indep\" or \"dep\", not %r" % (mode,))
+    s = [np.ascontiguousarray(stats[k], dtype=np.float64).reshape(-1) for k in ("est_sum", "est_sq", "ref_sum", "ref_sq")]
+    D = s[0].size
+    if any(a.size != D for a in s):
+        raise BPError("gv_factors: the four sums differ in length")
+    center, scale = np.empty(max(D, 1), np.float32), np.empty(max(D, 1), np.float32)
+    dpt = C.POINTER(C.c_double)
+    rc = lib.bp_gv_factors(D, int(stats["frames"]), *[a.ctypes.data_as(dpt) for a in s], GV_MODES[mode], _fp(center), _fp(scale))
+    if rc != 0:
+        raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
+    return center[:D], scale[:D]
 
 
 def mel_params(sample_rate, **fields):

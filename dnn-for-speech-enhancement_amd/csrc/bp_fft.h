@@ -84,17 +84,64 @@ __device__ __forceinline__ float2 rfft_bin(const float2 *z, const float2 *__rest
 // the LPS of one bin's power, with the 1e-10 floor
 __device__ __forceinline__ float lps_of(float p) { return p > 1e-10f ? logf(p) : LN_FLOOR; }
 
+// The power of one noisy bin as bp_wave_analysis forms it (there the compiler multiplies the pair with one packed multiply and adds:
+// two squares, each rounded, and their rounded sum; spelled out, uncontracted, for the code that makes the noisy LPS again from the
+// stored spectrum, so that it returns those bits wherever it sits)
+__device__ __forceinline__ float power_of(float2 X)
+{
+#pragma clang fp contract(off)
+    const float a = X.x * X.x, b = X.y * X.y;
+    return a + b;
+}
+
+// One post-processed value (bp_set_post; include/bp_c_api.h): x the LPS estimate, m the mask estimate (read
+// only with the gate), y the noisy LPS, k the bin.  GV equalisation, then the gate; every step one fp32 operation, rounded once.
+__device__ __forceinline__ float post_value(const PostP &p, float x, float m, float y, int k)
+{
+#pragma clang fp contract(off)
+    if (p.gv) {
+        const float c = p.c[k], d = x - c, t = p.s[k] * d;
+        x = c + t;
+    }
+    if (p.gate) {
+        float u;
+        if (p.hi > p.lo) {
+            u = (m - p.lo) * p.inv;
+            u = u > 0.0f ? (u < 1.0f ? u : 1.0f) : 0.0f;         // (a NaN mask: 0)
+        } else
+            u = m >= p.hi ? 1.0f : 0.0f;
+        const float w = p.weight * u, e = y - x, q = w * e;
+        x = x + q;
+    }
+    return x;
+}
+
+// What synth_frame takes for ok = o[k]: the net's column itself, or the post-processed value of it, of the mask column moff columns
+// further on and of the noisy LPS made from Y[k]
+struct NoPost {
+    __device__ __forceinline__ float operator()(float ok, const float *, int, float2) const { return ok; }
+};
+struct PostFn {
+    PostP p; int moff;
+    __device__ __forceinline__ float operator()(float ok, const float *__restrict__ o, int k, float2 y) const
+    {
+        return post_value(p, ok, p.gate ? o[moff + k] : 0.0f, lps_of(power_of(y)), k);
+    }
+};
+
 // Synthesis of one frame (bp_wave_synthesis, bp_stream_synthesis): S from the net outputs o[0 .. M] and the noisy spectrum
 // Y[0 .. M], inverse real FFT, times the window -> fr[0 .. 2M) (16-byte aligned; global or LDS).  z: lds_bytes(M) of FFT space
-// followed by M + 1 float2 for S.  Every thread of the workgroup calls it; no barrier behind the stores to fr.
+// followed by M + 1 float2 for S.  Every thread of the workgroup calls it; no barrier behind the stores to fr.  post: what stands
+// for o[k] (NoPost: o[k]).
+template <class Post = NoPost>
 __device__ __forceinline__ void synth_frame(float2 *z, const float *__restrict__ o, const float2 *__restrict__ Y, const float *__restrict__ win,
-                                            const float2 *__restrict__ tw, int log2M, int target, float *fr)
+                                            const float2 *__restrict__ tw, int log2M, int target, float *fr, const Post post = Post())
 {
     const int M = 1 << log2M, N = 2 * M, tid = threadIdx.x;
     float2 *S = z + lds_bytes(M) / sizeof(float2);      // S[0 .. M], unpadded (read twice below, written once)
     for (int k = tid; k <= M; k += blockDim.x) {
         const float2 y = Y[k];
-        const float ok = o[k];
+        const float ok = post(o[k], o, k, y);
         float2 v;
         if (target == BP_WAVE_MASK) v = make_float2(ok * y.x, ok * y.y);
         else {
@@ -202,8 +249,16 @@ hipError_t wave_dnat_launch(const NoiseP &np, const float2 *Y, const int *F, int
 // The noise-aware block of a staging call on h (bp_set_nat): *dyn = one tracked row per frame.  BP_ERR_ARG in the caller's name when
 // the handle is in BP_NAT_DYNAMIC and the net has no block (nat == false).
 int wave_nat_mode(const char *who, const bp_handle *h, bool nat, bool *dyn);
-// synthesis of `frames` frames from the net outputs out[frames][ldo] (columns [out_col, out_col + D)) and Y -> syn[frames][n_fft]
+// synthesis of `frames` frames from the net outputs out[frames][ldo] (columns [out_col, out_col + D)) and Y -> syn[frames][n_fft];
+// post: from the post-processed value of those columns (bp_set_post), or null
 hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
-                                 int D, int target, float *syn, int frames, hipStream_t st);
+                                 int D, int target, float *syn, int frames, hipStream_t st, const PostP *post = nullptr);
+// The post-processing of a call that resynthesises with h's net (bp_set_post): BP_OK while it is off; on, BP_ERR_ARG in the caller's
+// name when the call's fea_dim is not the one that was set or its target is BP_WAVE_MASK
+int wave_post_check(const char *who, const bp_handle *h, int fea_dim, int target);
+// the sums of bp_gv_mix (include/bp_c_api.h) over n frames: e from out (post: post-processed with Y's noisy LPS) and r from ref
+// [n][D], through h->gv_parts; sums: 4 D doubles on the device (est_sum | est_sq | ref_sum | ref_sq)
+hipError_t wave_gv_launch(bp_handle *h, const float *out, int ldo, int out_col, const float2 *Y, const float *ref, int D, int n,
+                          const PostP *post, hipStream_t st);
 // overlap-add of those frames into the padded layout (segment 0 and segment T of every sentence are not written)
 hipError_t wave_overlap_launch(const float *syn, const float *win, const int *F, int n_sent, int hop, float *pcm, int frames, hipStream_t st);

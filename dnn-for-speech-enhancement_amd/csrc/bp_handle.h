@@ -65,6 +65,12 @@ struct MelP {
     float mean[MEL_MAX], scale[MEL_MAX];
 };
 
+// Checked post-processing parameters (bp_set_post; post_check, bp_wave.hip) as the kernels take them: gate = mask_col >= 0,
+// inv = (float)(1 / (hi - lo)) made in double (hi > lo), c / s the centre and the scale on the device (read when gv)
+constexpr int POST_MAX_D = 1025;                                 // the largest fea_dim
+constexpr int GV_PARTS = 64;                                     // parts of a bp_gv_mix sum
+struct PostP { int gv, gate, mask_col; float lo, hi, inv, weight; const float *c, *s; };
+
 struct bp_handle {
     bp_config cfg;
     int L;                       // number of layer sizes
@@ -119,6 +125,12 @@ struct bp_handle {
     // bp_set_mix_aux (bp_mix.hip, bp_mel.h): the MFCC auxiliary target the next bp_set_mix_corpus is set with (checked parameters, or
     // aux_on) and the device block its tables go to, allocated once at the parameter limits
     bool aux_on; MelP aux; float *aux_tab;
+    // bp_set_post (bp_wave.hip): post-processing of the LPS estimate in the calls that resynthesise (post_on: for this fea_dim, with
+    // these parameters); post_tab: the device block of centre | scale, POST_MAX_D floats each, made by the first call that turns it on
+    bool post_on; int post_D; PostP post; float *post_tab;
+    // bp_gv_mix (bp_mix.hip): the part sums [GV_PARTS][4][POST_MAX_D] and behind them the totals [4][POST_MAX_D], in double; made
+    // on first use
+    float *gv_parts;
     // bp_stream_open (bp_stream.hip): the open streaming sessions of this handle
     std::vector<struct bp_stream *> streams;
 };

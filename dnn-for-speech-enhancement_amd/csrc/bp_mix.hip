@@ -749,35 +749,42 @@ extern "C" int bp_mix_features(bp_handle *h, int n_mix, const bp_mixture *m, flo
 }
 
 // bp_eval_mix (lm == null: the net's output columns [out_col, out_col + D) as `target`) and bp_eval_mix_logmmse (lm: the checked
-// parameters; the gain rows of the recursion as BP_WAVE_MASK): one sequence, one enhancer swapped for the other
+// parameters; the gain rows of the recursion as BP_WAVE_MASK): one sequence, one enhancer swapped for the other.  bp_gv_mix (gv:
+// where its sums go) is the same generate -> adopt -> forward with the net; then, in place of resynthesis and scoring, the LPS of
+// the clean signal and the sums over the net's columns (gv->post: over their post-processed values).
+struct GvOut { bool post; double *sums[4]; };
 static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const NoiseP &nz, const Call &c, const bp_mixture *m, int sample_rate, int target,
-                        int out_col, int NS, float *noisy_scores, float *enh_scores, float *enh_pcm)
+                        int out_col, int NS, float *noisy_scores, float *enh_scores, float *enh_pcm, const GvOut *gv = nullptr)
 {
     int r;
     const int n_mix = c.n;
     MixState *ms = h->mix;
     const int D = ms->D, L = h->L, n = (int)c.frames, hop = ms->hop;
-    if (!noisy_scores || !enh_scores) return fail(BP_ERR_ARG, std::string(who) + ": null scores");
+    if (!gv && (!noisy_scores || !enh_scores)) return fail(BP_ERR_ARG, std::string(who) + ": null scores");
     std::vector<int> len(n_mix);
     std::vector<int64_t> off(n_mix);
     for (int i = 0; i < n_mix; ++i) { len[i] = (int)ms->clean_len[m[i].clean]; off[i] = ((int64_t)c.Fs[i] + 1) * hop; }
     EvalPlan ep;
-    if ((r = eval_plan(who, sample_rate, D, NS, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
+    if (!gv && (r = eval_plan(who, sample_rate, D, NS, n_mix, len.data(), off.data(), c.F.data(), ep)) != BP_OK) return r;
     HIPCHK(hipSetDevice(h->cfg.device));
-    // every buffer first (a growth waits for the stream), then the sequence without a host wait
-    const size_t pcm_b = c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = (size_t)2 * n_mix * NS * 4;
-    r = wave_grow(h, {{ms->ev_Y, c.frames * D * sizeof(float2), false}, {ms->ev_syn, c.frames * 2 * hop * 4, false}, {ms->ev_ola, pcm_b, false},
-                      {ms->ev_lps, 2 * lps_b, false}, {ms->ev_tab, ep.t_bytes + sc_b, false}, {ms->ev_work, eval_work_bytes(ep, 3), false},
-                      {ms->ev_pin, ep.t_bytes, true}, {ms->lps, c.frames * D * 4, false},
+    if (gv && !h->gv_parts && (r = dev_alloc(h, &h->gv_parts, (size_t)(GV_PARTS + 1) * 4 * POST_MAX_D * 2)) != BP_OK) return r;
+    // every buffer first (a growth waits for the stream), then the sequence without a host wait (gv: Y and the clean LPS alone)
+    const size_t pcm_b = gv ? 0 : c.segs * hop * 4, lps_b = al256(c.frames * D * 4), sc_b = gv ? 0 : (size_t)2 * n_mix * NS * 4;
+    const size_t tab_b = gv ? 0 : ep.t_bytes;
+    r = wave_grow(h, {{ms->ev_Y, c.frames * D * sizeof(float2), false}, {ms->ev_syn, gv ? 0 : c.frames * 2 * hop * 4, false}, {ms->ev_ola, pcm_b, false},
+                      {ms->ev_lps, gv ? lps_b : 2 * lps_b, false}, {ms->ev_tab, tab_b + sc_b, false}, {ms->ev_work, gv ? 0 : eval_work_bytes(ep, 3), false},
+                      {ms->ev_pin, tab_b, true}, {ms->lps, gv ? 0 : c.frames * D * 4, false},
                       {ms->ev_gain, lm ? c.frames * ((size_t)D + 1) * 4 : 0, false}});
     if (r != BP_OK) return r;
     if (!lm && (r = out_chunk_reserve(h, n)) != BP_OK) return r;
     // the table block: the pinned buffer is free (the previous call ended in a synchronisation)
     char *tab = (char *)ms->ev_tab.p;
-    eval_fill(ep, (char *)ms->ev_pin.p);
-    HIPCHK(hipMemcpyAsync(tab, ms->ev_pin.p, ep.t_bytes, hipMemcpyHostToDevice, h->stream));
+    if (!gv) {
+        eval_fill(ep, (char *)ms->ev_pin.p);
+        HIPCHK(hipMemcpyAsync(tab, ms->ev_pin.p, ep.t_bytes, hipMemcpyHostToDevice, h->stream));
+    }
     float2 *Y = (float2 *)ms->ev_Y.p;
-    if ((r = generate(h, c, m, nullptr, true, nullptr, nullptr, nullptr, Y, false)) != BP_OK) return r;
+    if ((r = generate(h, c, m, nullptr, !gv, nullptr, nullptr, nullptr, Y, false)) != BP_OK) return r;
     if ((r = window_adopt(h, n, D, ms->ctx, ms->nat, false)) != BP_OK) return r;
     if (!lm && (r = forward_resident(h, n)) != BP_OK) return r;
     const char *cp = ms->corpus.as<char>();
@@ -785,12 +792,25 @@ static int eval_mix_run(const char *who, bp_handle *h, const LogmmseP *lm, const
     const float2 *tw = (const float2 *)(cp + ms->o_tw);
     const int *F = (const int *)((const char *)ms->in_d.p + c.o_F);
     float *ola = (float *)ms->ev_ola.p, *lps_s = (float *)ms->ev_lps.p, *lps_e = (float *)((char *)ms->ev_lps.p + lps_b);
+    if (gv) {
+        WaveAnaArgs w; memset(&w, 0, sizeof(w));                   // the LPS of s, as the scoring below analyses it for LSD
+        w.pcm = (const float *)ms->s.p; w.win = win; w.tw = tw; w.F = F;
+        w.n_sent = n_mix; w.log2M = ms->log2M; w.D = D; w.hop = hop; w.ctx = 1; w.lps = lps_s;
+        HIPCHK(wave_analysis_launch(w, n, h->stream));
+        HIPCHK(wave_gv_launch(h, h->out_chunk.as<float>(), h->ld[L - 1], out_col, Y, lps_s, D, n, gv->post ? &h->post : nullptr, h->stream));
+        const double *tot = reinterpret_cast<const double *>(h->gv_parts) + (size_t)GV_PARTS * 4 * D;
+        for (int k = 0; k < 4; ++k)
+            HIPCHK(hipMemcpyAsync(gv->sums[k], tot + (size_t)k * D, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return BP_OK;
+    }
     if (lm) {
         float *gain = (float *)ms->ev_gain.p;
         HIPCHK(logmmse_gain_launch(*lm, nz, Y, F, n_mix, D, gain, gain + c.frames * D, nullptr, h->stream));
         HIPCHK(wave_synthesis_launch(gain, D, 0, Y, win, tw, ms->log2M, D, BP_WAVE_MASK, (float *)ms->ev_syn.p, n, h->stream));
     } else
-        HIPCHK(wave_synthesis_launch(h->out_chunk.as<float>(), h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream));
+        HIPCHK(wave_synthesis_launch(h->out_chunk.as<float>(), h->ld[L - 1], out_col, Y, win, tw, ms->log2M, D, target, (float *)ms->ev_syn.p, n, h->stream,
+                                     h->post_on ? &h->post : nullptr));
     HIPCHK(wave_overlap_launch((const float *)ms->ev_syn.p, win, F, n_mix, hop, ola, n, h->stream));
     HIPCHK(eval_trim_launch(ep, tab, hop, ola, h->stream));        // = the enhanced sentences in bp_score_waves' padded layout
     for (int k = 0; k < 2; ++k) {                                  // the LPS of s and of the enhanced samples (x's: generate)
@@ -832,8 +852,28 @@ static int eval_mix_net(const char *who, bp_handle *h, int n_mix, const bp_mixtu
     if (target != BP_WAVE_LPS && target != BP_WAVE_MASK) return fail(BP_ERR_ARG, std::string(who) + ": target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, std::string(who) + ": out_col + fea_dim exceeds layersizes[last]");
     bool dyn;
-    if ((r = wave_nat_mode(who, h, h->mix->nat, &dyn)) != BP_OK) return r;
+    if ((r = wave_nat_mode(who, h, h->mix->nat, &dyn)) != BP_OK || (r = wave_post_check(who, h, D, target)) != BP_OK) return r;
     return eval_mix_run(who, h, nullptr, noise_vad(), c, m, sample_rate, target, out_col, n_scores, noisy_scores, enh_scores, enh_pcm);
+}
+
+// The second moments of the GV factors over the mixtures of a plan (include/bp_c_api.h): a mode of eval_mix_run
+extern "C" int bp_gv_mix(bp_handle *h, int n_mix, const bp_mixture *m, int out_col, int stage, double *est_sum, double *est_sq, double *ref_sum,
+                         double *ref_sq, int64_t *frames)
+{
+    Call c;
+    int r;
+    if ((r = plan_call(h, "bp_gv_mix", n_mix, m, c)) != BP_OK) return r;
+    const int D = h->mix->D, sL = h->s[h->L - 1];
+    if (stage != BP_GV_RAW && stage != BP_GV_POST) return fail(BP_ERR_ARG, "bp_gv_mix: stage must be BP_GV_RAW or BP_GV_POST");
+    if (out_col < 0 || (long)out_col + D > sL) return fail(BP_ERR_ARG, "bp_gv_mix: out_col + fea_dim exceeds layersizes[last]");
+    if (!est_sum || !est_sq || !ref_sum || !ref_sq || !frames) return fail(BP_ERR_ARG, "bp_gv_mix: null output");
+    bool dyn;
+    if ((r = wave_nat_mode("bp_gv_mix", h, h->mix->nat, &dyn)) != BP_OK) return r;
+    const GvOut gv = {stage == BP_GV_POST && h->post_on, {est_sum, est_sq, ref_sum, ref_sq}};
+    if (gv.post && (r = wave_post_check("bp_gv_mix", h, D, BP_WAVE_LPS)) != BP_OK) return r;
+    if ((r = eval_mix_run("bp_gv_mix", h, nullptr, noise_vad(), c, m, 0, BP_WAVE_LPS, out_col, 0, nullptr, nullptr, nullptr, &gv)) != BP_OK) return r;
+    *frames = (int64_t)c.frames;
+    return BP_OK;
 }
 
 // bp_eval_mix_logmmse (n_scores = BP_SCORE_N), bp_eval_mix_logmmse_ext and (nt: the noise update of np; else the VAD-gated one

@@ -177,17 +177,19 @@ struct StreamSynArgs {
 };
 }  // namespace
 
-__global__ __launch_bounds__(WAVE_THREADS) void bp_stream_synthesis(const StreamSynArgs a)
+// (Post: NoPost, or PostFn for a stream opened with post-processing on, bp_set_post)
+template <class Post>
+__global__ __launch_bounds__(WAVE_THREADS) void bp_stream_synthesis(const StreamSynArgs a, const Post post)
 {
     extern __shared__ __align__(16) float2 zs[];
     float2 *z = zs;
     const SynJob j = a.jobs[blockIdx.x];
     const int M = 1 << a.log2M, N = 2 * M, hop = M;
     float *cur = reinterpret_cast<float *>(zs) + syn_frames_at(M), *prev = cur + N;   // two frames behind synth_frame's space
-    synth_frame(z, a.out + (size_t)j.g * a.ldo + a.out_col, a.Y + (size_t)j.y * a.D, a.win, a.tw, a.log2M, a.target, cur);
+    synth_frame(z, a.out + (size_t)j.g * a.ldo + a.out_col, a.Y + (size_t)j.y * a.D, a.win, a.tw, a.log2M, a.target, cur, post);
     __syncthreads();
     if (j.prev == 0) {
-        synth_frame(z, a.out + (size_t)(j.g - 1) * a.ldo + a.out_col, a.Y + (size_t)(j.y - 1) * a.D, a.win, a.tw, a.log2M, a.target, prev);
+        synth_frame(z, a.out + (size_t)(j.g - 1) * a.ldo + a.out_col, a.Y + (size_t)(j.y - 1) * a.D, a.win, a.tw, a.log2M, a.target, prev, post);
         __syncthreads();
     }
     if (j.prev >= 0) {
@@ -217,12 +219,13 @@ struct bp_stream {
     bool nat;
     bool dyn; NoiseP nat_np;     // opened in BP_NAT_DYNAMIC (bp_set_nat): one tracked noise-aware row per frame, with these parameters
     bool packed;                 // opened in BP_FORWARD_ROWINV: dense placement, the row-invariant forward on every push
+    bool post; PostP pp;         // opened with post-processing on (bp_set_post): its parameters, centre and scale in a part of the stream's block
     std::vector<Chan> ch;
     std::vector<ChanPlan> plan;
     std::vector<AnaJob> ana; std::vector<NatJob> natj; std::vector<DnatJob> dnatj; std::vector<SynJob> syn;
     size_t max_enh;              // samples (frames to enhance) of one push at most
     StreamBlocks blk;            // device: consts | state | input block | Y of the push | output samples
-    size_t o_mean, o_istd, o_win, o_tw, o_rows, o_Y, o_nat, o_half, o_lam, o_pb, o_in, o_pY, o_out, in_cap;
+    size_t o_mean, o_istd, o_win, o_tw, o_post, o_rows, o_Y, o_nat, o_half, o_lam, o_pb, o_in, o_pY, o_out, in_cap;
 };
 
 void stream_free_all(bp_handle *h)
@@ -262,6 +265,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     { const int r = wave_nat_mode("bp_stream_open", h, nat, &dyn); if (r != BP_OK) return r; }
     if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_stream_open: target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_stream_open: out_col + fea_dim exceeds layersizes[last]");
+    { const int r = wave_post_check("bp_stream_open", h, D, c->target); if (r != BP_OK) return r; }
     if (c->n_chan < 1 || c->n_chan > (1 << 16)) return fail(BP_ERR_ARG, "bp_stream_open: n_chan must be in 1 .. 65536");
     if (c->max_push_samples < 1) return fail(BP_ERR_ARG, "bp_stream_open: max_push_samples must be >= 1");
     if (h->dp) return fail(BP_ERR_STATE, "bp_stream_open: not on an attached data-parallel handle");
@@ -272,6 +276,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     s->out_col = c->out_col; s->n_chan = c->n_chan; s->max_push = c->max_push_samples; s->hop = D - 1; s->log2M = wave_log2_fft(D);
     s->R = ctx + 6; s->nat = nat; s->warm = nat ? 6 : 0; s->packed = h->fwd_mode == BP_FORWARD_ROWINV;
     s->dyn = dyn; s->nat_np = h->nat_np;                         // the stream's from now on, as the forward's mode is
+    s->post = h->post_on; s->pp = h->post;                       // ... and so is the post-processing (the arrays: copied below)
     const int hop = s->hop, N = 2 * hop, nc = s->n_chan;
     // A push analyses at most n_in/hop + 3 frames per channel (the end of a sentence adds up to 3) and enhances those plus the
     // frames that waited; it can never enhance more than the chunk capacity lets it stage.
@@ -288,6 +293,7 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     s->o_istd = lay.take((size_t)D * 4);
     s->o_win = lay.take((size_t)N * 4);
     s->o_tw = lay.take((size_t)(hop + 1) * 8);
+    s->o_post = lay.take(s->post ? 2 * (size_t)D * 4 : 0);      // centre | scale
     s->o_rows = lay.take(slots * D * 4);
     s->o_Y = lay.take(slots * D * 8);
     s->o_nat = lay.take((size_t)nc * D * 4);
@@ -307,7 +313,12 @@ extern "C" int bp_stream_open(bp_handle *h, const bp_stream_config *c, bp_stream
     memcpy(pin + s->o_mean, c->mean, (size_t)D * 4);
     memcpy(pin + s->o_istd, c->inv_std, (size_t)D * 4);
     wave_window_twiddles(s->log2M, (float *)(pin + s->o_win), (float2 *)(pin + s->o_tw));
+    if (s->post) { s->pp.c = (const float *)(s->blk.dev.as<char>() + s->o_post); s->pp.s = s->pp.c + D; }
     e = s->blk.upload_consts(consts, s->o_in, h->stream);
+    if (e == hipSuccess && s->post && s->pp.gv) {                // centre and scale: device to device, from the handle's block
+        e = hipMemcpyAsync((void *)s->pp.c, h->post.c, (size_t)D * 4, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((void *)s->pp.s, h->post.s, (size_t)D * 4, hipMemcpyDeviceToDevice, h->stream);
+    }
     if (e != hipSuccess) { delete s; return fail(BP_ERR_DEVICE, std::string("bp_stream_open: ") + hipGetErrorString(e)); }
     s->ch.assign(nc, Chan{0, 0, Carry((size_t)2 * hop, hop)});
     s->plan.resize(nc);
@@ -489,7 +500,8 @@ extern "C" int bp_stream_push(bp_stream *s, const int *n_in, const float *pcm, c
         a.Y = Y; a.win = win; a.tw = tw; a.log2M = s->log2M; a.D = D; a.target = s->target;
         a.half = (float *)(dev + s->o_half); a.pcm = (float *)(dev + s->o_out);
         const size_t lds = (syn_frames_at(hop) + (size_t)4 * hop) * sizeof(float);
-        hipLaunchKernelGGL(bp_stream_synthesis, dim3((unsigned)n_enh), dim3(WAVE_THREADS), lds, h->stream, a);
+        if (s->post) hipLaunchKernelGGL(bp_stream_synthesis<PostFn>, dim3((unsigned)n_enh), dim3(WAVE_THREADS), lds, h->stream, a, PostFn{s->pp, s->pp.mask_col - s->out_col});
+        else hipLaunchKernelGGL(bp_stream_synthesis<NoPost>, dim3((unsigned)n_enh), dim3(WAVE_THREADS), lds, h->stream, a, NoPost());
         HIPCHK(hipGetLastError());
     }
     HIPCHK(s->blk.copy_back(s->o_out, due, out_pcm, h->stream));

@@ -22,6 +22,8 @@
 //                      atomics, the same bits on every run)
 //   bp_wave_resample   rational sample-rate conversion (bp_resample_waves, bp_resample.h): per output sample one lane's serial sum
 //                      in double over its polyphase taps, the workgroup's input span staged in LDS where it fits
+//   bp_wave_synthesis<PostFn>  the same from the post-processed value of the net's column (bp_set_post, bp_fft.h: post_value)
+//   bp_wave_post_rows  that value over caller rows (bp_post_rows); bp_wave_gv_parts / bp_wave_gv_total: the ordered double sums of bp_gv_mix
 //   bp_wave_mel        the MFCC auxiliary target (bp_wave_mfcc, bp_set_mix_aux; bp_mel.h): per frame |S|^2 in LDS, one
 //                      lane's serial sum in double per mel filter, one lane's serial sum in double per cepstral coefficient
 #include <hip/hip_runtime.h>
@@ -119,12 +121,64 @@ struct WaveSynArgs {
     float *frames;                          // [frames][n_fft]: window * irfft(S)
 };
 
-__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_synthesis(const WaveSynArgs a)
+// (Post: NoPost, or PostFn with bp_set_post -- the post-processed value stands for the net's column and is written nowhere)
+template <class Post>
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_synthesis(const WaveSynArgs a, const Post post)
 {
     extern __shared__ float2 z[];
     const int g = blockIdx.x;
     synth_frame(z, a.out + (size_t)g * a.ldo + a.out_col, a.Y + (size_t)g * a.D, a.win, a.tw, a.log2M, a.target,
-                a.frames + ((size_t)g << (a.log2M + 1)));
+                a.frames + ((size_t)g << (a.log2M + 1)), post);
+}
+
+// bp_post_rows: the post-processed value over caller rows, one thread per value
+__global__ __launch_bounds__(WAVE_THREADS) void bp_wave_post_rows(const float *__restrict__ est, const float *__restrict__ mask,
+                                                               const float *__restrict__ y, const PostP p, int D, size_t total,
+                                                               float *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * WAVE_THREADS + threadIdx.x;
+    if (i >= total) return;
+    out[i] = post_value(p, est[i], p.gate ? mask[i] : 0.0f, y[i], (int)(i % (size_t)D));
+}
+
+namespace {
+constexpr int GV_THREADS = 64;
+struct GvArgs {
+    const float *out; int ldo, out_col;     // net outputs [n][ldo], columns [out_col, out_col + D)
+    const float2 *Y; const float *ref;      // noisy spectrum and clean LPS, [n][D] each
+    int D, n, q, post;                      // q = ceil(n / GV_PARTS) frames per part
+    PostFn fn;
+    double *parts;                          // [GV_PARTS][4][D], then the totals [4][D]
+};
+}  // namespace
+
+// The part sums of bp_gv_mix (include/bp_c_api.h): workgroup (x, p) holds 64 bins of part p, one thread per bin, serial over the
+// part's frames in ascending order -- four double accumulators from 0.0: e, e^2, r, r^2.  The squares are exact in double, so each
+// step is one rounded addition, fused or not.
+__global__ __launch_bounds__(GV_THREADS) void bp_wave_gv_parts(const GvArgs a)
+{
+    const int k = blockIdx.x * GV_THREADS + threadIdx.x, part = blockIdx.y;
+    if (k >= a.D) return;
+    const int g0 = part * a.q, g1 = g0 + a.q < a.n ? g0 + a.q : a.n;
+    double es = 0.0, eq = 0.0, rs = 0.0, rq = 0.0;
+    for (int g = g0; g < g1; ++g) {
+        const float *o = a.out + (size_t)g * a.ldo + a.out_col;
+        const float e = a.post ? a.fn(o[k], o, k, a.Y[(size_t)g * a.D + k]) : o[k], r = a.ref[(size_t)g * a.D + k];
+        es += (double)e; eq += (double)e * (double)e;
+        rs += (double)r; rq += (double)r * (double)r;
+    }
+    double *dst = a.parts + (size_t)part * 4 * a.D + k;
+    dst[0] = es; dst[a.D] = eq; dst[2 * (size_t)a.D] = rs; dst[3 * (size_t)a.D] = rq;
+}
+
+// ... and their totals: part 0 + part 1 + ... in ascending order, one thread per (quantity, bin)
+__global__ __launch_bounds__(GV_THREADS) void bp_wave_gv_total(double *parts, int D)
+{
+    const int i = blockIdx.x * GV_THREADS + threadIdx.x;
+    if (i >= 4 * D) return;
+    double t = parts[i];
+    for (int p = 1; p < GV_PARTS; ++p) t += parts[(size_t)p * 4 * D + i];
+    parts[(size_t)GV_PARTS * 4 * D + i] = t;
 }
 
 // Segment t >= 1 of a sentence (padded samples [t hop, (t+1) hop)) is covered by frame t (offset k) and frame t-1 (offset
@@ -288,14 +342,159 @@ extern "C" int bp_set_nat(bp_handle *h, int mode, const bp_noise_params *np)
     return BP_OK;
 }
 
+// ------------------------------------------------------------------ post-processing of the LPS estimate (include/bp_c_api.h)
+// The range rules of bp_post_params in the caller's name; sL: the net's output width, or -1 without a net (bp_post_rows: mask_col
+// only switches the gate on).  out: everything but the device pointers.
+static int post_check(const char *who, int fea_dim, const bp_post_params *p, int sL, PostP &out)
+{
+    const std::string w(who);
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, w + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (p->gv != 0 && p->gv != 1) return fail(BP_ERR_ARG, w + ": gv must be 0 or 1");
+    if (p->gv) {
+        if (!p->gv_center || !p->gv_scale) return fail(BP_ERR_ARG, w + ": gv = 1 needs gv_center and gv_scale");
+        for (int k = 0; k < fea_dim; ++k) {
+            if (!std::isfinite(p->gv_center[k])) return fail(BP_ERR_ARG, w + ": gv_center[" + std::to_string(k) + "] is not finite");
+            if (!std::isfinite(p->gv_scale[k]) || !(p->gv_scale[k] > 0.0f))
+                return fail(BP_ERR_ARG, w + ": gv_scale[" + std::to_string(k) + "] must be finite and > 0");
+        }
+    }
+    if (p->mask_col < -1) return fail(BP_ERR_ARG, w + ": mask_col must be -1 (no gating) or a column");
+    if (sL >= 0 && p->mask_col >= 0 && (long)p->mask_col + fea_dim > sL) return fail(BP_ERR_ARG, w + ": mask_col + fea_dim exceeds layersizes[last]");
+    if (!std::isfinite(p->mask_lo) || !std::isfinite(p->mask_hi) || !std::isfinite(p->mask_weight))
+        return fail(BP_ERR_ARG, w + ": mask_lo, mask_hi and mask_weight must be finite");
+    if (p->mask_lo > p->mask_hi) return fail(BP_ERR_ARG, w + ": mask_lo must not exceed mask_hi");
+    if (p->mask_weight < 0.0f || p->mask_weight > 1.0f) return fail(BP_ERR_ARG, w + ": mask_weight outside [0, 1]");
+    memset(&out, 0, sizeof(out));
+    out.gv = p->gv; out.gate = p->mask_col >= 0; out.mask_col = p->mask_col;
+    out.lo = p->mask_lo; out.hi = p->mask_hi; out.weight = p->mask_weight;
+    out.inv = p->mask_hi > p->mask_lo ? (float)(1.0 / ((double)p->mask_hi - (double)p->mask_lo)) : 0.0f;
+    return BP_OK;
+}
+
+extern "C" int bp_post_defaults(bp_post_params *p)
+{
+    if (!p) return fail(BP_ERR_ARG, "bp_post_defaults: null pointer");
+    p->gv = 0; p->gv_center = p->gv_scale = nullptr;
+    p->mask_col = -1; p->mask_lo = p->mask_hi = 0.5f; p->mask_weight = 1.0f;
+    return BP_OK;
+}
+
+// Every check before anything is touched; the device block is allocated by the first call that turns post-processing on, at the
+// parameter limit of fea_dim, and never again.
+extern "C" int bp_set_post(bp_handle *h, int fea_dim, const bp_post_params *p)
+{
+    if (!h) return fail(BP_ERR_ARG, "bp_set_post: null handle");
+    if (h->dp) return fail(BP_ERR_STATE, "bp_set_post: not on an attached data-parallel handle");
+    if (!p) { h->post_on = false; return BP_OK; }
+    PostP q;
+    { const int r = post_check("bp_set_post", fea_dim, p, h->s[h->L - 1], q); if (r != BP_OK) return r; }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->post_tab) {
+        const int r = dev_alloc(h, &h->post_tab, 2 * (size_t)POST_MAX_D);
+        if (r != BP_OK) return r;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));                     // (an earlier call's synthesis may still read the block)
+    if (q.gv) {
+        HIPCHK(hipMemcpy(h->post_tab, p->gv_center, (size_t)fea_dim * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->post_tab + POST_MAX_D, p->gv_scale, (size_t)fea_dim * 4, hipMemcpyHostToDevice));
+    }
+    q.c = h->post_tab; q.s = h->post_tab + POST_MAX_D;
+    h->post = q; h->post_D = fea_dim; h->post_on = true;
+    return BP_OK;
+}
+
+int wave_post_check(const char *who, const bp_handle *h, int fea_dim, int target)
+{
+    if (!h->post_on) return BP_OK;
+    if (fea_dim != h->post_D)
+        return fail(BP_ERR_ARG, std::string(who) + ": post-processing is set for fea_dim " + std::to_string(h->post_D) + " (bp_set_post), not " +
+                                    std::to_string(fea_dim));
+    if (target == BP_WAVE_MASK) return fail(BP_ERR_ARG, std::string(who) + ": post-processing (bp_set_post) applies to BP_WAVE_LPS, not to BP_WAVE_MASK");
+    return BP_OK;
+}
+
+extern "C" int bp_post_rows(int device, int fea_dim, int n_frames, const float *est, const float *mask, const float *noisy_lps,
+                            const bp_post_params *p, float *out)
+{
+    if (!p) return fail(BP_ERR_ARG, "bp_post_rows: null parameters");
+    PostP q;
+    { const int r = post_check("bp_post_rows", fea_dim, p, -1, q); if (r != BP_OK) return r; }
+    if (n_frames < 1) return fail(BP_ERR_ARG, "bp_post_rows: n_frames must be >= 1");
+    if (!est || !noisy_lps || !out || (q.gate && !mask)) return fail(BP_ERR_ARG, "bp_post_rows: null pointer");
+    const size_t total = (size_t)n_frames * fea_dim, row_b = total * 4;
+    Layout lay;                                                  // centre | scale | est | mask | noisy LPS, then the output
+    const size_t o_c = lay.take((size_t)fea_dim * 4), o_s = lay.take((size_t)fea_dim * 4), o_e = lay.take(row_b);
+    const size_t o_m = lay.take(q.gate ? row_b : 0), o_y = lay.take(row_b), o_out = lay.take(row_b);
+    OneShot os;
+    { const int r = os.open("bp_post_rows", device, lay.size()); if (r != BP_OK) return r; }
+    hipError_t &e = os.e;
+    char *d = os.d.as<char>();
+    if (e == hipSuccess && q.gv) e = hipMemcpyAsync(d + o_c, p->gv_center, (size_t)fea_dim * 4, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess && q.gv) e = hipMemcpyAsync(d + o_s, p->gv_scale, (size_t)fea_dim * 4, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_e, est, row_b, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess && q.gate) e = hipMemcpyAsync(d + o_m, mask, row_b, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, noisy_lps, row_b, hipMemcpyHostToDevice, os.st);
+    if (e == hipSuccess) {
+        q.c = (const float *)(d + o_c); q.s = (const float *)(d + o_s);
+        hipLaunchKernelGGL(bp_wave_post_rows, dim3((unsigned)((total + WAVE_THREADS - 1) / WAVE_THREADS)), dim3(WAVE_THREADS), 0, os.st,
+                           (const float *)(d + o_e), (const float *)(d + o_m), (const float *)(d + o_y), q, fea_dim, total, (float *)(d + o_out));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + o_out, row_b, hipMemcpyDeviceToHost, os.st);
+    return os.finish("bp_post_rows");
+}
+
+extern "C" int bp_gv_factors(int fea_dim, int64_t frames, const double *est_sum, const double *est_sq, const double *ref_sum, const double *ref_sq,
+                             int mode, float *center, float *scale)
+{
+#pragma clang fp contract(off)                                   // (S2 / n - m * m: two roundings, as the definition has them)
+    if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, "bp_gv_factors: 2*(fea_dim-1) must be a power of two from 64 to 2048");
+    if (!est_sum || !est_sq || !ref_sum || !ref_sq || !center || !scale) return fail(BP_ERR_ARG, "bp_gv_factors: null pointer");
+    if (mode != BP_GV_INDEP && mode != BP_GV_DEP) return fail(BP_ERR_ARG, "bp_gv_factors: mode must be BP_GV_INDEP or BP_GV_DEP");
+    if (frames < 2) return fail(BP_ERR_ARG, "bp_gv_factors: need at least 2 frames");
+    const double n = (double)frames;
+    std::vector<double> ve((size_t)fea_dim), vr((size_t)fea_dim), mr((size_t)fea_dim);
+    for (int k = 0; k < fea_dim; ++k) {
+        const double me = est_sum[k] / n;
+        mr[k] = ref_sum[k] / n;
+        ve[k] = est_sq[k] / n - me * me; vr[k] = ref_sq[k] / n - mr[k] * mr[k];
+        if (!(ve[k] > 0.0) || !std::isfinite(ve[k])) return fail(BP_ERR_ARG, "bp_gv_factors: the estimate's variance of bin " + std::to_string(k) + " is not > 0");
+        if (!(vr[k] > 0.0) || !std::isfinite(vr[k])) return fail(BP_ERR_ARG, "bp_gv_factors: the reference's variance of bin " + std::to_string(k) + " is not > 0");
+    }
+    double pooled = 0.0;
+    for (int k = 0; k < fea_dim; ++k) pooled += ve[k] / vr[k];
+    const float beta = (float)sqrt((double)fea_dim / pooled);
+    for (int k = 0; k < fea_dim; ++k) {
+        center[k] = (float)mr[k];
+        scale[k] = mode == BP_GV_DEP ? (float)sqrt(vr[k] / ve[k]) : beta;
+    }
+    return BP_OK;
+}
+
 hipError_t wave_synthesis_launch(const float *out, int ldo, int out_col, const float2 *Y, const float *win, const float2 *tw, int log2M,
-                                 int D, int target, float *syn, int frames, hipStream_t st)
+                                 int D, int target, float *syn, int frames, hipStream_t st, const PostP *post)
 {
     WaveSynArgs a; memset(&a, 0, sizeof(a));
     a.out = out; a.ldo = ldo; a.out_col = out_col;
     a.Y = Y; a.win = win; a.tw = tw; a.log2M = log2M; a.D = D; a.target = target; a.frames = syn;
     const int M = 1 << log2M;
-    hipLaunchKernelGGL(bp_wave_synthesis, dim3((unsigned)frames), dim3(WAVE_THREADS), lds_bytes(M) + (size_t)(M + 1) * sizeof(float2), st, a);
+    const size_t lds = lds_bytes(M) + (size_t)(M + 1) * sizeof(float2);
+    if (post) hipLaunchKernelGGL(bp_wave_synthesis<PostFn>, dim3((unsigned)frames), dim3(WAVE_THREADS), lds, st, a, PostFn{*post, post->mask_col - out_col});
+    else hipLaunchKernelGGL(bp_wave_synthesis<NoPost>, dim3((unsigned)frames), dim3(WAVE_THREADS), lds, st, a, NoPost());
+    return hipGetLastError();
+}
+
+hipError_t wave_gv_launch(bp_handle *h, const float *out, int ldo, int out_col, const float2 *Y, const float *ref, int D, int n,
+                          const PostP *post, hipStream_t st)
+{
+    GvArgs a; memset(&a, 0, sizeof(a));
+    a.out = out; a.ldo = ldo; a.out_col = out_col; a.Y = Y; a.ref = ref; a.D = D; a.n = n; a.q = (n + GV_PARTS - 1) / GV_PARTS;
+    if (post) { a.post = 1; a.fn = PostFn{*post, post->mask_col - out_col}; }
+    a.parts = reinterpret_cast<double *>(h->gv_parts);
+    hipLaunchKernelGGL(bp_wave_gv_parts, dim3((unsigned)((D + GV_THREADS - 1) / GV_THREADS), GV_PARTS), dim3(GV_THREADS), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bp_wave_gv_total, dim3((unsigned)((4 * D + GV_THREADS - 1) / GV_THREADS)), dim3(GV_THREADS), 0, st, a.parts, D);
     return hipGetLastError();
 }
 
@@ -476,6 +675,7 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     { const int r = wave_nat_mode("bp_enhance_waves", h, nat, &dyn); if (r != BP_OK) return r; }
     if (c->target != BP_WAVE_LPS && c->target != BP_WAVE_MASK) return fail(BP_ERR_ARG, "bp_enhance_waves: target must be BP_WAVE_LPS or BP_WAVE_MASK");
     if (c->out_col < 0 || (long)c->out_col + D > sL) return fail(BP_ERR_ARG, "bp_enhance_waves: out_col + fea_dim exceeds layersizes[last]");
+    { const int r = wave_post_check("bp_enhance_waves", h, D, c->target); if (r != BP_OK) return r; }
     const size_t rows = p.frames + (size_t)c->n_sent * (ctx - 1);
     if (rows > (size_t)h->cap)
         return fail(BP_ERR_ARG, "bp_enhance_waves: " + std::to_string(rows) + " rows (frames + replicated edge rows) exceed the chunk capacity " +
@@ -516,13 +716,8 @@ extern "C" int bp_enhance_waves(bp_handle *h, int fea_dim, const bp_wave_chunk *
     }
     window_adopt(h, n, D, ctx, nat, false);
     if ((r = forward_resident(h, n)) != BP_OK) return r;
-    {
-        WaveSynArgs a; memset(&a, 0, sizeof(a));
-        a.out = h->out_chunk.as<float>(); a.ldo = h->ld[L - 1]; a.out_col = c->out_col;
-        a.Y = Y; a.win = win; a.tw = tw; a.log2M = p.log2M; a.D = D; a.target = c->target; a.frames = (float *)h->wave[2].p;
-        hipLaunchKernelGGL(bp_wave_synthesis, dim3((unsigned)n), dim3(WAVE_THREADS), lds_bytes(p.M) + (size_t)(p.M + 1) * sizeof(float2), h->stream, a);
-        HIPCHK(hipGetLastError());
-    }
+    HIPCHK(wave_synthesis_launch(h->out_chunk.as<float>(), h->ld[L - 1], c->out_col, Y, win, tw, p.log2M, D, c->target, (float *)h->wave[2].p, n,
+                                 h->stream, h->post_on ? &h->post : nullptr));
     hipLaunchKernelGGL(bp_wave_overlap, dim3((unsigned)n), dim3(WAVE_THREADS), 0, h->stream, (const float *)h->wave[2].p, win, F, c->n_sent, p.hop,
                        (float *)h->wave[3].p);
     HIPCHK(hipGetLastError());

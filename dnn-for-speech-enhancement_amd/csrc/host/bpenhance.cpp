@@ -7,6 +7,7 @@
 //             [traincache=102400] [activation=relu|sigmoid] [device=0] [compute=fp32|bf16]
 //             [output_act=linear|sigmoid output_linear_dims=<n> output_loss=xent|mse]   (as the net was trained, bptrain.cpp)
 //             [stream_block=<samples> [stream_chan=<n>]] [forward=default|rowinv] [rate=8000] [nat=static|dynamic]
+//             [post_gv=gv.norm] [post_mask_col=129 [post_mask_lo=0.5] [post_mask_hi=0.5] [post_mask_weight=1]]
 //   bpenhance method=logmmse fea_dim=129 (wav_list=... | in_wav=... out_wav=...) [device=0] [lm_alpha=0.98] [lm_mu=0.98]
 //             [lm_eta=0.15] [lm_xi_min_db=-25] [lm_gamma_max=40] [lm_init_frames=6] [lm_stream_block=<samples> [lm_stream_chan=<n>]]
 //             [lm_noise=vad|spp]
@@ -28,6 +29,9 @@
 // (bp_resample_waves), enhanced, converted back to f, trimmed to its original length and written at f as without the key; what it
 // held above R/2 is gone.  One call and one line on stdout per distinct rate and direction.  Not with stream_block or
 // lm_stream_block (a stream needs a filter that keeps state), and not with method=logmmse.
+// post_gv / post_mask_* (wave_target=lps): the net's LPS estimate is post-processed before resynthesis
+// (bp_set_post) -- GV equalisation with the factors of the file that `bpeval gv_out=` wrote, and the mask gate on the columns from
+// post_mask_col on; a streaming session opened below keeps them.  Without the keys the output is that of a run before they existed.
 // Errors: message + exit(0), success: return 1 (reference convention).
 #include <stdio.h>
 #include <stdlib.h>
@@ -176,6 +180,7 @@ int main(int argc, char **argv)
     int stream_block = 0, stream_chan = 1, forward = BP_FORWARD_DEFAULT, lm_block = 0, lm_chan = 1, rate = 0;
     bool lm_chan_given = false;
     int lm_noise = BP_NOISE_VAD, nat = BP_NAT_STATIC;
+    PostKeys post;
     float vis = 0.f, hid = 0.f;
     const char *const count = "is not a count >= 1";
     const Key keys[] = {
@@ -202,7 +207,7 @@ int main(int argc, char **argv)
         if (k == "lm_stream_chan") lm_chan_given = true;
         // output layer (.wts files do not record it): the keys and checks of bptrain
         if (key_apply(keys, WHO, a) || output_key(a, &out_act, &out_lin, &out_loss) || lm_noise_key(a, WHO, "is not vad or spp", &lm_noise) ||
-            nat_key(a, WHO, "is not static or dynamic", &nat)) continue;
+            nat_key(a, WHO, "is not static or dynamic", &nat) || post_key(a, WHO, true, &post)) continue;
         // the log-MMSE parameters stay by hand: any lm_ name is a number first (nan and inf included), and only then a known key
         if (k.compare(0, 3, "lm_") != 0) fail("bpenhance: unknown key " + k);
         char *end = nullptr;
@@ -252,6 +257,8 @@ int main(int argc, char **argv)
     if (stream_block > 0 && (long)stream_block * stream_chan > (1L << 28)) fail("bpenhance: stream_block * stream_chan is too large");
     if (forward == BP_FORWARD_ROWINV && compute == 1) fail("bpenhance: forward=rowinv needs compute=fp32");
     if (out_col < 0 || out_col + fea_dim > ls[L - 1]) fail("bpenhance: out_col + fea_dim exceeds layersizes[last]");
+    check_post_keys(WHO, post, target);
+    if (post.mask_col >= 0 && post.mask_col + fea_dim > ls[L - 1]) fail("bpenhance: post_mask_col + fea_dim exceeds layersizes[last]");
 
     // ---- inputs (all read and checked before the device is used)
     std::vector<std::string> ins, outs;
@@ -285,6 +292,7 @@ int main(int argc, char **argv)
     bp_handle *h = create_net(cfg, wts, out_act, out_lin, out_loss);
     check(bp_set_forward(h, forward));
     set_nat(WHO, h, nat, ctx, fea_dim, ls);                      // (a stream opened below keeps the mode, as it keeps the forward's)
+    set_post(h, post, fea_dim);                                  // (... and the post-processing)
 
     std::vector<float> pcm, out;
     std::vector<int> lens;

@@ -8,6 +8,8 @@
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
 //          [scores=basic|extended] [rate=16000] [lm_noise=vad|spp] [nat=static|dynamic]
+//          [post_gv=gv.norm] [post_mask_col=129 [post_mask_lo=0.5] [post_mask_hi=0.5] [post_mask_weight=1]]
+//          [gv_out=gv.norm [gv_mode=indep|dep]]
 //   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended] [rate=16000]
 //
 // rate=R (either mode): every clean, noise or pair WAV whose rate is not R is converted to R on the device as it is
@@ -32,6 +34,11 @@
 // sound + early_ms of reflections.  rir_rooms=N with rir_room_lo / rir_room_hi / rir_t60 / rir_margin / rir_dist / rir_ms / rir_window /
 // rir_rooms_out (bpmix's keys, its defaults) takes the place of rir_list: N simulated responses, their rooms drawn
 // by bp_rir_rooms(init_randem_seed, N, ...) and made by bp_rir_image at the rate of the others.
+// post_gv / post_mask_* (test-set mode, wave_target=lps; without them the output above, byte for byte): the net's
+// LPS estimate is post-processed before resynthesis (bp_set_post) -- GV equalisation with the factors of the file, and the mask gate
+// on the columns from post_mask_col on.  gv_out=FILE makes that file and scores nothing, as bpmix norm_out= trains nothing:
+// bp_gv_mix over the plan in the same cuts, the sums added in call order, bp_gv_factors (gv_mode, default indep), centre then scale
+// in norm-file format, and one line on stdout.
 // Errors: message + exit(0); success: return 1 (reference convention).
 #include <math.h>
 #include <stdio.h>
@@ -70,6 +77,10 @@ struct Params {
     int nat = BP_NAT_STATIC;                                 // nat=static|dynamic: the noise-aware block of the net's input
     int ext = 0;                                             // scores=extended: five score columns
     RirKeys rir;                                             // rir_rooms=N ...: simulated responses in place of rir_list
+    PostKeys post;                                           // post_gv / post_mask_*: post-processing of the LPS estimate
+    std::string gv_out;                                      // gv_out=FILE: the GV factors of the net on this test set, nothing scored
+    int gv_mode = BP_GV_INDEP;
+    bool gv_mode_given = false;
 };
 
 Params parse(int argc, char **argv)
@@ -105,12 +116,15 @@ Params parse(int argc, char **argv)
         {"compute", K_CHOICE, &P.compute_dtype, 0, 0, "fp32|bf16"},
         {"output_act", K_CHOICE, &P.output_act, 0, 0, "linear|sigmoid"},
         {"output_loss", K_CHOICE, &P.output_loss, 0, 0, "xent|mse"},
+        {"gv_out", K_STR, &P.gv_out},
     };
+    const Key gv_mode[] = {{"gv_mode", K_CHOICE, &P.gv_mode, BP_GV_INDEP, 0, "indep|dep"}};
     for (int i = 1; i < argc; ++i) {
         const Arg a = split_arg(argv[i]);
         if (key_apply(both, WHO, a)) continue;
         if (lm_noise_key(a, WHO, nullptr, &P.lm_noise)) P.lm_noise_given = true;
-        else if (nat_key(a, WHO, nullptr, &P.nat)) {}
+        else if (nat_key(a, WHO, nullptr, &P.nat) || post_key(a, WHO, false, &P.post)) {}
+        else if (key_apply(gv_mode, WHO, a)) P.gv_mode_given = true;
         else if (!key_apply(keys, WHO, a)) {
             const int r = rir_key(P.rir, a.k, a.v);
             if (!r) fail("bpeval: unknown key " + a.k);
@@ -119,6 +133,7 @@ Params parse(int argc, char **argv)
         P.net_keys = true;
     }
     if (P.lm_noise_given && !P.baseline && P.pairs_list.empty()) fail("bpeval: lm_noise needs baseline=logmmse");
+    if (P.gv_mode_given && P.gv_out.empty() && P.pairs_list.empty()) fail("bpeval: gv_mode needs gv_out");
     return P;
 }
 
@@ -215,6 +230,12 @@ int main(int argc, char **argv)
     if (P.layersizes[L - 1] != D && P.layersizes[L - 1] != 2 * D) fail("bpeval: layersizes[last] must be fea_dim or 2*fea_dim");
     if (P.out_col + D > P.layersizes[L - 1]) fail("bpeval: out_col + fea_dim exceeds layersizes[last]");
     if (P.snr.empty()) fail("bpeval: snr_list is empty");
+    check_post_keys(WHO, P.post, P.wave_target);
+    if (!P.gv_out.empty()) {
+        if (P.post.on()) fail("bpeval: gv_out takes no post_gv or post_mask_col (the factors are those of the net's own columns)");
+        if (P.wave_target != BP_WAVE_LPS) fail("bpeval: gv_out needs wave_target=lps");
+        if (P.baseline || !P.scores_out.empty()) fail("bpeval: gv_out scores nothing: it takes no baseline or scores_out");
+    }
     // every list and WAV is read and checked before the device is used
     int rate = 0;
     const Corpus clean = flatten(read_wav_list(WHO, "clean_list", P.clean_list, nullptr, &rate, P.rate, P.device));
@@ -261,9 +282,31 @@ int main(int argc, char **argv)
     cfg.activation = P.activation; cfg.compute_dtype = P.compute_dtype;
     bp_handle *h = create_net(cfg, wts, P.output_act, P.output_linear_dims, P.output_loss);
     set_nat(WHO, h, P.nat, ctx, D, P.layersizes);
+    set_post(h, P.post, D);
     const bp_mix_corpus mc = describe(D, ctx, toff, P.layersizes[L - 1] == D ? BP_MIX_LPS : BP_MIX_LPS_IRM, 5.0f, mean.data(), istd.data(), clean, noise);
     check(bp_set_mix_corpus(h, &mc));
     if (rv.on) set_reverb(h, P.rir, P.device, rv, P.seed, n_clean);
+    if (!P.gv_out.empty()) {                                     // the GV factors of the net on this test set; nothing is scored
+        std::vector<double> sums((size_t)4 * D, 0.0), part((size_t)4 * D);
+        int64_t frames = 0;
+        for (const auto &c : calls) {
+            int64_t f = 0;
+            check(bp_gv_mix(h, c.second - c.first, plan.data() + c.first, P.out_col, BP_GV_RAW, &part[0], &part[D], &part[2 * (size_t)D],
+                            &part[3 * (size_t)D], &f));
+            for (size_t k = 0; k < sums.size(); ++k) sums[k] += part[k];
+            frames += f;
+        }
+        bp_destroy(h);
+        std::vector<float> center(D), scale(D);
+        check(bp_gv_factors(D, frames, &sums[0], &sums[D], &sums[2 * (size_t)D], &sums[3 * (size_t)D], P.gv_mode, center.data(), scale.data()));
+        write_gv(P.gv_out, center, scale);
+        if (P.gv_mode == BP_GV_INDEP)
+            printf("bpeval: GV factor %.9g (indep) of %lld frames of %zu mixtures -> %s\n", scale[0], (long long)frames, plan.size(), P.gv_out.c_str());
+        else
+            printf("bpeval: GV factors %.9g .. %.9g (dep) of %lld frames of %zu mixtures -> %s\n", *std::min_element(scale.begin(), scale.end()),
+                   *std::max_element(scale.begin(), scale.end()), (long long)frames, plan.size(), P.gv_out.c_str());
+        return 1;
+    }
     std::map<float, Acc> by_snr, by_snr_lm;
     Acc all, all_lm;
     std::vector<float> ns, es, ls;

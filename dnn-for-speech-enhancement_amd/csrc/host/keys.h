@@ -209,6 +209,37 @@ inline bool nat_key(const Arg &a, const char *tool, const char *tail, int *mode)
     return key_apply(keys, tool, a);
 }
 
+// post_gv=FILE post_mask_col= post_mask_lo= post_mask_hi= post_mask_weight= as bpenhance (tails: its own texts) and
+// bpeval (tails off: `bad value`) take them: post-processing of the net's LPS estimate, GV factors from the file that
+// `bpeval gv_out=` writes and the mask gate; net_setup.h's set_post hands them to the handle
+struct PostKeys {
+    std::string gv;                                              // post_gv: centre then scale, in norm-file format
+    int mask_col = -1;
+    float lo = 0.5f, hi = 0.5f, weight = 1.0f;
+    bool gate_given = false;                                     // post_mask_lo, _hi or _weight was given
+    bool on() const { return !gv.empty() || mask_col >= 0; }
+};
+inline bool post_key(const Arg &a, const char *tool, bool tails, PostKeys *p)
+{
+    const Key keys[] = {
+        {"post_gv", K_STR, &p->gv},
+        {"post_mask_col", K_INT, &p->mask_col, 0, 1 << 20, nullptr, tails ? "is not a column >= 0" : nullptr},
+        {"post_mask_lo", K_FLOAT, &p->lo, 0, 0, nullptr, tails ? "is not a finite number" : nullptr},
+        {"post_mask_hi", K_FLOAT, &p->hi, 0, 0, nullptr, tails ? "is not a finite number" : nullptr},
+        {"post_mask_weight", K_FLOAT, &p->weight, 0, 1, nullptr, tails ? "is not a number in [0, 1]" : nullptr},
+    };
+    if (!key_apply(keys, tool, a)) return false;
+    if (a.k != "post_gv" && a.k != "post_mask_col") p->gate_given = true;
+    return true;
+}
+// what the keys must satisfy together, before the device is used
+inline void check_post_keys(const char *tool, const PostKeys &p, int wave_target)
+{
+    if (p.gate_given && p.mask_col < 0) fail(std::string(tool) + ": post_mask_lo, post_mask_hi and post_mask_weight need post_mask_col");
+    if (p.lo > p.hi) fail(std::string(tool) + ": post_mask_lo must not exceed post_mask_hi");
+    if (p.on() && wave_target != BP_WAVE_LPS) fail(std::string(tool) + ": post_gv and post_mask_col need wave_target=lps");
+}
+
 // output_act / output_linear_dims / output_loss as bptrain, bpforward and bpenhance take them: strict, with their own texts (a
 // typo must not silently run a different model)
 inline bool output_key(const Arg &a, int *act, int *dims, int *loss)

@@ -102,4 +102,31 @@ inline void set_nat(const char *tool, bp_handle *h, int nat, int context, int fe
     check(bp_set_nat(h, BP_NAT_DYNAMIC, nullptr));
 }
 
+// post_gv / post_mask_* (keys.h: post_key, checked by check_post_keys) on the handle.  Without the keys nothing is called.
+inline void set_post(bp_handle *h, const PostKeys &k, int fea_dim)
+{
+    if (!k.on()) return;
+    bp_post_params p;
+    check(bp_post_defaults(&p));
+    std::vector<float> center, scale;
+    if (!k.gv.empty()) {
+        read_norm(k.gv, fea_dim, center, scale);
+        p.gv = 1; p.gv_center = center.data(); p.gv_scale = scale.data();
+    }
+    p.mask_col = k.mask_col; p.mask_lo = k.lo; p.mask_hi = k.hi; p.mask_weight = k.weight;
+    check(bp_set_post(h, fea_dim, &p));
+}
+
+// the GV factors in norm-file format (bpeval gv_out=; read back by read_norm as post_gv=): centre, then scale
+inline void write_gv(const std::string &path, const std::vector<float> &center, const std::vector<float> &scale)
+{
+    FILE *fn = fopen(path.c_str(), "wt");
+    if (!fn) fail("can not open GV file: " + path);
+    fprintf(fn, "<gv center>\n");
+    for (float v : center) fprintf(fn, "%.9g\n", v);
+    fprintf(fn, "<gv scale>\n");
+    for (float v : scale) fprintf(fn, "%.9g\n", v);
+    fclose(fn);
+}
+
 }  // namespace bp

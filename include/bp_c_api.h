@@ -713,6 +713,69 @@ enum { BP_NAT_STATIC = 0, BP_NAT_DYNAMIC = 1 };
 int bp_set_nat(bp_handle *h, int mode, const bp_noise_params *np);   /* np NULL: bp_noise_defaults */
 
 /* ------------------------------------------------------------------------------------
+ * Post-processing of the net's LPS estimate before resynthesis: global variance (GV) equalisation and mask gating (Xu, Du, Dai,
+ * Lee, TASLP 2015 and Interspeech 2015; no counterpart in the reference's code).  INTEGRATION.md 1q, DESIGN.md 30.  Off by
+ * default: without bp_set_post every entry point returns the bits it returned before.
+ *
+ * One post-processed value, per frame and bin k.  x: the LPS estimate, net output column out_col + k, post-activation; m: the mask
+ * estimate, column mask_col + k; y: the noisy LPS of that frame and bin, with the bits of bp_wave_lps; c = gv_center[k],
+ * s = gv_scale[k].  Every operation is fp32, rounded once, never contracted:
+ *   1. GV, when gv is on:       d = x - c;  t = s * d;  x = c + t
+ *   2. gate, when mask_col >= 0: hi > lo:  u = (m - lo) * inv, inv = (float)(1.0 / ((double)hi - (double)lo)) made once on the host,
+ *                                          u = u > 0 ? (u < 1 ? u : 1) : 0                        (a NaN mask gives 0)
+ *                                hi == lo: u = m >= hi ? 1 : 0
+ *                                w = weight * u;  e = y - x;  q = w * e;  x = x + q
+ * GV first, then the gate.  The value is what the synthesis takes in place of the net's column under BP_WAVE_LPS; out_net remains
+ * the net's own outputs, and no post-processed row is written to memory by the enhancing calls.  lo = hi = theta, weight = 1 is the
+ * hard rule (the noisy LPS where the mask reaches theta), weight = 0.5 the average of the two.
+ *
+ * bp_post_defaults: gv 0, arrays NULL, mask_col -1, mask_lo = mask_hi = 0.5, mask_weight 1.
+ * bp_set_post(h, fea_dim, p): p NULL switches post-processing off.  Every argument is checked before the device is touched, and
+ * on an error the handle is unchanged: BP_ERR_ARG for a null handle, 2 (fea_dim - 1) no power of two in 64 .. 2048, gv neither 0
+ * nor 1, gv = 1 with a null array, a centre that is not finite, a scale that is not finite or not > 0, mask_col < -1 or mask_col +
+ * fea_dim > layersizes[last], lo / hi / weight not finite, lo > hi, weight outside [0, 1]; BP_ERR_STATE on an attached
+ * data-parallel handle.  The arrays are copied.  The parameters stay until the next call.  From then on bp_enhance_waves,
+ * bp_eval_mix and bp_eval_mix_ext resynthesise from the post-processed value; they return BP_ERR_ARG, with nothing touched, when
+ * the call's fea_dim differs from the one that was set, and when the target is BP_WAVE_MASK.  A stream copies the parameters when
+ * it is opened (bp_stream_open makes the same two checks) and keeps them: a later bp_set_post does not change an open stream.
+ * The log-MMSE calls, training and CV are unaffected.
+ *
+ * bp_post_rows (no handle): the same value over caller arrays, all [n_frames][fea_dim]; mask may be NULL when p->mask_col < 0 and
+ * is otherwise the mask block itself (p->mask_col only switches the gate on).  out may be est.
+ *
+ * bp_gv_mix: the second moments that the GV factors are made from, over the mixtures of a plan, on the corpus and the handle state
+ * of bp_eval_mix (fp32 and bf16 handles, both noise-aware modes; BP_ERR_STATE without a corpus).  For mixture-frame g = 0 .. n-1 of
+ * the call and bin k:  e[g][k] = the net's column out_col + k (BP_GV_RAW) or the post-processed value (BP_GV_POST; identical to
+ * BP_GV_RAW while post-processing is off);  r[g][k] = the LPS of the entry's clean target signal, the bits of bp_wave_lps on it.
+ * Sum order, with q = (n + 63) / 64: part p = 0 .. 63 covers the frames [p q, min(n, (p+1) q)) and is one double accumulator from
+ * 0.0 over ascending g, per bin and quantity -- the quantities (double)v and (double)v * (double)v, the product exact in double --
+ * and the total is part 0 + part 1 + ... in ascending p (an empty part adds 0.0).  est_sum, est_sq, ref_sum, ref_sq [fea_dim] and
+ * *frames (= n) are written, not added to: across calls the caller adds.  No float atomics; the same bits on every run.
+ *
+ * bp_gv_factors (host only), in double: me = S1e / n, ve = S2e / n - me^2, and the same for r.  frames < 2 is BP_ERR_ARG; a
+ * variance <= 0 (or not finite) is BP_ERR_ARG with the bin named in the message.  center[k] = (float)mr[k]: the paper scales in
+ * the domain normalised by the clean statistics, which is scaling about the clean mean.  BP_GV_DEP: scale[k] =
+ * (float)sqrt(vr[k] / ve[k]).  BP_GV_INDEP: every scale[k] = (float)sqrt(D / sum_k ve[k] / vr[k]), k ascending -- the paper's
+ * dimension-independent factor, the variance of the estimate pooled over the bins after each is normalised by the clean mean and
+ * deviation.  Additive: bp_abi_version stays 5. */
+enum { BP_GV_RAW = 0, BP_GV_POST = 1 };        /* bp_gv_mix: the net's columns | the rows that are resynthesised */
+enum { BP_GV_INDEP = 0, BP_GV_DEP = 1 };       /* bp_gv_factors: one factor for all bins | one per bin */
+typedef struct bp_post_params {
+    int gv;                                    /* 0 off | 1 on */
+    const float *gv_center, *gv_scale;         /* [fea_dim], read when gv = 1; finite, scale > 0 */
+    int mask_col;                              /* -1: no gating; else first column of the mask block in the net's output */
+    float mask_lo, mask_hi, mask_weight;       /* finite, lo <= hi, 0 <= weight <= 1 */
+} bp_post_params;
+int bp_post_defaults(bp_post_params *p);       /* gv 0, mask_col -1, lo = hi = 0.5, weight 1 */
+int bp_set_post(bp_handle *h, int fea_dim, const bp_post_params *p);     /* NULL: off.  Copies the arrays. */
+int bp_post_rows(int device, int fea_dim, int n_frames, const float *est, const float *mask /* or NULL */,
+                 const float *noisy_lps, const bp_post_params *p, float *out);               /* no handle; all [n_frames][fea_dim] */
+int bp_gv_mix(bp_handle *h, int n_mix, const bp_mixture *m, int out_col, int stage,
+              double *est_sum, double *est_sq, double *ref_sum, double *ref_sq /* [fea_dim] each */, int64_t *frames);
+int bp_gv_factors(int fea_dim, int64_t frames, const double *est_sum, const double *est_sq, const double *ref_sum,
+                  const double *ref_sq, int mode, float *center, float *scale);               /* host only */
+
+/* ------------------------------------------------------------------------------------
  * Sample-rate conversion by a rational factor (no reference counterpart: its README sends its users to TIMIT at 16 kHz, NOISEX-92
  * at 19.98 kHz and 100 noise types at 20 kHz for nets that work at 8 kHz, and leaves the conversion to outside tools).
  * INTEGRATION.md 1m, DESIGN.md 24.  Defined to the bit, as the reverberation FIR above is.
