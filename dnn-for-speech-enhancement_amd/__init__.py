@@ -15,5 +15,6 @@ from .bp_gpu import (BP_GPU, BPError, BPConfig, load_library, LIB_PATH, ABI_SYMB
                      RIR_MAX_IMAGES,
                      BPResampleParams, resample_waves, resample_ratio, resample_len, resample_taps, resample_params,
                      BPMelParams, mel_params, mel_filters, mel_dct, wave_mfcc,
-                     BPPostParams, post_params, post_rows, gv_factors, GV_RAW, GV_POST, GV_STAGES, GV_INDEP, GV_DEP, GV_MODES)
+                     BPPostParams, post_params, post_rows, gv_factors, GV_RAW, GV_POST, GV_STAGES, GV_INDEP, GV_DEP, GV_MODES,
+                     BPRbmConfig, BPRbmHyper, BPRbmTrace, RBMStack, rbm_open, rbm_defaults)
 from .weights_init import glorot_net  # noqa: F401

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "bp_resample_defaults", "bp_resample_ratio", "bp_resample_len", "bp_resample_taps", "bp_resample_waves",
     "bp_mel_defaults", "bp_mel_filters", "bp_mel_dct", "bp_wave_mfcc", "bp_set_mix_aux",
     "bp_post_defaults", "bp_set_post", "bp_post_rows", "bp_gv_mix", "bp_gv_factors",
+    "bp_rbm_defaults", "bp_rbm_create", "bp_rbm_destroy", "bp_rbm_set_hyper", "bp_rbm_train_chunk", "bp_rbm_up", "bp_rbm_step",
+    "bp_rbm_steps", "bp_rbm_get",
 ]
 WAVE_LPS, WAVE_MASK = 0, 1      # bp_wave_chunk.target
 FORWARD_DEFAULT, FORWARD_ROWINV = 0, 1   # bp_set_forward
@@ -177,6 +179,28 @@ class BPPostParams(C.Structure):
     ]
 
 
+class BPRbmConfig(C.Structure):
+    """bp_rbm_config (include/bp_c_api.h): a stack of RBMs."""
+    _fields_ = [
+        ("device", C.c_int), ("numlayers", C.c_int), ("layersizes", C.c_int * MAXLAYER),
+        ("bunchsize", C.c_int), ("max_chunk_frames", C.c_int), ("seed", C.c_uint64),
+    ]
+
+
+class BPRbmHyper(C.Structure):
+    """bp_rbm_hyper (include/bp_c_api.h): the hyper-parameters of one RBM's CD-1 step."""
+    _fields_ = [("lrate", C.c_float), ("momentum", C.c_float), ("weightcost", C.c_float), ("visible", C.c_int), ("sample", C.c_int)]
+
+
+class BPRbmTrace(C.Structure):
+    """bp_rbm_trace (include/bp_c_api.h): what bp_rbm_step hands back; any pointer may be NULL."""
+    _fields_ = [
+        ("v0", C.POINTER(C.c_float)), ("p0", C.POINTER(C.c_float)), ("s0", C.POINTER(C.c_float)), ("v1", C.POINTER(C.c_float)),
+        ("p1", C.POINTER(C.c_float)), ("gw", C.POINTER(C.c_float)), ("gc", C.POINTER(C.c_float)), ("ga", C.POINTER(C.c_float)),
+        ("recon", C.POINTER(C.c_double)),
+    ]
+
+
 class BPConfig(C.Structure):
     _fields_ = [
         ("gpu_used", C.c_int), ("numlayers", C.c_int), ("layersizes", C.c_int * MAXLAYER),
@@ -292,6 +316,15 @@ def load_library(path=None):
     lib.bp_post_rows.argtypes = [C.c_int, C.c_int, C.c_int, fp, fp, fp, C.POINTER(BPPostParams), fp]
     lib.bp_gv_mix.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.bp_gv_factors.argtypes = [C.c_int, C.c_int64, dp, dp, dp, dp, C.c_int, fp, fp]
+    lib.bp_rbm_defaults.argtypes = [C.c_int, C.POINTER(BPRbmHyper)]
+    lib.bp_rbm_create.argtypes = [C.POINTER(BPRbmConfig), fpp, fpp, fpp, C.POINTER(C.c_void_p)]
+    lib.bp_rbm_destroy.argtypes = [C.c_void_p]
+    lib.bp_rbm_set_hyper.argtypes = [C.c_void_p, C.c_int, C.POINTER(BPRbmHyper)]
+    lib.bp_rbm_train_chunk.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, dp]
+    lib.bp_rbm_up.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+    lib.bp_rbm_step.argtypes = [C.c_void_p, C.c_int, fp, C.c_int, C.POINTER(BPRbmTrace)]
+    lib.bp_rbm_steps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint)]
+    lib.bp_rbm_get.argtypes = [C.c_void_p, fpp, fpp, fpp]
     lib.bp_dp_attach.argtypes = [hp, C.c_int, C.c_int, C.c_char_p]
     lib.bp_dp_attach_ex.argtypes = [hp, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.bp_dp_peer_info.argtypes = [hp, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -1519,6 +1552,149 @@ def mix_shuffle(seed, stream, n):
     if rc != 0:
         raise BPError("%s (status %d)" % (lib.bp_last_error().decode(), rc))
     return out[:int(n)]
+
+
+# ------------------------------------------------------------------ pre-training: stacked RBMs, CD-1 (bp_rbm_*)
+RBM_HYPER_FIELDS = [f[0] for f in BPRbmHyper._fields_]
+
+
+def rbm_defaults(layer):
+    """bp_rbm_defaults: the hyper-parameters a new stack holds for RBM `layer`, as a dict."""
+    lib = load_library()
+    h = BPRbmHyper()
+    rc = lib.bp_rbm_defaults(int(layer), C.byref(h))
+    if rc != 0:
+        _raise(lib, rc)
+    return {k: getattr(h, k) for k in RBM_HYPER_FIELDS}
+
+
+class RBMStack(object):
+    """A stack of RBMs on the device (bp_rbm, include/bp_c_api.h); made by rbm_open."""
+
+    def __init__(self, lib, s, layersizes, bunchsize):
+        self._lib, self._s = lib, s
+        self.layersizes, self.bunchsize = list(layersizes), int(bunchsize)
+        self._hyper = {l: rbm_defaults(l) for l in range(1, len(self.layersizes))}
+
+    def _check(self, rc):
+        if rc != 0:
+            _raise(self._lib, rc)
+
+    def _rows(self, rows, n=None):
+        a = np.ascontiguousarray(rows, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.layersizes[0] or (n is not None and a.shape[0] != n):
+            raise BPError("rows must be [%s][%d]" % ("n" if n is None else n, self.layersizes[0]))
+        return a
+
+    def _layer(self, layer):
+        if not 1 <= int(layer) < len(self.layersizes):
+            raise BPError("layer must lie in [1, %d]" % (len(self.layersizes) - 1))
+        return int(layer)
+
+    def hyper(self, layer):
+        return dict(self._hyper[self._layer(layer)])
+
+    def set_hyper(self, layer, **fields):
+        """bp_rbm_set_hyper: the named fields (lrate, momentum, weightcost, visible, sample) change, the others stay."""
+        layer = self._layer(layer)
+        bad = sorted(set(fields) - set(RBM_HYPER_FIELDS))
+        if bad:
+            raise BPError("unknown hyper-parameter: %s" % ", ".join(bad))
+        new = dict(self._hyper[layer], **fields)
+        h = BPRbmHyper(float(new["lrate"]), float(new["momentum"]), float(new["weightcost"]), int(new["visible"]), int(new["sample"]))
+        self._check(self._lib.bp_rbm_set_hyper(self._s, layer, C.byref(h)))
+        self._hyper[layer] = new
+
+    def train(self, layer, rows):
+        """bp_rbm_train_chunk: one CD-1 step per full bunch of rows; the sum of the bunches' reconstruction errors."""
+        a = self._rows(rows)
+        e = C.c_double(0.0)
+        self._check(self._lib.bp_rbm_train_chunk(self._s, int(layer), a.shape[0], _fp(a), C.byref(e)))
+        return e.value
+
+    def up(self, layer, rows):
+        """bp_rbm_up: the mean-field output of RBM `layer`, [n][layersizes[layer]]."""
+        layer = self._layer(layer)
+        a = self._rows(rows)
+        out = np.empty((a.shape[0], self.layersizes[layer]), np.float32)
+        self._check(self._lib.bp_rbm_up(self._s, layer, a.shape[0], _fp(a), _fp(out)))
+        return out
+
+    def step(self, layer, rows, apply=False):
+        """bp_rbm_step on one bunch: every array of the trace (v0 p0 s0 v1 p1 gw gc ga) and recon, as a dict."""
+        layer = self._layer(layer)
+        a = self._rows(rows, self.bunchsize)
+        V, H, B = self.layersizes[layer - 1], self.layersizes[layer], self.bunchsize
+        out = dict(v0=np.empty((B, V), np.float32), p0=np.empty((B, H), np.float32), s0=np.empty((B, H), np.float32),
+                   v1=np.empty((B, V), np.float32), p1=np.empty((B, H), np.float32), gw=np.empty((V, H), np.float32),
+                   gc=np.empty(H, np.float32), ga=np.empty(V, np.float32))
+        recon = C.c_double(0.0)
+        tr = BPRbmTrace(*[_fp(out[k]) for k in ("v0", "p0", "s0", "v1", "p1", "gw", "gc", "ga")], C.pointer(recon))
+        self._check(self._lib.bp_rbm_step(self._s, layer, _fp(a), 1 if apply else 0, C.byref(tr)))
+        out["recon"] = recon.value
+        return out
+
+    def steps(self, layer):
+        n = C.c_uint(0)
+        self._check(self._lib.bp_rbm_steps(self._s, int(layer), C.byref(n)))
+        return int(n.value)
+
+    def get(self):
+        """bp_rbm_get: (weights, hbias, vbias), lists indexed 1 .. numlayers-1 (entry 0 is None)."""
+        L = len(self.layersizes)
+        w, c, a = [None] * L, [None] * L, [None] * L
+        for l in range(1, L):
+            w[l] = np.empty((self.layersizes[l - 1], self.layersizes[l]), np.float32)
+            c[l] = np.empty(self.layersizes[l], np.float32)
+            a[l] = np.empty(self.layersizes[l - 1], np.float32)
+        self._check(self._lib.bp_rbm_get(self._s, _ptrs(w), _ptrs(c), _ptrs(a)))
+        return w, c, a
+
+    def close(self):
+        if self._s is not None:
+            self._lib.bp_rbm_destroy(self._s)
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rbm_open(device, layersizes, bunchsize, weights, hbias, vbias=None, seed=0, max_chunk_frames=0):
+    """bp_rbm_create: weights / hbias / vbias are lists indexed 1 .. len(layersizes)-1 (vbias None or entries None: zeros)."""
+    lib = load_library()
+    ls = [int(x) for x in layersizes]
+    cfg = BPRbmConfig()
+    cfg.device, cfg.numlayers, cfg.bunchsize = int(device), len(ls), int(bunchsize)
+    for i, s in enumerate(ls[:MAXLAYER]):
+        cfg.layersizes[i] = s
+    cfg.max_chunk_frames, cfg.seed = int(max_chunk_frames), int(seed)
+
+    def flat(arrs, sizes, name):
+        out = [None] * MAXLAYER
+        for l in range(1, min(len(ls), MAXLAYER)):
+            if arrs is None or l >= len(arrs) or arrs[l] is None:
+                continue
+            out[l] = np.ascontiguousarray(arrs[l], dtype=np.float32).reshape(-1)
+            if out[l].size != sizes(l):
+                raise BPError("%s[%d] has the wrong size" % (name, l))
+        return out
+    w = flat(weights, lambda l: ls[l - 1] * ls[l], "weights")
+    c = flat(hbias, lambda l: ls[l], "hbias")
+    a = flat(vbias, lambda l: ls[l - 1], "vbias")
+    s = C.c_void_p()
+    rc = lib.bp_rbm_create(C.byref(cfg), _ptrs(w), _ptrs(c), _ptrs(a) if vbias is not None else None, C.byref(s))
+    if rc != 0:
+        _raise(lib, rc)
+    return RBMStack(lib, s, ls, bunchsize)
 
 
 def device_count():

@@ -16,6 +16,8 @@
 //   the block owner of the two streaming engines; bp_mel.h: the tables and the launcher of the MFCC auxiliary target, whose kernel
 //   lives in bp_wave.hip and whose setter in bp_mix.hip)
 //   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
+//   bp_rbm.hip      layer-wise pre-training: a stack of RBMs trained with CD-1 (bp_rbm_create, ...; its own handle, bp_rbm.h); linked as
+//                   libbp_rbm.so, which libbp_hip.so depends on: it shares bp_mem.h and bp_device.h with the nine units above, no state
 //   (bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
 //   and fail / HIPCHK; bp_chunk.h: the resident chunk -- bp_handle::res --, how one becomes resident and what its readers check)
 //

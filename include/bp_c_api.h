@@ -932,6 +932,71 @@ int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, float *avg_ms,
  * device copy of 1 GiB (GB/s, read + write bytes), to stand beside the vendor figures in a roofline report. */
 int bp_measure_peaks(bp_handle *h, float *mfma_f32_tflops, float *hbm_copy_gbs);
 
+/* ------------------------------------------------------------------------------------
+ * Layer-wise pre-training of sigmoid nets: a stack of restricted Boltzmann machines trained with one-step contrastive
+ * divergence (CD-1).  The reference has the slot (initwts_file) and fills it with random nets only (toolbox/weights/gen_rand_net).
+ * INTEGRATION.md 1r, DESIGN.md 31.  fp32 throughout; sigma(x) = 1/(1+expf(-x)), the hidden activation 1 of bp_config.
+ *
+ * A stack has layer sizes s[0..L-1] as bp_config has them.  RBM l (1 <= l <= L-1) has V = s[l-1] visible and H = s[l] hidden
+ * units: weights W_l [V][H] in the [prev][cur] layout of bp_create, hidden bias c_l [H] (the net's bias of layer l), visible
+ * bias a_l [V] (the RBM's alone), and a momentum state dW, dc, da that starts at zero.  The input of RBM 1 is the caller's
+ * stacked rows [n][s[0]], what bp_train_chunk takes as `in`; the input of RBM l > 1 is the mean-field output of RBMs 1 .. l-1
+ * on those rows, x <- sigma(x W_j + c_j) for j = 1 .. l-1 (nothing is sampled there).
+ *
+ * One CD-1 step of RBM l on a bunch v0 [B][V] with {lrate, momentum, weightcost, visible, sample}:
+ *   p0 = sigma(v0 W + c)
+ *   s0 = sample ? (u < p0 ? 1 : 0) : p0          u[r][j] = (float)(word >> 8) * 2^-24   (exact in fp32; 0 <= u < 1)
+ *   v1 = visible == 0 ? s0 W^T + a               (Gaussian visibles of unit variance: the inputs are mean/variance normalised)
+ *                     : sigma(s0 W^T + a)        (Bernoulli visibles: the probability, not a sample)
+ *   p1 = sigma(v1 W + c)
+ *   gW = v1^T p1 - v0^T p0,  gc = sum_r (p1 - p0),  ga = sum_r (v1 - v0)             (sums over the bunch)
+ *   d' = momentum d - lrate (g / B + wc w),  w' = w + d'        wc = weightcost for W and 0 for both biases
+ *   recon = sum_r sum_i (v0 - v1)^2              the fp32 difference, squared and summed in double in a fixed order
+ * word for row r and hidden unit j is word r & 3 of the Philox4x32-10 block with counter (idx_lo, idx_hi, l, t) and key
+ * (seed_lo, seed_hi), idx = (r >> 2) H + j, t = the number of CD steps RBM l has APPLIED so far (the keying of the step's
+ * dropout words with frame offset 0).  No float atomics, every summation order is fixed by the shapes: two stacks given the
+ * same calls hold the same bits.
+ *
+ * bp_rbm_defaults (host only): layer 1 {visible 0, lrate 0.0005}, layers >= 2 {visible 1, lrate 0.01}; momentum 0.9, weightcost
+ *   1e-5, sample 1 for both.  A new stack holds them.
+ * bp_rbm_create: weights / hbias / vbias are indexed 1 .. numlayers-1 as in bp_create; vbias NULL or an entry NULL = zeros.  The
+ *   stack allocates once, here: its parameters, one bunch of work space and room for max_chunk_frames rows (0 = BP_MAXCACHEFRAME).
+ * bp_rbm_train_chunk: uploads the rows and runs one CD-1 step per consecutive full bunch (propagating up first when layer > 1);
+ *   rows short of a bunch at the end train nothing, as in BP_GPU::train.  *recon_sq_sum (may be NULL) = the sum of the bunches'
+ *   recon, each with the weights that bunch saw.
+ * bp_rbm_up: out[n][s[layer]] = the mean-field output of RBM `layer` for every row, the rows short of a bunch included.
+ * bp_rbm_step: the parity entry, one bunch.  Whatever the trace asks for comes back (any pointer may be NULL, and so may the
+ *   trace); gw / gc / ga are the STORED gradients.  apply = 0: nothing of the stack changes -- not the weights, not the momentum
+ *   state, not the counter.  apply = 1: it does to the stack exactly what bp_rbm_train_chunk does for that bunch.
+ * bp_rbm_steps: the CD steps RBM `layer` has applied.  bp_rbm_get: the parameters (NULL arrays and NULL entries are skipped).
+ * BP_ERR_ARG before the device is touched, the stack unchanged: null pointers, numlayers outside [2, BP_MAXLAYER], a size or the
+ * bunch < 1, layer outside [1, numlayers-1], n_frames negative or over the capacity, lrate or weightcost negative or not
+ * finite, momentum outside [0, 1), visible or sample not 0/1.
+ * Out of scope: CD-k and persistent CD, sampled visibles, sparsity targets, bf16, data-parallel pre-training. */
+typedef struct bp_rbm bp_rbm;
+typedef struct bp_rbm_config {
+    int device, numlayers;
+    int layersizes[BP_MAXLAYER];
+    int bunchsize, max_chunk_frames;
+    uint64_t seed;
+} bp_rbm_config;
+typedef struct bp_rbm_hyper { float lrate, momentum, weightcost; int visible, sample; } bp_rbm_hyper;
+typedef struct bp_rbm_trace {
+    float *v0, *p0, *s0, *v1, *p1;   /* [B][V] or [B][H]; any may be NULL */
+    float *gw, *gc, *ga;             /* [V][H], [H], [V] */
+    double *recon;
+} bp_rbm_trace;
+int bp_rbm_defaults(int layer, bp_rbm_hyper *out);
+int bp_rbm_create(const bp_rbm_config *cfg, const float *const *weights, const float *const *hbias, const float *const *vbias,
+                  bp_rbm **out);
+int bp_rbm_destroy(bp_rbm *s);
+int bp_rbm_set_hyper(bp_rbm *s, int layer, const bp_rbm_hyper *p);
+int bp_rbm_train_chunk(bp_rbm *s, int layer, int n_frames, const float *in, double *recon_sq_sum);
+int bp_rbm_up(bp_rbm *s, int layer, int n_frames, const float *in, float *out /* [n][s[layer]] */);
+int bp_rbm_step(bp_rbm *s, int layer, const float *in /* [bunchsize][s[0]] */, int apply, const bp_rbm_trace *trace);
+int bp_rbm_steps(bp_rbm *s, int layer, unsigned *applied);
+int bp_rbm_get(bp_rbm *s, float *const *weights, float *const *hbias, float *const *vbias);
+
 #ifdef __cplusplus
 }
 #endif
