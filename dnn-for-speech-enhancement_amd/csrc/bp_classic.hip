@@ -1,4 +1,4 @@
-// bp_classic.hip -- C-ABI implementation (include/bp_c_api.h), part 8 of 9: the classic baseline.  The log-MMSE (Ephraim-Malah
+// bp_classic.hip -- C-ABI implementation (include/bp_c_api.h): the classic baseline.  The log-MMSE (Ephraim-Malah
 // log-spectral-amplitude) enhancer on the signal definition of bp_wave.hip: noisy PCM in, enhanced PCM out, no net
 // (bp_logmmse_waves[_nt] here; bp_eval_mix_logmmse[_nt] in bp_mix.hip through bp_classic.h).  Definition: include/bp_c_api.h,
 // INTEGRATION.md 1h, and 1n for the noise tracker of the _nt calls (a second instantiation of both kernels: lm_frame<NB, true>).  gfx950 only.  The second half of the unit is the baseline on live audio (bp_lmstream_*):

@@ -1,4 +1,4 @@
-// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h), part 6 of 9: objective scores of enhanced speech.  Segmental SNR,
+// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h): objective scores of enhanced speech.  Segmental SNR,
 // log-spectral distortion on the 1d analysis and STOI of estimates against a reference, and with five score columns ESTOI and
 // SI-SDR beside them (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions:
 // include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame plan and padded layout from bp_wave.hip

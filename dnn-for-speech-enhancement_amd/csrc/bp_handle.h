@@ -3,22 +3,27 @@
 // (bp_dp.hip) and the measurement entry points (bp_profile.hip).  Internal: nothing in here is part of the C ABI
 // (include/bp_c_api.h).
 //
-//   bp_step.hip     handle construction, chunk interface, every kernel launch of the training / CV / forward step
-//   bp_dp.hip       in-library data-parallel exchange (rendezvous, hipIpc peers, RCCL transport, the sharded step driver)
-//   bp_profile.hip  in-step event profile, measured peaks, isolated kernel timing
-//   bp_wave.hip     the signal layer: STFT analysis into a window chunk, overlap-add resynthesis (bp_enhance_waves, bp_wave_lps)
-//   bp_mix.hip      training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...)
-//   bp_eval.hip     objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval_mix lives in bp_mix.hip)
-//   bp_stream.hip   streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
-//   bp_classic.hip  the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_eval_mix_logmmse lives in
-//                   bp_mix.hip) and its streams (bp_lmstream_open, _push, ...)
+//   bp_step.hip      handle construction, chunk interface, every kernel launch of the training / CV / forward step
+//   bp_dp.hip        in-library data-parallel exchange (rendezvous, hipIpc peers, RCCL transport, the sharded step driver)
+//   bp_profile.hip   in-step event profile, measured peaks, isolated kernel timing
+//   bp_wave.hip      the signal layer: STFT analysis into a window chunk, overlap-add resynthesis (bp_enhance_waves, bp_wave_lps), the
+//                    noise-aware rows (bp_set_nat), post-processing of the LPS estimate (bp_set_post) and the MFCC kernel (bp_wave_mfcc)
+//   bp_resample.hip  rational sample-rate conversion (bp_resample_waves, bp_resample_*; bp_resample.h)
+//   bp_mix.hip       training mixtures made on the device from a resident clean + noise corpus (bp_set_mix_corpus, bp_train_mix, ...),
+//                    and the calls that score or measure on those mixtures (bp_eval_mix*, bp_gv_mix)
+//   bp_room.hip      room acoustics: sentences convolved with room impulse responses (bp_reverb_waves; bp_room.h for bp_set_mix_reverb)
+//                    and the responses simulated with the image method (bp_rir_image, bp_rir_*)
+//   bp_eval.hip      objective scores: segmental SNR, log-spectral distortion, STOI (bp_score_waves; bp_eval.h)
+//   bp_stream.hip    streaming sessions: live audio enhanced in blocks, bit-identical to bp_enhance_waves (bp_stream_open, _push, ...)
+//   bp_classic.hip   the classic baseline: the log-MMSE enhancer on the same signal layer (bp_logmmse_waves; bp_classic.h) and its
+//                    streams (bp_lmstream_open, _push, ...)
+//   bp_infer.hip     the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
+//   bp_rbm.hip       layer-wise pre-training: a stack of RBMs trained with CD-1 (bp_rbm_create, ...; its own handle, bp_rbm.h); it
+//                    shares bp_mem.h and bp_device.h with the other units, no state
 //   (bp_fft.h: the device functions and the frame plan of the signal-layer units; bp_stream_core.h: counts, carry, push checks and
-//   the block owner of the two streaming engines; bp_mel.h: the tables and the launcher of the MFCC auxiliary target, whose kernel
-//   lives in bp_wave.hip and whose setter in bp_mix.hip)
-//   bp_infer.hip    the row-invariant inference forward (bp_set_forward: BP_FORWARD_ROWINV), one thin-M kernel per layer
-//   bp_rbm.hip      layer-wise pre-training: a stack of RBMs trained with CD-1 (bp_rbm_create, ...; its own handle, bp_rbm.h); linked as
-//                   libbp_rbm.so, which libbp_hip.so depends on: it shares bp_mem.h and bp_device.h with the nine units above, no state
-//   (bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
+//   the block owner of the two streaming engines; bp_mel.h: the tables and the launcher of the MFCC auxiliary target;
+//   bp_philox_host.h: Philox on the host, for the planners of bp_mix.hip and bp_room.hip;
+//   bp_mem.h: the holders that free device memory, pinned memory, events and streams, the grow-only policy, block layouts,
 //   and fail / HIPCHK; bp_chunk.h: the resident chunk -- bp_handle::res --, how one becomes resident and what its readers check)
 //
 // Device layout (all fp32 unless a bf16 copy is named): every layer width s_l is padded to ld_l = roundup(s_l, 64); pad

@@ -1,4 +1,4 @@
-// bp_infer.hip -- part 9 of 9 of the library: the row-invariant inference forward (BP_FORWARD_ROWINV, include/bp_c_api.h).  gfx950 only.
+// bp_infer.hip -- the row-invariant inference forward (BP_FORWARD_ROWINV, include/bp_c_api.h).  gfx950 only.
 //
 // One launch per layer, Y[M][N] = act(alpha * X[M][K] . W[K][N] + b), fp32, for M from 1 to the bunch.  At the handful of rows a
 // stream push has, the layer is a stream of W: every weight is read ONCE per tile of 32 rows, with 16-byte loads straight into

@@ -1,4 +1,4 @@
-// bp_rbm.hip -- the library's tenth unit, built as libbp_rbm.so beside the nine of libbp_hip.so (csrc/Makefile): layer-wise pre-training of sigmoid nets, a stack of restricted Boltzmann machines
+// bp_rbm.hip -- C-ABI implementation (include/bp_c_api.h): layer-wise pre-training of sigmoid nets, a stack of restricted Boltzmann machines
 // trained with one-step contrastive divergence (the bp_rbm_* block of include/bp_c_api.h has the definition).  gfx950 only.
 //
 // One CD-1 bunch of RBM l is six launches on the stack's stream (layouts: bp_rbm.h):

@@ -1,4 +1,4 @@
-// bp_resample.h -- the rational sample-rate converter of bp_wave.hip (bp_resample_waves; include/bp_c_api.h): the
+// bp_resample.h -- the rational sample-rate converter of bp_resample.hip (bp_resample_waves; include/bp_c_api.h): the
 // kernel's arguments, the plan of a call and the launcher, for a unit that wants to convert what it already holds on the device.
 // Internal: nothing in here is part of the C ABI.
 //

@@ -1,4 +1,4 @@
-// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first of nine translation units: the device state of one
+// bp_step.hip -- C-ABI implementation (include/bp_c_api.h), the first translation unit: the device state of one
 // BP_GPU replacement object, the chunk interface and the per-bunch launch sequence (training, CV, forward).  gfx950 only.
 // The handle and what the other units use of this one: bp_handle.h.
 #include <hip/hip_runtime.h>

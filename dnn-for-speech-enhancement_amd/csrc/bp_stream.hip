@@ -1,4 +1,4 @@
-// bp_stream.hip -- C-ABI implementation (include/bp_c_api.h), part 7 of 9: streaming sessions.  Audio that is still arriving is
+// bp_stream.hip -- C-ABI implementation (include/bp_c_api.h): streaming sessions.  Audio that is still arriving is
 // enhanced in blocks of any sizes, on n_chan independent channels per push, and returns the SAME BITS as one bp_enhance_waves
 // call on the finished sentence: the analysis and the synthesis are the device functions of bp_wave.hip (bp_fft.h), the forward
 // is forward_resident on a window chunk, and the overlap-add is the same gather of two frames.  gfx950 only.

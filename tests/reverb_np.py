@@ -1,13 +1,13 @@
 """NumPy restatement of the reverberant corpus entries (include/bp_c_api.h): the delay of a room impulse
 response, the reverberant sentence r and its direct-plus-early part e, and the pairing of sentences with responses.  Written from
-the definition, not from csrc/bp_mix.hip: one float64 accumulator per output sample, the taps added in ascending order, each step
+the definition, not from csrc/bp_room.hip: one float64 accumulator per output sample, the taps added in ascending order, each step
 the exact product of two float32 numbers added with one rounding.  That is the device's sequence of operations element for
 element, so the tests compare with np.array_equal on the uint32 view."""
 import numpy as np
 
 import philox_np as PX
 
-BLOCK = 2048          # outputs of one workgroup of bp_mix_reverb_fir (RV_BLOCK in csrc/bp_mix.hip)
+BLOCK = 2048          # outputs of one workgroup of bp_mix_reverb_fir (RV_BLOCK in csrc/bp_room.hip)
 TAP_TILE = 256        # taps of one LDS tile (RV_TILE)
 MAX_TAPS = 65536      # BP_MIX_RIR_MAX_TAPS
 REVERBERANT, EARLY = 0, 1

@@ -1,7 +1,8 @@
 """Host-side checks of the row-invariant inference forward (no GPU): the bpenhance key, the exact-arithmetic data of
 tests/test_infer_gpu.py, where the bp_infer_* kernels live in the built library, and that every one of them is reached by a named
 case of tests/test_infer_gpu.py (the restatement of the dispatch is tests/infer_np.py).  Kernels are listed by name only
-(llvm-objdump --offloading, --syms, the .kd symbols), as tests/test_dispatch_coverage.py does."""
+(llvm-objdump --offloading, --syms, the .kd symbols), as tests/test_dispatch_coverage.py does.  The same listing holds the build to
+its rule: one shared library, one translation unit per subsystem (UNITS of csrc/Makefile), one gfx950 code object per unit."""
 import os
 import re
 import shutil
@@ -16,6 +17,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "dnn-for-speech-enhancement_amd")
 LIB = os.path.join(PKG, "libbp_hip.so")
 OBJDUMP = "/opt/rocm/llvm/bin/llvm-objdump"
+READELF = "/opt/rocm/llvm/bin/llvm-readelf"
+
+
+def _units():
+    """The names on the UNITS line of csrc/Makefile."""
+    mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
+    return re.search(r"^UNITS\s*=\s*(.+)$", mk, re.M).group(1).split()
 
 
 def test_bpenhance_rejects_an_unknown_forward_without_a_device():
@@ -84,7 +92,7 @@ def code_objects(tmp_path_factory):
 
 
 def test_infer_kernels_live_in_a_code_object_of_their_own(code_objects):
-    assert len(code_objects) == 9, "nine translation units, one gfx950 code object each: %d" % len(code_objects)
+    assert len(code_objects) == len(_units()), "one gfx950 code object per unit of %s: %d" % (_units(), len(code_objects))
     holders = [names for names in code_objects if any("bp_infer_" in n for n in names)]
     assert len(holders) == 1, holders
     assert all("bp_infer_" in n for n in holders[0]), "bp_infer.hip's code object holds other kernels: %s" % sorted(holders[0])
@@ -110,3 +118,60 @@ def test_every_infer_kernel_is_reached_by_a_named_case(code_objects):
         name, tag = re.match(r"(\w+)\[(\w+)\]", case).groups()
         assert "def %s(" % name in gpu and '"%s' % tag in gpu, case
 
+
+
+# Which unit's code object holds a kernel, by the kernel's name; the first row that matches.  A new subsystem adds its row.
+UNIT_OF_KERNEL = [
+    (r"bp_rbm_", "bp_rbm"),
+    (r"bp_rir_|bp_mix_reverb_", "bp_room"),
+    (r"bp_wave_resample$", "bp_resample"),
+    (r"bp_mix_", "bp_mix"),                                # ... the other bp_mix_* kernels, with bp_mix_gain
+    (r"bp_wave_", "bp_wave"),                              # ... the other bp_wave_* kernels, with bp_wave_analysis
+    (r"bp_infer_", "bp_infer"),
+    (r"bp_eval_", "bp_eval"),
+    (r"bp_stream_", "bp_stream"),
+    (r"bp_lmstream_|bp_logmmse_", "bp_classic"),
+    (r"bp_dp_", "bp_dp"),
+    (r"bp_peak_", "bp_profile"),
+    (r"bp_gemm|bp_wgrad_dma|bp_(apply_mask|bias_bf16|fill_normal|out_split_stage|stage_bunch|to_bf16_both)$", "bp_step"),
+]
+
+
+def _unit_of(kernel):
+    base = re.search(r"\bbp_\w+", kernel).group(0)         # the name without return type, template and argument lists
+    for pat, unit in UNIT_OF_KERNEL:
+        if re.match(pat, base):
+            return unit
+    pytest.fail("kernel %s matches no row of UNIT_OF_KERNEL: say which unit holds it" % kernel)
+
+
+def test_every_kernel_lives_in_the_code_object_of_its_unit(code_objects):
+    seen = {}
+    for i, names in enumerate(code_objects):
+        for n in names:
+            assert n not in seen, "%s occurs in two code objects" % n
+            seen[n] = i
+    holder = {}                                            # unit -> the code objects that hold its kernels
+    for n, i in seen.items():
+        holder.setdefault(_unit_of(n), set()).add(i)
+    assert sorted(holder) == sorted(_units()), "the units of the table against UNITS of the Makefile"
+    assert all(len(v) == 1 for v in holder.values()), "a unit's kernels in more than one code object: %s" % holder
+    assert len(set(min(v) for v in holder.values())) == len(holder), "two units share a code object: %s" % holder
+    assert holder["bp_mix"] == {seen[n] for n in seen if n.startswith("bp_mix_gain(")}
+    assert holder["bp_wave"] == {seen[n] for n in seen if n.startswith("bp_wave_analysis(")}
+
+
+def test_one_library_defines_the_whole_abi():
+    import dnnse_amd
+    dyn = subprocess.check_output([READELF, "-d", LIB], universal_newlines=True)
+    needed = re.findall(r"\(NEEDED\)\s+Shared library: \[(.+?)\]", dyn)
+    assert needed and not [n for n in needed if "bp_rbm" in n or "libbp_" in n], needed
+    syms = subprocess.check_output([READELF, "--dyn-syms", "-W", LIB], universal_newlines=True)
+    rows = [line.split() for line in syms.splitlines() if re.match(r"\s*\d+:", line)]
+    defined = [r for r in rows if len(r) >= 8 and r[6] != "UND"]          # Num Value Size Type Bind Vis Ndx Name
+    names = set(r[7].split("@")[0] for r in defined)
+    missing = [s for s in dnnse_amd.ABI_SYMBOLS if s not in names]
+    assert not missing, "not defined in libbp_hip.so itself: %s" % missing
+    err = [r[7] for r in defined if r[3] == "TLS" and "g_bp_err" in r[7]]
+    assert len(err) == 1, "the thread's error string is defined %d times: %s" % (len(err), err)
+    assert not [r[7] for r in rows if "g_bp_err" in r[-1] and r[3] == "TLS" and r[6] == "UND"]
