@@ -88,6 +88,10 @@ FEA_DIMS = (33, 129)
 T_CLASSES = (2, 3, 6, 7, 40)
 WIDE = 257                                           # once: the partial last 64-thread workgroup (257 = 4 * 64 + 1)
 CONTEXTS = ((3, 1), (1, 0))                          # (context, targ_offset)
+# The sizes the frame-size table (tests/geometry_cases.py) adds, at context 3 / targ_offset 1: ceil(D / 64) = 2 (the second
+# workgroup with one live thread), 9 and 17 workgroups of 64 threads per sentence or job, next to the 1, 3 and 5 above.
+GEOMETRY = (65, 513, 1025)
+ALL_DIMS = tuple(sorted(FEA_DIMS + (WIDE,) + GEOMETRY))
 
 
 def lengths(fea_dim):

@@ -4,10 +4,19 @@ tests/test_geometry_gpu.py holds the cases that no older file had the body for).
 
 What changes with the size (csrc/bp_fft.h): the trip counts of fft_lds / rfft_frame / synth_frame (less than one item per thread
 at 33, five bins per thread at 1025), the padded LDS index and the dynamic LDS sizes, and the workgroups per sentence of the two
-noise-aware-row kernels (kb = ceil(D / 256): one up to 129, two at 257, three at 513, five at 1025).
+noise-aware-row kernels (kb = ceil(D / 256): one up to 129, two at 257, three at 513, five at 1025).  For the entry points added
+since: NB, the bins per thread of bp_lmstream_push<NB, SPP> and of the PostFn synthesis kernels (1 up to 129, 2 at 257, 3 at 513,
+5 at 1025), whose per-channel lam / Ap / pb state is indexed by the clamped bin; ceil(D / 64), the 64-thread workgroups per
+sentence or job of bp_wave_dnat and bp_stream_dnat and the column blocks of bp_wave_gv_parts (1, 2 -- the second with one live
+thread -- 3, 5, 9, 17); the dynamic LDS of bp_wave_mel (the FFT, then P[M + 1], then the filters' words: other offsets and trip
+counts at every size); and the LDS of bp_stream_synthesis<PostFn> (the FFT space and S, then two frames of 2 M floats: the large
+layout from 257 on).
 
 A cell is "tests/<file>.py::<test>[<id>]", the id as pytest prints it.  The stream cells compare bit for bit with the offline call
-of the same size, which the `enhance_waves` rows hold to the float64 restatement; eval_mix compares bit for bit with its parts."""
+of the same size, which the `enhance_waves` rows hold to the float64 restatement; eval_mix compares bit for bit with its parts.
+
+API (below) maps every bp_* symbol of include/bp_c_api.h to the rows that hold it, or to the reason it has no frame size;
+tests/test_geometry_coverage.py fails on a symbol that is not classified, so an entry point added later cannot stay outside."""
 import numpy as np
 
 FEA_DIMS = [33, 65, 129, 257, 513, 1025]
@@ -70,7 +79,17 @@ def _merge(*parts):
     return out
 
 
+def _mel_ids():
+    """{fea_dim: the id of mel_np's geometry at that size}: one geometry per size."""
+    import mel_np
+    out = {g["fea_dim"]: mel_np.geo_id(g) for g in mel_np.GEOMETRIES}
+    assert len(out) == len(mel_np.GEOMETRIES), "mel_np.GEOMETRIES: two geometries of one fea_dim"
+    return out
+
+
 GEO = "tests/test_geometry_gpu.py::"
+NOISE, DNAT, POST = "tests/test_noise_gpu.py::", "tests/test_dnat_gpu.py::", "tests/test_post_gpu.py::"
+MEL_IDS = _mel_ids()
 COVERAGE = {
     "wave_lps": _per_size("tests/test_wave_gpu.py::test_analysis_matches_numpy[%d]"),
     "enhance_waves lps": _per_size(GEO + "test_resynthesis_matches_restatement[lps-%d]"),
@@ -89,9 +108,97 @@ COVERAGE = {
                                   _per_size("tests/test_lmstream_gpu.py::test_wide_spectra[%d]", [513, 1025])),
     "eval_mix": _merge({129: "tests/test_eval_gpu.py::test_eval_mix_is_its_parts[0-False-False]"},
                        _per_size(GEO + "test_eval_mix_is_its_parts[%d]", [33, 65, 257, 513, 1025])),
+    # ---- the entry points added after the table was first closed
+    "logmmse_waves spp": _merge(_per_size(NOISE + "test_tracker_matches_restatement[%d]", [33, 65, 129, 257]),
+                                {D: NOISE + "test_tracker_wide_spectrum_paths" for D in (513, 1025)}),
+    "logmmse_stream_open spp": _per_size(NOISE + "test_tracker_streams_return_the_offline_bits[%d]"),
+    "enhance_waves dynamic": _merge(_per_size(DNAT + "test_rows_match_restatement_and_the_baseline[%d-3-1]", [33, 65, 129, 513, 1025]),
+                                    {257: DNAT + "test_rows_match_restatement_and_the_baseline[257-1-0]"}),
+    "mix_features dynamic": _merge(_per_size(DNAT + "test_rows_match_restatement_and_the_baseline[%d-3-1]", [33, 65, 129, 513, 1025]),
+                                   {257: DNAT + "test_rows_match_restatement_and_the_baseline[257-1-0]"}),
+    "stream_open dynamic": _merge(_per_size(DNAT + "test_streams_return_the_bits_of_enhance_waves[%d-3-1-False]", [33, 65, 257, 513, 1025]),
+                                  {129: DNAT + "test_streams_return_the_bits_of_enhance_waves[129-1-0-False]"}),
+    "train_mix dynamic": _per_size(DNAT + "test_training_equals_host_stacked_rows[%d]"),
+    "wave_mfcc": {D: "tests/test_mel_gpu.py::test_wave_mfcc_matches_restatement[%s]" % i for D, i in MEL_IDS.items()},
+    "post_rows": _per_size(POST + "test_post_rows_equal_the_restatement[both-%d]"),
+    "gv_mix raw": _per_size(POST + "test_gv_mix_raw_equals_the_restated_sums[%d]"),
+    "gv_mix post": _per_size(POST + "test_gv_mix_post_equals_the_restated_sums[%d-static-False]"),
+    "enhance_waves post": _per_size(POST + "test_resynthesis_from_the_post_processed_rows[%d]"),
+    "stream_open post": _per_size(POST + "test_paths_agree_bit_for_bit[%d]"),
 }
 # the mask target at an odd column offset of a padded output row (out_col = D), streamed
 STREAM_MASK = _per_size("tests/test_stream_gpu.py::test_other_configurations[fea%d_mask]", [257, 1025])
+# Cells beside the table: a path that one size is enough for, because the kernel behind it is held at every size by a row above.
+EXTRA = {
+    "stream_open mask": STREAM_MASK,
+    # the packed (row-invariant) stream in dynamic mode, at the smallest and the largest size
+    "stream_open dynamic rowinv": _per_size(DNAT + "test_streams_return_the_bits_of_enhance_waves[%d-3-1-True]", [33, 1025]),
+    # bp_set_mix_aux: the MFCC columns of a mixing call behind a wide LPS block (two bins per thread)
+    "set_mix_aux": {257: "tests/test_mel_gpu.py::test_mfcc_columns_are_wave_mfcc_of_the_target_signal[lps+irm-257]"},
+}
+
+
+# Every bp_* symbol of include/bp_c_api.h: the COVERAGE rows that hold it at the six sizes (a tuple), or the reason it has no frame
+# size (a string).  A symbol whose prototype takes a fea_dim has rows, or a reason that begins with "host only".
+_HOST = "host only"
+_STEP = "the net's step: rows of any width, no fea_dim"
+_SAMPLES = "no fea_dim: sample-domain"
+_DP = "the data-parallel exchange: no fea_dim"
+_RBM = "pre-training: rows of any width, no fea_dim"
+_NET_STREAMS = ("stream_open", "stream_open rowinv", "stream_open dynamic", "stream_open post")
+_LM_STREAMS = ("logmmse_stream_open", "logmmse_stream_open spp")
+_MIX = ("mix_features", "mix_features dynamic")
+API = {
+    "bp_last_error": _HOST, "bp_abi_version": _HOST, "bp_build_target": _HOST, "bp_device_count": _HOST,
+    "bp_create": _STEP, "bp_destroy": _STEP, "bp_set_hyper": _STEP, "bp_set_output": _STEP, "bp_set_forward": _STEP,
+    "bp_train_chunk": _STEP, "bp_cv_chunk": _STEP, "bp_forward": _STEP, "bp_get_weights": _STEP, "bp_get_deltas": _STEP,
+    "bp_upload_chunk": _STEP, "bp_fill_chunk_synthetic": _STEP, "bp_train_resident": _STEP, "bp_sync": _STEP,
+    "bp_train_resident_masked": _STEP, "bp_upload_chunk_windows": _STEP, "bp_train_chunk_windows": _STEP,
+    "bp_cv_chunk_windows": _STEP, "bp_forward_windows": _STEP,
+    "bp_enhance_waves": ("enhance_waves lps", "enhance_waves mask", "enhance_waves dynamic", "enhance_waves post"),
+    "bp_wave_lps": ("wave_lps",),
+    # the mixing calls stage their rows with the kernels of bp_mix_features, then run the net's step
+    "bp_set_mix_corpus": _MIX, "bp_mix_features": _MIX, "bp_cv_mix": _MIX, "bp_train_mix": _MIX + ("train_mix dynamic",),
+    "bp_mix_plan": _HOST, "bp_mix_shuffle": _HOST,
+    "bp_mel_defaults": _HOST, "bp_mel_dct": _HOST,
+    "bp_mel_filters": _HOST + ": the filter table (tests/test_mel_host.py holds it at one geometry per size)",
+    "bp_wave_mfcc": ("wave_mfcc",), "bp_set_mix_aux": ("wave_mfcc",),
+    "bp_set_mix_reverb": _SAMPLES, "bp_reverb_waves": _SAMPLES, "bp_mix_rir_delay": _HOST, "bp_mix_reverb_pairs": _HOST,
+    "bp_rir_image": _SAMPLES, "bp_rir_orders": _HOST, "bp_rir_beta": _HOST, "bp_rir_rooms": _HOST,
+    "bp_score_waves": ("score_waves",), "bp_score_waves_ext": ("score_waves",),
+    "bp_eval_mix": ("eval_mix",), "bp_eval_mix_ext": ("eval_mix",),
+    "bp_logmmse_defaults": _HOST, "bp_noise_defaults": _HOST,
+    "bp_logmmse_waves": ("logmmse_waves",), "bp_logmmse_waves_nt": ("logmmse_waves", "logmmse_waves spp"),
+    # bit for bit their parts (tests/test_classic_gpu.py, tests/test_noise_gpu.py): the mixture, the baseline, the scores
+    "bp_eval_mix_logmmse": ("mix_features", "logmmse_waves", "score_waves"),
+    "bp_eval_mix_logmmse_ext": ("mix_features", "logmmse_waves", "score_waves"),
+    "bp_eval_mix_logmmse_nt": ("mix_features", "logmmse_waves", "logmmse_waves spp", "score_waves"),
+    "bp_stream_open": _NET_STREAMS, "bp_stream_push": _NET_STREAMS, "bp_stream_close": _NET_STREAMS, "bp_stream_packed": _HOST,
+    "bp_stream_counts": _HOST + ": frame counts (test_the_library_accepts_exactly_the_six_sizes probes every size)",
+    "bp_lmstream_open": ("logmmse_stream_open",), "bp_lmstream_open_nt": _LM_STREAMS, "bp_lmstream_push": _LM_STREAMS,
+    "bp_lmstream_close": _LM_STREAMS,
+    "bp_lmstream_counts": _HOST + ": frame counts (test_the_library_accepts_exactly_the_six_sizes probes every size)",
+    "bp_set_nat": ("enhance_waves dynamic", "mix_features dynamic", "stream_open dynamic", "train_mix dynamic"),
+    "bp_post_defaults": _HOST, "bp_set_post": ("enhance_waves post", "stream_open post", "gv_mix post"),
+    "bp_post_rows": ("post_rows",), "bp_gv_mix": ("gv_mix raw", "gv_mix post"),
+    "bp_gv_factors": _HOST + ": fea_dim is the length of the four sums (tests/test_post_host.py)",
+    "bp_resample_defaults": _HOST, "bp_resample_ratio": _HOST, "bp_resample_len": _HOST, "bp_resample_taps": _HOST,
+    "bp_resample_waves": _SAMPLES,
+    "bp_grads_resident": _STEP, "bp_grad_floats": _STEP, "bp_grad_layout": _STEP, "bp_read_grads": _STEP, "bp_read_layer_output": _STEP,
+    "bp_dp_attach": _DP, "bp_dp_attach_ex": _DP, "bp_dp_detach": _DP, "bp_dp_info": _DP, "bp_dp_peer_info": _DP, "bp_dp_handoff": _DP,
+    "bp_dp_barrier": _DP, "bp_dp_allgather": _DP, "bp_rdv_open": _HOST, "bp_rdv_barrier": _HOST, "bp_rdv_allgather": _HOST,
+    "bp_rdv_close": _HOST, "bp_host_register": _HOST, "bp_host_unregister": _HOST, "bp_device_pci_bus_id": _HOST,
+    "bp_last_train_ms": _STEP, "bp_time_kernel": _STEP, "bp_profile_step": _STEP, "bp_measure_peaks": _STEP,
+    "bp_rbm_defaults": _HOST, "bp_rbm_create": _RBM, "bp_rbm_destroy": _RBM, "bp_rbm_set_hyper": _RBM, "bp_rbm_train_chunk": _RBM,
+    "bp_rbm_up": _RBM, "bp_rbm_step": _RBM, "bp_rbm_steps": _RBM, "bp_rbm_get": _RBM,
+}
+
+
+def api_prototypes(header_text):
+    """{symbol: parameter text} of the bp_* prototypes of a C header: declarations that start a line (comments do not)."""
+    import re
+    return {m.group(1): m.group(2) for m in
+            re.finditer(r"^[A-Za-z_][A-Za-z0-9_ ]*[ *](bp_[a-z0-9_]+)\(([^;]*)\);", header_text, re.M)}
 
 
 def collected_ids(module_path):
@@ -110,7 +217,7 @@ def collected_ids(module_path):
             if m.name != "parametrize":
                 continue
             given = m.kwargs.get("ids")
-            axes.append([str(given[k]) if given else _value_id(v) for k, v in enumerate(m.args[1])])
+            axes.append([str(given(v) if callable(given) else given[k]) if given else _value_id(v) for k, v in enumerate(m.args[1])])
         out |= {"%s[%s]" % (name, "-".join(c)) for c in itertools.product(*axes)} if axes else {name}
     return out, mod
 
@@ -132,6 +239,14 @@ BARS = {
     "mix_features": [("lps_3", 1e-5), ("lps_4", 1e-5), ("irm_3", 1e-4), ("ibm_excluded_share", 1e-3)],
     "score_waves": [("ssnr_db", 1e-4), ("lsd_rel", 1e-3), ("lsd_rel_gpu_lps", 1e-5), ("stoi_abs", 1e-4)],
     "logmmse_waves": [("vad", 1e-4), ("pcm", 1e-4), ("gain_absY", 1e-4)],
+    "logmmse_waves spp": [("vad", 1e-4), ("pcm", 1e-4), ("gain_absY", 1e-4), ("noise", 1e-4)],
+    "enhance_waves dynamic": [("rows", 1e-4), ("net", 1e-4), ("busy_rows", 1e-4), ("busy_net", 1e-4)],
+    "mix_features dynamic": [("rows", 1e-4), ("baseline", 1e-4), ("busy_rows", 1e-4), ("busy_baseline", 1e-4)],
+    "wave_mfcc": [("sqrt_power_rel", WAVE_BAR), ("logmel_ulp", 5.0)],     # (the cepstrum: np.array_equal inside the test)
+    "enhance_waves post": [("wave_err", WAVE_BAR)],
+    "logmmse_stream_open spp": "bits", "stream_open dynamic": "bits", "stream_open post": "bits",
+    # "words": word for word with the restatement or the host-stacked run; the record counts the differing words, green is 0
+    "train_mix dynamic": "words", "post_rows": "words", "gv_mix raw": "words", "gv_mix post": "words",
 }
 
 
@@ -142,10 +257,16 @@ def cell_figure(entry, fea_dim, record):
     if BARS[entry] == "bits":
         n = int(record.get("samples_differing", 0))
         return "%d samples differ / 0" % n, n, 0
+    if BARS[entry] == "words":
+        have = [v for k, v in record.items() if k.startswith("words_differing")]
+        if not have:
+            return None
+        n = sum(sum(int(x) for x in v.values()) if isinstance(v, dict) else int(v) for v in have)
+        return "%d words differ / 0" % n, n, 0
     rec = dict(record)
     if "ibm_cells" in rec:
         rec["ibm_excluded_share"] = rec["ibm_excluded_cells"] / float(rec["ibm_cells"])
-    if entry == "logmmse_waves":                                 # per sentence (or per size, the wide call) a dict of the three
+    if entry in ("logmmse_waves", "logmmse_waves spp"):          # per sentence (or per size, the wide call) a dict of the three
         subs = [v for k, v in rec.items() if isinstance(v, dict) and (k[0].isdigit() or k == "fea_dim_%d" % fea_dim)]
         rec = {k: max(v[k] for v in subs) for k, _ in BARS[entry]} if subs else {}
     have = [(rec[k] / bar, k, rec[k], bar) for k, bar in BARS[entry] if k in rec]
@@ -165,8 +286,9 @@ def numbers_from_records(tests):
             assert fig is not None, "no record of %s in the parity JSON" % cell
             table[entry][str(D)] = fig[0]
             kept[cell] = tests[cell]
-    for cell in STREAM_MASK.values():
-        kept[cell] = tests[cell]
+    for row in EXTRA.values():
+        for cell in row.values():
+            kept[cell] = tests[cell]
     return {"table": table, "tests": kept}
 
 

@@ -15,6 +15,9 @@ GEOMETRIES = [
     dict(fea_dim=129, sample_rate=8000, n_mel=26, n_ceps=13, first_coef=0, lifter=22.0),
     dict(fea_dim=257, sample_rate=16000, n_mel=40, n_ceps=13, first_coef=0, lifter=22.0),
     dict(fea_dim=1025, sample_rate=16000, n_mel=64, n_ceps=20, first_coef=1, lifter=22.0),
+    # (appended: tests index the entries above by position)
+    dict(fea_dim=65, sample_rate=8000, n_mel=12, n_ceps=8, first_coef=0, lifter=22.0),
+    dict(fea_dim=513, sample_rate=16000, n_mel=48, n_ceps=16, first_coef=1, lifter=22.0),
 ]
 MUTANTS = ("edges_shifted", "j_for_j_half", "no_lifter", "log10", "c0_present")
 

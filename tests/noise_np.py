@@ -10,6 +10,9 @@ import classic_np as CN
 NOISE_DEFAULTS = dict(mode=1, xi_h1_db=15.0, q=0.5, a_pow=0.8, a_spp=0.9, p_lo=0.98, p_cap=0.99)
 MODE_VAD, MODE_SPP = 0, 1
 MUTANTS = ("no_ceiling", "hard_ceiling", "update_behind", "pbar_carried", "a_swapped", "no_c1")
+# A parameter set under which pbar climbs into the ramp in EVERY bin within a dozen frames of noise (at the defaults only the bins
+# of a sustained tone get there, after some 40 frames): the state a stream carries between pushes then moves every bin's lambda.
+BUSY = dict(q=0.9, xi_h1_db=0.0, a_spp=0.7, p_lo=0.4, p_cap=0.8)
 
 
 def constants(noise):
@@ -121,6 +124,15 @@ def step(seed, fea_dim):
     x[:n // 2] *= STEP_SIGMA[0]
     x[n // 2:] *= STEP_SIGMA[1]
     return np.round(x).astype(np.float32)
+
+
+def ceiling_share(x, fea_dim, noise):
+    """(ramp, full, share): the frame-bins inside the ramp and at the full ceiling, and the share of the bins whose lambda the
+    ceiling -- and so the carried pbar -- moves by more than 1e-3 somewhere in the sentence."""
+    Y = CN.analysis(np.asarray(x, np.float64), fea_dim)
+    r, m = recursion(Y, None, noise), recursion(Y, None, noise, mutant="no_ceiling")
+    moved = (np.abs(r["noise"] - m["noise"]) / r["noise"]).max(axis=0) > 1e-3
+    return r["ramp"], r["full"], float(moved.mean())
 
 
 def step_level_db(noise_rows, fea_dim):

@@ -5,13 +5,15 @@ Bars: the staged rows, and the de-normalised block read back through the selecto
 max|a - ref| / max|ref| < 1e-4 (tests/util.py) of the restatement on the call's own PCM, and of log(out_noise) of the baseline;
 the mode holds no decision, so no fixture needs a margin.  Everything else -- company, entry points, streams, training, residue,
 the tools -- bit for bit.  Shapes (dnat_np's case table): fea_dim 33 and 129, 257 once for the partial last 64-thread workgroup;
-sentences of 2 (the shortest there is), 3, 6, 7 and 40 frames in one batch; context 3 / targ_offset 1 and context 1."""
+sentences of 2 (the shortest there is), 3, 6, 7 and 40 frames in one batch; context 3 / targ_offset 1 and context 1.  The rows,
+the streams and the training also at the other sizes of the frame-size table (dnat_np.GEOMETRY; tests/geometry_cases.py)."""
 import subprocess
 
 import numpy as np
 import pytest
 
 import dnat_np as DN
+import noise_np as NN
 import stream_np as SN
 import wave_np as WN
 from util import TOL, relerr
@@ -56,7 +58,7 @@ def _split(pcm, lens):
 
 
 # ---- 1. the restatement and the baseline's tracker
-@pytest.mark.parametrize("D,ctx,toff", [(33, 3, 1), (33, 1, 0), (129, 3, 1), (257, 1, 0)])
+@pytest.mark.parametrize("D,ctx,toff", [(33, 3, 1), (33, 1, 0), (129, 3, 1), (257, 1, 0), (65, 3, 1), (513, 3, 1), (1025, 3, 1)])
 def test_rows_match_restatement_and_the_baseline(pkg, D, ctx, toff, parity_record):
     clean, noise = DN.sentences(D, D), _noise(D)
     g, mean, istd = _selector(pkg, D, ctx)
@@ -64,30 +66,37 @@ def test_rows_match_restatement_and_the_baseline(pkg, D, ctx, toff, parity_recor
         assert g.nat_mode == "dynamic"
         g.set_mix_corpus(clean, noise, mean, istd, ctx, toff)
         plan = _plan(pkg, len(clean), noise)
-        f = g.mix_features(plan)
-        lens = [clean[c].size for c in plan["clean"]]
-        T = [int(t) for t in g.mix_frames(plan)]
-        assert sorted(T) == list(DN.T_CLASSES) and f["nat"].shape == (sum(T), D) and np.isfinite(f["nat"]).all()
-        mix = _split(f["pcm"], lens)
-        ref, _ = DN.batch(mix, D, mean, istd)
-        e_rows = relerr(f["nat"], ref)
-        # through the net: bp_enhance_waves on the same samples returns the de-normalised block as its output
-        _, net = g.enhance_waves(mix, mean, istd, ctx, toff, return_net=True)
-        net = np.concatenate(net)
-        e_net = relerr(net, DN.denormalise(ref, mean, istd))
-        # the baseline's out_noise on the same PCM, default parameters
-        _, noise_rows = pkg.logmmse_waves(0, D, mix, noise="spp", return_noise=True)
-        lam32 = np.concatenate(noise_rows)
-        e_base = relerr(DN.denormalise(f["nat"], mean, istd), np.log(lam32.astype(np.float64)))
-        # the two analyses share Y's bits and the tracker: the rows are the fp32 expression of the baseline's fl32 lambdas, up to
-        # the last bits of logf against numpy's log (the lambdas themselves are not visible through the logarithm)
-        host = (np.log(lam32).astype(np.float32) - mean) * istd
-        e_bits = relerr(f["nat"], host)
-        print(D, ctx, dict(rows=e_rows, net=e_net, baseline=e_base, fp32_expression=e_bits))
-        parity_record(fea_dim=D, context=ctx, rows=e_rows, net=e_net, baseline=e_base, fp32_expression=e_bits)
-        assert e_rows < TOL and e_net < TOL and e_base < TOL
-        # (4 ulp of a float in [16, 32) -- logf against log, the subtraction -- times inv_std <= 0.5, over max|row| >= 1)
-        assert np.abs(host).max() >= 1.0 and istd.max() <= 0.5 and e_bits < 4 * 2.0 ** -19 * 0.5
+        # at the tracker's defaults, and under noise_np.BUSY, where pbar reaches the ramp in every bin within these short sentences
+        # (tests/test_noise_host.py): at the defaults the ceiling of the definition never acts on them
+        for tag, params in (("", None), ("busy_", NN.BUSY)):
+            g.set_nat("dynamic", params)
+            f = g.mix_features(plan)
+            lens = [clean[c].size for c in plan["clean"]]
+            T = [int(t) for t in g.mix_frames(plan)]
+            assert sorted(T) == list(DN.T_CLASSES) and f["nat"].shape == (sum(T), D) and np.isfinite(f["nat"]).all()
+            mix = _split(f["pcm"], lens)
+            ref, _ = DN.batch(mix, D, mean, istd, params)
+            e_rows = relerr(f["nat"], ref)
+            # through the net: bp_enhance_waves on the same samples returns the de-normalised block as its output
+            _, net = g.enhance_waves(mix, mean, istd, ctx, toff, return_net=True)
+            net = np.concatenate(net)
+            e_net = relerr(net, DN.denormalise(ref, mean, istd))
+            # the baseline's out_noise on the same PCM and parameters
+            _, noise_rows = pkg.logmmse_waves(0, D, mix, noise=params or "spp", return_noise=True)
+            lam32 = np.concatenate(noise_rows)
+            e_base = relerr(DN.denormalise(f["nat"], mean, istd), np.log(lam32.astype(np.float64)))
+            # the two analyses share Y's bits and the tracker: the rows are the fp32 expression of the baseline's fl32 lambdas, up to
+            # the last bits of logf against numpy's log (the lambdas themselves are not visible through the logarithm)
+            host = (np.log(lam32).astype(np.float32) - mean) * istd
+            e_bits = relerr(f["nat"], host)
+            print(D, ctx, tag, dict(rows=e_rows, net=e_net, baseline=e_base, fp32_expression=e_bits))
+            parity_record(fea_dim=D, context=ctx, **{tag + "rows": e_rows, tag + "net": e_net, tag + "baseline": e_base,
+                                                     tag + "fp32_expression": e_bits})
+            assert e_rows < TOL and e_net < TOL and e_base < TOL
+            # (4 ulp of a float in [16, 32) -- logf against log, the subtraction -- times inv_std <= 0.5, over max|row| >= 1)
+            assert np.abs(host).max() >= 1.0 and istd.max() <= 0.5 and e_bits < 4 * 2.0 ** -19 * 0.5
+            if params is not None:
+                assert relerr(ref, DN.batch(mix, D, mean, istd)[0]) > 10 * TOL          # (the parameters are read)
         # static mode on the same handle: one row per mixture again
         g.set_nat("static")
         assert g.mix_features(plan)["nat"].shape == (len(plan), D)
@@ -114,6 +123,10 @@ def test_a_sentence_alone_and_in_the_batch_and_twice(pkg, D):
         g.close()
 
 
+def _differing(got, want):
+    return sum(int((_bits(a) != _bits(b)).sum()) if a.shape == b.shape else max(a.size, b.size) for a, b in zip(got, want))
+
+
 def _play(stream, feeds, hop, rng, end_early=None):
     """feeds: per channel a list of sentences, played one after the other in ragged blocks; returns per channel the output."""
     nc = len(feeds)
@@ -136,9 +149,11 @@ def _play(stream, feeds, hop, rng, end_early=None):
     return [np.concatenate(o) for o in out]
 
 
-@pytest.mark.parametrize("packed", [False, True])
-@pytest.mark.parametrize("D,ctx,toff", [(33, 3, 1), (129, 1, 0)])
-def test_streams_return_the_bits_of_enhance_waves(pkg, D, ctx, toff, packed):
+# (every size of the frame-size table unpacked -- bp_stream_dnat with 1, 2, 3, 5, 9 and 17 workgroups per job -- and the packed form
+# at the smallest and the largest)
+@pytest.mark.parametrize("D,ctx,toff,packed", [(33, 3, 1, False), (33, 3, 1, True), (129, 1, 0, False), (129, 1, 0, True), (65, 3, 1, False),
+                                               (257, 3, 1, False), (513, 3, 1, False), (1025, 3, 1, False), (1025, 3, 1, True)])
+def test_streams_return_the_bits_of_enhance_waves(pkg, D, ctx, toff, packed, parity_record):
     hop = D - 1
     xs = DN.sentences(9, D)                                      # (2 and 3 frames: the sentence ends before the sixth frame)
     mean, istd = DN.norm(D)
@@ -158,6 +173,7 @@ def test_streams_return_the_bits_of_enhance_waves(pkg, D, ctx, toff, packed):
         finally:
             s.close()
         want = [np.concatenate([ref[4], ref[0], ref[2]]), np.concatenate([ref[1], ref[3]])]
+        differing = _differing(got, want)
         assert _same(got, want)
         # ... and one opened before bp_set_nat keeps the static row
         stat = [g.enhance_waves([x], mean, istd, ctx, toff)[0] for x in xs]
@@ -170,6 +186,20 @@ def test_streams_return_the_bits_of_enhance_waves(pkg, D, ctx, toff, packed):
         finally:
             s.close()
         assert _same(got, [np.concatenate([stat[4], stat[0], stat[2]]), np.concatenate([stat[1], stat[3]])])
+        # under noise_np.BUSY the pbar a channel carries between pushes moves every bin of these short sentences
+        # (tests/test_noise_host.py); at the defaults it never reaches the ramp, and a stream that lost it would return the same bits
+        g.set_nat("dynamic", NN.BUSY)
+        busy = [g.enhance_waves([x], mean, istd, ctx, toff)[0] for x in xs]
+        assert not _same(busy, ref)
+        s = g.stream_open(mean, istd, ctx, toff, n_chan=2, max_push_samples=2 * 9 * hop)
+        try:
+            got = _play(s, feeds, hop, np.random.default_rng(2))
+        finally:
+            s.close()
+        want = [np.concatenate([busy[4], busy[0], busy[2]]), np.concatenate([busy[1], busy[3]])]
+        differing += _differing(got, want)
+        parity_record(fea_dim=D, packed=packed, samples_differing=differing)
+        assert differing == 0
     finally:
         g.close()
 
@@ -202,8 +232,8 @@ def test_eval_mix_and_cv_mix_are_their_parts(pkg, D):
 
 
 # ---- 3. training: a window meets its own frame's row after the shuffle
-@pytest.mark.parametrize("D", DN.FEA_DIMS)
-def test_training_equals_host_stacked_rows(pkg, D):
+@pytest.mark.parametrize("D", DN.ALL_DIMS)
+def test_training_equals_host_stacked_rows(pkg, D, parity_record):
     ctx, toff = 3, 1
     clean, noise = DN.sentences(21, D), _noise(D)
     mean, istd = DN.norm(D)
@@ -223,6 +253,8 @@ def test_training_equals_host_stacked_rows(pkg, D):
         b.train(n, np.ascontiguousarray(x[order]), np.ascontiguousarray(f["targ"][order]))
         (wa, ba), (wb, bb) = a.get_weights(), b.get_weights()
         w0, _ = pkg.glorot_net(a.layersizes, seed=5, beta=0.5)
+        parity_record(fea_dim=D, rows=n, words_differing=sum(int((_bits(wa[l]) != _bits(wb[l])).sum()) + int((_bits(ba[l]) != _bits(bb[l])).sum())
+                                                             for l in range(1, a.numlayers)))
         for l in range(1, a.numlayers):
             assert not np.array_equal(wa[l].reshape(-1), np.asarray(w0[l], np.float32).reshape(-1))      # (it trained)
             assert np.array_equal(wa[l], wb[l]) and np.array_equal(ba[l], bb[l]), l

@@ -45,26 +45,29 @@ def test_dynamic_rows_follow_a_step_and_the_static_row_does_not(D):
 
 
 def test_wrong_stagings_miss_the_bar(record_property):
-    D = 33
-    xs = DN.sentences(5, D)
-    mean, istd = DN.norm(D)
-    good = DN.blocks(xs, D, mean, istd)
-    assert good.shape == (sum(DN.T_CLASSES), D)
-    for m in DN.MUTANTS:
-        bad = DN.blocks(xs, D, mean, istd, m)
-        assert bad.shape == good.shape
-        factor = relerr(bad, good) / TOL
-        print("%-24s misses the bar by a factor of %.0f" % (m, factor))
-        record_property(m, factor)
-        assert factor > 10.0, (m, factor)
+    """At every size the GPU test holds rows at (dnat_np.ALL_DIMS), on sentences of its frame classes; one factor per size and mutant."""
+    for D in DN.ALL_DIMS:
+        xs = DN.sentences(5, D)
+        mean, istd = DN.norm(D)
+        good = DN.blocks(xs, D, mean, istd)
+        assert good.shape == (sum(DN.T_CLASSES), D)
+        for m in DN.MUTANTS:
+            bad = DN.blocks(xs, D, mean, istd, m)
+            assert bad.shape == good.shape
+            factor = relerr(bad, good) / TOL
+            print("fea_dim %4d %-24s misses the bar by a factor of %.0f" % (D, m, factor))
+            record_property("%s_%d" % (m, D), factor)
+            assert factor > 10.0, (D, m, factor)
 
 
 def test_case_table_has_no_empty_cell():
     have = {(c["mode"], c["entry"], c["fea_dim"], c["T"]) for c in DN.cases()}
     want = set(itertools.product(DN.MODES, DN.ENTRIES, DN.FEA_DIMS, DN.T_CLASSES))
     assert have == want and len(DN.cases()) == len(want)
-    for D in DN.FEA_DIMS + (DN.WIDE,):
+    assert list(DN.ALL_DIMS) == [33, 65, 129, 257, 513, 1025] and [-(-D // 64) for D in DN.ALL_DIMS] == [1, 2, 3, 5, 9, 17]
+    for D in DN.ALL_DIMS:
         assert [WN.n_frames(n, D) for n in DN.lengths(D)] == list(DN.T_CLASSES)
+        assert max(DN.lengths(D)) <= 39 * (D - 1)                 # nothing longer than the 40-frame class
     assert min(DN.T_CLASSES) < 6 < max(DN.T_CLASSES) and 6 in DN.T_CLASSES and 7 in DN.T_CLASSES
     assert DN.WIDE % 64 == 1                                      # a last workgroup with one live lane
 

@@ -14,7 +14,10 @@ import geometry_cases as GC
 import wave_np as WN
 
 ENTRY_POINTS = ["wave_lps", "enhance_waves lps", "enhance_waves mask", "stream_open", "stream_open rowinv", "mix_features",
-                "score_waves", "logmmse_waves", "logmmse_stream_open", "eval_mix"]
+                "score_waves", "logmmse_waves", "logmmse_stream_open", "eval_mix",
+                # the entry points added after the table was first closed
+                "logmmse_waves spp", "logmmse_stream_open spp", "enhance_waves dynamic", "mix_features dynamic", "stream_open dynamic",
+                "train_mix dynamic", "wave_mfcc", "post_rows", "gv_mix raw", "gv_mix post", "enhance_waves post", "stream_open post"]
 
 
 def _accepted(pkg, call):
@@ -39,7 +42,7 @@ def test_every_cell_names_a_gpu_test_that_exists():
     cells = [(entry, D, cell) for entry, row in GC.COVERAGE.items() for D, cell in row.items()]
     for entry, row in GC.COVERAGE.items():
         assert sorted(row) == GC.FEA_DIMS, "%s: a cell for each of %s, none left at 'never'" % (entry, GC.FEA_DIMS)
-    cells += [("stream_open mask", D, cell) for D, cell in GC.STREAM_MASK.items()]
+    cells += [(entry, D, cell) for entry, row in GC.EXTRA.items() for D, cell in row.items()]
     ids = {}
     for entry, D, cell in cells:
         path, test = cell.split("::")
@@ -52,7 +55,29 @@ def test_every_cell_names_a_gpu_test_that_exists():
         marks = (marks if isinstance(marks, list) else [marks]) + list(getattr(fn, "pytestmark", []))
         assert any(m.name == "gpu" for m in marks), cell
         assert not any(m.name in ("skip", "skipif", "xfail") for m in marks), cell
-    assert sorted(GC.STREAM_MASK) == [257, 1025]
+    assert sorted(GC.STREAM_MASK) == [257, 1025] and GC.EXTRA["stream_open mask"] is GC.STREAM_MASK
+    assert sorted(GC.EXTRA["stream_open dynamic rowinv"]) == [33, 1025] and sorted(GC.EXTRA["set_mix_aux"]) == [257]
+
+
+def test_every_symbol_of_the_c_api_is_classified():
+    """include/bp_c_api.h against geometry_cases.API: every prototype is mapped to the rows that hold it or to the reason it has
+    no frame size, every row is named by a symbol, and a prototype that takes a fea_dim has rows unless it is host only.  An
+    entry point added to the header fails here until it is classified."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    protos = GC.api_prototypes(open(os.path.join(root, "include", "bp_c_api.h")).read())
+    assert len(protos) > 100 and "bp_enhance_waves" in protos and "bp_last_error" in protos
+    missing, stale = sorted(set(protos) - set(GC.API)), sorted(set(GC.API) - set(protos))
+    assert not missing, "include/bp_c_api.h declares %s: give each its COVERAGE rows or a reason in geometry_cases.API" % missing
+    assert not stale, "geometry_cases.API names %s, which include/bp_c_api.h does not declare" % stale
+    named = set()
+    for sym, what in GC.API.items():
+        if isinstance(what, tuple):
+            assert what and all(r in GC.COVERAGE for r in what), "%s: %s holds no such row" % (sym, [r for r in what if r not in GC.COVERAGE])
+            named |= set(what)
+        else:
+            assert isinstance(what, str) and what.strip(), sym
+            assert "fea_dim" not in protos[sym] or what.startswith("host only"), "%s takes a fea_dim: name its rows" % sym
+    assert named == set(GC.COVERAGE), "rows that no symbol names: %s" % sorted(set(GC.COVERAGE) - named)
 
 
 def test_the_cells_of_one_test_carry_its_size():
@@ -96,5 +121,7 @@ def test_committed_numbers_hold_a_figure_below_its_bar_for_every_cell():
             text, value, bar = fig
             assert num["table"][entry][str(D)] == text
             assert value <= bar and np.isfinite(value), (cell, text)
-    for cell in GC.STREAM_MASK.values():
-        assert num["tests"][cell]["samples_differing"] == 0
+    for row in GC.EXTRA.values():
+        for cell in row.values():
+            rec = num["tests"][cell]
+            assert rec.get("samples_differing", rec.get("words_differing")) == 0, cell

@@ -3,8 +3,8 @@ tests/mel_np.py, their properties, the range rules, the mutants of the definitio
 would use the device.
 
 Mutant factors on the GPU tests' own inputs (test_mutants_miss_the_gpu_bars; the bars are those of tests/test_mel_gpu.py: 2 fp32 ulp
-on logmel, bit equality on the coefficients, counted here as 1 ulp), smallest over the four geometries: edges shifted one bin
-2.7e5 x the logmel bar, log10 for ln 4.0e6 x, j for j + 0.5 5.6e9 ulp, lifter dropped 1.5e7 ulp, c0 present 2.2e9 ulp (the ulp is
+on logmel, bit equality on the coefficients, counted here as 1 ulp), smallest over the six geometries (one per frame size): edges
+shifted one bin 2.6e5 x the logmel bar, log10 for ln 3.8e6 x, j for j + 0.5 5.6e9 ulp, lifter dropped 1.5e7 ulp, c0 present 1.5e9 ulp (the ulp is
 that of the true value, and some true coefficients lie near zero).  A mutant is left out where it is the definition itself: the
 lifter at L = 0, c0 at first_coef = 0."""
 import os
@@ -97,6 +97,7 @@ def test_defaults(pkg):
 
 
 def test_the_four_geometries_hold_no_empty_filter_and_26_filters_do_not_fit_33_bins(pkg):
+    assert sorted(g["fea_dim"] for g in MN.GEOMETRIES) == [33, 65, 129, 257, 513, 1025]        # (six by now: one per frame size)
     for g in MN.GEOMETRIES:
         _, _, nb = MN.filters(g)
         assert nb.min() >= 1

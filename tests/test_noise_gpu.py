@@ -4,7 +4,9 @@ are made of.
 
 Bars: G |Y_ref|, out_pcm, out_vad and out_noise within the project's bar max|a - ref| / max|ref| < 1e-4 per sentence
 (tests/util.py); tracker mode holds no decision, so no fixture needs a margin.  Everything else -- VAD mode against the calls
-without noise parameters, company, streams, the evaluation, the tools -- bit for bit."""
+without noise parameters, company, streams, the evaluation, the tools -- bit for bit.  The streams run at every frame size
+(tests/geometry_cases.py), at the defaults and under noise_np.BUSY: only there does the pbar a channel carries between pushes
+move every bin, so only there does "the offline bits" say something about that state."""
 import subprocess
 
 import numpy as np
@@ -164,8 +166,52 @@ def _play(pkg, s, chans, hop):
     return [[np.concatenate(s) for s in o[:-1]] for o in out]
 
 
-@pytest.mark.parametrize("D", [33, 129])
+def _wide_plan(x, hop, schedule):
+    """The sentence in hop-sized blocks or as one block, the end flag on the last."""
+    sizes = [x.size] if schedule == "one" else [hop] * (x.size // hop) + ([x.size % hop] if x.size % hop else [])
+    pos = np.concatenate([[0], np.cumsum(sizes)])
+    return [(x[pos[j]:pos[j + 1]], j == len(sizes) - 1) for j in range(len(sizes))]
+
+
+def _wide_streams(pkg, D, noise):
+    """fea_dim 513 and 1025 (3 and 5 bins per thread): the third sentence of classic_np's wide call and, on a second channel, the
+    first one, so that the per-channel state is read at a stride of D with several bins per thread; the schedules "hop" and "one"
+    as tests/test_lmstream_gpu.py::test_wide_spectra plays them.  Returns the samples that differ from the offline call."""
+    xs = [w for w in CN.wide_fixtures() if w[0] == D][0][1]
+    sents = [xs[2], xs[0]]
+    ref = [pkg.logmmse_waves(0, D, [x], noise=noise)[0] for x in sents]
+    assert not np.array_equal(_bits(ref[0]), _bits(pkg.logmmse_waves(0, D, [sents[0]], noise="vad")[0]))
+    differing = 0
+    empty = np.zeros(0, np.float32)
+    for schedule in ("hop", "one"):
+        plans = [_wide_plan(x, D - 1, schedule) for x in sents]
+        out = [[] for _ in sents]
+        with pkg.logmmse_stream_open(0, D, n_chan=2, max_push_samples=sum(x.size for x in sents), noise=noise) as s:
+            for k in range(max(len(p) for p in plans)):
+                items = [p[k] if k < len(p) else (empty, False) for p in plans]
+                for c, y in enumerate(s.push([b for b, _ in items], [e for _, e in items])):
+                    out[c].append(y)
+        for c, r in enumerate(ref):
+            y = np.concatenate(out[c])
+            assert y.shape == r.shape, (D, schedule, c)
+            differing += int((_bits(y) != _bits(r)).sum())
+    return differing
+
+
+@pytest.mark.parametrize("D", [33, 65, 129, 257, 513, 1025])
 def test_tracker_streams_return_the_offline_bits(pkg, D, parity_record):
+    if D > 257:
+        # at the defaults, and under noise_np.BUSY: the carried pbar then moves every bin (tests/test_noise_host.py), and the offline
+        # call the stream is compared with is itself held to the restatement under these parameters
+        x = [w for w in CN.wide_fixtures() if w[0] == D][0][1][2]
+        e = _errors(pkg.logmmse_waves(0, D, [x], noise=NN.BUSY, return_gain=True, return_vad=True, return_noise=True), 0,
+                    NN.enhance(x, D, noise=NN.BUSY))
+        differing = {"defaults": _wide_streams(pkg, D, "spp"), "busy": _wide_streams(pkg, D, NN.BUSY)}
+        print(D, e, differing)
+        parity_record(fea_dim=D, sentences=2, samples_differing=sum(differing.values()), by_parameters=differing, offline_busy=e)
+        assert max(e.values()) < TOL, (D, e)
+        assert differing == {"defaults": 0, "busy": 0}
+        return
     _, kinds, xs = NN.fixture(D)
     ref = _spp(pkg, D)[0]
     sus, ton = kinds.index("sustained"), kinds.index("tones")
@@ -179,7 +225,14 @@ def test_tracker_streams_return_the_offline_bits(pkg, D, parity_record):
         assert len(got[c]) == len(o)
         for y, i in zip(got[c], o):
             assert np.shape(y) == np.shape(ref[i]) and np.array_equal(_bits(y), _bits(ref[i])), (D, c, kinds[i])
-    parity_record(fea_dim=D, sentences=sum(len(o) for o in order), samples_differing=0)
+    # under noise_np.BUSY the carried pbar moves every bin (tests/test_noise_host.py), not only those of a sustained tone
+    ref_busy = pkg.logmmse_waves(0, D, xs, noise=NN.BUSY)
+    with pkg.logmmse_stream_open(0, D, n_chan=3, max_push_samples=3 * 16000, noise=NN.BUSY) as s:
+        busy = _play(pkg, s, chans, D - 1)
+    differing = sum(int((_bits(y) != _bits(ref_busy[i])).sum()) if y.shape == ref_busy[i].shape else max(y.size, ref_busy[i].size)
+                    for c, o in enumerate(order) for y, i in zip(busy[c], o))
+    parity_record(fea_dim=D, sentences=sum(len(o) for o in order), samples_differing=differing)
+    assert differing == 0 and not _same(ref_busy, ref)
     # a VAD-mode stream opened with noise parameters against one opened without, on the same pushes
     with pkg.logmmse_stream_open(0, D, n_chan=3, max_push_samples=3 * 16000, noise="vad") as a:
         new = _play(pkg, a, chans, D - 1)

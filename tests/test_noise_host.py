@@ -47,6 +47,20 @@ def test_the_tracker_follows_a_step_and_the_vad_gated_estimate_does_not(D):
     assert spp >= -2.5 and vad <= -5.0
 
 
+def test_the_busy_parameters_make_the_carried_pbar_matter_in_every_bin():
+    """The stream tests compare with the offline call bit for bit; that says something about the pbar a stream carries between
+    pushes only where pbar reaches the ramp.  At the defaults that is a few tone bins of the 62-frame sentence and none at all of
+    the wide sentences (a dozen frames); under noise_np.BUSY it is every bin, at every size."""
+    cases = [(D, NN.fixture(D)[2][0]) for D in FEA_DIMS] + [(D, x) for D, xs in CN.wide_fixtures() for x in (xs[2], xs[0])]
+    assert sorted({D for D, _ in cases}) == [33, 65, 129, 257, 513, 1025]
+    for D, x in cases:
+        ramp, full, share = NN.ceiling_share(x, D, NN.BUSY)
+        print("fea_dim %d, %d samples: %d frame-bins inside the ramp, %d at the ceiling, %.3f of the bins moved" % (D, x.size, ramp, full, share))
+        assert ramp > 0 and full > 0 and share == 1.0, (D, x.size)
+        if D > 257:
+            assert NN.ceiling_share(x, D, None)[:2] == (0, 0)         # the defaults never get there in a dozen frames
+
+
 def test_vad_mode_is_the_classic_restatement():
     D = 129
     i, x = _sentence(D, "tones")

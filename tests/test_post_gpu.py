@@ -2,8 +2,12 @@
 the restatement in tests/post_np.py.  The value and the sums are held to the bit (np.array_equal); resynthesis from the
 post-processed rows to 1e-5 of the largest magnitude, the bar tests/test_wave_gpu.py holds resynthesis to.
 
-Shapes: fea_dim 33 and 129; sentences of 1, 31, 500 and 3000 samples; a corpus of three clean sentences (31, 500, 3000 samples) and
-two noises; nets 3 D -> 64 -> 2 D with a logistic mask block."""
+Shapes: every frame size of the signal layer (tests/geometry_cases.py).  At fea_dim 33 and 129 sentences of 1, 31, 500 and 3000
+samples and a corpus of three clean sentences (31, 500, 3000 samples); at the other four sizes nothing longer than 12 hop + 7
+samples (14 frames): sentences of 1, hop + 1, 5 hop + 3 and 12 hop + 7 samples, clean sentences of 2, 5 and 14 frames.  Two
+noises; nets 3 D -> 64 -> 2 D with a logistic mask block.  What changes with the size: the bins per thread of the synthesis
+kernels (one up to 257, two at 513, four at 1025) and the large LDS layout of the stream synthesis from 257 on, and the
+ceil(D / 64) column blocks of the two sum kernels (1, 2 -- the second with one live thread -- 3, 5, 9, 17)."""
 import subprocess
 
 import numpy as np
@@ -14,9 +18,8 @@ import wave_np as WN
 
 pytestmark = pytest.mark.gpu
 
-DIMS = [33, 129]
-LENS = [1, 31, 500, 3000]
-CLEAN = [31, 500, 3000]
+DIMS = [33, 65, 129, 257, 513, 1025]
+LONG = (33, 129)                                                         # the sizes that keep the long sentences
 FS = 8000
 GATE = dict(mask_lo=0.3, mask_hi=0.7, mask_weight=0.8)
 
@@ -51,23 +54,36 @@ def _gv(D):
     return rng.normal(0.5, 0.3, D).astype(np.float32), rng.uniform(1.1, 1.9, D).astype(np.float32)
 
 
+def _lens(D):
+    hop = D - 1
+    return [1, 31, 500, 3000] if D in LONG else [1, hop + 1, 5 * hop + 3, 12 * hop + 7]
+
+
+def _clean_lens(D):
+    hop = D - 1
+    return [31, 500, 3000] if D in LONG else [hop - 1, 3 * hop + 5, 12 * hop + 7]
+
+
 def _corpus(D):
     rng = np.random.default_rng(7 + D)
-    clean = WN.make_sentences(rng, CLEAN)
+    clean = WN.make_sentences(rng, _clean_lens(D))
     noise = [np.round(rng.normal(0, 1500, 5000)).astype(np.float32), np.round(rng.normal(0, 300, 777)).astype(np.float32)]
     return clean, noise
 
 
 # Frame counts of a bp_gv_mix call (64 parts): below 64, where some parts are empty; a multiple of 64; one frame more; about 700.
-# The clean entries have 2, 17 and 95 frames at fea_dim 33 and 2, 5 and 25 at 129.
+# The clean entries have 2, 17 and 95 frames at fea_dim 33 and 2, 5 and 25 at 129; 2, 5 and 14 at the other sizes, where the
+# largest call has 187 frames: three frames per part, part 62 with one frame and part 63 empty.
+SHORT = {7: [1, 0], 64: [2, 2, 2, 2, 0, 0, 0, 0], 65: [2, 2, 2, 2, 1, 0, 0], 187: [2] * 13 + [1]}
 PLANS = {33: {19: [1, 0], 128: [2, 1] + [0] * 8, 129: [2, 1, 1], 699: [2] * 7 + [1, 1]},
-         129: {7: [1, 0], 64: [2, 2, 1, 1, 0, 0], 65: [2, 2, 1, 1, 1], 700: [2] * 28}}
+         129: {7: [1, 0], 64: [2, 2, 1, 1, 0, 0], 65: [2, 2, 1, 1, 1], 700: [2] * 28},
+         65: SHORT, 257: SHORT, 513: SHORT, 1025: SHORT}
 
 
 def _plan(pkg, D, frames):
     """The plan of the corpus with exactly `frames` frames."""
     idx = PLANS[D][frames]
-    assert sum((CLEAN[c] - 1) // (D - 1) + 2 for c in idx) == frames
+    assert sum((_clean_lens(D)[c] - 1) // (D - 1) + 2 for c in idx) == frames
     p = np.zeros(len(idx), pkg.MIXTURE_DTYPE)
     for i, c in enumerate(idx):
         p[i] = (c, i % 2, (37 * i) % 700, float(5 * (i % 3)))
@@ -77,7 +93,7 @@ def _plan(pkg, D, frames):
 def _mixtures(g, plan):
     """The mixed sentences of the plan and the noisy LPS rows of the device."""
     f = g.mix_features(plan)
-    lens = [CLEAN[c] for c in plan["clean"]]
+    lens = [g.mix_clean_len[c] for c in plan["clean"]]
     return np.split(f["pcm"], np.cumsum(lens)[:-1]), f["lps"]
 
 
@@ -181,9 +197,9 @@ def test_gv_mix_raw_equals_the_restated_sums(pkg, raw_case, D, parity_record):
     assert _sums_equal(g.gv_mix(c["plan"], out_col=D), PN.gv_sums(c["net"][:, D:], c["ref"])) == 0
 
 
-@pytest.mark.parametrize("bf16", [False, True])
-@pytest.mark.parametrize("nat", ["static", "dynamic"])
-@pytest.mark.parametrize("D", DIMS)
+# (the bf16 x dynamic cross at fea_dim 33 and 129; the other four sizes in fp32 with the static row)
+@pytest.mark.parametrize("D,nat,bf16", [(D, nat, bf16) for D in LONG for nat in ("static", "dynamic") for bf16 in (False, True)] +
+                         [(D, "static", False) for D in DIMS if D not in LONG])
 def test_gv_mix_post_equals_the_restated_sums(pkg, D, bf16, nat, parity_record):
     """The fused value, pinned to the bit: the sums of post_np over the net's columns and the device's noisy LPS.  Nets with the
     noise-aware block (context 2: 3 D inputs), in both of its modes."""
@@ -222,7 +238,7 @@ def test_gv_mix_post_equals_the_restated_sums(pkg, D, bf16, nat, parity_record):
 @pytest.mark.parametrize("D", DIMS)
 def test_resynthesis_from_the_post_processed_rows(pkg, D, parity_record):
     rng = np.random.default_rng(40 + D)
-    xs = WN.make_sentences(rng, LENS)
+    xs = WN.make_sentences(rng, _lens(D))
     mean, istd = _norm(D)
     c, s = _gv(D)
     g = _handle(pkg, D)
@@ -306,7 +322,7 @@ def test_paths_agree_bit_for_bit(pkg, D, parity_record):
     c, s = _gv(D)
     post = dict(gv_center=c, gv_scale=s, mask_col=D, **GATE)
     plan = _plan(pkg, D, _frame_counts(D)[2])
-    xs = WN.make_sentences(np.random.default_rng(50 + D), LENS)
+    xs = WN.make_sentences(np.random.default_rng(50 + D), _lens(D))
     hop = D - 1
     g, fresh = _handle(pkg, D), _handle(pkg, D)
     try:
