@@ -194,11 +194,19 @@ API = {
 }
 
 
+_PROTOTYPE = r"^([A-Za-z_][A-Za-z0-9_ ]*[ *])(bp_[a-z0-9_]+)\(([^;]*)\);"
+
+
 def api_prototypes(header_text):
     """{symbol: parameter text} of the bp_* prototypes of a C header: declarations that start a line (comments do not)."""
     import re
-    return {m.group(1): m.group(2) for m in
-            re.finditer(r"^[A-Za-z_][A-Za-z0-9_ ]*[ *](bp_[a-z0-9_]+)\(([^;]*)\);", header_text, re.M)}
+    return {m.group(2): m.group(3) for m in re.finditer(_PROTOTYPE, header_text, re.M)}
+
+
+def api_return_types(header_text):
+    """{symbol: return type text} of the same prototypes."""
+    import re
+    return {m.group(2): " ".join(m.group(1).split()) for m in re.finditer(_PROTOTYPE, header_text, re.M)}
 
 
 def collected_ids(module_path):
