@@ -23,7 +23,7 @@ import numpy as np
 
 from ._abi import (BPConfig, BPError, BPMelParams, BPMixCorpus, BPMixReverb, BPStreamConfig, BPWaveChunk, BPWindowChunk, Closing,
                    FORWARD_DEFAULT, GV_STAGES, MAXLAYER, MIX_LPS, MIX_TARGETS, MIXTURE_DTYPE, NAT_MODES, PROF_KINDS, REVERB_TARGETS,
-                   WAVE_LPS, check, flat32, load_library, pack, ptr, ptrs, split)
+                   WAVE_LPS, check, flat32, load_library, pack, ptr, ptrs, score_columns, split)
 from .signal import logmmse_params, noise_params, post_params, stream_push
 
 __all__ = ["BP_GPU", "Stream", "Rendezvous", "device_count", "device_pci_bus_id"]
@@ -428,26 +428,28 @@ class BP_GPU(Closing):
         """bp_eval_mix: the plan's mixtures made on the device, enhanced with this net and scored against their clean sentences.
         dict of noisy [n_mix][3] and enhanced [n_mix][3] float32 scores (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where
         undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None.  extended: bp_eval_mix_ext with five
-        columns, SCORE_ESTOI and SCORE_SISDR behind the same three."""
+        columns, SCORE_ESTOI and SCORE_SISDR behind the same three; extended="full": seven, SCORE_LLR and SCORE_CD behind those
+        (any other value: BPError)."""
+        ns = score_columns("eval_mix", extended)
         p, pp = self._plan(plan)
         self._push_hyper()
         args = (self._h, p.size, pp, int(sample_rate), int(target), int(out_col))
-        if extended:
-            return self._eval(p, 5, return_pcm, self._lib.bp_eval_mix_ext, *(args + (5,)))
+        if ns != 3:
+            return self._eval(p, ns, return_pcm, self._lib.bp_eval_mix_ext, *(args + (ns,)))
         return self._eval(p, 3, return_pcm, self._lib.bp_eval_mix, *args)
 
     def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False, extended=False, noise=None):
         """bp_eval_mix_logmmse: eval_mix with the log-MMSE baseline in place of the net (params: None for the defaults, a dict of
-        bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix (extended: five columns,
-        bp_eval_mix_logmmse_ext).  noise: as for logmmse_waves (anything but None: bp_eval_mix_logmmse_nt)."""
+        bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix (extended: five columns, "full":
+        seven, bp_eval_mix_logmmse_ext).  noise: as for logmmse_waves (anything but None: bp_eval_mix_logmmse_nt)."""
+        ns = score_columns("eval_mix_logmmse", extended)
         p, pp = self._plan(plan)
-        ns = 5 if extended else 3
         lm = logmmse_params(params)
         lmp = None if lm is None else C.byref(lm)
         if noise is not None:
             nz = noise_params(noise)
             return self._eval(p, ns, return_pcm, self._lib.bp_eval_mix_logmmse_nt, self._h, lmp, C.byref(nz), p.size, pp, int(sample_rate), ns)
-        if extended:
+        if ns != 3:
             return self._eval(p, ns, return_pcm, self._lib.bp_eval_mix_logmmse_ext, self._h, lmp, p.size, pp, int(sample_rate), ns)
         return self._eval(p, ns, return_pcm, self._lib.bp_eval_mix_logmmse, self._h, lmp, p.size, pp, int(sample_rate))
 

@@ -1,6 +1,6 @@
 // bp_eval.h -- the scoring launchers of bp_eval.hip, for bp_score_waves (bp_eval.hip) and bp_eval_mix (bp_mix.hip): segmental SNR,
 // log-spectral distortion and STOI of estimates against a reference, with ESTOI and SI-SDR beside them where the call asks for five
-// score columns (definitions: include/bp_c_api.h).
+// score columns, and LLR and cepstral distance behind those with seven (definitions: include/bp_c_api.h).
 // Internal: nothing in here is part of the C ABI.
 //
 // One call scores n sentences of nsig signals: signal 0 is the reference, signals 1 .. nsig-1 the estimates.  Sample i of sentence
@@ -18,7 +18,8 @@ constexpr int EVAL_MAXSIG = 3;
 // Host plan of one call: the per-sentence tables (prefix sums [n + 1] unless noted) and where they lie in the table block.
 struct EvalPlan {
     int n, fs, p, q, Lh, taps, win, skip, D;      // rate p/q = 10000/fs in lowest terms; SSNR frame / skip; fea_dim
-    int ns;                                       // score columns per row: BP_SCORE_N, or BP_SCORE_EXT_N (ESTOI and SI-SDR are computed)
+    int ns;                                       // score columns per row: BP_SCORE_N, BP_SCORE_EXT_N (ESTOI and SI-SDR are computed) or
+                                                  // BP_SCORE_FULL_N (LLR and CD as well: per-frame values in the work block)
     std::vector<int64_t> off;                     // [n] first sample of each sentence
     std::vector<int> len;                         // [n]
     std::vector<int> o10, rb;                     // 10 kHz samples; resampler workgroups
@@ -32,10 +33,10 @@ struct EvalPlan {
 };
 // The rate rule: 10000/fs = p/q in lowest terms, max(p, q) <= 32.
 bool eval_rate(int fs, int *p, int *q);
-// BP_OK for BP_SCORE_N and BP_SCORE_EXT_N, else BP_ERR_ARG: the first check of every _ext call.
+// BP_OK for BP_SCORE_N, BP_SCORE_EXT_N and BP_SCORE_FULL_N, else BP_ERR_ARG: the first check of every _ext call.
 int eval_n_scores(const char *who, int n_scores);
 // Checks the rate and sizes (BP_ERR_ARG, nothing touched) and builds the plan; F: [n + 1] analysis frame prefix of the call;
-// n_scores: BP_SCORE_N or BP_SCORE_EXT_N (the caller has checked it).
+// n_scores: BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N (the caller has checked it).
 int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep);
 void eval_fill(const EvalPlan &ep, char *tab);    // the table block, t_bytes
 size_t eval_work_bytes(const EvalPlan &ep, int nsig);
@@ -46,7 +47,8 @@ struct EvalDev {
     float *scores;                                // [nsig - 1][n][ns]
 };
 // The whole scoring sequence on st: the reference side once, the estimates' sides, the per-sentence reductions.  With five
-// columns bp_eval_estoi and bp_eval_sisdr run before the reductions; with three nothing else changes.
+// columns bp_eval_estoi and bp_eval_sisdr run before the reductions; with three nothing else changes.  With seven the LLR / CD
+// kernels (bp_eval_lpc, bp_eval_lpcrank, bp_eval_lpcsum) run behind the five-column sequence and write columns 5 and 6 alone.
 hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream_t st);
 // Zero every sample of the padded layout outside [off[s], off[s] + len[s]) of its sentence (hop-sample segments).
 hipError_t eval_trim_launch(const EvalPlan &ep, const char *tab, int hop, float *pcm, hipStream_t st);

@@ -1,6 +1,7 @@
 // bp_eval.hip -- C-ABI implementation (include/bp_c_api.h): objective scores of enhanced speech.  Segmental SNR,
 // log-spectral distortion on the 1d analysis and STOI of estimates against a reference, and with five score columns ESTOI and
-// SI-SDR beside them (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions:
+// SI-SDR beside them, with seven LLR and cepstral distance as well (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip
+// through bp_eval.h).  Definitions:
 // include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame plan and padded layout from bp_wave.hip
 // (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
 //
@@ -19,6 +20,14 @@
 //   bp_eval_sisdr     five columns only, one workgroup per (sentence, estimate): rr, er, then with alpha num, den -- two passes
 //                     over the samples in double (strided sums, a fixed LDS tree)
 //   bp_eval_reduce    one workgroup per (sentence, estimate): the means in double (strided sums, a fixed LDS tree), one score row
+//   bp_eval_lpc<P>    seven columns only, one workgroup per 32 SSNR frames of the call: per (signal, frame) one wave64 puts the
+//                     windowed frame into LDS in double and sums the P + 1 autocorrelation lags (4 lag groups x 16 sample segments
+//                     over the lanes, a fixed shuffle tree over the segments); then one thread per (signal, frame) runs the Levinson-Durbin recursion and the LPC
+//                     cepstrum in registers (the reference's once, shared through LDS) and the quadratic forms: LLR_j, CD_j, valid_j
+//   bp_eval_lpcrank   seven columns only, one thread per SSNR frame of an estimate: the frame's rank among the sentence's valid
+//                     frames in either measure (integer counts; the sentence's values pass through LDS in tiles), selected iff rank < Jk
+//   bp_eval_lpcsum    seven columns only, one workgroup per (sentence, estimate): the selected values summed (strided sums, a
+//                     fixed LDS tree), divided by Jk: columns 5 and 6
 //   bp_eval_trim      per padded sample: zero outside the sentence (the overlap-add output, before it is analysed)
 // No float atomics and no cross-workgroup hand-off inside a kernel: the same bits on every run.
 #include <hip/hip_runtime.h>
@@ -54,6 +63,7 @@ struct EvalArgs {
     float *band; size_t sband;                               // [sig][P[n]][EV_BS]
     double *rho, *ssnr, *lsd; size_t srho, sssnr, slsd;      // [est][CP[n]], [est][SJ[n]], [est][F[n]]
     double *dm, *sdr; size_t sdm; int nsig;                  // five columns: [est][CP[n] / 15], [est][n]
+    double *llr, *lcd; int *lv, *lsel;                       // seven columns: [est][SJ[n]] each (lv: valid; lsel: bit 0 LLR, bit 1 CD selected)
     float *scores; int ns;                                   // [est][n][ns]
 };
 
@@ -287,7 +297,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_reduce(const EvalArgs a)
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x;
     const int J = a.SJ[s + 1] - a.SJ[s], T = a.F[s + 1] - a.F[s], S = a.C[s] - 1, np = S >= EV_SEG ? EV_NB * (S - (EV_SEG - 1)) : 0;
     const double *ss = a.ssnr + (e - 1) * a.sssnr + a.SJ[s], *ls = a.lsd + (e - 1) * a.slsd + a.F[s], *rh = a.rho + (e - 1) * a.srho + a.CP[s];
-    const bool ext = a.ns == BP_SCORE_EXT_N;
+    const bool ext = a.ns >= BP_SCORE_EXT_N;
     const int nd = ext ? np / EV_NB : 0;                            // the S - 29 segments
     double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
     for (int i = tid; i < J; i += WAVE_THREADS) q0 += ss[i];
@@ -312,6 +322,240 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_reduce(const EvalArgs a)
             o[BP_SCORE_ESTOI] = nd > 0 ? (float)(red[3][0] / nd) : nan;
             o[BP_SCORE_SISDR] = (float)a.sdr[(size_t)(e - 1) * a.n + s];
         }
+    }
+}
+
+// ---- LLR and cepstral distance (seven columns).  EV_LPAD zeros behind each windowed frame in LDS let every lag sum run over all
+// win samples: the products past the end are exact zeros.  A wave64 sums the lags of one frame as 4 lag groups x 16 sample
+// segments: lane (group, segment) keeps the EV_LL(P) lags from group EV_LL(P) on, over the samples i = segment (mod 16).
+constexpr int EV_LPAD = 24;
+__host__ __device__ constexpr int EV_LL(int P) { return (P + 4) / 4; }   // lags per lane: 3 (P = 10), 5 (P = 16); 4 EV_LL(P) - 1 < EV_LPAD
+constexpr double EV_WNC = 1.0 + 1e-6;                               // the white-noise correction of R[0]
+
+// Levinson-Durbin on R (R[0] corrected) and the LPC cepstrum: a[1..P], c[1..P] (index 0 unused).  Fully unrolled: registers only.
+template <int P> __device__ __forceinline__ void lpc_of(const double (&R)[P + 1], double (&a)[P + 1], double (&c)[P + 1])
+{
+    double E = R[0];
+#pragma unroll
+    for (int m = 1; m <= P; ++m) {
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 1; j < m; ++j) sum += a[j] * R[m - j];
+        const double k = (R[m] - sum) / E;
+#pragma unroll
+        for (int j = 1; j < m - j; ++j) {                           // a'[j] = a[j] - k a[m - j], in place by pairs
+            const double lo = a[j], hi = a[m - j];
+            a[j] = lo - k * hi; a[m - j] = hi - k * lo;
+        }
+        if (m % 2 == 0) a[m / 2] -= k * a[m / 2];
+        a[m] = k;
+        E = (1.0 - k * k) * E;
+    }
+    c[1] = a[1];
+#pragma unroll
+    for (int m = 2; m <= P; ++m) {
+        double sum = 0.0;
+#pragma unroll
+        for (int q = 1; q < m; ++q) sum += ((double)q / (double)m) * c[q] * a[m - q];
+        c[m] = a[m] + sum;
+    }
+}
+
+// A T A^T with A = [1, -a_1 .. -a_P] and T the Toeplitz matrix of R: rows in order, each row's sum first
+template <int P> __device__ __forceinline__ double lpc_form(const double (&a)[P + 1], const double (&R)[P + 1])
+{
+    double tot = 0.0;
+#pragma unroll
+    for (int i = 0; i <= P; ++i) {
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j <= P; ++j) row += (j == 0 ? 1.0 : -a[j]) * R[i > j ? i - j : j - i];
+        tot += (i == 0 ? 1.0 : -a[i]) * row;
+    }
+    return tot;
+}
+
+// Frame block of bp_eval_lpc: EV_FB consecutive frames of the call (global index g over SJ[n]; a block may span sentences).
+// LDS, in doubles: one slab of win + EV_LPAD per wave (the windowed frame; only up to EV_SLAB_WIN samples -- above that the lag
+// sums read the samples again from memory), Rl[signal][lag][frame], then Cr[m][frame] and Dl[frame] of the reference.
+constexpr int EV_FB = 32, EV_SLAB_WIN = 1440, EV_LB = 8;
+__host__ __device__ constexpr size_t lpc_slab_doubles(int win) { return win <= EV_SLAB_WIN ? (size_t)(WAVE_THREADS / 64) * (win + EV_LPAD) : 0; }
+
+// the lags k0 .. k0 + EV_LL(P) - 1 of the windowed frame at x, k0 = (lane / 16) EV_LL(P), in every lane of the group: each lane's
+// sum over its samples in order, then a fixed shuffle tree over the 16 segments (the barriers are met by the whole workgroup)
+template <int P> __device__ __forceinline__ void lpc_lags(const EvalArgs &a, const float *__restrict__ x, bool live, double *xw, int ln,
+                                                          double (&R)[EV_LL(P)])
+{
+    constexpr int L = EV_LL(P);
+    const bool slab = a.win <= EV_SLAB_WIN;
+    const double *__restrict__ w = a.w;
+    const int sgm = ln & 15, k0 = (ln >> 4) * L;
+    if (slab) {
+        if (live)
+            for (int i0 = ln; i0 < a.win; i0 += 64 * EV_LB) {       // EV_LB loads of either table in flight, then the products
+                float xv[EV_LB];
+                double wv[EV_LB];
+#pragma unroll
+                for (int u = 0; u < EV_LB; ++u) {
+                    const int i = i0 + 64 * u < a.win ? i0 + 64 * u : a.win - 1;
+                    xv[u] = x[i]; wv[u] = w[i];
+                }
+#pragma unroll
+                for (int u = 0; u < EV_LB; ++u)
+                    if (i0 + 64 * u < a.win) xw[i0 + 64 * u] = wv[u] * (double)xv[u];
+            }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int l = 0; l < L; ++l) R[l] = 0.0;
+    if (live && slab)
+        for (int i = sgm; i < a.win; i += 16) {
+            const double x0 = xw[i];
+#pragma unroll
+            for (int l = 0; l < L; ++l) R[l] += x0 * xw[i + k0 + l];
+        }
+    if (live && !slab)
+        for (int i = sgm; i < a.win; i += 16) {
+            const double x0 = w[i] * (double)x[i];
+#pragma unroll
+            for (int l = 0; l < L; ++l)
+                if (i + k0 + l < a.win) R[l] += x0 * (w[i + k0 + l] * (double)x[i + k0 + l]);
+        }
+    if (slab) __syncthreads();
+#pragma unroll
+    for (int l = 0; l < L; ++l)
+        for (int o = 8; o > 0; o >>= 1) R[l] += __shfl_xor(R[l], o);
+}
+
+template <int P> __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpc(const EvalArgs a)
+{
+    extern __shared__ double lpc_lds[];
+    __shared__ int64_t first[EV_FB];                                // the first sample of each frame of the block
+    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6, g0 = blockIdx.x * EV_FB, total = a.SJ[a.n];
+    if (tid < EV_FB) {                                              // (one search per frame, not one per item: each is a chain of loads)
+        const int g = g0 + tid < total ? g0 + tid : total - 1, s = sentence_of(a.SJ, a.n, g);
+        first[tid] = a.off[s] + (int64_t)(g - a.SJ[s]) * a.skip;
+    }
+    double *xw = lpc_lds + (size_t)wv * (a.win + EV_LPAD);
+    double *Rl = lpc_lds + lpc_slab_doubles(a.win), *Cr = Rl + (size_t)a.nsig * (P + 1) * EV_FB, *Dl = Cr + (size_t)P * EV_FB;
+    if (a.win <= EV_SLAB_WIN && ln < EV_LPAD) xw[a.win + ln] = 0.0;
+    __syncthreads();
+    // 1. the lags: item t = (signal t / EV_FB, frame t % EV_FB) of the block, one wave64 each, the waves taking the items in turn
+    for (int t = wv; t < a.nsig * EV_FB; t += WAVE_THREADS / 64) {  // (the same number of rounds in every wave: EV_FB % 4 == 0)
+        const int k = t / EV_FB, f = t % EV_FB;
+        const bool live = g0 + f < total;
+        const float *x = a.sig[k] + first[f];
+        double R[EV_LL(P)];
+        lpc_lags<P>(a, x, live, xw, ln, R);
+        if ((ln & 15) == 0) {
+#pragma unroll
+            for (int l = 0; l < EV_LL(P); ++l) {
+                const int q = (ln >> 4) * EV_LL(P) + l;
+                if (q <= P) Rl[((size_t)k * (P + 1) + q) * EV_FB + f] = R[l];
+            }
+        }
+    }
+    __syncthreads();
+    // 2. the recursions: thread t = (signal, frame) as above; the reference's cepstrum and quadratic form go to LDS
+    const int k = tid / EV_FB, f = tid % EV_FB, g = g0 + f;
+    const bool work = tid < a.nsig * EV_FB && g < total;
+    double R[P + 1], al[P + 1], c[P + 1];
+    bool pos = false;
+    if (work) {                                                     // (the waves past nsig EV_FB threads skip it whole)
+#pragma unroll
+        for (int q = 0; q <= P; ++q) R[q] = Rl[((size_t)k * (P + 1) + q) * EV_FB + f];
+        pos = R[0] > 0.0;
+        R[0] *= EV_WNC;
+        lpc_of<P>(R, al, c);
+        if (k == 0) {
+#pragma unroll
+            for (int m = 1; m <= P; ++m) Cr[(size_t)(m - 1) * EV_FB + f] = c[m];
+            Dl[f] = lpc_form<P>(al, R);
+        }
+    }
+    __syncthreads();
+    if (work && k > 0) {
+        double Rr[P + 1], d2 = 0.0;
+#pragma unroll
+        for (int q = 0; q <= P; ++q) Rr[q] = Rl[(size_t)q * EV_FB + f];
+        const bool valid = pos && Rr[0] > 0.0;
+        Rr[0] *= EV_WNC;
+        const double num = lpc_form<P>(al, Rr);
+#pragma unroll
+        for (int m = 1; m <= P; ++m) { const double d = Cr[(size_t)(m - 1) * EV_FB + f] - c[m]; d2 += d * d; }
+        const size_t o = (size_t)(k - 1) * a.sssnr + g;
+        a.llr[o] = valid ? fmin(fmax(log(num / Dl[f]), 0.0), 2.0) : 0.0;
+        a.lcd[o] = valid ? fmin(fmax(4.3429448190325182765 * sqrt(2.0 * d2), 0.0), 10.0) : 0.0;
+        a.lv[o] = valid;
+    }
+}
+
+// Jk of Jv valid frames: the lowest 95 %, at least one
+__device__ __forceinline__ int lpc_keep(int Jv) { const int k = (int)floor(0.95 * (double)Jv + 0.5); return k > 1 ? k : 1; }
+
+// one thread per frame (global index g; a block may span sentences): the values of all the sentences the block touches pass
+// through LDS in tiles, and every thread counts the frames of its own sentence among them (the reads of a tile entry are
+// the same address in every lane)
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcrank(const EvalArgs a)
+{
+    __shared__ double tl[WAVE_THREADS], tc[WAVE_THREADS];
+    __shared__ int tv[WAVE_THREADS];
+    const int e = blockIdx.y + 1, tid = threadIdx.x, total = a.SJ[a.n], g0 = blockIdx.x * WAVE_THREADS;
+    const int glast = g0 + WAVE_THREADS - 1 < total ? g0 + WAVE_THREADS - 1 : total - 1, g = g0 + tid;
+    const bool live = g < total;
+    const int s = sentence_of(a.SJ, a.n, live ? g : glast), lo = a.SJ[s], hi = a.SJ[s + 1];
+    const int ulo = a.SJ[sentence_of(a.SJ, a.n, g0)], uhi = a.SJ[sentence_of(a.SJ, a.n, glast) + 1];   // (uniform over the workgroup)
+    const size_t o = (size_t)(e - 1) * a.sssnr;
+    const double lj = live ? a.llr[o + g] : 0.0, cj = live ? a.lcd[o + g] : 0.0;
+    int jv = 0, rl = 0, rc = 0;                                     // valid frames; frames ranked before g in LLR, in CD
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    for (int t0 = ulo; t0 < uhi; t0 += WAVE_THREADS) {
+        const int i = t0 + tid, m = uhi - t0 < WAVE_THREADS ? uhi - t0 : WAVE_THREADS;
+        if (i < uhi) {                                              // (an invalid frame is +inf here: below no frame, equal to no valid one)
+            const int v = a.lv[o + i];
+            tl[tid] = v ? a.llr[o + i] : inf; tc[tid] = v ? a.lcd[o + i] : inf; tv[tid] = v;
+        }
+        __syncthreads();
+        // the thread's own sentence within the tile: the frames before g count when not above, the frames behind g when below
+        const int u0 = lo > t0 ? lo - t0 : 0, u3 = hi - t0 < m ? hi - t0 : m;
+        const int u1 = g - t0 < u3 ? g - t0 : u3, u2 = g + 1 - t0 > u0 ? g + 1 - t0 : u0;
+        for (int u = u0; u < u1; ++u) { jv += tv[u]; rl += tl[u] <= lj; rc += tc[u] <= cj; }
+        for (int u = u2; u < u3; ++u) { jv += tv[u]; rl += tl[u] < lj; rc += tc[u] < cj; }
+        if (g >= t0 && g < t0 + m) jv += tv[g - t0];
+        __syncthreads();
+    }
+    if (live) {
+        const int Jk = lpc_keep(jv);
+        a.lsel[o + g] = a.lv[o + g] ? (rl < Jk ? 1 : 0) | (rc < Jk ? 2 : 0) : 0;
+    }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcsum(const EvalArgs a)
+{
+    __shared__ double red[2][WAVE_THREADS];
+    __shared__ int cnt[WAVE_THREADS];
+    const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, J = a.SJ[s + 1] - a.SJ[s];
+    const size_t o = (size_t)(e - 1) * a.sssnr + a.SJ[s];
+    double q0 = 0.0, q1 = 0.0;
+    int jv = 0;
+    for (int i = tid; i < J; i += WAVE_THREADS) {
+        const int sel = a.lsel[o + i];
+        jv += a.lv[o + i];
+        if (sel & 1) q0 += a.llr[o + i];
+        if (sel & 2) q1 += a.lcd[o + i];
+    }
+    red[0][tid] = q0; red[1][tid] = q1; cnt[tid] = jv;
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; cnt[tid] += cnt[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float nan = __int_as_float(0x7fc00000);
+        float *sc = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
+        const int Jv = cnt[0], Jk = lpc_keep(Jv);
+        sc[BP_SCORE_LLR] = Jv > 0 ? (float)(red[0][0] / Jk) : nan;
+        sc[BP_SCORE_CD] = Jv > 0 ? (float)(red[1][0] / Jk) : nan;
     }
 }
 
@@ -360,7 +604,7 @@ double bessel_i0(double x)
 }
 
 // Work block layout for nsig signals.
-struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
+struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, llr, lcd, lv, lsel, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
 WorkLayout work_layout(const EvalPlan &ep, int nsig)
 {
     WorkLayout w;
@@ -378,9 +622,13 @@ WorkLayout work_layout(const EvalPlan &ep, int nsig)
     w.ssnr = lay.take(ne * w.sssnr * 8);
     w.lsd = lay.take(ne * w.slsd * 8);
     w.sdm = (size_t)ep.CP[n] / EV_NB;                               // five columns only (a part of 0 bytes takes no room)
-    const bool ext = ep.ns == BP_SCORE_EXT_N;
+    const bool ext = ep.ns >= BP_SCORE_EXT_N, full = ep.ns == BP_SCORE_FULL_N;
     w.dm = lay.take(ext ? ne * w.sdm * 8 : 0);
     w.sdr = lay.take(ext ? (size_t)ne * n * 8 : 0);
+    w.llr = lay.take(full ? ne * w.sssnr * 8 : 0);                  // seven columns only
+    w.lcd = lay.take(full ? ne * w.sssnr * 8 : 0);
+    w.lv = lay.take(full ? ne * w.sssnr * 4 : 0);
+    w.lsel = lay.take(full ? ne * w.sssnr * 4 : 0);
     w.bytes = lay.size();
     return w;
 }
@@ -398,8 +646,8 @@ bool eval_rate(int fs, int *p, int *q)
 
 int eval_n_scores(const char *who, int n_scores)
 {
-    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N) return BP_OK;
-    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N or BP_SCORE_EXT_N");
+    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N || n_scores == BP_SCORE_FULL_N) return BP_OK;
+    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N");
 }
 
 int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep)
@@ -494,6 +742,7 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
     a.ssnr = (double *)(d.work + w.ssnr); a.sssnr = w.sssnr;
     a.lsd = (double *)(d.work + w.lsd); a.slsd = w.slsd;
     a.dm = (double *)(d.work + w.dm); a.sdm = w.sdm; a.sdr = (double *)(d.work + w.sdr); a.nsig = nsig;
+    a.llr = (double *)(d.work + w.llr); a.lcd = (double *)(d.work + w.lcd); a.lv = (int *)(d.work + w.lv); a.lsel = (int *)(d.work + w.lsel);
     a.scores = d.scores; a.ns = ep.ns;
     const int n = ep.n, ne = nsig - 1;
     const dim3 blk(WAVE_THREADS);
@@ -508,11 +757,22 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
     if (ep.cb[n]) hipLaunchKernelGGL(bp_eval_corr, dim3((unsigned)ep.cb[n], (unsigned)ne), blk, 0, st, a);
     if (ep.sb[n]) hipLaunchKernelGGL(bp_eval_ssnr, dim3((unsigned)ep.sb[n], (unsigned)ne), blk, 0, st, a);
     hipLaunchKernelGGL(bp_eval_lsd, dim3((unsigned)((ep.F[n] + 3) / 4), (unsigned)ne), blk, 0, st, a);
-    if (ep.ns == BP_SCORE_EXT_N) {
+    if (ep.ns >= BP_SCORE_EXT_N) {
         if (ep.CP[n]) hipLaunchKernelGGL(bp_eval_estoi, dim3((unsigned)(ep.CP[n] / EV_NB)), dim3(64), 0, st, a);
         hipLaunchKernelGGL(bp_eval_sisdr, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
     }
     hipLaunchKernelGGL(bp_eval_reduce, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    if (ep.ns == BP_SCORE_FULL_N) {                                 // LLR and CD: order 10 below 10 kHz, else 16
+        if (ep.SJ[n]) {
+            const int P = ep.fs < 10000 ? 10 : 16;
+            const size_t lds = (lpc_slab_doubles(ep.win) + (size_t)(nsig * (P + 1) + P + 1) * EV_FB) * 8;
+            const dim3 fb((unsigned)((ep.SJ[n] + EV_FB - 1) / EV_FB));
+            if (P == 10) hipLaunchKernelGGL(bp_eval_lpc<10>, fb, blk, lds, st, a);
+            else hipLaunchKernelGGL(bp_eval_lpc<16>, fb, blk, lds, st, a);
+            hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((ep.SJ[n] + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, a);
+        }
+        hipLaunchKernelGGL(bp_eval_lpcsum, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    }
     return hipGetLastError();
 }
 

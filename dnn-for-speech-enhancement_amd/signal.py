@@ -6,7 +6,7 @@ import numpy as np
 
 from ._abi import (BPError, BPLogmmseParams, BPMelParams, BPNoiseParams, BPPostParams, BPResampleParams, BPRirRange, Closing,
                    GV_MODES, MIX_RIR_MAX_TAPS, MIXTURE_DTYPE, NOISE_SPP, NOISE_VAD, RIR_RANGE_DEFAULTS, RIR_ROOM_DTYPE, check,
-                   flat32, load_library, pack, ptr, set_fields, split, struct_params)
+                   flat32, load_library, pack, ptr, score_columns, set_fields, split, struct_params)
 
 __all__ = [
     "wave_lps", "post_params", "post_rows", "gv_factors", "mel_params", "mel_filters", "mel_dct", "wave_mfcc",
@@ -259,7 +259,9 @@ def logmmse_stream_counts(fea_dim, init_frames, received, ended):
 def score_waves(device, fea_dim, sample_rate, refs, ests, extended=False):
     """bp_score_waves: SSNR, LSD and STOI of every estimate against its reference (lists of 1-D arrays, int16 units, pairwise
     equal lengths), float32 [n][3] (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where undefined).  No handle.  extended:
-    bp_score_waves_ext, float32 [n][5] with SCORE_ESTOI and SCORE_SISDR behind the same three."""
+    bp_score_waves_ext, float32 [n][5] with SCORE_ESTOI and SCORE_SISDR behind the same three; extended="full": [n][7] with
+    SCORE_LLR and SCORE_CD behind those five.  Any other value is a BPError."""
+    ns = score_columns("score_waves", extended)
     lib = load_library()
     if len(refs) != len(ests):
         raise BPError("score_waves: %d references but %d estimates" % (len(refs), len(ests)))
@@ -269,9 +271,9 @@ def score_waves(device, fea_dim, sample_rate, refs, ests, extended=False):
     if bad.size:
         raise BPError("score_waves: pair %d: reference has %d samples, estimate %d" % (bad[0], lens[bad[0]], elens[bad[0]]))
     n = len(lens)
-    out = np.empty((max(n, 1), 5 if extended else 3), np.float32)
-    if extended:
-        rc = lib.bp_score_waves_ext(int(device), int(fea_dim), int(sample_rate), n, ptr(lens), ptr(rp), ptr(ep), 5, ptr(out))
+    out = np.empty((max(n, 1), ns), np.float32)
+    if ns != 3:
+        rc = lib.bp_score_waves_ext(int(device), int(fea_dim), int(sample_rate), n, ptr(lens), ptr(rp), ptr(ep), ns, ptr(out))
     else:
         rc = lib.bp_score_waves(int(device), int(fea_dim), int(sample_rate), n, ptr(lens), ptr(rp), ptr(ep), ptr(out))
     check(lib, rc)

@@ -469,14 +469,32 @@ int bp_rir_rooms(uint64_t seed, int n, const bp_rir_range *g, bp_rir_room *out);
  * SI-SDR (dB; Le Roux et al. 2019), over the n samples in double: rr = sum r^2, er = sum e r; rr == 0: NaN; alpha = er/rr; in a
  *   second pass num = sum (alpha r_i)^2, den = sum (alpha r_i - e_i)^2 (the residual itself: sum e^2 - er^2/rr cancels at high
  *   SDR); SI-SDR = 10 log10(num/(den + eps) + eps).  The mean is not removed and nothing is clamped.
- * Not computed: fwSNRseg and the composite measures (they need a 25-band table and PESQ).
  *
- * bp_score_waves_ext, bp_eval_mix_ext (and bp_eval_mix_logmmse_ext below): the calls above with rows of n_scores columns, n_scores =
- *   BP_SCORE_N or BP_SCORE_EXT_N, anything else BP_ERR_ARG before the device is touched; every other check, state and capacity rule
- *   is that of the call without _ext.  With BP_SCORE_N an _ext call is that call; with BP_SCORE_EXT_N columns 0..2 hold its bits,
- *   and only then do the ESTOI and SI-SDR kernels run. */
+ * The spectral-envelope scores (the _ext calls with n_scores = BP_SCORE_FULL_N; two more columns behind the five above):
+ * LLR and cepstral distance CD (dB) (Hu & Loizou 2008; the REVERB challenge's set), on the SSNR's own framing: win, skip, the J
+ *   frames and the window w above; P = 10 if fs < 10000, else 16; everything in double on the fp32 samples.  Per frame j and per
+ *   signal x in {r, e}: xw[i] = w[i] x[j skip + i]; R_x[k] = sum_{i=0}^{win-1-k} xw[i] xw[i+k], k = 0..P (one fixed order of
+ *   summation).  The frame is valid iff R_r[0] > 0 and R_e[0] > 0 (sums of squares: an exact decision).  White-noise correction:
+ *   R_x[0] <- R_x[0] (1 + 1e-6).  Levinson-Durbin on the corrected R: E = R[0]; for m = 1..P: k = (R[m] - sum_{j=1}^{m-1} a[j]
+ *   R[m-j])/E, a'[m] = k, a'[j] = a[j] - k a[m-j], E <- (1 - k^2) E; the prediction-error filter A = [1, -a_1 .. -a_P].  LPC
+ *   cepstrum: c_1 = a_1, c_m = a_m + sum_{q=1}^{m-1} (q/m) c_q a_{m-q}, m <= P.  With T the (P+1) x (P+1) Toeplitz matrix of
+ *   the corrected R_r: LLR_j = clamp(ln((A_e T A_e^T)/(A_r T A_r^T)), 0, 2), CD_j = clamp((10/ln 10) sqrt(2 sum_{m=1}^{P}
+ *   (c_r[m] - c_e[m])^2), 0, 10).  Per sentence and per measure alone: Jv valid frames (Jv = 0 or J < 1: NaN), Jk = max(1,
+ *   floor(0.95 Jv + 0.5)) (double); a valid frame is selected iff its rank #{valid i: v_i < v_j, or v_i == v_j and i < j} is
+ *   below Jk (the doubles compared before any rounding); the score = (the sum of the selected values in one fixed order)/Jk,
+ *   rounded once to fp32: Hu & Loizou's mean of the lowest 95 % with the tie rule stated.  The white-noise correction is not
+ *   in Hu & Loizou's comp_llr, which has no guard: it keeps the Toeplitz system positive definite with condition <= (P+1) 1e6,
+ *   so that the recursion never breaks down and no second, rounding-dependent validity decision exists.
+ * Not computed: PESQ, fwSNRseg and the composite measures (they need a 25-band table and PESQ: nothing here could be held to a source).
+ *
+ * bp_score_waves_ext, bp_eval_mix_ext (and bp_eval_mix_logmmse_ext, bp_eval_mix_logmmse_nt below): the calls above with rows of
+ *   n_scores columns, n_scores = BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N, anything else BP_ERR_ARG before the device is
+ *   touched; every other check, state and capacity rule is that of the call without _ext.  With BP_SCORE_N an _ext call is that
+ *   call; with BP_SCORE_EXT_N columns 0..2 hold its bits, and only then do the ESTOI and SI-SDR kernels run; with BP_SCORE_FULL_N
+ *   columns 0..4 hold the bits of the five-column call, and only then do the LLR and CD kernels run. */
 enum { BP_SCORE_SSNR = 0, BP_SCORE_LSD = 1, BP_SCORE_STOI = 2, BP_SCORE_N = 3 };
 enum { BP_SCORE_ESTOI = 3, BP_SCORE_SISDR = 4, BP_SCORE_EXT_N = 5 };
+enum { BP_SCORE_LLR = 5, BP_SCORE_CD = 6, BP_SCORE_FULL_N = 7 };
 int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
                    float *scores);
 int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,

@@ -8,7 +8,11 @@ against the forward's kernels).
 --extended: the five-column bp_eval_mix_ext (ESTOI and SI-SDR beside the three) against the three-column bp_eval_mix on the same
 mixtures instead: the two alternate in one process, each timed to its synchronisation; both medians and their ratio.
 
-    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16] [--extended]
+--full: the seven-column bp_eval_mix_ext (LLR and cepstral distance behind the five) against the five-column call on the same
+mixtures, alternating in the same way.  The new kernels' share: `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py
+--full` (bp_eval_lpc, bp_eval_lpcrank, bp_eval_lpcsum against the other bp_eval_* kernels).
+
+    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16] [--extended | --full]
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--compute", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--sentences", type=int, default=100)
     ap.add_argument("--extended", action="store_true", help="time bp_eval_mix_ext with five columns beside bp_eval_mix")
+    ap.add_argument("--full", action="store_true", help="time bp_eval_mix_ext with seven columns beside the five-column call")
     a = ap.parse_args()
     D, ctx, toff, rate, B = 129, 11, 5, 8000, 256
     ls = [(ctx + 1) * D, 2048, 2048, 2048, D]
@@ -62,6 +67,25 @@ def main():
                           "frames": frames, "basic_ms_median": 1e3 * m3, "extended_ms_median": 1e3 * m5, "extended_over_basic": m5 / m3,
                           "columns_0_to_2_same_bits": same, "noisy_mean": np.nanmean(ev5["noisy"], axis=0).tolist(),
                           "enhanced_mean": np.nanmean(ev5["enhanced"], axis=0).tolist()}))
+        return
+    if a.full:
+        t5, t7 = [], []
+        for r in range(a.reps + 1):                                # (rep 0: warm-up -- buffers, code objects)
+            t0 = time.perf_counter()
+            ev5 = g.eval_mix(plan, rate, extended=True)
+            t1 = time.perf_counter()
+            ev7 = g.eval_mix(plan, rate, extended="full")
+            t2 = time.perf_counter()
+            if r:
+                t5.append(t1 - t0)
+                t7.append(t2 - t1)
+        g.close()
+        same = all(np.array_equal(ev7[k][:, :5].view(np.uint32), ev5[k].view(np.uint32)) for k in ("noisy", "enhanced"))
+        m5, m7 = float(np.median(t5)), float(np.median(t7))
+        print(json.dumps({"what": "bp_eval_mix_ext (7 columns) vs bp_eval_mix_ext (5 columns)", "compute": a.compute, "mixtures": a.sentences,
+                          "frames": frames, "extended_ms_median": 1e3 * m5, "full_ms_median": 1e3 * m7, "full_over_extended": m7 / m5,
+                          "columns_0_to_4_same_bits": same, "noisy_mean": np.nanmean(ev7["noisy"], axis=0).tolist(),
+                          "enhanced_mean": np.nanmean(ev7["enhanced"], axis=0).tolist()}))
         return
     t_eval, t_enh = [], []
     for r in range(a.reps + 1):                                    # (rep 0: warm-up -- buffers, code objects)
