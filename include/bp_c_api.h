@@ -769,6 +769,8 @@ int bp_set_nat(bp_handle *h, int mode, const bp_noise_params *np);   /* np NULL:
  * 0.0 over ascending g, per bin and quantity -- the quantities (double)v and (double)v * (double)v, the product exact in double --
  * and the total is part 0 + part 1 + ... in ascending p (an empty part adds 0.0).  est_sum, est_sq, ref_sum, ref_sq [fea_dim] and
  * *frames (= n) are written, not added to: across calls the caller adds.  No float atomics; the same bits on every run.
+ * bp_gv_mix leaves the chunk as the resident window chunk, without targets, as bp_eval_mix does; weights, momentum state and the
+ * position of the dropout stream are untouched.
  *
  * bp_gv_factors (host only), in double: me = S1e / n, ve = S2e / n - me^2, and the same for r.  frames < 2 is BP_ERR_ARG; a
  * variance <= 0 (or not finite) is BP_ERR_ARG with the bin named in the message.  center[k] = (float)mr[k]: the paper scales in
@@ -936,13 +938,23 @@ int bp_device_pci_bus_id(int device, char *buf, int len);
 int bp_last_train_ms(bp_handle *h, float *ms, int *bunches);
 /* Time `iters` launches of one kernel of the step in isolation (HIP events on the handle's
  * stream).  which: 0 fwd hidden GEMM(layer 2), 1 dgrad hidden, 2 wgrad+update hidden,
- * 3 fwd layer 1, 4 fwd output layer, 5 wgrad+update layer 1.  Returns average ms. */
+ * 3 fwd layer 1, 4 fwd output layer, 5 wgrad+update layer 1.  Returns average ms.
+ * bp_time_kernel leaves the weights, the momentum state, the resident chunk and the position of the dropout stream unchanged (ids
+ * 2 and 5 update scratch copies of W, b and their deltas); it may overwrite the activations and the back-propagated errors of the
+ * last bunch (what bp_read_layer_output returns), which every later call computes afresh before it reads them.  It runs on the
+ * first bunchsize rows of a resident STACKED chunk, with or without targets (without: id 4 reads an older chunk's target rows,
+ * which changes the time alone).  Refusals of bp_time_kernel, in this order: BP_ERR_ARG for a null argument, iters < 1, or ids 0..2
+ * on a net without a hidden -> hidden layer; BP_ERR_STATE on a bf16 handle (the first of the state checks); BP_ERR_STATE when no
+ * stacked chunk of at least bunchsize rows is resident; BP_ERR_ARG for an unknown id.  The handle is unchanged after each. */
 int bp_time_kernel(bp_handle *h, int which, int iters, float *avg_ms);
 
 /* The same bunch loop as bp_train_resident over n_bunches bunches with a HIP event recorded after every launch
  * on the launch stream: avg_ms[BP_PROF_*] = average duration of one launch of that class AS IT RUNS INSIDE THE
  * STEP (previous event -> own event, i.e. the kernel plus the dependent-launch boundary in front of it),
- * launches_per_step[] = how many launches of the class a step makes.  Trains like bp_train_resident does. */
+ * launches_per_step[] = how many launches of the class a step makes.  Trains like bp_train_resident does: the same bits in the
+ * weights and the momentum state, the same advance of the dropout stream, the chunk left resident.
+ * Refusals of bp_profile_step, in this order: BP_ERR_STATE on a bf16 or data-parallel handle (checked first), then the two of
+ * bp_train_resident: a frame range outside the resident chunk (BP_ERR_ARG), a chunk without targets (BP_ERR_STATE). */
 enum { BP_PROF_FWD_L1 = 0, BP_PROF_FWD_HIDDEN = 1, BP_PROF_FWD_OUT = 2 /* split-K GEMM with its reduce, one launch */, BP_PROF_DGRAD_OUT = 3,
        BP_PROF_DGRAD_HIDDEN = 4, BP_PROF_WGRAD = 5 /* every layer's wgrad + update: one grouped launch */, BP_PROF_KINDS = 6 };
 int bp_profile_step(bp_handle *h, int first_frame, int n_bunches, float *avg_ms, int *launches_per_step);

@@ -10,8 +10,11 @@ buffers, the forward mode, the output switches) is invisible to a caller.  What 
     out                              the output setting (Config.outs)
     fwd                              the forward mode (0 default, 1 row-invariant)
     bunches                          training bunches so far (= the position of the dropout stream)
+    nat, maker_nat, post             (the extended table only) the noise-aware mode, the mode the resident chunk was made in, and
+                                     the post-processing setting
 
-KINDS is the one table of call kinds.  Each entry has four fields: `pre` (the precondition in model terms: None when it holds, else
+KINDS is the one table of call kinds of the fifteen walks `test_walk` runs; XKINDS, further down, is a superset of it with walks
+of its own (`test_extended_walk`) and API classifies every handle function of the header by the kinds that call it.  Each entry has four fields: `pre` (the precondition in model terms: None when it holds, else
 the name of what is wrong), `training` (changes weights or momentum, or a switch that training reads: the replay handle R repeats
 it; a query is left out of R), `apply` (how a successful call changes the model state) and `fail` (the status the call returns for
 each way its precondition can fail, BP_ERR_ARG or BP_ERR_STATE; the model state stays as it was; empty: no precondition).  The rule for what include/bp_c_api.h left open before this
@@ -84,11 +87,12 @@ def mix_rows(clean):
 
 # ------------------------------------------------------------------ the model
 def fresh_state():
-    return dict(maker=None, maker_kind=None, rows=0, windows=False, has_targ=False, preset=0, out=0, fwd=0, bunches=0)
+    return dict(maker=None, maker_kind=None, maker_nat=0, rows=0, windows=False, has_targ=False, preset=0, out=0, fwd=0, bunches=0,
+                nat=0, post=0)
 
 
 def _resident(st, pos, kind, rows, windows, has_targ):
-    st.update(maker=pos, maker_kind=kind, rows=rows, windows=windows, has_targ=has_targ)
+    st.update(maker=pos, maker_kind=kind, maker_nat=st["nat"], rows=rows, windows=windows, has_targ=has_targ)
 
 
 def _pre_none(cfg, st):
@@ -220,8 +224,12 @@ def closed_walk(cfg):
     directed graph with loops on the configuration's kinds (Hierholzer; the order of each node's edges from a seeded shuffle).
     K * K + 1 entries, the last one the first again."""
     ks = kinds_of(cfg)
-    K = len(ks)
-    rng = np.random.default_rng([cfg.index, 7])
+    return [ks[i] for i in _circuit(len(ks), [cfg.index, 7])]
+
+
+def _circuit(K, seed):
+    """An Eulerian circuit of the complete directed graph with loops on K nodes, from node 0."""
+    rng = np.random.default_rng(seed)
     nxt = [list(rng.permutation(K)) for _ in range(K)]
     stack, circuit = [0], []
     while stack:
@@ -232,7 +240,7 @@ def closed_walk(cfg):
             circuit.append(stack.pop())
     circuit.reverse()
     assert len(circuit) == K * K + 1 and circuit[0] == circuit[-1]
-    return [ks[i] for i in circuit]
+    return circuit
 
 
 # Pieces of the closed walk, each a GPU test of its own from a fresh subject and replay.  A whole closed walk takes about two
@@ -303,7 +311,8 @@ def _targets(cfg, rng, n):
     sL = cfg.ls[-1]
     t = rng.normal(size=(n, sL)).astype(np.float32)
     if len(cfg.outs) > 1:                                      # the logistic columns: targets in [0, 1]
-        t[:, FEA_DIM:] = rng.uniform(size=(n, sL - FEA_DIM)).astype(np.float32)
+        lo = cfg.outs[0][1]
+        t[:, lo:] = rng.uniform(size=(n, sL - lo)).astype(np.float32)
     return t
 
 
@@ -350,6 +359,342 @@ def call_data(cfg, walk, pos, kind):
         x = (rng.normal(size=STREAM_LEN) * 3000.0).astype(np.float32)
         return dict(blocks=np.split(x, np.cumsum(STREAM_BLOCKS)[:-1]))
     return {}
+
+
+# ------------------------------------------------------------------ the extended table
+# KINDS above was closed at 19 kinds and its fifteen walks stay as they are (tests/test_size_coverage.py pins their digest).  XKINDS is
+# a superset: the two switches the handle gained since (the noise-aware mode, post-processing), the two calls that share the ev_*
+# buffers with bp_eval_mix, and the two measurement calls that bench.py makes on the handle it goes on measuring with.  Model state
+# they add: nat (0 static, 1 dynamic; maker_nat: the mode the resident chunk was made in) and post (an index into post_settings).
+# A precondition of the extended table takes the call's position too: what a call asks for beyond its data -- the score width, the
+# target, the GV stage, the tracker, the kernel id -- is a function of (configuration, position) alone (choice).
+#
+# Configuration D: fp32, FOUR layers (bp_time_kernel's ids 0..2 need a hidden -> hidden layer), logistic on the mask columns of an
+# output [LPS | MFCC | mask] (bp_set_mix_aux before the corpus), a corpus with bp_set_mix_reverb derived entries that the plans of
+# train_mix / cv_mix / mix_features / eval_mix / gv_mix draw on.
+N_CEPS = 5
+AUX = dict(sample_rate=SAMPLE_RATE, n_mel=8, n_ceps=N_CEPS, first_coef=1, lifter=0.0)
+RIR_TAPS = [40, 24]
+REVERB_PAIRS = [(3, 0), (0, 1)]                                # (clean sentence, response): corpus entries 4 and 5, as long as 3 and 0
+REVERB_TARGET, EARLY_TAPS = "early", 10
+XCONFIGS = CONFIGS + [
+    Config("D", 3, [132, 64, 64, 2 * FEA_DIM + N_CEPS], 16, 0, 0, [(1, FEA_DIM + N_CEPS, 0), (1, FEA_DIM + N_CEPS, 1), (0, 0, 0)], "lps+irm"),
+]
+XBY_ID = {c.id: c for c in XCONFIGS}
+WIDTHS = (3, 5, 7)                                             # bp_eval_mix | bp_eval_mix_ext with 5 | with 7 score columns
+NAT_MODES = ("static", "dynamic")
+TIME_ITERS = (1, 2, 3)
+
+
+def has_reverb(cfg):
+    return cfg.id == "D"
+
+
+def mask_col(cfg):
+    """First column of the mask block in the net's output, or None on a net without one."""
+    return None if cfg.ls[-1] == FEA_DIM else cfg.outs[0][1]
+
+
+def post_settings(cfg):
+    """What set_post cycles through: (GV on?, gate: None | (lo, hi, weight)).  A net without mask columns gets GV only."""
+    if mask_col(cfg) is None:
+        return [(False, None), (True, None)]
+    return [(False, None), (True, None), (True, (0.3, 0.7, 0.5)), (False, (0.5, 0.5, 1.0))]
+
+
+def gv_arrays(cfg):
+    """(center, scale) of the GV setting: any finite centre and positive scale serve a bit-for-bit comparison."""
+    rng = np.random.default_rng([cfg.index, 55])
+    return rng.normal(10.0, 2.0, FEA_DIM).astype(np.float32), rng.uniform(0.6, 1.6, FEA_DIM).astype(np.float32)
+
+
+def time_ids(cfg):
+    """The kernel ids bp_time_kernel accepts on this net (0..2 need numlayers >= 4)."""
+    return list(range(6)) if len(cfg.ls) >= 4 else [3, 4, 5]
+
+
+def _mix(pos, salt, n):
+    """A choice among n by position: a fixed integer hash, no state."""
+    x = (pos * 2654435761 + salt * 40503 + 12345) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 2246822519) & 0xFFFFFFFF
+    x ^= x >> 13
+    return int(x % n)
+
+
+def choice(cfg, pos, kind):
+    """What the call at position pos asks for beyond its data."""
+    if kind == "eval_mix":
+        return dict(width=WIDTHS[_mix(pos, 1, 3)], masked=bool(_mix(pos, 2, 2)))
+    if kind == "eval_mix_logmmse":
+        return dict(width=WIDTHS[_mix(pos, 1, 3)], noise=(None, "spp")[_mix(pos, 3, 2)])
+    if kind == "gv_mix":
+        return dict(stage=("raw", "post")[_mix(pos, 4, 2)])
+    if kind == "time_kernel":
+        ids = time_ids(cfg)
+        return dict(which=ids[_mix(pos, 5, len(ids))], iters=TIME_ITERS[_mix(pos, 6, len(TIME_ITERS))])
+    return {}
+
+
+def x_train_clean(cfg):
+    """train_clean with the first long sentence taken from the room (entry 4 is sentence 3 reverberated: the same frames)."""
+    c = train_clean(cfg)
+    return [4] + c[1:] if has_reverb(cfg) else c
+
+
+def x_query_clean(cfg):
+    return [5, 3] if has_reverb(cfg) else QUERY_CLEAN             # (entry 5 is sentence 0 reverberated)
+
+
+def _pre_eval_mix_x(cfg, st, pos):
+    if st["post"] and mask_col(cfg) is not None and choice(cfg, pos, "eval_mix")["masked"]:
+        return "mask target under post-processing"
+    return None
+
+
+def _pre_time_kernel(cfg, st, pos):
+    if cfg.dtype == 1:
+        return "bf16"                                          # (checked first)
+    if st["rows"] < cfg.B or st["windows"]:
+        return "no stacked chunk"
+    return None
+
+
+def _pre_profile_step(cfg, st, pos):
+    return "bf16" if cfg.dtype == 1 else _pre_resident_bunch(cfg, st)
+
+
+def _ap_set_nat(cfg, st, pos):
+    st["nat"] ^= 1
+
+
+def _ap_set_post(cfg, st, pos):
+    st["post"] = (st["post"] + 1) % len(post_settings(cfg))
+
+
+def _lift(k):
+    """A kind of KINDS in the extended table: its precondition does not read the position."""
+    return Kind(k.name, lambda cfg, st, pos, pre=k.pre: pre(cfg, st), k.training, k.apply, k.fail)
+
+
+XKINDS = collections.OrderedDict((k.name, k) for k in [_lift(k) for k in KINDS.values()] + [
+    # read by bp_train_mix: the replay repeats it
+    Kind("set_nat", lambda cfg, st, pos: None, True, _ap_set_nat, {}),
+    # "The log-MMSE calls, training and CV are unaffected.": the replay leaves it out, like set_forward
+    Kind("set_post", lambda cfg, st, pos: None, False, _ap_set_post, {}),
+    Kind("gv_mix", lambda cfg, st, pos: None, False, _ap_query_chunk("gv_mix", True, False, _q41), {}),
+    Kind("eval_mix_logmmse", lambda cfg, st, pos: None, False, _ap_query_chunk("eval_mix_logmmse", True, False, _q41), {}),
+    # no training and no query: the handle trains on like the replay, which never made the call
+    Kind("time_kernel", _pre_time_kernel, False, _ap_nothing, {"bf16": BP_ERR_STATE, "no stacked chunk": BP_ERR_STATE}),
+    # profile_step(0, 1) is one bunch: the replay runs train_resident(0, B) in its place (REPLAY_AS)
+    Kind("profile_step", _pre_profile_step, True, _ap_train_resident, dict(_FAIL_RESIDENT_BUNCH, bf16=BP_ERR_STATE)),
+])
+XKINDS["eval_mix"] = XKINDS["eval_mix"]._replace(pre=_pre_eval_mix_x, fail={"mask target under post-processing": BP_ERR_ARG})
+NEW_KINDS = [k for k in XKINDS if k not in KINDS]
+REPLAY_AS = {"profile_step": "train_resident"}
+# non-training kinds that are no query: nothing to compare with a fresh handle
+NO_FRESH = ("checkpoint", "set_forward", "set_post", "time_kernel")
+READS_NAT = ("train_mix", "cv_mix", "mix_features", "enhance", "eval_mix", "gv_mix", "stream")
+READS_POST = ("enhance", "eval_mix", "gv_mix", "stream")      # (gv_mix: at stage POST)
+TRAINING_KINDS = [k for k, v in KINDS.items() if v.training and k not in ("preset", "set_output")]
+
+
+def x_kinds_of(cfg):
+    return [k for k in XKINDS if k != "set_output" or len(cfg.outs) > 1]
+
+
+def x_run_model(cfg, calls, st=None):
+    """run_model over the extended table."""
+    st = fresh_state() if st is None else dict(st)
+    out = []
+    for pos, kind in calls:
+        k = XKINDS[kind]
+        before = dict(st)
+        why = k.pre(cfg, st, pos)
+        status = BP_OK if why is None else k.fail[why]
+        if why is None:
+            k.apply(cfg, st, pos)
+        out.append(Step(pos, kind, status, before, dict(st)))
+    return out
+
+
+def x_closed_walk(cfg):
+    ks = x_kinds_of(cfg)
+    return [ks[i] for i in _circuit(len(ks), [cfg.index, X_CLOSED_SEED])]
+
+
+# Pieces of the extended closed walk (625 pairs, 576 on B).  A whole one takes 0.8 to 0.9 seconds on an MI355X in the run whose figures
+# are committed (3.0 to 3.4 on another day, measured in two halves), under the ten it may take: ONE piece.  With more, the rule of
+# `pieces` holds.
+X_N_PIECES = 1
+# (the seeds: the first at which every claim of tests/test_sequence_coverage.py about the extended walks holds in all configurations)
+X_N_RANDOM, X_SEED, X_CLOSED_SEED = 4, 3000, 17
+
+
+def x_pieces(cfg, n_pieces=None):
+    P = X_N_PIECES if n_pieces is None else n_pieces
+    w = x_closed_walk(cfg)
+    n = len(w) - 1
+    cuts = [round(i * n / P) for i in range(P + 1)]
+    return [[(p, w[p]) for p in range(cuts[i], cuts[i + 1] + 1)] for i in range(P)]
+
+
+def x_random_walk(cfg, seed):
+    ks = x_kinds_of(cfg)
+    rng = np.random.default_rng([cfg.index, X_SEED + seed])
+    return [(p, ks[int(rng.integers(len(ks)))]) for p in range(RANDOM_LEN)]
+
+
+N_TIME_TAIL = 16
+
+
+def measure_walk(cfg):
+    """The measurement calls where they succeed, which a seeded walk reaches by luck alone (bp_time_kernel wants a stacked chunk of a
+    bunch, bp_profile_step one with targets): each behind a chunk it accepts and in front of every training kind, then a row of
+    bp_time_kernel calls, whose kernel id follows the position, behind one stacked chunk."""
+    out = []
+    for t in TRAINING_KINDS:
+        out += ["train", "time_kernel", t, "checkpoint", "train_windows", "profile_step", t, "checkpoint"]
+    out += ["upload_train"] + ["time_kernel"] * N_TIME_TAIL + ["train_resident", "checkpoint"]
+    return list(enumerate(out))
+
+
+def x_walk_ids(cfg):
+    return ["x" + _piece_id(i, X_N_PIECES) for i in range(X_N_PIECES)] + ["xmeasure"] + ["xrandom%d" % s for s in range(X_N_RANDOM)]
+
+
+def x_walk_calls(cfg, wid):
+    """(walk number for the data, calls) of one extended walk id; the walk numbers lie behind the legacy walks'."""
+    if wid.startswith("xclosed"):
+        return 10, x_pieces(cfg)[int(wid[7:] or 0)]
+    if wid == "xmeasure":
+        return 11, measure_walk(cfg)
+    s = int(wid[7:])
+    return 12 + s, x_random_walk(cfg, s)
+
+
+def x_pair_table(cfg, n_pieces=None):
+    out = {}
+    for i, p in enumerate(x_pieces(cfg, n_pieces)):
+        for (_, a), (_, b) in zip(p, p[1:]):
+            out.setdefault((a, b), []).append("x" + _piece_id(i, X_N_PIECES if n_pieces is None else n_pieces))
+    return out
+
+
+def x_all_steps(cfg):
+    """[(walk id, steps)] of every extended walk, each from a fresh handle."""
+    return [(wid, x_run_model(cfg, x_walk_calls(cfg, wid)[1])) for wid in x_walk_ids(cfg)]
+
+
+def x_test_id(cfg, wid):
+    return "tests/test_sequence_gpu.py::test_extended_walk[%s-%s]" % (cfg.id, wid)
+
+
+X_GPU_TESTS = [x_test_id(c, w) for c in XCONFIGS for w in x_walk_ids(c)]
+
+
+def x_corpus(cfg):
+    """corpus(cfg); on D also the responses, the pairs and the MFCC setting."""
+    cor = corpus(cfg)
+    if has_reverb(cfg):
+        rng = np.random.default_rng([cfg.index, 98])
+        rirs = []
+        for n in RIR_TAPS:
+            h = (rng.normal(size=n) * np.exp(-np.arange(n) / 8.0)).astype(np.float32)
+            h[3] = 3.0                                         # the direct path
+            rirs.append(h)
+        cor.update(rirs=rirs, pair_clean=[c for c, _ in REVERB_PAIRS], pair_rir=[r for _, r in REVERB_PAIRS], reverb_target=REVERB_TARGET,
+                   early_taps=EARLY_TAPS, aux=dict(AUX))
+    return cor
+
+
+def x_call_data(cfg, walk, pos, kind):
+    """call_data for the extended table: the new kinds, the plans of D, and what the call asks for beyond its data (choice)."""
+    rng = np.random.default_rng([cfg.index, walk, pos])
+    if kind == "train_mix":
+        clean = x_train_clean(cfg)
+        return dict(plan=_plan(rng, clean), order=MX.shuffle(1 + pos, 10 * walk + cfg.index, mix_rows(train_clean(cfg))))
+    if kind in ("cv_mix", "mix_features", "eval_mix", "gv_mix", "eval_mix_logmmse"):
+        return dict(choice(cfg, pos, kind), plan=_plan(rng, x_query_clean(cfg)))
+    if kind in NEW_KINDS:
+        return choice(cfg, pos, kind)
+    return call_data(cfg, walk, pos, kind)
+
+
+# ------------------------------------------------------------------ every entry point that takes a handle
+# include/bp_c_api.h function (first parameter bp_handle *) -> the kinds of XKINDS whose call (tests/walk_harness.py) makes it, or
+# (one line of reason, the test file that holds it instead).  tests/test_sequence_coverage.py parses the header and fails on a
+# symbol that is not here, on a kind that is not in the table, and on a kind no entry names.
+API = collections.OrderedDict([
+    ("bp_destroy", ("every walk closes its handles: nothing is carried behind it", "tests/test_mem_gpu.py", ".close()")),
+    ("bp_set_hyper", ["preset"]),
+    ("bp_set_output", ["set_output"]),
+    ("bp_set_forward", ["set_forward"]),
+    ("bp_train_chunk", ["train"]),
+    ("bp_cv_chunk", ["cv"]),
+    ("bp_forward", ["forward"]),
+    ("bp_get_weights", ["checkpoint"]),
+    ("bp_get_deltas", ["checkpoint"]),
+    ("bp_upload_chunk", ["upload_train", "grads"]),
+    ("bp_fill_chunk_synthetic", ["grads", "grads_resident"]),   # (the fresh handle's way to the subject's dropout position)
+    ("bp_train_resident", ["upload_train", "train_resident"]),
+    ("bp_sync", ("a host wait on the handle's stream: it changes nothing", "tests/test_gpu_parity.py", ".sync()")),
+    ("bp_train_resident_masked", ("its own parity tests; its refusals stand beside train_resident's", "tests/test_sequence_gpu.py")),
+    ("bp_upload_chunk_windows", ["grads_resident", "train_resident"]),   # (load: the chunk a window call left, on a fresh handle)
+    ("bp_train_chunk_windows", ["train_windows"]),
+    ("bp_cv_chunk_windows", ["cv_windows"]),
+    ("bp_forward_windows", ("bp_cv_chunk_windows without targets: the same upload, the same forward", "tests/test_infer_gpu.py")),
+    ("bp_enhance_waves", ["enhance"]),
+    ("bp_set_mix_corpus", ("the construction of every walked handle", "tests/walk_harness.py", "g.set_mix_corpus(")),
+    ("bp_train_mix", ["train_mix"]),
+    ("bp_cv_mix", ["cv_mix"]),
+    ("bp_mix_features", ["mix_features"]),
+    ("bp_set_mix_aux", ("configuration D's construction: the MFCC columns, set before the corpus", "tests/walk_harness.py", "g.set_mix_aux(")),
+    ("bp_set_mix_reverb", ("configuration D's construction: the derived entries its plans draw on", "tests/walk_harness.py", "g.set_mix_reverb(")),
+    ("bp_eval_mix", ["eval_mix"]),
+    ("bp_eval_mix_ext", ["eval_mix"]),
+    ("bp_eval_mix_logmmse", ["eval_mix_logmmse"]),
+    ("bp_eval_mix_logmmse_ext", ["eval_mix_logmmse"]),
+    ("bp_eval_mix_logmmse_nt", ["eval_mix_logmmse"]),
+    ("bp_stream_open", ["stream"]),
+    ("bp_set_nat", ["set_nat"]),
+    ("bp_set_post", ["set_post"]),
+    ("bp_gv_mix", ["gv_mix"]),
+    ("bp_grads_resident", ["grads", "grads_resident"]),
+    ("bp_grad_floats", ["grads", "grads_resident"]),
+    ("bp_grad_layout", ["grads", "grads_resident"]),
+    ("bp_read_grads", ["grads", "grads_resident"]),
+    ("bp_read_layer_output", ("a pure read of the last bunch's activations", "tests/test_gpu_parity.py")),
+    # (the life of an attachment: tests/test_dp_life_gpu.py starts tests/dp_life_worker.py)
+    ("bp_dp_attach", ("data-parallel handles; the binding attaches through bp_dp_attach_ex", "tests/dp_life_worker.py", "dp_attach(")),
+    ("bp_dp_attach_ex", ("data-parallel handles: the life of an attachment", "tests/dp_life_worker.py", "dp_attach(")),
+    ("bp_dp_detach", ("data-parallel handles: the life of an attachment", "tests/dp_life_worker.py")),
+    ("bp_dp_info", ("a pure read of the attachment", "tests/dp_life_worker.py")),
+    ("bp_dp_peer_info", ("a pure read of the attachment", "tests/dp_worker.py")),
+    ("bp_dp_handoff", ("a pure read of the attachment", "tests/test_dp_native.py")),
+    ("bp_dp_barrier", ("host-side, over the rendezvous block", "bench.py")),
+    ("bp_dp_allgather", ("host-side, over the rendezvous block", "bench.py", "dp_allgather_f64(")),
+    ("bp_last_train_ms", ("a pure read of the two events around the last bunch loop; no test makes it", "tools/bench_bf16.py")),
+    ("bp_time_kernel", ["time_kernel"]),
+    ("bp_profile_step", ["profile_step"]),
+    ("bp_measure_peaks", ("it touches only the handle's stream and allocates 2 GiB", "bench.py")),
+])
+
+
+def api_problems(api, kinds, header_text):
+    """What is wrong between the header's handle functions, the API map and the kind table, each problem by name."""
+    import re
+    flat = re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S)
+    fns = re.findall(r"\b(bp_\w+)\s*\(\s*bp_handle\s*\*", flat)
+    out = ["unclassified entry point %s" % f for f in fns if f not in api]
+    out += ["%s is classified but the header has no such handle function" % f for f in api if f not in fns]
+    named = set()
+    for f, v in api.items():
+        if isinstance(v, list):
+            named.update(v)
+            out += ["%s names the kind %s, which the table does not have" % (f, k) for k in v if k not in kinds]
+    out += ["no entry point names the kind %s" % k for k in kinds if k not in named]
+    return out
 
 
 # ------------------------------------------------------------------ the figures of a GPU run

@@ -12,6 +12,7 @@ import json
 import os
 import re
 
+import numpy as np
 import pytest
 
 import dispatch_np as D
@@ -267,3 +268,306 @@ def test_committed_numbers_hold_zero_differing_words_for_every_walk():
     end = num["tests/test_dp_life_gpu.py::test_life_equals_one_attachment_and_one_rank"]
     assert end["life_vs_one_attachment_words_differing"] == 0 and end["life_rank0_vs_rank1_words_differing"] == 0
     assert max(end["life_vs_one_rank_global_bunch"].values()) < end["strict_bar"] == 1e-5
+
+
+# ------------------------------------------------------------------ 6. the extended table (sequence_model.XKINDS)
+XIDS = [c.id for c in SM.XCONFIGS]
+RAW_HEADER = open(os.path.join(ROOT, "include", "bp_c_api.h")).read()
+
+
+def _x_missing_and_repeated(cfg, pieces):
+    ks = SM.x_kinds_of(cfg)
+    seen = collections.Counter((a, b) for p in pieces for (_, a), (_, b) in zip(p, p[1:]))
+    return sorted((a, b) for a in ks for b in ks if seen[(a, b)] == 0), sorted(k for k, n in seen.items() if n > 1)
+
+
+def _why(cfg, s):
+    return SM.XKINDS[s.kind].pre(cfg, s.before, s.pos)
+
+
+def test_the_extended_table_is_a_superset_and_the_old_one_is_as_it_was():
+    assert list(SM.XKINDS)[:len(SM.KINDS)] == list(SM.KINDS) and len(SM.KINDS) == 19
+    assert SM.NEW_KINDS == ["set_nat", "set_post", "gv_mix", "eval_mix_logmmse", "time_kernel", "profile_step"]
+    for name, k in SM.KINDS.items():
+        x = SM.XKINDS[name]
+        assert (x.training, x.apply) == (k.training, k.apply) and (x.fail == k.fail or name == "eval_mix")
+    assert [n for n in SM.NEW_KINDS if SM.XKINDS[n].training] == ["set_nat", "profile_step"]
+    assert SM.XCONFIGS[:3] == SM.CONFIGS and [c.id for c in SM.XCONFIGS] == ["A", "B", "C", "D"]
+    assert not set(SM.X_GPU_TESTS) & set(SM.GPU_TESTS) and len(SM.X_GPU_TESTS) == 4 * (SM.X_N_PIECES + 1 + SM.X_N_RANDOM)
+    # on the old kinds and configurations a call of an extended walk is made of what call_data makes (eval_mix: plus its choices)
+    for cfg in SM.CONFIGS:
+        for kind in SM.KINDS:
+            a, b = SM.x_call_data(cfg, 10, 4, kind), SM.call_data(cfg, 10, 4, kind)
+            assert sorted(set(a) - set(b)) == (["masked", "width"] if kind == "eval_mix" else []), kind
+            for key in b:
+                assert repr(a[key]) == repr(b[key]) and np.asarray(a[key], dtype=object).shape == np.asarray(b[key], dtype=object).shape, (kind, key)
+
+
+@pytest.mark.parametrize("cid", XIDS)
+def test_the_extended_closed_walk_takes_every_ordered_pair_once(cid):
+    cfg = SM.XBY_ID[cid]
+    ks = SM.x_kinds_of(cfg)
+    assert len(ks) == (25 if len(cfg.outs) > 1 else 24) and len(set(ks)) == len(ks) and set(SM.kinds_of(cfg)) < set(ks)
+    pieces = SM.x_pieces(cfg)
+    assert sum(len(p) - 1 for p in pieces) == len(ks) ** 2 and _x_missing_and_repeated(cfg, pieces) == ([], [])
+    assert sorted(SM.x_pair_table(cfg)) == sorted((a, b) for a in ks for b in ks)
+    for n_pieces in (1, 2, 3, 7):                               # cut, a piece starts with the call the one before it ended with
+        ps = SM.x_pieces(cfg, n_pieces)
+        assert len(ps) == n_pieces and _x_missing_and_repeated(cfg, ps) == ([], [])
+        assert all(ps[i][-1] == ps[i + 1][0] for i in range(n_pieces - 1)) and ps[0][0][1] == ps[-1][-1][1]
+        assert all(len(v) == 1 for v in SM.x_pair_table(cfg, n_pieces).values())
+    ids = SM.x_walk_ids(cfg)
+    assert ids == ["xclosed", "xmeasure"] + ["xrandom%d" % s for s in range(4)] and SM.X_N_PIECES == 1
+    walks = {}
+    for wid in ids:
+        walk, calls = SM.x_walk_calls(cfg, wid)
+        walks[wid] = walk
+        assert [p for p, _ in calls] == list(range(calls[0][0], calls[0][0] + len(calls))) and all(k in ks for _, k in calls)
+    # the data of a walk follows its number: none of the legacy walks' (0 .. 4), no two the same
+    assert len(set(walks.values())) == len(ids) and min(walks.values()) > SM.N_RANDOM
+    rnd = [SM.x_random_walk(cfg, s) for s in range(SM.X_N_RANDOM)]
+    assert all(len(w) == SM.RANDOM_LEN for w in rnd) and len(set(map(tuple, rnd))) == SM.X_N_RANDOM
+    assert all(SM.x_random_walk(cfg, s) != SM.random_walk(cfg, s) for s in range(SM.X_N_RANDOM))
+    for at in (1, len(pieces[0]) // 2, len(pieces[0]) - 2):     # a removed call is noticed and named
+        cut = [list(p) for p in pieces]
+        gone = cut[0].pop(at)
+        missing, _ = _x_missing_and_repeated(cfg, cut)
+        before, after = pieces[0][at - 1][1], pieces[0][at + 1][1]
+        assert missing and set(missing) <= {(before, gone[1]), (gone[1], after)}, (at, gone, missing)
+        assert len(missing) == 2 or gone[1] in (before, after)
+
+
+@pytest.mark.parametrize("cid", XIDS)
+def test_every_extended_kind_succeeds_and_every_precondition_fails_somewhere(cid):
+    cfg = SM.XBY_ID[cid]
+    closed = [s for wid, ss in SM.x_all_steps(cfg) if wid.startswith("xclosed") for s in ss]
+    status, reasons = collections.defaultdict(set), collections.defaultdict(set)
+    for s in closed:
+        status[s.kind].add(s.status)
+        if s.status != SM.BP_OK:                                # a failed call leaves the model state as it was
+            assert s.before == s.after and SM.XKINDS[s.kind].fail[_why(cfg, s)] == s.status
+            reasons[s.kind].add(_why(cfg, s))
+    bf16, masked = cfg.dtype == 1, SM.mask_col(cfg) is not None
+    for kind in SM.x_kinds_of(cfg):
+        want = set(SM.XKINDS[kind].fail)
+        if kind in ("set_forward", "time_kernel", "profile_step") and bf16:
+            want = {"bf16"}                                     # (checked first: nothing behind it is reached)
+        elif kind in ("set_forward", "time_kernel", "profile_step"):
+            want -= {"bf16"}
+        if kind == "eval_mix" and not masked:
+            want = set()
+        assert reasons[kind] == want, (cid, kind, reasons[kind], want)
+        assert (SM.BP_OK in status[kind]) == (not (bf16 and "bf16" in SM.XKINDS[kind].fail)), (cid, kind)
+    assert [n for n, k in SM.XKINDS.items() if k.fail] == ["train_resident", "eval_mix", "grads_resident", "set_forward", "time_kernel", "profile_step"]
+    # the bunch counter: profile_step(0, 1) is one bunch, the other new kinds none
+    for s in closed:
+        d = s.after["bunches"] - s.before["bunches"]
+        want = {"train": 2, "train_windows": 2, "upload_train": 3, "train_resident": 1, "train_mix": 2, "profile_step": 1}.get(s.kind, 0)
+        assert d == (want if s.status == SM.BP_OK else 0), (s.kind, d)
+
+
+# (kind, configuration ids, model state, position or None for any, reason or None, the sentence of the header)
+_TK = "Refusals of bp_time_kernel, in this order:"
+_PS = "Refusals of bp_profile_step, in this order:"
+X_HEADER_STATUS = [
+    ("time_kernel", "C", dict(rows=1000), "bf16", "BP_ERR_STATE on a bf16 handle (the first of the state checks)"),
+    ("time_kernel", "C", dict(rows=0), "bf16", "BP_ERR_STATE on a bf16 handle (the first of the state checks)"),
+    ("time_kernel", "ABD", dict(rows=0), "no stacked chunk", "BP_ERR_STATE when no stacked chunk of at least bunchsize rows is resident"),
+    ("time_kernel", "ABD", dict(rows=1000, windows=True), "no stacked chunk", "BP_ERR_STATE when no stacked chunk of at least bunchsize rows is resident"),
+    ("time_kernel", "ABD", dict(rows=1000, has_targ=False), None, "It runs on the first bunchsize rows of a resident STACKED chunk, with or without targets"),
+    ("profile_step", "C", dict(rows=0), "bf16", "BP_ERR_STATE on a bf16 or data-parallel handle (checked first)"),
+    ("profile_step", "ABD", dict(rows=8, has_targ=False), "range", "then the two of bp_train_resident: a frame range outside the resident chunk (BP_ERR_ARG)"),
+    ("profile_step", "ABD", dict(rows=1000, has_targ=False), "no targets", "a chunk without targets (BP_ERR_STATE)"),
+    ("profile_step", "ABD", dict(rows=1000, has_targ=True), None, "Trains like bp_train_resident does: the same bits in the weights and the momentum state"),
+]
+
+
+def test_the_extended_model_is_the_headers():
+    assert _TK in HEADER and _PS in HEADER
+    for kind, cids, state, why, quote in X_HEADER_STATUS:
+        assert quote in HEADER, quote
+        for cid in cids:
+            cfg = SM.XBY_ID[cid]
+            got = SM.XKINDS[kind].pre(cfg, dict(SM.fresh_state(), **state), 0)
+            assert got == why, (kind, cid, state, got)
+            if why is not None:
+                assert SM.STATUS_NAMES[SM.XKINDS[kind].fail[why]] in quote
+    for name in ("time_kernel", "profile_step"):                # every reason of the two is held to a sentence
+        assert set(SM.XKINDS[name].fail) == set(w for k, _, _, w, _ in X_HEADER_STATUS if k == name and w)
+    # the order of the sentences in the header is the order of the checks in the model
+    tk = HEADER[HEADER.index(_TK):]
+    assert tk.index("on a bf16 handle") < tk.index("when no stacked chunk") < tk.index("The handle is unchanged after each.")
+    # bp_time_kernel: what it leaves and what it may overwrite; no training, no query, left out of the replay
+    assert ("bp_time_kernel leaves the weights, the momentum state, the resident chunk and the position of the dropout stream unchanged"
+            in HEADER and "it may overwrite the activations and the back-propagated errors of the last bunch" in HEADER)
+    tk_kind = SM.XKINDS["time_kernel"]
+    st = dict(SM.fresh_state(), rows=1000, has_targ=True)
+    before = dict(st)
+    tk_kind.apply(SM.XBY_ID["D"], st, 0)
+    assert st == before and not tk_kind.training and "time_kernel" in SM.NO_FRESH
+    assert SM.time_ids(SM.XBY_ID["D"]) == [0, 1, 2, 3, 4, 5] and all(SM.time_ids(SM.XBY_ID[c]) == [3, 4, 5] for c in "ABC")
+    assert "ids 0..2 on a net without a hidden -> hidden layer" in HEADER
+    # bp_profile_step is one bunch of bp_train_resident: the replay makes that call in its place
+    assert SM.REPLAY_AS == {"profile_step": "train_resident"} and SM.XKINDS["profile_step"].apply is SM.KINDS["train_resident"].apply
+    # the switches: who reads them
+    assert "bp_enhance_waves, bp_train_mix, bp_cv_mix, bp_mix_features, bp_eval_mix and bp_eval_mix_ext" in HEADER      # bp_set_nat
+    assert SM.XKINDS["set_nat"].training and set(SM.READS_NAT) == {"train_mix", "cv_mix", "mix_features", "enhance", "eval_mix", "gv_mix", "stream"}
+    assert "The log-MMSE calls, training and CV are unaffected." in HEADER and not SM.XKINDS["set_post"].training
+    assert "on the corpus and the handle state of bp_eval_mix (fp32 and bf16 handles, both noise-aware modes" in HEADER      # bp_gv_mix reads nat
+    # bp_eval_mix on the mask target under post-processing
+    quote = "they return BP_ERR_ARG, with nothing touched, when the call's fea_dim differs from the one that was set, and when the target is BP_WAVE_MASK"
+    assert quote in HEADER and SM.XKINDS["eval_mix"].fail == {"mask target under post-processing": SM.BP_ERR_ARG}
+    for cfg in SM.XCONFIGS:
+        pos_masked = [p for p in range(64) if SM.choice(cfg, p, "eval_mix")["masked"]][0]
+        pos_lps = [p for p in range(64) if not SM.choice(cfg, p, "eval_mix")["masked"]][0]
+        for post in range(len(SM.post_settings(cfg))):
+            st = dict(SM.fresh_state(), post=post)
+            refused = post > 0 and SM.mask_col(cfg) is not None
+            assert (SM.XKINDS["eval_mix"].pre(cfg, st, pos_masked) is not None) == refused
+            assert SM.XKINDS["eval_mix"].pre(cfg, st, pos_lps) is None
+    # what the two new queries leave resident
+    x_resident = {"gv_mix": "bp_gv_mix leaves the chunk as the resident window chunk, without targets, as bp_eval_mix does",
+                  "eval_mix_logmmse": HEADER_RESIDENT["forward"][2]}
+    assert "bp_eval_mix[_logmmse]" in x_resident["eval_mix_logmmse"]
+    for kind, quote in x_resident.items():
+        assert quote in HEADER, quote
+        for cfg in SM.XCONFIGS:
+            st = SM.fresh_state()
+            SM.XKINDS[kind].apply(cfg, st, 0)
+            assert (st["windows"], st["has_targ"], st["maker_kind"], st["rows"]) == (True, False, kind, SM.mix_rows(SM.QUERY_CLEAN))
+    queries = [n for n in SM.NEW_KINDS if not SM.XKINDS[n].training and n not in SM.NO_FRESH]
+    assert queries == sorted(x_resident, reverse=True)
+
+
+@pytest.mark.parametrize("cid", XIDS)
+def test_every_switch_setting_is_read_by_every_kind_that_reads_it(cid):
+    """From the model alone: each kind that reads the noise-aware mode succeeds under both modes, each kind that reads
+    post-processing under every setting the configuration has, profile_step and time_kernel are each followed by every training
+    kind (where they can succeed: by a call that succeeds behind one that did), every score width follows every other, and
+    bp_time_kernel runs every kernel id the net allows."""
+    cfg = SM.XBY_ID[cid]
+    nat, post, behind = collections.defaultdict(set), collections.defaultdict(set), collections.defaultdict(set)
+    widths, which, stages, trackers, targets = set(), set(), set(), set(), set()
+    for wid, steps in SM.x_all_steps(cfg):
+        last = None
+        for a, b in zip(steps, steps[1:]):
+            if a.kind in ("profile_step", "time_kernel") and (cfg.dtype == 1 or a.status == b.status == SM.BP_OK):
+                behind[a.kind].add(b.kind)
+        for s in steps:
+            if s.status != SM.BP_OK:
+                continue
+            c = SM.choice(cfg, s.pos, s.kind)
+            if s.kind in SM.READS_NAT:
+                nat[s.kind].add(s.before["nat"])
+            if s.kind in SM.READS_POST and (s.kind != "gv_mix" or c["stage"] == "post"):
+                post[s.kind].add(s.before["post"])
+            if s.kind == "time_kernel":
+                which.add(c["which"])
+            if s.kind == "gv_mix":
+                stages.add(c["stage"])
+            if s.kind == "eval_mix":
+                targets.add((c["masked"], s.before["post"] > 0))
+            if s.kind == "eval_mix_logmmse":
+                trackers.add(c["noise"])
+            if "width" in c:
+                if last is not None:
+                    widths.add((last, c["width"]))
+                last = c["width"]
+    for k in SM.READS_NAT:
+        assert nat[k] == {0, 1}, (cid, k, nat[k])
+    for k in SM.READS_POST:
+        assert post[k] == set(range(len(SM.post_settings(cfg)))), (cid, k, post[k])
+    for k in ("profile_step", "time_kernel"):
+        assert set(SM.TRAINING_KINDS) <= behind[k], (cid, k, set(SM.TRAINING_KINDS) - behind[k])
+    assert SM.TRAINING_KINDS == ["train", "train_windows", "upload_train", "train_resident", "train_mix"]
+    assert widths == set((a, b) for a in SM.WIDTHS for b in SM.WIDTHS) and SM.WIDTHS == (3, 5, 7)
+    assert which == (set() if cfg.dtype == 1 else set(SM.time_ids(cfg))), (cid, which)
+    assert stages == {"raw", "post"} and trackers == {None, "spp"}
+    # an eval_mix that succeeds on post-processed rows, and on the nets with mask columns one on the mask target without them
+    assert (False, True) in targets and (SM.mask_col(cfg) is None or (True, False) in targets)
+    assert len(SM.post_settings(cfg)) == (2 if SM.mask_col(cfg) is None else 4) and SM.post_settings(cfg)[0] == (False, None)
+
+
+def test_configuration_d_is_what_the_extended_table_needs():
+    d = SM.XBY_ID["D"]
+    assert len(d.ls) == 4 and d.dtype == 0 and d.ls[0] == (SM.CONTEXT + 1) * SM.FEA_DIM and d.ls[-1] == 2 * SM.FEA_DIM + SM.N_CEPS
+    assert SM.mask_col(d) == SM.FEA_DIM + SM.N_CEPS == d.outs[0][1] and d.outs[0][0] == 1      # logistic on the mask columns alone
+    assert [SM.mask_col(SM.XBY_ID[c]) for c in "ABC"] == [SM.FEA_DIM, None, SM.FEA_DIM]
+    cor = SM.x_corpus(d)
+    assert cor["aux"]["n_ceps"] == SM.N_CEPS and len(cor["rirs"]) == 2 and all(24 <= len(h) <= 48 for h in cor["rirs"])
+    assert len(cor["pair_clean"]) == len(cor["pair_rir"]) == 2 and max(cor["pair_rir"]) < len(cor["rirs"])
+    for c in SM.CONFIGS:                                        # the old configurations' corpus is the old corpus
+        assert sorted(SM.x_corpus(c)) == sorted(SM.corpus(c)) == ["clean", "inv_std", "mean", "noise"]
+    # the derived entries are as long as the sentences the sizes were chosen with: two bunches and a part, 41 query frames
+    n = len(SM.CLEAN_LEN)
+    lens = SM.CLEAN_LEN + [SM.CLEAN_LEN[c] for c in cor["pair_clean"]]
+    for plan_clean, legacy in ((SM.x_train_clean(d), SM.train_clean(d)), (SM.x_query_clean(d), SM.QUERY_CLEAN)):
+        assert [lens[c] for c in plan_clean] == [SM.CLEAN_LEN[c] for c in legacy] and any(c >= n for c in plan_clean)
+    for kind in ("train_mix", "cv_mix", "mix_features", "eval_mix", "gv_mix"):
+        assert any(r[0] >= n for r in SM.x_call_data(d, 10, 7, kind)["plan"]), kind
+    rows = SM.mix_rows(SM.train_clean(d))
+    assert rows // d.B == 2 and rows % d.B and len(SM.x_call_data(d, 10, 7, "train_mix")["order"]) == rows
+    t = SM.x_call_data(d, 10, 7, "train")["t"]                  # targets of the logistic columns in [0, 1], the others free
+    assert t[:, SM.mask_col(d):].min() >= 0 and t[:, SM.mask_col(d):].max() <= 1 and t[:, :SM.mask_col(d)].min() < 0
+    # call_data is a function of (configuration, walk, position): twice the same bytes
+    for kind in SM.x_kinds_of(d):
+        a, b = SM.x_call_data(d, 11, 9, kind), SM.x_call_data(d, 11, 9, kind)
+        assert sorted(a) == sorted(b) and all(repr(a[k]) == repr(b[k]) for k in a), kind
+
+
+# ------------------------------------------------------------------ 7. no entry point outside
+def test_every_handle_function_of_the_header_is_classified():
+    assert SM.api_problems(SM.API, SM.XKINDS, RAW_HEADER) == []
+    fns = re.findall(r"\b(bp_\w+)\s*\(\s*bp_handle\s*\*", re.sub(r"/\*.*?\*/", " ", RAW_HEADER, flags=re.S))
+    assert len(fns) == len(set(fns)) == len(SM.API) >= 50 and "bp_create" not in fns and "bp_stream_push" not in fns
+    for fn, v in SM.API.items():
+        if isinstance(v, list):
+            assert v and len(set(v)) == len(v), fn
+            continue
+        reason, path = v[0], v[1]
+        word = v[2] if len(v) > 2 else fn[3:] + "("
+        assert reason.strip() and "\n" not in reason, fn
+        assert os.path.exists(os.path.join(ROOT, path)), (fn, path)
+        assert word in open(os.path.join(ROOT, path)).read(), (fn, path, word)
+    # the kinds an entry names are the kinds whose call makes it: the binding's method stands in walk_harness.execute / load / make
+    harness = open(os.path.join(ROOT, "tests", "walk_harness.py")).read()
+    for fn in ("bp_set_nat", "bp_set_post", "bp_gv_mix", "bp_eval_mix_logmmse", "bp_time_kernel", "bp_profile_step", "bp_set_mix_aux",
+               "bp_set_mix_reverb"):
+        assert "g.%s(" % fn[3:] in harness, fn
+    # a new symbol without a row, a row without its symbol, and every new kind taken out of the table: each is named
+    assert SM.api_problems(SM.API, SM.XKINDS, RAW_HEADER + "\nint bp_new_call(bp_handle *h, int n);\n") == ["unclassified entry point bp_new_call"]
+    less = collections.OrderedDict((k, v) for k, v in SM.API.items() if k != "bp_gv_mix")
+    assert SM.api_problems(less, SM.XKINDS, RAW_HEADER) == ["unclassified entry point bp_gv_mix", "no entry point names the kind gv_mix"]
+    for gone in SM.NEW_KINDS:
+        table = collections.OrderedDict((k, v) for k, v in SM.XKINDS.items() if k != gone)
+        problems = SM.api_problems(SM.API, table, RAW_HEADER)
+        assert problems and all(p.endswith("names the kind %s, which the table does not have" % gone) for p in problems), (gone, problems)
+    # ... and the old table alone leaves the six outside, by name
+    old = SM.api_problems(SM.API, SM.KINDS, RAW_HEADER)
+    assert sorted(set(p.split("the kind ")[1].split(",")[0] for p in old)) == sorted(SM.NEW_KINDS)
+
+
+# ------------------------------------------------------------------ 8. the extended GPU tests and their figures
+def test_every_extended_gpu_test_exists_and_is_not_skipped():
+    mod = importlib.import_module("test_sequence_gpu")
+    fn = mod.test_extended_walk
+    marks = [mod.pytestmark] + list(getattr(fn, "pytestmark", []))
+    assert any(m.name == "gpu" for m in marks) and not any(m.name in ("skip", "skipif", "xfail") for m in marks)
+    ids = [i for m in marks if m.name == "parametrize" for i in m.kwargs["ids"]]
+    assert ["tests/test_sequence_gpu.py::test_extended_walk[%s]" % i for i in ids] == SM.X_GPU_TESTS
+
+
+def test_committed_numbers_hold_zero_differing_words_for_every_extended_walk_under_ten_seconds():
+    num = json.load(open(NUMBERS))["tests"]
+    for cfg in SM.XCONFIGS:
+        for wid in SM.x_walk_ids(cfg):
+            e = num.get(SM.x_test_id(cfg, wid))
+            assert e is not None, "no measured figure for %s" % SM.x_test_id(cfg, wid)
+            steps = SM.x_run_model(cfg, SM.x_walk_calls(cfg, wid)[1])
+            assert e["words_differing"] == 0 and e["state_vs_replay"] == 0 and e["query_vs_fresh"] == 0 and e["second_pass"] == 0
+            assert e["calls"] == len(steps) and e["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK)
+            assert e["checkpoints"] == sum(1 for s in steps if s.kind == "checkpoint" and s.status == SM.BP_OK)
+            assert e["queries_compared"] == sum(1 for s in steps if s.status == SM.BP_OK and not SM.XKINDS[s.kind].training
+                                                and s.kind not in SM.NO_FRESH)
+            assert e["replay_loads"] >= 0 and (e["queries_compared"] > 0 or wid == "xmeasure")
+            assert e["seconds"] < 10.0, (SM.x_test_id(cfg, wid), e["seconds"])

@@ -13,6 +13,8 @@ Per walk three long-lived handles take part, all made from the same weights and 
       of whatever is resident, F is also given the chunk of the call that made it resident on S (_load).
 Every expected error is a host-side check: its status and a non-empty message are checked on S and S2, and the checkpoints behind it
 still equal R, which never made the call."""
+import time
+
 import pytest
 
 import sequence_model as SM
@@ -34,6 +36,29 @@ def test_walk(pkg, parity_record, cid, wid):
     assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0     # (a size of the walks of tests/size_model.py)
     parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), **dict(count, **diff))
     print(cid, wid, count, diff)
+    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
+
+
+XPARAMS = [(c.id, w) for c in SM.XCONFIGS for w in SM.x_walk_ids(c)]
+
+
+@pytest.mark.parametrize("cid,wid", XPARAMS, ids=["%s-%s" % p for p in XPARAMS])
+def test_extended_walk(pkg, parity_record, cid, wid):
+    """The same procedure over sequence_model.XKINDS: the noise-aware mode and post-processing as switches, bp_gv_mix and the
+    log-MMSE evaluation among the queries, every score width, bp_time_kernel and bp_profile_step between the training calls, and
+    configuration D (four layers, MFCC columns, reverberated corpus entries).  bp_profile_step is replayed as the bunch of
+    bp_train_resident it is said to be; bp_time_kernel and set_post are left out of the replay."""
+    t0 = time.perf_counter()
+    cfg = SM.XBY_ID[cid]
+    walk, calls = SM.x_walk_calls(cfg, wid)
+    steps = SM.x_run_model(cfg, calls)
+    data = [SM.x_call_data(cfg, walk, s.pos, s.kind) for s in steps]
+    count, diff, bad = H.run_walk(pkg, cfg, steps, data, SM.x_corpus(cfg), kinds=SM.XKINDS)
+    assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0
+    assert count["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK)
+    seconds = round(time.perf_counter() - t0, 2)
+    parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), seconds=seconds, **dict(count, **diff))
+    print(cid, wid, seconds, "s", count, diff)
     assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
 
 

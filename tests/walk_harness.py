@@ -14,6 +14,8 @@ Per walk three long-lived handles take part, all made from the same weights and 
       of whatever is resident, F is also given the chunk of the call that made it resident on S (load).
 Every expected error is a host-side check: its status and a non-empty message are checked on S and S2, and the checkpoints behind it
 still equal R, which never made the call.
+With the extended table (sequence_model.XKINDS, passed as `kinds`): R repeats set_nat, makes train_resident(0, B) where S made
+profile_step(0, 1), and leaves out set_post and time_kernel like any query; a chunk is loaded in the noise-aware mode it was made in.
 
 A step is anything with the fields pos, kind, status, before, after of sequence_model.Step; the data of a call say how large it is
 (the rows of x, the sentences, the blocks), so one `execute` serves every size."""
@@ -35,14 +37,35 @@ def plan(pkg, rows):
     return p
 
 
+def apply_post(pkg, g, cfg, setting):
+    """set_post with setting number `setting` of sequence_model.post_settings (0: off)."""
+    gv, gate = SM.post_settings(cfg)[setting]
+    if not gv and gate is None:
+        g.set_post()
+        return
+    center, scale = SM.gv_arrays(cfg) if gv else (None, None)
+    lo, hi, weight = gate or (0.5, 0.5, 1.0)
+    g.set_post(center, scale, mask_col=SM.mask_col(cfg) if gate else -1, mask_lo=lo, mask_hi=hi, mask_weight=weight, fea_dim=SM.FEA_DIM)
+
+
 def make(pkg, cfg, W, b, st, cor, cap=SM.CAP):
-    """A handle in model state st (preset, output setting, forward mode) with the corpus."""
+    """A handle in model state st (preset, output setting, forward mode, noise-aware mode, post-processing) with the corpus (on
+    configuration D: the MFCC columns set before it, the reverberated entries behind it)."""
     lr, m, wc, flag = SM.PRESETS[st["preset"]]
     oa, ol, lo = cfg.outs[st["out"]]
     g = pkg.BP_GPU(1, len(cfg.ls), cfg.ls, cfg.B, lr, m, wc, W, b, dropoutflag=flag, visible_omit=SM.VISIBLE_OMIT, hid_omit=SM.HID_OMIT,
                    activation=cfg.act, seed=SEED, max_chunk_frames=cap, compute_dtype=cfg.dtype, output_activation=oa,
                    output_linear_cols=ol, output_loss=lo, forward_mode=st["fwd"])
+    if cor.get("aux"):
+        a = dict(cor["aux"])
+        g.set_mix_aux(pkg.mel_params(a.pop("sample_rate"), **a))
     g.set_mix_corpus(cor["clean"], cor["noise"], cor["mean"], cor["inv_std"], SM.CONTEXT, SM.TARG_OFFSET, cfg.corpus_target)
+    if cor.get("rirs"):
+        g.set_mix_reverb(cor["rirs"], cor["pair_clean"], cor["pair_rir"], cor["reverb_target"], cor["early_taps"])
+    if st.get("nat"):
+        g.set_nat(SM.NAT_MODES[st["nat"]])
+    if st.get("post"):
+        apply_post(pkg, g, cfg, st["post"])
     return g
 
 
@@ -56,8 +79,11 @@ def state(g):
 
 
 def wave_target(pkg, cfg, masked):
-    """(target, out_col): the LPS columns, or on the two-part nets the mask columns."""
-    return (pkg.WAVE_MASK, SM.FEA_DIM) if masked and cfg.ls[-1] == 2 * SM.FEA_DIM else (pkg.WAVE_LPS, 0)
+    """(target, out_col): the LPS columns, or on the nets that have them the mask columns."""
+    return (pkg.WAVE_MASK, SM.mask_col(cfg)) if masked and SM.mask_col(cfg) is not None else (pkg.WAVE_LPS, 0)
+
+
+_EXTENDED = {3: False, 5: True, 7: "full"}                     # score columns -> the binding's extended=
 
 
 def execute(pkg, g, cfg, cor, step, d):
@@ -86,6 +112,20 @@ def execute(pkg, g, cfg, cor, step, d):
         g.set_output(*cfg.outs[step.after["out"]])
     elif k == "set_forward":
         g.set_forward(step.before["fwd"] ^ 1)
+    elif k == "set_nat":
+        g.set_nat(SM.NAT_MODES[step.after["nat"]])
+    elif k == "set_post":
+        apply_post(pkg, g, cfg, step.after["post"])
+    elif k == "time_kernel":                                   # (its one result is a time)
+        g.time_kernel(d["which"], d["iters"])
+    elif k == "profile_step":                                  # (likewise; what it trains shows at the checkpoints)
+        g.profile_step(0, 1)
+    elif k == "gv_mix":
+        r = g.gv_mix(plan(pkg, d["plan"]), out_col=0, stage=d["stage"])
+        return [r["est_sum"], r["est_sq"], r["ref_sum"], r["ref_sq"], np.int64(r["frames"])]
+    elif k == "eval_mix_logmmse":
+        r = g.eval_mix_logmmse(plan(pkg, d["plan"]), SM.SAMPLE_RATE, return_pcm=True, extended=_EXTENDED[d["width"]], noise=d["noise"])
+        return [r["noisy"], r["enhanced"]] + list(r["pcm"])
     elif k == "forward":
         return [g.forward(d["x"])]
     elif k == "cv":
@@ -104,8 +144,8 @@ def execute(pkg, g, cfg, cor, step, d):
                                       return_net=True)
         return list(waves) + list(nets)
     elif k == "eval_mix":
-        t, c = wave_target(pkg, cfg, True)
-        r = g.eval_mix(plan(pkg, d["plan"]), SM.SAMPLE_RATE, target=t, out_col=c, return_pcm=True)
+        t, c = wave_target(pkg, cfg, d.get("masked", True))
+        r = g.eval_mix(plan(pkg, d["plan"]), SM.SAMPLE_RATE, target=t, out_col=c, return_pcm=True, extended=_EXTENDED[d.get("width", 3)])
         return [r["noisy"], r["enhanced"]] + list(r["pcm"])
     elif k == "grads":
         g.upload_chunk(d["x"], d["t"])
@@ -138,8 +178,17 @@ def execute(pkg, g, cfg, cor, step, d):
     return []
 
 
-def load(pkg, g, kind, d):
-    """Make the chunk that a call of `kind` with data d leaves resident WITH targets, without its training or its reads."""
+def load(pkg, g, kind, d, nat=None):
+    """Make the chunk that a call of `kind` with data d leaves resident WITH targets, without its training or its reads.  nat: the
+    noise-aware mode the chunk was made in, where it is not the one g is in now (the chunk keeps the rows it was made with)."""
+    if nat is not None and SM.NAT_MODES[nat] != g.nat_mode:
+        now = g.nat_mode
+        g.set_nat(SM.NAT_MODES[nat])
+        try:
+            load(pkg, g, kind, d)
+        finally:
+            g.set_nat(now)
+        return
     if kind == "mix_features":
         g.mix_features(plan(pkg, d["plan"]))
     elif kind in ("train", "upload_train", "grads"):
@@ -156,6 +205,8 @@ def load(pkg, g, kind, d):
         tg = np.zeros((rows.shape[0], f["targ"].shape[1]), np.float32)
         tg[:f["targ"].shape[0]] = f["targ"]
         ws, tf, nr = MX.window_tables(frames, SM.CONTEXT, d["order"])
+        if g.nat_mode == "dynamic":                            # one nat row per frame: nat_row is the global frame index
+            nr = tf
         g.upload_chunk_windows(rows, tg, SM.CONTEXT, ws, tf, nat=f["nat"], nat_row=nr)
     else:
         raise AssertionError(kind)
@@ -163,6 +214,8 @@ def load(pkg, g, kind, d):
 
 def words(a):
     a = np.ascontiguousarray(a)
+    if a.dtype == np.float64:                                  # (the double sums of gv_mix: by their bits)
+        return a.view(np.uint64)
     return a.view(np.uint32) if a.dtype == np.float32 else a.astype(np.int64)
 
 
@@ -207,13 +260,15 @@ def advance(g, cfg, n_bunches, W, b, cap=SM.CAP):
     assert differing(w[1:] + bb[1:], W[1:] + b[1:], "advance") == 0
 
 
-def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None):
+def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None, kinds=None):
     """The procedure above over steps and their data.  (count, diff, bad): what ran, the differing words per comparison, and
     (comparison, what, words) of everything that differs.
     error_names: step -> the text its expected error must contain (None: any message).
     idle: step -> True for a successful training call that the model says trains NOTHING.  The replay leaves such a call out, so a
     weight, a momentum word or a position of the dropout stream that it moved shows at the next checkpoint; and on the second pass
-    W, b, dW, db are read on both sides of it and must be the same words."""
+    W, b, dW, db are read on both sides of it and must be the same words.
+    kinds: the table the steps come from (default sequence_model.KINDS)."""
+    kinds = SM.KINDS if kinds is None else kinds
     by_pos = {s.pos: d for s, d in zip(steps, data)}
     W0, b0 = pkg.glorot_net(cfg.ls, seed=5 + cfg.index, beta=0.5)
     fresh = SM.fresh_state()
@@ -247,15 +302,16 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
                 compare("state_vs_replay", outs[i], execute(pkg, R, cfg, cor, s, d), ("checkpoint", s.pos))
                 count["checkpoints"] += 1
                 continue
-            if not SM.KINDS[s.kind].training or is_idle(s):
+            if not kinds[s.kind].training or is_idle(s):
                 continue
-            if s.kind == "train_resident" and s.before["maker"] != r_maker:
+            as_kind = SM.REPLAY_AS.get(s.kind, s.kind)         # (profile_step: the plain loop in its place)
+            if as_kind == "train_resident" and s.before["maker"] != r_maker:
                 mk, mp = s.before["maker_kind"], s.before["maker"]
                 assert mk in SM.LOADABLE, mk
-                load(pkg, R, mk, by_pos[mp])
+                load(pkg, R, mk, by_pos[mp], s.before["maker_nat"])
                 r_maker = mp
                 count["replay_loads"] += 1
-            execute(pkg, R, cfg, cor, s, d)
+            execute(pkg, R, cfg, cor, s._replace(kind=as_kind), d)
             if s.after["maker"] == s.pos and s.after["maker_kind"] == s.kind:
                 r_maker = s.pos
         end_S = state(S)
@@ -267,8 +323,8 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
             if s.status != SM.BP_OK:
                 expect_error(pkg, S2, cfg, cor, s, d, names(s))
                 continue
-            k = SM.KINDS[s.kind]
-            if not k.training and s.kind not in ("checkpoint", "set_forward"):
+            k = kinds[s.kind]
+            if not k.training and s.kind not in SM.NO_FRESH:
                 if cache is None:
                     cache = S2.get_weights()
                 F = make(pkg, cfg, cache[0], cache[1], s.before, cor, cap)
@@ -277,7 +333,7 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
                         advance(F, cfg, s.before["bunches"], cache[0], cache[1], cap)
                     if s.kind == "grads_resident":
                         mk, mp = s.before["maker_kind"], s.before["maker"]
-                        load(pkg, F, mk, by_pos[mp])
+                        load(pkg, F, mk, by_pos[mp], s.before["maker_nat"])
                     compare("query_vs_fresh", execute(pkg, F, cfg, cor, s, d), outs[i], (s.pos, s.kind, "after", steps[i - 1].kind if i else None))
                 finally:
                     F.close()
