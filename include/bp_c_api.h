@@ -541,7 +541,12 @@ int bp_eval_mix_ext(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rat
  *   it, enhanced exactly as bp_logmmse_waves would enhance the mixed samples, x and the result scored against the clean s exactly
  *   as bp_eval_mix scores them; the audio stays on the device.  The argument and capacity rules of bp_eval_mix; BP_ERR_STATE
  *   without a corpus and on a data-parallel-attached handle.  The call leaves the chunk as the resident window chunk; weights and
- *   momentum state are untouched.  bp_eval_mix_logmmse_ext: the same with rows of n_scores columns, as bp_eval_mix_ext has them. */
+ *   momentum state are untouched.  It does not run the net: it neither sizes nor writes the net's output block, whatever its size
+ *   against the calls before it, and nothing reads that block for this chunk -- the chunk has no targets, so the calls that would
+ *   run the net on it (bp_train_resident, bp_grads_resident, bp_profile_step) refuse it as a chunk without targets, and every
+ *   query computes its own outputs afresh.  In BP_NAT_DYNAMIC the call still stages one noise-aware row per frame (the mixing sequence is
+ *   bp_mix_features'); its scores do not read them.  bp_eval_mix_logmmse_ext: the same with rows of n_scores columns, as
+ *   bp_eval_mix_ext has them. */
 typedef struct bp_logmmse_params {
     double alpha;        /* decision-directed weight of the a-priori SNR */
     double mu;           /* smoothing of the noise update in frames the VAD calls noise */

@@ -19,10 +19,12 @@ import pytest
 
 import sequence_model as SM
 import size_model as ZM
+import xsize_model as XM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dnn-for-speech-enhancement_amd", "csrc")
 NUMBERS = os.path.join(ROOT, "profiles", "size_parity_numbers.json")
+X_NUMBERS = os.path.join(ROOT, "profiles", "xsize_parity_numbers.json")
 IDS = [c.id for c in SM.CONFIGS]
 
 
@@ -278,6 +280,15 @@ def test_buffers_names_every_buf_and_every_growing_call_site_of_the_sources():
     step = open(os.path.join(CSRC, "bp_step.hip")).read()
     assert "{{rw[0], rows_b, false}, {rw[1], targ_b, false}, {rw[2], nat_b, false}, {rw[3], tab_b, false}}" in step
     assert [n for n in ZM.BUFFERS if n.startswith("wset.r[")] == ["wset.r[%d]" % i for i in range(4)]
+    # the extended table (tests/xsize_model.py) over the same sources: ev_gain has a row, every nat_b expression is restated by the
+    # wset.r[2] row (static and dynamic, with and without a kept spectrum, a stream's), every window_reserve site is counted; a new
+    # expression or a new site fails by name (tests/test_xsize_coverage.py applies the mutants)
+    found = XM.scan({os.path.basename(p): open(p).read() for p in _sources()})
+    assert found["members"] == members and found["grown_args"] == grown_args and found["sites"] == dict(sites)
+    assert XM.scan_problems(found) == []
+    assert sorted(found["nat_b"]) == ["bp_mix.hip", "bp_step.hip", "bp_stream.hip", "bp_wave.hip"] == sorted(XM.NAT_EXPR)
+    assert found["reserve"] == {"bp_mix.hip": 1, "bp_stream.hip": 1, "bp_wave.hip": 1} == XM.WINDOW_RESERVE_SITES
+    assert "ev_gain" in XM.BUFFERS and "ev_gain" not in XM.UNMODELLED and set(XM.UNMODELLED) < set(ZM.UNMODELLED)
 
 
 # ------------------------------------------------------------------ 4. the dye
@@ -339,3 +350,19 @@ def test_committed_numbers_hold_zero_differing_words_for_every_walk_under_ten_se
             assert e["queries_compared"] == sum(1 for s in steps if s.status == SM.BP_OK and not SM.KINDS[s.kind].training
                                                 and s.kind not in ("checkpoint", "set_forward"))
             assert e["seconds"] < 10.0, (ZM.test_id(cfg, wid), e["seconds"])
+    # profiles/xsize_parity_numbers.json: `python tests/xsize_model.py numbers <parity JSON> <out>` behind a -m gpu run of the
+    # walks of the extended table
+    num = json.load(open(X_NUMBERS))["tests"]
+    assert sorted(num) == sorted(XM.GPU_TESTS)
+    for cfg in SM.XCONFIGS:
+        for wid in XM.walk_ids(cfg):
+            e = num.get(XM.test_id(cfg, wid))
+            assert e is not None, "no measured figure for %s" % XM.test_id(cfg, wid)
+            steps = XM.run_model(cfg, XM.walk_calls(cfg, wid)[1])
+            assert e["words_differing"] == 0 and e["state_vs_replay"] == 0 and e["query_vs_fresh"] == 0 and e["second_pass"] == 0
+            assert e["idle_training"] == 0 and e["idle_trainings"] == sum(1 for s in steps if XM.idle(cfg, s))
+            assert e["calls"] == len(steps) and e["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK)
+            assert e["checkpoints"] == sum(1 for s in steps if s.kind == "checkpoint" and s.status == SM.BP_OK)
+            assert e["queries_compared"] == sum(1 for s in steps if s.status == SM.BP_OK and not SM.XKINDS[s.kind].training
+                                                and s.kind not in SM.NO_FRESH)
+            assert e["seconds"] < 10.0, (XM.test_id(cfg, wid), e["seconds"])
