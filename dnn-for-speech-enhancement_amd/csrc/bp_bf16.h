@@ -418,7 +418,9 @@ __global__ __launch_bounds__(BM == 32 ? 128 : 256, DMA ? 1 : 2) void bp_gemm_bf1
                 const size_t i = (size_t)m * e.ldw + n;
                 if constexpr (EPI == BEPI_WGRAD_UPDATE) {
                     const float w = in0[blk][4 * q + j];
-                    const float d = update_delta(e.mom, e.c1, e.wc, e.ndiv, in1[blk][4 * q + j], acc[4 * q + j], w);
+                    // (the division for every bunch size: this is the per-layer form for the bunch sizes bp_wgrad_dma_bf16.h is not
+                    // built for, and a second body of the tile's stores for the multiply moved the code of every kernel of this template)
+                    const float d = update_delta<false>(e.mom, e.c1, e.wc, e.ndiv, 0.0f, in1[blk][4 * q + j], acc[4 * q + j], w);
                     e.D[i] = d;
                     v[j] = d + 1.0f * w;                                                                    // kernAccSum
                     e.W[i] = v[j];
@@ -491,7 +493,7 @@ __global__ void bp_to_bf16_both(const float *src, int lds, int rows, int cols, b
 // bias gradient = column sums of dEdX_l (kernAccSumrow) from the bf16 copy, fp32 accumulation; fused update of the
 // bias (kernUpdatedelta with wc = 0 + kernAccSum) or store into the gradient buffer.
 __global__ void bp_bias_bf16(const bf16_t *dx, int ld, int rows, int n_true, float *bias, float *dbias, float *gout,
-                             float mom, float c1, float ndiv)
+                             float mom, float c1, float ndiv, float rdiv)
 {
     // block = 64 columns x 16 row groups (the kernel is pure load latency: many rows in flight); fixed summation
     // order (row groups folded 0..15) => deterministic
@@ -516,7 +518,9 @@ __global__ void bp_bias_bf16(const bf16_t *dx, int ld, int rows, int n_true, flo
 #pragma unroll
     for (int y = 0; y < 16; ++y) s += part[y][threadIdx.x];
     if (gout) { gout[n] = s; return; }
-    const float d = update_delta(mom, c1, 0.0f, ndiv, dbias[n], s, bias[n]);
+    float d;                                          // (one value per thread: its whole update is the choice)
+    if (rdiv != 0.0f) d = update_delta<true>(mom, c1, 0.0f, ndiv, rdiv, dbias[n], s, bias[n]);
+    else d = update_delta<false>(mom, c1, 0.0f, ndiv, rdiv, dbias[n], s, bias[n]);
     dbias[n] = d;
     bias[n] = d + 1.0f * bias[n];
 }

@@ -72,9 +72,23 @@ __device__ __forceinline__ float act_bwd(int act, float y)
 // kernUpdatedelta: the new momentum state of one parameter from its old state d, its summed gradient g and its weight w;
 // c1 = (1-m)*lr or lr (host: update_coef in bp_handle.h), ndiv = (float)n, wc = 0 for biases.  Every caller then stores
 // d' and applies kernAccSum itself, w' = d' + 1.0f*w, reading w again where the delta store may alias it.
-__device__ __forceinline__ float update_delta(float mom, float c1, float wc, float ndiv, float d, float g, float w)
+//
+// RCP: the quotient as ONE multiply by rdiv = exact_rdiv(ndiv) (bp_handle.h), for the divisors where that is the division to the
+// bit; the IEEE division is 11 dependent VALU instructions per value (v_div_scale x 2, v_rcp, 6 fma, v_div_fmas, v_div_fixup), and
+// a wave that keeps the matrix pipe busy has no VALU slot to spare.  The caller chooses ONCE per tile (per thread in
+// the element-wise kernels) on the uniform rdiv != 0, around its whole update: chosen per value hipcc keeps every division and
+// adds a branch each.  The product is a rounding step of its own -- the empty asm keeps it out of a contraction: left alone hipcc
+// forms fma(g, rdiv, fl(wc * w)), which rounds wc * w first and is other bits than the division side's fma(wc, w, fl(g / ndiv)).
+template <bool RCP = false>
+__device__ __forceinline__ float update_delta(float mom, float c1, float wc, float ndiv, float rdiv, float d, float g, float w)
 {
-    return mom * d - c1 * (g / ndiv + wc * w);
+    if constexpr (RCP) {
+        float q = g * rdiv;
+        asm("" : "+v"(q));
+        return mom * d - c1 * (q + wc * w);
+    } else {
+        return mom * d - c1 * (g / ndiv + wc * w);
+    }
 }
 
 // ------------------------------------------------------------------ split-K ticket

@@ -220,11 +220,15 @@ __global__ __launch_bounds__(256) void bp_dp_reduce_update(const DpReduceArgs a)
             for (int p = 1; p < BP_DP_MAXRANKS; ++p)
                 if (p < world) s += g[u][p];
             const float wc = a.lo + 4 * q < a.w_end ? a.wc : 0.0f;      // (segments are multiples of 64 floats: a float4 never straddles)
+            // The division stays in this kernel for every bunch size: it moves 16 bytes per lane and value over the fabric and waits
+            // for them, so the quotient's 11 instructions hide; and neither form of the choice keeps what the kernel has -- with
+            // the pass loop as two bodies the bf16 form wants 477 registers for 258, with the choice around one float4 hipcc
+            // contracts the DIVISION side's mom*d - c1*s differently for two of the four lanes (other bits than before).
             float4 dn; bp_f32x4 wn;
-            dn.x = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].x, s.x, w[u].x); wn.x = dn.x + 1.0f * w[u].x;   // kernAccSum
-            dn.y = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].y, s.y, w[u].y); wn.y = dn.y + 1.0f * w[u].y;
-            dn.z = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].z, s.z, w[u].z); wn.z = dn.z + 1.0f * w[u].z;
-            dn.w = update_delta(a.mom, a.c1, wc, a.ndiv, d[u].w, s.w, w[u].w); wn.w = dn.w + 1.0f * w[u].w;
+            dn.x = update_delta<false>(a.mom, a.c1, wc, a.ndiv, 0.0f, d[u].x, s.x, w[u].x); wn.x = dn.x + 1.0f * w[u].x;   // kernAccSum
+            dn.y = update_delta<false>(a.mom, a.c1, wc, a.ndiv, 0.0f, d[u].y, s.y, w[u].y); wn.y = dn.y + 1.0f * w[u].y;
+            dn.z = update_delta<false>(a.mom, a.c1, wc, a.ndiv, 0.0f, d[u].z, s.z, w[u].z); wn.z = dn.z + 1.0f * w[u].z;
+            dn.w = update_delta<false>(a.mom, a.c1, wc, a.ndiv, 0.0f, d[u].w, s.w, w[u].w); wn.w = dn.w + 1.0f * w[u].w;
             *reinterpret_cast<float4 *>(d_own + 4 * q) = dn;      // (nontemporal accesses for the momentum stream: 0.2657 vs 0.2537 ms, profiles/r05_dp_world1.txt)
 #pragma unroll
             for (int p = 0; p < BP_DP_MAXRANKS; ++p)

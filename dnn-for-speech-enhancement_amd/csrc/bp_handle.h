@@ -35,6 +35,7 @@
 //   in    [cap][ld_0], targ [cap][ld_{L-1}]   resident stacked chunk (res.in() / res.targ(), bp_chunk.h)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string>
@@ -143,12 +144,24 @@ struct bp_handle {
 };
 
 // Coefficients of the momentum update (update_delta, bp_device.h; DevFunc.cu:313-318 for momentum_rule 0, :306-311 for 1):
-// c1 = (1-m)*lr or lr, ndiv = the global bunch.
-struct UpdateCoef { float mom, c1, wc, ndiv; };
+// c1 = (1-m)*lr or lr, ndiv = the global bunch, rdiv = exact_rdiv(ndiv).
+//
+// exact_rdiv: 1/ndiv where multiplying by it IS the division -- ndiv a power of two and 1/ndiv a normal float: g * rdiv is then
+// the correctly rounded g / ndiv for every float g, subnormal quotients included (both are g with its exponent moved, rounded
+// once) -- and 0 for every other divisor (3, 96, 100: about 30 % of the words differ), for 0, negative and non-finite ones.  The
+// kernels take rdiv != 0 as "multiply" (update_delta<true>, bp_device.h) and keep the IEEE division otherwise.
+static inline float exact_rdiv(float ndiv)
+{
+    int ex;
+    if (!(ndiv > 0.0f) || frexpf(ndiv, &ex) != 0.5f) return 0.0f;      // (frexpf of inf / NaN is not 0.5)
+    const float r = 1.0f / ndiv;
+    return r >= 1.17549435e-38f && r <= 3.40282347e+38f ? r : 0.0f;    // (2^127: the reciprocal is subnormal; below 2^-127: infinite)
+}
+struct UpdateCoef { float mom, c1, wc, ndiv, rdiv; };
 static inline UpdateCoef update_coef(const bp_handle *h)
 {
     const float m = h->cfg.momentum, lr = h->cfg.lrate;
-    return {m, h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr, h->cfg.weightcost, (float)h->Bg};
+    return {m, h->cfg.momentum_rule == 1 ? lr : (1 - m) * lr, h->cfg.weightcost, (float)h->Bg, exact_rdiv((float)h->Bg)};
 }
 
 // Every device buffer gets SLACK floats of zeroed tail so that whole-tile reads of the GEMM loaders (no predicates,

@@ -61,7 +61,10 @@ struct EpiArgs {
     int lin_cols;                    // fwd_out_logi: columns [0, lin_cols) stay linear (in what was alignment padding: the layout of
                                      // the struct, and so the code of every kernel that takes it, is the same as without the field)
     float *aux2; int ldaux2;         // fwd_out: out (may be null) | wgrad_update: delta_W
-    float scale;                     // fwd_out: 2/n_frames (DevFunc.cu:263)
+    union {                          // (one word, two readers: the struct has no padding left)
+        float scale;                 // fwd_out: 2/n_frames (DevFunc.cu:263)
+        float rdiv;                  // wgrad update: exact_rdiv(ndiv) (bp_handle.h), 0 = keep the division; in front of mom, c1, wc, ndiv
+    };
     // wgrad update (DevFunc.cu:313-318 + 270-277)
     float mom, c1, wc, ndiv;         // c1 = (1-m)*lr or lr ; ndiv = (float)n
     float *bias_w, *bias_d, *bias_g; // bias / delta_bias (update) or bias-gradient (store)
@@ -74,6 +77,10 @@ struct EpiArgs {
     unsigned *done;                  // wgrad store (data parallel): +1 per finished tile, for the exchange stream (bp_dp.h); may be null
 };
 static_assert(sizeof(EpiArgs) == 160 && offsetof(EpiArgs, aux2) == 56 && offsetof(EpiArgs, done) == 152, "lin_cols / loss must sit in padding");
+// rdiv shares the word of scale: no kernel reads both (scale: the output forwards; rdiv: the fused update), every other field keeps
+// its offset, and with it the forward, dgrad and output kernels keep their code behind the batched scalar head (BP_PIN_OPERANDS)
+static_assert(offsetof(EpiArgs, rdiv) == 68 && offsetof(EpiArgs, scale) == 68 && offsetof(EpiArgs, mom) == 72 && offsetof(EpiArgs, ndiv) == 84,
+              "rdiv lies in scale's word, in front of mom, c1, wc, ndiv");
 // The operand fields of g (and whatever scalars the caller adds as further "+s"(x) operands) are wanted in scalar registers at this
 // one point: their loads from the argument block then go out as ONE batch with one wait.  Left to itself hipcc reads each field
 // where its first use happens to be scheduled -- A and B behind the tile map, a grouped launch's fields behind the branch that
@@ -185,10 +192,13 @@ __device__ __forceinline__ void block_store(const EpiArgs &e, int mb, int nb, in
     }
 }
 
-template <int EPI, int R0, int RN>
+// RCP (EPI_WGRAD_UPDATE): the update's quotient as a multiply (update_delta<true>, bp_device.h); chosen by the caller, once for
+// the tile, on e.rdiv != 0
+template <int EPI, int R0, int RN, bool RCP = false>
 __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb, const f32x16 &acc, int lane,
                                                const EpiPre &p)
 {
+    static_assert(!RCP || EPI == EPI_WGRAD_UPDATE, "only the fused update divides");
     static_assert(RN % 4 == 0 && R0 % 4 == 0, "register range must cover whole 4-row groups");
     if constexpr (EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE) {
         const int n = nb + (lane & 31);
@@ -202,7 +212,7 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
             if constexpr (EPI == EPI_WGRAD_UPDATE) {
                 float *cd = uniform_ptr(e.aux2 + (size_t)mb * e.ldc + nb);
                 const float w = p.p0[r];
-                const float d = update_delta(e.mom, e.c1, e.wc, e.ndiv, p.p1[r], acc[r], w);
+                const float d = update_delta<RCP>(e.mom, e.c1, e.wc, e.ndiv, e.rdiv, p.p1[r], acc[r], w);
                 *reinterpret_cast<float *>(reinterpret_cast<char *>(sgpr_row_base(cd + ro)) + lob) = d;
                 *reinterpret_cast<float *>(reinterpret_cast<char *>(sgpr_row_base(cw + ro)) + lob) = d + 1.0f * w;   // kernAccSum
             } else {
@@ -275,6 +285,15 @@ __device__ __forceinline__ void epilogue_block(const EpiArgs &e, int mb, int nb,
     } else {
         static_assert(EPI == EPI_WGRAD_UPDATE || EPI == EPI_WGRAD_STORE, "epilogue without a branch");   // (wgrad returned above)
     }
+}
+
+// One lane of the fused update's bias tile: bias n from its summed gradient s (kernUpdatedelta with wc = 0 + kernAccSum).
+template <bool RCP>
+__device__ __forceinline__ void bias_update(const EpiArgs &e, int n, float s)
+{
+    const float d = update_delta<RCP>(e.mom, e.c1, 0.0f, e.ndiv, e.rdiv, e.bias_d[n], s, e.bias_w[n]);
+    e.bias_d[n] = d;
+    e.bias_w[n] = d + 1.0f * e.bias_w[n];
 }
 
 // EPI_OUT_SPLIT, registers [R0, R0+4) of the wave's 32x32 block.  store: this k-slice's partial sums into its slab, agent-scope
@@ -782,9 +801,7 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
                 for (int r = 0; r < RG; ++r) s += red[r * BN + tid];
                 const int n = n0 + tid;
                 if constexpr (EPI == EPI_WGRAD_UPDATE) {
-                    const float d = update_delta(e.mom, e.c1, 0.0f, e.ndiv, e.bias_d[n], s, e.bias_w[n]);
-                    e.bias_d[n] = d;
-                    e.bias_w[n] = d + 1.0f * e.bias_w[n];
+                    if (e.rdiv != 0.0f) bias_update<true>(e, n, s); else bias_update<false>(e, n, s);
                 } else {
                     e.bias_g[n] = s;
                 }
@@ -814,7 +831,23 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         }
     }
 
-    if constexpr (KS == 1) {
+    if constexpr (EPI == EPI_WGRAD_UPDATE) {
+        // the fused update: multiply or divide (update_delta, bp_device.h), chosen here for the whole tile
+        static_assert(KS == 1, "the update runs on whole blocks");
+        if (e.rdiv != 0.0f) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    epilogue_block<EPI_E, 0, 16, true>(e, mb0 + i * 32, nb0 + j * 32, acc[i][j], lane, pre[i][j]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    epilogue_block<EPI_E, 0, 16, false>(e, mb0 + i * 32, nb0 + j * 32, acc[i][j], lane, pre[i][j]);
+        }
+    } else if constexpr (KS == 1) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -860,6 +893,8 @@ struct MultiArgs {
     int n;
 };
 #ifndef BP_TRACE            // (the development build's GemmArgs carries one more pointer)
+// (920 bytes with EpiArgs::rdiv too: it lies in the word of EpiArgs::scale, so no problem's fields moved and the batched scalar head
+// of bp_gemm_multi reads what it read)
 static_assert(sizeof(MultiArgs) == 920 && offsetof(MultiArgs, first_tile) == 896 && offsetof(MultiArgs, n) == 916, "MultiArgs layout");
 #endif
 template <class K>

@@ -51,7 +51,7 @@ struct RbmStatsArgs {
     float *W, *dW, *GW;
     int ldx, ldp, K;
     int V, H, apply;
-    float mom, lrate, wc, ndiv;
+    float mom, lrate, wc, ndiv, rdiv;      // rdiv = exact_rdiv(ndiv) (bp_handle.h), 0 = divide
 };
 // Column sums gc = sum_r (p1 - p0), ga = sum_r (v1 - v0) over the B rows, stored or applied (wc = 0), and the bunch's recon:
 // the tiles' partial sums added in tile order, onto *recon.
@@ -61,7 +61,7 @@ struct RbmBiasArgs {
     const double *part;
     double *recon;
     int ldx, ldp, B, Bp, V, H, apply, n_part;
-    float mom, lrate, ndiv;
+    float mom, lrate, ndiv, rdiv;
 };
 
 hipError_t rbm_rows_launch(float *dst, int ld, int rows_p, const float *src, int count, int width, hipStream_t st);

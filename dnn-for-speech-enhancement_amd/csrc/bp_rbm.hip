@@ -24,6 +24,7 @@
 #include <string>
 
 #include "bp_device.h"
+#include "bp_handle.h"   // (exact_rdiv alone: no handle, no state)
 #include "bp_mem.h"
 
 namespace {
@@ -180,6 +181,9 @@ __global__ __launch_bounds__(256) void bp_rbm_gemm_stats(const RbmStatsArgs a)
     RBM_LANE_TILE;
     rbm_gemm<false, false>(a.Xs + m0, a.ldx, a.Ps + n0, a.ldp, a.K, lds, acc);
     const bool col_ok = col < a.H;
+    // (the tile's 16 values as a body per form of the update's quotient -- update_delta<RCP>, bp_device.h --, chosen once below)
+    auto tile_out = [&](auto rcp_tag) __attribute__((always_inline)) {
+    constexpr bool RCP = decltype(rcp_tag)::value;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -192,11 +196,13 @@ __global__ __launch_bounds__(256) void bp_rbm_gemm_stats(const RbmStatsArgs a)
                 a.GW[o] = live ? gr : 0.0f;
             } else if (live) {
                 const float wo = a.W[o];
-                const float dn = update_delta(a.mom, a.lrate, a.wc, a.ndiv, a.dW[o], gr, wo);
+                const float dn = update_delta<RCP>(a.mom, a.lrate, a.wc, a.ndiv, a.rdiv, a.dW[o], gr, wo);
                 a.dW[o] = dn;
                 a.W[o] = wo + dn;
             }
         }
+    };
+    if (a.rdiv != 0.0f) tile_out(std::true_type{}); else tile_out(std::false_type{});
 }
 
 // 64 columns per workgroup; thread (x = column, y) runs chain y of the column: the rows r with r % 4 == y, ascending.
@@ -225,7 +231,9 @@ __global__ __launch_bounds__(256) void bp_rbm_colsum(const RbmBiasArgs a)
             (hid ? a.gc : a.ga)[k] = g;
         } else {
             const float bo = b[k];
-            const float dn = update_delta(a.mom, a.lrate, 0.0f, a.ndiv, d[k], g, bo);
+            float dn;                                 // (one value per thread: its whole update is the choice)
+            if (a.rdiv != 0.0f) dn = update_delta<true>(a.mom, a.lrate, 0.0f, a.ndiv, a.rdiv, d[k], g, bo);
+            else dn = update_delta<false>(a.mom, a.lrate, 0.0f, a.ndiv, a.rdiv, d[k], g, bo);
             d[k] = dn;
             b[k] = bo + dn;
         }
@@ -358,14 +366,14 @@ hipError_t cd1_bunch(bp_rbm *s, int l, const float *rows, bool store, bool apply
         b.Xs = s->Xs; b.Ps = s->Ps; b.c = s->c[l]; b.dc = s->dc[l]; b.a = s->a[l]; b.da = s->da[l]; b.gc = s->gc; b.ga = s->ga;
         b.part = s->part; b.recon = recon_due ? s->recon : nullptr;
         b.ldx = Vp; b.ldp = Hp; b.B = B; b.Bp = Bp; b.V = V; b.H = H; b.apply = pass; b.n_part = (Bp / RBM_TILE) * (Vp / RBM_TILE);
-        b.mom = hy.momentum; b.lrate = hy.lrate; b.ndiv = (float)B;
+        b.mom = hy.momentum; b.lrate = hy.lrate; b.ndiv = (float)B; b.rdiv = exact_rdiv((float)B);
         e = rbm_bias_launch(b, s->st);
         recon_due = false;
         if (e != hipSuccess) break;
         RbmStatsArgs g = {};
         g.Xs = s->Xs; g.Ps = s->Ps; g.W = s->W[l]; g.dW = s->dW[l]; g.GW = s->GW;
         g.ldx = Vp; g.ldp = Hp; g.K = 2 * Bp; g.V = V; g.H = H; g.apply = pass;
-        g.mom = hy.momentum; g.lrate = hy.lrate; g.wc = hy.weightcost; g.ndiv = (float)B;
+        g.mom = hy.momentum; g.lrate = hy.lrate; g.wc = hy.weightcost; g.ndiv = (float)B; g.rdiv = exact_rdiv((float)B);
         e = rbm_stats_launch(g, Vp, Hp, s->st);
     }
     if (e == hipSuccess && apply) ++s->applied[l];

@@ -417,7 +417,7 @@ static EpiArgs wgrad_epi(const bp_handle *h, int l, bool fused)
     if (fused) {
         const UpdateCoef u = update_coef(h);
         e.C = h->W[l]; e.aux2 = h->dW[l]; e.ldaux2 = cur;
-        e.mom = u.mom; e.c1 = u.c1; e.wc = u.wc; e.ndiv = u.ndiv;
+        e.mom = u.mom; e.c1 = u.c1; e.wc = u.wc; e.ndiv = u.ndiv; e.rdiv = u.rdiv;
         e.bias_w = h->b[l]; e.bias_d = h->db[l];
     } else {
         e.C = h->grad + h->g_off[l];
@@ -656,7 +656,7 @@ static hipError_t bf_wgrad(bp_handle *h, int l, bool fused)
     if (er != hipSuccess) return er;
     hipLaunchKernelGGL(bp_bias_bf16, dim3((h->s[l] + 63) / 64), dim3(64, 16), 0, h->stream, h->dxb[l], cur, h->B, h->s[l],
                        h->b[l], h->db[l], fused ? (float *)nullptr : h->grad + h->g_off[l] + (size_t)prev * cur, u.mom, u.c1,
-                       u.ndiv);
+                       u.ndiv, u.rdiv);
     return hipGetLastError();
 }
 // The LDS-DMA wgrad of bp_wgrad_dma_bf16.h: static bunch sizes, layers ls[0..n) in one grouped launch (bias gradient

@@ -7,7 +7,7 @@
 // Both operands of this GEMM are k-major in memory ([frame][unit]: the reduction runs over the frames of the bunch),
 // which is exactly the LDS image the MFMA fragment fetch wants ([k][m] / [k][n], conflict-free ds_read_b32).  So the
 // tiles go global -> LDS by `global_load_lds_dwordx4` (1 KiB per wave instruction = 4 k-rows of a 64-wide tile): no
-// register staging, no ds_write, 90 VGPRs => 4 workgroups per CU instead of 3.  64x64 tiles, 16-row k-tiles in a
+// register staging, no ds_write, 100 VGPRs (90 while the update had one body) => 4 workgroups per CU instead of 3.  64x64 tiles, 16-row k-tiles in a
 // 4-stage LDS ring (32 KB), ONE raw s_barrier per k-tile with an exact, counted s_waitcnt vmcnt (a __syncthreads()
 // would fence with vmcnt(0) and drain the DMA queue); the k-loop is fully unrolled for the bunch size, so every count is
 // an immediate.  Results are bit-identical to the register-staged GemmKernel<64,64,32,...> it replaced (same k-order,
@@ -35,6 +35,12 @@
 // right behind the tile's LAST operand k-tile and has three k-tiles of MFMA work to land; the epilogue waits for it with
 // vmcnt(D * NDMA), which leaves the next tile's head in flight.  Those loads are written out (wd_fetch): with LDS-DMA in
 // flight the compiler turns every wait it places for a load of its own into vmcnt(0).
+// THE UPDATE HAS TWO BODIES, chosen per tile on the uniform e.rdiv != 0 (update_delta<RCP>, bp_device.h): the quotient g / ndiv as one
+// v_mul_f32 by the exact reciprocal of a power-of-two bunch -- per value v_mul, v_fmac, v_pk_mul, v_sub, v_add and two stores, no
+// v_div_* / v_rcp between the tile's last MFMA and its stores -- or the IEEE division (11 dependent VALU instructions per value, 187
+// of a tile's ~300; every bunch this launch is built for is a power of two, so that body is cold).  Both bodies store the same 32
+// words per lane: the counts above hold for either.  (The bias lanes are the same choice; their bias_w / bias_d loads are the
+// compiler's own and drain with vmcnt(0) as they did -- m-tile 0 only.)
 // The bias reduction's scratch is ring stage ST - 1: it held the tile's last k-tile and is next written behind the barrier
 // of the next tile's iter<0>.  Measured on C2 (grouped launch of all four layers, rocprofv3 average in the step): 74.5 us
 // against 77.5 us for one tile per workgroup (profiles/r08_wgrad_cross_tile_prefetch.txt).
@@ -233,15 +239,17 @@ struct WgradDma {
                     if constexpr (STORE) {
                         __hip_atomic_store(e.bias_g + n, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);     // (write-through, like the tile below)
                     } else {
-                        const float d = update_delta(e.mom, e.c1, 0.0f, e.ndiv, e.bias_d[n], s, e.bias_w[n]);
-                        e.bias_d[n] = d;
-                        e.bias_w[n] = d + 1.0f * e.bias_w[n];
+                        if (e.rdiv != 0.0f) bias_update<true>(e, n, s); else bias_update<false>(e, n, s);
                     }
                 }
             }
             EpiPre pre;
             if constexpr (!STORE) wd_landed(wd, pre);
-            epilogue_block<EPI, 0, 16>(e, mb, nb, acc[0], lane, pre);
+            // the fused update as two bodies, chosen once per tile: the quotient g / ndiv as one multiply where that is the division
+            // to the bit (e.rdiv != 0: a power-of-two bunch), the IEEE division otherwise (update_delta, bp_device.h)
+            if constexpr (STORE) epilogue_block<EPI, 0, 16>(e, mb, nb, acc[0], lane, pre);
+            else if (e.rdiv != 0.0f) epilogue_block<EPI, 0, 16, true>(e, mb, nb, acc[0], lane, pre);
+            else epilogue_block<EPI, 0, 16, false>(e, mb, nb, acc[0], lane, pre);
             if (mb >= e.m_limit || nb >= e.n_limit) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no stores: NST does not hold
             if constexpr (STORE) {
                 // data-parallel step: tell the exchange stream that this tile of the layer's gradient segment is complete, WITHOUT a

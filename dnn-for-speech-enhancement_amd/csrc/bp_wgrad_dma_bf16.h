@@ -199,7 +199,10 @@ struct WgradDmaBf6 {
                 float dn[4], wn_[4]; bf16_t hb[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    // kernUpdatedelta written out: through update_delta (bp_device.h) the bf16 packing below compiles to other instructions
+                    // kernUpdatedelta written out: through update_delta (bp_device.h) the bf16 packing below compiles to other instructions.
+                    // It keeps the division also where e.rdiv says a multiply would do: these two waves only move the W / delta tile
+                    // (the launch is HBM-bound and they run beside the four MFMA waves, not in their issue slots), and a second body
+                    // of this loop has not been held to the packing's listing.  The bias lanes below do take the choice.
                     dn[j] = e.mom * dv[j] - e.c1 * (gv[j] / e.ndiv + e.wc * wv[j]);
                     wn_[j] = dn[j] + 1.0f * wv[j];                                        // kernAccSum
                     hb[j] = f2bf(wn_[j]);
@@ -236,9 +239,7 @@ struct WgradDmaBf6 {
             bsum += __shfl_xor(bsum, 2);
             const int n = n0 + (tid >> 2);
             if ((tid & 3) == 0 && n < e.n_limit) {
-                const float d = update_delta(e.mom, e.c1, 0.0f, e.ndiv, e.bias_d[n], bsum, e.bias_w[n]);
-                e.bias_d[n] = d;
-                e.bias_w[n] = d + 1.0f * e.bias_w[n];
+                if (e.rdiv != 0.0f) bias_update<true>(e, n, bsum); else bias_update<false>(e, n, bsum);
             }
         }
     }
