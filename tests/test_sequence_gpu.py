@@ -1,5 +1,6 @@
-"""One handle held to fresh replays over the walks of tests/sequence_model.py (-m gpu).  Every comparison is between two runs of the
-same library and is bit for bit; there is no tolerance in this file.
+"""One handle held to fresh replays over the walks of the families WALK and EXTENDED of tests/sequence_model.py (-m gpu; the body of
+both tests is walk_harness.walk_test).  Every comparison is between two runs of the same library and is bit for bit; there is no
+tolerance in this file.
 
 Per walk three long-lived handles take part, all made from the same weights and seed:
   S   the subject: the whole walk, no read beyond the walk's own (pass 1)
@@ -10,11 +11,9 @@ Per walk three long-lived handles take part, all made from the same weights and 
       with the model's switches and the corpus, makes only that call, and every array it returns equals what S returned in pass 1;
       so does what S2 itself returns.  For the gradient query F is first brought to S's position of the dropout stream by bunches
       at lrate = momentum = weightcost = 0 (they leave the weights as they were, which is checked).  For grads_resident, the gradient
-      of whatever is resident, F is also given the chunk of the call that made it resident on S (_load).
+      of whatever is resident, F is also given the chunk of the call that made it resident on S (walk_harness.load).
 Every expected error is a host-side check: its status and a non-empty message are checked on S and S2, and the checkpoints behind it
 still equal R, which never made the call."""
-import time
-
 import pytest
 
 import sequence_model as SM
@@ -22,44 +21,25 @@ import walk_harness as H
 
 pytestmark = pytest.mark.gpu
 
-PARAMS = [(c.id, w) for c in SM.CONFIGS for w in SM.walk_ids(c)]
+PARAMS = [(c.id, w) for c in SM.WALK.configs for w in SM.walk_ids(SM.WALK, c)]
 _make, _state, _differing = H.make, H.state, H.differing
 
 
 @pytest.mark.parametrize("cid,wid", PARAMS, ids=["%s-%s" % p for p in PARAMS])
 def test_walk(pkg, parity_record, cid, wid):
-    cfg = SM.BY_ID[cid]
-    walk, calls = SM.walk_calls(cfg, wid)
-    steps = SM.run_model(cfg, calls)
-    data = [SM.call_data(cfg, walk, s.pos, s.kind) for s in steps]
-    count, diff, bad = H.run_walk(pkg, cfg, steps, data, SM.corpus(cfg))
-    assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0     # (a size of the walks of tests/size_model.py)
-    parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), **dict(count, **diff))
-    print(cid, wid, count, diff)
-    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
+    H.walk_test(pkg, parity_record, SM.WALK, cid, wid)
 
 
-XPARAMS = [(c.id, w) for c in SM.XCONFIGS for w in SM.x_walk_ids(c)]
+XPARAMS = [(c.id, w) for c in SM.EXTENDED.configs for w in SM.walk_ids(SM.EXTENDED, c)]
 
 
 @pytest.mark.parametrize("cid,wid", XPARAMS, ids=["%s-%s" % p for p in XPARAMS])
 def test_extended_walk(pkg, parity_record, cid, wid):
-    """The same procedure over sequence_model.XKINDS: the noise-aware mode and post-processing as switches, bp_gv_mix and the
+    """The same procedure over the whole of sequence_model.KINDS: the noise-aware mode and post-processing as switches, bp_gv_mix and the
     log-MMSE evaluation among the queries, every score width, bp_time_kernel and bp_profile_step between the training calls, and
     configuration D (four layers, MFCC columns, reverberated corpus entries).  bp_profile_step is replayed as the bunch of
     bp_train_resident it is said to be; bp_time_kernel and set_post are left out of the replay."""
-    t0 = time.perf_counter()
-    cfg = SM.XBY_ID[cid]
-    walk, calls = SM.x_walk_calls(cfg, wid)
-    steps = SM.x_run_model(cfg, calls)
-    data = [SM.x_call_data(cfg, walk, s.pos, s.kind) for s in steps]
-    count, diff, bad = H.run_walk(pkg, cfg, steps, data, SM.x_corpus(cfg), kinds=SM.XKINDS)
-    assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0
-    assert count["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK)
-    seconds = round(time.perf_counter() - t0, 2)
-    parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), seconds=seconds, **dict(count, **diff))
-    print(cid, wid, seconds, "s", count, diff)
-    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
+    H.walk_test(pkg, parity_record, SM.EXTENDED, cid, wid)
 
 
 def test_calls_that_need_targets_refuse_a_stacked_chunk_without_them(pkg):
@@ -67,10 +47,10 @@ def test_calls_that_need_targets_refuse_a_stacked_chunk_without_them(pkg):
     chunk's rows, and bp_grads_resident, bp_train_resident_masked, bp_profile_step and bp_train_resident return BP_ERR_STATE (the
     walks run only the first and the last).  Behind each refusal the handle trains like one that never made the calls."""
     cfg = SM.BY_ID["A"]
-    cor, B = SM.corpus(cfg), cfg.B
+    cor, B = SM.corpus(SM.WALK, cfg), cfg.B
     W0, b0 = pkg.glorot_net(cfg.ls, seed=5, beta=0.5)
     a, ref = (_make(pkg, cfg, W0, b0, SM.fresh_state(), cor) for _ in range(2))
-    d0, d1, d2 = (SM.call_data(cfg, 9, p, "train") for p in range(3))
+    d0, d1, d2 = (SM.call_data(SM.WALK, cfg, 9, p, "train") for p in range(3))
     masks = [None] * (len(cfg.ls) - 1)
     try:
         for g in (a, ref):

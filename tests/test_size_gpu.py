@@ -1,6 +1,7 @@
-"""One handle held to fresh replays across calls of CHANGING size: the walks of tests/size_model.py (-m gpu).  The procedure is that of
-tests/test_sequence_gpu.py (tests/walk_harness.py: the subject S, the replay R of the training calls, a fresh handle per query), every
-comparison is between two runs of the same library and bit for bit (uint32 words), so there is no tolerance in this file.
+"""One handle held to fresh replays across calls of CHANGING size: the walks of the family SIZE of tests/size_model.py (-m gpu).  The
+procedure is that of tests/test_sequence_gpu.py (tests/walk_harness.py, walk_test: the subject S, the replay R of the training calls, a
+fresh handle per query), every comparison is between two runs of the same library and bit for bit (uint32 words), so there is no
+tolerance in this file.
 
 What only exists with sizes:
   * a handle of capacity 1024 is regrown and shrunk along the walk (size_model.BUFFERS says which buffers and when), while every
@@ -12,8 +13,6 @@ What only exists with sizes:
   * a call of CAP + 1 rows returns BP_ERR_ARG with a message that names the capacity, and the call behind it matches a fresh handle.
 Per configuration: the closed walk of every family in pieces (every ordered pair of the family's (kind, size) nodes once), OVER once
 behind every other size of its kind, and four seeded random walks over all nodes."""
-import time
-
 import pytest
 
 import sequence_model as SM
@@ -22,21 +21,9 @@ import walk_harness as H
 
 pytestmark = pytest.mark.gpu
 
-PARAMS = [(c.id, w) for c in SM.CONFIGS for w in ZM.walk_ids(c)]
+PARAMS = [(c.id, w) for c in ZM.SIZE.configs for w in SM.walk_ids(ZM.SIZE, c)]
 
 
 @pytest.mark.parametrize("cid,wid", PARAMS, ids=["%s-%s" % p for p in PARAMS])
 def test_size_walk(pkg, parity_record, cid, wid):
-    t0 = time.perf_counter()
-    cfg = SM.BY_ID[cid]
-    walk, calls = ZM.walk_calls(cfg, wid)
-    steps = ZM.run_model(cfg, calls)
-    data = [ZM.call_data(cfg, walk, s.pos, s.kind, s.size) for s in steps]
-    count, diff, bad = H.run_walk(pkg, cfg, steps, data, ZM.corpus(cfg), cap=ZM.CAP,
-                                  error_names=lambda s: "capacity" if s.size == "OVER" else None, idle=lambda s: ZM.idle(cfg, s))
-    assert count["idle_trainings"] == sum(1 for s in steps if ZM.idle(cfg, s))
-    assert count["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK) >= sum(1 for s in steps if s.size == "OVER")
-    seconds = round(time.perf_counter() - t0, 2)
-    parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), seconds=seconds, **dict(count, **diff))
-    print(cid, wid, seconds, "s", count, diff)
-    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
+    H.walk_test(pkg, parity_record, ZM.SIZE, cid, wid)

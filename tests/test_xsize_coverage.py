@@ -1,4 +1,4 @@
-"""What the walks of tests/xsize_model.py reach -- checked without a GPU, from the model and the allocation policy of csrc/bp_mem.h alone.
+"""What the walks of the family XSIZE of tests/size_model.py reach -- checked without a GPU, from the model and the allocation policy of csrc/bp_mem.h alone.
 
 Here: every ordered pair of the nodes of the two new families is run by a named GPU test, which exists and is not skipped; the
 statuses the model predicts (CAP + 1 rows in either mode, a mask target under post-processing, the measurement calls on a bf16
@@ -17,12 +17,15 @@ import pytest
 
 import sequence_model as SM
 import size_model as ZM
-import xsize_model as XM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dnn-for-speech-enhancement_amd", "csrc")
-IDS = [c.id for c in SM.XCONFIGS]
-STATIC, DYNAMIC = XM.STATIC, XM.DYNAMIC
+IDS = [c.id for c in SM.CONFIGS]
+STATIC, DYNAMIC = ZM.STATIC, ZM.DYNAMIC
+LB = ZM.view(ZM.SIZE)                                          # BUFFERS as the family SIZE sees it
+SIZED, L_SIZED = list(ZM.XSIZE.sizes), list(ZM.SIZE.sizes)
+UNSIZED, L_UNSIZED = ([k for k in f.kinds if k not in f.sizes] for f in (ZM.XSIZE, ZM.SIZE))
+X_GPU_TESTS = SM.gpu_tests(ZM.XSIZE)
 
 
 def _texts():
@@ -31,23 +34,23 @@ def _texts():
 
 # ------------------------------------------------------------------ 1. the kinds, the families, the pairs
 def test_the_sized_kinds_and_the_nodes_are_what_the_model_says():
-    assert XM.SIZED == ZM.SIZED + ["gv_mix", "eval_mix_logmmse"] and sorted(XM.SIZED + XM.UNSIZED) == sorted(SM.XKINDS)
-    assert set(XM.UNSIZED) - set(ZM.UNSIZED) == {"set_nat", "set_post", "time_kernel", "profile_step"}
-    assert XM.EV_KINDS == ("eval_mix", "gv_mix", "eval_mix_logmmse", "mix_features") and XM.NAT_KINDS == SM.READS_NAT
-    assert XM.NAT_SIZES == ("Z", "M", "L") and XM.CAP == 1024
-    for cfg in SM.XCONFIGS:
-        assert len(XM.ev_nodes(cfg)) == 20 and len(XM.nat_nodes(cfg)) == 42
-        for k in XM.NEW_SIZED:                                   # the six size classes and the sentences of eval_mix
-            assert XM.sizes_of(k) == list(ZM.SIZES)
+    assert SIZED == L_SIZED + ["gv_mix", "eval_mix_logmmse"] and sorted(SIZED + UNSIZED) == sorted(SM.KINDS)
+    assert set(UNSIZED) - set(L_UNSIZED) == {"set_nat", "set_post", "time_kernel", "profile_step"}
+    assert ZM.EV_KINDS == ("eval_mix", "gv_mix", "eval_mix_logmmse", "mix_features") and ZM.NAT_KINDS == SM.READS_NAT
+    assert ZM.NAT_SIZES == ("Z", "M", "L") and ZM.CAP == 1024
+    for cfg in SM.CONFIGS:
+        assert len(SM.nodes(ZM.XSIZE, cfg, "ev")) == 20 and len(SM.nodes(ZM.XSIZE, cfg, "nat")) == 42
+        for k in ZM.NEW_SIZED:                                   # the six size classes and the sentences of eval_mix
+            assert ZM.sizes_of(k) == list(ZM.SIZES)
             for z in ZM.SIZES:
-                s, e = XM.shape(cfg, k, z), ZM.shape(cfg, "eval_mix", z)
+                s, e = ZM.shape(cfg, k, z), ZM.shape(cfg, "eval_mix", z)
                 assert s.kind == k and s._replace(kind="eval_mix") == e and s.T == ZM._sentence_T(cfg, "eval_mix", z, ZM.large(cfg, "eval_mix"))
-            assert XM.shape(cfg, k, "FULL").rows == XM.CAP and XM.shape(cfg, k, "OVER").rows == XM.CAP + 1 and not XM.shape(cfg, k, "OVER").ok
+            assert ZM.shape(cfg, k, "FULL").rows == ZM.CAP and ZM.shape(cfg, k, "OVER").rows == ZM.CAP + 1 and not ZM.shape(cfg, k, "OVER").ok
     # the walk numbers lie behind every walk number of both models
-    used = set(w for c in SM.CONFIGS for w, _ in [ZM.walk_calls(c, x) for x in ZM.walk_ids(c)])
-    used |= set(w for c in SM.XCONFIGS for w, _ in [SM.x_walk_calls(c, x) for x in SM.x_walk_ids(c)])
-    mine = set(w for c in SM.XCONFIGS for w, _ in [XM.walk_calls(c, x) for x in XM.walk_ids(c)])
-    assert min(mine) > max(used) and len(mine) == 2 + 3 + len(XM.MEASURE_SIZES) + XM.N_RANDOM
+    used = set(w for c in ZM.SIZE.configs for w, _ in [SM.walk_calls(ZM.SIZE, c, x) for x in SM.walk_ids(ZM.SIZE, c)])
+    used |= set(w for c in SM.CONFIGS for w, _ in [SM.walk_calls(SM.EXTENDED, c, x) for x in SM.walk_ids(SM.EXTENDED, c)])
+    mine = set(w for c in SM.CONFIGS for w, _ in [SM.walk_calls(ZM.XSIZE, c, x) for x in SM.walk_ids(ZM.XSIZE, c)])
+    assert min(mine) > max(used) and len(mine) == 2 + 3 + len(ZM.MEASURE_SIZES) + ZM.XSIZE.n_random
 
 
 def _missing(ns, pieces):
@@ -57,30 +60,30 @@ def _missing(ns, pieces):
 
 @pytest.mark.parametrize("cid", IDS)
 def test_every_ordered_pair_of_each_new_family_is_run_by_a_named_gpu_test(cid):
-    cfg = SM.XBY_ID[cid]
-    for fid in XM.N_PIECES:
-        ns = XM.nodes(cfg, fid)
-        ps = XM.piece_nodes(cfg, fid)                            # the nodes as the MODEL runs them: kind, size and the handle's mode
+    cfg = SM.BY_ID[cid]
+    for fid in SM.n_pieces(ZM.XSIZE):
+        ns = SM.nodes(ZM.XSIZE, cfg, fid)
+        ps = SM.piece_nodes(ZM.XSIZE, cfg, fid)                            # the nodes as the MODEL runs them: kind, size and the handle's mode
         assert _missing(ns, ps) == ([], [])
         for i in range(len(ps) - 1):
             assert ps[i][-1] == ps[i + 1][0]
         assert ps[0][0] == ps[-1][-1]
-        table = XM.pair_table(cfg, fid)
+        table = SM.pair_table(ZM.XSIZE, cfg, fid)
         assert sorted(table) == sorted((a, b) for a in ns for b in ns) and len(table) == len(ns) ** 2
-        assert all(len(v) == 1 and v[0] in XM.GPU_TESTS for v in table.values())
+        assert all(len(v) == 1 and SM.test_id(ZM.XSIZE, cfg, v[0]) in X_GPU_TESTS for v in table.values())
         for at in (1, len(ps[0]) // 2):                          # a removed call opens cells, by name
             cut = [list(p) for p in ps]
             gone = cut[0].pop(at)
             missing, _ = _missing(ns, cut)
             assert missing and set(missing) <= {(ps[0][at - 1], gone), (gone, ps[0][at + 1])}
-        for calls in XM.pieces(cfg, fid):                        # every call and every set_nat succeeds; a set_nat only where the mode changes
-            steps = XM.run_model(cfg, calls)
+        for calls in SM.pieces(ZM.XSIZE, cfg, fid):                        # every call and every set_nat succeeds; a set_nat only where the mode changes
+            steps = SM.run_model(ZM.XSIZE, cfg, calls)
             assert all(s.status == SM.BP_OK for s in steps) and len(set(s.pos for s in steps)) == len(steps)
             assert all(b.kind != "set_nat" for a, b in zip(steps, steps[1:]) if a.kind == "set_nat")
             assert (fid == "nat") == any(s.kind == "set_nat" for s in steps)
-    assert sum(len(p) - 1 for p in XM.piece_nodes(cfg, "ev")) == 400 and sum(len(p) - 1 for p in XM.piece_nodes(cfg, "nat")) == 1764
-    for wid, walk, calls in XM.all_walks(cfg):
-        assert all(k in XM.x_kinds_of(cfg) and (z in XM.sizes_of(k) if k in XM.SIZED else z is None) for _, k, z in calls), wid
+    assert sum(len(p) - 1 for p in SM.piece_nodes(ZM.XSIZE, cfg, "ev")) == 400 and sum(len(p) - 1 for p in SM.piece_nodes(ZM.XSIZE, cfg, "nat")) == 1764
+    for wid, walk, calls in SM.all_walks(ZM.XSIZE, cfg):
+        assert all(k in SM.kinds_of(ZM.XSIZE, cfg) and (z in ZM.sizes_of(k) if k in SIZED else z is None) for _, k, z in calls), wid
         assert len(set(p for p, _, _ in calls)) == len(calls) and [p for p, _, _ in calls] == sorted(p for p, _, _ in calls), wid
 
 
@@ -90,28 +93,30 @@ def test_every_named_gpu_test_exists_and_is_not_skipped():
     marks = [mod.pytestmark] + list(getattr(fn, "pytestmark", []))
     assert any(m.name == "gpu" for m in marks) and not any(m.name in ("skip", "skipif", "xfail") for m in marks)
     ids = [i for m in marks if m.name == "parametrize" for i in m.kwargs["ids"]]
-    assert ["tests/test_xsize_gpu.py::test_xsize_walk[%s]" % i for i in ids] == XM.GPU_TESTS
-    assert len(XM.GPU_TESTS) == len(SM.XCONFIGS) * (sum(XM.N_PIECES.values()) + 3 + len(XM.MEASURE_SIZES) + XM.N_RANDOM)
+    assert ["tests/test_xsize_gpu.py::test_xsize_walk[%s]" % i for i in ids] == X_GPU_TESTS
+    assert len(X_GPU_TESTS) == len(SM.CONFIGS) * (sum(SM.n_pieces(ZM.XSIZE).values()) + 3 + len(ZM.MEASURE_SIZES) + ZM.XSIZE.n_random)
     src = open(os.path.join(ROOT, "tests", "test_xsize_gpu.py")).read()
     assert "pytest.skip" not in src and "xfail" not in src and "importorskip" not in src
-    assert "kinds=SM.XKINDS" in src and "cap=XM.CAP" in src and "words_differing=sum(diff.values())" in src
+    harness = open(os.path.join(ROOT, "tests", "walk_harness.py")).read()
+    assert "H.walk_test(pkg, parity_record, ZM.XSIZE, cid, wid)" in src and ZM.XSIZE.kinds == tuple(SM.KINDS) and ZM.XSIZE.cap == ZM.CAP
+    assert "cap=fam.cap" in harness and "words_differing=sum(diff.values())" in harness
 
 
 # ------------------------------------------------------------------ 2. the statuses the model predicts
 @pytest.mark.parametrize("cid", IDS)
 def test_over_in_dynamic_mode_follows_every_other_size_of_its_kind_with_the_state_unchanged(cid):
-    cfg = SM.XBY_ID[cid]
-    steps = XM.run_model(cfg, XM.over_walk(cfg))
+    cfg = SM.BY_ID[cid]
+    steps = SM.run_model(ZM.XSIZE, cfg, ZM.mode_over_walk(cfg))
     behind = set((a.kind, a.size, b.before["nat"]) for a, b in zip(steps, steps[1:]) if b.size == "OVER" and b.kind == a.kind)
-    want = set((k, z, DYNAMIC) for k in XM.ASKS_NAT for z in XM.sizes_of(k) if z != "OVER")
-    want |= set((k, z, STATIC) for k in XM.NEW_SIZED for z in ZM.GOOD)
-    assert behind == want and set(XM.ASKS_NAT) >= set(SM.READS_NAT) | {"eval_mix_logmmse"}
-    in_random = [s for r in range(XM.N_RANDOM) for s in XM.run_model(cfg, XM.random_walk(cfg, r)) if s.size == "OVER"]
+    want = set((k, z, DYNAMIC) for k in ZM.ASKS_NAT for z in ZM.sizes_of(k) if z != "OVER")
+    want |= set((k, z, STATIC) for k in ZM.NEW_SIZED for z in ZM.GOOD)
+    assert behind == want and set(ZM.ASKS_NAT) >= set(SM.READS_NAT) | {"eval_mix_logmmse"}
+    in_random = [s for r in range(ZM.XSIZE.n_random) for s in SM.run_model(ZM.XSIZE, cfg, SM.random_walk(ZM.XSIZE, cfg, r)) if s.size == "OVER"]
     assert len(in_random) >= 4
     for s in steps + in_random:
         if s.size == "OVER":
-            assert s.status == SM.BP_ERR_ARG and s.before == s.after and XM.shape(cfg, s.kind, "OVER").rows == XM.CAP + 1
-        elif s.kind in XM.SIZED:
+            assert s.status == SM.BP_ERR_ARG and s.before == s.after and ZM.shape(cfg, s.kind, "OVER").rows == ZM.CAP + 1
+        elif s.kind in SIZED:
             assert s.status == SM.BP_OK or s.kind == "eval_mix"
     for a, b in zip(steps, steps[1:]):                          # the call behind an OVER is a good one: it is compared with a fresh handle
         assert not (a.size == "OVER" and b.size == "OVER")
@@ -119,17 +124,17 @@ def test_over_in_dynamic_mode_follows_every_other_size_of_its_kind_with_the_stat
 
 @pytest.mark.parametrize("cid", IDS)
 def test_the_measurement_calls_run_behind_chunks_of_every_size_and_in_front_of_every_training_kind(cid):
-    cfg = SM.XBY_ID[cid]
+    cfg = SM.BY_ID[cid]
     bf16 = cfg.dtype == 1
-    for z in XM.MEASURE_SIZES:
-        calls = XM.measure_walk(cfg, z)
-        steps = XM.run_model(cfg, calls)
+    for z in ZM.MEASURE_SIZES:
+        calls = ZM.sized_measure_walk(cfg, z)
+        steps = SM.run_model(ZM.XSIZE, cfg, calls)
         behind = collections.defaultdict(set)
         for a, b, c in zip(steps, steps[1:], steps[2:]):
             if b.kind not in ("time_kernel", "profile_step"):
                 continue
             assert a.kind in ("train", "upload_train", "train_windows") and a.size == z and a.status == SM.BP_OK
-            rows = XM.shape(cfg, a.kind, z).n
+            rows = ZM.shape(cfg, a.kind, z).n
             assert b.before["rows"] == rows and b.before["has_targ"] and b.before["windows"] == (b.kind == "profile_step")
             if bf16:
                 want = SM.BP_ERR_STATE
@@ -137,26 +142,26 @@ def test_the_measurement_calls_run_behind_chunks_of_every_size_and_in_front_of_e
                 want = SM.BP_ERR_STATE if b.kind == "time_kernel" else SM.BP_ERR_ARG
             else:
                 want = SM.BP_OK
-            assert b.status == want and rows == {"Z": 1, "ONE": cfg.B, "FULL": XM.CAP}.get(z, rows), (cid, z, b.kind, b.status)
+            assert b.status == want and rows == {"Z": 1, "ONE": cfg.B, "FULL": ZM.CAP}.get(z, rows), (cid, z, b.kind, b.status)
             behind[b.kind].add(c.kind)
         assert set(SM.TRAINING_KINDS) <= behind["time_kernel"] and set(SM.TRAINING_KINDS) <= behind["profile_step"]
-        assert set(XM._OUT_QUERIES) <= behind["time_kernel"]     # ... and a dyed L query of the out_chunk family behind a timing run
-        assert all(XM.dyed(s.kind, s.size) for s in steps if s.kind in XM._OUT_QUERIES)
+        assert set(ZM._OUT_QUERIES) <= behind["time_kernel"]     # ... and a dyed L query of the out_chunk family behind a timing run
+        assert all(ZM.dyed(s.kind, s.size) for s in steps if s.kind in ZM._OUT_QUERIES)
         assert sum(1 for s in steps if s.kind == "checkpoint") == 2 * len(SM.TRAINING_KINDS)
-        sim = XM.simulate(cfg, calls)
+        sim = ZM.simulate(ZM.XSIZE, cfg, calls)
         assert (sim.behind_time >= 1) == (not bf16 and z != "Z"), (cid, z, sim.behind_time)
         if not bf16 and z != "Z":                                # kernel ids by position
             assert len(set(SM.choice(cfg, s.pos, "time_kernel")["which"] for s in steps if s.kind == "time_kernel")) >= 2
-    assert XM.MEASURE_SIZES == ("Z", "ONE", "M", "L", "FULL") and set(XM._OUT_QUERIES) <= set(ZM.BUFFERS["out_chunk"].ask)
+    assert ZM.MEASURE_SIZES == ("Z", "ONE", "M", "L", "FULL") and set(ZM._OUT_QUERIES) <= set(LB["out_chunk"].ask)
     assert SM.REPLAY_AS == {"profile_step": "train_resident"} and "time_kernel" in SM.NO_FRESH
 
 
 @pytest.mark.parametrize("cid", IDS)
 def test_every_refusal_the_model_predicts_occurs_and_leaves_the_state_as_it_was(cid):
-    cfg = SM.XBY_ID[cid]
+    cfg = SM.BY_ID[cid]
     seen = collections.Counter()
-    for wid, _, calls in XM.all_walks(cfg):
-        for s in XM.run_model(cfg, calls):
+    for wid, _, calls in SM.all_walks(ZM.XSIZE, cfg):
+        for s in SM.run_model(ZM.XSIZE, cfg, calls):
             if s.status != SM.BP_OK:
                 assert s.before == s.after
                 seen["OVER" if s.size == "OVER" else s.kind] += 1
@@ -166,89 +171,89 @@ def test_every_refusal_the_model_predicts_occurs_and_leaves_the_state_as_it_was(
     if cfg.dtype == 1:
         want.add("set_forward")
     assert set(seen) == want, (cid, dict(seen))
-    steps = XM.run_model(cfg, XM.regrow_walk(cfg))
+    steps = SM.run_model(ZM.XSIZE, cfg, ZM.regrow_walk(cfg))
     refused = [s for s in steps if s.status != SM.BP_OK]
     assert len(refused) == (3 if SM.mask_col(cfg) is not None else 0)
     assert all(s.kind == "eval_mix" and s.status == SM.BP_ERR_ARG and s.before["post"] > 0 and SM.choice(cfg, s.pos, "eval_mix")["masked"] for s in refused)
     assert any(s.kind == "eval_mix" and s.status == SM.BP_OK and s.before["post"] > 0 for s in steps)
-    walks = [XM.random_walk(cfg, r) for r in range(XM.N_RANDOM)]
-    assert XM.N_RANDOM == 4 and all(len(w) == XM.RANDOM_LEN for w in walks) and len(set(map(tuple, walks))) == 4
+    walks = [SM.random_walk(ZM.XSIZE, cfg, r) for r in range(ZM.XSIZE.n_random)]
+    assert ZM.XSIZE.n_random == 4 and all(len(w) == SM.RANDOM_LEN for w in walks) and len(set(map(tuple, walks))) == 4
     assert set(k for w in walks for _, k, _ in w) >= set(SM.NEW_KINDS)
-    assert len(set(z for w in walks for _, k, z in w if k in XM.NEW_SIZED)) >= 4
-    dyn = set((s.kind, s.size) for w in walks for s in XM.run_model(cfg, w) if s.kind in XM.ASKS_NAT and s.before["nat"] == DYNAMIC and s.status == SM.BP_OK)
+    assert len(set(z for w in walks for _, k, z in w if k in ZM.NEW_SIZED)) >= 4
+    dyn = set((s.kind, s.size) for w in walks for s in SM.run_model(ZM.XSIZE, cfg, w) if s.kind in ZM.ASKS_NAT and s.before["nat"] == DYNAMIC and s.status == SM.BP_OK)
     assert len(dyn) >= 8 and {z for _, z in dyn} >= {"ONE", "FULL"}, (cid, sorted(dyn))
 
 
 # ------------------------------------------------------------------ 3. the table against the sources, and its two mutants
 def test_the_extended_table_names_every_buf_every_growing_site_and_every_nat_b_of_the_sources():
-    found = XM.scan(_texts())
-    assert XM.scan_problems(found) == []
-    assert sorted(found["nat_b"]) == sorted(XM.NAT_EXPR) and all(len(v) == 1 for v in found["nat_b"].values())
-    assert XM.DNAT_B in _texts()["bp_mix.hip"] and "if (dyn && !Y) Y = (float2 *)((char *)nat_d + dnat_b);" in _texts()["bp_mix.hip"]
+    found = ZM.scan(_texts())
+    assert ZM.scan_problems(found) == []
+    assert sorted(found["nat_b"]) == sorted(ZM.NAT_EXPR) and all(len(v) == 1 for v in found["nat_b"].values())
+    assert ZM.DNAT_B in _texts()["bp_mix.hip"] and "if (dyn && !Y) Y = (float2 *)((char *)nat_d + dnat_b);" in _texts()["bp_mix.hip"]
     # the rows that left UNMODELLED, and the three that stay with their reason
-    assert list(XM.UNMODELLED) == ["ev_tab", "ev_work", "ev_pin"] and "ev_gain" in ZM.UNMODELLED
-    assert XM.sizing_kinds("ev_gain") == ["eval_mix_logmmse"] and XM.zero_kinds("ev_gain") == ["eval_mix", "gv_mix"]
+    assert list(ZM.UNMODELLED) == ["ev_tab", "ev_work", "ev_pin"] and "ev_gain" in ZM.unmodelled(ZM.SIZE)
+    assert ZM.sizing_kinds("ev_gain") == ["eval_mix_logmmse"] and ZM.zero_kinds("ev_gain") == ["eval_mix", "gv_mix"]
     for name in ("ev_syn", "ev_ola", "lps"):
-        assert XM.zero_kinds(name) == ["gv_mix"] and "eval_mix_logmmse" in XM.sizing_kinds(name)
-    assert [n for n in XM.BUFFERS if XM.zero_kinds(n)] == ["lps", "ev_syn", "ev_ola", "ev_gain"] and list(XM.BUFFERS)[:-1] == list(ZM.BUFFERS)
+        assert ZM.zero_kinds(name) == ["gv_mix"] and "eval_mix_logmmse" in ZM.sizing_kinds(name)
+    assert [n for n in ZM.BUFFERS if ZM.zero_kinds(n)] == ["lps", "ev_syn", "ev_ola", "ev_gain"] and list(ZM.BUFFERS)[:-1] == list(LB)
     mix = _texts()["bp_mix.hip"]
     assert "{ms->ev_syn, gv ? 0 : c.frames * 2 * hop * 4, false}, {ms->ev_ola, pcm_b, false}" in mix and "pcm_b = gv ? 0 : c.segs * hop * 4" in mix
     assert "{ms->lps, gv ? 0 : c.frames * D * 4, false}" in mix and "{ms->ev_gain, lm ? c.frames * ((size_t)D + 1) * 4 : 0, false}" in mix
     assert "{ms->ev_lps, gv ? lps_b : 2 * lps_b, false}" in mix and "if (!lm && (r = out_chunk_reserve(h, n)) != BP_OK) return r;" in mix
-    cfg = SM.XBY_ID["D"]
-    m = XM.shape(cfg, "eval_mix_logmmse", "M")
-    assert XM.asks(cfg, "ev_gain", m) == m.n * (XM.D + 1) * 4 and XM.asks(cfg, "out_chunk", m) == 0 and XM.asks(cfg, "out_chunk", XM.shape(cfg, "gv_mix", "M")) == m.n
-    assert XM.asks(cfg, "ev_lps", XM.shape(cfg, "gv_mix", "M")) * 2 == XM.asks(cfg, "ev_lps", XM.shape(cfg, "eval_mix", "M"))
+    cfg = SM.BY_ID["D"]
+    m = ZM.shape(cfg, "eval_mix_logmmse", "M")
+    assert ZM.asks(cfg, "ev_gain", m) == m.n * (ZM.D + 1) * 4 and ZM.asks(cfg, "out_chunk", m) == 0 and ZM.asks(cfg, "out_chunk", ZM.shape(cfg, "gv_mix", "M")) == m.n
+    assert ZM.asks(cfg, "ev_lps", ZM.shape(cfg, "gv_mix", "M")) * 2 == ZM.asks(cfg, "ev_lps", ZM.shape(cfg, "eval_mix", "M"))
     # the old kinds ask every old row for what size_model says, in static mode
-    for name, b in ZM.BUFFERS.items():
+    for name, b in LB.items():
         for k in b.ask:
             for z in ZM.sizes_of(k):
-                assert XM.asks(cfg, name, XM.shape(cfg, k, z), STATIC) == ZM.asks(cfg, name, ZM.shape(cfg, k, z)), (name, k, z)
+                assert ZM.asks(cfg, name, ZM.shape(cfg, k, z), STATIC) == ZM.asks(cfg, name, ZM.shape(cfg, k, z), STATIC, LB), (name, k, z)
     # the four sites of the noise-aware rows, static and dynamic
-    s = XM.shape(cfg, "cv_mix", "M")
-    assert XM.asks(cfg, "wset.r[2]", s, STATIC) == s.n_sent * 132 and XM.asks(cfg, "wset.r[2]", s, DYNAMIC) == XM.al256(s.n * 132) + s.n * 264
+    s = ZM.shape(cfg, "cv_mix", "M")
+    assert ZM.asks(cfg, "wset.r[2]", s, STATIC) == s.n_sent * 132 and ZM.asks(cfg, "wset.r[2]", s, DYNAMIC) == ZM.al256(s.n * 132) + s.n * 264
     for k in ("eval_mix", "gv_mix", "eval_mix_logmmse", "enhance"):
-        s = XM.shape(cfg, k, "M")
-        assert XM.asks(cfg, "wset.r[2]", s, STATIC) == s.n_sent * 132 and XM.asks(cfg, "wset.r[2]", s, DYNAMIC) == s.n * 132
-    s = XM.shape(cfg, "stream", "L")
-    assert XM.asks(cfg, "wset.r[2]", s, STATIC) == 4 * 132 and XM.asks(cfg, "wset.r[2]", s, DYNAMIC) == s.n * 132 and s.n >= 500
-    s = XM.shape(cfg, "train_windows", "L")
-    assert XM.asks(cfg, "wset.r[2]", s, STATIC) == XM.asks(cfg, "wset.r[2]", s, DYNAMIC) == ZM.N_NAT_L * 132
+        s = ZM.shape(cfg, k, "M")
+        assert ZM.asks(cfg, "wset.r[2]", s, STATIC) == s.n_sent * 132 and ZM.asks(cfg, "wset.r[2]", s, DYNAMIC) == s.n * 132
+    s = ZM.shape(cfg, "stream", "L")
+    assert ZM.asks(cfg, "wset.r[2]", s, STATIC) == 4 * 132 and ZM.asks(cfg, "wset.r[2]", s, DYNAMIC) == s.n * 132 and s.n >= 500
+    s = ZM.shape(cfg, "train_windows", "L")
+    assert ZM.asks(cfg, "wset.r[2]", s, STATIC) == ZM.asks(cfg, "wset.r[2]", s, DYNAMIC) == ZM.N_NAT_L * 132
 
 
 def test_a_new_nat_b_expression_a_new_window_reserve_site_and_a_dropped_row_fail_by_name():
     texts = _texts()
-    found = XM.scan(texts)
+    found = ZM.scan(texts)
     # mutant: ev_gain dropped from BUFFERS
-    less = collections.OrderedDict((k, v) for k, v in XM.BUFFERS.items() if k != "ev_gain")
-    assert XM.scan_problems(found, less) == ["a Buf without a row: ev_gain", "wave_grow sizes ev_gain, which no row names"]
+    less = collections.OrderedDict((k, v) for k, v in ZM.BUFFERS.items() if k != "ev_gain")
+    assert ZM.scan_problems(found, less) == ["a Buf without a row: ev_gain", "wave_grow sizes ev_gain, which no row names"]
     # size_model's own table and UNMODELLED still pass (ev_gain is on record there), without the new claims
-    assert XM.scan_problems(found, ZM.BUFFERS, ZM.UNMODELLED) == []
+    assert ZM.scan_problems(found, LB, ZM.unmodelled(ZM.SIZE)) == []
     # a changed expression, a new expression and a new site, each in a copy of the text
     t = dict(texts, **{"bp_wave.hip": texts["bp_wave.hip"].replace("dyn ? p.frames * D * 4 :", "dyn ? 2 * p.frames * D * 4 :")})
-    assert XM.scan_problems(XM.scan(t)) == ["a nat_b expression in bp_wave.hip that the wset.r[2] row does not restate: "
+    assert ZM.scan_problems(ZM.scan(t)) == ["a nat_b expression in bp_wave.hip that the wset.r[2] row does not restate: "
                                             "!nat ? 0 : dyn ? 2 * p.frames * D * 4 : (size_t)c->n_sent * D * 4"]
     t = dict(texts, **{"bp_new.hip": "int f(bp_handle *h) {\n    const size_t nat_b = (size_t)n * 4;\n    return window_reserve(h, 1, 0, nat_b, 1, &a, nullptr, &b, &c);\n}\n"})
-    assert XM.scan_problems(XM.scan(t)) == ["a nat_b expression in bp_new.hip that the wset.r[2] row does not restate: (size_t)n * 4",
+    assert ZM.scan_problems(ZM.scan(t)) == ["a nat_b expression in bp_new.hip that the wset.r[2] row does not restate: (size_t)n * 4",
                                             "bp_new.hip holds 1 window_reserve calls, the table 0"]
     t = dict(texts, **{"bp_stream.hip": texts["bp_stream.hip"].replace("const size_t nat_b", "const size_t nat_bytes")})
-    assert "no nat_b expression left in bp_stream.hip" in XM.scan_problems(XM.scan(t))
+    assert "no nat_b expression left in bp_stream.hip" in ZM.scan_problems(ZM.scan(t))
 
 
 def _mode_regrows(cfg, buffers=None):
     total = collections.Counter()
-    for wid, _, calls in XM.all_walks(cfg):
-        total.update(XM.simulate(cfg, calls, buffers).by_mode["wset.r[2]"])
+    for wid, _, calls in SM.all_walks(ZM.XSIZE, cfg):
+        total.update(ZM.simulate(ZM.XSIZE, cfg, calls, buffers).by_mode["wset.r[2]"])
     return total
 
 
 @pytest.mark.parametrize("cid", IDS)
 def test_buffers_asked_by_mode_or_kind_are_regrown_twice_in_each_direction_and_followed_by_smaller_calls(cid):
-    cfg = SM.XBY_ID[cid]
+    cfg = SM.BY_ID[cid]
     regrows, smaller, zero_behind = collections.Counter(), collections.defaultdict(set), collections.defaultdict(set)
     by_prev = collections.defaultdict(collections.Counter)
-    for wid, _, calls in XM.all_walks(cfg):
-        sim = XM.simulate(cfg, calls)
+    for wid, _, calls in SM.all_walks(ZM.XSIZE, cfg):
+        sim = ZM.simulate(ZM.XSIZE, cfg, calls)
         regrows.update(sim.regrows)
         for n, v in sim.smaller.items():
             smaller[n] |= v
@@ -259,148 +264,148 @@ def test_buffers_asked_by_mode_or_kind_are_regrown_twice_in_each_direction_and_f
     # the mode: dynamic behind static and static behind dynamic, each at least twice, each owed to the mode
     by_mode = _mode_regrows(cfg)
     assert by_mode[(STATIC, DYNAMIC)] >= 2 and by_mode[(DYNAMIC, STATIC)] >= 2, (cid, dict(by_mode))
-    assert smaller["wset.r[2]"] >= set((k, m) for k in XM.ASKS_NAT for m in (STATIC, DYNAMIC)), cid
+    assert smaller["wset.r[2]"] >= set((k, m) for k in ZM.ASKS_NAT for m in (STATIC, DYNAMIC)), cid
     # the kind: every buffer of the list is regrown by, and runs smaller behind a regrow for, every kind that sizes it ...
-    for name in XM.BY_KIND:
-        ks = set(XM.sizing_kinds(name))
+    for name in ZM.BY_KIND:
+        ks = set(ZM.sizing_kinds(name))
         assert regrows[name] >= 2 and set(k for k, _ in smaller[name]) == ks, (cid, name)
         assert set(k for (_, k), n in by_prev[name].items() if n) == ks, (cid, name)
         # ... and the kinds that ask for 0 bytes of it run directly behind every kind that sizes it, in a regrown block
-        for zk in XM.zero_kinds(name):
-            assert set(p for k, p in zero_behind[name] if k == zk) >= ks & set(XM.EVAL + ("mix_features",)), (cid, name, zk)
+        for zk in ZM.zero_kinds(name):
+            assert set(p for k, p in zero_behind[name] if k == zk) >= ks & set(ZM.EVAL + ("mix_features",)), (cid, name, zk)
     # ev_gain: the log-MMSE call regrows it directly behind a net-scored call, and gv_mix runs behind both
     assert by_prev["ev_gain"][("eval_mix", "eval_mix_logmmse")] >= 2
     assert {("gv_mix", "eval_mix_logmmse"), ("gv_mix", "eval_mix"), ("eval_mix", "eval_mix_logmmse")} <= zero_behind["ev_gain"]
     # ev_lps: gv_mix asks for half of it
     assert by_prev["ev_lps"][("gv_mix", "eval_mix")] + by_prev["ev_lps"][("gv_mix", "eval_mix_logmmse")] >= 2
     # every other row keeps size_model's claim over the new walks: regrown twice, a smaller call of every sizing kind behind it
-    for name, b in XM.BUFFERS.items():
-        if name in XM.NEVER:
+    for name, b in ZM.BUFFERS.items():
+        if name in ZM.NEVER:
             assert regrows[name] == 0
         else:
-            assert regrows[name] >= 2 and set(k for k, _ in smaller[name]) >= set(XM.sizing_kinds(name)) - {"train_windows", "cv_windows"}, (cid, name)
-    assert XM.BY_MODE == ("wset.r[2]",) and XM.BY_KIND == ("lps", "ev_syn", "ev_ola", "ev_lps", "ev_gain")
+            assert regrows[name] >= 2 and set(k for k, _ in smaller[name]) >= set(ZM.sizing_kinds(name)) - {"train_windows", "cv_windows"}, (cid, name)
+    assert ZM.BY_MODE == ("wset.r[2]",) and ZM.BY_KIND == ("lps", "ev_syn", "ev_ola", "ev_lps", "ev_gain")
 
 
 @pytest.mark.parametrize("cid", IDS)
 def test_the_static_only_row_of_the_noise_aware_rows_fails_the_regrow_claim(cid):
     """The mutant: size_model's wset.r[2] row (n_nat * D * 4 whatever the mode) in place of the new one, in a copy of the table."""
-    cfg = SM.XBY_ID[cid]
-    old = collections.OrderedDict(XM.BUFFERS)
-    old["wset.r[2]"] = old["wset.r[2]"]._replace(ask=ZM._ask(list(XM.NAT_ASK), XM._static_nat_ask))
-    s = XM.shape(cfg, "cv_mix", "L")
-    assert XM.asks(cfg, "wset.r[2]", s, DYNAMIC, old) == XM.asks(cfg, "wset.r[2]", s, STATIC, old) == ZM.asks(cfg, "wset.r[2]", ZM.shape(cfg, "cv_mix", "L"))
+    cfg = SM.BY_ID[cid]
+    old = collections.OrderedDict(ZM.BUFFERS)
+    old["wset.r[2]"] = old["wset.r[2]"]._replace(ask=ZM._ask(list(ZM.NAT_ASK), ZM._static_nat_ask))
+    s = ZM.shape(cfg, "cv_mix", "L")
+    assert ZM.asks(cfg, "wset.r[2]", s, DYNAMIC, old) == ZM.asks(cfg, "wset.r[2]", s, STATIC, old) == ZM.asks(cfg, "wset.r[2]", ZM.shape(cfg, "cv_mix", "L"), STATIC, LB)
     by_mode = _mode_regrows(cfg, old)
     assert by_mode[(STATIC, DYNAMIC)] == 0 and by_mode[(DYNAMIC, STATIC)] == 0          # no regrow of it is owed to the mode
     assert _mode_regrows(cfg)[(STATIC, DYNAMIC)] >= 2
     # ... nor does it see the spectrum behind the rows: the largest ask of the walks is a third of the real one
-    big = max(XM.asks(cfg, "wset.r[2]", XM.shape(cfg, k, z), DYNAMIC) for k in XM.NO_Y for z in XM.NAT_SIZES)
-    assert big >= 3 * ZM.N_NAT_L * 132 > max(XM.asks(cfg, "wset.r[2]", XM.shape(cfg, k, z), DYNAMIC, old) for k in XM.NO_Y for z in XM.NAT_SIZES)
+    big = max(ZM.asks(cfg, "wset.r[2]", ZM.shape(cfg, k, z), DYNAMIC) for k in ZM.NO_Y for z in ZM.NAT_SIZES)
+    assert big >= 3 * ZM.N_NAT_L * 132 > max(ZM.asks(cfg, "wset.r[2]", ZM.shape(cfg, k, z), DYNAMIC, old) for k in ZM.NO_Y for z in ZM.NAT_SIZES)
 
 
 @pytest.mark.parametrize("cid", IDS)
 def test_l_regrows_behind_m_for_the_new_kinds_and_for_the_dynamic_asks(cid):
-    cfg = SM.XBY_ID[cid]
+    cfg = SM.BY_ID[cid]
     checked = 0
-    for name, b in XM.BUFFERS.items():
-        for k in XM.sizing_kinds(name):
-            for mode in ((STATIC, DYNAMIC) if name in XM.BY_MODE and k in XM.ASKS_NAT else (STATIC,)):
-                if not (k in XM.NEW_SIZED or mode == DYNAMIC) or name in XM.NEVER:
+    for name, b in ZM.BUFFERS.items():
+        for k in ZM.sizing_kinds(name):
+            for mode in ((STATIC, DYNAMIC) if name in ZM.BY_MODE and k in ZM.ASKS_NAT else (STATIC,)):
+                if not (k in ZM.NEW_SIZED or mode == DYNAMIC) or name in ZM.NEVER:
                     continue
-                m, l = XM.asks(cfg, name, XM.shape(cfg, k, "M"), mode), XM.asks(cfg, name, XM.shape(cfg, k, "L"), mode)
+                m, l = ZM.asks(cfg, name, ZM.shape(cfg, k, "M"), mode), ZM.asks(cfg, name, ZM.shape(cfg, k, "L"), mode)
                 if m == 0:
                     continue
-                if (k, name, mode) in XM.L_EXEMPT:
-                    assert l <= XM.POLICY[b.policy](m), "no longer exempt: %s %s" % (k, name)
+                if (k, name, mode) in ZM.L_EXEMPT_NEW:
+                    assert l <= ZM.POLICY[b.policy](m), "no longer exempt: %s %s" % (k, name)
                     continue
-                assert l > XM.POLICY[b.policy](m), (cid, k, name, mode, m, l)
+                assert l > ZM.POLICY[b.policy](m), (cid, k, name, mode, m, l)
                 checked += 1
-    assert checked >= 30 and XM.L_EXEMPT == {}
+    assert checked >= 30 and ZM.L_EXEMPT_NEW == {}
     # in dynamic mode the rows of the closed nat walk's three sizes regrow one behind the other for every kind (a stream's M, one
     # sentence of 8 frames, fits what its Z leaves: 1056 bytes against 4426)
-    for k in XM.NAT_KINDS:
-        z, m, l = (XM.asks(cfg, "wset.r[2]", XM.shape(cfg, k, s), DYNAMIC) for s in XM.NAT_SIZES)
-        assert (m > XM.grown(z) or k == "stream") and l > XM.grown(m), (cid, k, z, m, l)
+    for k in ZM.NAT_KINDS:
+        z, m, l = (ZM.asks(cfg, "wset.r[2]", ZM.shape(cfg, k, s), DYNAMIC) for s in ZM.NAT_SIZES)
+        assert (m > ZM.grown(z) or k == "stream") and l > ZM.grown(m), (cid, k, z, m, l)
 
 
 @pytest.mark.parametrize("cid", IDS)
 def test_the_spectrum_behind_the_rows_moves_between_consecutive_dynamic_calls(cid):
-    cfg = SM.XBY_ID[cid]
+    cfg = SM.BY_ID[cid]
     moves = set()
-    for wid, _, calls in XM.all_walks(cfg):
+    for wid, _, calls in SM.all_walks(ZM.XSIZE, cfg):
         if wid.startswith("nat"):
-            moves |= XM.simulate(cfg, calls).tail_moves
-    assert moves == set(XM.NO_Y) == {"train_mix", "cv_mix", "mix_features"}
-    offs = set(XM.y_tail(XM.shape(cfg, k, z)) for k in XM.NO_Y for z in XM.NAT_SIZES)
-    assert len(offs) >= 3 and all(o % 256 == 0 for o in offs) and XM.y_tail(XM.shape(cfg, "cv_mix", "Z")) == 512
+            moves |= ZM.simulate(ZM.XSIZE, cfg, calls).tail_moves
+    assert moves == set(ZM.NO_Y) == {"train_mix", "cv_mix", "mix_features"}
+    offs = set(ZM.y_tail(ZM.shape(cfg, k, z)) for k in ZM.NO_Y for z in ZM.NAT_SIZES)
+    assert len(offs) >= 3 and all(o % 256 == 0 for o in offs) and ZM.y_tail(ZM.shape(cfg, "cv_mix", "Z")) == 512
 
 
 # ------------------------------------------------------------------ 4. the widths, the dye, the corpus
 def test_every_width_follows_every_other_width_at_a_smaller_size_behind_a_dyed_call():
-    assert XM.WIDTH_PAIRS == {(3, 5), (3, 7), (5, 3), (5, 7), (7, 3), (7, 5)} and XM.SCORED == ("eval_mix", "eval_mix_logmmse")
-    for cfg in SM.XCONFIGS:
+    assert ZM.WIDTH_PAIRS == {(3, 5), (3, 7), (5, 3), (5, 7), (7, 3), (7, 5)} and ZM.SCORED == ("eval_mix", "eval_mix_logmmse")
+    for cfg in SM.CONFIGS:
         got = set()
-        for calls in XM.pieces(cfg, "ev"):
-            got |= XM.width_pairs(cfg, calls)
-            for s in XM.run_model(cfg, calls):                  # widths, stage and tracker go by position
-                d = XM.call_data(cfg, XM.WALK_NO["ev"], s.pos, s.kind, s.size)
+        for calls in SM.pieces(ZM.XSIZE, cfg, "ev"):
+            got |= ZM.width_pairs(cfg, calls)
+            for s in SM.run_model(ZM.XSIZE, cfg, calls):                  # widths, stage and tracker go by position
+                d = SM.call_data(ZM.XSIZE, cfg, SM.closed_of(ZM.XSIZE, "ev").walk, s.pos, s.kind, s.size)
                 assert {k: v for k, v in d.items() if k not in ("plan", "order")} == SM.choice(cfg, s.pos, s.kind)
-        assert got >= XM.WIDTH_PAIRS, (cfg.id, XM.WIDTH_PAIRS - got)
-        stages = set(SM.choice(cfg, p, "gv_mix")["stage"] for calls in XM.pieces(cfg, "ev") for p, k, z in calls if k == "gv_mix")
-        trackers = set(SM.choice(cfg, p, k)["noise"] for calls in XM.pieces(cfg, "ev") for p, k, z in calls if k == "eval_mix_logmmse")
+        assert got >= ZM.WIDTH_PAIRS, (cfg.id, ZM.WIDTH_PAIRS - got)
+        stages = set(SM.choice(cfg, p, "gv_mix")["stage"] for calls in SM.pieces(ZM.XSIZE, cfg, "ev") for p, k, z in calls if k == "gv_mix")
+        trackers = set(SM.choice(cfg, p, k)["noise"] for calls in SM.pieces(ZM.XSIZE, cfg, "ev") for p, k, z in calls if k == "eval_mix_logmmse")
         assert stages == {"raw", "post"} and trackers == {None, "spp"}
     # the seed is the first at which the claim holds in all four configurations
-    assert XM.ev_seed_holds(XM.EV_SEED) and not any(XM.ev_seed_holds(s) for s in range(XM.EV_SEED))
+    assert ZM.ev_seed_holds(ZM.EV_SEED) and not any(ZM.ev_seed_holds(s) for s in range(ZM.EV_SEED))
 
 
 def test_queries_at_l_and_full_are_dyed_and_training_stays_finite_for_the_new_kinds():
-    assert XM.FINITE_DYE == () and XM.DYED == ("L", "FULL")
-    for cfg in SM.XCONFIGS:
-        cor = XM.corpus(cfg)
-        for k in XM.MIXED:
-            for z in XM.sizes_of(k):
-                d = XM.call_data(cfg, 20, 5, k, z)
-                arrays = [cor["clean"][XM.source_of(cfg, r[0])] for r in d["plan"]]
-                assert [XM.frames_of_entry(cfg, r[0]) for r in d["plan"]] == XM.shape(cfg, k, z).T, (cfg.id, k, z)
+    assert ZM.FINITE_DYE == () and ZM.DYED == ("L", "FULL")
+    for cfg in SM.CONFIGS:
+        cor = SM.corpus(ZM.XSIZE, cfg)
+        for k in ZM.MIXED:
+            for z in ZM.sizes_of(k):
+                d = SM.call_data(ZM.XSIZE, cfg, 20, 5, k, z)
+                arrays = [cor["clean"][ZM.source_of(ZM.XSIZE, cfg, r[0])] for r in d["plan"]]
+                assert [ZM.frames_of_entry(ZM.XSIZE, cfg, r[0]) for r in d["plan"]] == ZM.shape(cfg, k, z).T, (cfg.id, k, z)
                 has_nan = any(np.isnan(a).any() for a in arrays)
-                assert has_nan == XM.dyed(k, z) == (z in XM.DYED and not SM.XKINDS[k].training), (cfg.id, k, z)
+                assert has_nan == ZM.dyed(k, z) == (z in ZM.DYED and not SM.KINDS[k].training), (cfg.id, k, z)
                 if has_nan and k not in SM.LOADABLE:
                     assert all(np.isnan(a).all() for a in arrays), (cfg.id, k, z)
                 if SM.has_reverb(cfg) and z != "OVER":          # D's reverberated entries appear in plans at every size
                     assert any(r[0] >= len(cor["clean"]) for r in d["plan"]), (k, z)
-        for z in XM.DYED:                                       # the chunk that can be trained on keeps its first mixture finite
-            p = XM.call_data(cfg, 20, 5, "mix_features", z)["plan"]
-            first = cor["clean"][XM.source_of(cfg, p[0][0])]
+        for z in ZM.DYED:                                       # the chunk that can be trained on keeps its first mixture finite
+            p = SM.call_data(ZM.XSIZE, cfg, 20, 5, "mix_features", z)["plan"]
+            first = cor["clean"][ZM.source_of(ZM.XSIZE, cfg, p[0][0])]
             assert np.isfinite(first).all() and SM.frames_of(len(first)) >= cfg.B
-            assert all(np.isnan(cor["clean"][XM.source_of(cfg, r[0])]).all() for r in p[1:])
+            assert all(np.isnan(cor["clean"][ZM.source_of(ZM.XSIZE, cfg, r[0])]).all() for r in p[1:])
         for k in ("forward", "enhance", "stream", "train", "cv_windows"):      # the other kinds: size_model's data under the new walk numbers
-            for z in XM.DYED:
-                d = XM.call_data(cfg, 24, 5, k, z)
+            for z in ZM.DYED:
+                d = SM.call_data(ZM.XSIZE, cfg, 24, 5, k, z)
                 arrays = [d[key] for key in ("x", "fea", "nat") if key in d] + list(d.get("sentences", [])) + [a for blk in d.get("blocks", []) for a in blk]
-                assert any(np.isnan(a).any() for a in arrays) == (not SM.XKINDS[k].training)
+                assert any(np.isnan(a).any() for a in arrays) == (not SM.KINDS[k].training)
 
 
 def test_the_corpus_is_the_extended_tables_with_size_models_entries_behind_it():
-    for cfg in SM.XCONFIGS:
-        cor, base = XM.corpus(cfg), SM.x_corpus(cfg)
+    for cfg in SM.CONFIGS:
+        cor, base = SM.corpus(ZM.XSIZE, cfg), SM.corpus(SM.EXTENDED, cfg)
         n0 = len(SM.CLEAN_LEN)
         assert all(np.array_equal(a, b) for a, b in zip(cor["clean"][:n0], base["clean"])) and len(cor["noise"]) == len(base["noise"])
         assert all(np.array_equal(a, b) for a, b in zip(cor["noise"], base["noise"])) and np.array_equal(cor["mean"], base["mean"])
         assert list(cor["index"]) == ZM.corpus_T(cfg) and list(cor["index"].values()) == list(range(n0, len(cor["clean"])))
-        if cfg in SM.CONFIGS:                                   # the same places as in size_model's corpus
-            assert cor["index"] == ZM.corpus(cfg)["index"] and not cor["twin"] and "rirs" not in cor
+        if cfg in ZM.SIZE.configs:                                   # the same places as in size_model's corpus
+            assert cor["index"] == SM.corpus(ZM.SIZE, cfg)["index"] and not cor["twin"] and "rirs" not in cor
         for (T, dy), i in cor["index"].items():
             x = cor["clean"][i]
-            assert SM.frames_of(len(x)) == T <= XM.CAP and bool(np.isnan(x).all()) == dy and bool(np.isfinite(x).all()) != dy
+            assert SM.frames_of(len(x)) == T <= ZM.CAP and bool(np.isnan(x).all()) == dy and bool(np.isfinite(x).all()) != dy
         if SM.has_reverb(cfg):
             n = len(cor["clean"])
             assert cor["pair_clean"][:2] == base["pair_clean"] and cor["pair_rir"][:2] == base["pair_rir"]
             assert cor["pair_clean"][2:] == list(range(n0, n)) and max(cor["pair_rir"]) < len(cor["rirs"]) and len(cor["pair_rir"]) == len(cor["pair_clean"])
-            assert all(XM.source_of(cfg, t) == c and t >= n for c, t in cor["twin"].items()) and len(cor["twin"]) == len(cor["pair_clean"])
+            assert all(ZM.source_of(ZM.XSIZE, cfg, t) == c and t >= n for c, t in cor["twin"].items()) and len(cor["twin"]) == len(cor["pair_clean"])
             # M is sequence_model's plan: its derived entries, at the places they have behind the longer clean list
-            p = XM.call_data(cfg, 20, 7, "gv_mix", "M")["plan"]
-            assert [XM.source_of(cfg, r[0]) for r in p] == [base["pair_clean"][c - n0] if c >= n0 else c for c in SM.x_query_clean(cfg)]
+            p = SM.call_data(ZM.XSIZE, cfg, 20, 7, "gv_mix", "M")["plan"]
+            assert [ZM.source_of(ZM.XSIZE, cfg, r[0]) for r in p] == [base["pair_clean"][c - n0] if c >= n0 else c for c in SM.plan_query_clean(cfg)]
             assert p[0][0] == n + 1
-        for k in XM.SIZED:                                      # call_data is a function of (configuration, walk, position, size)
-            a, b = XM.call_data(cfg, 21, 9, k, "M"), XM.call_data(cfg, 21, 9, k, "M")
+        for k in SIZED:                                      # call_data is a function of (configuration, walk, position, size)
+            a, b = SM.call_data(ZM.XSIZE, cfg, 21, 9, k, "M"), SM.call_data(ZM.XSIZE, cfg, 21, 9, k, "M")
             assert sorted(a) == sorted(b) and all(repr(a[key]) == repr(b[key]) for key in a), k

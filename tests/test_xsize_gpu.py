@@ -1,7 +1,7 @@
-"""One handle held to fresh replays across calls of CHANGING size, over the extended table: the walks of tests/xsize_model.py (-m gpu).
-The procedure is tests/walk_harness.py's (the subject S, the replay R of the training calls, a fresh handle per query), every
-comparison is between two runs of the same library and bit for bit (uint32 words; the double sums of gv_mix as uint64), so there is
-no tolerance in this file.
+"""One handle held to fresh replays across calls of CHANGING size, over the whole table: the walks of the family XSIZE of
+tests/size_model.py (-m gpu).  The procedure is tests/walk_harness.py's (walk_test: the subject S, the replay R of the training calls,
+a fresh handle per query), every comparison is between two runs of the same library and bit for bit (uint32 words; the double sums of
+gv_mix as uint64), so there is no tolerance in this file.
 
 What tests/test_size_gpu.py does not reach, per configuration A, B, C and D on a handle of capacity 1024:
   * `ev`: every ordered pair of (kind, size) over eval_mix, gv_mix, eval_mix_logmmse and mix_features -- the one wave_grow list of
@@ -18,32 +18,17 @@ What tests/test_size_gpu.py does not reach, per configuration A, B, C and D on a
   * four seeded random walks over all nodes of the extended table.
 The refusals the model predicts (CAP + 1 rows, a mask target under post-processing, the measurement calls on a bf16 handle or
 behind a chunk of fewer rows than a bunch) are host-side checks; none of them touches the device."""
-import time
-
 import pytest
 
 import sequence_model as SM
+import size_model as ZM
 import walk_harness as H
-import xsize_model as XM
 
 pytestmark = pytest.mark.gpu
 
-PARAMS = [(c.id, w) for c in SM.XCONFIGS for w in XM.walk_ids(c)]
+PARAMS = [(c.id, w) for c in ZM.XSIZE.configs for w in SM.walk_ids(ZM.XSIZE, c)]
 
 
 @pytest.mark.parametrize("cid,wid", PARAMS, ids=["%s-%s" % p for p in PARAMS])
 def test_xsize_walk(pkg, parity_record, cid, wid):
-    t0 = time.perf_counter()
-    cfg = SM.XBY_ID[cid]
-    walk, calls = XM.walk_calls(cfg, wid)
-    steps = XM.run_model(cfg, calls)
-    data = [XM.call_data(cfg, walk, s.pos, s.kind, s.size) for s in steps]
-    count, diff, bad = H.run_walk(pkg, cfg, steps, data, XM.corpus(cfg), cap=XM.CAP,
-                                  error_names=lambda s: "capacity" if s.size == "OVER" else None, idle=lambda s: XM.idle(cfg, s),
-                                  kinds=SM.XKINDS)
-    assert count["idle_trainings"] == sum(1 for s in steps if XM.idle(cfg, s))
-    assert count["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK) >= sum(1 for s in steps if s.size == "OVER")
-    seconds = round(time.perf_counter() - t0, 2)
-    parity_record(config=cid, walk=wid, words_differing=sum(diff.values()), seconds=seconds, **dict(count, **diff))
-    print(cid, wid, seconds, "s", count, diff)
-    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
+    H.walk_test(pkg, parity_record, ZM.XSIZE, cid, wid)

@@ -1,6 +1,7 @@
-"""What tests/test_sequence_gpu.py and tests/test_size_gpu.py share: one call of a model step on a handle (execute), the chunk a call
-leaves resident (load), the comparison as words, and the procedure of a walk (run_walk).  Every comparison is between two runs of
-the same library and is bit for bit; there is no tolerance in this file.
+"""What tests/test_sequence_gpu.py, tests/test_size_gpu.py and tests/test_xsize_gpu.py share: one call of a model step on a handle
+(execute), the chunk a call leaves resident (load), the comparison as words, the procedure of a walk (run_walk) and the one body of
+the four GPU tests (walk_test).  Every comparison is between two runs of the same library and is bit for bit; there is no tolerance
+in this file.
 
 Per walk three long-lived handles take part, all made from the same weights and seed:
   S   the subject: the whole walk, no read beyond the walk's own (pass 1)
@@ -14,12 +15,13 @@ Per walk three long-lived handles take part, all made from the same weights and 
       of whatever is resident, F is also given the chunk of the call that made it resident on S (load).
 Every expected error is a host-side check: its status and a non-empty message are checked on S and S2, and the checkpoints behind it
 still equal R, which never made the call.
-With the extended table (sequence_model.XKINDS, passed as `kinds`): R repeats set_nat, makes train_resident(0, B) where S made
-profile_step(0, 1), and leaves out set_post and time_kernel like any query; a chunk is loaded in the noise-aware mode it was made in.
+R repeats set_nat, makes train_resident(0, B) where S made profile_step(0, 1), and leaves out set_post and time_kernel like any
+query; a chunk is loaded in the noise-aware mode it was made in.
 
 A step is anything with the fields pos, kind, status, before, after of sequence_model.Step; the data of a call say how large it is
 (the rows of x, the sentences, the blocks), so one `execute` serves every size."""
 import re
+import time
 
 import numpy as np
 import pytest
@@ -260,15 +262,13 @@ def advance(g, cfg, n_bunches, W, b, cap=SM.CAP):
     assert differing(w[1:] + bb[1:], W[1:] + b[1:], "advance") == 0
 
 
-def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None, kinds=None):
+def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None):
     """The procedure above over steps and their data.  (count, diff, bad): what ran, the differing words per comparison, and
     (comparison, what, words) of everything that differs.
     error_names: step -> the text its expected error must contain (None: any message).
     idle: step -> True for a successful training call that the model says trains NOTHING.  The replay leaves such a call out, so a
     weight, a momentum word or a position of the dropout stream that it moved shows at the next checkpoint; and on the second pass
-    W, b, dW, db are read on both sides of it and must be the same words.
-    kinds: the table the steps come from (default sequence_model.KINDS)."""
-    kinds = SM.KINDS if kinds is None else kinds
+    W, b, dW, db are read on both sides of it and must be the same words."""
     by_pos = {s.pos: d for s, d in zip(steps, data)}
     W0, b0 = pkg.glorot_net(cfg.ls, seed=5 + cfg.index, beta=0.5)
     fresh = SM.fresh_state()
@@ -302,7 +302,7 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
                 compare("state_vs_replay", outs[i], execute(pkg, R, cfg, cor, s, d), ("checkpoint", s.pos))
                 count["checkpoints"] += 1
                 continue
-            if not kinds[s.kind].training or is_idle(s):
+            if not SM.KINDS[s.kind].training or is_idle(s):
                 continue
             as_kind = SM.REPLAY_AS.get(s.kind, s.kind)         # (profile_step: the plain loop in its place)
             if as_kind == "train_resident" and s.before["maker"] != r_maker:
@@ -323,7 +323,7 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
             if s.status != SM.BP_OK:
                 expect_error(pkg, S2, cfg, cor, s, d, names(s))
                 continue
-            k = kinds[s.kind]
+            k = SM.KINDS[s.kind]
             if not k.training and s.kind not in SM.NO_FRESH:
                 if cache is None:
                     cache = S2.get_weights()
@@ -352,4 +352,27 @@ def run_walk(pkg, cfg, steps, data, cor, cap=SM.CAP, error_names=None, idle=None
         for g in (S, R, S2):
             g.close()
     return count, diff, bad
+
+
+def walk_test(pkg, parity_record, fam, cid, wid):
+    """The body of a GPU test: walk `wid` of family `fam` on configuration `cid`, modelled, made, run and recorded.  A call of
+    CAP + 1 rows must name the capacity; the calls that train nothing and the refusals must be the model's.  Where calls have no
+    size nothing can be idle, and the record of such a family holds neither counter."""
+    t0 = time.perf_counter()
+    cfg = SM.BY_ID[cid]
+    walk, calls = SM.walk_calls(fam, cfg, wid)
+    steps = SM.run_model(fam, cfg, calls)
+    data = [SM.call_data(fam, cfg, walk, s.pos, s.kind, s.size) for s in steps]
+    count, diff, bad = run_walk(pkg, cfg, steps, data, SM.corpus(fam, cfg), cap=fam.cap,
+                                error_names=lambda s: "capacity" if s.size == "OVER" else None, idle=lambda s: SM.idle(fam, cfg, s))
+    assert count["idle_trainings"] == sum(1 for s in steps if SM.idle(fam, cfg, s))
+    assert count["expected_errors"] == sum(1 for s in steps if s.status != SM.BP_OK) >= sum(1 for s in steps if s.size == "OVER")
+    if not fam.sizes:
+        assert count.pop("idle_trainings") == 0 and diff.pop("idle_training") == 0
+    record = dict(count, config=cid, walk=wid, words_differing=sum(diff.values()), **diff)
+    if fam.timed:
+        record["seconds"] = round(time.perf_counter() - t0, 2)
+    parity_record(**record)
+    print(cid, wid, record)
+    assert not bad and sum(diff.values()) == 0, (cid, wid, diff, bad[:20])
 
