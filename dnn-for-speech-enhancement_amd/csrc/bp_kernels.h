@@ -387,6 +387,23 @@ struct GemmCfg {
     static constexpr int NK = BK / KS / 2;
     static constexpr int step_row(int ks, int s) { return ks * (BK / KS) + 2 * s; }
     static constexpr int step_chain(int s) { return s % NCH; }
+    // Where a k-tile's LDS traffic sits among its NK MFMA steps (tests/cpp/kloop_barrier_driver.cc holds these to the invariants
+    // GemmCfg::step argues from): fragment reads run RD steps ahead of their MFMA, so the read for step s + RD is issued behind
+    // MFMA s and the last one behind MFMA LAST_READ; the tile's one barrier sits behind MFMA BAR; the NP = NVA + NVB pieces that
+    // stage the NEXT tile are written behind MFMA store_slot(q), all of them at or in front of BAR; the global loads stay spread
+    // over the whole tile.  In the forwards (A [m][k], B [k][n]) BAR is one MFMA step in front of the tile's end: that MFMA
+    // covers the first reads of the next tile.  Every other configuration keeps the barrier behind the tile's last MFMA, as do
+    // tiles too short to have a step between their last read and their last MFMA: in the dgrads an earlier barrier let the
+    // eight workgroups that stream one weight panel drift apart and the launch end later, and the weight gradients' k-loops
+    // were longer with it (profiles/r19_kloop_barrier.txt, which also has the positions further forward: all slower).
+    static constexpr bool EARLY_BAR = A_KC && !B_KC;
+    static constexpr int NP = NVA + NVB;
+    static constexpr int RD = NK < 4 ? NK : 4;
+    static constexpr int LAST_READ = NK - RD - 1;                          // (-1: every read belongs to the first RD)
+    static constexpr int BAR = (EARLY_BAR && NK > RD + 2) ? NK - 2 : NK - 1;
+    static constexpr int store_slot(int q) { return (q * (BAR + 1)) / NP; }
+    static constexpr int load_slot(int q) { return (q * NK) / NP; }
+    static_assert(BAR > LAST_READ && BAR <= NK - 1, "the barrier's wait covers every fragment read of the tile, none of them young");
 
     // Addressing: uniform tile base (SGPR pair) + per-thread unsigned 32-bit BYTE offset that never changes: a load is one
     // instruction (global_load_dwordx4 v, v_off, s[base:base+1]) and the k-advance is scalar arithmetic.  Two things are needed
@@ -500,15 +517,48 @@ struct GemmCfg {
     // k-range `ks`); between the MFMAs (a) fetch the operand fragments RD steps ahead, (b) issue
     // the global loads of a later k-tile into register image rl, (c) move the NEXT k-tile
     // (register image rs) into the other LDS stage.  Everything except the first RD fragment
-    // reads issues while the matrix pipe is busy.  NCH independent accumulator chains
+    // reads issues while the matrix pipe is busy, and those are not the step's own: they arrive in `f`, read by the step of
+    // the tile before (by the head of GemmKernel::run for the first tile).  NCH independent accumulator chains
     // (a single dependent v_mfma_f32_32x32x2_f32 chain only reaches 90 % of the issue rate).
+    //
+    // A step that stages the next tile (DO_STORE) contains the k-tile's barrier, behind MFMA step BAR (in the forwards in front
+    // of the tile's last MFMA, which then covers what follows), and behind it reads the first RD fragments of the NEXT tile from
+    // the other stage into `f`.  Why the two stages suffice wherever BAR stands, with t the tile this step multiplies, in
+    // stage t&1:
+    //  - every fragment read of tile t is issued by step LAST_READ < BAR and completed by the lgkmcnt(0) in front of the
+    //    barrier, so no wave still reads stage t&1 when a wave that has passed the barrier starts the next step and its
+    //    ds_writes of tile t+2 overwrite it;
+    //  - every ds_write of tile t+1 sits in a slot <= BAR (store_slot) and is completed by the same wait, so behind the
+    //    barrier tile t+1 is whole and visible in stage (t+1)&1: the reads into `f` are reads behind the barrier that
+    //    publishes their tile, and that stage is next written behind barrier t+1;
+    //  - the MFMAs behind the barrier use registers only.
+    // Both waits are the barrier's own: __syncthreads() is a workgroup-scope release fence, s_barrier, and an acquire fence, and
+    // for LDS the release is the s_waitcnt lgkmcnt(0) in front of s_barrier, which retires this wave's ds_reads and ds_writes
+    // alike; the acquire keeps the reads into `f` behind it.  A bare __builtin_amdgcn_s_barrier() here would promise neither.
+    // With BAR = NK - 1 the order of the LDS instructions is the one the loop had when every step read its own first fragments;
+    // what the hand-over changes there is that the reads sit in the block of the barrier, so hipcc places the scalar k-advance of
+    // the next loads (ten SALU instructions) behind them, in the shadow of the LDS round trip, and no longer between the last
+    // MFMA and the barrier, where every wave paid it before it arrived (-2 us per C2 step, profiles/r19_kloop_barrier.txt).
+    // The last tile's step (no DO_STORE) has no barrier and leaves `f` alone.
+    struct Frags { float a[RD][TM], b[RD][TN]; };
+    static __device__ __forceinline__ void read_first(Frags &f, const float *As, const float *Bs, int ks, int a_off, int b_off, int kh)
+    {
+        const float *ap = As + (step_row(ks, 0) + kh) * LDA_S + a_off;
+        const float *bp = Bs + (step_row(ks, 0) + kh) * LDB_S + b_off;
+#pragma unroll
+        for (int s = 0; s < RD; ++s) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) f.a[s][i] = ap[step_row(0, s) * LDA_S + i * 32];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) f.b[s][j] = bp[step_row(0, s) * LDB_S + j * 32];
+        }
+    }
     template <bool DO_STORE, bool DO_LOAD>
     static __device__ __forceinline__ void step(const float *As, const float *Bs, f32x16 (&acc)[NCH][TM][TN], int ks,
                                                 int a_off, int b_off, int kh, const Regs &rs, float *AsN, float *BsN,
                                                 Regs &rl, const float *pa, const float *pb, Offs &o, int tid,
-                                                float4 &bsum, int krows)
+                                                float4 &bsum, int krows, Frags &f)
     {
-        constexpr int NP = NVA + NVB, RD = NK < 4 ? NK : 4;
         const float *ap = As + (step_row(ks, 0) + kh) * LDA_S + a_off;        // step s reads rows step_row(ks, s) + kh
         const float *bp = Bs + (step_row(ks, 0) + kh) * LDB_S + b_off;
         float av[NK][TM], bv[NK][TN];
@@ -519,11 +569,10 @@ struct GemmCfg {
 #pragma unroll
         for (int s = 0; s < RD; ++s) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) av[s][i] = ap[step_row(0, s) * LDA_S + i * 32];
+            for (int i = 0; i < TM; ++i) av[s][i] = f.a[s][i];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) bv[s][j] = bp[step_row(0, s) * LDB_S + j * 32];
+            for (int j = 0; j < TN; ++j) bv[s][j] = f.b[s][j];
         }
-        __builtin_amdgcn_sched_barrier(0);
         int pl = 0, ps = 0;
 #pragma unroll
         for (int s = 0; s < NK; ++s) {
@@ -532,6 +581,7 @@ struct GemmCfg {
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
                     acc[step_chain(s)][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][i], bv[s][j], acc[step_chain(s)][i][j], 0, 0, 0);
+            if (s == 0) __builtin_amdgcn_sched_barrier(0);     // (the tile's first MFMA goes in front of its first reads and loads)
             if (s + RD < NK) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) av[s + RD][i] = ap[step_row(0, s + RD) * LDA_S + i * 32];
@@ -540,8 +590,8 @@ struct GemmCfg {
             }
             if constexpr (DO_LOAD) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) {               // load piece q goes after MFMA step q*NK/NP (spread evenly over the k-tile)
-                    if (q == pl && (q * NK) / NP == s) {
+                for (int q = 0; q < NP; ++q) {               // load piece q goes after MFMA step load_slot(q) (spread evenly over the k-tile)
+                    if (q == pl && load_slot(q) == s) {
                         if (q < NVA) load_a(rl, q, pa, o); else load_b(rl, q - NVA, pb, o);
                         ++pl;
                     }
@@ -549,11 +599,16 @@ struct GemmCfg {
             }
             if constexpr (DO_STORE) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) {               // store piece q: same slots
-                    if (q == ps && (q * NK) / NP == s) {
+                for (int q = 0; q < NP; ++q) {               // store piece q goes after MFMA step store_slot(q) (spread over [0, BAR])
+                    if (q == ps && store_slot(q) == s) {
                         if (q < NVA) store_a(rs, q, AsN, tid, krows); else store_b(rs, q - NVA, BsN, tid, bsum);
                         ++ps;
                     }
+                }
+                if (s == BAR) {
+                    __syncthreads();
+                    __builtin_amdgcn_sched_barrier(0);
+                    read_first(f, AsN, BsN, ks, a_off, b_off, kh);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -673,7 +728,10 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     // and the first use of any of them there -- hipcc spills one into a VGPR lane -- is a second full scalar wait in front of the
     // first operand load.  WHEN THE COMPILER CHANGES, rerun the listing check of profiles/r15_gemm_head.txt section 1 and look for
     // copies of r1 in front of the k-loop (profiles/r16_gemm_tail.txt section 2), and for VALU instructions in the steady-state
-    // loop (profiles/r17_kloop_pairs.txt section 1: there are none, every operand load is global_load_dwordx4 v, v_off, s[base]):
+    // loop (profiles/r17_kloop_pairs.txt section 1: there are none, every operand load is global_load_dwordx4 v, v_off, s[base]),
+    // and for the shape of a k-tile around its barrier (profiles/r19_kloop_barrier.txt section 4: one s_barrier per tile, the
+    // first reads of the next tile and the scalar k-advance right behind it, nothing but an s_waitcnt lgkmcnt in front of the
+    // next tile's first MFMA):
     // this asm, BP_PIN_OPERANDS, the asm in bp_gemm_multi, the one in GemmCfg::lane_off and the branch weight on the k-loop steer
     // hipcc by side effects it does not promise, and no test on a machine without a GPU holds the instruction and wait counts in
     // front of the first global_load_dwordx4 or the first MFMA, or the instruction mix of the loop.
@@ -717,18 +775,22 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
         }
     }
 
-    // ---- software pipeline: LDS holds tile t (double buffered), the register images r0 / r1 tiles t+1 and t+2.  One barrier per k-tile.
+    // ---- software pipeline: LDS holds tile t (double buffered), the register images r0 / r1 tiles t+1 and t+2.  One barrier per k-tile,
+    // inside the step that stages the next tile (GemmCfg::step), which also reads that tile's first fragments behind it.
 // multiply stage `buf`; ST: store image RS (k-tile TS) into the other stage; LD: load tile TL into image RL
 #define STEP(ST, LD, buf, RS, TS, RL, TL)                                                                  \
     Cfg::template step<ST, LD>(AS(buf), BS(buf), accs, ks, a_off, b_off, kh, RS, AS((buf) ^ 1), BS((buf) ^ 1),    \
-                               RL, PA(TL), PB(TL), offs, tid, bsum, g.K - (TS) * BK)
+                               RL, PA(TL), PB(TL), offs, tid, bsum, g.K - (TS) * BK, frags)
     Cfg::store(r0, AS(0), BS(0), tid, bsum, g.K);
     __syncthreads();
     TRACE(1);
+    typename Cfg::Frags frags;                    // the first fragments of the tile the next STEP multiplies
+    Cfg::read_first(frags, AS(0), BS(0), ks, a_off, b_off, kh);
     // Invariant at the top of iteration t: LDS stage t&1 holds tile t; tile t+1 is in flight / landed in registers
     // (r1 for even t, r0 for odd t).  The iteration multiplies tile t and, between the MFMAs, issues the global loads of tile
-    // t+2 and moves tile t+1 into the other stage.  The steady-state loop contains no conditionals (a conditional step makes
-    // hipcc copy the accumulators between register ranges every iteration); the last one or two tiles run after.
+    // t+2, moves tile t+1 into the other stage and, behind its barrier, reads the first fragments of tile t+1.  The steady-state
+    // loop contains no conditionals (a conditional step makes hipcc copy the accumulators between register ranges every
+    // iteration); the last one or two tiles run after.
     // The loop is marked as the expected path (every layer of a real net has three or more k-tiles).  Without the mark hipcc
     // keeps the image r1 that the head loaded in other registers than the loop's r1 and copies it over in front of the loop,
     // behind a full vmcnt(0): the first MFMA then waits for all of k-tile 1 (profiles/r16_gemm_tail.txt section 2).
@@ -740,17 +802,14 @@ static __device__ __forceinline__ void run(const GemmArgs &g_in, const EpiArgs &
     if (__builtin_expect(nt >= 3, 1))
     for (; t + 3 <= nt; t += 2) {
         STEP(true, true, 0, r1, t + 1, r0, t + 2);
-        __syncthreads();
         STEP(true, true, 1, r0, t + 2, r1, t + 3);
-        __syncthreads();
     }
     if (nt - t == 2) {
         STEP(true, false, 0, r1, t + 1, r0, 0);
-        __syncthreads();
         buf = 1;
     }
-    STEP(false, false, buf, r0, 0, r0, 0);    // last tile: nothing left to stage or fetch
-    __syncthreads();
+    STEP(false, false, buf, r0, 0, r0, 0);    // last tile: nothing left to stage or fetch, no barrier in it
+    __syncthreads();                          // (every wave is past its reads of the stages: the exchange areas below reuse them)
     TRACE(2);
 #undef STEP
     // Every load issued so far has landed or is dead (the clamped image behind the last k-tile).  Said once, here: the epilogue's
