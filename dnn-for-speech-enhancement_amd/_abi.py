@@ -13,6 +13,7 @@ __all__ = [
     "GV_RAW", "GV_POST", "GV_STAGES", "GV_INDEP", "GV_DEP", "GV_MODES",
     "MIX_LPS", "MIX_IRM", "MIX_IBM", "MIX_LPS_IRM", "MIX_LPS_IBM", "MIX_TARGETS", "MIXTURE_DTYPE",
     "SCORE_SSNR", "SCORE_LSD", "SCORE_STOI", "SCORE_ESTOI", "SCORE_SISDR", "SCORE_LLR", "SCORE_CD", "SCORE_FULL_N",
+    "SCORE_FWSSNR", "SCORE_WSS", "SCORE_ALL_N",
     "REVERB_TARGET_REVERBERANT", "REVERB_TARGET_EARLY", "REVERB_TARGETS", "MIX_RIR_MAX_TAPS",
     "RIR_MAX_IMAGES", "RIR_ROOM_DTYPE", "RIR_RANGE_DEFAULTS", "NOISE_VAD", "NOISE_SPP", "PROF_KINDS",
     "BPConfig", "BPWindowChunk", "BPWaveChunk", "BPMixCorpus", "BPMixReverb", "BPRirRange", "BPStreamConfig",
@@ -38,6 +39,7 @@ MIX_LPS, MIX_IRM, MIX_IBM, MIX_LPS_IRM, MIX_LPS_IBM = 0, 1, 2, 3, 4   # bp_mix_c
 SCORE_SSNR, SCORE_LSD, SCORE_STOI = 0, 1, 2   # columns of bp_score_waves / bp_eval_mix scores
 SCORE_ESTOI, SCORE_SISDR = 3, 4               # the two further columns of the _ext calls (extended=True)
 SCORE_LLR, SCORE_CD, SCORE_FULL_N = 5, 6, 7   # the two behind those (extended="full") and the width of such a row
+SCORE_FWSSNR, SCORE_WSS, SCORE_ALL_N = 7, 8, 9   # fwSegSNR and WSS behind those (extended="all") and the width of such a row
 REVERB_TARGET_REVERBERANT, REVERB_TARGET_EARLY = 0, 1   # bp_mix_reverb.target
 REVERB_TARGETS = {"reverberant": REVERB_TARGET_REVERBERANT, "early": REVERB_TARGET_EARLY}
 MIX_RIR_MAX_TAPS = 65536
@@ -287,12 +289,14 @@ def check(lib, rc):
 
 
 def score_columns(who, extended):
-    """n_scores of an _ext call for a wrapper's extended=: False 3, True 5, "full" 7; anything else is a BPError of `who`."""
+    """n_scores of an _ext call for a wrapper's extended=: False 3, True 5, "full" 7, "all" 9; anything else is a BPError of `who`."""
     if isinstance(extended, (bool, np.bool_)):
         return 5 if extended else 3
     if isinstance(extended, str) and extended == "full":
         return SCORE_FULL_N
-    raise BPError("%s: extended must be False, True or \"full\", not %r" % (who, extended))
+    if isinstance(extended, str) and extended == "all":
+        return SCORE_ALL_N
+    raise BPError("%s: extended must be False, True or \"full\", or \"all\" for the nine columns, not %r" % (who, extended))
 
 
 _PTR = {np.dtype(np.float32): fp, np.dtype(np.int32): ip, np.dtype(np.float64): dp, np.dtype(np.int64): lp,

@@ -428,8 +428,8 @@ class BP_GPU(Closing):
         """bp_eval_mix: the plan's mixtures made on the device, enhanced with this net and scored against their clean sentences.
         dict of noisy [n_mix][3] and enhanced [n_mix][3] float32 scores (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where
         undefined) and pcm: the enhanced sentences (a list) with return_pcm, else None.  extended: bp_eval_mix_ext with five
-        columns, SCORE_ESTOI and SCORE_SISDR behind the same three; extended="full": seven, SCORE_LLR and SCORE_CD behind those
-        (any other value: BPError)."""
+        columns, SCORE_ESTOI and SCORE_SISDR behind the same three; extended="full": seven, SCORE_LLR and SCORE_CD behind those;
+        extended="all": nine, SCORE_FWSSNR and SCORE_WSS behind those (any other value: BPError)."""
         ns = score_columns("eval_mix", extended)
         p, pp = self._plan(plan)
         self._push_hyper()
@@ -441,7 +441,7 @@ class BP_GPU(Closing):
     def eval_mix_logmmse(self, plan, sample_rate, params=None, return_pcm=False, extended=False, noise=None):
         """bp_eval_mix_logmmse: eval_mix with the log-MMSE baseline in place of the net (params: None for the defaults, a dict of
         bp_logmmse_params fields over them, or a BPLogmmseParams).  The same dictionary as eval_mix (extended: five columns, "full":
-        seven, bp_eval_mix_logmmse_ext).  noise: as for logmmse_waves (anything but None: bp_eval_mix_logmmse_nt)."""
+        seven, "all": nine, bp_eval_mix_logmmse_ext).  noise: as for logmmse_waves (anything but None: bp_eval_mix_logmmse_nt)."""
         ns = score_columns("eval_mix_logmmse", extended)
         p, pp = self._plan(plan)
         lm = logmmse_params(params)

@@ -18,8 +18,9 @@ constexpr int EVAL_MAXSIG = 3;
 // Host plan of one call: the per-sentence tables (prefix sums [n + 1] unless noted) and where they lie in the table block.
 struct EvalPlan {
     int n, fs, p, q, Lh, taps, win, skip, D;      // rate p/q = 10000/fs in lowest terms; SSNR frame / skip; fea_dim
-    int ns;                                       // score columns per row: BP_SCORE_N, BP_SCORE_EXT_N (ESTOI and SI-SDR are computed) or
-                                                  // BP_SCORE_FULL_N (LLR and CD as well: per-frame values in the work block)
+    int ns;                                       // score columns per row: BP_SCORE_N, BP_SCORE_EXT_N (ESTOI and SI-SDR are computed),
+                                                  // BP_SCORE_FULL_N (LLR and CD as well: per-frame values in the work block) or
+                                                  // BP_SCORE_ALL_N (fwSegSNR and WSS as well: their tables and per-frame values)
     std::vector<int64_t> off;                     // [n] first sample of each sentence
     std::vector<int> len;                         // [n]
     std::vector<int> o10, rb;                     // 10 kHz samples; resampler workgroups
@@ -29,14 +30,19 @@ struct EvalPlan {
     std::vector<int> F, FS;                       // analysis frames (1d); padded segments F[s] + s
     std::vector<float> h, v;                      // resampler taps [taps]; STOI window [512] (second half zero)
     std::vector<double> w;                        // SSNR window [win]
+    int cH;                                       // nine columns: n_fft / 2 of fwSegSNR / WSS (else 0, and the two tables empty)
+    std::vector<int> cb_band;                     // [3][25] first bin, bins, offset into cb_g of the 25 band filters' supports
+    std::vector<double> cb_g;                     // their weights
     size_t t_bytes;                               // table block
 };
 // The rate rule: 10000/fs = p/q in lowest terms, max(p, q) <= 32.
 bool eval_rate(int fs, int *p, int *q);
-// BP_OK for BP_SCORE_N, BP_SCORE_EXT_N and BP_SCORE_FULL_N, else BP_ERR_ARG: the first check of every _ext call.
+// BP_OK for BP_SCORE_N, BP_SCORE_EXT_N, BP_SCORE_FULL_N and BP_SCORE_ALL_N, else BP_ERR_ARG: the first check of every _ext call.
 int eval_n_scores(const char *who, int n_scores);
+// With BP_SCORE_ALL_N: BP_ERR_ARG unless fs >= 8000 (all 25 bands below Nyquist) and win <= 4096 (n_fft <= 8192).  eval_plan checks it.
+int eval_cb_rate(const char *who, int fs, int n_scores);
 // Checks the rate and sizes (BP_ERR_ARG, nothing touched) and builds the plan; F: [n + 1] analysis frame prefix of the call;
-// n_scores: BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N (the caller has checked it).
+// n_scores: BP_SCORE_N, BP_SCORE_EXT_N, BP_SCORE_FULL_N or BP_SCORE_ALL_N (the caller has checked it).
 int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep);
 void eval_fill(const EvalPlan &ep, char *tab);    // the table block, t_bytes
 size_t eval_work_bytes(const EvalPlan &ep, int nsig);
@@ -48,7 +54,8 @@ struct EvalDev {
 };
 // The whole scoring sequence on st: the reference side once, the estimates' sides, the per-sentence reductions.  With five
 // columns bp_eval_estoi and bp_eval_sisdr run before the reductions; with three nothing else changes.  With seven the LLR / CD
-// kernels (bp_eval_lpc, bp_eval_lpcrank, bp_eval_lpcsum) run behind the five-column sequence and write columns 5 and 6 alone.
+// kernels (bp_eval_lpc, bp_eval_lpcrank, bp_eval_lpcsum) run behind the five-column sequence and write columns 5 and 6 alone; with
+// nine bp_eval_cb, bp_eval_lpcrank (on the WSS values) and bp_eval_cbsum run behind those and write columns 7 and 8 alone.
 hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream_t st);
 // Zero every sample of the padded layout outside [off[s], off[s] + len[s]) of its sentence (hop-sample segments).
 hipError_t eval_trim_launch(const EvalPlan &ep, const char *tab, int hop, float *pcm, hipStream_t st);

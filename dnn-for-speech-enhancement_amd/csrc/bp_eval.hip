@@ -1,7 +1,7 @@
 // bp_eval.hip -- C-ABI implementation (include/bp_c_api.h): objective scores of enhanced speech.  Segmental SNR,
 // log-spectral distortion on the 1d analysis and STOI of estimates against a reference, and with five score columns ESTOI and
-// SI-SDR beside them, with seven LLR and cepstral distance as well (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip
-// through bp_eval.h).  Definitions:
+// SI-SDR beside them, with seven LLR and cepstral distance as well, with nine the frequency-weighted segmental SNR and the weighted
+// spectral slope distance behind those (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions:
 // include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame plan and padded layout from bp_wave.hip
 // (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
 //
@@ -28,6 +28,15 @@
 //                     frames in either measure (integer counts; the sentence's values pass through LDS in tiles), selected iff rank < Jk
 //   bp_eval_lpcsum    seven columns only, one workgroup per (sentence, estimate): the selected values summed (strided sums, a
 //                     fixed LDS tree), divided by Jk: columns 5 and 6
+//   bp_eval_cb        nine columns only, one workgroup per 16 SSNR frames of the call: per (signal, frame), 1 to 4 of them at a time
+//                     (64 to 256 threads each, by n_fft), the windowed frame, zero-padded to n_fft, as a complex FFT of n_fft / 2
+//                     points in LDS in double (twiddles from a host double table) and the split step, |X| and |X|^2 in place; sum |X|
+//                     (strided sums, a fixed shuffle tree) and the 25 sparse band sums of both kinds (2 to 8 lanes per band, a fixed
+//                     shuffle tree) into LDS as [signal][band][frame], the reference's once; then 32 lanes per (estimate, frame), one per
+//                     band, do the 25-band part (a fixed shuffle tree over the bands): fwSegSNR_j, WSS_j and their validity
+//   bp_eval_cbsum     nine columns only, one workgroup per (sentence, estimate): the valid fwSegSNR values and the WSS values that
+//                     bp_eval_lpcrank selected (run a second time, on the WSS values) summed (strided sums, a fixed LDS tree):
+//                     columns 7 and 8
 //   bp_eval_trim      per padded sample: zero outside the sentence (the overlap-add output, before it is analysed)
 // No float atomics and no cross-workgroup hand-off inside a kernel: the same bits on every run.
 #include <hip/hip_runtime.h>
@@ -64,6 +73,9 @@ struct EvalArgs {
     double *rho, *ssnr, *lsd; size_t srho, sssnr, slsd;      // [est][CP[n]], [est][SJ[n]], [est][F[n]]
     double *dm, *sdr; size_t sdm; int nsig;                  // five columns: [est][CP[n] / 15], [est][n]
     double *llr, *lcd; int *lv, *lsel;                       // seven columns: [est][SJ[n]] each (lv: valid; lsel: bit 0 LLR, bit 1 CD selected)
+    // nine columns: twiddles exp(-2 pi i j / n_fft) [cH + 1]; per band first bin, bins, offset into cg [3][25]; the weights; n_fft / 2
+    const double2 *ctw; const int *cband; const double *cg; int cH;
+    double *fw, *ws; int *fv, *wv, *csel;                    // [est][SJ[n]] each (fv, wv: valid; csel: bits 0 and 1 WSS selected)
     float *scores; int ns;                                   // [est][n][ns]
 };
 
@@ -559,6 +571,192 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcsum(const EvalArgs a)
     }
 }
 
+// ---- fwSegSNR and WSS (nine columns).  Frame block of bp_eval_cb: EV_CF consecutive frames of the call (global index g over
+// SJ[n]; a block may span sentences).  The workgroup transforms G = 256 / T (signal, frame) items at a time, T = cb_threads(H)
+// threads each: a thread has at least two butterflies per stage, and at 80 kHz, where the points of one item are 68 KB, the
+// whole workgroup takes one item.  LDS, in doubles: per item in flight its H = n_fft / 2 complex points (one point of padding
+// after every 16: a point is 16 bytes, 16 of them fill the 64 banks once), then bs[signal][band][frame] = (c or d, B or C) and
+// ok[signal][frame].
+constexpr int EV_CBN = 25, EV_CF = 16;
+__device__ __forceinline__ int lpd(int i) { return i + (i >> 4); }
+__host__ __device__ constexpr int cb_threads(int H) { return H / 4 < 64 ? 64 : H / 4 > WAVE_THREADS ? WAVE_THREADS : H / 4; }
+__host__ __device__ constexpr size_t cb_z_doubles(int H) { return 2 * (size_t)(H + H / 16 + 1); }
+__host__ __device__ constexpr size_t cb_lds_bytes(int H, int nsig)
+{
+    return ((size_t)(WAVE_THREADS / cb_threads(H)) * cb_z_doubles(H) + (size_t)nsig * EV_CBN * EV_CF * 2) * 8 + (size_t)nsig * EV_CF * 4;
+}
+
+// the nearest peak of band i in the dB band energies B[0], B[st], .. B[24 st] (the search of the header, step for step)
+__device__ __forceinline__ double cb_peak(const double *B, int st, int i)
+{
+    int n = i;
+    if (B[(i + 1) * st] - B[i * st] > 0.0) {
+        while (n < EV_CBN - 1 && B[(n + 1) * st] - B[n * st] > 0.0) ++n;
+        return B[(n - 1) * st];
+    }
+    while (n >= 0 && B[(n + 1) * st] - B[n * st] <= 0.0) --n;
+    return B[(n + 1) * st];
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_cb(const EvalArgs a)
+{
+    extern __shared__ __align__(16) double cb_lds[];
+    __shared__ int64_t first[EV_CF];
+    __shared__ double part[WAVE_THREADS / 64];
+    __shared__ int wnz[WAVE_THREADS / 64];
+    const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6, g0 = blockIdx.x * EV_CF, total = a.SJ[a.n], H = a.cH;
+    const int nf = total - g0 < EV_CF ? total - g0 : EV_CF;         // frames of this block (>= 1: the grid is sized by total)
+    const int T = cb_threads(H), G = WAVE_THREADS / T, slot = tid / T, lt = tid % T, wps = T / 64, L = T / 32;
+    int log2H = 0;
+    while ((1 << log2H) < H) ++log2H;
+    if (tid < nf) {
+        const int g = g0 + tid, s = sentence_of(a.SJ, a.n, g);
+        first[tid] = a.off[s] + (int64_t)(g - a.SJ[s]) * a.skip;
+    }
+    double2 *z = reinterpret_cast<double2 *>(cb_lds) + (size_t)slot * (cb_z_doubles(H) / 2);
+    double2 *bs = reinterpret_cast<double2 *>(cb_lds + (size_t)G * cb_z_doubles(H));
+    int *ok = reinterpret_cast<int *>(bs + (size_t)a.nsig * EV_CBN * EV_CF);
+    __syncthreads();
+    // 1. the items t = (signal t / nf, frame t % nf), G per round, item t0 + slot by the T threads of its slot (every barrier is
+    // met by the whole workgroup; what a slot does between them depends on its own item alone)
+    for (int t0 = 0; t0 < a.nsig * nf; t0 += G) {
+        const int t = t0 + slot, k = t / nf, f = t % nf;
+        const bool item = t < a.nsig * nf;
+        // the windowed frame as H complex points z[m] = (xw[2m], xw[2m+1]), zeros from win on, at bit-reversed places.  Valid iff
+        // sum (w x)^2 > 0: w > 0 throughout and no such product or square underflows, so iff any sample is not zero
+        int nz = 0;
+        if (item) {
+            const float *__restrict__ x = a.sig[k] + first[f];
+            for (int m = lt; m < H; m += T) {
+                double re = 0.0, im = 0.0;
+                if (2 * m < a.win) { const float v = x[2 * m]; nz |= v != 0.0f; re = a.w[2 * m] * (double)v; }
+                if (2 * m + 1 < a.win) { const float v = x[2 * m + 1]; nz |= v != 0.0f; im = a.w[2 * m + 1] * (double)v; }
+                z[lpd((int)(__brev((unsigned)m) >> (32 - log2H)))] = make_double2(re, im);
+            }
+        }
+        nz = __any(nz);
+        if (ln == 0) wnz[wv] = nz;
+        __syncthreads();
+        bool live = false;
+        for (int u = 0; u < wps; ++u) live |= wnz[slot * wps + u] != 0;
+        live &= item;
+        if (item && lt == 0) ok[k * EV_CF + f] = live;
+        for (int h = 1; h < H; h <<= 1) {                            // radix-2 decimation in time, as fft_lds
+            const int tstep = H / h;
+            if (live)
+                for (int j = lt; j < H / 2; j += T) {
+                    const int jh = j & (h - 1), i0 = ((j - jh) << 1) + jh, i1 = i0 + h;
+                    const double2 w = a.ctw[jh * tstep], p = z[lpd(i0)], q = z[lpd(i1)];
+                    const double bx = q.x * w.x - q.y * w.y, by = q.x * w.y + q.y * w.x;
+                    z[lpd(i0)] = make_double2(p.x + bx, p.y + by);
+                    z[lpd(i1)] = make_double2(p.x - bx, p.y - by);
+                }
+            __syncthreads();
+        }
+        // split step in place, the pair (k2, H - k2) by one thread: X[k2] = E + W^k2 O and |X[H - k2]| = |E - W^k2 O|;
+        // z[k2] <- (|X|, |X|^2)
+        if (live)
+            for (int k2 = lt; k2 <= H / 2; k2 += T) {
+                const int m = (H - k2) & (H - 1);
+                const double2 zk = z[lpd(k2)], zm = z[lpd(m)], w = a.ctw[k2];
+                const double ex = 0.5 * (zk.x + zm.x), ey = 0.5 * (zk.y - zm.y), ox = 0.5 * (zk.y + zm.y), oy = -0.5 * (zk.x - zm.x);
+                const double tx = ox * w.x - oy * w.y, ty = ox * w.y + oy * w.x;
+                const double p0 = (ex + tx) * (ex + tx) + (ey + ty) * (ey + ty), p1 = (ex - tx) * (ex - tx) + (ey - ty) * (ey - ty);
+                z[lpd(k2)] = make_double2(sqrt(p0), p0);
+                if (m != k2) z[lpd(m)] = make_double2(sqrt(p1), p1);
+            }
+        __syncthreads();
+        double tot = 0.0;                                           // sum |X|: each thread's bins in order, a fixed tree over the threads
+        if (live)
+            for (int k2 = lt; k2 < H; k2 += T) tot += z[lpd(k2)].x;
+        tot = wave_sum(tot);
+        if (ln == 0) part[wv] = tot;
+        // the band sums: band lt / L by L = T / 32 lanes, each lane's bins in order, a fixed tree over the L
+        const int i = lt / L, sub = lt % L;
+        double sm = 0.0, sp = 0.0;
+        if (live && i < EV_CBN) {
+            const int b0 = a.cband[i], cnt = a.cband[EV_CBN + i];
+            const double *__restrict__ gw = a.cg + a.cband[2 * EV_CBN + i];
+            for (int q = sub; q < cnt; q += L) { const double2 v = z[lpd(b0 + q)]; sm += gw[q] * v.x; sp += gw[q] * v.y; }
+        }
+        for (int o = L >> 1; o > 0; o >>= 1) { sm += __shfl_xor(sm, o); sp += __shfl_xor(sp, o); }
+        __syncthreads();
+        if (live && i < EV_CBN && sub == 0) {
+            double all = part[slot * wps];                          // (the slot's waves in order)
+            for (int u = 1; u < wps; ++u) all += part[slot * wps + u];
+            bs[((size_t)k * EV_CBN + i) * EV_CF + f] = make_double2(sm / all, 10.0 * log10(fmax(sp, 1e-10)));
+        }
+        __syncthreads();                                            // (part, wnz and z are free for the next round)
+    }
+    // 2. the 25-band part: 32 lanes per (estimate, frame), lane i < 25 on band i (its power, its two logarithms and its two peak
+    // searches are where the time of this part goes), the four sums over the bands by a fixed shuffle tree over the 32
+    const int np = (a.nsig - 1) * nf, i = tid & 31;
+    for (int p0 = 0; p0 < np; p0 += WAVE_THREADS / 32) {
+        const int p = p0 + (tid >> 5), e = p / nf + 1, f = p % nf;
+        const bool pair = p < np, valid = pair && ok[f] && ok[e * EV_CF + f];
+        double fn = 0.0, fd = 0.0, wn = 0.0, wd = 0.0, bmax = -1e300, cmax = -1e300;
+        const double2 *R = bs + f, *E = bs + (size_t)e * EV_CBN * EV_CF + f;   // band i at [i EV_CF]
+        const double *B = &R[0].y, *C = &E[0].y;                    // stride 2 EV_CF doubles per band
+        constexpr int st = 2 * EV_CF;
+        const bool on = valid && i < EV_CBN;
+        if (on) {
+            const double c = R[i * EV_CF].x, d = E[i * EV_CF].x;
+            if (c > 0.0) {
+                const double df = c - d, err = fmax(df * df, EV_EPS);
+                fd = pow(c, 0.2);
+                fn = fd * (10.0 * log10(c * c / err));
+            }
+            bmax = B[i * st]; cmax = C[i * st];
+        }
+        for (int o = 16; o > 0; o >>= 1) { bmax = fmax(bmax, __shfl_xor(bmax, o)); cmax = fmax(cmax, __shfl_xor(cmax, o)); }
+        if (on && i < EV_CBN - 1) {
+            const double Bi = B[i * st], Ci = C[i * st], s = B[(i + 1) * st] - Bi, u = C[(i + 1) * st] - Ci;
+            const double wr = 20.0 / (20.0 + bmax - Bi) * (1.0 / (1.0 + cb_peak(B, st, i) - Bi));
+            const double we = 20.0 / (20.0 + cmax - Ci) * (1.0 / (1.0 + cb_peak(C, st, i) - Ci));
+            wd = (wr + we) / 2.0;
+            wn = wd * ((s - u) * (s - u));
+        }
+        for (int o = 16; o > 0; o >>= 1) {
+            fn += __shfl_xor(fn, o); fd += __shfl_xor(fd, o); wn += __shfl_xor(wn, o); wd += __shfl_xor(wd, o);
+        }
+        if (pair && i == 0) {
+            const bool fok = valid && fd > 0.0;
+            const size_t o = (size_t)(e - 1) * a.sssnr + g0 + f;
+            a.fw[o] = fok ? fmin(fmax(fn / fd, -10.0), 35.0) : 0.0; a.fv[o] = fok;
+            a.ws[o] = valid ? wn / wd : 0.0; a.wv[o] = valid;
+        }
+    }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_cbsum(const EvalArgs a)
+{
+    __shared__ double red[2][WAVE_THREADS];
+    __shared__ int cnt[2][WAVE_THREADS];
+    const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, J = a.SJ[s + 1] - a.SJ[s];
+    const size_t o = (size_t)(e - 1) * a.sssnr + a.SJ[s];
+    double q0 = 0.0, q1 = 0.0;
+    int n0 = 0, n1 = 0;
+    for (int i = tid; i < J; i += WAVE_THREADS) {
+        n0 += a.fv[o + i]; n1 += a.wv[o + i];
+        if (a.fv[o + i]) q0 += a.fw[o + i];
+        if (a.csel[o + i] & 1) q1 += a.ws[o + i];
+    }
+    red[0][tid] = q0; red[1][tid] = q1; cnt[0][tid] = n0; cnt[1][tid] = n1;
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; cnt[0][tid] += cnt[0][tid + w]; cnt[1][tid] += cnt[1][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float nan = __int_as_float(0x7fc00000);
+        float *sc = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
+        sc[BP_SCORE_FWSSNR] = cnt[0][0] > 0 ? (float)(red[0][0] / cnt[0][0]) : nan;
+        sc[BP_SCORE_WSS] = cnt[1][0] > 0 ? (float)(red[1][0] / lpc_keep(cnt[1][0])) : nan;
+    }
+}
+
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_trim(const int64_t *__restrict__ off, const int *__restrict__ len,
                                                           const int *__restrict__ FS, int n, int hop, float *__restrict__ pcm)
 {
@@ -574,7 +772,7 @@ namespace {
 
 // Where the tables lie in the table block (all offsets 256-byte aligned).
 struct TabLayout {
-    size_t off, len, pre[12], h, v, tw, w, bytes;   // pre: the prefix tables in EvalPlan order
+    size_t off, len, pre[12], h, v, tw, w, ctw, cband, cg, bytes;   // pre: the prefix tables in EvalPlan order; c*: nine columns only
 };
 TabLayout tab_layout(const EvalPlan &ep)
 {
@@ -587,6 +785,10 @@ TabLayout tab_layout(const EvalPlan &ep)
     t.v = lay.take((size_t)EV_NFFT * 4);
     t.tw = lay.take((size_t)(EV_NFFT / 2 + 1) * 8);
     t.w = lay.take((size_t)ep.win * 8);
+    const bool all = ep.ns >= BP_SCORE_ALL_N;                       // (a part of 0 bytes takes no room)
+    t.ctw = lay.take(all ? (size_t)(ep.cH + 1) * 16 : 0);
+    t.cband = lay.take(all ? (size_t)3 * EV_CBN * 4 : 0);
+    t.cg = lay.take(all ? ep.cb_g.size() * 8 : 0);
     t.bytes = lay.size();
     return t;
 }
@@ -604,7 +806,7 @@ double bessel_i0(double x)
 }
 
 // Work block layout for nsig signals.
-struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, llr, lcd, lv, lsel, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
+struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, llr, lcd, lv, lsel, fw, ws, fv, wv, csel, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
 WorkLayout work_layout(const EvalPlan &ep, int nsig)
 {
     WorkLayout w;
@@ -622,13 +824,18 @@ WorkLayout work_layout(const EvalPlan &ep, int nsig)
     w.ssnr = lay.take(ne * w.sssnr * 8);
     w.lsd = lay.take(ne * w.slsd * 8);
     w.sdm = (size_t)ep.CP[n] / EV_NB;                               // five columns only (a part of 0 bytes takes no room)
-    const bool ext = ep.ns >= BP_SCORE_EXT_N, full = ep.ns == BP_SCORE_FULL_N;
+    const bool ext = ep.ns >= BP_SCORE_EXT_N, full = ep.ns >= BP_SCORE_FULL_N, all = ep.ns >= BP_SCORE_ALL_N;
     w.dm = lay.take(ext ? ne * w.sdm * 8 : 0);
     w.sdr = lay.take(ext ? (size_t)ne * n * 8 : 0);
     w.llr = lay.take(full ? ne * w.sssnr * 8 : 0);                  // seven columns only
     w.lcd = lay.take(full ? ne * w.sssnr * 8 : 0);
     w.lv = lay.take(full ? ne * w.sssnr * 4 : 0);
     w.lsel = lay.take(full ? ne * w.sssnr * 4 : 0);
+    w.fw = lay.take(all ? ne * w.sssnr * 8 : 0);                    // nine columns only
+    w.ws = lay.take(all ? ne * w.sssnr * 8 : 0);
+    w.fv = lay.take(all ? ne * w.sssnr * 4 : 0);
+    w.wv = lay.take(all ? ne * w.sssnr * 4 : 0);
+    w.csel = lay.take(all ? ne * w.sssnr * 4 : 0);
     w.bytes = lay.size();
     return w;
 }
@@ -646,9 +853,46 @@ bool eval_rate(int fs, int *p, int *q)
 
 int eval_n_scores(const char *who, int n_scores)
 {
-    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N || n_scores == BP_SCORE_FULL_N) return BP_OK;
-    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N");
+    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N || n_scores == BP_SCORE_FULL_N || n_scores == BP_SCORE_ALL_N) return BP_OK;
+    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N, BP_SCORE_EXT_N, BP_SCORE_FULL_N or BP_SCORE_ALL_N");
 }
+
+int eval_cb_rate(const char *who, int fs, int n_scores)
+{
+    if (n_scores < BP_SCORE_ALL_N) return BP_OK;
+    if (fs < 8000) return fail(BP_ERR_ARG, std::string(who) + ": sample_rate must be at least 8000 with BP_SCORE_ALL_N (the 25 bands reach 3.8 kHz)");
+    if ((int)floor(0.03 * fs + 0.5) > 4096)
+        return fail(BP_ERR_ARG, std::string(who) + ": sample_rate gives a frame of more than 4096 samples: too long for BP_SCORE_ALL_N (n_fft <= 8192)");
+    return BP_OK;
+}
+
+namespace {
+
+// The 25 critical bands of fwSegSNR and WSS (include/bp_c_api.h): centre frequencies and bandwidths in Hz
+const double cb_cf[EV_CBN] = {50.0, 120.0, 190.0, 260.0, 330.0, 400.0, 470.0, 540.0, 617.372, 703.378, 798.717, 904.128, 1020.38,
+                              1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63};
+const double cb_bw[EV_CBN] = {70.0, 70.0, 70.0, 70.0, 70.0, 70.0, 70.0, 77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914,
+                              140.423, 153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136};
+
+// the supports of the 25 Gaussian filters on the bins 0 .. H - 1: first bin, bins, and the weights back to back
+void cb_table(int fs, int H, std::vector<int> &band, std::vector<double> &g)
+{
+    band.assign((size_t)3 * EV_CBN, 0); g.clear();
+    const double cut = exp(-30.0 / (2.0 * 2.303));
+    for (int i = 0; i < EV_CBN; ++i) {
+        const double f0 = floor(cb_cf[i] / (fs / 2.0) * H), b = cb_bw[i] / (fs / 2.0) * H;
+        int lo = -1, cnt = 0;
+        for (int k = 0; k < H; ++k) {
+            const double u = (k - f0) / b, v = exp(-11.0 * (u * u));
+            if (!(v > cut)) { if (cnt) break; continue; }            // (a Gaussian: its support is one run of bins)
+            if (!cnt) lo = k;
+            ++cnt; g.push_back(v);
+        }
+        band[i] = lo < 0 ? 0 : lo; band[EV_CBN + i] = cnt; band[2 * EV_CBN + i] = (int)g.size() - cnt;
+    }
+}
+
+}  // namespace
 
 int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const int *len, const int64_t *off, const int *F, EvalPlan &ep)
 {
@@ -661,6 +905,12 @@ int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const i
     ep.taps = 2 * ep.Lh + 1;
     ep.win = (int)floor(0.03 * fs + 0.5);
     ep.skip = ep.win / 4;
+    { const int r = eval_cb_rate(who, fs, n_scores); if (r != BP_OK) return r; }
+    ep.cH = 0; ep.cb_band.clear(); ep.cb_g.clear();
+    if (n_scores >= BP_SCORE_ALL_N) {                                // n_fft = 2^ceil(log2(2 win)), H = n_fft / 2: the least power of two >= win
+        for (ep.cH = 1; ep.cH < ep.win; ep.cH <<= 1) {}
+        cb_table(fs, ep.cH, ep.cb_band, ep.cb_g);
+    }
     ep.off.assign(off, off + n); ep.len.assign(len, len + n);
     for (std::vector<int> *v : {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS})
         v->assign((size_t)n + 1, 0);
@@ -716,6 +966,12 @@ void eval_fill(const EvalPlan &ep, char *tab)
     float2 *tw = (float2 *)(tab + t.tw);
     for (int k = 0; k <= EV_NFFT / 2; ++k) tw[k] = make_float2((float)cos(pi2 * k / EV_NFFT), (float)-sin(pi2 * k / EV_NFFT));
     memcpy(tab + t.w, ep.w.data(), ep.w.size() * 8);
+    if (ep.ns >= BP_SCORE_ALL_N) {
+        double *ctw = (double *)(tab + t.ctw);
+        for (int k = 0; k <= ep.cH; ++k) { ctw[2 * k] = cos(pi2 * k / (2.0 * ep.cH)); ctw[2 * k + 1] = -sin(pi2 * k / (2.0 * ep.cH)); }
+        memcpy(tab + t.cband, ep.cb_band.data(), ep.cb_band.size() * 4);
+        memcpy(tab + t.cg, ep.cb_g.data(), ep.cb_g.size() * 8);
+    }
 }
 
 size_t eval_work_bytes(const EvalPlan &ep, int nsig) { return work_layout(ep, nsig).bytes; }
@@ -743,6 +999,9 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
     a.lsd = (double *)(d.work + w.lsd); a.slsd = w.slsd;
     a.dm = (double *)(d.work + w.dm); a.sdm = w.sdm; a.sdr = (double *)(d.work + w.sdr); a.nsig = nsig;
     a.llr = (double *)(d.work + w.llr); a.lcd = (double *)(d.work + w.lcd); a.lv = (int *)(d.work + w.lv); a.lsel = (int *)(d.work + w.lsel);
+    a.ctw = (const double2 *)(d.tab + t.ctw); a.cband = (const int *)(d.tab + t.cband); a.cg = (const double *)(d.tab + t.cg); a.cH = ep.cH;
+    a.fw = (double *)(d.work + w.fw); a.ws = (double *)(d.work + w.ws); a.fv = (int *)(d.work + w.fv); a.wv = (int *)(d.work + w.wv);
+    a.csel = (int *)(d.work + w.csel);
     a.scores = d.scores; a.ns = ep.ns;
     const int n = ep.n, ne = nsig - 1;
     const dim3 blk(WAVE_THREADS);
@@ -762,7 +1021,7 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
         hipLaunchKernelGGL(bp_eval_sisdr, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
     }
     hipLaunchKernelGGL(bp_eval_reduce, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
-    if (ep.ns == BP_SCORE_FULL_N) {                                 // LLR and CD: order 10 below 10 kHz, else 16
+    if (ep.ns >= BP_SCORE_FULL_N) {                                 // LLR and CD: order 10 below 10 kHz, else 16
         if (ep.SJ[n]) {
             const int P = ep.fs < 10000 ? 10 : 16;
             const size_t lds = (lpc_slab_doubles(ep.win) + (size_t)(nsig * (P + 1) + P + 1) * EV_FB) * 8;
@@ -772,6 +1031,20 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
             hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((ep.SJ[n] + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, a);
         }
         hipLaunchKernelGGL(bp_eval_lpcsum, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    }
+    if (ep.ns >= BP_SCORE_ALL_N) {                                  // fwSegSNR and WSS
+        if (ep.SJ[n]) {
+            const size_t lds = cb_lds_bytes(ep.cH, nsig);
+            if (lds > 65536) {
+                const hipError_t e = hipFuncSetAttribute((const void *)bp_eval_cb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(bp_eval_cb, dim3((unsigned)((ep.SJ[n] + EV_CF - 1) / EV_CF)), blk, lds, st, a);
+            EvalArgs b = a;                                         // the rank-and-select of LLR / CD on the WSS values (both bits)
+            b.llr = a.ws; b.lcd = a.ws; b.lv = a.wv; b.lsel = a.csel;
+            hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((ep.SJ[n] + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, b);
+        }
+        hipLaunchKernelGGL(bp_eval_cbsum, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
     }
     return hipGetLastError();
 }
@@ -791,6 +1064,7 @@ static int score_waves_run(const char *who, int device, int fea_dim, int sample_
     { const int r = eval_n_scores(who, n_scores); if (r != BP_OK) return r; }
     if (wave_log2_fft(fea_dim) < 0) return fail(BP_ERR_ARG, std::string(who) + ": 2*(fea_dim-1) must be a power of two from 64 to 2048");
     { int p, q; if (!eval_rate(sample_rate, &p, &q)) return fail(BP_ERR_ARG, std::string(who) + ": sample_rate must be positive with 10000/sample_rate = p/q, max(p, q) <= 32"); }
+    { const int r = eval_cb_rate(who, sample_rate, n_scores); if (r != BP_OK) return r; }
     if (!est || !scores) return fail(BP_ERR_ARG, std::string(who) + ": no sentences or null pointer");
     WavePlan wp;
     { const int r = plan_waves(who, fea_dim, n_sent, sent_len, ref, (size_t)INT32_MAX / 8, wp); if (r != BP_OK) return r; }

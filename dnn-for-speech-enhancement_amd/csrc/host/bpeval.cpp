@@ -1,16 +1,17 @@
 // bpeval.cpp -- objective scores of enhanced speech on the MI355X: segmental SNR, log-spectral distortion and
 // STOI, through bp_eval_mix (a test set mixed on the GPU and enhanced with a trained net) or bp_score_waves (pairs of WAVs); with
-// scores=extended ESTOI and SI-SDR beside them, with scores=full LLR and cepstral distance as well, through the _ext calls.
+// scores=extended ESTOI and SI-SDR beside them, with scores=full LLR and cepstral distance as well, with scores=all fwSegSNR and
+// WSS behind those, through the _ext calls.
 //
 //   bpeval clean_list=test_clean.list noise_list=test_noise.list norm_file=x.norm initwts_file=mlp.N.wts fea_dim=129 fea_context=11
 //          targ_offset=5 layersizes=1548,2048,2048,2048,129 [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [init_randem_seed=0]
 //          [wave_target=lps|mask] [out_col=0] [traincache=102400] [bunchsize=1024] [dropoutflag=1 visible_omit=0.1 hid_omit=0.2]
 //          [activation=relu|sigmoid] [compute=fp32|bf16] [output_act=... output_linear_dims=... output_loss=...] [device=0]
 //          [scores_out=scores.txt] [baseline=logmmse] [rir_list=rir.list] [reverb_target=reverberant|early] [early_ms=50]
-//          [scores=basic|extended|full] [rate=16000] [lm_noise=vad|spp] [nat=static|dynamic]
+//          [scores=basic|extended|full|all] [rate=16000] [lm_noise=vad|spp] [nat=static|dynamic]
 //          [post_gv=gv.norm] [post_mask_col=129 [post_mask_lo=0.5] [post_mask_hi=0.5] [post_mask_weight=1]]
 //          [gv_out=gv.norm [gv_mode=indep|dep]]
-//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended|full] [rate=16000]
+//   bpeval pairs_list=<"ref.wav est.wav" per line> fea_dim=129 [device=0] [scores_out=scores.txt] [scores=basic|extended|full|all] [rate=16000]
 //
 // rate=R (either mode): every clean, noise or pair WAV whose rate is not R is converted to R on the device as it is
 // loaded (bp_resample_waves: one call and one line on stdout per list and distinct rate), and R is the rate handed to the scores;
@@ -31,6 +32,9 @@
 // scores=full: the extended output, and behind each of its additions the same for LLR and cepstral distance: `, LLR a -> b, CD a -> b
 // dB` on stdout (the count then over all seven columns), `llr_noisy llr_enh cd_noisy cd_enh` behind sisdr_enh, `llr_lm cd_lm` behind
 // sisdr_lm, `llr cd` behind sisdr in pairs mode.
+// scores=all: the full output, and behind each of its additions the same for fwSegSNR and WSS: `, fwSegSNR a -> b dB, WSS a -> b` on
+// stdout (the count then over all nine columns), `fwssnr_noisy fwssnr_enh wss_noisy wss_enh` behind cd_enh, `fwssnr_lm wss_lm`
+// behind cd_lm, `fwssnr wss` behind cd in pairs mode.  The rate must be 8 kHz or more.
 // rir_list: one room impulse response per WAV, at the rate of the others; clean sentence c is paired with response
 // bp_mix_reverb_pairs(init_randem_seed, ...)[c], the plan addresses the derived entry n_clean + c in place of c (so scores_out
 // lists it), the mixtures are reverberant and the scores are taken against reverb_target: the reverberant sentence or its direct
@@ -78,7 +82,7 @@ struct Params {
     int lm_noise = BP_NOISE_VAD;                             // lm_noise=vad|spp
     bool lm_noise_given = false;
     int nat = BP_NAT_STATIC;                                 // nat=static|dynamic: the noise-aware block of the net's input
-    int ext = 0;                                             // scores=basic|extended|full: 0, 1, 2 -> three, five, seven score columns
+    int ext = 0;                                             // scores=basic|extended|full|all: 0, 1, 2, 3 -> three, five, seven, nine score columns
     RirKeys rir;                                             // rir_rooms=N ...: simulated responses in place of rir_list
     PostKeys post;                                           // post_gv / post_mask_*: post-processing of the LPS estimate
     std::string gv_out;                                      // gv_out=FILE: the GV factors of the net on this test set, nothing scored
@@ -93,7 +97,7 @@ Params parse(int argc, char **argv)
         {"pairs_list", K_STR, &P.pairs_list}, {"scores_out", K_STR, &P.scores_out},
         {"fea_dim", K_INT, &P.fea_dim, 1, 1 << 20},
         {"device", K_INT, &P.device, 0, 1023},
-        {"scores", K_CHOICE, &P.ext, 0, 0, "basic|extended|full"},
+        {"scores", K_CHOICE, &P.ext, 0, 0, "basic|extended|full|all"},
         {"rate", K_INT, &P.rate, 1, (double)RATE_MAX},
     };
     const Key keys[] = {
@@ -148,10 +152,10 @@ void check_rate(int fs)
         fail("bpeval: " + std::to_string(fs) + " Hz is not a scoring rate (8, 10, 12, 16, 20, 24, 32, 48 kHz)");
 }
 
-// mean over the finite values; NaN count.  Slot k < BP_SCORE_FULL_N: column k of the noisy side, BP_SCORE_FULL_N + k: of the enhanced
+// mean over the finite values; NaN count.  Slot k < BP_SCORE_ALL_N: column k of the noisy side, BP_SCORE_ALL_N + k: of the enhanced
 // side; ns: the columns the rows have
-struct Acc { double sum[BP_SCORE_FULL_N * 2] = {0}; int cnt[BP_SCORE_FULL_N * 2] = {0}, n = 0, nan = 0; };
-int n_columns(int ext) { return ext == 2 ? (int)BP_SCORE_FULL_N : ext ? (int)BP_SCORE_EXT_N : (int)BP_SCORE_N; }
+struct Acc { double sum[BP_SCORE_ALL_N * 2] = {0}; int cnt[BP_SCORE_ALL_N * 2] = {0}, n = 0, nan = 0; };
+int n_columns(int ext) { return ext == 3 ? (int)BP_SCORE_ALL_N : ext == 2 ? (int)BP_SCORE_FULL_N : ext ? (int)BP_SCORE_EXT_N : (int)BP_SCORE_N; }
 void add(Acc &a, int ns, const float *noisy, const float *enh)
 {
     ++a.n;
@@ -159,11 +163,11 @@ void add(Acc &a, int ns, const float *noisy, const float *enh)
         for (int k = 0; k < ns; ++k) {
             const float v = side ? enh[k] : noisy[k];
             if (std::isnan(v)) { ++a.nan; continue; }
-            a.sum[side * BP_SCORE_FULL_N + k] += v; ++a.cnt[side * BP_SCORE_FULL_N + k];
+            a.sum[side * BP_SCORE_ALL_N + k] += v; ++a.cnt[side * BP_SCORE_ALL_N + k];
         }
 }
 double avg(const Acc &a, int k) { return a.cnt[k] ? a.sum[k] / a.cnt[k] : NAN; }
-double avg_enh(const Acc &a, int k) { return avg(a, BP_SCORE_FULL_N + k); }
+double avg_enh(const Acc &a, int k) { return avg(a, BP_SCORE_ALL_N + k); }
 
 int pairs_mode(const Params &P)
 {
@@ -208,13 +212,15 @@ int pairs_mode(const Params &P)
         add(a, ns, s, s);
         if (fo) fprintf(fo, "%s %s %.9g %.9g %.9g", refs[i].c_str(), ests[i].c_str(), s[0], s[1], s[2]);
         if (fo && P.ext) fprintf(fo, " %.9g %.9g", s[BP_SCORE_ESTOI], s[BP_SCORE_SISDR]);
-        if (fo && P.ext == 2) fprintf(fo, " %.9g %.9g", s[BP_SCORE_LLR], s[BP_SCORE_CD]);
+        if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g", s[BP_SCORE_LLR], s[BP_SCORE_CD]);
+        if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g", s[BP_SCORE_FWSSNR], s[BP_SCORE_WSS]);
         if (fo) fprintf(fo, "\n");
     }
     if (fo) fclose(fo);
     printf("pairs: %d pairs, SSNR %.3f dB, LSD %.3f dB, STOI %.4f", a.n, avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_STOI));
     if (P.ext) printf(", ESTOI %.4f, SI-SDR %.3f dB", avg(a, BP_SCORE_ESTOI), avg(a, BP_SCORE_SISDR));
-    if (P.ext == 2) printf(", LLR %.4f, CD %.3f dB", avg(a, BP_SCORE_LLR), avg(a, BP_SCORE_CD));
+    if (P.ext >= 2) printf(", LLR %.4f, CD %.3f dB", avg(a, BP_SCORE_LLR), avg(a, BP_SCORE_CD));
+    if (P.ext == 3) printf(", fwSegSNR %.3f dB, WSS %.3f", avg(a, BP_SCORE_FWSSNR), avg(a, BP_SCORE_WSS));
     printf(" (%d undefined)\n", a.nan / 2);
     return 1;
 }
@@ -342,13 +348,15 @@ int main(int argc, char **argv)
                 fprintf(fo, "%d %d %lld %.9g %.9g %.9g %.9g %.9g %.9g %.9g", m.clean, m.noise, (long long)m.offset, m.snr_db,
                         a[BP_SCORE_SSNR], b[BP_SCORE_SSNR], a[BP_SCORE_LSD], b[BP_SCORE_LSD], a[BP_SCORE_STOI], b[BP_SCORE_STOI]);
             if (fo && P.ext) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_ESTOI], b[BP_SCORE_ESTOI], a[BP_SCORE_SISDR], b[BP_SCORE_SISDR]);
-            if (fo && P.ext == 2) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_LLR], b[BP_SCORE_LLR], a[BP_SCORE_CD], b[BP_SCORE_CD]);
+            if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_LLR], b[BP_SCORE_LLR], a[BP_SCORE_CD], b[BP_SCORE_CD]);
+            if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_FWSSNR], b[BP_SCORE_FWSSNR], a[BP_SCORE_WSS], b[BP_SCORE_WSS]);
             if (P.baseline) {
                 const float *l = &ls[(size_t)i * NS];
                 add(by_snr_lm[m.snr_db], NS, a, l); add(all_lm, NS, a, l);
                 if (fo) fprintf(fo, " %.9g %.9g %.9g", l[BP_SCORE_SSNR], l[BP_SCORE_LSD], l[BP_SCORE_STOI]);
                 if (fo && P.ext) fprintf(fo, " %.9g %.9g", l[BP_SCORE_ESTOI], l[BP_SCORE_SISDR]);
-                if (fo && P.ext == 2) fprintf(fo, " %.9g %.9g", l[BP_SCORE_LLR], l[BP_SCORE_CD]);
+                if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g", l[BP_SCORE_LLR], l[BP_SCORE_CD]);
+                if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g", l[BP_SCORE_FWSSNR], l[BP_SCORE_WSS]);
             }
             if (fo) fprintf(fo, "\n");
         }
@@ -362,8 +370,11 @@ int main(int argc, char **argv)
         if (P.ext)
             printf(", ESTOI %.4f -> %.4f, SI-SDR %.3f -> %.3f dB", avg(a, BP_SCORE_ESTOI), avg_enh(a, BP_SCORE_ESTOI),
                    avg(a, BP_SCORE_SISDR), avg_enh(a, BP_SCORE_SISDR));
-        if (P.ext == 2)
+        if (P.ext >= 2)
             printf(", LLR %.4f -> %.4f, CD %.3f -> %.3f dB", avg(a, BP_SCORE_LLR), avg_enh(a, BP_SCORE_LLR), avg(a, BP_SCORE_CD), avg_enh(a, BP_SCORE_CD));
+        if (P.ext == 3)
+            printf(", fwSegSNR %.3f -> %.3f dB, WSS %.3f -> %.3f", avg(a, BP_SCORE_FWSSNR), avg_enh(a, BP_SCORE_FWSSNR), avg(a, BP_SCORE_WSS),
+                   avg_enh(a, BP_SCORE_WSS));
         printf(" (%d undefined)\n", a.nan);
     };
     for (const auto &kv : by_snr) {

@@ -260,7 +260,8 @@ def score_waves(device, fea_dim, sample_rate, refs, ests, extended=False):
     """bp_score_waves: SSNR, LSD and STOI of every estimate against its reference (lists of 1-D arrays, int16 units, pairwise
     equal lengths), float32 [n][3] (columns SCORE_SSNR, SCORE_LSD, SCORE_STOI; NaN where undefined).  No handle.  extended:
     bp_score_waves_ext, float32 [n][5] with SCORE_ESTOI and SCORE_SISDR behind the same three; extended="full": [n][7] with
-    SCORE_LLR and SCORE_CD behind those five.  Any other value is a BPError."""
+    SCORE_LLR and SCORE_CD behind those five; extended="all": [n][9] with SCORE_FWSSNR and SCORE_WSS behind those seven
+    (sample_rate from 8000 up).  Any other value is a BPError."""
     ns = score_columns("score_waves", extended)
     lib = load_library()
     if len(refs) != len(ests):

@@ -485,16 +485,41 @@ int bp_rir_rooms(uint64_t seed, int n, const bp_rir_range *g, bp_rir_room *out);
  *   rounded once to fp32: Hu & Loizou's mean of the lowest 95 % with the tie rule stated.  The white-noise correction is not
  *   in Hu & Loizou's comp_llr, which has no guard: it keeps the Toeplitz system positive definite with condition <= (P+1) 1e6,
  *   so that the recursion never breaks down and no second, rounding-dependent validity decision exists.
- * Not computed: PESQ, fwSNRseg and the composite measures (they need a 25-band table and PESQ: nothing here could be held to a source).
+ *
+ * The critical-band scores (the _ext calls with n_scores = BP_SCORE_ALL_N; two more columns behind the seven above; sample_rate >=
+ *   8000 and win <= 4096, else BP_ERR_ARG): the frequency-weighted segmental SNR fwSegSNR (dB) and the weighted spectral slope
+ *   distance WSS (Hu & Loizou 2008; Klatt 1982), on the SSNR's own framing: win, skip, the J frames and the window w above; n_fft
+ *   = 2^ceil(log2(2 win)), H = n_fft/2; everything in double on the fp32 samples, every sum in one fixed order.  This text is the
+ *   definition (the published code was not at hand: the nearest-peak search below is how it is remembered).
+ *   The bands, i = 0..24: centres cf (Hz) 50, 120, 190, 260, 330, 400, 470, 540, 617.372, 703.378, 798.717, 904.128, 1020.38,
+ *   1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63; widths bw (Hz) 70
+ *   (seven times), 77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154, 183.457, 199.776, 217.153,
+ *   235.631, 255.255, 276.072, 298.126, 321.465, 346.136; f0_i = cf_i/(fs/2) H, b_i = bw_i/(fs/2) H, g_i[k] = exp(-11 ((k -
+ *   floor(f0_i))/b_i)^2) for k = 0..H-1, set to 0 where it is not greater than exp(-30/(2 2.303)).
+ *   A frame is valid iff sum (w r)^2 > 0 and sum (w e)^2 > 0; an invalid frame is skipped.  R[k], E[k], k = 0..H-1: the n_fft-point
+ *   DFTs of the windowed, zero-padded frames.
+ *   fwSegSNR: a[k] = |R[k]|/sum_k |R[k]|, p[k] = |E[k]|/sum_k |E[k]|; c_i = sum_k g_i[k] a[k], d_i = sum_k g_i[k] p[k]; err_i =
+ *   max((c_i - d_i)^2, 2^-52), W_i = c_i^0.2; v = sum_i W_i 10 log10(c_i^2/err_i) / sum_i W_i over the bands with c_i > 0 (none:
+ *   the frame is invalid for this column); frame value min(max(v, -10), 35); the score = the mean over the valid frames, divided
+ *   once, rounded once to fp32.  No trim.
+ *   WSS: B_i = 10 log10(max(sum_k g_i[k] |R[k]|^2, 1e-10)), C_i likewise from E; slopes s_i = B_{i+1} - B_i, t_i = C_{i+1} - C_i,
+ *   i = 0..23.  Nearest peak L_i: if s_i > 0: n = i; while n < 24 and s_n > 0: n++; L_i = B_{n-1} (the band below the summit);
+ *   else: n = i; while n >= 0 and s_n <= 0: n--; L_i = B_{n+1}.  Wr_i = 20/(20 + max_j B_j - B_i) 1/(1 + L_i - B_i) (the max
+ *   over all 25 bands), We_i likewise from C and t, W_i = (Wr_i + We_i)/2; frame value sum_i W_i (s_i - t_i)^2 / sum_i W_i; the
+ *   score = the mean of the lowest 95 % of the valid frames under the rule of LLR / CD above (Jk, the tie rule), rounded once.
+ *   A column is NaN when it has no valid frame.
+ * Not computed: PESQ and the composite measures (no copy of P.862 to hold them to) and SRMR (non-intrusive).
  *
  * bp_score_waves_ext, bp_eval_mix_ext (and bp_eval_mix_logmmse_ext, bp_eval_mix_logmmse_nt below): the calls above with rows of
- *   n_scores columns, n_scores = BP_SCORE_N, BP_SCORE_EXT_N or BP_SCORE_FULL_N, anything else BP_ERR_ARG before the device is
- *   touched; every other check, state and capacity rule is that of the call without _ext.  With BP_SCORE_N an _ext call is that
- *   call; with BP_SCORE_EXT_N columns 0..2 hold its bits, and only then do the ESTOI and SI-SDR kernels run; with BP_SCORE_FULL_N
- *   columns 0..4 hold the bits of the five-column call, and only then do the LLR and CD kernels run. */
+ *   n_scores columns, n_scores = BP_SCORE_N, BP_SCORE_EXT_N, BP_SCORE_FULL_N or BP_SCORE_ALL_N, anything else BP_ERR_ARG before
+ *   the device is touched; every other check, state and capacity rule is that of the call without _ext.  With BP_SCORE_N an _ext
+ *   call is that call; with BP_SCORE_EXT_N columns 0..2 hold its bits, and only then do the ESTOI and SI-SDR kernels run; with
+ *   BP_SCORE_FULL_N columns 0..4 hold the bits of the five-column call, and only then do the LLR and CD kernels run; with
+ *   BP_SCORE_ALL_N columns 0..6 hold the bits of the seven-column call, and only then do the fwSegSNR and WSS kernels run. */
 enum { BP_SCORE_SSNR = 0, BP_SCORE_LSD = 1, BP_SCORE_STOI = 2, BP_SCORE_N = 3 };
 enum { BP_SCORE_ESTOI = 3, BP_SCORE_SISDR = 4, BP_SCORE_EXT_N = 5 };
 enum { BP_SCORE_LLR = 5, BP_SCORE_CD = 6, BP_SCORE_FULL_N = 7 };
+enum { BP_SCORE_FWSSNR = 7, BP_SCORE_WSS = 8, BP_SCORE_ALL_N = 9 };
 int bp_score_waves(int device, int fea_dim, int sample_rate, int n_sent, const int *sent_len, const float *ref, const float *est,
                    float *scores);
 int bp_eval_mix(bp_handle *h, int n_mix, const bp_mixture *m, int sample_rate, int target, int out_col, float *noisy_scores,

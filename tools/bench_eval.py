@@ -12,7 +12,12 @@ mixtures instead: the two alternate in one process, each timed to its synchronis
 mixtures, alternating in the same way.  The new kernels' share: `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py
 --full` (bp_eval_lpc, bp_eval_lpcrank, bp_eval_lpcsum against the other bp_eval_* kernels).
 
-    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16] [--extended | --full]
+--all: the nine-column bp_eval_mix_ext (fwSegSNR and WSS behind the seven) against the seven-column call on the same mixtures,
+alternating in the same way.  The new kernels' share: `rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py --all`
+(bp_eval_cb, bp_eval_cbsum and the second bp_eval_lpcrank against the other bp_eval_* kernels; bp_eval_bands also does one FFT
+per frame and signal).
+
+    python tools/bench_eval.py [--reps 10] [--compute fp32|bf16] [--extended | --full | --all]
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--sentences", type=int, default=100)
     ap.add_argument("--extended", action="store_true", help="time bp_eval_mix_ext with five columns beside bp_eval_mix")
     ap.add_argument("--full", action="store_true", help="time bp_eval_mix_ext with seven columns beside the five-column call")
+    ap.add_argument("--all", action="store_true", help="time bp_eval_mix_ext with nine columns beside the seven-column call")
     a = ap.parse_args()
     D, ctx, toff, rate, B = 129, 11, 5, 8000, 256
     ls = [(ctx + 1) * D, 2048, 2048, 2048, D]
@@ -86,6 +92,25 @@ def main():
                           "frames": frames, "extended_ms_median": 1e3 * m5, "full_ms_median": 1e3 * m7, "full_over_extended": m7 / m5,
                           "columns_0_to_4_same_bits": same, "noisy_mean": np.nanmean(ev7["noisy"], axis=0).tolist(),
                           "enhanced_mean": np.nanmean(ev7["enhanced"], axis=0).tolist()}))
+        return
+    if a.all:
+        t7, t9 = [], []
+        for r in range(a.reps + 1):                                # (rep 0: warm-up -- buffers, code objects)
+            t0 = time.perf_counter()
+            ev7 = g.eval_mix(plan, rate, extended="full")
+            t1 = time.perf_counter()
+            ev9 = g.eval_mix(plan, rate, extended="all")
+            t2 = time.perf_counter()
+            if r:
+                t7.append(t1 - t0)
+                t9.append(t2 - t1)
+        g.close()
+        same = all(np.array_equal(ev9[k][:, :7].view(np.uint32), ev7[k].view(np.uint32)) for k in ("noisy", "enhanced"))
+        m7, m9 = float(np.median(t7)), float(np.median(t9))
+        print(json.dumps({"what": "bp_eval_mix_ext (9 columns) vs bp_eval_mix_ext (7 columns)", "compute": a.compute, "mixtures": a.sentences,
+                          "frames": frames, "full_ms_median": 1e3 * m7, "all_ms_median": 1e3 * m9, "all_over_full": m9 / m7,
+                          "columns_0_to_6_same_bits": same, "noisy_mean": np.nanmean(ev9["noisy"], axis=0).tolist(),
+                          "enhanced_mean": np.nanmean(ev9["enhanced"], axis=0).tolist()}))
         return
     t_eval, t_enh = [], []
     for r in range(a.reps + 1):                                    # (rep 0: warm-up -- buffers, code objects)
