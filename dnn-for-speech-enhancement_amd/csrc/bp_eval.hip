@@ -1,9 +1,9 @@
-// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h): objective scores of enhanced speech.  Segmental SNR,
-// log-spectral distortion on the 1d analysis and STOI of estimates against a reference, and with five score columns ESTOI and
-// SI-SDR beside them, with seven LLR and cepstral distance as well, with nine the frequency-weighted segmental SNR and the weighted
-// spectral slope distance behind those (bp_score_waves[_ext] here; bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions:
-// include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.  bp_score_waves takes its frame plan and padded layout from bp_wave.hip
-// (plan_waves, wave_scatter: bp_fft.h) and its stream and device block from OneShot (bp_handle.h).
+// bp_eval.hip -- C-ABI implementation (include/bp_c_api.h): objective scores of enhanced speech, estimates against a reference, in
+// score rows of one of the widths of EVAL_WIDTHS (bp_eval.h: which columns and kernels each width adds; bp_score_waves[_ext] here,
+// bp_eval_mix[_ext] in bp_mix.hip through bp_eval.h).  Definitions: include/bp_c_api.h, INTEGRATION.md 1f.  gfx950 only.
+// bp_score_waves takes its frame plan and padded layout from bp_wave.hip (plan_waves, wave_scatter: bp_fft.h) and its stream and
+// device block from OneShot (bp_handle.h).  Host side: the prefix tables are named once in EVAL_PRE (bp_eval.h), the work arrays
+// once in work_rows, and the table and work blocks are laid out and bound to the kernels' argument block by walking those.
 //
 // Kernels (signal 0 is the reference, 1 .. nsig-1 the estimates; blockIdx.y picks the signal; a flat grid of workgroups finds its
 // sentence by a binary search over a prefix table, as bp_wave_analysis does over F):
@@ -24,8 +24,9 @@
 //                     windowed frame into LDS in double and sums the P + 1 autocorrelation lags (4 lag groups x 16 sample segments
 //                     over the lanes, a fixed shuffle tree over the segments); then one thread per (signal, frame) runs the Levinson-Durbin recursion and the LPC
 //                     cepstrum in registers (the reference's once, shared through LDS) and the quadratic forms: LLR_j, CD_j, valid_j
-//   bp_eval_lpcrank   seven columns only, one thread per SSNR frame of an estimate: the frame's rank among the sentence's valid
-//                     frames in either measure (integer counts; the sentence's values pass through LDS in tiles), selected iff rank < Jk
+//   bp_eval_lpcrank   seven columns and up, rank-and-select, one thread per SSNR frame of an estimate: the frame's rank among the
+//                     sentence's valid frames in each of the one or two measures that a.rank names for the launch (integer counts;
+//                     the sentence's values pass through LDS in tiles), selected iff rank < Jk
 //   bp_eval_lpcsum    seven columns only, one workgroup per (sentence, estimate): the selected values summed (strided sums, a
 //                     fixed LDS tree), divided by Jk: columns 5 and 6
 //   bp_eval_cb        nine columns only, one workgroup per 16 SSNR frames of the call: per (signal, frame), 1 to 4 of them at a time
@@ -35,8 +36,8 @@
 //                     shuffle tree) into LDS as [signal][band][frame], the reference's once; then 32 lanes per (estimate, frame), one per
 //                     band, do the 25-band part (a fixed shuffle tree over the bands): fwSegSNR_j, WSS_j and their validity
 //   bp_eval_cbsum     nine columns only, one workgroup per (sentence, estimate): the valid fwSegSNR values and the WSS values that
-//                     bp_eval_lpcrank selected (run a second time, on the WSS values) summed (strided sums, a fixed LDS tree):
-//                     columns 7 and 8
+//                     bp_eval_lpcrank selected (a second launch, ranking the WSS values alone) summed (strided sums, a fixed LDS
+//                     tree): columns 7 and 8
 //   bp_eval_trim      per padded sample: zero outside the sentence (the overlap-add output, before it is analysed)
 // No float atomics and no cross-workgroup hand-off inside a kernel: the same bits on every run.
 #include <hip/hip_runtime.h>
@@ -59,9 +60,15 @@ __constant__ int ev_band_lo[EV_NB] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 
 __constant__ int ev_band_hi[EV_NB] = {9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 constexpr int EV_BIN_LO = 7, EV_BIN_HI = 219;
 
+// What one bp_eval_lpcrank launch ranks: nval (1 or 2) arrays of per-frame values [est][SJ[n]], their frames' validity, and where
+// the selection goes (bit k: selected in val[k])
+struct RankSel { const double *val[2]; int nval; const int *valid; int *sel; };
+
 struct EvalArgs {
     const int64_t *off; const int *len;
-    const int *o10, *rb, *P, *eb, *Q, *qb, *CP, *cb, *SJ, *sb, *F, *FS;
+#define X(name) const int *name;
+    EVAL_PRE(X)                                              // a.o10 .. a.FS
+#undef X
     const float *h, *v; const float2 *tw; const double *w;
     int n, p, q, Lh, taps, win, skip, D;
     double clip;                                             // 1 + 10^(15/20)
@@ -75,14 +82,54 @@ struct EvalArgs {
     double *llr, *lcd; int *lv, *lsel;                       // seven columns: [est][SJ[n]] each (lv: valid; lsel: bit 0 LLR, bit 1 CD selected)
     // nine columns: twiddles exp(-2 pi i j / n_fft) [cH + 1]; per band first bin, bins, offset into cg [3][25]; the weights; n_fft / 2
     const double2 *ctw; const int *cband; const double *cg; int cH;
-    double *fw, *ws; int *fv, *wv, *csel;                    // [est][SJ[n]] each (fv, wv: valid; csel: bits 0 and 1 WSS selected)
+    double *fw, *ws; int *fv, *wv, *csel;                    // [est][SJ[n]] each (fv, wv: valid; csel: bit 0 WSS selected)
     float *scores; int ns;                                   // [est][n][ns]
+    RankSel rank;                                            // set per bp_eval_lpcrank launch
 };
 
 __device__ __forceinline__ double wave_sum(double x)
 {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     return x;
+}
+
+struct OpAdd { __device__ double operator()(double x, double y) const { return x + y; } };
+struct OpMax { __device__ double operator()(double x, double y) const { return fmax(x, y); } };
+constexpr float EV_NAN = __builtin_bit_cast(float, 0x7fc00000);   // the score of an undefined measure
+
+// The block reduction of the per-sentence kernels: ND doubles (combined by op) and NI ints (added) over the WAVE_THREADS threads by
+// the fixed LDS tree -- strides 128, 64, .. 1, thread tid < w takes in thread tid + w.  q and c: the thread's own results on entry
+// (its strided partial sums, formed in ascending order), the block's on return, in every thread.  A kernel that reduces twice puts
+// a barrier between the two: the LDS is the same.
+template <int ND, int NI, class Op = OpAdd> __device__ __forceinline__ void block_reduce(double *q, int *c, Op op = Op())
+{
+    __shared__ __align__(8) char lds[(ND * 8 + NI * 4) * WAVE_THREADS];
+    double (*red)[WAVE_THREADS] = reinterpret_cast<double (*)[WAVE_THREADS]>(lds);
+    int (*cnt)[WAVE_THREADS] = reinterpret_cast<int (*)[WAVE_THREADS]>(lds + ND * 8 * WAVE_THREADS);
+    const int tid = threadIdx.x;
+    for (int k = 0; k < ND; ++k) red[k][tid] = q[k];
+    for (int k = 0; k < NI; ++k) cnt[k][tid] = c[k];
+    __syncthreads();
+    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            for (int k = 0; k < ND; ++k) red[k][tid] = op(red[k][tid], red[k][tid + w]);
+            for (int k = 0; k < NI; ++k) cnt[k][tid] += cnt[k][tid + w];
+        }
+        __syncthreads();
+    }
+    for (int k = 0; k < ND; ++k) q[k] = red[k][0];
+    for (int k = 0; k < NI; ++k) c[k] = cnt[k][0];
+}
+
+// first[f], f < nf <= WAVE_THREADS: the first sample of frame g0 + f of the call (index over SJ[n], clamped to the last frame:
+// total >= 1) -- one search per frame, not one per item: each is a chain of loads.  The caller's barrier publishes it.
+__device__ __forceinline__ void frame_first(const EvalArgs &a, int64_t *first, int g0, int nf, int total)
+{
+    const int f = threadIdx.x;
+    if (f < nf) {
+        const int g = g0 + f < total ? g0 + f : total - 1, s = sentence_of(a.SJ, a.n, g);
+        first[f] = a.off[s] + (int64_t)(g - a.SJ[s]) * a.skip;
+    }
 }
 
 }  // namespace
@@ -115,18 +162,12 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_energy(const EvalArgs a)
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_mask(const EvalArgs a)
 {
-    __shared__ double mx[WAVE_THREADS];
     __shared__ int cnt[WAVE_THREADS];
     const int s = blockIdx.x, tid = threadIdx.x, base = a.P[s], J = a.P[s + 1] - base;
     double m = 0.0;
     for (int j = tid; j < J; j += WAVE_THREADS) m = fmax(m, a.E[base + j]);
-    mx[tid] = m;
-    __syncthreads();
-    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) mx[tid] = fmax(mx[tid], mx[tid + w]);
-        __syncthreads();
-    }
-    const double thr = 1e-4 * mx[0];
+    block_reduce<1, 0>(&m, nullptr, OpMax());
+    const double thr = 1e-4 * m;
     int total = 0;
     for (int j0 = 0; j0 < J; j0 += WAVE_THREADS) {
         const int j = j0 + tid, keep = j < J && a.E[base + j] > thr;
@@ -273,65 +314,48 @@ __global__ __launch_bounds__(64) void bp_eval_estoi(const EvalArgs a)
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_sisdr(const EvalArgs a)
 {
-    __shared__ double red[2][WAVE_THREADS];
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, n = a.len[s];
     const float *r = a.sig[0] + a.off[s], *x = a.sig[e] + a.off[s];
-    double al = 0.0;
-    for (int pass = 0; pass < 2; ++pass) {                          // 0: rr, er; 1: num, den (the residual itself, no cancellation)
-        double q0 = 0.0, q1 = 0.0;
-        for (int i = tid; i < n; i += WAVE_THREADS) {
-            const double rv = r[i], xv = x[i];
-            if (pass == 0) { q0 += rv * rv; q1 += xv * rv; }
-            else { const double t = al * rv, d = t - xv; q0 += t * t; q1 += d * d; }
-        }
-        red[0][tid] = q0; red[1][tid] = q1;
-        __syncthreads();
-        for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-            if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; }
-            __syncthreads();
-        }
-        q0 = red[0][0]; q1 = red[1][0];
-        __syncthreads();                                            // (read before pass 1 writes red again)
-        if (pass == 0) {
-            if (q0 == 0.0) {                                        // a silent reference (uniform over the workgroup)
-                if (tid == 0) a.sdr[(size_t)(e - 1) * a.n + s] = __longlong_as_double(0x7ff8000000000000LL);
-                return;
-            }
-            al = q1 / q0;
-        } else if (tid == 0)
-            a.sdr[(size_t)(e - 1) * a.n + s] = 10.0 * log10(q0 / (q1 + EV_EPS) + EV_EPS);
+    double q[2] = {0.0, 0.0}, p[2] = {0.0, 0.0};                    // rr, er; then num, den (the residual itself, no cancellation)
+    for (int i = tid; i < n; i += WAVE_THREADS) {
+        const double rv = r[i], xv = x[i];
+        q[0] += rv * rv; q[1] += xv * rv;
     }
+    block_reduce<2, 0>(q, nullptr);
+    __syncthreads();                                                // (read before the second pass writes the LDS again)
+    if (q[0] == 0.0) {                                              // a silent reference (uniform over the workgroup)
+        if (tid == 0) a.sdr[(size_t)(e - 1) * a.n + s] = __longlong_as_double(0x7ff8000000000000LL);
+        return;
+    }
+    const double al = q[1] / q[0];
+    for (int i = tid; i < n; i += WAVE_THREADS) {
+        const double rv = r[i], xv = x[i], t = al * rv, d = t - xv;
+        p[0] += t * t; p[1] += d * d;
+    }
+    block_reduce<2, 0>(p, nullptr);
+    if (tid == 0) a.sdr[(size_t)(e - 1) * a.n + s] = 10.0 * log10(p[0] / (p[1] + EV_EPS) + EV_EPS);
 }
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_reduce(const EvalArgs a)
 {
-    __shared__ double red[4][WAVE_THREADS];
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x;
     const int J = a.SJ[s + 1] - a.SJ[s], T = a.F[s + 1] - a.F[s], S = a.C[s] - 1, np = S >= EV_SEG ? EV_NB * (S - (EV_SEG - 1)) : 0;
     const double *ss = a.ssnr + (e - 1) * a.sssnr + a.SJ[s], *ls = a.lsd + (e - 1) * a.slsd + a.F[s], *rh = a.rho + (e - 1) * a.srho + a.CP[s];
     const bool ext = a.ns >= BP_SCORE_EXT_N;
     const int nd = ext ? np / EV_NB : 0;                            // the S - 29 segments
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
-    for (int i = tid; i < J; i += WAVE_THREADS) q0 += ss[i];
-    for (int i = tid; i < T; i += WAVE_THREADS) q1 += ls[i];
-    for (int i = tid; i < np; i += WAVE_THREADS) q2 += rh[i];
-    for (int i = tid; i < nd; i += WAVE_THREADS) q3 += a.dm[(e - 1) * a.sdm + a.CP[s] / EV_NB + i];
-    red[0][tid] = q0; red[1][tid] = q1; red[2][tid] = q2; red[3][tid] = q3;
-    __syncthreads();
-    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) {
-            red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; red[2][tid] += red[2][tid + w]; red[3][tid] += red[3][tid + w];
-        }
-        __syncthreads();
-    }
+    double q[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < J; i += WAVE_THREADS) q[0] += ss[i];
+    for (int i = tid; i < T; i += WAVE_THREADS) q[1] += ls[i];
+    for (int i = tid; i < np; i += WAVE_THREADS) q[2] += rh[i];
+    for (int i = tid; i < nd; i += WAVE_THREADS) q[3] += a.dm[(e - 1) * a.sdm + a.CP[s] / EV_NB + i];
+    block_reduce<4, 0>(q, nullptr);
     if (tid == 0) {
-        const float nan = __int_as_float(0x7fc00000);
         float *o = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
-        o[BP_SCORE_SSNR] = J >= 1 ? (float)(red[0][0] / J) : nan;
-        o[BP_SCORE_LSD] = T >= 1 ? (float)(red[1][0] / T) : nan;
-        o[BP_SCORE_STOI] = np > 0 ? (float)(red[2][0] / np) : nan;
+        o[BP_SCORE_SSNR] = J >= 1 ? (float)(q[0] / J) : EV_NAN;
+        o[BP_SCORE_LSD] = T >= 1 ? (float)(q[1] / T) : EV_NAN;
+        o[BP_SCORE_STOI] = np > 0 ? (float)(q[2] / np) : EV_NAN;
         if (ext) {
-            o[BP_SCORE_ESTOI] = nd > 0 ? (float)(red[3][0] / nd) : nan;
+            o[BP_SCORE_ESTOI] = nd > 0 ? (float)(q[3] / nd) : EV_NAN;
             o[BP_SCORE_SISDR] = (float)a.sdr[(size_t)(e - 1) * a.n + s];
         }
     }
@@ -444,10 +468,7 @@ template <int P> __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpc(con
     extern __shared__ double lpc_lds[];
     __shared__ int64_t first[EV_FB];                                // the first sample of each frame of the block
     const int tid = threadIdx.x, ln = tid & 63, wv = tid >> 6, g0 = blockIdx.x * EV_FB, total = a.SJ[a.n];
-    if (tid < EV_FB) {                                              // (one search per frame, not one per item: each is a chain of loads)
-        const int g = g0 + tid < total ? g0 + tid : total - 1, s = sentence_of(a.SJ, a.n, g);
-        first[tid] = a.off[s] + (int64_t)(g - a.SJ[s]) * a.skip;
-    }
+    frame_first(a, first, g0, EV_FB, total);
     double *xw = lpc_lds + (size_t)wv * (a.win + EV_LPAD);
     double *Rl = lpc_lds + lpc_slab_doubles(a.win), *Cr = Rl + (size_t)a.nsig * (P + 1) * EV_FB, *Dl = Cr + (size_t)P * EV_FB;
     if (a.win <= EV_SLAB_WIN && ln < EV_LPAD) xw[a.win + ln] = 0.0;
@@ -505,69 +526,78 @@ template <int P> __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpc(con
 // Jk of Jv valid frames: the lowest 95 %, at least one
 __device__ __forceinline__ int lpc_keep(int Jv) { const int k = (int)floor(0.95 * (double)Jv + 0.5); return k > 1 ? k : 1; }
 
-// one thread per frame (global index g; a block may span sentences): the values of all the sentences the block touches pass
-// through LDS in tiles, and every thread counts the frames of its own sentence among them (the reads of a tile entry are
-// the same address in every lane)
-__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcrank(const EvalArgs a)
+// Rank-and-select over the NV value arrays of a.rank.  One thread per frame (global index g; a block may span sentences): the
+// values of all the sentences the block touches pass through LDS in tiles, and every thread counts the frames of its own sentence
+// among them (the reads of a tile entry are the same address in every lane)
+template <int NV> __device__ __forceinline__ void rank_select(const EvalArgs &a, double (*tx)[WAVE_THREADS], int *tv)
 {
-    __shared__ double tl[WAVE_THREADS], tc[WAVE_THREADS];
-    __shared__ int tv[WAVE_THREADS];
+    const RankSel &r = a.rank;
     const int e = blockIdx.y + 1, tid = threadIdx.x, total = a.SJ[a.n], g0 = blockIdx.x * WAVE_THREADS;
     const int glast = g0 + WAVE_THREADS - 1 < total ? g0 + WAVE_THREADS - 1 : total - 1, g = g0 + tid;
     const bool live = g < total;
     const int s = sentence_of(a.SJ, a.n, live ? g : glast), lo = a.SJ[s], hi = a.SJ[s + 1];
     const int ulo = a.SJ[sentence_of(a.SJ, a.n, g0)], uhi = a.SJ[sentence_of(a.SJ, a.n, glast) + 1];   // (uniform over the workgroup)
     const size_t o = (size_t)(e - 1) * a.sssnr;
-    const double lj = live ? a.llr[o + g] : 0.0, cj = live ? a.lcd[o + g] : 0.0;
-    int jv = 0, rl = 0, rc = 0;                                     // valid frames; frames ranked before g in LLR, in CD
+    double xj[NV];
+    int jv = 0, rk[NV];                                             // valid frames; frames ranked before g in each measure
+    for (int k = 0; k < NV; ++k) { xj[k] = live ? r.val[k][o + g] : 0.0; rk[k] = 0; }
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     for (int t0 = ulo; t0 < uhi; t0 += WAVE_THREADS) {
         const int i = t0 + tid, m = uhi - t0 < WAVE_THREADS ? uhi - t0 : WAVE_THREADS;
         if (i < uhi) {                                              // (an invalid frame is +inf here: below no frame, equal to no valid one)
-            const int v = a.lv[o + i];
-            tl[tid] = v ? a.llr[o + i] : inf; tc[tid] = v ? a.lcd[o + i] : inf; tv[tid] = v;
+            const int v = r.valid[o + i];
+            for (int k = 0; k < NV; ++k) tx[k][tid] = v ? r.val[k][o + i] : inf;
+            tv[tid] = v;
         }
         __syncthreads();
         // the thread's own sentence within the tile: the frames before g count when not above, the frames behind g when below
         const int u0 = lo > t0 ? lo - t0 : 0, u3 = hi - t0 < m ? hi - t0 : m;
         const int u1 = g - t0 < u3 ? g - t0 : u3, u2 = g + 1 - t0 > u0 ? g + 1 - t0 : u0;
-        for (int u = u0; u < u1; ++u) { jv += tv[u]; rl += tl[u] <= lj; rc += tc[u] <= cj; }
-        for (int u = u2; u < u3; ++u) { jv += tv[u]; rl += tl[u] < lj; rc += tc[u] < cj; }
+        for (int u = u0; u < u1; ++u) {
+            jv += tv[u];
+            for (int k = 0; k < NV; ++k) rk[k] += tx[k][u] <= xj[k];
+        }
+        for (int u = u2; u < u3; ++u) {
+            jv += tv[u];
+            for (int k = 0; k < NV; ++k) rk[k] += tx[k][u] < xj[k];
+        }
         if (g >= t0 && g < t0 + m) jv += tv[g - t0];
         __syncthreads();
     }
     if (live) {
         const int Jk = lpc_keep(jv);
-        a.lsel[o + g] = a.lv[o + g] ? (rl < Jk ? 1 : 0) | (rc < Jk ? 2 : 0) : 0;
+        int sel = 0;
+        for (int k = 0; k < NV; ++k) sel |= rk[k] < Jk ? 1 << k : 0;
+        r.sel[o + g] = r.valid[o + g] ? sel : 0;
     }
+}
+
+__global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcrank(const EvalArgs a)
+{
+    __shared__ double tx[2][WAVE_THREADS];
+    __shared__ int tv[WAVE_THREADS];
+    if (a.rank.nval == 2) rank_select<2>(a, tx, tv);
+    else rank_select<1>(a, tx, tv);
 }
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_lpcsum(const EvalArgs a)
 {
-    __shared__ double red[2][WAVE_THREADS];
-    __shared__ int cnt[WAVE_THREADS];
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, J = a.SJ[s + 1] - a.SJ[s];
     const size_t o = (size_t)(e - 1) * a.sssnr + a.SJ[s];
-    double q0 = 0.0, q1 = 0.0;
-    int jv = 0;
+    double q[2] = {0.0, 0.0};
+    int Jv = 0;
     for (int i = tid; i < J; i += WAVE_THREADS) {
         const int sel = a.lsel[o + i];
-        jv += a.lv[o + i];
-        if (sel & 1) q0 += a.llr[o + i];
-        if (sel & 2) q1 += a.lcd[o + i];
+        Jv += a.lv[o + i];
+        if (sel & 1) q[0] += a.llr[o + i];
+        if (sel & 2) q[1] += a.lcd[o + i];
     }
-    red[0][tid] = q0; red[1][tid] = q1; cnt[tid] = jv;
-    __syncthreads();
-    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; cnt[tid] += cnt[tid + w]; }
-        __syncthreads();
-    }
+    block_reduce<2, 1>(q, &Jv);
     if (tid == 0) {
-        const float nan = __int_as_float(0x7fc00000);
         float *sc = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
-        const int Jv = cnt[0], Jk = lpc_keep(Jv);
-        sc[BP_SCORE_LLR] = Jv > 0 ? (float)(red[0][0] / Jk) : nan;
-        sc[BP_SCORE_CD] = Jv > 0 ? (float)(red[1][0] / Jk) : nan;
+        const int Jk = lpc_keep(Jv);
+        sc[BP_SCORE_LLR] = Jv > 0 ? (float)(q[0] / Jk) : EV_NAN;
+        sc[BP_SCORE_CD] = Jv > 0 ? (float)(q[1] / Jk) : EV_NAN;
     }
 }
 
@@ -609,10 +639,7 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_cb(const EvalArgs a)
     const int T = cb_threads(H), G = WAVE_THREADS / T, slot = tid / T, lt = tid % T, wps = T / 64, L = T / 32;
     int log2H = 0;
     while ((1 << log2H) < H) ++log2H;
-    if (tid < nf) {
-        const int g = g0 + tid, s = sentence_of(a.SJ, a.n, g);
-        first[tid] = a.off[s] + (int64_t)(g - a.SJ[s]) * a.skip;
-    }
+    frame_first(a, first, g0, nf, total);
     double2 *z = reinterpret_cast<double2 *>(cb_lds) + (size_t)slot * (cb_z_doubles(H) / 2);
     double2 *bs = reinterpret_cast<double2 *>(cb_lds + (size_t)G * cb_z_doubles(H));
     int *ok = reinterpret_cast<int *>(bs + (size_t)a.nsig * EV_CBN * EV_CF);
@@ -730,30 +757,20 @@ __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_cb(const EvalArgs a)
 
 __global__ __launch_bounds__(WAVE_THREADS) void bp_eval_cbsum(const EvalArgs a)
 {
-    __shared__ double red[2][WAVE_THREADS];
-    __shared__ int cnt[2][WAVE_THREADS];
     const int s = blockIdx.x, e = blockIdx.y + 1, tid = threadIdx.x, J = a.SJ[s + 1] - a.SJ[s];
     const size_t o = (size_t)(e - 1) * a.sssnr + a.SJ[s];
-    double q0 = 0.0, q1 = 0.0;
-    int n0 = 0, n1 = 0;
+    double q[2] = {0.0, 0.0};
+    int nv[2] = {0, 0};                                             // valid frames of fwSegSNR, of WSS
     for (int i = tid; i < J; i += WAVE_THREADS) {
-        n0 += a.fv[o + i]; n1 += a.wv[o + i];
-        if (a.fv[o + i]) q0 += a.fw[o + i];
-        if (a.csel[o + i] & 1) q1 += a.ws[o + i];
+        nv[0] += a.fv[o + i]; nv[1] += a.wv[o + i];
+        if (a.fv[o + i]) q[0] += a.fw[o + i];
+        if (a.csel[o + i] & 1) q[1] += a.ws[o + i];
     }
-    red[0][tid] = q0; red[1][tid] = q1; cnt[0][tid] = n0; cnt[1][tid] = n1;
-    __syncthreads();
-    for (int w = WAVE_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) {
-            red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; cnt[0][tid] += cnt[0][tid + w]; cnt[1][tid] += cnt[1][tid + w];
-        }
-        __syncthreads();
-    }
+    block_reduce<2, 2>(q, nv);
     if (tid == 0) {
-        const float nan = __int_as_float(0x7fc00000);
         float *sc = a.scores + ((size_t)(e - 1) * a.n + s) * a.ns;
-        sc[BP_SCORE_FWSSNR] = cnt[0][0] > 0 ? (float)(red[0][0] / cnt[0][0]) : nan;
-        sc[BP_SCORE_WSS] = cnt[1][0] > 0 ? (float)(red[1][0] / lpc_keep(cnt[1][0])) : nan;
+        sc[BP_SCORE_FWSSNR] = nv[0] > 0 ? (float)(q[0] / nv[0]) : EV_NAN;
+        sc[BP_SCORE_WSS] = nv[1] > 0 ? (float)(q[1] / lpc_keep(nv[1])) : EV_NAN;
     }
 }
 
@@ -772,7 +789,7 @@ namespace {
 
 // Where the tables lie in the table block (all offsets 256-byte aligned).
 struct TabLayout {
-    size_t off, len, pre[12], h, v, tw, w, ctw, cband, cg, bytes;   // pre: the prefix tables in EvalPlan order; c*: nine columns only
+    size_t off, len, pre[PRE_N], h, v, tw, w, ctw, cband, cg, bytes;   // pre: the prefix tables by id; c*: EVAL_ALL only
 };
 TabLayout tab_layout(const EvalPlan &ep)
 {
@@ -780,22 +797,17 @@ TabLayout tab_layout(const EvalPlan &ep)
     const size_t n = (size_t)ep.n;
     Layout lay;
     t.off = lay.take(n * 8); t.len = lay.take(n * 4);
-    for (int k = 0; k < 12; ++k) t.pre[k] = lay.take((n + 1) * 4);
+    for (int k = 0; k < PRE_N; ++k) t.pre[k] = lay.take((n + 1) * 4);
     t.h = lay.take((size_t)ep.taps * 4);
     t.v = lay.take((size_t)EV_NFFT * 4);
     t.tw = lay.take((size_t)(EV_NFFT / 2 + 1) * 8);
     t.w = lay.take((size_t)ep.win * 8);
-    const bool all = ep.ns >= BP_SCORE_ALL_N;                       // (a part of 0 bytes takes no room)
+    const bool all = ep.has(EVAL_ALL);                              // (a part of 0 bytes takes no room)
     t.ctw = lay.take(all ? (size_t)(ep.cH + 1) * 16 : 0);
     t.cband = lay.take(all ? (size_t)3 * EV_CBN * 4 : 0);
     t.cg = lay.take(all ? ep.cb_g.size() * 8 : 0);
     t.bytes = lay.size();
     return t;
-}
-const std::vector<int> &pre_k(const EvalPlan &ep, int k)
-{
-    const std::vector<int> *v[12] = {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS};
-    return *v[k];
 }
 
 double bessel_i0(double x)
@@ -805,39 +817,50 @@ double bessel_i0(double x)
     return s;
 }
 
-// Work block layout for nsig signals.
-struct WorkLayout { size_t r10, E, frm, C, comp, band, rho, ssnr, lsd, dm, sdr, llr, lcd, lv, lsel, fw, ws, fv, wv, csel, bytes; size_t s10, scomp, sband, srho, sssnr, slsd, sdm; };
-WorkLayout work_layout(const EvalPlan &ep, int nsig)
+// The work block: one row per array, in block order.  An array holds `per` x extent elements, and the narrowest width that has it
+// says whether it takes room (a part of 0 bytes takes none); bind puts its address, and the extent where a kernel strides by it,
+// into the argument block.
+enum Per { PER_SIG, PER_EST, ONCE };
+enum Extent { X_O10, X_P, X_N, X_Q, X_BAND, X_CP, X_SJ, X_F, X_SEG, X_COUNT };   // (X_O10: rounded up to 4 samples)
+struct WorkRow { const char *name; void (*bind)(EvalArgs &, char *, size_t); size_t elem; Per per; Extent ext; EvalWidth width; };
+#define ROW(p, stride, per, ext, width) \
+    {#p, [](EvalArgs &a, char *at, size_t st) { a.p = (decltype(a.p))at; stride; }, sizeof(*EvalArgs().p), per, ext, width}
+const WorkRow work_rows[] = {
+    ROW(r10, a.s10 = st, PER_SIG, X_O10, EVAL_BASIC),
+    ROW(E, (void)st, ONCE, X_P, EVAL_BASIC),
+    ROW(frm, (void)st, ONCE, X_P, EVAL_BASIC),
+    ROW(C, (void)st, ONCE, X_N, EVAL_BASIC),
+    ROW(comp, a.scomp = st, PER_SIG, X_Q, EVAL_BASIC),
+    ROW(band, a.sband = st, PER_SIG, X_BAND, EVAL_BASIC),
+    ROW(rho, a.srho = st, PER_EST, X_CP, EVAL_BASIC),
+    ROW(ssnr, a.sssnr = st, PER_EST, X_SJ, EVAL_BASIC),             // (sssnr: the stride of every [est][SJ[n]] array below)
+    ROW(lsd, a.slsd = st, PER_EST, X_F, EVAL_BASIC),
+    ROW(dm, a.sdm = st, PER_EST, X_SEG, EVAL_EXT),
+    ROW(sdr, (void)st, PER_EST, X_N, EVAL_EXT),
+    ROW(llr, (void)st, PER_EST, X_SJ, EVAL_FULL),
+    ROW(lcd, (void)st, PER_EST, X_SJ, EVAL_FULL),
+    ROW(lv, (void)st, PER_EST, X_SJ, EVAL_FULL),
+    ROW(lsel, (void)st, PER_EST, X_SJ, EVAL_FULL),
+    ROW(fw, (void)st, PER_EST, X_SJ, EVAL_ALL),
+    ROW(ws, (void)st, PER_EST, X_SJ, EVAL_ALL),
+    ROW(fv, (void)st, PER_EST, X_SJ, EVAL_ALL),
+    ROW(wv, (void)st, PER_EST, X_SJ, EVAL_ALL),
+    ROW(csel, (void)st, PER_EST, X_SJ, EVAL_ALL),
+};
+#undef ROW
+// Walks the table: the size of the work block for nsig signals and, with a, the binding of every array at work
+size_t work_walk(const EvalPlan &ep, int nsig, EvalArgs *a = nullptr, char *work = nullptr)
 {
-    WorkLayout w;
-    const int n = ep.n, ne = nsig - 1;
-    w.s10 = ((size_t)ep.o10[n] + 3) & ~(size_t)3; w.scomp = (size_t)ep.Q[n];
-    w.sband = (size_t)ep.P[n] * EV_BS; w.srho = (size_t)ep.CP[n]; w.sssnr = (size_t)ep.SJ[n]; w.slsd = (size_t)ep.F[n];
+    const size_t o10 = ep.tot(PRE_o10), P = ep.tot(PRE_P), CP = ep.tot(PRE_CP);
+    const size_t extent[X_COUNT] = {(o10 + 3) & ~(size_t)3, P, (size_t)ep.n, (size_t)ep.tot(PRE_Q), P * EV_BS, CP, (size_t)ep.tot(PRE_SJ),
+                                    (size_t)ep.tot(PRE_F), CP / EV_NB};
     Layout lay;
-    w.r10 = lay.take(nsig * w.s10 * 4);
-    w.E = lay.take((size_t)ep.P[n] * 8);
-    w.frm = lay.take((size_t)ep.P[n] * 4);
-    w.C = lay.take((size_t)n * 4);
-    w.comp = lay.take(nsig * w.scomp * 4);
-    w.band = lay.take(nsig * w.sband * 4);
-    w.rho = lay.take(ne * w.srho * 8);
-    w.ssnr = lay.take(ne * w.sssnr * 8);
-    w.lsd = lay.take(ne * w.slsd * 8);
-    w.sdm = (size_t)ep.CP[n] / EV_NB;                               // five columns only (a part of 0 bytes takes no room)
-    const bool ext = ep.ns >= BP_SCORE_EXT_N, full = ep.ns >= BP_SCORE_FULL_N, all = ep.ns >= BP_SCORE_ALL_N;
-    w.dm = lay.take(ext ? ne * w.sdm * 8 : 0);
-    w.sdr = lay.take(ext ? (size_t)ne * n * 8 : 0);
-    w.llr = lay.take(full ? ne * w.sssnr * 8 : 0);                  // seven columns only
-    w.lcd = lay.take(full ? ne * w.sssnr * 8 : 0);
-    w.lv = lay.take(full ? ne * w.sssnr * 4 : 0);
-    w.lsel = lay.take(full ? ne * w.sssnr * 4 : 0);
-    w.fw = lay.take(all ? ne * w.sssnr * 8 : 0);                    // nine columns only
-    w.ws = lay.take(all ? ne * w.sssnr * 8 : 0);
-    w.fv = lay.take(all ? ne * w.sssnr * 4 : 0);
-    w.wv = lay.take(all ? ne * w.sssnr * 4 : 0);
-    w.csel = lay.take(all ? ne * w.sssnr * 4 : 0);
-    w.bytes = lay.size();
-    return w;
+    for (const WorkRow &r : work_rows) {
+        const size_t ext = extent[r.ext], per = r.per == PER_SIG ? nsig : r.per == PER_EST ? nsig - 1 : 1;
+        const size_t at = lay.take(ep.has(r.width) ? per * ext * r.elem : 0);
+        if (a) r.bind(*a, work + at, ext);
+    }
+    return lay.size();
 }
 
 }  // namespace
@@ -853,8 +876,12 @@ bool eval_rate(int fs, int *p, int *q)
 
 int eval_n_scores(const char *who, int n_scores)
 {
-    if (n_scores == BP_SCORE_N || n_scores == BP_SCORE_EXT_N || n_scores == BP_SCORE_FULL_N || n_scores == BP_SCORE_ALL_N) return BP_OK;
-    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be BP_SCORE_N, BP_SCORE_EXT_N, BP_SCORE_FULL_N or BP_SCORE_ALL_N");
+    std::string names;                                             // "A, B, C or D"
+    for (int w = 0; w < EVAL_WIDTH_N; ++w) {
+        if (n_scores == EVAL_WIDTHS[w].ns) return BP_OK;
+        names += std::string(w == 0 ? "" : w == EVAL_WIDTH_N - 1 ? " or " : ", ") + EVAL_WIDTHS[w].name;
+    }
+    return fail(BP_ERR_ARG, std::string(who) + ": n_scores must be " + names);
 }
 
 int eval_cb_rate(const char *who, int fs, int n_scores)
@@ -907,13 +934,12 @@ int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const i
     ep.skip = ep.win / 4;
     { const int r = eval_cb_rate(who, fs, n_scores); if (r != BP_OK) return r; }
     ep.cH = 0; ep.cb_band.clear(); ep.cb_g.clear();
-    if (n_scores >= BP_SCORE_ALL_N) {                                // n_fft = 2^ceil(log2(2 win)), H = n_fft / 2: the least power of two >= win
+    if (ep.has(EVAL_ALL)) {                                          // n_fft = 2^ceil(log2(2 win)), H = n_fft / 2: the least power of two >= win
         for (ep.cH = 1; ep.cH < ep.win; ep.cH <<= 1) {}
         cb_table(fs, ep.cH, ep.cb_band, ep.cb_g);
     }
     ep.off.assign(off, off + n); ep.len.assign(len, len + n);
-    for (std::vector<int> *v : {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS})
-        v->assign((size_t)n + 1, 0);
+    for (std::vector<int> &v : ep.pre) v.assign((size_t)n + 1, 0);
     const int64_t LIM = INT32_MAX / 8;
     for (int s = 0; s < n; ++s) {
         const int64_t L = len[s], n10 = (L * ep.p + ep.q - 1) / ep.q;
@@ -922,13 +948,17 @@ int eval_plan(const char *who, int fs, int fea_dim, int n_scores, int n, const i
         const int64_t pairs = J10 > EV_SEG ? (int64_t)EV_NB * (J10 - EV_SEG) : 0;
         const double jd = floor((double)L / ep.skip - (double)ep.win / ep.skip);
         const int64_t J = jd >= 1.0 ? (int64_t)jd : 0;
-        const int64_t nx[12] = {ep.o10[s] + n10, ep.rb[s] + (n10 + WAVE_THREADS - 1) / WAVE_THREADS, ep.P[s] + J10, ep.eb[s] + (J10 + 3) / 4,
-                                ep.Q[s] + qc, ep.qb[s] + qc / WAVE_THREADS, ep.CP[s] + pairs, ep.cb[s] + (pairs + WAVE_THREADS - 1) / WAVE_THREADS,
-                                ep.SJ[s] + J, ep.sb[s] + (J + 3) / 4, F[s + 1], F[s + 1] + s + 1};
-        std::vector<int> *v[12] = {&ep.o10, &ep.rb, &ep.P, &ep.eb, &ep.Q, &ep.qb, &ep.CP, &ep.cb, &ep.SJ, &ep.sb, &ep.F, &ep.FS};
-        for (int k = 0; k < 12; ++k) {
+        int64_t nx[PRE_N];                                          // entry s + 1 of every table
+        const auto at = [&ep, s](EvalPre k) { return ep.pre[k][s]; };
+        nx[PRE_o10] = at(PRE_o10) + n10; nx[PRE_rb] = at(PRE_rb) + (n10 + WAVE_THREADS - 1) / WAVE_THREADS;
+        nx[PRE_P] = at(PRE_P) + J10; nx[PRE_eb] = at(PRE_eb) + (J10 + 3) / 4;
+        nx[PRE_Q] = at(PRE_Q) + qc; nx[PRE_qb] = at(PRE_qb) + qc / WAVE_THREADS;
+        nx[PRE_CP] = at(PRE_CP) + pairs; nx[PRE_cb] = at(PRE_cb) + (pairs + WAVE_THREADS - 1) / WAVE_THREADS;
+        nx[PRE_SJ] = at(PRE_SJ) + J; nx[PRE_sb] = at(PRE_sb) + (J + 3) / 4;
+        nx[PRE_F] = F[s + 1]; nx[PRE_FS] = F[s + 1] + s + 1;
+        for (int k = 0; k < PRE_N; ++k) {
             if (nx[k] > LIM) return fail(BP_ERR_ARG, std::string(who) + ": too many samples in one call");
-            (*v[k])[s + 1] = (int)nx[k];
+            ep.pre[k][s + 1] = (int)nx[k];
         }
     }
     // resampler: h[j] = kaiser_{2Lh+1, 5}[j] sinc((j - Lh) / m), normalised to sum 1, times p (double, rounded once)
@@ -959,14 +989,14 @@ void eval_fill(const EvalPlan &ep, char *tab)
     memset(tab, 0, t.bytes);
     memcpy(tab + t.off, ep.off.data(), (size_t)ep.n * 8);
     memcpy(tab + t.len, ep.len.data(), (size_t)ep.n * 4);
-    for (int k = 0; k < 12; ++k) memcpy(tab + t.pre[k], pre_k(ep, k).data(), ((size_t)ep.n + 1) * 4);
+    for (int k = 0; k < PRE_N; ++k) memcpy(tab + t.pre[k], ep.pre[k].data(), ((size_t)ep.n + 1) * 4);
     memcpy(tab + t.h, ep.h.data(), ep.h.size() * 4);
     memcpy(tab + t.v, ep.v.data(), ep.v.size() * 4);
     const double pi2 = 6.283185307179586476925286766559;
     float2 *tw = (float2 *)(tab + t.tw);
     for (int k = 0; k <= EV_NFFT / 2; ++k) tw[k] = make_float2((float)cos(pi2 * k / EV_NFFT), (float)-sin(pi2 * k / EV_NFFT));
     memcpy(tab + t.w, ep.w.data(), ep.w.size() * 8);
-    if (ep.ns >= BP_SCORE_ALL_N) {
+    if (ep.has(EVAL_ALL)) {
         double *ctw = (double *)(tab + t.ctw);
         for (int k = 0; k <= ep.cH; ++k) { ctw[2 * k] = cos(pi2 * k / (2.0 * ep.cH)); ctw[2 * k + 1] = -sin(pi2 * k / (2.0 * ep.cH)); }
         memcpy(tab + t.cband, ep.cb_band.data(), ep.cb_band.size() * 4);
@@ -974,77 +1004,68 @@ void eval_fill(const EvalPlan &ep, char *tab)
     }
 }
 
-size_t eval_work_bytes(const EvalPlan &ep, int nsig) { return work_layout(ep, nsig).bytes; }
+size_t eval_work_bytes(const EvalPlan &ep, int nsig) { return work_walk(ep, nsig); }
 
 hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream_t st)
 {
     const TabLayout t = tab_layout(ep);
-    const WorkLayout w = work_layout(ep, nsig);
     EvalArgs a; memset(&a, 0, sizeof(a));
-    const int *pre[12];
-    for (int k = 0; k < 12; ++k) pre[k] = (const int *)(d.tab + t.pre[k]);
     a.off = (const int64_t *)(d.tab + t.off); a.len = (const int *)(d.tab + t.len);
-    a.o10 = pre[0]; a.rb = pre[1]; a.P = pre[2]; a.eb = pre[3]; a.Q = pre[4]; a.qb = pre[5]; a.CP = pre[6]; a.cb = pre[7];
-    a.SJ = pre[8]; a.sb = pre[9]; a.F = pre[10]; a.FS = pre[11];
+#define X(name) a.name = (const int *)(d.tab + t.pre[PRE_##name]);
+    EVAL_PRE(X)
+#undef X
     a.h = (const float *)(d.tab + t.h); a.v = (const float *)(d.tab + t.v); a.tw = (const float2 *)(d.tab + t.tw); a.w = (const double *)(d.tab + t.w);
     a.n = ep.n; a.p = ep.p; a.q = ep.q; a.Lh = ep.Lh; a.taps = ep.taps; a.win = ep.win; a.skip = ep.skip; a.D = ep.D;
     a.clip = 1.0 + pow(10.0, 15.0 / 20.0);
     for (int k = 0; k < nsig; ++k) { a.sig[k] = d.sig[k]; a.lps[k] = d.lps[k]; }
-    a.r10 = (float *)(d.work + w.r10); a.s10 = w.s10;
-    a.E = (double *)(d.work + w.E); a.frm = (int *)(d.work + w.frm); a.C = (int *)(d.work + w.C);
-    a.comp = (float *)(d.work + w.comp); a.scomp = w.scomp;
-    a.band = (float *)(d.work + w.band); a.sband = w.sband;
-    a.rho = (double *)(d.work + w.rho); a.srho = w.srho;
-    a.ssnr = (double *)(d.work + w.ssnr); a.sssnr = w.sssnr;
-    a.lsd = (double *)(d.work + w.lsd); a.slsd = w.slsd;
-    a.dm = (double *)(d.work + w.dm); a.sdm = w.sdm; a.sdr = (double *)(d.work + w.sdr); a.nsig = nsig;
-    a.llr = (double *)(d.work + w.llr); a.lcd = (double *)(d.work + w.lcd); a.lv = (int *)(d.work + w.lv); a.lsel = (int *)(d.work + w.lsel);
+    work_walk(ep, nsig, &a, d.work);
+    a.nsig = nsig;
     a.ctw = (const double2 *)(d.tab + t.ctw); a.cband = (const int *)(d.tab + t.cband); a.cg = (const double *)(d.tab + t.cg); a.cH = ep.cH;
-    a.fw = (double *)(d.work + w.fw); a.ws = (double *)(d.work + w.ws); a.fv = (int *)(d.work + w.fv); a.wv = (int *)(d.work + w.wv);
-    a.csel = (int *)(d.work + w.csel);
     a.scores = d.scores; a.ns = ep.ns;
-    const int n = ep.n, ne = nsig - 1;
-    const dim3 blk(WAVE_THREADS);
+    const int n = ep.n, ne = nsig - 1, SJ = ep.tot(PRE_SJ);
+    const dim3 blk(WAVE_THREADS), per_row((unsigned)n, (unsigned)ne);
+    const auto rank = [&](int nval, const double *v0, const double *v1, const int *valid, int *sel) {
+        a.rank = RankSel{{v0, v1}, nval, valid, sel};
+        hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((SJ + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, a);
+    };
     // (grids that can be empty -- no STOI or SSNR frame in the whole call -- are skipped)
-    hipLaunchKernelGGL(bp_eval_resample, dim3((unsigned)ep.rb[n], (unsigned)nsig), blk, 0, st, a);
-    if (ep.eb[n]) hipLaunchKernelGGL(bp_eval_energy, dim3((unsigned)ep.eb[n]), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_resample, dim3((unsigned)ep.tot(PRE_rb), (unsigned)nsig), blk, 0, st, a);
+    if (ep.tot(PRE_eb)) hipLaunchKernelGGL(bp_eval_energy, dim3((unsigned)ep.tot(PRE_eb)), blk, 0, st, a);
     hipLaunchKernelGGL(bp_eval_mask, dim3((unsigned)n), blk, 0, st, a);
-    hipLaunchKernelGGL(bp_eval_compact, dim3((unsigned)ep.qb[n], (unsigned)nsig), blk, 0, st, a);
-    if (ep.P[n])
-        hipLaunchKernelGGL(bp_eval_bands, dim3((unsigned)ep.P[n], (unsigned)nsig), blk,
+    hipLaunchKernelGGL(bp_eval_compact, dim3((unsigned)ep.tot(PRE_qb), (unsigned)nsig), blk, 0, st, a);
+    if (ep.tot(PRE_P))
+        hipLaunchKernelGGL(bp_eval_bands, dim3((unsigned)ep.tot(PRE_P), (unsigned)nsig), blk,
                            lds_bytes(1 << EV_LOG2M) + (size_t)(EV_BIN_HI - EV_BIN_LO) * 4, st, a);
-    if (ep.cb[n]) hipLaunchKernelGGL(bp_eval_corr, dim3((unsigned)ep.cb[n], (unsigned)ne), blk, 0, st, a);
-    if (ep.sb[n]) hipLaunchKernelGGL(bp_eval_ssnr, dim3((unsigned)ep.sb[n], (unsigned)ne), blk, 0, st, a);
-    hipLaunchKernelGGL(bp_eval_lsd, dim3((unsigned)((ep.F[n] + 3) / 4), (unsigned)ne), blk, 0, st, a);
-    if (ep.ns >= BP_SCORE_EXT_N) {
-        if (ep.CP[n]) hipLaunchKernelGGL(bp_eval_estoi, dim3((unsigned)(ep.CP[n] / EV_NB)), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(bp_eval_sisdr, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+    if (ep.tot(PRE_cb)) hipLaunchKernelGGL(bp_eval_corr, dim3((unsigned)ep.tot(PRE_cb), (unsigned)ne), blk, 0, st, a);
+    if (ep.tot(PRE_sb)) hipLaunchKernelGGL(bp_eval_ssnr, dim3((unsigned)ep.tot(PRE_sb), (unsigned)ne), blk, 0, st, a);
+    hipLaunchKernelGGL(bp_eval_lsd, dim3((unsigned)((ep.tot(PRE_F) + 3) / 4), (unsigned)ne), blk, 0, st, a);
+    if (ep.has(EVAL_EXT)) {
+        if (ep.tot(PRE_CP)) hipLaunchKernelGGL(bp_eval_estoi, dim3((unsigned)(ep.tot(PRE_CP) / EV_NB)), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(bp_eval_sisdr, per_row, blk, 0, st, a);
     }
-    hipLaunchKernelGGL(bp_eval_reduce, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
-    if (ep.ns >= BP_SCORE_FULL_N) {                                 // LLR and CD: order 10 below 10 kHz, else 16
-        if (ep.SJ[n]) {
+    hipLaunchKernelGGL(bp_eval_reduce, per_row, blk, 0, st, a);
+    if (ep.has(EVAL_FULL)) {                                        // LLR and CD: order 10 below 10 kHz, else 16
+        if (SJ) {
             const int P = ep.fs < 10000 ? 10 : 16;
             const size_t lds = (lpc_slab_doubles(ep.win) + (size_t)(nsig * (P + 1) + P + 1) * EV_FB) * 8;
-            const dim3 fb((unsigned)((ep.SJ[n] + EV_FB - 1) / EV_FB));
+            const dim3 fb((unsigned)((SJ + EV_FB - 1) / EV_FB));
             if (P == 10) hipLaunchKernelGGL(bp_eval_lpc<10>, fb, blk, lds, st, a);
             else hipLaunchKernelGGL(bp_eval_lpc<16>, fb, blk, lds, st, a);
-            hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((ep.SJ[n] + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, a);
+            rank(2, a.llr, a.lcd, a.lv, a.lsel);
         }
-        hipLaunchKernelGGL(bp_eval_lpcsum, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+        hipLaunchKernelGGL(bp_eval_lpcsum, per_row, blk, 0, st, a);
     }
-    if (ep.ns >= BP_SCORE_ALL_N) {                                  // fwSegSNR and WSS
-        if (ep.SJ[n]) {
+    if (ep.has(EVAL_ALL)) {                                         // fwSegSNR and WSS
+        if (SJ) {
             const size_t lds = cb_lds_bytes(ep.cH, nsig);
             if (lds > 65536) {
                 const hipError_t e = hipFuncSetAttribute((const void *)bp_eval_cb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL(bp_eval_cb, dim3((unsigned)((ep.SJ[n] + EV_CF - 1) / EV_CF)), blk, lds, st, a);
-            EvalArgs b = a;                                         // the rank-and-select of LLR / CD on the WSS values (both bits)
-            b.llr = a.ws; b.lcd = a.ws; b.lv = a.wv; b.lsel = a.csel;
-            hipLaunchKernelGGL(bp_eval_lpcrank, dim3((unsigned)((ep.SJ[n] + WAVE_THREADS - 1) / WAVE_THREADS), (unsigned)ne), blk, 0, st, b);
+            hipLaunchKernelGGL(bp_eval_cb, dim3((unsigned)((SJ + EV_CF - 1) / EV_CF)), blk, lds, st, a);
+            rank(1, a.ws, nullptr, a.wv, a.csel);
         }
-        hipLaunchKernelGGL(bp_eval_cbsum, dim3((unsigned)n, (unsigned)ne), blk, 0, st, a);
+        hipLaunchKernelGGL(bp_eval_cbsum, per_row, blk, 0, st, a);
     }
     return hipGetLastError();
 }
@@ -1052,8 +1073,8 @@ hipError_t eval_launch(const EvalPlan &ep, const EvalDev &d, int nsig, hipStream
 hipError_t eval_trim_launch(const EvalPlan &ep, const char *tab, int hop, float *pcm, hipStream_t st)
 {
     const TabLayout t = tab_layout(ep);
-    hipLaunchKernelGGL(bp_eval_trim, dim3((unsigned)ep.FS[ep.n]), dim3(WAVE_THREADS), 0, st, (const int64_t *)(tab + t.off),
-                       (const int *)(tab + t.len), (const int *)(tab + t.pre[11]), ep.n, hop, pcm);
+    hipLaunchKernelGGL(bp_eval_trim, dim3((unsigned)ep.tot(PRE_FS)), dim3(WAVE_THREADS), 0, st, (const int64_t *)(tab + t.off),
+                       (const int *)(tab + t.len), (const int *)(tab + t.pre[PRE_FS]), ep.n, hop, pcm);
     return hipGetLastError();
 }
 
@@ -1094,7 +1115,7 @@ static int score_waves_run(const char *who, int device, int fea_dim, int sample_
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
         WaveAnaArgs a; memset(&a, 0, sizeof(a));
         a.pcm = (const float *)(d + (k ? o_est : o_ref)); a.win = (const float *)(d + o_win); a.tw = (const float2 *)(d + o_tw);
-        a.F = (const int *)(d + tab_layout(ep).pre[10]);
+        a.F = (const int *)(d + tab_layout(ep).pre[PRE_F]);
         a.n_sent = n_sent; a.log2M = wp.log2M; a.D = D; a.hop = wp.hop; a.ctx = 1;
         a.lps = (float *)(d + (k ? o_lps1 : o_lps));
         e = wave_analysis_launch(a, (int)f, os.st);

@@ -1,7 +1,6 @@
 // bpeval.cpp -- objective scores of enhanced speech on the MI355X: segmental SNR, log-spectral distortion and
 // STOI, through bp_eval_mix (a test set mixed on the GPU and enhanced with a trained net) or bp_score_waves (pairs of WAVs); with
-// scores=extended ESTOI and SI-SDR beside them, with scores=full LLR and cepstral distance as well, with scores=all fwSegSNR and
-// WSS behind those, through the _ext calls.
+// scores=extended|full|all the further columns of COLUMNS behind them, through the _ext calls.
 //
 //   bpeval clean_list=test_clean.list noise_list=test_noise.list norm_file=x.norm initwts_file=mlp.N.wts fea_dim=129 fea_context=11
 //          targ_offset=5 layersizes=1548,2048,2048,2048,129 [snr_list=-5,0,5,10,15,20] [mix_per_clean=1] [init_randem_seed=0]
@@ -26,15 +25,10 @@
 // the net's figures (noisy -> logmmse), and three more columns `ssnr_lm lsd_lm stoi_lm` at the end of every scores_out line.
 // lm_noise=spp (only with baseline=logmmse; default vad: the output above, byte for byte) gives the baseline the MMSE-SPP noise tracker
 // (bp_eval_mix_logmmse_nt).
-// scores=extended (default basic: the output above, byte for byte): every stdout line gains `, ESTOI a -> b, SI-SDR a -> b dB` before
-// the undefined count, which then counts the NaN of all five columns; scores_out lines gain `estoi_noisy estoi_enh sisdr_noisy
-// sisdr_enh` behind stoi_enh, the baseline's `estoi_lm sisdr_lm` behind its three, and pairs mode `estoi sisdr` behind stoi.
-// scores=full: the extended output, and behind each of its additions the same for LLR and cepstral distance: `, LLR a -> b, CD a -> b
-// dB` on stdout (the count then over all seven columns), `llr_noisy llr_enh cd_noisy cd_enh` behind sisdr_enh, `llr_lm cd_lm` behind
-// sisdr_lm, `llr cd` behind sisdr in pairs mode.
-// scores=all: the full output, and behind each of its additions the same for fwSegSNR and WSS: `, fwSegSNR a -> b dB, WSS a -> b` on
-// stdout (the count then over all nine columns), `fwssnr_noisy fwssnr_enh wss_noisy wss_enh` behind cd_enh, `fwssnr_lm wss_lm`
-// behind cd_lm, `fwssnr wss` behind cd in pairs mode.  The rate must be 8 kHz or more.
+// scores=extended|full|all (default basic: the output above, byte for byte): the columns of COLUMNS below that the value has, in its
+// order.  Every stdout line gains `, NAME a -> b` with the column's unit per added column before the undefined count, which then
+// counts the NaN of all columns; scores_out lines gain `x_noisy x_enh` per added column behind stoi_enh, the baseline's `x_lm` each
+// behind its three, and pairs mode `x` each behind stoi.  scores=all: the rate must be 8 kHz or more.
 // rir_list: one room impulse response per WAV, at the rate of the others; clean sentence c is paired with response
 // bp_mix_reverb_pairs(init_randem_seed, ...)[c], the plan addresses the derived entry n_clean + c in place of c (so scores_out
 // lists it), the mixtures are reverberant and the scores are taken against reverb_target: the reverberant sentence or its direct
@@ -155,7 +149,21 @@ void check_rate(int fs)
 // mean over the finite values; NaN count.  Slot k < BP_SCORE_ALL_N: column k of the noisy side, BP_SCORE_ALL_N + k: of the enhanced
 // side; ns: the columns the rows have
 struct Acc { double sum[BP_SCORE_ALL_N * 2] = {0}; int cnt[BP_SCORE_ALL_N * 2] = {0}, n = 0, nan = 0; };
-int n_columns(int ext) { return ext == 3 ? (int)BP_SCORE_ALL_N : ext == 2 ? (int)BP_SCORE_FULL_N : ext ? (int)BP_SCORE_EXT_N : (int)BP_SCORE_N; }
+// The score columns in row order (BP_SCORE_*): name and unit on stdout, digits there, and the narrowest scores= value
+// (0 .. 3: basic, extended, full, all) whose rows have the column
+const struct { const char *name, *unit; int digits, ext; } COLUMNS[BP_SCORE_ALL_N] = {
+    {"SSNR", " dB", 3, 0}, {"LSD", " dB", 3, 0}, {"STOI", "", 4, 0}, {"ESTOI", "", 4, 1}, {"SI-SDR", " dB", 3, 1},
+    {"LLR", "", 4, 2}, {"CD", " dB", 3, 2}, {"fwSegSNR", " dB", 3, 3}, {"WSS", "", 3, 3},
+};
+int n_columns(int ext) { int ns = 0; while (ns < BP_SCORE_ALL_N && COLUMNS[ns].ext <= ext) ++ns; return ns; }
+// the scores of one scores_out line: per column ` a` or, with b, ` a b`
+void put_scores(FILE *fo, int ns, const float *a, const float *b = nullptr)
+{
+    for (int k = 0; k < ns; ++k) {
+        fprintf(fo, " %.9g", a[k]);
+        if (b) fprintf(fo, " %.9g", b[k]);
+    }
+}
 void add(Acc &a, int ns, const float *noisy, const float *enh)
 {
     ++a.n;
@@ -167,7 +175,17 @@ void add(Acc &a, int ns, const float *noisy, const float *enh)
         }
 }
 double avg(const Acc &a, int k) { return a.cnt[k] ? a.sum[k] / a.cnt[k] : NAN; }
-double avg_enh(const Acc &a, int k) { return avg(a, BP_SCORE_ALL_N + k); }
+// the means of one stdout line: per column `, <who>NAME a` or, with both sides, `, <who>NAME a -> b`, then the unit (who: before
+// the first column alone)
+void put_means(int ns, const Acc &a, bool both, const char *who = "")
+{
+    for (int k = 0; k < ns; ++k) {
+        const int d = COLUMNS[k].digits;
+        printf(", %s%s %.*f", k ? "" : who, COLUMNS[k].name, d, avg(a, k));
+        if (both) printf(" -> %.*f", d, avg(a, BP_SCORE_ALL_N + k));
+        printf("%s", COLUMNS[k].unit);
+    }
+}
 
 int pairs_mode(const Params &P)
 {
@@ -210,17 +228,14 @@ int pairs_mode(const Params &P)
     for (size_t i = 0; i < lens.size(); ++i) {
         const float *s = &sc[i * ns];
         add(a, ns, s, s);
-        if (fo) fprintf(fo, "%s %s %.9g %.9g %.9g", refs[i].c_str(), ests[i].c_str(), s[0], s[1], s[2]);
-        if (fo && P.ext) fprintf(fo, " %.9g %.9g", s[BP_SCORE_ESTOI], s[BP_SCORE_SISDR]);
-        if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g", s[BP_SCORE_LLR], s[BP_SCORE_CD]);
-        if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g", s[BP_SCORE_FWSSNR], s[BP_SCORE_WSS]);
-        if (fo) fprintf(fo, "\n");
+        if (!fo) continue;
+        fprintf(fo, "%s %s", refs[i].c_str(), ests[i].c_str());
+        put_scores(fo, ns, s);
+        fprintf(fo, "\n");
     }
     if (fo) fclose(fo);
-    printf("pairs: %d pairs, SSNR %.3f dB, LSD %.3f dB, STOI %.4f", a.n, avg(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg(a, BP_SCORE_STOI));
-    if (P.ext) printf(", ESTOI %.4f, SI-SDR %.3f dB", avg(a, BP_SCORE_ESTOI), avg(a, BP_SCORE_SISDR));
-    if (P.ext >= 2) printf(", LLR %.4f, CD %.3f dB", avg(a, BP_SCORE_LLR), avg(a, BP_SCORE_CD));
-    if (P.ext == 3) printf(", fwSegSNR %.3f dB, WSS %.3f", avg(a, BP_SCORE_FWSSNR), avg(a, BP_SCORE_WSS));
+    printf("pairs: %d pairs", a.n);
+    put_means(ns, a, false);
     printf(" (%d undefined)\n", a.nan / 2);
     return 1;
 }
@@ -344,37 +359,23 @@ int main(int argc, char **argv)
             const bp_mixture &m = plan[c.first + i];
             const float *a = &ns[(size_t)i * NS], *b = &es[(size_t)i * NS];
             add(by_snr[m.snr_db], NS, a, b); add(all, NS, a, b);
-            if (fo)
-                fprintf(fo, "%d %d %lld %.9g %.9g %.9g %.9g %.9g %.9g %.9g", m.clean, m.noise, (long long)m.offset, m.snr_db,
-                        a[BP_SCORE_SSNR], b[BP_SCORE_SSNR], a[BP_SCORE_LSD], b[BP_SCORE_LSD], a[BP_SCORE_STOI], b[BP_SCORE_STOI]);
-            if (fo && P.ext) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_ESTOI], b[BP_SCORE_ESTOI], a[BP_SCORE_SISDR], b[BP_SCORE_SISDR]);
-            if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_LLR], b[BP_SCORE_LLR], a[BP_SCORE_CD], b[BP_SCORE_CD]);
-            if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g %.9g %.9g", a[BP_SCORE_FWSSNR], b[BP_SCORE_FWSSNR], a[BP_SCORE_WSS], b[BP_SCORE_WSS]);
+            if (fo) {
+                fprintf(fo, "%d %d %lld %.9g", m.clean, m.noise, (long long)m.offset, m.snr_db);
+                put_scores(fo, NS, a, b);
+            }
             if (P.baseline) {
                 const float *l = &ls[(size_t)i * NS];
                 add(by_snr_lm[m.snr_db], NS, a, l); add(all_lm, NS, a, l);
-                if (fo) fprintf(fo, " %.9g %.9g %.9g", l[BP_SCORE_SSNR], l[BP_SCORE_LSD], l[BP_SCORE_STOI]);
-                if (fo && P.ext) fprintf(fo, " %.9g %.9g", l[BP_SCORE_ESTOI], l[BP_SCORE_SISDR]);
-                if (fo && P.ext >= 2) fprintf(fo, " %.9g %.9g", l[BP_SCORE_LLR], l[BP_SCORE_CD]);
-                if (fo && P.ext == 3) fprintf(fo, " %.9g %.9g", l[BP_SCORE_FWSSNR], l[BP_SCORE_WSS]);
+                if (fo) put_scores(fo, NS, l);
             }
             if (fo) fprintf(fo, "\n");
         }
     }
     bp_destroy(h);
     if (fo) fclose(fo);
-    const auto line = [&P](const char *head, const char *who, const Acc &a) {       // who: "" or "logmmse: "
-        printf("%s: %d mixtures, %sSSNR %.3f -> %.3f dB, LSD %.3f -> %.3f dB, STOI %.4f -> %.4f", head, a.n, who,
-               avg(a, BP_SCORE_SSNR), avg_enh(a, BP_SCORE_SSNR), avg(a, BP_SCORE_LSD), avg_enh(a, BP_SCORE_LSD),
-               avg(a, BP_SCORE_STOI), avg_enh(a, BP_SCORE_STOI));
-        if (P.ext)
-            printf(", ESTOI %.4f -> %.4f, SI-SDR %.3f -> %.3f dB", avg(a, BP_SCORE_ESTOI), avg_enh(a, BP_SCORE_ESTOI),
-                   avg(a, BP_SCORE_SISDR), avg_enh(a, BP_SCORE_SISDR));
-        if (P.ext >= 2)
-            printf(", LLR %.4f -> %.4f, CD %.3f -> %.3f dB", avg(a, BP_SCORE_LLR), avg_enh(a, BP_SCORE_LLR), avg(a, BP_SCORE_CD), avg_enh(a, BP_SCORE_CD));
-        if (P.ext == 3)
-            printf(", fwSegSNR %.3f -> %.3f dB, WSS %.3f -> %.3f", avg(a, BP_SCORE_FWSSNR), avg_enh(a, BP_SCORE_FWSSNR), avg(a, BP_SCORE_WSS),
-                   avg_enh(a, BP_SCORE_WSS));
+    const auto line = [NS](const char *head, const char *who, const Acc &a) {       // who: "" or "logmmse: "
+        printf("%s: %d mixtures", head, a.n);
+        put_means(NS, a, true, who);
         printf(" (%d undefined)\n", a.nan);
     };
     for (const auto &kv : by_snr) {

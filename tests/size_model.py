@@ -30,7 +30,7 @@ the table as it stood before the noise-aware mode and the two new sized kinds: a
 whatever the site, and the asks for 0 bytes that a call site spells out (ZERO: bp_gv_mix on ev_syn, ev_ola and lps, the net-scored
 calls on ev_gain -- such a kind does not size the buffer and leaves its block as it was) all belong to kinds or rows outside it.  The
 one place where the view is no restriction has a name: LEGACY_UNMODELLED.
-ev_tab, ev_work and ev_pin stay in UNMODELLED: tab_layout / work_layout of csrc/bp_eval.hip lay out some thirty tables per plan
+ev_tab, ev_work and ev_pin stay in UNMODELLED: tab_layout / work_walk of csrc/bp_eval.hip lay out some thirty tables per plan
 (resampled lengths, STOI frames and segments, the LPC frame blocks of width 7), which is not short.  The claim made in their place
 needs no byte count (width_pairs): in every configuration a scoring call of each width 3 / 5 / 7 at Z or ONE runs directly behind a
 dyed L or FULL scoring call of each other width.
