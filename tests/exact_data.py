@@ -28,7 +28,8 @@ checked from the reference alone:
 A shard problem (SHARD_CASES) is the same at a global bunch Bg = 2B and a rank_frame_offset: t = o_ref - d Bg/2, and the masks are
 those of the global frames from the offset on.
 
-What it cannot cover: a second step (the updated weights are no longer few-bit numbers), Sigmoid nets, logistic forward columns."""
+What it cannot cover: a second step (the updated weights are no longer few-bit numbers), Sigmoid nets, logistic forward columns.
+Nor any bf16 store that rounds: tests/bf16_iso.py is the partner for that, each kernel alone on generic operands at half-ulp bars."""
 import numpy as np
 
 import dispatch_cases as DC
